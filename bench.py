@@ -12,15 +12,22 @@ compression of the next batch).
 One "step" = one pass of the hot path (LZ77 match -> Huffman/pack [-> gather]) over the whole
 batch, input already resident in HBM.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
 `--gpus N` with N > 1 and no WORLD_SIZE in the environment starts the N ranks itself (fresh
 child processes, one GPU each, started before this process touches the GPU).
 
-At N = 1 the default run appends, outside the timed region of the headline, the other two
-single-GPU configurations of BASELINE.json under "extra": configs[2] (1 GiB of 256 KiB streams)
-and configs[4] (inflate-only, 8 GiB of output).
+A plain run does only what the headline needs: set-up, warm-up, the timed steps and the result
+line.  `--full` adds everything else, outside the timed region: the CPU baseline and the parity
+check against the oracle, at N = 1 the other two single-GPU configurations of BASELINE.json under
+"extra" (configs[2], 1 GiB of 256 KiB streams, and configs[4], inflate-only, 8 GiB of output), at
+N > 1 the check of the gathered buffer and the exchange timed alone and through the C ABI, and in
+--mode inflate the round-trip check of every output byte.
+
+`--dump-outputs DIR` writes what the last timed step computed (rank 0's outputs) as DIR/<name>.npy:
+offsets / lengths / statuses in float64 and the bytes of a fixed, seeded sample of streams in
+float32 (at most DUMP_BYTES of them), so that two builds can be compared output for output.
 """
 import argparse
 import importlib
@@ -162,6 +169,34 @@ def summarize(times_s):
 
 
 # ----------------------------------------------------------------------------------------------
+# --dump-outputs
+# ----------------------------------------------------------------------------------------------
+DUMP_BYTES = 12 << 20  # bytes of sampled streams per dump: 48 MiB as float32, the rest of the 64 MB is offsets
+
+
+def dump_sample(n, stream_cap):
+    """A fixed, seeded choice of stream indices (sorted) whose bytes fit DUMP_BYTES at stream_cap bytes each."""
+    import numpy as np
+    k = max(1, min(n, DUMP_BYTES // max(int(stream_cap), 1)))
+    return np.sort(np.random.default_rng(0).choice(n, k, replace=False))
+
+
+def dump_outputs(out_dir, buf, lo, hi, idx, arrays):
+    """Write arrays (name -> integer array, as float64) and the bytes buf[lo[j]:hi[j]] of the sampled streams idx,
+    concatenated, as float32 -- DIR/<name>.npy."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    parts = [buf[int(a):int(b)] for a, b in zip(lo, hi)]
+    sample = torch.cat(parts).cpu().numpy() if parts else np.zeros(0, np.uint8)
+    out = {"sample_streams": np.asarray(idx), "sample_bytes": sample}
+    out.update(arrays)
+    for name, a in out.items():
+        a = np.asarray(a)
+        np.save(os.path.join(out_dir, name + ".npy"), a.astype(np.float32 if name == "sample_bytes" else np.float64))
+
+
+# ----------------------------------------------------------------------------------------------
 # CPU baseline (the oracle on the host cores) -- also the parity checker
 # ----------------------------------------------------------------------------------------------
 def cpu_leg(host, in_off, n, blen, sample_streams, g_out=None, g_off=None):
@@ -258,6 +293,13 @@ def main():
                     help="inflate = BASELINE.json configs[4]: decode the compressed streams (stream index supplied)")
     ap.add_argument("--option", action="append", default=[], metavar="NAME=VALUE",
                     help="flate_hip_set_option knob (developer A/B runs), may repeat")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: CPU baseline and parity check, the \"extra\" configurations (N=1), the "
+                         "gathered-buffer check and the exchange timed alone and through the C ABI (N>1), the "
+                         "round-trip check (--mode inflate).  The --no-* / --verify / --cpu-sample-streams options "
+                         "shape this part")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32 / float64)")
     args = ap.parse_args()
     if args.streams is None:
         args.streams = 131072 if args.mode == "inflate" else 16384
@@ -319,7 +361,7 @@ def main():
         res = bench_inflate(args, env, d_in, in_off, n, blen, host=host)
     else:
         res = bench_deflate(args, env, host, d_in, in_off, n, blen)
-        if rank == 0 and world == 1 and not args.no_extra and not args.spliced and cuda:
+        if args.full and rank == 0 and world == 1 and not args.no_extra and not args.spliced and cuda:
             del d_in, host
             torch.cuda.empty_cache()
             res["extra"] = extra_legs(args, env)
@@ -429,7 +471,7 @@ def bench_deflate(args, env, host, d_in, in_off, n, blen):
         nstep[0] += 1
         finish(i)
         if args.spliced:  # one DEFLATE stream per GPU; the gather then moves one "stream" per rank
-            _, nbytes, _ = eng.deflate_spliced(d_in, in_off, out=outs[i])
+            _, nbytes, last["bit_off"] = eng.deflate_spliced(d_in, in_off, out=outs[i])
             out_off = np.array([0, nbytes], dtype=np.uint64)
         else:
             _, out_off = eng.deflate_batch(d_in, in_off, out=outs[i])
@@ -471,6 +513,16 @@ def bench_deflate(args, env, host, d_in, in_off, n, blen):
         if b:
             split = {"lds_table_blocks": a, "l2_table_guest_blocks": b - a, "queued": b}
 
+    # what the last timed step wrote, before anything below may write these buffers again
+    if args.dump_outputs and rank == 0:
+        idx = dump_sample(n, flate.deflate_bound(blen))
+        if args.spliced:  # the ONE stream and its index: stream i's blocks span bits bit_off[i] .. bit_off[i + 1]
+            b_off = last["bit_off"]
+            dump_outputs(args.dump_outputs, outs[last_i], b_off[idx] // 8, (b_off[idx + 1] + 7) // 8, idx,
+                         {"bit_offsets": b_off, "nbytes": np.array([clen])})
+        else:
+            dump_outputs(args.dump_outputs, outs[last_i], out_off[idx], out_off[idx + 1], idx, {"offsets": out_off})
+
     # Parity of the exchange step FIRST, on the buffer the timed region's last overlapped
     # (wait=False) gather produced -- before anything else may write a gather buffer -- and then on
     # two more overlapped steps (both output buffers, both orders of reuse), each checked right after
@@ -488,7 +540,7 @@ def bench_deflate(args, env, host, d_in, in_off, n, blen):
                 cnt += 1
         return cnt
 
-    check = gather and args.verify and not args.spliced and not args.no_cpu_baseline
+    check = args.full and gather and args.verify and not args.spliced and not args.no_cpu_baseline
     if check:
         if rank == 0:
             gathered_verified += check_gathered(last["gathered"], 64)
@@ -508,9 +560,11 @@ def bench_deflate(args, env, host, d_in, in_off, n, blen):
         g = last["gathered"]
         recv = int(g.sizes.sum() - g.sizes[rank])
         gather_info.update({"bytes_received_per_gpu": recv, "padded_bytes_per_rank": int(g.pad)})
-        # (the timed region above is what `value` reports; a failure of this side measurement is
+        # (--full; the timed region above is what `value` reports; a failure of this side measurement is
         # recorded, it must not cost the run its line)
         modes = (args.gather_mode,) + tuple(m for m in ("allgather", "sendrecv") if m != args.gather_mode)
+        if not args.full:
+            modes = ()
         side_buf = None
         for mode in modes:
             try:
@@ -531,9 +585,9 @@ def bench_deflate(args, env, host, d_in, in_off, n, blen):
         # with the tests' rehearsal transport in place of RCCL -- take the same path)
         native_ok = (env["cuda"] and (dist.get_backend() == "nccl" or os.environ.get("FLATE_BENCH_FORCE_NATIVE") == "1")) \
             or hasattr(eng, "native_comm")
-        if not args.no_native_gather and native_ok:
-            # the same exchange through include/flate_hip.h (what a MoonBit / C++ host calls): ON by default, so
-            # that the first run on a multi-GPU node exercises flate_hip_gather_* over real RCCL / xGMI.
+        if args.full and not args.no_native_gather and native_ok:
+            # the same exchange through include/flate_hip.h (what a MoonBit / C++ host calls): ON in every --full run,
+            # so that the first such run on a multi-GPU node exercises flate_hip_gather_* over real RCCL / xGMI.
             # It is a side measurement that has never run on more than one real GPU: it may fail, it must never
             # cost the run its line, and it must never HANG it -- (1) every rank first probes, without a
             # collective, that it can bind RCCL, and the ranks agree on that before anyone enters the collective
@@ -592,13 +646,13 @@ def bench_deflate(args, env, host, d_in, in_off, n, blen):
                 "achieved_GBs": round(recv / (best * 1e-3) / 1e9, 2), "xgmi_peak_GBs": XGMI_PEAK_GBS,
                 "frac_of_xgmi": round(recv / (best * 1e-3) / 1e9 / XGMI_PEAK_GBS, 4)})
 
-    # cpu_baseline leg (rank 0, outside the timed region), the SAME at every N so that the 1-, 2-,
+    # cpu_baseline leg (--full, rank 0, outside the timed region), the SAME at every N so that the 1-, 2-,
     # 4- and 8-GPU lines read side by side: the oracle compresses rank 0's own shard (the first
     # --cpu-sample-streams streams of its 1 GiB) on the host cores (16 threads, and 1 thread on a
     # smaller sample); every stream it produced is compared with what this GPU wrote.
     verified = 0
     cpu_baseline = None
-    if rank == 0 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and not args.no_cpu_baseline:
         g_cpu = outs[last_i][:clen].cpu().numpy() if (args.verify and not args.spliced) else None
         cpu_baseline, verified = cpu_leg(host, in_off, n, blen, args.cpu_sample_streams, g_cpu, out_off)
         if args.spliced and args.verify and world == 1:
@@ -672,16 +726,21 @@ def bench_inflate(args, env, d_in, in_off, n, blen, host=None, steps=None, warmu
     t0 = time.perf_counter()
     for _ in range(steps):
         ts = time.perf_counter()
-        _, _, olen, status, _ = run()
+        _, o_off, olen, status, _ = run()
         step_s.append(time.perf_counter() - ts)
         ms += eng.last_timing()["inflate"]
     sync_all(env)
     dt = max_over_ranks(env, time.perf_counter() - t0)
-    ok = bool((status == 0).all()) and bool(torch.equal(out, d_in))  # round-trip property, full size
-    if not ok:
-        raise SystemExit("INFLATE ROUND-TRIP FAILURE: output != input")
+    if args.dump_outputs and rank == 0:
+        idx = dump_sample(n, blen)
+        dump_outputs(args.dump_outputs, out, o_off[idx], o_off[idx] + olen[idx], idx,
+                     {"out_lengths": olen, "status": status})
+    if args.full:
+        ok = bool((status == 0).all()) and bool(torch.equal(out, d_in))  # round-trip property, full size
+        if not ok:
+            raise SystemExit("INFLATE ROUND-TRIP FAILURE: output != input")
     cpu_baseline = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not args.spliced:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and not args.spliced:
         from oracle import pyoracle
         ns = min(args.cpu_sample_streams * 2, n)  # the decoder is faster than the encoder
         info = cpu_info()
@@ -744,8 +803,9 @@ def bench_inflate(args, env, d_in, in_off, n, blen, host=None, steps=None, warmu
         "steps": steps, "warmup": warmup, "ms_per_step": round(dt / steps * 1e3, 3),
         "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u8",
         "data": "synthetic",
-        "config": {"workload": "inflate %s%d x %d B streams per GPU, S-%s, output == input checked on every byte"
-                               % ("ONE spliced stream of " if args.spliced else "", n, blen, args.kind),
+        "config": {"workload": "inflate %s%d x %d B streams per GPU, S-%s, %s"
+                               % ("ONE spliced stream of " if args.spliced else "", n, blen, args.kind,
+                                  "output == input checked on every byte" if args.full else "output not checked in this run"),
                    "compressed_bytes_per_gpu": clen,
                    "stage_ms": {"inflate": round(k_ms, 3)}, "step_ms": summarize(step_s)},
         # (the library's choice at its default options: the sub-block decoder below 45056 streams)
@@ -903,7 +963,7 @@ def extra_legs(args, env):
     del host
     in_off = flate.uniform_offsets(n, blen)
     ia = argparse.Namespace(**vars(args))
-    ia.spliced, ia.no_cpu_baseline, ia.kind = False, True, "text"
+    ia.spliced, ia.no_cpu_baseline, ia.kind, ia.dump_outputs = False, True, "text", None
     ia.inflate_host_leg = True
     r = bench_inflate(ia, env, d_in, in_off, n, blen, steps=3, warmup=1)
     extra["config5_inflate_8GiB"] = {k: r[k] for k in ("metric", "value", "unit", "steps", "ms_per_step",

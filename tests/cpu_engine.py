@@ -44,7 +44,7 @@ class OracleEngine:
 
     def native_comm(self, rank, world, dist):
         """Stand-in for shard.NativeComm (the C-ABI exchange needs a GPU): the same interface over
-        torch.distributed, so that bench.py's DEFAULT N > 1 path -- exchange through the C ABI after the timed
+        torch.distributed, so that bench.py's --full N > 1 path -- exchange through the C ABI after the timed
         region, compared with the torch.distributed result -- is rehearsed on CPU."""
         return _RehearsalComm(rank, world, dist)
 

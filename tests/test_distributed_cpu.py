@@ -109,7 +109,7 @@ def test_bench_spawns_its_own_ranks_and_verifies_the_gathered_buffer():
         env.pop(k, None)
     env["FLATE_BENCH_TEST_ENGINE"] = "tests.cpu_engine:OracleEngine"
     env["PYTHONPATH"] = ROOT + os.pathsep + env.get("PYTHONPATH", "")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "2",
                         "--warmup", "1", "--streams", "128", "--stream-len", "4096"],
                        env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -119,7 +119,7 @@ def test_bench_spawns_its_own_ranks_and_verifies_the_gathered_buffer():
     g = line["config"]["gather"]
     assert g["allgather_ms"]["min"] > 0 and g["sendrecv_ms"]["min"] > 0 and g["bytes_received_per_gpu"] > 0
     assert line["cpu_baseline"]["value"] > 0 and "TEST-ENGINE" in line["data"]
-    # the exchange through the C ABI is part of the DEFAULT N > 1 run (here: the test engine's stand-in for it):
+    # the exchange through the C ABI is part of every --full N > 1 run (here: the test engine's stand-in for it):
     # both forms timed, priced against xGMI, compared with the torch.distributed result
     c = g["c_abi"]
     assert c["allgather_ms"]["mean"] > 0 and c["sendrecv_ms"]["mean"] > 0 and c["compared_streams"] >= 64
@@ -134,7 +134,7 @@ def test_bench_without_the_c_abi_exchange_when_asked():
         env.pop(k, None)
     env["FLATE_BENCH_TEST_ENGINE"] = "tests.cpu_engine:OracleEngine"
     env["PYTHONPATH"] = ROOT + os.pathsep + env.get("PYTHONPATH", "")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "1", "--warmup", "0",
                         "--streams", "64", "--stream-len", "4096", "--no-native-gather"],
                        env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -151,7 +151,7 @@ def test_bench_rejects_a_world_size_that_contradicts_gpus():
 
 
 def test_bench_line_survives_a_c_abi_exchange_that_hangs():
-    """The default N > 1 run must never lose its line to the side measurement: with one rank stuck outside the
+    """A --full N > 1 run must never lose its line to the side measurement: with one rank stuck outside the
     collective (the other then waits inside it for ever) every rank gives up at the time limit, rank 0's line is
     out -- with the failure recorded -- and every process ends."""
     import json
@@ -165,7 +165,7 @@ def test_bench_line_survives_a_c_abi_exchange_that_hangs():
     env["FLATE_TEST_STUCK_RANK"] = "1"
     env["FLATE_BENCH_NATIVE_LIMIT_S"] = "5"
     t0 = time.time()
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "1", "--warmup", "0",
                         "--streams", "64", "--stream-len", "4096"],
                        env=env, capture_output=True, text=True, timeout=240)
     assert r.returncode == 3, r.stderr[-2000:]  # (bench.kExitAbandoned: the hang shows in the exit code too)

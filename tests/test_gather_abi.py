@@ -186,7 +186,7 @@ def test_two_ranks_through_the_c_abi_exchange_on_one_card():
 
 @pytest.mark.gpu
 def test_bench_with_two_ranks_takes_the_c_abi_exchange_by_default_on_one_card():
-    """`bench.py --gpus 2` as the driver will run it on a multi-GPU node -- the exchange through the C ABI after the
+    """`bench.py --full --gpus 2` as the driver will run it on a multi-GPU node -- the exchange through the C ABI after the
     timed region, in its guarded helper thread -- rehearsed with two ranks on ONE card: gloo between the ranks,
     the library's test build with the rehearsal transport in place of RCCL (FLATE_BENCH_FORCE_NATIVE)."""
     import json
@@ -197,7 +197,7 @@ def test_bench_with_two_ranks_takes_the_c_abi_exchange_by_default_on_one_card():
                FLATE_REHEARSAL_SLOT_MB="64")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--gpus", "2", "--steps", "2", "--warmup", "1",
                           "--streams", "1536", "--cpu-sample-streams", "128"],
                          env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-3000:]

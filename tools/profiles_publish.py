@@ -1,9 +1,9 @@
-"""Copy the evidence of one tools/final_collect.sh call (gpurun_out/<tag>*) into profiles/<round>/ under
+"""Copy the evidence of one tools/final_collect.sh call ($FLATE_OUT_ROOT/<tag>, default results/<tag>) into profiles/<round>/ under
 the names bench.py and the READMEs refer to.   usage: tools/profiles_publish.py <tag> <round-dir> <prefix>"""
 import glob, json, os, shutil, sys
 
 tag, rnd, pre = sys.argv[1], sys.argv[2], sys.argv[3]
-src = os.path.join("gpurun_out", tag)
+src = os.path.join(os.environ.get("FLATE_OUT_ROOT", "results"), tag)
 dst = os.path.join("profiles", rnd)
 os.makedirs(dst, exist_ok=True)
 
