@@ -218,6 +218,27 @@ int flate_hip_inflate_batch(flate_hip_ctx *ctx, const uint8_t *in, const uint64_
                             uint64_t *out_len, int32_t *status, int64_t *err_off,
                             uint32_t flags);
 
+/* &Reader::new_dict(r, dict) (inflate.mbt:315-317) + read to EOF for n_streams independent streams: stream i
+ * decodes as if its output started with its PRESET DICTIONARY, which has already been read -- the last 32768
+ * bytes of it are the history (DictDecoder::new, dict-decoder.mbt:40-60), a distance may reach
+ * min(32768, dict_len + bytes produced) back (:63-69, inflate.mbt:677-680), beyond that FLATE_HIP_E_CORRUPT.
+ * Everything else -- in / in_off / out / out_off / out_len / status / err_off (counted from the stream's own
+ * input), FLATE_HIP_SIZE_ONLY, FLATE_HIP_DEVICE_PTRS, the options -- as flate_hip_inflate_batch.
+ *   dictionary j   = dicts[dict_off[j], dict_off[j+1]); dict_off: n_dicts + 1 entries, HOST array; dicts: host,
+ *                    or device under FLATE_HIP_DEVICE_PTRS (like in).  An empty dictionary = none.
+ *   dict_of[i]     = the dictionary of stream i, or FLATE_HIP_NO_DICT; HOST array of n_streams entries.
+ *                    NULL: every stream uses dictionary 0.
+ * FLATE_HIP_E_INVALID (before any HIP call): dict_off not monotone, a dict_of entry neither below n_dicts nor
+ * FLATE_HIP_NO_DICT, dict_of == NULL with n_dicts == 0, dicts == NULL with non-empty dictionaries.  A call in
+ * which no stream has a non-empty dictionary IS flate_hip_inflate_batch.  The used dictionaries' tails are
+ * uploaded once per call; every decoder has a dictionary build, chosen when a stream of the launch has one. */
+#define FLATE_HIP_NO_DICT 0xffffffffu
+int flate_hip_inflate_batch_dict(flate_hip_ctx *ctx, const uint8_t *in, const uint64_t *in_off, uint32_t n_streams,
+                                 const uint8_t *dicts, const uint64_t *dict_off, uint32_t n_dicts,
+                                 const uint32_t *dict_of,
+                                 uint8_t *out, const uint64_t *out_off, uint64_t *out_len,
+                                 int32_t *status, int64_t *err_off, uint32_t flags);
+
 /* ONE stream decoded in pieces -- Decompressor::read as the reference behaves (inflate.mbt:382-407): the
  * caller holds a piece of the compressed stream and room for a piece of the output, never the whole of
  * either; between two calls the decoder's state rests on the device: the 32 KiB window
@@ -238,7 +259,8 @@ int flate_hip_inflate_batch(flate_hip_ctx *ctx, const uint8_t *in, const uint64_
  *     stream, FLATE_HIP_E_UNEXPECTED_EOF when final_in was set and the stream is not complete); the
  *     bytes decoded in front of the error are delivered (:402-404).  in / out are HOST buffers; one
  *     call takes at most 1 GiB each way.  One wavefront decodes one stream: the reference's semantics
- *     for a long stream, not the engine's fast path (flate_hip_inflate_batch / _spliced are). */
+ *     for a long stream, not the engine's fast path (flate_hip_inflate_batch / _spliced are; batches of
+ *     streams with preset dictionaries: flate_hip_inflate_batch_dict). */
 typedef struct flate_hip_inflate_stream flate_hip_inflate_stream;
 #define FLATE_HIP_STREAM_END 1
 int flate_hip_inflate_stream_open(flate_hip_ctx *ctx, flate_hip_inflate_stream **stream);

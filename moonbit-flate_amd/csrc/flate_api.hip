@@ -52,6 +52,7 @@ struct flate_hip_ctx {
   // have three or more blocks on average (multi-window streams), 0 = never, 1 = whenever possible
   int entropy_per_block = -1;
   DevBuf d_istatus, d_ierr, d_debug, d_gtables, d_queue, d_simt_lens;
+  DevBuf d_dicts, d_dict_at, d_dict_len;  // flate_hip_inflate_batch_dict: dictionary tails, per-stream (at, len)
   hipStream_t guest_stream = nullptr;
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
   int guest_blocks = 0;      // 0 = guest kernel off
@@ -628,7 +629,8 @@ void flate_hip_destroy(flate_hip_ctx *c) {
   for (DevBuf *b : {&c->scan_tab, &c->d_in, &c->d_out, &c->d_in_off, &c->d_chunk_base, &c->d_ids16,
                     &c->d_ids32, &c->d_matches, &c->d_nmatch, &c->d_ntok, &c->d_blk_base,
                     &c->d_blk_hist, &c->d_blk_cl, &c->d_blk_hdr, &c->d_blk_meta, &c->d_tile_meta, &c->d_blk_sid, &c->d_slot_off, &c->d_out_len, &c->d_out_off, &c->d_status, &c->d_istatus,
-                    &c->d_ierr, &c->d_debug, &c->d_gtables, &c->d_queue, &c->d_simt_lens})
+                    &c->d_ierr, &c->d_debug, &c->d_gtables, &c->d_queue, &c->d_simt_lens,
+                    &c->d_dicts, &c->d_dict_at, &c->d_dict_len})
     release(*b);
   for (auto &e : c->ev)
     if (e) (void)hipEventDestroy(e);
@@ -1692,11 +1694,21 @@ int flate_hip_debug_lz_stamps(flate_hip_ctx *c, uint64_t *out, uint32_t max_chun
 
 }  // extern "C"
 
+// Preset dictionaries of a launch (flate_hip_inflate_batch_dict): the device tails and, per stream of the
+// launch, where its tail starts and how long it is (0 = none); h_len: the same lengths on the host.
+struct InfDict {
+  const uint8_t *buf;
+  const uint64_t *at;
+  const uint32_t *len;
+  const uint32_t *h_len;
+};
+
 // Both decode entry points.  spliced_len != 0: `in` is ONE stream of that many bytes and in_off
-// holds the bit positions of its n pieces (flate_hip_inflate_spliced).
+// holds the bit positions of its n pieces (flate_hip_inflate_spliced).  D != NULL: the streams'
+// dictionaries (a launch in which a stream has one runs the decoder's dictionary build).
 static int inflate_common(flate_hip_ctx *c, const uint8_t *in, const uint64_t *in_off, uint32_t n,
                           uint8_t *out, const uint64_t *out_off, uint64_t *out_len, int32_t *status,
-                          int64_t *err_off, uint32_t flags, uint64_t spliced_len) {
+                          int64_t *err_off, uint32_t flags, uint64_t spliced_len, const InfDict *D = nullptr) {
   const bool spliced = spliced_len != 0;
   const bool size_only = (flags & FLATE_HIP_SIZE_ONLY) != 0 && !spliced;
   const uint64_t in_bytes = spliced ? spliced_len : in_off[n];
@@ -1737,6 +1749,13 @@ static int inflate_common(flate_hip_ctx *c, const uint8_t *in, const uint64_t *i
   I.bit_off = spliced ? (const uint64_t *)c->d_in_off.p : nullptr;
   I.in_len = in_bytes;
   I.size_only = size_only ? 1u : 0u;
+  bool dict = false;
+  if (D) {
+    I.dict_buf = D->buf;
+    I.dict_at = D->at;
+    I.dict_len = D->len;
+    for (uint32_t i = 0; i < n && !dict; ++i) dict = D->h_len[i] != 0;
+  }
   {
     StageTimer t(c, FLATE_HIP_STAGE_INFLATE);
     // large batches: one lane per stream (64 streams per wavefront); small ones: one wavefront
@@ -1754,8 +1773,12 @@ static int inflate_common(flate_hip_ctx *c, const uint8_t *in, const uint64_t *i
       // (two builds of the same kernel: long token lists and a 16 KiB history ring while a SIMD holds
       // one wavefront, the small footprint beyond)
       const int shape = c->inflate_spec_shape ? c->inflate_spec_shape : (n <= 4u * c->num_cus ? 1 : 2);
-      if (shape == 1)
+      if (shape == 1 && dict)
+        hipLaunchKernelGGL(inflate_spec_dict_kernel<FLATE_SPEC_SMALL>, dim3(n), dim3(64), 0, c->stream, I);
+      else if (shape == 1)
         hipLaunchKernelGGL(inflate_spec_kernel<FLATE_SPEC_SMALL>, dim3(n), dim3(64), 0, c->stream, I);
+      else if (dict)
+        hipLaunchKernelGGL(inflate_spec_dict_kernel<FLATE_SPEC_LARGE>, dim3(n), dim3(64), 0, c->stream, I);
       else
         hipLaunchKernelGGL(inflate_spec_kernel<FLATE_SPEC_LARGE>, dim3(n), dim3(64), 0, c->stream, I);
     } else if (simt) {
@@ -1778,7 +1801,18 @@ static int inflate_common(flate_hip_ctx *c, const uint8_t *in, const uint64_t *i
         I.sid0 = b0 * (uint32_t)lpw;
         // (the output row -- a lane's output collected in registers and stored as whole aligned pieces -- pays
         // where the chip is full of lanes: the 64-lane form only)
-        if (lpw == 64 && c->inflate_row == 16)
+        if (dict) {
+          if (lpw == 64 && c->inflate_row == 16)
+            hipLaunchKernelGGL((inflate_simt_dict_kernel<64, 16>), dim3(nb), dim3(64), inflate_simt_lds_bytes(64), c->stream, I);
+          else if (lpw == 64 && c->inflate_row == 8)
+            hipLaunchKernelGGL((inflate_simt_dict_kernel<64, 8>), dim3(nb), dim3(64), inflate_simt_lds_bytes(64), c->stream, I);
+          else if (lpw == 64)
+            hipLaunchKernelGGL((inflate_simt_dict_kernel<64, 0>), dim3(nb), dim3(64), inflate_simt_lds_bytes(64), c->stream, I);
+          else if (lpw == 32)
+            hipLaunchKernelGGL((inflate_simt_dict_kernel<32, 0>), dim3(nb), dim3(64), inflate_simt_lds_bytes(32), c->stream, I);
+          else
+            hipLaunchKernelGGL((inflate_simt_dict_kernel<16, 0>), dim3(nb), dim3(64), inflate_simt_lds_bytes(16), c->stream, I);
+        } else if (lpw == 64 && c->inflate_row == 16)
           hipLaunchKernelGGL((inflate_simt_kernel<64, 16>), dim3(nb), dim3(64), inflate_simt_lds_bytes(64), c->stream, I);
         else if (lpw == 64 && c->inflate_row == 8)
           hipLaunchKernelGGL((inflate_simt_kernel<64, 8>), dim3(nb), dim3(64), inflate_simt_lds_bytes(64), c->stream, I);
@@ -1790,6 +1824,8 @@ static int inflate_common(flate_hip_ctx *c, const uint8_t *in, const uint64_t *i
           hipLaunchKernelGGL((inflate_simt_kernel<16, 0>), dim3(nb), dim3(64), inflate_simt_lds_bytes(16), c->stream, I);
       }
     }
+    else if (dict)
+      hipLaunchKernelGGL(inflate_dict_kernel, dim3(n), dim3(64), 0, c->stream, I);
     else
       hipLaunchKernelGGL(inflate_kernel, dim3(n), dim3(64), 0, c->stream, I);
   }
@@ -1818,7 +1854,8 @@ static int inflate_common(flate_hip_ctx *c, const uint8_t *in, const uint64_t *i
 // stream has its own input range and output slot, so a group is a contiguous range of both.
 static int inflate_host_pipelined(flate_hip_ctx *c, const uint8_t *in, const uint64_t *in_off, uint32_t n,
                                   uint8_t *out, const uint64_t *out_off, uint64_t *out_len,
-                                  int32_t *status, int64_t *err_off, uint32_t flags, uint32_t G) {
+                                  int32_t *status, int64_t *err_off, uint32_t flags, uint32_t G,
+                                  const InfDict *D) {
   HIP_TRY(c, hipSetDevice(c->device));
   int rc;
   if ((rc = ensure(c, c->d_in, in_off[n] + 16))) return rc;
@@ -1851,8 +1888,11 @@ static int inflate_host_pipelined(flate_hip_ctx *c, const uint8_t *in, const uin
     }
     if (cnt) {
       const double ta = host_now_ms();
+      InfDict gd{};  // (the group's slice of the per-stream dictionary arrays)
+      if (D) gd = {D->buf, D->at + a, D->len + a, D->h_len + a};
       const int r = inflate_common(c, d_in + in_off[a], gin.data(), cnt, d_out + out_off[a], gout.data(),
-                                   out_len + a, status + a, err_off + a, flags | FLATE_HIP_DEVICE_PTRS, 0);
+                                   out_len + a, status + a, err_off + a, flags | FLATE_HIP_DEVICE_PTRS, 0,
+                                   D ? &gd : nullptr);
       host_trace(t_call, "compute", g, ta, host_now_ms());
       // a stream's own failure (its status, also the return value) does not stop the batch: as in
       // one pass, every stream is decoded and the first failing status is what the call returns
@@ -1875,6 +1915,45 @@ static int inflate_host_pipelined(flate_hip_ctx *c, const uint8_t *in, const uin
   return rc;
 }
 
+// the argument checks of flate_hip_inflate_batch, for flate_hip_inflate_batch_dict (no HIP call)
+static int inflate_batch_check(flate_hip_ctx *c, const uint8_t *in, const uint64_t *in_off, uint32_t n,
+                               uint8_t *out, const uint64_t *out_off, uint64_t *out_len,
+                               int32_t *status, int64_t *err_off, uint32_t flags) {
+  const bool size_only = (flags & FLATE_HIP_SIZE_ONLY) != 0;
+  if (!c || !in_off || !out_len || !status || !err_off || (n && !in) ||
+      (!size_only && (!out_off || (n && !out))))
+    return FLATE_HIP_E_INVALID;
+  for (uint32_t i = 0; i < n; ++i)
+    if (in_off[i + 1] < in_off[i] || (!size_only && out_off[i + 1] < out_off[i])) return FLATE_HIP_E_INVALID;
+  for (uint32_t i = 0; i < n; ++i)
+    if (in_off[i + 1] - in_off[i] >= 0x7ffe0000ull) return FLATE_HIP_E_TOO_LARGE;
+  return FLATE_HIP_OK;
+}
+
+// flate_hip_inflate_batch after its checks; D: the streams' dictionaries (flate_hip_inflate_batch_dict)
+static int inflate_batch_run(flate_hip_ctx *c, const uint8_t *in, const uint64_t *in_off, uint32_t n,
+                             uint8_t *out, const uint64_t *out_off, uint64_t *out_len,
+                             int32_t *status, int64_t *err_off, uint32_t flags, const InfDict *D) {
+  const bool size_only = (flags & FLATE_HIP_SIZE_ONLY) != 0;
+  if (size_only)
+    return inflate_common(c, in, in_off, n, nullptr, nullptr, out_len, status, err_off, flags, 0, D);
+  // host pointers and a large batch: decode group g while g+1 is copied in and g-1 out
+  if (!(flags & FLATE_HIP_DEVICE_PTRS) && c->host_groups > 1 &&
+      in_off[n] - in_off[0] + out_off[n] - out_off[0] >= (64ull << 20)) {
+    uint32_t G = (uint32_t)c->host_groups;
+    const uint32_t iper = 4u * c->host_group_streams;  // (a group should still fill the lane-per-stream launch: 16384)
+    if (n / iper < G) G = n / iper;
+    if (G > 1) {
+      try {
+        return inflate_host_pipelined(c, in, in_off, n, out, out_off, out_len, status, err_off, flags, G, D);
+      } catch (const std::exception &e) {  // (no copy threads, out of host memory): one pass instead
+        c->hip_err.clear();
+      }
+    }
+  }
+  return inflate_common(c, in, in_off, n, out, out_off, out_len, status, err_off, flags, 0, D);
+}
+
 extern "C" {
 
 int flate_hip_inflate_batch(flate_hip_ctx *c, const uint8_t *in, const uint64_t *in_off, uint32_t n,
@@ -1890,23 +1969,67 @@ int flate_hip_inflate_batch(flate_hip_ctx *c, const uint8_t *in, const uint64_t 
     if (in_off[i + 1] < in_off[i] || (!size_only && out_off[i + 1] < out_off[i])) return FLATE_HIP_E_INVALID;
   for (uint32_t i = 0; i < n; ++i)
     if (in_off[i + 1] - in_off[i] >= 0x7ffe0000ull) return FLATE_HIP_E_TOO_LARGE;
-  if (size_only)
-    return inflate_common(c, in, in_off, n, nullptr, nullptr, out_len, status, err_off, flags, 0);
-  // host pointers and a large batch: decode group g while g+1 is copied in and g-1 out
-  if (!(flags & FLATE_HIP_DEVICE_PTRS) && c->host_groups > 1 &&
-      in_off[n] - in_off[0] + out_off[n] - out_off[0] >= (64ull << 20)) {
-    uint32_t G = (uint32_t)c->host_groups;
-    const uint32_t iper = 4u * c->host_group_streams;  // (a group should still fill the lane-per-stream launch: 16384)
-    if (n / iper < G) G = n / iper;
-    if (G > 1) {
-      try {
-        return inflate_host_pipelined(c, in, in_off, n, out, out_off, out_len, status, err_off, flags, G);
-      } catch (const std::exception &e) {  // (no copy threads, out of host memory): one pass instead
-        c->hip_err.clear();
-      }
-    }
+  return inflate_batch_run(c, in, in_off, n, out, out_off, out_len, status, err_off, flags, nullptr);
+}
+
+int flate_hip_inflate_batch_dict(flate_hip_ctx *c, const uint8_t *in, const uint64_t *in_off, uint32_t n,
+                                 const uint8_t *dicts, const uint64_t *dict_off, uint32_t n_dicts,
+                                 const uint32_t *dict_of, uint8_t *out, const uint64_t *out_off,
+                                 uint64_t *out_len, int32_t *status, int64_t *err_off, uint32_t flags) {
+  // every check before any HIP call
+  int rc = inflate_batch_check(c, in, in_off, n, out, out_off, out_len, status, err_off, flags);
+  if (rc != FLATE_HIP_OK && rc != FLATE_HIP_E_TOO_LARGE) return rc;
+  if (n_dicts && !dict_off) return FLATE_HIP_E_INVALID;
+  if (!dict_of && n_dicts == 0) return FLATE_HIP_E_INVALID;
+  for (uint32_t j = 0; j < n_dicts; ++j)
+    if (dict_off[j + 1] < dict_off[j]) return FLATE_HIP_E_INVALID;
+  if (n_dicts && dict_off[n_dicts] > dict_off[0] && !dicts) return FLATE_HIP_E_INVALID;
+  if (dict_of)
+    for (uint32_t i = 0; i < n; ++i)
+      if (dict_of[i] >= n_dicts && dict_of[i] != FLATE_HIP_NO_DICT) return FLATE_HIP_E_INVALID;
+  // the history each stream starts with: the last kMaxMatchOffset bytes of its dictionary
+  auto tail_len = [&](uint32_t j) -> uint32_t {
+    const uint64_t l = dict_off[j + 1] - dict_off[j];
+    return l < (uint64_t)kMaxMatchOffset ? (uint32_t)l : (uint32_t)kMaxMatchOffset;
+  };
+  auto dict_of_stream = [&](uint32_t i) { return dict_of ? dict_of[i] : 0u; };
+  bool any = false;
+  for (uint32_t i = 0; i < n && !any; ++i) any = dict_of_stream(i) != FLATE_HIP_NO_DICT && tail_len(dict_of_stream(i)) != 0;
+  if (!any)  // no stream has history in front of it: the plain call, its path and its results
+    return flate_hip_inflate_batch(c, in, in_off, n, out, out_off, out_len, status, err_off, flags);
+  c->hip_err.clear();
+  if (rc) return rc;
+  // every used dictionary's tail once, each followed by 16 bytes that a 16-byte load may touch
+  std::vector<uint64_t> tail_at(n_dicts, ~0ull);
+  uint64_t total = 0;
+  for (uint32_t i = 0; i < n; ++i) {
+    const uint32_t j = dict_of_stream(i);
+    if (j == FLATE_HIP_NO_DICT || tail_len(j) == 0 || tail_at[j] != ~0ull) continue;
+    tail_at[j] = total;
+    total += ((uint64_t)tail_len(j) + 16 + 15) & ~15ull;
   }
-  return inflate_common(c, in, in_off, n, out, out_off, out_len, status, err_off, flags, 0);
+  std::vector<uint64_t> h_at(n, 0);
+  std::vector<uint32_t> h_len(n, 0);
+  for (uint32_t i = 0; i < n; ++i) {
+    const uint32_t j = dict_of_stream(i);
+    if (j == FLATE_HIP_NO_DICT || tail_len(j) == 0) continue;
+    h_at[i] = tail_at[j];
+    h_len[i] = tail_len(j);
+  }
+  HIP_TRY(c, hipSetDevice(c->device));
+  if ((rc = ensure(c, c->d_dicts, total))) return rc;
+  if ((rc = ensure(c, c->d_dict_at, (size_t)n * 8))) return rc;
+  if ((rc = ensure(c, c->d_dict_len, (size_t)n * 4))) return rc;
+  uint8_t *d_dicts = (uint8_t *)c->d_dicts.p;
+  const hipMemcpyKind kind = (flags & FLATE_HIP_DEVICE_PTRS) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+  for (uint32_t j = 0; j < n_dicts; ++j)
+    if (tail_at[j] != ~0ull)
+      HIP_TRY(c, hipMemcpyAsync(d_dicts + tail_at[j], dicts + dict_off[j + 1] - tail_len(j), tail_len(j), kind, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(c->d_dict_at.p, h_at.data(), (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(c->d_dict_len.p, h_len.data(), (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  const InfDict D{d_dicts, (const uint64_t *)c->d_dict_at.p, (const uint32_t *)c->d_dict_len.p, h_len.data()};
+  return inflate_batch_run(c, in, in_off, n, out, out_off, out_len, status, err_off, flags, &D);
 }
 
 int flate_hip_inflate_spliced(flate_hip_ctx *c, const uint8_t *in, uint64_t in_len,

@@ -115,6 +115,13 @@ struct InfParams {
   uint32_t size_only;  // inflate_kernel: decode and count, store nothing (FLATE_HIP_SIZE_ONLY)
   uint32_t *simt_lens; // inflate_simt_kernel: per-lane scratch of the header being parsed (inflate_simt_lens_bytes)
   uint32_t sid0;       // inflate_simt_kernel: first stream of this launch (a batch of several rounds)
+  // preset dictionaries (the *_dict_kernel instantiations only): stream i's history starts with the
+  // dict_len[i] (<= 32768, 0 = none) bytes at dict_buf + dict_at[i], the tail of its dictionary; every
+  // tail is followed by at least 16 readable bytes.  Output byte k of the stream sits at history
+  // position dict_len[i] + k.
+  const uint8_t *dict_buf;
+  const uint64_t *dict_at;
+  const uint32_t *dict_len;
 };
 
 __global__ void lz77_serial_kernel(LzParams P);
@@ -144,10 +151,14 @@ __global__ void copy_ctl_kernel(uint32_t *dst, const uint32_t *src, size_t nword
 // spins (bounded) until *counter >= target: gates a sub-batch of the entropy stage on the match
 // finder that is still running on another stream
 __global__ void inflate_kernel(InfParams P);
+// the same decoders with preset dictionaries (InfParams::dict_*): the no-dictionary kernels keep their code
+__global__ void inflate_dict_kernel(InfParams P);
 // one wavefront per stream, 64 sub-blocks of the bit stream decoded at once (inflate_spec_kernel.inc):
 // <bits per sub-block, tokens per list, bytes of history ring>
 template <int SUB, int CAP, int RING>
 __global__ void inflate_spec_kernel(InfParams P);
+template <int SUB, int CAP, int RING>
+__global__ void inflate_spec_dict_kernel(InfParams P);
 #ifndef FLATE_SPEC_SMALL
 #define FLATE_SPEC_SMALL 288, 61, 8192  // batches up to one wavefront per SIMD (31.4 KiB of LDS)
 #endif
@@ -156,6 +167,8 @@ __global__ void inflate_spec_kernel(InfParams P);
 #endif
 template <int LPW, int ROWD>  // ROWD: dwords of the lane's output row (0 = none), see inflate_kernels.hip
 __global__ void inflate_simt_kernel(InfParams P);
+template <int LPW, int ROWD>
+__global__ void inflate_simt_dict_kernel(InfParams P);
 // one long stream decoded in pieces (inflate_stream_kernel.inc): the decoder's state -- the 32 KiB
 // window, the tables of the block in progress, the bit carry, a copy that did not fit -- rests in
 // `state` (inflate_stream_state_bytes()) between launches; its first 64 bytes are InfStreamResult

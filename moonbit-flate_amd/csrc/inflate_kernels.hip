@@ -213,8 +213,10 @@ FLATE_D int huff_sym(Bits &b, const Dec &d, int dmin, int dmax, const uint32_t *
 
 }  // namespace
 
-__global__ __launch_bounds__(64) void inflate_kernel(InfParams P) {
-  __shared__ InfShared sh;
+// The wave-per-stream decoder; DICT: with the preset dictionaries of InfParams (its tail is the
+// window in front of the output: output byte k at window index dict_len + k, mod kWin).
+template <bool DICT>
+FLATE_D void inflate_wave(const InfParams &P, InfShared &sh) {
   const int lane = threadIdx.x;
   const uint32_t sid = blockIdx.x;
   if (sid >= P.n_streams) return;
@@ -281,7 +283,13 @@ __global__ __launch_bounds__(64) void inflate_kernel(InfParams P) {
     err = (int)uni((uint32_t)err);
   };
 
-  restage();
+  uint32_t dict_len = 0;
+  if constexpr (DICT) {  // DictDecoder::new (dict-decoder.mbt:40-60): the tail at window -dict_len .. -1
+    dict_len = P.dict_len[sid];
+    const uint8_t *tail = P.dict_buf + P.dict_at[sid];
+    for (uint32_t i = lane; i < dict_len; i += 64) sh.win[(i - dict_len) & (kWin - 1)] = tail[i];
+  }
+  restage();  // (its barrier also publishes the dictionary)
   while (!final_block && !err) {  // next_block (inflate.mbt:345-379)
     pin();
     if (stage_low()) restage();
@@ -511,7 +519,8 @@ __global__ __launch_bounds__(64) void inflate_kernel(InfParams P) {
         err = E_CORRUPT;
         break;
       }
-      const uint32_t hist = opos < (uint32_t)kWin ? opos : (uint32_t)kWin;  // hist_size
+      uint32_t hist = opos < (uint32_t)kWin ? opos : (uint32_t)kWin;  // hist_size
+      if constexpr (DICT) hist = opos < (uint32_t)kWin - dict_len ? opos + dict_len : (uint32_t)kWin;
       if ((uint32_t)dist > hist) {
         err = E_CORRUPT;
         break;
@@ -539,10 +548,21 @@ __global__ __launch_bounds__(64) void inflate_kernel(InfParams P) {
   }
 }
 
+__global__ __launch_bounds__(64) void inflate_kernel(InfParams P) {
+  __shared__ InfShared sh;
+  inflate_wave<false>(P, sh);
+}
+__global__ __launch_bounds__(64) void inflate_dict_kernel(InfParams P) {
+  __shared__ InfShared sh;
+  inflate_wave<true>(P, sh);
+}
+
 #include "inflate_stream_kernel.inc"
 #include "inflate_spec_kernel.inc"
 template __global__ void inflate_spec_kernel<FLATE_SPEC_SMALL>(InfParams);
 template __global__ void inflate_spec_kernel<FLATE_SPEC_LARGE>(InfParams);
+template __global__ void inflate_spec_dict_kernel<FLATE_SPEC_SMALL>(InfParams);
+template __global__ void inflate_spec_dict_kernel<FLATE_SPEC_LARGE>(InfParams);
 
 }  // namespace flate
 
@@ -960,8 +980,10 @@ extern __shared__ uint16_t simt_lds[];  // kLaneWords * LPW entries
 
 // LPW = streams (active lanes) per wavefront; eight 64-lane wavefronts fit the LDS of a CU, and a
 // batch too small to give every SIMD one of those runs with 32 or 16 lanes per wavefront.
-template <int LPW, int ROWD>
-__global__ __launch_bounds__(64) void inflate_simt_kernel(InfParams P) {
+// DICT: with the preset dictionaries of InfParams -- a copy whose source lies in front of the output reads
+// the lane's dictionary tail in memory (a chunk never straddles the tail's end and the output's start).
+template <int LPW, int ROWD, bool DICT>
+FLATE_D void inflate_simt(const InfParams &P) {
   const int lane = threadIdx.x;
   const int lds_lane = lane < LPW ? lane : 0;
   const uint32_t sid = P.sid0 + blockIdx.x * (uint32_t)LPW + (uint32_t)lane;
@@ -1045,6 +1067,14 @@ __global__ __launch_bounds__(64) void inflate_simt_kernel(InfParams P) {
       const uint64_t rest = P.in_len - in_base;
       b.in_len = rest < (1ull << 28) ? (uint32_t)rest : (1u << 28);
       if (sid + 1 != P.n_streams) stop_bit = (uint32_t)(g1 - 8 * in_base);  // piece < 2^28 B: host
+    }
+  }
+  uint32_t dict_len = 0;          // DICT: the lane's dictionary tail, history positions -dict_len .. -1
+  const uint8_t *dict_tail = P.dict_buf;
+  if constexpr (DICT) {
+    if (have) {
+      dict_len = P.dict_len[sid];
+      dict_tail = P.dict_buf + P.dict_at[sid];
     }
   }
   b.in_bits = b.in_len * 8u;
@@ -1272,6 +1302,9 @@ __global__ __launch_bounds__(64) void inflate_simt_kernel(InfParams P) {
     if (state != S_STORED && copy_len != 0) {
       k = copy_len < copy_dist ? copy_len : copy_dist;  // source bytes that already exist
       if (k > kChunk) k = kChunk;
+      if constexpr (DICT) {  // a source in the dictionary: the chunk ends where the output starts
+        if (opos < copy_dist && k > copy_dist - opos) k = copy_dist - opos;
+      }
     }
     const bool last_chunk = copy_len == k;
     const uint32_t copy_dst = opos;  // where phase (2) stores those k bytes
@@ -1341,7 +1374,8 @@ __global__ __launch_bounds__(64) void inflate_simt_kernel(InfParams P) {
       const uint32_t dist =
           d < 4u ? d + 1u : (1u << (nb + 1u)) + 1u + ((d & 1u) << nb) + ((w >> len) & ((1u << nb) - 1u));
       const uint32_t t1 = b.bitpos + (uint32_t)dist_min, t2 = b.bitpos + len, t3 = t2 + nb;
-      const uint32_t hist = opos < 32768u ? opos : 32768u;  // hist_size
+      uint32_t hist = opos < 32768u ? opos : 32768u;  // hist_size
+      if constexpr (DICT) hist = opos < 32768u - dict_len ? opos + dict_len : 32768u;
       int e = 0;
       if (match_len > out_cap - opos) e = E_OUT_SMALL;
       if (dist > hist) e = E_CORRUPT;
@@ -1472,7 +1506,17 @@ __global__ __launch_bounds__(64) void inflate_simt_kernel(InfParams P) {
       b.n0 = (uint32_t)v;
       b.n1 = (uint32_t)(v >> 32);
     }
-    if (state != S_STORED && copy_len != 0) {
+    // DICT: the source starts in the dictionary (16 bytes from its tail stay inside the tail's padding)
+    const bool src_dict = DICT && opos < copy_dist;
+    if (src_dict && state != S_STORED && copy_len != 0) {
+      typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+      typedef u32x4 u128u __attribute__((aligned(1)));
+      const u32x4 hv = *reinterpret_cast<const u128u *>(dict_tail + (dict_len - (copy_dist - opos)));
+      pend_lo = hv.x;
+      pend_hi = hv.y;
+      pend_2 = hv.z;
+      pend_3 = hv.w;
+    } else if (state != S_STORED && copy_len != 0) {
       const uint8_t *src = out + opos - copy_dist;
       if constexpr (ROWD > 0) {
         // the 16 bytes about to be requested may reach into the row: memory must hold them first (the same
@@ -1516,11 +1560,24 @@ __global__ __launch_bounds__(64) void inflate_simt_kernel(InfParams P) {
     P.err_off[sid] = err == E_CORRUPT ? (long long)(in_base + sb_roffset(b)) : -1;
   }
 }
+template <int LPW, int ROWD>
+__global__ __launch_bounds__(64) void inflate_simt_kernel(InfParams P) {
+  inflate_simt<LPW, ROWD, false>(P);
+}
+template <int LPW, int ROWD>
+__global__ __launch_bounds__(64) void inflate_simt_dict_kernel(InfParams P) {
+  inflate_simt<LPW, ROWD, true>(P);
+}
 template __global__ void inflate_simt_kernel<64, 0>(InfParams);
 template __global__ void inflate_simt_kernel<64, 8>(InfParams);
 template __global__ void inflate_simt_kernel<64, 16>(InfParams);
 template __global__ void inflate_simt_kernel<32, 0>(InfParams);
 template __global__ void inflate_simt_kernel<16, 0>(InfParams);
+template __global__ void inflate_simt_dict_kernel<64, 0>(InfParams);
+template __global__ void inflate_simt_dict_kernel<64, 8>(InfParams);
+template __global__ void inflate_simt_dict_kernel<64, 16>(InfParams);
+template __global__ void inflate_simt_dict_kernel<32, 0>(InfParams);
+template __global__ void inflate_simt_dict_kernel<16, 0>(InfParams);
 
 size_t inflate_simt_lds_bytes(int lanes_per_wave) { return (size_t)kLaneWords * lanes_per_wave * sizeof(uint16_t); }
 size_t inflate_simt_lens_bytes(uint32_t blocks) { return (size_t)blocks * 64 * kLensDwords * sizeof(uint32_t); }

@@ -157,10 +157,12 @@ FLATE_D uint32_t spec_max(uint32_t v) {
 
 }  // namespace
 
-template <int SUB, int CAP, int RING>
-__global__ __launch_bounds__(64) void inflate_spec_kernel(InfParams P) {
+// DICT: with the preset dictionaries of InfParams -- the ring starts out holding the dictionary's tail (it
+// holds [opos - kSpecRing, opos) in history positions, the dictionary at -dict_len .. -1), and a far
+// source in front of the output reads the tail in memory.
+template <int SUB, int CAP, int RING, bool DICT>
+FLATE_D void inflate_spec(const InfParams &P, SpecShared<SUB, CAP, RING> &sh) {
   using Shared = SpecShared<SUB, CAP, RING>;
-  __shared__ Shared sh;
   constexpr uint32_t kSub = SUB;
   constexpr int kCap = CAP;
   constexpr int kSpecRing = RING;
@@ -206,6 +208,12 @@ __global__ __launch_bounds__(64) void inflate_spec_kernel(InfParams P) {
   uint32_t done_pos = 0;  // output below this is known to have reached memory (see put_group)
   int err = 0;
   bool final_block = false;
+  uint32_t dict_len = 0;  // DICT: the stream's dictionary tail, history positions -dict_len .. -1
+  const uint8_t *dict_tail = nullptr;
+  if constexpr (DICT) {
+    dict_len = P.dict_len[sid];
+    dict_tail = P.dict_buf + P.dict_at[sid];
+  }
 #ifdef FLATE_SPEC_STATS
   uint32_t st_batches = 0, st_rounds = 0, st_steps = 0, st_lanes = 0, st_tokens = 0, st_groups = 0, st_chunks = 0, st_exact = 0,
            st_far = 0, st_waits = 0, st_fill = 0, st_stop = 0, st_full = 0, st_check = 0, st_hazard = 0;
@@ -349,7 +357,12 @@ __global__ __launch_bounds__(64) void inflate_spec_kernel(InfParams P) {
         s = base0 + (t & 0x7fffu) - val + k;
       }
       // the ring holds [opos - kSpecRing, opos) at this point (opos = base0 + c_lo)
-      const bool far = cpy && s + (uint32_t)kSpecRing < opos;
+      bool far = cpy && s + (uint32_t)kSpecRing < opos;
+      bool in_dict = false;  // DICT: a far source in front of the output (opos - s: its distance from opos)
+      if constexpr (DICT) {
+        far = cpy && opos - s > (uint32_t)kSpecRing;
+        in_dict = far && opos - s > opos;
+      }
       // the far bytes of the chunk in front of this one (their loads had all of the above to arrive):
       // into the ring and the output before anything is read from the ring
       complete_pending();
@@ -357,7 +370,7 @@ __global__ __launch_bounds__(64) void inflate_spec_kernel(InfParams P) {
       if (__ballot(far)) {
         SPEC_STAT(++st_far);
         // a byte that left this wavefront only recently may still be on its way to memory
-        if (__ballot(far && s >= done_pos)) {
+        if (__ballot(far && !in_dict && s >= done_pos)) {
           SPEC_STAT(++st_waits);
           asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
           done_pos = opos;
@@ -368,12 +381,23 @@ __global__ __launch_bounds__(64) void inflate_spec_kernel(InfParams P) {
         pend_issue = opos;
       }
       put(v, cnt, far);
-      if (far) pend_val = out[s];  // (after the store of the chunk's other bytes: nothing is issued behind it)
+      if constexpr (DICT) {
+        if (in_dict) pend_val = dict_tail[dict_len + s];  // (s < 0: wraps to the tail's index)
+        else if (far) pend_val = out[s];
+      } else {
+        if (far) pend_val = out[s];  // (after the store of the chunk's other bytes: nothing is issued behind it)
+      }
       c_lo = c_hi;
     }
   };
 
-  restage_at(start_bit);
+  if constexpr (DICT) {
+    if (!size_only) {
+      const uint32_t m = dict_len < (uint32_t)kSpecRing ? dict_len : (uint32_t)kSpecRing;
+      for (uint32_t i = lane; i < m; i += 64) sh.ring[(i - m) & (kSpecRing - 1)] = dict_tail[dict_len - m + i];
+    }
+  }
+  restage_at(start_bit);  // (its barrier also publishes the ring)
   while (!final_block && !err) {  // next_block (inflate.mbt:345-379)
     SPEC_STAT(st_chdr -= __builtin_readcyclecounter());
     pin();
@@ -901,14 +925,14 @@ __global__ __launch_bounds__(64) void inflate_spec_kernel(InfParams P) {
           {
             const uint32_t oincl = spec_scan((uint32_t)lane < V ? osum : 0u);
             const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)oincl, 63);
-            if (opos < 32768u || total > out_cap - opos) {
+            if (opos < 32768u - dict_len || total > out_cap - opos) {
               SPEC_STAT(++st_check);
               uint32_t off = opos + oincl - osum;
               bool refuse = false;
               if ((uint32_t)lane < V) {
                 for (uint32_t i = 0; i < n; ++i) {
                   const uint32_t t = mytok[i];
-                  const uint32_t hist = off < 32768u ? off : 32768u;
+                  const uint32_t hist = off < 32768u - dict_len ? off + dict_len : 32768u;
                   refuse |= ((t & 0x200u) && (t >> 16) > hist) || (t & 0x1ffu) > out_cap - off;
                   off += t & 0x1ffu;
                 }
@@ -1049,7 +1073,7 @@ __global__ __launch_bounds__(64) void inflate_spec_kernel(InfParams P) {
         err = E_CORRUPT;
         break;
       }
-      const uint32_t hist = opos < (uint32_t)kWin ? opos : (uint32_t)kWin;  // hist_size
+      const uint32_t hist = opos < (uint32_t)kWin - dict_len ? opos + dict_len : (uint32_t)kWin;  // hist_size
       if ((uint32_t)dist > hist) {
         err = E_CORRUPT;
         break;
@@ -1090,4 +1114,15 @@ __global__ __launch_bounds__(64) void inflate_spec_kernel(InfParams P) {
     P.status[sid] = err;
     P.err_off[sid] = err == E_CORRUPT ? (long long)(in_base + b.roff) : -1;
   }
+}
+
+template <int SUB, int CAP, int RING>
+__global__ __launch_bounds__(64) void inflate_spec_kernel(InfParams P) {
+  __shared__ SpecShared<SUB, CAP, RING> sh;
+  inflate_spec<SUB, CAP, RING, false>(P, sh);
+}
+template <int SUB, int CAP, int RING>
+__global__ __launch_bounds__(64) void inflate_spec_dict_kernel(InfParams P) {
+  __shared__ SpecShared<SUB, CAP, RING> sh;
+  inflate_spec<SUB, CAP, RING, true>(P, sh);
 }

@@ -5,6 +5,7 @@ numpy / torch buffers into it.  PyTorch is used for device memory and streams on
 """
 import ctypes as C
 import os
+import zlib
 
 import numpy as np
 
@@ -14,6 +15,7 @@ DEVICE_PTRS = 0x1
 COMPAT_GO = 0x2
 LZ_SERIAL = 0x4
 SIZE_ONLY = 0x8
+NO_DICT = 0xFFFFFFFF  # FLATE_HIP_NO_DICT: a stream of flate_hip_inflate_batch_dict without a dictionary
 
 SYNTH_RAMP, SYNTH_TEXT, SYNTH_RAND, SYNTH_ZERO = 0, 1, 2, 3
 SYNTH_KINDS = {"ramp": SYNTH_RAMP, "text": SYNTH_TEXT, "rand": SYNTH_RAND, "zero": SYNTH_ZERO}
@@ -256,10 +258,12 @@ class FlateEngine:
             return ZLIB_HEADER + bytes(one[:int(nbytes)]) + s.to_bytes(4, "big")
         return GZIP_HEADER + bytes(one[:int(nbytes)]) + s.to_bytes(4, "little") + (total & 0xFFFFFFFF).to_bytes(4, "little")
 
-    def inflate_batch_framed(self, data, in_off, wrap, out_sizes=None):
+    def inflate_batch_framed(self, data, in_off, wrap, out_sizes=None, zdicts=None):
         """The reverse: zlib or gzip members -> (out, out_off, status[n]); status -4 (FLATE_HIP_E_CORRUPT) also
         for a bad header, a checksum or (gzip) a length that does not match.  zlib members carry no size:
-        out_sizes (or a size-only pass of the decoder) supplies it; gzip's ISIZE is used as the slot size."""
+        out_sizes (or a size-only pass of the decoder) supplies it; gzip's ISIZE is used as the slot size.
+        zdicts (zlib): one preset dictionary or a list of them; a member with FDICT is decoded with the one whose
+        Adler-32 is its DICTID (RFC 1950 2.2) -- none matches, or no zdicts: the member is corrupt."""
         data = np.ascontiguousarray(data, dtype=np.uint8)
         in_off = np.ascontiguousarray(in_off, dtype=np.uint64)
         n = in_off.size - 1
@@ -267,10 +271,18 @@ class FlateEngine:
         want = np.zeros(n, dtype=np.uint32)
         isize = np.zeros(n, dtype=np.uint64)
         bad = np.zeros(n, dtype=bool)
+        dlist = _dict_list(zdicts) if zdicts is not None and wrap == "zlib" else None
+        dict_of = np.full(n, NO_DICT, dtype=np.uint32) if dlist is not None else None
+        ids = zlib_dict_ids(dlist) if dlist is not None else None
         for i in range(n):
             a, b = int(in_off[i]), int(in_off[i + 1])
             m = data[a:b]
-            h, t = parse_container_header(m, wrap)
+            if wrap == "zlib":
+                h, t, j = zlib_member_header(m, ids)
+                if dict_of is not None:
+                    dict_of[i] = j
+            else:
+                h, t = parse_container_header(m, wrap)
             if h < 0 or b - a < h + t:
                 bad[i] = True
                 h = 0
@@ -286,8 +298,9 @@ class FlateEngine:
             if wrap == "gzip":
                 out_sizes = isize
             else:
-                out_sizes, _, _ = self.inflate_sizes(src, start)
-        out, ooff, olen, status, _ = self.inflate_batch(src, start, out_sizes, check=False)
+                out_sizes, _, _ = self.inflate_sizes(src, start, zdicts=dlist, dict_of=dict_of)
+        out, ooff, olen, status, _ = self.inflate_batch(src, start, out_sizes, check=False, zdicts=dlist,
+                                                        dict_of=dict_of)
         sums = self.checksum_batch(out, ooff, "adler32" if wrap == "zlib" else "crc32") if n else np.zeros(0, np.uint32)
         status = np.array(status, dtype=np.int32)
         for i in range(n):
@@ -304,9 +317,11 @@ class FlateEngine:
                     status[i] = E_CORRUPT
         return out, ooff, olen, status
 
-    def inflate_batch(self, data, in_off, out_sizes, out=None, check=True):
+    def inflate_batch(self, data, in_off, out_sizes, out=None, check=True, zdicts=None, dict_of=None):
         """Decompress independent DEFLATE streams (&Reader::new + read to EOF each).
         out_sizes[i] = capacity reserved for stream i's output (its exact size if known).
+        zdicts: preset dictionaries (&Reader::new_dict, flate_hip_inflate_batch_dict) -- one bytes-like object or
+        a list of them; dict_of[i] = the dictionary of stream i or NO_DICT (None: every stream uses the first).
         Returns (out, out_off, out_len, status, err_off); with check=True a failing stream raises."""
         in_off = np.ascontiguousarray(in_off, dtype=np.uint64)
         n = in_off.size - 1
@@ -332,17 +347,25 @@ class FlateEngine:
             else:
                 _check_out(out, data, int(out_off[-1]), "inflate")
             in_ptr, out_ptr = data.ctypes.data, out.ctypes.data
-        rc = self._L.flate_hip_inflate_batch(self._ctx, in_ptr, in_off.ctypes.data, n, out_ptr,
-                                             out_off.ctypes.data, out_len.ctypes.data,
-                                             status.ctypes.data, err_off.ctypes.data,
-                                             DEVICE_PTRS if device else 0)
+        if zdicts is None:
+            rc = self._L.flate_hip_inflate_batch(self._ctx, in_ptr, in_off.ctypes.data, n, out_ptr,
+                                                 out_off.ctypes.data, out_len.ctypes.data,
+                                                 status.ctypes.data, err_off.ctypes.data,
+                                                 DEVICE_PTRS if device else 0)
+        else:
+            dk = _DictArgs(zdicts, dict_of, n, device)
+            rc = self._L.flate_hip_inflate_batch_dict(self._ctx, in_ptr, in_off.ctypes.data, n, dk.ptr, dk.off_ptr,
+                                                      dk.n_dicts, dk.of_ptr, out_ptr, out_off.ctypes.data,
+                                                      out_len.ctypes.data, status.ctypes.data, err_off.ctypes.data,
+                                                      DEVICE_PTRS if device else 0)
         if rc != 0 and (check or rc not in (E_OUT_TOO_SMALL, E_CORRUPT, E_UNEXPECTED_EOF)):
             self._check(rc)
         return out, out_off, out_len, status, err_off
 
-    def inflate_sizes(self, data, in_off):
+    def inflate_sizes(self, data, in_off, zdicts=None, dict_of=None):
         """Decode without storing (FLATE_HIP_SIZE_ONLY): returns (out_len, status, err_off) -- the size
-        every stream inflates to (up to its error, if any).  Host or device input."""
+        every stream inflates to (up to its error, if any).  Host or device input; zdicts / dict_of as in
+        inflate_batch."""
         in_off = np.ascontiguousarray(in_off, dtype=np.uint64)
         n = in_off.size - 1
         out_len = np.zeros(max(n, 1), dtype=np.uint64)
@@ -352,9 +375,15 @@ class FlateEngine:
         if not device:
             data = np.ascontiguousarray(data, dtype=np.uint8)
         in_ptr = data.data_ptr() if device else data.ctypes.data
-        rc = self._L.flate_hip_inflate_batch(self._ctx, in_ptr, in_off.ctypes.data, n, None, None,
-                                             out_len.ctypes.data, status.ctypes.data, err_off.ctypes.data,
-                                             SIZE_ONLY | (DEVICE_PTRS if device else 0))
+        flags = SIZE_ONLY | (DEVICE_PTRS if device else 0)
+        if zdicts is None:
+            rc = self._L.flate_hip_inflate_batch(self._ctx, in_ptr, in_off.ctypes.data, n, None, None,
+                                                 out_len.ctypes.data, status.ctypes.data, err_off.ctypes.data, flags)
+        else:
+            dk = _DictArgs(zdicts, dict_of, n, device)
+            rc = self._L.flate_hip_inflate_batch_dict(self._ctx, in_ptr, in_off.ctypes.data, n, dk.ptr, dk.off_ptr,
+                                                      dk.n_dicts, dk.of_ptr, None, None, out_len.ctypes.data,
+                                                      status.ctypes.data, err_off.ctypes.data, flags)
         if rc != 0 and rc not in (E_OUT_TOO_SMALL, E_CORRUPT, E_UNEXPECTED_EOF):
             self._check(rc)
         return out_len[:n], status[:n], err_off[:n]
@@ -567,14 +596,74 @@ ZLIB_HEADER = bytes([0x78, 0x01])  # CM = 8, CINFO = 7 (32 KiB window), FLEVEL =
 GZIP_HEADER = bytes([0x1f, 0x8b, 8, 0, 0, 0, 0, 0, 4, 255])  # no name / time, XFL = 4 (fastest), OS unknown (RFC 1952 2.3)
 
 
-def parse_container_header(m, wrap):
+def _dict_list(zdicts):
+    """zdicts as a list of dictionaries: one bytes-like object (or 1-D tensor) is a list of one."""
+    if isinstance(zdicts, (bytes, bytearray, memoryview, np.ndarray)) or _is_torch(zdicts):
+        return [zdicts]
+    return list(zdicts)
+
+
+class _DictArgs:
+    """The dictionary arguments of flate_hip_inflate_batch_dict (kept alive as long as this object): the
+    dictionaries packed into one buffer (on the device when the call's pointers are), dict_off, dict_of."""
+
+    def __init__(self, zdicts, dict_of, n, device):
+        if device and _is_torch(zdicts):  # one dictionary already on the device
+            import torch
+            assert zdicts.dtype == torch.uint8 and zdicts.is_cuda and zdicts.is_contiguous()
+            self.buf = zdicts
+            lens = [zdicts.numel()]
+        else:
+            parts = [np.frombuffer(bytes(d), dtype=np.uint8) if not _is_torch(d) else d.cpu().numpy()
+                     for d in _dict_list(zdicts)]
+            lens = [p.size for p in parts]
+            self.buf = np.concatenate(parts + [np.zeros(16, np.uint8)])
+            if device:
+                import torch
+                self.buf = torch.from_numpy(self.buf).cuda()
+        self.off = np.zeros(len(lens) + 1, dtype=np.uint64)
+        np.cumsum(np.asarray(lens, dtype=np.uint64), out=self.off[1:])
+        self.n_dicts = len(lens)
+        self.ptr = self.buf.data_ptr() if _is_torch(self.buf) else self.buf.ctypes.data
+        self.off_ptr = self.off.ctypes.data
+        self.of = None
+        self.of_ptr = None
+        if dict_of is not None:
+            self.of = np.ascontiguousarray(dict_of, dtype=np.uint32)
+            assert self.of.size == n
+            self.of_ptr = self.of.ctypes.data
+
+
+def zlib_dict_ids(zdicts):
+    """{Adler-32 of the whole dictionary (a zlib DICTID, RFC 1950 2.2): index} of preset dictionaries."""
+    ids = {}
+    for j, d in enumerate(_dict_list(zdicts)):
+        ids.setdefault(zlib.adler32(bytes(d.cpu().numpy() if _is_torch(d) else d)), j)
+    return ids
+
+
+def zlib_member_header(m, ids):
+    """(header bytes, trailer bytes, dictionary) of one zlib member: the dictionary is NO_DICT, or with FDICT
+    the index its DICTID has in ids (zlib_dict_ids); (-1, 0, NO_DICT) = not valid -- also FDICT without ids or
+    with a DICTID that is not there."""
+    h, t = parse_container_header(m, "zlib", fdict=ids is not None)
+    if h != 6:
+        return h, t, NO_DICT
+    j = ids.get(int.from_bytes(bytes(m[2:6]), "big"))
+    return (-1, 0, NO_DICT) if j is None else (h, t, j)
+
+
+def parse_container_header(m, wrap, fdict=False):
     """(header bytes, trailer bytes) of one zlib / gzip member, or (-1, 0) if its header is not valid
-    (RFC 1950 2.2: CM = 8, window <= 32 KiB, FCHECK, no preset dictionary; RFC 1952 2.3: magic, CM = 8,
-    reserved flag bits zero, the optional fields skipped)."""
+    (RFC 1950 2.2: CM = 8, window <= 32 KiB, FCHECK, no preset dictionary unless fdict -- then FDICT gives a
+    6-byte header, DICTID in bytes 2-5; RFC 1952 2.3: magic, CM = 8, reserved flag bits zero, the optional
+    fields skipped)."""
     m = bytes(m[:min(len(m), 70000)])
     if wrap == "zlib":
-        if len(m) < 2 or (m[0] & 15) != 8 or (m[0] >> 4) > 7 or ((m[0] << 8) | m[1]) % 31 or (m[1] & 0x20):
+        if len(m) < 2 or (m[0] & 15) != 8 or (m[0] >> 4) > 7 or ((m[0] << 8) | m[1]) % 31:
             return -1, 0
+        if m[1] & 0x20:
+            return (6, 4) if fdict and len(m) >= 6 else (-1, 0)
         return 2, 4
     if len(m) < 10 or m[0] != 0x1f or m[1] != 0x8b or m[2] != 8 or (m[3] & 0xe0):
         return -1, 0

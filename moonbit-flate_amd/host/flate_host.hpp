@@ -398,6 +398,77 @@ inline Err decompress_batch(Engine &e, const std::vector<std::vector<uint8_t>> &
   return std::nullopt;
 }
 
+// &Reader::new_dict(r, dict) (inflate.mbt:315-317) in batch form (flate_hip_inflate_batch_dict): dicts[j] is a
+// preset dictionary (only its last 32768 bytes are history), dict_of[i] the dictionary of stream i or
+// FLATE_HIP_NO_DICT; an empty dict_of: every stream uses dicts[0].
+struct DictTable {
+  std::vector<uint8_t> bytes;
+  std::vector<uint64_t> off;
+  explicit DictTable(const std::vector<std::vector<uint8_t>> &dicts) : off(dicts.size() + 1, 0) {
+    for (size_t j = 0; j < dicts.size(); ++j) off[j + 1] = off[j] + dicts[j].size();
+    bytes.resize(off.back() + 16);
+    for (size_t j = 0; j < dicts.size(); ++j) std::copy(dicts[j].begin(), dicts[j].end(), bytes.begin() + off[j]);
+  }
+};
+
+inline Err inflate_sizes(Engine &e, const std::vector<std::vector<uint8_t>> &streams,
+                         const std::vector<std::vector<uint8_t>> &dicts, const std::vector<uint32_t> &dict_of,
+                         std::vector<uint64_t> &sizes) {
+  if (!e.ok()) return make_error(e, e.status());
+  const uint32_t n = (uint32_t)streams.size();
+  if (!dict_of.empty() && dict_of.size() != n) return make_error(e, FLATE_HIP_E_INVALID);
+  std::vector<uint64_t> in_off(n + 1, 0);
+  std::vector<int32_t> status(n + 1, 0);
+  std::vector<int64_t> err_off(n + 1, -1);
+  for (uint32_t i = 0; i < n; ++i) in_off[i + 1] = in_off[i] + streams[i].size();
+  std::vector<uint8_t> in(in_off[n] + 8);
+  for (uint32_t i = 0; i < n; ++i) std::copy(streams[i].begin(), streams[i].end(), in.begin() + in_off[i]);
+  const DictTable D(dicts);
+  sizes.assign(n + 1, 0);
+  const int rc = flate_hip_inflate_batch_dict(e.ctx(), in.data(), in_off.data(), n, D.bytes.data(), D.off.data(),
+                                              (uint32_t)dicts.size(), dict_of.empty() ? nullptr : dict_of.data(),
+                                              nullptr, nullptr, sizes.data(), status.data(), err_off.data(),
+                                              FLATE_HIP_SIZE_ONLY);
+  sizes.resize(n);
+  if (rc != 0 && rc != FLATE_HIP_E_CORRUPT && rc != FLATE_HIP_E_UNEXPECTED_EOF) return make_error(e, rc);
+  return std::nullopt;
+}
+
+inline Err decompress_batch(Engine &e, const std::vector<std::vector<uint8_t>> &streams,
+                            const std::vector<uint64_t> &sizes, const std::vector<std::vector<uint8_t>> &dicts,
+                            const std::vector<uint32_t> &dict_of, std::vector<Inflated> &out) {
+  if (!e.ok()) return make_error(e, e.status());
+  const uint32_t n = (uint32_t)streams.size();
+  if (!dict_of.empty() && dict_of.size() != n) return make_error(e, FLATE_HIP_E_INVALID);
+  std::vector<uint64_t> in_off(n + 1, 0), out_off(n + 1, 0), out_len(n + 1, 0);
+  std::vector<int32_t> status(n + 1, 0);
+  std::vector<int64_t> err_off(n + 1, -1);
+  for (uint32_t i = 0; i < n; ++i) {
+    in_off[i + 1] = in_off[i] + streams[i].size();
+    out_off[i + 1] = out_off[i] + sizes[i];
+  }
+  std::vector<uint8_t> in(in_off[n] + 8), buf(out_off[n] + 8);
+  for (uint32_t i = 0; i < n; ++i)
+    std::copy(streams[i].begin(), streams[i].end(), in.begin() + in_off[i]);
+  const DictTable D(dicts);
+  const int rc = flate_hip_inflate_batch_dict(e.ctx(), in.data(), in_off.data(), n, D.bytes.data(), D.off.data(),
+                                              (uint32_t)dicts.size(), dict_of.empty() ? nullptr : dict_of.data(),
+                                              buf.data(), out_off.data(), out_len.data(), status.data(),
+                                              err_off.data(), 0);
+  if (rc != 0 && rc != FLATE_HIP_E_CORRUPT && rc != FLATE_HIP_E_UNEXPECTED_EOF && rc != FLATE_HIP_E_OUT_TOO_SMALL)
+    return make_error(e, rc);
+  out.resize(n);
+  for (uint32_t i = 0; i < n; ++i) {
+    out[i].bytes.assign(buf.begin() + out_off[i], buf.begin() + out_off[i] + out_len[i]);
+    out[i].err = std::nullopt;
+    out[i].status = status[i];
+    if (status[i] == FLATE_HIP_E_CORRUPT) out[i].err = corrupt_input_error(err_off[i]);
+    else if (status[i] == FLATE_HIP_E_UNEXPECTED_EOF) out[i].err = err_unexpected_eof();
+    else if (status[i] != 0) out[i].err = make_error(e, status[i]);
+  }
+  return std::nullopt;
+}
+
 // header / trailer bytes of one zlib or gzip member, {-1, 0} if its header is not one (RFC 1950 2.2: CM = 8,
 // window <= 32 KiB, FCHECK, no preset dictionary; RFC 1952 2.3: magic, CM = 8, reserved flag bits zero, the
 // optional fields skipped)
