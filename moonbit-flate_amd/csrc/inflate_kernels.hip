@@ -1181,8 +1181,11 @@ FLATE_D void inflate_simt(const InfParams &P) {
             b.hi = (p + 4) * 8u;
             const uint32_t n = (uint32_t)b.in[p] | ((uint32_t)b.in[p + 1] << 8);
             const uint32_t nn = (uint32_t)b.in[p + 2] | ((uint32_t)b.in[p + 3] << 8);
+            const uint32_t avail = b.in_len - (p + 4);
             if ((nn & 0xffffu) != ((~n) & 0xffffu)) {
               serr = E_CORRUPT;
+            } else if ((n < avail ? n : avail) > out_cap - opos) {
+              serr = E_OUT_SMALL;  // (:745-750) a block that does not fit is not copied at all
             } else {
               copy_len = n;
               state = S_STORED;

@@ -4,26 +4,18 @@ import zlib
 import numpy as np
 import pytest
 
-from util import flate, make_streams
+from util import INFLATE_CONFIGS, STATUS_OF_ORACLE, flate, force_inflate_config, make_streams
 
 pytestmark = pytest.mark.gpu
 
 
-@pytest.fixture(scope="module", params=["wave_per_stream", "lane_per_stream", "lane_per_stream_64_row8",
-                                        "lane_per_stream_64_row16", "lane_per_stream_64_norow",
-                                        "speculative_wave_small_batch", "speculative_wave_large_batch"])
+@pytest.fixture(scope="module", params=INFLATE_CONFIGS)
 def eng(request):
     """All three inflater kernels (both builds of the third; the lane-per-stream one by batch size -- small test
-    batches take its 16-lane form -- and in its 64-lane form with an output row of 8 and 16 dwords and without
-    one) must pass every test: the options force one of them."""
+    batches take its 16-lane form -- in its 32-lane form, and in its 64-lane form with an output row of 8 and 16
+    dwords and without one) must pass every test: the options force one of them (util.INFLATE_CONFIGS)."""
     flate.build()
-    e = flate.FlateEngine(0)
-    e.set_option("inflate_simt_min_streams", 0 if request.param.startswith("lane_per_stream") else 1 << 30)
-    e.set_option("inflate_spec", 2 if request.param.startswith("speculative_wave") else 0)
-    e.set_option("inflate_spec_shape", 1 if request.param.endswith("small_batch") else 2)
-    if request.param.startswith("lane_per_stream_64"):
-        e.set_option("inflate_lanes", 64)
-        e.set_option("inflate_row_dwords", {"row8": 8, "row16": 16, "norow": 0}[request.param.rsplit("_", 1)[1]])
+    e = force_inflate_config(flate.FlateEngine(0), request.param)
     yield e
     e.close()
 
@@ -98,8 +90,9 @@ def test_inflate_errors_match_oracle(eng, oracle):
                        oracle.E_OUT_TOO_SMALL: -2}[rc]
         assert int(status[i]) == want_status, (i, bl[:8].hex(), int(status[i]), rc)
         assert int(err[i]) == eoff, (i, int(err[i]), eoff)
-        if rc == 0:
-            assert bytes(out[int(ooff[i]):int(ooff[i]) + int(olen[i])]) == res
+        # on every status: out_len is the bytes produced, and they are the oracle's
+        assert int(olen[i]) == len(res), (i, rc, int(olen[i]), len(res))
+        assert bytes(out[int(ooff[i]):int(ooff[i]) + int(olen[i])]) == res, (i, rc)
 
 
 def test_inflate_errors_in_long_streams_match_oracle(eng, oracle):
@@ -132,8 +125,9 @@ def test_inflate_errors_in_long_streams_match_oracle(eng, oracle):
                        oracle.E_OUT_TOO_SMALL: -2}[rc]
         assert int(status[i]) == want_status, (i, int(status[i]), rc)
         assert int(err[i]) == eoff, (i, int(err[i]), eoff)
-        if rc == 0:
-            assert bytes(out[int(ooff[i]):int(ooff[i]) + int(olen[i])]) == res
+        # on every status: out_len is the bytes produced, and they are the oracle's
+        assert int(olen[i]) == len(res), (i, rc, int(olen[i]), len(res))
+        assert bytes(out[int(ooff[i]):int(ooff[i]) + int(olen[i])]) == res, (i, rc)
 
 
 def test_inflate_token_density_swings(eng, oracle):
@@ -332,14 +326,15 @@ def test_literal_only_blocks_errors_and_long_codes(eng, oracle):
         want_status = {0: 0, oracle.E_CORRUPT: -4, oracle.E_UNEXPECTED_EOF: -7, oracle.E_OUT_TOO_SMALL: -2}[rc]
         assert int(status[i]) == want_status, (i, int(status[i]), rc)
         assert int(err[i]) == eoff, (i, int(err[i]), eoff)
-        if rc == 0:
-            assert bytes(out[int(ooff[i]):int(ooff[i]) + int(olen[i])]) == res
+        # on every status: out_len is the bytes produced, and they are the oracle's
+        assert int(olen[i]) == len(res), (i, rc, int(olen[i]), len(res))
+        assert bytes(out[int(ooff[i]):int(ooff[i]) + int(olen[i])]) == res, (i, rc)
     # sizes without output (FLATE_HIP_SIZE_ONLY) take the same path
     good = [b for b, c in zip(blobs, caps)][0::10]
     d2, o2 = _pack(good)
-    olen2, st2, _ = eng.inflate_sizes(d2, o2)
+    olen2, st2, err2 = eng.inflate_sizes(d2, o2)
     for i, bl in enumerate(good):
-        rc, res, _, _ = oracle.inflate(bl, 1 << 20, full=True)
+        rc, res, _, eoff = oracle.inflate(bl, 1 << 20, full=True)
         assert (int(st2[i]) == 0) == (rc == 0)
-        if rc == 0:
-            assert int(olen2[i]) == len(res)
+        # (the size up to the error, if any: FLATE_HIP_SIZE_ONLY)
+        assert (int(st2[i]), int(err2[i]), int(olen2[i])) == (STATUS_OF_ORACLE[rc], eoff, len(res)), i

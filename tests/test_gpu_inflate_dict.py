@@ -7,26 +7,19 @@ import zlib
 import numpy as np
 import pytest
 
-from util import flate
+from util import INFLATE_CONFIGS, flate, force_inflate_config
 
 pytestmark = pytest.mark.gpu
 
 NO_DICT = flate.NO_DICT
 
 
-@pytest.fixture(scope="module", params=["wave_per_stream", "lane_per_stream", "lane_per_stream_64_row8",
-                                        "lane_per_stream_64_row16", "lane_per_stream_64_norow",
-                                        "speculative_wave_small_batch", "speculative_wave_large_batch"])
+@pytest.fixture(scope="module", params=INFLATE_CONFIGS)
 def eng(request):
-    """Every decoder (as tests/test_gpu_inflate.py forces them) has a dictionary build: all must pass."""
+    """Every decoder (util.INFLATE_CONFIGS, as tests/test_gpu_inflate.py forces them) has a dictionary build: all
+    must pass."""
     flate.build()
-    e = flate.FlateEngine(0)
-    e.set_option("inflate_simt_min_streams", 0 if request.param.startswith("lane_per_stream") else 1 << 30)
-    e.set_option("inflate_spec", 2 if request.param.startswith("speculative_wave") else 0)
-    e.set_option("inflate_spec_shape", 1 if request.param.endswith("small_batch") else 2)
-    if request.param.startswith("lane_per_stream_64"):
-        e.set_option("inflate_lanes", 64)
-        e.set_option("inflate_row_dwords", {"row8": 8, "row16": 16, "norow": 0}[request.param.rsplit("_", 1)[1]])
+    e = force_inflate_config(flate.FlateEngine(0), request.param)
     yield e
     e.close()
 
@@ -48,7 +41,7 @@ def _pack(blobs):
 
 
 def _check(oracle, blobs, caps, dicts, dict_of, res):
-    """Stream by stream: status and error offset always, bytes and out_len where the oracle succeeds."""
+    """Stream by stream, on every status: status, error offset, out_len and the bytes delivered."""
     out, ooff, olen, status, err = res
     for i, bl in enumerate(blobs):
         j = 0 if dict_of is None else int(dict_of[i])
@@ -57,9 +50,8 @@ def _check(oracle, blobs, caps, dicts, dict_of, res):
         want_status = {0: 0, oracle.E_CORRUPT: -4, oracle.E_UNEXPECTED_EOF: -7, oracle.E_OUT_TOO_SMALL: -2}[rc]
         assert int(status[i]) == want_status, (i, int(status[i]), rc)
         assert int(err[i]) == eoff, (i, int(err[i]), eoff)
-        if rc == 0:
-            assert int(olen[i]) == len(want), i
-            assert bytes(out[int(ooff[i]):int(ooff[i]) + int(olen[i])]) == want, i
+        assert int(olen[i]) == len(want), (i, rc, int(olen[i]), len(want))
+        assert bytes(out[int(ooff[i]):int(ooff[i]) + int(olen[i])]) == want, (i, rc)
 
 
 # ---- a fixed-Huffman DEFLATE writer for hand-made edge copies (RFC 1951 3.2.5-3.2.6) ----
@@ -224,8 +216,7 @@ def test_size_only_sizes(eng, oracle):
         rc, want, used, eoff = oracle.inflate(bl, 1 << 20, full=True, zdict=dicts[dict_of[i]])
         assert int(status[i]) == {0: 0, oracle.E_CORRUPT: -4, oracle.E_UNEXPECTED_EOF: -7}[rc], i
         assert int(err[i]) == eoff
-        if rc == 0:
-            assert int(olen[i]) == len(want)
+        assert int(olen[i]) == len(want), (i, rc)  # (up to the error, if any)
 
 
 def test_device_pointers_with_dictionaries_on_the_device(eng, oracle):

@@ -60,3 +60,37 @@ def oracle_tokens_per_chunk(oracle, stream_bytes, compat=0):
     for start, n in flate.lz_chunks(len(stream_bytes)):
         out.append(df.encode(stream_bytes[start:start + n]))
     return out
+
+
+# Every decoder configuration of the batch inflater: wave-per-stream; lane-per-stream by batch size (small test
+# batches take its 16-lane form), in its 32-lane form, and in its 64-lane form with an output row of 8 and 16
+# dwords and without one; the speculative sub-block decoder in its small-batch and large-batch builds.
+INFLATE_CONFIGS = ["wave_per_stream", "lane_per_stream", "lane_per_stream_32", "lane_per_stream_64_row8",
+                   "lane_per_stream_64_row16", "lane_per_stream_64_norow", "speculative_wave_small_batch",
+                   "speculative_wave_large_batch"]
+
+
+def force_inflate_config(eng, name):
+    """Set the engine options that make every batch inflate call take decoder configuration `name`."""
+    assert name in INFLATE_CONFIGS, name
+    eng.set_option("inflate_simt_min_streams", 0 if name.startswith("lane_per_stream") else 1 << 30)
+    eng.set_option("inflate_spec", 2 if name.startswith("speculative_wave") else 0)
+    eng.set_option("inflate_spec_shape", 1 if name.endswith("small_batch") else 2)
+    eng.set_option("inflate_lanes", 32 if name == "lane_per_stream_32" else
+                   64 if name.startswith("lane_per_stream_64") else 0)
+    if name.startswith("lane_per_stream_64"):
+        eng.set_option("inflate_row_dwords", {"row8": 8, "row16": 16, "norow": 0}[name.rsplit("_", 1)[1]])
+    return eng
+
+
+STATUS_OF_ORACLE = {0: 0, -2: -4, -3: -7, -1: -2}  # oracle OK / E_CORRUPT / E_UNEXPECTED_EOF / E_OUT_TOO_SMALL
+
+
+def check_stream(i, oracle_result, status, err, out, ooff, olen):
+    """Stream i of a batch against the oracle's (rc, bytes, consumed, err_off): status, error offset, out_len and
+    the bytes delivered -- on every status."""
+    rc, want, _, eoff = oracle_result
+    got = bytes(out[int(ooff[i]):int(ooff[i]) + int(olen[i])])
+    assert (int(status[i]), int(err[i]), int(olen[i])) == (STATUS_OF_ORACLE[rc], eoff, len(want)), \
+        (i, int(status[i]), rc, int(err[i]), eoff, int(olen[i]), len(want))
+    assert got == want, (i, rc, len(want))
