@@ -1773,19 +1773,27 @@ static int inflate_common(flate_hip_ctx *c, const uint8_t *in, const uint64_t *i
       // (two builds of the same kernel: long token lists and a 16 KiB history ring while a SIMD holds
       // one wavefront, the small footprint beyond)
       const int shape = c->inflate_spec_shape ? c->inflate_spec_shape : (n <= 4u * c->num_cus ? 1 : 2);
-      if (shape == 1 && dict)
-        hipLaunchKernelGGL(inflate_spec_dict_kernel<FLATE_SPEC_SMALL>, dim3(n), dim3(64), 0, c->stream, I);
-      else if (shape == 1)
-        hipLaunchKernelGGL(inflate_spec_kernel<FLATE_SPEC_SMALL>, dim3(n), dim3(64), 0, c->stream, I);
-      else if (dict)
-        hipLaunchKernelGGL(inflate_spec_dict_kernel<FLATE_SPEC_LARGE>, dim3(n), dim3(64), 0, c->stream, I);
-      else
-        hipLaunchKernelGGL(inflate_spec_kernel<FLATE_SPEC_LARGE>, dim3(n), dim3(64), 0, c->stream, I);
+      void (*k)(InfParams) = shape == 1 ? (dict ? inflate_spec_dict_kernel<FLATE_SPEC_SMALL> : inflate_spec_kernel<FLATE_SPEC_SMALL>)
+                                        : (dict ? inflate_spec_dict_kernel<FLATE_SPEC_LARGE> : inflate_spec_kernel<FLATE_SPEC_LARGE>);
+      hipLaunchKernelGGL(k, dim3(n), dim3(64), 0, c->stream, I);
     } else if (simt) {
       // streams per wavefront
       int lpw = c->inflate_lanes;
       // (measured, same file: 16 lanes per wavefront up to ~20 k streams, 32 up to ~36 k, 64 beyond)
       if (lpw == 0) lpw = n >= 144u * c->num_cus ? 64 : (n >= 80u * c->num_cus ? 32 : 16);
+      // (the output row -- a lane's output collected in registers and stored as whole aligned pieces -- pays
+      // where the chip is full of lanes: the 64-lane form only)
+      void (*k)(InfParams);
+      if (lpw == 64 && c->inflate_row == 16)
+        k = dict ? inflate_simt_dict_kernel<64, 16> : inflate_simt_kernel<64, 16>;
+      else if (lpw == 64 && c->inflate_row == 8)
+        k = dict ? inflate_simt_dict_kernel<64, 8> : inflate_simt_kernel<64, 8>;
+      else if (lpw == 64)
+        k = dict ? inflate_simt_dict_kernel<64, 0> : inflate_simt_kernel<64, 0>;
+      else if (lpw == 32)
+        k = dict ? inflate_simt_dict_kernel<32, 0> : inflate_simt_kernel<32, 0>;
+      else
+        k = dict ? inflate_simt_dict_kernel<16, 0> : inflate_simt_kernel<16, 0>;
       const uint32_t sblocks = (n + (uint32_t)lpw - 1) / (uint32_t)lpw;
       // A CU holds eight of these wavefronts (320 B of LDS per lane): a batch of more blocks than
       // that runs in ROUNDS, and a lane's rate depends little on how full the chip is -- so the rounds
@@ -1799,35 +1807,11 @@ static int inflate_common(flate_hip_ctx *c, const uint8_t *in, const uint64_t *i
       for (uint32_t b0 = 0; b0 < sblocks; b0 += per) {
         const uint32_t nb = sblocks - b0 < per ? sblocks - b0 : per;
         I.sid0 = b0 * (uint32_t)lpw;
-        // (the output row -- a lane's output collected in registers and stored as whole aligned pieces -- pays
-        // where the chip is full of lanes: the 64-lane form only)
-        if (dict) {
-          if (lpw == 64 && c->inflate_row == 16)
-            hipLaunchKernelGGL((inflate_simt_dict_kernel<64, 16>), dim3(nb), dim3(64), inflate_simt_lds_bytes(64), c->stream, I);
-          else if (lpw == 64 && c->inflate_row == 8)
-            hipLaunchKernelGGL((inflate_simt_dict_kernel<64, 8>), dim3(nb), dim3(64), inflate_simt_lds_bytes(64), c->stream, I);
-          else if (lpw == 64)
-            hipLaunchKernelGGL((inflate_simt_dict_kernel<64, 0>), dim3(nb), dim3(64), inflate_simt_lds_bytes(64), c->stream, I);
-          else if (lpw == 32)
-            hipLaunchKernelGGL((inflate_simt_dict_kernel<32, 0>), dim3(nb), dim3(64), inflate_simt_lds_bytes(32), c->stream, I);
-          else
-            hipLaunchKernelGGL((inflate_simt_dict_kernel<16, 0>), dim3(nb), dim3(64), inflate_simt_lds_bytes(16), c->stream, I);
-        } else if (lpw == 64 && c->inflate_row == 16)
-          hipLaunchKernelGGL((inflate_simt_kernel<64, 16>), dim3(nb), dim3(64), inflate_simt_lds_bytes(64), c->stream, I);
-        else if (lpw == 64 && c->inflate_row == 8)
-          hipLaunchKernelGGL((inflate_simt_kernel<64, 8>), dim3(nb), dim3(64), inflate_simt_lds_bytes(64), c->stream, I);
-        else if (lpw == 64)
-          hipLaunchKernelGGL((inflate_simt_kernel<64, 0>), dim3(nb), dim3(64), inflate_simt_lds_bytes(64), c->stream, I);
-        else if (lpw == 32)
-          hipLaunchKernelGGL((inflate_simt_kernel<32, 0>), dim3(nb), dim3(64), inflate_simt_lds_bytes(32), c->stream, I);
-        else
-          hipLaunchKernelGGL((inflate_simt_kernel<16, 0>), dim3(nb), dim3(64), inflate_simt_lds_bytes(16), c->stream, I);
+        hipLaunchKernelGGL(k, dim3(nb), dim3(64), inflate_simt_lds_bytes(lpw), c->stream, I);
       }
+    } else {
+      hipLaunchKernelGGL(dict ? inflate_dict_kernel : inflate_kernel, dim3(n), dim3(64), 0, c->stream, I);
     }
-    else if (dict)
-      hipLaunchKernelGGL(inflate_dict_kernel, dim3(n), dim3(64), 0, c->stream, I);
-    else
-      hipLaunchKernelGGL(inflate_kernel, dim3(n), dim3(64), 0, c->stream, I);
   }
   HIP_TRY(c, hipGetLastError());
   if ((rc = ctl_down(c, out_len, c->d_out_len.p, (size_t)n * 8))) return rc;
@@ -1915,14 +1899,16 @@ static int inflate_host_pipelined(flate_hip_ctx *c, const uint8_t *in, const uin
   return rc;
 }
 
-// the argument checks of flate_hip_inflate_batch, for flate_hip_inflate_batch_dict (no HIP call)
-static int inflate_batch_check(flate_hip_ctx *c, const uint8_t *in, const uint64_t *in_off, uint32_t n,
-                               uint8_t *out, const uint64_t *out_off, uint64_t *out_len,
-                               int32_t *status, int64_t *err_off, uint32_t flags) {
+// The argument checks of flate_hip_inflate_batch(_dict) (no HIP call): the pointers ...
+static bool inflate_batch_ptrs_ok(flate_hip_ctx *c, const uint8_t *in, const uint64_t *in_off, uint32_t n,
+                                  uint8_t *out, const uint64_t *out_off, uint64_t *out_len,
+                                  int32_t *status, int64_t *err_off, uint32_t flags) {
   const bool size_only = (flags & FLATE_HIP_SIZE_ONLY) != 0;
-  if (!c || !in_off || !out_len || !status || !err_off || (n && !in) ||
-      (!size_only && (!out_off || (n && !out))))
-    return FLATE_HIP_E_INVALID;
+  return c && in_off && out_len && status && err_off && (!n || in) && (size_only || (out_off && (!n || out)));
+}
+// ... and the streams' offsets and sizes
+static int inflate_batch_ranges(const uint64_t *in_off, uint32_t n, const uint64_t *out_off, uint32_t flags) {
+  const bool size_only = (flags & FLATE_HIP_SIZE_ONLY) != 0;
   for (uint32_t i = 0; i < n; ++i)
     if (in_off[i + 1] < in_off[i] || (!size_only && out_off[i + 1] < out_off[i])) return FLATE_HIP_E_INVALID;
   for (uint32_t i = 0; i < n; ++i)
@@ -1959,17 +1945,11 @@ extern "C" {
 int flate_hip_inflate_batch(flate_hip_ctx *c, const uint8_t *in, const uint64_t *in_off, uint32_t n,
                             uint8_t *out, const uint64_t *out_off, uint64_t *out_len,
                             int32_t *status, int64_t *err_off, uint32_t flags) {
-  const bool size_only = (flags & FLATE_HIP_SIZE_ONLY) != 0;
-  if (!c || !in_off || !out_len || !status || !err_off || (n && !in) ||
-      (!size_only && (!out_off || (n && !out))))
-    return FLATE_HIP_E_INVALID;
+  if (!inflate_batch_ptrs_ok(c, in, in_off, n, out, out_off, out_len, status, err_off, flags)) return FLATE_HIP_E_INVALID;
   c->hip_err.clear();
   if (n == 0) return FLATE_HIP_OK;
-  for (uint32_t i = 0; i < n; ++i)
-    if (in_off[i + 1] < in_off[i] || (!size_only && out_off[i + 1] < out_off[i])) return FLATE_HIP_E_INVALID;
-  for (uint32_t i = 0; i < n; ++i)
-    if (in_off[i + 1] - in_off[i] >= 0x7ffe0000ull) return FLATE_HIP_E_TOO_LARGE;
-  return inflate_batch_run(c, in, in_off, n, out, out_off, out_len, status, err_off, flags, nullptr);
+  const int rc = inflate_batch_ranges(in_off, n, out_off, flags);
+  return rc ? rc : inflate_batch_run(c, in, in_off, n, out, out_off, out_len, status, err_off, flags, nullptr);
 }
 
 int flate_hip_inflate_batch_dict(flate_hip_ctx *c, const uint8_t *in, const uint64_t *in_off, uint32_t n,
@@ -1977,7 +1957,8 @@ int flate_hip_inflate_batch_dict(flate_hip_ctx *c, const uint8_t *in, const uint
                                  const uint32_t *dict_of, uint8_t *out, const uint64_t *out_off,
                                  uint64_t *out_len, int32_t *status, int64_t *err_off, uint32_t flags) {
   // every check before any HIP call
-  int rc = inflate_batch_check(c, in, in_off, n, out, out_off, out_len, status, err_off, flags);
+  if (!inflate_batch_ptrs_ok(c, in, in_off, n, out, out_off, out_len, status, err_off, flags)) return FLATE_HIP_E_INVALID;
+  int rc = inflate_batch_ranges(in_off, n, out_off, flags);
   if (rc != FLATE_HIP_OK && rc != FLATE_HIP_E_TOO_LARGE) return rc;
   if (n_dicts && !dict_off) return FLATE_HIP_E_INVALID;
   if (!dict_of && n_dicts == 0) return FLATE_HIP_E_INVALID;

@@ -211,6 +211,220 @@ FLATE_D int huff_sym(Bits &b, const Dec &d, int dmin, int dmax, const uint32_t *
   return -1;
 }
 
+// The steps of the one-symbol-at-a-time reader that every wave-uniform decoder (inflate_wave,
+// inflate_stream_kernel, the exact reader of inflate_spec) shares: one copy, so that their accept /
+// reject decisions and error offsets are the same.  Each returns 0 (read_stored_len: LEN), E_EOF or
+// E_CORRUPT.
+
+// Re-assert wave-uniformity of the reader (no-ops at run time: every lane already holds the same
+// values) so that the symbol loop is compiled for the scalar unit.
+FLATE_D void bits_pin(Bits &b) {
+  b.roff = uni(b.roff);
+  b.ipos = uni(b.ipos);
+  b.sbase = uni(b.sbase);
+  b.buf = ((uint64_t)uni((uint32_t)(b.buf >> 32)) << 32) | uni((uint32_t)b.buf);
+  b.cnt = (int)uni((uint32_t)b.cnt);
+  b.avail = (int)uni((uint32_t)b.avail);
+}
+// fewer than kStageMargin staged bytes left in front of the reader, and more input behind the stage
+FLATE_D bool stage_low(const Bits &b) { return b.ipos + kStageMargin > b.sbase + kStage && b.sbase + kStage < b.in_len; }
+// (Re)load the kStage-byte LDS stage of the compressed input in[0, b.in_len) at b.ipos.  All lanes.
+FLATE_D void restage(Bits &b, uint32_t *stage, const uint8_t *in, int lane) {
+  __syncthreads();
+  const uint32_t base = b.ipos;
+  for (int k = lane; k < kStage / 4; k += 64) {
+    const uint32_t p = base + 4u * k;
+    uint32_t w = 0;
+    if (p + 4 <= b.in_len) {
+      w = ld32g(in + p);
+    } else {
+      for (uint32_t q = p; q < b.in_len; ++q) w |= (uint32_t)in[q] << (8 * (q - p));
+    }
+    stage[k] = w;
+  }
+  b.sbase = base;
+  __syncthreads();
+  bits_refill(b, stage);
+}
+
+// next_block (inflate.mbt:345-379): the 3-bit block header; type 3 is reserved (:375-377)
+FLATE_D int read_block_header(Bits &b, const uint32_t *stage, bool &final_block, uint32_t &typ) {
+  if (!bits_need(b, 3)) return E_EOF;
+  const uint32_t h = bits_peek(b, 3);
+  final_block = h & 1;
+  typ = h >> 1;
+  bits_drop(b, 3, stage);
+  return typ == 3 ? E_CORRUPT : 0;
+}
+
+// data_block (:708-742): the partial byte is discarded; LEN and ~LEN at byte b.roff -> LEN.  The raw
+// bytes are the caller's.
+FLATE_D int read_stored_len(Bits &b, const uint8_t *in) {
+  const uint32_t p = b.roff;
+  if (b.in_len - p < 4) {
+    b.roff = b.in_len;
+    return E_EOF;
+  }
+  b.roff = p + 4;
+  const uint32_t n = uni((uint32_t)in[p] | ((uint32_t)in[p + 1] << 8));
+  const uint32_t nn = uni((uint32_t)in[p + 2] | ((uint32_t)in[p + 3] << 8));
+  if ((nn & 0xffffu) != ((~n) & 0xffffu)) return E_CORRUPT;
+  return (int)n;
+}
+
+// The decode tables of a Huffman block of type typ (1 fixed, 2 dynamic) into sh.lit / sh.dist, with
+// sh.lens as scratch, and the code lengths huff_sym reads them with.  nlit: HLIT + 257 (dynamic
+// blocks only).  step(): the caller's own bookkeeping in front of every code-length symbol (pin, restage).
+// All lanes.
+template <class Shared, class Step>
+FLATE_D int read_tables(Bits &b, Shared &sh, uint32_t typ, int lane, Step &&step, int &lit_min, int &lit_max,
+                        int &dist_min, int &dist_max, int &nlit) {
+  if (typ == 1) {  // fixed_huffman_decoder (:886-939); distances are 5-bit codes
+    __syncthreads();
+    uint8_t *fl = sh.lens + 32;
+    for (int i = lane; i < 288; i += 64) fl[i] = i < 144 ? 8 : (i < 256 ? 9 : (i < 280 ? 7 : 8));
+    if (lane < 32) fl[288 + lane] = 5;
+    __syncthreads();
+    dec_init(sh.lit, fl, 288, lane);
+    dec_init(sh.dist, fl + 288, 32, lane);
+  } else {  // read_huffman (:429-548)
+    if (!bits_need(b, 14)) return E_EOF;
+    const uint32_t v = bits_peek(b, 14);
+    nlit = (int)(v & 31u) + 257;
+    const int ndist = (int)((v >> 5) & 31u) + 1;
+    const int nclen = (int)((v >> 10) & 15u) + 4;
+    if (nlit > kMaxLit || ndist > kMaxDist) return E_CORRUPT;
+    bits_drop(b, 14, sh.stage);
+    __syncthreads();
+    if (lane < kNumCodes) sh.lens[lane] = 0;
+    __syncthreads();
+    for (int i = 0; i < nclen; ++i) {
+      if (!bits_need(b, 3)) return E_EOF;
+      if (lane == 0) sh.lens[kCodeOrder[i]] = (uint8_t)bits_peek(b, 3);
+      bits_drop(b, 3, sh.stage);
+    }
+    __syncthreads();
+    dec_init(sh.dist, sh.lens, kNumCodes, lane);  // code-length code
+    if (!uni((uint32_t)sh.dist.ok)) return E_CORRUPT;
+    const int cmin = (int)uni((uint32_t)sh.dist.min), cmax = (int)uni((uint32_t)sh.dist.max);
+    uint8_t *cl = sh.lens + 32;
+    const int total = nlit + ndist;
+    // (the symbols leave the loop through one exit, like the copies this replaced: tighter code in the callers)
+    int i = 0, err = 0;
+    while (i < total) {  // :471-530
+      i = (int)uni((uint32_t)i);
+      step();
+      const int x = huff_sym(b, sh.dist, cmin, cmax, sh.stage, &err);
+      if (x < 0) break;
+      if (x < 16) {
+        if (lane == 0) cl[i] = (uint8_t)x;
+        ++i;
+        continue;
+      }
+      int rep, nb;
+      uint32_t fill = 0;
+      if (x == 16) {
+        rep = 3;
+        nb = 2;
+        if (i == 0) {
+          err = E_CORRUPT;
+          break;
+        }
+        __syncthreads();
+        fill = uni(cl[i - 1]);
+      } else if (x == 17) {
+        rep = 3;
+        nb = 3;
+      } else {
+        rep = 11;
+        nb = 7;
+      }
+      if (!bits_need(b, nb)) {
+        err = E_EOF;
+        break;
+      }
+      rep += (int)bits_peek(b, (uint32_t)nb);
+      bits_drop(b, nb, sh.stage);
+      if (i + rep > total) {
+        err = E_CORRUPT;
+        break;
+      }
+      if (lane < rep) cl[i + lane] = (uint8_t)fill;
+      if (lane + 64 < rep) cl[i + lane + 64] = (uint8_t)fill;
+      if (lane + 128 < rep) cl[i + lane + 128] = (uint8_t)fill;
+      i += rep;
+    }
+    if (err) return err;
+    __syncthreads();
+    dec_init(sh.lit, cl, nlit, lane);
+    dec_init(sh.dist, cl + nlit, ndist, lane);
+    if (!uni((uint32_t)sh.lit.ok) || !uni((uint32_t)sh.dist.ok)) return E_CORRUPT;
+  }
+  lit_min = (int)uni((uint32_t)sh.lit.min);
+  lit_max = (int)uni((uint32_t)sh.lit.max);
+  dist_min = (int)uni((uint32_t)sh.dist.min);
+  dist_max = (int)uni((uint32_t)sh.dist.max);
+  if (typ == 2) {  // read at least the end-of-block code's length (:542-544)
+    const int eob = (int)uni(sh.lens[32 + 256]);
+    if (lit_min < eob) lit_min = eob;
+  }
+  return 0;
+}
+
+// read_literal (:600-684): the rest of a copy token after its length symbol v >= 257 -- the length's
+// extra bits, the distance code and its extra bits.  History and capacity checks are the caller's.
+FLATE_D int read_copy(Bits &b, const Dec &dd, int dist_min, int dist_max, const uint32_t *stage, int v, int &length,
+                      int &dist) {
+  length = 0;  // (defined on the error paths too: the callers compile to tighter code)
+  dist = 0;
+  int n;
+  if (v < 265) {
+    length = v - (257 - 3);
+    n = 0;
+  } else if (v < 269) {
+    length = v * 2 - (265 * 2 - 11);
+    n = 1;
+  } else if (v < 273) {
+    length = v * 4 - (269 * 4 - 19);
+    n = 2;
+  } else if (v < 277) {
+    length = v * 8 - (273 * 8 - 35);
+    n = 3;
+  } else if (v < 281) {
+    length = v * 16 - (277 * 16 - 67);
+    n = 4;
+  } else if (v < 285) {
+    length = v * 32 - (281 * 32 - 131);
+    n = 5;
+  } else if (v < kMaxLit) {
+    length = 258;
+    n = 0;
+  } else {
+    return E_CORRUPT;
+  }
+  if (n > 0) {
+    if (!bits_need(b, n)) return E_EOF;
+    length += (int)bits_peek(b, (uint32_t)n);
+    bits_drop(b, n, stage);
+  }
+  int err = 0;
+  dist = huff_sym(b, dd, dist_min, dist_max, stage, &err);
+  if (dist < 0) return err;
+  if (dist < 4) {
+    dist += 1;
+  } else if (dist < kMaxDist) {
+    const int nb = (dist - 2) >> 1;
+    int extra = (dist & 1) << nb;
+    if (!bits_need(b, nb)) return E_EOF;
+    extra |= (int)bits_peek(b, (uint32_t)nb);
+    bits_drop(b, nb, stage);
+    dist = (1 << (nb + 1)) + 1 + extra;
+  } else {
+    return E_CORRUPT;
+  }
+  return 0;
+}
+
 }  // namespace
 
 // The wave-per-stream decoder; DICT: with the preset dictionaries of InfParams (its tail is the
@@ -242,25 +456,6 @@ FLATE_D void inflate_wave(const InfParams &P, InfShared &sh) {
   int err = 0;
   bool final_block = false;
 
-  // (re)load the LDS stage of the compressed input at b.ipos
-  auto restage = [&]() {
-    __syncthreads();
-    const uint32_t base = b.ipos;
-    for (int k = lane; k < kStage / 4; k += 64) {
-      const uint32_t p = base + 4u * k;
-      uint32_t w = 0;
-      if (p + 4 <= in_len) {
-        w = ld32g(in + p);
-      } else {
-        for (uint32_t q = p; q < in_len; ++q) w |= (uint32_t)in[q] << (8 * (q - p));
-      }
-      sh.stage[k] = w;
-    }
-    b.sbase = base;
-    __syncthreads();
-    bits_refill(b, sh.stage);
-  };
-  auto stage_low = [&]() { return b.ipos + kStageMargin > b.sbase + kStage && b.sbase + kStage < in_len; };
   // read_flush (dict-decoder.mbt:200-209): window -> HBM, coalesced
   auto flush = [&]() {
     __syncthreads();
@@ -268,19 +463,13 @@ FLATE_D void inflate_wave(const InfParams &P, InfShared &sh) {
       for (uint32_t i = fpos + lane; i < opos; i += 64) out[i] = sh.win[i & (kWin - 1)];
     fpos = opos;
   };
-
-  // Re-assert wave-uniformity of the decoder state (no-ops at run time: every lane already holds
-  // the same values) so that the symbol loop is compiled for the scalar unit.
-  auto pin = [&]() {
-    b.roff = uni(b.roff);
-    b.ipos = uni(b.ipos);
-    b.sbase = uni(b.sbase);
-    b.buf = ((uint64_t)uni((uint32_t)(b.buf >> 32)) << 32) | uni((uint32_t)b.buf);
-    b.cnt = (int)uni((uint32_t)b.cnt);
-    b.avail = (int)uni((uint32_t)b.avail);
+  // in front of every symbol: the state pinned to the scalar unit (bits_pin), the stage refilled
+  auto step = [&]() {
+    bits_pin(b);
     opos = uni(opos);
     fpos = uni(fpos);
     err = (int)uni((uint32_t)err);
+    if (stage_low(b)) restage(b, sh.stage, in, lane);
   };
 
   uint32_t dict_len = 0;
@@ -289,34 +478,15 @@ FLATE_D void inflate_wave(const InfParams &P, InfShared &sh) {
     const uint8_t *tail = P.dict_buf + P.dict_at[sid];
     for (uint32_t i = lane; i < dict_len; i += 64) sh.win[(i - dict_len) & (kWin - 1)] = tail[i];
   }
-  restage();  // (its barrier also publishes the dictionary)
+  restage(b, sh.stage, in, lane);  // (its barrier also publishes the dictionary)
   while (!final_block && !err) {  // next_block (inflate.mbt:345-379)
-    pin();
-    if (stage_low()) restage();
-    if (!bits_need(b, 3)) {
-      err = E_EOF;
-      break;
-    }
-    const uint32_t h = bits_peek(b, 3);
-    final_block = h & 1;
-    const uint32_t typ = h >> 1;
-    bits_drop(b, 3, sh.stage);
-    if (typ == 3) {
-      err = E_CORRUPT;  // reserved (:375-377)
-      break;
-    }
+    step();
+    uint32_t typ;
+    if ((err = read_block_header(b, sh.stage, final_block, typ))) break;
     if (typ == 0) {  // data_block (:708-766): discard the partial byte, LEN, ~LEN, raw bytes
-      const uint32_t p = b.roff;
-      if (in_len - p < 4) {
-        b.roff = in_len;
-        err = E_EOF;
-        break;
-      }
-      b.roff = p + 4;
-      const uint32_t n = uni((uint32_t)in[p] | ((uint32_t)in[p + 1] << 8));
-      const uint32_t nn = uni((uint32_t)in[p + 2] | ((uint32_t)in[p + 3] << 8));
-      if ((nn & 0xffffu) != ((~n) & 0xffffu)) {
-        err = E_CORRUPT;
+      const int n = read_stored_len(b, in);
+      if (n < 0) {
+        err = n;
         break;
       }
       flush();
@@ -342,118 +512,14 @@ FLATE_D void inflate_wave(const InfParams &P, InfShared &sh) {
       b.buf = 0;
       b.cnt = 0;
       b.avail = 0;
-      restage();
+      restage(b, sh.stage, in, lane);
       continue;
     }
-    int lit_min, lit_max, dist_min, dist_max;
-    if (typ == 1) {  // fixed_huffman_decoder (:886-939); distances are 5-bit codes
-      __syncthreads();
-      uint8_t *fl = sh.lens + 32;
-      for (int i = lane; i < 288; i += 64) fl[i] = i < 144 ? 8 : (i < 256 ? 9 : (i < 280 ? 7 : 8));
-      if (lane < 32) fl[288 + lane] = 5;
-      __syncthreads();
-      dec_init(sh.lit, fl, 288, lane);
-      dec_init(sh.dist, fl + 288, 32, lane);
-    } else {  // read_huffman (:429-548)
-      if (!bits_need(b, 14)) {
-        err = E_EOF;
-        break;
-      }
-      const uint32_t v = bits_peek(b, 14);
-      const int nlit = (int)(v & 31u) + 257, ndist = (int)((v >> 5) & 31u) + 1;
-      const int nclen = (int)((v >> 10) & 15u) + 4;
-      if (nlit > kMaxLit || ndist > kMaxDist) {
-        err = E_CORRUPT;
-        break;
-      }
-      bits_drop(b, 14, sh.stage);
-      __syncthreads();
-      if (lane < kNumCodes) sh.lens[lane] = 0;
-      __syncthreads();
-      for (int i = 0; i < nclen && !err; ++i) {
-        if (!bits_need(b, 3)) {
-          err = E_EOF;
-          break;
-        }
-        if (lane == 0) sh.lens[kCodeOrder[i]] = (uint8_t)bits_peek(b, 3);
-        bits_drop(b, 3, sh.stage);
-      }
-      if (err) break;
-      __syncthreads();
-      dec_init(sh.dist, sh.lens, kNumCodes, lane);  // code-length code
-      if (!uni((uint32_t)sh.dist.ok)) {
-        err = E_CORRUPT;
-        break;
-      }
-      const int cmin = (int)uni((uint32_t)sh.dist.min), cmax = (int)uni((uint32_t)sh.dist.max);
-      uint8_t *cl = sh.lens + 32;
-      const int total = nlit + ndist;
-      int i = 0;
-      while (i < total) {  // :471-530
-        pin();
-        i = (int)uni((uint32_t)i);
-        if (stage_low()) restage();
-        const int x = huff_sym(b, sh.dist, cmin, cmax, sh.stage, &err);
-        if (x < 0) break;
-        if (x < 16) {
-          if (lane == 0) cl[i] = (uint8_t)x;
-          ++i;
-          continue;
-        }
-        int rep, nb;
-        uint32_t fill = 0;
-        if (x == 16) {
-          rep = 3;
-          nb = 2;
-          if (i == 0) {
-            err = E_CORRUPT;
-            break;
-          }
-          __syncthreads();
-          fill = uni(cl[i - 1]);
-        } else if (x == 17) {
-          rep = 3;
-          nb = 3;
-        } else {
-          rep = 11;
-          nb = 7;
-        }
-        if (!bits_need(b, nb)) {
-          err = E_EOF;
-          break;
-        }
-        rep += (int)bits_peek(b, (uint32_t)nb);
-        bits_drop(b, nb, sh.stage);
-        if (i + rep > total) {
-          err = E_CORRUPT;
-          break;
-        }
-        if (lane < rep) cl[i + lane] = (uint8_t)fill;
-        if (lane + 64 < rep) cl[i + lane + 64] = (uint8_t)fill;
-        if (lane + 128 < rep) cl[i + lane + 128] = (uint8_t)fill;
-        i += rep;
-      }
-      if (err) break;
-      __syncthreads();
-      dec_init(sh.lit, cl, nlit, lane);
-      dec_init(sh.dist, cl + nlit, ndist, lane);
-      if (!uni((uint32_t)sh.lit.ok) || !uni((uint32_t)sh.dist.ok)) {
-        err = E_CORRUPT;
-        break;
-      }
-    }
-    lit_min = (int)uni((uint32_t)sh.lit.min);
-    lit_max = (int)uni((uint32_t)sh.lit.max);
-    dist_min = (int)uni((uint32_t)sh.dist.min);
-    dist_max = (int)uni((uint32_t)sh.dist.max);
-    if (typ == 2) {  // read at least the end-of-block code's length (:542-544)
-      const int eob = (int)uni(sh.lens[32 + 256]);
-      if (lit_min < eob) lit_min = eob;
-    }
+    int lit_min, lit_max, dist_min, dist_max, nlit;
+    if ((err = read_tables(b, sh, typ, lane, step, lit_min, lit_max, dist_min, dist_max, nlit))) break;
 
     for (;;) {  // read_literal (:565-684)
-      pin();
-      if (stage_low()) restage();
+      step();
       if (opos - fpos >= (uint32_t)kFlushAt) flush();
       const int v = huff_sym(b, sh.lit, lit_min, lit_max, sh.stage, &err);
       if (v < 0) break;
@@ -467,58 +533,8 @@ FLATE_D void inflate_wave(const InfParams &P, InfShared &sh) {
         continue;
       }
       if (v == 256) break;  // finish_block
-      int length, n;
-      if (v < 265) {
-        length = v - (257 - 3);
-        n = 0;
-      } else if (v < 269) {
-        length = v * 2 - (265 * 2 - 11);
-        n = 1;
-      } else if (v < 273) {
-        length = v * 4 - (269 * 4 - 19);
-        n = 2;
-      } else if (v < 277) {
-        length = v * 8 - (273 * 8 - 35);
-        n = 3;
-      } else if (v < 281) {
-        length = v * 16 - (277 * 16 - 67);
-        n = 4;
-      } else if (v < 285) {
-        length = v * 32 - (281 * 32 - 131);
-        n = 5;
-      } else if (v < kMaxLit) {
-        length = 258;
-        n = 0;
-      } else {
-        err = E_CORRUPT;
-        break;
-      }
-      if (n > 0) {
-        if (!bits_need(b, n)) {
-          err = E_EOF;
-          break;
-        }
-        length += (int)bits_peek(b, (uint32_t)n);
-        bits_drop(b, n, sh.stage);
-      }
-      int dist = huff_sym(b, sh.dist, dist_min, dist_max, sh.stage, &err);
-      if (dist < 0) break;
-      if (dist < 4) {
-        dist += 1;
-      } else if (dist < kMaxDist) {
-        const int nb = (dist - 2) >> 1;
-        int extra = (dist & 1) << nb;
-        if (!bits_need(b, nb)) {
-          err = E_EOF;
-          break;
-        }
-        extra |= (int)bits_peek(b, (uint32_t)nb);
-        bits_drop(b, nb, sh.stage);
-        dist = (1 << (nb + 1)) + 1 + extra;
-      } else {
-        err = E_CORRUPT;
-        break;
-      }
+      int length, dist;
+      if ((err = read_copy(b, sh.dist, dist_min, dist_max, sh.stage, v, length, dist))) break;
       uint32_t hist = opos < (uint32_t)kWin ? opos : (uint32_t)kWin;  // hist_size
       if constexpr (DICT) hist = opos < (uint32_t)kWin - dict_len ? opos + dict_len : (uint32_t)kWin;
       if ((uint32_t)dist > hist) {

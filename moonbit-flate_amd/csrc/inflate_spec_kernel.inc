@@ -1,5 +1,6 @@
 // inflate_spec_kernel.inc -- included by inflate_kernels.hip (inside namespace flate, after the
-// wave-per-stream kernel whose helpers it shares: Dec, dec_init, Bits, huff_sym, uni, ld32g).
+// wave-per-stream kernel whose helpers it shares: Dec, dec_init, Bits, huff_sym and the reader steps
+// next to it, uni, ld32g).
 //
 // Third inflater: one WAVEFRONT per stream, 64 sub-blocks of the bit stream decoded at once.
 //
@@ -24,9 +25,10 @@
 // What stays exactly the reference's (inflate.mbt:345-854, dict-decoder.mbt:114-185):
 //  * block headers, table construction, stored blocks, and every irregular token -- end of block,
 //    an invalid code, a distance beyond the history, the end of the input or of the output slot --
-//    go through the SAME one-symbol-at-a-time reader as the kernel above (huff_sym on Bits), so
-//    accept / reject decisions and error offsets cannot differ: a lane whose list would contain
-//    such a token ends the batch in front of itself;
+//    go through the SAME one-symbol-at-a-time reader as the kernel above (huff_sym and the reader
+//    steps next to it in inflate_kernels.hip, on Bits), so accept / reject decisions and error
+//    offsets cannot differ: a lane whose list would contain such a token ends the batch in front of
+//    itself;
 //  * the fast path only runs where none of that can happen (every token it takes lies >= 64 bits in
 //    front of the end of the input); it keeps the byte-at-a-time reader's `roffset`
 //    (inflate.mbt:260,789,818-831) up to date as the bytes the bit requests of the last token taken
@@ -269,17 +271,16 @@ FLATE_D void inflate_spec(const InfParams &P, SpecShared<SUB, CAP, RING> &sh) {
     bits_at(bp);
   };
   auto bit_pos = [&]() { return 8u * b.ipos - (uint32_t)b.cnt; };
-  auto stage_low = [&]() { return b.ipos + kStageMargin > b.sbase + kStage && b.sbase + kStage < in_len; };
   auto pin = [&]() {
-    b.roff = uni(b.roff);
-    b.ipos = uni(b.ipos);
-    b.sbase = uni(b.sbase);
-    b.buf = ((uint64_t)uni((uint32_t)(b.buf >> 32)) << 32) | uni((uint32_t)b.buf);
-    b.cnt = (int)uni((uint32_t)b.cnt);
-    b.avail = (int)uni((uint32_t)b.avail);
+    bits_pin(b);
     opos = uni(opos);
     done_pos = uni(done_pos);
     err = (int)uni((uint32_t)err);
+  };
+  // in front of every code-length symbol (read_tables)
+  auto step = [&]() {
+    pin();
+    if (stage_low(b)) restage_at(bit_pos());
   };
 
   // Bytes of history older than the LDS ring come back from the output buffer itself (written by
@@ -405,31 +406,13 @@ FLATE_D void inflate_spec(const InfParams &P, SpecShared<SUB, CAP, RING> &sh) {
       if (bit_pos() != stop_bit) err = E_CORRUPT;    // the index does not point at a block boundary
       break;
     }
-    if (stage_low()) restage_at(bit_pos());
-    if (!bits_need(b, 3)) {
-      err = E_EOF;
-      break;
-    }
-    const uint32_t h = bits_peek(b, 3);
-    final_block = h & 1;
-    const uint32_t typ = h >> 1;
-    bits_drop(b, 3, sh.stage);
-    if (typ == 3) {
-      err = E_CORRUPT;  // reserved (:375-377)
-      break;
-    }
+    if (stage_low(b)) restage_at(bit_pos());
+    uint32_t typ;
+    if ((err = read_block_header(b, sh.stage, final_block, typ))) break;
     if (typ == 0) {  // data_block (:708-766): discard the partial byte, LEN, ~LEN, raw bytes
-      const uint32_t p = b.roff;
-      if (in_len - p < 4) {
-        b.roff = in_len;
-        err = E_EOF;
-        break;
-      }
-      b.roff = p + 4;
-      const uint32_t n = uni((uint32_t)in[p] | ((uint32_t)in[p + 1] << 8));
-      const uint32_t nn = uni((uint32_t)in[p + 2] | ((uint32_t)in[p + 3] << 8));
-      if ((nn & 0xffffu) != ((~n) & 0xffffu)) {
-        err = E_CORRUPT;
+      const int n = read_stored_len(b, in);
+      if (n < 0) {
+        err = n;
         break;
       }
       const uint32_t ip = b.roff, avail = in_len - ip;
@@ -480,119 +463,17 @@ FLATE_D void inflate_spec(const InfParams &P, SpecShared<SUB, CAP, RING> &sh) {
       SPEC_STAT(st_chdr += __builtin_readcyclecounter());
       continue;
     }
-    int lit_min, lit_max, dist_min, dist_max;
-    bool lit_only = false;  // a dynamic block whose literal/length code stops at the end-of-block symbol
-    if (typ == 1) {  // fixed_huffman_decoder (:886-939); distances are 5-bit codes
-      __syncthreads();
-      uint8_t *fl = sh.lens + 32;
-      for (int i = lane; i < 288; i += 64) fl[i] = i < 144 ? 8 : (i < 256 ? 9 : (i < 280 ? 7 : 8));
-      if (lane < 32) fl[288 + lane] = 5;
-      __syncthreads();
-      dec_init(sh.lit, fl, 288, lane);
-      dec_init(sh.dist, fl + 288, 32, lane);
-    } else {  // read_huffman (:429-548)
-      if (!bits_need(b, 14)) {
-        err = E_EOF;
-        break;
-      }
-      const uint32_t v = bits_peek(b, 14);
-      const int nlit = (int)(v & 31u) + 257, ndist = (int)((v >> 5) & 31u) + 1;
-      const int nclen = (int)((v >> 10) & 15u) + 4;
-      if (nlit > kMaxLit || ndist > kMaxDist) {
-        err = E_CORRUPT;
-        break;
-      }
-      bits_drop(b, 14, sh.stage);
-      lit_only = nlit == 257;  // (write_block_huff, huffman-bit-writer.mbt:738-824: num_literals = 257)
-      __syncthreads();
-      if (lane < kNumCodes) sh.lens[lane] = 0;
-      __syncthreads();
-      for (int i = 0; i < nclen && !err; ++i) {
-        if (!bits_need(b, 3)) {
-          err = E_EOF;
-          break;
-        }
-        if (lane == 0) sh.lens[kCodeOrder[i]] = (uint8_t)bits_peek(b, 3);
-        bits_drop(b, 3, sh.stage);
-      }
-      if (err) break;
-      __syncthreads();
-      dec_init(sh.dist, sh.lens, kNumCodes, lane);  // code-length code
-      if (!uni((uint32_t)sh.dist.ok)) {
-        err = E_CORRUPT;
-        break;
-      }
-      const int cmin = (int)uni((uint32_t)sh.dist.min), cmax = (int)uni((uint32_t)sh.dist.max);
-      uint8_t *cl = sh.lens + 32;
-      const int total = nlit + ndist;
-      int i = 0;
-      while (i < total) {  // :471-530
-        pin();
-        i = (int)uni((uint32_t)i);
-        if (stage_low()) restage_at(bit_pos());
-        const int x = huff_sym(b, sh.dist, cmin, cmax, sh.stage, &err);
-        if (x < 0) break;
-        if (x < 16) {
-          if (lane == 0) cl[i] = (uint8_t)x;
-          ++i;
-          continue;
-        }
-        int rep, nb;
-        uint32_t fill = 0;
-        if (x == 16) {
-          rep = 3;
-          nb = 2;
-          if (i == 0) {
-            err = E_CORRUPT;
-            break;
-          }
-          __syncthreads();
-          fill = uni(cl[i - 1]);
-        } else if (x == 17) {
-          rep = 3;
-          nb = 3;
-        } else {
-          rep = 11;
-          nb = 7;
-        }
-        if (!bits_need(b, nb)) {
-          err = E_EOF;
-          break;
-        }
-        rep += (int)bits_peek(b, (uint32_t)nb);
-        bits_drop(b, nb, sh.stage);
-        if (i + rep > total) {
-          err = E_CORRUPT;
-          break;
-        }
-        if (lane < rep) cl[i + lane] = (uint8_t)fill;
-        if (lane + 64 < rep) cl[i + lane + 64] = (uint8_t)fill;
-        if (lane + 128 < rep) cl[i + lane + 128] = (uint8_t)fill;
-        i += rep;
-      }
-      if (err) break;
-      __syncthreads();
-      SPEC_STAT(st_cinit -= __builtin_readcyclecounter());
-      dec_init(sh.lit, cl, nlit, lane);
-      dec_init(sh.dist, cl + nlit, ndist, lane);
-      if (!uni((uint32_t)sh.lit.ok) || !uni((uint32_t)sh.dist.ok)) {
-        err = E_CORRUPT;
-        break;
-      }
-    }
-    lit_min = (int)uni((uint32_t)sh.lit.min);
-    lit_max = (int)uni((uint32_t)sh.lit.max);
-    dist_min = (int)uni((uint32_t)sh.dist.min);
-    dist_max = (int)uni((uint32_t)sh.dist.max);
-    if (typ == 2) {  // read at least the end-of-block code's length (:542-544)
-      const int eob = (int)uni(sh.lens[32 + 256]);
-      if (lit_min < eob) lit_min = eob;
-    }
+    int lit_min, lit_max, dist_min, dist_max, nlit;
+    SPEC_STAT(st_cinit -= __builtin_readcyclecounter());  // (stats build: the whole tables read, either block type)
+    if ((err = read_tables(b, sh, typ, lane, step, lit_min, lit_max, dist_min, dist_max, nlit))) break;
+    // a dynamic block whose literal/length code stops at the end-of-block symbol
+    // (write_block_huff, huffman-bit-writer.mbt:738-824: num_literals = 257)
+    const bool lit_only = typ == 2 && nlit == 257;
 
     for (int i = lane; i < kPrimSize; i += 64) sh.lit32[i] = spec_lit_entry(sh.lit.prim[i], true);
     __syncthreads();
     SPEC_STAT(st_chdr += __builtin_readcyclecounter());
-    SPEC_STAT(st_cinit += typ == 2 ? __builtin_readcyclecounter() : 0);
+    SPEC_STAT(st_cinit += __builtin_readcyclecounter());
     for (;;) {  // read_literal (:565-684)
       pin();
       // ------------------------------ literal runs --------------------------------------
@@ -1007,7 +888,7 @@ FLATE_D void inflate_spec(const InfParams &P, SpecShared<SUB, CAP, RING> &sh) {
         }
       }
       // ------------------------------ one token, exactly --------------------------------
-      if (stage_low()) restage_at(bit_pos());
+      if (stage_low(b)) restage_at(bit_pos());
       const int v = huff_sym(b, sh.lit, lit_min, lit_max, sh.stage, &err);
       SPEC_STAT(++st_exact);
       if (v < 0) break;
@@ -1021,58 +902,8 @@ FLATE_D void inflate_spec(const InfParams &P, SpecShared<SUB, CAP, RING> &sh) {
         continue;
       }
       if (v == 256) break;  // finish_block
-      int length, n;
-      if (v < 265) {
-        length = v - (257 - 3);
-        n = 0;
-      } else if (v < 269) {
-        length = v * 2 - (265 * 2 - 11);
-        n = 1;
-      } else if (v < 273) {
-        length = v * 4 - (269 * 4 - 19);
-        n = 2;
-      } else if (v < 277) {
-        length = v * 8 - (273 * 8 - 35);
-        n = 3;
-      } else if (v < 281) {
-        length = v * 16 - (277 * 16 - 67);
-        n = 4;
-      } else if (v < 285) {
-        length = v * 32 - (281 * 32 - 131);
-        n = 5;
-      } else if (v < kMaxLit) {
-        length = 258;
-        n = 0;
-      } else {
-        err = E_CORRUPT;
-        break;
-      }
-      if (n > 0) {
-        if (!bits_need(b, n)) {
-          err = E_EOF;
-          break;
-        }
-        length += (int)bits_peek(b, (uint32_t)n);
-        bits_drop(b, n, sh.stage);
-      }
-      int dist = huff_sym(b, sh.dist, dist_min, dist_max, sh.stage, &err);
-      if (dist < 0) break;
-      if (dist < 4) {
-        dist += 1;
-      } else if (dist < kMaxDist) {
-        const int nb = (dist - 2) >> 1;
-        int extra = (dist & 1) << nb;
-        if (!bits_need(b, nb)) {
-          err = E_EOF;
-          break;
-        }
-        extra |= (int)bits_peek(b, (uint32_t)nb);
-        bits_drop(b, nb, sh.stage);
-        dist = (1 << (nb + 1)) + 1 + extra;
-      } else {
-        err = E_CORRUPT;
-        break;
-      }
+      int length, dist;
+      if ((err = read_copy(b, sh.dist, dist_min, dist_max, sh.stage, v, length, dist))) break;
       const uint32_t hist = opos < (uint32_t)kWin - dict_len ? opos + dict_len : (uint32_t)kWin;  // hist_size
       if ((uint32_t)dist > hist) {
         err = E_CORRUPT;

@@ -1,5 +1,6 @@
 // inflate_stream_kernel.inc -- ONE long DEFLATE stream decoded in pieces (included by
-// inflate_kernels.hip: it uses that file's decoder tables, bit reader and huff_sym).
+// inflate_kernels.hip: it uses that file's decoder tables, bit reader, huff_sym and the reader steps
+// next to it -- read_block_header, read_stored_len, read_tables, read_copy, restage).
 //
 // The reference's Decompressor is resumable: read() runs the step functions until the 32 KiB
 // window has something to hand out and remembers where it stopped -- step / step_state, the bit
@@ -100,52 +101,32 @@ __global__ __launch_bounds__(64) void inflate_stream_kernel(void *state, const u
   const uint32_t hist0 = h.total_out + h.dict_len >= (uint64_t)kWin ? (uint32_t)kWin : (uint32_t)h.total_out + h.dict_len;
   int err = 0;
   bool suspend = false;
-  uint32_t phase = h.phase, final_block = h.final_block, stored_left = h.stored_left;
+  uint32_t phase = h.phase, stored_left = h.stored_left;
+  bool final_block = h.final_block != 0;
   uint32_t copy_left = h.copy_left, copy_dist = h.copy_dist;
   int lit_min = h.lit_min, lit_max = h.lit_max, dist_min = h.dist_min, dist_max = h.dist_max;
   bool done = false;
 
-  auto restage = [&]() {
-    __syncthreads();
-    const uint32_t base = b.ipos;
-    for (int k = lane; k < kStage / 4; k += 64) {
-      const uint32_t p = base + 4u * k;
-      uint32_t w = 0;
-      if (p + 4 <= in_len) {
-        w = ld32g(in + p);
-      } else {
-        for (uint32_t q = p; q < in_len; ++q) w |= (uint32_t)in[q] << (8 * (q - p));
-      }
-      sh.stage[k] = w;
-    }
-    b.sbase = base;
-    __syncthreads();
-    bits_refill(b, sh.stage);
-  };
-  auto stage_low = [&]() { return b.ipos + kStageMargin > b.sbase + kStage && b.sbase + kStage < in_len; };
   auto flush = [&]() {
     __syncthreads();
     for (uint32_t i = fpos + lane; i < opos; i += 64) out[i] = sh.win[(wbase + i) & (kWin - 1)];
     fpos = opos;
   };
-  auto pin = [&]() {
-    b.roff = uni(b.roff);
-    b.ipos = uni(b.ipos);
-    b.sbase = uni(b.sbase);
-    b.buf = ((uint64_t)uni((uint32_t)(b.buf >> 32)) << 32) | uni((uint32_t)b.buf);
-    b.cnt = (int)uni((uint32_t)b.cnt);
-    b.avail = (int)uni((uint32_t)b.avail);
+  // in front of every symbol: the state pinned to the scalar unit (bits_pin), the stage refilled
+  auto step = [&]() {
+    bits_pin(b);
     opos = uni(opos);
     fpos = uni(fpos);
     err = (int)uni((uint32_t)err);
     phase = uni(phase);
     copy_left = uni(copy_left);
     stored_left = uni(stored_left);
+    if (stage_low(b)) restage(b, sh.stage, in, lane);
   };
   // bits of the presented input that are not consumed yet
   auto bits_left = [&]() -> int64_t { return 8ll * (int64_t)in_len - (8ll * (int64_t)b.roff - (int64_t)b.avail); };
 
-  restage();
+  restage(b, sh.stage, in, lane);
   if (bib) {  // the consumed bits of the first byte
     b.buf >>= bib;
     b.cnt -= (int)bib;
@@ -153,8 +134,7 @@ __global__ __launch_bounds__(64) void inflate_stream_kernel(void *state, const u
   }
 
   while (!err && !suspend && !done) {
-    pin();
-    if (stage_low()) restage();
+    step();
     if (opos - fpos >= (uint32_t)kFlushAt) flush();
 
     if (copy_left) {  // copy_history (inflate.mbt:689-704): as much as the output takes
@@ -195,7 +175,7 @@ __global__ __launch_bounds__(64) void inflate_stream_kernel(void *state, const u
         b.buf = 0;
         b.cnt = 0;
         b.avail = 0;
-        restage();
+        restage(b, sh.stage, in, lane);
         if (final_block) done = true;  // finish_block (:769-777)
       } else if (b.roff == in_len || opos == out_cap) {
         if (b.roff == in_len && final_in && opos < out_cap) {
@@ -212,30 +192,12 @@ __global__ __launch_bounds__(64) void inflate_stream_kernel(void *state, const u
         suspend = true;
         break;
       }
-      if (!bits_need(b, 3)) {
-        err = E_EOF;
-        break;
-      }
-      const uint32_t hd = bits_peek(b, 3);
-      final_block = hd & 1;
-      const uint32_t typ = hd >> 1;
-      bits_drop(b, 3, sh.stage);
-      if (typ == 3) {
-        err = E_CORRUPT;
-        break;
-      }
+      uint32_t typ;
+      if ((err = read_block_header(b, sh.stage, final_block, typ))) break;
       if (typ == 0) {  // data_block (:708-742)
-        const uint32_t p = b.roff;
-        if (in_len - p < 4) {
-          b.roff = in_len;
-          err = E_EOF;
-          break;
-        }
-        b.roff = p + 4;
-        const uint32_t n = uni((uint32_t)in[p] | ((uint32_t)in[p + 1] << 8));
-        const uint32_t nn = uni((uint32_t)in[p + 2] | ((uint32_t)in[p + 3] << 8));
-        if ((nn & 0xffffu) != ((~n) & 0xffffu)) {
-          err = E_CORRUPT;
+        const int n = read_stored_len(b, in);
+        if (n < 0) {
+          err = n;
           break;
         }
         b.avail = 0;  // "discard current half-byte"
@@ -243,7 +205,7 @@ __global__ __launch_bounds__(64) void inflate_stream_kernel(void *state, const u
           b.ipos = b.roff;
           b.buf = 0;
           b.cnt = 0;
-          restage();
+          restage(b, sh.stage, in, lane);
           if (final_block) done = true;
         } else {
           stored_left = n;
@@ -251,110 +213,8 @@ __global__ __launch_bounds__(64) void inflate_stream_kernel(void *state, const u
         }
         continue;
       }
-      if (typ == 1) {  // fixed_huffman_decoder (:886-939)
-        __syncthreads();
-        uint8_t *fl = sh.lens + 32;
-        for (int i = lane; i < 288; i += 64) fl[i] = i < 144 ? 8 : (i < 256 ? 9 : (i < 280 ? 7 : 8));
-        if (lane < 32) fl[288 + lane] = 5;
-        __syncthreads();
-        dec_init(sh.lit, fl, 288, lane);
-        dec_init(sh.dist, fl + 288, 32, lane);
-      } else {  // read_huffman (:429-548)
-        if (!bits_need(b, 14)) {
-          err = E_EOF;
-          break;
-        }
-        const uint32_t v = bits_peek(b, 14);
-        const int nlit = (int)(v & 31u) + 257, ndist = (int)((v >> 5) & 31u) + 1;
-        const int nclen = (int)((v >> 10) & 15u) + 4;
-        if (nlit > kMaxLit || ndist > kMaxDist) {
-          err = E_CORRUPT;
-          break;
-        }
-        bits_drop(b, 14, sh.stage);
-        __syncthreads();
-        if (lane < kNumCodes) sh.lens[lane] = 0;
-        __syncthreads();
-        for (int i = 0; i < nclen && !err; ++i) {
-          if (!bits_need(b, 3)) {
-            err = E_EOF;
-            break;
-          }
-          if (lane == 0) sh.lens[kCodeOrder[i]] = (uint8_t)bits_peek(b, 3);
-          bits_drop(b, 3, sh.stage);
-        }
-        if (err) break;
-        __syncthreads();
-        dec_init(sh.dist, sh.lens, kNumCodes, lane);  // code-length code
-        if (!uni((uint32_t)sh.dist.ok)) {
-          err = E_CORRUPT;
-          break;
-        }
-        const int cmin = (int)uni((uint32_t)sh.dist.min), cmax = (int)uni((uint32_t)sh.dist.max);
-        uint8_t *cl = sh.lens + 32;
-        const int total = nlit + ndist;
-        int i = 0;
-        while (i < total) {  // :471-530
-          pin();
-          i = (int)uni((uint32_t)i);
-          if (stage_low()) restage();
-          const int x = huff_sym(b, sh.dist, cmin, cmax, sh.stage, &err);
-          if (x < 0) break;
-          if (x < 16) {
-            if (lane == 0) cl[i] = (uint8_t)x;
-            ++i;
-            continue;
-          }
-          int rep, nb;
-          uint32_t fill = 0;
-          if (x == 16) {
-            rep = 3;
-            nb = 2;
-            if (i == 0) {
-              err = E_CORRUPT;
-              break;
-            }
-            __syncthreads();
-            fill = uni(cl[i - 1]);
-          } else if (x == 17) {
-            rep = 3;
-            nb = 3;
-          } else {
-            rep = 11;
-            nb = 7;
-          }
-          if (!bits_need(b, nb)) {
-            err = E_EOF;
-            break;
-          }
-          rep += (int)bits_peek(b, (uint32_t)nb);
-          bits_drop(b, nb, sh.stage);
-          if (i + rep > total) {
-            err = E_CORRUPT;
-            break;
-          }
-          if (lane < rep) cl[i + lane] = (uint8_t)fill;
-          if (lane + 64 < rep) cl[i + lane + 64] = (uint8_t)fill;
-          if (lane + 128 < rep) cl[i + lane + 128] = (uint8_t)fill;
-          i += rep;
-        }
-        if (err) break;
-        __syncthreads();
-        dec_init(sh.lit, cl, nlit, lane);
-        dec_init(sh.dist, cl + nlit, ndist, lane);
-        if (!uni((uint32_t)sh.lit.ok) || !uni((uint32_t)sh.dist.ok)) {
-          err = E_CORRUPT;
-          break;
-        }
-      }
-      lit_min = (int)uni((uint32_t)sh.lit.min);
-      lit_max = (int)uni((uint32_t)sh.lit.max);
-      dist_min = (int)uni((uint32_t)sh.dist.min);
-      dist_max = (int)uni((uint32_t)sh.dist.max);
-      if (typ == 2) {  // read at least the end-of-block code's length (:542-544)
-        const int eob = (int)uni(sh.lens[32 + 256]);
-        if (lit_min < eob) lit_min = eob;
-      }
+      int nlit;
+      if ((err = read_tables(b, sh, typ, lane, step, lit_min, lit_max, dist_min, dist_max, nlit))) break;
       phase = 1;
       continue;
     }
@@ -387,58 +247,8 @@ __global__ __launch_bounds__(64) void inflate_stream_kernel(void *state, const u
       suspend = true;
       break;
     }
-    int length, n;
-    if (v < 265) {
-      length = v - (257 - 3);
-      n = 0;
-    } else if (v < 269) {
-      length = v * 2 - (265 * 2 - 11);
-      n = 1;
-    } else if (v < 273) {
-      length = v * 4 - (269 * 4 - 19);
-      n = 2;
-    } else if (v < 277) {
-      length = v * 8 - (273 * 8 - 35);
-      n = 3;
-    } else if (v < 281) {
-      length = v * 16 - (277 * 16 - 67);
-      n = 4;
-    } else if (v < 285) {
-      length = v * 32 - (281 * 32 - 131);
-      n = 5;
-    } else if (v < kMaxLit) {
-      length = 258;
-      n = 0;
-    } else {
-      err = E_CORRUPT;
-      break;
-    }
-    if (n > 0) {
-      if (!bits_need(b, n)) {
-        err = E_EOF;
-        break;
-      }
-      length += (int)bits_peek(b, (uint32_t)n);
-      bits_drop(b, n, sh.stage);
-    }
-    int dist = huff_sym(b, sh.dist, dist_min, dist_max, sh.stage, &err);
-    if (dist < 0) break;
-    if (dist < 4) {
-      dist += 1;
-    } else if (dist < kMaxDist) {
-      const int nb = (dist - 2) >> 1;
-      int extra = (dist & 1) << nb;
-      if (!bits_need(b, nb)) {
-        err = E_EOF;
-        break;
-      }
-      extra |= (int)bits_peek(b, (uint32_t)nb);
-      bits_drop(b, nb, sh.stage);
-      dist = (1 << (nb + 1)) + 1 + extra;
-    } else {
-      err = E_CORRUPT;
-      break;
-    }
+    int length, dist;
+    if ((err = read_copy(b, sh.dist, dist_min, dist_max, sh.stage, v, length, dist))) break;
     uint32_t hist = hist0 + opos;  // hist_size (dict-decoder.mbt:63-69)
     if (hist > (uint32_t)kWin || hist < opos) hist = (uint32_t)kWin;
     if ((uint32_t)dist > hist) {
