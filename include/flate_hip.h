@@ -165,6 +165,41 @@ int flate_hip_deflate_fast_batch(flate_hip_ctx *ctx, const uint8_t *in,
                                  uint8_t *out, uint64_t out_cap, uint64_t *out_off,
                                  uint32_t flags);
 
+/* The same with PRESET DICTIONARIES as history: stream i is compressed as if its Writer had been handed its
+ * dictionary first without producing output, and can only be read by a Reader initialised with the same dictionary
+ * (&Reader::new_dict, flate_hip_inflate_batch_dict, zlib's inflateSetDictionary).  This is what the doc comment of
+ * the reference's Writer::new_dict promises and Go / zlib implement; the reference's CODE (writer.mbt:25-31,
+ * deflate.mbt:108-151) compresses the dictionary into the output as data, and the host mirror
+ * flate_host::Writer::new_dict keeps doing that.  Exactly: d = the last 32768 bytes of the dictionary; a fresh
+ * DeflateFast runs encode(d) once and its tokens are dropped (deflate-fast.mbt:123-270: the table holds what the
+ * greedy parser inserts, `cur` advances by len(d)); the payload then goes through the unchanged Compressor driver
+ * (65535-byte windows, enc_speed's size policy, close).  Consequences of that policy, kept as they are:
+ *   - a dictionary of fewer than 17 bytes (after the cut) has no effect at all (:136-140);
+ *   - a payload of fewer than 128 bytes gets nothing from its dictionary (deflate.mbt:243: it never reaches the
+ *     match finder), and a final window of fewer than 128 bytes likewise;
+ *   - with FLATE_HIP_COMPAT_GO matches extend into the dictionary and may run from the dictionary on into the
+ *     payload (match_len's third regime, :335-341): the USEFUL mode.  Without it `prev` is empty: a
+ *     candidate inside the dictionary yields a match of exactly length 4; the output is valid but usually LARGER
+ *     than without a dictionary.
+ * The dictionary arguments mean what they mean in flate_hip_inflate_batch_dict (a table of dictionaries,
+ * dict_of[i] or FLATE_HIP_NO_DICT, dict_of == NULL = every stream uses dictionary 0, dicts host or device with
+ * FLATE_HIP_DEVICE_PTRS) and get the same checks (FLATE_HIP_E_INVALID before any HIP call); everything else is
+ * flate_hip_deflate_fast_batch's.  A call in which no stream has a dictionary of at least 17 bytes IS
+ * flate_hip_deflate_fast_batch: same kernels, same bytes.  Every used dictionary is run through the match finder
+ * ONCE per call (not once per stream); its streams start from a copy of the resulting table.
+ *   FLATE_HIP_LZ_SERIAL together with such a dictionary: FLATE_HIP_E_INVALID (the debug kernel has no dictionary
+ *   build).  The dictionary is window 0 of its stream, so FLATE_HIP_E_TOO_LARGE comes one window earlier for a
+ *   stream with one: at 0x7ffe0000 - 65535 bytes, and without FLATE_HIP_COMPAT_GO at 32766 LZ77 windows instead of
+ *   32767.  flate_hip_deflate_bound is unchanged.  A host-pointer call is copied in and out in one piece (no
+ *   "host_pipeline_groups").
+ * Out of scope: dictionaries for flate_hip_stream_write, flate_hip_deflate_fast_spliced, flate_hip_lz77_matches
+ * and across ranks (flate_hip_gather_*). */
+int flate_hip_deflate_fast_batch_dict(flate_hip_ctx *ctx, const uint8_t *in, const uint64_t *in_off,
+                                      uint32_t n_streams,
+                                      const uint8_t *dicts, const uint64_t *dict_off, uint32_t n_dicts,
+                                      const uint32_t *dict_of,
+                                      uint8_t *out, uint64_t out_cap, uint64_t *out_off, uint32_t flags);
+
 /* ONE stream written in pieces -- Writer::write as the reference behaves: compressed bytes leave
  * while later input is still to come (Compressor::write -> fill_store / enc_speed per full
  * 65535-byte window, deflate.mbt:280-294,222-229,236-277; the sink sees output every >= 240
@@ -272,8 +307,9 @@ int flate_hip_inflate_stream_read(flate_hip_inflate_stream *stream, const uint8_
  * stream decodes as if its output started with `dict`, which has already been read -- the last 32768
  * bytes of it are kept as history (DictDecoder::new, dict-decoder.mbt:40-60), a distance may reach
  * min(32768, dict_len + bytes produced) back (:63-69, inflate.mbt:677-680).  dict is a HOST buffer, not
- * retained; dict_len = 0: none.  (The encoder side, Writer::new_dict, is outside this path: in the
- * reference it compresses the dictionary into the output as data) */
+ * retained; dict_len = 0: none.  (The encoder side of ONE stream, Writer::new_dict, is outside this path: in the
+ * reference it compresses the dictionary into the output as data; batches of streams that NEED their
+ * dictionary to be read: flate_hip_deflate_fast_batch_dict.) */
 int flate_hip_inflate_stream_reset(flate_hip_inflate_stream *stream, const uint8_t *dict, uint64_t dict_len);
 void flate_hip_inflate_stream_free(flate_hip_inflate_stream *stream);
 

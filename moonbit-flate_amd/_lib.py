@@ -21,6 +21,7 @@ EXPORTS = [
     "flate_hip_host_register", "flate_hip_host_unregister", "flate_hip_host_alloc", "flate_hip_host_free",
     "flate_hip_inflate_stream_open", "flate_hip_inflate_stream_read", "flate_hip_inflate_stream_free",
     "flate_hip_inflate_stream_reset", "flate_hip_checksum_batch", "flate_hip_inflate_batch_dict",
+    "flate_hip_deflate_fast_batch_dict",
 ]
 
 _lib = None
@@ -66,6 +67,9 @@ def load():
     L.flate_hip_inflate_batch_dict.argtypes = [vp, vp, vp, C.c_uint32, vp, vp, C.c_uint32, vp,
                                                vp, vp, vp, vp, vp, C.c_uint32]
     L.flate_hip_inflate_batch_dict.restype = C.c_int
+    L.flate_hip_deflate_fast_batch_dict.argtypes = [vp, vp, vp, C.c_uint32, vp, vp, C.c_uint32, vp,
+                                                    vp, C.c_uint64, vp, C.c_uint32]
+    L.flate_hip_deflate_fast_batch_dict.restype = C.c_int
     L.flate_hip_deflate_fast_spliced.argtypes = [vp, vp, vp, C.c_uint32, vp, C.c_uint64, vp, vp, C.c_uint32]
     L.flate_hip_deflate_fast_spliced.restype = C.c_int
     L.flate_hip_inflate_spliced.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint32, vp, vp, vp, vp, vp, C.c_uint32]

@@ -53,6 +53,9 @@ struct flate_hip_ctx {
   int entropy_per_block = -1;
   DevBuf d_istatus, d_ierr, d_debug, d_gtables, d_queue, d_simt_lens;
   DevBuf d_dicts, d_dict_at, d_dict_len;  // flate_hip_inflate_batch_dict: dictionary tails, per-stream (at, len)
+  // flate_hip_deflate_fast_batch_dict (it shares the three above, there per used dictionary): the streams that start
+  // from a dictionary, every stream's dictionary slot, the primed tables and sweep clocks of the slots
+  DevBuf d_idsD, d_lz_slot_of, d_lz_tables, d_lz_clocks;
   hipStream_t guest_stream = nullptr;
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
   int guest_blocks = 0;      // 0 = guest kernel off
@@ -262,16 +265,25 @@ std::vector<uint16_t> make_scan_table() {
   return t;
 }
 
+// The preset dictionaries of an encode call (flate_hip_deflate_fast_batch_dict), already on the device.
+struct DeflDict {
+  LzDictParams dev;
+  uint32_t n_slots;        // used dictionaries of at least kSmallHuffMin bytes (after the cut to 32768)
+  const uint8_t *has;      // host, per stream: it uses one of them
+};
+
 struct StagePlan {
   uint32_t n_streams = 0;
   std::vector<uint32_t> chunk_base;  // n+1
   std::vector<uint32_t> ids16, ids32;
+  std::vector<uint32_t> idsD;  // streams that start from a preset dictionary's table (flate_hip_deflate_fast_batch_dict)
   std::vector<uint32_t> blk_base;  // n+1
   uint32_t n_chunks = 0;
   uint32_t n_blocks = 0;
 };
 
-int make_plan(const uint64_t *in_off, uint32_t n, StagePlan &pl, uint32_t flags) {
+// has_dict (or null): per stream, whether DeflateFast::encode has run over a preset dictionary before the payload
+int make_plan(const uint64_t *in_off, uint32_t n, StagePlan &pl, uint32_t flags, const uint8_t *has_dict = nullptr) {
   pl.n_streams = n;
   pl.chunk_base.resize((size_t)n + 1);
   pl.blk_base.resize((size_t)n + 1);
@@ -279,7 +291,9 @@ int make_plan(const uint64_t *in_off, uint32_t n, StagePlan &pl, uint32_t flags)
   for (uint32_t i = 0; i < n; ++i) {
     if (in_off[i + 1] < in_off[i]) return FLATE_HIP_E_INVALID;
     const uint64_t len = in_off[i + 1] - in_off[i];
-    if (len >= 0x7ffe0000ull) return FLATE_HIP_E_TOO_LARGE;
+    // (a dictionary is window 0 of its stream: the payload's positions start at 65535, `cur` one window further on)
+    const bool dict = has_dict && has_dict[i];
+    if (len + (dict ? (uint64_t)kMaxStoreBlockSize : 0) >= 0x7ffe0000ull) return FLATE_HIP_E_TOO_LARGE;
     const uint64_t full = len / kMaxStoreBlockSize, r = len % kMaxStoreBlockSize;
     const uint64_t nch = full + (r >= (uint64_t)kSmallLzMin ? 1 : 0);
     // The reference's `cur` reaches buffer_reset at a Writer's window 32 766 (deflate-fast.mbt:55,130):
@@ -287,10 +301,12 @@ int make_plan(const uint64_t *in_off, uint32_t n, StagePlan &pl, uint32_t flags)
     // their table from start to end, so a stream with an LZ77 window that far in is refused here
     // (flate_hip_stream_write follows the reference past that point); in Go's semantics the shift
     // changes no distance and the 32-bit positions above are the only limit.
-    if (!(flags & FLATE_HIP_COMPAT_GO) && nch > 32766) return FLATE_HIP_E_TOO_LARGE;
+    if (!(flags & FLATE_HIP_COMPAT_GO) && nch + (dict ? 1 : 0) > 32766) return FLATE_HIP_E_TOO_LARGE;
     pl.chunk_base[i] = (uint32_t)chunks;
     pl.blk_base[i] = (uint32_t)blocks;
-    if (nch == 1) {
+    if (dict && nch > 0) {
+      pl.idsD.push_back(i);  // (a payload under 128 bytes never reaches the match finder: its dictionary is unused)
+    } else if (nch == 1) {
       pl.ids16.push_back(i);  // one LZ77 window (it starts at 0): positions fit a 16-bit slot
     } else if (nch > 0) {
       pl.ids32.push_back(i);
@@ -332,8 +348,9 @@ int collect_timing(flate_hip_ctx *c, const bool used[FLATE_HIP_STAGE_COUNT]) {
 
 // Upload the index arrays and run the match finder over every LZ77 chunk.
 // (the caller has checked that the launch is one persistent resident+guest launch in stream order)
+// DD: the preset dictionaries of the streams in pl.idsD (null: there are none)
 int run_lz77(flate_hip_ctx *c, const uint8_t *d_in, const uint64_t *in_off, const StagePlan &pl,
-             uint32_t flags) {
+             uint32_t flags, const DeflDict *DD = nullptr) {
   const uint32_t n = pl.n_streams;
   int rc;
   if ((rc = ensure(c, c->d_in_off, ((size_t)n + 1) * 8))) return rc;
@@ -348,6 +365,11 @@ int run_lz77(flate_hip_ctx *c, const uint8_t *d_in, const uint64_t *in_off, cons
   if ((rc = ctl_up(c, c->d_chunk_base.p, pl.chunk_base.data(), ((size_t)n + 1) * 4))) return rc;
   if ((rc = ctl_up(c, c->d_ids16.p, pl.ids16.data(), pl.ids16.size() * 4))) return rc;
   if ((rc = ctl_up(c, c->d_ids32.p, pl.ids32.data(), pl.ids32.size() * 4))) return rc;
+  if (!pl.idsD.empty()) {
+    if (!DD || (flags & FLATE_HIP_LZ_SERIAL)) return FLATE_HIP_E_INTERNAL;
+    if ((rc = ensure(c, c->d_idsD, pl.idsD.size() * 4 + 4))) return rc;
+    if ((rc = ctl_up(c, c->d_idsD.p, pl.idsD.data(), pl.idsD.size() * 4))) return rc;
+  }
 
   LzParams P{};  // (value-initialised: a field added later must never reach a kernel as stack garbage)
   P.in = d_in;
@@ -404,7 +426,8 @@ int run_lz77(flate_hip_ctx *c, const uint8_t *d_in, const uint64_t *in_off, cons
     if ((rc = ensure(c, c->d_queue, 64))) return rc;
     // words: [0..1] stream queues (single-, multi-window), [2..3] the guests' queues of a fixed
     // profiling split, [4..5] what the LDS-table launches took, [6..7] window-unit head / tail
-    HIP_TRY(c, hipMemsetAsync(c->d_queue.p, 0, 32, c->stream));
+    // [8] the queue of the streams with a preset dictionary
+    HIP_TRY(c, hipMemsetAsync(c->d_queue.p, 0, 40, c->stream));
   }
 #if defined(FLATE_LZ_STAMPS) || defined(FLATE_LZ_FINISH)
   if ((rc = ensure(c, c->d_debug, (size_t)pl.n_chunks * 64 + 64))) return rc;
@@ -487,6 +510,31 @@ int run_lz77(flate_hip_ctx *c, const uint8_t *d_in, const uint64_t *in_off, cons
       };
       launch(c->d_ids16, (uint32_t)pl.ids16.size(), false, 0);
       launch(c->d_ids32, (uint32_t)pl.ids32.size(), true, 1);
+      if (!pl.idsD.empty()) {
+        // Streams with a preset dictionary: every used dictionary is primed once (one wavefront each), then the
+        // dictionary builds of the stream kernels run the payloads as windows 1, 2, ... (whole-stream scheduling)
+        const uint32_t count = (uint32_t)pl.idsD.size();
+        LzParams Q = P;
+        Q.stream_ids = (const uint32_t *)c->d_idsD.p;
+        Q.win0 = 1;
+        hipLaunchKernelGGL(lz77_dict_prime_kernel, dim3(DD->n_slots), dim3(64), 0, c->stream, Q, DD->dev);
+        if (!(c->guest_blocks > 0 && count >= c->guest_min)) {
+          hipLaunchKernelGGL(lz77_wave_dict_kernel, dim3(count), dim3(64), 0, c->stream, Q, DD->dev);
+        } else {
+          Q.gtables = c->d_gtables.p;
+          Q.gtable_blocks = (uint32_t)c->guest_blocks;
+          Q.queue = (uint32_t *)c->d_queue.p + 8;
+          Q.queue_end = count;
+          (void)hipEventRecord(c->ev_fork, c->stream);
+          (void)hipStreamWaitEvent(c->guest_stream, c->ev_fork, 0);
+          const uint32_t resident = c->resident_blocks < count ? c->resident_blocks : count;
+          hipLaunchKernelGGL(lz77_wave_dict_kernel, dim3(resident), dim3(64), 0, c->stream, Q, DD->dev);
+          hipLaunchKernelGGL(lz77_guest_dict_kernel, dim3((uint32_t)c->guest_blocks), dim3(64), 0, c->guest_stream, Q,
+                             DD->dev);
+          (void)hipEventRecord(c->ev_join, c->guest_stream);
+          (void)hipStreamWaitEvent(c->stream, c->ev_join, 0);
+        }
+      }
     }
   }
   // (test hook: it loses one hand-over of THIS launch, not of every later one)
@@ -630,7 +678,8 @@ void flate_hip_destroy(flate_hip_ctx *c) {
                     &c->d_ids32, &c->d_matches, &c->d_nmatch, &c->d_ntok, &c->d_blk_base,
                     &c->d_blk_hist, &c->d_blk_cl, &c->d_blk_hdr, &c->d_blk_meta, &c->d_tile_meta, &c->d_blk_sid, &c->d_slot_off, &c->d_out_len, &c->d_out_off, &c->d_status, &c->d_istatus,
                     &c->d_ierr, &c->d_debug, &c->d_gtables, &c->d_queue, &c->d_simt_lens,
-                    &c->d_dicts, &c->d_dict_at, &c->d_dict_len})
+                    &c->d_dicts, &c->d_dict_at, &c->d_dict_len, &c->d_idsD, &c->d_lz_slot_of, &c->d_lz_tables,
+                    &c->d_lz_clocks})
     release(*b);
   for (auto &e : c->ev)
     if (e) (void)hipEventDestroy(e);
@@ -776,15 +825,15 @@ size_t flate_hip_deflate_bound(size_t n) {
 // receives the bit position of every stream (may be NULL) and *total_bytes the size.
 static int deflate_common(flate_hip_ctx *c, const uint8_t *in, const uint64_t *in_off, uint32_t n,
                           uint8_t *out, uint64_t out_cap, uint64_t *out_off, uint32_t flags,
-                          bool spliced, uint64_t *total_bytes) {
+                          bool spliced, uint64_t *total_bytes, const DeflDict *DD = nullptr) {
   HIP_TRY(c, hipSetDevice(c->device));
   StagePlan pl;
-  int rc = make_plan(in_off, n, pl, flags);
+  int rc = make_plan(in_off, n, pl, flags, DD ? DD->has : nullptr);
   if (rc) return rc;
   const bool dev = (flags & FLATE_HIP_DEVICE_PTRS) != 0;
   const uint64_t in_bytes = in_off[n];
   // the call's index arrays: in_off, chunk_base, blk_base (n + 1 each), the two stream lists, blk_sid
-  if ((rc = ctl_begin(c, ((size_t)n + 1) * 16 + (pl.ids16.size() + pl.ids32.size() + (size_t)pl.n_blocks) * 4,
+  if ((rc = ctl_begin(c, ((size_t)n + 1) * 16 + (pl.ids16.size() + pl.ids32.size() + pl.idsD.size() + (size_t)pl.n_blocks) * 4,
                       ((size_t)n + 1) * 8 + 64)))
     return rc;
 
@@ -829,7 +878,7 @@ static int deflate_common(flate_hip_ctx *c, const uint8_t *in, const uint64_t *i
     if ((rc = ctl_up(c, c->d_blk_sid.p, blk_sid.data(), (size_t)pl.n_blocks * 4))) return rc;
   }
 
-  if ((rc = run_lz77(c, d_in, in_off, pl, flags))) return rc;
+  if ((rc = run_lz77(c, d_in, in_off, pl, flags, DD))) return rc;
 
   HuffParams H{};
   H.in = d_in;
@@ -1916,6 +1965,20 @@ static int inflate_batch_ranges(const uint64_t *in_off, uint32_t n, const uint64
   return FLATE_HIP_OK;
 }
 
+// The dictionary arguments of flate_hip_inflate_batch_dict / flate_hip_deflate_fast_batch_dict (no HIP call)
+static bool dict_args_ok(const uint8_t *dicts, const uint64_t *dict_off, uint32_t n_dicts, const uint32_t *dict_of,
+                         uint32_t n) {
+  if (n_dicts && !dict_off) return false;
+  if (!dict_of && n_dicts == 0) return false;
+  for (uint32_t j = 0; j < n_dicts; ++j)
+    if (dict_off[j + 1] < dict_off[j]) return false;
+  if (n_dicts && dict_off[n_dicts] > dict_off[0] && !dicts) return false;
+  if (dict_of)
+    for (uint32_t i = 0; i < n; ++i)
+      if (dict_of[i] >= n_dicts && dict_of[i] != FLATE_HIP_NO_DICT) return false;
+  return true;
+}
+
 // flate_hip_inflate_batch after its checks; D: the streams' dictionaries (flate_hip_inflate_batch_dict)
 static int inflate_batch_run(flate_hip_ctx *c, const uint8_t *in, const uint64_t *in_off, uint32_t n,
                              uint8_t *out, const uint64_t *out_off, uint64_t *out_len,
@@ -1960,14 +2023,7 @@ int flate_hip_inflate_batch_dict(flate_hip_ctx *c, const uint8_t *in, const uint
   if (!inflate_batch_ptrs_ok(c, in, in_off, n, out, out_off, out_len, status, err_off, flags)) return FLATE_HIP_E_INVALID;
   int rc = inflate_batch_ranges(in_off, n, out_off, flags);
   if (rc != FLATE_HIP_OK && rc != FLATE_HIP_E_TOO_LARGE) return rc;
-  if (n_dicts && !dict_off) return FLATE_HIP_E_INVALID;
-  if (!dict_of && n_dicts == 0) return FLATE_HIP_E_INVALID;
-  for (uint32_t j = 0; j < n_dicts; ++j)
-    if (dict_off[j + 1] < dict_off[j]) return FLATE_HIP_E_INVALID;
-  if (n_dicts && dict_off[n_dicts] > dict_off[0] && !dicts) return FLATE_HIP_E_INVALID;
-  if (dict_of)
-    for (uint32_t i = 0; i < n; ++i)
-      if (dict_of[i] >= n_dicts && dict_of[i] != FLATE_HIP_NO_DICT) return FLATE_HIP_E_INVALID;
+  if (!dict_args_ok(dicts, dict_off, n_dicts, dict_of, n)) return FLATE_HIP_E_INVALID;
   // the history each stream starts with: the last kMaxMatchOffset bytes of its dictionary
   auto tail_len = [&](uint32_t j) -> uint32_t {
     const uint64_t l = dict_off[j + 1] - dict_off[j];
@@ -2011,6 +2067,83 @@ int flate_hip_inflate_batch_dict(flate_hip_ctx *c, const uint8_t *in, const uint
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   const InfDict D{d_dicts, (const uint64_t *)c->d_dict_at.p, (const uint32_t *)c->d_dict_len.p, h_len.data()};
   return inflate_batch_run(c, in, in_off, n, out, out_off, out_len, status, err_off, flags, &D);
+}
+
+int flate_hip_deflate_fast_batch_dict(flate_hip_ctx *c, const uint8_t *in, const uint64_t *in_off, uint32_t n,
+                                      const uint8_t *dicts, const uint64_t *dict_off, uint32_t n_dicts,
+                                      const uint32_t *dict_of, uint8_t *out, uint64_t out_cap, uint64_t *out_off,
+                                      uint32_t flags) {
+  // every check before any HIP call
+  if (!c || !in_off || !out_off || (n && (!in || !out))) return FLATE_HIP_E_INVALID;
+  if (!dict_args_ok(dicts, dict_off, n_dicts, dict_of, n)) return FLATE_HIP_E_INVALID;
+  // DeflateFast::encode(d) over the last 32768 bytes of the dictionary; under 17 bytes that call is the
+  // small-input path (deflate-fast.mbt:136-140) and leaves nothing behind
+  auto tail_len = [&](uint32_t j) -> uint32_t {
+    const uint64_t l = dict_off[j + 1] - dict_off[j];
+    return l < (uint64_t)kMaxMatchOffset ? (uint32_t)l : (uint32_t)kMaxMatchOffset;
+  };
+  auto dict_of_stream = [&](uint32_t i) { return dict_of ? dict_of[i] : 0u; };
+  std::vector<uint8_t> has(n, 0);
+  bool any = false;
+  for (uint32_t i = 0; i < n; ++i) {
+    const uint32_t j = dict_of_stream(i);
+    has[i] = j != FLATE_HIP_NO_DICT && tail_len(j) >= (uint32_t)kSmallHuffMin;
+    any = any || has[i];
+  }
+  if (!any)  // no stream's encoder has seen a dictionary: the plain call, its kernels and its bytes
+    return flate_hip_deflate_fast_batch(c, in, in_off, n, out, out_cap, out_off, flags);
+  if (flags & FLATE_HIP_LZ_SERIAL) return FLATE_HIP_E_INVALID;  // (the single-lane kernel has no dictionary build)
+  {
+    StagePlan pl;  // the whole index, before the context is touched
+    const int rc = make_plan(in_off, n, pl, flags, has.data());
+    if (rc) return rc;
+  }
+  c->hip_err.clear();
+  // every used dictionary's tail once (a slot), each followed by 16 bytes
+  std::vector<uint32_t> slot_of_dict(n_dicts, ~0u), h_slot_of(n, 0), h_len;
+  std::vector<uint64_t> h_at;
+  uint64_t total = 0;
+  for (uint32_t i = 0; i < n; ++i) {
+    if (!has[i]) continue;
+    const uint32_t j = dict_of_stream(i);
+    if (slot_of_dict[j] == ~0u) {
+      slot_of_dict[j] = (uint32_t)h_at.size();
+      h_at.push_back(total);
+      h_len.push_back(tail_len(j));
+      total += ((uint64_t)tail_len(j) + 16 + 15) & ~15ull;
+    }
+    h_slot_of[i] = slot_of_dict[j];
+  }
+  const uint32_t n_slots = (uint32_t)h_at.size();
+  HIP_TRY(c, hipSetDevice(c->device));
+  int rc;
+  if ((rc = ensure(c, c->d_dicts, total))) return rc;
+  if ((rc = ensure(c, c->d_dict_at, (size_t)n_slots * 8))) return rc;
+  if ((rc = ensure(c, c->d_dict_len, (size_t)n_slots * 4))) return rc;
+  if ((rc = ensure(c, c->d_lz_slot_of, (size_t)n * 4))) return rc;
+  if ((rc = ensure(c, c->d_lz_tables, (size_t)n_slots * kTableSize * 2))) return rc;
+  if ((rc = ensure(c, c->d_lz_clocks, (size_t)n_slots * 4))) return rc;
+  uint8_t *d_dicts = (uint8_t *)c->d_dicts.p;
+  const hipMemcpyKind kind = (flags & FLATE_HIP_DEVICE_PTRS) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+  for (uint32_t j = 0; j < n_dicts; ++j)
+    if (slot_of_dict[j] != ~0u)
+      HIP_TRY(c, hipMemcpyAsync(d_dicts + h_at[slot_of_dict[j]], dicts + dict_off[j + 1] - tail_len(j), tail_len(j), kind,
+                                c->stream));
+  HIP_TRY(c, hipMemcpyAsync(c->d_dict_at.p, h_at.data(), (size_t)n_slots * 8, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(c->d_dict_len.p, h_len.data(), (size_t)n_slots * 4, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(c->d_lz_slot_of.p, h_slot_of.data(), (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  DeflDict DD{};
+  DD.dev.dict_buf = d_dicts;
+  DD.dev.dict_at = (const uint64_t *)c->d_dict_at.p;
+  DD.dev.dict_len = (const uint32_t *)c->d_dict_len.p;
+  DD.dev.slot_of = (const uint32_t *)c->d_lz_slot_of.p;
+  DD.dev.tables = (uint16_t *)c->d_lz_tables.p;
+  DD.dev.clocks = (uint32_t *)c->d_lz_clocks.p;
+  DD.n_slots = n_slots;
+  DD.has = has.data();
+  // (host pointers: one copy in, compress, one copy out -- the pipelined host path is the plain call's)
+  return deflate_common(c, in, in_off, n, out, out_cap, out_off, flags, false, nullptr, &DD);
 }
 
 int flate_hip_inflate_spliced(flate_hip_ctx *c, const uint8_t *in, uint64_t in_len,

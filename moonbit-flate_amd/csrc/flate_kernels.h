@@ -58,6 +58,19 @@ struct LzParams {
   int *status;
 };
 
+// Preset dictionaries of a match-finder launch (the *_dict_kernel builds; flate_hip_deflate_fast_batch_dict).
+// A slot is one USED dictionary: the last dict_len (17 .. 32768) bytes of it sit at dict_buf + dict_at[slot],
+// followed by at least 16 readable bytes.  lz77_dict_prime_kernel leaves every slot's table and sweep clock in
+// tables / clocks; the stream kernels start stream i from the snapshot of slot_of[i].
+struct LzDictParams {
+  const uint8_t *dict_buf;
+  const uint64_t *dict_at;   // per slot
+  const uint32_t *dict_len;  // per slot
+  const uint32_t *slot_of;   // per stream of the batch (read for the streams of the launch only)
+  uint16_t *tables;          // per slot: kTableSize slots
+  uint32_t *clocks;          // per slot
+};
+
 // Entropy stage.  Blocks are the units enc_speed writes: every full 65535-byte window plus the
 // tail (blk_base[i] .. blk_base[i+1] are stream i's blocks; the first chunk_base[i+1]-chunk_base[i]
 // of them are LZ77 chunks).
@@ -137,6 +150,10 @@ __global__ void lz77_guest_kernel(LzParams P);
 // `prev`, deflate-fast.mbt:367-374: what the reference does in its default compat mode)
 __global__ void lz77_resume_kernel(LzParams P, uint16_t *table_io, uint32_t *clock_io, uint32_t nwin,
                                    uint32_t rebase, uint32_t forget);
+// preset dictionaries: one block per slot primes its table; the stream kernels' dictionary builds (P.win0 = 1)
+__global__ void lz77_dict_prime_kernel(LzParams P, LzDictParams DP);
+__global__ void lz77_wave_dict_kernel(LzParams P, LzDictParams DP);
+__global__ void lz77_guest_dict_kernel(LzParams P, LzDictParams DP);
 __global__ void huff_hist_kernel(HuffParams P);
 __global__ void huff_code_kernel(HuffParams P);
 __global__ void huff_pack_kernel(HuffParams P);

@@ -105,9 +105,56 @@ FLATE_D int prefix16(uint4 a, uint4 b) {
   return 16;
 }
 
+// Preset dictionaries (the DICT builds, flate_hip_deflate_fast_batch_dict).  A stream with a dictionary is a
+// multi-window stream whose window 0 has already run: the D <= 32768 bytes of the dictionary's tail are the END of a
+// virtual window 0, absolute positions [65535 - D, 65535), and the payload starts at position 65535, so its windows
+// start at multiples of 65535 as every stream's do.  `stream + p` is then valid for p >= 65535 only; a history read
+// below that comes from the dictionary (`dict + p`, dict = tail - (65535 - D)), and one that starts in the
+// dictionary and ends in the payload is put together byte by byte (match_len's third regime, deflate-fast.mbt:335-341).
+// Every tail is followed by 16 readable bytes.
+constexpr uint32_t kDictEnd = (uint32_t)kMaxStoreBlockSize;
+template <bool DICT>
+struct HistDict {};
+template <>
+struct HistDict<true> {
+  const uint8_t *dict;
+};
+template <bool DICT>
+struct Hist : HistDict<DICT> {
+  const uint8_t *stream;
+  FLATE_D uint8_t byte(uint32_t p) const {
+    if constexpr (DICT)
+      if (p < kDictEnd) return this->dict[p];
+    return stream[p];
+  }
+  FLATE_D uint32_t w32(uint32_t p) const {
+    if constexpr (!DICT) return ld32(stream + p);
+    if (p >= kDictEnd) return ld32(stream + p);
+    if constexpr (DICT)
+      if (p + 4u <= kDictEnd) return ld32(this->dict + p);
+    return (uint32_t)byte(p) | ((uint32_t)byte(p + 1) << 8) | ((uint32_t)byte(p + 2) << 16) | ((uint32_t)byte(p + 3) << 24);
+  }
+  FLATE_D uint32_t partial(uint32_t p, int rem) const {  // 1..3 bytes
+    if constexpr (!DICT) return ld_partial(stream + p, rem);
+    if (p >= kDictEnd) return ld_partial(stream + p, rem);
+    uint32_t v = byte(p);
+    if (rem > 1) v |= (uint32_t)byte(p + 1) << 8;
+    if (rem > 2) v |= (uint32_t)byte(p + 2) << 16;
+    return v;
+  }
+  FLATE_D uint4 w128(uint32_t p) const {
+    if constexpr (!DICT) return ld128(stream + p);
+    if (p >= kDictEnd) return ld128(stream + p);
+    if constexpr (DICT)
+      if (p + 16u <= kDictEnd) return ld128(this->dict + p);
+    return make_uint4(w32(p), w32(p + 4), w32(p + 8), w32(p + 12));
+  }
+};
+
 // Total match length at chunk position pf against absolute position cand, `have` bytes
 // already known equal (match_len, deflate-fast.mbt:286-342), 64 lanes x 4 bytes.
-FLATE_D int extend_match(const uint8_t *src, const uint8_t *stream, uint32_t W, int n, int pf,
+template <bool DICT = false>
+FLATE_D int extend_match(const uint8_t *src, const Hist<DICT> hist, uint32_t W, int n, int pf,
                          uint32_t cand, int have, uint32_t compat_go, int lane) {
   if (!compat_go && cand + 4 < W) return 4;  // MoonBit: prev window is empty
   int limit = n - pf;
@@ -116,8 +163,14 @@ FLATE_D int extend_match(const uint8_t *src, const uint8_t *stream, uint32_t W, 
   uint32_t x = 0;
   if (o < limit) {
     const int r = limit - o;
-    const uint8_t *pa = src + pf + o, *pb = stream + cand + o;
-    x = r >= 4 ? (ld32(pa) ^ ld32(pb)) : (ld_partial(pa, r) ^ ld_partial(pb, r));
+    const uint8_t *pa = src + pf + o;
+    if constexpr (!DICT) {  // (the pointer form the plain kernels were built with: their register counts stay)
+      const uint8_t *pb = hist.stream + cand + o;
+      x = r >= 4 ? (ld32(pa) ^ ld32(pb)) : (ld_partial(pa, r) ^ ld_partial(pb, r));
+    } else {
+      const uint32_t pb = cand + (uint32_t)o;
+      x = r >= 4 ? (ld32(pa) ^ hist.w32(pb)) : (ld_partial(pa, r) ^ hist.partial(pb, r));
+    }
   }
   const uint64_t mm = __ballot(x != 0);
   if (!mm) return limit;

@@ -207,16 +207,35 @@ FLATE_D void tag_set(uint32_t *tags, uint32_t h, uint32_t t) {
   atomicOr(&tags[h >> 4], t << sh);
 }
 
-template <bool MULTI, bool GUEST = false>
+//
+// DMODE (preset dictionaries, flate_hip_deflate_fast_batch_dict; see Hist in lz77_device.h), MULTI builds only:
+//   kLzDictStream: `sid` has a dictionary.  The caller has loaded the table and *sweep_io from the dictionary's
+//     snapshot and passes c_begin = P.win0 = 1: the payload is windows 1, 2, ... of a stream whose window 0 ended
+//     with the dictionary, and history reads below position 65535 go to the dictionary.
+//   kLzDictPrime: `sid` is a dictionary slot.  The parser runs over the D bytes of its tail as the one window
+//     [65535 - D, 65535) from an empty table -- DeflateFast::encode(d) with the tokens dropped -- and leaves the
+//     table and the sweep clock for the streams that use it.  The first sweep is due kSweepEvery behind the START
+//     of the tail, and the empty table's markers are kMarkerBack in front of it: the static_assert on
+//     kSweepEvery + kSpanMax + 64 + kMarkerBack holds for a parser that starts anywhere.
+constexpr int kLzDictStream = 1, kLzDictPrime = 2;
+template <bool MULTI, bool GUEST = false, int DMODE = 0>
 FLATE_D void lz77_stream(const LzParams &P, const uint32_t sid, uint16_t *table, const int lane,
                          const uint32_t c_begin = 0, const uint32_t c_end = 0xffffffffu,
-                         uint32_t *sweep_io = nullptr, uint32_t *tags = nullptr) {
+                         uint32_t *sweep_io = nullptr, uint32_t *tags = nullptr,
+                         const LzDictParams *DP = nullptr) {
   using E = uint16_t;
+  constexpr bool PRIME = DMODE == kLzDictPrime, DICT = DMODE == kLzDictStream;
+  static_assert(DMODE == 0 || MULTI, "a dictionary puts the payload behind position 65535: modular slots");
+  uint32_t prime_w = 0, prime_n = 0;  // PRIME: the tail's first position and its length
+  if constexpr (PRIME) {
+    prime_n = (uint32_t)__builtin_amdgcn_readfirstlane((int)DP->dict_len[sid]);
+    prime_w = kDictEnd - prime_n;
+  }
   if (tags && c_begin == 0)
     for (int i = lane; i < (int)kTagSlots / 16; i += 64) tags[i] = 0;
   if (c_begin == 0) {
     uint4 *t4 = reinterpret_cast<uint4 *>(table);
-    const uint32_t fill = MULTI ? (((0u - kMarkerBack + 1u) & 0xffffu) * 0x10001u) : 0u;
+    const uint32_t fill = MULTI ? (((prime_w - kMarkerBack + 1u) & 0xffffu) * 0x10001u) : 0u;
     const uint4 z = make_uint4(fill, fill, fill, fill);
     for (int i = lane; i < (int)(kTableSize * sizeof(E) / 16); i += 64) t4[i] = z;
   }
@@ -224,7 +243,7 @@ FLATE_D void lz77_stream(const LzParams &P, const uint32_t sid, uint16_t *table,
   volatile E *vtable = table;
   constexpr uint32_t kEMask = 0xffffu;
   // MULTI: absolute position at which the next sweep is due
-  uint32_t next_sweep = (sweep_io && c_begin != 0) ? *sweep_io : kSweepEvery;
+  uint32_t next_sweep = (sweep_io && c_begin != 0) ? *sweep_io : prime_w + kSweepEvery;
   // Sweep: slots whose position is more than 32768 behind R can never be candidates again.
   auto sweep = [&](uint32_t R) {
     uint32_t *t32 = reinterpret_cast<uint32_t *>(table);
@@ -249,7 +268,24 @@ FLATE_D void lz77_stream(const LzParams &P, const uint32_t sid, uint16_t *table,
     next_sweep = R + kSweepEvery;
   };
 
-  const ChunkGeom g = stream_geom(P, sid);
+  ChunkGeom g;
+  Hist<DICT> hist;
+  if constexpr (PRIME) {  // (the tail through a virtual base: g.stream + absolute position)
+    g.stream = DP->dict_buf + DP->dict_at[sid] - prime_w;
+    g.len = kDictEnd;
+    g.nchunks = 1;
+    g.chunk0 = 0;
+    g.mbase = 0;
+  } else {
+    g = stream_geom(P, sid);
+  }
+  if constexpr (DICT) {
+    const uint32_t slot = DP->slot_of[sid];
+    hist.dict = DP->dict_buf + DP->dict_at[slot] - (kDictEnd - DP->dict_len[slot]);
+    g.stream -= kDictEnd;  // the payload starts at position 65535 (never read below it through g.stream)
+    g.len += kDictEnd;
+  }
+  hist.stream = g.stream;
   const uint16_t *scan_tab = P.scan_off;
   uint32_t pf_val = 0, pf_sink = 0;
 #ifdef FLATE_LZ_FINISH  // diagnostic build: when did this stream start and end, on which block (100 MHz clock)
@@ -260,11 +296,11 @@ FLATE_D void lz77_stream(const LzParams &P, const uint32_t sid, uint16_t *table,
   const uint32_t w0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)P.win0);
   const uint32_t c_stop = c_end < w0 + g.nchunks ? c_end : w0 + g.nchunks;
   for (uint32_t c = c_begin; c < c_stop; ++c) {
-    const uint32_t W = c * (uint32_t)kMaxStoreBlockSize;
+    const uint32_t W = PRIME ? prime_w : c * (uint32_t)kMaxStoreBlockSize;
     const uint64_t rem_len = g.len - W;
     const int n = rem_len < (uint64_t)kMaxStoreBlockSize ? (int)rem_len : kMaxStoreBlockSize;
     const uint8_t *src = g.stream + W;
-    uint2 *mout = P.matches + g.mbase + (uint64_t)(c - w0) * kMatchCapPerChunk;
+    uint2 *mout = P.matches + g.mbase + (uint64_t)(c - w0) * kMatchCapPerChunk;  // (PRIME: nothing is stored)
     uint32_t nm = 0;
     uint32_t acc_len = 0;  // per-lane partial sums of match lengths
     const int s_limit = n - kInputMargin;
@@ -328,7 +364,7 @@ FLATE_D void lz77_stream(const LzParams &P, const uint32_t sid, uint16_t *table,
         const bool inr = maybe && (MULTI ? dist != 0 : old != 0) && dist <= (uint32_t)kMaxMatchOffset;
         const uint32_t cand_abs = A1 - 1u - dist;
         uint4 cb = own;
-        if (inr) cb = ld128(g.stream + cand_abs);
+        if (inr) cb = hist.w128(cand_abs);
         {  // look-ahead: pull the next lines of this stream towards L2.  Issued after the
            // candidate gather so that no wait of this batch has to include it.
           int pq = B + 768 + 4 * lane;
@@ -560,7 +596,7 @@ FLATE_D void lz77_stream(const LzParams &P, const uint32_t sid, uint16_t *table,
           if (have < 16)
             total = (!P.compat_go && cand + 4 < W) ? 4 : have;
           else
-            total = extend_match(src, g.stream, W, n, pf, cand, 16, P.compat_go, lane);
+            total = extend_match(src, hist, W, n, pf, cand, 16, P.compat_go, lane);
           M |= 1ull << f;
           if (lane == f) {
             rec_tok = kMatchType | ((uint32_t)(total - 3) << kLengthShift) | ((W + (uint32_t)pf) - cand - 1);
@@ -588,7 +624,7 @@ FLATE_D void lz77_stream(const LzParams &P, const uint32_t sid, uint16_t *table,
         }
         // match records of this batch, in position order, one coalesced store
         if ((MF >> lane) & 1) acc_len += (uint32_t)tot_self;
-        if ((M >> lane) & 1)
+        if (!PRIME && ((M >> lane) & 1))
           {  // streaming store: the records are read again only by the entropy kernels, and
              // keeping them out of L2 leaves more of it to the guest blocks' hash tables
             const unsigned long long rec = (unsigned long long)(uint32_t)q | ((unsigned long long)rec_tok << 32);
@@ -665,7 +701,7 @@ FLATE_D void lz77_stream(const LzParams &P, const uint32_t sid, uint16_t *table,
         const uint32_t cand_abs = A1 - 1u - dist;
         bool ok = false;
         if (exists && (MULTI ? dist != 0 : old != 0) && dist <= (uint32_t)kMaxMatchOffset)
-          ok = ld32(g.stream + cand_abs) == cv;
+          ok = hist.w32(cand_abs) == cv;
         const uint64_t V = __ballot(ok);
         const int f0 = ffs64(V);
 
@@ -729,8 +765,8 @@ FLATE_D void lz77_stream(const LzParams &P, const uint32_t sid, uint16_t *table,
           continue;
         }
         const int pf = (int)rdlane((uint32_t)p, f);
-        const int total = extend_match(src, g.stream, W, n, pf, cand, 4, P.compat_go, lane);
-        if (lane == 0)
+        const int total = extend_match(src, hist, W, n, pf, cand, 4, P.compat_go, lane);
+        if (!PRIME && lane == 0)
           mout[nm] = make_uint2((uint32_t)pf, kMatchType | ((uint32_t)(total - 3) << kLengthShift) |
                                                   ((W + (uint32_t)pf) - cand - 1));
         ++nm;
@@ -743,7 +779,7 @@ FLATE_D void lz77_stream(const LzParams &P, const uint32_t sid, uint16_t *table,
     uint32_t sumlen = acc_len;
     for (int d = 32; d >= 1; d >>= 1) sumlen += __shfl_xor(sumlen, d);
     if (pf_sink == 0x9e3779b9u && P.debug) P.debug[0] = pf_sink;  // keeps the look-ahead loads alive
-    if (lane == 0) {
+    if (!PRIME && lane == 0) {
       P.chunk_nmatch[g.chunk0 + c - w0] = nm;
       P.chunk_ntok[g.chunk0 + c - w0] = (uint32_t)n - sumlen + nm;
 #ifdef FLATE_LZ_STAMPS
@@ -1002,6 +1038,89 @@ __global__ __launch_bounds__(64) void lz77_guest_kernel(LzParams P) {
     if (q >= P.queue_end) break;
     __syncthreads();
     lz77_stream<MULTI, true>(P, P.stream_ids[q], table, lane, 0, 0xffffffffu, nullptr, tags);
+    __syncthreads();
+    all_lanes_here(P, lane);
+  }
+}
+
+// ---------------------------------------------------------------------------------
+// Preset dictionaries (flate_hip_deflate_fast_batch_dict).  lz77_dict_prime_kernel: one wavefront per USED dictionary
+// runs the parser over its tail once per call and leaves the table (32 KiB) and the sweep clock in global memory,
+// as a stream's table rests there between two window units (uq_run).  The parser is deterministic, so a stream
+// that starts from that snapshot is bit-identical to one that ran DeflateFast::encode(d) itself.  The stream
+// kernels' DICT builds copy the snapshot into their working table -- 32 KiB that all streams of a dictionary
+// share, so it comes from L2 / Infinity Cache -- and run the payload as windows 1, 2, ...  Whole-stream
+// scheduling (no window units); the guests run without slot tags (the snapshot's slots carry none).
+// ---------------------------------------------------------------------------------
+FLATE_D void dict_snapshot_load(const LzDictParams &DP, uint32_t sid, uint16_t *table, uint32_t *clock, int lane) {
+  const uint32_t slot = (uint32_t)__builtin_amdgcn_readfirstlane((int)DP.slot_of[sid]);
+  const uint32_t *src = reinterpret_cast<const uint32_t *>(DP.tables + (size_t)slot * kTableSize);
+  uint32_t *dst = reinterpret_cast<uint32_t *>(table);
+  static_assert(kTableSize / 2 % (64 * 16) == 0, "table = whole rounds of 16 dwords per lane");
+  for (int i0 = lane; i0 < kTableSize / 2; i0 += 64 * 16) {  // (sixteen loads in flight per lane, as uq_run)
+    uint32_t w[16];
+#pragma unroll
+    for (int k = 0; k < 16; ++k) w[k] = src[i0 + 64 * k];
+#pragma unroll
+    for (int k = 0; k < 16; ++k) dst[i0 + 64 * k] = w[k];
+  }
+  *clock = (uint32_t)__builtin_amdgcn_readfirstlane((int)DP.clocks[slot]);
+  asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+  __syncthreads();
+}
+
+__global__ __launch_bounds__(64) void lz77_dict_prime_kernel(LzParams P, LzDictParams DP) {
+  __shared__ uint16_t table[kTableSize];
+  const int lane = threadIdx.x;
+  const uint32_t slot = blockIdx.x;
+  uint32_t clock = 0;
+  lz77_stream<true, false, kLzDictPrime>(P, slot, table, lane, 0, 1, &clock, nullptr, &DP);
+  __syncthreads();
+  const uint4 *src = reinterpret_cast<const uint4 *>(table);
+  uint4 *dst = reinterpret_cast<uint4 *>(DP.tables + (size_t)slot * kTableSize);
+  for (int i = lane; i < (int)(kTableSize * sizeof(uint16_t) / 16); i += 64) dst[i] = src[i];
+  if (lane == 0) DP.clocks[slot] = clock;
+}
+
+// one block per stream (P.queue == null) or persistent, as lz77_wave_kernel
+__global__ __launch_bounds__(64) void lz77_wave_dict_kernel(LzParams P, LzDictParams DP) {
+  __shared__ uint16_t table[kTableSize];
+  const int lane = threadIdx.x;
+  for (bool first = true;; first = false) {
+    uint32_t q;
+    if (P.queue) {
+      q = 0;
+      if (lane == 0) q = atomicAdd(P.queue, 1u);  // (the ONE lane-0 block of the loop: see uq_pop)
+      q = (uint32_t)__builtin_amdgcn_readfirstlane((int)q);
+      if (q >= P.queue_end) break;
+    } else {
+      if (!first) break;
+      q = blockIdx.x;
+    }
+    __syncthreads();
+    const uint32_t sid = (uint32_t)__builtin_amdgcn_readfirstlane((int)P.stream_ids[q]);
+    uint32_t clock = 0;
+    dict_snapshot_load(DP, sid, table, &clock, lane);
+    lz77_stream<true, false, kLzDictStream>(P, sid, table, lane, 1, 0xffffffffu, &clock, nullptr, &DP);
+    __syncthreads();
+    all_lanes_here(P, lane);
+  }
+}
+
+__global__ __launch_bounds__(64) void lz77_guest_dict_kernel(LzParams P, LzDictParams DP) {
+  if (blockIdx.x >= P.gtable_blocks) return;  // (gtables holds one table per block of this launch)
+  uint16_t *table = reinterpret_cast<uint16_t *>(P.gtables) + (size_t)blockIdx.x * kTableSize;
+  const int lane = threadIdx.x;
+  for (;;) {
+    uint32_t q = 0;
+    if (lane == 0) q = atomicAdd(P.queue, 1u);  // (the ONE lane-0 block of the loop: see uq_pop)
+    q = (uint32_t)__builtin_amdgcn_readfirstlane((int)q);
+    if (q >= P.queue_end) break;
+    __syncthreads();
+    const uint32_t sid = (uint32_t)__builtin_amdgcn_readfirstlane((int)P.stream_ids[q]);
+    uint32_t clock = 0;
+    dict_snapshot_load(DP, sid, table, &clock, lane);
+    lz77_stream<true, true, kLzDictStream>(P, sid, table, lane, 1, 0xffffffffu, &clock, nullptr, &DP);
     __syncthreads();
     all_lanes_here(P, lane);
   }

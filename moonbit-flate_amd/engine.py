@@ -163,9 +163,15 @@ class FlateEngine:
         return (COMPAT_GO if compat_go else 0) | (LZ_SERIAL if lz_serial else 0) | \
                (DEVICE_PTRS if device else 0)
 
-    def deflate_batch(self, data, in_off, out=None, out_cap=None, compat_go=False, lz_serial=False):
+    def deflate_batch(self, data, in_off, out=None, out_cap=None, compat_go=False, lz_serial=False,
+                      zdicts=None, dict_of=None):
         """Compress independent streams: stream i = data[in_off[i]:in_off[i+1]] with fresh-Writer
         semantics.  data: numpy uint8 array (host) or torch uint8 CUDA tensor (device).
+        zdicts: preset dictionaries as HISTORY (flate_hip_deflate_fast_batch_dict) -- one bytes-like object or a
+        list of them; dict_of[i] = the dictionary of stream i or NO_DICT (None: every stream uses the first), the
+        argument shapes of inflate_batch.  Such a stream can only be read with the same dictionary
+        (inflate_batch(..., zdicts=), zlib.decompressobj(-15, zdict=)); compat_go=True is the mode in which
+        matches extend into the dictionary; payloads under 128 bytes get nothing from it (include/flate_hip.h).
         Returns (out, out_off): out has the same kind as data, out_off is numpy uint64[n+1]."""
         in_off = np.ascontiguousarray(in_off, dtype=np.uint64)
         n = in_off.size - 1
@@ -192,9 +198,16 @@ class FlateEngine:
                 _check_out(out, data, 1, "deflate_batch")
             cap = out.size
             in_ptr, out_ptr = data.ctypes.data, out.ctypes.data
-        rc = self._L.flate_hip_deflate_fast_batch(self._ctx, in_ptr, in_off.ctypes.data, n, out_ptr,
-                                                  cap, out_off.ctypes.data,
-                                                  self._flags(compat_go, lz_serial, device))
+        if zdicts is None:
+            rc = self._L.flate_hip_deflate_fast_batch(self._ctx, in_ptr, in_off.ctypes.data, n, out_ptr,
+                                                      cap, out_off.ctypes.data,
+                                                      self._flags(compat_go, lz_serial, device))
+        else:
+            dk = _DictArgs(zdicts, dict_of, n, device)
+            rc = self._L.flate_hip_deflate_fast_batch_dict(self._ctx, in_ptr, in_off.ctypes.data, n, dk.ptr,
+                                                           dk.off_ptr, dk.n_dicts, dk.of_ptr, out_ptr, cap,
+                                                           out_off.ctypes.data,
+                                                           self._flags(compat_go, lz_serial, device))
         self._check(rc)
         return out, out_off
 
@@ -215,22 +228,36 @@ class FlateEngine:
                                                      DEVICE_PTRS if device else 0))
         return out[:n]
 
-    def deflate_batch_framed(self, data, in_off, wrap, compat_go=False):
+    def deflate_batch_framed(self, data, in_off, wrap, compat_go=False, zdicts=None, dict_of=None):
         """The streams of a batch as zlib (RFC 1950) or gzip (RFC 1952) members: the raw DEFLATE streams of
         deflate_batch between the container's header and its trailer -- Adler-32, or CRC-32 and the length,
-        computed on the GPU (flate_hip_checksum_batch).  Host data; returns (bytes array, off[n+1])."""
+        computed on the GPU (flate_hip_checksum_batch).  Host data; returns (bytes array, off[n+1]).
+        zdicts / dict_of (zlib only; as in deflate_batch): a member written with a dictionary carries FDICT and
+        the dictionary's Adler-32 as DICTID (RFC 1950 2.2), so that inflate_batch_framed(..., zdicts=) and
+        zlib.decompressobj(zdict=) find it; the trailer stays the payload's checksum."""
         data = np.ascontiguousarray(data, dtype=np.uint8)
         in_off = np.ascontiguousarray(in_off, dtype=np.uint64)
         n = in_off.size - 1
-        raw, roff = self.deflate_batch(data, in_off, compat_go=compat_go)
+        heads = None
+        if zdicts is not None:
+            if wrap != "zlib":
+                raise ValueError("preset dictionaries exist in the zlib container only")
+            with_id = [zlib_dict_header(d) for d in _dict_list(zdicts)]
+            of = np.zeros(n, dtype=np.uint32) if dict_of is None else np.ascontiguousarray(dict_of, dtype=np.uint32)
+            heads = [ZLIB_HEADER if int(j) == NO_DICT else with_id[int(j)] for j in of]
+        raw, roff = self.deflate_batch(data, in_off, compat_go=compat_go, zdicts=zdicts, dict_of=dict_of)
         sums = self.checksum_batch(data, in_off, "adler32" if wrap == "zlib" else "crc32")
         head = ZLIB_HEADER if wrap == "zlib" else GZIP_HEADER
         tail = 4 if wrap == "zlib" else 8
-        off = roff + np.arange(n + 1, dtype=np.uint64) * np.uint64(len(head) + tail)
+        hlen = np.zeros(n + 1, dtype=np.uint64)
+        np.cumsum(np.array([len(h) for h in heads] if heads else [len(head)] * n, dtype=np.uint64), out=hlen[1:])
+        off = roff + hlen + np.arange(n + 1, dtype=np.uint64) * np.uint64(tail)
         out = np.empty(int(off[-1]), dtype=np.uint8)
         lens = (in_off[1:] - in_off[:-1]).astype(np.uint64)
         for i in range(n):
             o = int(off[i])
+            if heads:
+                head = heads[i]
             out[o:o + len(head)] = np.frombuffer(head, np.uint8)
             o += len(head)
             k = int(roff[i + 1] - roff[i])
@@ -640,6 +667,15 @@ def zlib_dict_ids(zdicts):
     for j, d in enumerate(_dict_list(zdicts)):
         ids.setdefault(zlib.adler32(bytes(d.cpu().numpy() if _is_torch(d) else d)), j)
     return ids
+
+
+def zlib_dict_header(zdict):
+    """The six header bytes of a zlib member written with preset dictionary `zdict`: CMF / FLG of ZLIB_HEADER with
+    FDICT set and FCHECK recomputed, then DICTID = the dictionary's Adler-32, big endian (RFC 1950 2.2)."""
+    cmf, flg = ZLIB_HEADER[0], (ZLIB_HEADER[1] & 0xC0) | 0x20
+    flg |= 31 - ((cmf << 8) | flg) % 31
+    d = zdict.cpu().numpy() if _is_torch(zdict) else zdict
+    return bytes([cmf, flg]) + zlib.adler32(bytes(d)).to_bytes(4, "big")
 
 
 def zlib_member_header(m, ids):

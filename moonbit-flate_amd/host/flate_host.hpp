@@ -100,6 +100,48 @@ inline Err compress_batch(Engine &e, const std::vector<std::vector<uint8_t>> &st
   return std::nullopt;
 }
 
+// &Reader::new_dict(r, dict) (inflate.mbt:315-317) in batch form (flate_hip_inflate_batch_dict): dicts[j] is a
+// preset dictionary (only its last 32768 bytes are history), dict_of[i] the dictionary of stream i or
+// FLATE_HIP_NO_DICT; an empty dict_of: every stream uses dicts[0].  The encode side (compress_batch with a
+// DictTable, BatchWriter) takes the same table: flate_hip_deflate_fast_batch_dict.
+struct DictTable {
+  std::vector<uint8_t> bytes;
+  std::vector<uint64_t> off;
+  explicit DictTable(const std::vector<std::vector<uint8_t>> &dicts) : off(dicts.size() + 1, 0) {
+    for (size_t j = 0; j < dicts.size(); ++j) off[j + 1] = off[j] + dicts[j].size();
+    bytes.resize(off.back() + 16);
+    for (size_t j = 0; j < dicts.size(); ++j) std::copy(dicts[j].begin(), dicts[j].end(), bytes.begin() + off[j]);
+  }
+};
+
+// compress_batch with preset dictionaries as HISTORY (flate_hip_deflate_fast_batch_dict): stream i is written as
+// if its Writer had seen dictionary dict_of[i] without producing output, and is read back by
+// Reader::new_dict / decompress_batch with the same dictionary.  FLATE_HIP_COMPAT_GO is the mode in which
+// matches extend into the dictionary (include/flate_hip.h).
+inline Err compress_batch(Engine &e, const std::vector<std::vector<uint8_t>> &streams, const DictTable &D,
+                          const std::vector<uint32_t> &dict_of, std::vector<std::vector<uint8_t>> &out,
+                          uint32_t flags = 0) {
+  if (!e.ok()) return make_error(e, e.status());
+  const uint32_t n = (uint32_t)streams.size();
+  if (!dict_of.empty() && dict_of.size() != n) return make_error(e, FLATE_HIP_E_INVALID);
+  std::vector<uint64_t> in_off(n + 1, 0), out_off(n + 1, 0);
+  uint64_t cap = 16;
+  for (uint32_t i = 0; i < n; ++i) {
+    in_off[i + 1] = in_off[i] + streams[i].size();
+    cap += flate_hip_deflate_bound(streams[i].size());
+  }
+  std::vector<uint8_t> in(in_off[n] + 1), buf(cap);
+  for (uint32_t i = 0; i < n; ++i)
+    std::copy(streams[i].begin(), streams[i].end(), in.begin() + in_off[i]);
+  const int rc = flate_hip_deflate_fast_batch_dict(e.ctx(), in.data(), in_off.data(), n, D.bytes.data(), D.off.data(),
+                                                   (uint32_t)D.off.size() - 1, dict_of.empty() ? nullptr : dict_of.data(),
+                                                   buf.data(), cap, out_off.data(), flags);
+  if (rc != 0) return make_error(e, rc);
+  out.resize(n);
+  for (uint32_t i = 0; i < n; ++i) out[i].assign(buf.begin() + out_off[i], buf.begin() + out_off[i + 1]);
+  return std::nullopt;
+}
+
 // The container formats around a raw stream (the reference has neither): zlib (RFC 1950: CMF, FLG,
 // data, Adler-32 big endian) and gzip (RFC 1952: ten header bytes, data, CRC-32 and length little endian).
 // The checksums come from the GPU (flate_hip_checksum_batch), the framing is these few bytes.
@@ -173,6 +215,7 @@ class Writer {
   // window and sets window_end, i.e. they are unprocessed DATA -- the stream is the one Writer::new
   // produces when those bytes are written first (the reference's own test asserts exactly that
   // equality, deflate_test.mbt:12-35).  Go ignores the dictionary at this level.
+  // (A dictionary as HISTORY, which the stream then needs to be read: BatchWriter with a DictTable.)
   static std::unique_ptr<Writer> new_dict(ByteSink &w, Engine &e, const uint8_t *dict, size_t n, uint32_t flags = 0) {
     std::unique_ptr<Writer> wr(new Writer(w, e, flags));
     constexpr size_t kDictWindow = 32768;  // window_size, deflate.mbt:12
@@ -264,9 +307,13 @@ class Writer {
 class BatchWriter {
  public:
   explicit BatchWriter(Engine &e, uint32_t flags = 0) : e_(e), flags_(flags) {}
-  Writer &add(ByteSink &sink) {
+  // With preset dictionaries as history (flate_hip_deflate_fast_batch_dict): `dicts` must outlive the
+  // BatchWriter; add(sink, j) gives a Writer dictionary j, add(sink) none.
+  BatchWriter(Engine &e, const DictTable &dicts, uint32_t flags = 0) : e_(e), flags_(flags), dicts_(&dicts) {}
+  Writer &add(ByteSink &sink, uint32_t dict = FLATE_HIP_NO_DICT) {
     ws_.emplace_back(new Writer(sink, e_, flags_));
     ws_.back()->batch_member_ = true;
+    dict_of_.push_back(dict);
     return *ws_.back();
   }
   size_t size() const { return ws_.size(); }
@@ -275,13 +322,15 @@ class BatchWriter {
   Err close_all() {
     std::vector<std::vector<uint8_t>> in, out;
     std::vector<Writer *> open;
-    for (auto &w : ws_)
-      if (!w->err_) {
-        open.push_back(w.get());
-        in.push_back(std::move(w->pending_));
+    std::vector<uint32_t> dict_of;
+    for (size_t k = 0; k < ws_.size(); ++k)
+      if (!ws_[k]->err_) {
+        open.push_back(ws_[k].get());
+        in.push_back(std::move(ws_[k]->pending_));
+        dict_of.push_back(dict_of_[k]);
       }
     if (open.empty()) return std::nullopt;
-    Err er = compress_batch(e_, in, out, flags_);
+    Err er = dicts_ ? compress_batch(e_, in, *dicts_, dict_of, out, flags_) : compress_batch(e_, in, out, flags_);
     Err first;
     for (size_t i = 0; i < open.size(); ++i) {
       Writer *w = open[i];
@@ -299,6 +348,8 @@ class BatchWriter {
  private:
   Engine &e_;
   uint32_t flags_;
+  const DictTable *dicts_ = nullptr;
+  std::vector<uint32_t> dict_of_;  // per Writer
   std::vector<std::unique_ptr<Writer>> ws_;
 };
 
@@ -397,19 +448,6 @@ inline Err decompress_batch(Engine &e, const std::vector<std::vector<uint8_t>> &
   }
   return std::nullopt;
 }
-
-// &Reader::new_dict(r, dict) (inflate.mbt:315-317) in batch form (flate_hip_inflate_batch_dict): dicts[j] is a
-// preset dictionary (only its last 32768 bytes are history), dict_of[i] the dictionary of stream i or
-// FLATE_HIP_NO_DICT; an empty dict_of: every stream uses dicts[0].
-struct DictTable {
-  std::vector<uint8_t> bytes;
-  std::vector<uint64_t> off;
-  explicit DictTable(const std::vector<std::vector<uint8_t>> &dicts) : off(dicts.size() + 1, 0) {
-    for (size_t j = 0; j < dicts.size(); ++j) off[j + 1] = off[j] + dicts[j].size();
-    bytes.resize(off.back() + 16);
-    for (size_t j = 0; j < dicts.size(); ++j) std::copy(dicts[j].begin(), dicts[j].end(), bytes.begin() + off[j]);
-  }
-};
 
 inline Err inflate_sizes(Engine &e, const std::vector<std::vector<uint8_t>> &streams,
                          const std::vector<std::vector<uint8_t>> &dicts, const std::vector<uint32_t> &dict_of,
