@@ -149,3 +149,30 @@ def test_uniform_search_is_the_count():
         s0 = 1 << (int(max(m, int(rng.integers(m, 400)))).bit_length() - 1)   # any power of two with 2 s0 > m
         assert _count_prefix(vals, m, s0, lambda v: v <= x) == int((vals <= x).sum())
         assert _count_prefix(vals, m, s0, lambda v: v < x) == int((vals < x).sum())
+
+
+def test_code_kernel_model_on_the_encode_corpus_limit_cases():
+    """The histograms of the encode corpus's length-limit cases (tests/encode_corpus.py), taken from the oracle's
+    tokens: model, oracle and -- in tests/test_gpu_encode_corpus.py -- the kernel are checked on the same data.
+    The model's lengths are also those the oracle wrote into the stream's header."""
+    import encode_corpus as E
+    o.build()
+    cases = {name: data for name, data, _ in E.cases()}
+    limited = 0
+    for name in ("fib_literals", "fib_literals_dynamic", "fib_offsets", "fib_code_lengths"):
+        b = E.Analysis(name, cases[name], E.MOONBIT, o).blocks[0]
+        h = b["hdr"]
+        cl_hist = np.bincount([s for s, _ in h["items"]], minlength=19)
+        tables = [(b["lit_hist"], 15, h["lit_lens"]), (cl_hist, 7, h["cl_lens"])]
+        if b["kind"] == E.DYN:
+            tables.append((b["dist_hist"], 15, h["dist_lens"]))
+        for f, mb, in_stream in tables:
+            f = np.asarray(f, np.int64)
+            want_codes, want_lens = o.huffman_generate(f.astype(np.int32), mb)
+            lens, codes = build_code_model(f, mb)
+            assert np.array_equal(lens, want_lens.astype(np.int64)), (name, mb)
+            used = lens > 0
+            assert np.array_equal(codes[used], want_codes.astype(np.int64)[used]), (name, mb)
+            assert lens[:len(in_stream)].tolist() == list(in_stream) and not lens[len(in_stream):].any(), (name, mb)
+            limited += int(lens.max() == mb and E.unlimited_depth(f) > mb)
+    assert limited >= 4   # 15-bit literal codes (twice), the 15-bit offset code, the 7-bit code-length code (twice)
