@@ -26,9 +26,17 @@ using namespace flate;
 
 namespace {
 
+// Device memory that belongs to one owner (the ctx, a stream handle): grown by ensure(), freed with the owner, whose
+// release function has selected the device.
 struct DevBuf {
   void *p = nullptr;
   size_t cap = 0;
+  DevBuf() = default;
+  DevBuf(const DevBuf &) = delete;
+  DevBuf &operator=(const DevBuf &) = delete;
+  ~DevBuf() {
+    if (p) (void)hipFree(p);
+  }
 };
 
 }  // namespace
@@ -168,12 +176,6 @@ int ensure(flate_hip_ctx *c, DevBuf &b, size_t bytes) {
   HIP_TRY(c, hipMalloc(&b.p, want));
   b.cap = want;
   return FLATE_HIP_OK;
-}
-
-void release(DevBuf &b) {
-  if (b.p) (void)hipFree(b.p);
-  b.p = nullptr;
-  b.cap = 0;
 }
 
 // ---- small index arrays: host <-> device through pinned staging and a copy kernel (copy_ctl_kernel) ----
@@ -346,6 +348,80 @@ int collect_timing(flate_hip_ctx *c, const bool used[FLATE_HIP_STAGE_COUNT]) {
   return FLATE_HIP_OK;
 }
 
+// The parameter blocks as far as the ctx owns what they point at (its scratch, its options); the callers add
+// the input, the index arrays and what is theirs alone.
+LzParams lz_params(const flate_hip_ctx *c, uint32_t flags) {
+  LzParams P{};  // (value-initialised: a field added later must never reach a kernel as stack garbage)
+  P.scan_off = (const uint16_t *)c->scan_tab.p;
+  P.scan_len = c->scan_len;
+  P.matches = (uint2 *)c->d_matches.p;
+  P.chunk_nmatch = (uint32_t *)c->d_nmatch.p;
+  P.chunk_ntok = (uint32_t *)c->d_ntok.p;
+  P.compat_go = (flags & FLATE_HIP_COMPAT_GO) ? 1u : 0u;
+  P.spin_limit = c->spin_limit;
+  P.status = (int *)c->d_status.p;
+  return P;
+}
+
+// spliced: the streams' blocks follow one another bit by bit (summaries in d_slot_off, bit positions in d_out_off)
+HuffParams huff_params(const flate_hip_ctx *c, uint32_t flags, bool spliced) {
+  HuffParams H{};
+  H.matches = (const uint2 *)c->d_matches.p;
+  H.chunk_nmatch = (const uint32_t *)c->d_nmatch.p;
+  H.chunk_ntok = (const uint32_t *)c->d_ntok.p;
+  H.blk_hist = (uint32_t *)c->d_blk_hist.p;
+  H.blk_cl = (uint32_t *)c->d_blk_cl.p;
+  H.blk_hdr = (uint32_t *)c->d_blk_hdr.p;
+  H.blk_meta = (uint4 *)c->d_blk_meta.p;
+  H.tile_meta = (uint8_t *)c->d_tile_meta.p;
+  H.spliced = spliced ? 1u : 0u;
+  H.stream_sum = spliced ? (uint64_t *)c->d_slot_off.p : nullptr;
+  H.stream_bit = spliced ? (const uint64_t *)c->d_out_off.p : nullptr;
+  H.out_len = (uint64_t *)c->d_out_len.p;
+  H.out_off = (const uint64_t *)c->d_out_off.p;
+  H.status = (int *)c->d_status.p;
+  H.compat_go = (flags & FLATE_HIP_COMPAT_GO) ? 1u : 0u;
+  return H;
+}
+
+// The encoder's device status word (not 0) as the call's return code.  A word of the scan kernels is a public
+// code already; everything from kStatusUqTimeout down is FLATE_HIP_E_INTERNAL, with what happened in hip_err.
+int encoder_status(flate_hip_ctx *c, int word) {
+  if (word > kStatusUqTimeout) return word;
+  if (word == kStatusNoProgress)
+    c->hip_err = "a match-finder batch made no progress (the chunk was abandoned)";
+  else if (word == kStatusLanesLost)
+    c->hip_err = "a persistent match-finder loop lost lanes of its wavefront (miscompiled loop?)";
+  else if (word == kStatusUqTimeout)
+    c->hip_err = "a match-finder block waited for a window that was never handed over";
+  else if (word == kStatusBadIndex)
+    c->hip_err = "a match-finder block was handed an index outside its scratch";
+  else if (word <= -0x100000)  // encoder self-check (huff_pack_kernel): -(0x100000 + stream)
+    c->hip_err = "packed bits differ from the computed block size in stream " +
+                 std::to_string((uint32_t)(-word) - 0x100000u) + " (mod 2^20)";
+  else
+    c->hip_err = "device status word " + std::to_string(word);
+  return FLATE_HIP_E_INTERNAL;
+}
+
+// A resident (LDS-table) kernel on c->stream and a guest (L2-table) kernel on c->guest_stream, side by side: the
+// blocks of both pull the `count` entries of one queue.  R / G: the two sides' parameters; extra: what both
+// kernels take after them.
+// The LDS-table kernel is submitted FIRST: its blocks need 26 contiguous LDS granules each, and guests that
+// reach a CU before them can leave it with room for three (measured: -1.4 % with this order, section 7 of
+// profiles/r05/README.md).
+template <typename... Extra>
+void launch_pair(flate_hip_ctx *c, void (*resident)(LzParams, Extra...), void (*guest)(LzParams, Extra...),
+                 uint32_t count, const LzParams &R, const LzParams &G, const Extra &...extra) {
+  (void)hipEventRecord(c->ev_fork, c->stream);
+  (void)hipStreamWaitEvent(c->guest_stream, c->ev_fork, 0);
+  const uint32_t blocks = c->resident_blocks < count ? c->resident_blocks : count;
+  hipLaunchKernelGGL(resident, dim3(blocks), dim3(64), 0, c->stream, R, extra...);
+  hipLaunchKernelGGL(guest, dim3((uint32_t)c->guest_blocks), dim3(64), 0, c->guest_stream, G, extra...);
+  (void)hipEventRecord(c->ev_join, c->guest_stream);
+  (void)hipStreamWaitEvent(c->stream, c->ev_join, 0);
+}
+
 // Upload the index arrays and run the match finder over every LZ77 chunk.
 // (the caller has checked that the launch is one persistent resident+guest launch in stream order)
 // DD: the preset dictionaries of the streams in pl.idsD (null: there are none)
@@ -371,32 +447,12 @@ int run_lz77(flate_hip_ctx *c, const uint8_t *d_in, const uint64_t *in_off, cons
     if ((rc = ctl_up(c, c->d_idsD.p, pl.idsD.data(), pl.idsD.size() * 4))) return rc;
   }
 
-  LzParams P{};  // (value-initialised: a field added later must never reach a kernel as stack garbage)
+  LzParams P = lz_params(c, flags);
   P.in = d_in;
   P.in_off = (const uint64_t *)c->d_in_off.p;
   P.chunk_base = (const uint32_t *)c->d_chunk_base.p;
-  P.stream_ids = nullptr;
-  P.scan_off = (const uint16_t *)c->scan_tab.p;
-  P.scan_len = c->scan_len;
-  P.matches = (uint2 *)c->d_matches.p;
-  P.chunk_nmatch = (uint32_t *)c->d_nmatch.p;
-  P.chunk_ntok = (uint32_t *)c->d_ntok.p;
-  P.compat_go = (flags & FLATE_HIP_COMPAT_GO) ? 1u : 0u;
-  P.debug = nullptr;
-  P.gtables = nullptr;
-  P.queue = nullptr;
-  P.queue_end = 0;
-  P.gtable_blocks = 0;
-  P.spin_limit = c->spin_limit;
-  P.inject_drop_push = c->inject_drop_push;
+  P.inject_drop_push = c->inject_drop_push;  // (the test hooks act on batch launches only)
   P.inject_stall = c->inject_stall;
-  P.taken = nullptr;
-  P.uq_ready = nullptr;
-  P.uq_ctr = nullptr;
-  P.uq_units = 0;
-  P.uq_tables = nullptr;
-  P.uq_sweep = nullptr;
-  P.status = (int *)c->d_status.p;
   c->last_count[0] = c->last_count[1] = 0;
   // multi-window streams of a persistent launch run one window at a time (see uq_run): the
   // streams' tables rest in global memory between windows (32 KiB each; the ready word limits it
@@ -451,23 +507,23 @@ int run_lz77(flate_hip_ctx *c, const uint8_t *d_in, const uint64_t *in_off, cons
     } else {
       // single-window streams (ids16) and multi-window streams (ids32) use the same 32 KiB
       // 16-bit tables; the latter add the periodic sweep (MULTI)
+      // a persistent launch: the blocks of both kernels take their streams from word `queue_word` of d_queue
+      auto queued = [&](LzParams X, uint32_t queue_word, uint32_t count) {
+        X.gtables = c->d_gtables.p;
+        X.gtable_blocks = (uint32_t)c->guest_blocks;  // d_gtables holds exactly this many tables
+        X.queue = (uint32_t *)c->d_queue.p + queue_word;
+        X.queue_end = count;
+        return X;
+      };
       auto launch = [&](const DevBuf &ids, uint32_t count, bool multi, uint32_t queue_slot) {
         if (!count) return;
         P.stream_ids = (const uint32_t *)ids.p;
-        const bool guests = c->guest_blocks > 0 && count >= c->guest_min;
-        if (!guests) {
-          if (multi)
-            hipLaunchKernelGGL(lz77_wave_kernel<true>, dim3(count), dim3(64), 0, c->stream, P);
-          else
-            hipLaunchKernelGGL(lz77_wave_kernel<false>, dim3(count), dim3(64), 0, c->stream, P);
+        void (*wave)(LzParams) = multi ? lz77_wave_kernel<true> : lz77_wave_kernel<false>;
+        if (!(c->guest_blocks > 0 && count >= c->guest_min)) {
+          hipLaunchKernelGGL(wave, dim3(count), dim3(64), 0, c->stream, P);
           return;
         }
-        // fork: resident (LDS-table) and guest (L2-table) blocks pull streams from one queue
-        LzParams G = P;
-        G.gtables = c->d_gtables.p;
-        G.gtable_blocks = (uint32_t)c->guest_blocks;  // d_gtables holds exactly this many tables
-        G.queue = (uint32_t *)c->d_queue.p + queue_slot;
-        G.queue_end = count;
+        LzParams G = queued(P, queue_slot, count);
         c->last_count[queue_slot] = count;
         if (multi && uq_units) {
           G.uq_ready = (uint32_t *)c->d_uq_ready.p;
@@ -489,24 +545,7 @@ int run_lz77(flate_hip_ctx *c, const uint8_t *d_in, const uint64_t *in_off, cons
           G.stream_ids = P.stream_ids + c->profile_split;
           G.queue_end = count - c->profile_split;
         }
-        (void)hipEventRecord(c->ev_fork, c->stream);
-        (void)hipStreamWaitEvent(c->guest_stream, c->ev_fork, 0);
-        uint32_t resident = c->resident_blocks < count ? c->resident_blocks : count;
-        // The LDS-table kernel is submitted FIRST: its blocks need 26 contiguous LDS granules each, and guests that
-        // reach a CU before them can leave it with room for three (measured: -1.4 % with this order, section 7 of
-        // profiles/r05/README.md).
-        if (multi) {
-          hipLaunchKernelGGL(lz77_wave_kernel<true>, dim3(resident), dim3(64), 0, c->stream, R);
-          hipLaunchKernelGGL(lz77_guest_kernel<true>, dim3((uint32_t)c->guest_blocks), dim3(64), 0,
-                             c->guest_stream, G);
-          (void)hipEventRecord(c->ev_join, c->guest_stream);
-        } else {
-          hipLaunchKernelGGL(lz77_wave_kernel<false>, dim3(resident), dim3(64), 0, c->stream, R);
-          hipLaunchKernelGGL(lz77_guest_kernel<false>, dim3((uint32_t)c->guest_blocks), dim3(64), 0,
-                             c->guest_stream, G);
-          (void)hipEventRecord(c->ev_join, c->guest_stream);
-        }
-        (void)hipStreamWaitEvent(c->stream, c->ev_join, 0);
+        launch_pair(c, wave, multi ? lz77_guest_kernel<true> : lz77_guest_kernel<false>, count, R, G);
       };
       launch(c->d_ids16, (uint32_t)pl.ids16.size(), false, 0);
       launch(c->d_ids32, (uint32_t)pl.ids32.size(), true, 1);
@@ -521,18 +560,8 @@ int run_lz77(flate_hip_ctx *c, const uint8_t *d_in, const uint64_t *in_off, cons
         if (!(c->guest_blocks > 0 && count >= c->guest_min)) {
           hipLaunchKernelGGL(lz77_wave_dict_kernel, dim3(count), dim3(64), 0, c->stream, Q, DD->dev);
         } else {
-          Q.gtables = c->d_gtables.p;
-          Q.gtable_blocks = (uint32_t)c->guest_blocks;
-          Q.queue = (uint32_t *)c->d_queue.p + 8;
-          Q.queue_end = count;
-          (void)hipEventRecord(c->ev_fork, c->stream);
-          (void)hipStreamWaitEvent(c->guest_stream, c->ev_fork, 0);
-          const uint32_t resident = c->resident_blocks < count ? c->resident_blocks : count;
-          hipLaunchKernelGGL(lz77_wave_dict_kernel, dim3(resident), dim3(64), 0, c->stream, Q, DD->dev);
-          hipLaunchKernelGGL(lz77_guest_dict_kernel, dim3((uint32_t)c->guest_blocks), dim3(64), 0, c->guest_stream, Q,
-                             DD->dev);
-          (void)hipEventRecord(c->ev_join, c->guest_stream);
-          (void)hipStreamWaitEvent(c->stream, c->ev_join, 0);
+          Q = queued(Q, 8, count);
+          launch_pair(c, lz77_wave_dict_kernel, lz77_guest_dict_kernel, count, Q, Q, DD->dev);
         }
       }
     }
@@ -674,25 +703,13 @@ void flate_hip_destroy(flate_hip_ctx *c) {
   if (c->ctl_down_buf.p) (void)hipHostFree(c->ctl_down_buf.p);
   if (c->h2d_stream) (void)hipStreamDestroy(c->h2d_stream);
   if (c->d2h_stream) (void)hipStreamDestroy(c->d2h_stream);
-  for (DevBuf *b : {&c->scan_tab, &c->d_in, &c->d_out, &c->d_in_off, &c->d_chunk_base, &c->d_ids16,
-                    &c->d_ids32, &c->d_matches, &c->d_nmatch, &c->d_ntok, &c->d_blk_base,
-                    &c->d_blk_hist, &c->d_blk_cl, &c->d_blk_hdr, &c->d_blk_meta, &c->d_tile_meta, &c->d_blk_sid, &c->d_slot_off, &c->d_out_len, &c->d_out_off, &c->d_status, &c->d_istatus,
-                    &c->d_ierr, &c->d_debug, &c->d_gtables, &c->d_queue, &c->d_simt_lens,
-                    &c->d_dicts, &c->d_dict_at, &c->d_dict_len, &c->d_idsD, &c->d_lz_slot_of, &c->d_lz_tables,
-                    &c->d_lz_clocks})
-    release(*b);
   for (auto &e : c->ev)
     if (e) (void)hipEventDestroy(e);
   if (c->guest_stream) (void)hipStreamDestroy(c->guest_stream);
-  release(c->d_uq_ready);
-  release(c->d_uq_tables);
-  release(c->d_uq_sweep);
-  release(c->d_aux[0]);
-  release(c->d_aux[1]);
   if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
   if (c->ev_join) (void)hipEventDestroy(c->ev_join);
   if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
-  delete c;
+  delete c;  // (and with it every DevBuf)
 }
 
 int flate_hip_set_stream(flate_hip_ctx *c, void *hip_stream) {
@@ -880,28 +897,13 @@ static int deflate_common(flate_hip_ctx *c, const uint8_t *in, const uint64_t *i
 
   if ((rc = run_lz77(c, d_in, in_off, pl, flags, DD))) return rc;
 
-  HuffParams H{};
+  HuffParams H = huff_params(c, flags, spliced);
   H.in = d_in;
   H.in_off = (const uint64_t *)c->d_in_off.p;
   H.chunk_base = (const uint32_t *)c->d_chunk_base.p;
   H.blk_base = (const uint32_t *)c->d_blk_base.p;
-  H.matches = (const uint2 *)c->d_matches.p;
-  H.chunk_nmatch = (const uint32_t *)c->d_nmatch.p;
-  H.chunk_ntok = (const uint32_t *)c->d_ntok.p;
-  H.blk_hist = (uint32_t *)c->d_blk_hist.p;
-  H.blk_cl = (uint32_t *)c->d_blk_cl.p;
-  H.blk_hdr = (uint32_t *)c->d_blk_hdr.p;
-  H.blk_meta = (uint4 *)c->d_blk_meta.p;
-  H.tile_meta = (uint8_t *)c->d_tile_meta.p;
-  H.spliced = spliced ? 1u : 0u;
-  H.stream_sum = spliced ? (uint64_t *)c->d_slot_off.p : nullptr;
-  H.stream_bit = spliced ? (const uint64_t *)c->d_out_off.p : nullptr;
-  H.out_len = (uint64_t *)c->d_out_len.p;
-  H.out_off = (const uint64_t *)c->d_out_off.p;
   H.out = d_out;
-  H.status = (int *)c->d_status.p;
   H.n_streams = n;
-  H.compat_go = (flags & FLATE_HIP_COMPAT_GO) ? 1u : 0u;
   H.blk_sid = per_block ? (const uint32_t *)c->d_blk_sid.p : nullptr;
   CompactParams C{};
   C.out_len = (const uint64_t *)c->d_out_len.p;
@@ -946,28 +948,7 @@ static int deflate_common(flate_hip_ctx *c, const uint8_t *in, const uint64_t *i
   HIP_TRY(c, hipGetLastError());
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   ctl_finish(c);
-  if (c->h_status_word) {
-    if (c->h_status_word == kStatusNoProgress) {
-      c->hip_err = "a match-finder batch made no progress (the chunk was abandoned)";
-      return FLATE_HIP_E_INTERNAL;
-    }
-    if (c->h_status_word == kStatusLanesLost) {
-      c->hip_err = "a persistent match-finder loop lost lanes of its wavefront (miscompiled loop?)";
-      return FLATE_HIP_E_INTERNAL;
-    }
-    if (c->h_status_word == kStatusUqTimeout || c->h_status_word == kStatusBadIndex) {
-      c->hip_err = c->h_status_word == kStatusUqTimeout
-                       ? "a match-finder block waited for a window that was never handed over"
-                       : "a match-finder block was handed an index outside its scratch";
-      return FLATE_HIP_E_INTERNAL;
-    }
-    if (c->h_status_word <= -0x100000) {  // encoder self-check (huff_pack_kernel): -(0x100000 + stream)
-      c->hip_err = "packed bits differ from the computed block size in stream " +
-                   std::to_string((uint32_t)(-c->h_status_word) - 0x100000u) + " (mod 2^20)";
-      return FLATE_HIP_E_INTERNAL;
-    }
-    return c->h_status_word;
-  }
+  if (c->h_status_word) return encoder_status(c, c->h_status_word);
   produced = spliced ? c->h_total_bytes : out_off[n];
   if (total_bytes) *total_bytes = produced;
   if (!dev) {
@@ -1421,18 +1402,10 @@ int stream_write_impl(flate_hip_stream *st, const uint8_t *in, uint64_t n, bool 
   if ((rc = ensure(c, c->d_ntok, (size_t)nch * 4 + 4))) return rc;
   HIP_TRY(c, hipMemsetAsync(c->d_status.p, 0, 4, c->stream));
   if (nch) {
-    LzParams P{};
+    LzParams P = lz_params(c, st->flags);
     P.in = stage + kHist - W0;  // virtual: only positions >= W0 - 32768 are ever dereferenced
     P.in_off = d_off_abs;
     P.chunk_base = d_chunk_base;
-    P.scan_off = (const uint16_t *)c->scan_tab.p;
-    P.scan_len = c->scan_len;
-    P.matches = (uint2 *)c->d_matches.p;
-    P.chunk_nmatch = (uint32_t *)c->d_nmatch.p;
-    P.chunk_ntok = (uint32_t *)c->d_ntok.p;
-    P.compat_go = (st->flags & FLATE_HIP_COMPAT_GO) ? 1u : 0u;
-    P.status = (int *)c->d_status.p;
-    P.spin_limit = c->spin_limit;
     // One launch per run of windows between two shift_offsets of the reference (one launch, except
     // for the piece in which `cur` passes buffer_reset: window 32 766 of a Writer, then every 32 767).
     const bool forgets = !(st->flags & FLATE_HIP_COMPAT_GO);
@@ -1473,28 +1446,13 @@ int stream_write_impl(flate_hip_stream *st, const uint8_t *in, uint64_t n, bool 
   if ((rc = ensure(c, c->d_out_off, 4 * 8))) return rc;
   if ((rc = ensure(c, c->d_slot_off, 4 * 16))) return rc;
   uint8_t *d_out = (uint8_t *)st->out.p;
-  HuffParams H{};
+  HuffParams H = huff_params(c, st->flags, true);
   H.in = stage + kHist;
   H.in_off = d_off_loc;
   H.chunk_base = d_chunk_base;
   H.blk_base = d_blk_base;
-  H.matches = (const uint2 *)c->d_matches.p;
-  H.chunk_nmatch = (const uint32_t *)c->d_nmatch.p;
-  H.chunk_ntok = (const uint32_t *)c->d_ntok.p;
-  H.blk_hist = (uint32_t *)c->d_blk_hist.p;
-  H.blk_cl = (uint32_t *)c->d_blk_cl.p;
-  H.blk_hdr = (uint32_t *)c->d_blk_hdr.p;
-  H.blk_meta = (uint4 *)c->d_blk_meta.p;
-  H.tile_meta = (uint8_t *)c->d_tile_meta.p;
-  H.spliced = 1u;
-  H.stream_sum = (uint64_t *)c->d_slot_off.p;
-  H.stream_bit = (const uint64_t *)c->d_out_off.p;
-  H.out_len = (uint64_t *)c->d_out_len.p;
-  H.out_off = (const uint64_t *)c->d_out_off.p;
   H.out = d_out;
-  H.status = (int *)c->d_status.p;
   H.n_streams = 1;
-  H.compat_go = (st->flags & FLATE_HIP_COMPAT_GO) ? 1u : 0u;
   H.no_close = final ? 0u : 1u;
   SpliceParams S{};
   S.sum = (const uint64_t *)c->d_slot_off.p;
@@ -1520,7 +1478,7 @@ int stream_write_impl(flate_hip_stream *st, const uint8_t *in, uint64_t n, bool 
   if (!final && n >= kHist)  // what the next piece may still reference
     HIP_TRY(c, hipMemcpyAsync(st->hist.p, stage + n, kHist, hipMemcpyDeviceToDevice, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
-  if (c->h_status_word) return c->h_status_word <= kStatusUqTimeout ? FLATE_HIP_E_INTERNAL : c->h_status_word;
+  if (c->h_status_word) return encoder_status(c, c->h_status_word);
   const uint64_t whole = final ? h_pos[1] : (h_pos[0] >> 3);
   if (whole > out_cap) return FLATE_HIP_E_OUT_TOO_SMALL;
   if (whole) HIP_TRY(c, hipMemcpyAsync(out, d_out, whole, hipMemcpyDeviceToHost, c->stream));
@@ -1551,7 +1509,6 @@ int flate_hip_stream_open(flate_hip_ctx *c, uint32_t flags, flate_hip_stream **o
 void flate_hip_stream_free(flate_hip_stream *st) {
   if (!st) return;
   (void)hipSetDevice(st->ctx->device);
-  for (DevBuf *b : {&st->table, &st->clock, &st->hist, &st->stage, &st->io, &st->out}) release(*b);
   delete st;
 }
 
@@ -1603,7 +1560,6 @@ int flate_hip_inflate_stream_open(flate_hip_ctx *c, flate_hip_inflate_stream **o
     if (hipGetLastError() != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) rc = FLATE_HIP_E_HIP;
   }
   if (rc != FLATE_HIP_OK) {
-    release(st->state);
     delete st;
     return rc;
   }
@@ -1640,7 +1596,6 @@ int flate_hip_inflate_stream_reset(flate_hip_inflate_stream *st, const uint8_t *
 void flate_hip_inflate_stream_free(flate_hip_inflate_stream *st) {
   if (!st) return;
   (void)hipSetDevice(st->ctx->device);
-  for (DevBuf *b : {&st->state, &st->in, &st->out}) release(*b);
   delete st;
 }
 
@@ -1722,7 +1677,7 @@ int flate_hip_lz77_matches(flate_hip_ctx *c, const uint8_t *in, const uint64_t *
                             hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipMemcpyAsync(&c->h_status_word, c->d_status.p, 4, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
-  if (c->h_status_word) return c->h_status_word <= kStatusUqTimeout ? FLATE_HIP_E_INTERNAL : c->h_status_word;
+  if (c->h_status_word) return encoder_status(c, c->h_status_word);
   for (uint32_t k = 0; k <= pl.n_chunks; ++k) chunk_rec_off[k] = (uint64_t)k * kMatchCapPerChunk;
   const hipMemcpyKind kind = dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
   HIP_TRY(c, hipMemcpyAsync(recs, c->d_matches.p, (size_t)pl.n_chunks * kMatchCapPerChunk * 8, kind,
@@ -1979,6 +1934,53 @@ static bool dict_args_ok(const uint8_t *dicts, const uint64_t *dict_off, uint32_
   return true;
 }
 
+// The dictionaries a *_batch_dict call uses, as slots: a slot is one dictionary that some stream names and whose
+// tail -- its last kMaxMatchOffset bytes, the history a stream can reach -- has at least min_len bytes.  The tails
+// lie one after another in c->d_dicts, each 16-byte aligned and followed by 16 bytes that a 16-byte load may touch.
+struct DictSlots {
+  static constexpr uint32_t kNone = ~0u;
+  std::vector<uint32_t> dict, len;  // per slot: the dictionary, the length of its tail
+  std::vector<uint64_t> at;         // per slot: where the tail starts in d_dicts
+  std::vector<uint32_t> slot_of;    // per stream: its slot, or kNone
+  uint64_t total = 0;               // bytes of d_dicts
+};
+
+// (host only, after dict_args_ok: the entry points make every check before any HIP call)
+static DictSlots dict_slots(const uint64_t *dict_off, uint32_t n_dicts, const uint32_t *dict_of, uint32_t n,
+                            uint32_t min_len) {
+  DictSlots S;
+  S.slot_of.assign(n, DictSlots::kNone);
+  std::vector<uint32_t> slot_of_dict(n_dicts, DictSlots::kNone);
+  for (uint32_t i = 0; i < n; ++i) {
+    const uint32_t j = dict_of ? dict_of[i] : 0u;
+    if (j == FLATE_HIP_NO_DICT) continue;
+    const uint64_t l = dict_off[j + 1] - dict_off[j];
+    const uint32_t tail = l < (uint64_t)kMaxMatchOffset ? (uint32_t)l : (uint32_t)kMaxMatchOffset;
+    if (tail < min_len) continue;
+    if (slot_of_dict[j] == DictSlots::kNone) {
+      slot_of_dict[j] = (uint32_t)S.at.size();
+      S.dict.push_back(j);
+      S.len.push_back(tail);
+      S.at.push_back(S.total);
+      S.total += ((uint64_t)tail + 16 + 15) & ~15ull;
+    }
+    S.slot_of[i] = slot_of_dict[j];
+  }
+  return S;
+}
+
+// the slots' tails into c->d_dicts (on c->stream; the caller synchronises)
+static int dict_upload(flate_hip_ctx *c, const DictSlots &S, const uint8_t *dicts, const uint64_t *dict_off,
+                       uint32_t flags) {
+  const int rc = ensure(c, c->d_dicts, S.total);
+  if (rc) return rc;
+  const hipMemcpyKind kind = (flags & FLATE_HIP_DEVICE_PTRS) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+  for (size_t k = 0; k < S.at.size(); ++k)
+    HIP_TRY(c, hipMemcpyAsync((uint8_t *)c->d_dicts.p + S.at[k], dicts + dict_off[S.dict[k] + 1] - S.len[k], S.len[k],
+                              kind, c->stream));
+  return FLATE_HIP_OK;
+}
+
 // flate_hip_inflate_batch after its checks; D: the streams' dictionaries (flate_hip_inflate_batch_dict)
 static int inflate_batch_run(flate_hip_ctx *c, const uint8_t *in, const uint64_t *in_off, uint32_t n,
                              uint8_t *out, const uint64_t *out_off, uint64_t *out_len,
@@ -2025,47 +2027,26 @@ int flate_hip_inflate_batch_dict(flate_hip_ctx *c, const uint8_t *in, const uint
   if (rc != FLATE_HIP_OK && rc != FLATE_HIP_E_TOO_LARGE) return rc;
   if (!dict_args_ok(dicts, dict_off, n_dicts, dict_of, n)) return FLATE_HIP_E_INVALID;
   // the history each stream starts with: the last kMaxMatchOffset bytes of its dictionary
-  auto tail_len = [&](uint32_t j) -> uint32_t {
-    const uint64_t l = dict_off[j + 1] - dict_off[j];
-    return l < (uint64_t)kMaxMatchOffset ? (uint32_t)l : (uint32_t)kMaxMatchOffset;
-  };
-  auto dict_of_stream = [&](uint32_t i) { return dict_of ? dict_of[i] : 0u; };
-  bool any = false;
-  for (uint32_t i = 0; i < n && !any; ++i) any = dict_of_stream(i) != FLATE_HIP_NO_DICT && tail_len(dict_of_stream(i)) != 0;
-  if (!any)  // no stream has history in front of it: the plain call, its path and its results
+  const DictSlots S = dict_slots(dict_off, n_dicts, dict_of, n, 1);
+  if (S.at.empty())  // no stream has history in front of it: the plain call, its path and its results
     return flate_hip_inflate_batch(c, in, in_off, n, out, out_off, out_len, status, err_off, flags);
   c->hip_err.clear();
   if (rc) return rc;
-  // every used dictionary's tail once, each followed by 16 bytes that a 16-byte load may touch
-  std::vector<uint64_t> tail_at(n_dicts, ~0ull);
-  uint64_t total = 0;
-  for (uint32_t i = 0; i < n; ++i) {
-    const uint32_t j = dict_of_stream(i);
-    if (j == FLATE_HIP_NO_DICT || tail_len(j) == 0 || tail_at[j] != ~0ull) continue;
-    tail_at[j] = total;
-    total += ((uint64_t)tail_len(j) + 16 + 15) & ~15ull;
-  }
-  std::vector<uint64_t> h_at(n, 0);
+  std::vector<uint64_t> h_at(n, 0);  // the decoders take {at, len} per stream (0 = none)
   std::vector<uint32_t> h_len(n, 0);
   for (uint32_t i = 0; i < n; ++i) {
-    const uint32_t j = dict_of_stream(i);
-    if (j == FLATE_HIP_NO_DICT || tail_len(j) == 0) continue;
-    h_at[i] = tail_at[j];
-    h_len[i] = tail_len(j);
+    if (S.slot_of[i] == DictSlots::kNone) continue;
+    h_at[i] = S.at[S.slot_of[i]];
+    h_len[i] = S.len[S.slot_of[i]];
   }
   HIP_TRY(c, hipSetDevice(c->device));
-  if ((rc = ensure(c, c->d_dicts, total))) return rc;
+  if ((rc = dict_upload(c, S, dicts, dict_off, flags))) return rc;
   if ((rc = ensure(c, c->d_dict_at, (size_t)n * 8))) return rc;
   if ((rc = ensure(c, c->d_dict_len, (size_t)n * 4))) return rc;
-  uint8_t *d_dicts = (uint8_t *)c->d_dicts.p;
-  const hipMemcpyKind kind = (flags & FLATE_HIP_DEVICE_PTRS) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-  for (uint32_t j = 0; j < n_dicts; ++j)
-    if (tail_at[j] != ~0ull)
-      HIP_TRY(c, hipMemcpyAsync(d_dicts + tail_at[j], dicts + dict_off[j + 1] - tail_len(j), tail_len(j), kind, c->stream));
   HIP_TRY(c, hipMemcpyAsync(c->d_dict_at.p, h_at.data(), (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
   HIP_TRY(c, hipMemcpyAsync(c->d_dict_len.p, h_len.data(), (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
-  const InfDict D{d_dicts, (const uint64_t *)c->d_dict_at.p, (const uint32_t *)c->d_dict_len.p, h_len.data()};
+  const InfDict D{(const uint8_t *)c->d_dicts.p, (const uint64_t *)c->d_dict_at.p, (const uint32_t *)c->d_dict_len.p, h_len.data()};
   return inflate_batch_run(c, in, in_off, n, out, out_off, out_len, status, err_off, flags, &D);
 }
 
@@ -2078,63 +2059,33 @@ int flate_hip_deflate_fast_batch_dict(flate_hip_ctx *c, const uint8_t *in, const
   if (!dict_args_ok(dicts, dict_off, n_dicts, dict_of, n)) return FLATE_HIP_E_INVALID;
   // DeflateFast::encode(d) over the last 32768 bytes of the dictionary; under 17 bytes that call is the
   // small-input path (deflate-fast.mbt:136-140) and leaves nothing behind
-  auto tail_len = [&](uint32_t j) -> uint32_t {
-    const uint64_t l = dict_off[j + 1] - dict_off[j];
-    return l < (uint64_t)kMaxMatchOffset ? (uint32_t)l : (uint32_t)kMaxMatchOffset;
-  };
-  auto dict_of_stream = [&](uint32_t i) { return dict_of ? dict_of[i] : 0u; };
-  std::vector<uint8_t> has(n, 0);
-  bool any = false;
-  for (uint32_t i = 0; i < n; ++i) {
-    const uint32_t j = dict_of_stream(i);
-    has[i] = j != FLATE_HIP_NO_DICT && tail_len(j) >= (uint32_t)kSmallHuffMin;
-    any = any || has[i];
-  }
-  if (!any)  // no stream's encoder has seen a dictionary: the plain call, its kernels and its bytes
+  const DictSlots S = dict_slots(dict_off, n_dicts, dict_of, n, (uint32_t)kSmallHuffMin);
+  if (S.at.empty())  // no stream's encoder has seen a dictionary: the plain call, its kernels and its bytes
     return flate_hip_deflate_fast_batch(c, in, in_off, n, out, out_cap, out_off, flags);
   if (flags & FLATE_HIP_LZ_SERIAL) return FLATE_HIP_E_INVALID;  // (the single-lane kernel has no dictionary build)
+  std::vector<uint8_t> has(n);
+  for (uint32_t i = 0; i < n; ++i) has[i] = S.slot_of[i] != DictSlots::kNone;
   {
     StagePlan pl;  // the whole index, before the context is touched
     const int rc = make_plan(in_off, n, pl, flags, has.data());
     if (rc) return rc;
   }
   c->hip_err.clear();
-  // every used dictionary's tail once (a slot), each followed by 16 bytes
-  std::vector<uint32_t> slot_of_dict(n_dicts, ~0u), h_slot_of(n, 0), h_len;
-  std::vector<uint64_t> h_at;
-  uint64_t total = 0;
-  for (uint32_t i = 0; i < n; ++i) {
-    if (!has[i]) continue;
-    const uint32_t j = dict_of_stream(i);
-    if (slot_of_dict[j] == ~0u) {
-      slot_of_dict[j] = (uint32_t)h_at.size();
-      h_at.push_back(total);
-      h_len.push_back(tail_len(j));
-      total += ((uint64_t)tail_len(j) + 16 + 15) & ~15ull;
-    }
-    h_slot_of[i] = slot_of_dict[j];
-  }
-  const uint32_t n_slots = (uint32_t)h_at.size();
+  const uint32_t n_slots = (uint32_t)S.at.size();
   HIP_TRY(c, hipSetDevice(c->device));
   int rc;
-  if ((rc = ensure(c, c->d_dicts, total))) return rc;
+  if ((rc = dict_upload(c, S, dicts, dict_off, flags))) return rc;
   if ((rc = ensure(c, c->d_dict_at, (size_t)n_slots * 8))) return rc;
   if ((rc = ensure(c, c->d_dict_len, (size_t)n_slots * 4))) return rc;
   if ((rc = ensure(c, c->d_lz_slot_of, (size_t)n * 4))) return rc;
   if ((rc = ensure(c, c->d_lz_tables, (size_t)n_slots * kTableSize * 2))) return rc;
   if ((rc = ensure(c, c->d_lz_clocks, (size_t)n_slots * 4))) return rc;
-  uint8_t *d_dicts = (uint8_t *)c->d_dicts.p;
-  const hipMemcpyKind kind = (flags & FLATE_HIP_DEVICE_PTRS) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-  for (uint32_t j = 0; j < n_dicts; ++j)
-    if (slot_of_dict[j] != ~0u)
-      HIP_TRY(c, hipMemcpyAsync(d_dicts + h_at[slot_of_dict[j]], dicts + dict_off[j + 1] - tail_len(j), tail_len(j), kind,
-                                c->stream));
-  HIP_TRY(c, hipMemcpyAsync(c->d_dict_at.p, h_at.data(), (size_t)n_slots * 8, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(c->d_dict_len.p, h_len.data(), (size_t)n_slots * 4, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(c->d_lz_slot_of.p, h_slot_of.data(), (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(c->d_dict_at.p, S.at.data(), (size_t)n_slots * 8, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(c->d_dict_len.p, S.len.data(), (size_t)n_slots * 4, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(c->d_lz_slot_of.p, S.slot_of.data(), (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   DeflDict DD{};
-  DD.dev.dict_buf = d_dicts;
+  DD.dev.dict_buf = (const uint8_t *)c->d_dicts.p;
   DD.dev.dict_at = (const uint64_t *)c->d_dict_at.p;
   DD.dev.dict_len = (const uint32_t *)c->d_dict_len.p;
   DD.dev.slot_of = (const uint32_t *)c->d_lz_slot_of.p;

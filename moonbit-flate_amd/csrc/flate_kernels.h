@@ -165,8 +165,6 @@ __global__ void uq_init_kernel(uint32_t *ready, uint32_t *ctr, uint32_t n_stream
 __global__ void scan_sizes_kernel(CompactParams P);
 // small index arrays between pinned host staging and the device (see compact_kernels.hip)
 __global__ void copy_ctl_kernel(uint32_t *dst, const uint32_t *src, size_t nwords);
-// spins (bounded) until *counter >= target: gates a sub-batch of the entropy stage on the match
-// finder that is still running on another stream
 __global__ void inflate_kernel(InfParams P);
 // the same decoders with preset dictionaries (InfParams::dict_*): the no-dictionary kernels keep their code
 __global__ void inflate_dict_kernel(InfParams P);

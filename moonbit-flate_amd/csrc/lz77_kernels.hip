@@ -966,80 +966,20 @@ FLATE_D uint32_t uq_run(const LzParams &P, const UqUnit u, uint16_t *table, int 
   return 0x80000000u | u.q;  // the stream is finished (entry < 2^17: the flag bit is free)
 }
 
-// Resident kernel: table in LDS (32 KiB per stream => 5 streams per CU).
-template <bool MULTI>
-__global__ __launch_bounds__(64) void lz77_wave_kernel(LzParams P) {
-  __shared__ uint16_t table[kTableSize];
-  const int lane = threadIdx.x;
-  if (MULTI && P.uq_ready) {  // persistent, one window at a time (see uq_run)
-    uint32_t push_word = 0;
-    uint32_t mine = 0;
-    for (;;) {
-      const UqUnit u = uq_pop(P, push_word, lane);
-      if (__builtin_amdgcn_readfirstlane((int)u.ok) == 0) break;
-      push_word = (uint32_t)__builtin_amdgcn_readfirstlane((int)uq_run<false>(P, u, table, lane));
-      all_lanes_here(P, lane);
-      ++mine;
-    }
-    if (P.taken && lane == 0) __hip_atomic_fetch_add(P.taken, mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    return;
-  }
-  // Either one block per stream (P.queue == null) or persistent: resident and guest blocks
-  // share one queue (dynamic balance).  One call site keeps a single copy of the parser.
-  uint32_t mine = 0;  // streams taken
-  for (bool first = true;; first = false) {
-    uint32_t q;
-    if (P.queue) {
-      q = 0;
-      if (lane == 0) q = atomicAdd(P.queue, 1u);  // (the ONE lane-0 block of the loop: see uq_pop)
-      q = (uint32_t)__builtin_amdgcn_readfirstlane((int)q);
-      if (q >= P.queue_end) break;
-    } else {
-      if (!first) break;
-      q = blockIdx.x;
-    }
-    __syncthreads();
-    lz77_stream<MULTI>(P, P.stream_ids ? P.stream_ids[q] : q, table, lane);
-    __syncthreads();
-    all_lanes_here(P, lane);
-    ++mine;
-  }
-  if (P.taken && lane == 0) __hip_atomic_fetch_add(P.taken, mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// Guest kernel: the LDS of a CU holds only five 32 KiB tables, but its SIMDs are mostly idle
-// (the parser is latency-bound).  A small persistent grid of extra wavefronts runs the same
-// parser with tables in HBM scratch -- few enough that those tables stay in the 4 MiB L2 of
-// their XCD -- and pulls streams from a queue.
-template <bool MULTI>
-__global__ __launch_bounds__(64) void lz77_guest_kernel(LzParams P) {
-  if (blockIdx.x >= P.gtable_blocks) return;  // (gtables holds one table per block of this launch)
-  uint16_t *table = reinterpret_cast<uint16_t *>(P.gtables) + (size_t)blockIdx.x * kTableSize;
-  const int lane = threadIdx.x;
-  // (round 2 gave multi-window guests no tags: -7 % with them at equal geometry, but the window
-  // units hand a stream from block to block and the tags did not travel; round 3 rebuilds them at the
-  // start of a unit instead, see uq_run)
-  __shared__ uint32_t tag_mem[kTagSlots / 16];  // see tag_of, kTagSlots
-  uint32_t *tags = tag_mem;
-  if (MULTI && P.uq_ready) {  // persistent, one window at a time, table in place (see uq_run)
-    uint32_t push_word = 0;
-    for (;;) {
-      const UqUnit u = uq_pop(P, push_word, lane);
-      if (__builtin_amdgcn_readfirstlane((int)u.ok) == 0) break;
-      push_word = (uint32_t)__builtin_amdgcn_readfirstlane((int)uq_run<true>(P, u, table, lane, tags));
-      all_lanes_here(P, lane);
-    }
-    return;
-  }
-  for (;;) {
-    uint32_t q = 0;
-    if (lane == 0) q = atomicAdd(P.queue, 1u);  // (the ONE lane-0 block of the loop: see uq_pop)
-    q = (uint32_t)__builtin_amdgcn_readfirstlane((int)q);
-    if (q >= P.queue_end) break;
-    __syncthreads();
-    lz77_stream<MULTI, true>(P, P.stream_ids[q], table, lane, 0, 0xffffffffu, nullptr, tags);
-    __syncthreads();
-    all_lanes_here(P, lane);
+// A whole 32 KiB table from `src` to `dst` (LDS or global memory, either way), sixteen dwords in flight per lane:
+// one at a time, each waited for before its store, is 128 round trips per table.  Plain loads and stores: the
+// copies between blocks that run at the same time are uq_run's own (agent-scope atomics).  The caller waits
+// and synchronises.
+FLATE_D void table_copy(uint16_t *dst, const uint16_t *src, int lane) {
+  const uint32_t *s = reinterpret_cast<const uint32_t *>(src);
+  uint32_t *d = reinterpret_cast<uint32_t *>(dst);
+  static_assert(kTableSize / 2 % (64 * 16) == 0, "table = whole rounds of 16 dwords per lane");
+  for (int i0 = lane; i0 < kTableSize / 2; i0 += 64 * 16) {
+    uint32_t w[16];
+#pragma unroll
+    for (int k = 0; k < 16; ++k) w[k] = s[i0 + 64 * k];
+#pragma unroll
+    for (int k = 0; k < 16; ++k) d[i0 + 64 * k] = w[k];
   }
 }
 
@@ -1054,19 +994,117 @@ __global__ __launch_bounds__(64) void lz77_guest_kernel(LzParams P) {
 // ---------------------------------------------------------------------------------
 FLATE_D void dict_snapshot_load(const LzDictParams &DP, uint32_t sid, uint16_t *table, uint32_t *clock, int lane) {
   const uint32_t slot = (uint32_t)__builtin_amdgcn_readfirstlane((int)DP.slot_of[sid]);
-  const uint32_t *src = reinterpret_cast<const uint32_t *>(DP.tables + (size_t)slot * kTableSize);
-  uint32_t *dst = reinterpret_cast<uint32_t *>(table);
-  static_assert(kTableSize / 2 % (64 * 16) == 0, "table = whole rounds of 16 dwords per lane");
-  for (int i0 = lane; i0 < kTableSize / 2; i0 += 64 * 16) {  // (sixteen loads in flight per lane, as uq_run)
-    uint32_t w[16];
-#pragma unroll
-    for (int k = 0; k < 16; ++k) w[k] = src[i0 + 64 * k];
-#pragma unroll
-    for (int k = 0; k < 16; ++k) dst[i0 + 64 * k] = w[k];
-  }
+  table_copy(table, DP.tables + (size_t)slot * kTableSize, lane);
   *clock = (uint32_t)__builtin_amdgcn_readfirstlane((int)DP.clocks[slot]);
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
   __syncthreads();
+}
+
+// ---------------------------------------------------------------------------------
+// The two loops every stream kernel below is made of.  `table` is the block's own working table; the
+// compile-time facts are GUEST (the table is a slice of HBM scratch, `tags` its slot tags in LDS or null, and
+// there is always a queue), DICT (every stream starts from its dictionary's snapshot, *DP) and COUNT (the
+// launch adds the units it took to *P.taken: the LDS-table side of a resident + guest pair).
+//
+// One lane-0 block per loop iteration (the queue's atomicAdd here, uq_pop's in the unit loop), and every value
+// that decides a branch made scalar with an explicit readfirstlane: with two lane-0 blocks in the body, or a
+// per-lane loop condition, hipcc peels lane 0 off the loop and the later iterations run without it (see
+// uq_pop, uq_run; all_lanes_here is the runtime guard).
+// (P by value: taken by reference, the same loops gave lz77_guest_kernel<true> 139 VGPRs instead of 125 -- three
+// wavefronts per SIMD instead of four -- for the same work; every function here is inlined, it is allocation order.)
+// ---------------------------------------------------------------------------------
+
+// Whole streams: one block per stream (P.queue == null, LDS-table kernels only) or persistent -- resident and
+// guest blocks share one queue (dynamic balance).  One call site keeps a single copy of the parser.
+template <bool MULTI, bool GUEST, bool DICT, bool COUNT>
+FLATE_D void stream_loop(const LzParams P, uint16_t *table, uint32_t *tags, const LzDictParams *DP, int lane) {
+  uint32_t mine = 0;  // streams taken
+  for (bool first = true;; first = false) {
+    uint32_t q;
+    if (GUEST || P.queue) {
+      q = 0;
+      if (lane == 0) q = atomicAdd(P.queue, 1u);  // (the ONE lane-0 block of the loop)
+      q = (uint32_t)__builtin_amdgcn_readfirstlane((int)q);
+      if (q >= P.queue_end) break;
+    } else {
+      if (!first) break;
+      q = blockIdx.x;
+    }
+    __syncthreads();
+    if constexpr (DICT) {
+      const uint32_t sid = (uint32_t)__builtin_amdgcn_readfirstlane((int)P.stream_ids[q]);
+      uint32_t clock = 0;
+      dict_snapshot_load(*DP, sid, table, &clock, lane);
+      lz77_stream<true, GUEST, kLzDictStream>(P, sid, table, lane, 1, 0xffffffffu, &clock, nullptr, DP);
+    } else {
+      lz77_stream<MULTI, GUEST>(P, (GUEST || P.stream_ids) ? P.stream_ids[q] : q, table, lane, 0, 0xffffffffu, nullptr,
+                                tags);
+    }
+    __syncthreads();
+    all_lanes_here(P, lane);
+    if (COUNT) ++mine;
+  }
+  if (COUNT && P.taken && lane == 0) __hip_atomic_fetch_add(P.taken, mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// Window units of multi-window streams (persistent launches with P.uq_ready): one window at a time, see uq_run.
+template <bool GUEST, bool COUNT>
+FLATE_D void unit_loop(const LzParams P, uint16_t *table, uint32_t *tags, int lane) {
+  uint32_t push_word = 0;
+  uint32_t mine = 0;  // units taken
+  for (;;) {
+    const UqUnit u = uq_pop(P, push_word, lane);
+    if (__builtin_amdgcn_readfirstlane((int)u.ok) == 0) break;
+    push_word = (uint32_t)__builtin_amdgcn_readfirstlane((int)uq_run<GUEST>(P, u, table, lane, tags));
+    all_lanes_here(P, lane);
+    if (COUNT) ++mine;
+  }
+  if (COUNT && P.taken && lane == 0) __hip_atomic_fetch_add(P.taken, mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// Resident kernel: table in LDS (32 KiB per stream => 5 streams per CU).
+template <bool MULTI>
+__global__ __launch_bounds__(64) void lz77_wave_kernel(LzParams P) {
+  __shared__ uint16_t table[kTableSize];
+  if (MULTI && P.uq_ready)
+    unit_loop<false, true>(P, table, nullptr, threadIdx.x);
+  else
+    stream_loop<MULTI, false, false, true>(P, table, nullptr, nullptr, threadIdx.x);
+}
+
+// Guest kernel: the LDS of a CU holds only five 32 KiB tables, but its SIMDs are mostly idle
+// (the parser is latency-bound).  A small persistent grid of extra wavefronts runs the same
+// parser with tables in HBM scratch -- few enough that those tables stay in the 4 MiB L2 of
+// their XCD -- and pulls streams from a queue.
+FLATE_D uint16_t *guest_table(const LzParams &P) {  // (gtables holds one table per block of the launch)
+  return reinterpret_cast<uint16_t *>(P.gtables) + (size_t)blockIdx.x * kTableSize;
+}
+
+template <bool MULTI>
+__global__ __launch_bounds__(64) void lz77_guest_kernel(LzParams P) {
+  if (blockIdx.x >= P.gtable_blocks) return;
+  // (round 2 gave multi-window guests no tags: -7 % with them at equal geometry, but the window
+  // units hand a stream from block to block and the tags did not travel; round 3 rebuilds them at the
+  // start of a unit instead, see uq_run)
+  __shared__ uint32_t tags[kTagSlots / 16];  // see tag_of, kTagSlots
+  uint16_t *table = guest_table(P);
+  const int lane = threadIdx.x;
+  if (MULTI && P.uq_ready) {
+    unit_loop<true, false>(P, table, tags, lane);
+    return;
+  }
+  stream_loop<MULTI, true, false, false>(P, table, tags, nullptr, lane);
+}
+
+// The dictionary builds: one block per stream (P.queue == null) or persistent, as lz77_wave_kernel
+__global__ __launch_bounds__(64) void lz77_wave_dict_kernel(LzParams P, LzDictParams DP) {
+  __shared__ uint16_t table[kTableSize];
+  stream_loop<true, false, true, false>(P, table, nullptr, &DP, threadIdx.x);
+}
+
+__global__ __launch_bounds__(64) void lz77_guest_dict_kernel(LzParams P, LzDictParams DP) {
+  if (blockIdx.x >= P.gtable_blocks) return;
+  stream_loop<true, true, true, false>(P, guest_table(P), nullptr, &DP, threadIdx.x);
 }
 
 __global__ __launch_bounds__(64) void lz77_dict_prime_kernel(LzParams P, LzDictParams DP) {
@@ -1076,55 +1114,10 @@ __global__ __launch_bounds__(64) void lz77_dict_prime_kernel(LzParams P, LzDictP
   uint32_t clock = 0;
   lz77_stream<true, false, kLzDictPrime>(P, slot, table, lane, 0, 1, &clock, nullptr, &DP);
   __syncthreads();
-  const uint4 *src = reinterpret_cast<const uint4 *>(table);
-  uint4 *dst = reinterpret_cast<uint4 *>(DP.tables + (size_t)slot * kTableSize);
-  for (int i = lane; i < (int)(kTableSize * sizeof(uint16_t) / 16); i += 64) dst[i] = src[i];
+  table_copy(DP.tables + (size_t)slot * kTableSize, table, lane);
   if (lane == 0) DP.clocks[slot] = clock;
 }
 
-// one block per stream (P.queue == null) or persistent, as lz77_wave_kernel
-__global__ __launch_bounds__(64) void lz77_wave_dict_kernel(LzParams P, LzDictParams DP) {
-  __shared__ uint16_t table[kTableSize];
-  const int lane = threadIdx.x;
-  for (bool first = true;; first = false) {
-    uint32_t q;
-    if (P.queue) {
-      q = 0;
-      if (lane == 0) q = atomicAdd(P.queue, 1u);  // (the ONE lane-0 block of the loop: see uq_pop)
-      q = (uint32_t)__builtin_amdgcn_readfirstlane((int)q);
-      if (q >= P.queue_end) break;
-    } else {
-      if (!first) break;
-      q = blockIdx.x;
-    }
-    __syncthreads();
-    const uint32_t sid = (uint32_t)__builtin_amdgcn_readfirstlane((int)P.stream_ids[q]);
-    uint32_t clock = 0;
-    dict_snapshot_load(DP, sid, table, &clock, lane);
-    lz77_stream<true, false, kLzDictStream>(P, sid, table, lane, 1, 0xffffffffu, &clock, nullptr, &DP);
-    __syncthreads();
-    all_lanes_here(P, lane);
-  }
-}
-
-__global__ __launch_bounds__(64) void lz77_guest_dict_kernel(LzParams P, LzDictParams DP) {
-  if (blockIdx.x >= P.gtable_blocks) return;  // (gtables holds one table per block of this launch)
-  uint16_t *table = reinterpret_cast<uint16_t *>(P.gtables) + (size_t)blockIdx.x * kTableSize;
-  const int lane = threadIdx.x;
-  for (;;) {
-    uint32_t q = 0;
-    if (lane == 0) q = atomicAdd(P.queue, 1u);  // (the ONE lane-0 block of the loop: see uq_pop)
-    q = (uint32_t)__builtin_amdgcn_readfirstlane((int)q);
-    if (q >= P.queue_end) break;
-    __syncthreads();
-    const uint32_t sid = (uint32_t)__builtin_amdgcn_readfirstlane((int)P.stream_ids[q]);
-    uint32_t clock = 0;
-    dict_snapshot_load(DP, sid, table, &clock, lane);
-    lz77_stream<true, true, kLzDictStream>(P, sid, table, lane, 1, 0xffffffffu, &clock, nullptr, &DP);
-    __syncthreads();
-    all_lanes_here(P, lane);
-  }
-}
 
 // A stream that continues across calls (flate_hip_stream_write): the table and the sweep clock rest
 // in global memory between the calls, exactly as between two window units (uq_run) -- but the next
@@ -1150,9 +1143,7 @@ __global__ __launch_bounds__(64) void lz77_resume_kernel(LzParams P, uint16_t *t
     for (int i = lane; i < (int)(kTableSize * sizeof(uint16_t) / 16); i += 64) dst[i] = make_uint4(fill, fill, fill, fill);
     clock = W + kSweepEvery;
   } else if (P.win0 != 0) {
-    const uint4 *src = reinterpret_cast<const uint4 *>(table_io);
-    uint4 *dst = reinterpret_cast<uint4 *>(table);
-    for (int i = lane; i < (int)(kTableSize * sizeof(uint16_t) / 16); i += 64) dst[i] = src[i];
+    table_copy(table, table_io, lane);
     clock = *clock_io - rebase;
     if (rebase) {
       __syncthreads();
@@ -1167,12 +1158,8 @@ __global__ __launch_bounds__(64) void lz77_resume_kernel(LzParams P, uint16_t *t
   __syncthreads();
   lz77_stream<true>(P, 0, table, lane, P.win0, P.win0 + nwin, &clock);
   __syncthreads();
-  {
-    const uint4 *src = reinterpret_cast<const uint4 *>(table);
-    uint4 *dst = reinterpret_cast<uint4 *>(table_io);
-    for (int i = lane; i < (int)(kTableSize * sizeof(uint16_t) / 16); i += 64) dst[i] = src[i];
-    if (lane == 0) *clock_io = clock;
-  }
+  table_copy(table_io, table, lane);
+  if (lane == 0) *clock_io = clock;
 }
 
 template __global__ void lz77_wave_kernel<false>(LzParams);
