@@ -97,3 +97,20 @@ def test_model_slot_tags_change_nothing(model, oracle, seed):
     specs += [(k, 65536) for k in KINDS]
     check(model, oracle, specs, seed=seed, slot_tags=True)
     check(model, oracle, specs[:8], compat_go=True, seed=seed, slot_tags=True)
+
+
+@pytest.mark.parametrize("seed", range(6))
+def test_model_fuzz_modular_table_mode(oracle, seed):
+    # the same fuzz through the model's MULTI mode (16-bit modular slots, sweeps, span cut; lz77_corpus.run_model):
+    # the oracle's tokens, and the modular table never disagrees with the shadow table of absolute positions
+    import lz77_corpus as Z
+    rng = np.random.default_rng(seed)
+    specs = [(KINDS[int(rng.integers(0, len(KINDS)))], int(rng.integers(128, 140000))) for _ in range(25)]
+    data, off = make_streams(specs, seed=seed)
+    go = bool(seed & 1)
+    for i, (kind, n) in enumerate(specs):
+        sb = data[int(off[i]):int(off[i + 1])]
+        m = Z.run_model(sb.tobytes(), go=go, tags=bool(seed & 2), multi=True, log=False)
+        want = oracle_tokens_per_chunk(oracle, sb, compat=1 if go else 0)
+        assert Z.same_tokens(m.tokens, want), (kind, n)
+        assert m.stats[Z.S_SHADOW_DISAGREE] == 0, (kind, n)
