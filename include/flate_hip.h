@@ -330,8 +330,9 @@ int flate_hip_inflate_spliced(flate_hip_ctx *ctx, const uint8_t *in, uint64_t in
  * the CRC-32 (RFC 1952 section 8: what a gzip member carries, little endian, followed by the length mod
  * 2^32) of stream i = in[in_off[i], in_off[i+1]).  in: host, or device with FLATE_HIP_DEVICE_PTRS; in_off and
  * out: host.  Streams of any length: the work is cut into 64 KiB pieces, so one long stream fills the chip
- * as a batch of short ones does.  The framing itself -- two or ten header bytes, the trailer -- is the
- * host mirrors' (flate_host::frame / unframe, FlateEngine.deflate_batch(..., wrap=)). */
+ * as a batch of short ones does.  WRITING members -- header, raw stream, trailer, in place on the device -- is
+ * flate_hip_deflate_fast_batch_framed / _spliced_framed below; READING them (header parsing, the check of the
+ * trailer) is still the host mirrors' (flate_host::decompress_batch(..., Wrap), FlateEngine.inflate_batch_framed). */
 #define FLATE_HIP_CHECKSUM_ADLER32 1
 #define FLATE_HIP_CHECKSUM_CRC32 2
 int flate_hip_checksum_batch(flate_hip_ctx *ctx, const uint8_t *in, const uint64_t *in_off, uint32_t n_streams,
@@ -354,6 +355,65 @@ int flate_hip_deflate_fast_spliced(flate_hip_ctx *ctx, const uint8_t *in,
                                    const uint64_t *in_off, uint32_t n_streams, uint8_t *out,
                                    uint64_t out_cap, uint64_t *out_len, uint64_t *bit_off,
                                    uint32_t flags);
+
+/* -- containers: zlib and gzip members, framed on the device ----------------------
+ * SURVEY 8(f)-3; the reference has no container format.  flate_hip_deflate_fast_batch_framed is
+ * flate_hip_deflate_fast_batch -- or, with dictionary arguments, flate_hip_deflate_fast_batch_dict: their
+ * arguments, checks, limits and flags -- with every stream inside its container: member i is
+ * out[out_off[i], out_off[i+1]) = header | exactly the bytes the raw call produces for stream i | trailer, the
+ * members back to back.
+ *   FLATE_HIP_WRAP_ZLIB (RFC 1950)  header 78 01; trailer: the Adler-32 of the INPUT of stream i, big endian.
+ *   FLATE_HIP_WRAP_GZIP (RFC 1952)  header 1f 8b 08 00 00 00 00 00 04 ff (no name, no time, XFL = fastest, OS
+ *                                   unknown); trailer: CRC-32, then the input's length mod 2^32, little endian.
+ *   FLATE_HIP_WRAP_RAW              IS the raw call: the same kernels, the same bytes.
+ *   An empty stream is header | 01 00 00 ff ff | the checksum of nothing (Adler-32 = 1, CRC-32 = 0).
+ * Dictionaries (zlib only): dicts == NULL, n_dicts == 0 and dict_of == NULL together mean none; otherwise the
+ * four arguments are flate_hip_deflate_fast_batch_dict's and get its FLATE_HIP_E_INVALID checks.  Stream i gets
+ * the six-byte header 78 3f | DICTID (FDICT, RFC 1950 2.2) exactly when dict_of names a dictionary for it
+ * (dict_of == NULL: every stream uses dictionary 0); a stream with FLATE_HIP_NO_DICT gets 78 01.  DICTID is the
+ * Adler-32 of the WHOLE dictionary as given, big endian -- not of the 32 KiB tail the match finder uses, and
+ * also for a dictionary too short to have any effect (an empty one: DICTID 1).  The trailer is always the
+ * payload's checksum.
+ *   FLATE_HIP_E_INVALID, before any HIP call: an unknown wrap; FLATE_HIP_WRAP_GZIP with any dictionary argument.
+ *   out_cap: the framed total is enough, to the byte (one byte less: FLATE_HIP_E_OUT_TOO_SMALL, decided on the
+ *   device by the scan, as in the raw call); sum of flate_hip_deflate_bound + n_streams *
+ *   flate_hip_frame_overhead is always enough.  n_streams == 0: out_off[0] = 0, FLATE_HIP_OK.
+ *   in, out, dicts: host buffers, or device buffers under FLATE_HIP_DEVICE_PTRS; out may have any byte alignment.
+ *   A host-pointer call is copied in ONCE, in one piece, and out once (no "host_pipeline_groups", as
+ *   flate_hip_deflate_fast_batch_dict): the checksums run on the staged copy, and for the DICTIDs the whole
+ *   dictionaries are uploaded, not only their tails.
+ * How: the entropy stage knows every stream's exact size before it writes, so a scan that adds header and
+ * trailer places the members and the pack kernels write each raw stream straight into its member; the checksum
+ * kernels run on the input where it already is, and one small kernel writes headers and trailers last.  With
+ * profiling on, the checksum and frame kernels are reported as FLATE_HIP_STAGE_CHECKSUM beside the two encode
+ * stages.
+ *
+ * flate_hip_deflate_fast_spliced_framed: out[0, *out_len) = header | exactly the stream
+ * flate_hip_deflate_fast_spliced writes | trailer over the CONCATENATED input in[in_off[0], in_off[n_streams])
+ * (ISIZE: that length mod 2^32) -- the one .gz / zlib blob that gzip -d or zlib's uncompress turn back into the
+ * whole buffer.  bit_off (may be NULL) is counted from the first byte of the raw stream, out + header length (2
+ * or 10): its values are the unframed call's, so flate_hip_inflate_spliced(out + header length, ...) reads it.
+ * n_streams == 0: header | 01 00 00 ff ff | the trailer of nothing.  out_cap >= header + raw stream + trailer is
+ * enough (the unframed call's 3 spare bytes lie inside the trailer).  No dictionaries; FLATE_HIP_WRAP_RAW is the
+ * unframed call; an unknown wrap: FLATE_HIP_E_INVALID.
+ *
+ * flate_hip_frame_overhead (host only): the bytes a member adds around its raw stream -- RAW 0; ZLIB 6, with
+ * with_dict != 0: 10; GZIP 18; an unknown wrap 0.
+ * Out of scope: reading members through this ABI (header parsing on the device, checksums over out_len rather
+ * than over slots, status merging) -- the host mirrors do that with flate_hip_inflate_batch(_dict) and
+ * flate_hip_checksum_batch. */
+#define FLATE_HIP_WRAP_RAW 0u
+#define FLATE_HIP_WRAP_ZLIB 1u /* RFC 1950 */
+#define FLATE_HIP_WRAP_GZIP 2u /* RFC 1952 */
+size_t flate_hip_frame_overhead(uint32_t wrap, int with_dict);
+int flate_hip_deflate_fast_batch_framed(flate_hip_ctx *ctx, const uint8_t *in, const uint64_t *in_off,
+                                        uint32_t n_streams, uint32_t wrap,
+                                        const uint8_t *dicts, const uint64_t *dict_off, uint32_t n_dicts,
+                                        const uint32_t *dict_of,
+                                        uint8_t *out, uint64_t out_cap, uint64_t *out_off, uint32_t flags);
+int flate_hip_deflate_fast_spliced_framed(flate_hip_ctx *ctx, const uint8_t *in, const uint64_t *in_off,
+                                          uint32_t n_streams, uint32_t wrap, uint8_t *out, uint64_t out_cap,
+                                          uint64_t *out_len, uint64_t *bit_off, uint32_t flags);
 
 /* -- exchange step (multi-GPU) ---------------------------------------------------
  * SURVEY 8(e) / section 5; no counterpart in the reference (single-threaded, no communication
@@ -423,7 +483,7 @@ int flate_hip_gather_end(flate_hip_comm *comm, uint64_t *stream_off, uint64_t *s
  * milliseconds of the last call (stage names via flate_hip_stage_name). */
 #define FLATE_HIP_STAGE_LZ77 0
 #define FLATE_HIP_STAGE_HUFF_PACK 1
-#define FLATE_HIP_STAGE_CHECKSUM 2 /* flate_hip_checksum_batch (the slot was "compact", never used) */
+#define FLATE_HIP_STAGE_CHECKSUM 2 /* flate_hip_checksum_batch; the checksum and frame kernels of the *_framed calls */
 #define FLATE_HIP_STAGE_INFLATE 3
 #define FLATE_HIP_STAGE_COUNT 4
 int flate_hip_set_profiling(flate_hip_ctx *ctx, int on);

@@ -65,3 +65,12 @@ int flate_hip_mbt_inflate_stream_read(flate_hip_inflate_stream *st, const uint8_
   res[2] = (uint64_t)eoff;
   return rc;
 }
+
+/* -- zlib / gzip members framed on the device: MoonBit has no null FixedArray, so the batch call without
+ * preset dictionaries gets an entry of its own (flate_hip_deflate_fast_spliced_framed takes no optional
+ * arrays and is bound by the .mbt file directly) -- */
+int flate_hip_mbt_deflate_batch_framed(flate_hip_ctx *c, const uint8_t *in, const uint64_t *in_off, uint32_t n,
+                                       uint32_t wrap, uint8_t *out, uint64_t out_cap, uint64_t *out_off,
+                                       uint32_t flags) {
+  return flate_hip_deflate_fast_batch_framed(c, in, in_off, n, wrap, 0, 0, 0, 0, out, out_cap, out_off, flags);
+}

@@ -303,6 +303,121 @@ __global__ __launch_bounds__(256) void checksum_fold_kernel(FoldParams P) {
 
 using namespace flate;
 
+namespace {
+// checksum_device's arrays in slot 0 of the ctx's scratch: offsets for np pieces of n streams, and the bytes of all
+struct Carve {
+  size_t poff, wsum, ioff, plen, pbase, crc, asum, bytes = 0;
+  Carve(size_t np, size_t n) {
+    auto carve = [&](size_t b) { const size_t o = bytes; bytes += (b + 255) & ~(size_t)255; return o; };
+    poff = carve(np * 8), wsum = carve(np * 8), ioff = carve((n + 1) * 8), plen = carve(np * 4 + 4);
+    pbase = carve((n + 1) * 4 + 4), crc = carve(np * 4), asum = carve(np * 4);
+  }
+};
+size_t count_pieces(const uint64_t *in_off, uint32_t n) {
+  uint64_t np = 0;
+  for (uint32_t i = 0; i < n; ++i) np += (in_off[i + 1] - in_off[i] + kPiece - 1) / kPiece;
+  return (size_t)np;
+}
+}  // namespace
+
+size_t flate::checksum_scratch_bytes(const uint64_t *in_off, uint32_t n) { return Carve(count_pieces(in_off, n), n).bytes; }
+
+// uploads of one checksum_device call through the ctx's staging: piece offsets and lengths, piece_base, in_off
+size_t flate::checksum_ctl_up_bytes(const uint64_t *in_off, uint32_t n) {
+  return count_pieces(in_off, n) * 12 + ((size_t)n + 1) * 12 + 4 * 512;
+}
+
+// The kernels of flate_hip_checksum_batch on input that is on the device already; the sums stay there (flate_kernels.h).
+int flate::checksum_device(flate_hip_ctx *c, const uint8_t *d_in, const uint64_t *in_off, uint32_t n, uint32_t kind,
+                           uint32_t *d_sums, int stage) {
+  if (n == 0) return FLATE_HIP_OK;
+  auto hip_fail = [&](const char *what) -> int {
+    ctx_set_error(c, std::string(what) + ": " + hipGetErrorString(hipGetLastError()));
+    return FLATE_HIP_E_HIP;
+  };
+  hipStream_t st = ctx_stream(c);
+  // pieces.  (The vectors may throw: nothing may cross the extern "C" boundary -- see the catch at the end.)
+  try {
+  std::vector<uint64_t> poff;
+  std::vector<uint32_t> plen, pbase(n + 1, 0);
+  for (uint32_t i = 0; i < n; ++i) {
+    pbase[i] = (uint32_t)plen.size();
+    for (uint64_t o = in_off[i]; o < in_off[i + 1]; o += kPiece) {
+      poff.push_back(o);
+      plen.push_back((uint32_t)(in_off[i + 1] - o < kPiece ? in_off[i + 1] - o : kPiece));
+      if (plen.size() >= 0xfffffff0u) return FLATE_HIP_E_TOO_LARGE;
+    }
+  }
+  pbase[n] = (uint32_t)plen.size();
+  const uint32_t np = (uint32_t)plen.size();
+  // one grow-only scratch of the ctx, carved into the call's arrays (round 4 did nine hipMalloc / hipFree
+  // pairs per call: hipFree drains the whole device, i.e. every other context and the host pipelines' lanes)
+  struct Dev { void *p = nullptr; } d_poff, d_plen, d_pbase, d_ioff, d_crc, d_asum, d_wsum;
+  {
+    const Carve o(np, n);
+    void *base = nullptr;
+    const int rc = ctx_scratch(c, 0, o.bytes, &base);
+    if (rc != FLATE_HIP_OK) return rc;
+    uint8_t *b8 = (uint8_t *)base;
+    d_poff.p = b8 + o.poff, d_wsum.p = b8 + o.wsum, d_ioff.p = b8 + o.ioff, d_plen.p = b8 + o.plen;
+    d_pbase.p = b8 + o.pbase, d_crc.p = b8 + o.crc, d_asum.p = b8 + o.asum;
+  }
+  // the index arrays travel through the ctx's pinned staging and its copy kernel, not through DMA
+  // commands that queue behind whatever bulk copy another thread has in flight (flate_api.hip: ctl_up)
+  {
+    int rc = ctx_ctl_up(c, d_poff.p, poff.data(), (size_t)np * 8);
+    if (rc == FLATE_HIP_OK) rc = ctx_ctl_up(c, d_plen.p, plen.data(), (size_t)np * 4);
+    if (rc == FLATE_HIP_OK) rc = ctx_ctl_up(c, d_pbase.p, pbase.data(), ((size_t)n + 1) * 4);
+    if (rc == FLATE_HIP_OK) rc = ctx_ctl_up(c, d_ioff.p, in_off, ((size_t)n + 1) * 8);
+    if (rc != FLATE_HIP_OK) return rc;
+  }
+  const X2n x2n = make_x2n();
+  if (np) {
+    PieceParams P{};
+    P.in = d_in;
+    P.piece_off = (const uint64_t *)d_poff.p;
+    P.piece_len = (const uint32_t *)d_plen.p;
+    P.n_pieces = np;
+    P.want_crc = kind == FLATE_HIP_CHECKSUM_CRC32;
+    P.want_adler = kind == FLATE_HIP_CHECKSUM_ADLER32;
+    P.crc = (uint32_t *)d_crc.p;
+    P.asum = (uint32_t *)d_asum.p;
+    P.wsum = (uint64_t *)d_wsum.p;
+    P.x2n = x2n;
+    uint32_t blocks = (np + 3) / 4;
+    const uint32_t cap = 8u * (uint32_t)ctx_num_cus(c);  // 32 wavefronts per CU
+    if (blocks > cap) blocks = cap;
+    if (stage >= 0) ctx_stage_begin(c, stage);
+    hipLaunchKernelGGL(checksum_piece_kernel, dim3(blocks), dim3(256), 0, st, P);
+  } else {
+    if (stage >= 0) ctx_stage_begin(c, stage);
+  }
+  FoldParams F{};
+  F.in_off = (const uint64_t *)d_ioff.p;
+  F.piece_base = (const uint32_t *)d_pbase.p;
+  F.piece_len = (const uint32_t *)d_plen.p;
+  F.crc = (const uint32_t *)d_crc.p;
+  F.asum = (const uint32_t *)d_asum.p;
+  F.wsum = (const uint64_t *)d_wsum.p;
+  F.out = d_sums;
+  F.n_streams = n;
+  F.want_crc = kind == FLATE_HIP_CHECKSUM_CRC32;
+  F.max_pieces = 0;
+  for (uint32_t i = 0; i < n; ++i) F.max_pieces = pbase[i + 1] - pbase[i] > F.max_pieces ? pbase[i + 1] - pbase[i] : F.max_pieces;
+  F.x2n = x2n;
+  hipLaunchKernelGGL(checksum_fold_kernel, dim3((n + 3) / 4), dim3(256), 0, st, F);
+  if (stage >= 0) ctx_stage_end(c, stage);
+  if (hipGetLastError() != hipSuccess) return hip_fail("checksum kernels");
+  return FLATE_HIP_OK;
+  } catch (const std::bad_alloc &) {
+    ctx_set_error(c, "out of host memory (checksum piece index)");
+    return FLATE_HIP_E_HIP;
+  } catch (const std::exception &e) {
+    ctx_set_error(c, e.what());
+    return FLATE_HIP_E_INTERNAL;
+  }
+}
+
 extern "C" int flate_hip_checksum_batch(flate_hip_ctx *c, const uint8_t *in, const uint64_t *in_off, uint32_t n,
                                         uint32_t kind, uint32_t *out, uint32_t flags) {
   if (!c || !in_off || (n && !out) || (kind != FLATE_HIP_CHECKSUM_ADLER32 && kind != FLATE_HIP_CHECKSUM_CRC32))
@@ -319,99 +434,20 @@ extern "C" int flate_hip_checksum_batch(flate_hip_ctx *c, const uint8_t *in, con
   };
   if (hipSetDevice(ctx_device(c)) != hipSuccess) return hip_fail("hipSetDevice");
   hipStream_t st = ctx_stream(c);
-  // pieces.  (The vectors may throw: nothing may cross the extern "C" boundary -- see the catch at the end.)
-  try {
-  std::vector<uint64_t> poff;
-  std::vector<uint32_t> plen, pbase(n + 1, 0);
-  for (uint32_t i = 0; i < n; ++i) {
-    pbase[i] = (uint32_t)plen.size();
-    for (uint64_t o = in_off[i]; o < in_off[i + 1]; o += kPiece) {
-      poff.push_back(o);
-      plen.push_back((uint32_t)(in_off[i + 1] - o < kPiece ? in_off[i + 1] - o : kPiece));
-      if (plen.size() >= 0xfffffff0u) return FLATE_HIP_E_TOO_LARGE;
-    }
-  }
-  pbase[n] = (uint32_t)plen.size();
-  const uint32_t np = (uint32_t)plen.size();
   const bool dev = (flags & FLATE_HIP_DEVICE_PTRS) != 0;
-  // one grow-only scratch of the ctx, carved into the call's arrays (round 4 did nine hipMalloc / hipFree
-  // pairs per call: hipFree drains the whole device, i.e. every other context and the host pipelines' lanes)
-  struct Dev { void *p = nullptr; } d_in, d_poff, d_plen, d_pbase, d_ioff, d_crc, d_asum, d_wsum, d_out;
-  {
-    size_t at = 0;
-    auto carve = [&](size_t bytes) { const size_t o = at; at += (bytes + 255) & ~(size_t)255; return o; };
-    const size_t o_poff = carve((size_t)np * 8), o_wsum = carve((size_t)np * 8), o_ioff = carve(((size_t)n + 1) * 8),
-                 o_plen = carve((size_t)np * 4 + 4), o_pbase = carve(((size_t)n + 1) * 4 + 4), o_crc = carve((size_t)np * 4),
-                 o_asum = carve((size_t)np * 4), o_out = carve((size_t)n * 4 + 4);
-    void *base = nullptr;
-    int rc = ctx_scratch(c, 0, at, &base);
-    if (rc == FLATE_HIP_OK && !dev) rc = ctx_scratch(c, 1, total + 16, &d_in.p);
-    if (rc != FLATE_HIP_OK) return rc;
-    uint8_t *b8 = (uint8_t *)base;
-    d_poff.p = b8 + o_poff, d_wsum.p = b8 + o_wsum, d_ioff.p = b8 + o_ioff, d_plen.p = b8 + o_plen;
-    d_pbase.p = b8 + o_pbase, d_crc.p = b8 + o_crc, d_asum.p = b8 + o_asum, d_out.p = b8 + o_out;
-  }
-  // the index arrays travel through the ctx's pinned staging and its copy kernel, not through DMA
-  // commands that queue behind whatever bulk copy another thread has in flight (flate_api.hip: ctl_up)
-  {
-    int rc = ctx_ctl_begin(c, (size_t)np * 12 + ((size_t)n + 1) * 12 + 4 * 512, (size_t)n * 4 + 512);
-    if (rc == FLATE_HIP_OK) rc = ctx_ctl_up(c, d_poff.p, poff.data(), (size_t)np * 8);
-    if (rc == FLATE_HIP_OK) rc = ctx_ctl_up(c, d_plen.p, plen.data(), (size_t)np * 4);
-    if (rc == FLATE_HIP_OK) rc = ctx_ctl_up(c, d_pbase.p, pbase.data(), ((size_t)n + 1) * 4);
-    if (rc == FLATE_HIP_OK) rc = ctx_ctl_up(c, d_ioff.p, in_off, ((size_t)n + 1) * 8);
-    if (rc != FLATE_HIP_OK) return rc;
-    if (!dev && total && hipMemcpyAsync(d_in.p, in, total, hipMemcpyHostToDevice, st) != hipSuccess)
-      return hip_fail("hipMemcpyAsync (checksum input)");
-  }
-  const X2n x2n = make_x2n();
-  if (np) {
-    PieceParams P{};
-    P.in = dev ? in : (const uint8_t *)d_in.p;
-    P.piece_off = (const uint64_t *)d_poff.p;
-    P.piece_len = (const uint32_t *)d_plen.p;
-    P.n_pieces = np;
-    P.want_crc = kind == FLATE_HIP_CHECKSUM_CRC32;
-    P.want_adler = kind == FLATE_HIP_CHECKSUM_ADLER32;
-    P.crc = (uint32_t *)d_crc.p;
-    P.asum = (uint32_t *)d_asum.p;
-    P.wsum = (uint64_t *)d_wsum.p;
-    P.x2n = x2n;
-    uint32_t blocks = (np + 3) / 4;
-    const uint32_t cap = 8u * (uint32_t)ctx_num_cus(c);  // 32 wavefronts per CU
-    if (blocks > cap) blocks = cap;
-    ctx_stage_begin(c, FLATE_HIP_STAGE_CHECKSUM);
-    hipLaunchKernelGGL(checksum_piece_kernel, dim3(blocks), dim3(256), 0, st, P);
-  } else {
-    ctx_stage_begin(c, FLATE_HIP_STAGE_CHECKSUM);
-  }
-  FoldParams F{};
-  F.in_off = (const uint64_t *)d_ioff.p;
-  F.piece_base = (const uint32_t *)d_pbase.p;
-  F.piece_len = (const uint32_t *)d_plen.p;
-  F.crc = (const uint32_t *)d_crc.p;
-  F.asum = (const uint32_t *)d_asum.p;
-  F.wsum = (const uint64_t *)d_wsum.p;
-  F.out = (uint32_t *)d_out.p;
-  F.n_streams = n;
-  F.want_crc = kind == FLATE_HIP_CHECKSUM_CRC32;
-  F.max_pieces = 0;
-  for (uint32_t i = 0; i < n; ++i) F.max_pieces = pbase[i + 1] - pbase[i] > F.max_pieces ? pbase[i + 1] - pbase[i] : F.max_pieces;
-  F.x2n = x2n;
-  hipLaunchKernelGGL(checksum_fold_kernel, dim3((n + 3) / 4), dim3(256), 0, st, F);
-  ctx_stage_end(c, FLATE_HIP_STAGE_CHECKSUM);
-  if (hipGetLastError() != hipSuccess) return hip_fail("checksum kernels");
-  {
-    const int rc = ctx_ctl_down(c, out, d_out.p, (size_t)n * 4);
-    if (rc != FLATE_HIP_OK) return rc;
-  }
+  // the sums, and a staged copy of host input, in slot 1 of the ctx's scratch (slot 0 is checksum_device's)
+  const size_t sums_bytes = ((size_t)n * 4 + 4 + 255) & ~(size_t)255;
+  void *aux = nullptr;
+  int rc = ctx_scratch(c, 1, sums_bytes + (dev ? 0 : total + 16), &aux);
+  if (rc != FLATE_HIP_OK) return rc;
+  uint32_t *d_sums = (uint32_t *)aux;
+  const uint8_t *d_in = dev ? in : (const uint8_t *)aux + sums_bytes;
+  if ((rc = ctx_ctl_begin(c, checksum_ctl_up_bytes(in_off, n), (size_t)n * 4 + 512)) != FLATE_HIP_OK) return rc;
+  if (!dev && total && hipMemcpyAsync((void *)d_in, in, total, hipMemcpyHostToDevice, st) != hipSuccess)
+    return hip_fail("hipMemcpyAsync (checksum input)");
+  if ((rc = checksum_device(c, d_in, in_off, n, kind, d_sums, FLATE_HIP_STAGE_CHECKSUM)) != FLATE_HIP_OK) return rc;
+  if ((rc = ctx_ctl_down(c, out, d_sums, (size_t)n * 4)) != FLATE_HIP_OK) return rc;
   if (hipStreamSynchronize(st) != hipSuccess) return hip_fail("checksum read-back");
   ctx_ctl_finish(c);
   return ctx_stage_collect(c, FLATE_HIP_STAGE_CHECKSUM);
-  } catch (const std::bad_alloc &) {
-    ctx_set_error(c, "out of host memory (checksum piece index)");
-    return FLATE_HIP_E_HIP;
-  } catch (const std::exception &e) {
-    ctx_set_error(c, e.what());
-    return FLATE_HIP_E_INTERNAL;
-  }
 }

@@ -64,6 +64,9 @@ struct flate_hip_ctx {
   // flate_hip_deflate_fast_batch_dict (it shares the three above, there per used dictionary): the streams that start
   // from a dictionary, every stream's dictionary slot, the primed tables and sweep clocks of the slots
   DevBuf d_idsD, d_lz_slot_of, d_lz_tables, d_lz_clocks;
+  // the *_framed calls: member offsets, the streams' checksums, per stream its dictionary, the dictionaries' Adler-32
+  // (DICTIDs) and, for host callers, the whole dictionaries
+  DevBuf d_frame_off, d_frame_sums, d_frame_dict_of, d_frame_ids, d_frame_dicts;
   hipStream_t guest_stream = nullptr;
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
   int guest_blocks = 0;      // 0 = guest kernel off
@@ -272,6 +275,16 @@ struct DeflDict {
   LzDictParams dev;
   uint32_t n_slots;        // used dictionaries of at least kSmallHuffMin bytes (after the cut to 32768)
   const uint8_t *has;      // host, per stream: it uses one of them
+};
+
+// The container of a *_framed call (frame_kernels.hip); everything here is the caller's.
+struct FrameReq {
+  uint32_t wrap;            // FLATE_HIP_WRAP_ZLIB / _GZIP
+  const uint32_t *dict_of;  // host, per stream: the dictionary whose DICTID its header carries, or FLATE_HIP_NO_DICT;
+                            // null: no dictionaries
+  const uint8_t *dicts;     // the WHOLE dictionaries (host, or device under FLATE_HIP_DEVICE_PTRS) ...
+  const uint64_t *dict_off; // ... dictionary j = dicts[dict_off[j], dict_off[j+1])
+  uint32_t n_dicts;
 };
 
 struct StagePlan {
@@ -840,17 +853,39 @@ size_t flate_hip_deflate_bound(size_t n) {
 
 // Both encode entry points.  spliced: the whole batch becomes one DEFLATE stream; out_off then
 // receives the bit position of every stream (may be NULL) and *total_bytes the size.
+// FR (the *_framed calls; null: raw streams, nothing below changes): every stream -- spliced: the one stream -- inside
+// its container.  The scan that places the streams adds header and trailer, the pack kernels write each raw stream into
+// its member, then the checksum kernels run on the input where it is and frame_write_kernel writes headers and trailers.
 static int deflate_common(flate_hip_ctx *c, const uint8_t *in, const uint64_t *in_off, uint32_t n,
                           uint8_t *out, uint64_t out_cap, uint64_t *out_off, uint32_t flags,
-                          bool spliced, uint64_t *total_bytes, const DeflDict *DD = nullptr) {
+                          bool spliced, uint64_t *total_bytes, const DeflDict *DD = nullptr,
+                          const FrameReq *FR = nullptr) {
   HIP_TRY(c, hipSetDevice(c->device));
   StagePlan pl;
   int rc = make_plan(in_off, n, pl, flags, DD ? DD->has : nullptr);
   if (rc) return rc;
   const bool dev = (flags & FLATE_HIP_DEVICE_PTRS) != 0;
   const uint64_t in_bytes = in_off[n];
+  // a spliced member's fixed header and trailer; what the checksum kernels sum: the streams, or the one stream
+  const uint32_t f_hl = !FR ? 0u : FR->wrap == FLATE_HIP_WRAP_GZIP ? 10u : 2u;
+  const uint32_t f_tl = !FR ? 0u : FR->wrap == FLATE_HIP_WRAP_GZIP ? 8u : 4u;
+  const uint64_t whole[2] = {in_off[0], in_off[n]};
+  const uint64_t *sum_off = spliced ? whole : in_off;
+  const uint32_t sum_n = spliced ? 1u : n;
+  std::vector<uint64_t> f_doff;  // the dictionaries' offsets counted from the first one
+  size_t f_up = 0;
+  if (FR) {
+    if (spliced && out_cap < (uint64_t)f_hl + f_tl) return FLATE_HIP_E_OUT_TOO_SMALL;
+    f_up = (size_t)n * 4 + 256 + checksum_ctl_up_bytes(sum_off, sum_n);
+    if (FR->dict_of) {
+      // (n_dicts == 0: every dict_of entry is FLATE_HIP_NO_DICT and dict_off may be null -- dict_args_ok)
+      f_doff.assign((size_t)FR->n_dicts + 1, 0);
+      for (uint32_t j = 1; j <= FR->n_dicts; ++j) f_doff[j] = FR->dict_off[j] - FR->dict_off[0];
+      f_up += checksum_ctl_up_bytes(f_doff.data(), FR->n_dicts);
+    }
+  }
   // the call's index arrays: in_off, chunk_base, blk_base (n + 1 each), the two stream lists, blk_sid
-  if ((rc = ctl_begin(c, ((size_t)n + 1) * 16 + (pl.ids16.size() + pl.ids32.size() + pl.idsD.size() + (size_t)pl.n_blocks) * 4,
+  if ((rc = ctl_begin(c, ((size_t)n + 1) * 16 + (pl.ids16.size() + pl.ids32.size() + pl.idsD.size() + (size_t)pl.n_blocks) * 4 + f_up,
                       ((size_t)n + 1) * 8 + 64)))
     return rc;
 
@@ -876,6 +911,28 @@ static int deflate_common(flate_hip_ctx *c, const uint8_t *in, const uint64_t *i
     if ((rc = ensure(c, c->d_slot_off, ((size_t)n + 1) * 16))) return rc;  // stream summaries {a, b}
   }
   if ((rc = ctl_up(c, c->d_blk_base.p, pl.blk_base.data(), ((size_t)n + 1) * 4))) return rc;
+  const uint8_t *d_whole_dicts = nullptr;
+  if (FR) {
+    if ((rc = ensure(c, c->d_frame_off, ((size_t)n + 1) * 8))) return rc;
+    if ((rc = ensure(c, c->d_frame_sums, (size_t)n * 4 + 8))) return rc;
+    if (FR->dict_of) {
+      if ((rc = ensure(c, c->d_frame_dict_of, (size_t)n * 4 + 4))) return rc;
+      if ((rc = ensure(c, c->d_frame_ids, (size_t)FR->n_dicts * 4 + 4))) return rc;
+      // both checksum_device calls below carve slot 0 of the scratch: sized once here for the larger, so that the
+      // second cannot grow it (a hipFree, which drains the device) inside the timed stage
+      const size_t a = checksum_scratch_bytes(f_doff.data(), FR->n_dicts), b = checksum_scratch_bytes(sum_off, sum_n);
+      void *unused = nullptr;
+      if ((rc = ctx_scratch(c, 0, a > b ? a : b, &unused))) return rc;
+      if ((rc = ctl_up(c, c->d_frame_dict_of.p, FR->dict_of, (size_t)n * 4))) return rc;
+      const uint64_t bytes = f_doff[FR->n_dicts];
+      d_whole_dicts = FR->dicts && FR->n_dicts ? FR->dicts + FR->dict_off[0] : nullptr;
+      if (!dev) {  // DICTID is the Adler-32 of the whole dictionary: the tails of dict_upload are not enough
+        if ((rc = ensure(c, c->d_frame_dicts, bytes + 16))) return rc;
+        if (bytes) HIP_TRY(c, hipMemcpyAsync(c->d_frame_dicts.p, d_whole_dicts, bytes, hipMemcpyHostToDevice, c->stream));
+        d_whole_dicts = (const uint8_t *)c->d_frame_dicts.p;
+      }
+    }
+  }
   HIP_TRY(c, hipMemsetAsync(c->d_status.p, 0, 4, c->stream));
   // One wavefront per block in the histogram and pack kernels when the streams have many blocks
   // (4096 streams of four windows are 4096 wavefronts per stream-kernel, a quarter of what fills
@@ -902,9 +959,25 @@ static int deflate_common(flate_hip_ctx *c, const uint8_t *in, const uint64_t *i
   H.in_off = (const uint64_t *)c->d_in_off.p;
   H.chunk_base = (const uint32_t *)c->d_chunk_base.p;
   H.blk_base = (const uint32_t *)c->d_blk_base.p;
-  H.out = d_out;
+  H.out = d_out + (spliced ? f_hl : 0u);  // (batch members: the header lengths are in the offsets, frame_scan_kernel)
   H.n_streams = n;
   H.blk_sid = per_block ? (const uint32_t *)c->d_blk_sid.p : nullptr;
+  FrameParams F{};
+  if (FR) {
+    F.out_len = (const uint64_t *)c->d_out_len.p + (spliced ? n : 0u);  // (spliced: total_bytes of splice_scan_kernel)
+    F.member_off = spliced ? nullptr : (uint64_t *)c->d_frame_off.p;
+    F.payload_off = (uint64_t *)c->d_out_off.p;
+    F.in_off = (const uint64_t *)c->d_in_off.p;
+    F.one_len = whole[1] - whole[0];
+    F.sums = (const uint32_t *)c->d_frame_sums.p;
+    F.dict_of = FR->dict_of ? (const uint32_t *)c->d_frame_dict_of.p : nullptr;
+    F.dict_id = (const uint32_t *)c->d_frame_ids.p;
+    F.out = d_out;
+    F.out_cap = out_cap;
+    F.n_streams = n;
+    F.wrap = FR->wrap;
+    F.status = (int *)c->d_status.p;
+  }
   CompactParams C{};
   C.out_len = (const uint64_t *)c->d_out_len.p;
   C.out_off = (uint64_t *)c->d_out_off.p;
@@ -919,17 +992,22 @@ static int deflate_common(flate_hip_ctx *c, const uint8_t *in, const uint64_t *i
       hipLaunchKernelGGL(huff_hist_kernel, dim3(n), dim3(64), 0, c->stream, H);
     hipLaunchKernelGGL(huff_code_kernel, dim3(n), dim3(64), 0, c->stream, H);
     if (!spliced) {
-      hipLaunchKernelGGL(scan_sizes_kernel, dim3(1), dim3(1024), 0, c->stream, C);
+      if (FR)
+        hipLaunchKernelGGL(frame_scan_kernel, dim3(1), dim3(1024), 0, c->stream, F);
+      else
+        hipLaunchKernelGGL(scan_sizes_kernel, dim3(1), dim3(1024), 0, c->stream, C);
     } else {
       SpliceParams S{};
       S.sum = (const uint64_t *)c->d_slot_off.p;
       S.stream_bit = (uint64_t *)c->d_out_off.p;
       S.total_bytes = (uint64_t *)c->d_out_len.p + n;  // (d_out_len has n + 1 slots)
-      S.out_cap = out_cap;
+      // (framed: header + stream + trailer <= out_cap is enough -- the 3 bytes the pack kernel's last dword may reach
+      // past the stream lie in the trailer, which is written after it)
+      S.out_cap = FR ? out_cap - f_hl - f_tl + 3 : out_cap;
       S.status = (int *)c->d_status.p;
       S.n_streams = n;
       hipLaunchKernelGGL(splice_scan_kernel, dim3(1), dim3(1024), 0, c->stream, S);
-      hipLaunchKernelGGL(splice_zero_kernel, dim3(n / 256 + 1), dim3(256), 0, c->stream, S, d_out);
+      hipLaunchKernelGGL(splice_zero_kernel, dim3(n / 256 + 1), dim3(256), 0, c->stream, S, H.out);
     }
     if (per_block) {
       hipLaunchKernelGGL(huff_zero_edges_kernel, dim3(pl.n_blocks / 256 + 1), dim3(256), 0, c->stream, H,
@@ -940,22 +1018,37 @@ static int deflate_common(flate_hip_ctx *c, const uint8_t *in, const uint64_t *i
     }
   }
   HIP_TRY(c, hipGetLastError());
+  if (FR) {
+    // after the pack kernel: its spliced form works on whole dwords around the stream
+    StageTimer t(c, FLATE_HIP_STAGE_CHECKSUM);
+    if (FR->dict_of &&
+        (rc = checksum_device(c, d_whole_dicts, f_doff.data(), FR->n_dicts, FLATE_HIP_CHECKSUM_ADLER32,
+                              (uint32_t *)c->d_frame_ids.p, -1)))
+      return rc;
+    if ((rc = checksum_device(c, d_in, sum_off, sum_n,
+                              FR->wrap == FLATE_HIP_WRAP_GZIP ? FLATE_HIP_CHECKSUM_CRC32 : FLATE_HIP_CHECKSUM_ADLER32,
+                              (uint32_t *)c->d_frame_sums.p, -1)))
+      return rc;
+    hipLaunchKernelGGL(frame_write_kernel, dim3(sum_n / 256 + 1), dim3(256), 0, c->stream, F);
+  }
+  HIP_TRY(c, hipGetLastError());
 
   uint64_t produced = 0;
-  if (out_off && (rc = ctl_down(c, out_off, c->d_out_off.p, ((size_t)n + 1) * 8))) return rc;
+  if (out_off && (rc = ctl_down(c, out_off, (FR && !spliced) ? c->d_frame_off.p : c->d_out_off.p, ((size_t)n + 1) * 8)))
+    return rc;
   if (spliced && (rc = ctl_down(c, &c->h_total_bytes, (uint64_t *)c->d_out_len.p + n, 8))) return rc;
   if ((rc = ctl_down(c, &c->h_status_word, c->d_status.p, 4))) return rc;
   HIP_TRY(c, hipGetLastError());
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   ctl_finish(c);
   if (c->h_status_word) return encoder_status(c, c->h_status_word);
-  produced = spliced ? c->h_total_bytes : out_off[n];
+  produced = spliced ? c->h_total_bytes + f_hl + f_tl : out_off[n];
   if (total_bytes) *total_bytes = produced;
   if (!dev) {
     HIP_TRY(c, hipMemcpyAsync(out, c->d_out.p, produced, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
   }
-  const bool used[FLATE_HIP_STAGE_COUNT] = {true, true, false, false};
+  const bool used[FLATE_HIP_STAGE_COUNT] = {true, true, FR != nullptr, false};
   return collect_timing(c, used);
 }
 
@@ -2050,18 +2143,34 @@ int flate_hip_inflate_batch_dict(flate_hip_ctx *c, const uint8_t *in, const uint
   return inflate_batch_run(c, in, in_off, n, out, out_off, out_len, status, err_off, flags, &D);
 }
 
-int flate_hip_deflate_fast_batch_dict(flate_hip_ctx *c, const uint8_t *in, const uint64_t *in_off, uint32_t n,
-                                      const uint8_t *dicts, const uint64_t *dict_off, uint32_t n_dicts,
-                                      const uint32_t *dict_of, uint8_t *out, uint64_t out_cap, uint64_t *out_off,
-                                      uint32_t flags) {
+}  // extern "C"
+
+// flate_hip_deflate_fast_batch_dict; wrap != FLATE_HIP_WRAP_RAW: flate_hip_deflate_fast_batch_framed with dictionaries
+// (zlib members, the streams that name a dictionary with FDICT and its DICTID)
+static int deflate_batch_dict_run(flate_hip_ctx *c, const uint8_t *in, const uint64_t *in_off, uint32_t n,
+                                  const uint8_t *dicts, const uint64_t *dict_off, uint32_t n_dicts,
+                                  const uint32_t *dict_of, uint8_t *out, uint64_t out_cap, uint64_t *out_off,
+                                  uint32_t flags, uint32_t wrap) {
   // every check before any HIP call
   if (!c || !in_off || !out_off || (n && (!in || !out))) return FLATE_HIP_E_INVALID;
   if (!dict_args_ok(dicts, dict_off, n_dicts, dict_of, n)) return FLATE_HIP_E_INVALID;
+  const bool framed = wrap != FLATE_HIP_WRAP_RAW;
+  std::vector<uint32_t> every0;  // dict_of == NULL: every stream uses dictionary 0
+  if (framed && !dict_of) every0.assign(n, 0u);
+  const FrameReq FRv{wrap, dict_of ? dict_of : every0.data(), dicts, dict_off, n_dicts};
+  const FrameReq *FR = framed ? &FRv : nullptr;
   // DeflateFast::encode(d) over the last 32768 bytes of the dictionary; under 17 bytes that call is the
   // small-input path (deflate-fast.mbt:136-140) and leaves nothing behind
   const DictSlots S = dict_slots(dict_off, n_dicts, dict_of, n, (uint32_t)kSmallHuffMin);
-  if (S.at.empty())  // no stream's encoder has seen a dictionary: the plain call, its kernels and its bytes
-    return flate_hip_deflate_fast_batch(c, in, in_off, n, out, out_cap, out_off, flags);
+  if (S.at.empty()) {  // no stream's encoder has seen a dictionary: the plain call, its kernels and its bytes
+    if (!framed) return flate_hip_deflate_fast_batch(c, in, in_off, n, out, out_cap, out_off, flags);
+    c->hip_err.clear();
+    if (n == 0) {
+      out_off[0] = 0;
+      return FLATE_HIP_OK;
+    }
+    return deflate_common(c, in, in_off, n, out, out_cap, out_off, flags, false, nullptr, nullptr, FR);
+  }
   if (flags & FLATE_HIP_LZ_SERIAL) return FLATE_HIP_E_INVALID;  // (the single-lane kernel has no dictionary build)
   std::vector<uint8_t> has(n);
   for (uint32_t i = 0; i < n; ++i) has[i] = S.slot_of[i] != DictSlots::kNone;
@@ -2094,7 +2203,82 @@ int flate_hip_deflate_fast_batch_dict(flate_hip_ctx *c, const uint8_t *in, const
   DD.n_slots = n_slots;
   DD.has = has.data();
   // (host pointers: one copy in, compress, one copy out -- the pipelined host path is the plain call's)
-  return deflate_common(c, in, in_off, n, out, out_cap, out_off, flags, false, nullptr, &DD);
+  return deflate_common(c, in, in_off, n, out, out_cap, out_off, flags, false, nullptr, &DD, FR);
+}
+
+extern "C" {
+
+int flate_hip_deflate_fast_batch_dict(flate_hip_ctx *c, const uint8_t *in, const uint64_t *in_off, uint32_t n,
+                                      const uint8_t *dicts, const uint64_t *dict_off, uint32_t n_dicts,
+                                      const uint32_t *dict_of, uint8_t *out, uint64_t out_cap, uint64_t *out_off,
+                                      uint32_t flags) {
+  return deflate_batch_dict_run(c, in, in_off, n, dicts, dict_off, n_dicts, dict_of, out, out_cap, out_off, flags,
+                                FLATE_HIP_WRAP_RAW);
+}
+
+size_t flate_hip_frame_overhead(uint32_t wrap, int with_dict) {
+  if (wrap == FLATE_HIP_WRAP_ZLIB) return with_dict ? 10 : 6;
+  return wrap == FLATE_HIP_WRAP_GZIP ? 18 : 0;
+}
+
+int flate_hip_deflate_fast_batch_framed(flate_hip_ctx *c, const uint8_t *in, const uint64_t *in_off, uint32_t n,
+                                        uint32_t wrap, const uint8_t *dicts, const uint64_t *dict_off,
+                                        uint32_t n_dicts, const uint32_t *dict_of, uint8_t *out, uint64_t out_cap,
+                                        uint64_t *out_off, uint32_t flags) {
+  // every check before any HIP call
+  if (!c || wrap > FLATE_HIP_WRAP_GZIP) return FLATE_HIP_E_INVALID;
+  const bool with_dicts = dicts || n_dicts || dict_of;
+  if (with_dicts && wrap == FLATE_HIP_WRAP_GZIP) return FLATE_HIP_E_INVALID;  // (RFC 1952 has no preset dictionary)
+  try {
+    if (with_dicts)
+      return deflate_batch_dict_run(c, in, in_off, n, dicts, dict_off, n_dicts, dict_of, out, out_cap, out_off, flags, wrap);
+    if (wrap == FLATE_HIP_WRAP_RAW) return flate_hip_deflate_fast_batch(c, in, in_off, n, out, out_cap, out_off, flags);
+    if (!in_off || !out_off || (n && (!in || !out))) return FLATE_HIP_E_INVALID;
+    c->hip_err.clear();
+    if (n == 0) {
+      out_off[0] = 0;
+      return FLATE_HIP_OK;
+    }
+    // (host pointers: one copy in -- the checksums run on it --, compress, one copy out)
+    const FrameReq FR{wrap, nullptr, nullptr, nullptr, 0};
+    return deflate_common(c, in, in_off, n, out, out_cap, out_off, flags, false, nullptr, nullptr, &FR);
+  } catch (const std::exception &e) {  // (out of host memory in an index vector)
+    c->hip_err = e.what();
+    return FLATE_HIP_E_INTERNAL;
+  }
+}
+
+int flate_hip_deflate_fast_spliced_framed(flate_hip_ctx *c, const uint8_t *in, const uint64_t *in_off, uint32_t n,
+                                          uint32_t wrap, uint8_t *out, uint64_t out_cap, uint64_t *out_len,
+                                          uint64_t *bit_off, uint32_t flags) {
+  if (!c || wrap > FLATE_HIP_WRAP_GZIP) return FLATE_HIP_E_INVALID;
+  if (wrap == FLATE_HIP_WRAP_RAW) return flate_hip_deflate_fast_spliced(c, in, in_off, n, out, out_cap, out_len, bit_off, flags);
+  if (!in_off || !out || !out_len || (n && !in)) return FLATE_HIP_E_INVALID;
+  c->hip_err.clear();
+  if (n == 0) {  // header, the closing block of Writer::close, the trailer of nothing
+    static const uint8_t zmember[11] = {0x78, 0x01, 0x01, 0x00, 0x00, 0xff, 0xff, 0, 0, 0, 1};
+    static const uint8_t gmember[23] = {0x1f, 0x8b, 8, 0, 0, 0, 0, 0, 4, 255, 0x01, 0x00, 0x00, 0xff, 0xff};
+    const uint8_t *m = wrap == FLATE_HIP_WRAP_ZLIB ? zmember : gmember;
+    const uint64_t len = wrap == FLATE_HIP_WRAP_ZLIB ? sizeof zmember : sizeof gmember;
+    if (out_cap < len) return FLATE_HIP_E_OUT_TOO_SMALL;
+    if (flags & FLATE_HIP_DEVICE_PTRS) {
+      HIP_TRY(c, hipSetDevice(c->device));
+      HIP_TRY(c, hipMemcpyAsync(out, m, len, hipMemcpyHostToDevice, c->stream));
+      HIP_TRY(c, hipStreamSynchronize(c->stream));
+    } else {
+      memcpy(out, m, len);
+    }
+    *out_len = len;
+    if (bit_off) bit_off[0] = 0;
+    return FLATE_HIP_OK;
+  }
+  try {
+    const FrameReq FR{wrap, nullptr, nullptr, nullptr, 0};
+    return deflate_common(c, in, in_off, n, out, out_cap, bit_off, flags, true, out_len, nullptr, &FR);
+  } catch (const std::exception &e) {
+    c->hip_err = e.what();
+    return FLATE_HIP_E_INTERNAL;
+  }
 }
 
 int flate_hip_inflate_spliced(flate_hip_ctx *c, const uint8_t *in, uint64_t in_len,

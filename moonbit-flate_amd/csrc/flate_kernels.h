@@ -211,6 +211,32 @@ struct SpliceParams {
 };
 __global__ void splice_scan_kernel(SpliceParams P);
 __global__ void splice_zero_kernel(SpliceParams P, uint8_t *out);
+
+// Containers around the raw streams (frame_kernels.hip; flate_hip_deflate_fast_*_framed): member i of a batch is
+// header | raw stream i | trailer, the members back to back.  wrap = FLATE_HIP_WRAP_ZLIB: two header bytes, or six
+// (FDICT + DICTID) for a stream that names a dictionary, and the Adler-32 of the input, big endian; _GZIP: ten
+// header bytes, the CRC-32 and the input's length mod 2^32, little endian.
+struct FrameParams {
+  const uint64_t *out_len;  // per stream: bytes of its raw stream (huff_code_kernel)
+  uint64_t *member_off;     // n_streams + 1: where every member starts (frame_scan_kernel writes it); null: ONE member
+                            // at out[0] whose raw stream has out_len[0] bytes (the spliced form)
+  uint64_t *payload_off;    // n_streams + 1: member_off[i] + header length = HuffParams::out_off (frame_scan_kernel)
+  const uint64_t *in_off;   // n_streams + 1: the streams' input (gzip: ISIZE); one member: unused
+  uint64_t one_len;         // one member: bytes of its input
+  const uint32_t *sums;     // per member: the checksum of its input
+  const uint32_t *dict_of;  // per stream: its dictionary or FLATE_HIP_NO_DICT; null: no member carries a DICTID
+  const uint32_t *dict_id;  // per dictionary: its Adler-32
+  uint8_t *out;             // any byte alignment
+  uint64_t out_cap;
+  uint32_t n_streams;
+  uint32_t wrap;
+  int *status;              // frame_scan_kernel: FLATE_HIP_E_OUT_TOO_SMALL if the members exceed out_cap
+};
+// scan_sizes_kernel for members: exclusive scan of header + out_len + trailer
+__global__ void frame_scan_kernel(FrameParams P);
+// headers and trailers, byte by byte (one thread per member); launched AFTER the pack kernel, whose spliced form
+// stores whole dwords around its stream
+__global__ void frame_write_kernel(FrameParams P);
 size_t inflate_simt_lds_bytes(int lanes_per_wave);  // dynamic LDS of that launch
 size_t inflate_simt_lens_bytes(uint32_t blocks);    // global scratch of that launch (InfParams::simt_lens)
 
@@ -238,4 +264,14 @@ int ctx_ctl_begin(flate_hip_ctx *c, size_t up_bytes, size_t down_bytes);
 int ctx_ctl_up(flate_hip_ctx *c, void *dev_dst, const void *host_src, size_t bytes);
 int ctx_ctl_down(flate_hip_ctx *c, void *host_dst, const void *dev_src, size_t bytes);
 void ctx_ctl_finish(flate_hip_ctx *c);
+// flate_hip_checksum_batch without its two ends (checksum.hip): d_in is DEVICE memory, in_off a host array, the n sums
+// stay in device memory at d_sums -- kernels queued on the ctx's stream, no read-back, no synchronise; the two
+// kernels between the events of `stage` (-1: the caller brackets a longer run of kernels itself).  The caller has
+// made room with ctx_ctl_begin: checksum_ctl_up_bytes(in_off, n) bytes of uploads.  Slot 0 of ctx_scratch holds the
+// partial results until the kernels have run, checksum_scratch_bytes(in_off, n) bytes of it: a caller that queues
+// several calls sizes the slot for the largest first, so that no call between them grows (frees) it.
+size_t checksum_ctl_up_bytes(const uint64_t *in_off, uint32_t n);
+size_t checksum_scratch_bytes(const uint64_t *in_off, uint32_t n);
+int checksum_device(flate_hip_ctx *c, const uint8_t *d_in, const uint64_t *in_off, uint32_t n, uint32_t kind,
+                    uint32_t *d_sums, int stage);
 }  // namespace flate

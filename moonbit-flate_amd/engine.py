@@ -43,6 +43,12 @@ def deflate_bound(n):
     return int(_lib.load().flate_hip_deflate_bound(int(n)))
 
 
+def frame_overhead(wrap, with_dict=False):
+    """Bytes a zlib / gzip member adds around its raw stream (flate_hip_frame_overhead)."""
+    return int(_lib.load().flate_hip_frame_overhead(_wrap_code(wrap) if isinstance(wrap, str) else int(wrap),
+                                                    1 if with_dict else 0))
+
+
 def synth(kind, n_streams, stream_len, seed=None, first_stream=0, nthreads=None):
     """Synthetic benchmark input: n_streams streams of stream_len bytes, back to back."""
     k = SYNTH_KINDS[kind] if isinstance(kind, str) else int(kind)
@@ -228,62 +234,92 @@ class FlateEngine:
                                                      DEVICE_PTRS if device else 0))
         return out[:n]
 
-    def deflate_batch_framed(self, data, in_off, wrap, compat_go=False, zdicts=None, dict_of=None):
+    def deflate_batch_framed(self, data, in_off, wrap, compat_go=False, zdicts=None, dict_of=None, out=None,
+                             out_cap=None):
         """The streams of a batch as zlib (RFC 1950) or gzip (RFC 1952) members: the raw DEFLATE streams of
-        deflate_batch between the container's header and its trailer -- Adler-32, or CRC-32 and the length,
-        computed on the GPU (flate_hip_checksum_batch).  Host data; returns (bytes array, off[n+1]).
+        deflate_batch between the container's header and its trailer -- Adler-32, or CRC-32 and the length --
+        written in place on the GPU by one call (flate_hip_deflate_fast_batch_framed; wrap "raw" is deflate_batch).
+        data: numpy uint8 (host; returns (exactly the members' bytes, off[n+1])) or a torch uint8 CUDA tensor (data
+        and result stay on the device; returns (out tensor, off[n+1] as numpy), the members in out[:off[-1]]).
         zdicts / dict_of (zlib only; as in deflate_batch): a member written with a dictionary carries FDICT and
         the dictionary's Adler-32 as DICTID (RFC 1950 2.2), so that inflate_batch_framed(..., zdicts=) and
-        zlib.decompressobj(zdict=) find it; the trailer stays the payload's checksum."""
-        data = np.ascontiguousarray(data, dtype=np.uint8)
+        zlib.decompressobj(zdict=) find it; the trailer stays the payload's checksum.  (gzip has no preset
+        dictionaries: ValueError.)"""
         in_off = np.ascontiguousarray(in_off, dtype=np.uint64)
         n = in_off.size - 1
-        heads = None
-        if zdicts is not None:
-            if wrap != "zlib":
-                raise ValueError("preset dictionaries exist in the zlib container only")
-            with_id = [zlib_dict_header(d) for d in _dict_list(zdicts)]
-            of = np.zeros(n, dtype=np.uint32) if dict_of is None else np.ascontiguousarray(dict_of, dtype=np.uint32)
-            heads = [ZLIB_HEADER if int(j) == NO_DICT else with_id[int(j)] for j in of]
-        raw, roff = self.deflate_batch(data, in_off, compat_go=compat_go, zdicts=zdicts, dict_of=dict_of)
-        sums = self.checksum_batch(data, in_off, "adler32" if wrap == "zlib" else "crc32")
-        head = ZLIB_HEADER if wrap == "zlib" else GZIP_HEADER
-        tail = 4 if wrap == "zlib" else 8
-        hlen = np.zeros(n + 1, dtype=np.uint64)
-        np.cumsum(np.array([len(h) for h in heads] if heads else [len(head)] * n, dtype=np.uint64), out=hlen[1:])
-        off = roff + hlen + np.arange(n + 1, dtype=np.uint64) * np.uint64(tail)
-        out = np.empty(int(off[-1]), dtype=np.uint8)
-        lens = (in_off[1:] - in_off[:-1]).astype(np.uint64)
-        for i in range(n):
-            o = int(off[i])
-            if heads:
-                head = heads[i]
-            out[o:o + len(head)] = np.frombuffer(head, np.uint8)
-            o += len(head)
-            k = int(roff[i + 1] - roff[i])
-            out[o:o + k] = raw[int(roff[i]):int(roff[i + 1])]
-            o += k
-            if wrap == "zlib":
-                out[o:o + 4] = np.frombuffer(int(sums[i]).to_bytes(4, "big"), np.uint8)
+        w = _wrap_code(wrap)
+        if zdicts is not None and w == WRAP_GZIP:
+            raise ValueError("preset dictionaries exist in the zlib container only")
+        device = _is_torch(data)
+        if out_cap is None and out is None:
+            lens = in_off[1:] - in_off[:-1]
+            out_cap = sum(deflate_bound(int(l)) * int(c) for l, c in zip(*np.unique(lens, return_counts=True))) + \
+                n * frame_overhead(wrap, zdicts is not None)
+        if device:
+            import torch
+            assert data.dtype == torch.uint8 and data.is_cuda and data.is_contiguous()
+            if out is None:
+                out = torch.empty(max(int(out_cap), 16), dtype=torch.uint8, device=data.device)
             else:
-                out[o:o + 8] = np.frombuffer(int(sums[i]).to_bytes(4, "little") +
-                                             (int(lens[i]) & 0xFFFFFFFF).to_bytes(4, "little"), np.uint8)
-        return out, off
+                _check_out(out, data, 0, "deflate_batch_framed")
+            cap = out.numel() if out_cap is None else min(int(out_cap), out.numel())
+            in_ptr, out_ptr = data.data_ptr(), out.data_ptr()
+        else:
+            data = np.ascontiguousarray(data, dtype=np.uint8)
+            if out is None:
+                out = np.empty(max(int(out_cap), 16), dtype=np.uint8)
+            else:
+                _check_out(out, data, 0, "deflate_batch_framed")
+            cap = out.size if out_cap is None else min(int(out_cap), out.size)
+            in_ptr, out_ptr = data.ctypes.data, out.ctypes.data
+        out_off = np.zeros(n + 1, dtype=np.uint64)
+        dk = _DictArgs(zdicts, dict_of, n, device) if zdicts is not None else None
+        self._check(self._L.flate_hip_deflate_fast_batch_framed(
+            self._ctx, in_ptr, in_off.ctypes.data, n, w, dk.ptr if dk else None, dk.off_ptr if dk else None,
+            dk.n_dicts if dk else 0, dk.of_ptr if dk else None, out_ptr, cap, out_off.ctypes.data,
+            self._flags(compat_go, False, device)))
+        return (out if device else out[:int(out_off[-1])]), out_off
 
-    def deflate_spliced_framed(self, data, in_off, wrap, compat_go=False):
+    def deflate_spliced_framed(self, data, in_off, wrap, compat_go=False, out=None, out_cap=None, index=False):
         """The whole batch as ONE zlib stream or ONE gzip member: the spliced DEFLATE stream of deflate_spliced
         (every input stream compressed on its own, in parallel, joined at bit granularity) between the
         container's header and the checksum of ALL the input -- what `gzip -d` / zlib.decompress turn back
-        into the concatenated input.  Host data; returns bytes."""
-        data = np.ascontiguousarray(data, dtype=np.uint8)
+        into the concatenated input; one call, framed on the GPU (flate_hip_deflate_fast_spliced_framed).
+        Host data: returns bytes.  A torch CUDA tensor, or index=True: returns (out, out_len, bit_off[n+1]) as
+        deflate_spliced does, bit_off counted from the raw stream's first byte (out[2:] zlib, out[10:] gzip)."""
         in_off = np.ascontiguousarray(in_off, dtype=np.uint64)
-        one, nbytes, _ = self.deflate_spliced(data, in_off, compat_go=compat_go)
-        total = int(in_off[-1] - in_off[0])
-        whole = np.array([in_off[0], in_off[-1]], dtype=np.uint64)
-        s = int(self.checksum_batch(data, whole, "adler32" if wrap == "zlib" else "crc32")[0])
-        if wrap == "zlib":
-            return ZLIB_HEADER + bytes(one[:int(nbytes)]) + s.to_bytes(4, "big")
-        return GZIP_HEADER + bytes(one[:int(nbytes)]) + s.to_bytes(4, "little") + (total & 0xFFFFFFFF).to_bytes(4, "little")
+        n = in_off.size - 1
+        w = _wrap_code(wrap)
+        device = _is_torch(data)
+        if out_cap is None and out is None:
+            lens = in_off[1:] - in_off[:-1]
+            out_cap = int(sum(deflate_bound(int(l)) * int(c) for l, c in zip(*np.unique(lens, return_counts=True)))) + \
+                16 + frame_overhead(wrap)
+        if device:
+            import torch
+            assert data.dtype == torch.uint8 and data.is_cuda and data.is_contiguous()
+            if out is None:
+                out = torch.empty(int(out_cap), dtype=torch.uint8, device=data.device)
+            else:
+                _check_out(out, data, 0, "deflate_spliced_framed")
+            cap = out.numel() if out_cap is None else min(int(out_cap), out.numel())
+            in_ptr, out_ptr = data.data_ptr(), out.data_ptr()
+        else:
+            data = np.ascontiguousarray(data, dtype=np.uint8)
+            if out is None:
+                out = np.zeros(int(out_cap), dtype=np.uint8)
+            else:
+                _check_out(out, data, 0, "deflate_spliced_framed")
+            cap = out.size if out_cap is None else min(int(out_cap), out.size)
+            in_ptr, out_ptr = data.ctypes.data, out.ctypes.data
+        bit_off = np.zeros(n + 1, dtype=np.uint64)
+        out_len = C.c_uint64(0)
+        self._check(self._L.flate_hip_deflate_fast_spliced_framed(
+            self._ctx, in_ptr, in_off.ctypes.data, n, w, out_ptr, cap, C.byref(out_len), bit_off.ctypes.data,
+            self._flags(compat_go, False, device)))
+        if device or index:
+            return out, int(out_len.value), bit_off
+        return bytes(out[:int(out_len.value)])
 
     def inflate_batch_framed(self, data, in_off, wrap, out_sizes=None, zdicts=None):
         """The reverse: zlib or gzip members -> (out, out_off, status[n]); status -4 (FLATE_HIP_E_CORRUPT) also
@@ -619,6 +655,14 @@ class StreamReader:
 
 
 CHECKSUM_ADLER32, CHECKSUM_CRC32 = 1, 2
+WRAP_RAW, WRAP_ZLIB, WRAP_GZIP = 0, 1, 2  # FLATE_HIP_WRAP_*
+WRAPS = {"raw": WRAP_RAW, "zlib": WRAP_ZLIB, "gzip": WRAP_GZIP}
+
+
+def _wrap_code(wrap):
+    """FLATE_HIP_WRAP_* of the framed methods' wrap argument ("zlib", "raw"; anything else has always meant gzip)."""
+    return WRAPS.get(wrap, WRAP_GZIP)
+
 ZLIB_HEADER = bytes([0x78, 0x01])  # CM = 8, CINFO = 7 (32 KiB window), FLEVEL = 0 (fastest), FCHECK (RFC 1950 2.2)
 GZIP_HEADER = bytes([0x1f, 0x8b, 8, 0, 0, 0, 0, 0, 4, 255])  # no name / time, XFL = 4 (fastest), OS unknown (RFC 1952 2.3)
 

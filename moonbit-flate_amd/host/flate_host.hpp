@@ -144,7 +144,8 @@ inline Err compress_batch(Engine &e, const std::vector<std::vector<uint8_t>> &st
 
 // The container formats around a raw stream (the reference has neither): zlib (RFC 1950: CMF, FLG,
 // data, Adler-32 big endian) and gzip (RFC 1952: ten header bytes, data, CRC-32 and length little endian).
-// The checksums come from the GPU (flate_hip_checksum_batch), the framing is these few bytes.
+// Members are WRITTEN on the GPU (flate_hip_deflate_fast_batch_framed); reading them -- parsing the header, checking the
+// trailer against flate_hip_checksum_batch -- is done here.
 enum class Wrap { Raw, Zlib, Gzip };
 
 inline Err checksum_batch(Engine &e, const std::vector<std::vector<uint8_t>> &streams, uint32_t kind,
@@ -161,36 +162,42 @@ inline Err checksum_batch(Engine &e, const std::vector<std::vector<uint8_t>> &st
   return std::nullopt;
 }
 
-// compress_batch with every stream inside its container
+inline uint32_t wrap_code(Wrap w) {
+  return w == Wrap::Zlib ? FLATE_HIP_WRAP_ZLIB : w == Wrap::Gzip ? FLATE_HIP_WRAP_GZIP : FLATE_HIP_WRAP_RAW;
+}
+
+// compress_batch with every stream inside its container: ONE call (flate_hip_deflate_fast_batch_framed) -- the input
+// crosses the link once, the checksums run on the device copy, headers and trailers are written there, and the
+// members come back in one piece.  D (may be null; zlib only): preset dictionaries as in compress_batch with a
+// DictTable; a member whose stream names one carries FDICT and the dictionary's Adler-32 as DICTID.
+inline Err compress_batch(Engine &e, const std::vector<std::vector<uint8_t>> &streams, const DictTable *D,
+                          const std::vector<uint32_t> &dict_of, std::vector<std::vector<uint8_t>> &out, Wrap wrap,
+                          uint32_t flags = 0) {
+  if (!e.ok()) return make_error(e, e.status());
+  const uint32_t n = (uint32_t)streams.size();
+  if (!dict_of.empty() && (!D || dict_of.size() != n)) return make_error(e, FLATE_HIP_E_INVALID);
+  const uint32_t w = wrap_code(wrap);
+  std::vector<uint64_t> in_off(n + 1, 0), out_off(n + 1, 0);
+  uint64_t cap = 16;
+  for (uint32_t i = 0; i < n; ++i) {
+    in_off[i + 1] = in_off[i] + streams[i].size();
+    cap += flate_hip_deflate_bound(streams[i].size()) + flate_hip_frame_overhead(w, D != nullptr);
+  }
+  std::vector<uint8_t> in(in_off[n] + 1), buf(cap);
+  for (uint32_t i = 0; i < n; ++i)
+    std::copy(streams[i].begin(), streams[i].end(), in.begin() + in_off[i]);
+  const int rc = flate_hip_deflate_fast_batch_framed(
+      e.ctx(), in.data(), in_off.data(), n, w, D ? D->bytes.data() : nullptr, D ? D->off.data() : nullptr,
+      D ? (uint32_t)D->off.size() - 1 : 0u, dict_of.empty() ? nullptr : dict_of.data(), buf.data(), cap, out_off.data(),
+      flags);
+  if (rc != 0) return make_error(e, rc);
+  out.resize(n);
+  for (uint32_t i = 0; i < n; ++i) out[i].assign(buf.begin() + out_off[i], buf.begin() + out_off[i + 1]);
+  return std::nullopt;
+}
 inline Err compress_batch(Engine &e, const std::vector<std::vector<uint8_t>> &streams,
                           std::vector<std::vector<uint8_t>> &out, Wrap wrap, uint32_t flags = 0) {
-  std::vector<std::vector<uint8_t>> raw;
-  if (Err er = compress_batch(e, streams, raw, flags)) return er;
-  if (wrap == Wrap::Raw) {
-    out = std::move(raw);
-    return std::nullopt;
-  }
-  std::vector<uint32_t> sums;
-  if (Err er = checksum_batch(e, streams, wrap == Wrap::Zlib ? FLATE_HIP_CHECKSUM_ADLER32 : FLATE_HIP_CHECKSUM_CRC32, sums))
-    return er;
-  static const uint8_t zhead[2] = {0x78, 0x01};  // CM = 8, 32 KiB window; FLEVEL = 0 (fastest), FCHECK
-  static const uint8_t ghead[10] = {0x1f, 0x8b, 8, 0, 0, 0, 0, 0, 4 /* XFL: fastest */, 255 /* OS: unknown */};
-  out.resize(raw.size());
-  for (size_t i = 0; i < raw.size(); ++i) {
-    std::vector<uint8_t> &m = out[i];
-    m.clear();
-    if (wrap == Wrap::Zlib) {
-      m.insert(m.end(), zhead, zhead + 2);
-      m.insert(m.end(), raw[i].begin(), raw[i].end());
-      for (int k = 3; k >= 0; --k) m.push_back((uint8_t)(sums[i] >> (8 * k)));
-    } else {
-      m.insert(m.end(), ghead, ghead + 10);
-      m.insert(m.end(), raw[i].begin(), raw[i].end());
-      for (int k = 0; k < 4; ++k) m.push_back((uint8_t)(sums[i] >> (8 * k)));
-      for (int k = 0; k < 4; ++k) m.push_back((uint8_t)((uint32_t)streams[i].size() >> (8 * k)));
-    }
-  }
-  return std::nullopt;
+  return compress_batch(e, streams, nullptr, {}, out, wrap, flags);
 }
 
 inline Err compress_spliced(Engine &e, const std::vector<std::vector<uint8_t>> &streams,
@@ -373,6 +380,32 @@ inline Err compress_spliced(Engine &e, const std::vector<std::vector<uint8_t>> &
   uint64_t len = 0;
   const int rc = flate_hip_deflate_fast_spliced(e.ctx(), in.data(), in_off.data(), n, buf.data(), cap, &len,
                                                 bo.data(), flags);
+  if (rc != 0) return make_error(e, rc);
+  out.assign(buf.begin(), buf.begin() + len);
+  if (bit_off) *bit_off = bo;
+  return std::nullopt;
+}
+
+// The whole batch as ONE zlib stream or ONE gzip member around the spliced stream, checksum and length over the
+// concatenated input (flate_hip_deflate_fast_spliced_framed): what gzip -d / zlib's uncompress turn back into all the
+// bytes.  bit_off counts from the raw stream's first byte, behind the 2 (zlib) or 10 (gzip) header bytes.
+inline Err compress_spliced(Engine &e, const std::vector<std::vector<uint8_t>> &streams, std::vector<uint8_t> &out,
+                            Wrap wrap, std::vector<uint64_t> *bit_off = nullptr, uint32_t flags = 0) {
+  if (!e.ok()) return make_error(e, e.status());
+  const uint32_t n = (uint32_t)streams.size();
+  const uint32_t w = wrap_code(wrap);
+  std::vector<uint64_t> in_off(n + 1, 0), bo(n + 1, 0);
+  uint64_t cap = 16 + flate_hip_frame_overhead(w, 0);
+  for (uint32_t i = 0; i < n; ++i) {
+    in_off[i + 1] = in_off[i] + streams[i].size();
+    cap += flate_hip_deflate_bound(streams[i].size());
+  }
+  std::vector<uint8_t> in(in_off[n] + 1), buf(cap);
+  for (uint32_t i = 0; i < n; ++i)
+    std::copy(streams[i].begin(), streams[i].end(), in.begin() + in_off[i]);
+  uint64_t len = 0;
+  const int rc = flate_hip_deflate_fast_spliced_framed(e.ctx(), in.data(), in_off.data(), n, w, buf.data(), cap, &len,
+                                                       bo.data(), flags);
   if (rc != 0) return make_error(e, rc);
   out.assign(buf.begin(), buf.begin() + len);
   if (bit_off) *bit_off = bo;
