@@ -332,7 +332,7 @@ int flate_hip_inflate_spliced(flate_hip_ctx *ctx, const uint8_t *in, uint64_t in
  * out: host.  Streams of any length: the work is cut into 64 KiB pieces, so one long stream fills the chip
  * as a batch of short ones does.  WRITING members -- header, raw stream, trailer, in place on the device -- is
  * flate_hip_deflate_fast_batch_framed / _spliced_framed below; READING them (header parsing, the check of the
- * trailer) is still the host mirrors' (flate_host::decompress_batch(..., Wrap), FlateEngine.inflate_batch_framed). */
+ * trailer against what was decoded) is flate_hip_inflate_batch_framed. */
 #define FLATE_HIP_CHECKSUM_ADLER32 1
 #define FLATE_HIP_CHECKSUM_CRC32 2
 int flate_hip_checksum_batch(flate_hip_ctx *ctx, const uint8_t *in, const uint64_t *in_off, uint32_t n_streams,
@@ -399,9 +399,7 @@ int flate_hip_deflate_fast_spliced(flate_hip_ctx *ctx, const uint8_t *in,
  *
  * flate_hip_frame_overhead (host only): the bytes a member adds around its raw stream -- RAW 0; ZLIB 6, with
  * with_dict != 0: 10; GZIP 18; an unknown wrap 0.
- * Out of scope: reading members through this ABI (header parsing on the device, checksums over out_len rather
- * than over slots, status merging) -- the host mirrors do that with flate_hip_inflate_batch(_dict) and
- * flate_hip_checksum_batch. */
+ * Reading members: flate_hip_inflate_batch_framed below. */
 #define FLATE_HIP_WRAP_RAW 0u
 #define FLATE_HIP_WRAP_ZLIB 1u /* RFC 1950 */
 #define FLATE_HIP_WRAP_GZIP 2u /* RFC 1952 */
@@ -414,6 +412,56 @@ int flate_hip_deflate_fast_batch_framed(flate_hip_ctx *ctx, const uint8_t *in, c
 int flate_hip_deflate_fast_spliced_framed(flate_hip_ctx *ctx, const uint8_t *in, const uint64_t *in_off,
                                           uint32_t n_streams, uint32_t wrap, uint8_t *out, uint64_t out_cap,
                                           uint64_t *out_len, uint64_t *bit_off, uint32_t flags);
+
+/* READING members: flate_hip_inflate_batch -- its output slots, out_len, status, return value (the first non-zero
+ * status), FLATE_HIP_DEVICE_PTRS, options and size limits -- for n_streams zlib or gzip members, member i =
+ * in[in_off[i], in_off[i+1]) = header | raw stream | trailer.  Header parsing, decoding and the check of the trailer
+ * against what was decoded all happen on the device, in one call, on one HIP stream: no host pass over member bytes, no
+ * host synchronisation between decode and verification.
+ *   Header, FLATE_HIP_WRAP_ZLIB (RFC 1950 2.2): CM = 8, CINFO <= 7, (CMF * 256 + FLG) % 31 == 0.  Without FDICT it is
+ *     2 bytes; with FDICT 6, and the member's dictionary is the FIRST j whose Adler-32 over the whole of dictionary j
+ *     equals DICTID (an empty dictionary has id 1).  FDICT with n_dicts == 0, or with an id that no dictionary has,
+ *     is a bad header.  The trailer is 4 bytes.
+ *   Header, FLATE_HIP_WRAP_GZIP (RFC 1952 2.3): 1f 8b, CM = 8, the reserved FLG bits zero; FEXTRA, FNAME, FCOMMENT and
+ *     FHCRC are skipped, in that order (the scan for a terminating NUL ends at the member's end).  The trailer is 8
+ *     bytes.  One range is one member: a file of several members is several ranges.
+ *   A member too short for its header plus trailer has a bad header.
+ *   The raw stream is exactly [member + header length, member end - trailer length): a stream that needs more bytes
+ *     than that is FLATE_HIP_E_UNEXPECTED_EOF -- the decoder does not run on into the trailer.  Bytes between the end
+ *     of the final block and the trailer are not examined: the trailer is the member's last 4 or 8 bytes.
+ *   The verdict, in this order:
+ *     1. a bad header: FLATE_HIP_E_CORRUPT, err_off = 0, out_len = 0;
+ *     2. the decoder's own non-zero status: status and err_off as flate_hip_inflate_batch reports them for the raw
+ *        stream alone (err_off counted from the raw stream's first byte); out_len = the bytes produced, delivered;
+ *     3. a checksum that is not the trailer's -- zlib: the Adler-32 of the out_len[i] bytes produced, big endian;
+ *        gzip: their CRC-32, little endian -- or, gzip, out_len mod 2^32 != ISIZE: FLATE_HIP_E_CORRUPT, err_off = the
+ *        member's length; the bytes are delivered.
+ *   dicts / dict_off / n_dicts (zlib only): the table of dictionaries of flate_hip_inflate_batch_dict (dict_off a HOST
+ *     array of n_dicts + 1 entries, dicts host or device like in); all NULL / 0: none.  There is no dict_of: every
+ *     member names its dictionary itself.  dict_used (HOST array of n_streams entries, may be NULL): entry i = the
+ *     dictionary chosen for member i, or FLATE_HIP_NO_DICT.  The tail of EVERY non-empty dictionary is staged per call
+ *     (which ones are used is known on the device only), and the decoders' dictionary build runs whenever a non-empty
+ *     dictionary is passed.
+ *   FLATE_HIP_SIZE_ONLY: as in flate_hip_inflate_batch -- and since nothing is stored, nothing can be summed: status
+ *     covers the header and the decode only, NOT the trailer's checksum or ISIZE.
+ *   FLATE_HIP_E_INVALID, before any HIP call: flate_hip_inflate_batch's checks; an unknown wrap; FLATE_HIP_WRAP_GZIP or
+ *     FLATE_HIP_WRAP_RAW with any dictionary argument; dict_off not monotone; dicts == NULL with non-empty dictionaries.
+ *   FLATE_HIP_WRAP_RAW (without dictionaries) IS flate_hip_inflate_batch: the same kernels, the same results (dict_used:
+ *     FLATE_HIP_NO_DICT throughout).  n_streams == 0: FLATE_HIP_OK.  A host-pointer call is copied in ONCE, in one
+ *     piece, and out once (no "host_pipeline_groups", as the framed write calls).
+ * How: the DICTIDs are the checksum kernels over the whole dictionaries; a parse kernel (one thread per member) checks
+ * the header, finds the raw stream, reads the trailer and matches the DICTID; the batch decoders read every stream's
+ * range and dictionary from what it wrote; the checksum kernels then run over 64 KiB pieces planned over the output
+ * SLOTS and clipped on the device to out_len[i]; a verdict kernel merges.  With profiling on, FLATE_HIP_STAGE_INFLATE is
+ * the decoder alone and FLATE_HIP_STAGE_CHECKSUM the contiguous run of output checksums plus verdict (0 for a size-only
+ * pass's sums: only the verdict kernel); the DICTID sums and the parse kernel run in front of the decoder's first
+ * event and are counted in NO stage. */
+int flate_hip_inflate_batch_framed(flate_hip_ctx *ctx, const uint8_t *in, const uint64_t *in_off,
+                                   uint32_t n_streams, uint32_t wrap,
+                                   const uint8_t *dicts, const uint64_t *dict_off, uint32_t n_dicts,
+                                   uint8_t *out, const uint64_t *out_off, uint64_t *out_len,
+                                   int32_t *status, int64_t *err_off, uint32_t *dict_used,
+                                   uint32_t flags);
 
 /* -- exchange step (multi-GPU) ---------------------------------------------------
  * SURVEY 8(e) / section 5; no counterpart in the reference (single-threaded, no communication
@@ -483,7 +531,8 @@ int flate_hip_gather_end(flate_hip_comm *comm, uint64_t *stream_off, uint64_t *s
  * milliseconds of the last call (stage names via flate_hip_stage_name). */
 #define FLATE_HIP_STAGE_LZ77 0
 #define FLATE_HIP_STAGE_HUFF_PACK 1
-#define FLATE_HIP_STAGE_CHECKSUM 2 /* flate_hip_checksum_batch; the checksum and frame kernels of the *_framed calls */
+#define FLATE_HIP_STAGE_CHECKSUM 2 /* flate_hip_checksum_batch; the checksum and frame kernels of the *_framed calls
+                                      (flate_hip_inflate_batch_framed: output checksums + verdict) */
 #define FLATE_HIP_STAGE_INFLATE 3
 #define FLATE_HIP_STAGE_COUNT 4
 int flate_hip_set_profiling(flate_hip_ctx *ctx, int on);

@@ -74,3 +74,12 @@ int flate_hip_mbt_deflate_batch_framed(flate_hip_ctx *c, const uint8_t *in, cons
                                        uint32_t flags) {
   return flate_hip_deflate_fast_batch_framed(c, in, in_off, n, wrap, 0, 0, 0, 0, out, out_cap, out_off, flags);
 }
+
+/* ... and so does the read side without preset dictionaries and without the per-member dictionary report (with
+ * dictionaries every array exists, and the .mbt file binds flate_hip_inflate_batch_framed directly) */
+int flate_hip_mbt_inflate_batch_framed(flate_hip_ctx *c, const uint8_t *in, const uint64_t *in_off, uint32_t n,
+                                       uint32_t wrap, uint8_t *out, const uint64_t *out_off, uint64_t *out_len,
+                                       int32_t *status, int64_t *err_off, uint32_t flags) {
+  return flate_hip_inflate_batch_framed(c, in, in_off, n, wrap, 0, 0, 0, out, out_off, out_len, status, err_off, 0,
+                                        flags);
+}

@@ -12,7 +12,7 @@ LIB_PATH = os.path.join(LIB_DIR, "libflate_hip.so")
 SOURCES = ["lz77_kernels.hip",  "huff_pack_kernels.hip", "compact_kernels.hip",
            "inflate_kernels.hip", "splice_kernels.hip", "flate_api.hip", "gather.hip", "checksum.hip", "frame_kernels.hip",
            "synth.cpp"]
-HEADERS = ["flate_common.h", "flate_kernels.h", "lz77_device.h", "inflate_spec_kernel.inc", "inflate_stream_kernel.inc",
+HEADERS = ["flate_common.h", "flate_kernels.h", "checksum_clip.h", "lz77_device.h", "inflate_spec_kernel.inc", "inflate_stream_kernel.inc",
            os.path.join(ROOT, "include", "flate_hip.h")]
 
 
@@ -20,8 +20,8 @@ GROUPS = {  # which sources a kernel family's measurements depend on (besides th
     "lz77": ["lz77_kernels.hip", "lz77_device.h"],
     "huff": ["huff_pack_kernels.hip", "compact_kernels.hip", "splice_kernels.hip"],
     "inflate": ["inflate_kernels.hip", "inflate_spec_kernel.inc", "inflate_stream_kernel.inc"],
-    "checksum": ["checksum.hip"],
-    "frame": ["frame_kernels.hip", "checksum.hip"],
+    "checksum": ["checksum.hip", "checksum_clip.h"],
+    "frame": ["frame_kernels.hip", "checksum.hip", "checksum_clip.h"],
 }
 SHARED = ["flate_common.h", "flate_kernels.h", "flate_api.hip"]
 

@@ -26,6 +26,7 @@
 
 #include <string>
 
+#include "checksum_clip.h"
 #include "flate_hip.h"
 #include "flate_kernels.h"
 
@@ -33,51 +34,15 @@ namespace flate {
 
 namespace {
 
-constexpr uint32_t kPiece = 65536;  // bytes per wavefront and step
+constexpr uint32_t kPiece = kSumPiece;  // bytes per wavefront and step (checksum_clip.h)
 constexpr uint32_t kChunk = 1024;   // bytes per lane of it
-constexpr uint32_t kPoly = 0xedb88320u;
-constexpr uint32_t kAdlerMod = 65521u;
-
-// a(x) * b(x) mod P in the reflected representation (bit 31 = x^0); zlib's multmodp
-__host__ __device__ inline uint32_t multmodp(uint32_t a, uint32_t b) {
-  uint32_t m = 1u << 31, p = 0;
-  for (;;) {
-    if (a & m) {
-      p ^= b;
-      if ((a & (m - 1u)) == 0) break;
-    }
-    m >>= 1;
-    b = (b & 1u) ? (b >> 1) ^ kPoly : b >> 1;
-  }
-  return p;
-}
-
-struct X2n {
-  uint32_t t[32];  // x^(2^n) mod P
-};
-inline X2n make_x2n() {
-  X2n r;
-  uint32_t p = 1u << 30;  // x^1
-  r.t[0] = p;
-  for (int n = 1; n < 32; ++n) r.t[n] = p = multmodp(p, p);
-  return r;
-}
-
-// x^(n * 2^k) mod P
-__device__ inline uint32_t x2nmodp(const X2n &T, uint64_t n, unsigned k) {
-  uint32_t p = 1u << 31;  // x^0
-  while (n) {
-    if (n & 1u) p = multmodp(T.t[k & 31u], p);
-    n >>= 1;
-    ++k;
-  }
-  return p;
-}
+constexpr uint32_t kPoly = kSumPoly;
+constexpr uint32_t kAdlerMod = kSumAdlerMod;
 
 struct PieceParams {
   const uint8_t *in;
   const uint64_t *piece_off;  // absolute offset of every piece in `in`
-  const uint32_t *piece_len;  // 1 .. kPiece
+  const uint32_t *piece_len;  // 1 .. kPiece; 0: a piece planned over a slot, beyond what its stream produced
   uint32_t n_pieces;
   uint32_t want_crc, want_adler;
   uint32_t *crc;      // per piece
@@ -236,6 +201,8 @@ struct FoldParams {
   uint32_t n_streams;
   uint32_t want_crc;  // else Adler-32
   uint32_t max_pieces;  // pieces of the longest stream
+  const uint64_t *n_len;  // per stream: its bytes where the pieces were planned over slots and clipped on the device
+                          // (checksum_clip_kernel); null: in_off[s + 1] - in_off[s]
   X2n x2n;
 };
 
@@ -255,14 +222,14 @@ __global__ __launch_bounds__(256) void checksum_fold_kernel(FoldParams P) {
   }
   if (s >= P.n_streams) return;
   const uint32_t p0 = P.piece_base[s], p1 = P.piece_base[s + 1];
-  const uint32_t np = p1 - p0, run = (np + 63u) / 64u;
-  const uint32_t k0 = p0 + run * (uint32_t)lane < p1 ? p0 + run * (uint32_t)lane : p1;
-  const uint32_t k1 = k0 + run < p1 ? k0 + run : p1;
-  const uint64_t n = P.in_off[s + 1] - P.in_off[s];
+  const uint64_t n = P.n_len ? P.n_len[s] : P.in_off[s + 1] - P.in_off[s];
+  // (clipped pieces: a piece may be empty and a run may lie beyond the data -- fold_run keeps `start` within n)
+  const FoldRun R = fold_run(p1 - p0, (uint32_t)lane, n);
+  const uint32_t k0 = p0 + R.k0, k1 = p0 + R.k1;
   if (P.want_crc) {
     const uint32_t xpiece = x2nmodp(P.x2n, kPiece, 3);
     uint32_t c = 0;
-    uint64_t end = (uint64_t)(k0 - p0) * kPiece;  // bytes of the stream in front of my run, then behind its pieces
+    uint64_t end = R.start;  // bytes of the stream in front of my run, then behind its pieces
     for (uint32_t k = k0; k < k1; ++k) {
       const uint32_t len = P.piece_len[k];
       if (len == kPiece && tables)
@@ -272,12 +239,12 @@ __global__ __launch_bounds__(256) void checksum_fold_kernel(FoldParams P) {
       c ^= P.crc[k];
       end += len;
     }
-    if (k1 > k0) c = multmodp(x2nmodp(P.x2n, n - end, 3), c);
+    if (k1 > k0) c = crc_place(P.x2n, c, n - end);
     for (int d = 32; d >= 1; d >>= 1) c ^= (uint32_t)__shfl_xor((int)c, d);
     if (lane == 0) P.out[s] = c;
   } else {
     // s1 = 1 + sum b;  s2 = n + sum (n - i) b_i = n + n * sum b - sum i b_i   (all mod 65521, RFC 1950 8.2)
-    uint64_t sa = 0, sib = 0, base = (uint64_t)(k0 - p0) * kPiece;
+    uint64_t sa = 0, sib = 0, base = R.start;
     for (uint32_t k = k0; k < k1; ++k) {
       const uint64_t a = P.asum[k];
       sa = (sa + a) % kAdlerMod;
@@ -288,13 +255,34 @@ __global__ __launch_bounds__(256) void checksum_fold_kernel(FoldParams P) {
       sa += (uint64_t)__shfl_xor((long long)sa, d);
       sib += (uint64_t)__shfl_xor((long long)sib, d);
     }
-    sa %= kAdlerMod;
-    sib %= kAdlerMod;
-    const uint64_t nm = n % kAdlerMod;
-    const uint32_t s1 = (uint32_t)((1u + sa) % kAdlerMod);
-    const uint32_t s2 = (uint32_t)((nm + nm * sa + (uint64_t)kAdlerMod * kAdlerMod - sib) % kAdlerMod);
-    if (lane == 0) P.out[s] = (s2 << 16) | s1;
+    if (lane == 0) P.out[s] = adler_finish(sa, sib, n);
   }
+}
+
+// Pieces planned over output SLOTS (flate_hip_inflate_batch_framed: what a stream produced is known on the device
+// only): one wavefront per stream clips its pieces to the bytes produced -- never more than the slot holds -- and
+// leaves that length for the fold.  A stream with a verdict already (a bad header, a decoder status) needs no sum:
+// its pieces are empty.
+struct ClipParams {
+  const uint64_t *slot_off;    // n_streams + 1
+  const uint32_t *piece_base;  // n_streams + 1
+  const uint64_t *produced;    // per stream: out_len of the decoder
+  const int32_t *status;       // per stream: the decoder's
+  const uint32_t *bad;         // per stream: non-zero = bad header
+  uint32_t *piece_len;
+  uint64_t *n_len;
+  uint32_t n_streams;
+};
+__global__ __launch_bounds__(256) void checksum_clip_kernel(ClipParams P) {
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t s = blockIdx.x * 4u + (threadIdx.x >> 6);
+  if (s >= P.n_streams) return;
+  const uint64_t slot = P.slot_off[s + 1] - P.slot_off[s];
+  uint64_t n = P.produced[s] < slot ? P.produced[s] : slot;
+  if (P.status[s] != 0 || P.bad[s] != 0) n = 0;
+  const uint32_t p0 = P.piece_base[s], np = P.piece_base[s + 1] - p0;
+  for (uint32_t k = lane; k < np; k += 64u) P.piece_len[p0 + k] = clip_piece_len(n, k);
+  if (lane == 0) P.n_len[s] = n;
 }
 
 }  // namespace
@@ -306,11 +294,11 @@ using namespace flate;
 namespace {
 // checksum_device's arrays in slot 0 of the ctx's scratch: offsets for np pieces of n streams, and the bytes of all
 struct Carve {
-  size_t poff, wsum, ioff, plen, pbase, crc, asum, bytes = 0;
+  size_t poff, wsum, ioff, plen, pbase, crc, asum, nlen, bytes = 0;
   Carve(size_t np, size_t n) {
     auto carve = [&](size_t b) { const size_t o = bytes; bytes += (b + 255) & ~(size_t)255; return o; };
     poff = carve(np * 8), wsum = carve(np * 8), ioff = carve((n + 1) * 8), plen = carve(np * 4 + 4);
-    pbase = carve((n + 1) * 4 + 4), crc = carve(np * 4), asum = carve(np * 4);
+    pbase = carve((n + 1) * 4 + 4), crc = carve(np * 4), asum = carve(np * 4), nlen = carve(n * 8 + 8);
   }
 };
 size_t count_pieces(const uint64_t *in_off, uint32_t n) {
@@ -328,8 +316,34 @@ size_t flate::checksum_ctl_up_bytes(const uint64_t *in_off, uint32_t n) {
 }
 
 // The kernels of flate_hip_checksum_batch on input that is on the device already; the sums stay there (flate_kernels.h).
+namespace {
+// what the decoder left on the device for checksum_device_clipped (null: the pieces are the streams')
+struct Produced {
+  const uint64_t *out_len;
+  const int32_t *status;
+  const uint32_t *bad;
+};
+int checksum_run(flate_hip_ctx *c, const uint8_t *d_in, const uint64_t *in_off, uint32_t n, uint32_t kind,
+                 uint32_t *d_sums, int stage, const Produced *clip);
+}  // namespace
+
 int flate::checksum_device(flate_hip_ctx *c, const uint8_t *d_in, const uint64_t *in_off, uint32_t n, uint32_t kind,
                            uint32_t *d_sums, int stage) {
+  return checksum_run(c, d_in, in_off, n, kind, d_sums, stage, nullptr);
+}
+
+// The same over what a decoder PRODUCED in its output slots (flate_kernels.h): the pieces are planned over the slots
+// slot_off, which the host knows, and clipped on the device to out_len[i].
+int flate::checksum_device_clipped(flate_hip_ctx *c, const uint8_t *d_out, const uint64_t *slot_off, uint32_t n,
+                                   uint32_t kind, const uint64_t *d_out_len, const int32_t *d_status,
+                                   const uint32_t *d_bad, uint32_t *d_sums) {
+  const Produced clip{d_out_len, d_status, d_bad};
+  return checksum_run(c, d_out, slot_off, n, kind, d_sums, -1, &clip);
+}
+
+namespace {
+int checksum_run(flate_hip_ctx *c, const uint8_t *d_in, const uint64_t *in_off, uint32_t n, uint32_t kind,
+                 uint32_t *d_sums, int stage, const Produced *clip) {
   if (n == 0) return FLATE_HIP_OK;
   auto hip_fail = [&](const char *what) -> int {
     ctx_set_error(c, std::string(what) + ": " + hipGetErrorString(hipGetLastError()));
@@ -352,7 +366,7 @@ int flate::checksum_device(flate_hip_ctx *c, const uint8_t *d_in, const uint64_t
   const uint32_t np = (uint32_t)plen.size();
   // one grow-only scratch of the ctx, carved into the call's arrays (round 4 did nine hipMalloc / hipFree
   // pairs per call: hipFree drains the whole device, i.e. every other context and the host pipelines' lanes)
-  struct Dev { void *p = nullptr; } d_poff, d_plen, d_pbase, d_ioff, d_crc, d_asum, d_wsum;
+  struct Dev { void *p = nullptr; } d_poff, d_plen, d_pbase, d_ioff, d_crc, d_asum, d_wsum, d_nlen;
   {
     const Carve o(np, n);
     void *base = nullptr;
@@ -360,16 +374,28 @@ int flate::checksum_device(flate_hip_ctx *c, const uint8_t *d_in, const uint64_t
     if (rc != FLATE_HIP_OK) return rc;
     uint8_t *b8 = (uint8_t *)base;
     d_poff.p = b8 + o.poff, d_wsum.p = b8 + o.wsum, d_ioff.p = b8 + o.ioff, d_plen.p = b8 + o.plen;
-    d_pbase.p = b8 + o.pbase, d_crc.p = b8 + o.crc, d_asum.p = b8 + o.asum;
+    d_pbase.p = b8 + o.pbase, d_crc.p = b8 + o.crc, d_asum.p = b8 + o.asum, d_nlen.p = b8 + o.nlen;
   }
   // the index arrays travel through the ctx's pinned staging and its copy kernel, not through DMA
   // commands that queue behind whatever bulk copy another thread has in flight (flate_api.hip: ctl_up)
   {
     int rc = ctx_ctl_up(c, d_poff.p, poff.data(), (size_t)np * 8);
-    if (rc == FLATE_HIP_OK) rc = ctx_ctl_up(c, d_plen.p, plen.data(), (size_t)np * 4);
+    if (rc == FLATE_HIP_OK && !clip) rc = ctx_ctl_up(c, d_plen.p, plen.data(), (size_t)np * 4);
     if (rc == FLATE_HIP_OK) rc = ctx_ctl_up(c, d_pbase.p, pbase.data(), ((size_t)n + 1) * 4);
     if (rc == FLATE_HIP_OK) rc = ctx_ctl_up(c, d_ioff.p, in_off, ((size_t)n + 1) * 8);
     if (rc != FLATE_HIP_OK) return rc;
+  }
+  if (clip) {  // the pieces' lengths come from what the decoder produced
+    ClipParams K{};
+    K.slot_off = (const uint64_t *)d_ioff.p;
+    K.piece_base = (const uint32_t *)d_pbase.p;
+    K.produced = clip->out_len;
+    K.status = clip->status;
+    K.bad = clip->bad;
+    K.piece_len = (uint32_t *)d_plen.p;
+    K.n_len = (uint64_t *)d_nlen.p;
+    K.n_streams = n;
+    hipLaunchKernelGGL(checksum_clip_kernel, dim3((n + 3) / 4), dim3(256), 0, st, K);
   }
   const X2n x2n = make_x2n();
   if (np) {
@@ -404,6 +430,7 @@ int flate::checksum_device(flate_hip_ctx *c, const uint8_t *d_in, const uint64_t
   F.want_crc = kind == FLATE_HIP_CHECKSUM_CRC32;
   F.max_pieces = 0;
   for (uint32_t i = 0; i < n; ++i) F.max_pieces = pbase[i + 1] - pbase[i] > F.max_pieces ? pbase[i + 1] - pbase[i] : F.max_pieces;
+  F.n_len = clip ? (const uint64_t *)d_nlen.p : nullptr;
   F.x2n = x2n;
   hipLaunchKernelGGL(checksum_fold_kernel, dim3((n + 3) / 4), dim3(256), 0, st, F);
   if (stage >= 0) ctx_stage_end(c, stage);
@@ -417,6 +444,7 @@ int flate::checksum_device(flate_hip_ctx *c, const uint8_t *d_in, const uint64_t
     return FLATE_HIP_E_INTERNAL;
   }
 }
+}  // namespace
 
 extern "C" int flate_hip_checksum_batch(flate_hip_ctx *c, const uint8_t *in, const uint64_t *in_off, uint32_t n,
                                         uint32_t kind, uint32_t *out, uint32_t flags) {

@@ -67,6 +67,10 @@ struct flate_hip_ctx {
   // the *_framed calls: member offsets, the streams' checksums, per stream its dictionary, the dictionaries' Adler-32
   // (DICTIDs) and, for host callers, the whole dictionaries
   DevBuf d_frame_off, d_frame_sums, d_frame_dict_of, d_frame_ids, d_frame_dicts;
+  // flate_hip_inflate_batch_framed (it shares d_frame_off: the raw streams' starts, d_frame_sums, d_frame_ids,
+  // d_frame_dicts): the raw streams' ends, the trailers' sums and ISIZEs, the header verdicts, the chosen dictionaries,
+  // and per dictionary where its staged tail lies and how long it is
+  DevBuf d_rd_end, d_rd_want, d_rd_isize, d_rd_bad, d_rd_dict, d_rd_tail_at, d_rd_tail_len;
   hipStream_t guest_stream = nullptr;
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
   int guest_blocks = 0;      // 0 = guest kernel off
@@ -1800,12 +1804,32 @@ struct InfDict {
   const uint32_t *h_len;
 };
 
+// The container of flate_hip_inflate_batch_framed (frame_kernels.hip: frame_parse_kernel / frame_verdict_kernel);
+// everything here is the caller's.
+struct InfFrame {
+  uint32_t wrap;             // FLATE_HIP_WRAP_ZLIB / _GZIP
+  const uint8_t *dicts;      // the WHOLE dictionaries (host, or device under FLATE_HIP_DEVICE_PTRS) ...
+  const uint64_t *dict_off;  // ... dictionary j = dicts[dict_off[j], dict_off[j+1])
+  uint32_t n_dicts;
+  uint32_t *dict_used;       // host, per member (may be null): the dictionary its DICTID chose
+};
+
+struct DictSlots;
+static DictSlots dict_slots(const uint64_t *dict_off, uint32_t n_dicts, const uint32_t *dict_of, uint32_t n,
+                            uint32_t min_len);
+static int dict_upload(flate_hip_ctx *c, const DictSlots &S, const uint8_t *dicts, const uint64_t *dict_off,
+                       uint32_t flags);
+static int inflate_frame_prepare(flate_hip_ctx *c, const InfFrame &FRD, const uint8_t *d_in, uint32_t n, uint32_t flags,
+                                 InfParams &I, FrameReadParams &R, bool &dict);
+
 // Both decode entry points.  spliced_len != 0: `in` is ONE stream of that many bytes and in_off
 // holds the bit positions of its n pieces (flate_hip_inflate_spliced).  D != NULL: the streams'
-// dictionaries (a launch in which a stream has one runs the decoder's dictionary build).
+// dictionaries (a launch in which a stream has one runs the decoder's dictionary build).  FRD != NULL: the streams are
+// members of a container (flate_hip_inflate_batch_framed): parsed in front of the decoder, checked behind it.
 static int inflate_common(flate_hip_ctx *c, const uint8_t *in, const uint64_t *in_off, uint32_t n,
                           uint8_t *out, const uint64_t *out_off, uint64_t *out_len, int32_t *status,
-                          int64_t *err_off, uint32_t flags, uint64_t spliced_len, const InfDict *D = nullptr) {
+                          int64_t *err_off, uint32_t flags, uint64_t spliced_len, const InfDict *D = nullptr,
+                          const InfFrame *FRD = nullptr) {
   const bool spliced = spliced_len != 0;
   const bool size_only = (flags & FLATE_HIP_SIZE_ONLY) != 0 && !spliced;
   const uint64_t in_bytes = spliced ? spliced_len : in_off[n];
@@ -1831,7 +1855,17 @@ static int inflate_common(flate_hip_ctx *c, const uint8_t *in, const uint64_t *i
   if ((rc = ensure(c, c->d_out_len, (size_t)n * 8 + 8))) return rc;
   if ((rc = ensure(c, c->d_istatus, (size_t)n * 4 + 4))) return rc;
   if ((rc = ensure(c, c->d_ierr, (size_t)n * 8 + 8))) return rc;
-  if ((rc = ctl_begin(c, ((size_t)n + 1) * 16, (size_t)n * 20 + 64))) return rc;
+  // (a member call: the index arrays of its two runs of checksums -- the DICTIDs, what the decoder produced -- and
+  // the dictionaries' tails travel the same way)
+  std::vector<uint64_t> f_doff;  // the dictionaries counted from the first one's start
+  size_t f_up = 0;
+  if (FRD) {
+    f_doff.assign((size_t)FRD->n_dicts + 1, 0);
+    for (uint32_t j = 1; j <= FRD->n_dicts; ++j) f_doff[j] = FRD->dict_off[j] - FRD->dict_off[0];
+    f_up = checksum_ctl_up_bytes(f_doff.data(), FRD->n_dicts) + (size_t)FRD->n_dicts * 12 + 1024;
+    if (!size_only) f_up += checksum_ctl_up_bytes(out_off, n);
+  }
+  if ((rc = ctl_begin(c, ((size_t)n + 1) * 16 + f_up, (size_t)n * (FRD ? 24 : 20) + 64 + (FRD ? 256 : 0)))) return rc;
   if ((rc = ctl_up(c, c->d_in_off.p, in_off, ((size_t)n + 1) * 8))) return rc;
   if ((rc = ctl_up(c, c->d_slot_off.p, out_off, ((size_t)n + 1) * 8))) return rc;
   InfParams I{};
@@ -1852,6 +1886,30 @@ static int inflate_common(flate_hip_ctx *c, const uint8_t *in, const uint64_t *i
     I.dict_at = D->at;
     I.dict_len = D->len;
     for (uint32_t i = 0; i < n && !dict; ++i) dict = D->h_len[i] != 0;
+  }
+  FrameReadParams R{};
+  if (FRD) {
+    // both runs of checksums carve slot 0 of the scratch: sized once for the larger, so that the second does not free
+    // what the first's kernels are still to read
+    const size_t sa = checksum_scratch_bytes(f_doff.data(), FRD->n_dicts);
+    const size_t sb = size_only ? 0 : checksum_scratch_bytes(out_off, n);
+    void *unused = nullptr;
+    if ((rc = ctx_scratch(c, 0, sa > sb ? sa : sb, &unused))) return rc;
+    if (FRD->n_dicts) {
+      const uint64_t bytes = f_doff[FRD->n_dicts];
+      const uint8_t *d_whole = FRD->dicts ? FRD->dicts + FRD->dict_off[0] : nullptr;
+      if (!dev) {  // (for the DICTIDs the whole dictionaries are uploaded, not only their tails)
+        if ((rc = ensure(c, c->d_frame_dicts, bytes + 16))) return rc;
+        if (bytes) HIP_TRY(c, hipMemcpyAsync(c->d_frame_dicts.p, d_whole, bytes, hipMemcpyHostToDevice, c->stream));
+        d_whole = (const uint8_t *)c->d_frame_dicts.p;
+      }
+      if ((rc = ensure(c, c->d_frame_ids, (size_t)FRD->n_dicts * 4 + 4))) return rc;
+      if ((rc = checksum_device(c, d_whole, f_doff.data(), FRD->n_dicts, FLATE_HIP_CHECKSUM_ADLER32,
+                                (uint32_t *)c->d_frame_ids.p, -1)))
+        return rc;
+    }
+    if ((rc = inflate_frame_prepare(c, *FRD, d_in, n, flags, I, R, dict))) return rc;
+    hipLaunchKernelGGL(frame_parse_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, R);
   }
   {
     StageTimer t(c, FLATE_HIP_STAGE_INFLATE);
@@ -1911,6 +1969,22 @@ static int inflate_common(flate_hip_ctx *c, const uint8_t *in, const uint64_t *i
     }
   }
   HIP_TRY(c, hipGetLastError());
+  if (FRD) {
+    // the sums of what every member produced (nothing is stored by a size-only pass: nothing to sum), then the verdict
+    StageTimer t(c, FLATE_HIP_STAGE_CHECKSUM);
+    if (!size_only) {
+      if ((rc = ensure(c, c->d_frame_sums, (size_t)n * 4 + 8))) return rc;
+      if ((rc = checksum_device_clipped(c, d_out, out_off, n,
+                                        FRD->wrap == FLATE_HIP_WRAP_GZIP ? FLATE_HIP_CHECKSUM_CRC32 : FLATE_HIP_CHECKSUM_ADLER32,
+                                        (const uint64_t *)c->d_out_len.p, (const int32_t *)c->d_istatus.p,
+                                        (const uint32_t *)c->d_rd_bad.p, (uint32_t *)c->d_frame_sums.p)))
+        return rc;
+      R.sums = (const uint32_t *)c->d_frame_sums.p;
+    }
+    hipLaunchKernelGGL(frame_verdict_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, R);
+    HIP_TRY(c, hipGetLastError());
+    if (FRD->dict_used && (rc = ctl_down(c, FRD->dict_used, c->d_rd_dict.p, (size_t)n * 4))) return rc;
+  }
   if ((rc = ctl_down(c, out_len, c->d_out_len.p, (size_t)n * 8))) return rc;
   if ((rc = ctl_down(c, status, c->d_istatus.p, (size_t)n * 4))) return rc;
   if ((rc = ctl_down(c, err_off, c->d_ierr.p, (size_t)n * 8))) return rc;
@@ -1919,7 +1993,7 @@ static int inflate_common(flate_hip_ctx *c, const uint8_t *in, const uint64_t *i
   HIP_TRY(c, hipGetLastError());
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   ctl_finish(c);
-  const bool used[FLATE_HIP_STAGE_COUNT] = {false, false, false, true};
+  const bool used[FLATE_HIP_STAGE_COUNT] = {false, false, FRD != nullptr, true};
   if ((rc = collect_timing(c, used))) return rc;
   // A size-only pass has no capacity -- but the kernels count output in 32 bits: a stream that inflates
   // to 4 GiB or more stops there with "slot too small", which for a call without slots means "too large"
@@ -2071,6 +2145,68 @@ static int dict_upload(flate_hip_ctx *c, const DictSlots &S, const uint8_t *dict
   for (size_t k = 0; k < S.at.size(); ++k)
     HIP_TRY(c, hipMemcpyAsync((uint8_t *)c->d_dicts.p + S.at[k], dicts + dict_off[S.dict[k] + 1] - S.len[k], S.len[k],
                               kind, c->stream));
+  return FLATE_HIP_OK;
+}
+
+// The device side of a member call in front of its parse kernel: the arrays that kernel fills, and -- the host cannot
+// know which dictionaries the members name before the device has parsed -- the tail of EVERY non-empty dictionary,
+// staged as for flate_hip_inflate_batch_dict.  The decoders read the raw streams' ranges and their dictionaries from
+// what the parse kernel writes; `dict`: run their dictionary build (whenever a non-empty dictionary is passed).
+static int inflate_frame_prepare(flate_hip_ctx *c, const InfFrame &FRD, const uint8_t *d_in, uint32_t n, uint32_t flags,
+                                 InfParams &I, FrameReadParams &R, bool &dict) {
+  int rc;
+  if ((rc = ensure(c, c->d_frame_off, ((size_t)n + 1) * 8))) return rc;
+  if ((rc = ensure(c, c->d_rd_end, (size_t)n * 8 + 8))) return rc;
+  if ((rc = ensure(c, c->d_rd_want, (size_t)n * 4 + 4))) return rc;
+  if ((rc = ensure(c, c->d_rd_isize, (size_t)n * 4 + 4))) return rc;
+  if ((rc = ensure(c, c->d_rd_bad, (size_t)n * 4 + 4))) return rc;
+  if ((rc = ensure(c, c->d_rd_dict, (size_t)n * 4 + 4))) return rc;
+  R.in = d_in;
+  R.in_off = (const uint64_t *)c->d_in_off.p;
+  R.n_streams = n;
+  R.wrap = FRD.wrap;
+  R.n_dicts = FRD.n_dicts;
+  R.pay_off = (uint64_t *)c->d_frame_off.p;
+  R.pay_end = (uint64_t *)c->d_rd_end.p;
+  R.want = (uint32_t *)c->d_rd_want.p;
+  R.isize = (uint32_t *)c->d_rd_isize.p;
+  R.bad = (uint32_t *)c->d_rd_bad.p;
+  R.dict_used = (uint32_t *)c->d_rd_dict.p;
+  R.out_len = I.out_len;
+  R.status = I.status;
+  R.err_off = I.err_off;
+  if (FRD.n_dicts) {
+    std::vector<uint32_t> every(FRD.n_dicts);
+    for (uint32_t j = 0; j < FRD.n_dicts; ++j) every[j] = j;
+    const DictSlots S = dict_slots(FRD.dict_off, FRD.n_dicts, every.data(), FRD.n_dicts, 1);
+    std::vector<uint64_t> t_at(FRD.n_dicts, 0);
+    std::vector<uint32_t> t_len(FRD.n_dicts, 0);
+    for (uint32_t j = 0; j < FRD.n_dicts; ++j) {
+      if (S.slot_of[j] == DictSlots::kNone) continue;
+      t_at[j] = S.at[S.slot_of[j]];
+      t_len[j] = S.len[S.slot_of[j]];
+    }
+    if ((rc = dict_upload(c, S, FRD.dicts, FRD.dict_off, flags))) return rc;
+    if ((rc = ensure(c, c->d_rd_tail_at, (size_t)FRD.n_dicts * 8 + 8))) return rc;
+    if ((rc = ensure(c, c->d_rd_tail_len, (size_t)FRD.n_dicts * 4 + 4))) return rc;
+    if ((rc = ensure(c, c->d_dict_at, (size_t)n * 8 + 8))) return rc;
+    if ((rc = ensure(c, c->d_dict_len, (size_t)n * 4 + 4))) return rc;
+    if ((rc = ctl_up(c, c->d_rd_tail_at.p, t_at.data(), (size_t)FRD.n_dicts * 8))) return rc;
+    if ((rc = ctl_up(c, c->d_rd_tail_len.p, t_len.data(), (size_t)FRD.n_dicts * 4))) return rc;
+    R.dict_id = (const uint32_t *)c->d_frame_ids.p;
+    R.tail_at = (const uint64_t *)c->d_rd_tail_at.p;
+    R.tail_len = (const uint32_t *)c->d_rd_tail_len.p;
+    R.dict_at = (uint64_t *)c->d_dict_at.p;
+    R.dict_len = (uint32_t *)c->d_dict_len.p;
+    dict = !S.at.empty();
+    if (dict) {
+      I.dict_buf = (const uint8_t *)c->d_dicts.p;
+      I.dict_at = R.dict_at;
+      I.dict_len = R.dict_len;
+    }
+  }
+  I.in_off = R.pay_off;
+  I.in_end = R.pay_end;
   return FLATE_HIP_OK;
 }
 
@@ -2276,6 +2412,41 @@ int flate_hip_deflate_fast_spliced_framed(flate_hip_ctx *c, const uint8_t *in, c
     const FrameReq FR{wrap, nullptr, nullptr, nullptr, 0};
     return deflate_common(c, in, in_off, n, out, out_cap, bit_off, flags, true, out_len, nullptr, &FR);
   } catch (const std::exception &e) {
+    c->hip_err = e.what();
+    return FLATE_HIP_E_INTERNAL;
+  }
+}
+
+int flate_hip_inflate_batch_framed(flate_hip_ctx *c, const uint8_t *in, const uint64_t *in_off, uint32_t n,
+                                   uint32_t wrap, const uint8_t *dicts, const uint64_t *dict_off, uint32_t n_dicts,
+                                   uint8_t *out, const uint64_t *out_off, uint64_t *out_len, int32_t *status,
+                                   int64_t *err_off, uint32_t *dict_used, uint32_t flags) {
+  // every check before any HIP call
+  if (!c || wrap > FLATE_HIP_WRAP_GZIP) return FLATE_HIP_E_INVALID;
+  const bool with_dicts = dicts || dict_off || n_dicts;
+  if (with_dicts && wrap != FLATE_HIP_WRAP_ZLIB) return FLATE_HIP_E_INVALID;  // (neither has a DICTID to choose by)
+  if (!inflate_batch_ptrs_ok(c, in, in_off, n, out, out_off, out_len, status, err_off, flags)) return FLATE_HIP_E_INVALID;
+  if (n_dicts && !dict_off) return FLATE_HIP_E_INVALID;
+  for (uint32_t j = 0; j < n_dicts; ++j)
+    if (dict_off[j + 1] < dict_off[j]) return FLATE_HIP_E_INVALID;
+  if (n_dicts && dict_off[n_dicts] > dict_off[0] && !dicts) return FLATE_HIP_E_INVALID;
+  if (wrap == FLATE_HIP_WRAP_RAW) {  // the raw call: its kernels, its results
+    const int rc = flate_hip_inflate_batch(c, in, in_off, n, out, out_off, out_len, status, err_off, flags);
+    if (dict_used && rc != FLATE_HIP_E_INVALID && rc != FLATE_HIP_E_TOO_LARGE)
+      for (uint32_t i = 0; i < n; ++i) dict_used[i] = FLATE_HIP_NO_DICT;
+    return rc;
+  }
+  c->hip_err.clear();
+  if (n == 0) return FLATE_HIP_OK;
+  const int rc = inflate_batch_ranges(in_off, n, out_off, flags);
+  if (rc) return rc;
+  try {
+    // (host pointers: one copy in, parse, decode, check, one copy out -- no "host_pipeline_groups")
+    const InfFrame FRD{wrap, dicts, dict_off, n_dicts, dict_used};
+    const bool size_only = (flags & FLATE_HIP_SIZE_ONLY) != 0;
+    return inflate_common(c, in, in_off, n, size_only ? nullptr : out, size_only ? nullptr : out_off, out_len, status,
+                          err_off, flags, 0, nullptr, &FRD);
+  } catch (const std::exception &e) {  // (out of host memory in an index vector)
     c->hip_err = e.what();
     return FLATE_HIP_E_INTERNAL;
   }

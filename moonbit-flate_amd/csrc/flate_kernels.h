@@ -135,6 +135,9 @@ struct InfParams {
   const uint8_t *dict_buf;
   const uint64_t *dict_at;
   const uint32_t *dict_len;
+  // members of a container (flate_hip_inflate_batch_framed): stream i is in[in_off[i], in_end[i]) -- its trailer
+  // follows, and the next stream's header.  NULL: stream i ends at in_off[i + 1].  Independent streams only.
+  const uint64_t *in_end;
 };
 
 __global__ void lz77_serial_kernel(LzParams P);
@@ -237,6 +240,38 @@ __global__ void frame_scan_kernel(FrameParams P);
 // headers and trailers, byte by byte (one thread per member); launched AFTER the pack kernel, whose spliced form
 // stores whole dwords around its stream
 __global__ void frame_write_kernel(FrameParams P);
+
+// Reading members (flate_hip_inflate_batch_framed): member i = in[in_off[i], in_off[i + 1]) = header | raw stream |
+// trailer.  frame_parse_kernel (one thread per member) checks the header, finds the raw stream -- pay_off / pay_end:
+// what the decoders read as InfParams::in_off / in_end --, reads the trailer and, for a zlib member with FDICT, looks
+// its DICTID up among dict_id (the first match) and hands the decoders that dictionary's staged tail.  A bad member
+// gets an empty raw stream.  frame_verdict_kernel (one thread per member, behind the decoder and the sums of what it
+// produced) merges header verdict, decoder status, checksum and ISIZE into status / err_off / out_len.
+struct FrameReadParams {
+  const uint8_t *in;
+  const uint64_t *in_off;   // n_streams + 1: the members
+  uint32_t n_streams;
+  uint32_t wrap;            // FLATE_HIP_WRAP_ZLIB / _GZIP
+  const uint32_t *dict_id;  // per dictionary: the Adler-32 of the whole of it (n_dicts == 0: unused)
+  uint32_t n_dicts;
+  const uint64_t *tail_at;  // per dictionary: where its tail lies in InfParams::dict_buf ...
+  const uint32_t *tail_len; // ... and its length (0: an empty dictionary)
+  uint64_t *pay_off;        // n_streams + 1 (entry n_streams: in_off[n_streams])
+  uint64_t *pay_end;        // per member
+  uint32_t *want;           // per member: the trailer's checksum
+  uint32_t *isize;          // per member: gzip's ISIZE
+  uint32_t *bad;            // per member: 1 = bad header
+  uint32_t *dict_used;      // per member: its dictionary or FLATE_HIP_NO_DICT
+  uint64_t *dict_at;        // per member: InfParams::dict_at / dict_len (null when n_dicts == 0)
+  uint32_t *dict_len;
+  // frame_verdict_kernel
+  const uint32_t *sums;     // per member: the checksum of what it produced; null: nothing was stored (FLATE_HIP_SIZE_ONLY)
+  uint64_t *out_len;
+  int32_t *status;
+  int64_t *err_off;
+};
+__global__ void frame_parse_kernel(FrameReadParams P);
+__global__ void frame_verdict_kernel(FrameReadParams P);
 size_t inflate_simt_lds_bytes(int lanes_per_wave);  // dynamic LDS of that launch
 size_t inflate_simt_lens_bytes(uint32_t blocks);    // global scratch of that launch (InfParams::simt_lens)
 
@@ -274,4 +309,12 @@ size_t checksum_ctl_up_bytes(const uint64_t *in_off, uint32_t n);
 size_t checksum_scratch_bytes(const uint64_t *in_off, uint32_t n);
 int checksum_device(flate_hip_ctx *c, const uint8_t *d_in, const uint64_t *in_off, uint32_t n, uint32_t kind,
                     uint32_t *d_sums, int stage);
+// The sums of what a batch decoder PRODUCED (flate_hip_inflate_batch_framed): stream i's bytes are
+// d_out[slot_off[i], slot_off[i] + d_out_len[i]) -- slot_off a host array, out_len known on the device only.  The 64 KiB
+// pieces are planned over the slots and clipped on the device (checksum_clip.h); a stream whose d_status or d_bad
+// entry is non-zero is not summed (its entry of d_sums is the sum of nothing).  No events: the caller brackets.
+// Room: checksum_ctl_up_bytes(slot_off, n) and checksum_scratch_bytes(slot_off, n), as for checksum_device.
+int checksum_device_clipped(flate_hip_ctx *c, const uint8_t *d_out, const uint64_t *slot_off, uint32_t n, uint32_t kind,
+                            const uint64_t *d_out_len, const int32_t *d_status, const uint32_t *d_bad,
+                            uint32_t *d_sums);
 }  // namespace flate

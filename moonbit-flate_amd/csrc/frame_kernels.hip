@@ -15,6 +15,9 @@
 //                       last is right by construction.
 // The checksums are checksum.hip's, left in device memory (checksum_device).  Neither kernel matters for the time
 // of a call: 18 bytes per member against the member itself.
+// READING members (flate_hip_inflate_batch_framed) is the other half of the file: frame_parse_kernel in front of the
+// batch decoders (header rules, the raw stream's range, the trailer's values, the DICTID's dictionary) and
+// frame_verdict_kernel behind them and behind the checksums of what they produced (flate_kernels.h: FrameReadParams).
 #include <hip/hip_runtime.h>
 
 #include "flate_hip.h"
@@ -110,6 +113,107 @@ __global__ __launch_bounds__(256) void frame_write_kernel(FrameParams P) {
       h[1] = 0x01;
     }
     put_be32(t, sum);
+  }
+}
+
+// ---- reading members (flate_hip_inflate_batch_framed) ----
+
+namespace {
+__device__ inline uint32_t get_be32(const uint8_t *p) {
+  return ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | p[3];
+}
+__device__ inline uint32_t get_le32(const uint8_t *p) {
+  return p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
+}
+}  // namespace
+
+// The rules are the host mirrors' (parse_container_header / zlib_member_header in engine.py, container_header in
+// flate_host.hpp).  Every read is below the member's end.
+__global__ __launch_bounds__(256) void frame_parse_kernel(FrameReadParams P) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= P.n_streams) return;
+  const uint64_t a = P.in_off[i], len = P.in_off[i + 1] - a;
+  const uint8_t *m = P.in + a;
+  uint64_t hl = 0, tl = 0;
+  bool ok = false;
+  uint32_t used = FLATE_HIP_NO_DICT;
+  if (P.wrap == FLATE_HIP_WRAP_GZIP) {
+    // RFC 1952 2.3: ID1 ID2, CM = 8, the reserved FLG bits zero; FEXTRA, FNAME, FCOMMENT, FHCRC skipped in that order
+    tl = 8;
+    if (len >= 10 && m[0] == 0x1f && m[1] == 0x8b && m[2] == 8 && (m[3] & 0xe0) == 0) {
+      const uint32_t flg = m[3];
+      uint64_t p = 10;
+      ok = true;
+      if (flg & 4u) {  // FEXTRA: XLEN, then that many bytes
+        if (len < p + 2) ok = false;
+        else p += 2u + (uint64_t)(m[p] | ((uint32_t)m[p + 1] << 8));
+      }
+      for (uint32_t bit = 8u; bit <= 16u && ok; bit <<= 1) {  // FNAME, FCOMMENT: zero-terminated
+        if (!(flg & bit)) continue;
+        while (p < len && m[p]) ++p;
+        if (p >= len) ok = false;
+        else ++p;
+      }
+      if (flg & 2u) p += 2;  // FHCRC
+      if (p > len) ok = false;
+      hl = p;
+    }
+  } else {
+    // RFC 1950 2.2: CM = 8, CINFO <= 7, FCHECK; FDICT: DICTID follows, and names the FIRST dictionary with that id
+    tl = 4;
+    if (len >= 2 && (m[0] & 15u) == 8u && (m[0] >> 4) <= 7u && (((uint32_t)m[0] << 8) | m[1]) % 31u == 0u) {
+      if (m[1] & 0x20u) {
+        if (P.n_dicts && len >= 6) {
+          const uint32_t id = get_be32(m + 2);
+          for (uint32_t j = 0; j < P.n_dicts && !ok; ++j)
+            if (P.dict_id[j] == id) used = j, ok = true;
+          hl = 6;
+        }
+      } else {
+        ok = true;
+        hl = 2;
+      }
+    }
+  }
+  if (ok && len < hl + tl) ok = false;  // too short for its header plus trailer
+  if (!ok) used = FLATE_HIP_NO_DICT;
+  // the raw stream is exactly [header's end, trailer's start): a decoder that needs more has met the stream's end
+  P.pay_off[i] = ok ? a + hl : a;
+  P.pay_end[i] = ok ? a + len - tl : a;
+  if (i + 1 == P.n_streams) P.pay_off[i + 1] = P.in_off[i + 1];
+  P.bad[i] = ok ? 0u : 1u;
+  uint32_t want = 0, isize = 0;
+  if (ok) {
+    const uint8_t *t = m + (len - tl);
+    if (P.wrap == FLATE_HIP_WRAP_GZIP) want = get_le32(t), isize = get_le32(t + 4);
+    else want = get_be32(t);
+  }
+  P.want[i] = want;
+  P.isize[i] = isize;
+  P.dict_used[i] = used;
+  if (P.dict_at) {
+    P.dict_at[i] = used != FLATE_HIP_NO_DICT ? P.tail_at[used] : 0ull;
+    P.dict_len[i] = used != FLATE_HIP_NO_DICT ? P.tail_len[used] : 0u;
+  }
+}
+
+// In this order: a bad header; the decoder's own status (left as it is, with its err_off and the bytes it produced);
+// a checksum -- or, gzip, a length mod 2^32 -- that is not the trailer's.
+__global__ __launch_bounds__(256) void frame_verdict_kernel(FrameReadParams P) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= P.n_streams) return;
+  if (P.bad[i]) {
+    P.status[i] = FLATE_HIP_E_CORRUPT;
+    P.err_off[i] = 0;
+    P.out_len[i] = 0;
+    return;
+  }
+  if (P.status[i] != 0 || P.sums == nullptr) return;
+  const bool mismatch = P.sums[i] != P.want[i] ||
+                        (P.wrap == FLATE_HIP_WRAP_GZIP && (uint32_t)P.out_len[i] != P.isize[i]);
+  if (mismatch) {
+    P.status[i] = FLATE_HIP_E_CORRUPT;
+    P.err_off[i] = (int64_t)(P.in_off[i + 1] - P.in_off[i]);
   }
 }
 

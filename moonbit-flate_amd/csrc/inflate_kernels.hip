@@ -441,7 +441,7 @@ FLATE_D void inflate_wave(const InfParams &P, InfShared &sh) {
   const uint64_t cap64 = size_only ? ~0ull : P.out_off[sid + 1] - P.out_off[sid];
   const uint32_t out_cap = cap64 > 0xfffffff0ull ? 0xfffffff0u : (uint32_t)cap64;
   const uint8_t *in = P.in + P.in_off[sid];
-  const uint32_t in_len = (uint32_t)(P.in_off[sid + 1] - P.in_off[sid]);
+  const uint32_t in_len = (uint32_t)((P.in_end ? P.in_end[sid] : P.in_off[sid + 1]) - P.in_off[sid]);
 
   Bits b;
   b.in_len = in_len;
@@ -1072,7 +1072,7 @@ FLATE_D void inflate_simt(const InfParams &P) {
     out_cap = cap64 > 0xfffffff0ull ? 0xfffffff0u : (uint32_t)cap64;
     if (P.bit_off == nullptr) {
       b.in = P.in + P.in_off[sid];
-      b.in_len = (uint32_t)(P.in_off[sid + 1] - P.in_off[sid]);  // < 2^28: checked by the host
+      b.in_len = (uint32_t)((P.in_end ? P.in_end[sid] : P.in_off[sid + 1]) - P.in_off[sid]);  // < 2^28: checked by the host
     } else {
       // bit positions are kept relative to the dword the piece starts in (32-bit arithmetic; byte
       // alignment relative to the whole stream is preserved, as stored blocks need it)

@@ -187,7 +187,7 @@ FLATE_D void inflate_spec(const InfParams &P, SpecShared<SUB, CAP, RING> &sh) {
   uint64_t in_base = 0;  // byte offset of `in` inside P.in (for the reported error offset)
   if (P.bit_off == nullptr) {
     in = P.in + P.in_off[sid];
-    in_len = (uint32_t)(P.in_off[sid + 1] - P.in_off[sid]);  // < 2^28: checked by the host
+    in_len = (uint32_t)((P.in_end ? P.in_end[sid] : P.in_off[sid + 1]) - P.in_off[sid]);  // < 2^28: checked by the host
   } else {
     const uint64_t g0 = P.bit_off[sid], g1 = P.bit_off[sid + 1];
     in_base = (g0 >> 5) * 4;

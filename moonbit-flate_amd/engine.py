@@ -321,64 +321,59 @@ class FlateEngine:
             return out, int(out_len.value), bit_off
         return bytes(out[:int(out_len.value)])
 
-    def inflate_batch_framed(self, data, in_off, wrap, out_sizes=None, zdicts=None):
-        """The reverse: zlib or gzip members -> (out, out_off, status[n]); status -4 (FLATE_HIP_E_CORRUPT) also
-        for a bad header, a checksum or (gzip) a length that does not match.  zlib members carry no size:
-        out_sizes (or a size-only pass of the decoder) supplies it; gzip's ISIZE is used as the slot size.
-        zdicts (zlib): one preset dictionary or a list of them; a member with FDICT is decoded with the one whose
-        Adler-32 is its DICTID (RFC 1950 2.2) -- none matches, or no zdicts: the member is corrupt."""
-        data = np.ascontiguousarray(data, dtype=np.uint8)
+    def inflate_batch_framed(self, data, in_off, wrap, out_sizes=None, zdicts=None, out=None):
+        """The reverse: zlib or gzip members -> (out, out_off, out_len, status[n]), parsed, decoded and checked against
+        their trailers on the GPU by one call (flate_hip_inflate_batch_framed); status -4 (FLATE_HIP_E_CORRUPT) also
+        for a bad header, a checksum or (gzip) a length that does not match, -7 for a raw stream that ends before
+        its final block does.  data: numpy uint8 (host) or a torch uint8 CUDA tensor (data and result stay on the
+        device).  zlib members carry no size: out_sizes (or a size-only pass of the same call) supplies it; gzip's
+        ISIZE is used as the slot size.  zdicts (zlib): one preset dictionary or a list of them; a member with
+        FDICT is decoded with the first one whose Adler-32 is its DICTID (RFC 1950 2.2) -- none matches, or no
+        zdicts: the member is corrupt.  The details (err_off, the dictionary every member chose) are kept in
+        self.last_framed_read = (err_off, dict_used)."""
         in_off = np.ascontiguousarray(in_off, dtype=np.uint64)
         n = in_off.size - 1
-        start = np.zeros(n + 1, dtype=np.uint64)
-        want = np.zeros(n, dtype=np.uint32)
-        isize = np.zeros(n, dtype=np.uint64)
-        bad = np.zeros(n, dtype=bool)
-        dlist = _dict_list(zdicts) if zdicts is not None and wrap == "zlib" else None
-        dict_of = np.full(n, NO_DICT, dtype=np.uint32) if dlist is not None else None
-        ids = zlib_dict_ids(dlist) if dlist is not None else None
-        for i in range(n):
-            a, b = int(in_off[i]), int(in_off[i + 1])
-            m = data[a:b]
-            if wrap == "zlib":
-                h, t, j = zlib_member_header(m, ids)
-                if dict_of is not None:
-                    dict_of[i] = j
-            else:
-                h, t = parse_container_header(m, wrap)
-            if h < 0 or b - a < h + t:
-                bad[i] = True
-                h = 0
-            else:
-                tr = bytes(m[len(m) - t:])
-                want[i] = int.from_bytes(tr[:4], "big" if wrap == "zlib" else "little")
-                if wrap == "gzip":
-                    isize[i] = int.from_bytes(tr[4:8], "little")
-            start[i] = a + h
-        start[n] = in_off[n]
-        src = np.concatenate([data[:int(in_off[n])], np.zeros(8, np.uint8)])
+        w = _wrap_code(wrap)
+        device = _is_torch(data)
+        if device:
+            import torch
+            assert data.dtype == torch.uint8 and data.is_cuda and data.is_contiguous()
+            in_ptr = data.data_ptr()
+        else:
+            data = np.ascontiguousarray(data, dtype=np.uint8)
+            in_ptr = data.ctypes.data
+        dk = _DictArgs(zdicts, None, n, device) if zdicts is not None and w == WRAP_ZLIB else None
+        out_len = np.zeros(max(n, 1), dtype=np.uint64)
+        status = np.zeros(max(n, 1), dtype=np.int32)
+        err_off = np.full(max(n, 1), -1, dtype=np.int64)
+        dict_used = np.full(max(n, 1), NO_DICT, dtype=np.uint32)
+
+        def call(out_ptr, off_ptr, flags):
+            rc = self._L.flate_hip_inflate_batch_framed(
+                self._ctx, in_ptr, in_off.ctypes.data, n, w, dk.ptr if dk else None, dk.off_ptr if dk else None,
+                dk.n_dicts if dk else 0, out_ptr, off_ptr, out_len.ctypes.data, status.ctypes.data,
+                err_off.ctypes.data, dict_used.ctypes.data, flags | (DEVICE_PTRS if device else 0))
+            if rc not in (0, E_OUT_TOO_SMALL, E_CORRUPT, E_UNEXPECTED_EOF):
+                self._check(rc)
+
         if out_sizes is None:
-            if wrap == "gzip":
-                out_sizes = isize
+            if w == WRAP_GZIP:
+                out_sizes = _gzip_isizes(data, in_off)
             else:
-                out_sizes, _, _ = self.inflate_sizes(src, start, zdicts=dlist, dict_of=dict_of)
-        out, ooff, olen, status, _ = self.inflate_batch(src, start, out_sizes, check=False, zdicts=dlist,
-                                                        dict_of=dict_of)
-        sums = self.checksum_batch(out, ooff, "adler32" if wrap == "zlib" else "crc32") if n else np.zeros(0, np.uint32)
-        status = np.array(status, dtype=np.int32)
-        for i in range(n):
-            if bad[i]:
-                status[i] = E_CORRUPT
-            elif status[i] == 0:
-                # (a slot larger than the member's output: the checksum is over the bytes produced)
-                if int(olen[i]) != int(ooff[i + 1] - ooff[i]):
-                    s = self.checksum_batch(out[int(ooff[i]):int(ooff[i]) + int(olen[i])], [0, int(olen[i])],
-                                            "adler32" if wrap == "zlib" else "crc32")[0]
-                else:
-                    s = sums[i]
-                if int(s) != int(want[i]) or (wrap == "gzip" and (int(olen[i]) & 0xFFFFFFFF) != int(isize[i])):
-                    status[i] = E_CORRUPT
-        return out, ooff, olen, status
+                call(None, None, SIZE_ONLY)
+                out_sizes = out_len[:n].copy()
+        out_off = np.zeros(n + 1, dtype=np.uint64)
+        np.cumsum(np.asarray(out_sizes, dtype=np.uint64), out=out_off[1:])
+        total = max(int(out_off[-1]), 16)
+        if out is not None:
+            _check_out(out, data, int(out_off[-1]), "inflate_batch_framed")
+        elif device:
+            out = torch.empty(total, dtype=torch.uint8, device=data.device)
+        else:
+            out = np.zeros(total, dtype=np.uint8)
+        call(out.data_ptr() if device else out.ctypes.data, out_off.ctypes.data, 0)
+        self.last_framed_read = (err_off[:n], dict_used[:n])
+        return out, out_off, out_len[:n], status[:n]
 
     def inflate_batch(self, data, in_off, out_sizes, out=None, check=True, zdicts=None, dict_of=None):
         """Decompress independent DEFLATE streams (&Reader::new + read to EOF each).
@@ -665,6 +660,24 @@ def _wrap_code(wrap):
 
 ZLIB_HEADER = bytes([0x78, 0x01])  # CM = 8, CINFO = 7 (32 KiB window), FLEVEL = 0 (fastest), FCHECK (RFC 1950 2.2)
 GZIP_HEADER = bytes([0x1f, 0x8b, 8, 0, 0, 0, 0, 0, 4, 255])  # no name / time, XFL = 4 (fastest), OS unknown (RFC 1952 2.3)
+
+
+def _gzip_isizes(data, in_off):
+    """ISIZE (RFC 1952 2.3.1: the last four bytes, little endian) of every gzip member data[in_off[i]:in_off[i+1]],
+    gathered in one indexing step (host or device data); a member of fewer than 18 bytes cannot be one: 0."""
+    lens = (in_off[1:] - in_off[:-1]).astype(np.int64)
+    ok = lens >= 18
+    at = np.where(ok, in_off[1:].astype(np.int64) - 4, 0)
+    idx = at[:, None] + np.arange(4, dtype=np.int64)[None, :]
+    if not ok.any():
+        return np.zeros(lens.size, dtype=np.uint64)
+    if _is_torch(data):
+        import torch
+        b = data[torch.from_numpy(idx.reshape(-1)).to(data.device)].cpu().numpy().reshape(-1, 4)
+    else:
+        b = data[idx.reshape(-1)].reshape(-1, 4)
+    v = b.astype(np.uint64) @ np.array([1, 1 << 8, 1 << 16, 1 << 24], dtype=np.uint64)
+    return np.where(ok, v, 0).astype(np.uint64)
 
 
 def _dict_list(zdicts):

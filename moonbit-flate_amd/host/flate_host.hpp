@@ -565,47 +565,58 @@ inline std::pair<int, int> container_header(const std::vector<uint8_t> &m, Wrap 
   return p <= m.size() ? std::pair<int, int>{(int)p, 8} : std::pair<int, int>{-1, 0};
 }
 
-// decompress_batch for zlib / gzip members: the raw streams decoded on the GPU, the trailers checked against the
-// checksums of what came out (flate_hip_checksum_batch); a bad header, checksum or (gzip) length is
-// corrupt_input_error at the member's end.  sizes[i] = capacity for member i's output (gzip: 0 = its ISIZE).
+// decompress_batch for zlib / gzip members: ONE call of flate_hip_inflate_batch_framed -- the headers parsed, the raw
+// streams decoded and the trailers checked against the checksums of what came out, all on the GPU; a bad header
+// (corrupt_input_error(0)), a checksum or (gzip) a length that does not match (corrupt_input_error at the member's
+// end).  sizes[i] = capacity for member i's output (gzip: 0 = its ISIZE).  dicts (zlib): preset dictionaries; a
+// member with FDICT is decoded with the first one whose Adler-32 is its DICTID (RFC 1950 2.2), and is corrupt if
+// none is; dict_used (may be null): the dictionary every member chose, or FLATE_HIP_NO_DICT.
+inline Err decompress_batch(Engine &e, const std::vector<std::vector<uint8_t>> &members, std::vector<uint64_t> sizes,
+                            const std::vector<std::vector<uint8_t>> &dicts, std::vector<Inflated> &out, Wrap wrap,
+                            std::vector<uint32_t> *dict_used = nullptr) {
+  if (wrap == Wrap::Raw && dicts.empty()) return decompress_batch(e, members, sizes, out);
+  if (!e.ok()) return make_error(e, e.status());
+  const uint32_t n = (uint32_t)members.size();
+  sizes.resize(n, 0);
+  std::vector<uint64_t> in_off(n + 1, 0), out_off(n + 1, 0), out_len(n + 1, 0);
+  std::vector<int32_t> status(n + 1, 0);
+  std::vector<int64_t> err_off(n + 1, -1);
+  std::vector<uint32_t> used(n + 1, FLATE_HIP_NO_DICT);
+  for (uint32_t i = 0; i < n; ++i) {
+    const std::vector<uint8_t> &m = members[i];
+    if (wrap == Wrap::Gzip && sizes[i] == 0 && m.size() >= 18) {  // ISIZE: the member's last four bytes
+      const uint8_t *t = m.data() + m.size() - 4;
+      sizes[i] = t[0] | ((uint32_t)t[1] << 8) | ((uint32_t)t[2] << 16) | ((uint32_t)t[3] << 24);
+    }
+    in_off[i + 1] = in_off[i] + m.size();
+    out_off[i + 1] = out_off[i] + sizes[i];
+  }
+  std::vector<uint8_t> in(in_off[n] + 8), buf(out_off[n] + 8);
+  for (uint32_t i = 0; i < n; ++i) std::copy(members[i].begin(), members[i].end(), in.begin() + in_off[i]);
+  const DictTable D(dicts);
+  const bool with = !dicts.empty();
+  const int rc = flate_hip_inflate_batch_framed(e.ctx(), in.data(), in_off.data(), n, wrap_code(wrap),
+                                                with ? D.bytes.data() : nullptr, with ? D.off.data() : nullptr,
+                                                (uint32_t)dicts.size(), buf.data(), out_off.data(), out_len.data(),
+                                                status.data(), err_off.data(), used.data(), 0);
+  if (rc != 0 && rc != FLATE_HIP_E_CORRUPT && rc != FLATE_HIP_E_UNEXPECTED_EOF && rc != FLATE_HIP_E_OUT_TOO_SMALL)
+    return make_error(e, rc);
+  out.resize(n);
+  for (uint32_t i = 0; i < n; ++i) {
+    out[i].bytes.assign(buf.begin() + out_off[i], buf.begin() + out_off[i] + out_len[i]);
+    out[i].err = std::nullopt;
+    out[i].status = status[i];
+    if (status[i] == FLATE_HIP_E_CORRUPT) out[i].err = corrupt_input_error(err_off[i]);
+    else if (status[i] == FLATE_HIP_E_UNEXPECTED_EOF) out[i].err = err_unexpected_eof();
+    else if (status[i] != 0) out[i].err = make_error(e, status[i]);
+  }
+  if (dict_used) dict_used->assign(used.begin(), used.begin() + n);
+  return std::nullopt;
+}
+
 inline Err decompress_batch(Engine &e, const std::vector<std::vector<uint8_t>> &members, std::vector<uint64_t> sizes,
                             std::vector<Inflated> &out, Wrap wrap) {
-  if (wrap == Wrap::Raw) return decompress_batch(e, members, sizes, out);
-  const size_t n = members.size();
-  std::vector<std::vector<uint8_t>> raw(n);
-  std::vector<uint32_t> want(n, 0), isize(n, 0);
-  std::vector<bool> bad(n, false);
-  sizes.resize(n, 0);
-  for (size_t i = 0; i < n; ++i) {
-    const auto ht = container_header(members[i], wrap);
-    if (ht.first < 0 || members[i].size() < (size_t)(ht.first + ht.second)) {
-      bad[i] = true;
-      continue;
-    }
-    raw[i].assign(members[i].begin() + ht.first, members[i].end() - ht.second);
-    const uint8_t *t = members[i].data() + members[i].size() - ht.second;
-    if (wrap == Wrap::Zlib) {
-      want[i] = ((uint32_t)t[0] << 24) | ((uint32_t)t[1] << 16) | ((uint32_t)t[2] << 8) | t[3];
-    } else {
-      want[i] = t[0] | ((uint32_t)t[1] << 8) | ((uint32_t)t[2] << 16) | ((uint32_t)t[3] << 24);
-      isize[i] = t[4] | ((uint32_t)t[5] << 8) | ((uint32_t)t[6] << 16) | ((uint32_t)t[7] << 24);
-      if (sizes[i] == 0) sizes[i] = isize[i];
-    }
-  }
-  if (Err er = decompress_batch(e, raw, sizes, out)) return er;
-  std::vector<std::vector<uint8_t>> plain(n);
-  for (size_t i = 0; i < n; ++i) plain[i] = out[i].bytes;
-  std::vector<uint32_t> sums;
-  if (Err er = checksum_batch(e, plain, wrap == Wrap::Zlib ? FLATE_HIP_CHECKSUM_ADLER32 : FLATE_HIP_CHECKSUM_CRC32, sums)) return er;
-  for (size_t i = 0; i < n; ++i) {
-    const bool mismatch = !bad[i] && out[i].status == 0 &&
-                          (sums[i] != want[i] || (wrap == Wrap::Gzip && (uint32_t)out[i].bytes.size() != isize[i]));
-    if (bad[i] || mismatch) {
-      out[i].status = FLATE_HIP_E_CORRUPT;
-      out[i].err = corrupt_input_error(bad[i] ? 0 : (int64_t)members[i].size());
-    }
-  }
-  return std::nullopt;
+  return decompress_batch(e, members, std::move(sizes), {}, out, wrap);
 }
 
 // &Reader (inflate.mbt:227-232): where a Decompressor pulls its input from
