@@ -247,7 +247,12 @@ int flate_hip_lz77_matches(flate_hip_ctx *ctx, const uint8_t *in, const uint64_t
  * goes to out[out_off[i] .. out_off[i+1]) (capacity; bytes of the slot beyond out_len[i] are
  * unspecified afterwards); out_len[i] = bytes produced;
  * status[i] = 0 or a negative code; err_off[i] = input offset reported by
- * corrupt_input_error (or -1). Returns the first non-zero status. */
+ * corrupt_input_error (or -1). Returns the first non-zero status.
+ * With FLATE_HIP_DEVICE_PTRS a stream writes only inside its own slot -- nothing outside
+ * out[out_off[0], out_off[n_streams]) is written, and nothing of another stream's slot -- and a stream that produces
+ * no bytes (out_len[i] == 0) writes nothing at all.  With host pointers the slots are copied back as one range:
+ * every byte of out[0, out_off[n_streams]) may be rewritten, the slot of a stream that produced nothing included, and
+ * nothing behind it.  (The same holds for flate_hip_inflate_batch_dict, _spliced and _batch_framed.) */
 int flate_hip_inflate_batch(flate_hip_ctx *ctx, const uint8_t *in, const uint64_t *in_off,
                             uint32_t n_streams, uint8_t *out, const uint64_t *out_off,
                             uint64_t *out_len, int32_t *status, int64_t *err_off,
