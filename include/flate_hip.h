@@ -397,14 +397,14 @@ int flate_hip_deflate_fast_spliced(flate_hip_ctx *ctx, const uint8_t *in,
  * flate_hip_deflate_fast_spliced writes | trailer over the CONCATENATED input in[in_off[0], in_off[n_streams])
  * (ISIZE: that length mod 2^32) -- the one .gz / zlib blob that gzip -d or zlib's uncompress turn back into the
  * whole buffer.  bit_off (may be NULL) is counted from the first byte of the raw stream, out + header length (2
- * or 10): its values are the unframed call's, so flate_hip_inflate_spliced(out + header length, ...) reads it.
+ * or 10): its values are the unframed call's, and flate_hip_inflate_spliced_framed takes the member and this index as they are.
  * n_streams == 0: header | 01 00 00 ff ff | the trailer of nothing.  out_cap >= header + raw stream + trailer is
  * enough (the unframed call's 3 spare bytes lie inside the trailer).  No dictionaries; FLATE_HIP_WRAP_RAW is the
  * unframed call; an unknown wrap: FLATE_HIP_E_INVALID.
  *
  * flate_hip_frame_overhead (host only): the bytes a member adds around its raw stream -- RAW 0; ZLIB 6, with
  * with_dict != 0: 10; GZIP 18; an unknown wrap 0.
- * Reading members: flate_hip_inflate_batch_framed below. */
+ * Reading members: flate_hip_inflate_batch_framed and flate_hip_inflate_spliced_framed below. */
 #define FLATE_HIP_WRAP_RAW 0u
 #define FLATE_HIP_WRAP_ZLIB 1u /* RFC 1950 */
 #define FLATE_HIP_WRAP_GZIP 2u /* RFC 1952 */
@@ -467,6 +467,52 @@ int flate_hip_inflate_batch_framed(flate_hip_ctx *ctx, const uint8_t *in, const 
                                    uint8_t *out, const uint64_t *out_off, uint64_t *out_len,
                                    int32_t *status, int64_t *err_off, uint32_t *dict_used,
                                    uint32_t flags);
+
+/* READING ONE member around a spliced stream: flate_hip_inflate_spliced -- its index, output slots (capacities: a
+ * piece may produce less than its slot holds), out_len, status, err_off, FLATE_HIP_DEVICE_PTRS and slot-write
+ * guarantees -- for in[0, in_len) = header | the raw spliced stream | trailer, as flate_hip_deflate_fast_spliced_framed
+ * writes it or any other zlib / gzip writer around the same raw stream.  bit_off (HOST array, n_streams + 1 entries) is
+ * counted from the first byte of the RAW stream, exactly as flate_hip_deflate_fast_spliced_framed returns it: the
+ * header's length is found on the device, and no caller parses it.  Header parsing, decoding and the check of the
+ * trailer against what was decoded all happen on the device, in one call, on one HIP stream: no host pass over member
+ * bytes, no host synchronisation between decode and verification; host pointers mean one copy in and one copy out.
+ *   Header: the rules of flate_hip_inflate_batch_framed (the same parse kernel over one range).  gzip: FEXTRA, FNAME,
+ *     FCOMMENT and FHCRC are skipped.  zlib: FDICT is a bad header -- the spliced writer has no dictionaries and this
+ *     call takes none.  A member too short for its header plus trailer has a bad header.
+ *   The raw stream is exactly [header end, in_len - trailer length): a piece that needs bytes behind that range is
+ *     FLATE_HIP_E_UNEXPECTED_EOF, and no decoder reads the trailer.  An index entry that lies behind that range once
+ *     the header's length is added (a header longer than the shortest) is clamped to its end: the piece sees no input
+ *     and reports FLATE_HIP_E_UNEXPECTED_EOF.
+ *   The verdict, in this order (member_status and member_err_off may each be NULL):
+ *     1. a bad header: every piece gets status FLATE_HIP_E_CORRUPT, err_off 0, out_len 0 and nothing is written to
+ *        out; *member_status = FLATE_HIP_E_CORRUPT, *member_err_off = 0; returns FLATE_HIP_E_CORRUPT;
+ *     2. a piece's own non-zero status: out_len, status and err_off are what flate_hip_inflate_spliced reports for the
+ *        raw stream alone (err_off counted from the raw stream's first byte), the bytes are delivered;
+ *        *member_status = the first non-zero piece status, *member_err_off = -1, no checksum is judged; returns that
+ *        status;
+ *     3. every piece 0, but the checksum of the logical concatenation out[out_off[i], out_off[i] + out_len[i]), i = 0
+ *        .. n_streams - 1 -- zlib: Adler-32, big endian; gzip: CRC-32, little endian -- is not the trailer's, or, gzip,
+ *        the sum of out_len mod 2^32 is not ISIZE: the statuses stay 0 and the bytes are delivered;
+ *        *member_status = FLATE_HIP_E_CORRUPT, *member_err_off = in_len; returns FLATE_HIP_E_CORRUPT;
+ *     otherwise *member_status = 0, *member_err_off = -1, FLATE_HIP_OK.
+ *   FLATE_HIP_E_INVALID, before any HIP call: flate_hip_inflate_spliced's checks; an unknown wrap; bit_off not
+ *     monotone; bit_off[n_streams] > 8 * (in_len - trailer length - shortest header: 6 bytes zlib, 18 gzip), or in_len
+ *     below those; FLATE_HIP_SIZE_ONLY (the spliced calls have no size-only pass).  FLATE_HIP_E_TOO_LARGE as in the raw
+ *     call (a piece of 2^30 bits or more).  n_streams == 0: FLATE_HIP_OK, nothing is read.
+ *   FLATE_HIP_WRAP_RAW IS flate_hip_inflate_spliced: the same kernels, the same results; the member's two words are
+ *     derived on the host as in case 2 and the last row.
+ * How: the parse kernel measures the header; a rebase kernel (one thread per index entry) adds it to the uploaded
+ * index, clamps, and on a bad header collapses every piece to an empty range; the spliced decoders then run unchanged
+ * on the member up to its trailer (whole bytes are added: stored blocks keep their alignment); the checksum kernels
+ * leave one finished sum per piece, a join kernel (one workgroup, a running count of the bytes behind every piece)
+ * turns them into the concatenation's sum and length, and a verdict kernel applies the cases.  With profiling on,
+ * FLATE_HIP_STAGE_INFLATE is the decoder alone and FLATE_HIP_STAGE_CHECKSUM the output sums plus the join plus the
+ * verdict; the parse and rebase kernels are counted in NO stage. */
+int flate_hip_inflate_spliced_framed(flate_hip_ctx *ctx, const uint8_t *in, uint64_t in_len, uint32_t wrap,
+                                     const uint64_t *bit_off, uint32_t n_streams,
+                                     uint8_t *out, const uint64_t *out_off, uint64_t *out_len,
+                                     int32_t *status, int64_t *err_off,
+                                     int32_t *member_status, int64_t *member_err_off, uint32_t flags);
 
 /* -- exchange step (multi-GPU) ---------------------------------------------------
  * SURVEY 8(e) / section 5; no counterpart in the reference (single-threaded, no communication

@@ -83,3 +83,18 @@ int flate_hip_mbt_inflate_batch_framed(flate_hip_ctx *c, const uint8_t *in, cons
   return flate_hip_inflate_batch_framed(c, in, in_off, n, wrap, 0, 0, 0, out, out_off, out_len, status, err_off, 0,
                                         flags);
 }
+
+/* -- ONE member around a spliced stream, read in one call: the member's two words packed into one array (MoonBit
+ * passes no pointers to scalars): res[0] = member status, res[1] = member_err_off -- */
+int flate_hip_mbt_inflate_spliced_framed(flate_hip_ctx *c, const uint8_t *in, uint64_t in_len, uint32_t wrap,
+                                         const uint64_t *bit_off, uint32_t n, uint8_t *out, const uint64_t *out_off,
+                                         uint64_t *out_len, int32_t *status, int64_t *err_off, int64_t *res,
+                                         uint32_t flags) {
+  int32_t ms = 0;
+  int64_t me = -1;
+  const int rc = flate_hip_inflate_spliced_framed(c, in, in_len, wrap, bit_off, n, out, out_off, out_len, status,
+                                                  err_off, &ms, &me, flags);
+  res[0] = ms;
+  res[1] = me;
+  return rc;
+}

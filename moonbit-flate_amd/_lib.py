@@ -23,7 +23,7 @@ EXPORTS = [
     "flate_hip_inflate_stream_reset", "flate_hip_checksum_batch", "flate_hip_inflate_batch_dict",
     "flate_hip_deflate_fast_batch_dict",
     "flate_hip_frame_overhead", "flate_hip_deflate_fast_batch_framed", "flate_hip_deflate_fast_spliced_framed",
-    "flate_hip_inflate_batch_framed",
+    "flate_hip_inflate_batch_framed", "flate_hip_inflate_spliced_framed",
 ]
 
 _lib = None
@@ -88,6 +88,10 @@ def load():
         L.flate_hip_inflate_batch_framed.argtypes = [vp, vp, vp, C.c_uint32, C.c_uint32, vp, vp, C.c_uint32,
                                                      vp, vp, vp, vp, vp, vp, C.c_uint32]
         L.flate_hip_inflate_batch_framed.restype = C.c_int
+    if os.environ.get("FLATE_HIP_LIB") is None or hasattr(L, "flate_hip_inflate_spliced_framed"):
+        L.flate_hip_inflate_spliced_framed.argtypes = [vp, vp, C.c_uint64, C.c_uint32, vp, C.c_uint32, vp, vp, vp, vp,
+                                                       vp, vp, vp, C.c_uint32]
+        L.flate_hip_inflate_spliced_framed.restype = C.c_int
     L.flate_hip_inflate_spliced.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint32, vp, vp, vp, vp, vp, C.c_uint32]
     L.flate_hip_inflate_spliced.restype = C.c_int
     L.flate_hip_set_profiling.argtypes = [vp, C.c_int]

@@ -15,7 +15,9 @@
 //       Adler-32 sum of the bytes and sum of (index * byte) per lane (v_dot4), added over the lanes.
 //       The last, shorter piece of a stream: lane L takes bytes [1024 L, 1024 L + 1024) of it instead;
 //   checksum_fold_kernel   one wavefront per stream folds its pieces: 64 runs of consecutive pieces, one per
-//       lane, then the lanes.
+//       lane, then the lanes;
+//   checksum_join_kernel   one workgroup joins the finished sums of the pieces of a spliced stream into the sum of
+//       their concatenation (flate_hip_inflate_spliced_framed).
 // One read of the input; what bounds the kernels is stated in DESIGN 4.7.
 #include <hip/hip_runtime.h>
 
@@ -285,6 +287,85 @@ __global__ __launch_bounds__(256) void checksum_clip_kernel(ClipParams P) {
   if (lane == 0) P.n_len[s] = n;
 }
 
+// The sum of a CONCATENATION (flate_hip_inflate_spliced_framed): the n pieces of a spliced stream each left a finished
+// sum (checksum_fold_kernel) of the L_i = min(out_len[i], slot) bytes they produced; the member's checksum is that of
+// the L_i-byte runs one after another.  Piece i's term needs the bytes BEHIND it, n_bytes - (L_0 + .. + L_i): one
+// workgroup first adds up n_bytes, then walks the pieces in chunks of 1024 with a running prefix, as
+// frame_scan_kernel walks sizes; every thread keeps the XOR (CRC-32) or the two sums mod 65521 (Adler-32) of its
+// terms, folded over the workgroup at the end.  The arithmetic is checksum_clip.h's.  2^20 pieces: 1024 chunks of at
+// most ~40 multmodp per thread -- nothing against the decode in front of it.
+struct JoinParams {
+  const uint32_t *sums;      // per piece: its finished Adler-32 / CRC-32
+  const uint64_t *slot_off;  // n_pieces + 1
+  const uint64_t *produced;  // per piece: out_len of the decoder
+  uint32_t n_pieces;
+  uint32_t want_crc;  // else Adler-32
+  uint32_t *sum;      // the whole's
+  uint64_t *total;    // its bytes (gzip: ISIZE is this mod 2^32)
+  X2n x2n;
+};
+__global__ __launch_bounds__(1024) void checksum_join_kernel(JoinParams P) {
+  __shared__ uint64_t wtot[16], wd1[16], wd2[16];
+  __shared__ uint32_t wcrc[16];
+  __shared__ uint64_t carry_s;
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const uint32_t hi = P.n_pieces;
+  auto len_of = [&](uint32_t i) { return clip_to_slot(P.produced[i], P.slot_off[i + 1] - P.slot_off[i]); };
+  // the whole's bytes
+  uint64_t mine = 0;
+  for (uint32_t i = (uint32_t)tid; i < hi; i += 1024u) mine += len_of(i);
+  for (int d = 32; d >= 1; d >>= 1) mine += (uint64_t)__shfl_xor((long long)mine, d);
+  if (lane == 0) wtot[wid] = mine;
+  if (tid == 0) carry_s = 0ull;
+  __syncthreads();
+  uint64_t n_bytes = 0;
+  for (int w = 0; w < 16; ++w) n_bytes += wtot[w];
+  __syncthreads();
+  // the terms
+  uint32_t c = 0;
+  uint64_t d1 = 0, d2 = 0;
+  for (uint32_t base = 0; base < hi; base += 1024u) {
+    const uint32_t i = base + (uint32_t)tid;
+    const uint64_t v = i < hi ? len_of(i) : 0ull;
+    uint64_t x = v;  // inclusive prefix inside my wavefront
+    for (int d = 1; d < 64; d <<= 1) {
+      const uint64_t o = (uint64_t)__shfl_up((long long)x, d);
+      if (lane >= d) x += o;
+    }
+    if (lane == 63) wtot[wid] = x;
+    __syncthreads();
+    uint64_t woff = 0;
+    for (int w = 0; w < wid; ++w) woff += wtot[w];
+    const uint64_t upto = carry_s + woff + x;  // L_0 + .. + L_i: never more than n_bytes
+    if (i < hi) {
+      const uint64_t behind = n_bytes - upto;
+      if (P.want_crc) {
+        c ^= crc_concat_term(P.x2n, P.sums[i], v, behind);
+      } else {
+        const AdlerTerm t = adler_concat_term(P.sums[i], v, behind);
+        d1 = (d1 + t.d1) % kAdlerMod;
+        d2 = (d2 + t.d2) % kAdlerMod;
+      }
+    }
+    __syncthreads();
+    if (tid == 1023) carry_s = upto;
+    __syncthreads();
+  }
+  for (int d = 32; d >= 1; d >>= 1) {
+    c ^= (uint32_t)__shfl_xor((int)c, d);
+    d1 += (uint64_t)__shfl_xor((long long)d1, d);
+    d2 += (uint64_t)__shfl_xor((long long)d2, d);
+  }
+  if (lane == 0) wcrc[wid] = c, wd1[wid] = d1, wd2[wid] = d2;
+  __syncthreads();
+  if (tid == 0) {
+    c = 0, d1 = 0, d2 = 0;
+    for (int w = 0; w < 16; ++w) c ^= wcrc[w], d1 += wd1[w], d2 += wd2[w];
+    *P.sum = P.want_crc ? c : adler_concat_finish(d1, d2, n_bytes);
+    *P.total = n_bytes;
+  }
+}
+
 }  // namespace
 
 }  // namespace flate
@@ -339,6 +420,28 @@ int flate::checksum_device_clipped(flate_hip_ctx *c, const uint8_t *d_out, const
                                    const uint32_t *d_bad, uint32_t *d_sums) {
   const Produced clip{d_out_len, d_status, d_bad};
   return checksum_run(c, d_out, slot_off, n, kind, d_sums, -1, &clip);
+}
+
+// The pieces' sums joined into the sum of their concatenation (flate_kernels.h); queued behind checksum_device_clipped.
+int flate::checksum_join_device(flate_hip_ctx *c, const uint32_t *d_sums, const uint64_t *d_slot_off,
+                                const uint64_t *d_out_len, uint32_t n, uint32_t kind, uint32_t *d_sum,
+                                uint64_t *d_total) {
+  JoinParams J{};
+  J.sums = d_sums;
+  J.slot_off = d_slot_off;
+  J.produced = d_out_len;
+  J.n_pieces = n;
+  J.want_crc = kind == FLATE_HIP_CHECKSUM_CRC32;
+  J.sum = d_sum;
+  J.total = d_total;
+  J.x2n = make_x2n();
+  hipLaunchKernelGGL(checksum_join_kernel, dim3(1), dim3(1024), 0, ctx_stream(c), J);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) {
+    ctx_set_error(c, std::string("checksum join kernel: ") + hipGetErrorString(e));
+    return FLATE_HIP_E_HIP;
+  }
+  return FLATE_HIP_OK;
 }
 
 namespace {

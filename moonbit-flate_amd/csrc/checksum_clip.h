@@ -105,4 +105,39 @@ FLATE_CLIP_HD inline uint32_t adler_finish(uint64_t sa, uint64_t sib, uint64_t n
   return (s2 << 16) | s1;
 }
 
+// ---- the sums of a CONCATENATION from the finished sums of its pieces (flate_hip_inflate_spliced_framed: the
+// member's checksum is that of what the pieces of the spliced stream produced, one after another; checksum_join_kernel
+// and tests/test_checksum_join.py).  Piece i has `len` bytes and `behind` bytes of the whole follow it.
+
+// CRC-32: crc(whole) = XOR over the pieces of crc_i * x^(8 behind_i); an empty piece (crc 0) adds nothing, and the
+// CRC of no piece at all is 0
+FLATE_CLIP_HD inline uint32_t crc_concat_term(const X2n &T, uint32_t crc, uint64_t len, uint64_t behind) {
+  return len ? crc_place(T, crc, behind) : 0u;
+}
+
+// Adler-32: with (a1, a2) the halves of piece i's sum, a1 - 1 = sum of its bytes and a2 - len = sum of
+// (len - k) * byte k.  In the whole, byte k of piece i weighs (behind + len - k), hence
+//   s1 = 1 + sum of d1,  d1 = a1 - 1;      s2 = n + sum of d2,  d2 = (a2 - len) + behind * d1      (mod 65521).
+// An empty piece (sum 1) gives d1 = d2 = 0; no piece at all: 1.
+struct AdlerTerm {
+  uint32_t d1, d2;  // both below 65521
+};
+FLATE_CLIP_HD inline AdlerTerm adler_concat_term(uint32_t adler, uint64_t len, uint64_t behind) {
+  const uint64_t M = kSumAdlerMod;
+  const uint64_t a1 = (adler & 0xffffu) % M, a2 = (adler >> 16) % M;
+  AdlerTerm t;
+  t.d1 = (uint32_t)((a1 + M - 1u) % M);
+  t.d2 = (uint32_t)((a2 + M - len % M + (behind % M) * t.d1) % M);
+  return t;
+}
+// d1, d2: the terms' sums (any multiple of 65521 may have been taken out on the way); n: bytes of the whole
+FLATE_CLIP_HD inline uint32_t adler_concat_finish(uint64_t d1, uint64_t d2, uint64_t n) {
+  const uint32_t s1 = (uint32_t)((1u + d1 % kSumAdlerMod) % kSumAdlerMod);
+  const uint32_t s2 = (uint32_t)((n % kSumAdlerMod + d2 % kSumAdlerMod) % kSumAdlerMod);
+  return (s2 << 16) | s1;
+}
+
+// what piece i counts: what its decoder produced, never more than its slot holds (checksum_clip_kernel's rule)
+FLATE_CLIP_HD inline uint64_t clip_to_slot(uint64_t produced, uint64_t slot) { return produced < slot ? produced : slot; }
+
 }  // namespace flate

@@ -71,6 +71,9 @@ struct flate_hip_ctx {
   // d_frame_dicts): the raw streams' ends, the trailers' sums and ISIZEs, the header verdicts, the chosen dictionaries,
   // and per dictionary where its staged tail lies and how long it is
   DevBuf d_rd_end, d_rd_want, d_rd_isize, d_rd_bad, d_rd_dict, d_rd_tail_at, d_rd_tail_len;
+  // flate_hip_inflate_spliced_framed (it shares d_frame_off: the index counted from the member's first byte,
+  // d_frame_sums: the pieces' sums, d_rd_bad: the header verdict per piece): the one member's words (FrameOne)
+  DevBuf d_rd_one;
   hipStream_t guest_stream = nullptr;
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
   int guest_blocks = 0;      // 0 = guest kernel off
@@ -1814,6 +1817,14 @@ struct InfFrame {
   uint32_t *dict_used;       // host, per member (may be null): the dictionary its DICTID chose
 };
 
+// The container of flate_hip_inflate_spliced_framed: ONE member around the spliced stream (frame_kernels.hip:
+// frame_rebase_kernel / frame_verdict_spliced_kernel).  The member's verdict comes back here.
+struct InfMember {
+  uint32_t wrap;  // FLATE_HIP_WRAP_ZLIB / _GZIP
+  int32_t status = 0;
+  int64_t err_off = -1;
+};
+
 struct DictSlots;
 static DictSlots dict_slots(const uint64_t *dict_off, uint32_t n_dicts, const uint32_t *dict_of, uint32_t n,
                             uint32_t min_len);
@@ -1821,15 +1832,19 @@ static int dict_upload(flate_hip_ctx *c, const DictSlots &S, const uint8_t *dict
                        uint32_t flags);
 static int inflate_frame_prepare(flate_hip_ctx *c, const InfFrame &FRD, const uint8_t *d_in, uint32_t n, uint32_t flags,
                                  InfParams &I, FrameReadParams &R, bool &dict);
+static int inflate_member_prepare(flate_hip_ctx *c, const InfMember &SM, const uint8_t *d_in, uint64_t in_len, uint32_t n,
+                                  InfParams &I, FrameSplicedParams &S);
 
 // Both decode entry points.  spliced_len != 0: `in` is ONE stream of that many bytes and in_off
 // holds the bit positions of its n pieces (flate_hip_inflate_spliced).  D != NULL: the streams'
 // dictionaries (a launch in which a stream has one runs the decoder's dictionary build).  FRD != NULL: the streams are
 // members of a container (flate_hip_inflate_batch_framed): parsed in front of the decoder, checked behind it.
+// SM != NULL (with spliced_len): `in` is ONE member of spliced_len bytes around the spliced stream and in_off is counted
+// from the raw stream's first byte (flate_hip_inflate_spliced_framed); the return value is the member's status.
 static int inflate_common(flate_hip_ctx *c, const uint8_t *in, const uint64_t *in_off, uint32_t n,
                           uint8_t *out, const uint64_t *out_off, uint64_t *out_len, int32_t *status,
                           int64_t *err_off, uint32_t flags, uint64_t spliced_len, const InfDict *D = nullptr,
-                          const InfFrame *FRD = nullptr) {
+                          const InfFrame *FRD = nullptr, InfMember *SM = nullptr) {
   const bool spliced = spliced_len != 0;
   const bool size_only = (flags & FLATE_HIP_SIZE_ONLY) != 0 && !spliced;
   const uint64_t in_bytes = spliced ? spliced_len : in_off[n];
@@ -1865,7 +1880,9 @@ static int inflate_common(flate_hip_ctx *c, const uint8_t *in, const uint64_t *i
     f_up = checksum_ctl_up_bytes(f_doff.data(), FRD->n_dicts) + (size_t)FRD->n_dicts * 12 + 1024;
     if (!size_only) f_up += checksum_ctl_up_bytes(out_off, n);
   }
-  if ((rc = ctl_begin(c, ((size_t)n + 1) * 16 + f_up, (size_t)n * (FRD ? 24 : 20) + 64 + (FRD ? 256 : 0)))) return rc;
+  if (SM) f_up = checksum_ctl_up_bytes(out_off, n) + sizeof(FrameOne) + 1024;
+  if ((rc = ctl_begin(c, ((size_t)n + 1) * 16 + f_up, (size_t)n * (FRD ? 24 : 20) + 64 + (FRD ? 256 : 0) + (SM ? 1024 : 0))))
+    return rc;
   if ((rc = ctl_up(c, c->d_in_off.p, in_off, ((size_t)n + 1) * 8))) return rc;
   if ((rc = ctl_up(c, c->d_slot_off.p, out_off, ((size_t)n + 1) * 8))) return rc;
   InfParams I{};
@@ -1910,6 +1927,12 @@ static int inflate_common(flate_hip_ctx *c, const uint8_t *in, const uint64_t *i
     }
     if ((rc = inflate_frame_prepare(c, *FRD, d_in, n, flags, I, R, dict))) return rc;
     hipLaunchKernelGGL(frame_parse_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, R);
+  }
+  FrameSplicedParams S{};
+  if (SM) {
+    // the one header is parsed where the member lies, and the index follows it there: the decoders below read the
+    // member from its first byte up to its trailer
+    if ((rc = inflate_member_prepare(c, *SM, d_in, in_bytes, n, I, S))) return rc;
   }
   {
     StageTimer t(c, FLATE_HIP_STAGE_INFLATE);
@@ -1985,6 +2008,22 @@ static int inflate_common(flate_hip_ctx *c, const uint8_t *in, const uint64_t *i
     HIP_TRY(c, hipGetLastError());
     if (FRD->dict_used && (rc = ctl_down(c, FRD->dict_used, c->d_rd_dict.p, (size_t)n * 4))) return rc;
   }
+  if (SM) {
+    // the sums of what every piece produced, their join into the member's, then the verdict
+    StageTimer t(c, FLATE_HIP_STAGE_CHECKSUM);
+    const uint32_t kind = SM->wrap == FLATE_HIP_WRAP_GZIP ? FLATE_HIP_CHECKSUM_CRC32 : FLATE_HIP_CHECKSUM_ADLER32;
+    if ((rc = checksum_device_clipped(c, d_out, out_off, n, kind, (const uint64_t *)c->d_out_len.p,
+                                      (const int32_t *)c->d_istatus.p, (const uint32_t *)c->d_rd_bad.p,
+                                      (uint32_t *)c->d_frame_sums.p)))
+      return rc;
+    if ((rc = checksum_join_device(c, (const uint32_t *)c->d_frame_sums.p, (const uint64_t *)c->d_slot_off.p,
+                                   (const uint64_t *)c->d_out_len.p, n, kind, &S.one->sum, &S.one->total)))
+      return rc;
+    hipLaunchKernelGGL(frame_verdict_spliced_kernel, dim3(1), dim3(1024), 0, c->stream, S);
+    HIP_TRY(c, hipGetLastError());
+    if ((rc = ctl_down(c, &SM->status, &S.one->member_status, 4))) return rc;
+    if ((rc = ctl_down(c, &SM->err_off, &S.one->member_err_off, 8))) return rc;
+  }
   if ((rc = ctl_down(c, out_len, c->d_out_len.p, (size_t)n * 8))) return rc;
   if ((rc = ctl_down(c, status, c->d_istatus.p, (size_t)n * 4))) return rc;
   if ((rc = ctl_down(c, err_off, c->d_ierr.p, (size_t)n * 8))) return rc;
@@ -1993,13 +2032,14 @@ static int inflate_common(flate_hip_ctx *c, const uint8_t *in, const uint64_t *i
   HIP_TRY(c, hipGetLastError());
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   ctl_finish(c);
-  const bool used[FLATE_HIP_STAGE_COUNT] = {false, false, FRD != nullptr, true};
+  const bool used[FLATE_HIP_STAGE_COUNT] = {false, false, FRD != nullptr || SM != nullptr, true};
   if ((rc = collect_timing(c, used))) return rc;
   // A size-only pass has no capacity -- but the kernels count output in 32 bits: a stream that inflates
   // to 4 GiB or more stops there with "slot too small", which for a call without slots means "too large"
   if (size_only)
     for (uint32_t i = 0; i < n; ++i)
       if (status[i] == FLATE_HIP_E_OUT_TOO_SMALL) status[i] = FLATE_HIP_E_TOO_LARGE;
+  if (SM) return SM->status;  // (the first non-zero piece status, or the trailer's verdict with every piece at 0)
   for (uint32_t i = 0; i < n; ++i)
     if (status[i]) return status[i];
   return FLATE_HIP_OK;
@@ -2207,6 +2247,49 @@ static int inflate_frame_prepare(flate_hip_ctx *c, const InfFrame &FRD, const ui
   }
   I.in_off = R.pay_off;
   I.in_end = R.pay_end;
+  return FLATE_HIP_OK;
+}
+
+// The device side of flate_hip_inflate_spliced_framed in front of its decoder: frame_parse_kernel over the one range
+// {0, in_len}, then frame_rebase_kernel, which moves the uploaded index (I.in_off, counted from the raw stream's first
+// byte) behind the header the device has just measured.  The decoders read the member up to its trailer.
+static int inflate_member_prepare(flate_hip_ctx *c, const InfMember &SM, const uint8_t *d_in, uint64_t in_len, uint32_t n,
+                                  InfParams &I, FrameSplicedParams &S) {
+  int rc;
+  if ((rc = ensure(c, c->d_rd_one, sizeof(FrameOne) + 16))) return rc;
+  if ((rc = ensure(c, c->d_frame_off, ((size_t)n + 1) * 8))) return rc;
+  if ((rc = ensure(c, c->d_frame_sums, (size_t)n * 4 + 8))) return rc;
+  if ((rc = ensure(c, c->d_rd_bad, (size_t)n * 4 + 4))) return rc;
+  FrameOne *one = (FrameOne *)c->d_rd_one.p;
+  const uint64_t range[2] = {0, in_len};
+  if ((rc = ctl_up(c, one->in_off, range, sizeof range))) return rc;
+  FrameReadParams R{};
+  R.in = d_in;
+  R.in_off = one->in_off;
+  R.n_streams = 1;
+  R.wrap = SM.wrap;
+  R.pay_off = one->pay_off;
+  R.pay_end = &one->pay_end;
+  R.want = &one->want;
+  R.isize = &one->isize;
+  R.bad = &one->bad;
+  R.dict_used = &one->dict_used;
+  hipLaunchKernelGGL(frame_parse_kernel, dim3(1), dim3(256), 0, c->stream, R);
+  S.one = one;
+  S.bit_in = I.in_off;
+  S.bit_out = (uint64_t *)c->d_frame_off.p;
+  S.piece_bad = (uint32_t *)c->d_rd_bad.p;
+  S.n_pieces = n;
+  S.wrap = SM.wrap;
+  S.in_len = in_len;
+  S.raw_end = in_len - (SM.wrap == FLATE_HIP_WRAP_GZIP ? 8u : 4u);  // (the entry point has checked in_len)
+  S.out_len = I.out_len;
+  S.status = I.status;
+  S.err_off = I.err_off;
+  hipLaunchKernelGGL(frame_rebase_kernel, dim3(n / 256 + 1), dim3(256), 0, c->stream, S);
+  HIP_TRY(c, hipGetLastError());
+  I.bit_off = S.bit_out;
+  I.in_len = S.raw_end;
   return FLATE_HIP_OK;
 }
 
@@ -2466,6 +2549,52 @@ int flate_hip_inflate_spliced(flate_hip_ctx *c, const uint8_t *in, uint64_t in_l
     if (bit_off[i + 1] - bit_off[i] >= (1ull << 30)) return FLATE_HIP_E_TOO_LARGE;  // piece < 128 MiB
   }
   return inflate_common(c, in, bit_off, n, out, out_off, out_len, status, err_off, flags, in_len);
+}
+
+// what a decode call returns when it has run: FLATE_HIP_OK or the first non-zero status of a stream
+static bool is_stream_status(int rc) {
+  return rc == FLATE_HIP_OK || rc == FLATE_HIP_E_OUT_TOO_SMALL || rc == FLATE_HIP_E_CORRUPT || rc == FLATE_HIP_E_UNEXPECTED_EOF;
+}
+
+int flate_hip_inflate_spliced_framed(flate_hip_ctx *c, const uint8_t *in, uint64_t in_len, uint32_t wrap,
+                                     const uint64_t *bit_off, uint32_t n, uint8_t *out, const uint64_t *out_off,
+                                     uint64_t *out_len, int32_t *status, int64_t *err_off, int32_t *member_status,
+                                     int64_t *member_err_off, uint32_t flags) {
+  // every check before any HIP call
+  if (!c || wrap > FLATE_HIP_WRAP_GZIP || (flags & FLATE_HIP_SIZE_ONLY)) return FLATE_HIP_E_INVALID;
+  if (wrap == FLATE_HIP_WRAP_RAW) {  // the raw call: its kernels, its results
+    const int rc = flate_hip_inflate_spliced(c, in, in_len, bit_off, n, out, out_off, out_len, status, err_off, flags);
+    if (!is_stream_status(rc)) return rc;  // (refused, or failed: no verdict)
+    int32_t first = 0;
+    for (uint32_t i = 0; i < n && !first; ++i) first = status[i];
+    if (member_status) *member_status = first;
+    if (member_err_off) *member_err_off = -1;
+    return rc;
+  }
+  if (!in || !in_len || !bit_off || !out_off || !out_len || !status || !err_off || (n && !out)) return FLATE_HIP_E_INVALID;
+  c->hip_err.clear();
+  if (n == 0) return FLATE_HIP_OK;
+  // the shortest header (2 / 10 bytes) and the trailer (4 / 8) must fit, and the index must end inside what is left
+  const uint64_t frame = wrap == FLATE_HIP_WRAP_GZIP ? 18u : 6u;
+  if (in_len < frame) return FLATE_HIP_E_INVALID;
+  for (uint32_t i = 0; i < n; ++i) {
+    if (bit_off[i + 1] < bit_off[i] || out_off[i + 1] < out_off[i] || bit_off[i + 1] > 8 * (in_len - frame))
+      return FLATE_HIP_E_INVALID;
+    if (bit_off[i + 1] - bit_off[i] >= (1ull << 30)) return FLATE_HIP_E_TOO_LARGE;  // piece < 128 MiB
+  }
+  try {
+    // (host pointers: one copy in, parse, decode, check, one copy out)
+    InfMember SM{wrap};
+    const int rc = inflate_common(c, in, bit_off, n, out, out_off, out_len, status, err_off, flags, in_len, nullptr,
+                                  nullptr, &SM);
+    if (!is_stream_status(rc)) return rc;  // (failed: no verdict was read back)
+    if (member_status) *member_status = SM.status;
+    if (member_err_off) *member_err_off = SM.err_off;
+    return rc;
+  } catch (const std::exception &e) {  // (out of host memory in an index vector)
+    c->hip_err = e.what();
+    return FLATE_HIP_E_INTERNAL;
+  }
 }
 
 }  // extern "C"

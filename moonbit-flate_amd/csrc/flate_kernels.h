@@ -272,6 +272,42 @@ struct FrameReadParams {
 };
 __global__ void frame_parse_kernel(FrameReadParams P);
 __global__ void frame_verdict_kernel(FrameReadParams P);
+
+// Reading ONE member whose raw stream is spliced (flate_hip_inflate_spliced_framed): in[0, in_len) = header | the
+// n_pieces pieces of one DEFLATE stream | trailer, the index counted from the raw stream's first byte.
+// frame_parse_kernel runs over the one range {0, in_len} and fills a FrameOne; frame_rebase_kernel (one thread per
+// index entry) then moves the index to the member's first byte -- bit_in[i] + 8 * header length, never beyond the
+// raw stream's end: a piece that would start behind it gets no input (the decoders compute in_len - start unsigned)
+// -- so that the spliced decoders run unchanged on InfParams::in = the member, in_len = raw_end.  Whole bytes are
+// added: the bit alignment that stored blocks need is kept.  A bad header collapses every piece to the empty range
+// at raw_end.  frame_verdict_spliced_kernel (one workgroup, behind the decoder, the pieces' sums and their join)
+// applies the three cases of flate_hip.h to every piece and writes the member's two words.
+struct FrameOne {
+  uint64_t in_off[2];       // {0, in_len}: uploaded
+  uint64_t pay_off[2];      // frame_parse_kernel: [0] = the header's length
+  uint64_t pay_end;
+  uint64_t total;           // checksum_join_kernel: bytes of the concatenation
+  int64_t member_err_off;   // frame_verdict_spliced_kernel
+  uint32_t want, isize, bad, dict_used;  // frame_parse_kernel
+  uint32_t sum;             // checksum_join_kernel
+  int32_t member_status;    // frame_verdict_spliced_kernel
+};
+struct FrameSplicedParams {
+  FrameOne *one;
+  const uint64_t *bit_in;   // n_pieces + 1: counted from the raw stream's first byte
+  uint64_t *bit_out;        // n_pieces + 1: counted from the member's first byte (InfParams::bit_off)
+  uint32_t *piece_bad;      // per piece: the member's header verdict (checksum_device_clipped's d_bad)
+  uint32_t n_pieces;
+  uint32_t wrap;
+  uint64_t in_len;          // the member's bytes
+  uint64_t raw_end;         // in_len - trailer length
+  // frame_verdict_spliced_kernel
+  uint64_t *out_len;
+  int32_t *status;
+  int64_t *err_off;
+};
+__global__ void frame_rebase_kernel(FrameSplicedParams P);
+__global__ void frame_verdict_spliced_kernel(FrameSplicedParams P);
 size_t inflate_simt_lds_bytes(int lanes_per_wave);  // dynamic LDS of that launch
 size_t inflate_simt_lens_bytes(uint32_t blocks);    // global scratch of that launch (InfParams::simt_lens)
 
@@ -317,4 +353,11 @@ int checksum_device(flate_hip_ctx *c, const uint8_t *d_in, const uint64_t *in_of
 int checksum_device_clipped(flate_hip_ctx *c, const uint8_t *d_out, const uint64_t *slot_off, uint32_t n, uint32_t kind,
                             const uint64_t *d_out_len, const int32_t *d_status, const uint32_t *d_bad,
                             uint32_t *d_sums);
+// Behind it, for ONE member whose raw stream is spliced (flate_hip_inflate_spliced_framed): the n sums of d_sums
+// joined into the checksum of the concatenation of d_out[slot_off[i], slot_off[i] + min(out_len[i], slot)), i = 0 ..
+// n - 1, left at *d_sum with its length at *d_total (checksum_join_kernel, one workgroup; d_slot_off is the DEVICE
+// copy of slot_off).  A piece with a status was summed as nothing but keeps its length here: a member with such a
+// piece is never judged by its checksum.
+int checksum_join_device(flate_hip_ctx *c, const uint32_t *d_sums, const uint64_t *d_slot_off,
+                         const uint64_t *d_out_len, uint32_t n, uint32_t kind, uint32_t *d_sum, uint64_t *d_total);
 }  // namespace flate

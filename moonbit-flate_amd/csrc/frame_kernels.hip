@@ -18,6 +18,8 @@
 // READING members (flate_hip_inflate_batch_framed) is the other half of the file: frame_parse_kernel in front of the
 // batch decoders (header rules, the raw stream's range, the trailer's values, the DICTID's dictionary) and
 // frame_verdict_kernel behind them and behind the checksums of what they produced (flate_kernels.h: FrameReadParams).
+// ONE member around a spliced stream (flate_hip_inflate_spliced_framed): the same parse kernel over one range, then
+// frame_rebase_kernel (the index moved behind the header) and frame_verdict_spliced_kernel (FrameSplicedParams).
 #include <hip/hip_runtime.h>
 
 #include "flate_hip.h"
@@ -215,6 +217,73 @@ __global__ __launch_bounds__(256) void frame_verdict_kernel(FrameReadParams P) {
     P.status[i] = FLATE_HIP_E_CORRUPT;
     P.err_off[i] = (int64_t)(P.in_off[i + 1] - P.in_off[i]);
   }
+}
+
+// ---- reading one member whose raw stream is spliced (flate_hip_inflate_spliced_framed; FrameSplicedParams) ----
+
+__global__ __launch_bounds__(256) void frame_rebase_kernel(FrameSplicedParams P) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (i > P.n_pieces) return;
+  const bool bad = P.one->bad != 0;
+  const uint64_t end_bit = 8ull * P.raw_end;
+  // (a good header ends at or below raw_end -- frame_parse_kernel -- and the host has kept bit_in below 2^61)
+  const uint64_t bit = P.bit_in[i] + 8ull * P.one->pay_off[0];
+  P.bit_out[i] = (bad || bit > end_bit) ? end_bit : bit;
+  if (i < P.n_pieces) P.piece_bad[i] = bad ? 1u : 0u;
+}
+
+// One workgroup: the cases per piece, the first piece with a status of its own, then the member's two words.
+__global__ __launch_bounds__(1024) void frame_verdict_spliced_kernel(FrameSplicedParams P) {
+  __shared__ uint32_t first_s;
+  const uint32_t tid = threadIdx.x;
+  if (tid == 0) first_s = 0xffffffffu;
+  __syncthreads();
+  FrameOne &O = *P.one;
+  const bool bad = O.bad != 0;
+  const int64_t hl = (int64_t)O.pay_off[0];
+  uint32_t first = 0xffffffffu;
+  for (uint32_t i = tid; i < P.n_pieces; i += 1024u) {
+    if (bad) {
+      P.status[i] = FLATE_HIP_E_CORRUPT;
+      P.err_off[i] = 0;
+      P.out_len[i] = 0;
+    } else {
+      // a piece whose start was clamped has no input: to the decoders one that ends where it starts is an empty
+      // piece, so the end of the stream is reported here (the last piece, which has no end, meets it by itself)
+      if (P.status[i] == 0 && P.bit_in[i] + 8ull * (uint64_t)hl > 8ull * P.raw_end) {
+        P.status[i] = FLATE_HIP_E_UNEXPECTED_EOF;
+        P.err_off[i] = -1;
+        P.out_len[i] = 0;
+      }
+      if (P.status[i] != 0) {
+        if (first == 0xffffffffu) first = i;
+        // (the decoders count from InfParams::in, the member's first byte)
+        if (P.err_off[i] >= 0) P.err_off[i] = P.err_off[i] >= hl ? P.err_off[i] - hl : 0;
+      }
+    }
+  }
+  if (first != 0xffffffffu) atomicMin(&first_s, first);
+  __syncthreads();
+  if (tid != 0) return;
+  // (the trailer's two tests are folded into one flag with plain arithmetic before anything branches on them, and
+  // the error offset is chosen by that flag alone: written as `a || (gzip && b)` in the chain of cases below, the
+  // compiler in use kept the offset at -1 on the path where only the ISIZE differs)
+  const uint32_t isize_off = P.wrap == FLATE_HIP_WRAP_GZIP ? ((uint32_t)O.total ^ O.isize) : 0u;
+  const bool mismatch = ((O.sum ^ O.want) | isize_off) != 0u;
+  const uint32_t first_bad = first_s;
+  int32_t ms = 0;
+  int64_t me = -1;
+  if (bad) {
+    ms = FLATE_HIP_E_CORRUPT;
+    me = 0;
+  } else if (first_bad != 0xffffffffu) {
+    ms = P.status[first_bad];
+  } else if (mismatch) {
+    ms = FLATE_HIP_E_CORRUPT;
+    me = (int64_t)P.in_len;
+  }
+  O.member_status = ms;
+  O.member_err_off = me;
 }
 
 }  // namespace flate

@@ -521,6 +521,56 @@ class FlateEngine:
             self._check(rc)
         return out, out_off, out_len[:n], status[:n], err_off[:n]
 
+    def inflate_spliced_framed(self, data, nbytes, wrap, bit_off, out_sizes, out=None, check=True):
+        """The reverse of deflate_spliced_framed: ONE zlib stream or gzip member data[:nbytes] around a spliced
+        stream, decoded in parallel from its index and checked against its trailer on the GPU by one call
+        (flate_hip_inflate_spliced_framed).  bit_off is counted from the raw stream's first byte, as
+        deflate_spliced_framed returns it: the header (also a foreign one with FNAME / FEXTRA) is measured on the
+        device.  out_sizes[i] = capacity of piece i's slot.  data: numpy uint8 or a torch uint8 CUDA tensor.
+        An index of one entry -- what the writer returns for no input at all -- is one piece of size 0 at bit 0: the
+        closing block and the trailer of nothing are still checked.
+        Returns (out, out_off, out_len, status, err_off, member_status); member_status is the first non-zero piece
+        status, or -4 for a bad header (every piece -4) or a checksum / ISIZE that does not match what the pieces
+        produced (every piece 0), else 0.  With check=True a non-zero member status raises FlateError."""
+        bit_off = np.ascontiguousarray(bit_off, dtype=np.uint64)
+        out_sizes = np.asarray(out_sizes, dtype=np.uint64)
+        if bit_off.size == 1:
+            bit_off = np.array([bit_off[0], bit_off[0]], dtype=np.uint64)
+            out_sizes = np.zeros(1, dtype=np.uint64)
+        n = bit_off.size - 1
+        w = _wrap_code(wrap)
+        out_off = np.zeros(n + 1, dtype=np.uint64)
+        np.cumsum(out_sizes, out=out_off[1:])
+        out_len = np.zeros(max(n, 1), dtype=np.uint64)
+        status = np.zeros(max(n, 1), dtype=np.int32)
+        err_off = np.full(max(n, 1), -1, dtype=np.int64)
+        member_status, member_err = C.c_int32(0), C.c_int64(-1)
+        device = _is_torch(data)
+        total = max(int(out_off[-1]), 16)
+        if device:
+            import torch
+            assert data.dtype == torch.uint8 and data.is_cuda and data.is_contiguous()
+            if out is None:
+                out = torch.empty(total, dtype=torch.uint8, device=data.device)
+            else:
+                _check_out(out, data, int(out_off[-1]), "inflate_spliced_framed")
+            in_ptr, out_ptr = data.data_ptr(), out.data_ptr()
+        else:
+            data = np.ascontiguousarray(data, dtype=np.uint8)
+            if out is None:
+                out = np.zeros(total, dtype=np.uint8)
+            else:
+                _check_out(out, data, int(out_off[-1]), "inflate_spliced_framed")
+            in_ptr, out_ptr = data.ctypes.data, out.ctypes.data
+        rc = self._L.flate_hip_inflate_spliced_framed(
+            self._ctx, in_ptr, int(nbytes), w, bit_off.ctypes.data, n, out_ptr, out_off.ctypes.data,
+            out_len.ctypes.data, status.ctypes.data, err_off.ctypes.data, C.byref(member_status),
+            C.byref(member_err), DEVICE_PTRS if device else 0)
+        if rc != 0 and (check or rc not in (E_OUT_TOO_SMALL, E_CORRUPT, E_UNEXPECTED_EOF)):
+            self._check(rc)
+        self.last_member_err_off = int(member_err.value)
+        return out, out_off, out_len[:n], status[:n], err_off[:n], int(member_status.value)
+
     def lz77_matches(self, data, in_off, compat_go=False, lz_serial=False):
         """Match finder only.  Returns a list over LZ77 chunks (stream order) of
         (pos uint32[], tok uint32[]) and the per-stream chunk counts."""

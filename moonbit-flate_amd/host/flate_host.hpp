@@ -388,7 +388,8 @@ inline Err compress_spliced(Engine &e, const std::vector<std::vector<uint8_t>> &
 
 // The whole batch as ONE zlib stream or ONE gzip member around the spliced stream, checksum and length over the
 // concatenated input (flate_hip_deflate_fast_spliced_framed): what gzip -d / zlib's uncompress turn back into all the
-// bytes.  bit_off counts from the raw stream's first byte, behind the 2 (zlib) or 10 (gzip) header bytes.
+// bytes.  bit_off counts from the raw stream's first byte, behind the 2 (zlib) or 10 (gzip) header bytes;
+// decompress_spliced(..., Wrap) below takes the member and that index as they are.
 inline Err compress_spliced(Engine &e, const std::vector<std::vector<uint8_t>> &streams, std::vector<uint8_t> &out,
                             Wrap wrap, std::vector<uint64_t> *bit_off = nullptr, uint32_t flags = 0) {
   if (!e.ok()) return make_error(e, e.status());
@@ -792,6 +793,50 @@ inline Err decompress_spliced(Engine &e, const std::vector<uint8_t> &stream, con
   }
   out.resize(out_off[n]);
   return std::nullopt;
+}
+
+// The same for ONE zlib stream or gzip member around the spliced stream -- what compress_spliced(..., Wrap) writes, or
+// any other writer around the same raw stream: ONE call of flate_hip_inflate_spliced_framed, the header measured, the
+// pieces decoded and the trailer checked against the checksum of their concatenation, all on the GPU.  bit_off is
+// counted from the raw stream's first byte, as compress_spliced returns it; an index of one entry (no input at all)
+// is one piece of size 0.  sizes[i] = capacity for piece i; out = what the pieces produced, one after another.
+// Errors: a bad header is corrupt_input_error(0); a piece's own error is that piece's (its offset counted from the
+// raw stream's first byte); a checksum or (gzip) a length that does not match is corrupt_input_error at the member's
+// end -- `out` then still holds the bytes.  Wrap::Raw is the overload above.
+inline Err decompress_spliced(Engine &e, const std::vector<uint8_t> &member, std::vector<uint64_t> bit_off,
+                              std::vector<uint64_t> sizes, Wrap wrap, std::vector<uint8_t> &out) {
+  if (wrap == Wrap::Raw) return decompress_spliced(e, member, bit_off, sizes, out);
+  if (!e.ok()) return make_error(e, e.status());
+  if (bit_off.size() == 1) {
+    bit_off.push_back(bit_off[0]);
+    sizes.assign(1, 0);
+  }
+  const uint32_t n = (uint32_t)sizes.size();
+  if (bit_off.size() != (size_t)n + 1) return make_error(e, FLATE_HIP_E_INVALID);
+  std::vector<uint64_t> out_off(n + 1, 0), out_len(n + 1, 0);
+  std::vector<int32_t> status(n + 1, 0);
+  std::vector<int64_t> err_off(n + 1, -1);
+  for (uint32_t i = 0; i < n; ++i) out_off[i + 1] = out_off[i] + sizes[i];
+  std::vector<uint8_t> in(member), buf(out_off[n] + 8);
+  in.resize(in.size() + 8);
+  int32_t member_status = 0;
+  int64_t member_err_off = -1;
+  const int rc = flate_hip_inflate_spliced_framed(e.ctx(), in.data(), member.size(), wrap_code(wrap), bit_off.data(), n,
+                                                  buf.data(), out_off.data(), out_len.data(), status.data(),
+                                                  err_off.data(), &member_status, &member_err_off, 0);
+  if (rc != 0 && rc != FLATE_HIP_E_CORRUPT && rc != FLATE_HIP_E_UNEXPECTED_EOF && rc != FLATE_HIP_E_OUT_TOO_SMALL)
+    return make_error(e, rc);
+  out.clear();
+  for (uint32_t i = 0; i < n; ++i)
+    out.insert(out.end(), buf.begin() + out_off[i], buf.begin() + out_off[i] + std::min(out_len[i], sizes[i]));
+  if (member_status == 0) return std::nullopt;
+  if (member_err_off >= 0) return corrupt_input_error(member_err_off);  // the header (0) or the trailer (the member's end)
+  for (uint32_t i = 0; i < n; ++i) {
+    if (status[i] == FLATE_HIP_E_CORRUPT) return corrupt_input_error(err_off[i]);
+    if (status[i] == FLATE_HIP_E_UNEXPECTED_EOF) return err_unexpected_eof();
+    if (status[i] != 0) return make_error(e, status[i]);
+  }
+  return make_error(e, member_status);
 }
 
 }  // namespace flate_host
