@@ -10,15 +10,15 @@
 //
 // Three kernels, one wavefront per stream each, split so that every phase runs at the
 // occupancy its LDS footprint allows:
-//   huff_hist_kernel  index_tokens: per-block symbol histograms          (1.8 KiB LDS; bound by the LDS pipe)
+//   huff_hist_kernel  index_tokens: per-block symbol histograms          (2.0 KiB LDS; bound by the LDS pipe)
 //   huff_code_kernel  code construction, header, exact block bit sizes   (11.8 KiB LDS: 13 wavefronts per CU;
 //                     bound by one block's chain of dependent LDS round trips)
 //   huff_pack_kernel  write_dynamic_header + write_tokens, straight into the final
 //                     output at the offsets given by a scan of the exact sizes (4.3 KiB LDS; VALU-bound);
 //                     the token walk itself is handed over by huff_hist_kernel (tile_meta)
 // Everything that is a loop over tokens or symbols in the reference is a wave-parallel pass:
-//  * the token sequence is never materialised: each lane owns four input positions of a
-//    256-byte tile and decides from the (sorted) match records which of them are literals,
+//  * the token sequence is never materialised: each lane owns eight input positions of a
+//    512-byte tile and decides from the (sorted) match records which of them are literals,
 //    the start of a match, or covered by one;
 //  * code lengths come from a level-parallel package-merge that yields the same counts
 //    as the lazy boundary algorithm of huffman-code.mbt:112-244 (ties between a leaf
@@ -33,8 +33,9 @@ namespace flate {
 
 namespace {
 
-constexpr int kRing = 512;  // dwords in the LDS bit ring (a 256-position tile adds <= 186 dwords)
-constexpr int kTile = 256;  // input positions per walk step: 4 consecutive positions per lane
+constexpr int kRing = 512;  // dwords in the LDS bit ring (a 512-position tile adds <= 372 dwords: see sink_emit_pair)
+constexpr int kTile = 512;  // input positions per walk step: 8 consecutive positions per lane
+constexpr int kRow = 256;   // input positions per 64-byte row of HuffParams::tile_meta
 constexpr int kHdrMax = 704;
 
 // codegen_order, huffman-bit-writer.mbt:83-85 (RFC 1951 3.2.7)
@@ -82,7 +83,7 @@ static_assert(3 * kHdrMax <= (int)sizeof(uint32_t) * 576, "header entries fit a 
 struct SharedHist {
   uint32_t lit_freq[288];
   uint32_t off_freq[32];
-  // per-tile scatter target, one byte per position (lane L reads its four as one dword): 1 = the
+  // per-tile scatter target, one byte per position (lane L reads its eight as two dwords): 1 = the
   // first position a match covers (start + 1), 2 = the last one, 4 = a match starts here.  Matches
   // are >= 4 long and do not overlap, so no position ever gets two marks: plain byte stores.
   uint32_t marks[kTile / 4];
@@ -189,25 +190,31 @@ FLATE_D void sink_emit(BitSink &S, uint64_t bits, uint32_t nb, int lane) {
   __syncthreads();
 }
 
-// Wide form: every lane appends nb (<= 96) bits held in (lo, hi), in lane order.
-FLATE_D void sink_emit_wide(BitSink &S, uint64_t lo, uint32_t hi, uint32_t nb, int lane) {
+// Two halves per lane: every lane appends nb_a (<= 93) bits held in (lo_a, hi_a) and then nb_b (<= 93) bits held in
+// (lo_b, hi_b), in lane order.  One scan of the lane totals places both halves (the second at q + nb_a), one
+// barrier pair and one flush loop cover them.  Ring positions only need the bit position modulo 32 * kRing.
+FLATE_D void sink_place(BitSink &S, uint32_t q, uint64_t lo, uint32_t hi) {
+  const uint32_t w = q >> 5;
+  const uint32_t sh = q & 31u;
+  // the 96 bits shifted left by sh < 32 into four dwords; (x >> 1) >> (31 - sh) is x >> (32 - sh)
+  // without the special case sh == 0
+  const uint64_t v0 = lo << sh;
+  const uint32_t d0 = (uint32_t)v0, d1 = (uint32_t)(v0 >> 32);
+  const uint32_t d2 = (hi << sh) | (((uint32_t)(lo >> 32) >> 1) >> (31u - sh));
+  const uint32_t d3 = (hi >> 1) >> (31u - sh);
+  if (d0) atomicOr(&S.ring[w & (kRing - 1)], d0);
+  if (d1) atomicOr(&S.ring[(w + 1) & (kRing - 1)], d1);
+  if (d2) atomicOr(&S.ring[(w + 2) & (kRing - 1)], d2);
+  if (d3) atomicOr(&S.ring[(w + 3) & (kRing - 1)], d3);
+}
+FLATE_D void sink_emit_pair(BitSink &S, uint64_t lo_a, uint32_t hi_a, uint32_t nb_a, uint64_t lo_b, uint32_t hi_b,
+                            uint32_t nb_b, int lane) {
+  const uint32_t nb = nb_a + nb_b;
   const uint32_t incl = wave_incl_scan(nb);
   const uint32_t total = rdlane(incl, 63);
-  if (nb) {
-    const uint64_t q = S.bitpos + (incl - nb);
-    const uint32_t w = (uint32_t)(q >> 5);
-    const uint32_t sh = (uint32_t)q & 31u;
-    // the 96 bits shifted left by sh < 32 into four dwords; (x >> 1) >> (31 - sh) is x >> (32 - sh)
-    // without the special case sh == 0
-    const uint64_t v0 = lo << sh;
-    const uint32_t d0 = (uint32_t)v0, d1 = (uint32_t)(v0 >> 32);
-    const uint32_t d2 = (hi << sh) | (((uint32_t)(lo >> 32) >> 1) >> (31u - sh));
-    const uint32_t d3 = (hi >> 1) >> (31u - sh);
-    if (d0) atomicOr(&S.ring[w & (kRing - 1)], d0);
-    if (d1) atomicOr(&S.ring[(w + 1) & (kRing - 1)], d1);
-    if (d2) atomicOr(&S.ring[(w + 2) & (kRing - 1)], d2);
-    if (d3) atomicOr(&S.ring[(w + 3) & (kRing - 1)], d3);
-  }
+  const uint32_t q = (uint32_t)S.bitpos + (incl - nb);
+  if (nb_a) sink_place(S, q, lo_a, hi_a);
+  if (nb_b) sink_place(S, q + nb_a, lo_b, hi_b);
   S.bitpos += total;
   __syncthreads();
   while ((uint32_t)(S.bitpos >> 5) - S.flushed >= 64u) {
@@ -218,6 +225,10 @@ FLATE_D void sink_emit_wide(BitSink &S, uint64_t lo, uint32_t hi, uint32_t nb, i
   }
   __syncthreads();
 }
+// What the ring must hold while a tile is placed: fewer than 64 dwords still pending from the tile before,
+// the tile's own bits, the partly filled dword they start in and the three further dwords sink_place may touch.
+constexpr int kLaneBitsMax = 2 * (3 * 15 + 48);  // per half: three literals and a match
+static_assert(64 + 64 * kLaneBitsMax / 32 + 1 + 3 <= kRing, "a tile fits the bit ring");
 
 // flush(): pad with zero bits to a byte boundary (huffman-bit-writer.mbt:139-158)
 FLATE_D void sink_pad_to_byte(BitSink &S) { S.bitpos = (S.bitpos + 7) & ~7ull; }
@@ -448,26 +459,35 @@ FLATE_D void build_code(Shared &sh, const uint32_t *freq, int nsym, int max_bits
 }
 
 // ---- tile walk over the implied token sequence ----------------------------------------
-// A tile is 256 consecutive input positions; lane L owns positions P0 + 4L .. P0 + 4L + 3.
-// At most one match can start inside a lane's four positions (matches are >= 4 long).
+// A tile is 512 consecutive input positions; lane L owns P0 + 8L .. P0 + 8L + 7 as two dwords of input bytes and
+// two dwords of marks.  Matches are >= 4 long, so at most one match starts inside a dword's four positions: a lane
+// holds at most two match starts, a tile at most 128 records, and every lane keeps two records in flight.  What
+// costs the same whatever the tile's size -- zeroing the marks, the two barriers, the coverage scan with its
+// v_readlane, the cov_until hand-over, the loop itself -- is paid once per 512 positions (it was a third of the
+// instructions of a 256-position tile).
+//
+// What huff_pack_kernel needs to know about four positions, in one byte: the walk is done once, by
+// huff_hist_kernel, and handed over through HuffParams::tile_meta (one byte per four positions, rows of 64 bytes
+// per 256 positions): bits 0..3 = literal at position k, bit 4 = a match starts in the group, bits 5..6 = at which
+// position.  The j-th group of a tile with bit 4 set starts the j-th match record of that tile.  Positions after a
+// match start are covered (matches are >= 4 long), so the literals of a group all precede its match.  Two byte
+// dot products (v_dot4_u32_u8) build the byte from the flags.
 struct TileTok {
-  uint32_t bytes;  // the lane's four input bytes (little endian)
-  uint32_t lit;    // byte k = 1: position k is a literal
-  uint32_t start;  // byte k = 1: a match starts at position k (at most one byte set)
-  uint32_t tok;    // its token
-  // What huff_pack_kernel needs to know about a lane's four positions, in one byte: the walk is
-  // done once, by huff_hist_kernel, and handed over through HuffParams::tile_meta (64 bytes per
-  // tile): bits 0..3 = literal at position k, bit 4 = a match starts in the lane, bits 5..6 = at
-  // which position.  The j-th lane of a tile with bit 4 set starts the j-th match record of that
-  // tile.  Positions after a match start are covered (matches are >= 4 long), so the literals of a
-  // lane all precede its match.  Two byte dot products (v_dot4_u32_u8) build it from the flags.
-  FLATE_D uint32_t pack() const {
+  // (lit, start: byte k = 1 <=> position k of the group is a literal / starts a match)
+  static FLATE_D uint32_t pack(uint32_t lit, uint32_t start) {
     return __builtin_amdgcn_udot4(lit, 0x08040201u, __builtin_amdgcn_udot4(start, 0x70503010u, 0u, false), false);
   }
+  uint2 bytes;      // the lane's eight input bytes (little endian)
+  uint32_t lit[2];  // per dword, byte k = 1: position k is a literal
+  uint32_t meta;    // the meta bytes of the lane's two groups, the first group's in bits 0..7
+  // The records that start in this tile, BY THE LANE THAT LOADED THEM, not by the lane that owns the position:
+  // the histogram needs every token counted once, whoever counts it.
+  bool has0, has1;
+  uint32_t tok0, tok1;
 };
-// Where a block's tile rows (64 bytes per 256-position tile) start in HuffParams::tile_meta: by
-// the block's position in the input plus its index, so that the whole array is input / 4 bytes
-// plus one row per block (a block of n bytes has ceil(n / 256) <= n / 256 + 1 rows).
+// Where a block's rows (64 bytes per 256 positions) start in HuffParams::tile_meta: by the block's position in
+// the input plus its index, so that the whole array is input / 4 bytes plus one row per block (a block of n bytes
+// has ceil(n / 256) <= n / 256 + 1 rows).  A tile is two rows.
 FLATE_D uint64_t tile_meta_at(uint64_t block_start_in_input, uint32_t gb) {
   return ((block_start_in_input >> 8) + gb) * 64u;
 }
@@ -480,27 +500,29 @@ struct Walker {
   uint32_t mp;         // next match record
   uint32_t cov_until;  // positions < cov_until are covered by an earlier match
   // software pipeline: data of the tile about to be processed, loaded one tile ahead
-  uint2 rec;           // recs[mp + lane]  (<= 64 matches start in a tile)
-  uint32_t bytes;      // src[P0 + 4 lane .. +3]
+  uint2 rec0, rec1;    // recs[mp + lane], recs[mp + 64 + lane]  (<= 128 matches start in a tile)
+  uint2 bytes;         // src[P0 + 8 lane .. +7]
 };
 
-FLATE_D uint2 load_rec(const Walker &w, uint32_t mp, int lane) {
+FLATE_D uint2 load_rec(const Walker &w, uint32_t i) {
   uint2 r = make_uint2(0xffffffffu, 0);
-  if (mp + (uint32_t)lane < w.nm) r = w.recs[mp + lane];
+  if (i < w.nm) r = w.recs[i];
   return r;
 }
-FLATE_D uint32_t load_bytes4(const Walker &w, int pos) {
+FLATE_D uint2 load_bytes8(const uint8_t *src, int n, int pos) {
 #ifdef FLATE_EXP_NO_INPUT  // TIMING EXPERIMENT ONLY (wrong bytes on purpose): the entropy kernels without their reads of the input
-  return 0x20746165u + 0x01010101u * (((uint32_t)pos * 2654435761u) >> 30);
+  return make_uint2(0x20746165u + 0x01010101u * (((uint32_t)pos * 2654435761u) >> 30), 0x20746165u);
 #endif
-  if (pos + 4 <= w.n) {
-    uint32_t v;
-    __builtin_memcpy(&v, w.src + pos, 4);
+  if (pos + 8 <= n) {
+    uint2 v;
+    __builtin_memcpy(&v, src + pos, 8);
     return v;
   }
-  uint32_t v = 0;  // chunk tail: never read past the chunk
-  for (int k = 0; k < 4; ++k)
-    if (pos + k < w.n) v |= (uint32_t)w.src[pos + k] << (8 * k);
+  uint2 v = make_uint2(0u, 0u);  // chunk tail: never read past the chunk
+  for (int k = 0; k < 4; ++k) {
+    if (pos + k < n) v.x |= (uint32_t)src[pos + k] << (8 * k);
+    if (pos + 4 + k < n) v.y |= (uint32_t)src[pos + 4 + k] << (8 * k);
+  }
   return v;
 }
 
@@ -512,67 +534,86 @@ FLATE_D Walker walker_init(const uint8_t *src, const uint2 *recs, uint32_t nm, i
   w.n = n;
   w.mp = 0;
   w.cov_until = 0;
-  w.rec = load_rec(w, 0, lane);
-  w.bytes = load_bytes4(w, 4 * lane);
+  w.rec0 = load_rec(w, (uint32_t)lane);
+  w.rec1 = load_rec(w, 64u + (uint32_t)lane);
+  w.bytes = load_bytes8(src, n, 8 * lane);
   return w;
 }
 
 FLATE_D int clamp04(int v) { return v < 0 ? 0 : (v > 4 ? 4 : v); }  // (v_med3_i32)
-// Byte-parallel form: the marks of a lane's four positions are the four bytes of a dword, so a
-// multiply by 0x01010101 is their inclusive prefix sum (sums <= 4: no carry between bytes) and the
-// classification of the four positions is straight-line dword arithmetic.  (v_mul_lo_u32 is a
+FLATE_D uint32_t low_bytes(int t) { return (uint32_t)((0x01010101ull << (8 * clamp04(t))) >> 32); }  // 1 in the t lowest bytes
+// Byte-parallel form: the marks of four positions are the four bytes of a dword, so a multiply by
+// 0x01010101 is their inclusive prefix sum (sums <= 4: no carry between bytes) and the
+// classification of the four positions is straight-line dword arithmetic, done for the lane's two dwords in
+// turn: the second one's entering coverage is what the first one leaves.  (v_mul_lo_u32 is a
 // quarter-rate instruction: the sums the walk needs come from v_sad_u8, the prefix sums from two
 // shift-adds, the packed result from v_dot4_u32_u8.)
 FLATE_D TileTok walk_tile(SharedHist &sh, Walker &w, int P0, int lane) {
   TileTok t;
-  const int pos = P0 + 4 * lane;
-  const uint2 rec = w.rec;
+  const int pos = P0 + 8 * lane;
+  const uint2 rec0 = w.rec0, rec1 = w.rec1;
   t.bytes = w.bytes;
-  const bool mine = rec.x < (uint32_t)(P0 + kTile);
-  const int cnt = __popcll(__ballot(mine));
+  // records are sorted: those of this tile are the first cnt of the 128 in flight
+  const bool mine0 = rec0.x < (uint32_t)(P0 + kTile), mine1 = rec1.x < (uint32_t)(P0 + kTile);
+  const int cnt = __popcll(__ballot(mine0)) + __popcll(__ballot(mine1));
   // issue the next tile's loads now; they are consumed one iteration later
   w.mp += (uint32_t)cnt;
-  w.rec = load_rec(w, w.mp, lane);
-  w.bytes = load_bytes4(w, pos + kTile);
-  sh.marks[lane] = 0;
+  w.rec0 = load_rec(w, w.mp + (uint32_t)lane);
+  w.rec1 = load_rec(w, w.mp + 64u + (uint32_t)lane);
+  w.bytes = load_bytes8(w.src, w.n, pos + kTile);
+  *reinterpret_cast<uint2 *>(&sh.marks[2 * lane]) = make_uint2(0u, 0u);
   __syncthreads();
-  const uint32_t mlen = ((rec.y >> kLengthShift) & 0xffu) + 3u;
-  if (mine) {
-    uint8_t *mb = reinterpret_cast<uint8_t *>(sh.marks);
-    const uint32_t o = rec.x - (uint32_t)P0;
+  const uint32_t mlen0 = ((rec0.y >> kLengthShift) & 0xffu) + 3u, mlen1 = ((rec1.y >> kLengthShift) & 0xffu) + 3u;
+  uint8_t *mb = reinterpret_cast<uint8_t *>(sh.marks);
+  if (mine0) {
+    const uint32_t o = rec0.x - (uint32_t)P0;
     mb[o] = 4;
-    const uint32_t o1 = o + 1u, o2 = o + mlen - 1u;
+    const uint32_t o1 = o + 1u, o2 = o + mlen0 - 1u;
+    if (o1 < (uint32_t)kTile) mb[o1] = 1;
+    if (o2 < (uint32_t)kTile) mb[o2] = 2;
+  }
+  if (mine1) {
+    const uint32_t o = rec1.x - (uint32_t)P0;
+    mb[o] = 4;
+    const uint32_t o1 = o + 1u, o2 = o + mlen1 - 1u;
     if (o1 < (uint32_t)kTile) mb[o1] = 1;
     if (o2 < (uint32_t)kTile) mb[o2] = 2;
   }
   __syncthreads();
-  const uint32_t m = sh.marks[lane];
-  const uint32_t first = m & 0x01010101u, last = (m >> 1) & 0x01010101u;
-  // net coverage change of this lane: marks are bytes 0 / 1, v_sad_u8 against 0 sums four of them
-  const uint32_t tot = __builtin_amdgcn_sad_u8(first, 0u, 0u) - __builtin_amdgcn_sad_u8(last, 0u, 0u);
-  const uint32_t base = wave_incl_scan(tot) - tot;  // coverage entering this lane: 0 or 1
-  // positions below cov_until are covered by a match of an earlier tile: the t lowest bytes
-  const int t_lo = clamp04((int)w.cov_until - pos);
-  const uint32_t low = (uint32_t)((0x01010101ull << (8 * t_lo)) >> 32);
-  if (cnt) w.cov_until = rdlane(rec.x, cnt - 1) + rdlane(mlen, cnt - 1);
-  // coverage of position k = coverage entering the lane + firsts up to k - lasts before k: per-byte
+  const uint2 m = *reinterpret_cast<const uint2 *>(&sh.marks[2 * lane]);
+  const uint32_t first0 = m.x & 0x01010101u, last0 = (m.x >> 1) & 0x01010101u;
+  const uint32_t first1 = m.y & 0x01010101u, last1 = (m.y >> 1) & 0x01010101u;
+  // net coverage change of each dword: marks are bytes 0 / 1, v_sad_u8 against 0 sums four of them; ONE scan of
+  // the lane's total over all eight bytes
+  const uint32_t tot0 = __builtin_amdgcn_sad_u8(first0, 0u, 0u) - __builtin_amdgcn_sad_u8(last0, 0u, 0u);
+  const uint32_t tot = __builtin_amdgcn_sad_u8(first1, 0u, tot0) - __builtin_amdgcn_sad_u8(last1, 0u, 0u);
+  const uint32_t base0 = wave_incl_scan(tot) - tot;  // coverage entering this lane: 0 or 1
+  const uint32_t base1 = base0 + tot0;               // ... and entering its second dword
+  // positions below cov_until are covered by a match of an earlier tile
+  const uint32_t low0 = low_bytes((int)w.cov_until - pos), low1 = low_bytes((int)w.cov_until - pos - 4);
+  if (cnt) {  // the end of the tile's last record, which sits in register (cnt - 1) >> 6, lane (cnt - 1) & 63
+    const uint32_t end = cnt > 64 ? rec1.x + mlen1 : rec0.x + mlen0;
+    w.cov_until = rdlane(end, (cnt - 1) & 63);
+  }
+  const uint32_t act0 = low_bytes(w.n - pos), act1 = low_bytes(w.n - pos - 4);  // my positions inside the chunk
+  // coverage of position k = coverage entering the dword + firsts up to k - lasts before k: per-byte
   // inclusive prefix sums of first - (last << 8), x * 0x01010101 as two shift-adds (the borrows
   // between the bytes cancel in the sums; the coverage itself is 0 or 1 in every byte).
   // (inline asm: written in C the compiler folds the two steps back into a quarter-rate multiply)
-  const uint32_t e = first - (last << 8) + base;
-  uint32_t e2, e4;
-  asm("v_lshl_add_u32 %0, %1, 8, %1" : "=v"(e2) : "v"(e));
-  asm("v_lshl_add_u32 %0, %1, 16, %1" : "=v"(e4) : "v"(e2));
-  const uint32_t cov = e4 | low;
-  const int t_act = clamp04(w.n - pos);  // my positions inside the chunk
-  const uint32_t act = (uint32_t)((0x01010101ull << (8 * t_act)) >> 32);
-  t.start = (m >> 2) & act;
-  t.lit = act & ~(cov | t.start);
-  // token of the match that starts here: the j-th lane with a start owns the j-th record of the tile
-  // (records are sorted, a lane holds at most one start), fetched from the lane that loaded it
-  const uint64_t sb = __ballot(t.start != 0);
-  const uint32_t tk = (uint32_t)__shfl((int)rec.y, (int)__popcll(sb & ((1ull << lane) - 1ull)));
-  t.tok = t.start ? tk : 0u;
+  const uint32_t ea = first0 - (last0 << 8) + base0, eb = first1 - (last1 << 8) + base1;
+  uint32_t ea2, ea4, eb2, eb4;
+  asm("v_lshl_add_u32 %0, %1, 8, %1" : "=v"(ea2) : "v"(ea));
+  asm("v_lshl_add_u32 %0, %1, 8, %1" : "=v"(eb2) : "v"(eb));
+  asm("v_lshl_add_u32 %0, %1, 16, %1" : "=v"(ea4) : "v"(ea2));
+  asm("v_lshl_add_u32 %0, %1, 16, %1" : "=v"(eb4) : "v"(eb2));
+  const uint32_t start0 = (m.x >> 2) & act0, start1 = (m.y >> 2) & act1;
+  t.lit[0] = act0 & ~(ea4 | low0 | start0);
+  t.lit[1] = act1 & ~(eb4 | low1 | start1);
+  t.meta = TileTok::pack(t.lit[0], start0) | (TileTok::pack(t.lit[1], start1) << 8);
+  t.has0 = mine0;
+  t.has1 = mine1;
+  t.tok0 = rec0.y;
+  t.tok1 = rec1.y;
   return t;
 }
 
@@ -793,14 +834,16 @@ FLATE_D void hist_block(const HuffParams &P, SharedHist &sh, const BlockGeom &g,
     uint32_t *lit_freq = sh.lit_freq, *off_freq = sh.off_freq;
     __syncthreads();
     if (kind == 1) {
-      Walker w = walker_init(src, nullptr, 0u, n, lane);
+      uint2 bt = load_bytes8(src, n, 8 * lane);
       for (int base = 0; base < n; base += kTile) {
-        const int i = base + 4 * lane;
-        const uint32_t bt = w.bytes;
-        w.bytes = load_bytes4(w, i + kTile);
+        const int i = base + 8 * lane;
+        const uint2 cur = bt;
+        bt = load_bytes8(src, n, i + kTile);
 #pragma unroll
-        for (int k = 0; k < 4; ++k)
-          if (i + k < n) atomicAdd(&lit_freq[(bt >> (8 * k)) & 0xffu], 1u);
+        for (int k = 0; k < 4; ++k) {
+          if (i + k < n) atomicAdd(&lit_freq[(cur.x >> (8 * k)) & 0xffu], 1u);
+          if (i + 4 + k < n) atomicAdd(&lit_freq[(cur.y >> (8 * k)) & 0xffu], 1u);
+        }
       }
       __syncthreads();
       if (lane == 0) {
@@ -809,21 +852,29 @@ FLATE_D void hist_block(const HuffParams &P, SharedHist &sh, const BlockGeom &g,
       }
     } else {
       const uint32_t chunk = g.chunk0 + b;
-      Walker w = walker_init(src, P.matches + (uint64_t)chunk * kMatchCapPerChunk, P.chunk_nmatch[chunk],
-                             n, lane);
+      Walker w = walker_init(src, P.matches + (uint64_t)chunk * kMatchCapPerChunk, P.chunk_nmatch[chunk], n, lane);
       uint8_t *tmeta = P.tile_meta + tile_meta_at((uint64_t)(src - P.in), gb);
+      // A tile spans two rows of tile_meta.  The block owns ceil(n / 256) rows; when that is odd, the second
+      // row of its last tile is the NEXT block's first row and another wavefront writes it.  A lane stores its two
+      // bytes (one row: pos is a multiple of 8) only inside the block's own rows -- all of them, zeros behind the
+      // chunk's end included, as the packer reads whole rows.
+      const int own = (n + kRow - 1) & ~(kRow - 1);
+      auto count_match = [&](uint32_t tok) {
+        const uint32_t lcode = sh.len_code[(tok >> kLengthShift) & 0xffu];
+        const CodeBits oc = offset_code_of(tok & ((1u << kLengthShift) - 1u));
+        atomicAdd(&lit_freq[kLengthCodesStart + lcode], 1u);
+        atomicAdd(&off_freq[oc.code], 1u);
+      };
       for (int P0 = 0; P0 < n; P0 += kTile) {
         const TileTok t = walk_tile(sh, w, P0, lane);
-        tmeta[(P0 >> 2) + lane] = (uint8_t)t.pack();
-        if (t.start) {
-          const uint32_t lcode = sh.len_code[(t.tok >> kLengthShift) & 0xffu];
-          const CodeBits oc = offset_code_of(t.tok & ((1u << kLengthShift) - 1u));
-          atomicAdd(&lit_freq[kLengthCodesStart + lcode], 1u);
-          atomicAdd(&off_freq[oc.code], 1u);
-        }
+        if (P0 + 8 * lane < own) *reinterpret_cast<uint16_t *>(tmeta + (P0 >> 2) + 2 * lane) = (uint16_t)t.meta;
+        if (t.has0) count_match(t.tok0);
+        if (t.has1) count_match(t.tok1);
 #pragma unroll
-        for (int k = 0; k < 4; ++k)
-          if ((t.lit >> (8 * k)) & 1u) atomicAdd(&lit_freq[(t.bytes >> (8 * k)) & 0xffu], 1u);
+        for (int k = 0; k < 4; ++k) {
+          if ((t.lit[0] >> (8 * k)) & 1u) atomicAdd(&lit_freq[(t.bytes.x >> (8 * k)) & 0xffu], 1u);
+          if ((t.lit[1] >> (8 * k)) & 1u) atomicAdd(&lit_freq[(t.bytes.y >> (8 * k)) & 0xffu], 1u);
+        }
       }
       if (lane == 0) atomicAdd(&lit_freq[kEndBlockMarker], 1u);  // tokens.push(EOB), :507
     }
@@ -995,84 +1046,110 @@ FLATE_D void pack_block(const HuffParams &P, SharedPack &sh, BitSink &S, const B
       }
     }
     if (kind == 1) {
-      Walker w = walker_init(src, nullptr, 0u, n, lane);
+      uint2 nx = load_bytes8(src, n, 8 * lane);
       for (int base = 0; base < n; base += kTile) {
-        const int i = base + 4 * lane;
-        const uint32_t bt = w.bytes;
-        w.bytes = load_bytes4(w, i + kTile);
-        uint64_t lo = 0;  // four codes of <= 15 bits
-        uint32_t nb = 0;
+        const int i = base + 8 * lane;
+        const uint2 bt = nx;
+        nx = load_bytes8(src, n, i + kTile);
+        uint64_t lo_a = 0, lo_b = 0;  // four codes of <= 15 bits each
+        uint32_t nb_a = 0, nb_b = 0;
 #pragma unroll
-        for (int k = 0; k < 4; ++k)
+        for (int k = 0; k < 4; ++k) {
           if (i + k < n) {
-            const uint32_t c = sh.lit_cl[(bt >> (8 * k)) & 0xffu];
-            lo |= (uint64_t)(c & 0xffffu) << nb;
-            nb += c >> 16;
+            const uint32_t c = sh.lit_cl[(bt.x >> (8 * k)) & 0xffu];
+            lo_a |= (uint64_t)(c & 0xffffu) << nb_a;
+            nb_a += c >> 16;
           }
-        sink_emit_wide(S, lo, 0u, nb, lane);
+          if (i + 4 + k < n) {
+            const uint32_t c = sh.lit_cl[(bt.y >> (8 * k)) & 0xffu];
+            lo_b |= (uint64_t)(c & 0xffffu) << nb_b;
+            nb_b += c >> 16;
+          }
+        }
+        sink_emit_pair(S, lo_a, 0u, nb_a, lo_b, 0u, nb_b, lane);
       }
     } else {
-      // The walk over the implied token sequence was done by huff_hist_kernel: per tile, one byte
-      // per lane (TileTok::pack) says which of the lane's four positions are literals and whether
-      // a match starts there; the lane's rank among the match lanes of the tile is its record.
-      // Everything a tile needs is loaded one tile ahead (its meta byte two ahead).
+      // The walk over the implied token sequence was done by huff_hist_kernel: per four positions one byte
+      // (TileTok::pack) says which of them are literals and whether a match starts there.  A lane owns eight
+      // positions of a 512-position tile, that is two consecutive bytes of a pair of tile_meta rows; the rank of
+      // a match start among the tile's starts, in position order (lane L's first half, its second half, lane
+      // L + 1's first half ...), is its record.  Everything a tile needs is loaded one tile ahead (its meta
+      // bytes two ahead).
       const uint32_t chunk = g.chunk0 + b;
       const uint2 *recs = P.matches + (uint64_t)chunk * kMatchCapPerChunk;
       const uint8_t *tmeta = P.tile_meta + tile_meta_at((uint64_t)(src - P.in), gb);
-      Walker w = walker_init(src, nullptr, 0u, n, lane);  // (input bytes only)
       const int ntiles = (n + kTile - 1) / kTile;
       uint32_t mp = 0;
-      auto tok_of = [&](uint32_t m) -> uint32_t {
-        const bool has = (m & 0x10u) != 0;
-        const uint64_t B = __ballot(has);
-        uint32_t tok = 0;
-        if (has) tok = recs[mp + (uint32_t)__popcll(B & ((1ull << lane) - 1ull))].y;
-        mp += (uint32_t)__popcll(B);
-        return tok;
+      // Only groups that begin inside the block are read: when the block has an odd number of rows the second
+      // row of its last tile belongs to the next block.  (pos < n: both bytes lie in one of the block's own rows,
+      // which huff_hist_kernel writes whole.)
+      auto meta_of = [&](int t) -> uint32_t {
+        return t * kTile + 8 * lane < n ? *reinterpret_cast<const uint16_t *>(tmeta + t * (kTile / 4) + 2 * lane) : 0u;
       };
-      uint32_t m_cur = tmeta[lane];
-      uint32_t tok_cur = tok_of(m_cur);
-      uint32_t m_next = ntiles > 1 ? tmeta[64 + lane] : 0u;
-      for (int t = 0; t < ntiles; ++t) {
-        const uint32_t bt = w.bytes;
-        w.bytes = load_bytes4(w, (t + 1) * kTile + 4 * lane);
-        const uint32_t tok_next = tok_of(m_next);
-        const uint32_t m_next2 = t + 2 < ntiles ? tmeta[(t + 2) * 64 + lane] : 0u;
-        uint64_t lo;
-        uint32_t hi = 0, nb;
-        {
-          // The codes of all four bytes are looked up at once (one LDS round trip, no branches) and
-          // those of covered positions masked off; pairs are joined in 32 bits (<= 30 each), the two
-          // pairs by one 64-bit shift.  At most three literals when a match follows: <= 45 bits.
-          uint32_t c[4];
+      auto toks_of = [&](uint32_t m, uint32_t &ta, uint32_t &tb) {
+        const bool ha = (m & 0x10u) != 0, hb = (m & 0x1000u) != 0;
+        const uint64_t A = __ballot(ha), B = __ballot(hb);
+        const uint64_t below = (1ull << lane) - 1ull;
+        const uint32_t r = mp + (uint32_t)__popcll(A & below) + (uint32_t)__popcll(B & below);
+        ta = tb = 0;
+        if (ha) ta = recs[r].y;
+        if (hb) tb = recs[r + (ha ? 1u : 0u)].y;
+        mp += (uint32_t)__popcll(A) + (uint32_t)__popcll(B);
+      };
+      // one half: the codes c[0..3] of its four bytes, its meta byte m and the token of its match
+      auto half_bits = [&](uint32_t *c, uint32_t m, uint32_t tok, uint64_t &lo, uint32_t &hi, uint32_t &nb) {
+        // codes of covered positions masked off; pairs are joined in 32 bits (<= 30 each), the two pairs by one
+        // 64-bit shift.  At most three literals when a match follows: <= 45 bits.
 #pragma unroll
-          for (int k = 0; k < 4; ++k) c[k] = sh.lit_cl[(bt >> (8 * k)) & 0xffu];
-#pragma unroll
-          for (int k = 0; k < 4; ++k) c[k] = ((m_cur >> k) & 1u) ? c[k] : 0u;
-          const uint32_t n0 = c[0] >> 16, n1 = c[1] >> 16, n2 = c[2] >> 16, n3 = c[3] >> 16;
-          const uint32_t p01 = (c[0] & 0xffffu) | ((c[1] & 0xffffu) << n0);
-          const uint32_t p23 = (c[2] & 0xffffu) | ((c[3] & 0xffffu) << n2);
-          lo = (uint64_t)p01 | ((uint64_t)p23 << (n0 + n1));
-          nb = n0 + n1 + n2 + n3;
-        }
-        if (m_cur & 0x10u) {
-          const uint32_t lb = sh.len_bits[(tok_cur >> kLengthShift) & 0xffu];
-          const CodeBits oc = offset_code_of(tok_cur & ((1u << kLengthShift) - 1u));
+        for (int k = 0; k < 4; ++k) c[k] = ((m >> k) & 1u) ? c[k] : 0u;
+        const uint32_t n0 = c[0] >> 16, n1 = c[1] >> 16, n2 = c[2] >> 16, n3 = c[3] >> 16;
+        const uint32_t p01 = (c[0] & 0xffffu) | ((c[1] & 0xffffu) << n0);
+        const uint32_t p23 = (c[2] & 0xffffu) | ((c[3] & 0xffffu) << n2);
+        lo = (uint64_t)p01 | ((uint64_t)p23 << (n0 + n1));
+        nb = n0 + n1 + n2 + n3;
+        hi = 0;
+        if (m & 0x10u) {
+          const uint32_t lb = sh.len_bits[(tok >> kLengthShift) & 0xffu];
+          const CodeBits oc = offset_code_of(tok & ((1u << kLengthShift) - 1u));
           const uint32_t c2 = sh.off_cl[oc.code];
           // length code + extra (<= 15 + 5 bits, from the block's table) and offset code + extra
           // (<= 15 + 13) each in one dword, joined by a single 64-bit shift
-          const uint32_t n1 = lb >> 24;
+          const uint32_t l1 = lb >> 24;
           const uint32_t part1 = lb & 0xffffffu;
           const uint32_t part2 = (c2 & 0xffffu) | (oc.extra << (c2 >> 16));
-          const uint64_t bits = part1 | ((uint64_t)part2 << n1);
-          const uint32_t mb = n1 + (c2 >> 16) + oc.nextra;  // <= 48
+          const uint64_t bits = part1 | ((uint64_t)part2 << l1);
+          const uint32_t mbits = l1 + (c2 >> 16) + oc.nextra;  // <= 48
           hi = nb ? (uint32_t)(bits >> (64u - nb)) : 0u;  // (< 2^29: 48 + 45 - 64 bits)
           lo |= bits << nb;
-          nb += mb;
+          nb += mbits;
         }
-        sink_emit_wide(S, lo, hi, nb, lane);
+      };
+      uint2 nx = load_bytes8(src, n, 8 * lane);
+      uint32_t m_cur = meta_of(0);
+      uint32_t ta_cur, tb_cur;
+      toks_of(m_cur, ta_cur, tb_cur);
+      uint32_t m_next = meta_of(1);
+      for (int t = 0; t < ntiles; ++t) {
+        const uint2 bt = nx;
+        nx = load_bytes8(src, n, (t + 1) * kTile + 8 * lane);
+        uint32_t ta_next, tb_next;
+        toks_of(m_next, ta_next, tb_next);
+        const uint32_t m_next2 = meta_of(t + 2);
+        // the codes of all eight bytes in one LDS round trip
+        uint32_t ca[4], cb[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          ca[k] = sh.lit_cl[(bt.x >> (8 * k)) & 0xffu];
+          cb[k] = sh.lit_cl[(bt.y >> (8 * k)) & 0xffu];
+        }
+        uint64_t lo_a, lo_b;
+        uint32_t hi_a, hi_b, nb_a, nb_b;
+        half_bits(ca, m_cur & 0xffu, ta_cur, lo_a, hi_a, nb_a);
+        half_bits(cb, m_cur >> 8, tb_cur, lo_b, hi_b, nb_b);
+        sink_emit_pair(S, lo_a, hi_a, nb_a, lo_b, hi_b, nb_b, lane);
         m_cur = m_next;
-        tok_cur = tok_next;
+        ta_cur = ta_next;
+        tb_cur = tb_next;
         m_next = m_next2;
       }
     }
@@ -1085,11 +1162,13 @@ FLATE_D void pack_block(const HuffParams &P, SharedPack &sh, BitSink &S, const B
 // (:788-823), stored blocks: the stream's bits go to out + out_off[sid].
 // ---------------------------------------------------------------------------------------
 // (amdgpu_num_sgpr: a SIMD's 800 scalar registers admit floor(800 / (ceil(sgpr / 16) * 16 + 16)) wavefronts -- 6 at
-// the 105 the compiler would take, 8 at 80; the kernel is VALU-bound and wants all eight: 1.09 -> 0.93 ms)
+// the 105 the compiler would take, 8 at 80; the kernel is VALU-bound and wants all eight: 1.09 -> 0.93 ms.
+// amdgpu_waves_per_eu: with two halves per lane the allocator would take 69 vector registers, seven wavefronts; held
+// to the 64 that eight allow it still needs no scratch, and 16384 one-wavefront blocks stay two exact rounds)
 #ifndef FLATE_HUFF_PACK_SGPR
 #define FLATE_HUFF_PACK_SGPR 80
 #endif
-__attribute__((amdgpu_num_sgpr(FLATE_HUFF_PACK_SGPR)))
+__attribute__((amdgpu_num_sgpr(FLATE_HUFF_PACK_SGPR), amdgpu_waves_per_eu(8, 8)))
 __global__ __launch_bounds__(64) void huff_pack_kernel(HuffParams P) {
   __shared__ SharedPack sh;
   const int lane = threadIdx.x;
@@ -1196,7 +1275,7 @@ __global__ __launch_bounds__(256) void huff_zero_edges_kernel(HuffParams P, uint
     if (k >= own_lo && k < own_hi) bytes[k] = 0;
 }
 
-__attribute__((amdgpu_num_sgpr(FLATE_HUFF_PACK_SGPR)))
+__attribute__((amdgpu_num_sgpr(FLATE_HUFF_PACK_SGPR), amdgpu_waves_per_eu(8, 8)))
 __global__ __launch_bounds__(64) void huff_pack_block_kernel(HuffParams P) {
   __shared__ SharedPack sh;
   const int lane = threadIdx.x;
