@@ -1,0 +1,64 @@
+// api_checks.h -- the argument checks of the C ABI's batch calls: plain C++17, no ctx and no HIP call, so that
+// tests/test_api_checks.py reaches every refusal on the CPU.  The entry points test their ctx first.
+#pragma once
+
+#include <stdint.h>
+
+#include "flate_hip.h"
+
+namespace flate {
+
+// flate_hip_inflate_batch(_dict, _framed): the pointers ...
+inline bool inflate_batch_ptrs_ok(const uint8_t *in, const uint64_t *in_off, uint32_t n, const uint8_t *out,
+                                  const uint64_t *out_off, const uint64_t *out_len, const int32_t *status,
+                                  const int64_t *err_off, uint32_t flags) {
+  const bool size_only = (flags & FLATE_HIP_SIZE_ONLY) != 0;
+  return in_off && out_len && status && err_off && (!n || in) && (size_only || (out_off && (!n || out)));
+}
+// ... and the streams' offsets and sizes
+inline int inflate_batch_ranges(const uint64_t *in_off, uint32_t n, const uint64_t *out_off, uint32_t flags) {
+  const bool size_only = (flags & FLATE_HIP_SIZE_ONLY) != 0;
+  for (uint32_t i = 0; i < n; ++i)
+    if (in_off[i + 1] < in_off[i] || (!size_only && out_off[i + 1] < out_off[i])) return FLATE_HIP_E_INVALID;
+  for (uint32_t i = 0; i < n; ++i)
+    if (in_off[i + 1] - in_off[i] >= 0x7ffe0000ull) return FLATE_HIP_E_TOO_LARGE;
+  return FLATE_HIP_OK;
+}
+
+// The dictionary table of a call (flate_hip_inflate_batch_framed needs no more: its members choose by DICTID) ...
+inline bool dict_table_ok(const uint8_t *dicts, const uint64_t *dict_off, uint32_t n_dicts) {
+  if (n_dicts && !dict_off) return false;
+  for (uint32_t j = 0; j < n_dicts; ++j)
+    if (dict_off[j + 1] < dict_off[j]) return false;
+  return !(n_dicts && dict_off[n_dicts] > dict_off[0] && !dicts);
+}
+// ... and with the streams' choices (flate_hip_inflate_batch_dict / flate_hip_deflate_fast_batch_dict)
+inline bool dict_args_ok(const uint8_t *dicts, const uint64_t *dict_off, uint32_t n_dicts, const uint32_t *dict_of,
+                         uint32_t n) {
+  if (!dict_of && n_dicts == 0) return false;
+  if (!dict_table_ok(dicts, dict_off, n_dicts)) return false;
+  if (dict_of)
+    for (uint32_t i = 0; i < n; ++i)
+      if (dict_of[i] >= n_dicts && dict_of[i] != FLATE_HIP_NO_DICT) return false;
+  return true;
+}
+
+// The index of a spliced stream of in_len bytes (flate_hip_inflate_spliced; _spliced_framed: frame_bytes =
+// frame_min_len(wrap), the shortest header and the trailer, which must fit and which the index must leave room for).
+inline int spliced_index_check(const uint64_t *bit_off, uint32_t n, const uint64_t *out_off, uint64_t in_len,
+                               uint64_t frame_bytes) {
+  if (in_len < frame_bytes) return FLATE_HIP_E_INVALID;
+  for (uint32_t i = 0; i < n; ++i) {
+    if (bit_off[i + 1] < bit_off[i] || out_off[i + 1] < out_off[i] || bit_off[i + 1] > 8 * (in_len - frame_bytes))
+      return FLATE_HIP_E_INVALID;
+    if (bit_off[i + 1] - bit_off[i] >= (1ull << 30)) return FLATE_HIP_E_TOO_LARGE;  // piece < 128 MiB
+  }
+  return FLATE_HIP_OK;
+}
+
+// what a decode call returns when it has run: FLATE_HIP_OK or the first non-zero status of a stream
+inline bool is_stream_status(int rc) {
+  return rc == FLATE_HIP_OK || rc == FLATE_HIP_E_OUT_TOO_SMALL || rc == FLATE_HIP_E_CORRUPT || rc == FLATE_HIP_E_UNEXPECTED_EOF;
+}
+
+}  // namespace flate

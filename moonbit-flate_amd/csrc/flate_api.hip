@@ -1,148 +1,23 @@
-// flate_api.hip -- C ABI of libflate_hip.so (see include/flate_hip.h).
+// flate_api.hip -- C ABI of libflate_hip.so (see include/flate_hip.h): the ctx, its options and staging, the encode
+// calls.  (The decode calls: flate_api_inflate.hip; what the two share: flate_ctx.h.)
 //
 // Host-side driver: plans the chunking exactly as Compressor::write / enc_speed /
 // close stage their 65535-byte window (reference deflate.mbt:222-294,157-183), owns
 // the HBM scratch (match records, output slots, index arrays) and launches the
 // kernels on one HIP stream.  There is no CPU compression path in this library.
-#include "flate_hip.h"
-
-#include <hip/hip_runtime.h>
+#include "flate_ctx.h"
 
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <condition_variable>
 #include <exception>
 #include <stdexcept>
-#include <mutex>
-#include <string>
-#include <thread>
-#include <vector>
 
-#include "flate_kernels.h"
+#include "api_checks.h"
 
 using namespace flate;
-
-namespace {
-
-// Device memory that belongs to one owner (the ctx, a stream handle): grown by ensure(), freed with the owner, whose
-// release function has selected the device.
-struct DevBuf {
-  void *p = nullptr;
-  size_t cap = 0;
-  DevBuf() = default;
-  DevBuf(const DevBuf &) = delete;
-  DevBuf &operator=(const DevBuf &) = delete;
-  ~DevBuf() {
-    if (p) (void)hipFree(p);
-  }
-};
-
-}  // namespace
-
-struct flate_hip_ctx {
-  int device = 0;
-  hipStream_t own_stream = nullptr;
-  hipStream_t stream = nullptr;
-  std::string hip_err;
-  bool profiling = false;
-  float stage_ms[FLATE_HIP_STAGE_COUNT] = {0, 0, 0, 0};
-  hipEvent_t ev[2 * FLATE_HIP_STAGE_COUNT] = {};
-  // persistent device data
-  DevBuf scan_tab;
-  int scan_len = 0;
-  // grow-only scratch
-  DevBuf d_in, d_out, d_in_off, d_chunk_base, d_ids16, d_ids32, d_matches, d_nmatch, d_ntok;
-  DevBuf d_slot_off, d_out_len, d_out_off, d_status;
-  DevBuf d_blk_base, d_blk_hist, d_blk_cl, d_blk_hdr, d_blk_meta, d_tile_meta, d_blk_sid;
-  // entropy stage with one wavefront per BLOCK instead of per stream: -1 = when the batch's streams
-  // have three or more blocks on average (multi-window streams), 0 = never, 1 = whenever possible
-  int entropy_per_block = -1;
-  DevBuf d_istatus, d_ierr, d_debug, d_gtables, d_queue, d_simt_lens;
-  DevBuf d_dicts, d_dict_at, d_dict_len;  // flate_hip_inflate_batch_dict: dictionary tails, per-stream (at, len)
-  // flate_hip_deflate_fast_batch_dict (it shares the three above, there per used dictionary): the streams that start
-  // from a dictionary, every stream's dictionary slot, the primed tables and sweep clocks of the slots
-  DevBuf d_idsD, d_lz_slot_of, d_lz_tables, d_lz_clocks;
-  // the *_framed calls: member offsets, the streams' checksums, per stream its dictionary, the dictionaries' Adler-32
-  // (DICTIDs) and, for host callers, the whole dictionaries
-  DevBuf d_frame_off, d_frame_sums, d_frame_dict_of, d_frame_ids, d_frame_dicts;
-  // flate_hip_inflate_batch_framed (it shares d_frame_off: the raw streams' starts, d_frame_sums, d_frame_ids,
-  // d_frame_dicts): the raw streams' ends, the trailers' sums and ISIZEs, the header verdicts, the chosen dictionaries,
-  // and per dictionary where its staged tail lies and how long it is
-  DevBuf d_rd_end, d_rd_want, d_rd_isize, d_rd_bad, d_rd_dict, d_rd_tail_at, d_rd_tail_len;
-  // flate_hip_inflate_spliced_framed (it shares d_frame_off: the index counted from the member's first byte,
-  // d_frame_sums: the pieces' sums, d_rd_bad: the header verdict per piece): the one member's words (FrameOne)
-  DevBuf d_rd_one;
-  hipStream_t guest_stream = nullptr;
-  hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-  int guest_blocks = 0;      // 0 = guest kernel off
-  uint32_t guest_min = 1280; // below this many streams (5 per CU) the guests stay idle: one block per stream
-  int32_t h_status_word = 0;  // landing pads of small async D2H copies
-  uint64_t h_total_bytes = 0;
-  uint32_t num_cus = 256;
-  int inflate_lanes = 0;  // streams per wavefront of that inflater: 0 = by batch size, or 16/32/64
-  int inflate_row = 8;    // dwords of a lane's output row in the 64-lane form (0 = stores go straight to memory, 8, 16)
-  // batches at least this large use the lane-per-stream inflater: it takes ~30 ms for 64 KiB
-  // streams whatever the batch size, the wave-per-stream one ~13 ms per 1024 streams (measured:
-  // tools/inflate_crossover.py)
-  uint32_t inflate_simt_min = 2049;
-  // the speculative wave-per-stream decoder (inflate_spec_kernel): 0 = never, 1 = for batches below
-  // inflate_spec_max streams (where it beats both other decoders), 2 = always (tests)
-  int inflate_spec = 1;
-  int inflate_spec_shape = 0;  // 0 = by batch size, 1 / 2 = always the small-batch / large-batch build (tests, tuning)
-  uint32_t inflate_spec_max = 45056;  // measured (tools/inflate_crossover.py, ms per batch of 64 KiB text streams,
-                                      // sub-block decoder against lane per stream; profiles/r04/inflate_crossover.txt):
-                                      // 8192: 6.7 / 29.3; 16384: 13.1 / 30.8; 32768: 26.0 / 32.4; 40960: 32.4 / 33.7;
-                                      // 49152: 38.8 / 35.3; 65536: 51.6 / 39.3 -- the lane-per-stream decoder wins
-                                      // from ~44 k streams on (round 3, with four of its wavefronts per CU: ~37 k)
-  uint32_t resident_blocks = 1024;  // persistent LDS-table blocks (4 per CU x 256 CUs)
-  // (Rounds 2-4 carried an entropy stage OVERLAPPED with the match finder -- sub-batches gated on counters
-  // the persistent launch incremented, in an even and an uneven form.  Never faster than running the two one
-  // after the other (profiles/r02, r04), and a soak run of round 4 once saw the pack kernel's self-check fire
-  // in the even form, not reproduced in 115 000 stress runs: removed)
-  // window-granular scheduling of multi-window streams (lz77_kernels.hip, uq_*): on by default
-  int window_units = 1;
-  DevBuf d_uq_ready, d_uq_tables, d_uq_sweep;
-  DevBuf d_aux[2];  // ctx_scratch (checksum.hip)
-  // measurement aids (flate_hip_last_resident_share, option "profile_split_streams")
-  uint32_t profile_split = 0;        // > 0: LDS-table blocks take exactly the first K queue entries,
-                                     // the guest blocks the rest (two queues instead of one)
-  uint32_t last_count[2] = {0, 0};   // queue lengths of the last persistent launches (16-bit, multi)
-  uint32_t queue_init = 0;
-  uint32_t debug_chunks = 0;
-  // Host-pointer calls of the batch encoder: the batch is cut into host_groups groups of streams
-  // and group g is compressed while group g+1 is copied in and the output of group g-1 is copied
-  // out (two copy threads on two non-blocking streams).  0 = one copy in, compress, one copy out.
-  int host_groups = 8;
-  uint32_t host_group_streams = 2048;  // a group holds at least this many streams (inflate: four times as many)
-  // bounded waits of the persistent kernels (uq_pop): polls before giving up
-  // (a poll is one relaxed load + s_sleep, >= 0.4 us; a wave that is not running does not count)
-  uint32_t spin_limit = 8u << 20;
-  uint32_t inject_drop_push = 0;  // test hook: the k-th window hand-over (1-based) is dropped
-  uint32_t inject_stall = 0;      // test hook: the k-th dense batch (1-based) of every chunk makes no progress
-  uint64_t stream_rebase = 1ull << 30;  // flate_hip_stream: origin moved up past this many bytes
-  int64_t debug_buffer_reset = 0;       // test hook: buffer_reset (deflate-fast.mbt:55) of streams opened from now on
-  hipStream_t h2d_stream = nullptr, d2h_stream = nullptr;
-  // Host-pointer batches run their groups on TWO lanes (sub-contexts with their own streams and
-  // scratch, driven by two host threads): the persistent match-finder launch of group g+1 fills the
-  // chip while group g's last streams, its entropy kernels and its size read-back drain, which a single
-  // lane leaves idle (4 groups of 4096 streams: 19.9 ms of match finding against 16.2 for the batch
-  // as one launch).  0 = one lane (round 3's behaviour).
-  int host_lanes = 2;
-  flate_hip_ctx *lane[2] = {nullptr, nullptr};
-  // pinned staging of a call's small index arrays (ctl_up / ctl_down): they travel by a copy KERNEL,
-  // never through the DMA engines the bulk transfers of the host-pointer pipelines occupy
-  struct CtlStage {
-    uint8_t *p = nullptr;
-    size_t cap = 0, used = 0;
-  } ctl_up_buf, ctl_down_buf;
-  struct CtlPending {
-    void *host_dst;
-    size_t off, bytes;
-  };
-  std::vector<CtlPending> ctl_pending;
-};
+using namespace flate_host;
 
 namespace flate {
 hipStream_t ctx_stream(flate_hip_ctx *c) { return c->stream; }
@@ -166,16 +41,7 @@ int ctx_stage_collect(flate_hip_ctx *c, int stage) {
 }
 }  // namespace flate
 
-namespace {
-
-#define HIP_TRY(ctx, expr)                                                         \
-  do {                                                                             \
-    hipError_t e_ = (expr);                                                        \
-    if (e_ != hipSuccess) {                                                        \
-      (ctx)->hip_err = std::string(#expr) + ": " + hipGetErrorString(e_);          \
-      return FLATE_HIP_E_HIP;                                                      \
-    }                                                                              \
-  } while (0)
+namespace flate_host {
 
 int ensure(flate_hip_ctx *c, DevBuf &b, size_t bytes) {
   if (bytes <= b.cap) return FLATE_HIP_OK;
@@ -211,7 +77,7 @@ int ctl_begin(flate_hip_ctx *c, size_t up_bytes, size_t down_bytes) {
   return grow(c->ctl_down_buf, down_bytes + 16 * 256);
 }
 
-void ctl_launch(flate_hip_ctx *c, void *dst, const void *src, size_t bytes) {
+static void ctl_launch(flate_hip_ctx *c, void *dst, const void *src, size_t bytes) {
   const size_t nwords = (bytes + 3) / 4;
   uint32_t blocks = (uint32_t)((nwords + 255) / 256);
   if (blocks > 512) blocks = 512;
@@ -248,7 +114,7 @@ void ctl_finish(flate_hip_ctx *c) {
   c->ctl_pending.clear();
 }
 
-}  // namespace
+}  // namespace flate_host
 namespace flate {
 int ctx_scratch(flate_hip_ctx *c, int slot, size_t bytes, void **p) {
   if (slot < 0 || slot > 1) return FLATE_HIP_E_INVALID;
@@ -345,18 +211,9 @@ int make_plan(const uint64_t *in_off, uint32_t n, StagePlan &pl, uint32_t flags,
   return FLATE_HIP_OK;
 }
 
-struct StageTimer {
-  flate_hip_ctx *c;
-  int stage;
-  StageTimer(flate_hip_ctx *ctx, int s) : c(ctx), stage(s) {
-    if (c->profiling) (void)hipEventRecord(c->ev[2 * stage], c->stream);
-  }
-  ~StageTimer() {
-    if (c->profiling) (void)hipEventRecord(c->ev[2 * stage + 1], c->stream);
-  }
-};
+}  // namespace
 
-int collect_timing(flate_hip_ctx *c, const bool used[FLATE_HIP_STAGE_COUNT]) {
+int flate_host::collect_timing(flate_hip_ctx *c, const bool used[FLATE_HIP_STAGE_COUNT]) {
   for (int s = 0; s < FLATE_HIP_STAGE_COUNT; ++s) {
     c->stage_ms[s] = 0.f;
     if (c->profiling && used[s]) {
@@ -367,6 +224,8 @@ int collect_timing(flate_hip_ctx *c, const bool used[FLATE_HIP_STAGE_COUNT]) {
   }
   return FLATE_HIP_OK;
 }
+
+namespace {
 
 // The parameter blocks as far as the ctx owns what they point at (its scratch, its options); the callers add
 // the input, the index arrays and what is theirs alone.
@@ -746,17 +605,17 @@ int flate_hip_set_option(flate_hip_ctx *c, const char *name, int64_t value) {
   } else if (k == "guest_min_streams" && value >= 0) {
     c->guest_min = (uint32_t)value;
   } else if (k == "inflate_lanes" && (value == 0 || value == 16 || value == 32 || value == 64)) {
-    c->inflate_lanes = (int)value;
+    c->inflate.lanes = (int)value;
   } else if (k == "inflate_row_dwords" && (value == 0 || value == 8 || value == 16)) {
-    c->inflate_row = (int)value;
+    c->inflate.row = (int)value;
   } else if (k == "inflate_simt_min_streams" && value >= 0) {
-    c->inflate_simt_min = (uint32_t)value;
+    c->inflate.simt_min = (uint32_t)value;
   } else if (k == "inflate_spec" && value >= 0 && value <= 2) {
-    c->inflate_spec = (int)value;
+    c->inflate.spec = (int)value;
   } else if (k == "inflate_spec_shape" && value >= 0 && value <= 2) {
-    c->inflate_spec_shape = (int)value;
+    c->inflate.spec_shape = (int)value;
   } else if (k == "inflate_spec_max_streams" && value >= 0 && value <= 0x7fffffff) {
-    c->inflate_spec_max = (uint32_t)value;
+    c->inflate.spec_max = (uint32_t)value;
   } else if (k == "resident_blocks" && value > 0 && value <= 65536) {
     c->resident_blocks = (uint32_t)value;
   } else if (k == "host_pipeline_groups" && value >= 0 && value <= 64) {
@@ -874,22 +733,17 @@ static int deflate_common(flate_hip_ctx *c, const uint8_t *in, const uint64_t *i
   const bool dev = (flags & FLATE_HIP_DEVICE_PTRS) != 0;
   const uint64_t in_bytes = in_off[n];
   // a spliced member's fixed header and trailer; what the checksum kernels sum: the streams, or the one stream
-  const uint32_t f_hl = !FR ? 0u : FR->wrap == FLATE_HIP_WRAP_GZIP ? 10u : 2u;
-  const uint32_t f_tl = !FR ? 0u : FR->wrap == FLATE_HIP_WRAP_GZIP ? 8u : 4u;
+  const uint32_t f_hl = FR ? frame_header_len(FR->wrap, false) : 0u;
+  const uint32_t f_tl = FR ? frame_trailer_len(FR->wrap) : 0u;
   const uint64_t whole[2] = {in_off[0], in_off[n]};
   const uint64_t *sum_off = spliced ? whole : in_off;
   const uint32_t sum_n = spliced ? 1u : n;
-  std::vector<uint64_t> f_doff;  // the dictionaries' offsets counted from the first one
   size_t f_up = 0;
   if (FR) {
     if (spliced && out_cap < (uint64_t)f_hl + f_tl) return FLATE_HIP_E_OUT_TOO_SMALL;
     f_up = (size_t)n * 4 + 256 + checksum_ctl_up_bytes(sum_off, sum_n);
-    if (FR->dict_of) {
-      // (n_dicts == 0: every dict_of entry is FLATE_HIP_NO_DICT and dict_off may be null -- dict_args_ok)
-      f_doff.assign((size_t)FR->n_dicts + 1, 0);
-      for (uint32_t j = 1; j <= FR->n_dicts; ++j) f_doff[j] = FR->dict_off[j] - FR->dict_off[0];
-      f_up += checksum_ctl_up_bytes(f_doff.data(), FR->n_dicts);
-    }
+    // (n_dicts == 0: every dict_of entry is FLATE_HIP_NO_DICT and dict_off may be null -- dict_args_ok)
+    if (FR->dict_of) f_up += dictid_ctl_up_bytes(FR->dict_off, FR->n_dicts);
   }
   // the call's index arrays: in_off, chunk_base, blk_base (n + 1 each), the two stream lists, blk_sid
   if ((rc = ctl_begin(c, ((size_t)n + 1) * 16 + (pl.ids16.size() + pl.ids32.size() + pl.idsD.size() + (size_t)pl.n_blocks) * 4 + f_up,
@@ -918,26 +772,19 @@ static int deflate_common(flate_hip_ctx *c, const uint8_t *in, const uint64_t *i
     if ((rc = ensure(c, c->d_slot_off, ((size_t)n + 1) * 16))) return rc;  // stream summaries {a, b}
   }
   if ((rc = ctl_up(c, c->d_blk_base.p, pl.blk_base.data(), ((size_t)n + 1) * 4))) return rc;
-  const uint8_t *d_whole_dicts = nullptr;
   if (FR) {
     if ((rc = ensure(c, c->d_frame_off, ((size_t)n + 1) * 8))) return rc;
     if ((rc = ensure(c, c->d_frame_sums, (size_t)n * 4 + 8))) return rc;
     if (FR->dict_of) {
       if ((rc = ensure(c, c->d_frame_dict_of, (size_t)n * 4 + 4))) return rc;
-      if ((rc = ensure(c, c->d_frame_ids, (size_t)FR->n_dicts * 4 + 4))) return rc;
-      // both checksum_device calls below carve slot 0 of the scratch: sized once here for the larger, so that the
-      // second cannot grow it (a hipFree, which drains the device) inside the timed stage
-      const size_t a = checksum_scratch_bytes(f_doff.data(), FR->n_dicts), b = checksum_scratch_bytes(sum_off, sum_n);
+      // the DICTIDs' checksums and the streams' (below) carve slot 0 of the scratch: sized once here for the larger, so
+      // that the second cannot grow it (a hipFree, which drains the device) inside the timed stage
+      const size_t a = dictid_scratch_bytes(FR->dict_off, FR->n_dicts), b = checksum_scratch_bytes(sum_off, sum_n);
       void *unused = nullptr;
       if ((rc = ctx_scratch(c, 0, a > b ? a : b, &unused))) return rc;
       if ((rc = ctl_up(c, c->d_frame_dict_of.p, FR->dict_of, (size_t)n * 4))) return rc;
-      const uint64_t bytes = f_doff[FR->n_dicts];
-      d_whole_dicts = FR->dicts && FR->n_dicts ? FR->dicts + FR->dict_off[0] : nullptr;
-      if (!dev) {  // DICTID is the Adler-32 of the whole dictionary: the tails of dict_upload are not enough
-        if ((rc = ensure(c, c->d_frame_dicts, bytes + 16))) return rc;
-        if (bytes) HIP_TRY(c, hipMemcpyAsync(c->d_frame_dicts.p, d_whole_dicts, bytes, hipMemcpyHostToDevice, c->stream));
-        d_whole_dicts = (const uint8_t *)c->d_frame_dicts.p;
-      }
+      // (DICTID is the Adler-32 of the whole dictionary: the tails of dict_upload are not enough)
+      if ((rc = dictid_stage(c, FR->dicts, FR->dict_off, FR->n_dicts, flags))) return rc;
     }
   }
   HIP_TRY(c, hipMemsetAsync(c->d_status.p, 0, 4, c->stream));
@@ -1028,13 +875,7 @@ static int deflate_common(flate_hip_ctx *c, const uint8_t *in, const uint64_t *i
   if (FR) {
     // after the pack kernel: its spliced form works on whole dwords around the stream
     StageTimer t(c, FLATE_HIP_STAGE_CHECKSUM);
-    if (FR->dict_of &&
-        (rc = checksum_device(c, d_whole_dicts, f_doff.data(), FR->n_dicts, FLATE_HIP_CHECKSUM_ADLER32,
-                              (uint32_t *)c->d_frame_ids.p, -1)))
-      return rc;
-    if ((rc = checksum_device(c, d_in, sum_off, sum_n,
-                              FR->wrap == FLATE_HIP_WRAP_GZIP ? FLATE_HIP_CHECKSUM_CRC32 : FLATE_HIP_CHECKSUM_ADLER32,
-                              (uint32_t *)c->d_frame_sums.p, -1)))
+    if ((rc = checksum_device(c, d_in, sum_off, sum_n, frame_sum_kind(FR->wrap), (uint32_t *)c->d_frame_sums.p, -1)))
       return rc;
     hipLaunchKernelGGL(frame_write_kernel, dim3(sum_n / 256 + 1), dim3(256), 0, c->stream, F);
   }
@@ -1064,108 +905,81 @@ static bool host_trace_on() {
   static const bool on = getenv("FLATE_HIP_TRACE_HOST") != nullptr;
   return on;
 }
-static double host_now_ms() {
+double flate_host::host_now_ms() {
   return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
-static void host_trace(double t0, const char *what, unsigned g, double a, double b) {
+void flate_host::host_trace(double t0, const char *what, unsigned g, double a, double b) {
   if (host_trace_on()) fprintf(stderr, "[host-pipe] %-8s g=%u  %.2f .. %.2f ms\n", what, g, a - t0, b - t0);
 }
 
-// ---- host-pointer batches, pipelined over groups of streams (flate_hip_ctx::host_groups) ----
-// Two copy threads beside the calling thread: one brings the groups' input to the device in
-// order, the other takes every group's output back as soon as the caller posts it.  Each uses its
-// own non-blocking HIP stream, so the copies run beside the kernels of the group in between.
-namespace {
-struct CopyJob {
-  void *dst;
-  const void *src;
-  size_t bytes;
-};
-class CopyPipe {
- public:
-  CopyPipe(size_t n_in, size_t n_out) : in_ready_(n_in, 0), out_state_(n_out, 0), out_jobs_(n_out) {}
-  // (not in the constructor: if the second thread cannot be created, the destructor must still run
-  // to join the first)
-  void start(int device, hipStream_t s_in, hipStream_t s_out, std::vector<CopyJob> in_jobs) {
-    const size_t n_out = out_jobs_.size();
-    t_in_ = std::thread([this, device, s_in, in_jobs] {
-      (void)hipSetDevice(device);
-      for (size_t g = 0; g < in_jobs.size(); ++g) {
-        {
-          std::lock_guard<std::mutex> l(mu_);
-          if (stop_) return;
-        }
-        const double a = host_now_ms();
-        const bool ok = run(in_jobs[g], hipMemcpyHostToDevice, s_in, "host-to-device copy: ");
-        host_trace(t0_, "h2d", (unsigned)g, a, host_now_ms());
+// ---- host-pointer batches, pipelined over groups of streams (flate_hip_ctx::host_groups; CopyPipe: flate_ctx.h) ----
+namespace flate_host {
+void CopyPipe::start(int device, hipStream_t s_in, hipStream_t s_out, std::vector<CopyJob> in_jobs) {
+  const size_t n_out = out_jobs_.size();
+  t_in_ = std::thread([this, device, s_in, in_jobs] {
+    (void)hipSetDevice(device);
+    for (size_t g = 0; g < in_jobs.size(); ++g) {
+      {
         std::lock_guard<std::mutex> l(mu_);
-        in_ready_[g] = ok ? 1 : -1;
-        cv_.notify_all();
-        if (!ok) return;
+        if (stop_) return;
       }
-    });
-    t_out_ = std::thread([this, device, s_out, n_out] {
-      (void)hipSetDevice(device);
-      for (size_t g = 0; g < n_out; ++g) {
-        CopyJob j;
-        {
-          std::unique_lock<std::mutex> l(mu_);
-          cv_.wait(l, [&] { return out_state_[g] != 0; });
-          if (out_state_[g] < 0) return;
-          j = out_jobs_[g];
-        }
-        const double a = host_now_ms();
-        if (!run(j, hipMemcpyDeviceToHost, s_out, "device-to-host copy: ")) return;
-        host_trace(t0_, "d2h", (unsigned)g, a, host_now_ms());
+      const double a = host_now_ms();
+      const bool ok = run(in_jobs[g], hipMemcpyHostToDevice, s_in, "host-to-device copy: ");
+      host_trace(t0_, "h2d", (unsigned)g, a, host_now_ms());
+      std::lock_guard<std::mutex> l(mu_);
+      in_ready_[g] = ok ? 1 : -1;
+      cv_.notify_all();
+      if (!ok) return;
+    }
+  });
+  t_out_ = std::thread([this, device, s_out, n_out] {
+    (void)hipSetDevice(device);
+    for (size_t g = 0; g < n_out; ++g) {
+      CopyJob j;
+      {
+        std::unique_lock<std::mutex> l(mu_);
+        cv_.wait(l, [&] { return out_state_[g] != 0; });
+        if (out_state_[g] < 0) return;
+        j = out_jobs_[g];
       }
-    });
-  }
-  // blocks until group g's input is on the device; false = its copy failed
-  bool wait_in(size_t g) {
-    std::unique_lock<std::mutex> l(mu_);
-    cv_.wait(l, [&] { return in_ready_[g] != 0; });
-    return in_ready_[g] > 0;
-  }
-  void post_out(size_t g, CopyJob j) {
+      const double a = host_now_ms();
+      if (!run(j, hipMemcpyDeviceToHost, s_out, "device-to-host copy: ")) return;
+      host_trace(t0_, "d2h", (unsigned)g, a, host_now_ms());
+    }
+  });
+}
+bool CopyPipe::wait_in(size_t g) {
+  std::unique_lock<std::mutex> l(mu_);
+  cv_.wait(l, [&] { return in_ready_[g] != 0; });
+  return in_ready_[g] > 0;
+}
+void CopyPipe::post_out(size_t g, CopyJob j) {
+  std::lock_guard<std::mutex> l(mu_);
+  out_jobs_[g] = j;
+  out_state_[g] = 1;
+  cv_.notify_all();
+}
+std::string CopyPipe::finish() {
+  {
     std::lock_guard<std::mutex> l(mu_);
-    out_jobs_[g] = j;
-    out_state_[g] = 1;
+    stop_ = true;
+    for (auto &st : out_state_)
+      if (st == 0) st = -1;
     cv_.notify_all();
   }
-  // ends both threads (outputs not posted yet are dropped) and returns the first copy error
-  std::string finish() {
-    {
-      std::lock_guard<std::mutex> l(mu_);
-      stop_ = true;
-      for (auto &st : out_state_)
-        if (st == 0) st = -1;
-      cv_.notify_all();
-    }
-    if (t_in_.joinable()) t_in_.join();
-    if (t_out_.joinable()) t_out_.join();
-    return err_;
-  }
-  ~CopyPipe() { (void)finish(); }
-
- private:
-  bool run(const CopyJob &j, hipMemcpyKind kind, hipStream_t s, const char *what) {
-    hipError_t e = hipSuccess;
-    if (j.bytes) e = hipMemcpyAsync(j.dst, j.src, j.bytes, kind, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e == hipSuccess) return true;
-    std::lock_guard<std::mutex> l(mu_);
-    if (err_.empty()) err_ = std::string(what) + hipGetErrorString(e);
-    return false;
-  }
-  double t0_ = host_now_ms();
-  std::mutex mu_;
-  std::condition_variable cv_;
-  std::vector<int> in_ready_, out_state_;  // 0 pending, 1 done / posted, -1 failed / dropped
-  std::vector<CopyJob> out_jobs_;
-  std::string err_;
-  bool stop_ = false;
-  std::thread t_in_, t_out_;
-};
+  if (t_in_.joinable()) t_in_.join();
+  if (t_out_.joinable()) t_out_.join();
+  return err_;
+}
+bool CopyPipe::run(const CopyJob &j, hipMemcpyKind kind, hipStream_t s, const char *what) {
+  hipError_t e = hipSuccess;
+  if (j.bytes) e = hipMemcpyAsync(j.dst, j.src, j.bytes, kind, s);
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  if (e == hipSuccess) return true;
+  std::lock_guard<std::mutex> l(mu_);
+  if (err_.empty()) err_ = std::string(what) + hipGetErrorString(e);
+  return false;
+}
 
 // Group boundaries of a host-pointer batch: group g ends at the first stream where the running byte
 // count (a, plus b when given) reaches g / G of the total -- streams of very different sizes still
@@ -1198,7 +1012,7 @@ int host_pipe_streams(flate_hip_ctx *c) {
   if (!c->d2h_stream) HIP_TRY(c, mk(&c->d2h_stream));
   return FLATE_HIP_OK;
 }
-}  // namespace
+}  // namespace flate_host
 
 // The launch options of the parent, as they are now, for a lane's sub-context.
 static void lane_options(flate_hip_ctx *dst, const flate_hip_ctx *src) {
@@ -1631,124 +1445,6 @@ int flate_hip_stream_write(flate_hip_stream *st, const uint8_t *in, uint64_t n, 
   return rc;
 }
 
-}  // extern "C"
-
-// ---- one long stream decoded in pieces (Decompressor::read as the reference behaves: the caller
-// ---- holds a piece of input and a piece of output, never the whole stream; inflate.mbt:382-407) ----
-struct flate_hip_inflate_stream {
-  flate_hip_ctx *ctx = nullptr;
-  DevBuf state, in, out;
-  int status = 0;           // sticky: 1 = the final block is done, < 0 = error
-  int64_t err_off = -1;
-  uint32_t bit_in_byte = 0; // of the byte the next call's input starts with
-  uint64_t total_in = 0, total_out = 0;
-};
-
-extern "C" {
-
-int flate_hip_inflate_stream_open(flate_hip_ctx *c, flate_hip_inflate_stream **out) {
-  if (!c || !out) return FLATE_HIP_E_INVALID;
-  *out = nullptr;
-  c->hip_err.clear();
-  HIP_TRY(c, hipSetDevice(c->device));
-  flate_hip_inflate_stream *st = new flate_hip_inflate_stream();
-  st->ctx = c;
-  int rc = ensure(c, st->state, inflate_stream_state_bytes() + 64);
-  if (rc == FLATE_HIP_OK) {
-    hipLaunchKernelGGL(inflate_stream_init_kernel, dim3(1), dim3(64), 0, c->stream, st->state.p,
-                       (const uint8_t *)nullptr, 0u);
-    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) rc = FLATE_HIP_E_HIP;
-  }
-  if (rc != FLATE_HIP_OK) {
-    delete st;
-    return rc;
-  }
-  *out = st;
-  return FLATE_HIP_OK;
-}
-
-// Decompressor::reset(r, dict) (inflate.mbt:862-884) / &Reader::new_dict (:315-317): a fresh decoder on
-// the same handle, with the last 32768 bytes of `dict` as history that has already been read
-// (DictDecoder::new, dict-decoder.mbt:40-60).
-int flate_hip_inflate_stream_reset(flate_hip_inflate_stream *st, const uint8_t *dict, uint64_t dict_len) {
-  if (!st || (dict_len && !dict)) return FLATE_HIP_E_INVALID;
-  flate_hip_ctx *c = st->ctx;
-  c->hip_err.clear();
-  HIP_TRY(c, hipSetDevice(c->device));
-  if (dict_len > (uint64_t)kMaxMatchOffset) {
-    dict += dict_len - (uint64_t)kMaxMatchOffset;
-    dict_len = (uint64_t)kMaxMatchOffset;
-  }
-  int rc;
-  if ((rc = ensure(c, st->in, dict_len + 16))) return rc;
-  if (dict_len) HIP_TRY(c, hipMemcpyAsync(st->in.p, dict, dict_len, hipMemcpyHostToDevice, c->stream));
-  hipLaunchKernelGGL(inflate_stream_init_kernel, dim3(1), dim3(256), 0, c->stream, st->state.p,
-                     (const uint8_t *)st->in.p, (uint32_t)dict_len);
-  HIP_TRY(c, hipGetLastError());
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  st->status = 0;
-  st->err_off = -1;
-  st->bit_in_byte = 0;
-  st->total_in = st->total_out = 0;
-  return FLATE_HIP_OK;
-}
-
-void flate_hip_inflate_stream_free(flate_hip_inflate_stream *st) {
-  if (!st) return;
-  (void)hipSetDevice(st->ctx->device);
-  delete st;
-}
-
-int flate_hip_inflate_stream_read(flate_hip_inflate_stream *st, const uint8_t *in, uint64_t in_len, int final_in,
-                                  uint8_t *out, uint64_t out_cap, uint64_t *in_used, uint64_t *out_len,
-                                  int64_t *err_off) {
-  if (!st || !in_used || !out_len || (in_len && !in) || (out_cap && !out)) return FLATE_HIP_E_INVALID;
-  *in_used = *out_len = 0;
-  if (err_off) *err_off = st->err_off;
-  if (st->status) return st->status == 1 ? FLATE_HIP_STREAM_END : st->status;  // sticky (Decompressor.err, inflate.mbt:285,398)
-  // the byte that holds the next unconsumed bit was reported as unused: it has to be here again
-  if (st->bit_in_byte && in_len == 0) return final_in ? FLATE_HIP_E_UNEXPECTED_EOF : FLATE_HIP_OK;
-  if (in_len == 0 && !final_in) return FLATE_HIP_OK;  // nothing to decode from
-  flate_hip_ctx *c = st->ctx;
-  c->hip_err.clear();
-  HIP_TRY(c, hipSetDevice(c->device));
-  // one call takes at most 1 GiB each way (32-bit positions inside the kernel); more input than that is
-  // simply not all used, and not final
-  const uint64_t kPiece = 1ull << 30;
-  if (in_len > kPiece) {
-    in_len = kPiece;
-    final_in = 0;
-  }
-  if (out_cap > kPiece) out_cap = kPiece;
-  int rc;
-  if ((rc = ensure(c, st->in, in_len + 16))) return rc;
-  if ((rc = ensure(c, st->out, out_cap + 16))) return rc;
-  if (in_len) HIP_TRY(c, hipMemcpyAsync(st->in.p, in, in_len, hipMemcpyHostToDevice, c->stream));
-  hipLaunchKernelGGL(inflate_stream_kernel, dim3(1), dim3(64), 0, c->stream, st->state.p, (const uint8_t *)st->in.p,
-                     (uint32_t)in_len, final_in ? 1u : 0u, (uint8_t *)st->out.p, (uint32_t)out_cap);
-  HIP_TRY(c, hipGetLastError());
-  InfStreamResult r{};
-  HIP_TRY(c, hipMemcpyAsync(&r, st->state.p, sizeof r, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  if (r.out_len > out_cap || r.in_used > in_len) return FLATE_HIP_E_INTERNAL;
-  if (r.out_len) {
-    HIP_TRY(c, hipMemcpyAsync(out, st->out.p, r.out_len, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-  }
-  *in_used = r.in_used;
-  *out_len = r.out_len;
-  st->bit_in_byte = r.bit_in_byte;
-  st->total_in = r.total_in;
-  st->total_out = r.total_out;
-  if (r.status) {
-    st->status = r.status;
-    st->err_off = r.err_off;
-    if (err_off) *err_off = r.err_off;
-    return r.status == 1 ? FLATE_HIP_STREAM_END : r.status;
-  }
-  return FLATE_HIP_OK;
-}
-
 int flate_hip_lz77_matches(flate_hip_ctx *c, const uint8_t *in, const uint64_t *in_off, uint32_t n,
                            uint32_t flags, uint32_t *n_chunks, uint64_t *n_recs_cap,
                            uint32_t *chunk_nmatch, uint64_t *chunk_rec_off, uint32_t *recs) {
@@ -1798,363 +1494,10 @@ int flate_hip_debug_lz_stamps(flate_hip_ctx *c, uint64_t *out, uint32_t max_chun
 
 }  // extern "C"
 
-// Preset dictionaries of a launch (flate_hip_inflate_batch_dict): the device tails and, per stream of the
-// launch, where its tail starts and how long it is (0 = none); h_len: the same lengths on the host.
-struct InfDict {
-  const uint8_t *buf;
-  const uint64_t *at;
-  const uint32_t *len;
-  const uint32_t *h_len;
-};
-
-// The container of flate_hip_inflate_batch_framed (frame_kernels.hip: frame_parse_kernel / frame_verdict_kernel);
-// everything here is the caller's.
-struct InfFrame {
-  uint32_t wrap;             // FLATE_HIP_WRAP_ZLIB / _GZIP
-  const uint8_t *dicts;      // the WHOLE dictionaries (host, or device under FLATE_HIP_DEVICE_PTRS) ...
-  const uint64_t *dict_off;  // ... dictionary j = dicts[dict_off[j], dict_off[j+1])
-  uint32_t n_dicts;
-  uint32_t *dict_used;       // host, per member (may be null): the dictionary its DICTID chose
-};
-
-// The container of flate_hip_inflate_spliced_framed: ONE member around the spliced stream (frame_kernels.hip:
-// frame_rebase_kernel / frame_verdict_spliced_kernel).  The member's verdict comes back here.
-struct InfMember {
-  uint32_t wrap;  // FLATE_HIP_WRAP_ZLIB / _GZIP
-  int32_t status = 0;
-  int64_t err_off = -1;
-};
-
-struct DictSlots;
-static DictSlots dict_slots(const uint64_t *dict_off, uint32_t n_dicts, const uint32_t *dict_of, uint32_t n,
-                            uint32_t min_len);
-static int dict_upload(flate_hip_ctx *c, const DictSlots &S, const uint8_t *dicts, const uint64_t *dict_off,
-                       uint32_t flags);
-static int inflate_frame_prepare(flate_hip_ctx *c, const InfFrame &FRD, const uint8_t *d_in, uint32_t n, uint32_t flags,
-                                 InfParams &I, FrameReadParams &R, bool &dict);
-static int inflate_member_prepare(flate_hip_ctx *c, const InfMember &SM, const uint8_t *d_in, uint64_t in_len, uint32_t n,
-                                  InfParams &I, FrameSplicedParams &S);
-
-// Both decode entry points.  spliced_len != 0: `in` is ONE stream of that many bytes and in_off
-// holds the bit positions of its n pieces (flate_hip_inflate_spliced).  D != NULL: the streams'
-// dictionaries (a launch in which a stream has one runs the decoder's dictionary build).  FRD != NULL: the streams are
-// members of a container (flate_hip_inflate_batch_framed): parsed in front of the decoder, checked behind it.
-// SM != NULL (with spliced_len): `in` is ONE member of spliced_len bytes around the spliced stream and in_off is counted
-// from the raw stream's first byte (flate_hip_inflate_spliced_framed); the return value is the member's status.
-static int inflate_common(flate_hip_ctx *c, const uint8_t *in, const uint64_t *in_off, uint32_t n,
-                          uint8_t *out, const uint64_t *out_off, uint64_t *out_len, int32_t *status,
-                          int64_t *err_off, uint32_t flags, uint64_t spliced_len, const InfDict *D = nullptr,
-                          const InfFrame *FRD = nullptr, InfMember *SM = nullptr) {
-  const bool spliced = spliced_len != 0;
-  const bool size_only = (flags & FLATE_HIP_SIZE_ONLY) != 0 && !spliced;
-  const uint64_t in_bytes = spliced ? spliced_len : in_off[n];
-  HIP_TRY(c, hipSetDevice(c->device));
-  const bool dev = (flags & FLATE_HIP_DEVICE_PTRS) != 0;
-  int rc;
-  const uint8_t *d_in = in;
-  uint8_t *d_out = out;
-  std::vector<uint64_t> no_slots;
-  if (size_only) {  // nothing is stored: no output buffer, no slots
-    no_slots.assign((size_t)n + 1, 0);
-    out_off = no_slots.data();
-  }
-  if (!dev) {
-    if ((rc = ensure(c, c->d_in, in_bytes + 16))) return rc;
-    if ((rc = ensure(c, c->d_out, out_off[n] + 16))) return rc;
-    HIP_TRY(c, hipMemcpyAsync(c->d_in.p, in, in_bytes, hipMemcpyHostToDevice, c->stream));
-    d_in = (const uint8_t *)c->d_in.p;
-    d_out = (uint8_t *)c->d_out.p;
-  }
-  if ((rc = ensure(c, c->d_in_off, ((size_t)n + 1) * 8))) return rc;
-  if ((rc = ensure(c, c->d_slot_off, ((size_t)n + 1) * 8))) return rc;
-  if ((rc = ensure(c, c->d_out_len, (size_t)n * 8 + 8))) return rc;
-  if ((rc = ensure(c, c->d_istatus, (size_t)n * 4 + 4))) return rc;
-  if ((rc = ensure(c, c->d_ierr, (size_t)n * 8 + 8))) return rc;
-  // (a member call: the index arrays of its two runs of checksums -- the DICTIDs, what the decoder produced -- and
-  // the dictionaries' tails travel the same way)
-  std::vector<uint64_t> f_doff;  // the dictionaries counted from the first one's start
-  size_t f_up = 0;
-  if (FRD) {
-    f_doff.assign((size_t)FRD->n_dicts + 1, 0);
-    for (uint32_t j = 1; j <= FRD->n_dicts; ++j) f_doff[j] = FRD->dict_off[j] - FRD->dict_off[0];
-    f_up = checksum_ctl_up_bytes(f_doff.data(), FRD->n_dicts) + (size_t)FRD->n_dicts * 12 + 1024;
-    if (!size_only) f_up += checksum_ctl_up_bytes(out_off, n);
-  }
-  if (SM) f_up = checksum_ctl_up_bytes(out_off, n) + sizeof(FrameOne) + 1024;
-  if ((rc = ctl_begin(c, ((size_t)n + 1) * 16 + f_up, (size_t)n * (FRD ? 24 : 20) + 64 + (FRD ? 256 : 0) + (SM ? 1024 : 0))))
-    return rc;
-  if ((rc = ctl_up(c, c->d_in_off.p, in_off, ((size_t)n + 1) * 8))) return rc;
-  if ((rc = ctl_up(c, c->d_slot_off.p, out_off, ((size_t)n + 1) * 8))) return rc;
-  InfParams I{};
-  I.in = d_in;
-  I.in_off = (const uint64_t *)c->d_in_off.p;
-  I.out = d_out;
-  I.out_off = (const uint64_t *)c->d_slot_off.p;
-  I.out_len = (uint64_t *)c->d_out_len.p;
-  I.status = (int32_t *)c->d_istatus.p;
-  I.err_off = (int64_t *)c->d_ierr.p;
-  I.n_streams = n;
-  I.bit_off = spliced ? (const uint64_t *)c->d_in_off.p : nullptr;
-  I.in_len = in_bytes;
-  I.size_only = size_only ? 1u : 0u;
-  bool dict = false;
-  if (D) {
-    I.dict_buf = D->buf;
-    I.dict_at = D->at;
-    I.dict_len = D->len;
-    for (uint32_t i = 0; i < n && !dict; ++i) dict = D->h_len[i] != 0;
-  }
-  FrameReadParams R{};
-  if (FRD) {
-    // both runs of checksums carve slot 0 of the scratch: sized once for the larger, so that the second does not free
-    // what the first's kernels are still to read
-    const size_t sa = checksum_scratch_bytes(f_doff.data(), FRD->n_dicts);
-    const size_t sb = size_only ? 0 : checksum_scratch_bytes(out_off, n);
-    void *unused = nullptr;
-    if ((rc = ctx_scratch(c, 0, sa > sb ? sa : sb, &unused))) return rc;
-    if (FRD->n_dicts) {
-      const uint64_t bytes = f_doff[FRD->n_dicts];
-      const uint8_t *d_whole = FRD->dicts ? FRD->dicts + FRD->dict_off[0] : nullptr;
-      if (!dev) {  // (for the DICTIDs the whole dictionaries are uploaded, not only their tails)
-        if ((rc = ensure(c, c->d_frame_dicts, bytes + 16))) return rc;
-        if (bytes) HIP_TRY(c, hipMemcpyAsync(c->d_frame_dicts.p, d_whole, bytes, hipMemcpyHostToDevice, c->stream));
-        d_whole = (const uint8_t *)c->d_frame_dicts.p;
-      }
-      if ((rc = ensure(c, c->d_frame_ids, (size_t)FRD->n_dicts * 4 + 4))) return rc;
-      if ((rc = checksum_device(c, d_whole, f_doff.data(), FRD->n_dicts, FLATE_HIP_CHECKSUM_ADLER32,
-                                (uint32_t *)c->d_frame_ids.p, -1)))
-        return rc;
-    }
-    if ((rc = inflate_frame_prepare(c, *FRD, d_in, n, flags, I, R, dict))) return rc;
-    hipLaunchKernelGGL(frame_parse_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, R);
-  }
-  FrameSplicedParams S{};
-  if (SM) {
-    // the one header is parsed where the member lies, and the index follows it there: the decoders below read the
-    // member from its first byte up to its trailer
-    if ((rc = inflate_member_prepare(c, *SM, d_in, in_bytes, n, I, S))) return rc;
-  }
-  {
-    StageTimer t(c, FLATE_HIP_STAGE_INFLATE);
-    // large batches: one lane per stream (64 streams per wavefront); small ones: one wavefront
-    // per stream
-    // (its bit positions are 32-bit: every compressed stream must be < 256 MiB)
-    // (size-only passes never use the lane-per-stream decoder: it reads its history back from the
-    // output it has written)
-    bool simt = (spliced || n >= c->inflate_simt_min) && !size_only;
-    for (uint32_t i = 0; i < n && simt && !spliced; ++i) simt = in_off[i + 1] - in_off[i] < (1ull << 28);
-    // (a size-only pass needs token lengths only: the sub-block decoder at any batch size, unless switched off)
-    bool spec = c->inflate_spec == 2 || (c->inflate_spec == 1 && (size_only || n < c->inflate_spec_max));
-    // 32-bit bit positions: a stream (a piece of a spliced stream: in_off holds bit offsets then) below 256 MiB
-    for (uint32_t i = 0; i < n && spec; ++i) spec = in_off[i + 1] - in_off[i] < (spliced ? (1ull << 31) : (1ull << 28));
-    if (spec) {
-      // (two builds of the same kernel: long token lists and a 16 KiB history ring while a SIMD holds
-      // one wavefront, the small footprint beyond)
-      const int shape = c->inflate_spec_shape ? c->inflate_spec_shape : (n <= 4u * c->num_cus ? 1 : 2);
-      void (*k)(InfParams) = shape == 1 ? (dict ? inflate_spec_dict_kernel<FLATE_SPEC_SMALL> : inflate_spec_kernel<FLATE_SPEC_SMALL>)
-                                        : (dict ? inflate_spec_dict_kernel<FLATE_SPEC_LARGE> : inflate_spec_kernel<FLATE_SPEC_LARGE>);
-      hipLaunchKernelGGL(k, dim3(n), dim3(64), 0, c->stream, I);
-    } else if (simt) {
-      // streams per wavefront
-      int lpw = c->inflate_lanes;
-      // (measured, same file: 16 lanes per wavefront up to ~20 k streams, 32 up to ~36 k, 64 beyond)
-      if (lpw == 0) lpw = n >= 144u * c->num_cus ? 64 : (n >= 80u * c->num_cus ? 32 : 16);
-      // (the output row -- a lane's output collected in registers and stored as whole aligned pieces -- pays
-      // where the chip is full of lanes: the 64-lane form only)
-      void (*k)(InfParams);
-      if (lpw == 64 && c->inflate_row == 16)
-        k = dict ? inflate_simt_dict_kernel<64, 16> : inflate_simt_kernel<64, 16>;
-      else if (lpw == 64 && c->inflate_row == 8)
-        k = dict ? inflate_simt_dict_kernel<64, 8> : inflate_simt_kernel<64, 8>;
-      else if (lpw == 64)
-        k = dict ? inflate_simt_dict_kernel<64, 0> : inflate_simt_kernel<64, 0>;
-      else if (lpw == 32)
-        k = dict ? inflate_simt_dict_kernel<32, 0> : inflate_simt_kernel<32, 0>;
-      else
-        k = dict ? inflate_simt_dict_kernel<16, 0> : inflate_simt_kernel<16, 0>;
-      const uint32_t sblocks = (n + (uint32_t)lpw - 1) / (uint32_t)lpw;
-      // A CU holds eight of these wavefronts (320 B of LDS per lane): a batch of more blocks than
-      // that runs in ROUNDS, and a lane's rate depends little on how full the chip is -- so the rounds
-      // are made equal (196608 streams: two launches of 98304 = 94 ms, against 60 + 47 for a full
-      // round and a third of one).
-      const uint32_t slots = 8u * c->num_cus;
-      const uint32_t rounds = (sblocks + slots - 1) / slots;
-      const uint32_t per = (sblocks + rounds - 1) / (rounds ? rounds : 1u);
-      if ((rc = ensure(c, c->d_simt_lens, inflate_simt_lens_bytes(per)))) return rc;
-      I.simt_lens = (uint32_t *)c->d_simt_lens.p;
-      for (uint32_t b0 = 0; b0 < sblocks; b0 += per) {
-        const uint32_t nb = sblocks - b0 < per ? sblocks - b0 : per;
-        I.sid0 = b0 * (uint32_t)lpw;
-        hipLaunchKernelGGL(k, dim3(nb), dim3(64), inflate_simt_lds_bytes(lpw), c->stream, I);
-      }
-    } else {
-      hipLaunchKernelGGL(dict ? inflate_dict_kernel : inflate_kernel, dim3(n), dim3(64), 0, c->stream, I);
-    }
-  }
-  HIP_TRY(c, hipGetLastError());
-  if (FRD) {
-    // the sums of what every member produced (nothing is stored by a size-only pass: nothing to sum), then the verdict
-    StageTimer t(c, FLATE_HIP_STAGE_CHECKSUM);
-    if (!size_only) {
-      if ((rc = ensure(c, c->d_frame_sums, (size_t)n * 4 + 8))) return rc;
-      if ((rc = checksum_device_clipped(c, d_out, out_off, n,
-                                        FRD->wrap == FLATE_HIP_WRAP_GZIP ? FLATE_HIP_CHECKSUM_CRC32 : FLATE_HIP_CHECKSUM_ADLER32,
-                                        (const uint64_t *)c->d_out_len.p, (const int32_t *)c->d_istatus.p,
-                                        (const uint32_t *)c->d_rd_bad.p, (uint32_t *)c->d_frame_sums.p)))
-        return rc;
-      R.sums = (const uint32_t *)c->d_frame_sums.p;
-    }
-    hipLaunchKernelGGL(frame_verdict_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, R);
-    HIP_TRY(c, hipGetLastError());
-    if (FRD->dict_used && (rc = ctl_down(c, FRD->dict_used, c->d_rd_dict.p, (size_t)n * 4))) return rc;
-  }
-  if (SM) {
-    // the sums of what every piece produced, their join into the member's, then the verdict
-    StageTimer t(c, FLATE_HIP_STAGE_CHECKSUM);
-    const uint32_t kind = SM->wrap == FLATE_HIP_WRAP_GZIP ? FLATE_HIP_CHECKSUM_CRC32 : FLATE_HIP_CHECKSUM_ADLER32;
-    if ((rc = checksum_device_clipped(c, d_out, out_off, n, kind, (const uint64_t *)c->d_out_len.p,
-                                      (const int32_t *)c->d_istatus.p, (const uint32_t *)c->d_rd_bad.p,
-                                      (uint32_t *)c->d_frame_sums.p)))
-      return rc;
-    if ((rc = checksum_join_device(c, (const uint32_t *)c->d_frame_sums.p, (const uint64_t *)c->d_slot_off.p,
-                                   (const uint64_t *)c->d_out_len.p, n, kind, &S.one->sum, &S.one->total)))
-      return rc;
-    hipLaunchKernelGGL(frame_verdict_spliced_kernel, dim3(1), dim3(1024), 0, c->stream, S);
-    HIP_TRY(c, hipGetLastError());
-    if ((rc = ctl_down(c, &SM->status, &S.one->member_status, 4))) return rc;
-    if ((rc = ctl_down(c, &SM->err_off, &S.one->member_err_off, 8))) return rc;
-  }
-  if ((rc = ctl_down(c, out_len, c->d_out_len.p, (size_t)n * 8))) return rc;
-  if ((rc = ctl_down(c, status, c->d_istatus.p, (size_t)n * 4))) return rc;
-  if ((rc = ctl_down(c, err_off, c->d_ierr.p, (size_t)n * 8))) return rc;
-  if (!dev && !size_only)
-    HIP_TRY(c, hipMemcpyAsync(out, c->d_out.p, out_off[n], hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipGetLastError());
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  ctl_finish(c);
-  const bool used[FLATE_HIP_STAGE_COUNT] = {false, false, FRD != nullptr || SM != nullptr, true};
-  if ((rc = collect_timing(c, used))) return rc;
-  // A size-only pass has no capacity -- but the kernels count output in 32 bits: a stream that inflates
-  // to 4 GiB or more stops there with "slot too small", which for a call without slots means "too large"
-  if (size_only)
-    for (uint32_t i = 0; i < n; ++i)
-      if (status[i] == FLATE_HIP_E_OUT_TOO_SMALL) status[i] = FLATE_HIP_E_TOO_LARGE;
-  if (SM) return SM->status;  // (the first non-zero piece status, or the trailer's verdict with every piece at 0)
-  for (uint32_t i = 0; i < n; ++i)
-    if (status[i]) return status[i];
-  return FLATE_HIP_OK;
-}
-
-// Host-pointer inflate of independent streams, pipelined like deflate_host_pipelined: every
-// stream has its own input range and output slot, so a group is a contiguous range of both.
-static int inflate_host_pipelined(flate_hip_ctx *c, const uint8_t *in, const uint64_t *in_off, uint32_t n,
-                                  uint8_t *out, const uint64_t *out_off, uint64_t *out_len,
-                                  int32_t *status, int64_t *err_off, uint32_t flags, uint32_t G,
-                                  const InfDict *D) {
-  HIP_TRY(c, hipSetDevice(c->device));
-  int rc;
-  if ((rc = ensure(c, c->d_in, in_off[n] + 16))) return rc;
-  if ((rc = ensure(c, c->d_out, out_off[n] + 16))) return rc;
-  if ((rc = host_pipe_streams(c))) return rc;
-  uint8_t *d_in = (uint8_t *)c->d_in.p, *d_out = (uint8_t *)c->d_out.p;
-  std::vector<uint32_t> lo(G + 1);
-  std::vector<CopyJob> in_jobs(G);
-  cut_by_bytes(in_off, out_off, n, G, lo);  // by input + output bytes (both cross PCIe)
-  for (uint32_t g = 0; g < G; ++g)
-    in_jobs[g] = {d_in + in_off[lo[g]], in + in_off[lo[g]], (size_t)(in_off[lo[g + 1]] - in_off[lo[g]])};
-  const double t_call = host_now_ms();
-  CopyPipe pipe(G, G);
-  pipe.start(c->device, c->h2d_stream, c->d2h_stream, in_jobs);
-  float stage_sum[FLATE_HIP_STAGE_COUNT] = {0, 0, 0, 0};
-  std::vector<uint64_t> gin, gout;
-  rc = FLATE_HIP_OK;
-  int first_status = FLATE_HIP_OK;
-  for (uint32_t g = 0; g < G; ++g) {
-    if (!pipe.wait_in(g)) {
-      rc = FLATE_HIP_E_HIP;
-      break;
-    }
-    const uint32_t a = lo[g], cnt = lo[g + 1] - lo[g];
-    gin.resize((size_t)cnt + 1);
-    gout.resize((size_t)cnt + 1);
-    for (uint32_t i = 0; i <= cnt; ++i) {
-      gin[i] = in_off[a + i] - in_off[a];
-      gout[i] = out_off[a + i] - out_off[a];
-    }
-    if (cnt) {
-      const double ta = host_now_ms();
-      InfDict gd{};  // (the group's slice of the per-stream dictionary arrays)
-      if (D) gd = {D->buf, D->at + a, D->len + a, D->h_len + a};
-      const int r = inflate_common(c, d_in + in_off[a], gin.data(), cnt, d_out + out_off[a], gout.data(),
-                                   out_len + a, status + a, err_off + a, flags | FLATE_HIP_DEVICE_PTRS, 0,
-                                   D ? &gd : nullptr);
-      host_trace(t_call, "compute", g, ta, host_now_ms());
-      // a stream's own failure (its status, also the return value) does not stop the batch: as in
-      // one pass, every stream is decoded and the first failing status is what the call returns
-      const bool stream_status = r == FLATE_HIP_E_CORRUPT || r == FLATE_HIP_E_UNEXPECTED_EOF ||
-                                 r == FLATE_HIP_E_OUT_TOO_SMALL;
-      if (r != FLATE_HIP_OK && !stream_status) {
-        rc = r;
-        break;
-      }
-      if (first_status == FLATE_HIP_OK) first_status = r;
-      for (int k = 0; k < FLATE_HIP_STAGE_COUNT; ++k) stage_sum[k] += c->stage_ms[k];
-    }
-    pipe.post_out(g, {out + out_off[a], d_out + out_off[a], (size_t)gout[cnt]});
-  }
-  const std::string err = pipe.finish();
-  if (rc == FLATE_HIP_OK) rc = first_status;
-  if ((rc == FLATE_HIP_OK || rc == first_status) && !err.empty()) rc = FLATE_HIP_E_HIP;
-  if (rc == FLATE_HIP_E_HIP && c->hip_err.empty()) c->hip_err = err;
-  for (int k = 0; k < FLATE_HIP_STAGE_COUNT; ++k) c->stage_ms[k] = stage_sum[k];
-  return rc;
-}
-
-// The argument checks of flate_hip_inflate_batch(_dict) (no HIP call): the pointers ...
-static bool inflate_batch_ptrs_ok(flate_hip_ctx *c, const uint8_t *in, const uint64_t *in_off, uint32_t n,
-                                  uint8_t *out, const uint64_t *out_off, uint64_t *out_len,
-                                  int32_t *status, int64_t *err_off, uint32_t flags) {
-  const bool size_only = (flags & FLATE_HIP_SIZE_ONLY) != 0;
-  return c && in_off && out_len && status && err_off && (!n || in) && (size_only || (out_off && (!n || out)));
-}
-// ... and the streams' offsets and sizes
-static int inflate_batch_ranges(const uint64_t *in_off, uint32_t n, const uint64_t *out_off, uint32_t flags) {
-  const bool size_only = (flags & FLATE_HIP_SIZE_ONLY) != 0;
-  for (uint32_t i = 0; i < n; ++i)
-    if (in_off[i + 1] < in_off[i] || (!size_only && out_off[i + 1] < out_off[i])) return FLATE_HIP_E_INVALID;
-  for (uint32_t i = 0; i < n; ++i)
-    if (in_off[i + 1] - in_off[i] >= 0x7ffe0000ull) return FLATE_HIP_E_TOO_LARGE;
-  return FLATE_HIP_OK;
-}
-
-// The dictionary arguments of flate_hip_inflate_batch_dict / flate_hip_deflate_fast_batch_dict (no HIP call)
-static bool dict_args_ok(const uint8_t *dicts, const uint64_t *dict_off, uint32_t n_dicts, const uint32_t *dict_of,
-                         uint32_t n) {
-  if (n_dicts && !dict_off) return false;
-  if (!dict_of && n_dicts == 0) return false;
-  for (uint32_t j = 0; j < n_dicts; ++j)
-    if (dict_off[j + 1] < dict_off[j]) return false;
-  if (n_dicts && dict_off[n_dicts] > dict_off[0] && !dicts) return false;
-  if (dict_of)
-    for (uint32_t i = 0; i < n; ++i)
-      if (dict_of[i] >= n_dicts && dict_of[i] != FLATE_HIP_NO_DICT) return false;
-  return true;
-}
-
-// The dictionaries a *_batch_dict call uses, as slots: a slot is one dictionary that some stream names and whose
-// tail -- its last kMaxMatchOffset bytes, the history a stream can reach -- has at least min_len bytes.  The tails
-// lie one after another in c->d_dicts, each 16-byte aligned and followed by 16 bytes that a 16-byte load may touch.
-struct DictSlots {
-  static constexpr uint32_t kNone = ~0u;
-  std::vector<uint32_t> dict, len;  // per slot: the dictionary, the length of its tail
-  std::vector<uint64_t> at;         // per slot: where the tail starts in d_dicts
-  std::vector<uint32_t> slot_of;    // per stream: its slot, or kNone
-  uint64_t total = 0;               // bytes of d_dicts
-};
+namespace flate_host {
 
 // (host only, after dict_args_ok: the entry points make every check before any HIP call)
-static DictSlots dict_slots(const uint64_t *dict_off, uint32_t n_dicts, const uint32_t *dict_of, uint32_t n,
-                            uint32_t min_len) {
+DictSlots dict_slots(const uint64_t *dict_off, uint32_t n_dicts, const uint32_t *dict_of, uint32_t n, uint32_t min_len) {
   DictSlots S;
   S.slot_of.assign(n, DictSlots::kNone);
   std::vector<uint32_t> slot_of_dict(n_dicts, DictSlots::kNone);
@@ -2177,8 +1520,7 @@ static DictSlots dict_slots(const uint64_t *dict_off, uint32_t n_dicts, const ui
 }
 
 // the slots' tails into c->d_dicts (on c->stream; the caller synchronises)
-static int dict_upload(flate_hip_ctx *c, const DictSlots &S, const uint8_t *dicts, const uint64_t *dict_off,
-                       uint32_t flags) {
+int dict_upload(flate_hip_ctx *c, const DictSlots &S, const uint8_t *dicts, const uint64_t *dict_off, uint32_t flags) {
   const int rc = ensure(c, c->d_dicts, S.total);
   if (rc) return rc;
   const hipMemcpyKind kind = (flags & FLATE_HIP_DEVICE_PTRS) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
@@ -2188,181 +1530,27 @@ static int dict_upload(flate_hip_ctx *c, const DictSlots &S, const uint8_t *dict
   return FLATE_HIP_OK;
 }
 
-// The device side of a member call in front of its parse kernel: the arrays that kernel fills, and -- the host cannot
-// know which dictionaries the members name before the device has parsed -- the tail of EVERY non-empty dictionary,
-// staged as for flate_hip_inflate_batch_dict.  The decoders read the raw streams' ranges and their dictionaries from
-// what the parse kernel writes; `dict`: run their dictionary build (whenever a non-empty dictionary is passed).
-static int inflate_frame_prepare(flate_hip_ctx *c, const InfFrame &FRD, const uint8_t *d_in, uint32_t n, uint32_t flags,
-                                 InfParams &I, FrameReadParams &R, bool &dict) {
+// (the byte counts depend on the dictionaries' lengths only: the offsets as the caller has them will do)
+size_t dictid_ctl_up_bytes(const uint64_t *dict_off, uint32_t n_dicts) { return checksum_ctl_up_bytes(dict_off, n_dicts); }
+size_t dictid_scratch_bytes(const uint64_t *dict_off, uint32_t n_dicts) { return checksum_scratch_bytes(dict_off, n_dicts); }
+
+int dictid_stage(flate_hip_ctx *c, const uint8_t *dicts, const uint64_t *dict_off, uint32_t n_dicts, uint32_t flags) {
   int rc;
-  if ((rc = ensure(c, c->d_frame_off, ((size_t)n + 1) * 8))) return rc;
-  if ((rc = ensure(c, c->d_rd_end, (size_t)n * 8 + 8))) return rc;
-  if ((rc = ensure(c, c->d_rd_want, (size_t)n * 4 + 4))) return rc;
-  if ((rc = ensure(c, c->d_rd_isize, (size_t)n * 4 + 4))) return rc;
-  if ((rc = ensure(c, c->d_rd_bad, (size_t)n * 4 + 4))) return rc;
-  if ((rc = ensure(c, c->d_rd_dict, (size_t)n * 4 + 4))) return rc;
-  R.in = d_in;
-  R.in_off = (const uint64_t *)c->d_in_off.p;
-  R.n_streams = n;
-  R.wrap = FRD.wrap;
-  R.n_dicts = FRD.n_dicts;
-  R.pay_off = (uint64_t *)c->d_frame_off.p;
-  R.pay_end = (uint64_t *)c->d_rd_end.p;
-  R.want = (uint32_t *)c->d_rd_want.p;
-  R.isize = (uint32_t *)c->d_rd_isize.p;
-  R.bad = (uint32_t *)c->d_rd_bad.p;
-  R.dict_used = (uint32_t *)c->d_rd_dict.p;
-  R.out_len = I.out_len;
-  R.status = I.status;
-  R.err_off = I.err_off;
-  if (FRD.n_dicts) {
-    std::vector<uint32_t> every(FRD.n_dicts);
-    for (uint32_t j = 0; j < FRD.n_dicts; ++j) every[j] = j;
-    const DictSlots S = dict_slots(FRD.dict_off, FRD.n_dicts, every.data(), FRD.n_dicts, 1);
-    std::vector<uint64_t> t_at(FRD.n_dicts, 0);
-    std::vector<uint32_t> t_len(FRD.n_dicts, 0);
-    for (uint32_t j = 0; j < FRD.n_dicts; ++j) {
-      if (S.slot_of[j] == DictSlots::kNone) continue;
-      t_at[j] = S.at[S.slot_of[j]];
-      t_len[j] = S.len[S.slot_of[j]];
-    }
-    if ((rc = dict_upload(c, S, FRD.dicts, FRD.dict_off, flags))) return rc;
-    if ((rc = ensure(c, c->d_rd_tail_at, (size_t)FRD.n_dicts * 8 + 8))) return rc;
-    if ((rc = ensure(c, c->d_rd_tail_len, (size_t)FRD.n_dicts * 4 + 4))) return rc;
-    if ((rc = ensure(c, c->d_dict_at, (size_t)n * 8 + 8))) return rc;
-    if ((rc = ensure(c, c->d_dict_len, (size_t)n * 4 + 4))) return rc;
-    if ((rc = ctl_up(c, c->d_rd_tail_at.p, t_at.data(), (size_t)FRD.n_dicts * 8))) return rc;
-    if ((rc = ctl_up(c, c->d_rd_tail_len.p, t_len.data(), (size_t)FRD.n_dicts * 4))) return rc;
-    R.dict_id = (const uint32_t *)c->d_frame_ids.p;
-    R.tail_at = (const uint64_t *)c->d_rd_tail_at.p;
-    R.tail_len = (const uint32_t *)c->d_rd_tail_len.p;
-    R.dict_at = (uint64_t *)c->d_dict_at.p;
-    R.dict_len = (uint32_t *)c->d_dict_len.p;
-    dict = !S.at.empty();
-    if (dict) {
-      I.dict_buf = (const uint8_t *)c->d_dicts.p;
-      I.dict_at = R.dict_at;
-      I.dict_len = R.dict_len;
-    }
+  if ((rc = ensure(c, c->d_frame_ids, (size_t)n_dicts * 4 + 4))) return rc;
+  if (!n_dicts) return FLATE_HIP_OK;
+  std::vector<uint64_t> rel((size_t)n_dicts + 1, 0);  // counted from the first dictionary's start
+  for (uint32_t j = 1; j <= n_dicts; ++j) rel[j] = dict_off[j] - dict_off[0];
+  const uint8_t *d_whole = dicts ? dicts + dict_off[0] : nullptr;
+  if (!(flags & FLATE_HIP_DEVICE_PTRS)) {
+    const uint64_t bytes = rel[n_dicts];
+    if ((rc = ensure(c, c->d_frame_dicts, bytes + 16))) return rc;
+    if (bytes) HIP_TRY(c, hipMemcpyAsync(c->d_frame_dicts.p, d_whole, bytes, hipMemcpyHostToDevice, c->stream));
+    d_whole = (const uint8_t *)c->d_frame_dicts.p;
   }
-  I.in_off = R.pay_off;
-  I.in_end = R.pay_end;
-  return FLATE_HIP_OK;
+  return checksum_device(c, d_whole, rel.data(), n_dicts, FLATE_HIP_CHECKSUM_ADLER32, (uint32_t *)c->d_frame_ids.p, -1);
 }
 
-// The device side of flate_hip_inflate_spliced_framed in front of its decoder: frame_parse_kernel over the one range
-// {0, in_len}, then frame_rebase_kernel, which moves the uploaded index (I.in_off, counted from the raw stream's first
-// byte) behind the header the device has just measured.  The decoders read the member up to its trailer.
-static int inflate_member_prepare(flate_hip_ctx *c, const InfMember &SM, const uint8_t *d_in, uint64_t in_len, uint32_t n,
-                                  InfParams &I, FrameSplicedParams &S) {
-  int rc;
-  if ((rc = ensure(c, c->d_rd_one, sizeof(FrameOne) + 16))) return rc;
-  if ((rc = ensure(c, c->d_frame_off, ((size_t)n + 1) * 8))) return rc;
-  if ((rc = ensure(c, c->d_frame_sums, (size_t)n * 4 + 8))) return rc;
-  if ((rc = ensure(c, c->d_rd_bad, (size_t)n * 4 + 4))) return rc;
-  FrameOne *one = (FrameOne *)c->d_rd_one.p;
-  const uint64_t range[2] = {0, in_len};
-  if ((rc = ctl_up(c, one->in_off, range, sizeof range))) return rc;
-  FrameReadParams R{};
-  R.in = d_in;
-  R.in_off = one->in_off;
-  R.n_streams = 1;
-  R.wrap = SM.wrap;
-  R.pay_off = one->pay_off;
-  R.pay_end = &one->pay_end;
-  R.want = &one->want;
-  R.isize = &one->isize;
-  R.bad = &one->bad;
-  R.dict_used = &one->dict_used;
-  hipLaunchKernelGGL(frame_parse_kernel, dim3(1), dim3(256), 0, c->stream, R);
-  S.one = one;
-  S.bit_in = I.in_off;
-  S.bit_out = (uint64_t *)c->d_frame_off.p;
-  S.piece_bad = (uint32_t *)c->d_rd_bad.p;
-  S.n_pieces = n;
-  S.wrap = SM.wrap;
-  S.in_len = in_len;
-  S.raw_end = in_len - (SM.wrap == FLATE_HIP_WRAP_GZIP ? 8u : 4u);  // (the entry point has checked in_len)
-  S.out_len = I.out_len;
-  S.status = I.status;
-  S.err_off = I.err_off;
-  hipLaunchKernelGGL(frame_rebase_kernel, dim3(n / 256 + 1), dim3(256), 0, c->stream, S);
-  HIP_TRY(c, hipGetLastError());
-  I.bit_off = S.bit_out;
-  I.in_len = S.raw_end;
-  return FLATE_HIP_OK;
-}
-
-// flate_hip_inflate_batch after its checks; D: the streams' dictionaries (flate_hip_inflate_batch_dict)
-static int inflate_batch_run(flate_hip_ctx *c, const uint8_t *in, const uint64_t *in_off, uint32_t n,
-                             uint8_t *out, const uint64_t *out_off, uint64_t *out_len,
-                             int32_t *status, int64_t *err_off, uint32_t flags, const InfDict *D) {
-  const bool size_only = (flags & FLATE_HIP_SIZE_ONLY) != 0;
-  if (size_only)
-    return inflate_common(c, in, in_off, n, nullptr, nullptr, out_len, status, err_off, flags, 0, D);
-  // host pointers and a large batch: decode group g while g+1 is copied in and g-1 out
-  if (!(flags & FLATE_HIP_DEVICE_PTRS) && c->host_groups > 1 &&
-      in_off[n] - in_off[0] + out_off[n] - out_off[0] >= (64ull << 20)) {
-    uint32_t G = (uint32_t)c->host_groups;
-    const uint32_t iper = 4u * c->host_group_streams;  // (a group should still fill the lane-per-stream launch: 16384)
-    if (n / iper < G) G = n / iper;
-    if (G > 1) {
-      try {
-        return inflate_host_pipelined(c, in, in_off, n, out, out_off, out_len, status, err_off, flags, G, D);
-      } catch (const std::exception &e) {  // (no copy threads, out of host memory): one pass instead
-        c->hip_err.clear();
-      }
-    }
-  }
-  return inflate_common(c, in, in_off, n, out, out_off, out_len, status, err_off, flags, 0, D);
-}
-
-extern "C" {
-
-int flate_hip_inflate_batch(flate_hip_ctx *c, const uint8_t *in, const uint64_t *in_off, uint32_t n,
-                            uint8_t *out, const uint64_t *out_off, uint64_t *out_len,
-                            int32_t *status, int64_t *err_off, uint32_t flags) {
-  if (!inflate_batch_ptrs_ok(c, in, in_off, n, out, out_off, out_len, status, err_off, flags)) return FLATE_HIP_E_INVALID;
-  c->hip_err.clear();
-  if (n == 0) return FLATE_HIP_OK;
-  const int rc = inflate_batch_ranges(in_off, n, out_off, flags);
-  return rc ? rc : inflate_batch_run(c, in, in_off, n, out, out_off, out_len, status, err_off, flags, nullptr);
-}
-
-int flate_hip_inflate_batch_dict(flate_hip_ctx *c, const uint8_t *in, const uint64_t *in_off, uint32_t n,
-                                 const uint8_t *dicts, const uint64_t *dict_off, uint32_t n_dicts,
-                                 const uint32_t *dict_of, uint8_t *out, const uint64_t *out_off,
-                                 uint64_t *out_len, int32_t *status, int64_t *err_off, uint32_t flags) {
-  // every check before any HIP call
-  if (!inflate_batch_ptrs_ok(c, in, in_off, n, out, out_off, out_len, status, err_off, flags)) return FLATE_HIP_E_INVALID;
-  int rc = inflate_batch_ranges(in_off, n, out_off, flags);
-  if (rc != FLATE_HIP_OK && rc != FLATE_HIP_E_TOO_LARGE) return rc;
-  if (!dict_args_ok(dicts, dict_off, n_dicts, dict_of, n)) return FLATE_HIP_E_INVALID;
-  // the history each stream starts with: the last kMaxMatchOffset bytes of its dictionary
-  const DictSlots S = dict_slots(dict_off, n_dicts, dict_of, n, 1);
-  if (S.at.empty())  // no stream has history in front of it: the plain call, its path and its results
-    return flate_hip_inflate_batch(c, in, in_off, n, out, out_off, out_len, status, err_off, flags);
-  c->hip_err.clear();
-  if (rc) return rc;
-  std::vector<uint64_t> h_at(n, 0);  // the decoders take {at, len} per stream (0 = none)
-  std::vector<uint32_t> h_len(n, 0);
-  for (uint32_t i = 0; i < n; ++i) {
-    if (S.slot_of[i] == DictSlots::kNone) continue;
-    h_at[i] = S.at[S.slot_of[i]];
-    h_len[i] = S.len[S.slot_of[i]];
-  }
-  HIP_TRY(c, hipSetDevice(c->device));
-  if ((rc = dict_upload(c, S, dicts, dict_off, flags))) return rc;
-  if ((rc = ensure(c, c->d_dict_at, (size_t)n * 8))) return rc;
-  if ((rc = ensure(c, c->d_dict_len, (size_t)n * 4))) return rc;
-  HIP_TRY(c, hipMemcpyAsync(c->d_dict_at.p, h_at.data(), (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(c->d_dict_len.p, h_len.data(), (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  const InfDict D{(const uint8_t *)c->d_dicts.p, (const uint64_t *)c->d_dict_at.p, (const uint32_t *)c->d_dict_len.p, h_len.data()};
-  return inflate_batch_run(c, in, in_off, n, out, out_off, out_len, status, err_off, flags, &D);
-}
-
-}  // extern "C"
+}  // namespace flate_host
 
 // flate_hip_deflate_fast_batch_dict; wrap != FLATE_HIP_WRAP_RAW: flate_hip_deflate_fast_batch_framed with dictionaries
 // (zlib members, the streams that name a dictionary with FDICT and its DICTID)
@@ -2436,8 +1624,8 @@ int flate_hip_deflate_fast_batch_dict(flate_hip_ctx *c, const uint8_t *in, const
 }
 
 size_t flate_hip_frame_overhead(uint32_t wrap, int with_dict) {
-  if (wrap == FLATE_HIP_WRAP_ZLIB) return with_dict ? 10 : 6;
-  return wrap == FLATE_HIP_WRAP_GZIP ? 18 : 0;
+  if (wrap != FLATE_HIP_WRAP_ZLIB && wrap != FLATE_HIP_WRAP_GZIP) return 0;
+  return frame_header_len(wrap, with_dict != 0) + frame_trailer_len(wrap);
 }
 
 int flate_hip_deflate_fast_batch_framed(flate_hip_ctx *c, const uint8_t *in, const uint64_t *in_off, uint32_t n,
@@ -2499,102 +1687,4 @@ int flate_hip_deflate_fast_spliced_framed(flate_hip_ctx *c, const uint8_t *in, c
     return FLATE_HIP_E_INTERNAL;
   }
 }
-
-int flate_hip_inflate_batch_framed(flate_hip_ctx *c, const uint8_t *in, const uint64_t *in_off, uint32_t n,
-                                   uint32_t wrap, const uint8_t *dicts, const uint64_t *dict_off, uint32_t n_dicts,
-                                   uint8_t *out, const uint64_t *out_off, uint64_t *out_len, int32_t *status,
-                                   int64_t *err_off, uint32_t *dict_used, uint32_t flags) {
-  // every check before any HIP call
-  if (!c || wrap > FLATE_HIP_WRAP_GZIP) return FLATE_HIP_E_INVALID;
-  const bool with_dicts = dicts || dict_off || n_dicts;
-  if (with_dicts && wrap != FLATE_HIP_WRAP_ZLIB) return FLATE_HIP_E_INVALID;  // (neither has a DICTID to choose by)
-  if (!inflate_batch_ptrs_ok(c, in, in_off, n, out, out_off, out_len, status, err_off, flags)) return FLATE_HIP_E_INVALID;
-  if (n_dicts && !dict_off) return FLATE_HIP_E_INVALID;
-  for (uint32_t j = 0; j < n_dicts; ++j)
-    if (dict_off[j + 1] < dict_off[j]) return FLATE_HIP_E_INVALID;
-  if (n_dicts && dict_off[n_dicts] > dict_off[0] && !dicts) return FLATE_HIP_E_INVALID;
-  if (wrap == FLATE_HIP_WRAP_RAW) {  // the raw call: its kernels, its results
-    const int rc = flate_hip_inflate_batch(c, in, in_off, n, out, out_off, out_len, status, err_off, flags);
-    if (dict_used && rc != FLATE_HIP_E_INVALID && rc != FLATE_HIP_E_TOO_LARGE)
-      for (uint32_t i = 0; i < n; ++i) dict_used[i] = FLATE_HIP_NO_DICT;
-    return rc;
-  }
-  c->hip_err.clear();
-  if (n == 0) return FLATE_HIP_OK;
-  const int rc = inflate_batch_ranges(in_off, n, out_off, flags);
-  if (rc) return rc;
-  try {
-    // (host pointers: one copy in, parse, decode, check, one copy out -- no "host_pipeline_groups")
-    const InfFrame FRD{wrap, dicts, dict_off, n_dicts, dict_used};
-    const bool size_only = (flags & FLATE_HIP_SIZE_ONLY) != 0;
-    return inflate_common(c, in, in_off, n, size_only ? nullptr : out, size_only ? nullptr : out_off, out_len, status,
-                          err_off, flags, 0, nullptr, &FRD);
-  } catch (const std::exception &e) {  // (out of host memory in an index vector)
-    c->hip_err = e.what();
-    return FLATE_HIP_E_INTERNAL;
-  }
-}
-
-int flate_hip_inflate_spliced(flate_hip_ctx *c, const uint8_t *in, uint64_t in_len,
-                              const uint64_t *bit_off, uint32_t n, uint8_t *out,
-                              const uint64_t *out_off, uint64_t *out_len, int32_t *status,
-                              int64_t *err_off, uint32_t flags) {
-  if (!c || !in || !in_len || !bit_off || !out_off || !out_len || !status || !err_off || (n && !out))
-    return FLATE_HIP_E_INVALID;
-  c->hip_err.clear();
-  if (n == 0) return FLATE_HIP_OK;
-  for (uint32_t i = 0; i < n; ++i) {
-    if (bit_off[i + 1] < bit_off[i] || out_off[i + 1] < out_off[i] || bit_off[i + 1] > in_len * 8)
-      return FLATE_HIP_E_INVALID;
-    if (bit_off[i + 1] - bit_off[i] >= (1ull << 30)) return FLATE_HIP_E_TOO_LARGE;  // piece < 128 MiB
-  }
-  return inflate_common(c, in, bit_off, n, out, out_off, out_len, status, err_off, flags, in_len);
-}
-
-// what a decode call returns when it has run: FLATE_HIP_OK or the first non-zero status of a stream
-static bool is_stream_status(int rc) {
-  return rc == FLATE_HIP_OK || rc == FLATE_HIP_E_OUT_TOO_SMALL || rc == FLATE_HIP_E_CORRUPT || rc == FLATE_HIP_E_UNEXPECTED_EOF;
-}
-
-int flate_hip_inflate_spliced_framed(flate_hip_ctx *c, const uint8_t *in, uint64_t in_len, uint32_t wrap,
-                                     const uint64_t *bit_off, uint32_t n, uint8_t *out, const uint64_t *out_off,
-                                     uint64_t *out_len, int32_t *status, int64_t *err_off, int32_t *member_status,
-                                     int64_t *member_err_off, uint32_t flags) {
-  // every check before any HIP call
-  if (!c || wrap > FLATE_HIP_WRAP_GZIP || (flags & FLATE_HIP_SIZE_ONLY)) return FLATE_HIP_E_INVALID;
-  if (wrap == FLATE_HIP_WRAP_RAW) {  // the raw call: its kernels, its results
-    const int rc = flate_hip_inflate_spliced(c, in, in_len, bit_off, n, out, out_off, out_len, status, err_off, flags);
-    if (!is_stream_status(rc)) return rc;  // (refused, or failed: no verdict)
-    int32_t first = 0;
-    for (uint32_t i = 0; i < n && !first; ++i) first = status[i];
-    if (member_status) *member_status = first;
-    if (member_err_off) *member_err_off = -1;
-    return rc;
-  }
-  if (!in || !in_len || !bit_off || !out_off || !out_len || !status || !err_off || (n && !out)) return FLATE_HIP_E_INVALID;
-  c->hip_err.clear();
-  if (n == 0) return FLATE_HIP_OK;
-  // the shortest header (2 / 10 bytes) and the trailer (4 / 8) must fit, and the index must end inside what is left
-  const uint64_t frame = wrap == FLATE_HIP_WRAP_GZIP ? 18u : 6u;
-  if (in_len < frame) return FLATE_HIP_E_INVALID;
-  for (uint32_t i = 0; i < n; ++i) {
-    if (bit_off[i + 1] < bit_off[i] || out_off[i + 1] < out_off[i] || bit_off[i + 1] > 8 * (in_len - frame))
-      return FLATE_HIP_E_INVALID;
-    if (bit_off[i + 1] - bit_off[i] >= (1ull << 30)) return FLATE_HIP_E_TOO_LARGE;  // piece < 128 MiB
-  }
-  try {
-    // (host pointers: one copy in, parse, decode, check, one copy out)
-    InfMember SM{wrap};
-    const int rc = inflate_common(c, in, bit_off, n, out, out_off, out_len, status, err_off, flags, in_len, nullptr,
-                                  nullptr, &SM);
-    if (!is_stream_status(rc)) return rc;  // (failed: no verdict was read back)
-    if (member_status) *member_status = SM.status;
-    if (member_err_off) *member_err_off = SM.err_off;
-    return rc;
-  } catch (const std::exception &e) {  // (out of host memory in an index vector)
-    c->hip_err = e.what();
-    return FLATE_HIP_E_INTERNAL;
-  }
-}
-
 }  // extern "C"

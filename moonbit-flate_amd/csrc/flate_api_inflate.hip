@@ -1,0 +1,720 @@
+// flate_api_inflate.hip -- the decode calls of the C ABI (see include/flate_hip.h): flate_hip_inflate_batch, _batch_dict,
+// _batch_framed, _spliced, _spliced_framed and the flate_hip_inflate_stream_* handle.
+//
+// One driver (inflate_common) serves the five batch calls as a sequence: stage the input and the index arrays, the
+// container's part in front of the decoders, the decoders (inflate_route.h says which; launch_decoders is the only
+// place that knows kernels), the container's part behind them, read back.  The argument checks are api_checks.h's; the
+// ctx, its staging and the host pipeline are flate_api.hip's (flate_ctx.h).
+#include "flate_ctx.h"
+
+#include <exception>
+#include <stdexcept>
+
+#include "api_checks.h"
+
+using namespace flate;
+using namespace flate_host;
+
+// One decode call as its entry point received and checked it.  spliced_len != 0: `in` is ONE stream (or one member
+// around it) of that many bytes and in_off holds the bit positions of its n pieces.
+struct InfCall {
+  const uint8_t *in;
+  const uint64_t *in_off;
+  uint32_t n;
+  uint8_t *out;
+  const uint64_t *out_off;
+  uint64_t *out_len;
+  int32_t *status;
+  int64_t *err_off;
+  uint32_t flags;
+  uint64_t spliced_len;
+};
+
+// Preset dictionaries of a launch (flate_hip_inflate_batch_dict): the device tails and, per stream of the
+// launch, where its tail starts and how long it is (0 = none); h_len: the same lengths on the host.
+struct InfDict {
+  const uint8_t *buf;
+  const uint64_t *at;
+  const uint32_t *len;
+  const uint32_t *h_len;
+};
+
+// The container of flate_hip_inflate_batch_framed (frame_kernels.hip: frame_parse_kernel / frame_verdict_kernel);
+// everything here is the caller's.
+struct InfFrame {
+  uint32_t wrap;             // FLATE_HIP_WRAP_ZLIB / _GZIP
+  const uint8_t *dicts;      // the WHOLE dictionaries (host, or device under FLATE_HIP_DEVICE_PTRS) ...
+  const uint64_t *dict_off;  // ... dictionary j = dicts[dict_off[j], dict_off[j+1])
+  uint32_t n_dicts;
+  uint32_t *dict_used;       // host, per member (may be null): the dictionary its DICTID chose
+};
+
+// The container of flate_hip_inflate_spliced_framed: ONE member around the spliced stream (frame_kernels.hip:
+// frame_rebase_kernel / frame_verdict_spliced_kernel).  The member's verdict comes back here.
+struct InfMember {
+  uint32_t wrap;  // FLATE_HIP_WRAP_ZLIB / _GZIP
+  int32_t status = 0;
+  int64_t err_off = -1;
+};
+
+// what a step of a call moves through the ctx's control-array staging (ctl_up / ctl_down)
+struct CtlBytes {
+  size_t up = 0, down = 0;
+  void operator+=(const CtlBytes &o) { up += o.up, down += o.down; }
+};
+
+// ---- the decoders ----
+
+using InfKernel = void (*)(InfParams);
+static const struct {
+  int decoder, shape, lanes, row;
+  InfKernel k[2];  // without / with preset dictionaries
+} kDecoders[] = {
+    {kDecodeWave, 0, 0, 0, {inflate_kernel, inflate_dict_kernel}},
+    {kDecodeSpec, 1, 0, 0, {inflate_spec_kernel<FLATE_SPEC_SMALL>, inflate_spec_dict_kernel<FLATE_SPEC_SMALL>}},
+    {kDecodeSpec, 2, 0, 0, {inflate_spec_kernel<FLATE_SPEC_LARGE>, inflate_spec_dict_kernel<FLATE_SPEC_LARGE>}},
+    {kDecodeSimt, 0, 16, 0, {inflate_simt_kernel<16, 0>, inflate_simt_dict_kernel<16, 0>}},
+    {kDecodeSimt, 0, 32, 0, {inflate_simt_kernel<32, 0>, inflate_simt_dict_kernel<32, 0>}},
+    {kDecodeSimt, 0, 64, 0, {inflate_simt_kernel<64, 0>, inflate_simt_dict_kernel<64, 0>}},
+    {kDecodeSimt, 0, 64, 8, {inflate_simt_kernel<64, 8>, inflate_simt_dict_kernel<64, 8>}},
+    {kDecodeSimt, 0, 64, 16, {inflate_simt_kernel<64, 16>, inflate_simt_dict_kernel<64, 16>}},
+};
+
+// The route's kernel over the n streams of I, inside the inflate stage's events.  dict: some stream starts from a
+// preset dictionary (the dictionary builds).
+static int launch_decoders(flate_hip_ctx *c, const InflateRoute &rt, InfParams I, bool dict) {
+  InfKernel k = nullptr;
+  for (const auto &e : kDecoders)
+    if (e.decoder == rt.decoder && e.shape == rt.shape && e.lanes == rt.lanes && e.row == rt.row) k = e.k[dict ? 1 : 0];
+  if (!k) {
+    c->hip_err = "no decoder kernel for the chosen route";
+    return FLATE_HIP_E_INTERNAL;
+  }
+  StageTimer t(c, FLATE_HIP_STAGE_INFLATE);
+  if (rt.decoder != kDecodeSimt) {  // one wavefront per stream
+    hipLaunchKernelGGL(k, dim3(I.n_streams), dim3(64), 0, c->stream, I);
+    return FLATE_HIP_OK;
+  }
+  // one lane per stream, in equal rounds (inflate_route.h)
+  const uint32_t sblocks = (I.n_streams + (uint32_t)rt.lanes - 1) / (uint32_t)rt.lanes;
+  const int rc = ensure(c, c->d_simt_lens, inflate_simt_lens_bytes(rt.blocks_per_launch));
+  if (rc) return rc;
+  I.simt_lens = (uint32_t *)c->d_simt_lens.p;
+  for (uint32_t b0 = 0; b0 < sblocks; b0 += rt.blocks_per_launch) {
+    const uint32_t nb = sblocks - b0 < rt.blocks_per_launch ? sblocks - b0 : rt.blocks_per_launch;
+    I.sid0 = b0 * (uint32_t)rt.lanes;
+    hipLaunchKernelGGL(k, dim3(nb), dim3(64), inflate_simt_lds_bytes(rt.lanes), c->stream, I);
+  }
+  return FLATE_HIP_OK;
+}
+
+// ---- a batch of members (flate_hip_inflate_batch_framed) ----
+
+// members_before: the DICTIDs' checksums, the tails' places (8 + 4 bytes per dictionary)
+static CtlBytes members_before_ctl(const InfFrame &FRD) {
+  return {dictid_ctl_up_bytes(FRD.dict_off, FRD.n_dicts) + (size_t)FRD.n_dicts * 12 + 1024, 0};
+}
+
+// In front of the decoders: the DICTIDs, the arrays the parse kernel fills, and -- the host cannot know which
+// dictionaries the members name before the device has parsed -- the tail of EVERY non-empty dictionary, staged as for
+// flate_hip_inflate_batch_dict; then frame_parse_kernel.  The decoders read the raw streams' ranges and their
+// dictionaries from what that kernel writes; `dict`: run their dictionary build (whenever a non-empty dictionary is
+// passed).  sum_slots: what members_after's checksums will run over (null: nothing).
+static int members_before(flate_hip_ctx *c, const InfFrame &FRD, const uint8_t *d_in, const uint64_t *sum_slots,
+                          uint32_t n, uint32_t flags, InfParams &I, FrameReadParams &R, bool &dict) {
+  int rc;
+  // both runs of checksums carve slot 0 of the scratch: sized once for the larger, so that the second does not free
+  // what the first's kernels are still to read
+  size_t scratch = dictid_scratch_bytes(FRD.dict_off, FRD.n_dicts);
+  if (sum_slots && checksum_scratch_bytes(sum_slots, n) > scratch) scratch = checksum_scratch_bytes(sum_slots, n);
+  void *unused = nullptr;
+  if ((rc = ctx_scratch(c, 0, scratch, &unused))) return rc;
+  // (for the DICTIDs the whole dictionaries are uploaded, not only their tails)
+  if ((rc = dictid_stage(c, FRD.dicts, FRD.dict_off, FRD.n_dicts, flags))) return rc;
+  if ((rc = ensure(c, c->d_frame_off, ((size_t)n + 1) * 8))) return rc;
+  if ((rc = ensure(c, c->d_rd_end, (size_t)n * 8 + 8))) return rc;
+  if ((rc = ensure(c, c->d_rd_want, (size_t)n * 4 + 4))) return rc;
+  if ((rc = ensure(c, c->d_rd_isize, (size_t)n * 4 + 4))) return rc;
+  if ((rc = ensure(c, c->d_rd_bad, (size_t)n * 4 + 4))) return rc;
+  if ((rc = ensure(c, c->d_rd_dict, (size_t)n * 4 + 4))) return rc;
+  R.in = d_in;
+  R.in_off = (const uint64_t *)c->d_in_off.p;
+  R.n_streams = n;
+  R.wrap = FRD.wrap;
+  R.n_dicts = FRD.n_dicts;
+  R.pay_off = (uint64_t *)c->d_frame_off.p;
+  R.pay_end = (uint64_t *)c->d_rd_end.p;
+  R.want = (uint32_t *)c->d_rd_want.p;
+  R.isize = (uint32_t *)c->d_rd_isize.p;
+  R.bad = (uint32_t *)c->d_rd_bad.p;
+  R.dict_used = (uint32_t *)c->d_rd_dict.p;
+  R.out_len = I.out_len;
+  R.status = I.status;
+  R.err_off = I.err_off;
+  if (FRD.n_dicts) {
+    std::vector<uint32_t> every(FRD.n_dicts);
+    for (uint32_t j = 0; j < FRD.n_dicts; ++j) every[j] = j;
+    const DictSlots S = dict_slots(FRD.dict_off, FRD.n_dicts, every.data(), FRD.n_dicts, 1);
+    std::vector<uint64_t> t_at(FRD.n_dicts, 0);
+    std::vector<uint32_t> t_len(FRD.n_dicts, 0);
+    for (uint32_t j = 0; j < FRD.n_dicts; ++j) {
+      if (S.slot_of[j] == DictSlots::kNone) continue;
+      t_at[j] = S.at[S.slot_of[j]];
+      t_len[j] = S.len[S.slot_of[j]];
+    }
+    if ((rc = dict_upload(c, S, FRD.dicts, FRD.dict_off, flags))) return rc;
+    if ((rc = ensure(c, c->d_rd_tail_at, (size_t)FRD.n_dicts * 8 + 8))) return rc;
+    if ((rc = ensure(c, c->d_rd_tail_len, (size_t)FRD.n_dicts * 4 + 4))) return rc;
+    if ((rc = ensure(c, c->d_dict_at, (size_t)n * 8 + 8))) return rc;
+    if ((rc = ensure(c, c->d_dict_len, (size_t)n * 4 + 4))) return rc;
+    if ((rc = ctl_up(c, c->d_rd_tail_at.p, t_at.data(), (size_t)FRD.n_dicts * 8))) return rc;
+    if ((rc = ctl_up(c, c->d_rd_tail_len.p, t_len.data(), (size_t)FRD.n_dicts * 4))) return rc;
+    R.dict_id = (const uint32_t *)c->d_frame_ids.p;
+    R.tail_at = (const uint64_t *)c->d_rd_tail_at.p;
+    R.tail_len = (const uint32_t *)c->d_rd_tail_len.p;
+    R.dict_at = (uint64_t *)c->d_dict_at.p;
+    R.dict_len = (uint32_t *)c->d_dict_len.p;
+    dict = !S.at.empty();
+    if (dict) {
+      I.dict_buf = (const uint8_t *)c->d_dicts.p;
+      I.dict_at = R.dict_at;
+      I.dict_len = R.dict_len;
+    }
+  }
+  I.in_off = R.pay_off;
+  I.in_end = R.pay_end;
+  hipLaunchKernelGGL(frame_parse_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, R);
+  return FLATE_HIP_OK;
+}
+
+// members_after: the checksums of what was produced (sum_slots: the slots, null: a size-only pass stored nothing);
+// down: dict_used
+static CtlBytes members_after_ctl(const uint64_t *sum_slots, uint32_t n) {
+  CtlBytes b{0, (size_t)n * 4 + 256};
+  if (sum_slots) b.up = checksum_ctl_up_bytes(sum_slots, n);
+  return b;
+}
+
+// Behind the decoders: the sums of what every member produced (nothing is stored by a size-only pass: nothing to
+// sum), then the verdict.
+static int members_after(flate_hip_ctx *c, const InfFrame &FRD, const uint8_t *d_out, const uint64_t *sum_slots,
+                         uint32_t n, FrameReadParams &R) {
+  int rc;
+  StageTimer t(c, FLATE_HIP_STAGE_CHECKSUM);
+  if (sum_slots) {
+    if ((rc = ensure(c, c->d_frame_sums, (size_t)n * 4 + 8))) return rc;
+    if ((rc = checksum_device_clipped(c, d_out, sum_slots, n, frame_sum_kind(FRD.wrap), (const uint64_t *)c->d_out_len.p,
+                                      (const int32_t *)c->d_istatus.p, (const uint32_t *)c->d_rd_bad.p,
+                                      (uint32_t *)c->d_frame_sums.p)))
+      return rc;
+    R.sums = (const uint32_t *)c->d_frame_sums.p;
+  }
+  hipLaunchKernelGGL(frame_verdict_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, R);
+  HIP_TRY(c, hipGetLastError());
+  return FRD.dict_used ? ctl_down(c, FRD.dict_used, c->d_rd_dict.p, (size_t)n * 4) : FLATE_HIP_OK;
+}
+
+// ---- one member around a spliced stream (flate_hip_inflate_spliced_framed) ----
+
+// member_before: the one range {0, in_len} of FrameOne
+static CtlBytes member_before_ctl() { return {sizeof(FrameOne) + 1024, 0}; }
+
+// In front of the decoders: frame_parse_kernel over the one range {0, in_len}, then frame_rebase_kernel, which moves
+// the uploaded index (I.in_off, counted from the raw stream's first byte) behind the header the device has just
+// measured.  The decoders read the member from its first byte up to its trailer.
+static int member_before(flate_hip_ctx *c, const InfMember &SM, const uint8_t *d_in, uint64_t in_len, uint32_t n,
+                         InfParams &I, FrameSplicedParams &S) {
+  int rc;
+  if ((rc = ensure(c, c->d_rd_one, sizeof(FrameOne) + 16))) return rc;
+  if ((rc = ensure(c, c->d_frame_off, ((size_t)n + 1) * 8))) return rc;
+  if ((rc = ensure(c, c->d_frame_sums, (size_t)n * 4 + 8))) return rc;
+  if ((rc = ensure(c, c->d_rd_bad, (size_t)n * 4 + 4))) return rc;
+  FrameOne *one = (FrameOne *)c->d_rd_one.p;
+  const uint64_t range[2] = {0, in_len};
+  if ((rc = ctl_up(c, one->in_off, range, sizeof range))) return rc;
+  FrameReadParams R{};
+  R.in = d_in;
+  R.in_off = one->in_off;
+  R.n_streams = 1;
+  R.wrap = SM.wrap;
+  R.pay_off = one->pay_off;
+  R.pay_end = &one->pay_end;
+  R.want = &one->want;
+  R.isize = &one->isize;
+  R.bad = &one->bad;
+  R.dict_used = &one->dict_used;
+  hipLaunchKernelGGL(frame_parse_kernel, dim3(1), dim3(256), 0, c->stream, R);
+  S.one = one;
+  S.bit_in = I.in_off;
+  S.bit_out = (uint64_t *)c->d_frame_off.p;
+  S.piece_bad = (uint32_t *)c->d_rd_bad.p;
+  S.n_pieces = n;
+  S.wrap = SM.wrap;
+  S.in_len = in_len;
+  S.raw_end = in_len - frame_trailer_len(SM.wrap);  // (the entry point has checked in_len)
+  S.out_len = I.out_len;
+  S.status = I.status;
+  S.err_off = I.err_off;
+  hipLaunchKernelGGL(frame_rebase_kernel, dim3(n / 256 + 1), dim3(256), 0, c->stream, S);
+  HIP_TRY(c, hipGetLastError());
+  I.bit_off = S.bit_out;
+  I.in_len = S.raw_end;
+  return FLATE_HIP_OK;
+}
+
+// member_after: the pieces' checksums; down: the member's two words
+static CtlBytes member_after_ctl(const uint64_t *out_off, uint32_t n) { return {checksum_ctl_up_bytes(out_off, n), 1024}; }
+
+// Behind the decoders: the sums of what every piece produced, their join into the member's, then the verdict.
+static int member_after(flate_hip_ctx *c, InfMember &SM, const uint8_t *d_out, const uint64_t *out_off, uint32_t n,
+                        const FrameSplicedParams &S) {
+  int rc;
+  StageTimer t(c, FLATE_HIP_STAGE_CHECKSUM);
+  const uint32_t kind = frame_sum_kind(SM.wrap);
+  if ((rc = checksum_device_clipped(c, d_out, out_off, n, kind, (const uint64_t *)c->d_out_len.p,
+                                    (const int32_t *)c->d_istatus.p, (const uint32_t *)c->d_rd_bad.p,
+                                    (uint32_t *)c->d_frame_sums.p)))
+    return rc;
+  if ((rc = checksum_join_device(c, (const uint32_t *)c->d_frame_sums.p, (const uint64_t *)c->d_slot_off.p,
+                                 (const uint64_t *)c->d_out_len.p, n, kind, &S.one->sum, &S.one->total)))
+    return rc;
+  hipLaunchKernelGGL(frame_verdict_spliced_kernel, dim3(1), dim3(1024), 0, c->stream, S);
+  HIP_TRY(c, hipGetLastError());
+  if ((rc = ctl_down(c, &SM.status, &S.one->member_status, 4))) return rc;
+  return ctl_down(c, &SM.err_off, &S.one->member_err_off, 8);
+}
+
+// ---- the driver of the five batch calls ----
+// D != NULL: the streams' dictionaries (a launch in which a stream has one runs the decoders' dictionary build).
+// FRD != NULL: the streams are members of a container, parsed in front of the decoders and checked behind them.
+// SM != NULL (a spliced call): `in` is ONE member around the spliced stream and in_off is counted from the raw stream's
+// first byte; the return value is the member's status.
+static int inflate_common(flate_hip_ctx *c, const InfCall &A, const InfDict *D = nullptr, const InfFrame *FRD = nullptr,
+                          InfMember *SM = nullptr) {
+  const uint32_t n = A.n;
+  const bool spliced = A.spliced_len != 0;
+  const bool size_only = (A.flags & FLATE_HIP_SIZE_ONLY) != 0 && !spliced;
+  const bool dev = (A.flags & FLATE_HIP_DEVICE_PTRS) != 0;
+  const uint64_t in_bytes = spliced ? A.spliced_len : A.in_off[n];
+  HIP_TRY(c, hipSetDevice(c->device));
+  int rc;
+
+  // stage the input and the index arrays
+  const uint64_t *out_off = A.out_off;
+  std::vector<uint64_t> no_slots;
+  if (size_only) {  // nothing is stored: no output buffer, no slots
+    no_slots.assign((size_t)n + 1, 0);
+    out_off = no_slots.data();
+  }
+  const uint64_t *sum_slots = size_only ? nullptr : out_off;  // (what a container's checksums run over)
+  const uint8_t *d_in = A.in;
+  uint8_t *d_out = A.out;
+  if (!dev) {
+    if ((rc = ensure(c, c->d_in, in_bytes + 16))) return rc;
+    if ((rc = ensure(c, c->d_out, out_off[n] + 16))) return rc;
+    HIP_TRY(c, hipMemcpyAsync(c->d_in.p, A.in, in_bytes, hipMemcpyHostToDevice, c->stream));
+    d_in = (const uint8_t *)c->d_in.p;
+    d_out = (uint8_t *)c->d_out.p;
+  }
+  if ((rc = ensure(c, c->d_in_off, ((size_t)n + 1) * 8))) return rc;
+  if ((rc = ensure(c, c->d_slot_off, ((size_t)n + 1) * 8))) return rc;
+  if ((rc = ensure(c, c->d_out_len, (size_t)n * 8 + 8))) return rc;
+  if ((rc = ensure(c, c->d_istatus, (size_t)n * 4 + 4))) return rc;
+  if ((rc = ensure(c, c->d_ierr, (size_t)n * 8 + 8))) return rc;
+  // up: in_off, out_off; down: out_len, status, err_off
+  CtlBytes ctl{((size_t)n + 1) * 16, (size_t)n * 20 + 64};
+  if (FRD) {
+    ctl += members_before_ctl(*FRD);
+    ctl += members_after_ctl(sum_slots, n);
+  }
+  if (SM) {
+    ctl += member_before_ctl();
+    ctl += member_after_ctl(out_off, n);
+  }
+  if ((rc = ctl_begin(c, ctl.up, ctl.down))) return rc;
+  if ((rc = ctl_up(c, c->d_in_off.p, A.in_off, ((size_t)n + 1) * 8))) return rc;
+  if ((rc = ctl_up(c, c->d_slot_off.p, out_off, ((size_t)n + 1) * 8))) return rc;
+  InfParams I{};
+  I.in = d_in;
+  I.in_off = (const uint64_t *)c->d_in_off.p;
+  I.out = d_out;
+  I.out_off = (const uint64_t *)c->d_slot_off.p;
+  I.out_len = (uint64_t *)c->d_out_len.p;
+  I.status = (int32_t *)c->d_istatus.p;
+  I.err_off = (int64_t *)c->d_ierr.p;
+  I.n_streams = n;
+  I.bit_off = spliced ? (const uint64_t *)c->d_in_off.p : nullptr;
+  I.in_len = in_bytes;
+  I.size_only = size_only ? 1u : 0u;
+  bool dict = false;
+  if (D) {
+    I.dict_buf = D->buf;
+    I.dict_at = D->at;
+    I.dict_len = D->len;
+    for (uint32_t i = 0; i < n && !dict; ++i) dict = D->h_len[i] != 0;
+  }
+
+  // the container in front of the decoders
+  FrameReadParams R{};
+  FrameSplicedParams S{};
+  if (FRD && (rc = members_before(c, *FRD, d_in, sum_slots, n, A.flags, I, R, dict))) return rc;
+  if (SM && (rc = member_before(c, *SM, d_in, in_bytes, n, I, S))) return rc;
+
+  const InflateRoute route = inflate_route(c->inflate, c->num_cus, n, longest_entry(A.in_off, n), spliced, size_only);
+  if ((rc = launch_decoders(c, route, I, dict))) return rc;
+  HIP_TRY(c, hipGetLastError());
+
+  // the container behind them
+  if (FRD && (rc = members_after(c, *FRD, d_out, sum_slots, n, R))) return rc;
+  if (SM && (rc = member_after(c, *SM, d_out, out_off, n, S))) return rc;
+
+  // read back, synchronise, fold the statuses
+  if ((rc = ctl_down(c, A.out_len, c->d_out_len.p, (size_t)n * 8))) return rc;
+  if ((rc = ctl_down(c, A.status, c->d_istatus.p, (size_t)n * 4))) return rc;
+  if ((rc = ctl_down(c, A.err_off, c->d_ierr.p, (size_t)n * 8))) return rc;
+  if (!dev && !size_only)
+    HIP_TRY(c, hipMemcpyAsync(A.out, c->d_out.p, out_off[n], hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  ctl_finish(c);
+  const bool used[FLATE_HIP_STAGE_COUNT] = {false, false, FRD != nullptr || SM != nullptr, true};
+  if ((rc = collect_timing(c, used))) return rc;
+  // A size-only pass has no capacity -- but the kernels count output in 32 bits: a stream that inflates
+  // to 4 GiB or more stops there with "slot too small", which for a call without slots means "too large"
+  if (size_only)
+    for (uint32_t i = 0; i < n; ++i)
+      if (A.status[i] == FLATE_HIP_E_OUT_TOO_SMALL) A.status[i] = FLATE_HIP_E_TOO_LARGE;
+  if (SM) return SM->status;  // (the first non-zero piece status, or the trailer's verdict with every piece at 0)
+  for (uint32_t i = 0; i < n; ++i)
+    if (A.status[i]) return A.status[i];
+  return FLATE_HIP_OK;
+}
+
+// Host-pointer inflate of independent streams, pipelined like deflate_host_pipelined: every
+// stream has its own input range and output slot, so a group is a contiguous range of both.
+static int inflate_host_pipelined(flate_hip_ctx *c, const InfCall &A, uint32_t G, const InfDict *D) {
+  HIP_TRY(c, hipSetDevice(c->device));
+  const uint64_t *in_off = A.in_off, *out_off = A.out_off;
+  int rc;
+  if ((rc = ensure(c, c->d_in, in_off[A.n] + 16))) return rc;
+  if ((rc = ensure(c, c->d_out, out_off[A.n] + 16))) return rc;
+  if ((rc = host_pipe_streams(c))) return rc;
+  uint8_t *d_in = (uint8_t *)c->d_in.p, *d_out = (uint8_t *)c->d_out.p;
+  std::vector<uint32_t> lo(G + 1);
+  std::vector<CopyJob> in_jobs(G);
+  cut_by_bytes(in_off, out_off, A.n, G, lo);  // by input + output bytes (both cross PCIe)
+  for (uint32_t g = 0; g < G; ++g)
+    in_jobs[g] = {d_in + in_off[lo[g]], A.in + in_off[lo[g]], (size_t)(in_off[lo[g + 1]] - in_off[lo[g]])};
+  const double t_call = host_now_ms();
+  CopyPipe pipe(G, G);
+  pipe.start(c->device, c->h2d_stream, c->d2h_stream, in_jobs);
+  float stage_sum[FLATE_HIP_STAGE_COUNT] = {0, 0, 0, 0};
+  std::vector<uint64_t> gin, gout;
+  rc = FLATE_HIP_OK;
+  int first_status = FLATE_HIP_OK;
+  for (uint32_t g = 0; g < G; ++g) {
+    if (!pipe.wait_in(g)) {
+      rc = FLATE_HIP_E_HIP;
+      break;
+    }
+    const uint32_t a = lo[g], cnt = lo[g + 1] - lo[g];
+    gin.resize((size_t)cnt + 1);
+    gout.resize((size_t)cnt + 1);
+    for (uint32_t i = 0; i <= cnt; ++i) {
+      gin[i] = in_off[a + i] - in_off[a];
+      gout[i] = out_off[a + i] - out_off[a];
+    }
+    if (cnt) {
+      const double ta = host_now_ms();
+      InfDict gd{};  // (the group's slice of the per-stream dictionary arrays)
+      if (D) gd = {D->buf, D->at + a, D->len + a, D->h_len + a};
+      const InfCall GA{d_in + in_off[a], gin.data(), cnt, d_out + out_off[a], gout.data(), A.out_len + a, A.status + a,
+                       A.err_off + a, A.flags | FLATE_HIP_DEVICE_PTRS, 0};
+      const int r = inflate_common(c, GA, D ? &gd : nullptr);
+      host_trace(t_call, "compute", g, ta, host_now_ms());
+      // a stream's own failure (its status, also the return value) does not stop the batch: as in
+      // one pass, every stream is decoded and the first failing status is what the call returns
+      if (!is_stream_status(r)) {
+        rc = r;
+        break;
+      }
+      if (first_status == FLATE_HIP_OK) first_status = r;
+      for (int k = 0; k < FLATE_HIP_STAGE_COUNT; ++k) stage_sum[k] += c->stage_ms[k];
+    }
+    pipe.post_out(g, {A.out + out_off[a], d_out + out_off[a], (size_t)gout[cnt]});
+  }
+  const std::string err = pipe.finish();
+  if (rc == FLATE_HIP_OK) rc = first_status;
+  if ((rc == FLATE_HIP_OK || rc == first_status) && !err.empty()) rc = FLATE_HIP_E_HIP;
+  if (rc == FLATE_HIP_E_HIP && c->hip_err.empty()) c->hip_err = err;
+  for (int k = 0; k < FLATE_HIP_STAGE_COUNT; ++k) c->stage_ms[k] = stage_sum[k];
+  return rc;
+}
+
+// flate_hip_inflate_batch after its checks; D: the streams' dictionaries (flate_hip_inflate_batch_dict)
+static int inflate_batch_run(flate_hip_ctx *c, InfCall A, const InfDict *D) {
+  if (A.flags & FLATE_HIP_SIZE_ONLY) {
+    A.out = nullptr, A.out_off = nullptr;
+    return inflate_common(c, A, D);
+  }
+  // host pointers and a large batch: decode group g while g+1 is copied in and g-1 out
+  if (!(A.flags & FLATE_HIP_DEVICE_PTRS) && c->host_groups > 1 &&
+      A.in_off[A.n] - A.in_off[0] + A.out_off[A.n] - A.out_off[0] >= (64ull << 20)) {
+    uint32_t G = (uint32_t)c->host_groups;
+    const uint32_t iper = 4u * c->host_group_streams;  // (a group should still fill the lane-per-stream launch: 16384)
+    if (A.n / iper < G) G = A.n / iper;
+    if (G > 1) {
+      try {
+        return inflate_host_pipelined(c, A, G, D);
+      } catch (const std::exception &e) {  // (no copy threads, out of host memory): one pass instead
+        c->hip_err.clear();
+      }
+    }
+  }
+  return inflate_common(c, A, D);
+}
+
+extern "C" {
+
+int flate_hip_inflate_batch(flate_hip_ctx *c, const uint8_t *in, const uint64_t *in_off, uint32_t n,
+                            uint8_t *out, const uint64_t *out_off, uint64_t *out_len,
+                            int32_t *status, int64_t *err_off, uint32_t flags) {
+  if (!c || !inflate_batch_ptrs_ok(in, in_off, n, out, out_off, out_len, status, err_off, flags)) return FLATE_HIP_E_INVALID;
+  c->hip_err.clear();
+  if (n == 0) return FLATE_HIP_OK;
+  const int rc = inflate_batch_ranges(in_off, n, out_off, flags);
+  return rc ? rc : inflate_batch_run(c, {in, in_off, n, out, out_off, out_len, status, err_off, flags, 0}, nullptr);
+}
+
+int flate_hip_inflate_batch_dict(flate_hip_ctx *c, const uint8_t *in, const uint64_t *in_off, uint32_t n,
+                                 const uint8_t *dicts, const uint64_t *dict_off, uint32_t n_dicts,
+                                 const uint32_t *dict_of, uint8_t *out, const uint64_t *out_off,
+                                 uint64_t *out_len, int32_t *status, int64_t *err_off, uint32_t flags) {
+  // every check before any HIP call
+  if (!c || !inflate_batch_ptrs_ok(in, in_off, n, out, out_off, out_len, status, err_off, flags)) return FLATE_HIP_E_INVALID;
+  int rc = inflate_batch_ranges(in_off, n, out_off, flags);
+  if (rc != FLATE_HIP_OK && rc != FLATE_HIP_E_TOO_LARGE) return rc;
+  if (!dict_args_ok(dicts, dict_off, n_dicts, dict_of, n)) return FLATE_HIP_E_INVALID;
+  // the history each stream starts with: the last kMaxMatchOffset bytes of its dictionary
+  const DictSlots S = dict_slots(dict_off, n_dicts, dict_of, n, 1);
+  if (S.at.empty())  // no stream has history in front of it: the plain call, its path and its results
+    return flate_hip_inflate_batch(c, in, in_off, n, out, out_off, out_len, status, err_off, flags);
+  c->hip_err.clear();
+  if (rc) return rc;
+  std::vector<uint64_t> h_at(n, 0);  // the decoders take {at, len} per stream (0 = none)
+  std::vector<uint32_t> h_len(n, 0);
+  for (uint32_t i = 0; i < n; ++i) {
+    if (S.slot_of[i] == DictSlots::kNone) continue;
+    h_at[i] = S.at[S.slot_of[i]];
+    h_len[i] = S.len[S.slot_of[i]];
+  }
+  HIP_TRY(c, hipSetDevice(c->device));
+  if ((rc = dict_upload(c, S, dicts, dict_off, flags))) return rc;
+  if ((rc = ensure(c, c->d_dict_at, (size_t)n * 8))) return rc;
+  if ((rc = ensure(c, c->d_dict_len, (size_t)n * 4))) return rc;
+  HIP_TRY(c, hipMemcpyAsync(c->d_dict_at.p, h_at.data(), (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(c->d_dict_len.p, h_len.data(), (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  const InfDict D{(const uint8_t *)c->d_dicts.p, (const uint64_t *)c->d_dict_at.p, (const uint32_t *)c->d_dict_len.p, h_len.data()};
+  return inflate_batch_run(c, {in, in_off, n, out, out_off, out_len, status, err_off, flags, 0}, &D);
+}
+
+int flate_hip_inflate_batch_framed(flate_hip_ctx *c, const uint8_t *in, const uint64_t *in_off, uint32_t n,
+                                   uint32_t wrap, const uint8_t *dicts, const uint64_t *dict_off, uint32_t n_dicts,
+                                   uint8_t *out, const uint64_t *out_off, uint64_t *out_len, int32_t *status,
+                                   int64_t *err_off, uint32_t *dict_used, uint32_t flags) {
+  // every check before any HIP call
+  if (!c || wrap > FLATE_HIP_WRAP_GZIP) return FLATE_HIP_E_INVALID;
+  const bool with_dicts = dicts || dict_off || n_dicts;
+  if (with_dicts && wrap != FLATE_HIP_WRAP_ZLIB) return FLATE_HIP_E_INVALID;  // (neither has a DICTID to choose by)
+  if (!inflate_batch_ptrs_ok(in, in_off, n, out, out_off, out_len, status, err_off, flags)) return FLATE_HIP_E_INVALID;
+  if (!dict_table_ok(dicts, dict_off, n_dicts)) return FLATE_HIP_E_INVALID;
+  if (wrap == FLATE_HIP_WRAP_RAW) {  // the raw call: its kernels, its results
+    const int rc = flate_hip_inflate_batch(c, in, in_off, n, out, out_off, out_len, status, err_off, flags);
+    if (dict_used && rc != FLATE_HIP_E_INVALID && rc != FLATE_HIP_E_TOO_LARGE)
+      for (uint32_t i = 0; i < n; ++i) dict_used[i] = FLATE_HIP_NO_DICT;
+    return rc;
+  }
+  c->hip_err.clear();
+  if (n == 0) return FLATE_HIP_OK;
+  const int rc = inflate_batch_ranges(in_off, n, out_off, flags);
+  if (rc) return rc;
+  try {
+    // (host pointers: one copy in, parse, decode, check, one copy out -- no "host_pipeline_groups")
+    const InfFrame FRD{wrap, dicts, dict_off, n_dicts, dict_used};
+    const bool size_only = (flags & FLATE_HIP_SIZE_ONLY) != 0;
+    return inflate_common(c, {in, in_off, n, size_only ? nullptr : out, size_only ? nullptr : out_off, out_len, status,
+                              err_off, flags, 0},
+                          nullptr, &FRD);
+  } catch (const std::exception &e) {  // (out of host memory in an index vector)
+    c->hip_err = e.what();
+    return FLATE_HIP_E_INTERNAL;
+  }
+}
+
+int flate_hip_inflate_spliced(flate_hip_ctx *c, const uint8_t *in, uint64_t in_len,
+                              const uint64_t *bit_off, uint32_t n, uint8_t *out,
+                              const uint64_t *out_off, uint64_t *out_len, int32_t *status,
+                              int64_t *err_off, uint32_t flags) {
+  if (!c || !in || !in_len || !bit_off || !out_off || !out_len || !status || !err_off || (n && !out))
+    return FLATE_HIP_E_INVALID;
+  c->hip_err.clear();
+  if (n == 0) return FLATE_HIP_OK;
+  const int rc = spliced_index_check(bit_off, n, out_off, in_len, 0);
+  return rc ? rc : inflate_common(c, {in, bit_off, n, out, out_off, out_len, status, err_off, flags, in_len});
+}
+
+int flate_hip_inflate_spliced_framed(flate_hip_ctx *c, const uint8_t *in, uint64_t in_len, uint32_t wrap,
+                                     const uint64_t *bit_off, uint32_t n, uint8_t *out, const uint64_t *out_off,
+                                     uint64_t *out_len, int32_t *status, int64_t *err_off, int32_t *member_status,
+                                     int64_t *member_err_off, uint32_t flags) {
+  // every check before any HIP call
+  if (!c || wrap > FLATE_HIP_WRAP_GZIP || (flags & FLATE_HIP_SIZE_ONLY)) return FLATE_HIP_E_INVALID;
+  if (wrap == FLATE_HIP_WRAP_RAW) {  // the raw call: its kernels, its results
+    const int rc = flate_hip_inflate_spliced(c, in, in_len, bit_off, n, out, out_off, out_len, status, err_off, flags);
+    if (!is_stream_status(rc)) return rc;  // (refused, or failed: no verdict)
+    int32_t first = 0;
+    for (uint32_t i = 0; i < n && !first; ++i) first = status[i];
+    if (member_status) *member_status = first;
+    if (member_err_off) *member_err_off = -1;
+    return rc;
+  }
+  if (!in || !in_len || !bit_off || !out_off || !out_len || !status || !err_off || (n && !out)) return FLATE_HIP_E_INVALID;
+  c->hip_err.clear();
+  if (n == 0) return FLATE_HIP_OK;
+  // the shortest header and the trailer must fit, and the index must end inside what is left
+  if (const int rc = spliced_index_check(bit_off, n, out_off, in_len, frame_min_len(wrap))) return rc;
+  try {
+    // (host pointers: one copy in, parse, decode, check, one copy out)
+    InfMember SM{wrap};
+    const int rc = inflate_common(c, {in, bit_off, n, out, out_off, out_len, status, err_off, flags, in_len}, nullptr,
+                                  nullptr, &SM);
+    if (!is_stream_status(rc)) return rc;  // (failed: no verdict was read back)
+    if (member_status) *member_status = SM.status;
+    if (member_err_off) *member_err_off = SM.err_off;
+    return rc;
+  } catch (const std::exception &e) {  // (out of host memory in an index vector)
+    c->hip_err = e.what();
+    return FLATE_HIP_E_INTERNAL;
+  }
+}
+
+}  // extern "C"
+
+// ---- one long stream decoded in pieces (Decompressor::read as the reference behaves: the caller
+// ---- holds a piece of input and a piece of output, never the whole stream; inflate.mbt:382-407) ----
+struct flate_hip_inflate_stream {
+  flate_hip_ctx *ctx = nullptr;
+  DevBuf state, in, out;
+  int status = 0;           // sticky: 1 = the final block is done, < 0 = error
+  int64_t err_off = -1;
+  uint32_t bit_in_byte = 0; // of the byte the next call's input starts with
+  uint64_t total_in = 0, total_out = 0;
+};
+
+extern "C" {
+
+int flate_hip_inflate_stream_open(flate_hip_ctx *c, flate_hip_inflate_stream **out) {
+  if (!c || !out) return FLATE_HIP_E_INVALID;
+  *out = nullptr;
+  c->hip_err.clear();
+  HIP_TRY(c, hipSetDevice(c->device));
+  flate_hip_inflate_stream *st = new flate_hip_inflate_stream();
+  st->ctx = c;
+  int rc = ensure(c, st->state, inflate_stream_state_bytes() + 64);
+  if (rc == FLATE_HIP_OK) {
+    hipLaunchKernelGGL(inflate_stream_init_kernel, dim3(1), dim3(64), 0, c->stream, st->state.p,
+                       (const uint8_t *)nullptr, 0u);
+    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) rc = FLATE_HIP_E_HIP;
+  }
+  if (rc != FLATE_HIP_OK) {
+    delete st;
+    return rc;
+  }
+  *out = st;
+  return FLATE_HIP_OK;
+}
+
+// Decompressor::reset(r, dict) (inflate.mbt:862-884) / &Reader::new_dict (:315-317): a fresh decoder on
+// the same handle, with the last 32768 bytes of `dict` as history that has already been read
+// (DictDecoder::new, dict-decoder.mbt:40-60).
+int flate_hip_inflate_stream_reset(flate_hip_inflate_stream *st, const uint8_t *dict, uint64_t dict_len) {
+  if (!st || (dict_len && !dict)) return FLATE_HIP_E_INVALID;
+  flate_hip_ctx *c = st->ctx;
+  c->hip_err.clear();
+  HIP_TRY(c, hipSetDevice(c->device));
+  if (dict_len > (uint64_t)kMaxMatchOffset) {
+    dict += dict_len - (uint64_t)kMaxMatchOffset;
+    dict_len = (uint64_t)kMaxMatchOffset;
+  }
+  int rc;
+  if ((rc = ensure(c, st->in, dict_len + 16))) return rc;
+  if (dict_len) HIP_TRY(c, hipMemcpyAsync(st->in.p, dict, dict_len, hipMemcpyHostToDevice, c->stream));
+  hipLaunchKernelGGL(inflate_stream_init_kernel, dim3(1), dim3(256), 0, c->stream, st->state.p,
+                     (const uint8_t *)st->in.p, (uint32_t)dict_len);
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  st->status = 0;
+  st->err_off = -1;
+  st->bit_in_byte = 0;
+  st->total_in = st->total_out = 0;
+  return FLATE_HIP_OK;
+}
+
+void flate_hip_inflate_stream_free(flate_hip_inflate_stream *st) {
+  if (!st) return;
+  (void)hipSetDevice(st->ctx->device);
+  delete st;
+}
+
+int flate_hip_inflate_stream_read(flate_hip_inflate_stream *st, const uint8_t *in, uint64_t in_len, int final_in,
+                                  uint8_t *out, uint64_t out_cap, uint64_t *in_used, uint64_t *out_len,
+                                  int64_t *err_off) {
+  if (!st || !in_used || !out_len || (in_len && !in) || (out_cap && !out)) return FLATE_HIP_E_INVALID;
+  *in_used = *out_len = 0;
+  if (err_off) *err_off = st->err_off;
+  if (st->status) return st->status == 1 ? FLATE_HIP_STREAM_END : st->status;  // sticky (Decompressor.err, inflate.mbt:285,398)
+  // the byte that holds the next unconsumed bit was reported as unused: it has to be here again
+  if (st->bit_in_byte && in_len == 0) return final_in ? FLATE_HIP_E_UNEXPECTED_EOF : FLATE_HIP_OK;
+  if (in_len == 0 && !final_in) return FLATE_HIP_OK;  // nothing to decode from
+  flate_hip_ctx *c = st->ctx;
+  c->hip_err.clear();
+  HIP_TRY(c, hipSetDevice(c->device));
+  // one call takes at most 1 GiB each way (32-bit positions inside the kernel); more input than that is
+  // simply not all used, and not final
+  const uint64_t kPiece = 1ull << 30;
+  if (in_len > kPiece) {
+    in_len = kPiece;
+    final_in = 0;
+  }
+  if (out_cap > kPiece) out_cap = kPiece;
+  int rc;
+  if ((rc = ensure(c, st->in, in_len + 16))) return rc;
+  if ((rc = ensure(c, st->out, out_cap + 16))) return rc;
+  if (in_len) HIP_TRY(c, hipMemcpyAsync(st->in.p, in, in_len, hipMemcpyHostToDevice, c->stream));
+  hipLaunchKernelGGL(inflate_stream_kernel, dim3(1), dim3(64), 0, c->stream, st->state.p, (const uint8_t *)st->in.p,
+                     (uint32_t)in_len, final_in ? 1u : 0u, (uint8_t *)st->out.p, (uint32_t)out_cap);
+  HIP_TRY(c, hipGetLastError());
+  InfStreamResult r{};
+  HIP_TRY(c, hipMemcpyAsync(&r, st->state.p, sizeof r, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  if (r.out_len > out_cap || r.in_used > in_len) return FLATE_HIP_E_INTERNAL;
+  if (r.out_len) {
+    HIP_TRY(c, hipMemcpyAsync(out, st->out.p, r.out_len, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+  }
+  *in_used = r.in_used;
+  *out_len = r.out_len;
+  st->bit_in_byte = r.bit_in_byte;
+  st->total_in = r.total_in;
+  st->total_out = r.total_out;
+  if (r.status) {
+    st->status = r.status;
+    st->err_off = r.err_off;
+    if (err_off) *err_off = r.err_off;
+    return r.status == 1 ? FLATE_HIP_STREAM_END : r.status;
+  }
+  return FLATE_HIP_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,220 @@
+// flate_ctx.h -- the ctx and the host-side helpers that more than one host file of the C ABI uses (private, host
+// only).  Everything in flate_host is DEFINED in flate_api.hip; flate_api_inflate.hip is the other user.
+// (checksum.hip and gather.hip see the ctx through the flate::ctx_* accessors of flate_kernels.h.)
+#pragma once
+
+#include "flate_hip.h"
+
+#include <hip/hip_runtime.h>
+
+#include <condition_variable>
+#include <mutex>
+#include <string>
+#include <thread>
+#include <vector>
+
+#include "flate_kernels.h"
+#include "inflate_route.h"
+
+namespace flate_host {
+
+// Device memory that belongs to one owner (the ctx, a stream handle): grown by ensure(), freed with the owner, whose
+// release function has selected the device.
+struct DevBuf {
+  void *p = nullptr;
+  size_t cap = 0;
+  DevBuf() = default;
+  DevBuf(const DevBuf &) = delete;
+  DevBuf &operator=(const DevBuf &) = delete;
+  ~DevBuf() {
+    if (p) (void)hipFree(p);
+  }
+};
+
+}  // namespace flate_host
+
+struct flate_hip_ctx {
+  using DevBuf = flate_host::DevBuf;
+  int device = 0;
+  hipStream_t own_stream = nullptr;
+  hipStream_t stream = nullptr;
+  std::string hip_err;
+  bool profiling = false;
+  float stage_ms[FLATE_HIP_STAGE_COUNT] = {0, 0, 0, 0};
+  hipEvent_t ev[2 * FLATE_HIP_STAGE_COUNT] = {};
+  // persistent device data
+  DevBuf scan_tab;
+  int scan_len = 0;
+  // grow-only scratch
+  DevBuf d_in, d_out, d_in_off, d_chunk_base, d_ids16, d_ids32, d_matches, d_nmatch, d_ntok;
+  DevBuf d_slot_off, d_out_len, d_out_off, d_status;
+  DevBuf d_blk_base, d_blk_hist, d_blk_cl, d_blk_hdr, d_blk_meta, d_tile_meta, d_blk_sid;
+  // entropy stage with one wavefront per BLOCK instead of per stream: -1 = when the batch's streams
+  // have three or more blocks on average (multi-window streams), 0 = never, 1 = whenever possible
+  int entropy_per_block = -1;
+  DevBuf d_istatus, d_ierr, d_debug, d_gtables, d_queue, d_simt_lens;
+  DevBuf d_dicts, d_dict_at, d_dict_len;  // flate_hip_inflate_batch_dict: dictionary tails, per-stream (at, len)
+  // flate_hip_deflate_fast_batch_dict (it shares the three above, there per used dictionary): the streams that start
+  // from a dictionary, every stream's dictionary slot, the primed tables and sweep clocks of the slots
+  DevBuf d_idsD, d_lz_slot_of, d_lz_tables, d_lz_clocks;
+  // the *_framed calls: member offsets, the streams' checksums, per stream its dictionary, the dictionaries' Adler-32
+  // (DICTIDs) and, for host callers, the whole dictionaries
+  DevBuf d_frame_off, d_frame_sums, d_frame_dict_of, d_frame_ids, d_frame_dicts;
+  // flate_hip_inflate_batch_framed (it shares d_frame_off: the raw streams' starts, d_frame_sums, d_frame_ids,
+  // d_frame_dicts): the raw streams' ends, the trailers' sums and ISIZEs, the header verdicts, the chosen dictionaries,
+  // and per dictionary where its staged tail lies and how long it is
+  DevBuf d_rd_end, d_rd_want, d_rd_isize, d_rd_bad, d_rd_dict, d_rd_tail_at, d_rd_tail_len;
+  // flate_hip_inflate_spliced_framed (it shares d_frame_off: the index counted from the member's first byte,
+  // d_frame_sums: the pieces' sums, d_rd_bad: the header verdict per piece): the one member's words (FrameOne)
+  DevBuf d_rd_one;
+  hipStream_t guest_stream = nullptr;
+  hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+  int guest_blocks = 0;      // 0 = guest kernel off
+  uint32_t guest_min = 1280; // below this many streams (5 per CU) the guests stay idle: one block per stream
+  int32_t h_status_word = 0;  // landing pads of small async D2H copies
+  uint64_t h_total_bytes = 0;
+  uint32_t num_cus = 256;
+  flate::InflateOpts inflate;  // the "inflate_*" options (inflate_route.h)
+  uint32_t resident_blocks = 1024;  // persistent LDS-table blocks (4 per CU x 256 CUs)
+  // (Rounds 2-4 carried an entropy stage OVERLAPPED with the match finder -- sub-batches gated on counters
+  // the persistent launch incremented, in an even and an uneven form.  Never faster than running the two one
+  // after the other (profiles/r02, r04), and a soak run of round 4 once saw the pack kernel's self-check fire
+  // in the even form, not reproduced in 115 000 stress runs: removed)
+  // window-granular scheduling of multi-window streams (lz77_kernels.hip, uq_*): on by default
+  int window_units = 1;
+  DevBuf d_uq_ready, d_uq_tables, d_uq_sweep;
+  DevBuf d_aux[2];  // ctx_scratch (checksum.hip)
+  // measurement aids (flate_hip_last_resident_share, option "profile_split_streams")
+  uint32_t profile_split = 0;        // > 0: LDS-table blocks take exactly the first K queue entries,
+                                     // the guest blocks the rest (two queues instead of one)
+  uint32_t last_count[2] = {0, 0};   // queue lengths of the last persistent launches (16-bit, multi)
+  uint32_t queue_init = 0;
+  uint32_t debug_chunks = 0;
+  // Host-pointer calls of the batch encoder: the batch is cut into host_groups groups of streams
+  // and group g is compressed while group g+1 is copied in and the output of group g-1 is copied
+  // out (two copy threads on two non-blocking streams).  0 = one copy in, compress, one copy out.
+  int host_groups = 8;
+  uint32_t host_group_streams = 2048;  // a group holds at least this many streams (inflate: four times as many)
+  // bounded waits of the persistent kernels (uq_pop): polls before giving up
+  // (a poll is one relaxed load + s_sleep, >= 0.4 us; a wave that is not running does not count)
+  uint32_t spin_limit = 8u << 20;
+  uint32_t inject_drop_push = 0;  // test hook: the k-th window hand-over (1-based) is dropped
+  uint32_t inject_stall = 0;      // test hook: the k-th dense batch (1-based) of every chunk makes no progress
+  uint64_t stream_rebase = 1ull << 30;  // flate_hip_stream: origin moved up past this many bytes
+  int64_t debug_buffer_reset = 0;       // test hook: buffer_reset (deflate-fast.mbt:55) of streams opened from now on
+  hipStream_t h2d_stream = nullptr, d2h_stream = nullptr;
+  // Host-pointer batches run their groups on TWO lanes (sub-contexts with their own streams and
+  // scratch, driven by two host threads): the persistent match-finder launch of group g+1 fills the
+  // chip while group g's last streams, its entropy kernels and its size read-back drain, which a single
+  // lane leaves idle (4 groups of 4096 streams: 19.9 ms of match finding against 16.2 for the batch
+  // as one launch).  0 = one lane (round 3's behaviour).
+  int host_lanes = 2;
+  flate_hip_ctx *lane[2] = {nullptr, nullptr};
+  // pinned staging of a call's small index arrays (ctl_up / ctl_down): they travel by a copy KERNEL,
+  // never through the DMA engines the bulk transfers of the host-pointer pipelines occupy
+  struct CtlStage {
+    uint8_t *p = nullptr;
+    size_t cap = 0, used = 0;
+  } ctl_up_buf, ctl_down_buf;
+  struct CtlPending {
+    void *host_dst;
+    size_t off, bytes;
+  };
+  std::vector<CtlPending> ctl_pending;
+};
+
+#define HIP_TRY(ctx, expr)                                                         \
+  do {                                                                             \
+    hipError_t e_ = (expr);                                                        \
+    if (e_ != hipSuccess) {                                                        \
+      (ctx)->hip_err = std::string(#expr) + ": " + hipGetErrorString(e_);          \
+      return FLATE_HIP_E_HIP;                                                      \
+    }                                                                              \
+  } while (0)
+
+namespace flate_host {
+
+int ensure(flate_hip_ctx *c, DevBuf &b, size_t bytes);
+
+// ---- small index arrays: host <-> device through pinned staging and a copy kernel (copy_ctl_kernel) ----
+// ctl_begin: room for the call's uploads / downloads (a staging buffer only grows between calls: the
+// stream is drained first).  ctl_up: stage + launch.  ctl_down: launch into the staging; the bytes reach
+// the caller's array in ctl_finish, after the stream has been synchronised.
+int ctl_begin(flate_hip_ctx *c, size_t up_bytes, size_t down_bytes);
+int ctl_up(flate_hip_ctx *c, void *dev_dst, const void *host_src, size_t bytes);  // (bytes: rounded up to 4)
+int ctl_down(flate_hip_ctx *c, void *host_dst, const void *dev_src, size_t bytes);
+void ctl_finish(flate_hip_ctx *c);
+
+struct StageTimer {
+  flate_hip_ctx *c;
+  int stage;
+  StageTimer(flate_hip_ctx *ctx, int s) : c(ctx), stage(s) {
+    if (c->profiling) (void)hipEventRecord(c->ev[2 * stage], c->stream);
+  }
+  ~StageTimer() {
+    if (c->profiling) (void)hipEventRecord(c->ev[2 * stage + 1], c->stream);
+  }
+};
+int collect_timing(flate_hip_ctx *c, const bool used[FLATE_HIP_STAGE_COUNT]);
+
+// ---- host-pointer batches, pipelined over groups of streams (flate_hip_ctx::host_groups) ----
+double host_now_ms();
+void host_trace(double t0, const char *what, unsigned g, double a, double b);
+struct CopyJob {
+  void *dst;
+  const void *src;
+  size_t bytes;
+};
+// Two copy threads beside the calling thread: one brings the groups' input to the device in
+// order, the other takes every group's output back as soon as the caller posts it.  Each uses its
+// own non-blocking HIP stream, so the copies run beside the kernels of the group in between.
+class CopyPipe {
+ public:
+  CopyPipe(size_t n_in, size_t n_out) : in_ready_(n_in, 0), out_state_(n_out, 0), out_jobs_(n_out) {}
+  // (not in the constructor: if the second thread cannot be created, the destructor must still run
+  // to join the first)
+  void start(int device, hipStream_t s_in, hipStream_t s_out, std::vector<CopyJob> in_jobs);
+  // blocks until group g's input is on the device; false = its copy failed
+  bool wait_in(size_t g);
+  void post_out(size_t g, CopyJob j);
+  // ends both threads (outputs not posted yet are dropped) and returns the first copy error
+  std::string finish();
+  ~CopyPipe() { (void)finish(); }
+
+ private:
+  bool run(const CopyJob &j, hipMemcpyKind kind, hipStream_t s, const char *what);
+  double t0_ = host_now_ms();
+  std::mutex mu_;
+  std::condition_variable cv_;
+  std::vector<int> in_ready_, out_state_;  // 0 pending, 1 done / posted, -1 failed / dropped
+  std::vector<CopyJob> out_jobs_;
+  std::string err_;
+  bool stop_ = false;
+  std::thread t_in_, t_out_;
+};
+void cut_by_bytes(const uint64_t *a, const uint64_t *b, uint32_t n, uint32_t G, std::vector<uint32_t> &lo);
+int host_pipe_streams(flate_hip_ctx *c);
+
+// The dictionaries a *_batch_dict call uses, as slots: a slot is one dictionary that some stream names and whose
+// tail -- its last kMaxMatchOffset bytes, the history a stream can reach -- has at least min_len bytes.  The tails
+// lie one after another in c->d_dicts, each 16-byte aligned and followed by 16 bytes that a 16-byte load may touch.
+struct DictSlots {
+  static constexpr uint32_t kNone = ~0u;
+  std::vector<uint32_t> dict, len;  // per slot: the dictionary, the length of its tail
+  std::vector<uint64_t> at;         // per slot: where the tail starts in d_dicts
+  std::vector<uint32_t> slot_of;    // per stream: its slot, or kNone
+  uint64_t total = 0;               // bytes of d_dicts
+};
+DictSlots dict_slots(const uint64_t *dict_off, uint32_t n_dicts, const uint32_t *dict_of, uint32_t n, uint32_t min_len);
+int dict_upload(flate_hip_ctx *c, const DictSlots &S, const uint8_t *dicts, const uint64_t *dict_off, uint32_t flags);
+
+// The DICTIDs of a *_framed call: the Adler-32 of every WHOLE dictionary, left in c->d_frame_ids (host callers: the
+// dictionaries are uploaded to c->d_frame_dicts first).  Queued on c->stream behind a ctl_begin that covers
+// dictid_ctl_up_bytes; slot 0 of the scratch must already hold dictid_scratch_bytes -- a caller that queues another
+// run of checksums behind it sizes the slot ONCE for the larger of the two before either is queued, so that the
+// second cannot grow (free) what the first's kernels are still to read.
+size_t dictid_ctl_up_bytes(const uint64_t *dict_off, uint32_t n_dicts);
+size_t dictid_scratch_bytes(const uint64_t *dict_off, uint32_t n_dicts);
+int dictid_stage(flate_hip_ctx *c, const uint8_t *dicts, const uint64_t *dict_off, uint32_t n_dicts, uint32_t flags);
+
+}  // namespace flate_host

@@ -2,7 +2,26 @@
 #pragma once
 
 #include "flate_common.h"
+#include "flate_hip.h"
 
+namespace flate {
+
+// A container's constants (RFC 1950 / RFC 1952), for the kernels of frame_kernels.hip and every host site.
+// wrap: FLATE_HIP_WRAP_ZLIB / _GZIP.  The header as this library WRITES it (a member that is read may carry a longer
+// gzip header: frame_parse_kernel); with_dict: zlib's FDICT + DICTID.
+FLATE_HD uint32_t frame_header_len(uint32_t wrap, bool with_dict) {
+  return wrap == FLATE_HIP_WRAP_GZIP ? 10u : (with_dict ? 6u : 2u);
+}
+FLATE_HD uint32_t frame_trailer_len(uint32_t wrap) { return wrap == FLATE_HIP_WRAP_GZIP ? 8u : 4u; }
+// the shortest member: the header without a dictionary, nothing, the trailer
+FLATE_HD uint32_t frame_min_len(uint32_t wrap) { return frame_header_len(wrap, false) + frame_trailer_len(wrap); }
+FLATE_HD uint32_t frame_sum_kind(uint32_t wrap) {
+  return wrap == FLATE_HIP_WRAP_GZIP ? (uint32_t)FLATE_HIP_CHECKSUM_CRC32 : (uint32_t)FLATE_HIP_CHECKSUM_ADLER32;
+}
+
+}  // namespace flate
+
+#if defined(__HIPCC__)  // (what follows needs the HIP compiler; the constants above are also compiled as plain C++)
 namespace flate {
 
 // A stream is cut into LZ77 chunks as Compressor::enc_speed does (reference
@@ -361,3 +380,4 @@ int checksum_device_clipped(flate_hip_ctx *c, const uint8_t *d_out, const uint64
 int checksum_join_device(flate_hip_ctx *c, const uint32_t *d_sums, const uint64_t *d_slot_off,
                          const uint64_t *d_out_len, uint32_t n, uint32_t kind, uint32_t *d_sum, uint64_t *d_total);
 }  // namespace flate
+#endif  // __HIPCC__

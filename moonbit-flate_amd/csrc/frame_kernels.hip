@@ -31,10 +31,9 @@ namespace {
 
 // bytes in front of / behind stream i's raw stream
 __device__ inline uint32_t header_len(const FrameParams &P, uint32_t i) {
-  if (P.wrap == FLATE_HIP_WRAP_GZIP) return 10u;
-  return (P.dict_of && P.dict_of[i] != FLATE_HIP_NO_DICT) ? 6u : 2u;
+  return frame_header_len(P.wrap, P.wrap != FLATE_HIP_WRAP_GZIP && P.dict_of && P.dict_of[i] != FLATE_HIP_NO_DICT);
 }
-__device__ inline uint32_t trailer_len(const FrameParams &P) { return P.wrap == FLATE_HIP_WRAP_GZIP ? 8u : 4u; }
+__device__ inline uint32_t trailer_len(const FrameParams &P) { return frame_trailer_len(P.wrap); }
 
 __device__ inline void put_be32(uint8_t *p, uint32_t v) {
   p[0] = (uint8_t)(v >> 24), p[1] = (uint8_t)(v >> 16), p[2] = (uint8_t)(v >> 8), p[3] = (uint8_t)v;
@@ -89,7 +88,7 @@ __global__ __launch_bounds__(256) void frame_write_kernel(FrameParams P) {
   const uint32_t members = P.member_off ? P.n_streams : 1u;
   if (i >= members || *P.status != 0) return;  // (a status: the scan found the output too small -- nothing may be written)
   const bool one = P.member_off == nullptr;
-  const uint32_t hl = one ? (P.wrap == FLATE_HIP_WRAP_GZIP ? 10u : 2u) : header_len(P, i);
+  const uint32_t hl = one ? frame_header_len(P.wrap, false) : header_len(P, i);
   const uint64_t at = one ? 0ull : P.member_off[i];
   const uint64_t raw = P.out_len[i];
   const uint64_t in_len = one ? P.one_len : P.in_off[i + 1] - P.in_off[i];
@@ -108,7 +107,7 @@ __global__ __launch_bounds__(256) void frame_write_kernel(FrameParams P) {
     // CMF = 0x78 (deflate, 32 KiB window); FLG: FLEVEL = 0, FDICT, FCHECK makes CMF * 256 + FLG a multiple of 31
     // (RFC 1950 2.2): 0x01 without a dictionary, 0x3f with one
     h[0] = 0x78;
-    if (hl == 6u) {
+    if (hl == frame_header_len(FLATE_HIP_WRAP_ZLIB, true)) {
       h[1] = 0x3f;
       put_be32(h + 2, P.dict_id[P.dict_of[i]]);
     } else {
@@ -141,10 +140,10 @@ __global__ __launch_bounds__(256) void frame_parse_kernel(FrameReadParams P) {
   uint32_t used = FLATE_HIP_NO_DICT;
   if (P.wrap == FLATE_HIP_WRAP_GZIP) {
     // RFC 1952 2.3: ID1 ID2, CM = 8, the reserved FLG bits zero; FEXTRA, FNAME, FCOMMENT, FHCRC skipped in that order
-    tl = 8;
-    if (len >= 10 && m[0] == 0x1f && m[1] == 0x8b && m[2] == 8 && (m[3] & 0xe0) == 0) {
+    tl = frame_trailer_len(FLATE_HIP_WRAP_GZIP);
+    if (len >= frame_header_len(FLATE_HIP_WRAP_GZIP, false) && m[0] == 0x1f && m[1] == 0x8b && m[2] == 8 && (m[3] & 0xe0) == 0) {
       const uint32_t flg = m[3];
-      uint64_t p = 10;
+      uint64_t p = frame_header_len(FLATE_HIP_WRAP_GZIP, false);  // the fixed part
       ok = true;
       if (flg & 4u) {  // FEXTRA: XLEN, then that many bytes
         if (len < p + 2) ok = false;
@@ -162,18 +161,18 @@ __global__ __launch_bounds__(256) void frame_parse_kernel(FrameReadParams P) {
     }
   } else {
     // RFC 1950 2.2: CM = 8, CINFO <= 7, FCHECK; FDICT: DICTID follows, and names the FIRST dictionary with that id
-    tl = 4;
-    if (len >= 2 && (m[0] & 15u) == 8u && (m[0] >> 4) <= 7u && (((uint32_t)m[0] << 8) | m[1]) % 31u == 0u) {
+    tl = frame_trailer_len(FLATE_HIP_WRAP_ZLIB);
+    if (len >= frame_header_len(FLATE_HIP_WRAP_ZLIB, false) && (m[0] & 15u) == 8u && (m[0] >> 4) <= 7u && (((uint32_t)m[0] << 8) | m[1]) % 31u == 0u) {
       if (m[1] & 0x20u) {
-        if (P.n_dicts && len >= 6) {
+        if (P.n_dicts && len >= frame_header_len(FLATE_HIP_WRAP_ZLIB, true)) {
           const uint32_t id = get_be32(m + 2);
           for (uint32_t j = 0; j < P.n_dicts && !ok; ++j)
             if (P.dict_id[j] == id) used = j, ok = true;
-          hl = 6;
+          hl = frame_header_len(FLATE_HIP_WRAP_ZLIB, true);
         }
       } else {
         ok = true;
-        hl = 2;
+        hl = frame_header_len(FLATE_HIP_WRAP_ZLIB, false);
       }
     }
   }
