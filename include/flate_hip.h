@@ -429,7 +429,8 @@ int flate_hip_deflate_fast_spliced_framed(flate_hip_ctx *ctx, const uint8_t *in,
  *     is a bad header.  The trailer is 4 bytes.
  *   Header, FLATE_HIP_WRAP_GZIP (RFC 1952 2.3): 1f 8b, CM = 8, the reserved FLG bits zero; FEXTRA, FNAME, FCOMMENT and
  *     FHCRC are skipped, in that order (the scan for a terminating NUL ends at the member's end).  The trailer is 8
- *     bytes.  One range is one member: a file of several members is several ranges.
+ *     bytes.  One range is one member: a file of several members is several ranges (a BGZF file:
+ *     flate_hip_bgzf_read below finds them itself).
  *   A member too short for its header plus trailer has a bad header.
  *   The raw stream is exactly [member + header length, member end - trailer length): a stream that needs more bytes
  *     than that is FLATE_HIP_E_UNEXPECTED_EOF -- the decoder does not run on into the trailer.  Bytes between the end
@@ -513,6 +514,74 @@ int flate_hip_inflate_spliced_framed(flate_hip_ctx *ctx, const uint8_t *in, uint
                                      uint8_t *out, const uint64_t *out_off, uint64_t *out_len,
                                      int32_t *status, int64_t *err_off,
                                      int32_t *member_status, int64_t *member_err_off, uint32_t flags);
+
+/* -- BGZF files: written and read in one call each ------------------------------------
+ * BGZF is the blocked gzip of the SAM/BAM specification (section 4.1; what bgzip, htslib and tabix read and write): a
+ * gzip file (RFC 1952) of members of at most 65536 bytes, each of which carries its own size in an extra subfield
+ * ('B' 'C', BSIZE = size - 1) and its output size in ISIZE, ended by a canonical empty member.  Such a file is its own
+ * index, so it is the one form of multi-member gzip FILE this engine reads without a side index: member boundaries and
+ * output slots are found on the device from the file's bytes.  gzip -d and every gzip reader read what is written
+ * here.  (Multi-member files WITHOUT 'BC' subfields stay out of scope: several ranges for
+ * flate_hip_inflate_batch_framed.)
+ *
+ * flate_hip_bgzf_write: block k = in[k * block_bytes, min((k + 1) * block_bytes, in_len)), n_blocks = ceil(in_len /
+ * block_bytes); block_bytes 0 = FLATE_HIP_BGZF_BLOCK_DEFAULT, else 1 .. 65535 (one LZ77 window), anything else
+ * FLATE_HIP_E_INVALID.  Member k = 1f 8b 08 04 00 00 00 00 00 ff 06 00 42 43 02 00 (htslib's) | BSIZE, little endian |
+ * exactly the bytes flate_hip_deflate_fast_batch produces for block k under the same flags | the block's CRC-32 and
+ * length, little endian; the members back to back, then the 28-byte EOF marker (the same 16 bytes, 1b 00 03 00, eight
+ * zero bytes).  in_len == 0: the marker alone.  *out_len = the file's size; member_off (HOST, n_blocks + 1 entries,
+ * may be NULL): where every member starts, member_off[n_blocks] = where the marker starts.
+ *   This is the framed encode path: the scan adds 18 + 8 bytes per member and the marker, the pack kernels write into
+ *   the members, the checksums run on the input where it is, the frame kernel writes headers, trailers and the marker.
+ *   A member of more than 65536 bytes cannot be expressed (incompressible blocks near 65535 bytes): decided on the
+ *   device by the scan, FLATE_HIP_E_TOO_LARGE, flate_hip_last_hip_error names the first such block, out must not be
+ *   used.  out_cap: the exact total is enough, to the byte (less: FLATE_HIP_E_OUT_TOO_SMALL); flate_hip_bgzf_bound
+ *   (host only; 0 for a refused block_bytes) always is.  FLATE_HIP_DEVICE_PTRS and FLATE_HIP_COMPAT_GO as in
+ *   flate_hip_deflate_fast_batch_framed; other flags: FLATE_HIP_E_INVALID.  Host pointers: one copy in, one copy out.
+ *
+ * flate_hip_bgzf_index (discovery only): a member at offset p has all of: 1f 8b 08; FLG with FEXTRA set and the
+ * reserved bits zero; XLEN >= 6; inside the XLEN bytes a well-formed run of subfields, the first of which with SI = 'B'
+ * 'C' and SLEN = 2 gives BSIZE; total = BSIZE + 1 >= 12 + XLEN + 8; p + total <= in_len.  The first member is at 0,
+ * member k + 1 starts where member k ends, the file ends where a member ends at in_len.  FNAME, FCOMMENT and FHCRC are
+ * not examined here (the parse kernel handles them at decode time).  Anything else: FLATE_HIP_E_CORRUPT, *err_off = the
+ * offset at which no member could be read, *n_members = the well-formed members in front of it, *out_bytes = 0.
+ *   On success member_off[0 .. n] (member_off[n] = in_len) and out_off[0 .. n] (the exclusive prefix sum of the
+ *   members' ISIZE, out_off[n] = *out_bytes) are exactly what flate_hip_inflate_batch_framed(FLATE_HIP_WRAP_GZIP) takes
+ *   as in_off and out_off; *eof_marker = 1 if the last member is the canonical 28 bytes; *err_off = -1.  Both arrays
+ *   are HOST arrays of index_cap entries, or both NULL: a query that returns only the counts.  index_cap < n + 1:
+ *   FLATE_HIP_E_OUT_TOO_SMALL with the counts set.  in_len == 0: FLATE_HIP_OK, zero members.  More candidates than 32
+ *   bits count: FLATE_HIP_E_TOO_LARGE.  eof_marker and err_off may be NULL.  in: host, or device under
+ *   FLATE_HIP_DEVICE_PTRS (any alignment); nothing outside in[0, in_len) is read.
+ *   How (bgzf_kernels.hip): every offset that passes the rule is a candidate (one pass with 16-byte loads, compacted in
+ *   file order); every candidate finds the candidate at offset + total by binary search; the chain from offset 0 is
+ *   ranked by pointer doubling -- log2 rounds instead of one dependent miss per member.  The result equals the serial
+ *   walk on every input, also where compressed bytes look like member headers.  The kernels are counted in no
+ *   profiling stage.
+ *
+ * flate_hip_bgzf_read: index, then flate_hip_inflate_batch_framed(FLATE_HIP_WRAP_GZIP) over every member into the
+ * dense slots out_off, fed with the index the device has just produced (it comes back to the host once, 16 bytes per
+ * member, behind its counts: decoder routing and checksum planning are host code).  Host pointers: the file is
+ * uploaded once -- index and decode use the same staged copy -- and out[0, *out_len) downloaded once.
+ *   A malformed chain: flate_hip_bgzf_index's return value and *err_off, *bad_member = the count of good members,
+ *   *out_len = 0, nothing is written.  A total above out_cap: FLATE_HIP_E_OUT_TOO_SMALL, *out_len = the size needed,
+ *   nothing is decoded.  Otherwise every member is decoded (a failing member does not stop the others), *out_len =
+ *   out_off[n], and the return value is the first non-zero member status as flate_hip_inflate_batch_framed defines it
+ *   (FLATE_HIP_E_CORRUPT: bad header, CRC or ISIZE mismatch; FLATE_HIP_E_UNEXPECTED_EOF: the raw stream is cut short;
+ *   FLATE_HIP_E_OUT_TOO_SMALL: the member produces more than its ISIZE) with *bad_member = its index and *err_off =
+ *   its file offset; on success 0xffffffff and -1.  n_members, bad_member, err_off and eof_marker may each be NULL.
+ *   The slot-write guarantees of flate_hip_inflate_batch hold. */
+#define FLATE_HIP_BGZF_BLOCK_DEFAULT 65280u /* 0xff00, what bgzip cuts at */
+#define FLATE_HIP_BGZF_MEMBER_MAX 65536u
+#define FLATE_HIP_BGZF_EOF_BYTES 28u
+size_t flate_hip_bgzf_bound(uint64_t in_len, uint32_t block_bytes);
+int flate_hip_bgzf_write(flate_hip_ctx *ctx, const uint8_t *in, uint64_t in_len, uint32_t block_bytes,
+                         uint8_t *out, uint64_t out_cap, uint64_t *out_len, uint64_t *member_off, uint32_t flags);
+int flate_hip_bgzf_index(flate_hip_ctx *ctx, const uint8_t *in, uint64_t in_len, uint64_t index_cap,
+                         uint64_t *member_off, uint64_t *out_off, uint32_t *n_members, uint64_t *out_bytes,
+                         int *eof_marker, int64_t *err_off, uint32_t flags);
+int flate_hip_bgzf_read(flate_hip_ctx *ctx, const uint8_t *in, uint64_t in_len, uint8_t *out, uint64_t out_cap,
+                        uint64_t *out_len, uint32_t *n_members, uint32_t *bad_member, int64_t *err_off,
+                        int *eof_marker, uint32_t flags);
 
 /* -- exchange step (multi-GPU) ---------------------------------------------------
  * SURVEY 8(e) / section 5; no counterpart in the reference (single-threaded, no communication

@@ -98,3 +98,44 @@ int flate_hip_mbt_inflate_spliced_framed(flate_hip_ctx *c, const uint8_t *in, ui
   res[1] = me;
   return rc;
 }
+
+/* -- BGZF files (flate_hip_bgzf_write / _read): the scalar results packed into one array (MoonBit passes no pointers
+ * to scalars).  write: res[0] = the file's size.  read: res[0] = out_len, res[1] = n_members, res[2] = bad_member
+ * (-1: none), res[3] = err_off, res[4] = eof_marker.  query: res[0] = out_bytes, res[1] = n_members, res[2] =
+ * eof_marker, res[3] = err_off -- the size a caller needs before it can make room for flate_hip_mbt_bgzf_read -- */
+uint64_t flate_hip_mbt_bgzf_bound(uint64_t in_len, uint32_t block_bytes) {
+  return (uint64_t)flate_hip_bgzf_bound(in_len, block_bytes);
+}
+int flate_hip_mbt_bgzf_write(flate_hip_ctx *c, const uint8_t *in, uint64_t in_len, uint32_t block_bytes, uint8_t *out,
+                             uint64_t out_cap, int64_t *res, uint32_t flags) {
+  uint64_t len = 0;
+  const int rc = flate_hip_bgzf_write(c, in, in_len, block_bytes, out, out_cap, &len, 0, flags);
+  res[0] = (int64_t)len;
+  return rc;
+}
+int flate_hip_mbt_bgzf_query(flate_hip_ctx *c, const uint8_t *in, uint64_t in_len, int64_t *res) {
+  uint32_t n = 0;
+  uint64_t bytes = 0;
+  int eof = 0;
+  int64_t err = -1;
+  const int rc = flate_hip_bgzf_index(c, in, in_len, 0, 0, 0, &n, &bytes, &eof, &err, 0);
+  res[0] = (int64_t)bytes;
+  res[1] = n;
+  res[2] = eof;
+  res[3] = err;
+  return rc;
+}
+int flate_hip_mbt_bgzf_read(flate_hip_ctx *c, const uint8_t *in, uint64_t in_len, uint8_t *out, uint64_t out_cap,
+                            int64_t *res) {
+  uint64_t len = 0;
+  uint32_t n = 0, bad = 0xffffffffu;
+  int64_t err = -1;
+  int eof = 0;
+  const int rc = flate_hip_bgzf_read(c, in, in_len, out, out_cap, &len, &n, &bad, &err, &eof, 0);
+  res[0] = (int64_t)len;
+  res[1] = n;
+  res[2] = bad == 0xffffffffu ? -1 : (int64_t)bad;
+  res[3] = err;
+  res[4] = eof;
+  return rc;
+}

@@ -56,6 +56,55 @@ inline int spliced_index_check(const uint64_t *bit_off, uint32_t n, const uint64
   return FLATE_HIP_OK;
 }
 
+// ---- BGZF files (flate_hip_bgzf_write / _index / _read) ----
+
+// block_bytes as the caller passes it -> the block size in use (0 = the default), or 0: not 1 .. 65535, one LZ77 window
+inline uint32_t bgzf_block_bytes(uint32_t block_bytes) {
+  if (block_bytes == 0) return FLATE_HIP_BGZF_BLOCK_DEFAULT;
+  return block_bytes <= 65535u ? block_bytes : 0u;
+}
+inline uint64_t bgzf_n_blocks(uint64_t in_len, uint32_t bb) { return in_len / bb + (in_len % bb ? 1u : 0u); }
+// room that is always enough for the file: every block at its raw bound inside 18 + 8 bytes, and the EOF marker
+// (bound: flate_hip_deflate_bound); 0 for a block size that is refused
+inline uint64_t bgzf_file_bound(uint64_t in_len, uint32_t block_bytes, size_t (*bound)(size_t)) {
+  const uint32_t bb = bgzf_block_bytes(block_bytes);
+  if (!bb) return 0;
+  const uint64_t full = in_len / bb, tail = in_len % bb;
+  return full * ((uint64_t)bound(bb) + 26u) + (tail ? (uint64_t)bound((size_t)tail) + 26u : 0u) + FLATE_HIP_BGZF_EOF_BYTES;
+}
+inline int bgzf_write_args(const uint8_t *in, uint64_t in_len, uint32_t block_bytes, const uint8_t *out,
+                           const uint64_t *out_len, uint32_t flags) {
+  if (!out || !out_len || (in_len && !in)) return FLATE_HIP_E_INVALID;
+  if (flags & ~(FLATE_HIP_DEVICE_PTRS | FLATE_HIP_COMPAT_GO)) return FLATE_HIP_E_INVALID;
+  const uint32_t bb = bgzf_block_bytes(block_bytes);
+  if (!bb) return FLATE_HIP_E_INVALID;
+  if (bgzf_n_blocks(in_len, bb) > 0xfffffffeull) return FLATE_HIP_E_TOO_LARGE;
+  return FLATE_HIP_OK;
+}
+// member_off and out_off come together or not at all (the query form)
+inline int bgzf_index_args(const uint8_t *in, uint64_t in_len, const uint64_t *member_off, const uint64_t *out_off,
+                           const uint32_t *n_members, const uint64_t *out_bytes, uint32_t flags) {
+  if (!n_members || !out_bytes || (in_len && !in) || (!member_off != !out_off)) return FLATE_HIP_E_INVALID;
+  return (flags & ~FLATE_HIP_DEVICE_PTRS) ? FLATE_HIP_E_INVALID : FLATE_HIP_OK;
+}
+inline int bgzf_read_args(const uint8_t *in, uint64_t in_len, const uint8_t *out, uint64_t out_cap,
+                          const uint64_t *out_len, uint32_t flags) {
+  if (!out_len || (in_len && !in) || (out_cap && !out)) return FLATE_HIP_E_INVALID;
+  return (flags & ~FLATE_HIP_DEVICE_PTRS) ? FLATE_HIP_E_INVALID : FLATE_HIP_OK;
+}
+// how many candidates the discovery arrays hold on the first attempt (real files: one member per tens of KiB; a file
+// of nothing but empty members has one per 28 bytes and takes the second attempt, sized from the count)
+inline uint32_t bgzf_first_cap(uint64_t in_len) {
+  const uint64_t c = in_len / 1024u + 4096u;
+  return c > 0xfffffff0ull ? 0xfffffff0u : (uint32_t)c;
+}
+// the pointer-doubling rounds for that many candidates: the smallest R with 2^R >= cap + 2
+inline uint32_t bgzf_rounds(uint32_t cap) {
+  uint32_t r = 1;
+  while (r < 32u && (1ull << r) < (uint64_t)cap + 2u) ++r;
+  return r;
+}
+
 // what a decode call returns when it has run: FLATE_HIP_OK or the first non-zero status of a stream
 inline bool is_stream_status(int rc) {
   return rc == FLATE_HIP_OK || rc == FLATE_HIP_E_OUT_TOO_SMALL || rc == FLATE_HIP_E_CORRUPT || rc == FLATE_HIP_E_UNEXPECTED_EOF;

@@ -15,6 +15,7 @@
 #include <stdexcept>
 
 #include "api_checks.h"
+#include "bgzf_rule.h"
 
 using namespace flate;
 using namespace flate_host;
@@ -787,7 +788,7 @@ static int deflate_common(flate_hip_ctx *c, const uint8_t *in, const uint64_t *i
       if ((rc = dictid_stage(c, FR->dicts, FR->dict_off, FR->n_dicts, flags))) return rc;
     }
   }
-  HIP_TRY(c, hipMemsetAsync(c->d_status.p, 0, 4, c->stream));
+  HIP_TRY(c, hipMemsetAsync(c->d_status.p, 0, 8, c->stream));  // (word 1: frame_scan_kernel's first oversized BGZF member)
   // One wavefront per block in the histogram and pack kernels when the streams have many blocks
   // (4096 streams of four windows are 4096 wavefronts per stream-kernel, a quarter of what fills
   // the chip).  Every stream needs at least one block (a stream without any has nobody to write
@@ -886,11 +887,16 @@ static int deflate_common(flate_hip_ctx *c, const uint8_t *in, const uint64_t *i
     return rc;
   if (spliced && (rc = ctl_down(c, &c->h_total_bytes, (uint64_t *)c->d_out_len.p + n, 8))) return rc;
   if ((rc = ctl_down(c, &c->h_status_word, c->d_status.p, 4))) return rc;
+  const bool bgzf = FR && FR->wrap == kWrapBgzf;
+  if (bgzf && (rc = ctl_down(c, &c->h_status_aux, (int *)c->d_status.p + 1, 4))) return rc;
   HIP_TRY(c, hipGetLastError());
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   ctl_finish(c);
+  if (bgzf && c->h_status_word == FLATE_HIP_E_TOO_LARGE)
+    c->hip_err = "BGZF: block " + std::to_string((uint32_t)c->h_status_aux) + " compresses to a member of more than 65536 bytes";
   if (c->h_status_word) return encoder_status(c, c->h_status_word);
-  produced = spliced ? c->h_total_bytes + f_hl + f_tl : out_off[n];
+  // (a BGZF file: the members, then the EOF marker frame_write_kernel has put behind them)
+  produced = spliced ? c->h_total_bytes + f_hl + f_tl : out_off[n] + (bgzf ? (uint64_t)kBgzfEofLen : 0ull);
   if (total_bytes) *total_bytes = produced;
   if (!dev) {
     HIP_TRY(c, hipMemcpyAsync(out, c->d_out.p, produced, hipMemcpyDeviceToHost, c->stream));
@@ -1683,6 +1689,51 @@ int flate_hip_deflate_fast_spliced_framed(flate_hip_ctx *c, const uint8_t *in, c
     const FrameReq FR{wrap, nullptr, nullptr, nullptr, 0};
     return deflate_common(c, in, in_off, n, out, out_cap, bit_off, flags, true, out_len, nullptr, &FR);
   } catch (const std::exception &e) {
+    c->hip_err = e.what();
+    return FLATE_HIP_E_INTERNAL;
+  }
+}
+
+// ---- BGZF files (the writing half; reading: flate_api_inflate.hip) ----
+
+size_t flate_hip_bgzf_bound(uint64_t in_len, uint32_t block_bytes) {
+  return (size_t)bgzf_file_bound(in_len, block_bytes, flate_hip_deflate_bound);
+}
+
+int flate_hip_bgzf_write(flate_hip_ctx *c, const uint8_t *in, uint64_t in_len, uint32_t block_bytes, uint8_t *out,
+                         uint64_t out_cap, uint64_t *out_len, uint64_t *member_off, uint32_t flags) {
+  // every check before any HIP call
+  if (!c) return FLATE_HIP_E_INVALID;
+  int rc = bgzf_write_args(in, in_len, block_bytes, out, out_len, flags);
+  if (rc) return rc;
+  c->hip_err.clear();
+  const uint32_t bb = bgzf_block_bytes(block_bytes);
+  const uint32_t n = (uint32_t)bgzf_n_blocks(in_len, bb);
+  if (n == 0) {  // the EOF marker alone
+    uint8_t eof[kBgzfEofLen];
+    for (uint32_t i = 0; i < kBgzfEofLen; ++i) eof[i] = bgzf_eof_byte(i);
+    if (out_cap < kBgzfEofLen) return FLATE_HIP_E_OUT_TOO_SMALL;
+    if (flags & FLATE_HIP_DEVICE_PTRS) {
+      HIP_TRY(c, hipSetDevice(c->device));
+      HIP_TRY(c, hipMemcpyAsync(out, eof, kBgzfEofLen, hipMemcpyHostToDevice, c->stream));
+      HIP_TRY(c, hipStreamSynchronize(c->stream));
+    } else {
+      memcpy(out, eof, kBgzfEofLen);
+    }
+    *out_len = kBgzfEofLen;
+    if (member_off) member_off[0] = 0;
+    return FLATE_HIP_OK;
+  }
+  try {
+    // the blocks as the streams of a batch: the framed encode path with the internal wrap (host pointers: one copy
+    // in -- the checksums run on it --, compress, one copy out)
+    std::vector<uint64_t> in_off((size_t)n + 1), off;
+    for (uint32_t k = 0; k < n; ++k) in_off[k] = (uint64_t)k * bb;
+    in_off[n] = in_len;
+    if (!member_off) off.resize((size_t)n + 1), member_off = off.data();
+    const FrameReq FR{kWrapBgzf, nullptr, nullptr, nullptr, 0};
+    return deflate_common(c, in, in_off.data(), n, out, out_cap, member_off, flags, false, out_len, nullptr, &FR);
+  } catch (const std::exception &e) {  // (out of host memory in an index vector)
     c->hip_err = e.what();
     return FLATE_HIP_E_INTERNAL;
   }

@@ -11,6 +11,7 @@
 #include <stdexcept>
 
 #include "api_checks.h"
+#include "bgzf_rule.h"
 
 using namespace flate;
 using namespace flate_host;
@@ -593,6 +594,193 @@ int flate_hip_inflate_spliced_framed(flate_hip_ctx *c, const uint8_t *in, uint64
     if (member_status) *member_status = SM.status;
     if (member_err_off) *member_err_off = SM.err_off;
     return rc;
+  } catch (const std::exception &e) {  // (out of host memory in an index vector)
+    c->hip_err = e.what();
+    return FLATE_HIP_E_INTERNAL;
+  }
+}
+
+}  // extern "C"
+
+// ---- BGZF files: member discovery (bgzf_kernels.hip) and the read built on it ----
+namespace {
+
+// The discovery kernels over d_in[0, in_len) (DEVICE memory), queued on the ctx's stream; H = their result words once
+// the stream has drained (the call's synchronisation), P.member_off / P.out_off = the index, still on the device.  The
+// arrays are sized for bgzf_first_cap candidates; a file with more (H.n_cand, counted by the first attempt) takes a
+// second attempt sized from that count.  Counted in no profiling stage.
+int bgzf_discover(flate_hip_ctx *c, const uint8_t *d_in, uint64_t in_len, BgzfHead &H, BgzfParams &P) {
+  const uint64_t A = reinterpret_cast<uintptr_t>(d_in) & 15u;
+  const uint64_t tiles = (A + in_len + kBgzfTile - 1) / kBgzfTile;
+  if (tiles > 0x7fffffffull) return FLATE_HIP_E_TOO_LARGE;
+  uint32_t cap = bgzf_first_cap(in_len);
+  for (int attempt = 0; attempt < 2; ++attempt) {
+    if (cap > 0x7ffffff0u) return FLATE_HIP_E_TOO_LARGE;
+    const uint32_t rounds = bgzf_rounds(cap);
+    P = BgzfParams{};
+    P.in = d_in;
+    P.in_len = in_len;
+    P.n_tiles = (uint32_t)tiles;
+    P.cap = cap;
+    P.path_len = 1u << rounds;
+    size_t at = 0;
+    auto carve = [&](size_t bytes) {
+      const size_t here = at;
+      at += (bytes + 255) & ~(size_t)255;
+      return here;
+    };
+    const size_t o_head = carve(sizeof(BgzfHead)), o_tile = carve(((size_t)P.n_tiles + 1) * 4),
+                 o_coff = carve((size_t)cap * 8), o_ctot = carve((size_t)cap * 4), o_j0 = carve(((size_t)cap + 2) * 4),
+                 o_j1 = carve(((size_t)cap + 2) * 4), o_path = carve((size_t)P.path_len * 4),
+                 o_isize = carve((size_t)cap * 4), o_moff = carve(((size_t)cap + 1) * 8),
+                 o_ooff = carve(((size_t)cap + 1) * 8);
+    const int rc = ensure(c, c->d_bgzf, at);  // (a failed allocation is FLATE_HIP_E_HIP, never a truncated result)
+    if (rc) return rc;
+    uint8_t *b = (uint8_t *)c->d_bgzf.p;
+    P.head = (BgzfHead *)(b + o_head);
+    P.tile_cnt = (uint32_t *)(b + o_tile);
+    P.cand_off = (uint64_t *)(b + o_coff);
+    P.cand_total = (uint32_t *)(b + o_ctot);
+    P.jump[0] = (uint32_t *)(b + o_j0);
+    P.jump[1] = (uint32_t *)(b + o_j1);
+    P.path = (uint32_t *)(b + o_path);
+    P.isize = (uint32_t *)(b + o_isize);
+    P.member_off = (uint64_t *)(b + o_moff);
+    P.out_off = (uint64_t *)(b + o_ooff);
+    const uint32_t node_blocks = (uint32_t)(((uint64_t)cap + 2 + 255) / 256);
+    hipLaunchKernelGGL(bgzf_count_kernel, dim3(P.n_tiles), dim3(256), 0, c->stream, P);
+    hipLaunchKernelGGL(bgzf_scan_kernel, dim3(1), dim3(1024), 0, c->stream, P);
+    hipLaunchKernelGGL(bgzf_fill_kernel, dim3(P.n_tiles), dim3(256), 0, c->stream, P);
+    hipLaunchKernelGGL(bgzf_link_kernel, dim3(node_blocks), dim3(256), 0, c->stream, P);
+    for (uint32_t j = 0; j < rounds; ++j)
+      hipLaunchKernelGGL(bgzf_round_kernel, dim3(node_blocks), dim3(256), 0, c->stream, P, j);
+    hipLaunchKernelGGL(bgzf_finish_kernel, dim3((P.path_len + 255) / 256), dim3(256), 0, c->stream, P);
+    hipLaunchKernelGGL(bgzf_out_scan_kernel, dim3(1), dim3(1024), 0, c->stream, P);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(&H, P.head, sizeof H, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (H.n_cand <= cap) return FLATE_HIP_OK;
+    // more candidates than the arrays hold: nothing behind the scan has run; once more, sized from the count
+    cap = H.n_cand;
+  }
+  c->hip_err = "BGZF discovery: the candidate count changed between two passes";
+  return FLATE_HIP_E_INTERNAL;
+}
+
+// in[0, in_len) on the device: the caller's buffer, or the ctx's staged copy of it
+int bgzf_stage(flate_hip_ctx *c, const uint8_t *in, uint64_t in_len, uint32_t flags, const uint8_t **d_in) {
+  HIP_TRY(c, hipSetDevice(c->device));
+  *d_in = in;
+  if (flags & FLATE_HIP_DEVICE_PTRS) return FLATE_HIP_OK;
+  const int rc = ensure(c, c->d_in, in_len + 16);
+  if (rc) return rc;
+  HIP_TRY(c, hipMemcpyAsync(c->d_in.p, in, in_len, hipMemcpyHostToDevice, c->stream));
+  *d_in = (const uint8_t *)c->d_in.p;
+  return FLATE_HIP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int flate_hip_bgzf_index(flate_hip_ctx *c, const uint8_t *in, uint64_t in_len, uint64_t index_cap, uint64_t *member_off,
+                         uint64_t *out_off, uint32_t *n_members, uint64_t *out_bytes, int *eof_marker, int64_t *err_off,
+                         uint32_t flags) {
+  // every check before any HIP call
+  if (!c) return FLATE_HIP_E_INVALID;
+  int rc = bgzf_index_args(in, in_len, member_off, out_off, n_members, out_bytes, flags);
+  if (rc) return rc;
+  c->hip_err.clear();
+  *n_members = 0, *out_bytes = 0;
+  if (eof_marker) *eof_marker = 0;
+  if (err_off) *err_off = -1;
+  if (in_len == 0) {
+    if (member_off && index_cap < 1) return FLATE_HIP_E_OUT_TOO_SMALL;
+    if (member_off) member_off[0] = 0, out_off[0] = 0;
+    return FLATE_HIP_OK;
+  }
+  const uint8_t *d_in = nullptr;
+  if ((rc = bgzf_stage(c, in, in_len, flags, &d_in))) return rc;
+  BgzfHead H{};
+  BgzfParams P{};
+  if ((rc = bgzf_discover(c, d_in, in_len, H, P))) return rc;
+  *n_members = H.n_members;
+  if (H.rc) {
+    if (err_off) *err_off = H.err_off;
+    return H.rc;
+  }
+  *out_bytes = H.out_bytes;
+  if (eof_marker) *eof_marker = (int)H.eof_marker;
+  if (!member_off) return FLATE_HIP_OK;
+  const uint64_t entries = (uint64_t)H.n_members + 1;
+  if (index_cap < entries) return FLATE_HIP_E_OUT_TOO_SMALL;
+  HIP_TRY(c, hipMemcpyAsync(member_off, P.member_off, entries * 8, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(out_off, P.out_off, entries * 8, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return FLATE_HIP_OK;
+}
+
+int flate_hip_bgzf_read(flate_hip_ctx *c, const uint8_t *in, uint64_t in_len, uint8_t *out, uint64_t out_cap,
+                        uint64_t *out_len, uint32_t *n_members, uint32_t *bad_member, int64_t *err_off, int *eof_marker,
+                        uint32_t flags) {
+  // every check before any HIP call
+  if (!c) return FLATE_HIP_E_INVALID;
+  int rc = bgzf_read_args(in, in_len, out, out_cap, out_len, flags);
+  if (rc) return rc;
+  c->hip_err.clear();
+  *out_len = 0;
+  if (n_members) *n_members = 0;
+  if (bad_member) *bad_member = 0xffffffffu;
+  if (err_off) *err_off = -1;
+  if (eof_marker) *eof_marker = 0;
+  if (in_len == 0) return FLATE_HIP_OK;
+  try {
+    const bool dev = (flags & FLATE_HIP_DEVICE_PTRS) != 0;
+    const uint8_t *d_in = nullptr;
+    if ((rc = bgzf_stage(c, in, in_len, flags, &d_in))) return rc;
+    BgzfHead H{};
+    BgzfParams P{};
+    if ((rc = bgzf_discover(c, d_in, in_len, H, P))) return rc;
+    const uint32_t n = H.n_members;
+    if (n_members) *n_members = n;
+    if (H.rc) {  // a malformed chain: nothing is decoded, nothing is written
+      if (bad_member) *bad_member = n;
+      if (err_off) *err_off = H.err_off;
+      return H.rc;
+    }
+    if (eof_marker) *eof_marker = (int)H.eof_marker;
+    *out_len = H.out_bytes;
+    if (H.out_bytes > out_cap) return FLATE_HIP_E_OUT_TOO_SMALL;
+    // the index comes back once, 16 bytes per member: the decoders' routing and the checksum plan are host code
+    std::vector<uint64_t> moff((size_t)n + 1), ooff((size_t)n + 1), olen(n);
+    std::vector<int32_t> st(n);
+    std::vector<int64_t> eo(n);
+    HIP_TRY(c, hipMemcpyAsync(moff.data(), P.member_off, ((size_t)n + 1) * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(ooff.data(), P.out_off, ((size_t)n + 1) * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if ((rc = inflate_batch_ranges(moff.data(), n, ooff.data(), 0))) return rc;
+    uint8_t *d_out = out;
+    if (!dev) {
+      if ((rc = ensure(c, c->d_out, H.out_bytes + 16))) return rc;
+      d_out = (uint8_t *)c->d_out.p;
+    }
+    // the framed gzip read over the staged copy, fed with the index the device has just produced
+    const InfFrame FRD{FLATE_HIP_WRAP_GZIP, nullptr, nullptr, 0, nullptr};
+    rc = inflate_common(c, {d_in, moff.data(), n, d_out, ooff.data(), olen.data(), st.data(), eo.data(),
+                            flags | FLATE_HIP_DEVICE_PTRS, 0},
+                        nullptr, &FRD);
+    if (!is_stream_status(rc)) return rc;
+    if (!dev && H.out_bytes) {
+      HIP_TRY(c, hipMemcpyAsync(out, d_out, H.out_bytes, hipMemcpyDeviceToHost, c->stream));
+      HIP_TRY(c, hipStreamSynchronize(c->stream));
+    }
+    for (uint32_t i = 0; i < n; ++i)
+      if (st[i]) {
+        if (bad_member) *bad_member = i;
+        if (err_off) *err_off = (int64_t)moff[i];
+        return st[i];
+      }
+    return FLATE_HIP_OK;
   } catch (const std::exception &e) {  // (out of host memory in an index vector)
     c->hip_err = e.what();
     return FLATE_HIP_E_INTERNAL;

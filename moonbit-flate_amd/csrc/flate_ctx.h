@@ -67,11 +67,14 @@ struct flate_hip_ctx {
   // flate_hip_inflate_spliced_framed (it shares d_frame_off: the index counted from the member's first byte,
   // d_frame_sums: the pieces' sums, d_rd_bad: the header verdict per piece): the one member's words (FrameOne)
   DevBuf d_rd_one;
+  // flate_hip_bgzf_index / _read: the discovery kernels' arrays (BgzfParams), carved from one buffer
+  DevBuf d_bgzf;
   hipStream_t guest_stream = nullptr;
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
   int guest_blocks = 0;      // 0 = guest kernel off
   uint32_t guest_min = 1280; // below this many streams (5 per CU) the guests stay idle: one block per stream
   int32_t h_status_word = 0;  // landing pads of small async D2H copies
+  int32_t h_status_aux = 0;   // (flate_hip_bgzf_write: the first block whose member BSIZE cannot express)
   uint64_t h_total_bytes = 0;
   uint32_t num_cus = 256;
   flate::InflateOpts inflate;  // the "inflate_*" options (inflate_route.h)

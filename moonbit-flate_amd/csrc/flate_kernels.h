@@ -9,14 +9,18 @@ namespace flate {
 // A container's constants (RFC 1950 / RFC 1952), for the kernels of frame_kernels.hip and every host site.
 // wrap: FLATE_HIP_WRAP_ZLIB / _GZIP.  The header as this library WRITES it (a member that is read may carry a longer
 // gzip header: frame_parse_kernel); with_dict: zlib's FDICT + DICTID.
+// kWrapBgzf: the members of a BGZF file (flate_hip_bgzf_write) -- gzip members with the 18-byte header that carries
+// BSIZE, followed by the 28-byte EOF marker.  INTERNAL: the public *_framed calls refuse every wrap above _GZIP.
+constexpr uint32_t kWrapBgzf = 3u;
 FLATE_HD uint32_t frame_header_len(uint32_t wrap, bool with_dict) {
-  return wrap == FLATE_HIP_WRAP_GZIP ? 10u : (with_dict ? 6u : 2u);
+  return wrap == kWrapBgzf ? 18u : wrap == FLATE_HIP_WRAP_GZIP ? 10u : (with_dict ? 6u : 2u);
 }
-FLATE_HD uint32_t frame_trailer_len(uint32_t wrap) { return wrap == FLATE_HIP_WRAP_GZIP ? 8u : 4u; }
+FLATE_HD uint32_t frame_trailer_len(uint32_t wrap) { return (wrap == FLATE_HIP_WRAP_GZIP || wrap == kWrapBgzf) ? 8u : 4u; }
 // the shortest member: the header without a dictionary, nothing, the trailer
 FLATE_HD uint32_t frame_min_len(uint32_t wrap) { return frame_header_len(wrap, false) + frame_trailer_len(wrap); }
 FLATE_HD uint32_t frame_sum_kind(uint32_t wrap) {
-  return wrap == FLATE_HIP_WRAP_GZIP ? (uint32_t)FLATE_HIP_CHECKSUM_CRC32 : (uint32_t)FLATE_HIP_CHECKSUM_ADLER32;
+  return (wrap == FLATE_HIP_WRAP_GZIP || wrap == kWrapBgzf) ? (uint32_t)FLATE_HIP_CHECKSUM_CRC32
+                                                            : (uint32_t)FLATE_HIP_CHECKSUM_ADLER32;
 }
 
 }  // namespace flate
@@ -252,7 +256,8 @@ struct FrameParams {
   uint64_t out_cap;
   uint32_t n_streams;
   uint32_t wrap;
-  int *status;              // frame_scan_kernel: FLATE_HIP_E_OUT_TOO_SMALL if the members exceed out_cap
+  int *status;              // frame_scan_kernel: FLATE_HIP_E_OUT_TOO_SMALL if the members exceed out_cap; kWrapBgzf:
+                            // FLATE_HIP_E_TOO_LARGE if a member exceeds 65536 bytes, status[1] = the first such block
 };
 // scan_sizes_kernel for members: exclusive scan of header + out_len + trailer
 __global__ void frame_scan_kernel(FrameParams P);
@@ -327,6 +332,46 @@ struct FrameSplicedParams {
 };
 __global__ void frame_rebase_kernel(FrameSplicedParams P);
 __global__ void frame_verdict_spliced_kernel(FrameSplicedParams P);
+
+// BGZF member discovery (bgzf_kernels.hip; flate_hip_bgzf_index / _read): the members of a file form a linked list
+// through their BSIZE fields, ranked here in parallel.  Every offset that passes the member rule (bgzf_rule.h) is a
+// CANDIDATE; the candidates are compacted in file order (count per 4 KiB tile, scan, fill), every candidate finds the
+// one at offset + total by binary search (in_len: the terminal node n_cand, nothing: the dead node n_cand + 1), and
+// the chain from candidate 0 is ranked by pointer doubling.  All loops are bounded by values the host computed from
+// in_len and cap before the launches; no kernel waits for another workgroup.
+struct BgzfHead {          // the result words, read back as one block
+  uint64_t out_bytes;      // sum of the members' ISIZE (0 unless rc == 0)
+  int64_t err_off;         // the offset at which no member could be read, or -1
+  uint32_t n_members;      // well-formed members from offset 0
+  int32_t rc;              // 0 or FLATE_HIP_E_CORRUPT
+  uint32_t eof_marker;     // the last member is the canonical 28 bytes
+  uint32_t n_cand;         // candidates counted (saturating); above cap: nothing else here is valid, run again
+};
+struct BgzfParams {
+  const uint8_t *in;       // any byte alignment
+  uint64_t in_len;
+  uint32_t n_tiles;        // 4 KiB tiles on the 16-byte grid of in's ADDRESS
+  uint32_t cap;            // candidates the arrays hold
+  uint32_t path_len;       // a power of two >= cap + 2
+  uint32_t *tile_cnt;      // n_tiles + 1: candidates per tile, then their exclusive scan
+  uint64_t *cand_off;      // cap
+  uint32_t *cand_total;    // cap
+  uint32_t *jump[2];       // cap + 2 each: the successor after 2^j steps, double-buffered
+  uint32_t *path;          // path_len: node r steps from candidate 0
+  uint32_t *isize;         // cap: per member
+  uint64_t *member_off;    // cap + 1
+  uint64_t *out_off;       // cap + 1
+  BgzfHead *head;
+};
+__global__ void bgzf_count_kernel(BgzfParams P);
+__global__ void bgzf_scan_kernel(BgzfParams P);
+__global__ void bgzf_fill_kernel(BgzfParams P);
+__global__ void bgzf_link_kernel(BgzfParams P);
+__global__ void bgzf_round_kernel(BgzfParams P, uint32_t j);
+__global__ void bgzf_finish_kernel(BgzfParams P);
+__global__ void bgzf_out_scan_kernel(BgzfParams P);
+constexpr uint32_t kBgzfTile = 4096;
+
 size_t inflate_simt_lds_bytes(int lanes_per_wave);  // dynamic LDS of that launch
 size_t inflate_simt_lens_bytes(uint32_t blocks);    // global scratch of that launch (InfParams::simt_lens)
 

@@ -22,6 +22,7 @@
 // frame_rebase_kernel (the index moved behind the header) and frame_verdict_spliced_kernel (FrameSplicedParams).
 #include <hip/hip_runtime.h>
 
+#include "bgzf_rule.h"
 #include "flate_hip.h"
 #include "flate_kernels.h"
 
@@ -31,7 +32,7 @@ namespace {
 
 // bytes in front of / behind stream i's raw stream
 __device__ inline uint32_t header_len(const FrameParams &P, uint32_t i) {
-  return frame_header_len(P.wrap, P.wrap != FLATE_HIP_WRAP_GZIP && P.dict_of && P.dict_of[i] != FLATE_HIP_NO_DICT);
+  return frame_header_len(P.wrap, P.wrap == FLATE_HIP_WRAP_ZLIB && P.dict_of && P.dict_of[i] != FLATE_HIP_NO_DICT);
 }
 __device__ inline uint32_t trailer_len(const FrameParams &P) { return frame_trailer_len(P.wrap); }
 
@@ -48,15 +49,17 @@ __device__ inline void put_le32(uint8_t *p, uint32_t v) {
 __global__ __launch_bounds__(1024) void frame_scan_kernel(FrameParams P) {
   __shared__ uint64_t wtot[16];
   __shared__ uint64_t carry_s;
+  __shared__ uint32_t big_s;  // kWrapBgzf: the first member that BSIZE cannot express
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const uint32_t hi = P.n_streams;
   const uint32_t tl = trailer_len(P);
-  if (tid == 0) carry_s = 0ull;
+  if (tid == 0) carry_s = 0ull, big_s = 0xffffffffu;
   __syncthreads();
   for (uint32_t base = 0; base < hi; base += 1024) {
     const uint32_t i = base + (uint32_t)tid;
     const uint32_t hl = i < hi ? header_len(P, i) : 0u;
     const uint64_t v = i < hi ? P.out_len[i] + hl + tl : 0ull;
+    if (P.wrap == kWrapBgzf && v > (uint64_t)kBgzfMemberMax) atomicMin(&big_s, i);
     uint64_t x = v;
     for (int d = 1; d < 64; d <<= 1) {
       const uint64_t o = __shfl_up(x, d);
@@ -79,14 +82,25 @@ __global__ __launch_bounds__(1024) void frame_scan_kernel(FrameParams P) {
   if (tid == 0) {
     P.member_off[P.n_streams] = carry_s;
     P.payload_off[P.n_streams] = carry_s;
-    if (carry_s > P.out_cap) *P.status = FLATE_HIP_E_OUT_TOO_SMALL;
+    // (a BGZF file ends with the EOF marker behind its last member)
+    const uint64_t total = carry_s + (P.wrap == kWrapBgzf ? (uint64_t)kBgzfEofLen : 0ull);
+    if (total > P.out_cap) *P.status = FLATE_HIP_E_OUT_TOO_SMALL;
+    if (big_s != 0xffffffffu) {
+      P.status[1] = (int)big_s;
+      *P.status = FLATE_HIP_E_TOO_LARGE;
+    }
   }
 }
 
 __global__ __launch_bounds__(256) void frame_write_kernel(FrameParams P) {
   const uint32_t i = blockIdx.x * 256u + threadIdx.x;
   const uint32_t members = P.member_off ? P.n_streams : 1u;
-  if (i >= members || *P.status != 0) return;  // (a status: the scan found the output too small -- nothing may be written)
+  if (*P.status != 0) return;  // (a status: the scan found the output too small -- nothing may be written)
+  if (P.wrap == kWrapBgzf && i == members) {  // the EOF marker behind the last member (the scan has counted it)
+    uint8_t *e = P.out + P.member_off[members];
+    for (uint32_t b = 0; b < kBgzfEofLen; ++b) e[b] = bgzf_eof_byte(b);
+  }
+  if (i >= members) return;
   const bool one = P.member_off == nullptr;
   const uint32_t hl = one ? frame_header_len(P.wrap, false) : header_len(P, i);
   const uint64_t at = one ? 0ull : P.member_off[i];
@@ -96,7 +110,15 @@ __global__ __launch_bounds__(256) void frame_write_kernel(FrameParams P) {
   uint8_t *h = P.out + at;
   uint8_t *t = h + hl + raw;
   const uint32_t sum = P.sums[i];
-  if (P.wrap == FLATE_HIP_WRAP_GZIP) {
+  if (P.wrap == kWrapBgzf) {
+    // htslib's header: FEXTRA, XLEN = 6, the subfield 'B' 'C' with BSIZE = the member's size - 1 (the scan has
+    // refused the call if that does not fit 16 bits)
+    const uint32_t bsize = (uint32_t)(hl + raw + trailer_len(P)) - 1u;
+    for (uint32_t b = 0; b < 16u; ++b) h[b] = bgzf_header_byte(b);
+    h[16] = (uint8_t)bsize, h[17] = (uint8_t)(bsize >> 8);
+    put_le32(t, sum);
+    put_le32(t + 4, (uint32_t)in_len);
+  } else if (P.wrap == FLATE_HIP_WRAP_GZIP) {
     // ID1 ID2, CM = 8, FLG = 0, MTIME = 0, XFL = 4 (fastest), OS = 255 (unknown): RFC 1952 2.3
     h[0] = 0x1f, h[1] = 0x8b, h[2] = 8, h[3] = 0;
     h[4] = h[5] = h[6] = h[7] = 0;

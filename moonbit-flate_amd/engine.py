@@ -3,6 +3,7 @@
 The C ABI (include/flate_hip.h) is the product boundary; this module only marshals
 numpy / torch buffers into it.  PyTorch is used for device memory and streams only.
 """
+import collections
 import ctypes as C
 import os
 import zlib
@@ -47,6 +48,18 @@ def frame_overhead(wrap, with_dict=False):
     """Bytes a zlib / gzip member adds around its raw stream (flate_hip_frame_overhead)."""
     return int(_lib.load().flate_hip_frame_overhead(_wrap_code(wrap) if isinstance(wrap, str) else int(wrap),
                                                     1 if with_dict else 0))
+
+
+BGZF_BLOCK_DEFAULT = 65280  # FLATE_HIP_BGZF_BLOCK_DEFAULT
+BGZF_MEMBER_MAX = 65536
+BGZF_EOF = bytes.fromhex("1f8b08040000000000ff0600424302001b0003000000000000000000")
+BgzfIndex = collections.namedtuple("BgzfIndex", "rc n_members out_bytes eof_marker err_off member_off out_off")
+BgzfRead = collections.namedtuple("BgzfRead", "rc out_len n_members bad_member err_off eof_marker")
+
+
+def bgzf_bound(n, block_bytes=0):
+    """Room that always holds the BGZF file of n input bytes (flate_hip_bgzf_bound; 0: block_bytes is refused)."""
+    return int(_lib.load().flate_hip_bgzf_bound(int(n), int(block_bytes)))
 
 
 def synth(kind, n_streams, stream_len, seed=None, first_stream=0, nthreads=None):
@@ -374,6 +387,116 @@ class FlateEngine:
         call(out.data_ptr() if device else out.ctypes.data, out_off.ctypes.data, 0)
         self.last_framed_read = (err_off[:n], dict_used[:n])
         return out, out_off, out_len[:n], status[:n]
+
+    @staticmethod
+    def _bgzf_in(data):
+        """(data, pointer, bytes, device) of a numpy uint8 array or a torch uint8 CUDA tensor."""
+        if _is_torch(data):
+            import torch
+            assert data.dtype == torch.uint8 and data.is_cuda and data.is_contiguous()
+            return data, (data.data_ptr() if data.numel() else None), data.numel(), True
+        data = np.ascontiguousarray(np.frombuffer(data, dtype=np.uint8) if isinstance(data, (bytes, bytearray))
+                                    else data, dtype=np.uint8)
+        return data, (data.ctypes.data if data.size else None), data.size, False
+
+    def bgzf_write(self, data, block_bytes=0, compat_go=False, out=None, index=False, out_cap=None):
+        """data as ONE BGZF file (the blocked gzip of the SAM/BAM specification; flate_hip_bgzf_write): a member of
+        its own for every block_bytes of input (0: 65280, what bgzip cuts at; at most 65535), each with its size in
+        a 'BC' extra subfield, then the 28-byte EOF marker -- a .gz file that gzip -d, gzip.decompress and every
+        BGZF reader turn back into data, written on the GPU by one call.  data: numpy uint8 / bytes (host; returns
+        the file as bytes) or a torch uint8 CUDA tensor (data and file stay on the device; returns (out, out_len),
+        the file in out[:out_len]).  index=True: member_off (numpy uint64[n_blocks + 1]) is appended to the result.
+        A block that compresses to more than 65536 bytes: FlateError(E_TOO_LARGE) naming it."""
+        data, in_ptr, n, device = self._bgzf_in(data)
+        if out_cap is None and out is None:
+            out_cap = bgzf_bound(n, block_bytes)
+            if out_cap == 0:
+                raise FlateError(E_INVALID, "bgzf_write: block_bytes must be 0 or 1 .. 65535")
+        if device:
+            import torch
+            if out is None:
+                out = torch.empty(max(int(out_cap), 32), dtype=torch.uint8, device=data.device)
+            else:
+                _check_out(out, data, 0, "bgzf_write")
+            cap = out.numel() if out_cap is None else min(int(out_cap), out.numel())
+            out_ptr = out.data_ptr()
+        else:
+            if out is None:
+                out = np.empty(max(int(out_cap), 32), dtype=np.uint8)
+            else:
+                _check_out(out, data, 0, "bgzf_write")
+            cap = out.size if out_cap is None else min(int(out_cap), out.size)
+            out_ptr = out.ctypes.data
+        bb = int(block_bytes) if block_bytes else BGZF_BLOCK_DEFAULT
+        member_off = np.zeros((n + bb - 1) // max(bb, 1) + 1, dtype=np.uint64)
+        out_len = C.c_uint64(0)
+        self._check(self._L.flate_hip_bgzf_write(self._ctx, in_ptr, n, int(block_bytes), out_ptr, cap,
+                                                 C.byref(out_len), member_off.ctypes.data,
+                                                 self._flags(compat_go, False, device)))
+        res = (out, int(out_len.value)) if device else (bytes(out[:int(out_len.value)]),)
+        if index:
+            res = res + (member_off,)
+        return res if len(res) > 1 else res[0]
+
+    def bgzf_index(self, data, index_cap=None, query=False):
+        """Where the members of a BGZF file start and where their output goes, found on the GPU from the file's bytes
+        (flate_hip_bgzf_index) -> BgzfIndex(rc, n_members, out_bytes, eof_marker, err_off, member_off, out_off).
+        rc 0: member_off / out_off (numpy uint64[n_members + 1]) are what inflate_batch_framed(..., "gzip") takes as
+        in_off / the cumulative out_sizes.  rc -4 (FLATE_HIP_E_CORRUPT): no member could be read at err_off, behind
+        n_members good ones.  query=True: only the counts (the arrays are None); index_cap: the arrays' size (default:
+        what a query says is needed; too small: rc -2).  Other failures raise FlateError."""
+        data, in_ptr, n, device = self._bgzf_in(data)
+        flags = DEVICE_PTRS if device else 0
+        nm, ob, eof, eo = C.c_uint32(0), C.c_uint64(0), C.c_int(0), C.c_int64(-1)
+
+        def call(cap, a, b):
+            rc = self._L.flate_hip_bgzf_index(self._ctx, in_ptr, n, cap, a, b, C.byref(nm), C.byref(ob), C.byref(eof),
+                                              C.byref(eo), flags)
+            if rc not in (0, E_CORRUPT, E_OUT_TOO_SMALL):
+                self._check(rc)
+            return rc
+
+        if query or index_cap is None:
+            rc = call(0, None, None)
+            if query or rc != 0:
+                return BgzfIndex(rc, int(nm.value), int(ob.value), int(eof.value), int(eo.value), None, None)
+            index_cap = int(nm.value) + 1
+        moff = np.zeros(max(int(index_cap), 1), dtype=np.uint64)
+        ooff = np.zeros(max(int(index_cap), 1), dtype=np.uint64)
+        rc = call(int(index_cap), moff.ctypes.data, ooff.ctypes.data)
+        k = int(nm.value) + 1
+        ok = rc == 0
+        return BgzfIndex(rc, int(nm.value), int(ob.value), int(eof.value), int(eo.value),
+                         moff[:k] if ok else None, ooff[:k] if ok else None)
+
+    def bgzf_read(self, data, out=None, out_cap=None):
+        """A BGZF file -- bgzf_write's, bgzip's, htslib's -- back into its bytes by one call (flate_hip_bgzf_read):
+        member discovery, decode and the check of every member's CRC-32 and ISIZE on the GPU, no side index.
+        Returns (out, BgzfRead(rc, out_len, n_members, bad_member, err_off, eof_marker)); the bytes are out[:out_len]
+        (numpy for host data, a torch CUDA tensor for device data).  rc 0; -4 with bad_member == n_members: a
+        malformed chain at err_off (nothing decoded); otherwise the first failing member's status (-4 header, CRC or
+        ISIZE; -7 raw stream cut short; -2 more output than ISIZE) with its index and file offset, all other members
+        delivered; -2 with out_len > capacity: out too small, nothing decoded.  out=None: sized by a query of the
+        index first.  Other failures raise FlateError."""
+        data, in_ptr, n, device = self._bgzf_in(data)
+        if out is None:
+            need = self.bgzf_index(data, query=True).out_bytes
+            if device:
+                import torch
+                out = torch.empty(max(need, 16), dtype=torch.uint8, device=data.device)
+            else:
+                out = np.zeros(max(need, 16), dtype=np.uint8)
+        else:
+            _check_out(out, data, 0, "bgzf_read")
+        room = out.numel() if device else out.size
+        cap = room if out_cap is None else min(int(out_cap), room)
+        out_ptr = out.data_ptr() if device else out.ctypes.data
+        ol, nm, bad, eo, eof = C.c_uint64(0), C.c_uint32(0), C.c_uint32(0), C.c_int64(-1), C.c_int(0)
+        rc = self._L.flate_hip_bgzf_read(self._ctx, in_ptr, n, out_ptr, cap, C.byref(ol), C.byref(nm), C.byref(bad),
+                                         C.byref(eo), C.byref(eof), DEVICE_PTRS if device else 0)
+        if rc not in (0, E_OUT_TOO_SMALL, E_CORRUPT, E_UNEXPECTED_EOF):
+            self._check(rc)
+        return out, BgzfRead(rc, int(ol.value), int(nm.value), int(bad.value), int(eo.value), int(eof.value))
 
     def inflate_batch(self, data, in_off, out_sizes, out=None, check=True, zdicts=None, dict_of=None):
         """Decompress independent DEFLATE streams (&Reader::new + read to EOF each).

@@ -839,4 +839,66 @@ inline Err decompress_spliced(Engine &e, const std::vector<uint8_t> &member, std
   return make_error(e, member_status);
 }
 
+// ---- BGZF files (the blocked gzip of the SAM/BAM specification) -----------------------------
+// compress_bgzf: `data` as ONE .gz file that gzip -d, bgzip and htslib read -- a member per block_bytes of input (0:
+// 65280), each with its size in a 'BC' extra subfield, then the 28-byte EOF marker; one call
+// (flate_hip_bgzf_write), framed on the GPU.  member_off (may be null): where every member starts, the marker last.
+// A block that compresses to more than 65536 bytes is FLATE_HIP_E_TOO_LARGE (the message names it).
+inline Err compress_bgzf(Engine &e, const std::vector<uint8_t> &data, std::vector<uint8_t> &out, uint32_t block_bytes = 0,
+                         std::vector<uint64_t> *member_off = nullptr, uint32_t flags = 0) {
+  if (!e.ok()) return make_error(e, e.status());
+  const size_t cap = flate_hip_bgzf_bound(data.size(), block_bytes);
+  if (!cap) return make_error(e, FLATE_HIP_E_INVALID);
+  const uint32_t bb = block_bytes ? block_bytes : FLATE_HIP_BGZF_BLOCK_DEFAULT;
+  std::vector<uint64_t> off((data.size() + bb - 1) / bb + 1, 0);
+  std::vector<uint8_t> buf(cap);
+  uint64_t len = 0;
+  const int rc = flate_hip_bgzf_write(e.ctx(), data.data(), data.size(), block_bytes, buf.data(), cap, &len, off.data(),
+                                      flags);
+  if (rc != 0) return make_error(e, rc);
+  out.assign(buf.begin(), buf.begin() + len);
+  if (member_off) *member_off = off;
+  return std::nullopt;
+}
+
+// What decompress_bgzf found beside the bytes.
+struct BgzfInfo {
+  uint32_t n_members = 0;
+  uint32_t bad_member = 0xffffffffu;  // the first failing member, or (a malformed chain) the count of good ones
+  int64_t err_off = -1;               // its file offset, or where no member could be read
+  bool eof_marker = false;            // the file ends with the canonical empty member
+  int status = 0;                     // the FLATE_HIP_E_* code behind the error (0 = none)
+};
+
+// decompress_bgzf: the reverse, for any BGZF file: member discovery, decoding and the check of every member's CRC-32
+// and ISIZE on the GPU (flate_hip_bgzf_index for the size, flate_hip_bgzf_read for the bytes); no side index.
+// Errors: a malformed chain is corrupt_input_error(the offset at which no member could be read), `out` empty; a
+// failing member is corrupt_input_error(its file offset) or err_unexpected_eof -- `out` then still holds every other
+// member's bytes.
+inline Err decompress_bgzf(Engine &e, const std::vector<uint8_t> &file, std::vector<uint8_t> &out, BgzfInfo *info = nullptr) {
+  if (!e.ok()) return make_error(e, e.status());
+  BgzfInfo I;
+  uint64_t need = 0, len = 0;
+  int eof = 0;
+  int rc = flate_hip_bgzf_index(e.ctx(), file.data(), file.size(), 0, nullptr, nullptr, &I.n_members, &need, &eof,
+                                &I.err_off, 0);
+  out.clear();
+  if (rc == 0) {
+    std::vector<uint8_t> buf(need + 8);
+    rc = flate_hip_bgzf_read(e.ctx(), file.data(), file.size(), buf.data(), need, &len, &I.n_members, &I.bad_member,
+                             &I.err_off, &eof, 0);
+    if (rc == 0 || rc == FLATE_HIP_E_CORRUPT || rc == FLATE_HIP_E_UNEXPECTED_EOF || rc == FLATE_HIP_E_OUT_TOO_SMALL)
+      out.assign(buf.begin(), buf.begin() + std::min(len, need));
+  } else if (rc == FLATE_HIP_E_CORRUPT) {
+    I.bad_member = I.n_members;
+  }
+  I.eof_marker = eof != 0;
+  I.status = rc;
+  if (info) *info = I;
+  if (rc == 0) return std::nullopt;
+  if (rc == FLATE_HIP_E_CORRUPT) return corrupt_input_error(I.err_off);
+  if (rc == FLATE_HIP_E_UNEXPECTED_EOF) return err_unexpected_eof();
+  return make_error(e, rc);
+}
+
 }  // namespace flate_host
