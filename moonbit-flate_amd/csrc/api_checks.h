@@ -25,6 +25,18 @@ inline int inflate_batch_ranges(const uint64_t *in_off, uint32_t n, const uint64
   return FLATE_HIP_OK;
 }
 
+// flate_hip_deflate_fast_batch(_dict, _framed): the pointers (out_off receives the index, so it is never optional)
+inline bool deflate_batch_ptrs_ok(const uint8_t *in, const uint64_t *in_off, uint32_t n, const uint8_t *out,
+                                  const uint64_t *out_off) {
+  return in_off && out_off && (!n || (in && out));
+}
+// flate_hip_deflate_fast_spliced(_framed): one stream comes out even of no input, so `out` and out_len are never optional
+// (the bit index is)
+inline bool deflate_spliced_ptrs_ok(const uint8_t *in, const uint64_t *in_off, uint32_t n, const uint8_t *out,
+                                    const uint64_t *out_len) {
+  return in_off && out && out_len && (!n || in);
+}
+
 // The dictionary table of a call (flate_hip_inflate_batch_framed needs no more: its members choose by DICTID) ...
 inline bool dict_table_ok(const uint8_t *dicts, const uint64_t *dict_off, uint32_t n_dicts) {
   if (n_dicts && !dict_off) return false;

@@ -1,21 +1,13 @@
-// flate_api.hip -- C ABI of libflate_hip.so (see include/flate_hip.h): the ctx, its options and staging, the encode
-// calls.  (The decode calls: flate_api_inflate.hip; what the two share: flate_ctx.h.)
-//
-// Host-side driver: plans the chunking exactly as Compressor::write / enc_speed /
-// close stage their 65535-byte window (reference deflate.mbt:222-294,157-183), owns
-// the HBM scratch (match records, output slots, index arrays) and launches the
-// kernels on one HIP stream.  There is no CPU compression path in this library.
+// flate_api.hip -- C ABI of libflate_hip.so (see include/flate_hip.h): the ctx, its options and what the encode and
+// the decode calls share -- the scratch and the control-array staging, the host-pointer pipeline's copy threads, the
+// staging of preset dictionaries.  (The encode calls: flate_api_deflate.hip; the decode calls: flate_api_inflate.hip;
+// what crosses the file boundaries: flate_ctx.h.)
 #include "flate_ctx.h"
 
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <exception>
-#include <stdexcept>
-
-#include "api_checks.h"
-#include "bgzf_rule.h"
 
 using namespace flate;
 using namespace flate_host;
@@ -144,74 +136,6 @@ std::vector<uint16_t> make_scan_table() {
   return t;
 }
 
-// The preset dictionaries of an encode call (flate_hip_deflate_fast_batch_dict), already on the device.
-struct DeflDict {
-  LzDictParams dev;
-  uint32_t n_slots;        // used dictionaries of at least kSmallHuffMin bytes (after the cut to 32768)
-  const uint8_t *has;      // host, per stream: it uses one of them
-};
-
-// The container of a *_framed call (frame_kernels.hip); everything here is the caller's.
-struct FrameReq {
-  uint32_t wrap;            // FLATE_HIP_WRAP_ZLIB / _GZIP
-  const uint32_t *dict_of;  // host, per stream: the dictionary whose DICTID its header carries, or FLATE_HIP_NO_DICT;
-                            // null: no dictionaries
-  const uint8_t *dicts;     // the WHOLE dictionaries (host, or device under FLATE_HIP_DEVICE_PTRS) ...
-  const uint64_t *dict_off; // ... dictionary j = dicts[dict_off[j], dict_off[j+1])
-  uint32_t n_dicts;
-};
-
-struct StagePlan {
-  uint32_t n_streams = 0;
-  std::vector<uint32_t> chunk_base;  // n+1
-  std::vector<uint32_t> ids16, ids32;
-  std::vector<uint32_t> idsD;  // streams that start from a preset dictionary's table (flate_hip_deflate_fast_batch_dict)
-  std::vector<uint32_t> blk_base;  // n+1
-  uint32_t n_chunks = 0;
-  uint32_t n_blocks = 0;
-};
-
-// has_dict (or null): per stream, whether DeflateFast::encode has run over a preset dictionary before the payload
-int make_plan(const uint64_t *in_off, uint32_t n, StagePlan &pl, uint32_t flags, const uint8_t *has_dict = nullptr) {
-  pl.n_streams = n;
-  pl.chunk_base.resize((size_t)n + 1);
-  pl.blk_base.resize((size_t)n + 1);
-  uint64_t chunks = 0, blocks = 0;
-  for (uint32_t i = 0; i < n; ++i) {
-    if (in_off[i + 1] < in_off[i]) return FLATE_HIP_E_INVALID;
-    const uint64_t len = in_off[i + 1] - in_off[i];
-    // (a dictionary is window 0 of its stream: the payload's positions start at 65535, `cur` one window further on)
-    const bool dict = has_dict && has_dict[i];
-    if (len + (dict ? (uint64_t)kMaxStoreBlockSize : 0) >= 0x7ffe0000ull) return FLATE_HIP_E_TOO_LARGE;
-    const uint64_t full = len / kMaxStoreBlockSize, r = len % kMaxStoreBlockSize;
-    const uint64_t nch = full + (r >= (uint64_t)kSmallLzMin ? 1 : 0);
-    // The reference's `cur` reaches buffer_reset at a Writer's window 32 766 (deflate-fast.mbt:55,130):
-    // shift_offsets then CLEARS the table in MoonBit (`prev` is empty, :367-374).  Batch streams keep
-    // their table from start to end, so a stream with an LZ77 window that far in is refused here
-    // (flate_hip_stream_write follows the reference past that point); in Go's semantics the shift
-    // changes no distance and the 32-bit positions above are the only limit.
-    if (!(flags & FLATE_HIP_COMPAT_GO) && nch + (dict ? 1 : 0) > 32766) return FLATE_HIP_E_TOO_LARGE;
-    pl.chunk_base[i] = (uint32_t)chunks;
-    pl.blk_base[i] = (uint32_t)blocks;
-    if (dict && nch > 0) {
-      pl.idsD.push_back(i);  // (a payload under 128 bytes never reaches the match finder: its dictionary is unused)
-    } else if (nch == 1) {
-      pl.ids16.push_back(i);  // one LZ77 window (it starts at 0): positions fit a 16-bit slot
-    } else if (nch > 0) {
-      pl.ids32.push_back(i);
-    }
-    chunks += nch;
-    if (chunks > 0xffffffffull) return FLATE_HIP_E_TOO_LARGE;
-    blocks += full + (r > 0 ? 1 : 0);
-    if (blocks > 0xffffffffull) return FLATE_HIP_E_TOO_LARGE;
-  }
-  pl.chunk_base[n] = (uint32_t)chunks;
-  pl.blk_base[n] = (uint32_t)blocks;
-  pl.n_chunks = (uint32_t)chunks;
-  pl.n_blocks = (uint32_t)blocks;
-  return FLATE_HIP_OK;
-}
-
 }  // namespace
 
 int flate_host::collect_timing(flate_hip_ctx *c, const bool used[FLATE_HIP_STAGE_COUNT]) {
@@ -225,234 +149,6 @@ int flate_host::collect_timing(flate_hip_ctx *c, const bool used[FLATE_HIP_STAGE
   }
   return FLATE_HIP_OK;
 }
-
-namespace {
-
-// The parameter blocks as far as the ctx owns what they point at (its scratch, its options); the callers add
-// the input, the index arrays and what is theirs alone.
-LzParams lz_params(const flate_hip_ctx *c, uint32_t flags) {
-  LzParams P{};  // (value-initialised: a field added later must never reach a kernel as stack garbage)
-  P.scan_off = (const uint16_t *)c->scan_tab.p;
-  P.scan_len = c->scan_len;
-  P.matches = (uint2 *)c->d_matches.p;
-  P.chunk_nmatch = (uint32_t *)c->d_nmatch.p;
-  P.chunk_ntok = (uint32_t *)c->d_ntok.p;
-  P.compat_go = (flags & FLATE_HIP_COMPAT_GO) ? 1u : 0u;
-  P.spin_limit = c->spin_limit;
-  P.status = (int *)c->d_status.p;
-  return P;
-}
-
-// spliced: the streams' blocks follow one another bit by bit (summaries in d_slot_off, bit positions in d_out_off)
-HuffParams huff_params(const flate_hip_ctx *c, uint32_t flags, bool spliced) {
-  HuffParams H{};
-  H.matches = (const uint2 *)c->d_matches.p;
-  H.chunk_nmatch = (const uint32_t *)c->d_nmatch.p;
-  H.chunk_ntok = (const uint32_t *)c->d_ntok.p;
-  H.blk_hist = (uint32_t *)c->d_blk_hist.p;
-  H.blk_cl = (uint32_t *)c->d_blk_cl.p;
-  H.blk_hdr = (uint32_t *)c->d_blk_hdr.p;
-  H.blk_meta = (uint4 *)c->d_blk_meta.p;
-  H.tile_meta = (uint8_t *)c->d_tile_meta.p;
-  H.spliced = spliced ? 1u : 0u;
-  H.stream_sum = spliced ? (uint64_t *)c->d_slot_off.p : nullptr;
-  H.stream_bit = spliced ? (const uint64_t *)c->d_out_off.p : nullptr;
-  H.out_len = (uint64_t *)c->d_out_len.p;
-  H.out_off = (const uint64_t *)c->d_out_off.p;
-  H.status = (int *)c->d_status.p;
-  H.compat_go = (flags & FLATE_HIP_COMPAT_GO) ? 1u : 0u;
-  return H;
-}
-
-// The encoder's device status word (not 0) as the call's return code.  A word of the scan kernels is a public
-// code already; everything from kStatusUqTimeout down is FLATE_HIP_E_INTERNAL, with what happened in hip_err.
-int encoder_status(flate_hip_ctx *c, int word) {
-  if (word > kStatusUqTimeout) return word;
-  if (word == kStatusNoProgress)
-    c->hip_err = "a match-finder batch made no progress (the chunk was abandoned)";
-  else if (word == kStatusLanesLost)
-    c->hip_err = "a persistent match-finder loop lost lanes of its wavefront (miscompiled loop?)";
-  else if (word == kStatusUqTimeout)
-    c->hip_err = "a match-finder block waited for a window that was never handed over";
-  else if (word == kStatusBadIndex)
-    c->hip_err = "a match-finder block was handed an index outside its scratch";
-  else if (word <= -0x100000)  // encoder self-check (huff_pack_kernel): -(0x100000 + stream)
-    c->hip_err = "packed bits differ from the computed block size in stream " +
-                 std::to_string((uint32_t)(-word) - 0x100000u) + " (mod 2^20)";
-  else
-    c->hip_err = "device status word " + std::to_string(word);
-  return FLATE_HIP_E_INTERNAL;
-}
-
-// A resident (LDS-table) kernel on c->stream and a guest (L2-table) kernel on c->guest_stream, side by side: the
-// blocks of both pull the `count` entries of one queue.  R / G: the two sides' parameters; extra: what both
-// kernels take after them.
-// The LDS-table kernel is submitted FIRST: its blocks need 26 contiguous LDS granules each, and guests that
-// reach a CU before them can leave it with room for three (measured: -1.4 % with this order, section 7 of
-// profiles/r05/README.md).
-template <typename... Extra>
-void launch_pair(flate_hip_ctx *c, void (*resident)(LzParams, Extra...), void (*guest)(LzParams, Extra...),
-                 uint32_t count, const LzParams &R, const LzParams &G, const Extra &...extra) {
-  (void)hipEventRecord(c->ev_fork, c->stream);
-  (void)hipStreamWaitEvent(c->guest_stream, c->ev_fork, 0);
-  const uint32_t blocks = c->resident_blocks < count ? c->resident_blocks : count;
-  hipLaunchKernelGGL(resident, dim3(blocks), dim3(64), 0, c->stream, R, extra...);
-  hipLaunchKernelGGL(guest, dim3((uint32_t)c->guest_blocks), dim3(64), 0, c->guest_stream, G, extra...);
-  (void)hipEventRecord(c->ev_join, c->guest_stream);
-  (void)hipStreamWaitEvent(c->stream, c->ev_join, 0);
-}
-
-// Upload the index arrays and run the match finder over every LZ77 chunk.
-// (the caller has checked that the launch is one persistent resident+guest launch in stream order)
-// DD: the preset dictionaries of the streams in pl.idsD (null: there are none)
-int run_lz77(flate_hip_ctx *c, const uint8_t *d_in, const uint64_t *in_off, const StagePlan &pl,
-             uint32_t flags, const DeflDict *DD = nullptr) {
-  const uint32_t n = pl.n_streams;
-  int rc;
-  if ((rc = ensure(c, c->d_in_off, ((size_t)n + 1) * 8))) return rc;
-  if ((rc = ensure(c, c->d_chunk_base, ((size_t)n + 1) * 4))) return rc;
-  if ((rc = ensure(c, c->d_ids16, pl.ids16.size() * 4 + 4))) return rc;
-  if ((rc = ensure(c, c->d_ids32, pl.ids32.size() * 4 + 4))) return rc;
-  if ((rc = ensure(c, c->d_matches, (size_t)pl.n_chunks * kMatchCapPerChunk * sizeof(uint2) + 16)))
-    return rc;
-  if ((rc = ensure(c, c->d_nmatch, (size_t)pl.n_chunks * 4 + 4))) return rc;
-  if ((rc = ensure(c, c->d_ntok, (size_t)pl.n_chunks * 4 + 4))) return rc;
-  if ((rc = ctl_up(c, c->d_in_off.p, in_off, ((size_t)n + 1) * 8))) return rc;
-  if ((rc = ctl_up(c, c->d_chunk_base.p, pl.chunk_base.data(), ((size_t)n + 1) * 4))) return rc;
-  if ((rc = ctl_up(c, c->d_ids16.p, pl.ids16.data(), pl.ids16.size() * 4))) return rc;
-  if ((rc = ctl_up(c, c->d_ids32.p, pl.ids32.data(), pl.ids32.size() * 4))) return rc;
-  if (!pl.idsD.empty()) {
-    if (!DD || (flags & FLATE_HIP_LZ_SERIAL)) return FLATE_HIP_E_INTERNAL;
-    if ((rc = ensure(c, c->d_idsD, pl.idsD.size() * 4 + 4))) return rc;
-    if ((rc = ctl_up(c, c->d_idsD.p, pl.idsD.data(), pl.idsD.size() * 4))) return rc;
-  }
-
-  LzParams P = lz_params(c, flags);
-  P.in = d_in;
-  P.in_off = (const uint64_t *)c->d_in_off.p;
-  P.chunk_base = (const uint32_t *)c->d_chunk_base.p;
-  P.inject_drop_push = c->inject_drop_push;  // (the test hooks act on batch launches only)
-  P.inject_stall = c->inject_stall;
-  c->last_count[0] = c->last_count[1] = 0;
-  // multi-window streams of a persistent launch run one window at a time (see uq_run): the
-  // streams' tables rest in global memory between windows (32 KiB each; the ready word limits it
-  // to 2^17 - 2 streams; more than that, or no memory for the scratch: whole-stream scheduling)
-  uint32_t uq_units = 0;
-  const size_t n32 = pl.ids32.size();
-  const bool use_uq = c->window_units && c->guest_blocks > 0 && n32 >= c->guest_min &&
-                      n32 < (1u << 17) - 1u && !(flags & FLATE_HIP_LZ_SERIAL);
-  if (use_uq) {
-    uint64_t units = 0;
-    for (uint32_t sid : pl.ids32) units += pl.chunk_base[sid + 1] - pl.chunk_base[sid];
-    if (units < 0xffffffffull) uq_units = (uint32_t)units;
-  }
-  if (uq_units) {
-    // (grow-only scratch, 32 KiB per multi-window stream: when the device cannot give it, the
-    // launch falls back to whole-stream scheduling, which needs none)
-    if (ensure(c, c->d_uq_ready, (size_t)uq_units * 4 + 64) != FLATE_HIP_OK ||
-        ensure(c, c->d_uq_tables, n32 * (size_t)kTableSize * 2 + 64) != FLATE_HIP_OK ||
-        ensure(c, c->d_uq_sweep, n32 * 4 + 64) != FLATE_HIP_OK) {
-      (void)hipGetLastError();
-      c->hip_err.clear();
-      uq_units = 0;
-    }
-  }
-  if (c->guest_blocks > 0) {
-    if ((rc = ensure(c, c->d_gtables, (size_t)c->guest_blocks * kTableSize * 2 + 64))) return rc;
-    if ((rc = ensure(c, c->d_queue, 64))) return rc;
-    // words: [0..1] stream queues (single-, multi-window), [2..3] the guests' queues of a fixed
-    // profiling split, [4..5] what the LDS-table launches took, [6..7] window-unit head / tail
-    // [8] the queue of the streams with a preset dictionary
-    HIP_TRY(c, hipMemsetAsync(c->d_queue.p, 0, 40, c->stream));
-  }
-#if defined(FLATE_LZ_STAMPS) || defined(FLATE_LZ_FINISH)
-  if ((rc = ensure(c, c->d_debug, (size_t)pl.n_chunks * 64 + 64))) return rc;
-  HIP_TRY(c, hipMemsetAsync(c->d_debug.p, 0, (size_t)pl.n_chunks * 64, c->stream));
-  P.debug = (uint64_t *)c->d_debug.p;
-  c->debug_chunks = pl.n_chunks;
-#endif
-  {
-    StageTimer t(c, FLATE_HIP_STAGE_LZ77);
-    if (flags & FLATE_HIP_LZ_SERIAL) {
-      if (!pl.ids16.empty()) {
-        P.stream_ids = (const uint32_t *)c->d_ids16.p;
-        hipLaunchKernelGGL(lz77_serial_kernel, dim3((uint32_t)pl.ids16.size()), dim3(64), 0,
-                           c->stream, P);
-      }
-      if (!pl.ids32.empty()) {
-        P.stream_ids = (const uint32_t *)c->d_ids32.p;
-        hipLaunchKernelGGL(lz77_serial_kernel, dim3((uint32_t)pl.ids32.size()), dim3(64), 0,
-                           c->stream, P);
-      }
-    } else {
-      // single-window streams (ids16) and multi-window streams (ids32) use the same 32 KiB
-      // 16-bit tables; the latter add the periodic sweep (MULTI)
-      // a persistent launch: the blocks of both kernels take their streams from word `queue_word` of d_queue
-      auto queued = [&](LzParams X, uint32_t queue_word, uint32_t count) {
-        X.gtables = c->d_gtables.p;
-        X.gtable_blocks = (uint32_t)c->guest_blocks;  // d_gtables holds exactly this many tables
-        X.queue = (uint32_t *)c->d_queue.p + queue_word;
-        X.queue_end = count;
-        return X;
-      };
-      auto launch = [&](const DevBuf &ids, uint32_t count, bool multi, uint32_t queue_slot) {
-        if (!count) return;
-        P.stream_ids = (const uint32_t *)ids.p;
-        void (*wave)(LzParams) = multi ? lz77_wave_kernel<true> : lz77_wave_kernel<false>;
-        if (!(c->guest_blocks > 0 && count >= c->guest_min)) {
-          hipLaunchKernelGGL(wave, dim3(count), dim3(64), 0, c->stream, P);
-          return;
-        }
-        LzParams G = queued(P, queue_slot, count);
-        c->last_count[queue_slot] = count;
-        if (multi && uq_units) {
-          G.uq_ready = (uint32_t *)c->d_uq_ready.p;
-          G.uq_ctr = (uint32_t *)c->d_queue.p + 6;  // {head, tail}
-          G.uq_units = uq_units;
-          G.uq_tables = (uint16_t *)c->d_uq_tables.p;
-          G.uq_sweep = (uint32_t *)c->d_uq_sweep.p;
-          c->last_count[queue_slot] = uq_units;
-          hipLaunchKernelGGL(uq_init_kernel, dim3((uq_units + 255) / 256), dim3(256), 0, c->stream,
-                             G.uq_ready, G.uq_ctr, count, uq_units);
-        }
-        LzParams R = G;  // the LDS-table launch counts what it takes
-        R.taken = (uint32_t *)c->d_queue.p + 4 + queue_slot;
-        if (c->profile_split > 0 && c->profile_split < count && !G.uq_ready) {
-          // measurement aid: a fixed split instead of the shared queue, so that a profiler that
-          // serialises the two kernels still sees each of them do its share of the work
-          R.queue_end = c->profile_split;
-          G.queue = (uint32_t *)c->d_queue.p + 2 + queue_slot;
-          G.stream_ids = P.stream_ids + c->profile_split;
-          G.queue_end = count - c->profile_split;
-        }
-        launch_pair(c, wave, multi ? lz77_guest_kernel<true> : lz77_guest_kernel<false>, count, R, G);
-      };
-      launch(c->d_ids16, (uint32_t)pl.ids16.size(), false, 0);
-      launch(c->d_ids32, (uint32_t)pl.ids32.size(), true, 1);
-      if (!pl.idsD.empty()) {
-        // Streams with a preset dictionary: every used dictionary is primed once (one wavefront each), then the
-        // dictionary builds of the stream kernels run the payloads as windows 1, 2, ... (whole-stream scheduling)
-        const uint32_t count = (uint32_t)pl.idsD.size();
-        LzParams Q = P;
-        Q.stream_ids = (const uint32_t *)c->d_idsD.p;
-        Q.win0 = 1;
-        hipLaunchKernelGGL(lz77_dict_prime_kernel, dim3(DD->n_slots), dim3(64), 0, c->stream, Q, DD->dev);
-        if (!(c->guest_blocks > 0 && count >= c->guest_min)) {
-          hipLaunchKernelGGL(lz77_wave_dict_kernel, dim3(count), dim3(64), 0, c->stream, Q, DD->dev);
-        } else {
-          Q = queued(Q, 8, count);
-          launch_pair(c, lz77_wave_dict_kernel, lz77_guest_dict_kernel, count, Q, Q, DD->dev);
-        }
-      }
-    }
-  }
-  // (test hook: it loses one hand-over of THIS launch, not of every later one)
-  if (uq_units) c->inject_drop_push = 0;
-  HIP_TRY(c, hipGetLastError());
-  return FLATE_HIP_OK;
-}
-
-}  // namespace
 
 extern "C" {
 
@@ -542,18 +238,18 @@ int flate_hip_init(int device, flate_hip_ctx **out) {
     if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0)
       cus = prop.multiProcessorCount;
     c->num_cus = (uint32_t)cus;
-    c->guest_min = 5u * (uint32_t)cus;  // measured: 1024 streams 1.72 ms as one block per stream vs 2.15 ms
+    c->enc.guest_min = 5u * (uint32_t)cus;  // measured: 1024 streams 1.72 ms as one block per stream vs 2.15 ms
                                         // persistent; 1280: 3.41 vs 2.35; 2048: 3.61 vs 2.76; 3072: 5.55 vs 3.96
     // LDS comes in 128 granules of 1280 B per CU: an LDS-table block (32768 B) takes 26, a guest (4096 B of slot
     // tags) 4, so 4 + 6 blocks fill a CU exactly.  Launching MORE guests than fit (rounds 2-4 asked for 6.5 per CU)
     // lets guests that arrive first take the granules of an LDS-table block: most processes then ran 3.5 + 6.5
     // blocks per CU and the match finder 4 % slower (profiles/r05/README.md section 7).  Ask for what fits.
-    c->resident_blocks = 4u * (uint32_t)cus;
-    c->guest_blocks = 6 * cus;
+    c->enc.resident_blocks = 4u * (uint32_t)cus;
+    c->enc.guest_blocks = 6 * cus;
   }
-  if (const char *e = getenv("FLATE_HIP_GUEST_BLOCKS")) c->guest_blocks = atoi(e) < 0 ? 0 : atoi(e);
-  if (const char *e = getenv("FLATE_HIP_GUEST_MIN")) c->guest_min = (uint32_t)atoi(e);
-  if (const char *e = getenv("FLATE_HIP_RESIDENT_BLOCKS")) c->resident_blocks = atoi(e) < 1 ? 1u : (uint32_t)atoi(e);
+  if (const char *e = getenv("FLATE_HIP_GUEST_BLOCKS")) c->enc.guest_blocks = atoi(e) < 0 ? 0 : atoi(e);
+  if (const char *e = getenv("FLATE_HIP_GUEST_MIN")) c->enc.guest_min = (uint32_t)atoi(e);
+  if (const char *e = getenv("FLATE_HIP_RESIDENT_BLOCKS")) c->enc.resident_blocks = atoi(e) < 1 ? 1u : (uint32_t)atoi(e);
   for (auto &e : c->ev)
     if (hipEventCreate(&e) != hipSuccess) {
       flate_hip_destroy(c);
@@ -602,9 +298,9 @@ int flate_hip_set_option(flate_hip_ctx *c, const char *name, int64_t value) {
   if (!c || !name) return FLATE_HIP_E_INVALID;
   const std::string k(name);
   if (k == "guest_blocks" && value >= 0 && value <= 65536) {
-    c->guest_blocks = (int)value;
+    c->enc.guest_blocks = (int)value;
   } else if (k == "guest_min_streams" && value >= 0) {
-    c->guest_min = (uint32_t)value;
+    c->enc.guest_min = (uint32_t)value;
   } else if (k == "inflate_lanes" && (value == 0 || value == 16 || value == 32 || value == 64)) {
     c->inflate.lanes = (int)value;
   } else if (k == "inflate_row_dwords" && (value == 0 || value == 8 || value == 16)) {
@@ -618,7 +314,7 @@ int flate_hip_set_option(flate_hip_ctx *c, const char *name, int64_t value) {
   } else if (k == "inflate_spec_max_streams" && value >= 0 && value <= 0x7fffffff) {
     c->inflate.spec_max = (uint32_t)value;
   } else if (k == "resident_blocks" && value > 0 && value <= 65536) {
-    c->resident_blocks = (uint32_t)value;
+    c->enc.resident_blocks = (uint32_t)value;
   } else if (k == "host_pipeline_groups" && value >= 0 && value <= 64) {
     c->host_groups = (int)value;
   } else if (k == "host_pipeline_group_streams" && value > 0 && value <= 0x7fffffff) {
@@ -626,13 +322,13 @@ int flate_hip_set_option(flate_hip_ctx *c, const char *name, int64_t value) {
   } else if (k == "host_pipeline_lanes" && value >= 1 && value <= 2) {
     c->host_lanes = (int)value;
   } else if (k == "profile_split_streams" && value >= 0 && value <= 0x7fffffff) {
-    c->profile_split = (uint32_t)value;
+    c->enc.profile_split = (uint32_t)value;
   } else if (k == "window_units" && (value == 0 || value == 1)) {
-    c->window_units = (int)value;
+    c->enc.window_units = (int)value;
   } else if (k == "spin_limit_polls" && value > 0 && value <= 0x7fffffff) {
-    c->spin_limit = (uint32_t)value;
+    c->enc.spin_limit = (uint32_t)value;
   } else if (k == "entropy_per_block" && value >= -1 && value <= 1) {
-    c->entropy_per_block = (int)value;
+    c->enc.entropy_per_block = (int)value;
   } else if (k == "stream_rebase_bytes" && value >= 65535 && value <= (1ll << 30)) {
     c->stream_rebase = (uint64_t)value;
   } else if (k == "debug_drop_window_push" && value >= 0 && value <= 0x7fffffff) {
@@ -709,202 +405,7 @@ int flate_hip_last_timing(flate_hip_ctx *c, float *ms, int n) {
   return FLATE_HIP_OK;
 }
 
-// Worst case of one stream: every window Huffman-coded with matches (< 15 bits per
-// byte), a <= 320-byte dynamic header per window, 5 bytes per stored block.
-size_t flate_hip_deflate_bound(size_t n) {
-  const size_t windows = n / kMaxStoreBlockSize + 1;
-  return n * 2 + windows * 320 + 16;
-}
-
 }  // extern "C"
-
-// Both encode entry points.  spliced: the whole batch becomes one DEFLATE stream; out_off then
-// receives the bit position of every stream (may be NULL) and *total_bytes the size.
-// FR (the *_framed calls; null: raw streams, nothing below changes): every stream -- spliced: the one stream -- inside
-// its container.  The scan that places the streams adds header and trailer, the pack kernels write each raw stream into
-// its member, then the checksum kernels run on the input where it is and frame_write_kernel writes headers and trailers.
-static int deflate_common(flate_hip_ctx *c, const uint8_t *in, const uint64_t *in_off, uint32_t n,
-                          uint8_t *out, uint64_t out_cap, uint64_t *out_off, uint32_t flags,
-                          bool spliced, uint64_t *total_bytes, const DeflDict *DD = nullptr,
-                          const FrameReq *FR = nullptr) {
-  HIP_TRY(c, hipSetDevice(c->device));
-  StagePlan pl;
-  int rc = make_plan(in_off, n, pl, flags, DD ? DD->has : nullptr);
-  if (rc) return rc;
-  const bool dev = (flags & FLATE_HIP_DEVICE_PTRS) != 0;
-  const uint64_t in_bytes = in_off[n];
-  // a spliced member's fixed header and trailer; what the checksum kernels sum: the streams, or the one stream
-  const uint32_t f_hl = FR ? frame_header_len(FR->wrap, false) : 0u;
-  const uint32_t f_tl = FR ? frame_trailer_len(FR->wrap) : 0u;
-  const uint64_t whole[2] = {in_off[0], in_off[n]};
-  const uint64_t *sum_off = spliced ? whole : in_off;
-  const uint32_t sum_n = spliced ? 1u : n;
-  size_t f_up = 0;
-  if (FR) {
-    if (spliced && out_cap < (uint64_t)f_hl + f_tl) return FLATE_HIP_E_OUT_TOO_SMALL;
-    f_up = (size_t)n * 4 + 256 + checksum_ctl_up_bytes(sum_off, sum_n);
-    // (n_dicts == 0: every dict_of entry is FLATE_HIP_NO_DICT and dict_off may be null -- dict_args_ok)
-    if (FR->dict_of) f_up += dictid_ctl_up_bytes(FR->dict_off, FR->n_dicts);
-  }
-  // the call's index arrays: in_off, chunk_base, blk_base (n + 1 each), the two stream lists, blk_sid
-  if ((rc = ctl_begin(c, ((size_t)n + 1) * 16 + (pl.ids16.size() + pl.ids32.size() + pl.idsD.size() + (size_t)pl.n_blocks) * 4 + f_up,
-                      ((size_t)n + 1) * 8 + 64)))
-    return rc;
-
-  const uint8_t *d_in = in;
-  uint8_t *d_out = out;
-  if (!dev) {
-    if ((rc = ensure(c, c->d_in, in_bytes + 16))) return rc;
-    if ((rc = ensure(c, c->d_out, out_cap + 16))) return rc;
-    HIP_TRY(c, hipMemcpyAsync(c->d_in.p, in, in_bytes, hipMemcpyHostToDevice, c->stream));
-    d_in = (const uint8_t *)c->d_in.p;
-    d_out = (uint8_t *)c->d_out.p;
-  }
-  const size_t nb = (size_t)pl.n_blocks + 1;
-  if ((rc = ensure(c, c->d_blk_base, ((size_t)n + 1) * 4))) return rc;
-  if ((rc = ensure(c, c->d_blk_hist, nb * 320 * 4))) return rc;
-  if ((rc = ensure(c, c->d_blk_cl, nb * 320 * 4))) return rc;
-  if ((rc = ensure(c, c->d_blk_hdr, nb * 704 * 4))) return rc;
-  if ((rc = ensure(c, c->d_blk_meta, nb * 16))) return rc;
-  if ((rc = ensure(c, c->d_tile_meta, ((in_bytes >> 8) + nb + 2) * 64))) return rc;  // (tile_meta_at)
-  if ((rc = ensure(c, c->d_out_len, (size_t)n * 8 + 8))) return rc;
-  if ((rc = ensure(c, c->d_out_off, ((size_t)n + 1) * 8))) return rc;
-  if (spliced) {
-    if ((rc = ensure(c, c->d_slot_off, ((size_t)n + 1) * 16))) return rc;  // stream summaries {a, b}
-  }
-  if ((rc = ctl_up(c, c->d_blk_base.p, pl.blk_base.data(), ((size_t)n + 1) * 4))) return rc;
-  if (FR) {
-    if ((rc = ensure(c, c->d_frame_off, ((size_t)n + 1) * 8))) return rc;
-    if ((rc = ensure(c, c->d_frame_sums, (size_t)n * 4 + 8))) return rc;
-    if (FR->dict_of) {
-      if ((rc = ensure(c, c->d_frame_dict_of, (size_t)n * 4 + 4))) return rc;
-      // the DICTIDs' checksums and the streams' (below) carve slot 0 of the scratch: sized once here for the larger, so
-      // that the second cannot grow it (a hipFree, which drains the device) inside the timed stage
-      const size_t a = dictid_scratch_bytes(FR->dict_off, FR->n_dicts), b = checksum_scratch_bytes(sum_off, sum_n);
-      void *unused = nullptr;
-      if ((rc = ctx_scratch(c, 0, a > b ? a : b, &unused))) return rc;
-      if ((rc = ctl_up(c, c->d_frame_dict_of.p, FR->dict_of, (size_t)n * 4))) return rc;
-      // (DICTID is the Adler-32 of the whole dictionary: the tails of dict_upload are not enough)
-      if ((rc = dictid_stage(c, FR->dicts, FR->dict_off, FR->n_dicts, flags))) return rc;
-    }
-  }
-  HIP_TRY(c, hipMemsetAsync(c->d_status.p, 0, 8, c->stream));  // (word 1: frame_scan_kernel's first oversized BGZF member)
-  // One wavefront per block in the histogram and pack kernels when the streams have many blocks
-  // (4096 streams of four windows are 4096 wavefronts per stream-kernel, a quarter of what fills
-  // the chip).  Every stream needs at least one block (a stream without any has nobody to write
-  // its closing block in that form).  Not for spliced output: where a block starts then depends on
-  // the bit its stream starts at (a stored block pads to a byte of the SPLICED stream), which only the
-  // stream's own walk knows.
-  bool per_block = c->entropy_per_block != 0 && pl.n_blocks > 0 && !spliced &&
-                   (c->entropy_per_block == 1 || (uint64_t)pl.n_blocks >= 3ull * n);
-  for (uint32_t i = 0; i < n && per_block; ++i) per_block = pl.blk_base[i + 1] > pl.blk_base[i];
-  std::vector<uint32_t> blk_sid;
-  if (per_block) {
-    blk_sid.resize(pl.n_blocks);
-    for (uint32_t i = 0; i < n; ++i)
-      for (uint32_t b = pl.blk_base[i]; b < pl.blk_base[i + 1]; ++b) blk_sid[b] = i;
-    if ((rc = ensure(c, c->d_blk_sid, (size_t)pl.n_blocks * 4 + 4))) return rc;
-    if ((rc = ctl_up(c, c->d_blk_sid.p, blk_sid.data(), (size_t)pl.n_blocks * 4))) return rc;
-  }
-
-  if ((rc = run_lz77(c, d_in, in_off, pl, flags, DD))) return rc;
-
-  HuffParams H = huff_params(c, flags, spliced);
-  H.in = d_in;
-  H.in_off = (const uint64_t *)c->d_in_off.p;
-  H.chunk_base = (const uint32_t *)c->d_chunk_base.p;
-  H.blk_base = (const uint32_t *)c->d_blk_base.p;
-  H.out = d_out + (spliced ? f_hl : 0u);  // (batch members: the header lengths are in the offsets, frame_scan_kernel)
-  H.n_streams = n;
-  H.blk_sid = per_block ? (const uint32_t *)c->d_blk_sid.p : nullptr;
-  FrameParams F{};
-  if (FR) {
-    F.out_len = (const uint64_t *)c->d_out_len.p + (spliced ? n : 0u);  // (spliced: total_bytes of splice_scan_kernel)
-    F.member_off = spliced ? nullptr : (uint64_t *)c->d_frame_off.p;
-    F.payload_off = (uint64_t *)c->d_out_off.p;
-    F.in_off = (const uint64_t *)c->d_in_off.p;
-    F.one_len = whole[1] - whole[0];
-    F.sums = (const uint32_t *)c->d_frame_sums.p;
-    F.dict_of = FR->dict_of ? (const uint32_t *)c->d_frame_dict_of.p : nullptr;
-    F.dict_id = (const uint32_t *)c->d_frame_ids.p;
-    F.out = d_out;
-    F.out_cap = out_cap;
-    F.n_streams = n;
-    F.wrap = FR->wrap;
-    F.status = (int *)c->d_status.p;
-  }
-  CompactParams C{};
-  C.out_len = (const uint64_t *)c->d_out_len.p;
-  C.out_off = (uint64_t *)c->d_out_off.p;
-  C.out_cap = out_cap;
-  C.n_streams = n;
-  C.status = (int *)c->d_status.p;
-  {
-    StageTimer t(c, FLATE_HIP_STAGE_HUFF_PACK);
-    if (per_block)
-      hipLaunchKernelGGL(huff_hist_block_kernel, dim3(pl.n_blocks), dim3(64), 0, c->stream, H);
-    else
-      hipLaunchKernelGGL(huff_hist_kernel, dim3(n), dim3(64), 0, c->stream, H);
-    hipLaunchKernelGGL(huff_code_kernel, dim3(n), dim3(64), 0, c->stream, H);
-    if (!spliced) {
-      if (FR)
-        hipLaunchKernelGGL(frame_scan_kernel, dim3(1), dim3(1024), 0, c->stream, F);
-      else
-        hipLaunchKernelGGL(scan_sizes_kernel, dim3(1), dim3(1024), 0, c->stream, C);
-    } else {
-      SpliceParams S{};
-      S.sum = (const uint64_t *)c->d_slot_off.p;
-      S.stream_bit = (uint64_t *)c->d_out_off.p;
-      S.total_bytes = (uint64_t *)c->d_out_len.p + n;  // (d_out_len has n + 1 slots)
-      // (framed: header + stream + trailer <= out_cap is enough -- the 3 bytes the pack kernel's last dword may reach
-      // past the stream lie in the trailer, which is written after it)
-      S.out_cap = FR ? out_cap - f_hl - f_tl + 3 : out_cap;
-      S.status = (int *)c->d_status.p;
-      S.n_streams = n;
-      hipLaunchKernelGGL(splice_scan_kernel, dim3(1), dim3(1024), 0, c->stream, S);
-      hipLaunchKernelGGL(splice_zero_kernel, dim3(n / 256 + 1), dim3(256), 0, c->stream, S, H.out);
-    }
-    if (per_block) {
-      hipLaunchKernelGGL(huff_zero_edges_kernel, dim3(pl.n_blocks / 256 + 1), dim3(256), 0, c->stream, H,
-                         pl.n_blocks);
-      hipLaunchKernelGGL(huff_pack_block_kernel, dim3(pl.n_blocks), dim3(64), 0, c->stream, H);
-    } else {
-      hipLaunchKernelGGL(huff_pack_kernel, dim3(n), dim3(64), 0, c->stream, H);
-    }
-  }
-  HIP_TRY(c, hipGetLastError());
-  if (FR) {
-    // after the pack kernel: its spliced form works on whole dwords around the stream
-    StageTimer t(c, FLATE_HIP_STAGE_CHECKSUM);
-    if ((rc = checksum_device(c, d_in, sum_off, sum_n, frame_sum_kind(FR->wrap), (uint32_t *)c->d_frame_sums.p, -1)))
-      return rc;
-    hipLaunchKernelGGL(frame_write_kernel, dim3(sum_n / 256 + 1), dim3(256), 0, c->stream, F);
-  }
-  HIP_TRY(c, hipGetLastError());
-
-  uint64_t produced = 0;
-  if (out_off && (rc = ctl_down(c, out_off, (FR && !spliced) ? c->d_frame_off.p : c->d_out_off.p, ((size_t)n + 1) * 8)))
-    return rc;
-  if (spliced && (rc = ctl_down(c, &c->h_total_bytes, (uint64_t *)c->d_out_len.p + n, 8))) return rc;
-  if ((rc = ctl_down(c, &c->h_status_word, c->d_status.p, 4))) return rc;
-  const bool bgzf = FR && FR->wrap == kWrapBgzf;
-  if (bgzf && (rc = ctl_down(c, &c->h_status_aux, (int *)c->d_status.p + 1, 4))) return rc;
-  HIP_TRY(c, hipGetLastError());
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  ctl_finish(c);
-  if (bgzf && c->h_status_word == FLATE_HIP_E_TOO_LARGE)
-    c->hip_err = "BGZF: block " + std::to_string((uint32_t)c->h_status_aux) + " compresses to a member of more than 65536 bytes";
-  if (c->h_status_word) return encoder_status(c, c->h_status_word);
-  // (a BGZF file: the members, then the EOF marker frame_write_kernel has put behind them)
-  produced = spliced ? c->h_total_bytes + f_hl + f_tl : out_off[n] + (bgzf ? (uint64_t)kBgzfEofLen : 0ull);
-  if (total_bytes) *total_bytes = produced;
-  if (!dev) {
-    HIP_TRY(c, hipMemcpyAsync(out, c->d_out.p, produced, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-  }
-  const bool used[FLATE_HIP_STAGE_COUNT] = {true, true, FR != nullptr, false};
-  return collect_timing(c, used);
-}
 
 // FLATE_HIP_TRACE_HOST=1: timestamps of the host-pointer pipeline's stages on stderr (developer aid)
 static bool host_trace_on() {
@@ -1018,489 +519,8 @@ int host_pipe_streams(flate_hip_ctx *c) {
   if (!c->d2h_stream) HIP_TRY(c, mk(&c->d2h_stream));
   return FLATE_HIP_OK;
 }
-}  // namespace flate_host
 
-// The launch options of the parent, as they are now, for a lane's sub-context.
-static void lane_options(flate_hip_ctx *dst, const flate_hip_ctx *src) {
-  dst->guest_blocks = src->guest_blocks;
-  dst->guest_min = src->guest_min;
-  dst->resident_blocks = src->resident_blocks;
-  dst->window_units = src->window_units;
-  dst->entropy_per_block = src->entropy_per_block;
-  dst->spin_limit = src->spin_limit;
-  dst->profile_split = src->profile_split;
-  dst->profiling = src->profiling;
-  dst->host_groups = 0;
-}
-
-// The streams are independent, so the bytes are those of one call over the whole batch.
-// Group g is compressed on lane g % lanes into its own slot of the device output (the slots are
-// sized by the groups' bounds: where a group's bytes end up in `out` depends on the sizes of the
-// groups before it, which the host only learns as they finish); the calling thread takes the groups
-// in order, fills the index and posts each group's bytes to the copy-out thread.
-static int deflate_host_pipelined(flate_hip_ctx *c, const uint8_t *in, const uint64_t *in_off, uint32_t n,
-                                  uint8_t *out, uint64_t out_cap, uint64_t *out_off, uint32_t flags,
-                                  uint32_t G) {
-  HIP_TRY(c, hipSetDevice(c->device));
-  int rc;
-  const int lanes = c->host_lanes > 1 ? 2 : 1;
-  for (int k = 0; k < lanes; ++k) {
-    if (!c->lane[k] && (rc = flate_hip_init(c->device, &c->lane[k]))) return rc;
-    lane_options(c->lane[k], c);
-  }
-  std::vector<uint32_t> lo(G + 1);
-  std::vector<CopyJob> in_jobs(G);
-  cut_by_bytes(in_off, nullptr, n, G, lo);  // equal BYTES per group: copy and compute stages stay balanced
-  // device slots of the groups' output
-  std::vector<uint64_t> slot(G + 1, 0);
-  for (uint32_t g = 0; g < G; ++g) {
-    uint64_t bound = 0;
-    for (uint32_t i = lo[g]; i < lo[g + 1]; ++i) bound += flate_hip_deflate_bound((size_t)(in_off[i + 1] - in_off[i]));
-    if (bound > out_cap) bound = out_cap;  // (a group that needs more than that fails the call anyway)
-    slot[g + 1] = slot[g] + ((bound + 255) & ~255ull);
-  }
-  if ((rc = ensure(c, c->d_in, in_off[n] + 16))) return rc;
-  if ((rc = ensure(c, c->d_out, slot[G] + 16))) return rc;
-  if ((rc = host_pipe_streams(c))) return rc;
-  uint8_t *d_in = (uint8_t *)c->d_in.p, *d_out = (uint8_t *)c->d_out.p;
-  for (uint32_t g = 0; g < G; ++g)
-    in_jobs[g] = {d_in + in_off[lo[g]], in + in_off[lo[g]], (size_t)(in_off[lo[g + 1]] - in_off[lo[g]])};
-  const double t_call = host_now_ms();
-  CopyPipe pipe(G, G);
-  pipe.start(c->device, c->h2d_stream, c->d2h_stream, in_jobs);
-
-  struct GroupResult {
-    std::vector<uint64_t> off;
-    int rc = FLATE_HIP_OK;
-    bool done = false;
-    bool threw = false;  // an exception was caught in the lane's thread
-    float stage[FLATE_HIP_STAGE_COUNT] = {0, 0, 0, 0};
-    std::string err;
-  };
-  std::vector<GroupResult> res(G);
-  std::mutex mu;
-  std::condition_variable cv;
-  bool stop = false;
-  auto run_lane = [&](int k) {
-    flate_hip_ctx *lc = c->lane[k];
-    std::vector<uint64_t> gin;
-    for (uint32_t g = (uint32_t)k; g < G; g += (uint32_t)lanes) {
-      GroupResult &r = res[g];
-      {
-        std::lock_guard<std::mutex> l(mu);
-        if (stop) r.rc = FLATE_HIP_E_INTERNAL;
-      }
-      // (this is a worker thread: an exception that left it would end the process.  std::bad_alloc /
-      // length_error from the vectors here or inside deflate_common are recorded instead; the calling thread
-      // rethrows after the join, and its caller runs the batch as one pass, as before the lanes existed)
-      try {
-        if (r.rc == FLATE_HIP_OK && !pipe.wait_in(g)) r.rc = FLATE_HIP_E_HIP;
-        const uint32_t cnt = lo[g + 1] - lo[g];
-        r.off.assign((size_t)cnt + 1, 0);
-        if (r.rc == FLATE_HIP_OK && cnt) {
-          gin.resize((size_t)cnt + 1);
-          const uint64_t base = in_off[lo[g]];
-          for (uint32_t i = 0; i <= cnt; ++i) gin[i] = in_off[lo[g] + i] - base;
-          lc->hip_err.clear();
-          const double a = host_now_ms();
-          r.rc = deflate_common(lc, d_in + base, gin.data(), cnt, d_out + slot[g], slot[g + 1] - slot[g], r.off.data(),
-                                flags | FLATE_HIP_DEVICE_PTRS, false, nullptr);
-          host_trace(t_call, "compute", g, a, host_now_ms());
-          for (int s = 0; s < FLATE_HIP_STAGE_COUNT; ++s) r.stage[s] = lc->stage_ms[s];
-          if (r.rc != FLATE_HIP_OK) r.err = lc->hip_err;
-        }
-      } catch (const std::exception &e) {
-        r.rc = FLATE_HIP_E_INTERNAL;
-        r.threw = true;
-        try {
-          r.err = std::string("host pipeline lane: ") + e.what();
-        } catch (...) {
-        }
-      } catch (...) {
-        r.rc = FLATE_HIP_E_INTERNAL;
-        r.threw = true;
-      }
-      std::lock_guard<std::mutex> l(mu);
-      r.done = true;
-      if (r.rc != FLATE_HIP_OK) stop = true;
-      cv.notify_all();
-    }
-  };
-  // (the calling thread only collects; a thread that cannot be started ends the others before the
-  // exception travels on to the caller, which then runs the batch as one pass)
-  std::thread workers[2];
-  try {
-    for (int k = 0; k < lanes; ++k) workers[k] = std::thread(run_lane, k);
-  } catch (...) {
-    {
-      std::lock_guard<std::mutex> l(mu);
-      stop = true;
-    }
-    (void)pipe.finish();
-    for (auto &w : workers)
-      if (w.joinable()) w.join();
-    throw;
-  }
-
-  float stage_sum[FLATE_HIP_STAGE_COUNT] = {0, 0, 0, 0};
-  uint64_t at = 0;
-  bool lane_threw = false;
-  rc = FLATE_HIP_OK;
-  out_off[0] = 0;
-  for (uint32_t g = 0; g < G && rc == FLATE_HIP_OK; ++g) {
-    GroupResult &r = res[g];
-    {
-      std::unique_lock<std::mutex> l(mu);
-      cv.wait(l, [&] { return r.done; });
-    }
-    if (r.rc != FLATE_HIP_OK) {
-      rc = r.rc;
-      lane_threw = r.threw;
-      if (c->hip_err.empty()) c->hip_err = r.err;
-      break;
-    }
-    const uint32_t cnt = lo[g + 1] - lo[g];
-    const uint64_t bytes = r.off[cnt];
-    if (at + bytes > out_cap) {
-      rc = FLATE_HIP_E_OUT_TOO_SMALL;
-      break;
-    }
-    for (uint32_t i = 1; i <= cnt; ++i) out_off[lo[g] + i] = at + r.off[i];
-    pipe.post_out(g, {out + at, d_out + slot[g], (size_t)bytes});
-    at += bytes;
-    for (int k = 0; k < FLATE_HIP_STAGE_COUNT; ++k) stage_sum[k] += r.stage[k];
-  }
-  {
-    std::lock_guard<std::mutex> l(mu);
-    if (rc != FLATE_HIP_OK) stop = true;
-  }
-  for (auto &w : workers)
-    if (w.joinable()) w.join();
-  const std::string err = pipe.finish();
-  // A lane that threw may sit behind the group the collector stopped at (lane 1 throws in group 3 and raises `stop`
-  // before lane 0 has started group 2: group 2 then carries E_INTERNAL without a message): look at every group.
-  for (uint32_t g = 0; g < G; ++g)
-    if (res[g].threw) {
-      lane_threw = true;
-      if (!res[g].err.empty()) c->hip_err = res[g].err;
-      break;
-    }
-  if (lane_threw) {
-    // the one-pass fallback reuses c->d_in / c->d_out: nothing of the lanes may still be writing there
-    for (int k = 0; k < lanes; ++k) {
-      (void)hipStreamSynchronize(c->lane[k]->stream);
-      if (c->lane[k]->guest_stream) (void)hipStreamSynchronize(c->lane[k]->guest_stream);
-    }
-    throw std::runtime_error(c->hip_err);  // every thread has ended: the caller falls back to one pass
-  }
-  if (rc == FLATE_HIP_OK && !err.empty()) rc = FLATE_HIP_E_HIP;
-  if (rc == FLATE_HIP_E_HIP && c->hip_err.empty()) c->hip_err = err;
-  for (int k = 0; k < FLATE_HIP_STAGE_COUNT; ++k) c->stage_ms[k] = stage_sum[k];
-  return rc;
-}
-
-extern "C" {
-
-int flate_hip_deflate_fast_batch(flate_hip_ctx *c, const uint8_t *in, const uint64_t *in_off,
-                                 uint32_t n, uint8_t *out, uint64_t out_cap, uint64_t *out_off,
-                                 uint32_t flags) {
-  if (!c || !in_off || !out_off || (n && (!in || !out))) return FLATE_HIP_E_INVALID;
-  c->hip_err.clear();
-  if (n == 0) {
-    out_off[0] = 0;
-    return FLATE_HIP_OK;
-  }
-  // host pointers and a batch large enough that every group still fills the persistent launch
-  if (!(flags & FLATE_HIP_DEVICE_PTRS) && c->host_groups > 1 && in_off[n] >= (64ull << 20)) {
-    uint32_t G = (uint32_t)c->host_groups;
-    // (a group of 4096 64-KiB streams still runs at 80 %; option host_pipeline_group_streams)
-    const uint32_t per = c->guest_min > c->host_group_streams ? c->guest_min : c->host_group_streams;
-    if (n / per < G) G = n / per;
-    if (G > 1) {
-      StagePlan pl;  // validate the whole index first (the same checks as the one-call path)
-      const int rc = make_plan(in_off, n, pl, flags);
-      if (rc) return rc;
-      try {
-        return deflate_host_pipelined(c, in, in_off, n, out, out_cap, out_off, flags, G);
-      } catch (const std::exception &e) {  // (no copy threads, out of host memory): one pass instead
-        c->hip_err.clear();
-      }
-    }
-  }
-  return deflate_common(c, in, in_off, n, out, out_cap, out_off, flags, false, nullptr);
-}
-
-int flate_hip_deflate_fast_spliced(flate_hip_ctx *c, const uint8_t *in, const uint64_t *in_off,
-                                   uint32_t n, uint8_t *out, uint64_t out_cap, uint64_t *out_len,
-                                   uint64_t *bit_off, uint32_t flags) {
-  if (!c || !in_off || !out || !out_len || (n && !in)) return FLATE_HIP_E_INVALID;
-  c->hip_err.clear();
-  if (n == 0) {  // nothing but the closing block of Writer::close
-    static const uint8_t closing[5] = {0x01, 0x00, 0x00, 0xff, 0xff};
-    if (out_cap < 5) return FLATE_HIP_E_OUT_TOO_SMALL;
-    if (flags & FLATE_HIP_DEVICE_PTRS) {
-      HIP_TRY(c, hipSetDevice(c->device));
-      HIP_TRY(c, hipMemcpyAsync(out, closing, 5, hipMemcpyHostToDevice, c->stream));
-      HIP_TRY(c, hipStreamSynchronize(c->stream));
-    } else {
-      memcpy(out, closing, 5);
-    }
-    *out_len = 5;
-    if (bit_off) bit_off[0] = 0;
-    return FLATE_HIP_OK;
-  }
-  return deflate_common(c, in, in_off, n, out, out_cap, bit_off, flags, true, out_len);
-}
-
-// ---- one long stream, written in pieces (Writer::write as the reference behaves: output leaves
-// ---- while later input is still to come, deflate.mbt:280-294) ---------------------------------
-}  // extern "C"
-
-struct flate_hip_stream {
-  flate_hip_ctx *ctx = nullptr;
-  uint32_t flags = 0;
-  DevBuf table, clock, hist, stage, io, out;  // io: {lz77 in_off[2], huff in_off[2]} (u64) + chunk/blk bases
-  uint64_t abs = 0;        // bytes of the stream consumed so far (a multiple of 65535 until the end)
-  uint64_t pos = 0;        // the same, counted from the stream's current origin (see rebase_at)
-  uint64_t rebase_at = 1ull << 30;  // origin moved up when pos passes this (option stream_rebase_bytes)
-  // DeflateFast.cur as the reference counts it (deflate-fast.mbt:107,115,156): 65535 at the start,
-  // + the window's length after every encode; when it reaches buffer_reset (:55,130-132) shift_offsets
-  // runs -- in MoonBit `prev` is always empty, so that CLEARS the table (:367-374); in Go
-  // the offsets move down and every distance stays what it was
-  int64_t ref_cur = kMaxStoreBlockSize;
-  int64_t buffer_reset = 2147483647ll - 2 * kMaxStoreBlockSize;
-  uint32_t carry_bits = 0; // bits of the last, incomplete output byte (0..7) ...
-  uint8_t carry = 0;       // ... and their value
-  bool closed = false;
-  int err = 0;             // sticky (Compressor.err, deflate.mbt:74)
-};
-
-namespace {
-constexpr uint64_t kHist = 32768;  // max_match_offset: what a later window can still reference
-
-int stream_write_impl(flate_hip_stream *st, const uint8_t *in, uint64_t n, bool final, uint8_t *out,
-                      uint64_t out_cap, uint64_t *out_len) {
-  flate_hip_ctx *c = st->ctx;
-  HIP_TRY(c, hipSetDevice(c->device));
-  // Positions inside the kernels are 32-bit and counted from the stream's origin.  A long stream
-  // moves its origin up (the reference's shift_offsets, deflate-fast.mbt:366-389: same distances,
-  // smaller numbers), so its length is not limited; one piece is (< 1 GiB).
-  if (n >= (1ull << 30)) return FLATE_HIP_E_TOO_LARGE;
-  uint32_t rebase = 0;
-  if (st->pos >= st->rebase_at && st->pos > (uint64_t)kMaxStoreBlockSize) {
-    rebase = (uint32_t)(st->pos - (uint64_t)kMaxStoreBlockSize);  // new origin: one window in front
-    st->pos = kMaxStoreBlockSize;
-  }
-  const uint64_t W0 = st->pos;
-  const uint64_t full = n / kMaxStoreBlockSize, r = n % kMaxStoreBlockSize;
-  const uint32_t nch = (uint32_t)(full + (r >= (uint64_t)kSmallLzMin ? 1 : 0));
-  const uint32_t nblk = (uint32_t)(full + (r > 0 ? 1 : 0));
-  const uint32_t win0 = (uint32_t)(W0 / kMaxStoreBlockSize);
-  int rc;
-  // device staging: [the last 32 KiB of what came before][the new bytes]
-  if ((rc = ensure(c, st->table, kTableSize * 2 + 64))) return rc;
-  if ((rc = ensure(c, st->clock, 64))) return rc;
-  if ((rc = ensure(c, st->hist, kHist + 64))) return rc;
-  if ((rc = ensure(c, st->stage, kHist + n + 64))) return rc;
-  if ((rc = ensure(c, st->io, 256))) return rc;
-  const uint64_t cap_need = flate_hip_deflate_bound(n) + 16;
-  if ((rc = ensure(c, st->out, cap_need + 16))) return rc;
-  uint8_t *stage = (uint8_t *)st->stage.p;
-  if (W0) HIP_TRY(c, hipMemcpyAsync(stage, st->hist.p, kHist, hipMemcpyDeviceToDevice, c->stream));
-  if (n) HIP_TRY(c, hipMemcpyAsync(stage + kHist, in, n, hipMemcpyHostToDevice, c->stream));
-  // index arrays: the match finder sees the stream through a virtual base (absolute positions, the
-  // table's mod-2^16 arithmetic needs them), the entropy stage sees the new bytes only
-  uint64_t h_io[8] = {0, W0 + n, 0, n, 0, 0, 0, 0};
-  uint32_t *h32 = reinterpret_cast<uint32_t *>(h_io + 4);
-  h32[0] = 0; h32[1] = nch;   // chunk_base
-  h32[2] = 0; h32[3] = nblk;  // blk_base
-  HIP_TRY(c, hipMemcpyAsync(st->io.p, h_io, sizeof h_io, hipMemcpyHostToDevice, c->stream));
-  const uint64_t *d_off_abs = (const uint64_t *)st->io.p, *d_off_loc = d_off_abs + 2;
-  const uint32_t *d_chunk_base = (const uint32_t *)((const uint64_t *)st->io.p + 4), *d_blk_base = d_chunk_base + 2;
-  if ((rc = ensure(c, c->d_matches, (size_t)(nch ? nch : 1) * kMatchCapPerChunk * sizeof(uint2) + 16))) return rc;
-  if ((rc = ensure(c, c->d_nmatch, (size_t)nch * 4 + 4))) return rc;
-  if ((rc = ensure(c, c->d_ntok, (size_t)nch * 4 + 4))) return rc;
-  HIP_TRY(c, hipMemsetAsync(c->d_status.p, 0, 4, c->stream));
-  if (nch) {
-    LzParams P = lz_params(c, st->flags);
-    P.in = stage + kHist - W0;  // virtual: only positions >= W0 - 32768 are ever dereferenced
-    P.in_off = d_off_abs;
-    P.chunk_base = d_chunk_base;
-    // One launch per run of windows between two shift_offsets of the reference (one launch, except
-    // for the piece in which `cur` passes buffer_reset: window 32 766 of a Writer, then every 32 767).
-    const bool forgets = !(st->flags & FLATE_HIP_COMPAT_GO);
-    uint32_t k0 = 0;        // first window (of this piece) of the launch being collected
-    bool forget0 = false;   // ... and whether it starts on a cleared table
-    auto flush = [&](uint32_t k1) {
-      if (k1 == k0) return;
-      LzParams Q = P;
-      Q.win0 = win0 + k0;
-      Q.matches = P.matches + (size_t)k0 * kMatchCapPerChunk;  // the kernel indexes both by window - win0
-      Q.chunk_nmatch = P.chunk_nmatch + k0;
-      Q.chunk_ntok = P.chunk_ntok + k0;
-      hipLaunchKernelGGL(lz77_resume_kernel, dim3(1), dim3(64), 0, c->stream, Q, (uint16_t *)st->table.p,
-                         (uint32_t *)st->clock.p, k1 - k0, k0 == 0 ? rebase : 0u, forget0 ? 1u : 0u);
-    };
-    for (uint32_t k = 0; k < nch; ++k) {
-      if (st->ref_cur >= st->buffer_reset) {  // deflate-fast.mbt:130-132
-        st->ref_cur = kMaxMatchOffset + 1;    // :372,388
-        if (forgets) {
-          flush(k);
-          k0 = k;
-          forget0 = true;
-        }
-      }
-      st->ref_cur += k < full ? (int64_t)kMaxStoreBlockSize : (int64_t)r;  // :156
-    }
-    flush(nch);
-  } else if (rebase) {
-    st->pos += rebase;  // (nothing ran: the table still counts from the old origin)
-  }
-  const size_t nb = (size_t)nblk + 1;
-  if ((rc = ensure(c, c->d_blk_hist, nb * 320 * 4))) return rc;
-  if ((rc = ensure(c, c->d_blk_cl, nb * 320 * 4))) return rc;
-  if ((rc = ensure(c, c->d_blk_hdr, nb * 704 * 4))) return rc;
-  if ((rc = ensure(c, c->d_blk_meta, nb * 16))) return rc;
-  if ((rc = ensure(c, c->d_tile_meta, ((n >> 8) + nb + 2) * 64))) return rc;
-  if ((rc = ensure(c, c->d_out_len, 4 * 8))) return rc;
-  if ((rc = ensure(c, c->d_out_off, 4 * 8))) return rc;
-  if ((rc = ensure(c, c->d_slot_off, 4 * 16))) return rc;
-  uint8_t *d_out = (uint8_t *)st->out.p;
-  HuffParams H = huff_params(c, st->flags, true);
-  H.in = stage + kHist;
-  H.in_off = d_off_loc;
-  H.chunk_base = d_chunk_base;
-  H.blk_base = d_blk_base;
-  H.out = d_out;
-  H.n_streams = 1;
-  H.no_close = final ? 0u : 1u;
-  SpliceParams S{};
-  S.sum = (const uint64_t *)c->d_slot_off.p;
-  S.stream_bit = (uint64_t *)c->d_out_off.p;
-  S.total_bytes = (uint64_t *)c->d_out_len.p + 1;
-  S.out_cap = cap_need;
-  S.status = (int *)c->d_status.p;
-  S.n_streams = 1;
-  S.start_bit = st->carry_bits;
-  S.no_close = H.no_close;
-  hipLaunchKernelGGL(huff_hist_kernel, dim3(1), dim3(64), 0, c->stream, H);
-  hipLaunchKernelGGL(huff_code_kernel, dim3(1), dim3(64), 0, c->stream, H);
-  hipLaunchKernelGGL(splice_scan_kernel, dim3(1), dim3(1024), 0, c->stream, S);
-  hipLaunchKernelGGL(splice_zero_kernel, dim3(1), dim3(256), 0, c->stream, S, d_out);
-  // the bits left over from the previous piece share the first byte with this piece's first block
-  if (st->carry_bits) HIP_TRY(c, hipMemcpyAsync(d_out, &st->carry, 1, hipMemcpyHostToDevice, c->stream));
-  hipLaunchKernelGGL(huff_pack_kernel, dim3(1), dim3(64), 0, c->stream, H);
-  HIP_TRY(c, hipGetLastError());
-  uint64_t h_pos[2] = {0, 0};  // {end bit of the piece, total bytes}
-  HIP_TRY(c, hipMemcpyAsync(&h_pos[0], (uint64_t *)c->d_out_off.p + 1, 8, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(&h_pos[1], (uint64_t *)c->d_out_len.p + 1, 8, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(&c->h_status_word, c->d_status.p, 4, hipMemcpyDeviceToHost, c->stream));
-  if (!final && n >= kHist)  // what the next piece may still reference
-    HIP_TRY(c, hipMemcpyAsync(st->hist.p, stage + n, kHist, hipMemcpyDeviceToDevice, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  if (c->h_status_word) return encoder_status(c, c->h_status_word);
-  const uint64_t whole = final ? h_pos[1] : (h_pos[0] >> 3);
-  if (whole > out_cap) return FLATE_HIP_E_OUT_TOO_SMALL;
-  if (whole) HIP_TRY(c, hipMemcpyAsync(out, d_out, whole, hipMemcpyDeviceToHost, c->stream));
-  st->carry_bits = final ? 0u : (uint32_t)(h_pos[0] & 7u);
-  if (st->carry_bits) HIP_TRY(c, hipMemcpyAsync(&st->carry, d_out + whole, 1, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  if (st->carry_bits) st->carry &= (uint8_t)((1u << st->carry_bits) - 1u);
-  st->pos += n;
-  st->abs += n;
-  *out_len = whole;
-  return FLATE_HIP_OK;
-}
-}  // namespace
-
-extern "C" {
-
-int flate_hip_stream_open(flate_hip_ctx *c, uint32_t flags, flate_hip_stream **out) {
-  if (!c || !out || (flags & ~FLATE_HIP_COMPAT_GO)) return FLATE_HIP_E_INVALID;
-  flate_hip_stream *st = new flate_hip_stream();
-  st->ctx = c;
-  st->flags = flags;
-  st->rebase_at = c->stream_rebase;
-  if (c->debug_buffer_reset > 0) st->buffer_reset = c->debug_buffer_reset;
-  *out = st;
-  return FLATE_HIP_OK;
-}
-
-void flate_hip_stream_free(flate_hip_stream *st) {
-  if (!st) return;
-  (void)hipSetDevice(st->ctx->device);
-  delete st;
-}
-
-size_t flate_hip_stream_bound(size_t n) { return flate_hip_deflate_bound(n) + 8; }
-
-int flate_hip_stream_write(flate_hip_stream *st, const uint8_t *in, uint64_t n, int final, uint8_t *out,
-                           uint64_t out_cap, uint64_t *out_len) {
-  if (!st || !out_len || (n && !in) || !out) return FLATE_HIP_E_INVALID;
-  *out_len = 0;
-  if (st->err) return st->err;
-  if (st->closed) return FLATE_HIP_E_INVALID;
-  // a piece that is not the last one is whole windows: the 65535-byte staging window of
-  // Compressor::fill_store (deflate.mbt:222-229) is what enc_speed compresses at a time
-  if (!final && (n == 0 || n % kMaxStoreBlockSize != 0)) return FLATE_HIP_E_INVALID;
-  st->ctx->hip_err.clear();
-  const int rc = stream_write_impl(st, in, n, final != 0, out, out_cap, out_len);
-  if (rc != FLATE_HIP_OK && rc != FLATE_HIP_E_OUT_TOO_SMALL) st->err = rc;  // sticky, as Compressor.err
-  if (rc == FLATE_HIP_E_OUT_TOO_SMALL) st->err = rc;  // (the piece's state is gone with the call)
-  if (rc == FLATE_HIP_OK && final) st->closed = true;
-  return rc;
-}
-
-int flate_hip_lz77_matches(flate_hip_ctx *c, const uint8_t *in, const uint64_t *in_off, uint32_t n,
-                           uint32_t flags, uint32_t *n_chunks, uint64_t *n_recs_cap,
-                           uint32_t *chunk_nmatch, uint64_t *chunk_rec_off, uint32_t *recs) {
-  if (!c || !in_off || !n_chunks || !n_recs_cap) return FLATE_HIP_E_INVALID;
-  c->hip_err.clear();
-  StagePlan pl;
-  int rc = make_plan(in_off, n, pl, flags);
-  if (rc) return rc;
-  *n_chunks = pl.n_chunks;
-  *n_recs_cap = (uint64_t)pl.n_chunks * kMatchCapPerChunk;
-  if (!recs) return FLATE_HIP_OK;
-  if (!in || !chunk_nmatch || !chunk_rec_off) return FLATE_HIP_E_INVALID;
-  if (pl.n_chunks == 0) return FLATE_HIP_OK;
-  HIP_TRY(c, hipSetDevice(c->device));
-  const bool dev = (flags & FLATE_HIP_DEVICE_PTRS) != 0;
-  const uint8_t *d_in = in;
-  if (!dev) {
-    if ((rc = ensure(c, c->d_in, in_off[n] + 16))) return rc;
-    HIP_TRY(c, hipMemcpyAsync(c->d_in.p, in, in_off[n], hipMemcpyHostToDevice, c->stream));
-    d_in = (const uint8_t *)c->d_in.p;
-  }
-  HIP_TRY(c, hipMemsetAsync(c->d_status.p, 0, 4, c->stream));
-  if ((rc = ctl_begin(c, ((size_t)n + 1) * 12 + (pl.ids16.size() + pl.ids32.size()) * 4, 64))) return rc;
-  if ((rc = run_lz77(c, d_in, in_off, pl, flags))) return rc;
-  HIP_TRY(c, hipMemcpyAsync(chunk_nmatch, c->d_nmatch.p, (size_t)pl.n_chunks * 4,
-                            hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(&c->h_status_word, c->d_status.p, 4, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  if (c->h_status_word) return encoder_status(c, c->h_status_word);
-  for (uint32_t k = 0; k <= pl.n_chunks; ++k) chunk_rec_off[k] = (uint64_t)k * kMatchCapPerChunk;
-  const hipMemcpyKind kind = dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-  HIP_TRY(c, hipMemcpyAsync(recs, c->d_matches.p, (size_t)pl.n_chunks * kMatchCapPerChunk * 8, kind,
-                            c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  const bool used[FLATE_HIP_STAGE_COUNT] = {true, false, false, false};
-  return collect_timing(c, used);
-}
-
-#if defined(FLATE_LZ_STAMPS) || defined(FLATE_LZ_FINISH)
-// diagnostic builds only: per-chunk phase cycle sums (or start / finish times) of the last match-finder launch
-int flate_hip_debug_lz_stamps(flate_hip_ctx *c, uint64_t *out, uint32_t max_chunks) {
-  uint32_t k = c->debug_chunks < max_chunks ? c->debug_chunks : max_chunks;
-  if (hipMemcpy(out, c->d_debug.p, (size_t)k * 64, hipMemcpyDeviceToHost) != hipSuccess) return -3;
-  return (int)k;
-}
-#endif
-
-}  // extern "C"
-
-namespace flate_host {
+// ---- preset dictionaries, as the encode and the decode calls stage them ----
 
 // (host only, after dict_args_ok: the entry points make every check before any HIP call)
 DictSlots dict_slots(const uint64_t *dict_off, uint32_t n_dicts, const uint32_t *dict_of, uint32_t n, uint32_t min_len) {
@@ -1557,185 +577,3 @@ int dictid_stage(flate_hip_ctx *c, const uint8_t *dicts, const uint64_t *dict_of
 }
 
 }  // namespace flate_host
-
-// flate_hip_deflate_fast_batch_dict; wrap != FLATE_HIP_WRAP_RAW: flate_hip_deflate_fast_batch_framed with dictionaries
-// (zlib members, the streams that name a dictionary with FDICT and its DICTID)
-static int deflate_batch_dict_run(flate_hip_ctx *c, const uint8_t *in, const uint64_t *in_off, uint32_t n,
-                                  const uint8_t *dicts, const uint64_t *dict_off, uint32_t n_dicts,
-                                  const uint32_t *dict_of, uint8_t *out, uint64_t out_cap, uint64_t *out_off,
-                                  uint32_t flags, uint32_t wrap) {
-  // every check before any HIP call
-  if (!c || !in_off || !out_off || (n && (!in || !out))) return FLATE_HIP_E_INVALID;
-  if (!dict_args_ok(dicts, dict_off, n_dicts, dict_of, n)) return FLATE_HIP_E_INVALID;
-  const bool framed = wrap != FLATE_HIP_WRAP_RAW;
-  std::vector<uint32_t> every0;  // dict_of == NULL: every stream uses dictionary 0
-  if (framed && !dict_of) every0.assign(n, 0u);
-  const FrameReq FRv{wrap, dict_of ? dict_of : every0.data(), dicts, dict_off, n_dicts};
-  const FrameReq *FR = framed ? &FRv : nullptr;
-  // DeflateFast::encode(d) over the last 32768 bytes of the dictionary; under 17 bytes that call is the
-  // small-input path (deflate-fast.mbt:136-140) and leaves nothing behind
-  const DictSlots S = dict_slots(dict_off, n_dicts, dict_of, n, (uint32_t)kSmallHuffMin);
-  if (S.at.empty()) {  // no stream's encoder has seen a dictionary: the plain call, its kernels and its bytes
-    if (!framed) return flate_hip_deflate_fast_batch(c, in, in_off, n, out, out_cap, out_off, flags);
-    c->hip_err.clear();
-    if (n == 0) {
-      out_off[0] = 0;
-      return FLATE_HIP_OK;
-    }
-    return deflate_common(c, in, in_off, n, out, out_cap, out_off, flags, false, nullptr, nullptr, FR);
-  }
-  if (flags & FLATE_HIP_LZ_SERIAL) return FLATE_HIP_E_INVALID;  // (the single-lane kernel has no dictionary build)
-  std::vector<uint8_t> has(n);
-  for (uint32_t i = 0; i < n; ++i) has[i] = S.slot_of[i] != DictSlots::kNone;
-  {
-    StagePlan pl;  // the whole index, before the context is touched
-    const int rc = make_plan(in_off, n, pl, flags, has.data());
-    if (rc) return rc;
-  }
-  c->hip_err.clear();
-  const uint32_t n_slots = (uint32_t)S.at.size();
-  HIP_TRY(c, hipSetDevice(c->device));
-  int rc;
-  if ((rc = dict_upload(c, S, dicts, dict_off, flags))) return rc;
-  if ((rc = ensure(c, c->d_dict_at, (size_t)n_slots * 8))) return rc;
-  if ((rc = ensure(c, c->d_dict_len, (size_t)n_slots * 4))) return rc;
-  if ((rc = ensure(c, c->d_lz_slot_of, (size_t)n * 4))) return rc;
-  if ((rc = ensure(c, c->d_lz_tables, (size_t)n_slots * kTableSize * 2))) return rc;
-  if ((rc = ensure(c, c->d_lz_clocks, (size_t)n_slots * 4))) return rc;
-  HIP_TRY(c, hipMemcpyAsync(c->d_dict_at.p, S.at.data(), (size_t)n_slots * 8, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(c->d_dict_len.p, S.len.data(), (size_t)n_slots * 4, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(c->d_lz_slot_of.p, S.slot_of.data(), (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  DeflDict DD{};
-  DD.dev.dict_buf = (const uint8_t *)c->d_dicts.p;
-  DD.dev.dict_at = (const uint64_t *)c->d_dict_at.p;
-  DD.dev.dict_len = (const uint32_t *)c->d_dict_len.p;
-  DD.dev.slot_of = (const uint32_t *)c->d_lz_slot_of.p;
-  DD.dev.tables = (uint16_t *)c->d_lz_tables.p;
-  DD.dev.clocks = (uint32_t *)c->d_lz_clocks.p;
-  DD.n_slots = n_slots;
-  DD.has = has.data();
-  // (host pointers: one copy in, compress, one copy out -- the pipelined host path is the plain call's)
-  return deflate_common(c, in, in_off, n, out, out_cap, out_off, flags, false, nullptr, &DD, FR);
-}
-
-extern "C" {
-
-int flate_hip_deflate_fast_batch_dict(flate_hip_ctx *c, const uint8_t *in, const uint64_t *in_off, uint32_t n,
-                                      const uint8_t *dicts, const uint64_t *dict_off, uint32_t n_dicts,
-                                      const uint32_t *dict_of, uint8_t *out, uint64_t out_cap, uint64_t *out_off,
-                                      uint32_t flags) {
-  return deflate_batch_dict_run(c, in, in_off, n, dicts, dict_off, n_dicts, dict_of, out, out_cap, out_off, flags,
-                                FLATE_HIP_WRAP_RAW);
-}
-
-size_t flate_hip_frame_overhead(uint32_t wrap, int with_dict) {
-  if (wrap != FLATE_HIP_WRAP_ZLIB && wrap != FLATE_HIP_WRAP_GZIP) return 0;
-  return frame_header_len(wrap, with_dict != 0) + frame_trailer_len(wrap);
-}
-
-int flate_hip_deflate_fast_batch_framed(flate_hip_ctx *c, const uint8_t *in, const uint64_t *in_off, uint32_t n,
-                                        uint32_t wrap, const uint8_t *dicts, const uint64_t *dict_off,
-                                        uint32_t n_dicts, const uint32_t *dict_of, uint8_t *out, uint64_t out_cap,
-                                        uint64_t *out_off, uint32_t flags) {
-  // every check before any HIP call
-  if (!c || wrap > FLATE_HIP_WRAP_GZIP) return FLATE_HIP_E_INVALID;
-  const bool with_dicts = dicts || n_dicts || dict_of;
-  if (with_dicts && wrap == FLATE_HIP_WRAP_GZIP) return FLATE_HIP_E_INVALID;  // (RFC 1952 has no preset dictionary)
-  try {
-    if (with_dicts)
-      return deflate_batch_dict_run(c, in, in_off, n, dicts, dict_off, n_dicts, dict_of, out, out_cap, out_off, flags, wrap);
-    if (wrap == FLATE_HIP_WRAP_RAW) return flate_hip_deflate_fast_batch(c, in, in_off, n, out, out_cap, out_off, flags);
-    if (!in_off || !out_off || (n && (!in || !out))) return FLATE_HIP_E_INVALID;
-    c->hip_err.clear();
-    if (n == 0) {
-      out_off[0] = 0;
-      return FLATE_HIP_OK;
-    }
-    // (host pointers: one copy in -- the checksums run on it --, compress, one copy out)
-    const FrameReq FR{wrap, nullptr, nullptr, nullptr, 0};
-    return deflate_common(c, in, in_off, n, out, out_cap, out_off, flags, false, nullptr, nullptr, &FR);
-  } catch (const std::exception &e) {  // (out of host memory in an index vector)
-    c->hip_err = e.what();
-    return FLATE_HIP_E_INTERNAL;
-  }
-}
-
-int flate_hip_deflate_fast_spliced_framed(flate_hip_ctx *c, const uint8_t *in, const uint64_t *in_off, uint32_t n,
-                                          uint32_t wrap, uint8_t *out, uint64_t out_cap, uint64_t *out_len,
-                                          uint64_t *bit_off, uint32_t flags) {
-  if (!c || wrap > FLATE_HIP_WRAP_GZIP) return FLATE_HIP_E_INVALID;
-  if (wrap == FLATE_HIP_WRAP_RAW) return flate_hip_deflate_fast_spliced(c, in, in_off, n, out, out_cap, out_len, bit_off, flags);
-  if (!in_off || !out || !out_len || (n && !in)) return FLATE_HIP_E_INVALID;
-  c->hip_err.clear();
-  if (n == 0) {  // header, the closing block of Writer::close, the trailer of nothing
-    static const uint8_t zmember[11] = {0x78, 0x01, 0x01, 0x00, 0x00, 0xff, 0xff, 0, 0, 0, 1};
-    static const uint8_t gmember[23] = {0x1f, 0x8b, 8, 0, 0, 0, 0, 0, 4, 255, 0x01, 0x00, 0x00, 0xff, 0xff};
-    const uint8_t *m = wrap == FLATE_HIP_WRAP_ZLIB ? zmember : gmember;
-    const uint64_t len = wrap == FLATE_HIP_WRAP_ZLIB ? sizeof zmember : sizeof gmember;
-    if (out_cap < len) return FLATE_HIP_E_OUT_TOO_SMALL;
-    if (flags & FLATE_HIP_DEVICE_PTRS) {
-      HIP_TRY(c, hipSetDevice(c->device));
-      HIP_TRY(c, hipMemcpyAsync(out, m, len, hipMemcpyHostToDevice, c->stream));
-      HIP_TRY(c, hipStreamSynchronize(c->stream));
-    } else {
-      memcpy(out, m, len);
-    }
-    *out_len = len;
-    if (bit_off) bit_off[0] = 0;
-    return FLATE_HIP_OK;
-  }
-  try {
-    const FrameReq FR{wrap, nullptr, nullptr, nullptr, 0};
-    return deflate_common(c, in, in_off, n, out, out_cap, bit_off, flags, true, out_len, nullptr, &FR);
-  } catch (const std::exception &e) {
-    c->hip_err = e.what();
-    return FLATE_HIP_E_INTERNAL;
-  }
-}
-
-// ---- BGZF files (the writing half; reading: flate_api_inflate.hip) ----
-
-size_t flate_hip_bgzf_bound(uint64_t in_len, uint32_t block_bytes) {
-  return (size_t)bgzf_file_bound(in_len, block_bytes, flate_hip_deflate_bound);
-}
-
-int flate_hip_bgzf_write(flate_hip_ctx *c, const uint8_t *in, uint64_t in_len, uint32_t block_bytes, uint8_t *out,
-                         uint64_t out_cap, uint64_t *out_len, uint64_t *member_off, uint32_t flags) {
-  // every check before any HIP call
-  if (!c) return FLATE_HIP_E_INVALID;
-  int rc = bgzf_write_args(in, in_len, block_bytes, out, out_len, flags);
-  if (rc) return rc;
-  c->hip_err.clear();
-  const uint32_t bb = bgzf_block_bytes(block_bytes);
-  const uint32_t n = (uint32_t)bgzf_n_blocks(in_len, bb);
-  if (n == 0) {  // the EOF marker alone
-    uint8_t eof[kBgzfEofLen];
-    for (uint32_t i = 0; i < kBgzfEofLen; ++i) eof[i] = bgzf_eof_byte(i);
-    if (out_cap < kBgzfEofLen) return FLATE_HIP_E_OUT_TOO_SMALL;
-    if (flags & FLATE_HIP_DEVICE_PTRS) {
-      HIP_TRY(c, hipSetDevice(c->device));
-      HIP_TRY(c, hipMemcpyAsync(out, eof, kBgzfEofLen, hipMemcpyHostToDevice, c->stream));
-      HIP_TRY(c, hipStreamSynchronize(c->stream));
-    } else {
-      memcpy(out, eof, kBgzfEofLen);
-    }
-    *out_len = kBgzfEofLen;
-    if (member_off) member_off[0] = 0;
-    return FLATE_HIP_OK;
-  }
-  try {
-    // the blocks as the streams of a batch: the framed encode path with the internal wrap (host pointers: one copy
-    // in -- the checksums run on it --, compress, one copy out)
-    std::vector<uint64_t> in_off((size_t)n + 1), off;
-    for (uint32_t k = 0; k < n; ++k) in_off[k] = (uint64_t)k * bb;
-    in_off[n] = in_len;
-    if (!member_off) off.resize((size_t)n + 1), member_off = off.data();
-    const FrameReq FR{kWrapBgzf, nullptr, nullptr, nullptr, 0};
-    return deflate_common(c, in, in_off.data(), n, out, out_cap, member_off, flags, false, out_len, nullptr, &FR);
-  } catch (const std::exception &e) {  // (out of host memory in an index vector)
-    c->hip_err = e.what();
-    return FLATE_HIP_E_INTERNAL;
-  }
-}
-}  // extern "C"

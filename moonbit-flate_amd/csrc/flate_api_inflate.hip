@@ -58,12 +58,6 @@ struct InfMember {
   int64_t err_off = -1;
 };
 
-// what a step of a call moves through the ctx's control-array staging (ctl_up / ctl_down)
-struct CtlBytes {
-  size_t up = 0, down = 0;
-  void operator+=(const CtlBytes &o) { up += o.up, down += o.down; }
-};
-
 // ---- the decoders ----
 
 using InfKernel = void (*)(InfParams);

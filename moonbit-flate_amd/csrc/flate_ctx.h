@@ -1,5 +1,6 @@
 // flate_ctx.h -- the ctx and the host-side helpers that more than one host file of the C ABI uses (private, host
-// only).  Everything in flate_host is DEFINED in flate_api.hip; flate_api_inflate.hip is the other user.
+// only).  Everything in flate_host is DEFINED in flate_api.hip; flate_api_deflate.hip (the encode calls) and
+// flate_api_inflate.hip (the decode calls) are the users.
 // (checksum.hip and gather.hip see the ctx through the flate::ctx_* accessors of flate_kernels.h.)
 #pragma once
 
@@ -13,6 +14,7 @@
 #include <thread>
 #include <vector>
 
+#include "deflate_plan.h"
 #include "flate_kernels.h"
 #include "inflate_route.h"
 
@@ -49,9 +51,6 @@ struct flate_hip_ctx {
   DevBuf d_in, d_out, d_in_off, d_chunk_base, d_ids16, d_ids32, d_matches, d_nmatch, d_ntok;
   DevBuf d_slot_off, d_out_len, d_out_off, d_status;
   DevBuf d_blk_base, d_blk_hist, d_blk_cl, d_blk_hdr, d_blk_meta, d_tile_meta, d_blk_sid;
-  // entropy stage with one wavefront per BLOCK instead of per stream: -1 = when the batch's streams
-  // have three or more blocks on average (multi-window streams), 0 = never, 1 = whenever possible
-  int entropy_per_block = -1;
   DevBuf d_istatus, d_ierr, d_debug, d_gtables, d_queue, d_simt_lens;
   DevBuf d_dicts, d_dict_at, d_dict_len;  // flate_hip_inflate_batch_dict: dictionary tails, per-stream (at, len)
   // flate_hip_deflate_fast_batch_dict (it shares the three above, there per used dictionary): the streams that start
@@ -71,25 +70,20 @@ struct flate_hip_ctx {
   DevBuf d_bgzf;
   hipStream_t guest_stream = nullptr;
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-  int guest_blocks = 0;      // 0 = guest kernel off
-  uint32_t guest_min = 1280; // below this many streams (5 per CU) the guests stay idle: one block per stream
   int32_t h_status_word = 0;  // landing pads of small async D2H copies
   int32_t h_status_aux = 0;   // (flate_hip_bgzf_write: the first block whose member BSIZE cannot express)
   uint64_t h_total_bytes = 0;
   uint32_t num_cus = 256;
   flate::InflateOpts inflate;  // the "inflate_*" options (inflate_route.h)
-  uint32_t resident_blocks = 1024;  // persistent LDS-table blocks (4 per CU x 256 CUs)
+  flate::EncodeOpts enc;       // the encoder's launch options (deflate_plan.h)
   // (Rounds 2-4 carried an entropy stage OVERLAPPED with the match finder -- sub-batches gated on counters
   // the persistent launch incremented, in an even and an uneven form.  Never faster than running the two one
   // after the other (profiles/r02, r04), and a soak run of round 4 once saw the pack kernel's self-check fire
   // in the even form, not reproduced in 115 000 stress runs: removed)
-  // window-granular scheduling of multi-window streams (lz77_kernels.hip, uq_*): on by default
-  int window_units = 1;
+  // window-granular scheduling of multi-window streams (lz77_kernels.hip, uq_*)
   DevBuf d_uq_ready, d_uq_tables, d_uq_sweep;
   DevBuf d_aux[2];  // ctx_scratch (checksum.hip)
-  // measurement aids (flate_hip_last_resident_share, option "profile_split_streams")
-  uint32_t profile_split = 0;        // > 0: LDS-table blocks take exactly the first K queue entries,
-                                     // the guest blocks the rest (two queues instead of one)
+  // measurement aid (flate_hip_last_resident_share)
   uint32_t last_count[2] = {0, 0};   // queue lengths of the last persistent launches (16-bit, multi)
   uint32_t queue_init = 0;
   uint32_t debug_chunks = 0;
@@ -98,9 +92,6 @@ struct flate_hip_ctx {
   // out (two copy threads on two non-blocking streams).  0 = one copy in, compress, one copy out.
   int host_groups = 8;
   uint32_t host_group_streams = 2048;  // a group holds at least this many streams (inflate: four times as many)
-  // bounded waits of the persistent kernels (uq_pop): polls before giving up
-  // (a poll is one relaxed load + s_sleep, >= 0.4 us; a wave that is not running does not count)
-  uint32_t spin_limit = 8u << 20;
   uint32_t inject_drop_push = 0;  // test hook: the k-th window hand-over (1-based) is dropped
   uint32_t inject_stall = 0;      // test hook: the k-th dense batch (1-based) of every chunk makes no progress
   uint64_t stream_rebase = 1ull << 30;  // flate_hip_stream: origin moved up past this many bytes
@@ -147,6 +138,11 @@ int ctl_begin(flate_hip_ctx *c, size_t up_bytes, size_t down_bytes);
 int ctl_up(flate_hip_ctx *c, void *dev_dst, const void *host_src, size_t bytes);  // (bytes: rounded up to 4)
 int ctl_down(flate_hip_ctx *c, void *host_dst, const void *dev_src, size_t bytes);
 void ctl_finish(flate_hip_ctx *c);
+// what a step of a call moves through that staging (the sum of a call's steps is what ctl_begin is given)
+struct CtlBytes {
+  size_t up = 0, down = 0;
+  void operator+=(const CtlBytes &o) { up += o.up, down += o.down; }
+};
 
 struct StageTimer {
   flate_hip_ctx *c;

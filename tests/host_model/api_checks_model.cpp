@@ -18,6 +18,14 @@ extern "C" int m_ptrs_ok(const uint8_t *in, const uint64_t *in_off, uint32_t n, 
 extern "C" int m_ranges(const uint64_t *in_off, uint32_t n, const uint64_t *out_off, uint32_t flags) {
   return inflate_batch_ranges(in_off, n, out_off, flags);
 }
+extern "C" int m_deflate_batch_ptrs_ok(const uint8_t *in, const uint64_t *in_off, uint32_t n, const uint8_t *out,
+                                       const uint64_t *out_off) {
+  return deflate_batch_ptrs_ok(in, in_off, n, out, out_off) ? 1 : 0;
+}
+extern "C" int m_deflate_spliced_ptrs_ok(const uint8_t *in, const uint64_t *in_off, uint32_t n, const uint8_t *out,
+                                         const uint64_t *out_len) {
+  return deflate_spliced_ptrs_ok(in, in_off, n, out, out_len) ? 1 : 0;
+}
 extern "C" int m_dict_table_ok(const uint8_t *dicts, const uint64_t *dict_off, uint32_t n_dicts) {
   return dict_table_ok(dicts, dict_off, n_dicts) ? 1 : 0;
 }
@@ -66,6 +74,19 @@ int main() {
     want(m_ranges(fits, 2, up, 0), 0, "ranges: one byte less");
     const uint64_t big_down[3] = {0, 0x7ffe0000ull, 1};
     want(m_ranges(big_down, 2, up, 0), INV, "ranges: descending wins over too large");
+  }
+  for (uint32_t n : {0u, 2u}) {  // the encode calls' pointers: every one missing in turn, without and with streams
+    const uint64_t up[3] = {0, 5, 9};
+    want(m_deflate_batch_ptrs_ok(&byte, up, n, &byte, up), 1, "deflate batch ptrs ok");
+    want(m_deflate_batch_ptrs_ok(nullptr, up, n, &byte, up), n ? 0 : 1, "deflate batch: no in");
+    want(m_deflate_batch_ptrs_ok(&byte, nullptr, n, &byte, up), 0, "deflate batch: no in_off");
+    want(m_deflate_batch_ptrs_ok(&byte, up, n, nullptr, up), n ? 0 : 1, "deflate batch: no out");
+    want(m_deflate_batch_ptrs_ok(&byte, up, n, &byte, nullptr), 0, "deflate batch: no out_off");
+    want(m_deflate_spliced_ptrs_ok(&byte, up, n, &byte, &len1), 1, "deflate spliced ptrs ok");
+    want(m_deflate_spliced_ptrs_ok(nullptr, up, n, &byte, &len1), n ? 0 : 1, "deflate spliced: no in");
+    want(m_deflate_spliced_ptrs_ok(&byte, nullptr, n, &byte, &len1), 0, "deflate spliced: no in_off");
+    want(m_deflate_spliced_ptrs_ok(&byte, up, n, nullptr, &len1), 0, "deflate spliced: no out (the closing block needs it)");
+    want(m_deflate_spliced_ptrs_ok(&byte, up, n, &byte, nullptr), 0, "deflate spliced: no out_len");
   }
   {  // dictionary tables
     const uint64_t up[3] = {4, 10, 10}, down[3] = {4, 10, 9}, empty[3] = {4, 4, 4};

@@ -1,4 +1,4 @@
-"""The argument checks of the decode calls (moonbit-flate_amd/csrc/api_checks.h) and the containers' constants
+"""The argument checks of the batch calls (moonbit-flate_amd/csrc/api_checks.h) and the containers' constants
 (flate_kernels.h) on the CPU: the entry points refuse a missing ctx first, so through the library every other refusal
 needs a device.  tests/host_model/api_checks_model.cpp includes the headers the entry points include."""
 import ctypes as C
@@ -38,6 +38,7 @@ def m():
     p = C.c_void_p
     L.m_ptrs_ok.argtypes = [p, p, C.c_uint32, p, p, p, p, p, C.c_uint32]
     L.m_ranges.argtypes = [p, C.c_uint32, p, C.c_uint32]
+    L.m_deflate_batch_ptrs_ok.argtypes = L.m_deflate_spliced_ptrs_ok.argtypes = [p, p, C.c_uint32, p, p]
     L.m_dict_table_ok.argtypes = [p, p, C.c_uint32]
     L.m_dict_args_ok.argtypes = [p, p, C.c_uint32, p, C.c_uint32]
     L.m_spliced_index_check.argtypes = [p, C.c_uint32, p, C.c_uint64, C.c_uint64]
@@ -74,6 +75,26 @@ def test_batch_pointers(m):
     assert m.m_ptrs_ok(None, up, 0, None, up, a, b, c, 0) == 1
     assert m.m_ptrs_ok(None, None, 0, None, up, a, b, c, 0) == 0
     assert m.m_ptrs_ok(None, up, 0, None, None, a, b, c, 0) == 0
+
+
+@pytest.mark.parametrize("n", [0, 2])
+def test_encode_pointers(m, n):
+    buf, up, one = (C.c_uint8 * 8)(), u64(0, 5, 9), (C.c_uint64 * 1)()
+    # flate_hip_deflate_fast_batch(_dict, _framed): (in, in_off, n, out, out_off) -- the index arrays always, the data
+    # pointers when there are streams
+    assert m.m_deflate_batch_ptrs_ok(buf, up, n, buf, up) == 1
+    for missing, needed in ((0, n > 0), (1, True), (3, n > 0), (4, True)):
+        args = [buf, up, n, buf, up]
+        args[missing] = None
+        assert m.m_deflate_batch_ptrs_ok(*args) == (0 if needed else 1), missing
+    assert m.m_deflate_batch_ptrs_ok(None, up, n, None, up) == (0 if n else 1)
+    # flate_hip_deflate_fast_spliced(_framed): (in, in_off, n, out, out_len) -- no streams still write the closing
+    # block, so out and out_len always; the bit index is optional and not part of the check
+    assert m.m_deflate_spliced_ptrs_ok(buf, up, n, buf, one) == 1
+    for missing, needed in ((0, n > 0), (1, True), (3, True), (4, True)):
+        args = [buf, up, n, buf, one]
+        args[missing] = None
+        assert m.m_deflate_spliced_ptrs_ok(*args) == (0 if needed else 1), missing
 
 
 def test_batch_ranges(m):

@@ -240,6 +240,32 @@ def test_zlib_members_with_dictionaries(eng, oracle, dict_case, compat_go, devic
         assert out.size == at
 
 
+@pytest.mark.parametrize("device", [False, True], ids=["host", "device"])
+def test_five_streams_that_make_every_upload_of_the_call(eng, oracle, device):
+    """The call with the most control-array uploads for the fewest streams: every match-finder list has one stream
+    (single-window, multi-window, dictionary), a fourth names a dictionary its encoder never sees (under 128 bytes),
+    the DICTIDs and the streams' checksums are staged, and every stream has a block, so the per-block entropy form
+    uploads its block list as well.  Each upload takes a 256-byte-aligned slot of the staging: a budget that is too
+    small shows here as FLATE_HIP_E_INTERNAL."""
+    dicts = [words(61, 40000), words(62, 900)]
+    shape = [(65535, NO_DICT), (3 * 65535 + 200, NO_DICT), (65535 + 300, 0), (100, 1), (20, NO_DICT)]
+    dict_of = [j for _, j in shape]
+    payloads = [((dicts[j][-300:] if j != NO_DICT else b"") + words(180 + k, n))[:n] for k, (n, j) in enumerate(shape)]
+    data, off = pack(payloads)
+    want = [dict_member(oracle, p, None if j == NO_DICT else dicts[j], False) for p, j in zip(payloads, dict_of)]
+    want_off = np.zeros(len(want) + 1, np.uint64)
+    np.cumsum(np.array([len(m) for m in want], dtype=np.uint64), out=want_off[1:])
+    eng.set_option("entropy_per_block", 1)
+    try:
+        out, ooff = eng.deflate_batch_framed(to_dev(data) if device else data, off, "zlib", zdicts=dicts, dict_of=dict_of)
+    finally:
+        eng.set_option("entropy_per_block", -1)
+    assert np.array_equal(ooff, want_off), (ooff.tolist(), want_off.tolist())
+    out = out.cpu().numpy() if device else out
+    for i, m in enumerate(want):
+        assert out[int(ooff[i]):int(ooff[i + 1])].tobytes() == m, "member %d (%d bytes of input)" % (i, len(payloads[i]))
+
+
 def test_dictionary_arguments(eng, oracle, dict_case):
     dicts, dict_of, payloads = dict_case
     data, off = pack(payloads)

@@ -127,8 +127,11 @@ def test_gpu_spliced_device_pointers_and_relation_to_the_batch_output(eng, oracl
 
 @pytest.mark.gpu
 def test_gpu_spliced_edge_cases(eng, oracle):
+    import torch
     out, n, bit_off = eng.deflate_spliced(np.zeros(8, np.uint8), np.zeros(1, np.uint64))
     assert bytes(out[:n]) == b"\x01\x00\x00\xff\xff"
+    out, n, bit_off = eng.deflate_spliced(torch.zeros(8, dtype=torch.uint8, device="cuda"), np.zeros(1, np.uint64))
+    assert bytes(out[:n].cpu().numpy()) == b"\x01\x00\x00\xff\xff" and bit_off.tolist() == [0]  # (device pointers)
     for specs in ([("text", 0)], [("text", 0), ("text", 0), ("text", 1)], [("rand", 5)] * 70,
                   [("text", 3000)], [("text", 20), ("zero", 3), ("text", 20), ("zero", 16)] * 9):
         data, off = make_streams(specs, seed=2)
