@@ -583,6 +583,78 @@ int flate_hip_bgzf_read(flate_hip_ctx *ctx, const uint8_t *in, uint64_t in_len, 
                         uint64_t *out_len, uint32_t *n_members, uint32_t *bad_member, int64_t *err_off,
                         int *eof_marker, uint32_t flags);
 
+/* -- BGZF random access: byte and virtual-offset ranges in one call --------------------
+ * BGZF exists for random access: a BAM, tabix or CSI index stores VIRTUAL FILE OFFSETS (coffset << 16 | uoffset: the
+ * file offset of a member, and a position in that member's output), and a region query is a list of chunks [v_begin,
+ * v_end); bgzip -b/-s does the same with plain byte positions.  flate_hip_bgzf_read_ranges takes a batch of such ranges,
+ * decodes the members they touch -- each ONCE, however many ranges touch it -- and delivers the requested bytes back to
+ * back.
+ *
+ * Notation: U = the file's uncompressed bytes (what flate_hip_bgzf_read delivers), T their count, member_off[0 .. n]
+ * and out_off_m[0 .. n] what flate_hip_bgzf_index defines, ISIZE[k] = out_off_m[k + 1] - out_off_m[k].
+ * begin, end: HOST arrays of n_ranges entries.  out_off: HOST array of n_ranges + 1 entries, written.  range_status:
+ * HOST array of n_ranges entries, written, may be NULL.  (Offset tables are always host arrays in this ABI.)  n_members,
+ * n_decoded, bad_member and err_off may each be NULL.  in / out: host, or device under FLATE_HIP_DEVICE_PTRS.
+ *
+ * Positions.  FLATE_HIP_BGZF_POS_BYTES: range r is U[min(begin[r], T), min(end[r], T)) -- it reads short at the end of
+ * the file, as pread does.  FLATE_HIP_BGZF_POS_VIRTUAL: v = (c << 16) | u is VALID iff c == member_off[k] for some k in
+ * [0, n] (k == n: c == in_len, the end of the file; a c that merely passes the member rule, such as a decoy inside a
+ * stored block, is not valid) and u <= ISIZE[k], with only u == 0 allowed for k == n.  Its position is p(v) =
+ * out_off_m[k] + u, and range r is U[p(begin[r]), p(end[r])).  A range with an invalid end point is decided on the
+ * device: range_status[r] = FLATE_HIP_E_INVALID, and it delivers zero bytes.
+ *
+ * Touched members.  Member k is touched iff ISIZE[k] > 0 and [out_off_m[k], out_off_m[k + 1]) intersects some valid,
+ * non-empty range.  Every touched member is decoded once per call, whole, and verified exactly as
+ * flate_hip_inflate_batch_framed(FLATE_HIP_WRAP_GZIP) verifies it: header, raw stream up to the trailer, CRC-32, ISIZE.
+ * Untouched members are neither decoded nor verified.  The CHAIN is always validated whole: discovery runs as in
+ * flate_hip_bgzf_read.  *n_members = n, *n_decoded = the number of touched members.
+ *
+ * Output.  out[out_off[r], out_off[r + 1]) = the bytes of range r: the ranges lie back to back in the order given,
+ * out_off[0] = 0, out_off[n_ranges] = the total.  Ranges may overlap, repeat, be empty and come in any order.  Bytes
+ * that come from a member whose status is non-zero are unspecified; everything else is exact.  Device pointers: nothing
+ * outside out[0, out_off[n_ranges]) is written.  Host pointers: that range is copied back once, nothing behind it is
+ * written.
+ *
+ * Verdict, in this order.
+ *  1. FLATE_HIP_E_INVALID before any HIP call: NULL ctx / in (with in_len > 0) / begin / end / out_off (with n_ranges >
+ *     0); out == NULL with out_cap > 0; an unknown pos_kind; flags other than FLATE_HIP_DEVICE_PTRS; begin[r] > end[r]
+ *     numerically for any r, in either kind (for valid virtual offsets numeric order is position order).
+ *  2. n_ranges == 0: out_off[0] = 0 if out_off is given, FLATE_HIP_OK, nothing is read.
+ *  3. A malformed chain: the return value and *err_off are flate_hip_bgzf_index's, *bad_member = the count of good
+ *     members, every out_off entry is 0, every range_status[r] = FLATE_HIP_E_CORRUPT; nothing is decoded or written.
+ *  4. A total above out_cap: FLATE_HIP_E_OUT_TOO_SMALL; out_off is fully written (out_off[n_ranges] = the size needed),
+ *     nothing is decoded or written.  out == NULL with out_cap == 0 is the size query -- unless the total is 0, which
+ *     is FLATE_HIP_OK.
+ *  5. Otherwise everything is decoded and delivered.  range_status[r] = FLATE_HIP_E_INVALID as above, else the first
+ *     non-zero status among the members r touches in file order, else 0.  The return value is the first non-zero status
+ *     among the decoded members in file order, with *bad_member = its index in the file and *err_off = its file offset;
+ *     otherwise FLATE_HIP_E_INVALID if any range was invalid, else FLATE_HIP_OK with *bad_member = 0xffffffff and
+ *     *err_off = -1.
+ * in_len == 0: zero members, T = 0; every byte range is empty, virtual offset 0 is the only valid one.
+ *
+ * Host pointers: the file is uploaded once -- index, selection and decode share the staged copy, as in
+ * flate_hip_bgzf_read -- and the delivered bytes come down once.  A caller with many queries keeps the file on the
+ * device and uses FLATE_HIP_DEVICE_PTRS.
+ *   How (bgzf_range_kernels.hip), all on the ctx's stream behind discovery, no host pass over file bytes: LOCATE, one
+ *   thread per range (the rule is bgzf_range_rule.h: byte positions clamped, virtual offsets found in member_off by
+ *   binary search); SELECT, +1 / -1 per range into a difference array over the members, a scan, the mask ISIZE > 0, one
+ *   scan for rank and scratch offset, compaction in file order -- no walk over a range's span; ONE read-back of the
+ *   selected members' index and the ranges' layout (the synchronisation flate_hip_bgzf_read has between index and
+ *   decode); DECODE of the selected members, which are not consecutive in the file, through the framed gzip read into a
+ *   dense scratch; GATHER of every range's one contiguous run of that scratch into out: pieces of at most 64 KiB,
+ *   16-byte stores on the destination's grid with the source realigned in registers, heads and tails byte-exact.
+ *   Locate, select and gather are counted in no profiling stage; FLATE_HIP_STAGE_INFLATE / _CHECKSUM mean what they
+ *   mean in flate_hip_bgzf_read.  A failed scratch allocation is FLATE_HIP_E_HIP, never a truncated result.
+ *   Out of scope: a caller-supplied index; uploading only the touched members from host memory; caching the index
+ *   across calls; decoding straight into out for whole-member spans. */
+#define FLATE_HIP_BGZF_POS_BYTES   0u  /* begin/end: positions in the file's uncompressed bytes       */
+#define FLATE_HIP_BGZF_POS_VIRTUAL 1u  /* begin/end: BGZF virtual offsets, coffset << 16 | uoffset     */
+int flate_hip_bgzf_read_ranges(flate_hip_ctx *ctx, const uint8_t *in, uint64_t in_len, uint32_t pos_kind,
+                               const uint64_t *begin, const uint64_t *end, uint32_t n_ranges,
+                               uint8_t *out, uint64_t out_cap, uint64_t *out_off, int32_t *range_status,
+                               uint32_t *n_members, uint32_t *n_decoded, uint32_t *bad_member,
+                               int64_t *err_off, uint32_t flags);
+
 /* -- exchange step (multi-GPU) ---------------------------------------------------
  * SURVEY 8(e) / section 5; no counterpart in the reference (single-threaded, no communication
  * layer).  Independent streams shard by contiguous index range, one process and one ctx per

@@ -25,6 +25,7 @@ EXPORTS = [
     "flate_hip_frame_overhead", "flate_hip_deflate_fast_batch_framed", "flate_hip_deflate_fast_spliced_framed",
     "flate_hip_inflate_batch_framed", "flate_hip_inflate_spliced_framed",
     "flate_hip_bgzf_bound", "flate_hip_bgzf_write", "flate_hip_bgzf_index", "flate_hip_bgzf_read",
+    "flate_hip_bgzf_read_ranges",
 ]
 
 _lib = None
@@ -103,6 +104,11 @@ def load():
         L.flate_hip_bgzf_index.restype = C.c_int
         L.flate_hip_bgzf_read.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, u64p, u32p, u32p, i64p, ip, C.c_uint32]
         L.flate_hip_bgzf_read.restype = C.c_int
+    if os.environ.get("FLATE_HIP_LIB") is None or hasattr(L, "flate_hip_bgzf_read_ranges"):
+        u32p, i64p = C.POINTER(C.c_uint32), C.POINTER(C.c_int64)
+        L.flate_hip_bgzf_read_ranges.argtypes = [vp, vp, C.c_uint64, C.c_uint32, vp, vp, C.c_uint32, vp, C.c_uint64, vp, vp,
+                                                 u32p, u32p, u32p, i64p, C.c_uint32]
+        L.flate_hip_bgzf_read_ranges.restype = C.c_int
     L.flate_hip_inflate_spliced.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint32, vp, vp, vp, vp, vp, C.c_uint32]
     L.flate_hip_inflate_spliced.restype = C.c_int
     L.flate_hip_set_profiling.argtypes = [vp, C.c_int]

@@ -68,7 +68,7 @@ inline int spliced_index_check(const uint64_t *bit_off, uint32_t n, const uint64
   return FLATE_HIP_OK;
 }
 
-// ---- BGZF files (flate_hip_bgzf_write / _index / _read) ----
+// ---- BGZF files (flate_hip_bgzf_write / _index / _read / _read_ranges) ----
 
 // block_bytes as the caller passes it -> the block size in use (0 = the default), or 0: not 1 .. 65535, one LZ77 window
 inline uint32_t bgzf_block_bytes(uint32_t block_bytes) {
@@ -103,6 +103,20 @@ inline int bgzf_read_args(const uint8_t *in, uint64_t in_len, const uint8_t *out
                           const uint64_t *out_len, uint32_t flags) {
   if (!out_len || (in_len && !in) || (out_cap && !out)) return FLATE_HIP_E_INVALID;
   return (flags & ~FLATE_HIP_DEVICE_PTRS) ? FLATE_HIP_E_INVALID : FLATE_HIP_OK;
+}
+// flate_hip_bgzf_read_ranges: everything that is refused before any HIP call.  begin, end and out_off are HOST arrays;
+// begin[r] > end[r] numerically is refused in either kind of position (for valid virtual offsets numeric order is
+// position order).
+inline int bgzf_ranges_args(const uint8_t *in, uint64_t in_len, uint32_t pos_kind, const uint64_t *begin,
+                            const uint64_t *end, uint32_t n_ranges, const uint8_t *out, uint64_t out_cap,
+                            const uint64_t *out_off, uint32_t flags) {
+  if ((in_len && !in) || (out_cap && !out)) return FLATE_HIP_E_INVALID;
+  if (n_ranges && (!begin || !end || !out_off)) return FLATE_HIP_E_INVALID;
+  if (pos_kind != FLATE_HIP_BGZF_POS_BYTES && pos_kind != FLATE_HIP_BGZF_POS_VIRTUAL) return FLATE_HIP_E_INVALID;
+  if (flags & ~FLATE_HIP_DEVICE_PTRS) return FLATE_HIP_E_INVALID;
+  for (uint32_t r = 0; r < n_ranges; ++r)
+    if (begin[r] > end[r]) return FLATE_HIP_E_INVALID;
+  return FLATE_HIP_OK;
 }
 // how many candidates the discovery arrays hold on the first attempt (real files: one member per tens of KiB; a file
 // of nothing but empty members has one per 28 bytes and takes the second attempt, sized from the count)

@@ -7,10 +7,12 @@
 // ctx, its staging and the host pipeline are flate_api.hip's (flate_ctx.h).
 #include "flate_ctx.h"
 
+#include <cstring>
 #include <exception>
 #include <stdexcept>
 
 #include "api_checks.h"
+#include "bgzf_range_rule.h"
 #include "bgzf_rule.h"
 
 using namespace flate;
@@ -29,6 +31,9 @@ struct InfCall {
   int64_t *err_off;
   uint32_t flags;
   uint64_t spliced_len;
+  // members of a container that are NOT consecutive in `in` (flate_hip_bgzf_read_ranges: the touched members of a file):
+  // member i = in[in_off[i], in_end[i]); null: it ends at in_off[i + 1].  With an InfFrame and device pointers only.
+  const uint64_t *in_end = nullptr;
 };
 
 // Preset dictionaries of a launch (flate_hip_inflate_batch_dict): the device tails and, per stream of the
@@ -316,8 +321,9 @@ static int inflate_common(flate_hip_ctx *c, const InfCall &A, const InfDict *D =
   if ((rc = ensure(c, c->d_out_len, (size_t)n * 8 + 8))) return rc;
   if ((rc = ensure(c, c->d_istatus, (size_t)n * 4 + 4))) return rc;
   if ((rc = ensure(c, c->d_ierr, (size_t)n * 8 + 8))) return rc;
-  // up: in_off, out_off; down: out_len, status, err_off
-  CtlBytes ctl{((size_t)n + 1) * 16, (size_t)n * 20 + 64};
+  if (A.in_end && (rc = ensure(c, c->d_in_end, (size_t)n * 8 + 8))) return rc;
+  // up: in_off, out_off (the members' ends); down: out_len, status, err_off
+  CtlBytes ctl{((size_t)n + 1) * 16 + (A.in_end ? (size_t)n * 8 + 8 : 0), (size_t)n * 20 + 64};
   if (FRD) {
     ctl += members_before_ctl(*FRD);
     ctl += members_after_ctl(sum_slots, n);
@@ -329,6 +335,7 @@ static int inflate_common(flate_hip_ctx *c, const InfCall &A, const InfDict *D =
   if ((rc = ctl_begin(c, ctl.up, ctl.down))) return rc;
   if ((rc = ctl_up(c, c->d_in_off.p, A.in_off, ((size_t)n + 1) * 8))) return rc;
   if ((rc = ctl_up(c, c->d_slot_off.p, out_off, ((size_t)n + 1) * 8))) return rc;
+  if (A.in_end && (rc = ctl_up(c, c->d_in_end.p, A.in_end, (size_t)n * 8))) return rc;
   InfParams I{};
   I.in = d_in;
   I.in_off = (const uint64_t *)c->d_in_off.p;
@@ -352,10 +359,11 @@ static int inflate_common(flate_hip_ctx *c, const InfCall &A, const InfDict *D =
   // the container in front of the decoders
   FrameReadParams R{};
   FrameSplicedParams S{};
+  if (A.in_end) R.in_end = (const uint64_t *)c->d_in_end.p;
   if (FRD && (rc = members_before(c, *FRD, d_in, sum_slots, n, A.flags, I, R, dict))) return rc;
   if (SM && (rc = member_before(c, *SM, d_in, in_bytes, n, I, S))) return rc;
 
-  const InflateRoute route = inflate_route(c->inflate, c->num_cus, n, longest_entry(A.in_off, n), spliced, size_only);
+  const InflateRoute route = inflate_route(c->inflate, c->num_cus, n, longest_entry(A.in_off, A.in_end, n), spliced, size_only);
   if ((rc = launch_decoders(c, route, I, dict))) return rc;
   HIP_TRY(c, hipGetLastError());
 
@@ -775,6 +783,188 @@ int flate_hip_bgzf_read(flate_hip_ctx *c, const uint8_t *in, uint64_t in_len, ui
         return st[i];
       }
     return FLATE_HIP_OK;
+  } catch (const std::exception &e) {  // (out of host memory in an index vector)
+    c->hip_err = e.what();
+    return FLATE_HIP_E_INTERNAL;
+  }
+}
+
+// Random access: discovery as in flate_hip_bgzf_read, then locate / select / layout (bgzf_range_kernels.hip) behind it
+// on the same stream, ONE read-back (the ranges' layout and the selected members' index), the framed gzip read over
+// the selected members -- which are not consecutive in the file: InfCall::in_end -- into a dense scratch, the gather.
+int flate_hip_bgzf_read_ranges(flate_hip_ctx *c, const uint8_t *in, uint64_t in_len, uint32_t pos_kind,
+                               const uint64_t *begin, const uint64_t *end, uint32_t n_ranges, uint8_t *out,
+                               uint64_t out_cap, uint64_t *out_off, int32_t *range_status, uint32_t *n_members,
+                               uint32_t *n_decoded, uint32_t *bad_member, int64_t *err_off, uint32_t flags) {
+  // every check before any HIP call
+  if (!c) return FLATE_HIP_E_INVALID;
+  int rc = bgzf_ranges_args(in, in_len, pos_kind, begin, end, n_ranges, out, out_cap, out_off, flags);
+  if (rc) return rc;
+  c->hip_err.clear();
+  if (n_members) *n_members = 0;
+  if (n_decoded) *n_decoded = 0;
+  if (bad_member) *bad_member = 0xffffffffu;
+  if (err_off) *err_off = -1;
+  if (n_ranges == 0) {
+    if (out_off) out_off[0] = 0;
+    return FLATE_HIP_OK;
+  }
+  const uint32_t nr = n_ranges;
+  if (in_len == 0) {  // no members, T = 0: the rule over the index {0}, {0}; nothing to run on the device
+    const uint64_t zero = 0;
+    bool invalid = false;
+    out_off[0] = 0;
+    for (uint32_t r = 0; r < nr; ++r) {
+      const BgzfRangeLoc L = bgzf_range_locate(pos_kind, begin[r], end[r], &zero, &zero, 0);
+      out_off[r + 1] = 0;
+      if (range_status) range_status[r] = L.status ? FLATE_HIP_E_INVALID : FLATE_HIP_OK;
+      invalid = invalid || L.status != 0;
+    }
+    return invalid ? FLATE_HIP_E_INVALID : FLATE_HIP_OK;
+  }
+  try {
+    const bool dev = (flags & FLATE_HIP_DEVICE_PTRS) != 0;
+    const uint8_t *d_in = nullptr;
+    if ((rc = bgzf_stage(c, in, in_len, flags, &d_in))) return rc;
+    for (int k = 0; k < FLATE_HIP_STAGE_COUNT; ++k) c->stage_ms[k] = 0;
+    BgzfHead H{};
+    BgzfParams P{};
+    if ((rc = bgzf_discover(c, d_in, in_len, H, P))) return rc;
+    const uint32_t n = H.n_members;
+    if (n_members) *n_members = n;
+    if (H.rc) {  // a malformed chain: nothing is decoded, nothing is written
+      if (bad_member) *bad_member = n;
+      if (err_off) *err_off = H.err_off;
+      for (uint32_t r = 0; r <= nr; ++r) out_off[r] = 0;
+      if (range_status)
+        for (uint32_t r = 0; r < nr; ++r) range_status[r] = FLATE_HIP_E_CORRUPT;
+      return H.rc;
+    }
+
+    // locate, select, layout: the arrays carved from one buffer, what the host reads back as one block at its end
+    size_t at = 0;
+    auto carve = [&](size_t bytes) {
+      const size_t here = at;
+      at += (bytes + 255) & ~(size_t)255;
+      return here;
+    };
+    const size_t o_begin = carve((size_t)nr * 8), o_end = carve((size_t)nr * 8), o_diff = carve(((size_t)n + 1) * 4),
+                 o_rank = carve((size_t)n * 4 + 4), o_sat = carve((size_t)n * 8 + 8), o_rb = carve((size_t)nr * 8),
+                 o_rlen = carve((size_t)nr * 8), o_rfirst = carve((size_t)nr * 4), o_rlast = carve((size_t)nr * 4),
+                 o_rsrc = carve((size_t)nr * 8);
+    const size_t o_back = at;
+    const size_t o_head = carve(sizeof(BgzfRangeHead)), o_roff = carve(((size_t)nr + 1) * 8), o_rst = carve((size_t)nr * 4),
+                 o_rlo = carve((size_t)nr * 4), o_rhi = carve((size_t)nr * 4), o_sel = carve((size_t)n * sizeof(BgzfSel) + 8);
+    const size_t back_bytes = at - o_back;
+    if ((rc = ensure(c, c->d_bgzf_rng, at))) return rc;  // (a failed allocation is FLATE_HIP_E_HIP)
+    uint8_t *b = (uint8_t *)c->d_bgzf_rng.p;
+    BgzfRangeParams Q{};
+    Q.member_off = P.member_off;
+    Q.out_off_m = P.out_off;
+    Q.isize = P.isize;
+    Q.n_members = n;
+    Q.n_ranges = nr;
+    Q.pos_kind = pos_kind;
+    Q.begin = (const uint64_t *)(b + o_begin);
+    Q.end = (const uint64_t *)(b + o_end);
+    Q.diff = (int32_t *)(b + o_diff);
+    Q.rank = (uint32_t *)(b + o_rank);
+    Q.scratch_at = (uint64_t *)(b + o_sat);
+    Q.r_b = (uint64_t *)(b + o_rb);
+    Q.r_len = (uint64_t *)(b + o_rlen);
+    Q.r_first = (uint32_t *)(b + o_rfirst);
+    Q.r_last = (uint32_t *)(b + o_rlast);
+    Q.r_src = (uint64_t *)(b + o_rsrc);
+    Q.head = (BgzfRangeHead *)(b + o_head);
+    Q.r_out_off = (uint64_t *)(b + o_roff);
+    Q.r_status = (int32_t *)(b + o_rst);
+    Q.r_rank_lo = (uint32_t *)(b + o_rlo);
+    Q.r_rank_hi = (uint32_t *)(b + o_rhi);
+    Q.sel = (BgzfSel *)(b + o_sel);
+    HIP_TRY(c, hipMemcpyAsync(b + o_begin, begin, (size_t)nr * 8, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(b + o_end, end, (size_t)nr * 8, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemsetAsync(b + o_diff, 0, ((size_t)n + 1) * 4, c->stream));
+    hipLaunchKernelGGL(bgzf_range_locate_kernel, dim3((nr + 255u) / 256u), dim3(256), 0, c->stream, Q);
+    hipLaunchKernelGGL(bgzf_range_select_kernel, dim3(1), dim3(1024), 0, c->stream, Q);
+    hipLaunchKernelGGL(bgzf_range_layout_kernel, dim3(1), dim3(1024), 0, c->stream, Q);
+    HIP_TRY(c, hipGetLastError());
+    std::vector<uint8_t> back(back_bytes);
+    HIP_TRY(c, hipMemcpyAsync(back.data(), b + o_back, back_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    BgzfRangeHead RH;
+    memcpy(&RH, back.data() + (o_head - o_back), sizeof RH);
+    const int32_t *r_status = (const int32_t *)(back.data() + (o_rst - o_back));
+    const uint32_t *r_lo = (const uint32_t *)(back.data() + (o_rlo - o_back));
+    const uint32_t *r_hi = (const uint32_t *)(back.data() + (o_rhi - o_back));
+    const BgzfSel *sel = (const BgzfSel *)(back.data() + (o_sel - o_back));
+    const uint32_t ns = RH.n_sel;
+    if (ns > n) {
+      c->hip_err = "BGZF ranges: more members selected than the file has";
+      return FLATE_HIP_E_INTERNAL;
+    }
+    memcpy(out_off, back.data() + (o_roff - o_back), ((size_t)nr + 1) * 8);
+    if (n_decoded) *n_decoded = ns;
+    if (range_status)
+      for (uint32_t r = 0; r < nr; ++r) range_status[r] = r_status[r];
+    if (RH.out_total > out_cap) return FLATE_HIP_E_OUT_TOO_SMALL;  // (the size query too: nothing is decoded)
+    const int verdict = RH.any_invalid ? FLATE_HIP_E_INVALID : FLATE_HIP_OK;
+    if (ns == 0 || RH.out_total == 0) return verdict;  // (no range holds a byte)
+
+    // the framed gzip read over the selected members into the dense scratch
+    std::vector<uint64_t> moff((size_t)ns + 1), mend(ns), soff((size_t)ns + 1), olen(ns);
+    std::vector<int32_t> st(ns);
+    std::vector<int64_t> eo(ns);
+    for (uint32_t i = 0; i < ns; ++i) {
+      moff[i] = sel[i].in_off, mend[i] = sel[i].in_end, soff[i] = sel[i].scratch_off;
+      if (mend[i] < moff[i] || mend[i] > in_len || mend[i] - moff[i] > kBgzfMemberMax ||
+          soff[i] + sel[i].isize > RH.scratch_total) {
+        c->hip_err = "BGZF ranges: a selected member outside the file or the scratch";
+        return FLATE_HIP_E_INTERNAL;
+      }
+    }
+    moff[ns] = in_len, soff[ns] = RH.scratch_total;
+    if ((rc = ensure(c, c->d_bgzf_dense, RH.scratch_total + 64))) return rc;
+    uint8_t *d_dense = (uint8_t *)c->d_bgzf_dense.p;
+    const InfFrame FRD{FLATE_HIP_WRAP_GZIP, nullptr, nullptr, 0, nullptr};
+    InfCall call{d_in, moff.data(), ns, d_dense, soff.data(), olen.data(), st.data(), eo.data(),
+                 flags | FLATE_HIP_DEVICE_PTRS, 0};
+    call.in_end = mend.data();
+    rc = inflate_common(c, call, nullptr, &FRD);
+    if (!is_stream_status(rc)) return rc;
+
+    // the gather: every range's run of the scratch to its place in out
+    uint8_t *d_out = out;
+    if (!dev) {
+      if ((rc = ensure(c, c->d_out, RH.out_total + 16))) return rc;
+      d_out = (uint8_t *)c->d_out.p;
+    }
+    const uint64_t windows = (RH.out_total + (uint64_t)kBgzfGatherRangeCost * nr + kBgzfGatherWindow - 1) / kBgzfGatherWindow;
+    if (windows > 0x7fffffffull) return FLATE_HIP_E_TOO_LARGE;
+    BgzfGatherParams G{};
+    G.scratch = d_dense;
+    G.out = d_out;
+    G.r_out_off = Q.r_out_off;
+    G.r_src = Q.r_src;
+    G.n_ranges = nr;
+    hipLaunchKernelGGL(bgzf_gather_kernel, dim3((uint32_t)windows), dim3(256), 0, c->stream, G);
+    HIP_TRY(c, hipGetLastError());
+    if (!dev) HIP_TRY(c, hipMemcpyAsync(out, d_out, RH.out_total, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+
+    // the statuses: nxt[i] = the first selected member at or behind i with a status
+    std::vector<uint32_t> nxt((size_t)ns + 1);
+    nxt[ns] = ns;
+    for (uint32_t i = ns; i-- > 0;) nxt[i] = st[i] ? i : nxt[i + 1];
+    if (range_status)
+      for (uint32_t r = 0; r < nr; ++r)
+        if (!r_status[r] && r_lo[r] < r_hi[r] && r_hi[r] <= ns && nxt[r_lo[r]] < r_hi[r]) range_status[r] = st[nxt[r_lo[r]]];
+    if (nxt[0] < ns) {
+      const uint32_t i = nxt[0];
+      if (bad_member) *bad_member = sel[i].member;
+      if (err_off) *err_off = (int64_t)moff[i];
+      return st[i];
+    }
+    return verdict;
   } catch (const std::exception &e) {  // (out of host memory in an index vector)
     c->hip_err = e.what();
     return FLATE_HIP_E_INTERNAL;

@@ -68,6 +68,9 @@ struct flate_hip_ctx {
   DevBuf d_rd_one;
   // flate_hip_bgzf_index / _read: the discovery kernels' arrays (BgzfParams), carved from one buffer
   DevBuf d_bgzf;
+  // flate_hip_bgzf_read_ranges: the range kernels' arrays (BgzfRangeParams), carved from one buffer; the dense scratch
+  // the touched members are decoded into; and, for the framed read it runs over them, the members' ends
+  DevBuf d_bgzf_rng, d_bgzf_dense, d_in_end;
   hipStream_t guest_stream = nullptr;
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
   int32_t h_status_word = 0;  // landing pads of small async D2H copies

@@ -274,6 +274,8 @@ __global__ void frame_write_kernel(FrameParams P);
 struct FrameReadParams {
   const uint8_t *in;
   const uint64_t *in_off;   // n_streams + 1: the members
+  const uint64_t *in_end;   // per member: where it ends; null (the public call): member i ends at in_off[i + 1].  Members
+                            // that are NOT consecutive in `in` (flate_hip_bgzf_read_ranges: the touched ones of a file)
   uint32_t n_streams;
   uint32_t wrap;            // FLATE_HIP_WRAP_ZLIB / _GZIP
   const uint32_t *dict_id;  // per dictionary: the Adler-32 of the whole of it (n_dicts == 0: unused)
@@ -371,6 +373,69 @@ __global__ void bgzf_round_kernel(BgzfParams P, uint32_t j);
 __global__ void bgzf_finish_kernel(BgzfParams P);
 __global__ void bgzf_out_scan_kernel(BgzfParams P);
 constexpr uint32_t kBgzfTile = 4096;
+
+// BGZF random access (bgzf_range_kernels.hip; flate_hip_bgzf_read_ranges): behind the discovery kernels, on the index
+// where they left it.  Locate: one thread per range (bgzf_range_rule.h) -- b, length, status, the first and the last
+// member with bytes inside it -- and +1 / -1 into a difference array over the members.  Select: its scan says which
+// members some range covers; masked with ISIZE > 0, one scan of (1, ISIZE) gives every selected member its rank and its
+// place in the dense scratch, and the members are compacted in file order.  Layout: the scan of the ranges' lengths
+// (their places in `out`), and where every range's ONE run starts in the scratch.  Gather: the runs into `out`.
+struct BgzfRangeHead {     // the result words, read back in front of the arrays
+  uint64_t out_total;      // bytes of all ranges
+  uint64_t scratch_total;  // bytes of all selected members
+  uint32_t n_sel;          // selected (touched) members
+  uint32_t any_invalid;    // some range had an invalid end point
+};
+struct BgzfSel {           // one selected member, in file order
+  uint64_t in_off, in_end; // its bytes in the file
+  uint64_t scratch_off;    // where its output goes in the dense scratch
+  uint32_t member;         // its index in the file
+  uint32_t isize;
+};
+struct BgzfRangeParams {
+  // the index (BgzfParams), n = head->n_members of a well-formed chain
+  const uint64_t *member_off;
+  const uint64_t *out_off_m;
+  const uint32_t *isize;
+  uint32_t n_members;
+  uint32_t n_ranges;
+  uint32_t pos_kind;
+  const uint64_t *begin;   // n_ranges each (device copies of the caller's arrays)
+  const uint64_t *end;
+  int32_t *diff;           // n_members + 1, zeroed: +1 at a range's first member, -1 behind its last
+  uint32_t *rank;          // n_members: selected members in front of member k
+  uint64_t *scratch_at;    // n_members: selected bytes in front of member k
+  // per range
+  uint64_t *r_b;           // locate: where it starts in U
+  uint64_t *r_len;         // locate: its length
+  uint32_t *r_first;       // locate: its first / last member, or kBgzfNoMember
+  uint32_t *r_last;
+  uint64_t *r_src;         // layout: where its run starts in the scratch
+  // what the host reads back, one block: head | r_out_off (n_ranges + 1) | r_status | r_rank_lo | r_rank_hi | sel
+  BgzfRangeHead *head;
+  uint64_t *r_out_off;
+  int32_t *r_status;
+  uint32_t *r_rank_lo;     // the selected members [r_rank_lo, r_rank_hi) are the ones the range touches
+  uint32_t *r_rank_hi;
+  BgzfSel *sel;            // n_members entries of room, head->n_sel used
+};
+__global__ void bgzf_range_locate_kernel(BgzfRangeParams P);
+__global__ void bgzf_range_select_kernel(BgzfRangeParams P);
+__global__ void bgzf_range_layout_kernel(BgzfRangeParams P);
+// The gather: range r's run scratch[r_src[r], + len) -> out[r_out_off[r], + len), both sides at any byte alignment.
+// Work is cut by COST = bytes + kBgzfGatherRangeCost per range: workgroup j owns the cost window [j, j + 1) *
+// kBgzfGatherWindow, so one huge range fills the chip in 64 KiB pieces and many tiny ranges share a workgroup.  The
+// scratch must be a 16-byte aligned allocation with 32 readable bytes behind its last run.
+struct BgzfGatherParams {
+  const uint8_t *scratch;
+  uint8_t *out;
+  const uint64_t *r_out_off;  // n_ranges + 1
+  const uint64_t *r_src;      // n_ranges
+  uint32_t n_ranges;
+};
+constexpr uint32_t kBgzfGatherWindow = 65536;
+constexpr uint32_t kBgzfGatherRangeCost = 256;
+__global__ void bgzf_gather_kernel(BgzfGatherParams P);
 
 size_t inflate_simt_lds_bytes(int lanes_per_wave);  // dynamic LDS of that launch
 size_t inflate_simt_lens_bytes(uint32_t blocks);    // global scratch of that launch (InfParams::simt_lens)

@@ -155,7 +155,7 @@ __device__ inline uint32_t get_le32(const uint8_t *p) {
 __global__ __launch_bounds__(256) void frame_parse_kernel(FrameReadParams P) {
   const uint32_t i = blockIdx.x * 256u + threadIdx.x;
   if (i >= P.n_streams) return;
-  const uint64_t a = P.in_off[i], len = P.in_off[i + 1] - a;
+  const uint64_t a = P.in_off[i], len = (P.in_end ? P.in_end[i] : P.in_off[i + 1]) - a;
   const uint8_t *m = P.in + a;
   uint64_t hl = 0, tl = 0;
   bool ok = false;
@@ -236,7 +236,7 @@ __global__ __launch_bounds__(256) void frame_verdict_kernel(FrameReadParams P) {
                         (P.wrap == FLATE_HIP_WRAP_GZIP && (uint32_t)P.out_len[i] != P.isize[i]);
   if (mismatch) {
     P.status[i] = FLATE_HIP_E_CORRUPT;
-    P.err_off[i] = (int64_t)(P.in_off[i + 1] - P.in_off[i]);
+    P.err_off[i] = (int64_t)((P.in_end ? P.in_end[i] : P.in_off[i + 1]) - P.in_off[i]);
   }
 }
 

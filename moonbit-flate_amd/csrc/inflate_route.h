@@ -48,6 +48,15 @@ inline uint64_t longest_entry(const uint64_t *off, uint32_t n) {
   return longest;
 }
 
+// ... of entries that end at end[i] (members that are not consecutive: InfParams::in_end)
+inline uint64_t longest_entry(const uint64_t *off, const uint64_t *end, uint32_t n) {
+  if (!end) return longest_entry(off, n);
+  uint64_t longest = 0;
+  for (uint32_t i = 0; i < n; ++i)
+    if (end[i] - off[i] > longest) longest = end[i] - off[i];
+  return longest;
+}
+
 // longest: longest_entry of the call's in_off -- bytes of a stream, or, spliced, bits of a piece.
 // size_only: FLATE_HIP_SIZE_ONLY was asked for (it holds for independent streams only).
 inline InflateRoute inflate_route(const InflateOpts &o, uint32_t num_cus, uint32_t n, uint64_t longest, bool spliced,

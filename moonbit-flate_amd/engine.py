@@ -55,6 +55,7 @@ BGZF_MEMBER_MAX = 65536
 BGZF_EOF = bytes.fromhex("1f8b08040000000000ff0600424302001b0003000000000000000000")
 BgzfIndex = collections.namedtuple("BgzfIndex", "rc n_members out_bytes eof_marker err_off member_off out_off")
 BgzfRead = collections.namedtuple("BgzfRead", "rc out_len n_members bad_member err_off eof_marker")
+BgzfRanges = collections.namedtuple("BgzfRanges", "rc out_off range_status n_members n_decoded bad_member err_off")
 
 
 def bgzf_bound(n, block_bytes=0):
@@ -497,6 +498,59 @@ class FlateEngine:
         if rc not in (0, E_OUT_TOO_SMALL, E_CORRUPT, E_UNEXPECTED_EOF):
             self._check(rc)
         return out, BgzfRead(rc, int(ol.value), int(nm.value), int(bad.value), int(eo.value), int(eof.value))
+
+    def bgzf_read_ranges(self, data, begin, end, virtual=False, out=None, out_cap=None):
+        """Random access into a BGZF file (flate_hip_bgzf_read_ranges): the bytes of the ranges [begin[r], end[r]) --
+        positions in the file's uncompressed bytes, or (virtual=True) BGZF virtual offsets coffset << 16 | uoffset as
+        BAM, tabix and CSI indexes store them -- back to back in out.  Only the members the ranges touch are decoded
+        and verified, each once; the chain is validated whole.  data: numpy uint8 / bytes, or a torch uint8 CUDA tensor
+        (the bytes then stay on the device).  Returns (out, BgzfRanges(rc, out_off, range_status, n_members, n_decoded,
+        bad_member, err_off)): range r is out[out_off[r]:out_off[r + 1]].  rc 0; -1: some range had an invalid virtual
+        offset (range_status[r] == -1, zero bytes; the others are delivered); -4 with bad_member == n_members: a
+        malformed chain; -2 with out_off[-1] > capacity: out too small, nothing decoded; else the first failing touched
+        member's status with its index and file offset.  out=None: sized by the size query first.  begin[r] > end[r]
+        and other refusals raise FlateError."""
+        data, in_ptr, n, device = self._bgzf_in(data)
+        begin = np.ascontiguousarray(begin, dtype=np.uint64)
+        end = np.ascontiguousarray(end, dtype=np.uint64)
+        if begin.ndim != 1 or begin.shape != end.shape:
+            raise FlateError(E_INVALID, "bgzf_read_ranges: begin and end must be one-dimensional and of one length")
+        nr = begin.size
+        out_off = np.zeros(nr + 1, dtype=np.uint64)
+        status = np.zeros(max(nr, 1), dtype=np.int32)
+        nm, nd, bad, eo = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0), C.c_int64(-1)
+        flags = DEVICE_PTRS if device else 0
+
+        def call(out_ptr, cap):
+            rc = self._L.flate_hip_bgzf_read_ranges(self._ctx, in_ptr, n, 1 if virtual else 0, begin.ctypes.data,
+                                                    end.ctypes.data, nr, out_ptr, cap, out_off.ctypes.data,
+                                                    status.ctypes.data, C.byref(nm), C.byref(nd), C.byref(bad),
+                                                    C.byref(eo), flags)
+            if rc not in (0, E_OUT_TOO_SMALL, E_CORRUPT, E_UNEXPECTED_EOF) and \
+                    not (rc == E_INVALID and nr and (status[:nr] == E_INVALID).any()):
+                self._check(rc)
+            return rc
+
+        def result(rc):
+            return BgzfRanges(rc, out_off, status[:nr], int(nm.value), int(nd.value), int(bad.value), int(eo.value))
+
+        if out is None:
+            rc = call(None, 0)  # the size query: nothing is decoded
+            need = int(out_off[nr])
+            if rc != E_OUT_TOO_SMALL:  # nothing to deliver, or a malformed chain
+                need = 0
+            if device:
+                import torch
+                out = torch.empty(max(need, 16), dtype=torch.uint8, device=data.device)
+            else:
+                out = np.zeros(max(need, 16), dtype=np.uint8)
+            if rc != E_OUT_TOO_SMALL:
+                return out, result(rc)
+        else:
+            _check_out(out, data, 0, "bgzf_read_ranges")
+        room = out.numel() if device else out.size
+        cap = room if out_cap is None else min(int(out_cap), room)
+        return out, result(call(out.data_ptr() if device else out.ctypes.data, cap))
 
     def inflate_batch(self, data, in_off, out_sizes, out=None, check=True, zdicts=None, dict_of=None):
         """Decompress independent DEFLATE streams (&Reader::new + read to EOF each).

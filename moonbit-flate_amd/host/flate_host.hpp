@@ -901,4 +901,57 @@ inline Err decompress_bgzf(Engine &e, const std::vector<uint8_t> &file, std::vec
   return make_error(e, rc);
 }
 
+// One range of decompress_bgzf_ranges: positions in the file's uncompressed bytes, or -- virtual_offsets -- BGZF
+// virtual offsets (coffset << 16 | uoffset, as BAM, tabix and CSI indexes store them).
+struct BgzfRange {
+  uint64_t begin = 0, end = 0;
+};
+// What decompress_bgzf_ranges found beside the bytes.
+struct BgzfRangesInfo {
+  std::vector<uint64_t> out_off;      // n_ranges + 1: range r is out[out_off[r], out_off[r + 1])
+  std::vector<int32_t> range_status;  // per range: 0, FLATE_HIP_E_INVALID (an invalid virtual offset: zero bytes), or
+                                      // the status of the first failing member it touches
+  uint32_t n_members = 0;
+  uint32_t n_decoded = 0;             // the members the ranges touch: each decoded and verified once
+  uint32_t bad_member = 0xffffffffu;  // the first failing member, or (a malformed chain) the count of good ones
+  int64_t err_off = -1;
+  int status = 0;                     // the FLATE_HIP_E_* code behind the error (0 = none)
+};
+
+// decompress_bgzf_ranges: random access into a BGZF file (flate_hip_bgzf_read_ranges) -- the bytes of `ranges` back to
+// back in `out`; only the members they touch are decoded and verified, the chain is validated whole.  The size comes
+// from the call's size query.  Errors: as decompress_bgzf; an invalid virtual offset is make_error(FLATE_HIP_E_INVALID)
+// with every other range delivered (info->range_status says which).
+inline Err decompress_bgzf_ranges(Engine &e, const std::vector<uint8_t> &file, const std::vector<BgzfRange> &ranges,
+                                  std::vector<uint8_t> &out, BgzfRangesInfo *info = nullptr, bool virtual_offsets = false) {
+  if (!e.ok()) return make_error(e, e.status());
+  BgzfRangesInfo I;
+  const uint32_t nr = (uint32_t)ranges.size();
+  std::vector<uint64_t> begin(nr), end(nr);
+  for (uint32_t r = 0; r < nr; ++r) begin[r] = ranges[r].begin, end[r] = ranges[r].end;
+  I.out_off.assign((size_t)nr + 1, 0);
+  I.range_status.assign(nr, 0);
+  const uint32_t kind = virtual_offsets ? FLATE_HIP_BGZF_POS_VIRTUAL : FLATE_HIP_BGZF_POS_BYTES;
+  out.clear();
+  auto call = [&](uint8_t *buf, uint64_t cap) {
+    return flate_hip_bgzf_read_ranges(e.ctx(), file.data(), file.size(), kind, begin.data(), end.data(), nr, buf, cap,
+                                      I.out_off.data(), I.range_status.data(), &I.n_members, &I.n_decoded, &I.bad_member,
+                                      &I.err_off, 0);
+  };
+  int rc = call(nullptr, 0);  // the size query
+  if (rc == FLATE_HIP_E_OUT_TOO_SMALL) {
+    const uint64_t need = I.out_off[nr];
+    std::vector<uint8_t> buf(need + 8);
+    rc = call(buf.data(), need);
+    if (rc == 0 || rc == FLATE_HIP_E_INVALID || rc == FLATE_HIP_E_CORRUPT || rc == FLATE_HIP_E_UNEXPECTED_EOF)
+      out.assign(buf.begin(), buf.begin() + std::min<uint64_t>(I.out_off[nr], need));
+  }
+  I.status = rc;
+  if (info) *info = I;
+  if (rc == 0) return std::nullopt;
+  if (rc == FLATE_HIP_E_CORRUPT) return corrupt_input_error(I.err_off);
+  if (rc == FLATE_HIP_E_UNEXPECTED_EOF) return err_unexpected_eof();
+  return make_error(e, rc);
+}
+
 }  // namespace flate_host
