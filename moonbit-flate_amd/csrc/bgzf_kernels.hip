@@ -10,17 +10,20 @@
 //                       outside in[0, in_len) is touched), plus one chunk of halo for a header's first bytes; every
 //                       thread tests its 16 offsets for the 4-byte magic in LDS and runs the member rule on the rare
 //                       hit; the tile's count goes to tile_cnt
-//   bgzf_scan_kernel    exclusive scan of the counts (one workgroup); n_cand
-//   bgzf_fill_kernel    the same pass again, the hits written in file order: cand_off, cand_total
+//   bgzf_scan_kernel    exclusive scan of the counts (one workgroup: scan_range of block_scan.h); n_cand
+//   bgzf_fill_kernel    the same pass again, the hits written in file order (their places inside the tile:
+//                       block_scan_excl of block_scan.h, which also adds up bgzf_count_kernel's count): cand_off,
+//                       cand_total
 //   bgzf_link_kernel    jump[0][c] = the candidate at cand_off[c] + cand_total[c] (binary search), the terminal node
 //                       n_cand when that is in_len, else the dead node n_cand + 1; both absorb
 //   bgzf_round_kernel   round j of pointer doubling: path[2^j + r] = jump[path[r]] for r < 2^j, jump = jump o jump
 //   bgzf_finish_kernel  path rank r -> member_off[r], ISIZE; the thread whose successor is a sink writes the verdict
-//   bgzf_out_scan_kernel  exclusive scan of ISIZE -> out_off (one workgroup)
+//   bgzf_out_scan_kernel  exclusive scan of ISIZE -> out_off (one workgroup, scan_range again)
 // A successor lies strictly above its member, so nothing cycles; the host launches ceil(log2(cap + 2)) rounds.
 #include <hip/hip_runtime.h>
 
 #include "bgzf_rule.h"
+#include "block_scan.h"
 #include "flate_hip.h"
 #include "flate_kernels.h"
 
@@ -69,25 +72,6 @@ __device__ inline uint32_t test_offsets(const BgzfParams &P, const uint8_t *lds,
   return hits;
 }
 
-// exclusive scan of one value per thread over the 256 threads of the workgroup; *sum: the total
-__device__ inline uint32_t block_scan_256(uint32_t v, uint32_t *wtot, uint32_t *sum) {
-  const uint32_t lane = threadIdx.x & 63u, wid = threadIdx.x >> 6;
-  uint32_t x = v;
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint32_t o = __shfl_up(x, d);
-    if (lane >= (uint32_t)d) x += o;
-  }
-  if (lane == 63u) wtot[wid] = x;
-  __syncthreads();
-  uint32_t before = 0, all = 0;
-  for (uint32_t w = 0; w < 4u; ++w) {
-    if (w < wid) before += wtot[w];
-    all += wtot[w];
-  }
-  *sum = all;
-  return before + x - v;
-}
-
 __device__ inline uint32_t buf_align(const BgzfParams &P) { return (uint32_t)(reinterpret_cast<uintptr_t>(P.in) & 15u); }
 
 }  // namespace
@@ -101,47 +85,27 @@ __global__ __launch_bounds__(256) void bgzf_count_kernel(BgzfParams P) {
   uint32_t totals[6];  // (two hits are at least 3 bytes apart: at most 6 in 16 offsets)
   const uint32_t hits = test_offsets(P, lds, v0, A, totals);
   uint32_t sum = 0;
-  (void)block_scan_256((uint32_t)__popc(hits), wtot, &sum);
+  (void)block_scan_excl<4, uint32_t>((uint32_t)__popc(hits), wtot, &sum);
   if (threadIdx.x == 0) P.tile_cnt[blockIdx.x] = sum;
 }
 
 // One workgroup: tile_cnt becomes its exclusive scan (n_tiles + 1 entries); the head is initialised.
 __global__ __launch_bounds__(1024) void bgzf_scan_kernel(BgzfParams P) {
   __shared__ uint64_t wtot[16];
-  __shared__ uint64_t carry_s;
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  if (tid == 0) carry_s = 0ull;
-  __syncthreads();
-  for (uint32_t base = 0; base < P.n_tiles; base += 1024u) {
-    const uint32_t i = base + (uint32_t)tid;
-    const uint64_t v = i < P.n_tiles ? P.tile_cnt[i] : 0ull;
-    uint64_t x = v;
-    for (int d = 1; d < 64; d <<= 1) {
-      const uint64_t o = __shfl_up(x, d);
-      if (lane >= d) x += o;
-    }
-    if (lane == 63) wtot[wid] = x;
-    __syncthreads();
-    uint64_t woff = 0;
-    for (int w = 0; w < wid; ++w) woff += wtot[w];
-    const uint64_t carry = carry_s;
-    const uint64_t at = carry + woff + x - v;
-    // (above cap nothing downstream runs: the saturated value only has to stay above it)
-    if (i < P.n_tiles) P.tile_cnt[i] = at > 0xffffffffull ? 0xffffffffu : (uint32_t)at;
-    __syncthreads();
-    if (tid == 1023) carry_s = carry + woff + x;
-    __syncthreads();
-  }
-  if (tid == 0) {
-    const uint64_t n = carry_s;
-    P.tile_cnt[P.n_tiles] = n > 0xffffffffull ? 0xffffffffu : (uint32_t)n;
+  // (above cap nothing downstream runs: the saturated value only has to stay above it)
+  auto sat = [](uint64_t x) { return x > 0xffffffffull ? 0xffffffffu : (uint32_t)x; };
+  const uint64_t n = scan_range<16, uint64_t>(
+      P.n_tiles, wtot, [&](uint32_t i) { return (uint64_t)P.tile_cnt[i]; },
+      [&](uint32_t i, uint64_t at, uint64_t) { P.tile_cnt[i] = sat(at); });
+  if (threadIdx.x == 0) {
+    P.tile_cnt[P.n_tiles] = sat(n);
     BgzfHead h;
     h.out_bytes = 0;
     h.err_off = 0;
     h.n_members = 0;
     h.rc = FLATE_HIP_E_CORRUPT;  // (until bgzf_finish_kernel has found the chain's end)
     h.eof_marker = 0;
-    h.n_cand = n > 0xffffffffull ? 0xffffffffu : (uint32_t)n;
+    h.n_cand = sat(n);
     *P.head = h;
   }
 }
@@ -158,7 +122,7 @@ __global__ __launch_bounds__(256) void bgzf_fill_kernel(BgzfParams P) {
   uint32_t totals[6];
   const uint32_t hits = test_offsets(P, lds, v0, A, totals);
   uint32_t sum = 0;
-  uint32_t at = first + block_scan_256((uint32_t)__popc(hits), wtot, &sum);
+  uint32_t at = first + block_scan_excl<4, uint32_t>((uint32_t)__popc(hits), wtot, &sum);
   uint32_t k = 0;
   for (uint32_t b = 0; b < 16u; ++b) {
     if (!((hits >> b) & 1u)) continue;
@@ -244,33 +208,14 @@ __global__ __launch_bounds__(256) void bgzf_finish_kernel(BgzfParams P) {
 // One workgroup, behind bgzf_finish_kernel: out_off = the exclusive scan of the members' ISIZE.
 __global__ __launch_bounds__(1024) void bgzf_out_scan_kernel(BgzfParams P) {
   __shared__ uint64_t wtot[16];
-  __shared__ uint64_t carry_s;
-  if (P.head->n_cand > P.cap || P.head->rc != 0) return;
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  if (P.head->n_cand > P.cap || P.head->rc != 0) return;  // (uniform)
   const uint32_t hi = P.head->n_members;
-  if (tid == 0) carry_s = 0ull;
-  __syncthreads();
-  for (uint32_t base = 0; base < hi; base += 1024u) {
-    const uint32_t i = base + (uint32_t)tid;
-    const uint64_t v = i < hi ? P.isize[i] : 0ull;
-    uint64_t x = v;
-    for (int d = 1; d < 64; d <<= 1) {
-      const uint64_t o = __shfl_up(x, d);
-      if (lane >= d) x += o;
-    }
-    if (lane == 63) wtot[wid] = x;
-    __syncthreads();
-    uint64_t woff = 0;
-    for (int w = 0; w < wid; ++w) woff += wtot[w];
-    const uint64_t carry = carry_s;
-    if (i < hi) P.out_off[i] = carry + woff + x - v;
-    __syncthreads();
-    if (tid == 1023) carry_s = carry + woff + x;
-    __syncthreads();
-  }
-  if (tid == 0) {
-    P.out_off[hi] = carry_s;
-    P.head->out_bytes = carry_s;
+  const uint64_t total = scan_range<16, uint64_t>(
+      hi, wtot, [&](uint32_t i) { return (uint64_t)P.isize[i]; },
+      [&](uint32_t i, uint64_t before, uint64_t) { P.out_off[i] = before; });
+  if (threadIdx.x == 0) {
+    P.out_off[hi] = total;
+    P.head->out_bytes = total;
   }
 }
 

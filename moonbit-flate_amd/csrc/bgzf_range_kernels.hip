@@ -9,7 +9,9 @@
 //   bgzf_range_select_kernel  one workgroup over the members: the scan of the differences says whether any range
 //                             covers member k; masked with ISIZE > 0, one scan of (1, ISIZE) gives the selected
 //                             members their rank and their place in the dense scratch; compacted in file order
-//   bgzf_range_layout_kernel  one workgroup over the ranges: the scan of their lengths (their places in `out`); every
+//                             (three dependent block_scan_excl of block_scan.h per chunk, the carries in registers)
+//   bgzf_range_layout_kernel  one workgroup over the ranges: the scan of their lengths (their places in `out`;
+//                             scan_range of block_scan.h); every
 //                             member with bytes inside a range is selected, so the range's bytes are ONE run of the
 //                             scratch, starting at scratch_at[first] + (b - out_off[first])
 //   bgzf_gather_kernel        the runs into `out`.  No LDS: 16-byte stores on the destination's 16-byte grid, the
@@ -22,36 +24,11 @@
 #include <hip/hip_runtime.h>
 
 #include "bgzf_range_rule.h"
+#include "block_scan.h"
 #include "flate_hip.h"
 #include "flate_kernels.h"
 
 namespace flate {
-
-namespace {
-
-// exclusive scan of one value per thread over the 1024 threads of the workgroup; *sum: the total.  wtot: 16 entries
-// of LDS, free for the next call when this one returns.
-template <typename T>
-__device__ inline T block_scan_1024(T v, T *wtot, T *sum) {
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  T x = v;
-  for (int d = 1; d < 64; d <<= 1) {
-    const T o = __shfl_up(x, d);
-    if (lane >= d) x += o;
-  }
-  if (lane == 63) wtot[wid] = x;
-  __syncthreads();
-  T before = 0, all = 0;
-  for (int w = 0; w < 16; ++w) {
-    if (w < wid) before += wtot[w];
-    all += wtot[w];
-  }
-  __syncthreads();
-  *sum = all;
-  return before + x - v;
-}
-
-}  // namespace
 
 __global__ __launch_bounds__(256) void bgzf_range_locate_kernel(BgzfRangeParams P) {
   const uint32_t r = blockIdx.x * 256u + threadIdx.x;
@@ -70,22 +47,17 @@ __global__ __launch_bounds__(256) void bgzf_range_locate_kernel(BgzfRangeParams 
 
 __global__ __launch_bounds__(1024) void bgzf_range_select_kernel(BgzfRangeParams P) {
   __shared__ int64_t wtot[16];
-  __shared__ int64_t cover_s;
-  __shared__ uint64_t cnt_s, bytes_s;
-  const uint32_t tid = threadIdx.x;
-  if (tid == 0) cover_s = 0, cnt_s = 0ull, bytes_s = 0ull;
-  __syncthreads();
+  int64_t cover_c = 0, cnt_c = 0, bytes_c = 0;  // the three sums over the chunks in front
   for (uint32_t base = 0; base < P.n_members; base += 1024u) {
-    const uint32_t k = base + tid;
+    const uint32_t k = base + threadIdx.x;
     const bool in = k < P.n_members;
     const int64_t d = in ? (int64_t)P.diff[k] : 0;
-    int64_t dsum = 0;
-    const int64_t cover = cover_s + block_scan_1024<int64_t>(d, wtot, &dsum) + d;  // ranges that cover member k
+    int64_t dsum, csum, bsum;
+    const int64_t cover = cover_c + block_scan_excl<16, int64_t>(d, wtot, &dsum) + d;  // ranges that cover member k
     const uint32_t isize = in ? P.isize[k] : 0u;
     const bool sel = in && cover > 0 && isize > 0u;
-    int64_t csum = 0, bsum = 0;
-    const uint64_t rank = cnt_s + (uint64_t)block_scan_1024<int64_t>(sel ? 1 : 0, wtot, &csum);
-    const uint64_t at = bytes_s + (uint64_t)block_scan_1024<int64_t>(sel ? (int64_t)isize : 0, wtot, &bsum);
+    const uint64_t rank = (uint64_t)(cnt_c + block_scan_excl<16, int64_t>(sel ? 1 : 0, wtot, &csum));
+    const uint64_t at = (uint64_t)(bytes_c + block_scan_excl<16, int64_t>(sel ? (int64_t)isize : 0, wtot, &bsum));
     if (in) {
       P.rank[k] = (uint32_t)rank;
       P.scratch_at[k] = at;
@@ -99,50 +71,39 @@ __global__ __launch_bounds__(1024) void bgzf_range_select_kernel(BgzfRangeParams
       s.isize = isize;
       P.sel[rank] = s;
     }
-    __syncthreads();  // (everyone has read the three carries)
-    if (tid == 0) cover_s += dsum, cnt_s += (uint64_t)csum, bytes_s += (uint64_t)bsum;
-    __syncthreads();
+    cover_c += dsum, cnt_c += csum, bytes_c += bsum;
   }
-  if (tid == 0) {
-    P.head->n_sel = (uint32_t)cnt_s;
-    P.head->scratch_total = bytes_s;
+  if (threadIdx.x == 0) {
+    P.head->n_sel = (uint32_t)cnt_c;
+    P.head->scratch_total = (uint64_t)bytes_c;
   }
 }
 
 __global__ __launch_bounds__(1024) void bgzf_range_layout_kernel(BgzfRangeParams P) {
   __shared__ int64_t wtot[16];
-  __shared__ uint64_t carry_s;
   __shared__ uint32_t invalid_s;
-  const uint32_t tid = threadIdx.x;
-  if (tid == 0) carry_s = 0ull, invalid_s = 0u;
+  if (threadIdx.x == 0) invalid_s = 0u;
   __syncthreads();
-  for (uint32_t base = 0; base < P.n_ranges; base += 1024u) {
-    const uint32_t r = base + tid;
-    const bool in = r < P.n_ranges;
-    const uint64_t len = in ? P.r_len[r] : 0ull;
-    int64_t sum = 0;
-    const uint64_t at = carry_s + (uint64_t)block_scan_1024<int64_t>((int64_t)len, wtot, &sum);
-    if (in) {
-      const uint32_t first = P.r_first[r], last = P.r_last[r];
-      P.r_out_off[r] = at;
-      if (first != kBgzfNoMember) {
-        P.r_src[r] = P.scratch_at[first] + (P.r_b[r] - P.out_off_m[first]);
-        P.r_rank_lo[r] = P.rank[first];
-        P.r_rank_hi[r] = P.rank[last] + 1u;
-      } else {
-        P.r_src[r] = 0ull;
-        P.r_rank_lo[r] = 0u;
-        P.r_rank_hi[r] = 0u;
-      }
-      if (P.r_status[r] != 0) atomicOr(&invalid_s, 1u);
-    }
-    __syncthreads();
-    if (tid == 0) carry_s += (uint64_t)sum;
-    __syncthreads();
-  }
-  if (tid == 0) {
-    P.r_out_off[P.n_ranges] = carry_s;
-    P.head->out_total = carry_s;
+  const uint64_t total = (uint64_t)scan_range<16, int64_t>(
+      P.n_ranges, wtot, [&](uint32_t r) { return (int64_t)P.r_len[r]; },
+      [&](uint32_t r, int64_t at, int64_t) {
+        const uint32_t first = P.r_first[r], last = P.r_last[r];
+        P.r_out_off[r] = (uint64_t)at;
+        if (first != kBgzfNoMember) {
+          P.r_src[r] = P.scratch_at[first] + (P.r_b[r] - P.out_off_m[first]);
+          P.r_rank_lo[r] = P.rank[first];
+          P.r_rank_hi[r] = P.rank[last] + 1u;
+        } else {
+          P.r_src[r] = 0ull;
+          P.r_rank_lo[r] = 0u;
+          P.r_rank_hi[r] = 0u;
+        }
+        if (P.r_status[r] != 0) atomicOr(&invalid_s, 1u);
+      });
+  __syncthreads();  // (the last chunk's flags)
+  if (threadIdx.x == 0) {
+    P.r_out_off[P.n_ranges] = total;
+    P.head->out_total = total;
     P.head->any_invalid = invalid_s;
   }
 }

@@ -28,6 +28,7 @@
 
 #include <string>
 
+#include "block_scan.h"
 #include "checksum_clip.h"
 #include "flate_hip.h"
 #include "flate_kernels.h"
@@ -290,8 +291,8 @@ __global__ __launch_bounds__(256) void checksum_clip_kernel(ClipParams P) {
 // The sum of a CONCATENATION (flate_hip_inflate_spliced_framed): the n pieces of a spliced stream each left a finished
 // sum (checksum_fold_kernel) of the L_i = min(out_len[i], slot) bytes they produced; the member's checksum is that of
 // the L_i-byte runs one after another.  Piece i's term needs the bytes BEHIND it, n_bytes - (L_0 + .. + L_i): one
-// workgroup first adds up n_bytes, then walks the pieces in chunks of 1024 with a running prefix, as
-// frame_scan_kernel walks sizes; every thread keeps the XOR (CRC-32) or the two sums mod 65521 (Adler-32) of its
+// workgroup first adds up n_bytes, then walks the pieces with a running prefix (scan_range of block_scan.h, as
+// frame_scan_kernel walks sizes); every thread keeps the XOR (CRC-32) or the two sums mod 65521 (Adler-32) of its
 // terms, folded over the workgroup at the end.  The arithmetic is checksum_clip.h's.  2^20 pieces: 1024 chunks of at
 // most ~40 multmodp per thread -- nothing against the decode in front of it.
 struct JoinParams {
@@ -307,7 +308,6 @@ struct JoinParams {
 __global__ __launch_bounds__(1024) void checksum_join_kernel(JoinParams P) {
   __shared__ uint64_t wtot[16], wd1[16], wd2[16];
   __shared__ uint32_t wcrc[16];
-  __shared__ uint64_t carry_s;
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const uint32_t hi = P.n_pieces;
   auto len_of = [&](uint32_t i) { return clip_to_slot(P.produced[i], P.slot_off[i + 1] - P.slot_off[i]); };
@@ -316,7 +316,6 @@ __global__ __launch_bounds__(1024) void checksum_join_kernel(JoinParams P) {
   for (uint32_t i = (uint32_t)tid; i < hi; i += 1024u) mine += len_of(i);
   for (int d = 32; d >= 1; d >>= 1) mine += (uint64_t)__shfl_xor((long long)mine, d);
   if (lane == 0) wtot[wid] = mine;
-  if (tid == 0) carry_s = 0ull;
   __syncthreads();
   uint64_t n_bytes = 0;
   for (int w = 0; w < 16; ++w) n_bytes += wtot[w];
@@ -324,33 +323,17 @@ __global__ __launch_bounds__(1024) void checksum_join_kernel(JoinParams P) {
   // the terms
   uint32_t c = 0;
   uint64_t d1 = 0, d2 = 0;
-  for (uint32_t base = 0; base < hi; base += 1024u) {
-    const uint32_t i = base + (uint32_t)tid;
-    const uint64_t v = i < hi ? len_of(i) : 0ull;
-    uint64_t x = v;  // inclusive prefix inside my wavefront
-    for (int d = 1; d < 64; d <<= 1) {
-      const uint64_t o = (uint64_t)__shfl_up((long long)x, d);
-      if (lane >= d) x += o;
+  (void)scan_range<16, uint64_t>(hi, wtot, len_of, [&](uint32_t i, uint64_t before, uint64_t v) {
+    const uint64_t upto = before + v;  // L_0 + .. + L_i: never more than n_bytes
+    const uint64_t behind = n_bytes - upto;
+    if (P.want_crc) {
+      c ^= crc_concat_term(P.x2n, P.sums[i], v, behind);
+    } else {
+      const AdlerTerm t = adler_concat_term(P.sums[i], v, behind);
+      d1 = (d1 + t.d1) % kAdlerMod;
+      d2 = (d2 + t.d2) % kAdlerMod;
     }
-    if (lane == 63) wtot[wid] = x;
-    __syncthreads();
-    uint64_t woff = 0;
-    for (int w = 0; w < wid; ++w) woff += wtot[w];
-    const uint64_t upto = carry_s + woff + x;  // L_0 + .. + L_i: never more than n_bytes
-    if (i < hi) {
-      const uint64_t behind = n_bytes - upto;
-      if (P.want_crc) {
-        c ^= crc_concat_term(P.x2n, P.sums[i], v, behind);
-      } else {
-        const AdlerTerm t = adler_concat_term(P.sums[i], v, behind);
-        d1 = (d1 + t.d1) % kAdlerMod;
-        d2 = (d2 + t.d2) % kAdlerMod;
-      }
-    }
-    __syncthreads();
-    if (tid == 1023) carry_s = upto;
-    __syncthreads();
-  }
+  });
   for (int d = 32; d >= 1; d >>= 1) {
     c ^= (uint32_t)__shfl_xor((int)c, d);
     d1 += (uint64_t)__shfl_xor((long long)d1, d);

@@ -4,9 +4,9 @@
 // Member i = header | raw DEFLATE stream i | trailer.  The entropy stage knows the exact size of every raw stream
 // before a byte of it is written (huff_code_kernel), so the members' places follow from a scan like the raw
 // form's, and the pack kernels write every stream straight into its member:
-//   frame_scan_kernel   scan_sizes_kernel with header + trailer added to every size: member offsets (returned to
-//                       the caller) and payload offsets (= member offset + header length: what the pack kernels
-//                       read as HuffParams::out_off);
+//   frame_scan_kernel   scan_sizes_kernel with header + trailer added to every size (scan_range of block_scan.h):
+//                       member offsets (returned to the caller) and payload offsets (= member offset + header
+//                       length: what the pack kernels read as HuffParams::out_off);
 //   frame_write_kernel  the header and trailer bytes of every member, one thread each, byte by byte -- a member
 //                       starts at any alignment, and an empty stream's member (11 or 23 bytes) shares its dwords
 //                       with its neighbours.  It runs AFTER the pack kernel: in the spliced form that kernel works
@@ -23,6 +23,7 @@
 #include <hip/hip_runtime.h>
 
 #include "bgzf_rule.h"
+#include "block_scan.h"
 #include "flate_hip.h"
 #include "flate_kernels.h"
 
@@ -45,45 +46,29 @@ __device__ inline void put_le32(uint8_t *p, uint32_t v) {
 
 }  // namespace
 
-// Exclusive scan of the members' sizes (one workgroup, as scan_sizes_kernel; the same status word).
+// Exclusive scan of the members' sizes (one workgroup, block_scan.h; scan_sizes_kernel's status word).
 __global__ __launch_bounds__(1024) void frame_scan_kernel(FrameParams P) {
   __shared__ uint64_t wtot[16];
-  __shared__ uint64_t carry_s;
   __shared__ uint32_t big_s;  // kWrapBgzf: the first member that BSIZE cannot express
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  const uint32_t hi = P.n_streams;
   const uint32_t tl = trailer_len(P);
-  if (tid == 0) carry_s = 0ull, big_s = 0xffffffffu;
+  if (threadIdx.x == 0) big_s = 0xffffffffu;
   __syncthreads();
-  for (uint32_t base = 0; base < hi; base += 1024) {
-    const uint32_t i = base + (uint32_t)tid;
-    const uint32_t hl = i < hi ? header_len(P, i) : 0u;
-    const uint64_t v = i < hi ? P.out_len[i] + hl + tl : 0ull;
-    if (P.wrap == kWrapBgzf && v > (uint64_t)kBgzfMemberMax) atomicMin(&big_s, i);
-    uint64_t x = v;
-    for (int d = 1; d < 64; d <<= 1) {
-      const uint64_t o = __shfl_up(x, d);
-      if (lane >= d) x += o;
-    }
-    if (lane == 63) wtot[wid] = x;
-    __syncthreads();
-    uint64_t woff = 0;
-    for (int w = 0; w < wid; ++w) woff += wtot[w];
-    const uint64_t carry = carry_s;
-    if (i < hi) {
-      const uint64_t at = carry + woff + x - v;
-      P.member_off[i] = at;
-      P.payload_off[i] = at + hl;
-    }
-    __syncthreads();
-    if (tid == 1023) carry_s = carry + woff + x;
-    __syncthreads();
-  }
-  if (tid == 0) {
-    P.member_off[P.n_streams] = carry_s;
-    P.payload_off[P.n_streams] = carry_s;
+  const uint64_t sum = scan_range<16, uint64_t>(
+      P.n_streams, wtot,
+      [&](uint32_t i) {
+        const uint64_t v = P.out_len[i] + header_len(P, i) + tl;
+        if (P.wrap == kWrapBgzf && v > (uint64_t)kBgzfMemberMax) atomicMin(&big_s, i);
+        return v;
+      },
+      [&](uint32_t i, uint64_t at, uint64_t) {
+        P.member_off[i] = at;
+        P.payload_off[i] = at + header_len(P, i);
+      });
+  if (threadIdx.x == 0) {  // (behind the scan's barriers: big_s is final)
+    P.member_off[P.n_streams] = sum;
+    P.payload_off[P.n_streams] = sum;
     // (a BGZF file ends with the EOF marker behind its last member)
-    const uint64_t total = carry_s + (P.wrap == kWrapBgzf ? (uint64_t)kBgzfEofLen : 0ull);
+    const uint64_t total = sum + (P.wrap == kWrapBgzf ? (uint64_t)kBgzfEofLen : 0ull);
     if (total > P.out_cap) *P.status = FLATE_HIP_E_OUT_TOO_SMALL;
     if (big_s != 0xffffffffu) {
       P.status[1] = (int)big_s;
