@@ -45,6 +45,8 @@ typedef struct flate_hip_ctx flate_hip_ctx;
                                            rank holds more streams than the plan allows for; the
                                            plan has been raised on every rank: repeat this batch
                                            with flate_hip_gather_compressed                      */
+#define FLATE_HIP_E_UNSUPPORTED (-10)   /* ZIP: an entry that is encrypted, patched, or of a method other than 0
+                                           and 8 (that entry's status) */
 #define FLATE_HIP_E_INTERNAL (-8)       /* encoder self-check failed (the reference abort()s on its
                                            invariants, deflate.mbt:111, huffman-code.mbt:118,232):
                                            packed bits != the size computed before packing;
@@ -654,6 +656,84 @@ int flate_hip_bgzf_read_ranges(flate_hip_ctx *ctx, const uint8_t *in, uint64_t i
                                uint8_t *out, uint64_t out_cap, uint64_t *out_off, int32_t *range_status,
                                uint32_t *n_members, uint32_t *n_decoded, uint32_t *bad_member,
                                int64_t *err_off, uint32_t flags);
+
+/* -- ZIP archives ----------------------------------------------------------------
+ * The everyday container of a batch of independent DEFLATE streams (.zip, .npz, .jar, .whl, .docx; PKWARE APPNOTE
+ * 6.3), and the one whose own index, the central directory, makes writing and reading parallel.  The format rule is
+ * written once, csrc/zip_rule.h; the kernels are csrc/zip_kernels.hip.
+ *
+ * WRITING: entry i is in[in_off[i], in_off[i+1]), named names[name_off[i], name_off[i+1]) (UTF-8; names and name_off
+ * are HOST arrays always, like every offset table).  Its data is exactly the bytes the raw batch call produces for
+ * stream i under the same flags (an empty entry: 01 00 00 ff ff).  Local headers carry CRC-32 and both sizes (no data
+ * descriptors), flags 0x0800, method 8, time 0, date 0x0021; a central record carries a Zip64 extra exactly when its
+ * header offset >= 0xffffffff, and the Zip64 end record and locator appear exactly when n >= 65535 or the directory's
+ * offset or size >= 0xffffffff.  entry_off (host, n + 1, may be NULL) receives the local header offsets, [n] = where
+ * the directory starts.  Refused before any HIP call with FLATE_HIP_E_INVALID: a name of 0 or more than 65535 bytes,
+ * name_off not monotone, NULLs, flags other than FLATE_HIP_DEVICE_PTRS | FLATE_HIP_COMPAT_GO.  out_cap: the exact
+ * total is enough to the byte, one byte less is FLATE_HIP_E_OUT_TOO_SMALL (decided on the device by the scan); the
+ * bound below is always enough.  n == 0 gives the 22-byte empty archive.  Host pointers: one copy in, one copy out.
+ *   How: a scan over 30 + name + raw size places the members and gives the pack kernels their offsets; the CRC-32s
+ *   run on the input where it is; one thread per entry writes its local header and its central record behind the
+ *   pack kernel, one thread the end records -- all queued on the ctx's stream, the checksum and writer kernels
+ *   counted as FLATE_HIP_STAGE_CHECKSUM.
+ *
+ * READING.  Absolute offsets, one disk.  The end record is the HIGHEST p in [max(0, in_len - 65557), in_len - 22] with
+ * its signature and p + 22 + comment length == in_len; a Zip64 locator at p - 20 moves the values to the Zip64 end
+ * record.  The directory is exactly n records chained from its offset and ending exactly at offset + size.  Sizes and
+ * CRC-32 always come from the directory (data descriptors need no pass), data_off from the LOCAL header's lengths.
+ * The archive's verdict is FLATE_HIP_E_CORRUPT with err_off = in_len (no end record), the end record's offset (a
+ * refused end record, Zip64 record or directory range) or the offset at which a record was expected (a record that
+ * cannot be read, bytes left behind n records, the directory's end reached early); n_entries = the well-formed
+ * records in front of it.  An entry's status at index time: FLATE_HIP_E_UNSUPPORTED for flag bit 0, 5 or 6 or a
+ * method other than 0 and 8; FLATE_HIP_E_CORRUPT for a local header without its signature or not in front of the
+ * directory, data that runs into the directory, or a stored entry whose two sizes differ.
+ *   How: the end record by one thread per offset of the tail window and an atomic max; the directory as BGZF members
+ *   are found (every offset tested with 16-byte loads, hits compacted in file order, each linked to the candidate at
+ *   its own end by binary search, the chain ranked by pointer doubling); one thread per record reads the record and
+ *   its local header; a scan of the sizes.  No host pass over file bytes; nothing outside in[0, in_len) is read, at
+ *   any alignment of in.
+ * Out of scope: archives with prepended data, several disks, encryption, methods other than 0 and 8, comments on
+ * write; uploading only the selected entries from host memory; caching the index across calls. */
+typedef struct flate_hip_zip_entry {
+  uint64_t name_off;    /* the name's place in the archive (the directory's copy), name_len bytes */
+  uint64_t header_off;  /* the local header */
+  uint64_t data_off;    /* the entry's data (0 where the local header cannot be used) */
+  uint64_t comp_size, size;
+  uint32_t crc32;
+  uint16_t name_len, method, flags, reserved;
+  int32_t status;
+  uint32_t reserved2;
+} flate_hip_zip_entry; /* 64 bytes: 60 of fields and 4 of padding behind them */
+/* room that is always enough for the archive of these entries; 0 for offsets or names that would be refused */
+size_t flate_hip_zip_bound(const uint64_t *in_off, uint32_t n, const uint64_t *name_off);
+int flate_hip_zip_write(flate_hip_ctx *ctx, const uint8_t *in, const uint64_t *in_off, uint32_t n,
+                        const uint8_t *names, const uint64_t *name_off, uint8_t *out, uint64_t out_cap,
+                        uint64_t *out_len, uint64_t *entry_off, uint32_t flags);
+/* Discovery only.  entries / out_off: host arrays of index_cap / index_cap + 1 entries, both NULL for a count query;
+ * too small is FLATE_HIP_E_OUT_TOO_SMALL with the counts set.  out_off = the exclusive prefix sum of size over the
+ * entries with status 0 (the others get empty slots), *out_bytes its last entry.  More than 2^32 - 2 entries:
+ * FLATE_HIP_E_TOO_LARGE.  flags: FLATE_HIP_DEVICE_PTRS or 0. */
+int flate_hip_zip_index(flate_hip_ctx *ctx, const uint8_t *in, uint64_t in_len, uint64_t index_cap,
+                        flate_hip_zip_entry *entries, uint64_t *out_off, uint32_t *n_entries, uint64_t *out_bytes,
+                        int64_t *err_off, uint32_t flags);
+/* Index, one read-back, then decode and verify.  sel (host, n_sel entry numbers in any order, duplicates allowed) or
+ * NULL = every entry; n_cap = the capacity of out_off (n_cap + 1), out_len, status and err_off (host arrays).  The
+ * selected entries' bytes lie back to back in out in the order given; out_off (n_sel + 1) is written.  Method 8 runs
+ * through the batch decoders, method 0 through a copy kernel; the CRC-32 of what was produced is judged on the device.
+ * An entry's verdict, in order: its index status; the decoder's own status with err_off counted from data_off;
+ * FLATE_HIP_E_OUT_TOO_SMALL if it produces more than size; FLATE_HIP_E_CORRUPT with err_off = comp_size if it produced
+ * another length than size or another CRC-32.  An entry of 4 GiB or more (or of 2 GiB or more of compressed data) is
+ * FLATE_HIP_E_TOO_LARGE for that entry.  A failing entry does not stop the others and gets an empty slot or leaves
+ * its slot as far as it came.
+ * Returns: the archive's verdict (with *archive_err_off, nothing written); FLATE_HIP_E_INVALID for a sel entry >= n or
+ * n_sel > n_cap, before decoding (sel == NULL takes n_sel == 0, and more entries than n_cap are
+ * FLATE_HIP_E_OUT_TOO_SMALL with *n_entries set); an entry's err_off is -1 unless stated; FLATE_HIP_E_OUT_TOO_SMALL with out_off fully written and nothing decoded when the
+ * total exceeds out_cap (out == NULL and out_cap == 0 is the size query); else the first non-zero entry status in the
+ * order given.  With device pointers nothing outside out[0, out_off[n_sel]) is written. */
+int flate_hip_zip_read(flate_hip_ctx *ctx, const uint8_t *in, uint64_t in_len, const uint32_t *sel, uint32_t n_sel,
+                       uint32_t n_cap, uint8_t *out, uint64_t out_cap, uint64_t *out_off, uint64_t *out_len,
+                       int32_t *status, int64_t *err_off, uint32_t *n_entries, int64_t *archive_err_off,
+                       uint32_t flags);
 
 /* -- exchange step (multi-GPU) ---------------------------------------------------
  * SURVEY 8(e) / section 5; no counterpart in the reference (single-threaded, no communication

@@ -26,6 +26,7 @@ EXPORTS = [
     "flate_hip_inflate_batch_framed", "flate_hip_inflate_spliced_framed",
     "flate_hip_bgzf_bound", "flate_hip_bgzf_write", "flate_hip_bgzf_index", "flate_hip_bgzf_read",
     "flate_hip_bgzf_read_ranges",
+    "flate_hip_zip_bound", "flate_hip_zip_write", "flate_hip_zip_index", "flate_hip_zip_read",
 ]
 
 _lib = None
@@ -109,6 +110,17 @@ def load():
         L.flate_hip_bgzf_read_ranges.argtypes = [vp, vp, C.c_uint64, C.c_uint32, vp, vp, C.c_uint32, vp, C.c_uint64, vp, vp,
                                                  u32p, u32p, u32p, i64p, C.c_uint32]
         L.flate_hip_bgzf_read_ranges.restype = C.c_int
+    if os.environ.get("FLATE_HIP_LIB") is None or hasattr(L, "flate_hip_zip_write"):
+        u32p, i64p = C.POINTER(C.c_uint32), C.POINTER(C.c_int64)
+        L.flate_hip_zip_bound.argtypes = [vp, C.c_uint32, vp]
+        L.flate_hip_zip_bound.restype = C.c_size_t
+        L.flate_hip_zip_write.argtypes = [vp, vp, vp, C.c_uint32, vp, vp, vp, C.c_uint64, u64p, vp, C.c_uint32]
+        L.flate_hip_zip_write.restype = C.c_int
+        L.flate_hip_zip_index.argtypes = [vp, vp, C.c_uint64, C.c_uint64, vp, vp, u32p, u64p, i64p, C.c_uint32]
+        L.flate_hip_zip_index.restype = C.c_int
+        L.flate_hip_zip_read.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint32, C.c_uint32, vp, C.c_uint64, vp, vp, vp, vp,
+                                         u32p, i64p, C.c_uint32]
+        L.flate_hip_zip_read.restype = C.c_int
     L.flate_hip_inflate_spliced.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint32, vp, vp, vp, vp, vp, C.c_uint32]
     L.flate_hip_inflate_spliced.restype = C.c_int
     L.flate_hip_set_profiling.argtypes = [vp, C.c_int]

@@ -131,6 +131,52 @@ inline uint32_t bgzf_rounds(uint32_t cap) {
   return r;
 }
 
+// ---- ZIP archives (flate_hip_zip_write / _index / _read) ----
+
+// everything flate_hip_zip_write refuses before any HIP call
+inline int zip_write_args(const uint8_t *in, const uint64_t *in_off, uint32_t n, const uint8_t *names,
+                          const uint64_t *name_off, const uint8_t *out, const uint64_t *out_len, uint32_t flags) {
+  if (!in_off || !name_off || !out || !out_len || (n && (!in || !names))) return FLATE_HIP_E_INVALID;
+  if (flags & ~(FLATE_HIP_DEVICE_PTRS | FLATE_HIP_COMPAT_GO)) return FLATE_HIP_E_INVALID;
+  for (uint32_t i = 0; i < n; ++i) {
+    if (in_off[i + 1] < in_off[i] || name_off[i + 1] <= name_off[i]) return FLATE_HIP_E_INVALID;  // (a name of 0 bytes)
+    if (name_off[i + 1] - name_off[i] > 65535u) return FLATE_HIP_E_INVALID;
+  }
+  return FLATE_HIP_OK;
+}
+// room that is always enough for the archive: every entry at its raw bound (bound: flate_hip_deflate_bound) behind its
+// local header, every central record with its Zip64 extra, all three end records; 0 for arguments that are refused
+inline uint64_t zip_archive_bound(const uint64_t *in_off, uint32_t n, const uint64_t *name_off, size_t (*bound)(size_t)) {
+  if (!in_off || !name_off) return 0;
+  uint64_t total = 22u + 56u + 20u;
+  for (uint32_t i = 0; i < n; ++i) {
+    if (in_off[i + 1] < in_off[i] || name_off[i + 1] <= name_off[i] || name_off[i + 1] - name_off[i] > 65535u) return 0;
+    total += 30u + 46u + 12u + 2u * (name_off[i + 1] - name_off[i]) + (uint64_t)bound((size_t)(in_off[i + 1] - in_off[i]));
+  }
+  return total;
+}
+// entries and out_off come together or not at all (the count query)
+inline int zip_index_args(const uint8_t *in, uint64_t in_len, const void *entries, const uint64_t *out_off,
+                          const uint32_t *n_entries, const uint64_t *out_bytes, uint32_t flags) {
+  if (!n_entries || !out_bytes || (in_len && !in) || (!entries != !out_off)) return FLATE_HIP_E_INVALID;
+  return (flags & ~FLATE_HIP_DEVICE_PTRS) ? FLATE_HIP_E_INVALID : FLATE_HIP_OK;
+}
+inline int zip_read_args(const uint8_t *in, uint64_t in_len, const uint32_t *sel, uint32_t n_sel, uint32_t n_cap,
+                         const uint8_t *out, uint64_t out_cap, const uint64_t *out_off, const uint64_t *out_len,
+                         const int32_t *status, const int64_t *err_off, uint32_t flags) {
+  if ((in_len && !in) || (out_cap && !out) || !out_off) return FLATE_HIP_E_INVALID;
+  if (n_cap && (!out_len || !status || !err_off)) return FLATE_HIP_E_INVALID;
+  if (sel ? n_sel > n_cap : n_sel != 0) return FLATE_HIP_E_INVALID;  // (sel == NULL: every entry, n_sel is 0)
+  return (flags & ~FLATE_HIP_DEVICE_PTRS) ? FLATE_HIP_E_INVALID : FLATE_HIP_OK;
+}
+// how many candidates the directory's discovery arrays hold on the first attempt: the records the end record promises
+// and some decoys (names or extras that look like records); never more than fit the directory, 4 bytes apart
+inline uint32_t zip_first_cap(uint64_t n, uint64_t cd_size) {
+  const uint64_t fit = cd_size / 4u + 1u, want = n + 4096u;
+  const uint64_t c = want < fit ? want : fit;
+  return c > 0xfffffff0ull ? 0xfffffff0u : (uint32_t)c;
+}
+
 // what a decode call returns when it has run: FLATE_HIP_OK or the first non-zero status of a stream
 inline bool is_stream_status(int rc) {
   return rc == FLATE_HIP_OK || rc == FLATE_HIP_E_OUT_TOO_SMALL || rc == FLATE_HIP_E_CORRUPT || rc == FLATE_HIP_E_UNEXPECTED_EOF;

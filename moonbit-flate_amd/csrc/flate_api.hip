@@ -164,6 +164,7 @@ const char *flate_hip_strerror(int code) {
     case FLATE_HIP_E_UNEXPECTED_EOF: return "unexpected EOF";
     case FLATE_HIP_E_INTERNAL: return "internal error: encoder self-check failed";
     case FLATE_HIP_E_AGAIN: return "a shard outgrew the agreed plan (pad or stream count): repeat this batch with the blocking exchange";
+    case FLATE_HIP_E_UNSUPPORTED: return "ZIP: entry not supported (encrypted, patched, or a method other than stored and deflate)";
     default: return "unknown error";
   }
 }

@@ -326,8 +326,9 @@ int blk_sid_up(flate_hip_ctx *c, const StagePlan &pl) {
 // The kernels of the entropy stage over the streams of H, inside the stage's events: histograms and codes, the scan
 // that places the streams (a raw batch, a batch of members -- F, null for raw output -- or one spliced stream), pack.
 // place_cap: the room the scan may give out.
+// ZW (flate_hip_zip_write): the members of a ZIP archive, placed by zip_scan_kernel.
 void launch_entropy(flate_hip_ctx *c, const EncodeRoute &rt, const HuffParams &H, uint32_t n_blocks, const FrameParams *F,
-                    uint64_t place_cap) {
+                    uint64_t place_cap, const ZipWriteParams *ZW = nullptr) {
   const uint32_t n = H.n_streams;
   StageTimer t(c, FLATE_HIP_STAGE_HUFF_PACK);
   if (rt.per_block)
@@ -347,6 +348,8 @@ void launch_entropy(flate_hip_ctx *c, const EncodeRoute &rt, const HuffParams &H
     hipLaunchKernelGGL(splice_zero_kernel, dim3(n / 256 + 1), dim3(256), 0, c->stream, S, H.out);
   } else if (F) {
     hipLaunchKernelGGL(frame_scan_kernel, dim3(1), dim3(1024), 0, c->stream, *F);
+  } else if (ZW) {
+    hipLaunchKernelGGL(zip_scan_kernel, dim3(1), dim3(1024), 0, c->stream, *ZW);
   } else {
     CompactParams C{};
     C.out_len = (const uint64_t *)c->d_out_len.p;
@@ -425,12 +428,65 @@ int frame_after(flate_hip_ctx *c, const FrameReq &FR, const FrameParams &F, cons
   return FLATE_HIP_OK;
 }
 
+// ---- the container of flate_hip_zip_write (zip_kernels.hip) ----
+// The members of a ZIP archive: zip_scan_kernel places them (30 + name in front of every raw stream), the pack kernels
+// write each raw stream into its member, then the CRC-32s run on the input where it is and zip_write_kernel writes the
+// local headers, the central directory and the end records.
+struct ZipReq {
+  const uint8_t *names;      // HOST
+  const uint64_t *name_off;  // HOST, n + 1
+};
+
+// zip_after: the entries' checksums; down: the archive's size
+CtlBytes zip_ctl(const uint64_t *sum_off, uint32_t sum_n) { return {checksum_ctl_up_bytes(sum_off, sum_n), 64}; }
+
+// In front of the match finder: the container's arrays, the names on the device.
+int zip_before(flate_hip_ctx *c, const ZipReq &ZR, uint32_t n) {
+  int rc;
+  const uint64_t name_bytes = ZR.name_off[n];
+  if ((rc = ensure(c, c->d_frame_off, ((size_t)n + 1) * 8))) return rc;
+  if ((rc = ensure(c, c->d_frame_sums, (size_t)n * 4 + 8))) return rc;
+  if ((rc = ensure(c, c->d_zip_names, name_bytes + 16))) return rc;
+  if ((rc = ensure(c, c->d_zip_name_off, ((size_t)n + 1) * 8))) return rc;
+  if ((rc = ensure(c, c->d_zip_whead, sizeof(ZipWriteHead)))) return rc;
+  HIP_TRY(c, hipMemcpyAsync(c->d_zip_names.p, ZR.names, name_bytes, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(c->d_zip_name_off.p, ZR.name_off, ((size_t)n + 1) * 8, hipMemcpyHostToDevice, c->stream));
+  return FLATE_HIP_OK;
+}
+
+ZipWriteParams zip_params(const flate_hip_ctx *c, const EncCall &A, uint8_t *d_out) {
+  ZipWriteParams Z{};
+  Z.out_len = (const uint64_t *)c->d_out_len.p;
+  Z.in_off = (const uint64_t *)c->d_in_off.p;
+  Z.name_off = (const uint64_t *)c->d_zip_name_off.p;
+  Z.names = (const uint8_t *)c->d_zip_names.p;
+  Z.entry_off = (uint64_t *)c->d_frame_off.p;
+  Z.payload_off = (uint64_t *)c->d_out_off.p;
+  Z.sums = (const uint32_t *)c->d_frame_sums.p;
+  Z.out = d_out;
+  Z.out_cap = A.out_cap;
+  Z.n = A.n;
+  Z.status = (int *)c->d_status.p;
+  Z.head = (ZipWriteHead *)c->d_zip_whead.p;
+  return Z;
+}
+
+// Behind the pack kernel: the CRC-32s, then headers, directory and end records.
+int zip_after(flate_hip_ctx *c, const ZipWriteParams &ZW, const uint8_t *d_in, const uint64_t *sum_off, uint32_t sum_n) {
+  StageTimer t(c, FLATE_HIP_STAGE_CHECKSUM);
+  const int rc = checksum_device(c, d_in, sum_off, sum_n, FLATE_HIP_CHECKSUM_CRC32, (uint32_t *)c->d_frame_sums.p, -1);
+  if (rc) return rc;
+  hipLaunchKernelGGL(zip_write_kernel, dim3(sum_n / 256 + 1), dim3(256), 0, c->stream, ZW);
+  return FLATE_HIP_OK;
+}
+
 // ---- the driver of the batch calls ----
 // DD != NULL: the preset dictionaries of the streams whose encoder starts from one.
 // FR != NULL (the *_framed calls; null: raw streams): the container, frame_before / frame_after.
 // planned: the call's plan where the entry point has made it already (null: made here).
+// ZR != NULL (flate_hip_zip_write): the ZIP container, zip_before / zip_after.
 int deflate_common(flate_hip_ctx *c, const EncCall &A, const DeflDict *DD = nullptr, const FrameReq *FR = nullptr,
-                   const StagePlan *planned = nullptr) {
+                   const StagePlan *planned = nullptr, const ZipReq *ZR = nullptr) {
   const uint32_t n = A.n;
   const bool dev = (A.flags & FLATE_HIP_DEVICE_PTRS) != 0;
   HIP_TRY(c, hipSetDevice(c->device));
@@ -457,6 +513,7 @@ int deflate_common(flate_hip_ctx *c, const EncCall &A, const DeflDict *DD = null
     ctl += frame_before_ctl(*FR, n);
     ctl += frame_after_ctl(sum_off, sum_n);
   }
+  if (ZR) ctl += zip_ctl(sum_off, sum_n);
   if ((rc = ctl_begin(c, ctl.up, ctl.down))) return rc;
 
   // stage the input
@@ -478,6 +535,7 @@ int deflate_common(flate_hip_ctx *c, const EncCall &A, const DeflDict *DD = null
 
   // the container in front of the match finder
   if (FR && (rc = frame_before(c, *FR, n, sum_off, sum_n, A.flags))) return rc;
+  if (ZR && (rc = zip_before(c, *ZR, n))) return rc;
 
   // the match finder
   HIP_TRY(c, hipMemsetAsync(c->d_status.p, 0, 8, c->stream));  // (word 1: frame_scan_kernel's first oversized BGZF member)
@@ -497,18 +555,23 @@ int deflate_common(flate_hip_ctx *c, const EncCall &A, const DeflDict *DD = null
   if (FR) F = frame_params(c, *FR, A, d_out, whole[1] - whole[0]);
   // (a spliced member: header + stream + trailer <= out_cap is enough -- the 3 bytes the pack kernel's last dword may
   // reach past the stream lie in the trailer, which is written after it)
-  launch_entropy(c, route, H, pl.n_blocks, FR ? &F : nullptr, FR && A.spliced ? A.out_cap - f_hl - f_tl + 3 : A.out_cap);
+  ZipWriteParams ZW{};
+  if (ZR) ZW = zip_params(c, A, d_out);
+  launch_entropy(c, route, H, pl.n_blocks, FR ? &F : nullptr, FR && A.spliced ? A.out_cap - f_hl - f_tl + 3 : A.out_cap,
+                 ZR ? &ZW : nullptr);
   HIP_TRY(c, hipGetLastError());
 
   // the container behind it
   if (FR && (rc = frame_after(c, *FR, F, d_in, sum_off, sum_n))) return rc;
+  if (ZR && (rc = zip_after(c, ZW, d_in, sum_off, sum_n))) return rc;
   HIP_TRY(c, hipGetLastError());
 
   // read back
   uint64_t *out_off = A.out_off;
-  if (out_off && (rc = ctl_down(c, out_off, (FR && !A.spliced) ? c->d_frame_off.p : c->d_out_off.p, ((size_t)n + 1) * 8)))
+  if (out_off && (rc = ctl_down(c, out_off, ((FR && !A.spliced) || ZR) ? c->d_frame_off.p : c->d_out_off.p, ((size_t)n + 1) * 8)))
     return rc;
   if (A.spliced && (rc = ctl_down(c, &c->h_total_bytes, (uint64_t *)c->d_out_len.p + n, 8))) return rc;
+  if (ZR && (rc = ctl_down(c, &c->h_total_bytes, &ZW.head->total, 8))) return rc;
   if ((rc = ctl_down(c, &c->h_status_word, c->d_status.p, 4))) return rc;
   const bool bgzf = FR && FR->wrap == kWrapBgzf;
   if (bgzf && (rc = ctl_down(c, &c->h_status_aux, (int *)c->d_status.p + 1, 4))) return rc;
@@ -519,13 +582,15 @@ int deflate_common(flate_hip_ctx *c, const EncCall &A, const DeflDict *DD = null
     c->hip_err = "BGZF: block " + std::to_string((uint32_t)c->h_status_aux) + " compresses to a member of more than 65536 bytes";
   if (c->h_status_word) return encoder_status(c, c->h_status_word);
   // (a BGZF file: the members, then the EOF marker frame_write_kernel has put behind them)
-  const uint64_t produced = A.spliced ? c->h_total_bytes + f_hl + f_tl : out_off[n] + (bgzf ? (uint64_t)kBgzfEofLen : 0ull);
+  const uint64_t produced = ZR          ? c->h_total_bytes
+                            : A.spliced ? c->h_total_bytes + f_hl + f_tl
+                                        : out_off[n] + (bgzf ? (uint64_t)kBgzfEofLen : 0ull);
   if (A.total_bytes) *A.total_bytes = produced;
   if (!dev) {
     HIP_TRY(c, hipMemcpyAsync(A.out, c->d_out.p, produced, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
   }
-  const bool used[FLATE_HIP_STAGE_COUNT] = {true, true, FR != nullptr, false};
+  const bool used[FLATE_HIP_STAGE_COUNT] = {true, true, FR != nullptr || ZR != nullptr, false};
   return collect_timing(c, used);
 }
 
@@ -1166,3 +1231,20 @@ int flate_hip_bgzf_write(flate_hip_ctx *c, const uint8_t *in, uint64_t in_len, u
   }
 }
 }  // extern "C"
+
+// ---- ZIP archives (the writing half; the entry point and the reading half: flate_api_zip.hip) ----
+int flate_host::zip_deflate(flate_hip_ctx *c, const uint8_t *in, const uint64_t *in_off, uint32_t n, const uint8_t *names,
+                            const uint64_t *name_off, uint8_t *out, uint64_t out_cap, uint64_t *out_len, uint64_t *entry_off,
+                            uint32_t flags) {
+  try {
+    // (host pointers: one copy in, one copy out -- no "host_pipeline_groups")
+    std::vector<uint64_t> index((size_t)n + 1);  // (the driver reads the archive's index back in any case)
+    const ZipReq ZR{names, name_off};
+    const int rc = deflate_common(c, {in, in_off, n, out, out_cap, entry_off ? entry_off : index.data(), out_len, flags, false},
+                                  nullptr, nullptr, nullptr, &ZR);
+    return rc;
+  } catch (const std::exception &e) {  // (out of host memory in an index vector)
+    c->hip_err = e.what();
+    return FLATE_HIP_E_INTERNAL;
+  }
+}

@@ -360,6 +360,7 @@ static int inflate_common(flate_hip_ctx *c, const InfCall &A, const InfDict *D =
   FrameReadParams R{};
   FrameSplicedParams S{};
   if (A.in_end) R.in_end = (const uint64_t *)c->d_in_end.p;
+  if (A.in_end && !FRD && !SM) I.in_end = (const uint64_t *)c->d_in_end.p;  // (raw streams: inflate_ranges_device)
   if (FRD && (rc = members_before(c, *FRD, d_in, sum_slots, n, A.flags, I, R, dict))) return rc;
   if (SM && (rc = member_before(c, *SM, d_in, in_bytes, n, I, S))) return rc;
 
@@ -603,6 +604,15 @@ int flate_hip_inflate_spliced_framed(flate_hip_ctx *c, const uint8_t *in, uint64
 }
 
 }  // extern "C"
+
+// Raw streams that are not consecutive in device memory (flate_hip_zip_read: the selected entries of an archive).
+int flate_host::inflate_ranges_device(flate_hip_ctx *c, const uint8_t *d_in, const uint64_t *in_off, const uint64_t *in_end,
+                                      uint32_t n, uint8_t *d_out, const uint64_t *out_off, uint64_t *out_len, int32_t *status,
+                                      int64_t *err_off) {
+  InfCall call{d_in, in_off, n, d_out, out_off, out_len, status, err_off, FLATE_HIP_DEVICE_PTRS, 0};
+  call.in_end = in_end;
+  return inflate_common(c, call);
+}
 
 // ---- BGZF files: member discovery (bgzf_kernels.hip) and the read built on it ----
 namespace {

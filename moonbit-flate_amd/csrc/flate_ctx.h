@@ -17,6 +17,7 @@
 #include "deflate_plan.h"
 #include "flate_kernels.h"
 #include "inflate_route.h"
+#include "zip_kernels.h"
 
 namespace flate_host {
 
@@ -71,6 +72,9 @@ struct flate_hip_ctx {
   // flate_hip_bgzf_read_ranges: the range kernels' arrays (BgzfRangeParams), carved from one buffer; the dense scratch
   // the touched members are decoded into; and, for the framed read it runs over them, the members' ends
   DevBuf d_bgzf_rng, d_bgzf_dense, d_in_end;
+  // flate_hip_zip_write: the names and their offsets; flate_hip_zip_index / _read: the end record's words, the
+  // discovery kernels' arrays (ZipDirParams) carved from one buffer, the selected entries and the stored pieces
+  DevBuf d_zip_names, d_zip_name_off, d_zip_whead, d_zip_end, d_zip_dir, d_zip_sel;
   hipStream_t guest_stream = nullptr;
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
   int32_t h_status_word = 0;  // landing pads of small async D2H copies

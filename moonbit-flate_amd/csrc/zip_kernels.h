@@ -1,0 +1,124 @@
+// zip_kernels.h -- the parameter blocks of zip_kernels.hip (flate_hip_zip_write / _index / _read) and the host entry
+// points of the two drivers those calls run through (private).  The format itself is zip_rule.h.
+#pragma once
+
+#include <stdint.h>
+
+#include "flate_hip.h"
+#include "flate_kernels.h"
+
+namespace flate {
+
+// ---- writing: the members placed by a scan, headers and directory behind the pack kernels ----
+struct ZipWriteHead {     // the scan's result words
+  uint64_t cd_off;        // where the directory starts = the sum of the members
+  uint64_t cd_size;
+  uint64_t total;         // the archive's bytes
+  uint32_t k0, pad;       // the first entry whose header offset >= 0xffffffff (n: none)
+};
+struct ZipWriteParams {
+  const uint64_t *out_len;   // per stream: the raw stream's bytes (huff_code_kernel)
+  const uint64_t *in_off;    // n + 1: the entries' input
+  const uint64_t *name_off;  // n + 1, DEVICE copy
+  const uint8_t *names;      // DEVICE copy
+  uint64_t *entry_off;       // n + 1: the local headers, [n] = cd_off
+  uint64_t *payload_off;     // n + 1: what the pack kernels read as HuffParams::out_off
+  const uint32_t *sums;      // the entries' CRC-32
+  uint8_t *out;
+  uint64_t out_cap;
+  uint32_t n;
+  int *status;               // scan_sizes_kernel's status word
+  ZipWriteHead *head;
+};
+
+// ---- reading: the end record ----
+struct ZipEndHead {       // read back as one block
+  uint64_t end_p1;        // the highest consistent end record's offset + 1 (atomic max; 0: none)
+  uint64_t n, cd_off, cd_size, rec_off;
+  int64_t err_off;
+  int32_t rc;
+  uint32_t zip64;
+};
+
+// ---- reading: the directory.  Candidates as in BGZF discovery, their offsets counted from cd_off, so that
+// bgzf_link_kernel and bgzf_round_kernel (which know nothing of the format) link and rank them unchanged. ----
+struct ZipDirHead {       // read back as one block
+  uint64_t out_bytes;     // the sum of size over the entries with status 0 (rc == 0 only)
+  int64_t err_off;
+  uint32_t n_entries;     // well-formed records in front of err_off
+  int32_t rc;
+};
+struct ZipDirParams {
+  const uint8_t *in;      // any byte alignment
+  uint64_t in_len, cd_off, cd_size;
+  uint32_t n;             // records the end record promises
+  uint32_t n_tiles;       // 4 KiB tiles over the directory, on the 16-byte grid of in's ADDRESS
+  uint32_t cap, path_len, ent_cap;  // ent_cap = min(n, cap): entries / out_off hold that many (+ 1)
+  uint32_t *tile_cnt;     // n_tiles + 1
+  uint64_t *cand_off;     // cap: counted from cd_off
+  uint32_t *cand_total;   // cap
+  const uint32_t *path;   // path_len
+  BgzfHead *bhead;        // n_cand for the shared link / round kernels
+  ZipDirHead *head;
+  flate_hip_zip_entry *entries;
+  uint64_t *out_off;
+};
+constexpr uint32_t kZipTile = 4096;
+
+// ---- reading: behind the decoders ----
+struct ZipSel {           // one selected entry, built by the host from the index it has read back
+  uint64_t src;           // data_off
+  uint64_t comp_size, size;
+  uint32_t crc;
+  int32_t status;         // the index status (or FLATE_HIP_E_TOO_LARGE)
+  uint32_t method, pad;
+};
+struct ZipCopyPiece {     // at most kZipCopyPiece bytes of a stored entry
+  uint64_t dst, src;
+  uint32_t len, pad;
+};
+constexpr uint32_t kZipCopyPiece = 65536;
+struct ZipReadParams {
+  const uint8_t *in;
+  uint8_t *out;
+  const ZipSel *sel;
+  const ZipCopyPiece *pieces;
+  uint32_t n_sel, n_pieces;
+  uint64_t *out_len;      // per selected entry: the decoders', then the verdict's
+  int32_t *status;
+  int64_t *err_off;
+  uint32_t *bad;          // per selected entry: not to be summed
+  const uint32_t *sums;   // the CRC-32 of what was produced
+  uint32_t decoded;       // the decoders have run (0: no entry of method 8 was selected)
+};
+
+#if defined(__HIPCC__)
+__global__ void zip_scan_kernel(ZipWriteParams P);
+__global__ void zip_write_kernel(ZipWriteParams P);
+__global__ void zip_end_find_kernel(const uint8_t *in, uint64_t in_len, ZipEndHead *head);
+__global__ void zip_end_read_kernel(const uint8_t *in, uint64_t in_len, ZipEndHead *head);
+__global__ void zip_dir_count_kernel(ZipDirParams P);
+__global__ void zip_dir_scan_kernel(ZipDirParams P);
+__global__ void zip_dir_fill_kernel(ZipDirParams P);
+__global__ void zip_entry_kernel(ZipDirParams P);
+__global__ void zip_out_scan_kernel(ZipDirParams P);
+__global__ void zip_prep_kernel(ZipReadParams P);
+__global__ void zip_copy_kernel(ZipReadParams P);
+__global__ void zip_verdict_kernel(ZipReadParams P);
+#endif
+
+}  // namespace flate
+
+#if defined(__HIPCC__)
+namespace flate_host {
+// flate_api_deflate.hip: flate_hip_zip_write after its checks (n > 0) -- the encode driver with the ZIP container
+int zip_deflate(flate_hip_ctx *c, const uint8_t *in, const uint64_t *in_off, uint32_t n, const uint8_t *names,
+                const uint64_t *name_off, uint8_t *out, uint64_t out_cap, uint64_t *out_len, uint64_t *entry_off,
+                uint32_t flags);
+// flate_api_inflate.hip: the batch decoders over raw streams that are not consecutive in DEVICE memory: stream i =
+// d_in[in_off[i], in_end[i]) into d_out[out_off[i], out_off[i + 1]).  The results reach the host arrays and stay in the
+// ctx's d_out_len / d_istatus / d_ierr.  Returns FLATE_HIP_OK or the first non-zero stream status.
+int inflate_ranges_device(flate_hip_ctx *c, const uint8_t *d_in, const uint64_t *in_off, const uint64_t *in_end, uint32_t n,
+                          uint8_t *d_out, const uint64_t *out_off, uint64_t *out_len, int32_t *status, int64_t *err_off);
+}  // namespace flate_host
+#endif

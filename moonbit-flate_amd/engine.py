@@ -63,6 +63,30 @@ def bgzf_bound(n, block_bytes=0):
     return int(_lib.load().flate_hip_bgzf_bound(int(n), int(block_bytes)))
 
 
+# flate_hip_zip_entry, as numpy sees it (64 bytes)
+ZIP_ENTRY = np.dtype([("name_off", "<u8"), ("header_off", "<u8"), ("data_off", "<u8"), ("comp_size", "<u8"), ("size", "<u8"),
+                      ("crc32", "<u4"), ("name_len", "<u2"), ("method", "<u2"), ("flags", "<u2"), ("reserved", "<u2"),
+                      ("status", "<i4"), ("reserved2", "<u4")], align=True)
+assert ZIP_ENTRY.itemsize == 64
+ZipIndex = collections.namedtuple("ZipIndex", "rc n_entries out_bytes err_off entries out_off names")
+ZipRead = collections.namedtuple("ZipRead", "rc out_off out_len status err_off n_entries archive_err_off")
+
+
+def _zip_names(names):
+    """A list of str / bytes -> (the names back to back as numpy uint8, name_off as numpy uint64)."""
+    raw = [n.encode("utf-8") if isinstance(n, str) else bytes(n) for n in names]
+    off = np.zeros(len(raw) + 1, dtype=np.uint64)
+    np.cumsum([len(r) for r in raw], out=off[1:])
+    return np.frombuffer(b"".join(raw) or b"\0", dtype=np.uint8).copy(), off
+
+
+def zip_bound(in_off, names):
+    """Room that always holds the ZIP archive of these entries (flate_hip_zip_bound; 0: a name would be refused)."""
+    in_off = np.ascontiguousarray(in_off, dtype=np.uint64)
+    _, name_off = _zip_names(names)
+    return int(_lib.load().flate_hip_zip_bound(in_off.ctypes.data, len(names), name_off.ctypes.data))
+
+
 def synth(kind, n_streams, stream_len, seed=None, first_stream=0, nthreads=None):
     """Synthetic benchmark input: n_streams streams of stream_len bytes, back to back."""
     k = SYNTH_KINDS[kind] if isinstance(kind, str) else int(kind)
@@ -552,6 +576,162 @@ class FlateEngine:
         cap = room if out_cap is None else min(int(out_cap), room)
         return out, result(call(out.data_ptr() if device else out.ctypes.data, cap))
 
+    def zip_write(self, data, in_off, names, compat_go=False, out=None, out_cap=None, index=False):
+        """The entries data[in_off[i]:in_off[i + 1]], named names[i] (str or UTF-8 bytes), as ONE ZIP archive that
+        zipfile, unzip and every other reader open (flate_hip_zip_write): each entry's data is the raw stream
+        deflate_batch gives for it, local headers, central directory and end records are written on the GPU.  data:
+        numpy uint8 / bytes (returns the archive as bytes) or a torch uint8 CUDA tensor (returns (out, out_len), the
+        archive in out[:out_len] on the device).  index=True: entry_off (numpy uint64[n + 1], the local headers and
+        the directory's offset) is appended to the result."""
+        data, in_ptr, _, device = self._bgzf_in(data)
+        in_off = np.ascontiguousarray(in_off, dtype=np.uint64)
+        n = in_off.size - 1
+        if n != len(names):
+            raise FlateError(E_INVALID, "zip_write: one name per entry")
+        name_bytes, name_off = _zip_names(names)
+        if out_cap is None and out is None:
+            out_cap = int(self._L.flate_hip_zip_bound(in_off.ctypes.data, n, name_off.ctypes.data))
+            if out_cap == 0:
+                raise FlateError(E_INVALID, "zip_write: a name must have 1 .. 65535 bytes and in_off must not decrease")
+        if device:
+            import torch
+            if out is None:
+                out = torch.empty(max(int(out_cap), 32), dtype=torch.uint8, device=data.device)
+            else:
+                _check_out(out, data, 0, "zip_write")
+            cap = out.numel() if out_cap is None else min(int(out_cap), out.numel())
+            out_ptr = out.data_ptr()
+        else:
+            if out is None:
+                out = np.empty(max(int(out_cap), 32), dtype=np.uint8)
+            else:
+                _check_out(out, data, 0, "zip_write")
+            cap = out.size if out_cap is None else min(int(out_cap), out.size)
+            out_ptr = out.ctypes.data
+        entry_off = np.zeros(n + 1, dtype=np.uint64)
+        out_len = C.c_uint64(0)
+        self._check(self._L.flate_hip_zip_write(self._ctx, in_ptr, in_off.ctypes.data, n, name_bytes.ctypes.data,
+                                                name_off.ctypes.data, out_ptr, cap, C.byref(out_len),
+                                                entry_off.ctypes.data, self._flags(compat_go, False, device)))
+        res = (out, int(out_len.value)) if device else (bytes(out[:int(out_len.value)]),)
+        if index:
+            res = res + (entry_off,)
+        return res if len(res) > 1 else res[0]
+
+    def zip_index(self, data):
+        """The entries of a ZIP archive, found on the GPU from the archive's bytes (flate_hip_zip_index) ->
+        ZipIndex(rc, n_entries, out_bytes, err_off, entries, out_off, names).  rc 0: entries is a numpy structured
+        array (ZIP_ENTRY: name_off, header_off, data_off, comp_size, size, crc32, name_len, method, flags, status),
+        out_off (numpy uint64[n + 1]) where each entry's bytes go when all are read, names the entries' names (str;
+        bytes where a name is not UTF-8).  rc -4 (FLATE_HIP_E_CORRUPT): a malformed archive at err_off behind
+        n_entries good records; the arrays are None.  data: numpy uint8 / bytes, or a torch uint8 CUDA tensor.
+        Other failures raise FlateError."""
+        data, in_ptr, n, device = self._bgzf_in(data)
+        flags = DEVICE_PTRS if device else 0
+        ne, ob, eo = C.c_uint32(0), C.c_uint64(0), C.c_int64(-1)
+        rc = self._L.flate_hip_zip_index(self._ctx, in_ptr, n, 0, None, None, C.byref(ne), C.byref(ob), C.byref(eo), flags)
+        if rc not in (0, E_CORRUPT):
+            self._check(rc)
+        if rc != 0:
+            return ZipIndex(rc, int(ne.value), 0, int(eo.value), None, None, None)
+        cnt = int(ne.value)
+        entries = np.zeros(max(cnt, 1), dtype=ZIP_ENTRY)
+        out_off = np.zeros(cnt + 1, dtype=np.uint64)
+        self._check(self._L.flate_hip_zip_index(self._ctx, in_ptr, n, cnt, entries.ctypes.data, out_off.ctypes.data,
+                                                C.byref(ne), C.byref(ob), C.byref(eo), flags))
+        entries = entries[:cnt]
+        names = []
+        if cnt:
+            lo = int(entries["name_off"].min())
+            hi = int((entries["name_off"] + entries["name_len"]).max())
+            blob = data[lo:hi].cpu().numpy().tobytes() if device else data[lo:hi].tobytes()
+            for e in entries:
+                raw = blob[int(e["name_off"]) - lo:int(e["name_off"]) - lo + int(e["name_len"])]
+                try:
+                    names.append(raw.decode("utf-8"))
+                except UnicodeDecodeError:
+                    names.append(raw)
+        return ZipIndex(0, cnt, int(ob.value), -1, entries, out_off, names)
+
+    def zip_read(self, data, select=None, out=None, out_cap=None):
+        """Entries of a ZIP archive back into their bytes by one call (flate_hip_zip_read): discovery, decode
+        (deflate through the batch decoders, stored through a copy kernel) and the check of every entry's size and
+        CRC-32 on the GPU.  select: entry numbers or names (a list in any order, duplicates allowed; names cost an index
+        call first), None = every entry.  Returns (out, ZipRead(rc, out_off, out_len, status, err_off, n_entries,
+        archive_err_off)): selected entry j is out[out_off[j]:out_off[j] + out_len[j]] (numpy for host data, a torch
+        CUDA tensor for device data).  rc 0; -4 with archive_err_off >= 0: a malformed archive, nothing decoded; -2
+        with out_off[-1] > capacity: out too small, nothing decoded; otherwise the first non-zero entry status, all other
+        entries delivered.  out=None: sized by the size query first.  A name that is not in the archive raises KeyError;
+        other failures raise FlateError."""
+        data, in_ptr, n, device = self._bgzf_in(data)
+        flags = DEVICE_PTRS if device else 0
+        sel = None
+        if select is not None:
+            select = list(select)
+            if any(not isinstance(x, (int, np.integer)) for x in select):
+                ix = self.zip_index(data)
+                if ix.rc != 0:
+                    return out, ZipRead(ix.rc, None, None, None, None, ix.n_entries, ix.err_off)
+                where = {}
+                for k, name in enumerate(ix.names):
+                    where.setdefault(name, k)
+
+                def number(x):
+                    if isinstance(x, (int, np.integer)):
+                        return int(x)
+                    if isinstance(x, (bytes, bytearray)):
+                        try:
+                            x = bytes(x).decode("utf-8")
+                        except UnicodeDecodeError:
+                            x = bytes(x)
+                    return where[x]
+
+                select = [number(x) for x in select]
+            sel = np.ascontiguousarray(select, dtype=np.uint32)
+            ns = sel.size
+        else:
+            ne, ob, eo = C.c_uint32(0), C.c_uint64(0), C.c_int64(-1)
+            rc = self._L.flate_hip_zip_index(self._ctx, in_ptr, n, 0, None, None, C.byref(ne), C.byref(ob), C.byref(eo), flags)
+            if rc not in (0, E_CORRUPT):
+                self._check(rc)
+            if rc != 0:
+                return out, ZipRead(rc, None, None, None, None, int(ne.value), int(eo.value))
+            ns = int(ne.value)
+        out_off = np.zeros(ns + 1, dtype=np.uint64)
+        out_len = np.zeros(max(ns, 1), dtype=np.uint64)
+        status = np.zeros(max(ns, 1), dtype=np.int32)
+        err_off = np.full(max(ns, 1), -1, dtype=np.int64)
+        ne, aeo = C.c_uint32(0), C.c_int64(-1)
+        statuses = (0, E_OUT_TOO_SMALL, E_CORRUPT, E_UNEXPECTED_EOF, E_TOO_LARGE, E_UNSUPPORTED)
+
+        def call(out_ptr, cap):
+            rc = self._L.flate_hip_zip_read(self._ctx, in_ptr, n, sel.ctypes.data if sel is not None else None,
+                                            ns if sel is not None else 0, ns, out_ptr, cap, out_off.ctypes.data,
+                                            out_len.ctypes.data, status.ctypes.data, err_off.ctypes.data, C.byref(ne),
+                                            C.byref(aeo), flags)
+            if rc not in statuses:
+                self._check(rc)
+            return rc
+
+        def result(rc):
+            return ZipRead(rc, out_off, out_len[:ns], status[:ns], err_off[:ns], int(ne.value), int(aeo.value))
+
+        if out is None:
+            rc = call(None, 0)  # the size query: nothing is decoded
+            need = int(out_off[ns]) if rc == E_OUT_TOO_SMALL else 0
+            if device:
+                import torch
+                out = torch.empty(max(need, 16), dtype=torch.uint8, device=data.device)
+            else:
+                out = np.zeros(max(need, 16), dtype=np.uint8)
+            if rc != E_OUT_TOO_SMALL:
+                return out, result(rc)
+        else:
+            _check_out(out, data, 0, "zip_read")
+        room = out.numel() if device else out.size
+        cap = room if out_cap is None else min(int(out_cap), room)
+        return out, result(call(out.data_ptr() if device else out.ctypes.data, cap))
+
     def inflate_batch(self, data, in_off, out_sizes, out=None, check=True, zdicts=None, dict_of=None):
         """Decompress independent DEFLATE streams (&Reader::new + read to EOF each).
         out_sizes[i] = capacity reserved for stream i's output (its exact size if known).
@@ -1005,6 +1185,7 @@ def parse_container_header(m, wrap, fdict=False):
 
 # status codes of inflate_batch (include/flate_hip.h)
 E_INVALID, E_OUT_TOO_SMALL, E_CORRUPT, E_UNEXPECTED_EOF, E_INTERNAL = -1, -2, -4, -7, -8
+E_TOO_LARGE, E_UNSUPPORTED = -6, -10
 
 
 def lz_chunks(stream_len):

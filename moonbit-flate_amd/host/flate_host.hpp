@@ -954,4 +954,93 @@ inline Err decompress_bgzf_ranges(Engine &e, const std::vector<uint8_t> &file, c
   return make_error(e, rc);
 }
 
+// ---- ZIP archives ----------------------------------------------------------------------------
+// compress_zip: entries[i] under names[i] (UTF-8, 1 .. 65535 bytes each) as ONE archive that zipfile, unzip and
+// every other reader open; one call (flate_hip_zip_write), headers and directory written on the GPU.  entry_off (may
+// be null): the local header offsets and, last, where the directory starts.
+inline Err compress_zip(Engine &e, const std::vector<std::vector<uint8_t>> &entries, const std::vector<std::string> &names,
+                        std::vector<uint8_t> &out, std::vector<uint64_t> *entry_off = nullptr, uint32_t flags = 0) {
+  if (!e.ok()) return make_error(e, e.status());
+  if (entries.size() != names.size()) return make_error(e, FLATE_HIP_E_INVALID);
+  const uint32_t n = (uint32_t)entries.size();
+  std::vector<uint64_t> in_off(n + 1, 0), name_off(n + 1, 0), off(n + 1, 0);
+  for (uint32_t i = 0; i < n; ++i) {
+    in_off[i + 1] = in_off[i] + entries[i].size();
+    name_off[i + 1] = name_off[i] + names[i].size();
+  }
+  std::vector<uint8_t> in(in_off[n] + 1), nm(name_off[n] + 1);
+  for (uint32_t i = 0; i < n; ++i) {
+    std::copy(entries[i].begin(), entries[i].end(), in.begin() + in_off[i]);
+    std::copy(names[i].begin(), names[i].end(), nm.begin() + name_off[i]);
+  }
+  const size_t cap = flate_hip_zip_bound(in_off.data(), n, name_off.data());
+  if (!cap) return make_error(e, FLATE_HIP_E_INVALID);
+  std::vector<uint8_t> buf(cap);
+  uint64_t len = 0;
+  const int rc = flate_hip_zip_write(e.ctx(), in.data(), in_off.data(), n, nm.data(), name_off.data(), buf.data(), cap, &len,
+                                     off.data(), flags);
+  if (rc != 0) return make_error(e, rc);
+  out.assign(buf.begin(), buf.begin() + len);
+  if (entry_off) *entry_off = off;
+  return std::nullopt;
+}
+
+// What decompress_zip found beside the bytes.
+struct ZipInfo {
+  std::vector<std::string> names;            // every entry's name, as the directory has it
+  std::vector<flate_hip_zip_entry> entries;  // the index
+  std::vector<int32_t> entry_status;         // per entry: 0 or its FLATE_HIP_E_* code
+  std::vector<int64_t> entry_err_off;
+  uint32_t n_entries = 0;
+  int64_t err_off = -1;                      // a malformed archive: where (flate_hip_zip_index)
+  int status = 0;                            // the FLATE_HIP_E_* code behind the error (0 = none)
+};
+
+// decompress_zip: every entry of an archive: discovery, decoding (deflate and stored) and the check of every entry's
+// size and CRC-32 on the GPU (flate_hip_zip_index for the names and sizes, flate_hip_zip_read for the bytes).  out[i] =
+// entry i's bytes (empty for a failing entry).  Errors: a malformed archive is corrupt_input_error(where), `out` empty; a
+// failing entry is corrupt_input_error(its header offset), err_unexpected_eof or make_error(its status) -- `out` then
+// still holds every other entry (info->entry_status says which failed).
+inline Err decompress_zip(Engine &e, const std::vector<uint8_t> &file, std::vector<std::vector<uint8_t>> &out,
+                          ZipInfo *info = nullptr) {
+  if (!e.ok()) return make_error(e, e.status());
+  ZipInfo I;
+  uint64_t need = 0;
+  out.clear();
+  int rc = flate_hip_zip_index(e.ctx(), file.data(), file.size(), 0, nullptr, nullptr, &I.n_entries, &need, &I.err_off, 0);
+  int64_t where = I.err_off;
+  if (rc == 0) {
+    const uint32_t n = I.n_entries;
+    I.entries.resize((size_t)n + 1);
+    std::vector<uint64_t> out_off((size_t)n + 1, 0), out_len((size_t)n + 1, 0);
+    I.entry_status.assign((size_t)n + 1, 0);
+    I.entry_err_off.assign((size_t)n + 1, -1);
+    rc = flate_hip_zip_index(e.ctx(), file.data(), file.size(), n, I.entries.data(), out_off.data(), &I.n_entries, &need,
+                             &I.err_off, 0);
+    if (rc == 0) {
+      std::vector<uint8_t> buf(need + 8);
+      rc = flate_hip_zip_read(e.ctx(), file.data(), file.size(), nullptr, 0, n, buf.data(), need, out_off.data(), out_len.data(),
+                              I.entry_status.data(), I.entry_err_off.data(), &I.n_entries, &I.err_off, 0);
+      if (I.err_off < 0) {  // (the archive itself is well-formed: rc is an entry's status)
+        out.resize(n);
+        for (uint32_t i = 0; i < n; ++i) {
+          const flate_hip_zip_entry &z = I.entries[i];
+          I.names.emplace_back(file.begin() + z.name_off, file.begin() + z.name_off + z.name_len);
+          if (I.entry_status[i] == 0) out[i].assign(buf.begin() + out_off[i], buf.begin() + out_off[i] + out_len[i]);
+          else if (where < 0) where = (int64_t)z.header_off;
+        }
+      } else {
+        where = I.err_off;
+      }
+    }
+    I.entries.resize(n), I.entry_status.resize(n), I.entry_err_off.resize(n);
+  }
+  I.status = rc;
+  if (info) *info = I;
+  if (rc == 0) return std::nullopt;
+  if (rc == FLATE_HIP_E_CORRUPT) return corrupt_input_error(where);
+  if (rc == FLATE_HIP_E_UNEXPECTED_EOF) return err_unexpected_eof();
+  return make_error(e, rc);
+}
+
 }  // namespace flate_host
