@@ -657,6 +657,73 @@ int flate_hip_bgzf_read_ranges(flate_hip_ctx *ctx, const uint8_t *in, uint64_t i
                                uint32_t *n_members, uint32_t *n_decoded, uint32_t *bad_member,
                                int64_t *err_off, uint32_t flags);
 
+/* -- Plain multi-member gzip files: indexed and read in one call each -----------------
+ * The gzip files people have -- `cat a.gz b.gz`, rotated logs, Hadoop part files, WARC / WET records, the concatenated
+ * members flate_hip_deflate_fast_batch_framed(FLATE_HIP_WRAP_GZIP) writes -- carry no index: member k + 1 starts where
+ * member k's DEFLATE stream ends, plus 8 bytes, and nothing in a header says where that is.  These two calls find the
+ * members on the device, from the file's bytes alone.  The rule and the walk are written once, csrc/gzip_rule.h; the
+ * kernels are csrc/gzip_kernels.hip.
+ *
+ * THE RULE.  A member can start at offset p iff in[p, E), E = min(in_len, p + M), begins with a gzip header as
+ * flate_hip_inflate_batch_framed accepts it: 1f 8b 08; FLG with the reserved bits zero; the 10 fixed bytes; FEXTRA,
+ * FNAME, FCOMMENT, FHCRC skipped in that order, every NUL below E; and 8 bytes left for the trailer.  M is the option
+ * "gzip_member_max" (flate_hip_set_option): 2^28 - 1 by default, which is also the most -- the bit positions of the
+ * decoder are 32 bits wide -- so it can only be lowered.  Every such p is a CANDIDATE.  Its raw stream is decoded
+ * size-only over in[p + header, E - 8): status s, the size z it inflates to, and `used`, the bytes up to and including
+ * the one that holds the last bit of the final block.  s == 0: the member is in[p, e), e = p + header + used + 8.
+ *
+ * THE WALK that defines every result starts at p = 0.  p == in_len: success (in_len == 0: zero members).  No header at
+ * p: FLATE_HIP_E_CORRUPT, *err_off = p.  s != 0: the walk ends with *err_off = p and s -- FLATE_HIP_E_CORRUPT,
+ * FLATE_HIP_E_UNEXPECTED_EOF, or FLATE_HIP_E_TOO_LARGE for a member that inflates to 4 GiB or more -- except that
+ * FLATE_HIP_E_UNEXPECTED_EOF in a range that M clipped (p + M < in_len) is FLATE_HIP_E_TOO_LARGE: such a member is read
+ * with flate_hip_inflate_stream_read.  Otherwise p = e.  The file must end exactly where a member ends: padding or
+ * garbage behind the last member, zero bytes included, is FLATE_HIP_E_CORRUPT at its offset.
+ *
+ * flate_hip_gzip_index has flate_hip_bgzf_index's conventions.  On success member_off[0 .. n] (member_off[n] = in_len)
+ * and out_off[0 .. n] (the exclusive prefix sum of what the members ACTUALLY inflate to, never of ISIZE: a wrong ISIZE
+ * is that member's failure at read time, not a misplaced slot) are exactly what
+ * flate_hip_inflate_batch_framed(FLATE_HIP_WRAP_GZIP) takes as in_off and out_off; *out_bytes = out_off[n]; *err_off =
+ * -1.  Both arrays are HOST arrays of index_cap entries, or both NULL: a query that returns only the counts.
+ * index_cap < n + 1: FLATE_HIP_E_OUT_TOO_SMALL with the counts set.  A broken chain: the return value and *err_off are
+ * the walk's, *n_members = the good members in front, *out_bytes = 0, and the first n_members + 1 entries of both arrays
+ * are still filled if they fit -- a caller can salvage the good prefix through the framed batch call.  *n_candidates
+ * (may be NULL, as may err_off): how many offsets were decoded speculatively.  flags: FLATE_HIP_DEVICE_PTRS or 0,
+ * anything else is FLATE_HIP_E_INVALID before any HIP call.  More candidates than 32 bits count: FLATE_HIP_E_TOO_LARGE.
+ * Nothing outside in[0, in_len) is read, at any alignment of in.
+ *   How: every offset that passes the rule is a candidate (one pass with 16-byte loads, the 3-byte magic and the FLG
+ *   mask tested in LDS, the rule run from global memory on the rare hit, compacted in file order); the count comes
+ *   back to the host; ONE size-only launch of the batch decoders runs over all candidates -- it stores nothing, so a
+ *   decoy can write nothing --; every candidate finds the candidate at its end by binary search; the chain from offset
+ *   0 is ranked by pointer doubling.  A decoy (a gzip member inside a stored block, a header inside a file name) is a
+ *   candidate like any other, gets a successor like any other, and is simply not on the path from candidate 0.  The
+ *   discovery kernels are counted in no profiling stage.
+ *   The work: the sum, over the candidates, of the bytes each consumes before its stream ends or fails, each at most M
+ *   -- the members themselves once, plus the decoys; and every false hit's header rule, a NUL scan of at most M bytes.
+ *   1f 8b 08 and three zero FLG bits have probability 2^-27 per offset of random bytes, about eight per GiB (arithmetic,
+ *   not a measurement), and a garbage stream dies within a few blocks.  Both are properties of the method: a file
+ *   built to hold many long decoys costs their sum, and no further guard exists.
+ *
+ * flate_hip_gzip_read: the discovery, then flate_hip_bgzf_read's tail -- one read-back of the index, the framed gzip
+ * decode of every member into the dense slots out_off, CRC-32 and ISIZE judged on the device.  Host pointers: the file
+ * is uploaded once, shared by discovery and decode, and out[0, *out_len) is downloaded once.
+ *   A broken chain: the walk's code and *err_off, *bad_member = the count of good members, *out_len = 0, nothing is
+ *   written.  A total above out_cap: FLATE_HIP_E_OUT_TOO_SMALL, *out_len = the size needed, nothing is decoded (out ==
+ *   NULL with out_cap == 0 is the size query).  Otherwise every member is decoded, *out_len = out_off[n], and the return
+ *   value is the first non-zero member status as flate_hip_inflate_batch_framed defines it, with *bad_member = its index
+ *   and *err_off = its file offset; on success 0xffffffff and -1.  n_members, bad_member and err_off may each be NULL.
+ *   The slot-write guarantees of flate_hip_inflate_batch hold.  With profiling on, FLATE_HIP_STAGE_INFLATE and
+ *   FLATE_HIP_STAGE_CHECKSUM are the decode pass's, as in flate_hip_bgzf_read: the size-only pass of the discovery is in
+ *   neither.
+ *   Out of scope: zero or garbage padding behind the last member; members of M bytes or more; running a clipped
+ *   candidate again unclipped; caching the index across calls; salvage inside flate_hip_gzip_read; zlib or raw
+ *   concatenations. */
+int flate_hip_gzip_index(flate_hip_ctx *ctx, const uint8_t *in, uint64_t in_len, uint64_t index_cap,
+                         uint64_t *member_off, uint64_t *out_off, uint32_t *n_members, uint64_t *out_bytes,
+                         uint32_t *n_candidates, int64_t *err_off, uint32_t flags);
+int flate_hip_gzip_read(flate_hip_ctx *ctx, const uint8_t *in, uint64_t in_len, uint8_t *out, uint64_t out_cap,
+                        uint64_t *out_len, uint32_t *n_members, uint32_t *bad_member, int64_t *err_off,
+                        uint32_t flags);
+
 /* -- ZIP archives ----------------------------------------------------------------
  * The everyday container of a batch of independent DEFLATE streams (.zip, .npz, .jar, .whl, .docx; PKWARE APPNOTE
  * 6.3), and the one whose own index, the central directory, makes writing and reading parallel.  The format rule is

@@ -131,6 +131,23 @@ inline uint32_t bgzf_rounds(uint32_t cap) {
   return r;
 }
 
+// ---- plain multi-member gzip files (flate_hip_gzip_index / _read) ----
+
+// the option "gzip_member_max": the range a candidate is given, 1 .. 2^28 - 1 bytes (the default, which a caller can
+// only lower: the sub-block decoder's bit positions are 32 bits wide)
+inline bool gzip_member_max_ok(int64_t value) { return value >= 1 && value <= (1ll << 28) - 1; }
+// member_off and out_off come together or not at all (the count query)
+inline int gzip_index_args(const uint8_t *in, uint64_t in_len, const uint64_t *member_off, const uint64_t *out_off,
+                           const uint32_t *n_members, const uint64_t *out_bytes, uint32_t flags) {
+  if (!n_members || !out_bytes || (in_len && !in) || (!member_off != !out_off)) return FLATE_HIP_E_INVALID;
+  return (flags & ~FLATE_HIP_DEVICE_PTRS) ? FLATE_HIP_E_INVALID : FLATE_HIP_OK;
+}
+inline int gzip_read_args(const uint8_t *in, uint64_t in_len, const uint8_t *out, uint64_t out_cap,
+                          const uint64_t *out_len, uint32_t flags) {
+  if (!out_len || (in_len && !in) || (out_cap && !out)) return FLATE_HIP_E_INVALID;
+  return (flags & ~FLATE_HIP_DEVICE_PTRS) ? FLATE_HIP_E_INVALID : FLATE_HIP_OK;
+}
+
 // ---- ZIP archives (flate_hip_zip_write / _index / _read) ----
 
 // everything flate_hip_zip_write refuses before any HIP call

@@ -9,6 +9,8 @@
 #include <cstdlib>
 #include <cstring>
 
+#include "api_checks.h"
+
 using namespace flate;
 using namespace flate_host;
 
@@ -338,7 +340,8 @@ int flate_hip_set_option(flate_hip_ctx *c, const char *name, int64_t value) {
     c->inject_stall = (uint32_t)value;
   } else if (k == "debug_buffer_reset" && value >= 0 && value <= 0x7fffffff) {
     c->debug_buffer_reset = value;
-
+  } else if (k == "gzip_member_max" && gzip_member_max_ok(value)) {
+    c->gzip_member_max = (uint64_t)value;
   } else {
     return FLATE_HIP_E_INVALID;
   }

@@ -14,6 +14,7 @@
 #include "api_checks.h"
 #include "bgzf_range_rule.h"
 #include "bgzf_rule.h"
+#include "gzip_rule.h"
 
 using namespace flate;
 using namespace flate_host;
@@ -691,6 +692,47 @@ int bgzf_stage(flate_hip_ctx *c, const uint8_t *in, uint64_t in_len, uint32_t fl
   return FLATE_HIP_OK;
 }
 
+// The tail flate_hip_bgzf_read and flate_hip_gzip_read share, behind a discovery that found a sound chain of n members
+// whose output fits: d_member_off / d_out_off (n + 1 entries each) are the index, still on the device.  It comes back
+// once, 16 bytes per member -- the decoders' routing and the checksum plan are host code --, then the framed gzip read
+// runs over d_in (DEVICE memory: the caller's buffer or the staged copy) into the dense slots, and, for a host caller,
+// out[0, out_bytes) comes down once.  Returns the first non-zero member status, with that member's index and offset.
+int members_read(flate_hip_ctx *c, const uint8_t *d_in, uint32_t n, const uint64_t *d_member_off,
+                 const uint64_t *d_out_off, uint64_t out_bytes, uint8_t *out, uint32_t flags, uint32_t *bad_member,
+                 int64_t *err_off) {
+  const bool dev = (flags & FLATE_HIP_DEVICE_PTRS) != 0;
+  int rc;
+  std::vector<uint64_t> moff((size_t)n + 1), ooff((size_t)n + 1), olen(n);
+  std::vector<int32_t> st(n);
+  std::vector<int64_t> eo(n);
+  HIP_TRY(c, hipMemcpyAsync(moff.data(), d_member_off, ((size_t)n + 1) * 8, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(ooff.data(), d_out_off, ((size_t)n + 1) * 8, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  if ((rc = inflate_batch_ranges(moff.data(), n, ooff.data(), 0))) return rc;
+  uint8_t *d_out = out;
+  if (!dev) {
+    if ((rc = ensure(c, c->d_out, out_bytes + 16))) return rc;
+    d_out = (uint8_t *)c->d_out.p;
+  }
+  // the framed gzip read over the staged copy, fed with the index the device has just produced
+  const InfFrame FRD{FLATE_HIP_WRAP_GZIP, nullptr, nullptr, 0, nullptr};
+  rc = inflate_common(c, {d_in, moff.data(), n, d_out, ooff.data(), olen.data(), st.data(), eo.data(),
+                          flags | FLATE_HIP_DEVICE_PTRS, 0},
+                      nullptr, &FRD);
+  if (!is_stream_status(rc)) return rc;
+  if (!dev && out_bytes) {
+    HIP_TRY(c, hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+  }
+  for (uint32_t i = 0; i < n; ++i)
+    if (st[i]) {
+      if (bad_member) *bad_member = i;
+      if (err_off) *err_off = (int64_t)moff[i];
+      return st[i];
+    }
+  return FLATE_HIP_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -747,7 +789,6 @@ int flate_hip_bgzf_read(flate_hip_ctx *c, const uint8_t *in, uint64_t in_len, ui
   if (eof_marker) *eof_marker = 0;
   if (in_len == 0) return FLATE_HIP_OK;
   try {
-    const bool dev = (flags & FLATE_HIP_DEVICE_PTRS) != 0;
     const uint8_t *d_in = nullptr;
     if ((rc = bgzf_stage(c, in, in_len, flags, &d_in))) return rc;
     BgzfHead H{};
@@ -763,36 +804,7 @@ int flate_hip_bgzf_read(flate_hip_ctx *c, const uint8_t *in, uint64_t in_len, ui
     if (eof_marker) *eof_marker = (int)H.eof_marker;
     *out_len = H.out_bytes;
     if (H.out_bytes > out_cap) return FLATE_HIP_E_OUT_TOO_SMALL;
-    // the index comes back once, 16 bytes per member: the decoders' routing and the checksum plan are host code
-    std::vector<uint64_t> moff((size_t)n + 1), ooff((size_t)n + 1), olen(n);
-    std::vector<int32_t> st(n);
-    std::vector<int64_t> eo(n);
-    HIP_TRY(c, hipMemcpyAsync(moff.data(), P.member_off, ((size_t)n + 1) * 8, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(ooff.data(), P.out_off, ((size_t)n + 1) * 8, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if ((rc = inflate_batch_ranges(moff.data(), n, ooff.data(), 0))) return rc;
-    uint8_t *d_out = out;
-    if (!dev) {
-      if ((rc = ensure(c, c->d_out, H.out_bytes + 16))) return rc;
-      d_out = (uint8_t *)c->d_out.p;
-    }
-    // the framed gzip read over the staged copy, fed with the index the device has just produced
-    const InfFrame FRD{FLATE_HIP_WRAP_GZIP, nullptr, nullptr, 0, nullptr};
-    rc = inflate_common(c, {d_in, moff.data(), n, d_out, ooff.data(), olen.data(), st.data(), eo.data(),
-                            flags | FLATE_HIP_DEVICE_PTRS, 0},
-                        nullptr, &FRD);
-    if (!is_stream_status(rc)) return rc;
-    if (!dev && H.out_bytes) {
-      HIP_TRY(c, hipMemcpyAsync(out, d_out, H.out_bytes, hipMemcpyDeviceToHost, c->stream));
-      HIP_TRY(c, hipStreamSynchronize(c->stream));
-    }
-    for (uint32_t i = 0; i < n; ++i)
-      if (st[i]) {
-        if (bad_member) *bad_member = i;
-        if (err_off) *err_off = (int64_t)moff[i];
-        return st[i];
-      }
-    return FLATE_HIP_OK;
+    return members_read(c, d_in, n, P.member_off, P.out_off, H.out_bytes, out, flags, bad_member, err_off);
   } catch (const std::exception &e) {  // (out of host memory in an index vector)
     c->hip_err = e.what();
     return FLATE_HIP_E_INTERNAL;
@@ -975,6 +987,198 @@ int flate_hip_bgzf_read_ranges(flate_hip_ctx *c, const uint8_t *in, uint64_t in_
       return st[i];
     }
     return verdict;
+  } catch (const std::exception &e) {  // (out of host memory in an index vector)
+    c->hip_err = e.what();
+    return FLATE_HIP_E_INTERNAL;
+  }
+}
+
+}  // extern "C"
+
+// ---- plain multi-member gzip files: member discovery (gzip_kernels.hip) and the read built on it ----
+namespace {
+
+// The discovery over d_in[0, in_len) (DEVICE memory) on the ctx's stream: count and scan, ONE read-back of the candidate
+// count (the launches behind it have a thread or a wavefront per candidate), then fill, frame_parse_kernel, one
+// size-only launch of the batch decoders over all candidates, link, rounds, finish, out-scan.  H = the result words once
+// the stream has drained; P.B.member_off / P.B.out_off = the index, still on the device (null when the file holds no
+// candidate: H then says FLATE_HIP_E_CORRUPT at offset 0).  The discovery kernels are counted in no profiling stage.
+int gzip_discover(flate_hip_ctx *c, const uint8_t *d_in, uint64_t in_len, BgzfHead &H, GzipParams &P) {
+  const uint64_t A = reinterpret_cast<uintptr_t>(d_in) & 15u;
+  const uint64_t tiles = (A + in_len + kBgzfTile - 1) / kBgzfTile;
+  if (tiles > 0x7fffffffull) return FLATE_HIP_E_TOO_LARGE;
+  size_t at = 0;
+  auto carve = [&](size_t bytes) {
+    const size_t here = at;
+    at += (bytes + 255) & ~(size_t)255;
+    return here;
+  };
+  P = GzipParams{};
+  P.B.in = d_in;
+  P.B.in_len = in_len;
+  P.B.n_tiles = (uint32_t)tiles;
+  P.member_max = c->gzip_member_max;
+  int rc;
+  {
+    const size_t o_head = carve(sizeof(BgzfHead)), o_tile = carve(((size_t)P.B.n_tiles + 1) * 4);
+    if ((rc = ensure(c, c->d_gzip_tiles, at))) return rc;
+    uint8_t *b = (uint8_t *)c->d_gzip_tiles.p;
+    P.B.head = (BgzfHead *)(b + o_head);
+    P.B.tile_cnt = (uint32_t *)(b + o_tile);
+  }
+  hipLaunchKernelGGL(gzip_count_kernel, dim3(P.B.n_tiles), dim3(256), 0, c->stream, P);
+  hipLaunchKernelGGL(bgzf_scan_kernel, dim3(1), dim3(1024), 0, c->stream, P.B);
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipMemcpyAsync(&H, P.B.head, sizeof H, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  const uint32_t cap = H.n_cand;
+  if (cap > 0x7ffffff0u) return FLATE_HIP_E_TOO_LARGE;  // (the count saturates at 2^32 - 1)
+  if (cap == 0) return FLATE_HIP_OK;  // (the scan kernel has left the verdict: no member can start at offset 0)
+
+  const uint32_t rounds = bgzf_rounds(cap);
+  P.B.cap = cap;
+  P.B.path_len = 1u << rounds;
+  at = 0;
+  const size_t n = cap;
+  const size_t o_coff = carve((n + 1) * 8), o_cend = carve(n * 8), o_poff = carve((n + 1) * 8), o_pend = carve(n * 8),
+               o_want = carve(n * 4), o_isize = carve(n * 4), o_bad = carve(n * 4), o_dict = carve(n * 4),
+               o_olen = carve(n * 8), o_st = carve(n * 4), o_err = carve(n * 8), o_used = carve(n * 8),
+               o_j0 = carve((n + 2) * 4), o_j1 = carve((n + 2) * 4), o_path = carve((size_t)P.B.path_len * 4),
+               o_msize = carve(n * 8), o_moff = carve((n + 1) * 8), o_ooff = carve((n + 1) * 8);
+  if ((rc = ensure(c, c->d_gzip, at))) return rc;  // (a failed allocation is FLATE_HIP_E_HIP, never a truncated result)
+  uint8_t *b = (uint8_t *)c->d_gzip.p;
+  P.B.cand_off = (uint64_t *)(b + o_coff);
+  P.cand_end = (uint64_t *)(b + o_cend);
+  P.B.jump[0] = (uint32_t *)(b + o_j0);
+  P.B.jump[1] = (uint32_t *)(b + o_j1);
+  P.B.path = (uint32_t *)(b + o_path);
+  P.msize = (uint64_t *)(b + o_msize);
+  P.B.member_off = (uint64_t *)(b + o_moff);
+  P.B.out_off = (uint64_t *)(b + o_ooff);
+  FrameReadParams R{};
+  R.in = d_in;
+  R.in_off = P.B.cand_off;
+  R.in_end = P.cand_end;
+  R.n_streams = cap;
+  R.wrap = FLATE_HIP_WRAP_GZIP;
+  R.pay_off = (uint64_t *)(b + o_poff);
+  R.pay_end = (uint64_t *)(b + o_pend);
+  R.want = (uint32_t *)(b + o_want);
+  R.isize = (uint32_t *)(b + o_isize);
+  R.bad = (uint32_t *)(b + o_bad);
+  R.dict_used = (uint32_t *)(b + o_dict);
+  InfParams I{};  // size-only: no output buffer, no slots
+  I.in = d_in;
+  I.in_off = R.pay_off;
+  I.in_end = R.pay_end;
+  I.out_len = (uint64_t *)(b + o_olen);
+  I.status = (int32_t *)(b + o_st);
+  I.err_off = (int64_t *)(b + o_err);
+  I.n_streams = cap;
+  I.in_len = in_len;
+  I.size_only = 1u;
+  I.used = (uint64_t *)(b + o_used);
+  P.pay_off = R.pay_off;
+  P.bad = R.bad;
+  P.status = I.status;
+  P.out_len = I.out_len;
+  P.used = I.used;
+  // every candidate's range is at most member_max < 2^28 bytes: the sub-block decoder at any batch size, or -- switched
+  // off -- the scalar walk; both report `used`
+  const uint64_t longest = in_len < P.member_max ? in_len : P.member_max;
+  const InflateRoute route = inflate_route(c->inflate, c->num_cus, cap, longest, false, true);
+  if (route.decoder == kDecodeSimt) {
+    c->hip_err = "gzip discovery: a size-only pass was routed to the lane-per-stream decoder";
+    return FLATE_HIP_E_INTERNAL;
+  }
+  const uint32_t node_blocks = (uint32_t)(((uint64_t)cap + 2 + 255) / 256);
+  hipLaunchKernelGGL(gzip_fill_kernel, dim3(P.B.n_tiles), dim3(256), 0, c->stream, P);
+  hipLaunchKernelGGL(frame_parse_kernel, dim3((cap + 255) / 256), dim3(256), 0, c->stream, R);
+  HIP_TRY(c, hipGetLastError());
+  if ((rc = launch_decoders(c, route, I, false))) return rc;
+  hipLaunchKernelGGL(gzip_link_kernel, dim3(node_blocks), dim3(256), 0, c->stream, P);
+  for (uint32_t j = 0; j < rounds; ++j)
+    hipLaunchKernelGGL(bgzf_round_kernel, dim3(node_blocks), dim3(256), 0, c->stream, P.B, j);
+  hipLaunchKernelGGL(gzip_finish_kernel, dim3((P.B.path_len + 255) / 256), dim3(256), 0, c->stream, P);
+  hipLaunchKernelGGL(gzip_out_scan_kernel, dim3(1), dim3(1024), 0, c->stream, P);
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipMemcpyAsync(&H, P.B.head, sizeof H, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return FLATE_HIP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int flate_hip_gzip_index(flate_hip_ctx *c, const uint8_t *in, uint64_t in_len, uint64_t index_cap, uint64_t *member_off,
+                         uint64_t *out_off, uint32_t *n_members, uint64_t *out_bytes, uint32_t *n_candidates,
+                         int64_t *err_off, uint32_t flags) {
+  // every check before any HIP call
+  if (!c) return FLATE_HIP_E_INVALID;
+  int rc = gzip_index_args(in, in_len, member_off, out_off, n_members, out_bytes, flags);
+  if (rc) return rc;
+  c->hip_err.clear();
+  *n_members = 0, *out_bytes = 0;
+  if (n_candidates) *n_candidates = 0;
+  if (err_off) *err_off = -1;
+  if (in_len == 0) {
+    if (member_off && index_cap < 1) return FLATE_HIP_E_OUT_TOO_SMALL;
+    if (member_off) member_off[0] = 0, out_off[0] = 0;
+    return FLATE_HIP_OK;
+  }
+  const uint8_t *d_in = nullptr;
+  if ((rc = bgzf_stage(c, in, in_len, flags, &d_in))) return rc;
+  BgzfHead H{};
+  GzipParams P{};
+  if ((rc = gzip_discover(c, d_in, in_len, H, P))) return rc;
+  *n_members = H.n_members;
+  if (n_candidates) *n_candidates = H.n_cand;
+  if (err_off) *err_off = H.rc ? H.err_off : -1;
+  *out_bytes = H.out_bytes;  // (0 on a broken chain)
+  // the index -- of a broken chain its good prefix, if that fits: the verdict is the walk's either way
+  const uint64_t entries = (uint64_t)H.n_members + 1;
+  if (member_off && index_cap >= entries) {
+    if (P.B.member_off) {
+      HIP_TRY(c, hipMemcpyAsync(member_off, P.B.member_off, entries * 8, hipMemcpyDeviceToHost, c->stream));
+      HIP_TRY(c, hipMemcpyAsync(out_off, P.B.out_off, entries * 8, hipMemcpyDeviceToHost, c->stream));
+      HIP_TRY(c, hipStreamSynchronize(c->stream));
+    } else {  // (no candidate at all: zero members in front of offset 0)
+      member_off[0] = 0, out_off[0] = 0;
+    }
+  }
+  if (H.rc) return H.rc;
+  return member_off && index_cap < entries ? FLATE_HIP_E_OUT_TOO_SMALL : FLATE_HIP_OK;
+}
+
+int flate_hip_gzip_read(flate_hip_ctx *c, const uint8_t *in, uint64_t in_len, uint8_t *out, uint64_t out_cap,
+                        uint64_t *out_len, uint32_t *n_members, uint32_t *bad_member, int64_t *err_off, uint32_t flags) {
+  // every check before any HIP call
+  if (!c) return FLATE_HIP_E_INVALID;
+  int rc = gzip_read_args(in, in_len, out, out_cap, out_len, flags);
+  if (rc) return rc;
+  c->hip_err.clear();
+  *out_len = 0;
+  if (n_members) *n_members = 0;
+  if (bad_member) *bad_member = 0xffffffffu;
+  if (err_off) *err_off = -1;
+  if (in_len == 0) return FLATE_HIP_OK;
+  try {
+    const uint8_t *d_in = nullptr;
+    if ((rc = bgzf_stage(c, in, in_len, flags, &d_in))) return rc;
+    BgzfHead H{};
+    GzipParams P{};
+    if ((rc = gzip_discover(c, d_in, in_len, H, P))) return rc;
+    const uint32_t n = H.n_members;
+    if (n_members) *n_members = n;
+    if (H.rc) {  // a broken chain: nothing is decoded, nothing is written
+      if (bad_member) *bad_member = n;
+      if (err_off) *err_off = H.err_off;
+      return H.rc;
+    }
+    *out_len = H.out_bytes;
+    if (H.out_bytes > out_cap) return FLATE_HIP_E_OUT_TOO_SMALL;
+    return members_read(c, d_in, n, P.B.member_off, P.B.out_off, H.out_bytes, out, flags, bad_member, err_off);
   } catch (const std::exception &e) {  // (out of host memory in an index vector)
     c->hip_err = e.what();
     return FLATE_HIP_E_INTERNAL;

@@ -74,6 +74,12 @@ struct flate_hip_ctx {
   DevBuf d_bgzf_rng, d_bgzf_dense, d_in_end;
   // flate_hip_zip_write: the names and their offsets; flate_hip_zip_index / _read: the end record's words, the
   // discovery kernels' arrays (ZipDirParams) carved from one buffer, the selected entries and the stored pieces
+  // flate_hip_gzip_index / _read: the discovery kernels' arrays (GzipParams) and what the parse kernel and the size-only
+  // decode leave per candidate, carved from one buffer; in front of it (sized before the candidates are counted) the
+  // result words and the tiles' counts
+  DevBuf d_gzip, d_gzip_tiles;
+  // ... and the range a candidate is given at most (option "gzip_member_max": it can only be lowered)
+  uint64_t gzip_member_max = (1ull << 28) - 1;
   DevBuf d_zip_names, d_zip_name_off, d_zip_whead, d_zip_end, d_zip_dir, d_zip_sel;
   hipStream_t guest_stream = nullptr;
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;

@@ -161,6 +161,10 @@ struct InfParams {
   // members of a container (flate_hip_inflate_batch_framed): stream i is in[in_off[i], in_end[i]) -- its trailer
   // follows, and the next stream's header.  NULL: stream i ends at in_off[i + 1].  Independent streams only.
   const uint64_t *in_end;
+  // inflate_kernel, inflate_spec_kernel (what a size-only pass routes to): per stream, the bytes consumed from the
+  // stream's first byte up to and including the byte that holds the last bit of the final block; meaningful when the
+  // status is 0 (gzip member discovery: where the member's trailer starts).  NULL: not reported.
+  uint64_t *used;
 };
 
 __global__ void lz77_serial_kernel(LzParams P);
@@ -436,6 +440,33 @@ struct BgzfGatherParams {
 constexpr uint32_t kBgzfGatherWindow = 65536;
 constexpr uint32_t kBgzfGatherRangeCost = 256;
 __global__ void bgzf_gather_kernel(BgzfGatherParams P);
+
+// Plain multi-member gzip files (gzip_kernels.hip; flate_hip_gzip_index / _read): BGZF's discovery for members that do
+// not carry their size.  Every offset that passes the header rule (gzip_rule.h) over the range it is given -- in[p,
+// min(in_len, p + member_max)) -- is a CANDIDATE, compacted in file order (count per 4 KiB tile, bgzf_scan_kernel,
+// fill); frame_parse_kernel and ONE size-only launch of the batch decoders run over all candidates (InfParams::used);
+// gzip_link_kernel sends every candidate to the candidate at its end (in_len: the terminal node n_cand, nothing or a
+// failed decode: the dead node n_cand + 1); bgzf_round_kernel ranks the chain from candidate 0; gzip_finish_kernel and
+// gzip_out_scan_kernel turn the ranks into member_off / out_off and the walk's verdict (gzip_serial_walk).  B carries
+// what the two BGZF kernels read (head, cap, path_len, tile_cnt, jump, path) and the arrays of the same meaning;
+// B.cand_total and B.isize are unused.  B.cap is the exact candidate count: the host reads it back behind the scan.
+struct GzipParams {
+  BgzfParams B;
+  uint64_t member_max;     // option "gzip_member_max"
+  uint64_t *cand_end;      // cap: where candidate c's range ends; B.cand_off has cap + 1 entries (the last: in_len)
+  // what frame_parse_kernel and the decoders left, per candidate
+  const uint64_t *pay_off; // where the raw stream starts
+  const uint32_t *bad;     // (never 1: the candidates passed the same rule)
+  const int32_t *status;
+  const uint64_t *out_len;
+  const uint64_t *used;
+  uint64_t *msize;         // cap: per member of the chain, what it inflates to
+};
+__global__ void gzip_count_kernel(GzipParams P);
+__global__ void gzip_fill_kernel(GzipParams P);
+__global__ void gzip_link_kernel(GzipParams P);
+__global__ void gzip_finish_kernel(GzipParams P);
+__global__ void gzip_out_scan_kernel(GzipParams P);
 
 size_t inflate_simt_lds_bytes(int lanes_per_wave);  // dynamic LDS of that launch
 size_t inflate_simt_lens_bytes(uint32_t blocks);    // global scratch of that launch (InfParams::simt_lens)

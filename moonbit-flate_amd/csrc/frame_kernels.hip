@@ -26,6 +26,7 @@
 #include "block_scan.h"
 #include "flate_hip.h"
 #include "flate_kernels.h"
+#include "gzip_rule.h"
 
 namespace flate {
 
@@ -147,25 +148,10 @@ __global__ __launch_bounds__(256) void frame_parse_kernel(FrameReadParams P) {
   uint32_t used = FLATE_HIP_NO_DICT;
   if (P.wrap == FLATE_HIP_WRAP_GZIP) {
     // RFC 1952 2.3: ID1 ID2, CM = 8, the reserved FLG bits zero; FEXTRA, FNAME, FCOMMENT, FHCRC skipped in that order
+    // (the rule is gzip_rule.h's: member discovery tests every offset of a file with it)
     tl = frame_trailer_len(FLATE_HIP_WRAP_GZIP);
-    if (len >= frame_header_len(FLATE_HIP_WRAP_GZIP, false) && m[0] == 0x1f && m[1] == 0x8b && m[2] == 8 && (m[3] & 0xe0) == 0) {
-      const uint32_t flg = m[3];
-      uint64_t p = frame_header_len(FLATE_HIP_WRAP_GZIP, false);  // the fixed part
-      ok = true;
-      if (flg & 4u) {  // FEXTRA: XLEN, then that many bytes
-        if (len < p + 2) ok = false;
-        else p += 2u + (uint64_t)(m[p] | ((uint32_t)m[p + 1] << 8));
-      }
-      for (uint32_t bit = 8u; bit <= 16u && ok; bit <<= 1) {  // FNAME, FCOMMENT: zero-terminated
-        if (!(flg & bit)) continue;
-        while (p < len && m[p]) ++p;
-        if (p >= len) ok = false;
-        else ++p;
-      }
-      if (flg & 2u) p += 2;  // FHCRC
-      if (p > len) ok = false;
-      hl = p;
-    }
+    hl = gzip_header_len(m, len);
+    ok = hl != 0;
   } else {
     // RFC 1950 2.2: CM = 8, CINFO <= 7, FCHECK; FDICT: DICTID follows, and names the FIRST dictionary with that id
     tl = frame_trailer_len(FLATE_HIP_WRAP_ZLIB);

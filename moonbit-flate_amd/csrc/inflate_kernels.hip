@@ -561,6 +561,8 @@ FLATE_D void inflate_wave(const InfParams &P, InfShared &sh) {
     P.out_len[sid] = opos;
     P.status[sid] = err;
     P.err_off[sid] = err == E_CORRUPT ? (long long)b.roff : -1;
+    // (8 * roff - avail bits are consumed: the last of them closes the final block)
+    if (P.used) P.used[sid] = (8ull * b.roff - (uint64_t)b.avail + 7u) >> 3;
   }
 }
 

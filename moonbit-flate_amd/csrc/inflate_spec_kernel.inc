@@ -944,6 +944,8 @@ FLATE_D void inflate_spec(const InfParams &P, SpecShared<SUB, CAP, RING> &sh) {
     P.out_len[sid] = opos;
     P.status[sid] = err;
     P.err_off[sid] = err == E_CORRUPT ? (long long)(in_base + b.roff) : -1;
+    // (8 * roff - avail bits are consumed: the last of them closes the final block)
+    if (P.used) P.used[sid] = in_base + ((8ull * b.roff - (uint64_t)b.avail + 7u) >> 3);
   }
 }
 

@@ -56,6 +56,9 @@ BGZF_EOF = bytes.fromhex("1f8b08040000000000ff0600424302001b00030000000000000000
 BgzfIndex = collections.namedtuple("BgzfIndex", "rc n_members out_bytes eof_marker err_off member_off out_off")
 BgzfRead = collections.namedtuple("BgzfRead", "rc out_len n_members bad_member err_off eof_marker")
 BgzfRanges = collections.namedtuple("BgzfRanges", "rc out_off range_status n_members n_decoded bad_member err_off")
+GZIP_MEMBER_MAX = (1 << 28) - 1  # the option "gzip_member_max": its default and its maximum
+GzipIndex = collections.namedtuple("GzipIndex", "rc n_members out_bytes n_candidates err_off member_off out_off")
+GzipRead = collections.namedtuple("GzipRead", "rc out_len n_members bad_member err_off")
 
 
 def bgzf_bound(n, block_bytes=0):
@@ -522,6 +525,68 @@ class FlateEngine:
         if rc not in (0, E_OUT_TOO_SMALL, E_CORRUPT, E_UNEXPECTED_EOF):
             self._check(rc)
         return out, BgzfRead(rc, int(ol.value), int(nm.value), int(bad.value), int(eo.value), int(eof.value))
+
+    def gzip_index(self, data, index_cap=None, query=False):
+        """Where the members of a plain multi-member gzip file (cat a.gz b.gz, rotated logs, WARC records) start and
+        where their output goes, found on the GPU from the file's bytes (flate_hip_gzip_index) -> GzipIndex(rc,
+        n_members, out_bytes, n_candidates, err_off, member_off, out_off).  rc 0: member_off / out_off (numpy
+        uint64[n_members + 1]) are what inflate_batch_framed(..., "gzip") takes as in_off / the cumulative out_sizes.
+        A broken chain: rc -4 (no member can start at err_off), -7 (the stream at err_off is cut short) or -6 (the
+        member at err_off has more than "gzip_member_max" bytes, or inflates to 4 GiB or more), behind n_members good
+        ones, whose index the arrays still hold.  n_candidates: the offsets decoded speculatively.  query=True: only the
+        counts (the arrays are None); index_cap: the arrays' size (default: what a query says is needed; too small: rc
+        -2, the arrays None).  Other failures raise FlateError."""
+        data, in_ptr, n, device = self._bgzf_in(data)
+        flags = DEVICE_PTRS if device else 0
+        nm, ob, nc, eo = C.c_uint32(0), C.c_uint64(0), C.c_uint32(0), C.c_int64(-1)
+
+        def call(cap, a, b):
+            rc = self._L.flate_hip_gzip_index(self._ctx, in_ptr, n, cap, a, b, C.byref(nm), C.byref(ob), C.byref(nc),
+                                              C.byref(eo), flags)
+            if rc not in (0, E_CORRUPT, E_UNEXPECTED_EOF, E_TOO_LARGE, E_OUT_TOO_SMALL):
+                self._check(rc)
+            return rc
+
+        if query or index_cap is None:
+            rc = call(0, None, None)
+            if query:
+                return GzipIndex(rc, int(nm.value), int(ob.value), int(nc.value), int(eo.value), None, None)
+            index_cap = int(nm.value) + 1
+        moff = np.zeros(max(int(index_cap), 1), dtype=np.uint64)
+        ooff = np.zeros(max(int(index_cap), 1), dtype=np.uint64)
+        rc = call(int(index_cap), moff.ctypes.data, ooff.ctypes.data)
+        k = int(nm.value) + 1
+        fits = k <= int(index_cap)
+        return GzipIndex(rc, int(nm.value), int(ob.value), int(nc.value), int(eo.value),
+                         moff[:k] if fits else None, ooff[:k] if fits else None)
+
+    def gzip_read(self, data, out=None, out_cap=None):
+        """A plain multi-member gzip file back into its bytes by one call (flate_hip_gzip_read): member discovery,
+        decode and the check of every member's CRC-32 and ISIZE on the GPU, no side index.  Returns (out, GzipRead(rc,
+        out_len, n_members, bad_member, err_off)); the bytes are out[:out_len] (numpy for host data, a torch CUDA tensor
+        for device data).  rc 0; a broken chain (bad_member == n_members): gzip_index's rc at err_off, nothing decoded;
+        otherwise the first failing member's status (-4 CRC or ISIZE, -2 more output than the slot) with its index and
+        file offset, all other members delivered; -2 with out_len > capacity: out too small, nothing decoded.
+        out=None: sized by a query of the index first.  Other failures raise FlateError."""
+        data, in_ptr, n, device = self._bgzf_in(data)
+        if out is None:
+            need = self.gzip_index(data, query=True).out_bytes
+            if device:
+                import torch
+                out = torch.empty(max(need, 16), dtype=torch.uint8, device=data.device)
+            else:
+                out = np.zeros(max(need, 16), dtype=np.uint8)
+        else:
+            _check_out(out, data, 0, "gzip_read")
+        room = out.numel() if device else out.size
+        cap = room if out_cap is None else min(int(out_cap), room)
+        out_ptr = out.data_ptr() if device else out.ctypes.data
+        ol, nm, bad, eo = C.c_uint64(0), C.c_uint32(0), C.c_uint32(0), C.c_int64(-1)
+        rc = self._L.flate_hip_gzip_read(self._ctx, in_ptr, n, out_ptr, cap, C.byref(ol), C.byref(nm), C.byref(bad),
+                                         C.byref(eo), DEVICE_PTRS if device else 0)
+        if rc not in (0, E_OUT_TOO_SMALL, E_CORRUPT, E_UNEXPECTED_EOF, E_TOO_LARGE):
+            self._check(rc)
+        return out, GzipRead(rc, int(ol.value), int(nm.value), int(bad.value), int(eo.value))
 
     def bgzf_read_ranges(self, data, begin, end, virtual=False, out=None, out_cap=None):
         """Random access into a BGZF file (flate_hip_bgzf_read_ranges): the bytes of the ranges [begin[r], end[r]) --

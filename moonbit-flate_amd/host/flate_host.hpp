@@ -901,6 +901,45 @@ inline Err decompress_bgzf(Engine &e, const std::vector<uint8_t> &file, std::vec
   return make_error(e, rc);
 }
 
+// ---- plain multi-member gzip files (cat a.gz b.gz, rotated logs, WARC records) ----------------
+// What decompress_gzip found beside the bytes.
+struct GzipInfo {
+  uint32_t n_members = 0;
+  uint32_t bad_member = 0xffffffffu;  // the first failing member, or (a broken chain) the count of good ones
+  int64_t err_off = -1;               // its file offset, or where the chain broke
+  uint32_t n_candidates = 0;          // offsets that were decoded speculatively
+  int status = 0;                     // the FLATE_HIP_E_* code behind the error (0 = none)
+};
+
+// decompress_gzip: a .gz file of any number of members back into its bytes: member discovery, decoding and the check of
+// every member's CRC-32 and ISIZE on the GPU (flate_hip_gzip_index for the size, flate_hip_gzip_read for the bytes); no
+// side index.  Errors: a broken chain is corrupt_input_error(where no member can start), err_unexpected_eof (the last
+// member is cut short) or FLATE_HIP_E_TOO_LARGE (a member beyond the option "gzip_member_max"), `out` empty; a failing
+// member is corrupt_input_error(its file offset) -- `out` then still holds every other member's bytes.
+inline Err decompress_gzip(Engine &e, const std::vector<uint8_t> &file, std::vector<uint8_t> &out, GzipInfo *info = nullptr) {
+  if (!e.ok()) return make_error(e, e.status());
+  GzipInfo I;
+  uint64_t need = 0, len = 0;
+  int rc = flate_hip_gzip_index(e.ctx(), file.data(), file.size(), 0, nullptr, nullptr, &I.n_members, &need,
+                                &I.n_candidates, &I.err_off, 0);
+  out.clear();
+  if (rc == 0) {
+    std::vector<uint8_t> buf(need + 8);
+    rc = flate_hip_gzip_read(e.ctx(), file.data(), file.size(), buf.data(), need, &len, &I.n_members, &I.bad_member,
+                             &I.err_off, 0);
+    if (rc == 0 || rc == FLATE_HIP_E_CORRUPT || rc == FLATE_HIP_E_UNEXPECTED_EOF || rc == FLATE_HIP_E_OUT_TOO_SMALL)
+      out.assign(buf.begin(), buf.begin() + std::min(len, need));
+  } else if (rc == FLATE_HIP_E_CORRUPT || rc == FLATE_HIP_E_UNEXPECTED_EOF || rc == FLATE_HIP_E_TOO_LARGE) {
+    I.bad_member = I.n_members;
+  }
+  I.status = rc;
+  if (info) *info = I;
+  if (rc == 0) return std::nullopt;
+  if (rc == FLATE_HIP_E_CORRUPT) return corrupt_input_error(I.err_off);
+  if (rc == FLATE_HIP_E_UNEXPECTED_EOF) return err_unexpected_eof();
+  return make_error(e, rc);
+}
+
 // One range of decompress_bgzf_ranges: positions in the file's uncompressed bytes, or -- virtual_offsets -- BGZF
 // virtual offsets (coffset << 16 | uoffset, as BAM, tabix and CSI indexes store them).
 struct BgzfRange {
