@@ -126,6 +126,13 @@ inline EncodeRoute encode_route(const StagePlan &pl, const EncodeOpts &o, uint32
   return r;
 }
 
+// Which build of the match-finder kernels a batch launch takes.  The test hooks (options "debug_stall_batch" and
+// "debug_drop_window_push": flate_hip_ctx::inject_stall / inject_drop_push) exist only in the kernels' HOOKS
+// instantiations; a call with neither option set runs the product instantiations, whose batch loop carries no hook.
+inline bool lz77_hooks_build(uint32_t inject_stall, uint32_t inject_drop_push) {
+  return inject_stall != 0 || inject_drop_push != 0;
+}
+
 // The groups a host-pointer batch of n streams is cut into (host_groups / host_group_streams: the options
 // "host_pipeline_groups" / "host_pipeline_group_streams"); 0 or 1: one pass.  Host pointers and a batch large enough
 // that every group still fills the persistent launch (a group of 4096 64-KiB streams still runs at 80 %).

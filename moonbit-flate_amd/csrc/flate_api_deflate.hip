@@ -167,6 +167,7 @@ int run_lz77(flate_hip_ctx *c, const uint8_t *d_in, const uint64_t *in_off, cons
   P.chunk_base = (const uint32_t *)c->d_chunk_base.p;
   P.inject_drop_push = c->inject_drop_push;  // (the test hooks act on batch launches only)
   P.inject_stall = c->inject_stall;
+  const bool hooks = lz77_hooks_build(c->inject_stall, c->inject_drop_push);  // only the HOOKS builds read the two
   c->last_count[0] = c->last_count[1] = 0;
   // multi-window streams of a persistent launch run one window at a time (EncodeRoute::uq_units) -- the one launch
   // decision the route does not settle: no memory for the scratch is whole-stream scheduling as well
@@ -224,7 +225,10 @@ int run_lz77(flate_hip_ctx *c, const uint8_t *d_in, const uint64_t *in_off, cons
       auto launch = [&](const DevBuf &ids, uint32_t count, bool multi, uint32_t queue_slot, bool pair) {
         if (!count) return;
         P.stream_ids = (const uint32_t *)ids.p;
-        void (*wave)(LzParams) = multi ? lz77_wave_kernel<true> : lz77_wave_kernel<false>;
+        void (*wave)(LzParams) = hooks ? (multi ? lz77_wave_kernel<true, true> : lz77_wave_kernel<false, true>)
+                                       : (multi ? lz77_wave_kernel<true, false> : lz77_wave_kernel<false, false>);
+        void (*guest)(LzParams) = hooks ? (multi ? lz77_guest_kernel<true, true> : lz77_guest_kernel<false, true>)
+                                        : (multi ? lz77_guest_kernel<true, false> : lz77_guest_kernel<false, false>);
         if (!pair) {
           hipLaunchKernelGGL(wave, dim3(count), dim3(64), 0, c->stream, P);
           return;
@@ -251,7 +255,7 @@ int run_lz77(flate_hip_ctx *c, const uint8_t *d_in, const uint64_t *in_off, cons
           G.stream_ids = P.stream_ids + c->enc.profile_split;
           G.queue_end = count - c->enc.profile_split;
         }
-        launch_pair(c, wave, multi ? lz77_guest_kernel<true> : lz77_guest_kernel<false>, count, R, G);
+        launch_pair(c, wave, guest, count, R, G);
       };
       launch(c->d_ids16, (uint32_t)pl.ids16.size(), false, 0, rt.pair16);
       launch(c->d_ids32, (uint32_t)pl.ids32.size(), true, 1, rt.pair32);
@@ -263,11 +267,13 @@ int run_lz77(flate_hip_ctx *c, const uint8_t *d_in, const uint64_t *in_off, cons
         Q.stream_ids = (const uint32_t *)c->d_idsD.p;
         Q.win0 = 1;
         hipLaunchKernelGGL(lz77_dict_prime_kernel, dim3(DD->n_slots), dim3(64), 0, c->stream, Q, DD->dev);
+        void (*wave_d)(LzParams, LzDictParams) = hooks ? lz77_wave_dict_kernel<true> : lz77_wave_dict_kernel<false>;
+        void (*guest_d)(LzParams, LzDictParams) = hooks ? lz77_guest_dict_kernel<true> : lz77_guest_dict_kernel<false>;
         if (!rt.pairD) {
-          hipLaunchKernelGGL(lz77_wave_dict_kernel, dim3(count), dim3(64), 0, c->stream, Q, DD->dev);
+          hipLaunchKernelGGL(wave_d, dim3(count), dim3(64), 0, c->stream, Q, DD->dev);
         } else {
           Q = queued(Q, 8, count);
-          launch_pair(c, lz77_wave_dict_kernel, lz77_guest_dict_kernel, count, Q, Q, DD->dev);
+          launch_pair(c, wave_d, guest_d, count, Q, Q, DD->dev);
         }
       }
     }

@@ -168,9 +168,10 @@ struct InfParams {
 };
 
 __global__ void lz77_serial_kernel(LzParams P);
-template <bool MULTI>
+// HOOKS: the build that carries the test hooks (inject_stall, inject_drop_push); see lz77_hooks_build, deflate_plan.h
+template <bool MULTI, bool HOOKS>
 __global__ void lz77_wave_kernel(LzParams P);
-template <bool MULTI>
+template <bool MULTI, bool HOOKS>
 __global__ void lz77_guest_kernel(LzParams P);
 // one stream continued from an earlier launch: table and sweep clock come from / go back to `table_io`,
 // `clock_io`; runs the nwin windows from P.win0 on
@@ -182,7 +183,9 @@ __global__ void lz77_resume_kernel(LzParams P, uint16_t *table_io, uint32_t *clo
                                    uint32_t rebase, uint32_t forget);
 // preset dictionaries: one block per slot primes its table; the stream kernels' dictionary builds (P.win0 = 1)
 __global__ void lz77_dict_prime_kernel(LzParams P, LzDictParams DP);
+template <bool HOOKS>
 __global__ void lz77_wave_dict_kernel(LzParams P, LzDictParams DP);
+template <bool HOOKS>
 __global__ void lz77_guest_dict_kernel(LzParams P, LzDictParams DP);
 __global__ void huff_hist_kernel(HuffParams P);
 __global__ void huff_code_kernel(HuffParams P);

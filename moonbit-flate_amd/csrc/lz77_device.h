@@ -29,9 +29,12 @@ static_assert(kDenseKeep >= 0 && kDenseKeep <= 61, "an event must start at a lan
 #endif
 constexpr uint32_t kSweepEvery = FLATE_LZ_SWEEP_EVERY, kSpanMax = FLATE_LZ_SPAN_MAX, kMarkerBack = FLATE_LZ_MARKER_BACK;
 // A sweep at R leaves no slot older than 32768 and writes dead slots as "kMarkerBack behind R".  Until the next sweep a
-// lookup comes from at most R + kSweepEvery + one batch (64 positions dense, kSpanMax sparse): the marker must read as
-// out of range (> 32768) and every distance, the marker's included, must stay below 2^16 to be told apart.
-static_assert(kMarkerBack > 32768u && kSweepEvery + kSpanMax + 64u + kMarkerBack < 65536u && kSpanMax >= 64u,
+// lookup comes from at most R + kSweepEvery + one batch: the marker must read as out of range (> 32768) and every
+// distance, the marker's included, must stay below 2^16 to be told apart.  The batch's worst case: the sweep is due
+// at the first position of a batch, and the batch before it may have started one short of the clock and ended with
+// a match of 258 bytes found at its last lane (+ 64 + 258); an interior dense batch probes up to B + 65 (+ 66 with
+// its own base), a sparse one spans kSpanMax.  The A/B overrides above can be set right up to this limit.
+static_assert(kMarkerBack > 32768u && kSweepEvery + kSpanMax + 66u + 258u + kMarkerBack < 65536u && kSpanMax >= 64u,
               "16-bit modular table slots: sweep period + batch span + marker distance must stay below 2^16");
 
 FLATE_D uint32_t ld32(const uint8_t *p) {

@@ -216,9 +216,12 @@ FLATE_D void tag_set(uint32_t *tags, uint32_t h, uint32_t t) {
 //     [65535 - D, 65535) from an empty table -- DeflateFast::encode(d) with the tokens dropped -- and leaves the
 //     table and the sweep clock for the streams that use it.  The first sweep is due kSweepEvery behind the START
 //     of the tail, and the empty table's markers are kMarkerBack in front of it: the static_assert on
-//     kSweepEvery + kSpanMax + 64 + kMarkerBack holds for a parser that starts anywhere.
+//     kSweepEvery + kSpanMax + 66 + 258 + kMarkerBack holds for a parser that starts anywhere.
 constexpr int kLzDictStream = 1, kLzDictPrime = 2;
-template <bool MULTI, bool GUEST = false, int DMODE = 0>
+// HOOKS: the build with the test hooks (options debug_stall_batch, debug_drop_window_push).  The product
+// instantiations carry none of them: run_lz77 launches a HOOKS build only when one of the options is set
+// (lz77_hooks_build, deflate_plan.h).
+template <bool MULTI, bool GUEST = false, int DMODE = 0, bool HOOKS = false>
 FLATE_D void lz77_stream(const LzParams &P, const uint32_t sid, uint16_t *table, const int lane,
                          const uint32_t c_begin = 0, const uint32_t c_end = 0xffffffffu,
                          uint32_t *sweep_io = nullptr, uint32_t *tags = nullptr,
@@ -287,7 +290,7 @@ FLATE_D void lz77_stream(const LzParams &P, const uint32_t sid, uint16_t *table,
   }
   hist.stream = g.stream;
   const uint16_t *scan_tab = P.scan_off;
-  uint32_t pf_val = 0, pf_sink = 0;
+  uint32_t pf_sink = 0;  // the last look-ahead load's word
 #ifdef FLATE_LZ_FINISH  // diagnostic build: when did this stream start and end, on which block (100 MHz clock)
   const uint64_t fin_t0 = __builtin_amdgcn_s_memrealtime();
 #endif
@@ -311,6 +314,7 @@ FLATE_D void lz77_stream(const LzParams &P, const uint32_t sid, uint16_t *table,
     bool done = false;
     uint4 own_pre = make_uint4(0, 0, 0, 0);  // input bytes of the next dense batch, loaded early
     bool pre_valid = false;
+    int pf_blk = -2;  // the 256-byte block (of B) whose look-ahead load was issued last; B >= -2, so B >> 8 >= -1
 #ifdef FLATE_LZ_STAMPS
     uint64_t st_load = 0, st_dup = 0, st_ev = 0, st_commit = 0, st_sparse = 0, st_nb = 0, st_ext = 0;
 #endif
@@ -322,15 +326,25 @@ FLATE_D void lz77_stream(const LzParams &P, const uint32_t sid, uint16_t *table,
     // Progress guard: every batch moves the parser (a dense batch raises s or turns sparse, a sparse batch raises
     // e_idx or finds a match) or ends the chunk.  A batch that leaves all of it where it was would repeat for ever
     // (the kDenseKeep = 62 build of round 5 did): the chunk is abandoned and the call ends FLATE_HIP_E_INTERNAL.
-    int g_s = -2, g_e = -1;
-    bool g_sp = false;
-    uint32_t g_nb = 0;
+    // The test is each batch kind's own: a dense batch must not end with s where it found it unless it turned sparse
+    // or ended the chunk (`moved`: one scalar compare per batch, looked at before the next batch starts); a sparse
+    // batch that goes on adds nexist to e_idx, and nexist >= 1 there (lane 0 is inside the span, so nall >= 1 gives
+    // nexist >= 1): one compare on that path.  tests/host_model/lz77_guard_model.cpp restates both rules.
+    // (`moved` tested at the loop's head and s0 taken outside the batch is the form that keeps the single-window
+    // kernels at 85 / 91 VGPRs; the same test at the end of the batch body came out at 90 / 91.)
+    auto no_progress = [&]() {
+      if (lane == 0) atomicExch(P.status, kStatusNoProgress);
+      done = true;
+    };
+    uint32_t h_nb = 0, h_acc = 0;  // HOOKS: dense batches so far; the lengths and e_idx as the batch found them
+    int h_e = 0;
+    bool moved = true;
     while (!done) {
-      if (s == g_s && e_idx == g_e && sparse == g_sp) {
-        if (lane == 0) atomicExch(P.status, kStatusNoProgress);
+      if (!moved) {
+        no_progress();
         break;
       }
-      g_s = s, g_e = e_idx, g_sp = sparse;
+      if constexpr (HOOKS) h_acc = acc_len, h_e = e_idx;
       if (!sparse) {
         // =============================== dense batch ===============================
         auto dense_batch = [&](auto interior_tag) {
@@ -351,7 +365,6 @@ FLATE_D void lz77_stream(const LzParams &P, const uint32_t sid, uint16_t *table,
         uint4 own = make_uint4(0, 0, 0, 0);
         uint32_t h = 0, old = 0;
         bool maybe = false;  // my slot may hold a position with my four bytes
-        pf_sink ^= pf_val;  // retire the previous batch's look-ahead load
         if (e1) {
           own = pre_valid ? own_pre : ld128(src + q);
           h = hash4(own.x);
@@ -365,11 +378,16 @@ FLATE_D void lz77_stream(const LzParams &P, const uint32_t sid, uint16_t *table,
         const uint32_t cand_abs = A1 - 1u - dist;
         uint4 cb = own;
         if (inr) cb = hist.w128(cand_abs);
-        {  // look-ahead: pull the next lines of this stream towards L2.  Issued after the
-           // candidate gather so that no wait of this batch has to include it.
-          int pq = B + 768 + 4 * lane;
+        // look-ahead: pull the next lines of this stream towards L2.  Issued after the candidate gather so that
+        // no wait of this batch has to include it, and once per 256-byte block of the window -- the batch whose base
+        // is the first inside block k asks for block k + 4, at least 768 bytes ahead -- not once per batch: a batch
+        // moves on by about 58 bytes, and every line was asked for four times.  The loaded word is only kept (see
+        // pf_sink at the end of the chunk): nothing waits for it and a batch that issues no load retires none.
+        if ((B >> 8) != pf_blk) {  // (wave-uniform; pf_blk starts below every block: a chunk's first batch issues)
+          pf_blk = B >> 8;
+          int pq = (B & ~255) + 1024 + 4 * lane;
           if (pq > n - 4) pq = n - 4;
-          pf_val = ld32(src + pq);
+          pf_sink = ld32(src + pq);
         }
         // DUPall: every lane that shares its slot with another lane of the batch (the commit
         // below must order their writes).  DUP: the lanes whose candidate may be a position
@@ -614,6 +632,16 @@ FLATE_D void lz77_stream(const LzParams &P, const uint32_t sid, uint16_t *table,
         }
         M |= MF;
         INS |= fast_inserts(VISall);
+        // (test hook, option debug_stall_batch: the k-th dense batch of a chunk forgets what it did -- the parser is
+        // exactly as the batch found it, records, lengths and inserts included, so the guard ends the chunk and the
+        // call fails; nothing is written twice)
+        if constexpr (HOOKS) {
+          if (P.inject_stall != 0 && ++h_nb == P.inject_stall) {
+            s = B + 1, e_idx = h_e, sparse = false, done = false;
+            acc_len = h_acc;
+            M = MF = INS = 0;
+          }
+        }
         STAMP(t3);
         // the next dense batch starts at s - 1: issue its input load now so that its latency
         // overlaps the record store and the table commit below
@@ -663,12 +691,12 @@ FLATE_D void lz77_stream(const LzParams &P, const uint32_t sid, uint16_t *table,
         st_nb += 1;
 #endif
         };
+        const int s0 = s;
         if (s - 1 >= 0 && s - 1 + 65 <= s_limit)
           dense_batch(std::true_type{});
         else
           dense_batch(std::false_type{});
-        // (test hook, option debug_stall_batch: the k-th dense batch of a chunk forgets what it did)
-        if (P.inject_stall != 0 && ++g_nb == P.inject_stall) s = g_s, sparse = false, done = false, pre_valid = false;
+        moved = (s != s0) | sparse | done;  // the guard's dense half
       } else {
         // =============================== sparse batch ==============================
         const int e = e_idx + lane;
@@ -761,6 +789,10 @@ FLATE_D void lz77_stream(const LzParams &P, const uint32_t sid, uint16_t *table,
         }
         if (f == 64) {
           if (nexist == nall && nall < 64) break;  // the scan ran into s_limit
+          if (nexist == 0) {  // (the guard's sparse half: going on must raise e_idx)
+            no_progress();
+            break;
+          }
           e_idx += nexist;
           continue;
         }
@@ -831,6 +863,7 @@ struct UqUnit {
 // Pop the next unit: a ticket from the head counter, then wait until the unit with that ticket
 // has been pushed (its producer is a block that is running a window right now, so the wait is
 // bounded by one window time; a bounded spin turns anything else into an error, not a hang).
+template <bool HOOKS>
 FLATE_D UqUnit uq_pop(const LzParams &P, const uint32_t push_word, int lane) {
   // One lane-0 block per loop iteration: publish the window this block has just finished with
   // (push_word: 0 = nothing, bit 31 = that stream is complete, else the next window's ready word; its payload was stored write-through and drained by every storing lane, the
@@ -841,9 +874,11 @@ FLATE_D UqUnit uq_pop(const LzParams &P, const uint32_t push_word, int lane) {
   if (lane == 0) {
     if (push_word != 0 && !(push_word & 0x80000000u)) {  // (bit 31: the previous unit was its stream's last window)
       const uint32_t k = __hip_atomic_fetch_add(P.uq_ctr + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      // (test hook: option debug_drop_window_push loses one hand-over, so that the bounded wait
-      // below can be shown to end in an error code and not in a hang)
-      if (k + 1u - P.queue_end != P.inject_drop_push)
+      // (test hook, HOOKS builds: option debug_drop_window_push loses one hand-over, so that the bounded
+      // wait below can be shown to end in an error code and not in a hang)
+      bool dropped = false;
+      if constexpr (HOOKS) dropped = k + 1u - P.queue_end == P.inject_drop_push;
+      if (!dropped)
         __hip_atomic_store(P.uq_ready + k, push_word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     t = __hip_atomic_fetch_add(P.uq_ctr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -891,7 +926,7 @@ __global__ void uq_init_kernel(uint32_t *ready, uint32_t *ctr, uint32_t n_stream
 // (table, sweep clock) is stored and loaded with agent-scope relaxed atomics -- `sc1` accesses that
 // go past L1 and are written through L2 -- every storing lane drains its stores, then one lane
 // publishes the ready word; the consumer polls that word and acquires once (uq_pop).
-template <bool GUEST>
+template <bool GUEST, bool HOOKS>
 FLATE_D uint32_t uq_run(const LzParams &P, const UqUnit u, uint16_t *table, int lane, uint32_t *tags = nullptr) {
   // (wave-uniform values made scalar explicitly: with a per-lane `nch` the branch around the push
   // below is divergent for the compiler, which then peels lane 0 off the unit loop)
@@ -947,7 +982,7 @@ FLATE_D uint32_t uq_run(const LzParams &P, const UqUnit u, uint16_t *table, int 
   }
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
   __syncthreads();
-  lz77_stream<true, GUEST>(P, sid, table, lane, u.c, u.c + 1, &clock, tags);
+  lz77_stream<true, GUEST, 0, HOOKS>(P, sid, table, lane, u.c, u.c + 1, &clock, tags);
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
   __syncthreads();
   if (u.c + 1 < nch) {
@@ -1016,7 +1051,7 @@ FLATE_D void dict_snapshot_load(const LzDictParams &DP, uint32_t sid, uint16_t *
 
 // Whole streams: one block per stream (P.queue == null, LDS-table kernels only) or persistent -- resident and
 // guest blocks share one queue (dynamic balance).  One call site keeps a single copy of the parser.
-template <bool MULTI, bool GUEST, bool DICT, bool COUNT>
+template <bool MULTI, bool GUEST, bool DICT, bool COUNT, bool HOOKS>
 FLATE_D void stream_loop(const LzParams P, uint16_t *table, uint32_t *tags, const LzDictParams *DP, int lane) {
   uint32_t mine = 0;  // streams taken
   for (bool first = true;; first = false) {
@@ -1035,10 +1070,10 @@ FLATE_D void stream_loop(const LzParams P, uint16_t *table, uint32_t *tags, cons
       const uint32_t sid = (uint32_t)__builtin_amdgcn_readfirstlane((int)P.stream_ids[q]);
       uint32_t clock = 0;
       dict_snapshot_load(*DP, sid, table, &clock, lane);
-      lz77_stream<true, GUEST, kLzDictStream>(P, sid, table, lane, 1, 0xffffffffu, &clock, nullptr, DP);
+      lz77_stream<true, GUEST, kLzDictStream, HOOKS>(P, sid, table, lane, 1, 0xffffffffu, &clock, nullptr, DP);
     } else {
-      lz77_stream<MULTI, GUEST>(P, (GUEST || P.stream_ids) ? P.stream_ids[q] : q, table, lane, 0, 0xffffffffu, nullptr,
-                                tags);
+      lz77_stream<MULTI, GUEST, 0, HOOKS>(P, (GUEST || P.stream_ids) ? P.stream_ids[q] : q, table, lane, 0, 0xffffffffu,
+                                          nullptr, tags);
     }
     __syncthreads();
     all_lanes_here(P, lane);
@@ -1048,14 +1083,14 @@ FLATE_D void stream_loop(const LzParams P, uint16_t *table, uint32_t *tags, cons
 }
 
 // Window units of multi-window streams (persistent launches with P.uq_ready): one window at a time, see uq_run.
-template <bool GUEST, bool COUNT>
+template <bool GUEST, bool COUNT, bool HOOKS>
 FLATE_D void unit_loop(const LzParams P, uint16_t *table, uint32_t *tags, int lane) {
   uint32_t push_word = 0;
   uint32_t mine = 0;  // units taken
   for (;;) {
-    const UqUnit u = uq_pop(P, push_word, lane);
+    const UqUnit u = uq_pop<HOOKS>(P, push_word, lane);
     if (__builtin_amdgcn_readfirstlane((int)u.ok) == 0) break;
-    push_word = (uint32_t)__builtin_amdgcn_readfirstlane((int)uq_run<GUEST>(P, u, table, lane, tags));
+    push_word = (uint32_t)__builtin_amdgcn_readfirstlane((int)uq_run<GUEST, HOOKS>(P, u, table, lane, tags));
     all_lanes_here(P, lane);
     if (COUNT) ++mine;
   }
@@ -1063,13 +1098,13 @@ FLATE_D void unit_loop(const LzParams P, uint16_t *table, uint32_t *tags, int la
 }
 
 // Resident kernel: table in LDS (32 KiB per stream => 5 streams per CU).
-template <bool MULTI>
+template <bool MULTI, bool HOOKS>
 __global__ __launch_bounds__(64) void lz77_wave_kernel(LzParams P) {
   __shared__ uint16_t table[kTableSize];
   if (MULTI && P.uq_ready)
-    unit_loop<false, true>(P, table, nullptr, threadIdx.x);
+    unit_loop<false, true, HOOKS>(P, table, nullptr, threadIdx.x);
   else
-    stream_loop<MULTI, false, false, true>(P, table, nullptr, nullptr, threadIdx.x);
+    stream_loop<MULTI, false, false, true, HOOKS>(P, table, nullptr, nullptr, threadIdx.x);
 }
 
 // Guest kernel: the LDS of a CU holds only five 32 KiB tables, but its SIMDs are mostly idle
@@ -1080,7 +1115,7 @@ FLATE_D uint16_t *guest_table(const LzParams &P) {  // (gtables holds one table 
   return reinterpret_cast<uint16_t *>(P.gtables) + (size_t)blockIdx.x * kTableSize;
 }
 
-template <bool MULTI>
+template <bool MULTI, bool HOOKS>
 __global__ __launch_bounds__(64) void lz77_guest_kernel(LzParams P) {
   if (blockIdx.x >= P.gtable_blocks) return;
   // (round 2 gave multi-window guests no tags: -7 % with them at equal geometry, but the window
@@ -1090,21 +1125,23 @@ __global__ __launch_bounds__(64) void lz77_guest_kernel(LzParams P) {
   uint16_t *table = guest_table(P);
   const int lane = threadIdx.x;
   if (MULTI && P.uq_ready) {
-    unit_loop<true, false>(P, table, tags, lane);
+    unit_loop<true, false, HOOKS>(P, table, tags, lane);
     return;
   }
-  stream_loop<MULTI, true, false, false>(P, table, tags, nullptr, lane);
+  stream_loop<MULTI, true, false, false, HOOKS>(P, table, tags, nullptr, lane);
 }
 
 // The dictionary builds: one block per stream (P.queue == null) or persistent, as lz77_wave_kernel
+template <bool HOOKS>
 __global__ __launch_bounds__(64) void lz77_wave_dict_kernel(LzParams P, LzDictParams DP) {
   __shared__ uint16_t table[kTableSize];
-  stream_loop<true, false, true, false>(P, table, nullptr, &DP, threadIdx.x);
+  stream_loop<true, false, true, false, HOOKS>(P, table, nullptr, &DP, threadIdx.x);
 }
 
+template <bool HOOKS>
 __global__ __launch_bounds__(64) void lz77_guest_dict_kernel(LzParams P, LzDictParams DP) {
   if (blockIdx.x >= P.gtable_blocks) return;
-  stream_loop<true, true, true, false>(P, guest_table(P), nullptr, &DP, threadIdx.x);
+  stream_loop<true, true, true, false, HOOKS>(P, guest_table(P), nullptr, &DP, threadIdx.x);
 }
 
 __global__ __launch_bounds__(64) void lz77_dict_prime_kernel(LzParams P, LzDictParams DP) {
@@ -1162,9 +1199,18 @@ __global__ __launch_bounds__(64) void lz77_resume_kernel(LzParams P, uint16_t *t
   if (lane == 0) *clock_io = clock;
 }
 
-template __global__ void lz77_wave_kernel<false>(LzParams);
-template __global__ void lz77_wave_kernel<true>(LzParams);
-template __global__ void lz77_guest_kernel<false>(LzParams);
-template __global__ void lz77_guest_kernel<true>(LzParams);
+// (MULTI, HOOKS): the product instantiations and, for the calls that set a test hook, their HOOKS builds
+template __global__ void lz77_wave_kernel<false, false>(LzParams);
+template __global__ void lz77_wave_kernel<true, false>(LzParams);
+template __global__ void lz77_guest_kernel<false, false>(LzParams);
+template __global__ void lz77_guest_kernel<true, false>(LzParams);
+template __global__ void lz77_wave_dict_kernel<false>(LzParams, LzDictParams);
+template __global__ void lz77_guest_dict_kernel<false>(LzParams, LzDictParams);
+template __global__ void lz77_wave_kernel<false, true>(LzParams);
+template __global__ void lz77_wave_kernel<true, true>(LzParams);
+template __global__ void lz77_guest_kernel<false, true>(LzParams);
+template __global__ void lz77_guest_kernel<true, true>(LzParams);
+template __global__ void lz77_wave_dict_kernel<true>(LzParams, LzDictParams);
+template __global__ void lz77_guest_dict_kernel<true>(LzParams, LzDictParams);
 
 }  // namespace flate
