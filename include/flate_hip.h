@@ -676,7 +676,9 @@ int flate_hip_bgzf_read_ranges(flate_hip_ctx *ctx, const uint8_t *in, uint64_t i
  * p: FLATE_HIP_E_CORRUPT, *err_off = p.  s != 0: the walk ends with *err_off = p and s -- FLATE_HIP_E_CORRUPT,
  * FLATE_HIP_E_UNEXPECTED_EOF, or FLATE_HIP_E_TOO_LARGE for a member that inflates to 4 GiB or more -- except that
  * FLATE_HIP_E_UNEXPECTED_EOF in a range that M clipped (p + M < in_len) is FLATE_HIP_E_TOO_LARGE: such a member is read
- * with flate_hip_inflate_stream_read.  Otherwise p = e.  The file must end exactly where a member ends: padding or
+ * with flate_hip_inflate_one, which decodes a single long member in parallel, or in pieces with
+ * flate_hip_inflate_stream_read.
+ * Otherwise p = e.  The file must end exactly where a member ends: padding or
  * garbage behind the last member, zero bytes included, is FLATE_HIP_E_CORRUPT at its offset.
  *
  * flate_hip_gzip_index has flate_hip_bgzf_index's conventions.  On success member_off[0 .. n] (member_off[n] = in_len)
@@ -723,6 +725,91 @@ int flate_hip_gzip_index(flate_hip_ctx *ctx, const uint8_t *in, uint64_t in_len,
 int flate_hip_gzip_read(flate_hip_ctx *ctx, const uint8_t *in, uint64_t in_len, uint8_t *out, uint64_t out_cap,
                         uint64_t *out_len, uint32_t *n_members, uint32_t *bad_member, int64_t *err_off,
                         uint32_t flags);
+
+/* -- One long stream: its block starts found on the device ----------------------------
+ * The most common compressed file there is carries nothing that cuts it into independent pieces: ONE .gz, zlib or raw
+ * DEFLATE stream as gzip, zlib or pigz write it -- one member, many blocks.  flate_hip_inflate_one_index finds where
+ * its dynamic-Huffman blocks start, at bit granularity, from the stream's bits alone.  The rule is written once,
+ * csrc/deflate_block_rule.h; the kernels are csrc/one_kernels.hip and csrc/one_probe_kernel.inc.
+ *
+ * The input is ONE stream: wrap = FLATE_HIP_WRAP_RAW, _ZLIB or _GZIP, with exactly the header rules of
+ * flate_hip_inflate_spliced_framed (FEXTRA, FNAME, FCOMMENT and FHCRC skipped; zlib's FDICT, or a member too short for
+ * header plus trailer, is a bad header: *status = FLATE_HIP_E_CORRUPT, *err_off = 0, no units).  Bits and offsets below
+ * are counted from the RAW stream's first byte.
+ *
+ * UNITS.  A unit starts at bit 0 and at every dynamic block header (BTYPE = 2) the serial decode reaches; stored and
+ * fixed blocks belong to the unit in front of them, so a stream made only of them is one unit.  On success
+ * unit_bit[0 .. n] (unit_bit[n] = the bit behind the final block) and out_off[0 .. n] (the exclusive prefix sum of what
+ * the units inflate to) describe the stream; *out_bytes = out_off[n]; *status = 0; *err_off = -1.
+ *
+ * THE VERDICT is the serial decoder's, as far as it does not depend on history: the bits a DEFLATE stream consumes never
+ * depend on the bytes it has produced, so *status and *err_off equal what flate_hip_inflate_batch reports for the raw
+ * stream -- FLATE_HIP_E_CORRUPT with its offset, FLATE_HIP_E_UNEXPECTED_EOF with -1 -- except for a distance that reaches
+ * in front of the stream and for the container's trailer, which only a decode can judge: neither is looked at here.  A
+ * unit whose input spans 2^28 bytes or more (option "one_unit_max", which can only be lowered) is FLATE_HIP_E_TOO_LARGE:
+ * the decoders count positions inside one unit in 32 bits; such a stream is read with flate_hip_inflate_stream_read.
+ * Exactly: a unit is too large iff its reader, counting from the byte that holds the unit's first bit, takes more than
+ * that many bytes before the unit ends (the three bits of the next block header included).  A
+ * stream that fails: *n_units = the good units in front of the failing one, *out_bytes = 0, and the first n_units + 1
+ * entries of both arrays are still filled if they fit (unit_bit[n_units]: where the failing unit starts).
+ *
+ * Conventions: flate_hip_gzip_index's.  Both arrays are HOST arrays of index_cap entries, or both NULL: a query that
+ * returns only the counts.  index_cap < n + 1: FLATE_HIP_E_OUT_TOO_SMALL with the counts set.  The return value is
+ * *status when that is not 0.  *n_candidates (may be NULL, as may err_off): how many bit offsets were decoded
+ * speculatively, bit 0 included.  flags: FLATE_HIP_DEVICE_PTRS or 0, anything else -- or a wrap above _GZIP -- is
+ * FLATE_HIP_E_INVALID before any HIP call.  in_len == 0: a bad header for zlib and gzip, FLATE_HIP_E_UNEXPECTED_EOF for
+ * raw.  More candidates than 32 bits count: FLATE_HIP_E_TOO_LARGE.  Nothing outside in[0, in_len) is read, at any
+ * alignment of in; nothing is written to device memory the caller owns.
+ *   How, all on the ctx's stream, no host pass over stream bytes: FIND, one thread per BIT offset of the raw stream
+ *   tests the rule -- exactly what the decoder's header reader accepts: BTYPE = 2 with either BFINAL, at most 286
+ *   literal/length and 30 distance codes, a code-length code the decoder takes, every repeat inside the counts, both
+ *   codes taken, all inside the raw stream; nothing stricter, or a true header would be missed -- the counts and the
+ *   code-length code first, in LDS; hits are compacted in bit order and the count comes back to the host.  PROBE, one
+ *   wavefront per candidate, decodes from the candidate's bit without history, window or stores -- a decoy can write
+ *   nothing -- up to the next header with BTYPE = 2 or through the final block: end bit, bytes produced, status.  LINK /
+ *   RANK / SCAN as for gzip members: every candidate finds the candidate at its end bit by binary search, the chain
+ *   from bit 0 is ranked by pointer doubling, a scan of the sizes gives out_off.  A chain that stops at a header with
+ *   BTYPE = 2 that is no candidate takes its verdict from one more probe at that bit.  A decoy (a stream inside a
+ *   stored block, compressed bits that look like a header) is a candidate like any other and is simply not on the path
+ *   from bit 0.  Counted in no profiling stage.
+ *
+ * flate_hip_inflate_one: the discovery, then the units DECODED IN PARALLEL.  in / out are host buffers, or device buffers
+ * under FLATE_HIP_DEVICE_PTRS (any other flag: FLATE_HIP_E_INVALID before any HIP call), at any alignment.  *status,
+ * *err_off and *out_len are what the serial decoder reports for the same bytes as one stream
+ * (flate_hip_inflate_batch_framed; flate_hip_inflate_batch for a raw stream): err_off counted from the raw stream's
+ * first byte, the bytes in front of an error delivered, a distance that reaches in front of the stream
+ * FLATE_HIP_E_CORRUPT at the serial offset, a trailer mismatch (CRC-32 or ISIZE, Adler-32) FLATE_HIP_E_CORRUPT with
+ * err_off = in_len.  The return value is *status when that is not 0.  The total is known after discovery: above out_cap
+ * it is FLATE_HIP_E_OUT_TOO_SMALL with *out_len = the size needed and nothing decoded (out == NULL with out_cap == 0 is
+ * the size query); with device pointers nothing outside out[0, total) is written.  Host pointers: the stream is
+ * uploaded once, shared by discovery and decode, and out[0, *out_len) is downloaded once.  err_off, n_units and
+ * n_candidates may be NULL.
+ *   How: in rounds of at most "one_round_units" units (flate_hip_set_option; 4096 by default, 160 KiB of scratch per
+ *   unit: two buffers of tail functions and the windows).  TAIL: the probe's decoder with a SYMBOLIC 32 KiB window in
+ *   LDS (16-bit entries: a literal byte, or "byte j of the 32 KiB in front of this unit"; csrc/window_compose.h), one
+ *   wavefront per unit; copies move entries as they move bytes, and only the unit's final window is stored: its tail
+ *   function, with the shifted pass-through of a unit shorter than 32 KiB.  COMPOSE: the functions are scanned over the
+ *   round in ceil(log2(units)) dependent launches and resolved against the last window of the round in front (nothing
+ *   for round 0: entries in front of the stream resolve to 0, and no valid stream reads them).  DECODE: the round's
+ *   units go through the lane-per-stream dictionary decoder as spliced pieces with dictionaries: piece k starts at the
+ *   unit's bit and ends where the next unit starts, its dictionary is its resolved history, dict_len = min(32768,
+ *   out_off[k]), and its output slot is out + out_off[k] with exactly the unit's size.
+ *   TAIL and DECODE apply the distance rule with the history the unit really has, min(32768, out_off[k] + bytes
+ *   produced), so the one history-dependent verdict comes out where the serial decoder has it; the first failing unit's
+ *   slot ends at its failure and the units behind it get an empty one: nothing behind an error is written.  VERIFY:
+ *   the checksum kernels over out[0, total) in 64 KiB pieces and a verdict kernel.  No kernel waits for another
+ *   workgroup.  Profiling: FLATE_HIP_STAGE_INFLATE is DECODE (of several rounds the last),
+ *   FLATE_HIP_STAGE_CHECKSUM is VERIFY; FIND, PROBE, LINK, TAIL and COMPOSE are counted in no stage.
+ *   Out of scope: finding stored or fixed block starts (streams made of them stay serial inside one unit); fusing
+ *   PROBE with TAIL; routing long members of flate_hip_gzip_read here; multi-member input; caching the index across
+ *   calls; seeking. */
+int flate_hip_inflate_one(flate_hip_ctx *ctx, const uint8_t *in, uint64_t in_len, uint32_t wrap, uint8_t *out,
+                          uint64_t out_cap, uint64_t *out_len, int32_t *status, int64_t *err_off, uint32_t *n_units,
+                          uint32_t *n_candidates, uint32_t flags);
+int flate_hip_inflate_one_index(flate_hip_ctx *ctx, const uint8_t *in, uint64_t in_len, uint32_t wrap,
+                                uint64_t index_cap, uint64_t *unit_bit, uint64_t *out_off, uint32_t *n_units,
+                                uint64_t *out_bytes, uint32_t *n_candidates, int32_t *status, int64_t *err_off,
+                                uint32_t flags);
 
 /* -- ZIP archives ----------------------------------------------------------------
  * The everyday container of a batch of independent DEFLATE streams (.zip, .npz, .jar, .whl, .docx; PKWARE APPNOTE

@@ -26,7 +26,7 @@ EXPORTS = [
     "flate_hip_inflate_batch_framed", "flate_hip_inflate_spliced_framed",
     "flate_hip_bgzf_bound", "flate_hip_bgzf_write", "flate_hip_bgzf_index", "flate_hip_bgzf_read",
     "flate_hip_bgzf_read_ranges",
-    "flate_hip_gzip_index", "flate_hip_gzip_read",
+    "flate_hip_gzip_index", "flate_hip_gzip_read", "flate_hip_inflate_one_index", "flate_hip_inflate_one",
     "flate_hip_zip_bound", "flate_hip_zip_write", "flate_hip_zip_index", "flate_hip_zip_read",
 ]
 
@@ -117,6 +117,14 @@ def load():
         L.flate_hip_gzip_index.restype = C.c_int
         L.flate_hip_gzip_read.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, u64p, u32p, u32p, i64p, C.c_uint32]
         L.flate_hip_gzip_read.restype = C.c_int
+    if os.environ.get("FLATE_HIP_LIB") is None or hasattr(L, "flate_hip_inflate_one_index"):
+        u32p, i64p, i32p = C.POINTER(C.c_uint32), C.POINTER(C.c_int64), C.POINTER(C.c_int32)
+        L.flate_hip_inflate_one_index.argtypes = [vp, vp, C.c_uint64, C.c_uint32, C.c_uint64, vp, vp, u32p, u64p, u32p,
+                                                  i32p, i64p, C.c_uint32]
+        L.flate_hip_inflate_one_index.restype = C.c_int
+        L.flate_hip_inflate_one.argtypes = [vp, vp, C.c_uint64, C.c_uint32, vp, C.c_uint64, u64p, i32p, i64p, u32p, u32p,
+                                            C.c_uint32]
+        L.flate_hip_inflate_one.restype = C.c_int
     if os.environ.get("FLATE_HIP_LIB") is None or hasattr(L, "flate_hip_zip_write"):
         u32p, i64p = C.POINTER(C.c_uint32), C.POINTER(C.c_int64)
         L.flate_hip_zip_bound.argtypes = [vp, C.c_uint32, vp]

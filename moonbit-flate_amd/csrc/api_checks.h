@@ -148,6 +148,30 @@ inline int gzip_read_args(const uint8_t *in, uint64_t in_len, const uint8_t *out
   return (flags & ~FLATE_HIP_DEVICE_PTRS) ? FLATE_HIP_E_INVALID : FLATE_HIP_OK;
 }
 
+// ---- one long stream (flate_hip_inflate_one_index) ----
+
+// the option "one_unit_max": the bytes a unit's input spans at most, 1 .. 2^28 (the default, which a caller can only
+// lower: the decoders' positions inside one unit are 32 bits wide)
+inline bool one_unit_max_ok(int64_t value) { return value >= 1 && value <= (1ll << 28); }
+// unit_bit and out_off come together or not at all (the count query); the input is ONE raw, zlib or gzip stream
+inline int one_index_args(const uint8_t *in, uint64_t in_len, uint32_t wrap, const uint64_t *unit_bit,
+                          const uint64_t *out_off, const uint32_t *n_units, const uint64_t *out_bytes,
+                          const int32_t *status, uint32_t flags) {
+  if (!n_units || !out_bytes || !status || (in_len && !in) || (!unit_bit != !out_off)) return FLATE_HIP_E_INVALID;
+  if (wrap > FLATE_HIP_WRAP_GZIP) return FLATE_HIP_E_INVALID;
+  return (flags & ~FLATE_HIP_DEVICE_PTRS) ? FLATE_HIP_E_INVALID : FLATE_HIP_OK;
+}
+
+// the option "one_round_units": the units flate_hip_inflate_one decodes per round, 1 .. 65536 (scratch: 160 KiB each)
+inline bool one_round_units_ok(int64_t value) { return value >= 1 && value <= 65536; }
+// flate_hip_inflate_one: out == NULL with out_cap == 0 is the size query
+inline int one_args(const uint8_t *in, uint64_t in_len, uint32_t wrap, const uint8_t *out, uint64_t out_cap,
+                    const uint64_t *out_len, const int32_t *status, uint32_t flags) {
+  if (!out_len || !status || (in_len && !in) || (out_cap && !out)) return FLATE_HIP_E_INVALID;
+  if (wrap > FLATE_HIP_WRAP_GZIP) return FLATE_HIP_E_INVALID;
+  return (flags & ~FLATE_HIP_DEVICE_PTRS) ? FLATE_HIP_E_INVALID : FLATE_HIP_OK;
+}
+
 // ---- ZIP archives (flate_hip_zip_write / _index / _read) ----
 
 // everything flate_hip_zip_write refuses before any HIP call

@@ -162,7 +162,9 @@ const char *flate_hip_strerror(int code) {
     case FLATE_HIP_E_HIP: return "HIP runtime error";
     case FLATE_HIP_E_CORRUPT: return "flate: corrupt input";
     case FLATE_HIP_E_NO_DEVICE: return "no usable HIP device (this engine has no CPU path)";
-    case FLATE_HIP_E_TOO_LARGE: return "stream too large";
+    case FLATE_HIP_E_TOO_LARGE:
+      return "stream too large (a single long gzip member is read with flate_hip_inflate_one; a stream with 2^28 bytes "
+             "or more between two dynamic block headers with flate_hip_inflate_stream_read)";
     case FLATE_HIP_E_UNEXPECTED_EOF: return "unexpected EOF";
     case FLATE_HIP_E_INTERNAL: return "internal error: encoder self-check failed";
     case FLATE_HIP_E_AGAIN: return "a shard outgrew the agreed plan (pad or stream count): repeat this batch with the blocking exchange";
@@ -342,6 +344,10 @@ int flate_hip_set_option(flate_hip_ctx *c, const char *name, int64_t value) {
     c->debug_buffer_reset = value;
   } else if (k == "gzip_member_max" && gzip_member_max_ok(value)) {
     c->gzip_member_max = (uint64_t)value;
+  } else if (k == "one_unit_max" && one_unit_max_ok(value)) {
+    c->one_unit_max = (uint64_t)value;
+  } else if (k == "one_round_units" && one_round_units_ok(value)) {
+    c->one_round_units = (uint32_t)value;
   } else {
     return FLATE_HIP_E_INVALID;
   }

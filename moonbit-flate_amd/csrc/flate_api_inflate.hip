@@ -15,6 +15,7 @@
 #include "bgzf_range_rule.h"
 #include "bgzf_rule.h"
 #include "gzip_rule.h"
+#include "window_compose.h"
 
 using namespace flate;
 using namespace flate_host;
@@ -1180,6 +1181,312 @@ int flate_hip_gzip_read(flate_hip_ctx *c, const uint8_t *in, uint64_t in_len, ui
     if (H.out_bytes > out_cap) return FLATE_HIP_E_OUT_TOO_SMALL;
     return members_read(c, d_in, n, P.B.member_off, P.B.out_off, H.out_bytes, out, flags, bad_member, err_off);
   } catch (const std::exception &e) {  // (out of host memory in an index vector)
+    c->hip_err = e.what();
+    return FLATE_HIP_E_INTERNAL;
+  }
+}
+
+}  // extern "C"
+
+// ---- one long stream: block discovery (one_kernels.hip, one_probe_kernel.inc) ----
+namespace {
+
+// The discovery over the ONE stream d_in[0, in_len) (DEVICE memory) on the ctx's stream: the container's header, count
+// and scan, ONE read-back of the candidate count (the launches behind it have a thread or a wavefront per candidate),
+// then fill, probe, link, rounds, finish, out-scan, the tail probe and ONE read-back of the result words H with the
+// index (P.B.member_off / P.B.out_off on the device; null when the header is bad).  Counted in no
+// profiling stage.
+// index_cap != 0: the first min(index_cap, candidates + 1) entries of unit_bit / out_off come back into `index` (the
+// two arrays one after the other) in the same read-back as H -- the units are a subset of the candidates, so what fits
+// the caller's arrays is known before the chain is.
+int one_discover(flate_hip_ctx *c, const uint8_t *d_in, uint64_t in_len, uint32_t wrap, uint64_t index_cap, OneHead &H,
+                 OneParams &P, std::vector<uint64_t> &index) {
+  const uint64_t A = reinterpret_cast<uintptr_t>(d_in) & 15u;
+  const uint64_t tiles = (A + in_len + kBgzfTile - 1) / kBgzfTile;
+  if (tiles > 0x7fffffffull) return FLATE_HIP_E_TOO_LARGE;
+  size_t at = 0;
+  auto carve = [&](size_t bytes) {
+    const size_t here = at;
+    at += (bytes + 255) & ~(size_t)255;
+    return here;
+  };
+  P = OneParams{};
+  P.B.in = d_in;
+  P.B.in_len = in_len;
+  P.B.n_tiles = (uint32_t)tiles;
+  P.unit_max = c->one_unit_max;
+  int rc;
+  {
+    const size_t o_head = carve(sizeof(OneHead)), o_one = carve(sizeof(FrameOne)), o_tile = carve(((size_t)P.B.n_tiles + 1) * 4);
+    if ((rc = ensure(c, c->d_one_tiles, at))) return rc;
+    uint8_t *b = (uint8_t *)c->d_one_tiles.p;
+    P.head = (OneHead *)(b + o_head);
+    P.B.head = &P.head->h;
+    P.one = (FrameOne *)(b + o_one);
+    P.B.tile_cnt = (uint32_t *)(b + o_tile);
+  }
+  hipLaunchKernelGGL(one_init_kernel, dim3(1), dim3(64), 0, c->stream, P.one, in_len);
+  if (wrap != FLATE_HIP_WRAP_RAW) {  // the header rules of flate_hip_inflate_spliced_framed (no dictionaries: FDICT is bad)
+    FrameReadParams R{};
+    R.in = d_in;
+    R.in_off = P.one->in_off;
+    R.n_streams = 1;
+    R.wrap = wrap;
+    R.pay_off = P.one->pay_off;
+    R.pay_end = &P.one->pay_end;
+    R.want = &P.one->want;
+    R.isize = &P.one->isize;
+    R.bad = &P.one->bad;
+    R.dict_used = &P.one->dict_used;
+    hipLaunchKernelGGL(frame_parse_kernel, dim3(1), dim3(256), 0, c->stream, R);
+  }
+  hipLaunchKernelGGL(one_count_kernel, dim3(P.B.n_tiles), dim3(256), 0, c->stream, P);
+  hipLaunchKernelGGL(bgzf_scan_kernel, dim3(1), dim3(1024), 0, c->stream, P.B);
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipMemcpyAsync(&H, P.head, sizeof H, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  const uint32_t cap = H.h.n_cand;
+  if (cap > 0x7ffffff0u) return FLATE_HIP_E_TOO_LARGE;  // (the count saturates at 2^32 - 1)
+  if (cap == 0) return FLATE_HIP_OK;  // (a bad header: the scan kernel has left FLATE_HIP_E_CORRUPT at offset 0)
+
+  const uint32_t rounds = bgzf_rounds(cap);
+  P.B.cap = cap;
+  P.B.path_len = 1u << rounds;
+  at = 0;
+  const size_t n = cap;
+  const size_t o_cand = carve(n * 8), o_probe = carve(n * sizeof(OneProbe)), o_j0 = carve((n + 2) * 4),
+               o_j1 = carve((n + 2) * 4), o_path = carve((size_t)P.B.path_len * 4), o_usize = carve(n * 8),
+               o_ubit = carve((n + 1) * 8), o_ooff = carve((n + 1) * 8);
+  if ((rc = ensure(c, c->d_one, at))) return rc;  // (a failed allocation is FLATE_HIP_E_HIP, never a truncated result)
+  uint8_t *b = (uint8_t *)c->d_one.p;
+  P.B.cand_off = (uint64_t *)(b + o_cand);
+  P.probe = (OneProbe *)(b + o_probe);
+  P.B.jump[0] = (uint32_t *)(b + o_j0);
+  P.B.jump[1] = (uint32_t *)(b + o_j1);
+  P.B.path = (uint32_t *)(b + o_path);
+  P.usize = (uint64_t *)(b + o_usize);
+  P.B.member_off = (uint64_t *)(b + o_ubit);
+  P.B.out_off = (uint64_t *)(b + o_ooff);
+  const uint32_t node_blocks = (uint32_t)(((uint64_t)cap + 2 + 255) / 256);
+  hipLaunchKernelGGL(one_fill_kernel, dim3(P.B.n_tiles), dim3(256), 0, c->stream, P);
+  hipLaunchKernelGGL(one_probe_kernel, dim3(cap), dim3(64), 0, c->stream, P, 0u);
+  hipLaunchKernelGGL(one_link_kernel, dim3(node_blocks), dim3(256), 0, c->stream, P);
+  for (uint32_t j = 0; j < rounds; ++j)
+    hipLaunchKernelGGL(bgzf_round_kernel, dim3(node_blocks), dim3(256), 0, c->stream, P.B, j);
+  hipLaunchKernelGGL(one_finish_kernel, dim3((P.B.path_len + 255) / 256), dim3(256), 0, c->stream, P);
+  hipLaunchKernelGGL(one_out_scan_kernel, dim3(1), dim3(1024), 0, c->stream, P);
+  hipLaunchKernelGGL(one_probe_kernel, dim3(1), dim3(64), 0, c->stream, P, 1u);
+  HIP_TRY(c, hipGetLastError());
+  // ONE read-back behind the count: the result words, then 16 bytes per unit
+  const size_t take = (size_t)(index_cap < n + 1 ? index_cap : n + 1);
+  index.assign(2 * take, 0);
+  HIP_TRY(c, hipMemcpyAsync(&H, P.head, sizeof H, hipMemcpyDeviceToHost, c->stream));
+  if (take) {
+    HIP_TRY(c, hipMemcpyAsync(index.data(), P.B.member_off, take * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(index.data() + take, P.B.out_off, take * 8, hipMemcpyDeviceToHost, c->stream));
+  }
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return FLATE_HIP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int flate_hip_inflate_one_index(flate_hip_ctx *c, const uint8_t *in, uint64_t in_len, uint32_t wrap, uint64_t index_cap,
+                                uint64_t *unit_bit, uint64_t *out_off, uint32_t *n_units, uint64_t *out_bytes,
+                                uint32_t *n_candidates, int32_t *status, int64_t *err_off, uint32_t flags) {
+  // every check before any HIP call
+  if (!c) return FLATE_HIP_E_INVALID;
+  int rc = one_index_args(in, in_len, wrap, unit_bit, out_off, n_units, out_bytes, status, flags);
+  if (rc) return rc;
+  c->hip_err.clear();
+  *n_units = 0, *out_bytes = 0, *status = 0;
+  if (n_candidates) *n_candidates = 0;
+  if (err_off) *err_off = -1;
+  OneHead H{};
+  try {
+    OneParams P{};
+    std::vector<uint64_t> index;
+    if (in_len == 0) {  // no header at all, or a raw stream that ends in front of its first block header
+      H.h.rc = wrap == FLATE_HIP_WRAP_RAW ? FLATE_HIP_E_UNEXPECTED_EOF : FLATE_HIP_E_CORRUPT;
+      H.h.err_off = wrap == FLATE_HIP_WRAP_RAW ? -1 : 0;
+    } else {
+      const uint8_t *d_in = nullptr;
+      if ((rc = bgzf_stage(c, in, in_len, flags, &d_in))) return rc;
+      if ((rc = one_discover(c, d_in, in_len, wrap, unit_bit ? index_cap : 0, H, P, index))) return rc;
+    }
+    *n_units = H.h.n_members;
+    if (n_candidates) *n_candidates = H.h.n_cand;
+    *status = H.h.rc;
+    if (err_off) *err_off = H.h.rc ? H.h.err_off : -1;
+    *out_bytes = H.h.out_bytes;  // (0 unless the chain reaches the final block)
+    // the index -- of a stream that fails its good prefix, if that fits: the verdict is the serial decoder's either way
+    const uint64_t entries = (uint64_t)H.h.n_members + 1;
+    if (unit_bit && index_cap >= entries) {
+      if (index.size() >= 2 * entries) {
+        memcpy(unit_bit, index.data(), entries * 8);
+        memcpy(out_off, index.data() + index.size() / 2, entries * 8);
+      } else {  // (a bad header or no input: zero units in front of offset 0)
+        unit_bit[0] = 0, out_off[0] = 0;
+      }
+    }
+    if (H.h.rc) return H.h.rc;
+    return unit_bit && index_cap < entries ? FLATE_HIP_E_OUT_TOO_SMALL : FLATE_HIP_OK;
+  } catch (const std::exception &e) {  // (out of host memory in the index vector)
+    c->hip_err = e.what();
+    return FLATE_HIP_E_INTERNAL;
+  }
+}
+
+// The whole call: discovery, then the units decoded in parallel in rounds of "one_round_units" -- TAIL (symbolic
+// windows), COMPOSE (a scan of the tail functions), DECODE (the units again, each with its resolved 32 KiB of history,
+// straight into out + out_off[k]) --, then the checksum of out[0, total) and the verdict.  Behind the discovery's two
+// read-backs the host reads nothing but the result words.
+int flate_hip_inflate_one(flate_hip_ctx *c, const uint8_t *in, uint64_t in_len, uint32_t wrap, uint8_t *out, uint64_t out_cap,
+                          uint64_t *out_len, int32_t *status, int64_t *err_off, uint32_t *n_units, uint32_t *n_candidates,
+                          uint32_t flags) {
+  // every check before any HIP call
+  if (!c) return FLATE_HIP_E_INVALID;
+  int rc = one_args(in, in_len, wrap, out, out_cap, out_len, status, flags);
+  if (rc) return rc;
+  c->hip_err.clear();
+  *out_len = 0, *status = 0;
+  if (err_off) *err_off = -1;
+  if (n_units) *n_units = 0;
+  if (n_candidates) *n_candidates = 0;
+  auto verdict = [&](int st, int64_t eo) {
+    *status = st;
+    if (err_off) *err_off = st ? eo : -1;
+    return st;
+  };
+  if (in_len == 0)
+    return wrap == FLATE_HIP_WRAP_RAW ? verdict(FLATE_HIP_E_UNEXPECTED_EOF, -1) : verdict(FLATE_HIP_E_CORRUPT, 0);
+  try {
+    const bool dev = (flags & FLATE_HIP_DEVICE_PTRS) != 0;
+    const uint8_t *d_in = nullptr;
+    if ((rc = bgzf_stage(c, in, in_len, flags, &d_in))) return rc;
+    OneHead H{};
+    OneParams P{};
+    std::vector<uint64_t> none;
+    if ((rc = one_discover(c, d_in, in_len, wrap, 0, H, P, none))) return rc;
+    if (n_units) *n_units = H.h.n_members;
+    if (n_candidates) *n_candidates = H.h.n_cand;
+    if (H.h.n_cand == 0) return verdict(H.h.rc, H.h.err_off);  // a bad header
+    if (H.h.rc == FLATE_HIP_E_TOO_LARGE || H.h.rc == FLATE_HIP_E_INTERNAL) return verdict(H.h.rc, H.h.err_off);
+    // the units to decode: the good ones and, so that the bytes in front of an error are delivered, a unit that fails
+    // behind its header; the total is known here
+    const uint32_t n_dec = H.h.n_members + (H.fail_unit ? 1u : 0u);
+    const uint64_t total = H.prefix_bytes + (H.fail_unit ? H.fail_out : 0ull);
+    *out_len = total;
+    if (total > out_cap) return FLATE_HIP_E_OUT_TOO_SMALL;  // (nothing is decoded; out == NULL: the size query)
+    uint8_t *d_out = out;
+    if (!dev) {
+      if ((rc = ensure(c, c->d_out, total + 16))) return rc;
+      d_out = (uint8_t *)c->d_out.p;
+    }
+    const uint32_t per_round = n_dec < c->one_round_units ? (n_dec ? n_dec : 1u) : c->one_round_units;
+    size_t at = 0;
+    auto carve = [&](size_t bytes) {
+      const size_t here = at;
+      at += (bytes + 255) & ~(size_t)255;
+      return here;
+    };
+    const size_t fbytes = (size_t)per_round * kWinEntries * 2;
+    const size_t o_dh = carve(sizeof(OneDecHead)), o_sum = carve(16), o_f0 = carve(fbytes), o_f1 = carve(fbytes),
+                 o_r = carve(((size_t)per_round + 1) * kWinEntries), o_st = carve((size_t)n_dec * 4 + 4),
+                 o_eo = carve((size_t)n_dec * 8 + 8), o_pr = carve((size_t)n_dec * 8 + 8),
+                 o_po = carve(((size_t)per_round + 1) * 8), o_pa = carve((size_t)per_round * 8),
+                 o_pl = carve((size_t)per_round * 4), o_ds = carve((size_t)per_round * 4),
+                 o_dl = carve((size_t)per_round * 8), o_de = carve((size_t)per_round * 8);
+    if ((rc = ensure(c, c->d_one_dec, at))) return rc;
+    uint8_t *b = (uint8_t *)c->d_one_dec.p;
+    OneDecParams D{};
+    D.in = d_in;
+    D.one = P.one;
+    D.unit_bit = P.B.member_off;
+    D.out_off = P.B.out_off;
+    D.total = total;
+    D.unit_max = c->one_unit_max;
+    D.F[0] = (uint16_t *)(b + o_f0);
+    D.F[1] = (uint16_t *)(b + o_f1);
+    D.R = b + o_r;
+    D.p_out_off = (uint64_t *)(b + o_po);
+    D.p_dict_at = (uint64_t *)(b + o_pa);
+    D.p_dict_len = (uint32_t *)(b + o_pl);
+    D.d_status = (const int32_t *)(b + o_ds);
+    D.d_out_len = (const uint64_t *)(b + o_dl);
+    D.dh = (OneDecHead *)(b + o_dh);
+    D.status = (int32_t *)(b + o_st);
+    D.err_off = (int64_t *)(b + o_eo);
+    D.produced = (uint64_t *)(b + o_pr);
+    D.head = P.head;
+    D.wrap = wrap;
+    D.in_len = in_len;
+    HIP_TRY(c, hipMemsetAsync(D.dh, 0xff, sizeof(OneDecHead), c->stream));  // first_bad, decode_bad: none
+    HIP_TRY(c, hipMemsetAsync(D.R, 0, kWinEntries, c->stream));            // in front of the stream: zeros
+    bool used[FLATE_HIP_STAGE_COUNT] = {false, false, false, false};
+    for (uint32_t u0 = 0; u0 < n_dec; u0 += per_round) {
+      D.u0 = u0;
+      D.count = n_dec - u0 < per_round ? n_dec - u0 : per_round;
+      const uint32_t entry_blocks = (uint32_t)(((uint64_t)D.count * kWinEntries + 255) / 256);
+      const uint32_t unit_blocks = (D.count + 1u + 255u) / 256u;
+      hipLaunchKernelGGL(one_tail_kernel, dim3(D.count), dim3(64), 0, c->stream, D);
+      int cur = 0;
+      for (uint32_t s = 1; s < D.count; s <<= 1, cur ^= 1)
+        hipLaunchKernelGGL(one_compose_kernel, dim3(entry_blocks), dim3(256), 0, c->stream, D.F[cur], D.F[cur ^ 1], D.count, s);
+      hipLaunchKernelGGL(one_resolve_kernel, dim3(entry_blocks), dim3(256), 0, c->stream, D.F[cur], D.R, D.count);
+      // DECODE: the round's units as spliced pieces with dictionaries, through the lane-per-stream decoder.  The
+      // stream's last piece runs to BFINAL (or to its failure); every other round's last piece ends where the next
+      // unit starts, and so does the last unit of a chain that stopped at a header the decoder refuses.
+      hipLaunchKernelGGL(one_pieces_kernel, dim3(unit_blocks), dim3(256), 0, c->stream, D);
+      InfParams I{};
+      I.in = d_in + H.raw_off;
+      I.in_len = H.raw_len;
+      I.bit_off = D.unit_bit + u0;
+      I.closed = (u0 + D.count < n_dec || (H.h.rc != 0 && !H.fail_unit)) ? 1u : 0u;
+      I.n_streams = D.count;
+      I.out = d_out;
+      I.out_off = D.p_out_off;
+      I.out_len = (uint64_t *)(b + o_dl);
+      I.status = (int32_t *)(b + o_ds);
+      I.err_off = (int64_t *)(b + o_de);
+      I.dict_buf = D.R;
+      I.dict_at = D.p_dict_at;
+      I.dict_len = D.p_dict_len;
+      if ((rc = launch_decoders(c, inflate_route_units(c->inflate, c->num_cus, D.count), I, true))) return rc;  // (of several rounds the stage's time is the last one's)
+      hipLaunchKernelGGL(one_check_kernel, dim3(unit_blocks), dim3(256), 0, c->stream, D);
+      used[FLATE_HIP_STAGE_INFLATE] = true;
+      HIP_TRY(c, hipGetLastError());
+      // the window behind the round's last unit seeds the next round
+      if (u0 + D.count < n_dec)
+        HIP_TRY(c, hipMemcpyAsync(D.R, D.R + (size_t)D.count * kWinEntries, kWinEntries, hipMemcpyDeviceToDevice, c->stream));
+    }
+    bool ctl = false;
+    if (wrap != FLATE_HIP_WRAP_RAW && total) {
+      const uint64_t whole[2] = {0, total};
+      if ((rc = ctl_begin(c, checksum_ctl_up_bytes(whole, 1), 0))) return rc;
+      ctl = true;
+      D.sum = (uint32_t *)(b + o_sum);
+      if ((rc = checksum_device(c, d_out, whole, 1, frame_sum_kind(wrap), (uint32_t *)(b + o_sum), FLATE_HIP_STAGE_CHECKSUM)))
+        return rc;
+      used[FLATE_HIP_STAGE_CHECKSUM] = true;
+    }
+    hipLaunchKernelGGL(one_verdict_kernel, dim3(1), dim3(64), 0, c->stream, D);
+    HIP_TRY(c, hipGetLastError());
+    OneDecHead R{};
+    HIP_TRY(c, hipMemcpyAsync(&R, D.dh, sizeof R, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (ctl) ctl_finish(c);
+    if (R.out_len > total) return FLATE_HIP_E_INTERNAL;
+    *out_len = R.out_len;
+    if (!dev && R.out_len) {  // the result comes down once
+      HIP_TRY(c, hipMemcpyAsync(out, d_out, R.out_len, hipMemcpyDeviceToHost, c->stream));
+      HIP_TRY(c, hipStreamSynchronize(c->stream));
+    }
+    if (c->profiling && (rc = collect_timing(c, used))) return rc;
+    return verdict(R.status, R.err_off);
+  } catch (const std::exception &e) {
     c->hip_err = e.what();
     return FLATE_HIP_E_INTERNAL;
   }

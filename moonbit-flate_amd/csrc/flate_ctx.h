@@ -80,6 +80,16 @@ struct flate_hip_ctx {
   DevBuf d_gzip, d_gzip_tiles;
   // ... and the range a candidate is given at most (option "gzip_member_max": it can only be lowered)
   uint64_t gzip_member_max = (1ull << 28) - 1;
+  // flate_hip_inflate_one_index: the block discovery's arrays (OneParams) and the probes' results, carved from one
+  // buffer; in front of it (sized before the candidates are counted) the result words, the one member's words
+  // (FrameOne) and the tiles' counts
+  DevBuf d_one, d_one_tiles;
+  // ... and the bytes a unit's input spans at most (option "one_unit_max": it can only be lowered)
+  uint64_t one_unit_max = 1ull << 28;
+  // flate_hip_inflate_one: the decode's arrays of one round (OneDecParams: the tail functions twice, the windows, the
+  // per-unit results), carved from one buffer; the units of a round (option "one_round_units")
+  DevBuf d_one_dec;
+  uint32_t one_round_units = 4096;
   DevBuf d_zip_names, d_zip_name_off, d_zip_whead, d_zip_end, d_zip_dir, d_zip_sel;
   hipStream_t guest_stream = nullptr;
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;

@@ -148,6 +148,9 @@ struct InfParams {
   // NULL: independent streams given by in_off.
   const uint64_t *bit_off;
   uint64_t in_len;
+  // inflate_simt_kernel, spliced: nonzero = the pieces are a part of a longer stream (a round of
+  // flate_hip_inflate_one): the last piece does not run to BFINAL, it ends at bit_off[n_streams] like the others
+  uint32_t closed;
   uint32_t size_only;  // inflate_kernel: decode and count, store nothing (FLATE_HIP_SIZE_ONLY)
   uint32_t *simt_lens; // inflate_simt_kernel: per-lane scratch of the header being parsed (inflate_simt_lens_bytes)
   uint32_t sid0;       // inflate_simt_kernel: first stream of this launch (a batch of several rounds)
@@ -470,6 +473,99 @@ __global__ void gzip_fill_kernel(GzipParams P);
 __global__ void gzip_link_kernel(GzipParams P);
 __global__ void gzip_finish_kernel(GzipParams P);
 __global__ void gzip_out_scan_kernel(GzipParams P);
+
+// One long DEFLATE stream (one_kernels.hip, one_probe_kernel.inc; flate_hip_inflate_one_index): the gzip discovery one
+// level down.  Bit 0 of the raw stream and every bit offset that passes the dynamic-header rule (deflate_block_rule.h)
+// is a CANDIDATE, compacted in bit order (count per 4 KiB tile, bgzf_scan_kernel, fill); one_probe_kernel decodes every
+// candidate without history or stores up to the next dynamic header (OneProbe); one_link_kernel sends every candidate
+// to the candidate at its end bit (a final block: the terminal node n_cand; nothing or a failed probe: the dead node
+// n_cand + 1); bgzf_round_kernel ranks the chain from candidate 0; one_finish_kernel and one_out_scan_kernel turn the
+// ranks into unit_bit / out_off; a chain that stops at a dynamic header the rule refused takes its verdict from one
+// more probe there (one_probe_kernel, tail form).  B carries what the two BGZF kernels read (head, cap, path_len,
+// tile_cnt, jump, path); B.in is the whole input, B.cand_off the candidates' bits, B.member_off the units' bits (both
+// counted from the raw stream's first byte); B.cand_total and B.isize are unused.  B.cap is the exact candidate count.
+struct OneProbe {          // what a candidate's probe left
+  uint64_t end_bit;        // where it stopped: in front of a dynamic header, or behind the final block
+  uint64_t out;            // bytes it inflates to
+  int64_t err_off;         // counted from the raw stream's first byte, or -1
+  int32_t status;          // 0, FLATE_HIP_E_CORRUPT / _UNEXPECTED_EOF / _TOO_LARGE
+  uint32_t final_block;    // it ended with BFINAL
+};
+struct OneHead {           // the result words, read back as one block; B.head = &h
+  BgzfHead h;              // n_members: the units; rc / err_off: the serial decoder's verdict
+  uint64_t tail_bit;       // tail != 0: the chain stopped here, at a dynamic header that is no candidate
+  uint32_t tail;
+  uint32_t bad;            // the container's header verdict (frame_parse_kernel)
+  uint64_t raw_off, raw_len;  // the raw stream inside the input
+  uint64_t prefix_bytes;   // what the good units inflate to (out_off[n_members]), of a stream that fails too
+  uint64_t fail_out;       // a unit that fails behind its header: the bytes it produced in front of the failure
+  uint32_t fail_unit;      // ... and 1: that unit is decoded too, so that those bytes are delivered
+  uint32_t pad;
+};
+struct OneParams {
+  BgzfParams B;
+  FrameOne *one;           // one_init_kernel, frame_parse_kernel: pay_off[0] .. pay_end is the raw stream
+  OneHead *head;
+  OneProbe *probe;         // cap
+  uint64_t *usize;         // cap: per unit of the chain, what it inflates to
+  uint64_t unit_max;       // option "one_unit_max": a unit's input spans fewer bytes than this
+};
+// The decode of the units (flate_hip_inflate_one), in rounds of `count` units from unit u0.  one_tail_kernel (TAIL)
+// decodes every unit of the round with a SYMBOLIC window (window_compose.h) and stores its tail function into F[0];
+// one_compose_kernel scans the functions over the round (Hillis-Steele, ceil(log2(count)) launches between F[0] and
+// F[1]); one_resolve_kernel turns them into the byte windows R[1 .. count] from the seed R[0]; one_pieces_kernel
+// writes the round as spliced pieces with dictionaries (InfParams: bit_off = unit_bit + u0, dict = R[i], dict_len =
+// min(32768, out_off[k]), slot = out + out_off[k]) and the lane-per-stream dictionary decoder (DECODE) decodes them
+// straight into the output; one_check_kernel holds what it reports against the discovery.  TAIL and DECODE apply the
+// distance rule of the serial decoder (history = min(32768, out_off[k] + bytes produced)): the first unit that fails
+// is dh->first_bad; its slot ends at the failure and the units behind it get an empty slot (nothing is written).
+struct OneDecHead {        // the call's result words
+  uint64_t out_len;
+  int64_t err_off;
+  int32_t status;
+  uint32_t first_bad;      // 0xffffffff: none
+  uint32_t decode_bad;     // 0xffffffff: none; else a good unit DECODE did not decode as TAIL did (E_INTERNAL)
+  uint32_t pad;
+};
+struct OneDecParams {
+  const uint8_t *in;
+  const FrameOne *one;
+  const uint64_t *unit_bit;  // n_dec + 1 (OneParams::B.member_off)
+  const uint64_t *out_off;   // n_dec + 1
+  uint32_t u0, count;
+  uint64_t total;            // nothing at or behind out + total is written
+  uint64_t unit_max;
+  uint16_t *F[2];            // count * 32768 entries each
+  uint8_t *R;                // (count + 1) * 32768 bytes: R[i] = the window in front of unit u0 + i
+  OneDecHead *dh;
+  int32_t *status;           // per unit (TAIL)
+  int64_t *err_off;
+  uint64_t *produced;
+  // the round's pieces (one_pieces_kernel -> InfParams) and what DECODE reports for them (one_check_kernel)
+  uint64_t *p_out_off;       // count + 1: piece i's slot is [p_out_off[i], p_out_off[i + 1]) of the output
+  uint64_t *p_dict_at;       // count: where in R piece i's dict_len bytes of history start
+  uint32_t *p_dict_len;      // count
+  const int32_t *d_status;   // count
+  const uint64_t *d_out_len; // count
+  // one_verdict_kernel
+  const OneHead *head;
+  const uint32_t *sum;       // the checksum of out[0, total), or null
+  uint32_t wrap;
+  uint64_t in_len;
+};
+__global__ void one_tail_kernel(OneDecParams D);
+__global__ void one_pieces_kernel(OneDecParams D);
+__global__ void one_check_kernel(OneDecParams D);
+__global__ void one_compose_kernel(const uint16_t *src, uint16_t *dst, uint32_t count, uint32_t s);
+__global__ void one_resolve_kernel(const uint16_t *F, uint8_t *R, uint32_t count);
+__global__ void one_verdict_kernel(OneDecParams D);
+__global__ void one_init_kernel(FrameOne *one, uint64_t in_len);
+__global__ void one_count_kernel(OneParams P);
+__global__ void one_fill_kernel(OneParams P);
+__global__ void one_probe_kernel(OneParams P, uint32_t tail);
+__global__ void one_link_kernel(OneParams P);
+__global__ void one_finish_kernel(OneParams P);
+__global__ void one_out_scan_kernel(OneParams P);
 
 size_t inflate_simt_lds_bytes(int lanes_per_wave);  // dynamic LDS of that launch
 size_t inflate_simt_lens_bytes(uint32_t blocks);    // global scratch of that launch (InfParams::simt_lens)

@@ -18,6 +18,9 @@
 // (more_bits :789, huff_sym :818-831) has consumed, which is a function of the bits requested so
 // far: roffset = max(roffset, ceil((consumed_bits + requested) / 8)).
 #include "flate_kernels.h"
+#include "window_compose.h"
+
+#include <type_traits>
 
 namespace flate {
 
@@ -581,6 +584,7 @@ template __global__ void inflate_spec_kernel<FLATE_SPEC_SMALL>(InfParams);
 template __global__ void inflate_spec_kernel<FLATE_SPEC_LARGE>(InfParams);
 template __global__ void inflate_spec_dict_kernel<FLATE_SPEC_SMALL>(InfParams);
 template __global__ void inflate_spec_dict_kernel<FLATE_SPEC_LARGE>(InfParams);
+#include "one_probe_kernel.inc"
 
 }  // namespace flate
 
@@ -1084,7 +1088,8 @@ FLATE_D void inflate_simt(const InfParams &P) {
       start_bit = (uint32_t)(g0 - 8 * in_base);
       const uint64_t rest = P.in_len - in_base;
       b.in_len = rest < (1ull << 28) ? (uint32_t)rest : (1u << 28);
-      if (sid + 1 != P.n_streams) stop_bit = (uint32_t)(g1 - 8 * in_base);  // piece < 2^28 B: host
+      // (closed: the pieces are a part of a longer stream -- the last one, too, ends where the next piece starts)
+      if (sid + 1 != P.n_streams || P.closed) stop_bit = (uint32_t)(g1 - 8 * in_base);  // piece < 2^28 B: host
     }
   }
   uint32_t dict_len = 0;          // DICT: the lane's dictionary tail, history positions -dict_len .. -1

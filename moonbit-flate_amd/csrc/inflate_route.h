@@ -97,4 +97,14 @@ inline InflateRoute inflate_route(const InflateOpts &o, uint32_t num_cus, uint32
   return r;
 }
 
+// flate_hip_inflate_one: a round of n units of ONE stream -- spliced pieces (bit offsets) that each start from their
+// own 32 KiB of resolved history (dictionaries).  Always the lane-per-stream decoder in its dictionary build: it is
+// the one that ends a piece at the next piece's bit (InfParams::closed covers the round's last) and that takes a
+// piece's history from the dictionary tail; lanes, row and launches as for any spliced call.
+inline InflateRoute inflate_route_units(const InflateOpts &o, uint32_t num_cus, uint32_t n) {
+  InflateOpts s = o;
+  s.spec = 0;
+  return inflate_route(s, num_cus, n, 0, true, false);
+}
+
 }  // namespace flate

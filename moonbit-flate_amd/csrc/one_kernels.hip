@@ -1,0 +1,312 @@
+// one_kernels.hip -- block discovery for ONE long DEFLATE stream (flate_hip_inflate_one_index): where the units of the
+// raw stream inside in[0, in_len) start -- bit 0 and every dynamic block header the serial decode reaches -- and where
+// their output goes, from the stream's bits alone (flate_kernels.h: OneParams; the rule: deflate_block_rule.h).
+//
+// The shape is gzip_kernels.hip's, at bit granularity:
+//   one_init_kernel      the one range {0, in_len}, and the raw stream of FLATE_HIP_WRAP_RAW: all of it
+//   frame_parse_kernel   (frame_kernels.hip; zlib and gzip) the header's verdict and the raw stream's range
+//   one_count_kernel     one workgroup per 4 KiB tile, as gzip_count_kernel: 16-byte loads into LDS on the grid of the
+//                        buffer's address plus one chunk of halo; every thread tests its 128 bit offsets -- 13 bits of a
+//                        32-bit window first, then the three counts and the code-length code, all in LDS (at most 81
+//                        bits from the byte: inside the halo) -- and runs the whole rule FROM GLOBAL MEMORY on the rare hit; bit 0 of the raw stream is a candidate
+//                        whatever it holds; the tile's count goes to tile_cnt
+//   bgzf_scan_kernel     (bgzf_kernels.hip) the exclusive scan of the counts; n_cand, which the host reads back
+//   one_fill_kernel      the same pass again, the hits written in bit order: cand_off
+//   one_probe_kernel     (one_probe_kernel.inc) every candidate decoded to the next dynamic header: OneProbe
+//   one_link_kernel      jump[0][c] = the candidate at end_bit[c] (binary search), the terminal node n_cand behind a final
+//                        block, else -- or when the probe failed -- the dead node n_cand + 1; both absorb
+//   bgzf_round_kernel    (bgzf_kernels.hip) pointer doubling
+//   one_finish_kernel    path rank r -> unit_bit[r], the unit's size; the thread at which the path meets a sink writes
+//                        the verdict, or asks for the tail probe
+//   one_out_scan_kernel  the exclusive scan of the sizes -> out_off (one workgroup, scan_range)
+// A unit ends strictly above its start (a block header has three bits), so nothing cycles.  No kernel waits for
+// another workgroup; every loop is bounded by the tile, by the candidate count or by 32 search steps.
+#include <hip/hip_runtime.h>
+
+#include "block_scan.h"
+#include "deflate_block_rule.h"
+#include "flate_hip.h"
+#include "flate_kernels.h"
+#include "window_compose.h"
+
+namespace flate {
+
+namespace {
+
+constexpr uint32_t kChunks = kBgzfTile / 16;  // 256: one per thread
+
+__device__ inline uint32_t buf_align(const OneParams &P) { return (uint32_t)(reinterpret_cast<uintptr_t>(P.B.in) & 15u); }
+
+// the tile's bytes (kBgzfTile + 16 of halo) into LDS; bytes outside the input read as zero.  (bgzf_kernels.hip's
+// load_tile: virtual position = input offset + A, so that multiples of 16 are aligned addresses.)
+__device__ inline void load_tile(const OneParams &P, uint8_t *lds, uint64_t v0, uint32_t A) {
+  const uint8_t *in = P.B.in;
+  const uint64_t v_end = (uint64_t)A + P.B.in_len;
+  for (uint32_t ch = threadIdx.x; ch <= kChunks; ch += 256u) {
+    const uint64_t v = v0 + 16ull * ch;
+    uint4 w = make_uint4(0u, 0u, 0u, 0u);
+    if (v >= A && v + 16u <= v_end) {
+      w = *reinterpret_cast<const uint4 *>(in + (v - A));
+    } else if (v + 16u > A && v < v_end) {
+      uint32_t d[4] = {0u, 0u, 0u, 0u};
+      for (uint32_t b = 0; b < 16u; ++b) {
+        const uint64_t vv = v + b;
+        if (vv >= A && vv < v_end) d[b >> 2] |= (uint32_t)in[vv - A] << (8u * (b & 3u));
+      }
+      w = make_uint4(d[0], d[1], d[2], d[3]);
+    }
+    *reinterpret_cast<uint4 *>(lds + 16u * ch) = w;
+  }
+  __syncthreads();
+}
+
+// this thread's 128 bit offsets: bit j of hits = a unit can start at bit (j & 7) of the byte at virtual position
+// v0 + 16 * tid + (j >> 3).  Returns how many.
+__device__ inline uint32_t test_bits(const OneParams &P, const uint8_t *lds, uint64_t v0, uint32_t A, uint32_t hits[4]) {
+  hits[0] = hits[1] = hits[2] = hits[3] = 0u;
+  const uint64_t raw_off = P.one->pay_off[0], raw_end = P.one->pay_end;
+  const bool bad = P.one->bad != 0;
+  const uint32_t at = 16u * threadIdx.x;
+  uint32_t n = 0;
+  for (uint32_t b = 0; b < 16u; ++b) {
+    const uint64_t v = v0 + at + b;
+    if (v < A) continue;
+    const uint64_t p = v - A;
+    if (bad || p < raw_off || p >= P.B.in_len) continue;
+    uint32_t m = 0;
+    if (p < raw_end) {
+      const uint64_t end_bit = 8u * (raw_end - p);  // (the bytes the head test reads lie in LDS: see above)
+      // the cheap rejections first: 13 bits of a 32-bit window (bits behind the stream's end fail in dblk_head_ok)
+      const uint8_t *l = lds + at + b;
+      const uint32_t w = l[0] | ((uint32_t)l[1] << 8) | ((uint32_t)l[2] << 16) | ((uint32_t)l[3] << 24);
+      for (uint32_t k = 0; k < 8u; ++k)
+        if (dblk_quick_ok(w >> k) && dblk_head_ok(l, end_bit, k) &&
+            deflate_dyn_header_ok(P.B.in + raw_off, raw_end - raw_off, 8u * (p - raw_off) + k))
+          m |= 1u << k;
+    }
+    if (p == raw_off) m |= 1u;  // bit 0 starts the first unit
+    hits[b >> 2] |= m << (8u * (b & 3u));
+    n += (uint32_t)__popc(m);
+  }
+  return n;
+}
+
+}  // namespace
+
+// {0, in_len} and the raw stream of a bare DEFLATE stream; frame_parse_kernel overwrites the latter for a container
+__global__ void one_init_kernel(FrameOne *one, uint64_t in_len) {
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  FrameOne o{};
+  o.in_off[1] = in_len;
+  o.pay_off[1] = in_len;
+  o.pay_end = in_len;
+  o.dict_used = FLATE_HIP_NO_DICT;
+  *one = o;
+}
+
+__global__ __launch_bounds__(256) void one_count_kernel(OneParams P) {
+  __shared__ __attribute__((aligned(16))) uint8_t lds[kBgzfTile + 16];
+  __shared__ uint32_t wtot[4];
+  if (blockIdx.x == 0 && threadIdx.x == 0) {  // (bgzf_scan_kernel writes head->h, and nothing behind it)
+    P.head->tail_bit = 0;
+    P.head->tail = 0;
+    P.head->prefix_bytes = 0;
+    P.head->fail_out = 0;
+    P.head->fail_unit = 0;
+    P.head->pad = 0;
+    P.head->bad = P.one->bad;
+    P.head->raw_off = P.one->pay_off[0];
+    P.head->raw_len = P.one->pay_end - P.one->pay_off[0];
+  }
+  const uint32_t A = buf_align(P);
+  const uint64_t v0 = (uint64_t)blockIdx.x * kBgzfTile;
+  load_tile(P, lds, v0, A);
+  uint32_t hits[4];
+  const uint32_t mine = test_bits(P, lds, v0, A, hits);
+  uint32_t sum = 0;
+  (void)block_scan_excl<4, uint32_t>(mine, wtot, &sum);
+  if (threadIdx.x == 0) P.B.tile_cnt[blockIdx.x] = sum;
+}
+
+__global__ __launch_bounds__(256) void one_fill_kernel(OneParams P) {
+  __shared__ __attribute__((aligned(16))) uint8_t lds[kBgzfTile + 16];
+  __shared__ uint32_t wtot[4];
+  const uint32_t cap = P.B.cap;
+  if (P.B.head->n_cand != cap) return;  // (uniform, never: the arrays are sized from the count the host read back)
+  const uint32_t first = P.B.tile_cnt[blockIdx.x];
+  if (P.B.tile_cnt[blockIdx.x + 1] == first) return;  // (uniform: nothing in this tile)
+  const uint32_t A = buf_align(P);
+  const uint64_t v0 = (uint64_t)blockIdx.x * kBgzfTile;
+  load_tile(P, lds, v0, A);
+  uint32_t hits[4];
+  const uint32_t mine = test_bits(P, lds, v0, A, hits);
+  uint32_t sum = 0;
+  uint32_t at = first + block_scan_excl<4, uint32_t>(mine, wtot, &sum);
+  const uint64_t raw_off = P.one->pay_off[0];
+  for (uint32_t j = 0; j < 128u; ++j) {
+    if (!((hits[j >> 5] >> (j & 31u)) & 1u)) continue;
+    // (a hit lies at or above raw_off: test_bits)
+    if (at < cap) P.B.cand_off[at] = 8u * (v0 + 16u * threadIdx.x + (j >> 3) - A - raw_off) + (j & 7u);
+    ++at;
+  }
+}
+
+// One thread per node (n_cand + 2 of them).
+__global__ __launch_bounds__(256) void one_link_kernel(OneParams P) {
+  const uint32_t n = P.B.cap;
+  const uint32_t c = blockIdx.x * 256u + threadIdx.x;
+  const uint32_t term = n, dead = n + 1u;
+  if (c == 0) {
+    P.B.path[0] = (n && P.B.cand_off[0] == 0ull) ? 0u : dead;  // the first unit starts at bit 0
+    P.B.member_off[0] = 0ull;
+  }
+  if (c > dead) return;
+  uint32_t next = c;  // the two sinks absorb
+  if (c < n) {
+    next = dead;
+    const OneProbe pr = P.probe[c];
+    if (pr.status == 0) {
+      if (pr.final_block) {
+        next = term;
+      } else {
+        const uint64_t want = pr.end_bit;
+        uint32_t lo = c + 1u, hi = n;  // a unit ends strictly above its start
+        for (int it = 0; it < 32 && lo < hi; ++it) {
+          const uint32_t mid = lo + (hi - lo) / 2u;
+          if (P.B.cand_off[mid] < want) lo = mid + 1u;
+          else hi = mid;
+        }
+        if (lo < n && P.B.cand_off[lo] == want) next = lo;
+      }
+    }
+  }
+  P.B.jump[0][c] = next;
+}
+
+__global__ __launch_bounds__(256) void one_finish_kernel(OneParams P) {
+  const uint32_t n = P.B.cap;
+  const uint32_t r = blockIdx.x * 256u + threadIdx.x;
+  if (r + 1u >= P.B.path_len) return;  // (the last entry is a sink: see below)
+  const uint32_t c = P.B.path[r];
+  if (c >= n) return;
+  BgzfHead *h = P.B.head;
+  const OneProbe pr = P.probe[c];
+  P.B.member_off[r] = P.B.cand_off[c];
+  if (pr.status != 0) {  // the decode ends IN this unit: one thread gets here, or one gets below
+    P.head->fail_out = pr.out;
+    P.head->fail_unit = 1u;
+    h->n_members = r;
+    h->rc = pr.status;
+    h->err_off = pr.err_off;
+    return;
+  }
+  P.usize[r] = pr.out;
+  // (the chain holds at most n candidates and path_len >= n + 2: r + 1 is inside the path)
+  const uint32_t succ = P.B.path[r + 1u];
+  if (succ < n) return;
+  h->n_members = r + 1u;  // this is the last good unit
+  P.B.member_off[r + 1u] = pr.end_bit;
+  if (succ == n) {
+    h->rc = 0;
+    h->err_off = -1;
+  } else {  // a dynamic header that is no candidate: the tail probe reads it as the serial decoder does
+    P.head->tail_bit = pr.end_bit;
+    P.head->tail = 1u;
+  }
+}
+
+// One workgroup, behind one_finish_kernel: out_off = the exclusive scan of what the units inflate to -- of a broken
+// chain too (its good prefix).
+__global__ __launch_bounds__(1024) void one_out_scan_kernel(OneParams P) {
+  __shared__ uint64_t wtot[16];
+  const uint32_t hi = P.B.head->n_members;
+  const uint64_t total = scan_range<16, uint64_t>(
+      hi, wtot, [&](uint32_t i) { return P.usize[i]; },
+      [&](uint32_t i, uint64_t before, uint64_t) { P.B.out_off[i] = before; });
+  if (threadIdx.x == 0) {
+    P.B.out_off[hi] = total;
+    P.head->prefix_bytes = total;
+    P.B.head->out_bytes = P.B.head->rc == 0 ? total : 0ull;
+  }
+}
+
+// ---- the decode's scan (flate_hip_inflate_one; OneDecParams) ----
+
+// One step of the scan over the round's tail functions: dst[k] = src[k] o src[k - s] for k >= s.  One thread per entry.
+__global__ __launch_bounds__(256) void one_compose_kernel(const uint16_t *src, uint16_t *dst, uint32_t count, uint32_t s) {
+  const uint64_t idx = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+  const uint64_t k = idx / kWinEntries;
+  if (k >= count) return;
+  const uint16_t e = src[idx];
+  dst[idx] = k >= s ? wc_compose(e, src + (k - s) * kWinEntries) : e;
+}
+
+// R[k + 1] = F[k] applied to the seed R[0], where F[k] is the composition of the round's functions up to unit k.
+__global__ __launch_bounds__(256) void one_resolve_kernel(const uint16_t *F, uint8_t *R, uint32_t count) {
+  const uint64_t idx = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+  if (idx / kWinEntries >= count) return;
+  R[kWinEntries + idx] = wc_resolve(F[idx], R);
+}
+
+// One thread per unit of the round (and one more): the round as spliced pieces with dictionaries.  Piece i's slot is
+// the unit's range of the output; the first failing unit's slot ends at its failure (the bytes in front are delivered)
+// and the units behind it get an empty slot: the decoder stops at their first token and writes nothing.  No slot
+// reaches beyond `total`.
+__global__ __launch_bounds__(256) void one_pieces_kernel(OneDecParams D) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (i > D.count) return;
+  const uint32_t u = D.u0 + i, fb = D.dh->first_bad;
+  uint64_t limit = D.total;
+  if (fb != 0xffffffffu) limit = D.out_off[fb] + D.produced[fb];
+  if (limit > D.total) limit = D.total;
+  uint64_t at = u > fb ? limit : D.out_off[u];  // (out_off is defined up to the first failing unit)
+  if (at > limit) at = limit;
+  D.p_out_off[i] = at;
+  if (i == D.count) return;
+  const uint32_t dict_len = at < (uint64_t)kWinEntries ? (uint32_t)at : kWinEntries;
+  D.p_dict_len[i] = dict_len;
+  D.p_dict_at[i] = (uint64_t)(i + 1u) * kWinEntries - dict_len;  // the tail of R[i]; R[i + 1] follows it
+}
+
+// One thread per unit of the round, behind DECODE: a unit in front of the first failing one decodes without error to
+// exactly its slot, or TAIL, the scan and DECODE disagree (the verdict is FLATE_HIP_E_INTERNAL then).  The failing
+// unit's verdict is TAIL's.
+__global__ __launch_bounds__(256) void one_check_kernel(OneDecParams D) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= D.count) return;
+  const uint32_t u = D.u0 + i;
+  if (u >= D.dh->first_bad) return;
+  if (D.d_status[i] != 0 || D.d_out_len[i] != D.p_out_off[i + 1u] - D.p_out_off[i]) atomicMin(&D.dh->decode_bad, u);
+}
+
+// One thread: a disagreement of the two decodes, else the first failing unit's verdict, else the header's (a chain that stopped at a refused header), else the
+// trailer's.
+__global__ void one_verdict_kernel(OneDecParams D) {
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  OneDecHead *dh = D.dh;
+  const uint32_t fb = dh->first_bad;
+  dh->out_len = D.total;
+  dh->status = 0;
+  dh->err_off = -1;
+  if (dh->decode_bad != 0xffffffffu) {
+    dh->status = FLATE_HIP_E_INTERNAL;
+    dh->out_len = 0;
+  } else if (fb != 0xffffffffu) {
+    dh->status = D.status[fb];
+    dh->err_off = D.err_off[fb];
+    dh->out_len = D.out_off[fb] + D.produced[fb];
+  } else if (D.head->h.rc != 0) {
+    dh->status = D.head->h.rc;
+    dh->err_off = D.head->h.err_off;
+  } else if (D.wrap != FLATE_HIP_WRAP_RAW) {
+    const uint32_t empty = D.wrap == FLATE_HIP_WRAP_ZLIB ? 1u : 0u;  // the sums of nothing
+    const uint32_t sum = D.sum ? *D.sum : empty;
+    const uint32_t isize_off = D.wrap == FLATE_HIP_WRAP_GZIP ? ((uint32_t)D.total ^ D.one->isize) : 0u;
+    if (((sum ^ D.one->want) | isize_off) != 0u) {
+      dh->status = FLATE_HIP_E_CORRUPT;
+      dh->err_off = (int64_t)D.in_len;
+    }
+  }
+}
+
+}  // namespace flate

@@ -58,6 +58,8 @@ BgzfRead = collections.namedtuple("BgzfRead", "rc out_len n_members bad_member e
 BgzfRanges = collections.namedtuple("BgzfRanges", "rc out_off range_status n_members n_decoded bad_member err_off")
 GZIP_MEMBER_MAX = (1 << 28) - 1  # the option "gzip_member_max": its default and its maximum
 GzipIndex = collections.namedtuple("GzipIndex", "rc n_members out_bytes n_candidates err_off member_off out_off")
+OneRead = collections.namedtuple("OneRead", "rc out_len status err_off n_units n_candidates")
+OneIndex = collections.namedtuple("OneIndex", "rc n_units out_bytes n_candidates status err_off unit_bit out_off")
 GzipRead = collections.namedtuple("GzipRead", "rc out_len n_members bad_member err_off")
 
 
@@ -559,6 +561,99 @@ class FlateEngine:
         fits = k <= int(index_cap)
         return GzipIndex(rc, int(nm.value), int(ob.value), int(nc.value), int(eo.value),
                          moff[:k] if fits else None, ooff[:k] if fits else None)
+
+    def inflate_one_index(self, data, wrap="gzip", index_cap=None, query=False):
+        """Where the units of ONE long stream ("raw", "zlib" or "gzip": what gzip, zlib or pigz write, one member, many
+        blocks) start and where their output goes, found on the GPU from the stream's bits
+        (flate_hip_inflate_one_index) -> OneIndex(rc, n_units, out_bytes, n_candidates, status, err_off, unit_bit,
+        out_off).  A unit starts at bit 0 of the raw stream and at every dynamic-Huffman block header the serial decode
+        reaches; unit_bit (numpy uint64[n_units + 1], bits counted from the raw stream's first byte, the last entry the
+        bit behind the final block) and out_off (the exclusive prefix sum of what the units inflate to).  status: 0, or
+        what the serial decoder says of the stream without looking at its history or its trailer: -4 (at err_off,
+        counted from the raw stream's first byte; a bad container header: 0), -7, or -6 for a unit whose input spans
+        "one_unit_max" bytes or more; the arrays then hold the good units in front.  n_candidates: the bit offsets
+        decoded speculatively.  query=True: only the counts (the arrays are None); index_cap: the arrays' size (default: a
+        unit per 256 bytes of input, and a second call only if the stream has more; given and too small: rc -2, the
+        arrays None).  Other failures raise FlateError."""
+        data, in_ptr, n, device = self._bgzf_in(data)
+        flags = DEVICE_PTRS if device else 0
+        nu, ob, nc, st, eo = C.c_uint32(0), C.c_uint64(0), C.c_uint32(0), C.c_int32(0), C.c_int64(-1)
+
+        def call(cap, a, b):
+            rc = self._L.flate_hip_inflate_one_index(self._ctx, in_ptr, n, WRAPS[wrap], cap, a, b, C.byref(nu),
+                                                     C.byref(ob), C.byref(nc), C.byref(st), C.byref(eo), flags)
+            if rc not in (0, E_CORRUPT, E_UNEXPECTED_EOF, E_TOO_LARGE, E_OUT_TOO_SMALL):
+                self._check(rc)
+            return rc
+
+        def result(rc, a, b):
+            return OneIndex(rc, int(nu.value), int(ob.value), int(nc.value), int(st.value), int(eo.value), a, b)
+
+        if query:
+            return result(call(0, None, None), None, None)
+        # no query first: the discovery is the whole cost of the call.  A unit per 256 bytes of input is more than
+        # zlib writes at its smallest memLevel; a stream that has more takes a second call, sized from the count.
+        for cap in ([int(index_cap)] if index_cap is not None else [n // 256 + 64, None]):
+            cap = int(nu.value) + 1 if cap is None else cap
+            ubit = np.zeros(max(cap, 1), dtype=np.uint64)
+            ooff = np.zeros(max(cap, 1), dtype=np.uint64)
+            rc = call(cap, ubit.ctypes.data, ooff.ctypes.data)
+            k = int(nu.value) + 1
+            if k <= cap:
+                return result(rc, ubit[:k].copy(), ooff[:k].copy())
+        return result(rc, None, None)
+
+    def inflate_one(self, data, wrap="gzip", out=None, out_cap=None):
+        """ONE long stream ("raw", "zlib" or "gzip": one member, many blocks) back into its bytes, its blocks found and
+        decoded in parallel on the GPU and its trailer checked there (flate_hip_inflate_one).  Returns (out, OneRead(rc,
+        out_len, status, err_off, n_units, n_candidates)); the bytes are out[:out_len] (numpy for host data, a torch
+        CUDA tensor for device data).  status is the serial decoder's: 0; -4 at err_off (counted from the raw stream's
+        first byte; a bad header: 0; a trailer that does not match: len(data)); -7; -6 for a unit beyond
+        "one_unit_max"; the bytes in front of an error are delivered.  rc -2 with out_len > capacity: out too small,
+        nothing decoded.  out=None: sized from a gzip member's ISIZE, else (or if that was too little) by a query
+        first.  Other failures raise FlateError."""
+        data, in_ptr, n, device = self._bgzf_in(data)
+        flags = DEVICE_PTRS if device else 0
+        ol, st, eo, nu, nc = C.c_uint64(0), C.c_int32(0), C.c_int64(-1), C.c_uint32(0), C.c_uint32(0)
+
+        def call(out_ptr, cap):
+            rc = self._L.flate_hip_inflate_one(self._ctx, in_ptr, n, WRAPS[wrap], out_ptr, cap, C.byref(ol), C.byref(st),
+                                               C.byref(eo), C.byref(nu), C.byref(nc), flags)
+            if rc not in (0, E_OUT_TOO_SMALL, E_CORRUPT, E_UNEXPECTED_EOF, E_TOO_LARGE):
+                self._check(rc)
+            return OneRead(rc, int(ol.value), int(st.value), int(eo.value), int(nu.value), int(nc.value))
+
+        def room_for(size):
+            if device:
+                import torch
+                return torch.empty(max(size, 16), dtype=torch.uint8, device=data.device)
+            return np.zeros(max(size, 16), dtype=np.uint8)
+
+        if out is None:
+            # a gzip member says in its last four bytes what it inflates to (mod 2^32): room for that, and the one
+            # call is the decode -- no discovery spent on a size query.  A trailer that is wrong only costs the
+            # second call the query would have cost anyway.  (DEFLATE expands at most 1032 times.)
+            hint = 0
+            if wrap == "gzip" and n >= 18:
+                last = data[n - 4:n]
+                hint = int.from_bytes(bytes((last.cpu().numpy() if device else last).tobytes()), "little")
+                if hint > 1032 * n:
+                    hint = 0
+            if hint:
+                out = room_for(hint)
+                q = call(out.data_ptr() if device else out.ctypes.data, hint)
+                if not (q.rc == E_OUT_TOO_SMALL and q.out_len > hint):
+                    return out, q
+            else:
+                q = call(None, 0)
+                if q.rc != E_OUT_TOO_SMALL:  # nothing to deliver: an empty stream, or a verdict without bytes
+                    return (np.zeros(0, np.uint8) if not device else data[:0]), q
+            out = room_for(q.out_len)
+        else:
+            _check_out(out, data, 0, "inflate_one")
+        room = out.numel() if device else out.size
+        cap = room if out_cap is None else min(int(out_cap), room)
+        return out, call(out.data_ptr() if device else out.ctypes.data, cap)
 
     def gzip_read(self, data, out=None, out_cap=None):
         """A plain multi-member gzip file back into its bytes by one call (flate_hip_gzip_read): member discovery,

@@ -940,6 +940,96 @@ inline Err decompress_gzip(Engine &e, const std::vector<uint8_t> &file, std::vec
   return make_error(e, rc);
 }
 
+// ---- one long stream (one .gz, zlib or raw DEFLATE stream of many blocks) ----------------------
+// What index_one found: the units of the stream -- bit 0 of the raw stream and every dynamic block header the serial
+// decode reaches.
+struct OneIndex {
+  std::vector<uint64_t> unit_bit;  // n_units + 1: bits counted from the raw stream's first byte
+  std::vector<uint64_t> out_off;   // n_units + 1: the exclusive prefix sum of what the units inflate to
+  uint32_t n_units = 0;
+  uint64_t out_bytes = 0;          // what the stream inflates to (0 unless status == 0)
+  uint32_t n_candidates = 0;       // bit offsets that were decoded speculatively
+  int64_t err_off = -1;            // counted from the raw stream's first byte
+  int status = 0;                  // the FLATE_HIP_E_* code behind the error (0 = none)
+};
+
+// index_one: where the blocks of ONE long stream start and where their output goes, found on the GPU
+// (flate_hip_inflate_one_index).  Errors: corrupt_input_error(err_off) for a bad container header (offset 0) or a block
+// the decoder refuses, err_unexpected_eof for a stream that is cut short, FLATE_HIP_E_TOO_LARGE for a unit beyond the
+// option "one_unit_max"; `ix` then holds the good units in front.
+inline Err index_one(Engine &e, const std::vector<uint8_t> &stream, Wrap wrap, OneIndex &ix) {
+  if (!e.ok()) return make_error(e, e.status());
+  ix = OneIndex();
+  int32_t st = 0;
+  int rc = 0;
+  // no query first: the discovery is the whole cost of the call.  A unit per 256 bytes of input is more than zlib
+  // writes at its smallest memLevel; a stream that has more takes a second call, sized from the count.
+  size_t cap = stream.size() / 256 + 64;
+  for (int attempt = 0; attempt < 2; ++attempt) {
+    ix.unit_bit.assign(cap, 0);
+    ix.out_off.assign(cap, 0);
+    rc = flate_hip_inflate_one_index(e.ctx(), stream.data(), stream.size(), wrap_code(wrap), cap, ix.unit_bit.data(),
+                                     ix.out_off.data(), &ix.n_units, &ix.out_bytes, &ix.n_candidates, &st, &ix.err_off, 0);
+    if ((size_t)ix.n_units + 1 <= cap) break;
+    cap = (size_t)ix.n_units + 1;
+  }
+  ix.unit_bit.resize(std::min(cap, (size_t)ix.n_units + 1));
+  ix.out_off.resize(ix.unit_bit.size());
+  ix.status = rc;
+  if (rc == 0) return std::nullopt;
+  if (rc == FLATE_HIP_E_CORRUPT) return corrupt_input_error(ix.err_off);
+  if (rc == FLATE_HIP_E_UNEXPECTED_EOF) return err_unexpected_eof();
+  return make_error(e, rc);
+}
+
+// What decompress_one found beside the bytes.
+struct OneInfo {
+  uint32_t n_units = 0;
+  uint32_t n_candidates = 0;
+  int64_t err_off = -1;  // counted from the raw stream's first byte; a trailer that does not match: the stream's size
+  int status = 0;        // the FLATE_HIP_E_* code behind the error (0 = none)
+};
+
+// decompress_one: ONE long stream -- a .gz, zlib or raw DEFLATE stream of many blocks -- back into its bytes, its blocks
+// found and decoded in parallel and its trailer checked on the GPU (flate_hip_inflate_one: one call with room for a
+// gzip member's ISIZE; else, or if that was too little, a size query and the decode).  Errors are the serial
+// decoder's: corrupt_input_error(err_off), err_unexpected_eof, FLATE_HIP_E_TOO_LARGE for a unit beyond the option
+// "one_unit_max"; `out` then holds the bytes in front of the error.
+inline Err decompress_one(Engine &e, const std::vector<uint8_t> &stream, Wrap wrap, std::vector<uint8_t> &out,
+                          OneInfo *info = nullptr) {
+  if (!e.ok()) return make_error(e, e.status());
+  OneInfo I;
+  int32_t st = 0;
+  uint64_t need = 0, len = 0;
+  out.clear();
+  // a gzip member says in its last four bytes what it inflates to (mod 2^32): with room for that the first call is
+  // the decode, and no discovery is spent on a size query; a trailer that is wrong costs the second call the query
+  // would have cost anyway.  (DEFLATE expands at most 1032 times.)
+  const size_t n = stream.size();
+  if (wrap == Wrap::Gzip && n >= 18) {
+    need = (uint64_t)stream[n - 4] | ((uint64_t)stream[n - 3] << 8) | ((uint64_t)stream[n - 2] << 16) | ((uint64_t)stream[n - 1] << 24);
+    if (need > 1032ull * n) need = 0;
+  }
+  std::vector<uint8_t> buf(need ? need + 8 : 0);
+  uint64_t cap = need;
+  int rc = flate_hip_inflate_one(e.ctx(), stream.data(), n, wrap_code(wrap), cap ? buf.data() : nullptr, cap, &len, &st,
+                                 &I.err_off, &I.n_units, &I.n_candidates, 0);
+  if (rc == FLATE_HIP_E_OUT_TOO_SMALL && len > cap) {  // (len: the size needed)
+    cap = len;
+    buf.assign(cap + 8, 0);
+    rc = flate_hip_inflate_one(e.ctx(), stream.data(), n, wrap_code(wrap), buf.data(), cap, &len, &st, &I.err_off,
+                               &I.n_units, &I.n_candidates, 0);
+  }
+  if (cap && (rc == 0 || rc == FLATE_HIP_E_CORRUPT || rc == FLATE_HIP_E_UNEXPECTED_EOF))
+    out.assign(buf.begin(), buf.begin() + std::min(len, cap));
+  I.status = rc;
+  if (info) *info = I;
+  if (rc == 0) return std::nullopt;
+  if (rc == FLATE_HIP_E_CORRUPT) return corrupt_input_error(I.err_off);
+  if (rc == FLATE_HIP_E_UNEXPECTED_EOF) return err_unexpected_eof();
+  return make_error(e, rc);
+}
+
 // One range of decompress_bgzf_ranges: positions in the file's uncompressed bytes, or -- virtual_offsets -- BGZF
 // virtual offsets (coffset << 16 | uoffset, as BAM, tabix and CSI indexes store them).
 struct BgzfRange {
