@@ -29,6 +29,7 @@
 #include <string>
 
 #include "block_scan.h"
+#include "carve.h"
 #include "checksum_clip.h"
 #include "flate_hip.h"
 #include "flate_kernels.h"
@@ -356,13 +357,16 @@ __global__ __launch_bounds__(1024) void checksum_join_kernel(JoinParams P) {
 using namespace flate;
 
 namespace {
-// checksum_device's arrays in slot 0 of the ctx's scratch: offsets for np pieces of n streams, and the bytes of all
-struct Carve {
-  size_t poff, wsum, ioff, plen, pbase, crc, asum, nlen, bytes = 0;
-  Carve(size_t np, size_t n) {
-    auto carve = [&](size_t b) { const size_t o = bytes; bytes += (b + 255) & ~(size_t)255; return o; };
-    poff = carve(np * 8), wsum = carve(np * 8), ioff = carve((n + 1) * 8), plen = carve(np * 4 + 4);
-    pbase = carve((n + 1) * 4 + 4), crc = carve(np * 4), asum = carve(np * 4), nlen = carve(n * 8 + 8);
+// checksum_device's arrays in slot 0 of the ctx's scratch, for np pieces of n streams; bytes: of all of them
+struct Arrays {
+  uint64_t *poff, *wsum, *ioff, *nlen;
+  uint32_t *plen, *pbase, *crc, *asum;
+  size_t bytes;
+  Arrays(void *base, size_t np, size_t n) {
+    flate_host::Carve k{base};
+    k.take(poff, np), k.take(wsum, np), k.take(ioff, n + 1), k.take(plen, np + 1);
+    k.take(pbase, n + 2), k.take(crc, np), k.take(asum, np), k.take(nlen, n + 1);
+    bytes = k.at;
   }
 };
 size_t count_pieces(const uint64_t *in_off, uint32_t n) {
@@ -372,7 +376,7 @@ size_t count_pieces(const uint64_t *in_off, uint32_t n) {
 }
 }  // namespace
 
-size_t flate::checksum_scratch_bytes(const uint64_t *in_off, uint32_t n) { return Carve(count_pieces(in_off, n), n).bytes; }
+size_t flate::checksum_scratch_bytes(const uint64_t *in_off, uint32_t n) { return Arrays(nullptr, count_pieces(in_off, n), n).bytes; }
 
 // uploads of one checksum_device call through the ctx's staging: piece offsets and lengths, piece_base, in_off
 size_t flate::checksum_ctl_up_bytes(const uint64_t *in_off, uint32_t n) {
@@ -452,34 +456,30 @@ int checksum_run(flate_hip_ctx *c, const uint8_t *d_in, const uint64_t *in_off, 
   const uint32_t np = (uint32_t)plen.size();
   // one grow-only scratch of the ctx, carved into the call's arrays (round 4 did nine hipMalloc / hipFree
   // pairs per call: hipFree drains the whole device, i.e. every other context and the host pipelines' lanes)
-  struct Dev { void *p = nullptr; } d_poff, d_plen, d_pbase, d_ioff, d_crc, d_asum, d_wsum, d_nlen;
+  void *base = nullptr;
   {
-    const Carve o(np, n);
-    void *base = nullptr;
-    const int rc = ctx_scratch(c, 0, o.bytes, &base);
+    const int rc = ctx_scratch(c, 0, Arrays(nullptr, np, n).bytes, &base);
     if (rc != FLATE_HIP_OK) return rc;
-    uint8_t *b8 = (uint8_t *)base;
-    d_poff.p = b8 + o.poff, d_wsum.p = b8 + o.wsum, d_ioff.p = b8 + o.ioff, d_plen.p = b8 + o.plen;
-    d_pbase.p = b8 + o.pbase, d_crc.p = b8 + o.crc, d_asum.p = b8 + o.asum, d_nlen.p = b8 + o.nlen;
   }
+  const Arrays d(base, np, n);
   // the index arrays travel through the ctx's pinned staging and its copy kernel, not through DMA
   // commands that queue behind whatever bulk copy another thread has in flight (flate_api.hip: ctl_up)
   {
-    int rc = ctx_ctl_up(c, d_poff.p, poff.data(), (size_t)np * 8);
-    if (rc == FLATE_HIP_OK && !clip) rc = ctx_ctl_up(c, d_plen.p, plen.data(), (size_t)np * 4);
-    if (rc == FLATE_HIP_OK) rc = ctx_ctl_up(c, d_pbase.p, pbase.data(), ((size_t)n + 1) * 4);
-    if (rc == FLATE_HIP_OK) rc = ctx_ctl_up(c, d_ioff.p, in_off, ((size_t)n + 1) * 8);
+    int rc = ctx_ctl_up(c, d.poff, poff.data(), (size_t)np * 8);
+    if (rc == FLATE_HIP_OK && !clip) rc = ctx_ctl_up(c, d.plen, plen.data(), (size_t)np * 4);
+    if (rc == FLATE_HIP_OK) rc = ctx_ctl_up(c, d.pbase, pbase.data(), ((size_t)n + 1) * 4);
+    if (rc == FLATE_HIP_OK) rc = ctx_ctl_up(c, d.ioff, in_off, ((size_t)n + 1) * 8);
     if (rc != FLATE_HIP_OK) return rc;
   }
   if (clip) {  // the pieces' lengths come from what the decoder produced
     ClipParams K{};
-    K.slot_off = (const uint64_t *)d_ioff.p;
-    K.piece_base = (const uint32_t *)d_pbase.p;
+    K.slot_off = d.ioff;
+    K.piece_base = d.pbase;
     K.produced = clip->out_len;
     K.status = clip->status;
     K.bad = clip->bad;
-    K.piece_len = (uint32_t *)d_plen.p;
-    K.n_len = (uint64_t *)d_nlen.p;
+    K.piece_len = d.plen;
+    K.n_len = d.nlen;
     K.n_streams = n;
     hipLaunchKernelGGL(checksum_clip_kernel, dim3((n + 3) / 4), dim3(256), 0, st, K);
   }
@@ -487,14 +487,14 @@ int checksum_run(flate_hip_ctx *c, const uint8_t *d_in, const uint64_t *in_off, 
   if (np) {
     PieceParams P{};
     P.in = d_in;
-    P.piece_off = (const uint64_t *)d_poff.p;
-    P.piece_len = (const uint32_t *)d_plen.p;
+    P.piece_off = d.poff;
+    P.piece_len = d.plen;
     P.n_pieces = np;
     P.want_crc = kind == FLATE_HIP_CHECKSUM_CRC32;
     P.want_adler = kind == FLATE_HIP_CHECKSUM_ADLER32;
-    P.crc = (uint32_t *)d_crc.p;
-    P.asum = (uint32_t *)d_asum.p;
-    P.wsum = (uint64_t *)d_wsum.p;
+    P.crc = d.crc;
+    P.asum = d.asum;
+    P.wsum = d.wsum;
     P.x2n = x2n;
     uint32_t blocks = (np + 3) / 4;
     const uint32_t cap = 8u * (uint32_t)ctx_num_cus(c);  // 32 wavefronts per CU
@@ -505,18 +505,18 @@ int checksum_run(flate_hip_ctx *c, const uint8_t *d_in, const uint64_t *in_off, 
     if (stage >= 0) ctx_stage_begin(c, stage);
   }
   FoldParams F{};
-  F.in_off = (const uint64_t *)d_ioff.p;
-  F.piece_base = (const uint32_t *)d_pbase.p;
-  F.piece_len = (const uint32_t *)d_plen.p;
-  F.crc = (const uint32_t *)d_crc.p;
-  F.asum = (const uint32_t *)d_asum.p;
-  F.wsum = (const uint64_t *)d_wsum.p;
+  F.in_off = d.ioff;
+  F.piece_base = d.pbase;
+  F.piece_len = d.plen;
+  F.crc = d.crc;
+  F.asum = d.asum;
+  F.wsum = d.wsum;
   F.out = d_sums;
   F.n_streams = n;
   F.want_crc = kind == FLATE_HIP_CHECKSUM_CRC32;
   F.max_pieces = 0;
   for (uint32_t i = 0; i < n; ++i) F.max_pieces = pbase[i + 1] - pbase[i] > F.max_pieces ? pbase[i + 1] - pbase[i] : F.max_pieces;
-  F.n_len = clip ? (const uint64_t *)d_nlen.p : nullptr;
+  F.n_len = clip ? d.nlen : nullptr;
   F.x2n = x2n;
   hipLaunchKernelGGL(checksum_fold_kernel, dim3((n + 3) / 4), dim3(256), 0, st, F);
   if (stage >= 0) ctx_stage_end(c, stage);

@@ -49,6 +49,31 @@ int ensure(flate_hip_ctx *c, DevBuf &b, size_t bytes) {
   return FLATE_HIP_OK;
 }
 
+int stage_input(flate_hip_ctx *c, const uint8_t *in, uint64_t in_len, uint32_t flags, const uint8_t **d_in) {
+  HIP_TRY(c, hipSetDevice(c->device));
+  *d_in = in;
+  if (flags & FLATE_HIP_DEVICE_PTRS) return FLATE_HIP_OK;
+  const int rc = ensure(c, c->d_in, in_len + 16);
+  if (rc) return rc;
+  HIP_TRY(c, hipMemcpyAsync(c->d_in.p, in, in_len, hipMemcpyHostToDevice, c->stream));
+  *d_in = (const uint8_t *)c->d_in.p;
+  return FLATE_HIP_OK;
+}
+
+int tiles_for(const uint8_t *d_in, uint64_t lo, uint64_t len, uint32_t *n_tiles) {
+  const uint64_t tiles = chain_tiles(reinterpret_cast<uintptr_t>(d_in) & 15u, lo, len);
+  if (tiles > 0x7fffffffull) return FLATE_HIP_E_TOO_LARGE;
+  *n_tiles = (uint32_t)tiles;
+  return FLATE_HIP_OK;
+}
+
+int chain_size(ChainParams &C, uint32_t cap) {
+  if (cap > 0x7ffffff0u) return FLATE_HIP_E_TOO_LARGE;
+  C.cap = cap;
+  C.path_len = 1u << bgzf_rounds(cap);
+  return FLATE_HIP_OK;
+}
+
 // ---- small index arrays: host <-> device through pinned staging and a copy kernel (copy_ctl_kernel) ----
 // ctl_begin: room for the call's uploads / downloads (a staging buffer only grows between calls: the
 // stream is drained first).  ctl_up: stage + launch.  ctl_down: launch into the staging; the bytes reach

@@ -624,54 +624,33 @@ namespace {
 // arrays are sized for bgzf_first_cap candidates; a file with more (H.n_cand, counted by the first attempt) takes a
 // second attempt sized from that count.  Counted in no profiling stage.
 int bgzf_discover(flate_hip_ctx *c, const uint8_t *d_in, uint64_t in_len, BgzfHead &H, BgzfParams &P) {
-  const uint64_t A = reinterpret_cast<uintptr_t>(d_in) & 15u;
-  const uint64_t tiles = (A + in_len + kBgzfTile - 1) / kBgzfTile;
-  if (tiles > 0x7fffffffull) return FLATE_HIP_E_TOO_LARGE;
+  int rc;
+  P = BgzfParams{};
+  ChainParams &C = P.C;
+  C.in = d_in;
+  C.in_len = in_len;
+  if ((rc = tiles_for(d_in, 0, in_len, &C.n_tiles))) return rc;
   uint32_t cap = bgzf_first_cap(in_len);
   for (int attempt = 0; attempt < 2; ++attempt) {
-    if (cap > 0x7ffffff0u) return FLATE_HIP_E_TOO_LARGE;
-    const uint32_t rounds = bgzf_rounds(cap);
-    P = BgzfParams{};
-    P.in = d_in;
-    P.in_len = in_len;
-    P.n_tiles = (uint32_t)tiles;
-    P.cap = cap;
-    P.path_len = 1u << rounds;
-    size_t at = 0;
-    auto carve = [&](size_t bytes) {
-      const size_t here = at;
-      at += (bytes + 255) & ~(size_t)255;
-      return here;
-    };
-    const size_t o_head = carve(sizeof(BgzfHead)), o_tile = carve(((size_t)P.n_tiles + 1) * 4),
-                 o_coff = carve((size_t)cap * 8), o_ctot = carve((size_t)cap * 4), o_j0 = carve(((size_t)cap + 2) * 4),
-                 o_j1 = carve(((size_t)cap + 2) * 4), o_path = carve((size_t)P.path_len * 4),
-                 o_isize = carve((size_t)cap * 4), o_moff = carve(((size_t)cap + 1) * 8),
-                 o_ooff = carve(((size_t)cap + 1) * 8);
-    const int rc = ensure(c, c->d_bgzf, at);  // (a failed allocation is FLATE_HIP_E_HIP, never a truncated result)
+    if ((rc = chain_size(C, cap))) return rc;
+    rc = carve(c, c->d_bgzf, [&](Carve &k) {
+      k.take(C.head, 1);
+      k.take(C.tile_cnt, (size_t)C.n_tiles + 1);
+      k.take(C.cand_off, cap);
+      k.take(P.cand_total, cap);
+      k.take(C.jump[0], (size_t)cap + 2);
+      k.take(C.jump[1], (size_t)cap + 2);
+      k.take(C.path, C.path_len);
+      k.take(P.isize, cap);
+      k.take(C.member_off, (size_t)cap + 1);
+      k.take(C.out_off, (size_t)cap + 1);
+    });
     if (rc) return rc;
-    uint8_t *b = (uint8_t *)c->d_bgzf.p;
-    P.head = (BgzfHead *)(b + o_head);
-    P.tile_cnt = (uint32_t *)(b + o_tile);
-    P.cand_off = (uint64_t *)(b + o_coff);
-    P.cand_total = (uint32_t *)(b + o_ctot);
-    P.jump[0] = (uint32_t *)(b + o_j0);
-    P.jump[1] = (uint32_t *)(b + o_j1);
-    P.path = (uint32_t *)(b + o_path);
-    P.isize = (uint32_t *)(b + o_isize);
-    P.member_off = (uint64_t *)(b + o_moff);
-    P.out_off = (uint64_t *)(b + o_ooff);
-    const uint32_t node_blocks = (uint32_t)(((uint64_t)cap + 2 + 255) / 256);
-    hipLaunchKernelGGL(bgzf_count_kernel, dim3(P.n_tiles), dim3(256), 0, c->stream, P);
-    hipLaunchKernelGGL(bgzf_scan_kernel, dim3(1), dim3(1024), 0, c->stream, P);
-    hipLaunchKernelGGL(bgzf_fill_kernel, dim3(P.n_tiles), dim3(256), 0, c->stream, P);
-    hipLaunchKernelGGL(bgzf_link_kernel, dim3(node_blocks), dim3(256), 0, c->stream, P);
-    for (uint32_t j = 0; j < rounds; ++j)
-      hipLaunchKernelGGL(bgzf_round_kernel, dim3(node_blocks), dim3(256), 0, c->stream, P, j);
-    hipLaunchKernelGGL(bgzf_finish_kernel, dim3((P.path_len + 255) / 256), dim3(256), 0, c->stream, P);
-    hipLaunchKernelGGL(bgzf_out_scan_kernel, dim3(1), dim3(1024), 0, c->stream, P);
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipMemcpyAsync(&H, P.head, sizeof H, hipMemcpyDeviceToHost, c->stream));
+    hipLaunchKernelGGL(bgzf_count_kernel, dim3(C.n_tiles), dim3(256), 0, c->stream, P);
+    hipLaunchKernelGGL(chain_scan_kernel, dim3(1), dim3(1024), 0, c->stream, C);
+    hipLaunchKernelGGL(bgzf_fill_kernel, dim3(C.n_tiles), dim3(256), 0, c->stream, P);
+    if ((rc = chain_tail(c, C, bgzf_link_kernel, P, bgzf_finish_kernel, bgzf_out_scan_kernel, P))) return rc;
+    HIP_TRY(c, hipMemcpyAsync(&H, C.head, sizeof H, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     if (H.n_cand <= cap) return FLATE_HIP_OK;
     // more candidates than the arrays hold: nothing behind the scan has run; once more, sized from the count
@@ -679,18 +658,6 @@ int bgzf_discover(flate_hip_ctx *c, const uint8_t *d_in, uint64_t in_len, BgzfHe
   }
   c->hip_err = "BGZF discovery: the candidate count changed between two passes";
   return FLATE_HIP_E_INTERNAL;
-}
-
-// in[0, in_len) on the device: the caller's buffer, or the ctx's staged copy of it
-int bgzf_stage(flate_hip_ctx *c, const uint8_t *in, uint64_t in_len, uint32_t flags, const uint8_t **d_in) {
-  HIP_TRY(c, hipSetDevice(c->device));
-  *d_in = in;
-  if (flags & FLATE_HIP_DEVICE_PTRS) return FLATE_HIP_OK;
-  const int rc = ensure(c, c->d_in, in_len + 16);
-  if (rc) return rc;
-  HIP_TRY(c, hipMemcpyAsync(c->d_in.p, in, in_len, hipMemcpyHostToDevice, c->stream));
-  *d_in = (const uint8_t *)c->d_in.p;
-  return FLATE_HIP_OK;
 }
 
 // The tail flate_hip_bgzf_read and flate_hip_gzip_read share, behind a discovery that found a sound chain of n members
@@ -755,7 +722,7 @@ int flate_hip_bgzf_index(flate_hip_ctx *c, const uint8_t *in, uint64_t in_len, u
     return FLATE_HIP_OK;
   }
   const uint8_t *d_in = nullptr;
-  if ((rc = bgzf_stage(c, in, in_len, flags, &d_in))) return rc;
+  if ((rc = stage_input(c, in, in_len, flags, &d_in))) return rc;
   BgzfHead H{};
   BgzfParams P{};
   if ((rc = bgzf_discover(c, d_in, in_len, H, P))) return rc;
@@ -769,8 +736,8 @@ int flate_hip_bgzf_index(flate_hip_ctx *c, const uint8_t *in, uint64_t in_len, u
   if (!member_off) return FLATE_HIP_OK;
   const uint64_t entries = (uint64_t)H.n_members + 1;
   if (index_cap < entries) return FLATE_HIP_E_OUT_TOO_SMALL;
-  HIP_TRY(c, hipMemcpyAsync(member_off, P.member_off, entries * 8, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(out_off, P.out_off, entries * 8, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(member_off, P.C.member_off, entries * 8, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(out_off, P.C.out_off, entries * 8, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   return FLATE_HIP_OK;
 }
@@ -791,7 +758,7 @@ int flate_hip_bgzf_read(flate_hip_ctx *c, const uint8_t *in, uint64_t in_len, ui
   if (in_len == 0) return FLATE_HIP_OK;
   try {
     const uint8_t *d_in = nullptr;
-    if ((rc = bgzf_stage(c, in, in_len, flags, &d_in))) return rc;
+    if ((rc = stage_input(c, in, in_len, flags, &d_in))) return rc;
     BgzfHead H{};
     BgzfParams P{};
     if ((rc = bgzf_discover(c, d_in, in_len, H, P))) return rc;
@@ -805,7 +772,7 @@ int flate_hip_bgzf_read(flate_hip_ctx *c, const uint8_t *in, uint64_t in_len, ui
     if (eof_marker) *eof_marker = (int)H.eof_marker;
     *out_len = H.out_bytes;
     if (H.out_bytes > out_cap) return FLATE_HIP_E_OUT_TOO_SMALL;
-    return members_read(c, d_in, n, P.member_off, P.out_off, H.out_bytes, out, flags, bad_member, err_off);
+    return members_read(c, d_in, n, P.C.member_off, P.C.out_off, H.out_bytes, out, flags, bad_member, err_off);
   } catch (const std::exception &e) {  // (out of host memory in an index vector)
     c->hip_err = e.what();
     return FLATE_HIP_E_INTERNAL;
@@ -848,7 +815,7 @@ int flate_hip_bgzf_read_ranges(flate_hip_ctx *c, const uint8_t *in, uint64_t in_
   try {
     const bool dev = (flags & FLATE_HIP_DEVICE_PTRS) != 0;
     const uint8_t *d_in = nullptr;
-    if ((rc = bgzf_stage(c, in, in_len, flags, &d_in))) return rc;
+    if ((rc = stage_input(c, in, in_len, flags, &d_in))) return rc;
     for (int k = 0; k < FLATE_HIP_STAGE_COUNT; ++k) c->stage_ms[k] = 0;
     BgzfHead H{};
     BgzfParams P{};
@@ -865,67 +832,60 @@ int flate_hip_bgzf_read_ranges(flate_hip_ctx *c, const uint8_t *in, uint64_t in_
     }
 
     // locate, select, layout: the arrays carved from one buffer, what the host reads back as one block at its end
-    size_t at = 0;
-    auto carve = [&](size_t bytes) {
-      const size_t here = at;
-      at += (bytes + 255) & ~(size_t)255;
-      return here;
-    };
-    const size_t o_begin = carve((size_t)nr * 8), o_end = carve((size_t)nr * 8), o_diff = carve(((size_t)n + 1) * 4),
-                 o_rank = carve((size_t)n * 4 + 4), o_sat = carve((size_t)n * 8 + 8), o_rb = carve((size_t)nr * 8),
-                 o_rlen = carve((size_t)nr * 8), o_rfirst = carve((size_t)nr * 4), o_rlast = carve((size_t)nr * 4),
-                 o_rsrc = carve((size_t)nr * 8);
-    const size_t o_back = at;
-    const size_t o_head = carve(sizeof(BgzfRangeHead)), o_roff = carve(((size_t)nr + 1) * 8), o_rst = carve((size_t)nr * 4),
-                 o_rlo = carve((size_t)nr * 4), o_rhi = carve((size_t)nr * 4), o_sel = carve((size_t)n * sizeof(BgzfSel) + 8);
-    const size_t back_bytes = at - o_back;
-    if ((rc = ensure(c, c->d_bgzf_rng, at))) return rc;  // (a failed allocation is FLATE_HIP_E_HIP)
-    uint8_t *b = (uint8_t *)c->d_bgzf_rng.p;
     BgzfRangeParams Q{};
-    Q.member_off = P.member_off;
-    Q.out_off_m = P.out_off;
+    Q.member_off = P.C.member_off;
+    Q.out_off_m = P.C.out_off;
     Q.isize = P.isize;
     Q.n_members = n;
     Q.n_ranges = nr;
     Q.pos_kind = pos_kind;
-    Q.begin = (const uint64_t *)(b + o_begin);
-    Q.end = (const uint64_t *)(b + o_end);
-    Q.diff = (int32_t *)(b + o_diff);
-    Q.rank = (uint32_t *)(b + o_rank);
-    Q.scratch_at = (uint64_t *)(b + o_sat);
-    Q.r_b = (uint64_t *)(b + o_rb);
-    Q.r_len = (uint64_t *)(b + o_rlen);
-    Q.r_first = (uint32_t *)(b + o_rfirst);
-    Q.r_last = (uint32_t *)(b + o_rlast);
-    Q.r_src = (uint64_t *)(b + o_rsrc);
-    Q.head = (BgzfRangeHead *)(b + o_head);
-    Q.r_out_off = (uint64_t *)(b + o_roff);
-    Q.r_status = (int32_t *)(b + o_rst);
-    Q.r_rank_lo = (uint32_t *)(b + o_rlo);
-    Q.r_rank_hi = (uint32_t *)(b + o_rhi);
-    Q.sel = (BgzfSel *)(b + o_sel);
-    HIP_TRY(c, hipMemcpyAsync(b + o_begin, begin, (size_t)nr * 8, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(b + o_end, end, (size_t)nr * 8, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemsetAsync(b + o_diff, 0, ((size_t)n + 1) * 4, c->stream));
+    uint64_t *d_begin, *d_end;
+    size_t o_back = 0, o_end = 0;
+    rc = carve(c, c->d_bgzf_rng, [&](Carve &k) {
+      k.take(d_begin, nr);
+      k.take(d_end, nr);
+      k.take(Q.diff, (size_t)n + 1);
+      k.take(Q.rank, (size_t)n + 1);
+      k.take(Q.scratch_at, (size_t)n + 1);
+      k.take(Q.r_b, nr);
+      k.take(Q.r_len, nr);
+      k.take(Q.r_first, nr);
+      k.take(Q.r_last, nr);
+      k.take(Q.r_src, nr);
+      o_back = k.at;
+      k.take(Q.head, 1);
+      k.take(Q.r_out_off, (size_t)nr + 1);
+      k.take(Q.r_status, nr);
+      k.take(Q.r_rank_lo, nr);
+      k.take(Q.r_rank_hi, nr);
+      k.take(Q.sel, n, 8);
+      o_end = k.at;
+    });
+    if (rc) return rc;
+    Q.begin = d_begin, Q.end = d_end;
+    const size_t back_bytes = o_end - o_back;
+    const uint8_t *d_back = (const uint8_t *)c->d_bgzf_rng.p + o_back;
+    HIP_TRY(c, hipMemcpyAsync(d_begin, begin, (size_t)nr * 8, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(d_end, end, (size_t)nr * 8, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemsetAsync(Q.diff, 0, ((size_t)n + 1) * 4, c->stream));
     hipLaunchKernelGGL(bgzf_range_locate_kernel, dim3((nr + 255u) / 256u), dim3(256), 0, c->stream, Q);
     hipLaunchKernelGGL(bgzf_range_select_kernel, dim3(1), dim3(1024), 0, c->stream, Q);
     hipLaunchKernelGGL(bgzf_range_layout_kernel, dim3(1), dim3(1024), 0, c->stream, Q);
     HIP_TRY(c, hipGetLastError());
     std::vector<uint8_t> back(back_bytes);
-    HIP_TRY(c, hipMemcpyAsync(back.data(), b + o_back, back_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(back.data(), d_back, back_bytes, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    BgzfRangeHead RH;
-    memcpy(&RH, back.data() + (o_head - o_back), sizeof RH);
-    const int32_t *r_status = (const int32_t *)(back.data() + (o_rst - o_back));
-    const uint32_t *r_lo = (const uint32_t *)(back.data() + (o_rlo - o_back));
-    const uint32_t *r_hi = (const uint32_t *)(back.data() + (o_rhi - o_back));
-    const BgzfSel *sel = (const BgzfSel *)(back.data() + (o_sel - o_back));
+    auto got = [&](const auto *d) { return (decltype(d))(back.data() + ((const uint8_t *)d - d_back)); };  // d's host copy
+    const BgzfRangeHead RH = *got(Q.head);
+    const int32_t *r_status = got(Q.r_status);
+    const uint32_t *r_lo = got(Q.r_rank_lo), *r_hi = got(Q.r_rank_hi);
+    const BgzfSel *sel = got(Q.sel);
     const uint32_t ns = RH.n_sel;
     if (ns > n) {
       c->hip_err = "BGZF ranges: more members selected than the file has";
       return FLATE_HIP_E_INTERNAL;
     }
-    memcpy(out_off, back.data() + (o_roff - o_back), ((size_t)nr + 1) * 8);
+    memcpy(out_off, got(Q.r_out_off), ((size_t)nr + 1) * 8);
     if (n_decoded) *n_decoded = ns;
     if (range_status)
       for (uint32_t r = 0; r < nr; ++r) range_status[r] = r_status[r];
@@ -1002,83 +962,65 @@ namespace {
 // The discovery over d_in[0, in_len) (DEVICE memory) on the ctx's stream: count and scan, ONE read-back of the candidate
 // count (the launches behind it have a thread or a wavefront per candidate), then fill, frame_parse_kernel, one
 // size-only launch of the batch decoders over all candidates, link, rounds, finish, out-scan.  H = the result words once
-// the stream has drained; P.B.member_off / P.B.out_off = the index, still on the device (null when the file holds no
+// the stream has drained; P.C.member_off / P.C.out_off = the index, still on the device (null when the file holds no
 // candidate: H then says FLATE_HIP_E_CORRUPT at offset 0).  The discovery kernels are counted in no profiling stage.
 int gzip_discover(flate_hip_ctx *c, const uint8_t *d_in, uint64_t in_len, BgzfHead &H, GzipParams &P) {
-  const uint64_t A = reinterpret_cast<uintptr_t>(d_in) & 15u;
-  const uint64_t tiles = (A + in_len + kBgzfTile - 1) / kBgzfTile;
-  if (tiles > 0x7fffffffull) return FLATE_HIP_E_TOO_LARGE;
-  size_t at = 0;
-  auto carve = [&](size_t bytes) {
-    const size_t here = at;
-    at += (bytes + 255) & ~(size_t)255;
-    return here;
-  };
-  P = GzipParams{};
-  P.B.in = d_in;
-  P.B.in_len = in_len;
-  P.B.n_tiles = (uint32_t)tiles;
-  P.member_max = c->gzip_member_max;
   int rc;
-  {
-    const size_t o_head = carve(sizeof(BgzfHead)), o_tile = carve(((size_t)P.B.n_tiles + 1) * 4);
-    if ((rc = ensure(c, c->d_gzip_tiles, at))) return rc;
-    uint8_t *b = (uint8_t *)c->d_gzip_tiles.p;
-    P.B.head = (BgzfHead *)(b + o_head);
-    P.B.tile_cnt = (uint32_t *)(b + o_tile);
-  }
-  hipLaunchKernelGGL(gzip_count_kernel, dim3(P.B.n_tiles), dim3(256), 0, c->stream, P);
-  hipLaunchKernelGGL(bgzf_scan_kernel, dim3(1), dim3(1024), 0, c->stream, P.B);
+  P = GzipParams{};
+  ChainParams &C = P.C;
+  C.in = d_in;
+  C.in_len = in_len;
+  P.member_max = c->gzip_member_max;
+  if ((rc = tiles_for(d_in, 0, in_len, &C.n_tiles))) return rc;
+  rc = carve(c, c->d_gzip_tiles, [&](Carve &k) {
+    k.take(C.head, 1);
+    k.take(C.tile_cnt, (size_t)C.n_tiles + 1);
+  });
+  if (rc) return rc;
+  hipLaunchKernelGGL(gzip_count_kernel, dim3(C.n_tiles), dim3(256), 0, c->stream, P);
+  hipLaunchKernelGGL(chain_scan_kernel, dim3(1), dim3(1024), 0, c->stream, C);
   HIP_TRY(c, hipGetLastError());
-  HIP_TRY(c, hipMemcpyAsync(&H, P.B.head, sizeof H, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(&H, C.head, sizeof H, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   const uint32_t cap = H.n_cand;
-  if (cap > 0x7ffffff0u) return FLATE_HIP_E_TOO_LARGE;  // (the count saturates at 2^32 - 1)
+  if ((rc = chain_size(C, cap))) return rc;  // (the count saturates at 2^32 - 1)
   if (cap == 0) return FLATE_HIP_OK;  // (the scan kernel has left the verdict: no member can start at offset 0)
 
-  const uint32_t rounds = bgzf_rounds(cap);
-  P.B.cap = cap;
-  P.B.path_len = 1u << rounds;
-  at = 0;
-  const size_t n = cap;
-  const size_t o_coff = carve((n + 1) * 8), o_cend = carve(n * 8), o_poff = carve((n + 1) * 8), o_pend = carve(n * 8),
-               o_want = carve(n * 4), o_isize = carve(n * 4), o_bad = carve(n * 4), o_dict = carve(n * 4),
-               o_olen = carve(n * 8), o_st = carve(n * 4), o_err = carve(n * 8), o_used = carve(n * 8),
-               o_j0 = carve((n + 2) * 4), o_j1 = carve((n + 2) * 4), o_path = carve((size_t)P.B.path_len * 4),
-               o_msize = carve(n * 8), o_moff = carve((n + 1) * 8), o_ooff = carve((n + 1) * 8);
-  if ((rc = ensure(c, c->d_gzip, at))) return rc;  // (a failed allocation is FLATE_HIP_E_HIP, never a truncated result)
-  uint8_t *b = (uint8_t *)c->d_gzip.p;
-  P.B.cand_off = (uint64_t *)(b + o_coff);
-  P.cand_end = (uint64_t *)(b + o_cend);
-  P.B.jump[0] = (uint32_t *)(b + o_j0);
-  P.B.jump[1] = (uint32_t *)(b + o_j1);
-  P.B.path = (uint32_t *)(b + o_path);
-  P.msize = (uint64_t *)(b + o_msize);
-  P.B.member_off = (uint64_t *)(b + o_moff);
-  P.B.out_off = (uint64_t *)(b + o_ooff);
   FrameReadParams R{};
+  InfParams I{};  // size-only: no output buffer, no slots
+  const size_t n = cap;
+  rc = carve(c, c->d_gzip, [&](Carve &k) {
+    k.take(C.cand_off, n + 1);
+    k.take(P.cand_end, n);
+    k.take(R.pay_off, n + 1);
+    k.take(R.pay_end, n);
+    k.take(R.want, n);
+    k.take(R.isize, n);
+    k.take(R.bad, n);
+    k.take(R.dict_used, n);
+    k.take(I.out_len, n);
+    k.take(I.status, n);
+    k.take(I.err_off, n);
+    k.take(I.used, n);
+    k.take(C.jump[0], n + 2);
+    k.take(C.jump[1], n + 2);
+    k.take(C.path, C.path_len);
+    k.take(P.msize, n);
+    k.take(C.member_off, n + 1);
+    k.take(C.out_off, n + 1);
+  });
+  if (rc) return rc;
   R.in = d_in;
-  R.in_off = P.B.cand_off;
+  R.in_off = C.cand_off;
   R.in_end = P.cand_end;
   R.n_streams = cap;
   R.wrap = FLATE_HIP_WRAP_GZIP;
-  R.pay_off = (uint64_t *)(b + o_poff);
-  R.pay_end = (uint64_t *)(b + o_pend);
-  R.want = (uint32_t *)(b + o_want);
-  R.isize = (uint32_t *)(b + o_isize);
-  R.bad = (uint32_t *)(b + o_bad);
-  R.dict_used = (uint32_t *)(b + o_dict);
-  InfParams I{};  // size-only: no output buffer, no slots
   I.in = d_in;
   I.in_off = R.pay_off;
   I.in_end = R.pay_end;
-  I.out_len = (uint64_t *)(b + o_olen);
-  I.status = (int32_t *)(b + o_st);
-  I.err_off = (int64_t *)(b + o_err);
   I.n_streams = cap;
   I.in_len = in_len;
   I.size_only = 1u;
-  I.used = (uint64_t *)(b + o_used);
   P.pay_off = R.pay_off;
   P.bad = R.bad;
   P.status = I.status;
@@ -1092,18 +1034,12 @@ int gzip_discover(flate_hip_ctx *c, const uint8_t *d_in, uint64_t in_len, BgzfHe
     c->hip_err = "gzip discovery: a size-only pass was routed to the lane-per-stream decoder";
     return FLATE_HIP_E_INTERNAL;
   }
-  const uint32_t node_blocks = (uint32_t)(((uint64_t)cap + 2 + 255) / 256);
-  hipLaunchKernelGGL(gzip_fill_kernel, dim3(P.B.n_tiles), dim3(256), 0, c->stream, P);
+  hipLaunchKernelGGL(gzip_fill_kernel, dim3(C.n_tiles), dim3(256), 0, c->stream, P);
   hipLaunchKernelGGL(frame_parse_kernel, dim3((cap + 255) / 256), dim3(256), 0, c->stream, R);
   HIP_TRY(c, hipGetLastError());
   if ((rc = launch_decoders(c, route, I, false))) return rc;
-  hipLaunchKernelGGL(gzip_link_kernel, dim3(node_blocks), dim3(256), 0, c->stream, P);
-  for (uint32_t j = 0; j < rounds; ++j)
-    hipLaunchKernelGGL(bgzf_round_kernel, dim3(node_blocks), dim3(256), 0, c->stream, P.B, j);
-  hipLaunchKernelGGL(gzip_finish_kernel, dim3((P.B.path_len + 255) / 256), dim3(256), 0, c->stream, P);
-  hipLaunchKernelGGL(gzip_out_scan_kernel, dim3(1), dim3(1024), 0, c->stream, P);
-  HIP_TRY(c, hipGetLastError());
-  HIP_TRY(c, hipMemcpyAsync(&H, P.B.head, sizeof H, hipMemcpyDeviceToHost, c->stream));
+  if ((rc = chain_tail(c, C, gzip_link_kernel, P, gzip_finish_kernel, gzip_out_scan_kernel, P))) return rc;
+  HIP_TRY(c, hipMemcpyAsync(&H, P.C.head, sizeof H, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   return FLATE_HIP_OK;
 }
@@ -1129,7 +1065,7 @@ int flate_hip_gzip_index(flate_hip_ctx *c, const uint8_t *in, uint64_t in_len, u
     return FLATE_HIP_OK;
   }
   const uint8_t *d_in = nullptr;
-  if ((rc = bgzf_stage(c, in, in_len, flags, &d_in))) return rc;
+  if ((rc = stage_input(c, in, in_len, flags, &d_in))) return rc;
   BgzfHead H{};
   GzipParams P{};
   if ((rc = gzip_discover(c, d_in, in_len, H, P))) return rc;
@@ -1140,9 +1076,9 @@ int flate_hip_gzip_index(flate_hip_ctx *c, const uint8_t *in, uint64_t in_len, u
   // the index -- of a broken chain its good prefix, if that fits: the verdict is the walk's either way
   const uint64_t entries = (uint64_t)H.n_members + 1;
   if (member_off && index_cap >= entries) {
-    if (P.B.member_off) {
-      HIP_TRY(c, hipMemcpyAsync(member_off, P.B.member_off, entries * 8, hipMemcpyDeviceToHost, c->stream));
-      HIP_TRY(c, hipMemcpyAsync(out_off, P.B.out_off, entries * 8, hipMemcpyDeviceToHost, c->stream));
+    if (P.C.member_off) {
+      HIP_TRY(c, hipMemcpyAsync(member_off, P.C.member_off, entries * 8, hipMemcpyDeviceToHost, c->stream));
+      HIP_TRY(c, hipMemcpyAsync(out_off, P.C.out_off, entries * 8, hipMemcpyDeviceToHost, c->stream));
       HIP_TRY(c, hipStreamSynchronize(c->stream));
     } else {  // (no candidate at all: zero members in front of offset 0)
       member_off[0] = 0, out_off[0] = 0;
@@ -1166,7 +1102,7 @@ int flate_hip_gzip_read(flate_hip_ctx *c, const uint8_t *in, uint64_t in_len, ui
   if (in_len == 0) return FLATE_HIP_OK;
   try {
     const uint8_t *d_in = nullptr;
-    if ((rc = bgzf_stage(c, in, in_len, flags, &d_in))) return rc;
+    if ((rc = stage_input(c, in, in_len, flags, &d_in))) return rc;
     BgzfHead H{};
     GzipParams P{};
     if ((rc = gzip_discover(c, d_in, in_len, H, P))) return rc;
@@ -1179,7 +1115,7 @@ int flate_hip_gzip_read(flate_hip_ctx *c, const uint8_t *in, uint64_t in_len, ui
     }
     *out_len = H.out_bytes;
     if (H.out_bytes > out_cap) return FLATE_HIP_E_OUT_TOO_SMALL;
-    return members_read(c, d_in, n, P.B.member_off, P.B.out_off, H.out_bytes, out, flags, bad_member, err_off);
+    return members_read(c, d_in, n, P.C.member_off, P.C.out_off, H.out_bytes, out, flags, bad_member, err_off);
   } catch (const std::exception &e) {  // (out of host memory in an index vector)
     c->hip_err = e.what();
     return FLATE_HIP_E_INTERNAL;
@@ -1194,37 +1130,27 @@ namespace {
 // The discovery over the ONE stream d_in[0, in_len) (DEVICE memory) on the ctx's stream: the container's header, count
 // and scan, ONE read-back of the candidate count (the launches behind it have a thread or a wavefront per candidate),
 // then fill, probe, link, rounds, finish, out-scan, the tail probe and ONE read-back of the result words H with the
-// index (P.B.member_off / P.B.out_off on the device; null when the header is bad).  Counted in no
+// index (P.C.member_off / P.C.out_off on the device; null when the header is bad).  Counted in no
 // profiling stage.
 // index_cap != 0: the first min(index_cap, candidates + 1) entries of unit_bit / out_off come back into `index` (the
 // two arrays one after the other) in the same read-back as H -- the units are a subset of the candidates, so what fits
 // the caller's arrays is known before the chain is.
 int one_discover(flate_hip_ctx *c, const uint8_t *d_in, uint64_t in_len, uint32_t wrap, uint64_t index_cap, OneHead &H,
                  OneParams &P, std::vector<uint64_t> &index) {
-  const uint64_t A = reinterpret_cast<uintptr_t>(d_in) & 15u;
-  const uint64_t tiles = (A + in_len + kBgzfTile - 1) / kBgzfTile;
-  if (tiles > 0x7fffffffull) return FLATE_HIP_E_TOO_LARGE;
-  size_t at = 0;
-  auto carve = [&](size_t bytes) {
-    const size_t here = at;
-    at += (bytes + 255) & ~(size_t)255;
-    return here;
-  };
-  P = OneParams{};
-  P.B.in = d_in;
-  P.B.in_len = in_len;
-  P.B.n_tiles = (uint32_t)tiles;
-  P.unit_max = c->one_unit_max;
   int rc;
-  {
-    const size_t o_head = carve(sizeof(OneHead)), o_one = carve(sizeof(FrameOne)), o_tile = carve(((size_t)P.B.n_tiles + 1) * 4);
-    if ((rc = ensure(c, c->d_one_tiles, at))) return rc;
-    uint8_t *b = (uint8_t *)c->d_one_tiles.p;
-    P.head = (OneHead *)(b + o_head);
-    P.B.head = &P.head->h;
-    P.one = (FrameOne *)(b + o_one);
-    P.B.tile_cnt = (uint32_t *)(b + o_tile);
-  }
+  P = OneParams{};
+  ChainParams &C = P.C;
+  C.in = d_in;
+  C.in_len = in_len;
+  P.unit_max = c->one_unit_max;
+  if ((rc = tiles_for(d_in, 0, in_len, &C.n_tiles))) return rc;
+  rc = carve(c, c->d_one_tiles, [&](Carve &k) {
+    k.take(P.head, 1);
+    k.take(P.one, 1);
+    k.take(C.tile_cnt, (size_t)C.n_tiles + 1);
+  });
+  if (rc) return rc;
+  C.head = &P.head->h;
   hipLaunchKernelGGL(one_init_kernel, dim3(1), dim3(64), 0, c->stream, P.one, in_len);
   if (wrap != FLATE_HIP_WRAP_RAW) {  // the header rules of flate_hip_inflate_spliced_framed (no dictionaries: FDICT is bad)
     FrameReadParams R{};
@@ -1240,41 +1166,30 @@ int one_discover(flate_hip_ctx *c, const uint8_t *d_in, uint64_t in_len, uint32_
     R.dict_used = &P.one->dict_used;
     hipLaunchKernelGGL(frame_parse_kernel, dim3(1), dim3(256), 0, c->stream, R);
   }
-  hipLaunchKernelGGL(one_count_kernel, dim3(P.B.n_tiles), dim3(256), 0, c->stream, P);
-  hipLaunchKernelGGL(bgzf_scan_kernel, dim3(1), dim3(1024), 0, c->stream, P.B);
+  hipLaunchKernelGGL(one_count_kernel, dim3(C.n_tiles), dim3(256), 0, c->stream, P);
+  hipLaunchKernelGGL(chain_scan_kernel, dim3(1), dim3(1024), 0, c->stream, C);
   HIP_TRY(c, hipGetLastError());
   HIP_TRY(c, hipMemcpyAsync(&H, P.head, sizeof H, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   const uint32_t cap = H.h.n_cand;
-  if (cap > 0x7ffffff0u) return FLATE_HIP_E_TOO_LARGE;  // (the count saturates at 2^32 - 1)
+  if ((rc = chain_size(C, cap))) return rc;  // (the count saturates at 2^32 - 1)
   if (cap == 0) return FLATE_HIP_OK;  // (a bad header: the scan kernel has left FLATE_HIP_E_CORRUPT at offset 0)
 
-  const uint32_t rounds = bgzf_rounds(cap);
-  P.B.cap = cap;
-  P.B.path_len = 1u << rounds;
-  at = 0;
   const size_t n = cap;
-  const size_t o_cand = carve(n * 8), o_probe = carve(n * sizeof(OneProbe)), o_j0 = carve((n + 2) * 4),
-               o_j1 = carve((n + 2) * 4), o_path = carve((size_t)P.B.path_len * 4), o_usize = carve(n * 8),
-               o_ubit = carve((n + 1) * 8), o_ooff = carve((n + 1) * 8);
-  if ((rc = ensure(c, c->d_one, at))) return rc;  // (a failed allocation is FLATE_HIP_E_HIP, never a truncated result)
-  uint8_t *b = (uint8_t *)c->d_one.p;
-  P.B.cand_off = (uint64_t *)(b + o_cand);
-  P.probe = (OneProbe *)(b + o_probe);
-  P.B.jump[0] = (uint32_t *)(b + o_j0);
-  P.B.jump[1] = (uint32_t *)(b + o_j1);
-  P.B.path = (uint32_t *)(b + o_path);
-  P.usize = (uint64_t *)(b + o_usize);
-  P.B.member_off = (uint64_t *)(b + o_ubit);
-  P.B.out_off = (uint64_t *)(b + o_ooff);
-  const uint32_t node_blocks = (uint32_t)(((uint64_t)cap + 2 + 255) / 256);
-  hipLaunchKernelGGL(one_fill_kernel, dim3(P.B.n_tiles), dim3(256), 0, c->stream, P);
+  rc = carve(c, c->d_one, [&](Carve &k) {
+    k.take(C.cand_off, n);
+    k.take(P.probe, n);
+    k.take(C.jump[0], n + 2);
+    k.take(C.jump[1], n + 2);
+    k.take(C.path, C.path_len);
+    k.take(P.usize, n);
+    k.take(C.member_off, n + 1);
+    k.take(C.out_off, n + 1);
+  });
+  if (rc) return rc;
+  hipLaunchKernelGGL(one_fill_kernel, dim3(C.n_tiles), dim3(256), 0, c->stream, P);
   hipLaunchKernelGGL(one_probe_kernel, dim3(cap), dim3(64), 0, c->stream, P, 0u);
-  hipLaunchKernelGGL(one_link_kernel, dim3(node_blocks), dim3(256), 0, c->stream, P);
-  for (uint32_t j = 0; j < rounds; ++j)
-    hipLaunchKernelGGL(bgzf_round_kernel, dim3(node_blocks), dim3(256), 0, c->stream, P.B, j);
-  hipLaunchKernelGGL(one_finish_kernel, dim3((P.B.path_len + 255) / 256), dim3(256), 0, c->stream, P);
-  hipLaunchKernelGGL(one_out_scan_kernel, dim3(1), dim3(1024), 0, c->stream, P);
+  if ((rc = chain_tail(c, C, one_link_kernel, P, one_finish_kernel, one_out_scan_kernel, P))) return rc;
   hipLaunchKernelGGL(one_probe_kernel, dim3(1), dim3(64), 0, c->stream, P, 1u);
   HIP_TRY(c, hipGetLastError());
   // ONE read-back behind the count: the result words, then 16 bytes per unit
@@ -1282,8 +1197,8 @@ int one_discover(flate_hip_ctx *c, const uint8_t *d_in, uint64_t in_len, uint32_
   index.assign(2 * take, 0);
   HIP_TRY(c, hipMemcpyAsync(&H, P.head, sizeof H, hipMemcpyDeviceToHost, c->stream));
   if (take) {
-    HIP_TRY(c, hipMemcpyAsync(index.data(), P.B.member_off, take * 8, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(index.data() + take, P.B.out_off, take * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(index.data(), P.C.member_off, take * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(index.data() + take, P.C.out_off, take * 8, hipMemcpyDeviceToHost, c->stream));
   }
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   return FLATE_HIP_OK;
@@ -1313,7 +1228,7 @@ int flate_hip_inflate_one_index(flate_hip_ctx *c, const uint8_t *in, uint64_t in
       H.h.err_off = wrap == FLATE_HIP_WRAP_RAW ? -1 : 0;
     } else {
       const uint8_t *d_in = nullptr;
-      if ((rc = bgzf_stage(c, in, in_len, flags, &d_in))) return rc;
+      if ((rc = stage_input(c, in, in_len, flags, &d_in))) return rc;
       if ((rc = one_discover(c, d_in, in_len, wrap, unit_bit ? index_cap : 0, H, P, index))) return rc;
     }
     *n_units = H.h.n_members;
@@ -1365,7 +1280,7 @@ int flate_hip_inflate_one(flate_hip_ctx *c, const uint8_t *in, uint64_t in_len, 
   try {
     const bool dev = (flags & FLATE_HIP_DEVICE_PTRS) != 0;
     const uint8_t *d_in = nullptr;
-    if ((rc = bgzf_stage(c, in, in_len, flags, &d_in))) return rc;
+    if ((rc = stage_input(c, in, in_len, flags, &d_in))) return rc;
     OneHead H{};
     OneParams P{};
     std::vector<uint64_t> none;
@@ -1386,40 +1301,37 @@ int flate_hip_inflate_one(flate_hip_ctx *c, const uint8_t *in, uint64_t in_len, 
       d_out = (uint8_t *)c->d_out.p;
     }
     const uint32_t per_round = n_dec < c->one_round_units ? (n_dec ? n_dec : 1u) : c->one_round_units;
-    size_t at = 0;
-    auto carve = [&](size_t bytes) {
-      const size_t here = at;
-      at += (bytes + 255) & ~(size_t)255;
-      return here;
-    };
-    const size_t fbytes = (size_t)per_round * kWinEntries * 2;
-    const size_t o_dh = carve(sizeof(OneDecHead)), o_sum = carve(16), o_f0 = carve(fbytes), o_f1 = carve(fbytes),
-                 o_r = carve(((size_t)per_round + 1) * kWinEntries), o_st = carve((size_t)n_dec * 4 + 4),
-                 o_eo = carve((size_t)n_dec * 8 + 8), o_pr = carve((size_t)n_dec * 8 + 8),
-                 o_po = carve(((size_t)per_round + 1) * 8), o_pa = carve((size_t)per_round * 8),
-                 o_pl = carve((size_t)per_round * 4), o_ds = carve((size_t)per_round * 4),
-                 o_dl = carve((size_t)per_round * 8), o_de = carve((size_t)per_round * 8);
-    if ((rc = ensure(c, c->d_one_dec, at))) return rc;
-    uint8_t *b = (uint8_t *)c->d_one_dec.p;
+    const size_t fentries = (size_t)per_round * kWinEntries;
     OneDecParams D{};
+    uint32_t *d_sum;
+    int32_t *d_ds;
+    uint64_t *d_dl;
+    int64_t *d_de;
+    rc = carve(c, c->d_one_dec, [&](Carve &k) {
+      k.take(D.dh, 1);
+      k.take(d_sum, 4);
+      k.take(D.F[0], fentries);
+      k.take(D.F[1], fentries);
+      k.take(D.R, ((size_t)per_round + 1) * kWinEntries);
+      k.take(D.status, (size_t)n_dec + 1);
+      k.take(D.err_off, (size_t)n_dec + 1);
+      k.take(D.produced, (size_t)n_dec + 1);
+      k.take(D.p_out_off, (size_t)per_round + 1);
+      k.take(D.p_dict_at, per_round);
+      k.take(D.p_dict_len, per_round);
+      k.take(d_ds, per_round);
+      k.take(d_dl, per_round);
+      k.take(d_de, per_round);
+    });
+    if (rc) return rc;
     D.in = d_in;
     D.one = P.one;
-    D.unit_bit = P.B.member_off;
-    D.out_off = P.B.out_off;
+    D.unit_bit = P.C.member_off;
+    D.out_off = P.C.out_off;
     D.total = total;
     D.unit_max = c->one_unit_max;
-    D.F[0] = (uint16_t *)(b + o_f0);
-    D.F[1] = (uint16_t *)(b + o_f1);
-    D.R = b + o_r;
-    D.p_out_off = (uint64_t *)(b + o_po);
-    D.p_dict_at = (uint64_t *)(b + o_pa);
-    D.p_dict_len = (uint32_t *)(b + o_pl);
-    D.d_status = (const int32_t *)(b + o_ds);
-    D.d_out_len = (const uint64_t *)(b + o_dl);
-    D.dh = (OneDecHead *)(b + o_dh);
-    D.status = (int32_t *)(b + o_st);
-    D.err_off = (int64_t *)(b + o_eo);
-    D.produced = (uint64_t *)(b + o_pr);
+    D.d_status = d_ds;
+    D.d_out_len = d_dl;
     D.head = P.head;
     D.wrap = wrap;
     D.in_len = in_len;
@@ -1448,9 +1360,9 @@ int flate_hip_inflate_one(flate_hip_ctx *c, const uint8_t *in, uint64_t in_len, 
       I.n_streams = D.count;
       I.out = d_out;
       I.out_off = D.p_out_off;
-      I.out_len = (uint64_t *)(b + o_dl);
-      I.status = (int32_t *)(b + o_ds);
-      I.err_off = (int64_t *)(b + o_de);
+      I.out_len = d_dl;
+      I.status = d_ds;
+      I.err_off = d_de;
       I.dict_buf = D.R;
       I.dict_at = D.p_dict_at;
       I.dict_len = D.p_dict_len;
@@ -1467,8 +1379,8 @@ int flate_hip_inflate_one(flate_hip_ctx *c, const uint8_t *in, uint64_t in_len, 
       const uint64_t whole[2] = {0, total};
       if ((rc = ctl_begin(c, checksum_ctl_up_bytes(whole, 1), 0))) return rc;
       ctl = true;
-      D.sum = (uint32_t *)(b + o_sum);
-      if ((rc = checksum_device(c, d_out, whole, 1, frame_sum_kind(wrap), (uint32_t *)(b + o_sum), FLATE_HIP_STAGE_CHECKSUM)))
+      D.sum = d_sum;
+      if ((rc = checksum_device(c, d_out, whole, 1, frame_sum_kind(wrap), d_sum, FLATE_HIP_STAGE_CHECKSUM)))
         return rc;
       used[FLATE_HIP_STAGE_CHECKSUM] = true;
     }

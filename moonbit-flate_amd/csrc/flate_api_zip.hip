@@ -19,18 +19,6 @@ static_assert(sizeof(ZipSel) == 40 && sizeof(ZipCopyPiece) == 24, "device record
 
 namespace {
 
-// in[0, in_len) on the device: the caller's buffer, or the ctx's staged copy of it
-int zip_stage(flate_hip_ctx *c, const uint8_t *in, uint64_t in_len, uint32_t flags, const uint8_t **d_in) {
-  HIP_TRY(c, hipSetDevice(c->device));
-  *d_in = in;
-  if (flags & FLATE_HIP_DEVICE_PTRS) return FLATE_HIP_OK;
-  const int rc = ensure(c, c->d_in, in_len + 16);
-  if (rc) return rc;
-  HIP_TRY(c, hipMemcpyAsync(c->d_in.p, in, in_len, hipMemcpyHostToDevice, c->stream));
-  *d_in = (const uint8_t *)c->d_in.p;
-  return FLATE_HIP_OK;
-}
-
 // What discovery leaves: the archive's verdict and, when it is FLATE_HIP_OK, the index in device memory.
 struct ZipFound {
   int rc = FLATE_HIP_OK;
@@ -71,73 +59,45 @@ int zip_discover(flate_hip_ctx *c, const uint8_t *d_in, uint64_t in_len, ZipFoun
     if (EH.n != 0 || EH.cd_size != 0) F.rc = FLATE_HIP_E_CORRUPT, F.err_off = (int64_t)EH.cd_off;
     return FLATE_HIP_OK;
   }
-  const uint64_t A = reinterpret_cast<uintptr_t>(d_in) & 15u;
-  const uint64_t v_lo = (EH.cd_off + A) & ~15ull, v_hi = EH.cd_off + EH.cd_size + A;
-  const uint64_t tiles = (v_hi - v_lo + kZipTile - 1) / kZipTile;
-  if (tiles > 0x7fffffffull) return FLATE_HIP_E_TOO_LARGE;
+  ZipDirParams P{};
+  ChainParams &C = P.C;
+  C.in = d_in;
+  C.in_len = in_len;
+  P.cd_off = EH.cd_off;
+  P.cd_size = EH.cd_size;
+  P.n = (uint32_t)EH.n;
+  if ((rc = tiles_for(d_in, EH.cd_off, EH.cd_size, &C.n_tiles))) return rc;
   uint32_t cap = zip_first_cap(EH.n, EH.cd_size);
   for (int attempt = 0; attempt < 2; ++attempt) {
-    if (cap > 0x7ffffff0u) return FLATE_HIP_E_TOO_LARGE;
-    const uint32_t rounds = bgzf_rounds(cap);
-    ZipDirParams P{};
-    P.in = d_in;
-    P.in_len = in_len;
-    P.cd_off = EH.cd_off;
-    P.cd_size = EH.cd_size;
-    P.n = (uint32_t)EH.n;
-    P.n_tiles = (uint32_t)tiles;
-    P.cap = cap;
-    P.path_len = 1u << rounds;
+    if ((rc = chain_size(C, cap))) return rc;
     P.ent_cap = P.n < cap ? P.n : cap;
-    size_t at = 0;
-    auto carve = [&](size_t bytes) {
-      const size_t here = at;
-      at += (bytes + 255) & ~(size_t)255;
-      return here;
-    };
-    const size_t o_head = carve(sizeof(ZipDirHead)), o_bhead = carve(sizeof(BgzfHead)), o_tile = carve(((size_t)P.n_tiles + 1) * 4),
-                 o_coff = carve((size_t)cap * 8), o_ctot = carve((size_t)cap * 4), o_j0 = carve(((size_t)cap + 2) * 4),
-                 o_j1 = carve(((size_t)cap + 2) * 4), o_path = carve((size_t)P.path_len * 4),
-                 o_ent = carve(((size_t)P.ent_cap + 1) * sizeof(flate_hip_zip_entry)),
-                 o_ooff = carve(((size_t)P.ent_cap + 1) * 8);
-    if ((rc = ensure(c, c->d_zip_dir, at))) return rc;  // (a failed allocation is FLATE_HIP_E_HIP, never a truncated result)
-    uint8_t *b = (uint8_t *)c->d_zip_dir.p;
-    P.head = (ZipDirHead *)(b + o_head);
-    P.bhead = (BgzfHead *)(b + o_bhead);
-    P.tile_cnt = (uint32_t *)(b + o_tile);
-    P.cand_off = (uint64_t *)(b + o_coff);
-    P.cand_total = (uint32_t *)(b + o_ctot);
-    P.path = (const uint32_t *)(b + o_path);
-    P.entries = (flate_hip_zip_entry *)(b + o_ent);
-    P.out_off = (uint64_t *)(b + o_ooff);
-    BgzfParams B{};  // the shared link / round kernels: the directory as a "file" of cd_size bytes that starts at 0
-    B.in_len = EH.cd_size;
-    B.cap = cap;
-    B.path_len = P.path_len;
-    B.cand_off = P.cand_off;
-    B.cand_total = P.cand_total;
-    B.jump[0] = (uint32_t *)(b + o_j0);
-    B.jump[1] = (uint32_t *)(b + o_j1);
-    B.path = (uint32_t *)(b + o_path);
-    B.head = P.bhead;
-    const uint32_t node_blocks = (uint32_t)(((uint64_t)cap + 2 + 255) / 256);
-    hipLaunchKernelGGL(zip_dir_count_kernel, dim3(P.n_tiles), dim3(256), 0, c->stream, P);
+    rc = carve(c, c->d_zip_dir, [&](Carve &k) {
+      k.take(P.head, 1);
+      k.take(C.head, 1);
+      k.take(C.tile_cnt, (size_t)C.n_tiles + 1);
+      k.take(C.cand_off, cap);
+      k.take(P.cand_total, cap);
+      k.take(C.jump[0], (size_t)cap + 2);
+      k.take(C.jump[1], (size_t)cap + 2);
+      k.take(C.path, C.path_len);
+      k.take(P.entries, (size_t)P.ent_cap + 1);
+      k.take(C.out_off, (size_t)P.ent_cap + 1);
+    });
+    if (rc) return rc;
+    BgzfParams L{C, P.cand_total, nullptr};  // bgzf_link_kernel: the directory as a file of cd_size bytes that starts at 0
+    L.C.in_len = EH.cd_size;
+    hipLaunchKernelGGL(zip_dir_count_kernel, dim3(C.n_tiles), dim3(256), 0, c->stream, P);
     hipLaunchKernelGGL(zip_dir_scan_kernel, dim3(1), dim3(1024), 0, c->stream, P);
-    hipLaunchKernelGGL(zip_dir_fill_kernel, dim3(P.n_tiles), dim3(256), 0, c->stream, P);
-    hipLaunchKernelGGL(bgzf_link_kernel, dim3(node_blocks), dim3(256), 0, c->stream, B);
-    for (uint32_t j = 0; j < rounds; ++j)
-      hipLaunchKernelGGL(bgzf_round_kernel, dim3(node_blocks), dim3(256), 0, c->stream, B, j);
-    hipLaunchKernelGGL(zip_entry_kernel, dim3((P.path_len + 255) / 256), dim3(256), 0, c->stream, P);
-    hipLaunchKernelGGL(zip_out_scan_kernel, dim3(1), dim3(1024), 0, c->stream, P);
-    HIP_TRY(c, hipGetLastError());
+    hipLaunchKernelGGL(zip_dir_fill_kernel, dim3(C.n_tiles), dim3(256), 0, c->stream, P);
+    if ((rc = chain_tail(c, C, bgzf_link_kernel, L, zip_entry_kernel, zip_out_scan_kernel, P))) return rc;
     ZipDirHead H{};
     BgzfHead BH{};
     HIP_TRY(c, hipMemcpyAsync(&H, P.head, sizeof H, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(&BH, P.bhead, sizeof BH, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(&BH, C.head, sizeof BH, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     if (BH.n_cand <= cap) {
       F.rc = H.rc, F.err_off = H.err_off, F.n = H.n_entries, F.out_bytes = H.out_bytes;
-      F.d_entries = P.entries, F.d_out_off = P.out_off;
+      F.d_entries = P.entries, F.d_out_off = C.out_off;
       return FLATE_HIP_OK;
     }
     // more candidates than the arrays hold: nothing behind the scan has run; once more, sized from the count
@@ -192,7 +152,7 @@ int flate_hip_zip_index(flate_hip_ctx *c, const uint8_t *in, uint64_t in_len, ui
   *n_entries = 0, *out_bytes = 0;
   if (err_off) *err_off = -1;
   const uint8_t *d_in = nullptr;
-  if ((rc = zip_stage(c, in, in_len, flags, &d_in))) return rc;
+  if ((rc = stage_input(c, in, in_len, flags, &d_in))) return rc;
   ZipFound F;
   if ((rc = zip_discover(c, d_in, in_len, F))) return rc;
   *n_entries = F.n;
@@ -225,7 +185,7 @@ int flate_hip_zip_read(flate_hip_ctx *c, const uint8_t *in, uint64_t in_len, con
   try {
     const bool dev = (flags & FLATE_HIP_DEVICE_PTRS) != 0;
     const uint8_t *d_in = nullptr;
-    if ((rc = zip_stage(c, in, in_len, flags, &d_in))) return rc;
+    if ((rc = stage_input(c, in, in_len, flags, &d_in))) return rc;
     for (int k = 0; k < FLATE_HIP_STAGE_COUNT; ++k) c->stage_ms[k] = 0;
     ZipFound F;
     if ((rc = zip_discover(c, d_in, in_len, F))) return rc;

@@ -1,5 +1,5 @@
 // flate_ctx.h -- the ctx and the host-side helpers that more than one host file of the C ABI uses (private, host
-// only).  Everything in flate_host is DEFINED in flate_api.hip; flate_api_deflate.hip (the encode calls) and
+// only).  Everything in flate_host but its templates is DEFINED in flate_api.hip; flate_api_deflate.hip (the encode calls) and
 // flate_api_inflate.hip (the decode calls) are the users.
 // (checksum.hip and gather.hip see the ctx through the flate::ctx_* accessors of flate_kernels.h.)
 #pragma once
@@ -14,6 +14,7 @@
 #include <thread>
 #include <vector>
 
+#include "carve.h"
 #include "deflate_plan.h"
 #include "flate_kernels.h"
 #include "inflate_route.h"
@@ -67,7 +68,7 @@ struct flate_hip_ctx {
   // flate_hip_inflate_spliced_framed (it shares d_frame_off: the index counted from the member's first byte,
   // d_frame_sums: the pieces' sums, d_rd_bad: the header verdict per piece): the one member's words (FrameOne)
   DevBuf d_rd_one;
-  // flate_hip_bgzf_index / _read: the discovery kernels' arrays (BgzfParams), carved from one buffer
+  // flate_hip_bgzf_index / _read: the discovery kernels' arrays (BgzfParams), carved from one buffer (carve.h)
   DevBuf d_bgzf;
   // flate_hip_bgzf_read_ranges: the range kernels' arrays (BgzfRangeParams), carved from one buffer; the dense scratch
   // the touched members are decoded into; and, for the framed read it runs over them, the members' ends
@@ -152,6 +153,41 @@ struct flate_hip_ctx {
 namespace flate_host {
 
 int ensure(flate_hip_ctx *c, DevBuf &b, size_t bytes);
+// b as a call's arrays: lay(k) names every array on the Carve k, in order, with its type and its count.  It runs over
+// no buffer for the size, and again over b once ensure() has made that much room (a failed allocation is
+// FLATE_HIP_E_HIP, never a truncated result).
+template <typename Lay>
+int carve(flate_hip_ctx *c, DevBuf &b, Lay lay) {
+  Carve k;
+  lay(k);
+  const int rc = ensure(c, b, k.at);
+  if (rc) return rc;
+  k = Carve{b.p, 0};
+  lay(k);
+  return FLATE_HIP_OK;
+}
+// in[0, in_len) on the device: the caller's buffer, or the ctx's staged copy of it
+int stage_input(flate_hip_ctx *c, const uint8_t *in, uint64_t in_len, uint32_t flags, const uint8_t **d_in);
+
+// ---- what the four discoveries share on the host (flate_kernels.h: THE DISCOVERY SKELETON) ----
+// the tiles over the offsets [lo, lo + len) of the device buffer d_in, or FLATE_HIP_E_TOO_LARGE
+int tiles_for(const uint8_t *d_in, uint64_t lo, uint64_t len, uint32_t *n_tiles);
+// C.cap and C.path_len for arrays of cap candidates, or FLATE_HIP_E_TOO_LARGE
+int chain_size(flate::ChainParams &C, uint32_t cap);
+// The launches behind a format's fill (and whatever it runs over the candidates): its link kernel, the rounds of
+// pointer doubling, its finish and out-scan kernels; one check of all launches so far.
+template <typename LP, typename FP>
+int chain_tail(flate_hip_ctx *c, const flate::ChainParams &C, void (*link)(LP), const LP &lp, void (*finish)(FP),
+               void (*out_scan)(FP), const FP &fp) {
+  const uint32_t node_blocks = (uint32_t)(((uint64_t)C.cap + 2 + 255) / 256);
+  hipLaunchKernelGGL(link, dim3(node_blocks), dim3(256), 0, c->stream, lp);
+  for (uint32_t j = 0; (1u << j) < C.path_len; ++j)
+    hipLaunchKernelGGL(flate::chain_round_kernel, dim3(node_blocks), dim3(256), 0, c->stream, C, j);
+  hipLaunchKernelGGL(finish, dim3((C.path_len + 255) / 256), dim3(256), 0, c->stream, fp);
+  hipLaunchKernelGGL(out_scan, dim3(1), dim3(1024), 0, c->stream, fp);
+  HIP_TRY(c, hipGetLastError());
+  return FLATE_HIP_OK;
+}
 
 // ---- small index arrays: host <-> device through pinned staging and a copy kernel (copy_ctl_kernel) ----
 // ctl_begin: room for the call's uploads / downloads (a staging buffer only grows between calls: the

@@ -1,6 +1,7 @@
 // flate_kernels.h -- kernel parameter blocks and launch entry points (internal).
 #pragma once
 
+#include "chain_rule.h"
 #include "flate_common.h"
 #include "flate_hip.h"
 
@@ -345,12 +346,12 @@ struct FrameSplicedParams {
 __global__ void frame_rebase_kernel(FrameSplicedParams P);
 __global__ void frame_verdict_spliced_kernel(FrameSplicedParams P);
 
-// BGZF member discovery (bgzf_kernels.hip; flate_hip_bgzf_index / _read): the members of a file form a linked list
-// through their BSIZE fields, ranked here in parallel.  Every offset that passes the member rule (bgzf_rule.h) is a
-// CANDIDATE; the candidates are compacted in file order (count per 4 KiB tile, scan, fill), every candidate finds the
-// one at offset + total by binary search (in_len: the terminal node n_cand, nothing: the dead node n_cand + 1), and
-// the chain from candidate 0 is ranked by pointer doubling.  All loops are bounded by values the host computed from
-// in_len and cap before the launches; no kernel waits for another workgroup.
+// THE DISCOVERY SKELETON (chain_walk.h, chain_rule.h, chain_kernels.hip), shared by the four formats below.  Every
+// offset of the input that passes a format's rule is a CANDIDATE; the candidates are compacted in file order (count per
+// 4 KiB tile, chain_scan_kernel, fill), every candidate finds the one at its own end by binary search (the end of the
+// file: the terminal node n_cand; nothing there: the dead node n_cand + 1; both absorb), and the chain from candidate 0
+// is ranked by pointer doubling (chain_round_kernel).  All loops are bounded by values the host computed before the
+// launches; no kernel waits for another workgroup.
 struct BgzfHead {          // the result words, read back as one block
   uint64_t out_bytes;      // sum of the members' ISIZE (0 unless rc == 0)
   int64_t err_off;         // the offset at which no member could be read, or -1
@@ -359,30 +360,36 @@ struct BgzfHead {          // the result words, read back as one block
   uint32_t eof_marker;     // the last member is the canonical 28 bytes
   uint32_t n_cand;         // candidates counted (saturating); above cap: nothing else here is valid, run again
 };
-struct BgzfParams {
+struct ChainParams {       // what the shared code reads
   const uint8_t *in;       // any byte alignment
   uint64_t in_len;
   uint32_t n_tiles;        // 4 KiB tiles on the 16-byte grid of in's ADDRESS
   uint32_t cap;            // candidates the arrays hold
   uint32_t path_len;       // a power of two >= cap + 2
   uint32_t *tile_cnt;      // n_tiles + 1: candidates per tile, then their exclusive scan
-  uint64_t *cand_off;      // cap
-  uint32_t *cand_total;    // cap
+  uint64_t *cand_off;      // cap: where the candidates start
   uint32_t *jump[2];       // cap + 2 each: the successor after 2^j steps, double-buffered
   uint32_t *path;          // path_len: node r steps from candidate 0
-  uint32_t *isize;         // cap: per member
-  uint64_t *member_off;    // cap + 1
-  uint64_t *out_off;       // cap + 1
+  uint64_t *member_off;    // cap + 1: where the chain's members start
+  uint64_t *out_off;       // cap + 1: where their output goes
   BgzfHead *head;
 };
+__global__ void chain_scan_kernel(ChainParams C);
+__global__ void chain_round_kernel(ChainParams C, uint32_t j);
+
+// BGZF member discovery (bgzf_kernels.hip; flate_hip_bgzf_index / _read): the members of a file form a linked list
+// through their BSIZE fields; a candidate is an offset that passes the member rule (bgzf_rule.h), and it ends at
+// offset + total.  ZIP's directory is linked by the same kernel (zip_kernels.h).
+struct BgzfParams {
+  ChainParams C;
+  uint32_t *cand_total;    // cap
+  uint32_t *isize;         // cap: per member
+};
 __global__ void bgzf_count_kernel(BgzfParams P);
-__global__ void bgzf_scan_kernel(BgzfParams P);
 __global__ void bgzf_fill_kernel(BgzfParams P);
 __global__ void bgzf_link_kernel(BgzfParams P);
-__global__ void bgzf_round_kernel(BgzfParams P, uint32_t j);
 __global__ void bgzf_finish_kernel(BgzfParams P);
 __global__ void bgzf_out_scan_kernel(BgzfParams P);
-constexpr uint32_t kBgzfTile = 4096;
 
 // BGZF random access (bgzf_range_kernels.hip; flate_hip_bgzf_read_ranges): behind the discovery kernels, on the index
 // where they left it.  Locate: one thread per range (bgzf_range_rule.h) -- b, length, status, the first and the last
@@ -447,19 +454,17 @@ constexpr uint32_t kBgzfGatherWindow = 65536;
 constexpr uint32_t kBgzfGatherRangeCost = 256;
 __global__ void bgzf_gather_kernel(BgzfGatherParams P);
 
-// Plain multi-member gzip files (gzip_kernels.hip; flate_hip_gzip_index / _read): BGZF's discovery for members that do
-// not carry their size.  Every offset that passes the header rule (gzip_rule.h) over the range it is given -- in[p,
-// min(in_len, p + member_max)) -- is a CANDIDATE, compacted in file order (count per 4 KiB tile, bgzf_scan_kernel,
-// fill); frame_parse_kernel and ONE size-only launch of the batch decoders run over all candidates (InfParams::used);
-// gzip_link_kernel sends every candidate to the candidate at its end (in_len: the terminal node n_cand, nothing or a
-// failed decode: the dead node n_cand + 1); bgzf_round_kernel ranks the chain from candidate 0; gzip_finish_kernel and
-// gzip_out_scan_kernel turn the ranks into member_off / out_off and the walk's verdict (gzip_serial_walk).  B carries
-// what the two BGZF kernels read (head, cap, path_len, tile_cnt, jump, path) and the arrays of the same meaning;
-// B.cand_total and B.isize are unused.  B.cap is the exact candidate count: the host reads it back behind the scan.
+// Plain multi-member gzip files (gzip_kernels.hip; flate_hip_gzip_index / _read): the skeleton for members that do not
+// carry their size.  A candidate is an offset that passes the header rule (gzip_rule.h) over the range it is given --
+// in[p, min(in_len, p + member_max)); frame_parse_kernel and ONE size-only launch of the batch decoders run over all
+// candidates (InfParams::used) between the fill and the link, and a candidate ends behind its trailer -- or, when its
+// decode failed, nowhere: the dead node.  gzip_finish_kernel and gzip_out_scan_kernel turn the ranks into member_off /
+// out_off and the walk's verdict (gzip_serial_walk).  C.cap is the exact candidate count: the host reads it back
+// behind the scan.
 struct GzipParams {
-  BgzfParams B;
+  ChainParams C;
   uint64_t member_max;     // option "gzip_member_max"
-  uint64_t *cand_end;      // cap: where candidate c's range ends; B.cand_off has cap + 1 entries (the last: in_len)
+  uint64_t *cand_end;      // cap: where candidate c's range ends; C.cand_off has cap + 1 entries (the last: in_len)
   // what frame_parse_kernel and the decoders left, per candidate
   const uint64_t *pay_off; // where the raw stream starts
   const uint32_t *bad;     // (never 1: the candidates passed the same rule)
@@ -474,16 +479,14 @@ __global__ void gzip_link_kernel(GzipParams P);
 __global__ void gzip_finish_kernel(GzipParams P);
 __global__ void gzip_out_scan_kernel(GzipParams P);
 
-// One long DEFLATE stream (one_kernels.hip, one_probe_kernel.inc; flate_hip_inflate_one_index): the gzip discovery one
-// level down.  Bit 0 of the raw stream and every bit offset that passes the dynamic-header rule (deflate_block_rule.h)
-// is a CANDIDATE, compacted in bit order (count per 4 KiB tile, bgzf_scan_kernel, fill); one_probe_kernel decodes every
-// candidate without history or stores up to the next dynamic header (OneProbe); one_link_kernel sends every candidate
-// to the candidate at its end bit (a final block: the terminal node n_cand; nothing or a failed probe: the dead node
-// n_cand + 1); bgzf_round_kernel ranks the chain from candidate 0; one_finish_kernel and one_out_scan_kernel turn the
-// ranks into unit_bit / out_off; a chain that stops at a dynamic header the rule refused takes its verdict from one
-// more probe there (one_probe_kernel, tail form).  B carries what the two BGZF kernels read (head, cap, path_len,
-// tile_cnt, jump, path); B.in is the whole input, B.cand_off the candidates' bits, B.member_off the units' bits (both
-// counted from the raw stream's first byte); B.cand_total and B.isize are unused.  B.cap is the exact candidate count.
+// One long DEFLATE stream (one_kernels.hip, one_probe_kernel.inc; flate_hip_inflate_one_index): the skeleton one level
+// down.  A candidate is bit 0 of the raw stream or a bit offset that passes the dynamic-header rule
+// (deflate_block_rule.h); one_probe_kernel decodes every candidate without history or stores up to the next dynamic
+// header (OneProbe) between the fill and the link, and a candidate ends at that header's bit (a final block: the
+// terminal node; a failed probe: the dead node).  one_finish_kernel and one_out_scan_kernel turn the ranks into
+// unit_bit / out_off; a chain that stops at a dynamic header the rule refused takes its verdict from one more probe
+// there (one_probe_kernel, tail form).  C.in is the whole input, C.cand_off the candidates' bits, C.member_off the
+// units' bits (both counted from the raw stream's first byte).  C.cap is the exact candidate count.
 struct OneProbe {          // what a candidate's probe left
   uint64_t end_bit;        // where it stopped: in front of a dynamic header, or behind the final block
   uint64_t out;            // bytes it inflates to
@@ -491,7 +494,7 @@ struct OneProbe {          // what a candidate's probe left
   int32_t status;          // 0, FLATE_HIP_E_CORRUPT / _UNEXPECTED_EOF / _TOO_LARGE
   uint32_t final_block;    // it ended with BFINAL
 };
-struct OneHead {           // the result words, read back as one block; B.head = &h
+struct OneHead {           // the result words, read back as one block; C.head = &h
   BgzfHead h;              // n_members: the units; rc / err_off: the serial decoder's verdict
   uint64_t tail_bit;       // tail != 0: the chain stopped here, at a dynamic header that is no candidate
   uint32_t tail;
@@ -503,7 +506,7 @@ struct OneHead {           // the result words, read back as one block; B.head =
   uint32_t pad;
 };
 struct OneParams {
-  BgzfParams B;
+  ChainParams C;
   FrameOne *one;           // one_init_kernel, frame_parse_kernel: pay_off[0] .. pay_end is the raw stream
   OneHead *head;
   OneProbe *probe;         // cap
@@ -530,7 +533,7 @@ struct OneDecHead {        // the call's result words
 struct OneDecParams {
   const uint8_t *in;
   const FrameOne *one;
-  const uint64_t *unit_bit;  // n_dec + 1 (OneParams::B.member_off)
+  const uint64_t *unit_bit;  // n_dec + 1 (OneParams::C.member_off)
   const uint64_t *out_off;   // n_dec + 1
   uint32_t u0, count;
   uint64_t total;            // nothing at or behind out + total is written

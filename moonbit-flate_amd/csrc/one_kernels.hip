@@ -2,63 +2,32 @@
 // raw stream inside in[0, in_len) start -- bit 0 and every dynamic block header the serial decode reaches -- and where
 // their output goes, from the stream's bits alone (flate_kernels.h: OneParams; the rule: deflate_block_rule.h).
 //
-// The shape is gzip_kernels.hip's, at bit granularity:
+// The skeleton is chain_walk.h's (flate_kernels.h: THE DISCOVERY SKELETON), at bit granularity and, as for gzip
+// members, with the candidate count read back behind the scan.  What is this format's own:
 //   one_init_kernel      the one range {0, in_len}, and the raw stream of FLATE_HIP_WRAP_RAW: all of it
 //   frame_parse_kernel   (frame_kernels.hip; zlib and gzip) the header's verdict and the raw stream's range
-//   one_count_kernel     one workgroup per 4 KiB tile, as gzip_count_kernel: 16-byte loads into LDS on the grid of the
-//                        buffer's address plus one chunk of halo; every thread tests its 128 bit offsets -- 13 bits of a
-//                        32-bit window first, then the three counts and the code-length code, all in LDS (at most 81
-//                        bits from the byte: inside the halo) -- and runs the whole rule FROM GLOBAL MEMORY on the rare hit; bit 0 of the raw stream is a candidate
-//                        whatever it holds; the tile's count goes to tile_cnt
-//   bgzf_scan_kernel     (bgzf_kernels.hip) the exclusive scan of the counts; n_cand, which the host reads back
-//   one_fill_kernel      the same pass again, the hits written in bit order: cand_off
+//   one_count_kernel / one_fill_kernel   the offset test: every thread tests its 128 BIT offsets -- 13 bits of a 32-bit
+//                        window first, then the three counts and the code-length code, all in LDS (at most 81 bits from
+//                        the byte: inside the halo) -- and runs the whole rule FROM GLOBAL MEMORY on the rare hit; bit 0
+//                        of the raw stream is a candidate whatever it holds; a hit stores its bit, cand_off.  The loop
+//                        over the 128 bits stays here: the byte formats' 16-bit mask does not hold them
 //   one_probe_kernel     (one_probe_kernel.inc) every candidate decoded to the next dynamic header: OneProbe
-//   one_link_kernel      jump[0][c] = the candidate at end_bit[c] (binary search), the terminal node n_cand behind a final
-//                        block, else -- or when the probe failed -- the dead node n_cand + 1; both absorb
-//   bgzf_round_kernel    (bgzf_kernels.hip) pointer doubling
+//   one_link_kernel      a candidate whose probe succeeded ends at end_bit; the last one ends with a final block
 //   one_finish_kernel    path rank r -> unit_bit[r], the unit's size; the thread at which the path meets a sink writes
 //                        the verdict, or asks for the tail probe
-//   one_out_scan_kernel  the exclusive scan of the sizes -> out_off (one workgroup, scan_range)
+//   one_out_scan_kernel  the exclusive scan of the sizes -> out_off (one workgroup, scan_range of block_scan.h)
 // A unit ends strictly above its start (a block header has three bits), so nothing cycles.  No kernel waits for
 // another workgroup; every loop is bounded by the tile, by the candidate count or by 32 search steps.
 #include <hip/hip_runtime.h>
 
-#include "block_scan.h"
+#include "chain_walk.h"
 #include "deflate_block_rule.h"
 #include "flate_hip.h"
-#include "flate_kernels.h"
 #include "window_compose.h"
 
 namespace flate {
 
 namespace {
-
-constexpr uint32_t kChunks = kBgzfTile / 16;  // 256: one per thread
-
-__device__ inline uint32_t buf_align(const OneParams &P) { return (uint32_t)(reinterpret_cast<uintptr_t>(P.B.in) & 15u); }
-
-// the tile's bytes (kBgzfTile + 16 of halo) into LDS; bytes outside the input read as zero.  (bgzf_kernels.hip's
-// load_tile: virtual position = input offset + A, so that multiples of 16 are aligned addresses.)
-__device__ inline void load_tile(const OneParams &P, uint8_t *lds, uint64_t v0, uint32_t A) {
-  const uint8_t *in = P.B.in;
-  const uint64_t v_end = (uint64_t)A + P.B.in_len;
-  for (uint32_t ch = threadIdx.x; ch <= kChunks; ch += 256u) {
-    const uint64_t v = v0 + 16ull * ch;
-    uint4 w = make_uint4(0u, 0u, 0u, 0u);
-    if (v >= A && v + 16u <= v_end) {
-      w = *reinterpret_cast<const uint4 *>(in + (v - A));
-    } else if (v + 16u > A && v < v_end) {
-      uint32_t d[4] = {0u, 0u, 0u, 0u};
-      for (uint32_t b = 0; b < 16u; ++b) {
-        const uint64_t vv = v + b;
-        if (vv >= A && vv < v_end) d[b >> 2] |= (uint32_t)in[vv - A] << (8u * (b & 3u));
-      }
-      w = make_uint4(d[0], d[1], d[2], d[3]);
-    }
-    *reinterpret_cast<uint4 *>(lds + 16u * ch) = w;
-  }
-  __syncthreads();
-}
 
 // this thread's 128 bit offsets: bit j of hits = a unit can start at bit (j & 7) of the byte at virtual position
 // v0 + 16 * tid + (j >> 3).  Returns how many.
@@ -72,7 +41,7 @@ __device__ inline uint32_t test_bits(const OneParams &P, const uint8_t *lds, uin
     const uint64_t v = v0 + at + b;
     if (v < A) continue;
     const uint64_t p = v - A;
-    if (bad || p < raw_off || p >= P.B.in_len) continue;
+    if (bad || p < raw_off || p >= P.C.in_len) continue;
     uint32_t m = 0;
     if (p < raw_end) {
       const uint64_t end_bit = 8u * (raw_end - p);  // (the bytes the head test reads lie in LDS: see above)
@@ -81,7 +50,7 @@ __device__ inline uint32_t test_bits(const OneParams &P, const uint8_t *lds, uin
       const uint32_t w = l[0] | ((uint32_t)l[1] << 8) | ((uint32_t)l[2] << 16) | ((uint32_t)l[3] << 24);
       for (uint32_t k = 0; k < 8u; ++k)
         if (dblk_quick_ok(w >> k) && dblk_head_ok(l, end_bit, k) &&
-            deflate_dyn_header_ok(P.B.in + raw_off, raw_end - raw_off, 8u * (p - raw_off) + k))
+            deflate_dyn_header_ok(P.C.in + raw_off, raw_end - raw_off, 8u * (p - raw_off) + k))
           m |= 1u << k;
     }
     if (p == raw_off) m |= 1u;  // bit 0 starts the first unit
@@ -105,9 +74,8 @@ __global__ void one_init_kernel(FrameOne *one, uint64_t in_len) {
 }
 
 __global__ __launch_bounds__(256) void one_count_kernel(OneParams P) {
-  __shared__ __attribute__((aligned(16))) uint8_t lds[kBgzfTile + 16];
-  __shared__ uint32_t wtot[4];
-  if (blockIdx.x == 0 && threadIdx.x == 0) {  // (bgzf_scan_kernel writes head->h, and nothing behind it)
+  __shared__ TileLds L;
+  if (blockIdx.x == 0 && threadIdx.x == 0) {  // (chain_scan_kernel writes head->h, and nothing behind it)
     P.head->tail_bit = 0;
     P.head->tail = 0;
     P.head->prefix_bytes = 0;
@@ -118,80 +86,47 @@ __global__ __launch_bounds__(256) void one_count_kernel(OneParams P) {
     P.head->raw_off = P.one->pay_off[0];
     P.head->raw_len = P.one->pay_end - P.one->pay_off[0];
   }
-  const uint32_t A = buf_align(P);
-  const uint64_t v0 = (uint64_t)blockIdx.x * kBgzfTile;
-  load_tile(P, lds, v0, A);
+  const uint32_t A = tile_align(P.C.in);
+  const uint64_t v0 = (uint64_t)blockIdx.x * kTileBytes;
   uint32_t hits[4];
-  const uint32_t mine = test_bits(P, lds, v0, A, hits);
-  uint32_t sum = 0;
-  (void)block_scan_excl<4, uint32_t>(mine, wtot, &sum);
-  if (threadIdx.x == 0) P.B.tile_cnt[blockIdx.x] = sum;
+  tile_count(P.C, L, v0, [&](const uint8_t *lds) { return test_bits(P, lds, v0, A, hits); });
 }
 
 __global__ __launch_bounds__(256) void one_fill_kernel(OneParams P) {
-  __shared__ __attribute__((aligned(16))) uint8_t lds[kBgzfTile + 16];
-  __shared__ uint32_t wtot[4];
-  const uint32_t cap = P.B.cap;
-  if (P.B.head->n_cand != cap) return;  // (uniform, never: the arrays are sized from the count the host read back)
-  const uint32_t first = P.B.tile_cnt[blockIdx.x];
-  if (P.B.tile_cnt[blockIdx.x + 1] == first) return;  // (uniform: nothing in this tile)
-  const uint32_t A = buf_align(P);
-  const uint64_t v0 = (uint64_t)blockIdx.x * kBgzfTile;
-  load_tile(P, lds, v0, A);
-  uint32_t hits[4];
-  const uint32_t mine = test_bits(P, lds, v0, A, hits);
-  uint32_t sum = 0;
-  uint32_t at = first + block_scan_excl<4, uint32_t>(mine, wtot, &sum);
+  __shared__ TileLds L;
+  const uint32_t A = tile_align(P.C.in), cap = P.C.cap;
+  const uint64_t v0 = (uint64_t)blockIdx.x * kTileBytes;
+  uint32_t first, hits[4];
+  if (!tile_fill_load(P.C, L, v0, true, &first)) return;
+  uint32_t at = tile_fill_at(L, first, test_bits(P, L.bytes, v0, A, hits));
   const uint64_t raw_off = P.one->pay_off[0];
   for (uint32_t j = 0; j < 128u; ++j) {
     if (!((hits[j >> 5] >> (j & 31u)) & 1u)) continue;
     // (a hit lies at or above raw_off: test_bits)
-    if (at < cap) P.B.cand_off[at] = 8u * (v0 + 16u * threadIdx.x + (j >> 3) - A - raw_off) + (j & 7u);
+    if (at < cap) P.C.cand_off[at] = 8u * (v0 + 16u * threadIdx.x + (j >> 3) - A - raw_off) + (j & 7u);
     ++at;
   }
 }
 
 // One thread per node (n_cand + 2 of them).
 __global__ __launch_bounds__(256) void one_link_kernel(OneParams P) {
-  const uint32_t n = P.B.cap;
+  const uint32_t n = P.C.cap;
   const uint32_t c = blockIdx.x * 256u + threadIdx.x;
-  const uint32_t term = n, dead = n + 1u;
-  if (c == 0) {
-    P.B.path[0] = (n && P.B.cand_off[0] == 0ull) ? 0u : dead;  // the first unit starts at bit 0
-    P.B.member_off[0] = 0ull;
-  }
-  if (c > dead) return;
-  uint32_t next = c;  // the two sinks absorb
-  if (c < n) {
-    next = dead;
-    const OneProbe pr = P.probe[c];
-    if (pr.status == 0) {
-      if (pr.final_block) {
-        next = term;
-      } else {
-        const uint64_t want = pr.end_bit;
-        uint32_t lo = c + 1u, hi = n;  // a unit ends strictly above its start
-        for (int it = 0; it < 32 && lo < hi; ++it) {
-          const uint32_t mid = lo + (hi - lo) / 2u;
-          if (P.B.cand_off[mid] < want) lo = mid + 1u;
-          else hi = mid;
-        }
-        if (lo < n && P.B.cand_off[lo] == want) next = lo;
-      }
-    }
-  }
-  P.B.jump[0][c] = next;
+  if (c == 0) P.C.member_off[0] = 0ull;
+  OneProbe pr{};
+  if (c < n) pr = P.probe[c];
+  chain_link(P.C, n, c, c < n && pr.status == 0, pr.final_block != 0u, pr.end_bit);
 }
 
 __global__ __launch_bounds__(256) void one_finish_kernel(OneParams P) {
-  const uint32_t n = P.B.cap;
+  const uint32_t n = P.C.cap;
   const uint32_t r = blockIdx.x * 256u + threadIdx.x;
-  if (r + 1u >= P.B.path_len) return;  // (the last entry is a sink: see below)
-  const uint32_t c = P.B.path[r];
+  if (r + 1u >= P.C.path_len) return;  // (the last entry is a sink: see below)
+  const uint32_t c = P.C.path[r];
   if (c >= n) return;
-  BgzfHead *h = P.B.head;
+  BgzfHead *h = P.C.head;
   const OneProbe pr = P.probe[c];
-  P.B.member_off[r] = P.B.cand_off[c];
+  P.C.member_off[r] = P.C.cand_off[c];
   if (pr.status != 0) {  // the decode ends IN this unit: one thread gets here, or one gets below
     P.head->fail_out = pr.out;
     P.head->fail_unit = 1u;
@@ -202,10 +137,10 @@ __global__ __launch_bounds__(256) void one_finish_kernel(OneParams P) {
   }
   P.usize[r] = pr.out;
   // (the chain holds at most n candidates and path_len >= n + 2: r + 1 is inside the path)
-  const uint32_t succ = P.B.path[r + 1u];
+  const uint32_t succ = P.C.path[r + 1u];
   if (succ < n) return;
   h->n_members = r + 1u;  // this is the last good unit
-  P.B.member_off[r + 1u] = pr.end_bit;
+  P.C.member_off[r + 1u] = pr.end_bit;
   if (succ == n) {
     h->rc = 0;
     h->err_off = -1;
@@ -219,14 +154,14 @@ __global__ __launch_bounds__(256) void one_finish_kernel(OneParams P) {
 // chain too (its good prefix).
 __global__ __launch_bounds__(1024) void one_out_scan_kernel(OneParams P) {
   __shared__ uint64_t wtot[16];
-  const uint32_t hi = P.B.head->n_members;
+  const uint32_t hi = P.C.head->n_members;
   const uint64_t total = scan_range<16, uint64_t>(
       hi, wtot, [&](uint32_t i) { return P.usize[i]; },
-      [&](uint32_t i, uint64_t before, uint64_t) { P.B.out_off[i] = before; });
+      [&](uint32_t i, uint64_t before, uint64_t) { P.C.out_off[i] = before; });
   if (threadIdx.x == 0) {
-    P.B.out_off[hi] = total;
+    P.C.out_off[hi] = total;
     P.head->prefix_bytes = total;
-    P.B.head->out_bytes = P.B.head->rc == 0 ? total : 0ull;
+    P.C.head->out_bytes = P.C.head->rc == 0 ? total : 0ull;
   }
 }
 

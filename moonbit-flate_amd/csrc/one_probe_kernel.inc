@@ -155,11 +155,11 @@ __global__ __launch_bounds__(64) void one_probe_kernel(OneParams P, uint32_t tai
     if (c != 0 || !P.head->tail) return;
     start = P.head->tail_bit;
   } else {
-    if (c >= P.B.cap) return;
-    start = P.B.cand_off[c];
+    if (c >= P.C.cap) return;
+    start = P.C.cand_off[c];
   }
   const uint64_t raw_off = P.one->pay_off[0], raw_len = P.one->pay_end - raw_off;
-  const OneWalk w = one_walk<false>(sh, P.B.in + raw_off, raw_len, P.unit_max, start, 0, lane);
+  const OneWalk w = one_walk<false>(sh, P.C.in + raw_off, raw_len, P.unit_max, start, 0, lane);
   if (lane != 0) return;
   if (tail) {
     // (status 0 here = the rule refused a header the reader takes: the two disagree.  The CPU model holds the rule

@@ -40,8 +40,9 @@ struct ZipEndHead {       // read back as one block
   uint32_t zip64;
 };
 
-// ---- reading: the directory.  Candidates as in BGZF discovery, their offsets counted from cd_off, so that
-// bgzf_link_kernel and bgzf_round_kernel (which know nothing of the format) link and rank them unchanged. ----
+// ---- reading: the directory.  The discovery skeleton (flate_kernels.h) over the directory: the tiles count from
+// (cd_off + A) & ~15, the candidates' offsets from cd_off, and bgzf_link_kernel links them as the members of a file of
+// cd_size bytes. ----
 struct ZipDirHead {       // read back as one block
   uint64_t out_bytes;     // the sum of size over the entries with status 0 (rc == 0 only)
   int64_t err_off;
@@ -49,21 +50,15 @@ struct ZipDirHead {       // read back as one block
   int32_t rc;
 };
 struct ZipDirParams {
-  const uint8_t *in;      // any byte alignment
-  uint64_t in_len, cd_off, cd_size;
+  ChainParams C;          // in / in_len: the archive; n_tiles: over the directory; cand_off: counted from cd_off;
+                          // member_off: unused; head: n_cand alone
+  uint64_t cd_off, cd_size;
   uint32_t n;             // records the end record promises
-  uint32_t n_tiles;       // 4 KiB tiles over the directory, on the 16-byte grid of in's ADDRESS
-  uint32_t cap, path_len, ent_cap;  // ent_cap = min(n, cap): entries / out_off hold that many (+ 1)
-  uint32_t *tile_cnt;     // n_tiles + 1
-  uint64_t *cand_off;     // cap: counted from cd_off
+  uint32_t ent_cap;       // min(n, cap): entries / C.out_off hold that many (+ 1)
   uint32_t *cand_total;   // cap
-  const uint32_t *path;   // path_len
-  BgzfHead *bhead;        // n_cand for the shared link / round kernels
   ZipDirHead *head;
   flate_hip_zip_entry *entries;
-  uint64_t *out_off;
 };
-constexpr uint32_t kZipTile = 4096;
 
 // ---- reading: behind the decoders ----
 struct ZipSel {           // one selected entry, built by the host from the index it has read back

@@ -11,12 +11,13 @@
 // READING, the end record:
 //   zip_end_find_kernel one thread per offset of the tail window: signature and p + 22 + comment == in_len, atomic max
 //   zip_end_read_kernel one thread: the rule at that offset (zip_end_read): n, the directory's range, or the verdict
-// READING, the directory (the host knows its range by now), as bgzf_kernels.hip finds members:
-//   zip_dir_count_kernel / zip_dir_scan_kernel / zip_dir_fill_kernel   every offset of the directory tested for the
-//                       signature in LDS (16-byte loads on the grid of the buffer's address, edges byte by byte, nothing
-//                       outside in[0, in_len) touched), the record rule on the rare hit, hits compacted in file order
-//   bgzf_link_kernel / bgzf_round_kernel (bgzf_kernels.hip, unchanged: offsets counted from cd_off, in_len = cd_size)
-//                       each candidate linked to the one at its own end, the chain from cd_off ranked by doubling
+// READING, the directory (the host knows its range by now): the skeleton of chain_walk.h (flate_kernels.h: THE
+// DISCOVERY SKELETON) over tiles that count from cd_off, the candidates' offsets counted from cd_off too:
+//   zip_dir_count_kernel / zip_dir_fill_kernel   the offset test: the signature in LDS, the record rule on the rare hit
+//                       inside the directory; a hit stores cand_off and cand_total
+//   zip_dir_scan_kernel the shared scan, and this format's own head
+//   bgzf_link_kernel    (bgzf_kernels.hip) over the directory as a file of cd_size bytes: a record ends at cand_off +
+//                       cand_total, the last one at cd_size
 //   zip_entry_kernel    one thread per rank: the record and its local header -> the entry (zip_entry_make); the threads
 //                       at rank n and at the chain's end write the archive's verdict
 //   zip_out_scan_kernel one workgroup: out_off = the exclusive scan of size over the entries with status 0
@@ -27,7 +28,7 @@
 //   zip_verdict_kernel  behind the CRC-32s of what was produced: the entry's verdict
 #include <hip/hip_runtime.h>
 
-#include "block_scan.h"
+#include "chain_walk.h"
 #include "flate_hip.h"
 #include "zip_kernels.h"
 #include "zip_rule.h"
@@ -105,32 +106,8 @@ __global__ void zip_end_read_kernel(const uint8_t *in, uint64_t in_len, ZipEndHe
 
 namespace {
 
-constexpr uint32_t kChunks = kZipTile / 16;  // 256: one per thread
-
-__device__ inline uint32_t buf_align(const ZipDirParams &P) { return (uint32_t)(reinterpret_cast<uintptr_t>(P.in) & 15u); }
 // the first tile's virtual position (virtual position = file offset + A: multiples of 16 are aligned addresses)
 __device__ inline uint64_t tiles_base(const ZipDirParams &P, uint32_t A) { return (P.cd_off + A) & ~15ull; }
-
-// the tile's bytes (kZipTile + 16 of halo) into LDS; bytes outside the file read as zero
-__device__ inline void load_tile(const ZipDirParams &P, uint8_t *lds, uint64_t v0, uint32_t A) {
-  const uint64_t v_end = (uint64_t)A + P.in_len;
-  for (uint32_t ch = threadIdx.x; ch <= kChunks; ch += 256u) {
-    const uint64_t v = v0 + 16ull * ch;
-    uint4 w = make_uint4(0u, 0u, 0u, 0u);
-    if (v >= A && v + 16u <= v_end) {
-      w = *reinterpret_cast<const uint4 *>(P.in + (v - A));
-    } else if (v + 16u > A && v < v_end) {
-      uint32_t d[4] = {0u, 0u, 0u, 0u};
-      for (uint32_t b = 0; b < 16u; ++b) {
-        const uint64_t vv = v + b;
-        if (vv >= A && vv < v_end) d[b >> 2] |= (uint32_t)P.in[vv - A] << (8u * (b & 3u));
-      }
-      w = make_uint4(d[0], d[1], d[2], d[3]);
-    }
-    *reinterpret_cast<uint4 *>(lds + 16u * ch) = w;
-  }
-  __syncthreads();
-}
 
 // this thread's 16 offsets: bit b of the result = a record can be read at virtual position v0 + 16 * tid + b (inside
 // the directory); totals[k]: the length of the k-th of them (two signatures are 4 bytes apart: at most 4 in 16)
@@ -145,7 +122,7 @@ __device__ inline uint32_t test_offsets(const ZipDirParams &P, const uint8_t *ld
     const uint64_t p = v - A;
     if (p < P.cd_off || p >= cd_end) continue;
     ZipCentral R;
-    const uint32_t t = zip_central_read(P.in + p, cd_end - p, &R);
+    const uint32_t t = zip_central_read(P.C.in + p, cd_end - p, &R);
     if (t && k < 4u) hits |= 1u << b, totals[k++] = t;
   }
   return hits;
@@ -154,31 +131,18 @@ __device__ inline uint32_t test_offsets(const ZipDirParams &P, const uint8_t *ld
 }  // namespace
 
 __global__ __launch_bounds__(256) void zip_dir_count_kernel(ZipDirParams P) {
-  __shared__ __attribute__((aligned(16))) uint8_t lds[kZipTile + 16];
-  __shared__ uint32_t wtot[4];
-  const uint32_t A = buf_align(P);
-  const uint64_t v0 = tiles_base(P, A) + (uint64_t)blockIdx.x * kZipTile;
-  load_tile(P, lds, v0, A);
+  __shared__ TileLds L;
+  const uint32_t A = tile_align(P.C.in);
+  const uint64_t v0 = tiles_base(P, A) + (uint64_t)blockIdx.x * kTileBytes;
   uint32_t totals[4];
-  const uint32_t hits = test_offsets(P, lds, v0, A, totals);
-  uint32_t sum = 0;
-  (void)block_scan_excl<4, uint32_t>((uint32_t)__popc(hits), wtot, &sum);
-  if (threadIdx.x == 0) P.tile_cnt[blockIdx.x] = sum;
+  tile_count(P.C, L, v0, [&](const uint8_t *lds) { return (uint32_t)__popc(test_offsets(P, lds, v0, A, totals)); });
 }
 
 // One workgroup: tile_cnt becomes its exclusive scan (n_tiles + 1 entries); both heads are initialised.
 __global__ __launch_bounds__(1024) void zip_dir_scan_kernel(ZipDirParams P) {
   __shared__ uint64_t wtot[16];
-  auto sat = [](uint64_t x) { return x > 0xffffffffull ? 0xffffffffu : (uint32_t)x; };
-  const uint64_t n = scan_range<16, uint64_t>(
-      P.n_tiles, wtot, [&](uint32_t i) { return (uint64_t)P.tile_cnt[i]; },
-      [&](uint32_t i, uint64_t at, uint64_t) { P.tile_cnt[i] = sat(at); });
+  tile_scan(P.C, wtot, 0);
   if (threadIdx.x == 0) {
-    P.tile_cnt[P.n_tiles] = sat(n);
-    BgzfHead b;
-    b.out_bytes = 0, b.err_off = 0, b.n_members = 0, b.rc = 0, b.eof_marker = 0;
-    b.n_cand = sat(n);
-    *P.bhead = b;
     ZipDirHead h;  // (what stands when not even cd_off holds a record)
     h.out_bytes = 0, h.err_off = (int64_t)P.cd_off, h.n_entries = 0, h.rc = FLATE_HIP_E_CORRUPT;
     *P.head = h;
@@ -186,39 +150,28 @@ __global__ __launch_bounds__(1024) void zip_dir_scan_kernel(ZipDirParams P) {
 }
 
 __global__ __launch_bounds__(256) void zip_dir_fill_kernel(ZipDirParams P) {
-  __shared__ __attribute__((aligned(16))) uint8_t lds[kZipTile + 16];
-  __shared__ uint32_t wtot[4];
-  if (P.bhead->n_cand > P.cap) return;  // (uniform: the arrays are too small, the host runs the pass again)
-  const uint32_t first = P.tile_cnt[blockIdx.x];
-  if (P.tile_cnt[blockIdx.x + 1] == first) return;  // (uniform: nothing in this tile)
-  const uint32_t A = buf_align(P);
-  const uint64_t v0 = tiles_base(P, A) + (uint64_t)blockIdx.x * kZipTile;
-  load_tile(P, lds, v0, A);
-  uint32_t totals[4];
-  const uint32_t hits = test_offsets(P, lds, v0, A, totals);
-  uint32_t sum = 0;
-  uint32_t at = first + block_scan_excl<4, uint32_t>((uint32_t)__popc(hits), wtot, &sum);
-  uint32_t k = 0;
-  for (uint32_t b = 0; b < 16u; ++b) {
-    if (!((hits >> b) & 1u)) continue;
-    if (at < P.cap) {
-      P.cand_off[at] = v0 + 16u * threadIdx.x + b - A - P.cd_off;
-      P.cand_total[at] = totals[k];
-    }
-    ++at, ++k;
-  }
+  __shared__ TileLds L;
+  const uint32_t A = tile_align(P.C.in);
+  const uint64_t v0 = tiles_base(P, A) + (uint64_t)blockIdx.x * kTileBytes;
+  uint32_t first, totals[4];
+  if (!tile_fill_load(P.C, L, v0, false, &first)) return;
+  const uint32_t hits = test_offsets(P, L.bytes, v0, A, totals);
+  tile_put16(hits, tile_fill_at(L, first, (uint32_t)__popc(hits)), P.C.cap, [&](uint32_t i, uint32_t b, uint32_t k) {
+    P.C.cand_off[i] = v0 + 16u * threadIdx.x + b - A - P.cd_off;
+    P.cand_total[i] = totals[k];
+  });
 }
 
 // One thread per rank of the chain from cd_off.  L = the chain's records; the serial walk reads min(L, n) of them and
 // then stops: at the n-th record's end (which must be the directory's), or where the chain does.
 __global__ __launch_bounds__(256) void zip_entry_kernel(ZipDirParams P) {
-  const uint32_t nc = P.bhead->n_cand;
-  if (nc > P.cap) return;
+  const uint32_t nc = P.C.head->n_cand;
+  if (nc > P.C.cap) return;
   const uint32_t r = blockIdx.x * 256u + threadIdx.x;
-  if (r + 1u >= P.path_len) return;  // (the last entry is a sink)
-  const uint32_t c = P.path[r];
+  if (r + 1u >= P.C.path_len) return;  // (the last entry is a sink)
+  const uint32_t c = P.C.path[r];
   if (c >= nc) return;
-  const uint64_t off = P.cd_off + P.cand_off[c];
+  const uint64_t off = P.cd_off + P.C.cand_off[c];
   const uint32_t total = P.cand_total[c];
   ZipDirHead *h = P.head;
   if (r == P.n) {  // a record where the directory should have ended: bytes left behind n records
@@ -228,10 +181,10 @@ __global__ __launch_bounds__(256) void zip_entry_kernel(ZipDirParams P) {
   if (r > P.n) return;
   if (r < P.ent_cap) {
     ZipCentral R;
-    (void)zip_central_read(P.in + off, P.cd_off + P.cd_size - off, &R);  // (a candidate: it reads)
-    zip_entry_make(P.in, P.cd_off, off, R, P.entries + r);
+    (void)zip_central_read(P.C.in + off, P.cd_off + P.cd_size - off, &R);  // (a candidate: it reads)
+    zip_entry_make(P.C.in, P.cd_off, off, R, P.entries + r);
   }
-  const uint32_t succ = P.path[r + 1u];  // (path_len >= cap + 2: r + 1 is inside the path)
+  const uint32_t succ = P.C.path[r + 1u];  // (path_len >= cap + 2: r + 1 is inside the path)
   if (succ < nc) return;
   // the chain's last record, L = r + 1 <= n: one thread gets here
   h->n_entries = r + 1u;
@@ -244,13 +197,13 @@ __global__ __launch_bounds__(256) void zip_entry_kernel(ZipDirParams P) {
 
 __global__ __launch_bounds__(1024) void zip_out_scan_kernel(ZipDirParams P) {
   __shared__ uint64_t wtot[16];
-  if (P.bhead->n_cand > P.cap || P.head->rc != 0) return;  // (uniform)
+  if (P.C.head->n_cand > P.C.cap || P.head->rc != 0) return;  // (uniform)
   const uint32_t hi = P.head->n_entries;                    // (= n <= ent_cap)
   const uint64_t total = scan_range<16, uint64_t>(
       hi, wtot, [&](uint32_t i) { return P.entries[i].status == 0 ? P.entries[i].size : 0ull; },
-      [&](uint32_t i, uint64_t before, uint64_t) { P.out_off[i] = before; });
+      [&](uint32_t i, uint64_t before, uint64_t) { P.C.out_off[i] = before; });
   if (threadIdx.x == 0) {
-    P.out_off[hi] = total;
+    P.C.out_off[hi] = total;
     P.head->out_bytes = total;
   }
 }

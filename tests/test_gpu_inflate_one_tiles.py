@@ -19,7 +19,7 @@ from util import flate
 
 gpu = pytest.mark.gpu  # (the one test without it checks the placed streams themselves, on the CPU)
 
-TILE = 4096  # kBgzfTile
+TILE = 4096  # kTileBytes
 OFFSETS = tuple(range(-17, 2))  # the header's byte against the tile boundary: the last 11 bytes of a tile read the halo
 LIT, DIST = dc.small_lens()
 
@@ -105,7 +105,7 @@ def small_stream(blocks):
 @gpu
 @pytest.mark.parametrize("A", (1, 15))
 def test_first_chunk_at_an_unaligned_address(eng, A):
-    """The stream starts with a dynamic block at a pointer that is not 16-aligned: the byte-wise branch of load_tile."""
+    """The stream starts with a dynamic block at a pointer that is not 16-aligned: the byte-wise branch of tile_load."""
     raw, plain = small_stream(2)
     w = ref.Walk(raw)
     assert zlib.decompress(raw, -15) == plain and w.n_units == 2

@@ -2,7 +2,7 @@
 wavefront, a chunk of 1024 or the carry between two chunks can go wrong -- through the calls that run them:
     scan_sizes_kernel          deflate_batch on device pointers
     frame_scan_kernel          deflate_batch_framed (zlib, gzip) and bgzf_write
-    bgzf_scan_kernel           bgzf_index / bgzf_read of files of more than 1024 and 2048 tiles of 4 KiB
+    chain_scan_kernel           bgzf_index / bgzf_read of files of more than 1024 and 2048 tiles of 4 KiB
     bgzf_range_layout_kernel   bgzf_read_ranges with more than 1024 and 2048 ranges
 Every expectation is exact and comes from the CPU (the oracle, tests/bgzf_ref.py, tests/bgzf_range_ref.py), computed
 once for the largest count; the smaller counts use its prefixes."""
@@ -21,7 +21,7 @@ N = max(COUNTS)
 KINDS = ["ramp", "zero", "rand", "text", "low", "period", "runs"]  # (util.make_streams)
 WRAPS = ["zlib", "gzip"]
 BLOCK = 16  # bgzf_write: bytes per member
-TILE = 4096  # bgzf_count_kernel: bytes per workgroup, one element of bgzf_scan_kernel each
+TILE = 4096  # bgzf_count_kernel: bytes per workgroup, one element of chain_scan_kernel each
 GUARD = 0xA5
 
 
@@ -129,7 +129,7 @@ def test_bgzf_member_offsets(eng, blocks, n):
     assert ei.value.code == E_OUT_TOO_SMALL
 
 
-# ---- 3. bgzf_scan_kernel -------------------------------------------------------------------------------------------
+# ---- 3. chain_scan_kernel -------------------------------------------------------------------------------------------
 TILE_COUNTS = [1023, 1024, 1025, 2048, 2049]
 
 
