@@ -2,6 +2,11 @@
 
 The C ABI (include/flate_hip.h) is the product boundary; this module only marshals
 numpy / torch buffers into it.  PyTorch is used for device memory and streams only.
+
+Every method resolves its buffers through the same few helpers: _in_buf for the
+input, _out_buf for the output and the capacity the library is told, _stream_results for the per-stream tables,
+FlateEngine._tolerate for the statuses a method hands back instead of raising, _query_then_fill for the index
+calls and _read_into for the calls that size their output by a query.
 """
 import collections
 import ctypes as C
@@ -18,6 +23,21 @@ LZ_SERIAL = 0x4
 SIZE_ONLY = 0x8
 NO_DICT = 0xFFFFFFFF  # FLATE_HIP_NO_DICT: a stream of flate_hip_inflate_batch_dict without a dictionary
 
+# status codes (include/flate_hip.h)
+E_INVALID, E_OUT_TOO_SMALL, E_CORRUPT, E_UNEXPECTED_EOF, E_INTERNAL = -1, -2, -4, -7, -8
+E_TOO_LARGE, E_UNSUPPORTED = -6, -10
+# what a call returns when some stream, member or entry failed: the caller reads the verdicts, nothing is raised
+PER_STREAM = (E_OUT_TOO_SMALL, E_CORRUPT, E_UNEXPECTED_EOF)
+# ... and the index calls, whose chain can also break at a member or unit beyond the size limit
+PER_CHAIN = PER_STREAM + (E_TOO_LARGE,)
+
+CHECKSUM_ADLER32, CHECKSUM_CRC32 = 1, 2
+CHECKSUMS = {"adler32": CHECKSUM_ADLER32, "crc32": CHECKSUM_CRC32}
+WRAP_RAW, WRAP_ZLIB, WRAP_GZIP = 0, 1, 2  # FLATE_HIP_WRAP_*
+WRAPS = {"raw": WRAP_RAW, "zlib": WRAP_ZLIB, "gzip": WRAP_GZIP}
+ZLIB_HEADER = bytes([0x78, 0x01])  # CM = 8, CINFO = 7 (32 KiB window), FLEVEL = 0 (fastest), FCHECK (RFC 1950 2.2)
+GZIP_HEADER = bytes([0x1f, 0x8b, 8, 0, 0, 0, 0, 0, 4, 255])  # no name / time, XFL = 4 (fastest), OS unknown (RFC 1952 2.3)
+
 SYNTH_RAMP, SYNTH_TEXT, SYNTH_RAND, SYNTH_ZERO = 0, 1, 2, 3
 SYNTH_KINDS = {"ramp": SYNTH_RAMP, "text": SYNTH_TEXT, "rand": SYNTH_RAND, "zero": SYNTH_ZERO}
 SEED_TEXT = 0x5EED0001
@@ -27,6 +47,26 @@ STAGES = ("lz77_match", "huff_pack", "checksum", "inflate")
 
 MAX_STORE_BLOCK_SIZE = 65535
 MATCH_CAP_PER_CHUNK = 16384
+
+BGZF_BLOCK_DEFAULT = 65280  # FLATE_HIP_BGZF_BLOCK_DEFAULT
+BGZF_MEMBER_MAX = 65536
+BGZF_EOF = bytes.fromhex("1f8b08040000000000ff0600424302001b0003000000000000000000")
+BgzfIndex = collections.namedtuple("BgzfIndex", "rc n_members out_bytes eof_marker err_off member_off out_off")
+BgzfRead = collections.namedtuple("BgzfRead", "rc out_len n_members bad_member err_off eof_marker")
+BgzfRanges = collections.namedtuple("BgzfRanges", "rc out_off range_status n_members n_decoded bad_member err_off")
+GZIP_MEMBER_MAX = (1 << 28) - 1  # the option "gzip_member_max": its default and its maximum
+GzipIndex = collections.namedtuple("GzipIndex", "rc n_members out_bytes n_candidates err_off member_off out_off")
+OneRead = collections.namedtuple("OneRead", "rc out_len status err_off n_units n_candidates")
+OneIndex = collections.namedtuple("OneIndex", "rc n_units out_bytes n_candidates status err_off unit_bit out_off")
+GzipRead = collections.namedtuple("GzipRead", "rc out_len n_members bad_member err_off")
+
+# flate_hip_zip_entry, as numpy sees it (64 bytes)
+ZIP_ENTRY = np.dtype([("name_off", "<u8"), ("header_off", "<u8"), ("data_off", "<u8"), ("comp_size", "<u8"), ("size", "<u8"),
+                      ("crc32", "<u4"), ("name_len", "<u2"), ("method", "<u2"), ("flags", "<u2"), ("reserved", "<u2"),
+                      ("status", "<i4"), ("reserved2", "<u4")], align=True)
+assert ZIP_ENTRY.itemsize == 64
+ZipIndex = collections.namedtuple("ZipIndex", "rc n_entries out_bytes err_off entries out_off names")
+ZipRead = collections.namedtuple("ZipRead", "rc out_off out_len status err_off n_entries archive_err_off")
 
 
 class FlateError(RuntimeError):
@@ -44,37 +84,20 @@ def deflate_bound(n):
     return int(_lib.load().flate_hip_deflate_bound(int(n)))
 
 
+def _wrap_code(wrap):
+    """FLATE_HIP_WRAP_* of the framed methods' wrap argument ("zlib", "raw"; anything else has always meant gzip)."""
+    return WRAPS.get(wrap, WRAP_GZIP)
+
+
 def frame_overhead(wrap, with_dict=False):
     """Bytes a zlib / gzip member adds around its raw stream (flate_hip_frame_overhead)."""
     return int(_lib.load().flate_hip_frame_overhead(_wrap_code(wrap) if isinstance(wrap, str) else int(wrap),
                                                     1 if with_dict else 0))
 
 
-BGZF_BLOCK_DEFAULT = 65280  # FLATE_HIP_BGZF_BLOCK_DEFAULT
-BGZF_MEMBER_MAX = 65536
-BGZF_EOF = bytes.fromhex("1f8b08040000000000ff0600424302001b0003000000000000000000")
-BgzfIndex = collections.namedtuple("BgzfIndex", "rc n_members out_bytes eof_marker err_off member_off out_off")
-BgzfRead = collections.namedtuple("BgzfRead", "rc out_len n_members bad_member err_off eof_marker")
-BgzfRanges = collections.namedtuple("BgzfRanges", "rc out_off range_status n_members n_decoded bad_member err_off")
-GZIP_MEMBER_MAX = (1 << 28) - 1  # the option "gzip_member_max": its default and its maximum
-GzipIndex = collections.namedtuple("GzipIndex", "rc n_members out_bytes n_candidates err_off member_off out_off")
-OneRead = collections.namedtuple("OneRead", "rc out_len status err_off n_units n_candidates")
-OneIndex = collections.namedtuple("OneIndex", "rc n_units out_bytes n_candidates status err_off unit_bit out_off")
-GzipRead = collections.namedtuple("GzipRead", "rc out_len n_members bad_member err_off")
-
-
 def bgzf_bound(n, block_bytes=0):
     """Room that always holds the BGZF file of n input bytes (flate_hip_bgzf_bound; 0: block_bytes is refused)."""
     return int(_lib.load().flate_hip_bgzf_bound(int(n), int(block_bytes)))
-
-
-# flate_hip_zip_entry, as numpy sees it (64 bytes)
-ZIP_ENTRY = np.dtype([("name_off", "<u8"), ("header_off", "<u8"), ("data_off", "<u8"), ("comp_size", "<u8"), ("size", "<u8"),
-                      ("crc32", "<u4"), ("name_len", "<u2"), ("method", "<u2"), ("flags", "<u2"), ("reserved", "<u2"),
-                      ("status", "<i4"), ("reserved2", "<u4")], align=True)
-assert ZIP_ENTRY.itemsize == 64
-ZipIndex = collections.namedtuple("ZipIndex", "rc n_entries out_bytes err_off entries out_off names")
-ZipRead = collections.namedtuple("ZipRead", "rc out_off out_len status err_off n_entries archive_err_off")
 
 
 def _zip_names(names):
@@ -131,6 +154,127 @@ def _check_out(out, data, need, what):
                                     "same device as the input" % (what, need))
 
 
+def _in_buf(data, accept_bytes=False, lax=False, null_if_empty=False):
+    """(data, pointer, bytes, device) of a call's input: a numpy uint8 array (made contiguous; with accept_bytes also
+    bytes / bytearray) or a torch uint8 CUDA tensor, which must be contiguous (lax: checksum_batch and inflate_sizes
+    have never asserted that).  null_if_empty: the single-buffer calls hand the library NULL for no input at all;
+    the batch calls, whose offset table says that there is none, hand it the buffer's address whatever its size."""
+    device = _is_torch(data)
+    if device:
+        if not lax:
+            import torch
+            assert data.dtype == torch.uint8 and data.is_cuda and data.is_contiguous()
+        ptr, nbytes = data.data_ptr(), data.numel()
+    else:
+        if accept_bytes and isinstance(data, (bytes, bytearray)):
+            data = np.frombuffer(data, dtype=np.uint8)
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        ptr, nbytes = data.ctypes.data, data.size
+    return data, (None if null_if_empty and not nbytes else ptr), nbytes, device
+
+
+def _out_buf(out, data, size, out_cap, need, what, floor=16):
+    """(out, pointer, capacity) of a call's output.  out=None: room for `size` bytes (at least `floor`) on the side
+    of `data` -- zeroed on the host, torch.empty on the device; otherwise the caller's buffer, which _check_out
+    wants to be of data's kind and of at least `need` bytes.  The capacity is what the library is told: the
+    buffer's size, cut to out_cap where the method has one and the caller gave it.  (deflate_batch and
+    deflate_spliced pass out_cap=None: they have always told the library the whole buffer.  The inflate calls take
+    no capacity at all: their slot table bounds every write, which is why `need` is that table's end for them.)"""
+    device = _is_torch(data)
+    if out is not None:
+        _check_out(out, data, need, what)
+    elif device:
+        import torch
+        out = torch.empty(max(int(size), floor), dtype=torch.uint8, device=data.device)
+    else:
+        out = np.zeros(max(int(size), floor), dtype=np.uint8)
+    room = out.numel() if device else out.size
+    return out, (out.data_ptr() if device else out.ctypes.data), room if out_cap is None else min(int(out_cap), room)
+
+
+def _host_bytes(x):
+    """The bytes of a (small) piece of the input, wherever it is."""
+    return (x.cpu().numpy() if _is_torch(x) else x).tobytes()
+
+
+def _no_bytes(data):
+    """An empty buffer of data's kind."""
+    return data[:0] if _is_torch(data) else np.zeros(0, dtype=np.uint8)
+
+
+def _offsets(off):
+    """(the offset table as contiguous numpy uint64, the number of streams it describes)."""
+    off = np.ascontiguousarray(off, dtype=np.uint64)
+    return off, off.size - 1
+
+
+def _slots(out_sizes, n):
+    """out_off[n + 1]: the slots of out_sizes back to back."""
+    out_off = np.zeros(n + 1, dtype=np.uint64)
+    np.cumsum(np.asarray(out_sizes, dtype=np.uint64), out=out_off[1:])
+    return out_off
+
+
+def _deflate_room(in_off):
+    """Room that always holds the raw streams of a batch: the sum of deflate_bound over its stream lengths."""
+    lens = in_off[1:] - in_off[:-1]
+    return int(sum(deflate_bound(int(l)) * int(c) for l, c in zip(*np.unique(lens, return_counts=True))))
+
+
+def _stream_results(n, pad=True):
+    """(out_len, status, err_off) for the library to fill.  pad: one entry even for an empty batch, so that the
+    pointers are never those of empty arrays; the caller returns [:n]."""
+    m = max(n, 1) if pad else n
+    return np.zeros(m, dtype=np.uint64), np.zeros(m, dtype=np.int32), np.full(m, -1, dtype=np.int64)
+
+
+def _file_result(out, out_len, device, index, table):
+    """What bgzf_write and zip_write return: the file as bytes (host) or (out, out_len) (device), then the table."""
+    res = (out, out_len) if device else (bytes(out[:out_len]),)
+    if index:
+        res = res + (table,)
+    return res if len(res) > 1 else res[0]
+
+
+def _query_then_fill(call, found, result, index_cap, query, prefix, guess=None):
+    """The protocol of the index calls.  call(cap, a_ptr, b_ptr) -> rc fills two uint64 tables of cap entries;
+    found() is the count the last call reported, its tables have found() + 1 entries; result(rc, a, b) builds what
+    the method returns.  query: the counts alone.  index_cap=None: sized by a query first -- or, with `guess`, by
+    that guess, and by the count only if the guess was too small (where the discovery is the whole cost of a call).
+    prefix: a broken chain still delivers the tables of the good entries in front (whenever they fit); without it
+    the tables come with rc 0 only, and a query that fails is the answer."""
+    if query:
+        return result(call(0, None, None), None, None)
+    if index_cap is not None:
+        caps = [int(index_cap)]
+    elif guess is not None:
+        caps = [guess, None]
+    else:
+        rc = call(0, None, None)
+        if rc != 0 and not prefix:
+            return result(rc, None, None)
+        caps = [None]
+    for cap in caps:
+        cap = found() + 1 if cap is None else cap
+        a = np.zeros(max(cap, 1), dtype=np.uint64)
+        b = np.zeros(max(cap, 1), dtype=np.uint64)
+        rc = call(cap, a.ctypes.data, b.ctypes.data)
+        k = found() + 1
+        if (k <= cap) if prefix else (rc == 0):
+            a, b = a[:k], b[:k]
+            return result(rc, a, b) if guess is None else result(rc, a.copy(), b.copy())  # (a guess can be far too large)
+    return result(rc, None, None)
+
+
+def _read_into(out, data, out_cap, what, call, size):
+    """The calls that deliver bytes into `out`: call(out_ptr, cap) -> the method's result.  out=None: size() ->
+    (bytes needed, None) first, or (0, the result) when the query is the answer already and there is nothing to
+    deliver; then room for that.  Otherwise the caller's buffer, its capacity cut to out_cap.  One call."""
+    need, done = size() if out is None else (0, None)
+    out, ptr, cap = _out_buf(out, data, need, out_cap, 0, what)
+    return out, (call(ptr, cap) if done is None else done)
+
+
 class FlateEngine:
     """One engine = one flate_hip_ctx = one GPU + one HIP stream."""
 
@@ -158,6 +302,12 @@ class FlateEngine:
             msg = self._L.flate_hip_strerror(rc).decode()
             extra = self._L.flate_hip_last_hip_error(self._ctx).decode()
             raise FlateError(rc, msg + (" [" + extra + "]" if extra else ""))
+
+    def _tolerate(self, rc, *allowed):
+        """rc, if it is 0 or one of the statuses this call hands back to its caller; anything else raises."""
+        if rc not in allowed:
+            self._check(rc)
+        return rc
 
     def use_stream(self, hip_stream_ptr):
         """Launch on the given hipStream_t (int address), e.g. torch.cuda.current_stream().cuda_stream."""
@@ -222,60 +372,35 @@ class FlateEngine:
         (inflate_batch(..., zdicts=), zlib.decompressobj(-15, zdict=)); compat_go=True is the mode in which
         matches extend into the dictionary; payloads under 128 bytes get nothing from it (include/flate_hip.h).
         Returns (out, out_off): out has the same kind as data, out_off is numpy uint64[n+1]."""
-        in_off = np.ascontiguousarray(in_off, dtype=np.uint64)
-        n = in_off.size - 1
+        in_off, n = _offsets(in_off)
         out_off = np.zeros(n + 1, dtype=np.uint64)
-        device = _is_torch(data)
+        data, in_ptr, _, device = _in_buf(data)
         if out_cap is None and out is None:
-            lens = in_off[1:] - in_off[:-1]
-            out_cap = sum(deflate_bound(int(l)) * int(c)
-                          for l, c in zip(*np.unique(lens, return_counts=True)))
-        if device:
-            import torch
-            assert data.dtype == torch.uint8 and data.is_cuda and data.is_contiguous()
-            if out is None:
-                out = torch.empty(max(int(out_cap), 16), dtype=torch.uint8, device=data.device)
-            else:
-                _check_out(out, data, 1, "deflate_batch")
-            cap = out.numel()
-            in_ptr, out_ptr = data.data_ptr(), out.data_ptr()
-        else:
-            data = np.ascontiguousarray(data, dtype=np.uint8)
-            if out is None:
-                out = np.empty(max(int(out_cap), 16), dtype=np.uint8)
-            else:
-                _check_out(out, data, 1, "deflate_batch")
-            cap = out.size
-            in_ptr, out_ptr = data.ctypes.data, out.ctypes.data
+            out_cap = _deflate_room(in_off)
+        out, out_ptr, cap = _out_buf(out, data, out_cap, None, 1, "deflate_batch")
+        flags = self._flags(compat_go, lz_serial, device)
         if zdicts is None:
             rc = self._L.flate_hip_deflate_fast_batch(self._ctx, in_ptr, in_off.ctypes.data, n, out_ptr,
-                                                      cap, out_off.ctypes.data,
-                                                      self._flags(compat_go, lz_serial, device))
+                                                      cap, out_off.ctypes.data, flags)
         else:
             dk = _DictArgs(zdicts, dict_of, n, device)
             rc = self._L.flate_hip_deflate_fast_batch_dict(self._ctx, in_ptr, in_off.ctypes.data, n, dk.ptr,
                                                            dk.off_ptr, dk.n_dicts, dk.of_ptr, out_ptr, cap,
-                                                           out_off.ctypes.data,
-                                                           self._flags(compat_go, lz_serial, device))
+                                                           out_off.ctypes.data, flags)
         self._check(rc)
         return out, out_off
 
     def checksum_batch(self, data, in_off, kind="adler32"):
         """Adler-32 (RFC 1950) or CRC-32 (RFC 1952) of every stream data[in_off[i]:in_off[i+1]] -> numpy uint32[n]
         (flate_hip_checksum_batch; numpy data = host pointers, torch CUDA tensor = device pointers)."""
-        in_off = np.ascontiguousarray(in_off, dtype=np.uint64)
-        n = in_off.size - 1
-        out = np.zeros(max(n, 1), dtype=np.uint32)
-        device = _is_torch(data)
-        if device:
-            ptr = data.data_ptr()
-        else:
-            data = np.ascontiguousarray(data, dtype=np.uint8)
-            ptr = data.ctypes.data if data.size else None
-        k = {"adler32": CHECKSUM_ADLER32, "crc32": CHECKSUM_CRC32}[kind]
-        self._check(self._L.flate_hip_checksum_batch(self._ctx, ptr, in_off.ctypes.data, n, k, out.ctypes.data,
-                                                     DEVICE_PTRS if device else 0))
-        return out[:n]
+        in_off, n = _offsets(in_off)
+        sums = np.zeros(max(n, 1), dtype=np.uint32)
+        data, ptr, nbytes, device = _in_buf(data, lax=True)
+        if not device and not nbytes:
+            ptr = None  # (only here, and only for host data, does a batch call say NULL for no bytes)
+        self._check(self._L.flate_hip_checksum_batch(self._ctx, ptr, in_off.ctypes.data, n, CHECKSUMS[kind],
+                                                     sums.ctypes.data, self._flags(False, False, device)))
+        return sums[:n]
 
     def deflate_batch_framed(self, data, in_off, wrap, compat_go=False, zdicts=None, dict_of=None, out=None,
                              out_cap=None):
@@ -288,39 +413,19 @@ class FlateEngine:
         the dictionary's Adler-32 as DICTID (RFC 1950 2.2), so that inflate_batch_framed(..., zdicts=) and
         zlib.decompressobj(zdict=) find it; the trailer stays the payload's checksum.  (gzip has no preset
         dictionaries: ValueError.)"""
-        in_off = np.ascontiguousarray(in_off, dtype=np.uint64)
-        n = in_off.size - 1
+        in_off, n = _offsets(in_off)
         w = _wrap_code(wrap)
         if zdicts is not None and w == WRAP_GZIP:
             raise ValueError("preset dictionaries exist in the zlib container only")
-        device = _is_torch(data)
+        data, in_ptr, _, device = _in_buf(data)
         if out_cap is None and out is None:
-            lens = in_off[1:] - in_off[:-1]
-            out_cap = sum(deflate_bound(int(l)) * int(c) for l, c in zip(*np.unique(lens, return_counts=True))) + \
-                n * frame_overhead(wrap, zdicts is not None)
-        if device:
-            import torch
-            assert data.dtype == torch.uint8 and data.is_cuda and data.is_contiguous()
-            if out is None:
-                out = torch.empty(max(int(out_cap), 16), dtype=torch.uint8, device=data.device)
-            else:
-                _check_out(out, data, 0, "deflate_batch_framed")
-            cap = out.numel() if out_cap is None else min(int(out_cap), out.numel())
-            in_ptr, out_ptr = data.data_ptr(), out.data_ptr()
-        else:
-            data = np.ascontiguousarray(data, dtype=np.uint8)
-            if out is None:
-                out = np.empty(max(int(out_cap), 16), dtype=np.uint8)
-            else:
-                _check_out(out, data, 0, "deflate_batch_framed")
-            cap = out.size if out_cap is None else min(int(out_cap), out.size)
-            in_ptr, out_ptr = data.ctypes.data, out.ctypes.data
+            out_cap = _deflate_room(in_off) + n * frame_overhead(wrap, zdicts is not None)
+        out, out_ptr, cap = _out_buf(out, data, out_cap, out_cap, 0, "deflate_batch_framed")
         out_off = np.zeros(n + 1, dtype=np.uint64)
-        dk = _DictArgs(zdicts, dict_of, n, device) if zdicts is not None else None
+        dk = _DictArgs(zdicts, dict_of, n, device)
         self._check(self._L.flate_hip_deflate_fast_batch_framed(
-            self._ctx, in_ptr, in_off.ctypes.data, n, w, dk.ptr if dk else None, dk.off_ptr if dk else None,
-            dk.n_dicts if dk else 0, dk.of_ptr if dk else None, out_ptr, cap, out_off.ctypes.data,
-            self._flags(compat_go, False, device)))
+            self._ctx, in_ptr, in_off.ctypes.data, n, w, dk.ptr, dk.off_ptr, dk.n_dicts, dk.of_ptr, out_ptr, cap,
+            out_off.ctypes.data, self._flags(compat_go, False, device)))
         return (out if device else out[:int(out_off[-1])]), out_off
 
     def deflate_spliced_framed(self, data, in_off, wrap, compat_go=False, out=None, out_cap=None, index=False):
@@ -330,31 +435,12 @@ class FlateEngine:
         into the concatenated input; one call, framed on the GPU (flate_hip_deflate_fast_spliced_framed).
         Host data: returns bytes.  A torch CUDA tensor, or index=True: returns (out, out_len, bit_off[n+1]) as
         deflate_spliced does, bit_off counted from the raw stream's first byte (out[2:] zlib, out[10:] gzip)."""
-        in_off = np.ascontiguousarray(in_off, dtype=np.uint64)
-        n = in_off.size - 1
+        in_off, n = _offsets(in_off)
         w = _wrap_code(wrap)
-        device = _is_torch(data)
+        data, in_ptr, _, device = _in_buf(data)
         if out_cap is None and out is None:
-            lens = in_off[1:] - in_off[:-1]
-            out_cap = int(sum(deflate_bound(int(l)) * int(c) for l, c in zip(*np.unique(lens, return_counts=True)))) + \
-                16 + frame_overhead(wrap)
-        if device:
-            import torch
-            assert data.dtype == torch.uint8 and data.is_cuda and data.is_contiguous()
-            if out is None:
-                out = torch.empty(int(out_cap), dtype=torch.uint8, device=data.device)
-            else:
-                _check_out(out, data, 0, "deflate_spliced_framed")
-            cap = out.numel() if out_cap is None else min(int(out_cap), out.numel())
-            in_ptr, out_ptr = data.data_ptr(), out.data_ptr()
-        else:
-            data = np.ascontiguousarray(data, dtype=np.uint8)
-            if out is None:
-                out = np.zeros(int(out_cap), dtype=np.uint8)
-            else:
-                _check_out(out, data, 0, "deflate_spliced_framed")
-            cap = out.size if out_cap is None else min(int(out_cap), out.size)
-            in_ptr, out_ptr = data.ctypes.data, out.ctypes.data
+            out_cap = _deflate_room(in_off) + 16 + frame_overhead(wrap)
+        out, out_ptr, cap = _out_buf(out, data, out_cap, out_cap, 0, "deflate_spliced_framed")
         bit_off = np.zeros(n + 1, dtype=np.uint64)
         out_len = C.c_uint64(0)
         self._check(self._L.flate_hip_deflate_fast_spliced_framed(
@@ -374,30 +460,18 @@ class FlateEngine:
         FDICT is decoded with the first one whose Adler-32 is its DICTID (RFC 1950 2.2) -- none matches, or no
         zdicts: the member is corrupt.  The details (err_off, the dictionary every member chose) are kept in
         self.last_framed_read = (err_off, dict_used)."""
-        in_off = np.ascontiguousarray(in_off, dtype=np.uint64)
-        n = in_off.size - 1
+        in_off, n = _offsets(in_off)
         w = _wrap_code(wrap)
-        device = _is_torch(data)
-        if device:
-            import torch
-            assert data.dtype == torch.uint8 and data.is_cuda and data.is_contiguous()
-            in_ptr = data.data_ptr()
-        else:
-            data = np.ascontiguousarray(data, dtype=np.uint8)
-            in_ptr = data.ctypes.data
-        dk = _DictArgs(zdicts, None, n, device) if zdicts is not None and w == WRAP_ZLIB else None
-        out_len = np.zeros(max(n, 1), dtype=np.uint64)
-        status = np.zeros(max(n, 1), dtype=np.int32)
-        err_off = np.full(max(n, 1), -1, dtype=np.int64)
+        data, in_ptr, _, device = _in_buf(data)
+        dk = _DictArgs(zdicts if w == WRAP_ZLIB else None, None, n, device)
+        out_len, status, err_off = _stream_results(n)
         dict_used = np.full(max(n, 1), NO_DICT, dtype=np.uint32)
 
         def call(out_ptr, off_ptr, flags):
-            rc = self._L.flate_hip_inflate_batch_framed(
-                self._ctx, in_ptr, in_off.ctypes.data, n, w, dk.ptr if dk else None, dk.off_ptr if dk else None,
-                dk.n_dicts if dk else 0, out_ptr, off_ptr, out_len.ctypes.data, status.ctypes.data,
-                err_off.ctypes.data, dict_used.ctypes.data, flags | (DEVICE_PTRS if device else 0))
-            if rc not in (0, E_OUT_TOO_SMALL, E_CORRUPT, E_UNEXPECTED_EOF):
-                self._check(rc)
+            self._tolerate(self._L.flate_hip_inflate_batch_framed(
+                self._ctx, in_ptr, in_off.ctypes.data, n, w, dk.ptr, dk.off_ptr, dk.n_dicts, out_ptr, off_ptr,
+                out_len.ctypes.data, status.ctypes.data, err_off.ctypes.data, dict_used.ctypes.data,
+                flags | self._flags(False, False, device)), *PER_STREAM)
 
         if out_sizes is None:
             if w == WRAP_GZIP:
@@ -405,29 +479,11 @@ class FlateEngine:
             else:
                 call(None, None, SIZE_ONLY)
                 out_sizes = out_len[:n].copy()
-        out_off = np.zeros(n + 1, dtype=np.uint64)
-        np.cumsum(np.asarray(out_sizes, dtype=np.uint64), out=out_off[1:])
-        total = max(int(out_off[-1]), 16)
-        if out is not None:
-            _check_out(out, data, int(out_off[-1]), "inflate_batch_framed")
-        elif device:
-            out = torch.empty(total, dtype=torch.uint8, device=data.device)
-        else:
-            out = np.zeros(total, dtype=np.uint8)
-        call(out.data_ptr() if device else out.ctypes.data, out_off.ctypes.data, 0)
+        out_off = _slots(out_sizes, n)
+        out, out_ptr, _ = _out_buf(out, data, out_off[-1], None, int(out_off[-1]), "inflate_batch_framed")
+        call(out_ptr, out_off.ctypes.data, 0)
         self.last_framed_read = (err_off[:n], dict_used[:n])
         return out, out_off, out_len[:n], status[:n]
-
-    @staticmethod
-    def _bgzf_in(data):
-        """(data, pointer, bytes, device) of a numpy uint8 array or a torch uint8 CUDA tensor."""
-        if _is_torch(data):
-            import torch
-            assert data.dtype == torch.uint8 and data.is_cuda and data.is_contiguous()
-            return data, (data.data_ptr() if data.numel() else None), data.numel(), True
-        data = np.ascontiguousarray(np.frombuffer(data, dtype=np.uint8) if isinstance(data, (bytes, bytearray))
-                                    else data, dtype=np.uint8)
-        return data, (data.ctypes.data if data.size else None), data.size, False
 
     def bgzf_write(self, data, block_bytes=0, compat_go=False, out=None, index=False, out_cap=None):
         """data as ONE BGZF file (the blocked gzip of the SAM/BAM specification; flate_hip_bgzf_write): a member of
@@ -437,36 +493,19 @@ class FlateEngine:
         the file as bytes) or a torch uint8 CUDA tensor (data and file stay on the device; returns (out, out_len),
         the file in out[:out_len]).  index=True: member_off (numpy uint64[n_blocks + 1]) is appended to the result.
         A block that compresses to more than 65536 bytes: FlateError(E_TOO_LARGE) naming it."""
-        data, in_ptr, n, device = self._bgzf_in(data)
+        data, in_ptr, n, device = _in_buf(data, accept_bytes=True, null_if_empty=True)
         if out_cap is None and out is None:
             out_cap = bgzf_bound(n, block_bytes)
             if out_cap == 0:
                 raise FlateError(E_INVALID, "bgzf_write: block_bytes must be 0 or 1 .. 65535")
-        if device:
-            import torch
-            if out is None:
-                out = torch.empty(max(int(out_cap), 32), dtype=torch.uint8, device=data.device)
-            else:
-                _check_out(out, data, 0, "bgzf_write")
-            cap = out.numel() if out_cap is None else min(int(out_cap), out.numel())
-            out_ptr = out.data_ptr()
-        else:
-            if out is None:
-                out = np.empty(max(int(out_cap), 32), dtype=np.uint8)
-            else:
-                _check_out(out, data, 0, "bgzf_write")
-            cap = out.size if out_cap is None else min(int(out_cap), out.size)
-            out_ptr = out.ctypes.data
+        out, out_ptr, cap = _out_buf(out, data, out_cap, out_cap, 0, "bgzf_write", floor=32)
         bb = int(block_bytes) if block_bytes else BGZF_BLOCK_DEFAULT
         member_off = np.zeros((n + bb - 1) // max(bb, 1) + 1, dtype=np.uint64)
         out_len = C.c_uint64(0)
         self._check(self._L.flate_hip_bgzf_write(self._ctx, in_ptr, n, int(block_bytes), out_ptr, cap,
                                                  C.byref(out_len), member_off.ctypes.data,
                                                  self._flags(compat_go, False, device)))
-        res = (out, int(out_len.value)) if device else (bytes(out[:int(out_len.value)]),)
-        if index:
-            res = res + (member_off,)
-        return res if len(res) > 1 else res[0]
+        return _file_result(out, int(out_len.value), device, index, member_off)
 
     def bgzf_index(self, data, index_cap=None, query=False):
         """Where the members of a BGZF file start and where their output goes, found on the GPU from the file's bytes
@@ -475,29 +514,18 @@ class FlateEngine:
         in_off / the cumulative out_sizes.  rc -4 (FLATE_HIP_E_CORRUPT): no member could be read at err_off, behind
         n_members good ones.  query=True: only the counts (the arrays are None); index_cap: the arrays' size (default:
         what a query says is needed; too small: rc -2).  Other failures raise FlateError."""
-        data, in_ptr, n, device = self._bgzf_in(data)
-        flags = DEVICE_PTRS if device else 0
+        data, in_ptr, n, device = _in_buf(data, accept_bytes=True, null_if_empty=True)
         nm, ob, eof, eo = C.c_uint32(0), C.c_uint64(0), C.c_int(0), C.c_int64(-1)
 
         def call(cap, a, b):
-            rc = self._L.flate_hip_bgzf_index(self._ctx, in_ptr, n, cap, a, b, C.byref(nm), C.byref(ob), C.byref(eof),
-                                              C.byref(eo), flags)
-            if rc not in (0, E_CORRUPT, E_OUT_TOO_SMALL):
-                self._check(rc)
-            return rc
+            return self._tolerate(self._L.flate_hip_bgzf_index(
+                self._ctx, in_ptr, n, cap, a, b, C.byref(nm), C.byref(ob), C.byref(eof), C.byref(eo),
+                self._flags(False, False, device)), E_CORRUPT, E_OUT_TOO_SMALL)
 
-        if query or index_cap is None:
-            rc = call(0, None, None)
-            if query or rc != 0:
-                return BgzfIndex(rc, int(nm.value), int(ob.value), int(eof.value), int(eo.value), None, None)
-            index_cap = int(nm.value) + 1
-        moff = np.zeros(max(int(index_cap), 1), dtype=np.uint64)
-        ooff = np.zeros(max(int(index_cap), 1), dtype=np.uint64)
-        rc = call(int(index_cap), moff.ctypes.data, ooff.ctypes.data)
-        k = int(nm.value) + 1
-        ok = rc == 0
-        return BgzfIndex(rc, int(nm.value), int(ob.value), int(eof.value), int(eo.value),
-                         moff[:k] if ok else None, ooff[:k] if ok else None)
+        def result(rc, a, b):
+            return BgzfIndex(rc, int(nm.value), int(ob.value), int(eof.value), int(eo.value), a, b)
+
+        return _query_then_fill(call, lambda: int(nm.value), result, index_cap, query, prefix=False)
 
     def bgzf_read(self, data, out=None, out_cap=None):
         """A BGZF file -- bgzf_write's, bgzip's, htslib's -- back into its bytes by one call (flate_hip_bgzf_read):
@@ -508,25 +536,17 @@ class FlateEngine:
         ISIZE; -7 raw stream cut short; -2 more output than ISIZE) with its index and file offset, all other members
         delivered; -2 with out_len > capacity: out too small, nothing decoded.  out=None: sized by a query of the
         index first.  Other failures raise FlateError."""
-        data, in_ptr, n, device = self._bgzf_in(data)
-        if out is None:
-            need = self.bgzf_index(data, query=True).out_bytes
-            if device:
-                import torch
-                out = torch.empty(max(need, 16), dtype=torch.uint8, device=data.device)
-            else:
-                out = np.zeros(max(need, 16), dtype=np.uint8)
-        else:
-            _check_out(out, data, 0, "bgzf_read")
-        room = out.numel() if device else out.size
-        cap = room if out_cap is None else min(int(out_cap), room)
-        out_ptr = out.data_ptr() if device else out.ctypes.data
+        data, in_ptr, n, device = _in_buf(data, accept_bytes=True, null_if_empty=True)
         ol, nm, bad, eo, eof = C.c_uint64(0), C.c_uint32(0), C.c_uint32(0), C.c_int64(-1), C.c_int(0)
-        rc = self._L.flate_hip_bgzf_read(self._ctx, in_ptr, n, out_ptr, cap, C.byref(ol), C.byref(nm), C.byref(bad),
-                                         C.byref(eo), C.byref(eof), DEVICE_PTRS if device else 0)
-        if rc not in (0, E_OUT_TOO_SMALL, E_CORRUPT, E_UNEXPECTED_EOF):
-            self._check(rc)
-        return out, BgzfRead(rc, int(ol.value), int(nm.value), int(bad.value), int(eo.value), int(eof.value))
+
+        def call(out_ptr, cap):
+            rc = self._tolerate(self._L.flate_hip_bgzf_read(
+                self._ctx, in_ptr, n, out_ptr, cap, C.byref(ol), C.byref(nm), C.byref(bad), C.byref(eo), C.byref(eof),
+                self._flags(False, False, device)), *PER_STREAM)
+            return BgzfRead(rc, int(ol.value), int(nm.value), int(bad.value), int(eo.value), int(eof.value))
+
+        return _read_into(out, data, out_cap, "bgzf_read", call,
+                          lambda: (self.bgzf_index(data, query=True).out_bytes, None))
 
     def gzip_index(self, data, index_cap=None, query=False):
         """Where the members of a plain multi-member gzip file (cat a.gz b.gz, rotated logs, WARC records) start and
@@ -538,29 +558,18 @@ class FlateEngine:
         ones, whose index the arrays still hold.  n_candidates: the offsets decoded speculatively.  query=True: only the
         counts (the arrays are None); index_cap: the arrays' size (default: what a query says is needed; too small: rc
         -2, the arrays None).  Other failures raise FlateError."""
-        data, in_ptr, n, device = self._bgzf_in(data)
-        flags = DEVICE_PTRS if device else 0
+        data, in_ptr, n, device = _in_buf(data, accept_bytes=True, null_if_empty=True)
         nm, ob, nc, eo = C.c_uint32(0), C.c_uint64(0), C.c_uint32(0), C.c_int64(-1)
 
         def call(cap, a, b):
-            rc = self._L.flate_hip_gzip_index(self._ctx, in_ptr, n, cap, a, b, C.byref(nm), C.byref(ob), C.byref(nc),
-                                              C.byref(eo), flags)
-            if rc not in (0, E_CORRUPT, E_UNEXPECTED_EOF, E_TOO_LARGE, E_OUT_TOO_SMALL):
-                self._check(rc)
-            return rc
+            return self._tolerate(self._L.flate_hip_gzip_index(
+                self._ctx, in_ptr, n, cap, a, b, C.byref(nm), C.byref(ob), C.byref(nc), C.byref(eo),
+                self._flags(False, False, device)), *PER_CHAIN)
 
-        if query or index_cap is None:
-            rc = call(0, None, None)
-            if query:
-                return GzipIndex(rc, int(nm.value), int(ob.value), int(nc.value), int(eo.value), None, None)
-            index_cap = int(nm.value) + 1
-        moff = np.zeros(max(int(index_cap), 1), dtype=np.uint64)
-        ooff = np.zeros(max(int(index_cap), 1), dtype=np.uint64)
-        rc = call(int(index_cap), moff.ctypes.data, ooff.ctypes.data)
-        k = int(nm.value) + 1
-        fits = k <= int(index_cap)
-        return GzipIndex(rc, int(nm.value), int(ob.value), int(nc.value), int(eo.value),
-                         moff[:k] if fits else None, ooff[:k] if fits else None)
+        def result(rc, a, b):
+            return GzipIndex(rc, int(nm.value), int(ob.value), int(nc.value), int(eo.value), a, b)
+
+        return _query_then_fill(call, lambda: int(nm.value), result, index_cap, query, prefix=True)
 
     def inflate_one_index(self, data, wrap="gzip", index_cap=None, query=False):
         """Where the units of ONE long stream ("raw", "zlib" or "gzip": what gzip, zlib or pigz write, one member, many
@@ -575,33 +584,21 @@ class FlateEngine:
         decoded speculatively.  query=True: only the counts (the arrays are None); index_cap: the arrays' size (default: a
         unit per 256 bytes of input, and a second call only if the stream has more; given and too small: rc -2, the
         arrays None).  Other failures raise FlateError."""
-        data, in_ptr, n, device = self._bgzf_in(data)
-        flags = DEVICE_PTRS if device else 0
+        data, in_ptr, n, device = _in_buf(data, accept_bytes=True, null_if_empty=True)
         nu, ob, nc, st, eo = C.c_uint32(0), C.c_uint64(0), C.c_uint32(0), C.c_int32(0), C.c_int64(-1)
 
         def call(cap, a, b):
-            rc = self._L.flate_hip_inflate_one_index(self._ctx, in_ptr, n, WRAPS[wrap], cap, a, b, C.byref(nu),
-                                                     C.byref(ob), C.byref(nc), C.byref(st), C.byref(eo), flags)
-            if rc not in (0, E_CORRUPT, E_UNEXPECTED_EOF, E_TOO_LARGE, E_OUT_TOO_SMALL):
-                self._check(rc)
-            return rc
+            return self._tolerate(self._L.flate_hip_inflate_one_index(
+                self._ctx, in_ptr, n, WRAPS[wrap], cap, a, b, C.byref(nu), C.byref(ob), C.byref(nc), C.byref(st),
+                C.byref(eo), self._flags(False, False, device)), *PER_CHAIN)
 
         def result(rc, a, b):
             return OneIndex(rc, int(nu.value), int(ob.value), int(nc.value), int(st.value), int(eo.value), a, b)
 
-        if query:
-            return result(call(0, None, None), None, None)
         # no query first: the discovery is the whole cost of the call.  A unit per 256 bytes of input is more than
         # zlib writes at its smallest memLevel; a stream that has more takes a second call, sized from the count.
-        for cap in ([int(index_cap)] if index_cap is not None else [n // 256 + 64, None]):
-            cap = int(nu.value) + 1 if cap is None else cap
-            ubit = np.zeros(max(cap, 1), dtype=np.uint64)
-            ooff = np.zeros(max(cap, 1), dtype=np.uint64)
-            rc = call(cap, ubit.ctypes.data, ooff.ctypes.data)
-            k = int(nu.value) + 1
-            if k <= cap:
-                return result(rc, ubit[:k].copy(), ooff[:k].copy())
-        return result(rc, None, None)
+        return _query_then_fill(call, lambda: int(nu.value), result, index_cap, query, prefix=True,
+                                guess=n // 256 + 64)
 
     def inflate_one(self, data, wrap="gzip", out=None, out_cap=None):
         """ONE long stream ("raw", "zlib" or "gzip": one member, many blocks) back into its bytes, its blocks found and
@@ -612,22 +609,14 @@ class FlateEngine:
         "one_unit_max"; the bytes in front of an error are delivered.  rc -2 with out_len > capacity: out too small,
         nothing decoded.  out=None: sized from a gzip member's ISIZE, else (or if that was too little) by a query
         first.  Other failures raise FlateError."""
-        data, in_ptr, n, device = self._bgzf_in(data)
-        flags = DEVICE_PTRS if device else 0
+        data, in_ptr, n, device = _in_buf(data, accept_bytes=True, null_if_empty=True)
         ol, st, eo, nu, nc = C.c_uint64(0), C.c_int32(0), C.c_int64(-1), C.c_uint32(0), C.c_uint32(0)
 
         def call(out_ptr, cap):
-            rc = self._L.flate_hip_inflate_one(self._ctx, in_ptr, n, WRAPS[wrap], out_ptr, cap, C.byref(ol), C.byref(st),
-                                               C.byref(eo), C.byref(nu), C.byref(nc), flags)
-            if rc not in (0, E_OUT_TOO_SMALL, E_CORRUPT, E_UNEXPECTED_EOF, E_TOO_LARGE):
-                self._check(rc)
+            rc = self._tolerate(self._L.flate_hip_inflate_one(
+                self._ctx, in_ptr, n, WRAPS[wrap], out_ptr, cap, C.byref(ol), C.byref(st), C.byref(eo), C.byref(nu),
+                C.byref(nc), self._flags(False, False, device)), *PER_CHAIN)
             return OneRead(rc, int(ol.value), int(st.value), int(eo.value), int(nu.value), int(nc.value))
-
-        def room_for(size):
-            if device:
-                import torch
-                return torch.empty(max(size, 16), dtype=torch.uint8, device=data.device)
-            return np.zeros(max(size, 16), dtype=np.uint8)
 
         if out is None:
             # a gzip member says in its last four bytes what it inflates to (mod 2^32): room for that, and the one
@@ -635,25 +624,19 @@ class FlateEngine:
             # second call the query would have cost anyway.  (DEFLATE expands at most 1032 times.)
             hint = 0
             if wrap == "gzip" and n >= 18:
-                last = data[n - 4:n]
-                hint = int.from_bytes(bytes((last.cpu().numpy() if device else last).tobytes()), "little")
+                hint = int.from_bytes(_host_bytes(data[n - 4:n]), "little")
                 if hint > 1032 * n:
                     hint = 0
             if hint:
-                out = room_for(hint)
-                q = call(out.data_ptr() if device else out.ctypes.data, hint)
+                room, ptr, _ = _out_buf(None, data, hint, None, 0, "inflate_one")
+                q = call(ptr, hint)
                 if not (q.rc == E_OUT_TOO_SMALL and q.out_len > hint):
-                    return out, q
+                    return room, q
             else:
                 q = call(None, 0)
                 if q.rc != E_OUT_TOO_SMALL:  # nothing to deliver: an empty stream, or a verdict without bytes
-                    return (np.zeros(0, np.uint8) if not device else data[:0]), q
-            out = room_for(q.out_len)
-        else:
-            _check_out(out, data, 0, "inflate_one")
-        room = out.numel() if device else out.size
-        cap = room if out_cap is None else min(int(out_cap), room)
-        return out, call(out.data_ptr() if device else out.ctypes.data, cap)
+                    return _no_bytes(data), q
+        return _read_into(out, data, out_cap, "inflate_one", call, lambda: (q.out_len, None))
 
     def gzip_read(self, data, out=None, out_cap=None):
         """A plain multi-member gzip file back into its bytes by one call (flate_hip_gzip_read): member discovery,
@@ -663,25 +646,17 @@ class FlateEngine:
         otherwise the first failing member's status (-4 CRC or ISIZE, -2 more output than the slot) with its index and
         file offset, all other members delivered; -2 with out_len > capacity: out too small, nothing decoded.
         out=None: sized by a query of the index first.  Other failures raise FlateError."""
-        data, in_ptr, n, device = self._bgzf_in(data)
-        if out is None:
-            need = self.gzip_index(data, query=True).out_bytes
-            if device:
-                import torch
-                out = torch.empty(max(need, 16), dtype=torch.uint8, device=data.device)
-            else:
-                out = np.zeros(max(need, 16), dtype=np.uint8)
-        else:
-            _check_out(out, data, 0, "gzip_read")
-        room = out.numel() if device else out.size
-        cap = room if out_cap is None else min(int(out_cap), room)
-        out_ptr = out.data_ptr() if device else out.ctypes.data
+        data, in_ptr, n, device = _in_buf(data, accept_bytes=True, null_if_empty=True)
         ol, nm, bad, eo = C.c_uint64(0), C.c_uint32(0), C.c_uint32(0), C.c_int64(-1)
-        rc = self._L.flate_hip_gzip_read(self._ctx, in_ptr, n, out_ptr, cap, C.byref(ol), C.byref(nm), C.byref(bad),
-                                         C.byref(eo), DEVICE_PTRS if device else 0)
-        if rc not in (0, E_OUT_TOO_SMALL, E_CORRUPT, E_UNEXPECTED_EOF, E_TOO_LARGE):
-            self._check(rc)
-        return out, GzipRead(rc, int(ol.value), int(nm.value), int(bad.value), int(eo.value))
+
+        def call(out_ptr, cap):
+            rc = self._tolerate(self._L.flate_hip_gzip_read(
+                self._ctx, in_ptr, n, out_ptr, cap, C.byref(ol), C.byref(nm), C.byref(bad), C.byref(eo),
+                self._flags(False, False, device)), *PER_CHAIN)
+            return GzipRead(rc, int(ol.value), int(nm.value), int(bad.value), int(eo.value))
+
+        return _read_into(out, data, out_cap, "gzip_read", call,
+                          lambda: (self.gzip_index(data, query=True).out_bytes, None))
 
     def bgzf_read_ranges(self, data, begin, end, virtual=False, out=None, out_cap=None):
         """Random access into a BGZF file (flate_hip_bgzf_read_ranges): the bytes of the ranges [begin[r], end[r]) --
@@ -694,7 +669,7 @@ class FlateEngine:
         malformed chain; -2 with out_off[-1] > capacity: out too small, nothing decoded; else the first failing touched
         member's status with its index and file offset.  out=None: sized by the size query first.  begin[r] > end[r]
         and other refusals raise FlateError."""
-        data, in_ptr, n, device = self._bgzf_in(data)
+        data, in_ptr, n, device = _in_buf(data, accept_bytes=True, null_if_empty=True)
         begin = np.ascontiguousarray(begin, dtype=np.uint64)
         end = np.ascontiguousarray(end, dtype=np.uint64)
         if begin.ndim != 1 or begin.shape != end.shape:
@@ -703,38 +678,22 @@ class FlateEngine:
         out_off = np.zeros(nr + 1, dtype=np.uint64)
         status = np.zeros(max(nr, 1), dtype=np.int32)
         nm, nd, bad, eo = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0), C.c_int64(-1)
-        flags = DEVICE_PTRS if device else 0
 
         def call(out_ptr, cap):
             rc = self._L.flate_hip_bgzf_read_ranges(self._ctx, in_ptr, n, 1 if virtual else 0, begin.ctypes.data,
                                                     end.ctypes.data, nr, out_ptr, cap, out_off.ctypes.data,
                                                     status.ctypes.data, C.byref(nm), C.byref(nd), C.byref(bad),
-                                                    C.byref(eo), flags)
-            if rc not in (0, E_OUT_TOO_SMALL, E_CORRUPT, E_UNEXPECTED_EOF) and \
-                    not (rc == E_INVALID and nr and (status[:nr] == E_INVALID).any()):
-                self._check(rc)
-            return rc
-
-        def result(rc):
+                                                    C.byref(eo), self._flags(False, False, device))
+            # (E_INVALID is a verdict only where some range carries it; otherwise the call itself was refused)
+            invalid_range = rc == E_INVALID and nr and (status[:nr] == E_INVALID).any()
+            self._tolerate(rc, *PER_STREAM + ((E_INVALID,) if invalid_range else ()))
             return BgzfRanges(rc, out_off, status[:nr], int(nm.value), int(nd.value), int(bad.value), int(eo.value))
 
-        if out is None:
-            rc = call(None, 0)  # the size query: nothing is decoded
-            need = int(out_off[nr])
-            if rc != E_OUT_TOO_SMALL:  # nothing to deliver, or a malformed chain
-                need = 0
-            if device:
-                import torch
-                out = torch.empty(max(need, 16), dtype=torch.uint8, device=data.device)
-            else:
-                out = np.zeros(max(need, 16), dtype=np.uint8)
-            if rc != E_OUT_TOO_SMALL:
-                return out, result(rc)
-        else:
-            _check_out(out, data, 0, "bgzf_read_ranges")
-        room = out.numel() if device else out.size
-        cap = room if out_cap is None else min(int(out_cap), room)
-        return out, result(call(out.data_ptr() if device else out.ctypes.data, cap))
+        def size():  # the size query: nothing is decoded
+            q = call(None, 0)
+            return (int(out_off[nr]), None) if q.rc == E_OUT_TOO_SMALL else (0, q)  # else: nothing to deliver, or a malformed chain
+
+        return _read_into(out, data, out_cap, "bgzf_read_ranges", call, size)
 
     def zip_write(self, data, in_off, names, compat_go=False, out=None, out_cap=None, index=False):
         """The entries data[in_off[i]:in_off[i + 1]], named names[i] (str or UTF-8 bytes), as ONE ZIP archive that
@@ -743,9 +702,8 @@ class FlateEngine:
         numpy uint8 / bytes (returns the archive as bytes) or a torch uint8 CUDA tensor (returns (out, out_len), the
         archive in out[:out_len] on the device).  index=True: entry_off (numpy uint64[n + 1], the local headers and
         the directory's offset) is appended to the result."""
-        data, in_ptr, _, device = self._bgzf_in(data)
-        in_off = np.ascontiguousarray(in_off, dtype=np.uint64)
-        n = in_off.size - 1
+        data, in_ptr, _, device = _in_buf(data, accept_bytes=True, null_if_empty=True)
+        in_off, n = _offsets(in_off)
         if n != len(names):
             raise FlateError(E_INVALID, "zip_write: one name per entry")
         name_bytes, name_off = _zip_names(names)
@@ -753,30 +711,20 @@ class FlateEngine:
             out_cap = int(self._L.flate_hip_zip_bound(in_off.ctypes.data, n, name_off.ctypes.data))
             if out_cap == 0:
                 raise FlateError(E_INVALID, "zip_write: a name must have 1 .. 65535 bytes and in_off must not decrease")
-        if device:
-            import torch
-            if out is None:
-                out = torch.empty(max(int(out_cap), 32), dtype=torch.uint8, device=data.device)
-            else:
-                _check_out(out, data, 0, "zip_write")
-            cap = out.numel() if out_cap is None else min(int(out_cap), out.numel())
-            out_ptr = out.data_ptr()
-        else:
-            if out is None:
-                out = np.empty(max(int(out_cap), 32), dtype=np.uint8)
-            else:
-                _check_out(out, data, 0, "zip_write")
-            cap = out.size if out_cap is None else min(int(out_cap), out.size)
-            out_ptr = out.ctypes.data
+        out, out_ptr, cap = _out_buf(out, data, out_cap, out_cap, 0, "zip_write", floor=32)
         entry_off = np.zeros(n + 1, dtype=np.uint64)
         out_len = C.c_uint64(0)
         self._check(self._L.flate_hip_zip_write(self._ctx, in_ptr, in_off.ctypes.data, n, name_bytes.ctypes.data,
                                                 name_off.ctypes.data, out_ptr, cap, C.byref(out_len),
                                                 entry_off.ctypes.data, self._flags(compat_go, False, device)))
-        res = (out, int(out_len.value)) if device else (bytes(out[:int(out_len.value)]),)
-        if index:
-            res = res + (entry_off,)
-        return res if len(res) > 1 else res[0]
+        return _file_result(out, int(out_len.value), device, index, entry_off)
+
+    def _zip_count(self, in_ptr, n, flags):
+        """The counting call of flate_hip_zip_index -> (rc: 0 or E_CORRUPT, n_entries, out_bytes, err_off)."""
+        ne, ob, eo = C.c_uint32(0), C.c_uint64(0), C.c_int64(-1)
+        rc = self._tolerate(self._L.flate_hip_zip_index(self._ctx, in_ptr, n, 0, None, None, C.byref(ne), C.byref(ob),
+                                                        C.byref(eo), flags), E_CORRUPT)
+        return rc, int(ne.value), int(ob.value), int(eo.value)
 
     def zip_index(self, data):
         """The entries of a ZIP archive, found on the GPU from the archive's bytes (flate_hip_zip_index) ->
@@ -786,17 +734,14 @@ class FlateEngine:
         bytes where a name is not UTF-8).  rc -4 (FLATE_HIP_E_CORRUPT): a malformed archive at err_off behind
         n_entries good records; the arrays are None.  data: numpy uint8 / bytes, or a torch uint8 CUDA tensor.
         Other failures raise FlateError."""
-        data, in_ptr, n, device = self._bgzf_in(data)
-        flags = DEVICE_PTRS if device else 0
-        ne, ob, eo = C.c_uint32(0), C.c_uint64(0), C.c_int64(-1)
-        rc = self._L.flate_hip_zip_index(self._ctx, in_ptr, n, 0, None, None, C.byref(ne), C.byref(ob), C.byref(eo), flags)
-        if rc not in (0, E_CORRUPT):
-            self._check(rc)
+        data, in_ptr, n, device = _in_buf(data, accept_bytes=True, null_if_empty=True)
+        flags = self._flags(False, False, device)
+        rc, cnt, _, err = self._zip_count(in_ptr, n, flags)
         if rc != 0:
-            return ZipIndex(rc, int(ne.value), 0, int(eo.value), None, None, None)
-        cnt = int(ne.value)
+            return ZipIndex(rc, cnt, 0, err, None, None, None)
         entries = np.zeros(max(cnt, 1), dtype=ZIP_ENTRY)
         out_off = np.zeros(cnt + 1, dtype=np.uint64)
+        ne, ob, eo = C.c_uint32(0), C.c_uint64(0), C.c_int64(-1)
         self._check(self._L.flate_hip_zip_index(self._ctx, in_ptr, n, cnt, entries.ctypes.data, out_off.ctypes.data,
                                                 C.byref(ne), C.byref(ob), C.byref(eo), flags))
         entries = entries[:cnt]
@@ -804,7 +749,7 @@ class FlateEngine:
         if cnt:
             lo = int(entries["name_off"].min())
             hi = int((entries["name_off"] + entries["name_len"]).max())
-            blob = data[lo:hi].cpu().numpy().tobytes() if device else data[lo:hi].tobytes()
+            blob = _host_bytes(data[lo:hi])
             for e in entries:
                 raw = blob[int(e["name_off"]) - lo:int(e["name_off"]) - lo + int(e["name_len"])]
                 try:
@@ -823,8 +768,8 @@ class FlateEngine:
         with out_off[-1] > capacity: out too small, nothing decoded; otherwise the first non-zero entry status, all other
         entries delivered.  out=None: sized by the size query first.  A name that is not in the archive raises KeyError;
         other failures raise FlateError."""
-        data, in_ptr, n, device = self._bgzf_in(data)
-        flags = DEVICE_PTRS if device else 0
+        data, in_ptr, n, device = _in_buf(data, accept_bytes=True, null_if_empty=True)
+        flags = self._flags(False, False, device)
         sel = None
         if select is not None:
             select = list(select)
@@ -850,47 +795,37 @@ class FlateEngine:
             sel = np.ascontiguousarray(select, dtype=np.uint32)
             ns = sel.size
         else:
-            ne, ob, eo = C.c_uint32(0), C.c_uint64(0), C.c_int64(-1)
-            rc = self._L.flate_hip_zip_index(self._ctx, in_ptr, n, 0, None, None, C.byref(ne), C.byref(ob), C.byref(eo), flags)
-            if rc not in (0, E_CORRUPT):
-                self._check(rc)
+            rc, ns, _, err = self._zip_count(in_ptr, n, flags)
             if rc != 0:
-                return out, ZipRead(rc, None, None, None, None, int(ne.value), int(eo.value))
-            ns = int(ne.value)
+                return out, ZipRead(rc, None, None, None, None, ns, err)
         out_off = np.zeros(ns + 1, dtype=np.uint64)
-        out_len = np.zeros(max(ns, 1), dtype=np.uint64)
-        status = np.zeros(max(ns, 1), dtype=np.int32)
-        err_off = np.full(max(ns, 1), -1, dtype=np.int64)
+        out_len, status, err_off = _stream_results(ns)
         ne, aeo = C.c_uint32(0), C.c_int64(-1)
-        statuses = (0, E_OUT_TOO_SMALL, E_CORRUPT, E_UNEXPECTED_EOF, E_TOO_LARGE, E_UNSUPPORTED)
 
         def call(out_ptr, cap):
-            rc = self._L.flate_hip_zip_read(self._ctx, in_ptr, n, sel.ctypes.data if sel is not None else None,
-                                            ns if sel is not None else 0, ns, out_ptr, cap, out_off.ctypes.data,
-                                            out_len.ctypes.data, status.ctypes.data, err_off.ctypes.data, C.byref(ne),
-                                            C.byref(aeo), flags)
-            if rc not in statuses:
-                self._check(rc)
-            return rc
-
-        def result(rc):
+            rc = self._tolerate(self._L.flate_hip_zip_read(
+                self._ctx, in_ptr, n, sel.ctypes.data if sel is not None else None, ns if sel is not None else 0, ns,
+                out_ptr, cap, out_off.ctypes.data, out_len.ctypes.data, status.ctypes.data, err_off.ctypes.data,
+                C.byref(ne), C.byref(aeo), flags), *PER_CHAIN, E_UNSUPPORTED)
             return ZipRead(rc, out_off, out_len[:ns], status[:ns], err_off[:ns], int(ne.value), int(aeo.value))
 
-        if out is None:
-            rc = call(None, 0)  # the size query: nothing is decoded
-            need = int(out_off[ns]) if rc == E_OUT_TOO_SMALL else 0
-            if device:
-                import torch
-                out = torch.empty(max(need, 16), dtype=torch.uint8, device=data.device)
-            else:
-                out = np.zeros(max(need, 16), dtype=np.uint8)
-            if rc != E_OUT_TOO_SMALL:
-                return out, result(rc)
+        def size():  # the size query: nothing is decoded
+            q = call(None, 0)
+            return (int(out_off[ns]), None) if q.rc == E_OUT_TOO_SMALL else (0, q)
+
+        return _read_into(out, data, out_cap, "zip_read", call, size)
+
+    def _inflate_call(self, in_ptr, in_off, n, zdicts, dict_of, device, out_ptr, off_ptr, results, flags, allowed):
+        """flate_hip_inflate_batch, or with zdicts flate_hip_inflate_batch_dict, into results = (out_len, status,
+        err_off)."""
+        tail = (out_ptr, off_ptr) + tuple(r.ctypes.data for r in results) + (flags | self._flags(False, False, device),)
+        if zdicts is None:
+            rc = self._L.flate_hip_inflate_batch(self._ctx, in_ptr, in_off.ctypes.data, n, *tail)
         else:
-            _check_out(out, data, 0, "zip_read")
-        room = out.numel() if device else out.size
-        cap = room if out_cap is None else min(int(out_cap), room)
-        return out, result(call(out.data_ptr() if device else out.ctypes.data, cap))
+            dk = _DictArgs(zdicts, dict_of, n, device)
+            rc = self._L.flate_hip_inflate_batch_dict(self._ctx, in_ptr, in_off.ctypes.data, n, dk.ptr, dk.off_ptr,
+                                                      dk.n_dicts, dk.of_ptr, *tail)
+        self._tolerate(rc, *allowed)
 
     def inflate_batch(self, data, in_off, out_sizes, out=None, check=True, zdicts=None, dict_of=None):
         """Decompress independent DEFLATE streams (&Reader::new + read to EOF each).
@@ -898,70 +833,24 @@ class FlateEngine:
         zdicts: preset dictionaries (&Reader::new_dict, flate_hip_inflate_batch_dict) -- one bytes-like object or
         a list of them; dict_of[i] = the dictionary of stream i or NO_DICT (None: every stream uses the first).
         Returns (out, out_off, out_len, status, err_off); with check=True a failing stream raises."""
-        in_off = np.ascontiguousarray(in_off, dtype=np.uint64)
-        n = in_off.size - 1
-        out_off = np.zeros(n + 1, dtype=np.uint64)
-        np.cumsum(np.asarray(out_sizes, dtype=np.uint64), out=out_off[1:])
-        out_len = np.zeros(n, dtype=np.uint64)
-        status = np.zeros(n, dtype=np.int32)
-        err_off = np.full(n, -1, dtype=np.int64)
-        device = _is_torch(data)
-        total = max(int(out_off[-1]), 16)
-        if device:
-            import torch
-            assert data.dtype == torch.uint8 and data.is_cuda and data.is_contiguous()
-            if out is None:
-                out = torch.empty(total, dtype=torch.uint8, device=data.device)
-            else:
-                _check_out(out, data, int(out_off[-1]), "inflate")
-            in_ptr, out_ptr = data.data_ptr(), out.data_ptr()
-        else:
-            data = np.ascontiguousarray(data, dtype=np.uint8)
-            if out is None:
-                out = np.zeros(total, dtype=np.uint8)
-            else:
-                _check_out(out, data, int(out_off[-1]), "inflate")
-            in_ptr, out_ptr = data.ctypes.data, out.ctypes.data
-        if zdicts is None:
-            rc = self._L.flate_hip_inflate_batch(self._ctx, in_ptr, in_off.ctypes.data, n, out_ptr,
-                                                 out_off.ctypes.data, out_len.ctypes.data,
-                                                 status.ctypes.data, err_off.ctypes.data,
-                                                 DEVICE_PTRS if device else 0)
-        else:
-            dk = _DictArgs(zdicts, dict_of, n, device)
-            rc = self._L.flate_hip_inflate_batch_dict(self._ctx, in_ptr, in_off.ctypes.data, n, dk.ptr, dk.off_ptr,
-                                                      dk.n_dicts, dk.of_ptr, out_ptr, out_off.ctypes.data,
-                                                      out_len.ctypes.data, status.ctypes.data, err_off.ctypes.data,
-                                                      DEVICE_PTRS if device else 0)
-        if rc != 0 and (check or rc not in (E_OUT_TOO_SMALL, E_CORRUPT, E_UNEXPECTED_EOF)):
-            self._check(rc)
-        return out, out_off, out_len, status, err_off
+        in_off, n = _offsets(in_off)
+        out_off = _slots(out_sizes, n)
+        results = _stream_results(n, pad=False)  # (this call alone returns its tables unpadded and whole)
+        data, in_ptr, _, device = _in_buf(data)
+        out, out_ptr, _ = _out_buf(out, data, out_off[-1], None, int(out_off[-1]), "inflate")
+        self._inflate_call(in_ptr, in_off, n, zdicts, dict_of, device, out_ptr, out_off.ctypes.data, results, 0,
+                           () if check else PER_STREAM)
+        return (out, out_off) + results
 
     def inflate_sizes(self, data, in_off, zdicts=None, dict_of=None):
         """Decode without storing (FLATE_HIP_SIZE_ONLY): returns (out_len, status, err_off) -- the size
         every stream inflates to (up to its error, if any).  Host or device input; zdicts / dict_of as in
         inflate_batch."""
-        in_off = np.ascontiguousarray(in_off, dtype=np.uint64)
-        n = in_off.size - 1
-        out_len = np.zeros(max(n, 1), dtype=np.uint64)
-        status = np.zeros(max(n, 1), dtype=np.int32)
-        err_off = np.full(max(n, 1), -1, dtype=np.int64)
-        device = _is_torch(data)
-        if not device:
-            data = np.ascontiguousarray(data, dtype=np.uint8)
-        in_ptr = data.data_ptr() if device else data.ctypes.data
-        flags = SIZE_ONLY | (DEVICE_PTRS if device else 0)
-        if zdicts is None:
-            rc = self._L.flate_hip_inflate_batch(self._ctx, in_ptr, in_off.ctypes.data, n, None, None,
-                                                 out_len.ctypes.data, status.ctypes.data, err_off.ctypes.data, flags)
-        else:
-            dk = _DictArgs(zdicts, dict_of, n, device)
-            rc = self._L.flate_hip_inflate_batch_dict(self._ctx, in_ptr, in_off.ctypes.data, n, dk.ptr, dk.off_ptr,
-                                                      dk.n_dicts, dk.of_ptr, None, None, out_len.ctypes.data,
-                                                      status.ctypes.data, err_off.ctypes.data, flags)
-        if rc != 0 and rc not in (E_OUT_TOO_SMALL, E_CORRUPT, E_UNEXPECTED_EOF):
-            self._check(rc)
-        return out_len[:n], status[:n], err_off[:n]
+        in_off, n = _offsets(in_off)
+        results = _stream_results(n)
+        data, in_ptr, _, device = _in_buf(data, lax=True)
+        self._inflate_call(in_ptr, in_off, n, zdicts, dict_of, device, None, None, results, SIZE_ONLY, PER_STREAM)
+        return tuple(r[:n] for r in results)
 
     def open_inflate_stream(self, zdict=None):
         """One long DEFLATE stream decoded in pieces (see StreamReader); zdict: a preset dictionary
@@ -976,66 +865,28 @@ class FlateEngine:
         """Compress the streams as deflate_batch does, but into ONE legal DEFLATE stream that
         inflates to the concatenation of the inputs.
         Returns (out, out_len, bit_off[N+1]): bit_off[i] = bit position of stream i's first block."""
-        in_off = np.ascontiguousarray(in_off, dtype=np.uint64)
-        n = in_off.size - 1
-        lens = in_off[1:] - in_off[:-1]
-        cap = int(sum(deflate_bound(int(l)) * int(c) for l, c in zip(*np.unique(lens, return_counts=True)))) + 16
+        in_off, n = _offsets(in_off)
         bit_off = np.zeros(n + 1, dtype=np.uint64)
         out_len = C.c_uint64(0)
-        device = _is_torch(data)
-        if device:
-            import torch
-            assert data.dtype == torch.uint8 and data.is_cuda and data.is_contiguous()
-            if out is None:
-                out = torch.empty(cap, dtype=torch.uint8, device=data.device)
-            else:
-                _check_out(out, data, 8, "deflate_spliced")
-            in_ptr, out_ptr, out_cap = data.data_ptr(), out.data_ptr(), out.numel()
-        else:
-            data = np.ascontiguousarray(data, dtype=np.uint8)
-            if out is None:
-                out = np.zeros(cap, dtype=np.uint8)
-            else:
-                _check_out(out, data, 8, "deflate_spliced")
-            in_ptr, out_ptr, out_cap = data.ctypes.data, out.ctypes.data, out.size
+        data, in_ptr, _, device = _in_buf(data)
+        out, out_ptr, cap = _out_buf(out, data, _deflate_room(in_off) + 16, None, 8, "deflate_spliced")
         self._check(self._L.flate_hip_deflate_fast_spliced(
-            self._ctx, in_ptr, in_off.ctypes.data, n, out_ptr, out_cap, C.byref(out_len),
+            self._ctx, in_ptr, in_off.ctypes.data, n, out_ptr, cap, C.byref(out_len),
             bit_off.ctypes.data, self._flags(compat_go, False, device)))
         return out, int(out_len.value), bit_off
 
     def inflate_spliced(self, data, nbytes, bit_off, out_sizes, out=None, check=True):
         """Decompress ONE spliced DEFLATE stream data[:nbytes] in parallel from its index:
         piece i starts at bit bit_off[i].  Returns (out, out_off, out_len, status, err_off)."""
-        bit_off = np.ascontiguousarray(bit_off, dtype=np.uint64)
-        n = bit_off.size - 1
-        out_off = np.zeros(n + 1, dtype=np.uint64)
-        np.cumsum(np.asarray(out_sizes, dtype=np.uint64), out=out_off[1:])
-        out_len = np.zeros(max(n, 1), dtype=np.uint64)
-        status = np.zeros(max(n, 1), dtype=np.int32)
-        err_off = np.full(max(n, 1), -1, dtype=np.int64)
-        device = _is_torch(data)
-        total = max(int(out_off[-1]), 16)
-        if device:
-            import torch
-            assert data.dtype == torch.uint8 and data.is_cuda and data.is_contiguous()
-            if out is None:
-                out = torch.empty(total, dtype=torch.uint8, device=data.device)
-            else:
-                _check_out(out, data, int(out_off[-1]), "inflate")
-            in_ptr, out_ptr = data.data_ptr(), out.data_ptr()
-        else:
-            data = np.ascontiguousarray(data, dtype=np.uint8)
-            if out is None:
-                out = np.zeros(total, dtype=np.uint8)
-            else:
-                _check_out(out, data, int(out_off[-1]), "inflate")
-            in_ptr, out_ptr = data.ctypes.data, out.ctypes.data
-        rc = self._L.flate_hip_inflate_spliced(self._ctx, in_ptr, int(nbytes), bit_off.ctypes.data, n,
-                                               out_ptr, out_off.ctypes.data, out_len.ctypes.data,
-                                               status.ctypes.data, err_off.ctypes.data,
-                                               DEVICE_PTRS if device else 0)
-        if rc != 0 and (check or rc not in (E_OUT_TOO_SMALL, E_CORRUPT, E_UNEXPECTED_EOF)):
-            self._check(rc)
+        bit_off, n = _offsets(bit_off)
+        out_off = _slots(out_sizes, n)
+        out_len, status, err_off = _stream_results(n)
+        data, in_ptr, _, device = _in_buf(data)
+        out, out_ptr, _ = _out_buf(out, data, out_off[-1], None, int(out_off[-1]), "inflate")
+        self._tolerate(self._L.flate_hip_inflate_spliced(
+            self._ctx, in_ptr, int(nbytes), bit_off.ctypes.data, n, out_ptr, out_off.ctypes.data, out_len.ctypes.data,
+            status.ctypes.data, err_off.ctypes.data, self._flags(False, False, device)),
+            0, *(() if check else PER_STREAM))
         return out, out_off, out_len[:n], status[:n], err_off[:n]
 
     def inflate_spliced_framed(self, data, nbytes, wrap, bit_off, out_sizes, out=None, check=True):
@@ -1049,61 +900,38 @@ class FlateEngine:
         Returns (out, out_off, out_len, status, err_off, member_status); member_status is the first non-zero piece
         status, or -4 for a bad header (every piece -4) or a checksum / ISIZE that does not match what the pieces
         produced (every piece 0), else 0.  With check=True a non-zero member status raises FlateError."""
-        bit_off = np.ascontiguousarray(bit_off, dtype=np.uint64)
+        bit_off, n = _offsets(bit_off)
         out_sizes = np.asarray(out_sizes, dtype=np.uint64)
-        if bit_off.size == 1:
-            bit_off = np.array([bit_off[0], bit_off[0]], dtype=np.uint64)
+        if n == 0:
+            bit_off, n = np.array([bit_off[0], bit_off[0]], dtype=np.uint64), 1
             out_sizes = np.zeros(1, dtype=np.uint64)
-        n = bit_off.size - 1
-        w = _wrap_code(wrap)
-        out_off = np.zeros(n + 1, dtype=np.uint64)
-        np.cumsum(out_sizes, out=out_off[1:])
-        out_len = np.zeros(max(n, 1), dtype=np.uint64)
-        status = np.zeros(max(n, 1), dtype=np.int32)
-        err_off = np.full(max(n, 1), -1, dtype=np.int64)
+        out_off = _slots(out_sizes, n)
+        out_len, status, err_off = _stream_results(n)
         member_status, member_err = C.c_int32(0), C.c_int64(-1)
-        device = _is_torch(data)
-        total = max(int(out_off[-1]), 16)
-        if device:
-            import torch
-            assert data.dtype == torch.uint8 and data.is_cuda and data.is_contiguous()
-            if out is None:
-                out = torch.empty(total, dtype=torch.uint8, device=data.device)
-            else:
-                _check_out(out, data, int(out_off[-1]), "inflate_spliced_framed")
-            in_ptr, out_ptr = data.data_ptr(), out.data_ptr()
-        else:
-            data = np.ascontiguousarray(data, dtype=np.uint8)
-            if out is None:
-                out = np.zeros(total, dtype=np.uint8)
-            else:
-                _check_out(out, data, int(out_off[-1]), "inflate_spliced_framed")
-            in_ptr, out_ptr = data.ctypes.data, out.ctypes.data
-        rc = self._L.flate_hip_inflate_spliced_framed(
-            self._ctx, in_ptr, int(nbytes), w, bit_off.ctypes.data, n, out_ptr, out_off.ctypes.data,
+        data, in_ptr, _, device = _in_buf(data)
+        out, out_ptr, _ = _out_buf(out, data, out_off[-1], None, int(out_off[-1]), "inflate_spliced_framed")
+        self._tolerate(self._L.flate_hip_inflate_spliced_framed(
+            self._ctx, in_ptr, int(nbytes), _wrap_code(wrap), bit_off.ctypes.data, n, out_ptr, out_off.ctypes.data,
             out_len.ctypes.data, status.ctypes.data, err_off.ctypes.data, C.byref(member_status),
-            C.byref(member_err), DEVICE_PTRS if device else 0)
-        if rc != 0 and (check or rc not in (E_OUT_TOO_SMALL, E_CORRUPT, E_UNEXPECTED_EOF)):
-            self._check(rc)
+            C.byref(member_err), self._flags(False, False, device)), *(() if check else PER_STREAM))
         self.last_member_err_off = int(member_err.value)
         return out, out_off, out_len[:n], status[:n], err_off[:n], int(member_status.value)
 
     def lz77_matches(self, data, in_off, compat_go=False, lz_serial=False):
         """Match finder only.  Returns a list over LZ77 chunks (stream order) of
         (pos uint32[], tok uint32[]) and the per-stream chunk counts."""
-        in_off = np.ascontiguousarray(in_off, dtype=np.uint64)
-        n = in_off.size - 1
-        data = np.ascontiguousarray(data, dtype=np.uint8)
+        in_off, n = _offsets(in_off)
+        data, in_ptr, _, _ = _in_buf(np.asarray(data))
         n_chunks, cap = C.c_uint32(0), C.c_uint64(0)
         flags = self._flags(compat_go, lz_serial, False)
-        self._check(self._L.flate_hip_lz77_matches(self._ctx, data.ctypes.data, in_off.ctypes.data, n,
+        self._check(self._L.flate_hip_lz77_matches(self._ctx, in_ptr, in_off.ctypes.data, n,
                                                    flags, C.byref(n_chunks), C.byref(cap),
                                                    None, None, None))
         nc = n_chunks.value
         nmatch = np.zeros(max(nc, 1), dtype=np.uint32)
         rec_off = np.zeros(nc + 1, dtype=np.uint64)
         recs = np.zeros((max(cap.value, 1), 2), dtype=np.uint32)
-        self._check(self._L.flate_hip_lz77_matches(self._ctx, data.ctypes.data, in_off.ctypes.data, n,
+        self._check(self._L.flate_hip_lz77_matches(self._ctx, in_ptr, in_off.ctypes.data, n,
                                                    flags, C.byref(n_chunks), C.byref(cap),
                                                    nmatch.ctypes.data, rec_off.ctypes.data,
                                                    recs.ctypes.data))
@@ -1112,6 +940,15 @@ class FlateEngine:
             r = recs[int(rec_off[c]):int(rec_off[c]) + int(nmatch[c])]
             out.append((r[:, 0].copy(), r[:, 1].copy()))
         return out
+
+
+def _piece(x):
+    """(a piece of a stream as contiguous numpy uint8 -- bytes-like or an array, None = nothing; its pointer, NULL for
+    no bytes; its size)."""
+    if not isinstance(x, np.ndarray):
+        x = np.frombuffer(bytes(x if x is not None else b""), dtype=np.uint8)
+    x, ptr, nbytes, _ = _in_buf(x, null_if_empty=True)
+    return x, ptr, nbytes
 
 
 class StreamWriter:
@@ -1126,13 +963,11 @@ class StreamWriter:
         eng._check(self._L.flate_hip_stream_open(eng._ctx, COMPAT_GO if compat_go else 0, C.byref(self._st)))
 
     def _write(self, piece, final):
-        piece = np.ascontiguousarray(piece, dtype=np.uint8)
-        cap = int(self._L.flate_hip_stream_bound(piece.size))
-        out = np.empty(cap, dtype=np.uint8)
+        piece, ptr, nbytes = _piece(piece)
+        out, out_ptr, cap = _out_buf(None, piece, self._L.flate_hip_stream_bound(nbytes), None, 0, "write", floor=0)
         n = C.c_uint64(0)
-        rc = self._L.flate_hip_stream_write(self._st, piece.ctypes.data if piece.size else None, piece.size,
-                                            1 if final else 0, out.ctypes.data, cap, C.byref(n))
-        self._eng._check(rc)
+        self._eng._check(self._L.flate_hip_stream_write(self._st, ptr, nbytes, 1 if final else 0, out_ptr, cap,
+                                                        C.byref(n)))
         return out[:int(n.value)]
 
     def write(self, piece):
@@ -1141,7 +976,6 @@ class StreamWriter:
 
     def close(self, tail=b""):
         """The rest of the stream (any length) and Writer::close.  Returns the last output bytes."""
-        tail = np.frombuffer(bytes(tail), dtype=np.uint8) if not isinstance(tail, np.ndarray) else tail
         out = self._write(tail, True)
         self.free()
         return out
@@ -1177,24 +1011,20 @@ class StreamReader:
     def reset(self, zdict=None):
         """Decompressor::reset(r, dict) (inflate.mbt:862-884): a fresh decoder on the same handle, with the
         last 32768 bytes of zdict as history that has already been read."""
-        d = np.ascontiguousarray(np.frombuffer(bytes(zdict), dtype=np.uint8) if zdict is not None and not isinstance(zdict, np.ndarray)
-                                 else (zdict if zdict is not None else np.zeros(0, np.uint8)), dtype=np.uint8)
-        self._eng._check(self._L.flate_hip_inflate_stream_reset(self._st, d.ctypes.data if d.size else None, d.size))
+        _, ptr, nbytes = _piece(zdict)
+        self._eng._check(self._L.flate_hip_inflate_stream_reset(self._st, ptr, nbytes))
         self._rest = np.zeros(0, dtype=np.uint8)
         self.err_off = -1
         self.total_in = 0
 
     def feed(self, piece, final=False, room=1 << 20):
-        piece = np.ascontiguousarray(np.frombuffer(bytes(piece), dtype=np.uint8) if not isinstance(piece, np.ndarray) else piece,
-                                     dtype=np.uint8)
-        buf = np.concatenate([self._rest, piece]) if self._rest.size else piece
-        out = np.empty(max(int(room), 1), dtype=np.uint8)
+        piece, _, _ = _piece(piece)
+        buf, ptr, nbytes = _piece(np.concatenate([self._rest, piece]) if self._rest.size else piece)
+        out, out_ptr, cap = _out_buf(None, buf, room, room, 0, "feed", floor=1)
         used, n, eo = C.c_uint64(0), C.c_uint64(0), C.c_int64(-1)
-        rc = self._L.flate_hip_inflate_stream_read(self._st, buf.ctypes.data if buf.size else None, buf.size,
-                                                   1 if final else 0, out.ctypes.data, int(room), C.byref(used),
-                                                   C.byref(n), C.byref(eo))
-        if rc not in (0, 1, E_CORRUPT, E_UNEXPECTED_EOF):
-            self._eng._check(rc)
+        rc = self._eng._tolerate(self._L.flate_hip_inflate_stream_read(
+            self._st, ptr, nbytes, 1 if final else 0, out_ptr, cap, C.byref(used), C.byref(n), C.byref(eo)),
+            1, E_CORRUPT, E_UNEXPECTED_EOF)  # (1: the end of the stream)
         self._rest = buf[int(used.value):].copy()
         self.total_in += int(used.value)
         self.err_off = int(eo.value)
@@ -1214,19 +1044,6 @@ class StreamReader:
             self.free()
         except Exception:
             pass
-
-
-CHECKSUM_ADLER32, CHECKSUM_CRC32 = 1, 2
-WRAP_RAW, WRAP_ZLIB, WRAP_GZIP = 0, 1, 2  # FLATE_HIP_WRAP_*
-WRAPS = {"raw": WRAP_RAW, "zlib": WRAP_ZLIB, "gzip": WRAP_GZIP}
-
-
-def _wrap_code(wrap):
-    """FLATE_HIP_WRAP_* of the framed methods' wrap argument ("zlib", "raw"; anything else has always meant gzip)."""
-    return WRAPS.get(wrap, WRAP_GZIP)
-
-ZLIB_HEADER = bytes([0x78, 0x01])  # CM = 8, CINFO = 7 (32 KiB window), FLEVEL = 0 (fastest), FCHECK (RFC 1950 2.2)
-GZIP_HEADER = bytes([0x1f, 0x8b, 8, 0, 0, 0, 0, 0, 4, 255])  # no name / time, XFL = 4 (fastest), OS unknown (RFC 1952 2.3)
 
 
 def _gzip_isizes(data, in_off):
@@ -1256,9 +1073,14 @@ def _dict_list(zdicts):
 
 class _DictArgs:
     """The dictionary arguments of flate_hip_inflate_batch_dict (kept alive as long as this object): the
-    dictionaries packed into one buffer (on the device when the call's pointers are), dict_off, dict_of."""
+    dictionaries packed into one buffer (on the device when the call's pointers are), dict_off, dict_of.
+    zdicts=None: the arguments of a call without dictionaries (NULL, NULL, 0, NULL)."""
 
     def __init__(self, zdicts, dict_of, n, device):
+        self.buf = self.off = self.of = self.ptr = self.off_ptr = self.of_ptr = None
+        self.n_dicts = 0
+        if zdicts is None:
+            return
         if device and _is_torch(zdicts):  # one dictionary already on the device
             import torch
             assert zdicts.dtype == torch.uint8 and zdicts.is_cuda and zdicts.is_contiguous()
@@ -1277,8 +1099,6 @@ class _DictArgs:
         self.n_dicts = len(lens)
         self.ptr = self.buf.data_ptr() if _is_torch(self.buf) else self.buf.ctypes.data
         self.off_ptr = self.off.ctypes.data
-        self.of = None
-        self.of_ptr = None
         if dict_of is not None:
             self.of = np.ascontiguousarray(dict_of, dtype=np.uint32)
             assert self.of.size == n
@@ -1341,11 +1161,6 @@ def parse_container_header(m, wrap, fdict=False):
     if flg & 2:  # FHCRC
         p += 2
     return (p, 8) if p <= len(m) else (-1, 0)
-
-
-# status codes of inflate_batch (include/flate_hip.h)
-E_INVALID, E_OUT_TOO_SMALL, E_CORRUPT, E_UNEXPECTED_EOF, E_INTERNAL = -1, -2, -4, -7, -8
-E_TOO_LARGE, E_UNSUPPORTED = -6, -10
 
 
 def lz_chunks(stream_len):
