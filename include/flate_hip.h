@@ -802,7 +802,7 @@ int flate_hip_gzip_read(flate_hip_ctx *ctx, const uint8_t *in, uint64_t in_len, 
  *   FLATE_HIP_STAGE_CHECKSUM is VERIFY; FIND, PROBE, LINK, TAIL and COMPOSE are counted in no stage.
  *   Out of scope: finding stored or fixed block starts (streams made of them stay serial inside one unit); fusing
  *   PROBE with TAIL; routing long members of flate_hip_gzip_read here; multi-member input; caching the index across
- *   calls; seeking. */
+ *   calls (the seek index below is what a caller keeps). */
 int flate_hip_inflate_one(flate_hip_ctx *ctx, const uint8_t *in, uint64_t in_len, uint32_t wrap, uint8_t *out,
                           uint64_t out_cap, uint64_t *out_len, int32_t *status, int64_t *err_off, uint32_t *n_units,
                           uint32_t *n_candidates, uint32_t flags);
@@ -810,6 +810,110 @@ int flate_hip_inflate_one_index(flate_hip_ctx *ctx, const uint8_t *in, uint64_t 
                                 uint64_t index_cap, uint64_t *unit_bit, uint64_t *out_off, uint32_t *n_units,
                                 uint64_t *out_bytes, uint32_t *n_candidates, int32_t *status, int64_t *err_off,
                                 uint32_t flags);
+
+/* -- Seek index for one long stream: build once, read ranges --------------------------
+ * flate_hip_inflate_one pays the whole discovery on every call.  A SEEK INDEX keeps it: flate_hip_inflate_one_seek_index
+ * builds one, flate_hip_inflate_one_ranges reads byte ranges of the stream's output through it and decodes only the
+ * units they need.  The rule and the layout are written once, csrc/seek_index_rule.h; the kernels are
+ * csrc/one_seek_kernels.hip.
+ *
+ * Notation: n, unit_bit[0 .. n] and out_off[0 .. n] are exactly what flate_hip_inflate_one_index defines; T =
+ * out_off[n]; U[0, T) is what the stream inflates to.
+ *
+ * THE POINT RULE.  Unit k is a POINT iff k == 0 or out_off[k] / span > out_off[k - 1] / span (integer division).  span
+ * >= 1; span == 0 means FLATE_HIP_SEEK_SPAN_DEFAULT; FLATE_HIP_SEEK_SPAN_NONE leaves unit 0 as the only point: the
+ * index then holds no window at all and is simply the cached discovery; span == 1 makes every unit that produces output
+ * behind a non-empty predecessor a point.  pstart(k) is the last point at or in front of k; a SEGMENT is a point and the
+ * units behind it up to the next point.
+ *
+ * TWO BUFFERS.  index: a HOST array of 64-bit words (offset tables are always host arrays in this ABI):
+ *   word 0 the magic "FONESIDX" (little endian), 1 the version (1), 2 wrap, 3 in_len, 4 the raw stream's first byte, 5
+ *   the byte behind it, 6 T, 7 span, 8 n, 9 n_points, 10 / 11 the container's trailer words as the device parses them
+ *   (the checksum as a number and ISIZE; 0 for raw), 12 .. 15 zero;
+ *   then unit_bit[n + 1], out_off[n + 1], point_unit[n_points] (rising, point_unit[0] = 0):
+ *   16 + 2 (n + 1) + n_points words.
+ * windows: host, or device under FLATE_HIP_DEVICE_PTRS like in, at any byte alignment: n_points - 1 blocks of 32768
+ * bytes; block p - 1 is the 32 KiB of output in front of unit point_unit[p], in stream order, bytes in front of the
+ * stream 0.  Point 0 needs no window.  The windows are neither compressed nor checksummed.
+ *
+ * flate_hip_inflate_one_seek_index: BUILD.  Conventions are flate_hip_inflate_one's: the wrap rules, flags
+ * FLATE_HIP_DEVICE_PTRS or 0, FLATE_HIP_E_INVALID before any HIP call (NULL ctx / in with in_len > 0 / index_words /
+ * windows_bytes / n_units / n_points / out_bytes / status; index == NULL with index_cap_words > 0, windows == NULL with
+ * windows_cap > 0; a wrap above _GZIP; any other flag); host pointers are uploaded once.  n_candidates and err_off may
+ * be NULL.  Both sizes are known after POINTS, in front of TAIL: a too-small index_cap_words or windows_cap -- both
+ * buffers NULL with capacity 0 is the size query -- returns FLATE_HIP_E_OUT_TOO_SMALL with every count set
+ * (*index_words, *windows_bytes, *n_units, *n_points, *out_bytes = T) and nothing written; the query costs the
+ * discovery only.
+ * Verdict: *status / *err_off are flate_hip_inflate_one's for the same bytes, EXCEPT THAT THE TRAILER IS NOT JUDGED:
+ * nothing is decoded to output, so there is nothing to sum.  The history-independent verdict comes from the discovery;
+ * a distance that reaches in front of the stream comes from TAIL at the serial offset, which therefore runs over every
+ * unit whatever the span (a size query returns in front of it and reports the discovery's verdict).  A caller who wants
+ * the trailer judged calls flate_hip_inflate_one once.  A stream whose status is not 0 gets no index: *index_words =
+ * *windows_bytes = 0, *n_points = 0, the return value is the status; what `windows` holds then is unspecified, nothing
+ * outside windows[0, windows_cap) is ever written.
+ *   How: discovery as in flate_hip_inflate_one_index; POINTS, one thread per unit, the rule from two neighbouring
+ *   out_off entries, a scan and a compaction; per round of "one_round_units" TAIL and COMPOSE / RESOLVE exactly as
+ *   flate_hip_inflate_one runs them; in DECODE's place PACK, the resolved window in front of every point unit of the
+ *   round into its block by the gather kernel of the BGZF range call.  No kernel waits for another workgroup.
+ *
+ * flate_hip_inflate_one_ranges: READ.  begin, end: HOST arrays of n_ranges positions in U; range r is U[min(begin[r], T),
+ * min(end[r], T)) -- it reads short at the end, as FLATE_HIP_BGZF_POS_BYTES does.  out_off (HOST, n_ranges + 1, written),
+ * range_status (HOST, n_ranges, written, may be NULL), the output's layout, overlapping, repeated and empty ranges and
+ * what is written where are flate_hip_bgzf_read_ranges's.  n_decoded and bad_unit may be NULL.
+ * Unit k is TOUCHED iff it produces output and its output range intersects a non-empty range.  The DECODED set is the
+ * union, over touched k, of [pstart(k), k]: units behind the last touched unit of a segment are not decoded.
+ * *n_decoded is the size of that set.
+ * Verdict, in this order.
+ *  1. FLATE_HIP_E_INVALID before any HIP call: any of flate_hip_bgzf_read_ranges's argument refusals; a wrap above
+ *     _GZIP; windows == NULL with windows_bytes > 0; an index that fails seek_index_ok (host, O(n)): a wrong magic or
+ *     version; wrap or in_len not the call's; a word count or windows_bytes that is not what the counts imply; unit_bit
+ *     not strictly increasing from 0 inside the raw stream, or a unit of more than 2^28 bytes of input; out_off not
+ *     non-decreasing from 0 to T; point_unit not exactly the point rule's set for the stored span.
+ *  2. n_ranges == 0: out_off[0] = 0 if out_off is given, FLATE_HIP_OK, nothing is read.
+ *  3. The stream is not the one the index was built from -- the raw stream's range or the trailer words, parsed on the
+ *     device, differ from the head's: FLATE_HIP_E_CORRUPT, every range_status FLATE_HIP_E_CORRUPT, every out_off 0,
+ *     nothing decoded.
+ *  4. A total above out_cap: FLATE_HIP_E_OUT_TOO_SMALL, out_off fully written, nothing decoded.  out == NULL with out_cap
+ *     == 0 is the size query -- unless the total is 0, which is FLATE_HIP_OK.
+ *  5. Decode and deliver.  A decoded unit is GOOD iff its piece ends with status 0 and produces exactly out_off[k + 1] -
+ *     out_off[k] bytes; anything else means that the index does not fit the stream: the decoder's status, or
+ *     FLATE_HIP_E_CORRUPT if only the size differs.  range_status[r] is the first non-zero status, in stream order,
+ *     among the units [pstart(first), last] decoded for range r (first / last: its first and last touched unit), else
+ *     0.  The return value is the first non-zero status among all decoded units in stream order, with *bad_unit = that
+ *     unit; otherwise FLATE_HIP_OK and *bad_unit = 0xffffffff.  Bytes from units behind a bad unit of the same segment
+ *     are unspecified; everything else is exact.  A wrong byte inside `windows` cannot be detected: ranges carry no
+ *     checksum.
+ * Host pointers: the stream is uploaded once, at most the windows of the selected points are uploaded (the host has
+ * the selection after the read-back), the delivered bytes come down once.
+ *   How, all on the ctx's stream, no host pass over stream bytes: LOCATE, one thread per range, binary search in
+ *   out_off, +1 at pstart(first) and -1 behind last into a difference array over the units.  SELECT: its scan marks the
+ *   decoded units, a second scan gives each its rank and its place in a dense scratch, compaction in stream order gives
+ *   the unit list; ONE read-back of counts and layout (the synchronisation flate_hip_bgzf_read_ranges has).  Rounds of
+ *   "one_round_units" over the list: TAIL through the list; a SEGMENTED scan -- every unit of the round carries the
+ *   round-local place of its seed, the nearest selected point at or in front of it, or place 0 when its segment
+ *   continues from the round in front; the stride-s step composes only when k - s is not in front of that seed;
+ *   RESOLVE applies each unit's composed function to its seed's window: the point's stored one, copied from `windows`
+ *   into the round's slots first, or the carried one -- and DECODE: the units as spliced pieces with dictionaries, each
+ *   with its own end, straight into the dense scratch, every unit in a slot of exactly its size.  CHECK per unit, then
+ *   GATHER: every range's one run of the scratch into out.  Locate, select and gather are counted in no profiling
+ *   stage; FLATE_HIP_STAGE_INFLATE is DECODE (of several rounds the last).
+ *   Out of scope: delivering the output or judging the trailer from the build call; compressed or sparse windows;
+ *   importing or exporting other tools' index formats; multi-member input; an index cached inside the ctx; uploading
+ *   only the touched part of the stream from host memory; stored and fixed block starts as units; skipping TAIL for
+ *   units whose tail function nobody reads. */
+#define FLATE_HIP_SEEK_SPAN_DEFAULT (1ull << 20)
+#define FLATE_HIP_SEEK_SPAN_NONE 0xffffffffffffffffull
+#define FLATE_HIP_SEEK_WINDOW_BYTES 32768u
+int flate_hip_inflate_one_seek_index(flate_hip_ctx *ctx, const uint8_t *in, uint64_t in_len, uint32_t wrap,
+                                     uint64_t span, uint64_t *index, uint64_t index_cap_words, uint64_t *index_words,
+                                     uint8_t *windows, uint64_t windows_cap, uint64_t *windows_bytes, uint32_t *n_units,
+                                     uint32_t *n_points, uint64_t *out_bytes, uint32_t *n_candidates, int32_t *status,
+                                     int64_t *err_off, uint32_t flags);
+int flate_hip_inflate_one_ranges(flate_hip_ctx *ctx, const uint8_t *in, uint64_t in_len, uint32_t wrap,
+                                 const uint64_t *index, uint64_t index_words, const uint8_t *windows,
+                                 uint64_t windows_bytes, const uint64_t *begin, const uint64_t *end, uint32_t n_ranges,
+                                 uint8_t *out, uint64_t out_cap, uint64_t *out_off, int32_t *range_status,
+                                 uint32_t *n_decoded, uint32_t *bad_unit, uint32_t flags);
 
 /* -- ZIP archives ----------------------------------------------------------------
  * The everyday container of a batch of independent DEFLATE streams (.zip, .npz, .jar, .whl, .docx; PKWARE APPNOTE

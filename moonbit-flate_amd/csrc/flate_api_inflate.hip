@@ -1204,6 +1204,17 @@ int one_discover(flate_hip_ctx *c, const uint8_t *d_in, uint64_t in_len, uint32_
   return FLATE_HIP_OK;
 }
 
+// TAIL, COMPOSE and RESOLVE of the round D.u0 .. D.u0 + D.count - 1 of consecutive units: the windows R[1 .. count]
+// from the seed R[0] (flate_hip_inflate_one and the build of the seek index run exactly these launches).
+void one_round_windows(flate_hip_ctx *c, const OneDecParams &D) {
+  const uint32_t entry_blocks = (uint32_t)(((uint64_t)D.count * kWinEntries + 255) / 256);
+  hipLaunchKernelGGL(one_tail_kernel, dim3(D.count), dim3(64), 0, c->stream, D);
+  int cur = 0;
+  for (uint32_t s = 1; s < D.count; s <<= 1, cur ^= 1)
+    hipLaunchKernelGGL(one_compose_kernel, dim3(entry_blocks), dim3(256), 0, c->stream, D.F[cur], D.F[cur ^ 1], D.count, s);
+  hipLaunchKernelGGL(one_resolve_kernel, dim3(entry_blocks), dim3(256), 0, c->stream, D.F[cur], D.R, D.count);
+}
+
 }  // namespace
 
 extern "C" {
@@ -1341,13 +1352,8 @@ int flate_hip_inflate_one(flate_hip_ctx *c, const uint8_t *in, uint64_t in_len, 
     for (uint32_t u0 = 0; u0 < n_dec; u0 += per_round) {
       D.u0 = u0;
       D.count = n_dec - u0 < per_round ? n_dec - u0 : per_round;
-      const uint32_t entry_blocks = (uint32_t)(((uint64_t)D.count * kWinEntries + 255) / 256);
       const uint32_t unit_blocks = (D.count + 1u + 255u) / 256u;
-      hipLaunchKernelGGL(one_tail_kernel, dim3(D.count), dim3(64), 0, c->stream, D);
-      int cur = 0;
-      for (uint32_t s = 1; s < D.count; s <<= 1, cur ^= 1)
-        hipLaunchKernelGGL(one_compose_kernel, dim3(entry_blocks), dim3(256), 0, c->stream, D.F[cur], D.F[cur ^ 1], D.count, s);
-      hipLaunchKernelGGL(one_resolve_kernel, dim3(entry_blocks), dim3(256), 0, c->stream, D.F[cur], D.R, D.count);
+      one_round_windows(c, D);
       // DECODE: the round's units as spliced pieces with dictionaries, through the lane-per-stream decoder.  The
       // stream's last piece runs to BFINAL (or to its failure); every other round's last piece ends where the next
       // unit starts, and so does the last unit of a chain that stopped at a header the decoder refuses.
@@ -1398,6 +1404,426 @@ int flate_hip_inflate_one(flate_hip_ctx *c, const uint8_t *in, uint64_t in_len, 
     }
     if (c->profiling && (rc = collect_timing(c, used))) return rc;
     return verdict(R.status, R.err_off);
+  } catch (const std::exception &e) {
+    c->hip_err = e.what();
+    return FLATE_HIP_E_INTERNAL;
+  }
+}
+
+// The seek index: discovery, POINTS, then per round TAIL / COMPOSE / RESOLVE as above and, in DECODE's place, PACK: the
+// windows in front of the round's point units into their blocks.  Nothing is decoded to output.
+int flate_hip_inflate_one_seek_index(flate_hip_ctx *c, const uint8_t *in, uint64_t in_len, uint32_t wrap, uint64_t span,
+                                     uint64_t *index, uint64_t index_cap_words, uint64_t *index_words, uint8_t *windows,
+                                     uint64_t windows_cap, uint64_t *windows_bytes, uint32_t *n_units, uint32_t *n_points,
+                                     uint64_t *out_bytes, uint32_t *n_candidates, int32_t *status, int64_t *err_off,
+                                     uint32_t flags) {
+  // every check before any HIP call
+  if (!c) return FLATE_HIP_E_INVALID;
+  int rc = one_seek_index_args(in, in_len, wrap, index, index_cap_words, index_words, windows, windows_cap, windows_bytes,
+                               n_units, n_points, out_bytes, status, flags);
+  if (rc) return rc;
+  c->hip_err.clear();
+  *index_words = 0, *windows_bytes = 0, *n_units = 0, *n_points = 0, *out_bytes = 0, *status = 0;
+  if (n_candidates) *n_candidates = 0;
+  if (err_off) *err_off = -1;
+  auto verdict = [&](int st, int64_t eo) {  // a stream that fails gets no index
+    *status = st;
+    if (err_off) *err_off = st ? eo : -1;
+    if (st) *index_words = 0, *windows_bytes = 0, *n_points = 0, *out_bytes = 0;
+    return st;
+  };
+  if (in_len == 0)
+    return wrap == FLATE_HIP_WRAP_RAW ? verdict(FLATE_HIP_E_UNEXPECTED_EOF, -1) : verdict(FLATE_HIP_E_CORRUPT, 0);
+  span = seek_span(span);
+  try {
+    const bool dev = (flags & FLATE_HIP_DEVICE_PTRS) != 0;
+    const uint8_t *d_in = nullptr;
+    if ((rc = stage_input(c, in, in_len, flags, &d_in))) return rc;
+    OneHead H{};
+    OneParams P{};
+    std::vector<uint64_t> found;  // unit_bit, then out_off: one entry per candidate and one more, the units in front
+    if ((rc = one_discover(c, d_in, in_len, wrap, ~0ull, H, P, found))) return rc;
+    const uint32_t n = H.h.n_members;
+    *n_units = n;
+    if (n_candidates) *n_candidates = H.h.n_cand;
+    if (H.h.n_cand == 0) return verdict(H.h.rc, H.h.err_off);  // a bad header
+    if (H.h.rc == FLATE_HIP_E_TOO_LARGE || H.h.rc == FLATE_HIP_E_INTERNAL) return verdict(H.h.rc, H.h.err_off);
+    const bool sound = H.h.rc == 0;  // (a stream that fails is still walked: an earlier unit's distance may fail first)
+    const uint32_t n_dec = n + (H.fail_unit ? 1u : 0u);
+    const uint32_t per_round = n_dec < c->one_round_units ? (n_dec ? n_dec : 1u) : c->one_round_units;
+
+    // POINTS: mark, scan, compact; the sizes are known here, in front of TAIL
+    OneSeekPointsParams PP{};
+    uint64_t *d_r_out_off, *d_r_src;
+    rc = carve(c, c->d_one_seek, [&](Carve &k) {
+      k.take(PP.n_points, 1);
+      k.take(PP.point_unit, (size_t)n + 1);
+      k.take(d_r_out_off, (size_t)per_round + 1);
+      k.take(d_r_src, per_round);
+    });
+    if (rc) return rc;
+    std::vector<uint64_t> points;
+    FrameOne one{};
+    uint32_t np = 0;
+    uint64_t need_words = 0, need_bytes = 0;
+    if (sound) {
+      PP.out_off = P.C.out_off;
+      PP.n = n;
+      PP.span = span;
+      hipLaunchKernelGGL(one_seek_points_kernel, dim3(1), dim3(1024), 0, c->stream, PP);
+      HIP_TRY(c, hipGetLastError());
+      points.assign(n, 0);
+      HIP_TRY(c, hipMemcpyAsync(&np, PP.n_points, 4, hipMemcpyDeviceToHost, c->stream));
+      HIP_TRY(c, hipMemcpyAsync(points.data(), PP.point_unit, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
+      HIP_TRY(c, hipMemcpyAsync(&one, P.one, sizeof one, hipMemcpyDeviceToHost, c->stream));
+      HIP_TRY(c, hipStreamSynchronize(c->stream));
+      if (np < 1u || np > n || found.size() < 2 * ((size_t)n + 1)) {
+        c->hip_err = "seek index: the point count does not fit the units";
+        return FLATE_HIP_E_INTERNAL;
+      }
+      need_words = seek_index_words(n, np);
+      need_bytes = seek_windows_bytes(np);
+      *index_words = need_words, *windows_bytes = need_bytes, *n_points = np, *out_bytes = H.h.out_bytes;
+      if (index_cap_words < need_words || windows_cap < need_bytes) return FLATE_HIP_E_OUT_TOO_SMALL;  // (the size query too)
+    }
+    uint8_t *d_windows = windows;
+    if (sound && !dev && need_bytes) {
+      if ((rc = ensure(c, c->d_one_seek_win, need_bytes + 16))) return rc;
+      d_windows = (uint8_t *)c->d_one_seek_win.p;
+    }
+
+    OneDecParams D{};
+    rc = carve(c, c->d_one_dec, [&](Carve &k) {
+      k.take(D.dh, 1);
+      k.take(D.F[0], (size_t)per_round * kWinEntries);
+      k.take(D.F[1], (size_t)per_round * kWinEntries);
+      k.take(D.R, ((size_t)per_round + 1) * kWinEntries);
+      k.take(D.status, (size_t)n_dec + 1);
+      k.take(D.err_off, (size_t)n_dec + 1);
+      k.take(D.produced, (size_t)n_dec + 1);
+    });
+    if (rc) return rc;
+    D.in = d_in;
+    D.one = P.one;
+    D.unit_bit = P.C.member_off;
+    D.out_off = P.C.out_off;
+    D.unit_max = c->one_unit_max;
+    HIP_TRY(c, hipMemsetAsync(D.dh, 0xff, sizeof(OneDecHead), c->stream));  // first_bad: none
+    HIP_TRY(c, hipMemsetAsync(D.R, 0, kWinEntries, c->stream));            // in front of the stream: zeros
+    uint32_t p_next = 1;  // the first point whose window is not packed yet (point 0 has none)
+    for (uint32_t u0 = 0; u0 < n_dec; u0 += per_round) {
+      D.u0 = u0;
+      D.count = n_dec - u0 < per_round ? n_dec - u0 : per_round;
+      one_round_windows(c, D);
+      // PACK: R[i] of the round's point units -> their blocks, which lie one behind the other in `windows`
+      uint32_t p_hi = p_next;
+      while (p_hi < np && points[p_hi] < (uint64_t)u0 + D.count) ++p_hi;
+      if (p_hi > p_next) {
+        const uint32_t cnt = p_hi - p_next;
+        hipLaunchKernelGGL(one_seek_pack_kernel, dim3((cnt + 1u + 255u) / 256u), dim3(256), 0, c->stream, PP.point_unit,
+                           p_next, cnt, u0, d_r_out_off, d_r_src);
+        BgzfGatherParams G{};
+        G.scratch = D.R;  // (R[count] lies behind the last run: the 32 bytes the gather may touch)
+        G.out = d_windows + (uint64_t)(p_next - 1u) * kSeekWindow;
+        G.r_out_off = d_r_out_off;
+        G.r_src = d_r_src;
+        G.n_ranges = cnt;
+        const uint64_t pieces = ((uint64_t)cnt * (kSeekWindow + kBgzfGatherRangeCost) + kBgzfGatherWindow - 1) / kBgzfGatherWindow;
+        hipLaunchKernelGGL(bgzf_gather_kernel, dim3((uint32_t)pieces), dim3(256), 0, c->stream, G);
+        p_next = p_hi;
+      }
+      HIP_TRY(c, hipGetLastError());
+      if (u0 + D.count < n_dec)
+        HIP_TRY(c, hipMemcpyAsync(D.R, D.R + (size_t)D.count * kWinEntries, kWinEntries, hipMemcpyDeviceToDevice, c->stream));
+    }
+    OneDecHead R{};
+    HIP_TRY(c, hipMemcpyAsync(&R, D.dh, sizeof R, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (R.first_bad != 0xffffffffu) {  // TAIL's verdict: the serial decoder's, at the serial offset
+      if (R.first_bad >= n_dec) return FLATE_HIP_E_INTERNAL;
+      int32_t st = 0;
+      int64_t eo = -1;
+      HIP_TRY(c, hipMemcpyAsync(&st, D.status + R.first_bad, 4, hipMemcpyDeviceToHost, c->stream));
+      HIP_TRY(c, hipMemcpyAsync(&eo, D.err_off + R.first_bad, 8, hipMemcpyDeviceToHost, c->stream));
+      HIP_TRY(c, hipStreamSynchronize(c->stream));
+      return verdict(st ? st : FLATE_HIP_E_INTERNAL, eo);
+    }
+    if (!sound) return verdict(H.h.rc, H.h.err_off);
+    if (p_next != np) return FLATE_HIP_E_INTERNAL;
+    if (!dev && need_bytes) {
+      HIP_TRY(c, hipMemcpyAsync(windows, d_windows, need_bytes, hipMemcpyDeviceToHost, c->stream));
+      HIP_TRY(c, hipStreamSynchronize(c->stream));
+    }
+    for (uint32_t k = 0; k < kSeekHeadWords; ++k) index[k] = 0;
+    index[kSeekMagicAt] = kSeekMagic;
+    index[kSeekVersionAt] = kSeekVersion;
+    index[kSeekWrapAt] = wrap;
+    index[kSeekInLenAt] = in_len;
+    index[kSeekRawOffAt] = H.raw_off;
+    index[kSeekRawEndAt] = H.raw_off + H.raw_len;
+    index[kSeekTotalAt] = H.h.out_bytes;
+    index[kSeekSpanAt] = span;
+    index[kSeekUnitsAt] = n;
+    index[kSeekPointsAt] = np;
+    index[kSeekWantAt] = one.want;
+    index[kSeekIsizeAt] = one.isize;
+    uint64_t *w = index + kSeekHeadWords;
+    memcpy(w, found.data(), ((size_t)n + 1) * 8);
+    memcpy(w + (n + 1), found.data() + found.size() / 2, ((size_t)n + 1) * 8);
+    memcpy(w + 2 * ((size_t)n + 1), points.data(), (size_t)np * 8);
+    return FLATE_HIP_OK;
+  } catch (const std::exception &e) {
+    c->hip_err = e.what();
+    return FLATE_HIP_E_INTERNAL;
+  }
+}
+
+// Random access through the seek index: locate, select, layout (one_seek_kernels.hip), ONE read-back (the parsed
+// container, the ranges' layout, the unit list), rounds of TAIL / segmented scan / DECODE over the list into a dense
+// scratch, the per-unit check, the gather.
+int flate_hip_inflate_one_ranges(flate_hip_ctx *c, const uint8_t *in, uint64_t in_len, uint32_t wrap, const uint64_t *index,
+                                 uint64_t index_words, const uint8_t *windows, uint64_t windows_bytes, const uint64_t *begin,
+                                 const uint64_t *end, uint32_t n_ranges, uint8_t *out, uint64_t out_cap, uint64_t *out_off,
+                                 int32_t *range_status, uint32_t *n_decoded, uint32_t *bad_unit, uint32_t flags) {
+  // every check before any HIP call
+  if (!c) return FLATE_HIP_E_INVALID;
+  int rc = one_ranges_args(in, in_len, wrap, index, index_words, windows, windows_bytes, begin, end, n_ranges, out, out_cap,
+                           out_off, flags);
+  if (rc) return rc;
+  c->hip_err.clear();
+  if (n_decoded) *n_decoded = 0;
+  if (bad_unit) *bad_unit = 0xffffffffu;
+  if (n_ranges == 0) {
+    if (out_off) out_off[0] = 0;
+    return FLATE_HIP_OK;
+  }
+  const uint32_t nr = n_ranges;
+  try {
+    const bool dev = (flags & FLATE_HIP_DEVICE_PTRS) != 0;
+    const uint8_t *d_in = nullptr;
+    if ((rc = stage_input(c, in, in_len, flags, &d_in))) return rc;
+    const uint32_t n = (uint32_t)index[kSeekUnitsAt], np = (uint32_t)index[kSeekPointsAt];
+    const uint64_t raw_off = index[kSeekRawOffAt], raw_end = index[kSeekRawEndAt];
+    const uint64_t *h_point = index + kSeekHeadWords + 2 * ((size_t)n + 1);
+    const size_t idx_words = 2 * ((size_t)n + 1) + np;
+
+    OneSeekParams Q{};
+    Q.n = n, Q.n_points = np, Q.span = index[kSeekSpanAt], Q.n_ranges = nr;
+    uint64_t *d_idx, *d_begin, *d_end;
+    FrameOne *d_one;
+    size_t o_back = 0, o_end = 0;
+    rc = carve(c, c->d_one_seek, [&](Carve &k) {
+      k.take(d_idx, idx_words);
+      k.take(d_begin, nr);
+      k.take(d_end, nr);
+      k.take(Q.diff, (size_t)n + 1);
+      k.take(Q.rank, n);
+      k.take(Q.scratch_at, n);
+      k.take(Q.r_b, nr);
+      k.take(Q.r_len, nr);
+      k.take(Q.r_first, nr);
+      k.take(Q.r_last, nr);
+      k.take(Q.r_seg, nr);
+      k.take(Q.r_src, nr);
+      k.take(Q.sel_at, (size_t)n + 1);
+      o_back = k.at;
+      k.take(Q.head, 1);
+      k.take(d_one, 1);
+      k.take(Q.r_out_off, (size_t)nr + 1);
+      k.take(Q.r_rank_lo, nr);
+      k.take(Q.r_rank_hi, nr);
+      k.take(Q.sel_unit, n);
+      o_end = k.at;
+    });
+    if (rc) return rc;
+    Q.unit_bit = d_idx, Q.out_off = d_idx + (n + 1), Q.point_unit = d_idx + 2 * ((size_t)n + 1);
+    Q.begin = d_begin, Q.end = d_end;
+    const size_t back_bytes = o_end - o_back;
+    const uint8_t *d_back = (const uint8_t *)c->d_one_seek.p + o_back;
+    HIP_TRY(c, hipMemcpyAsync(d_idx, index + kSeekHeadWords, idx_words * 8, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(d_begin, begin, (size_t)nr * 8, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(d_end, end, (size_t)nr * 8, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemsetAsync(Q.diff, 0, ((size_t)n + 1) * 4, c->stream));
+    // the container as this stream has it: the raw stream's range and the trailer's words
+    hipLaunchKernelGGL(one_init_kernel, dim3(1), dim3(64), 0, c->stream, d_one, in_len);
+    if (wrap != FLATE_HIP_WRAP_RAW) {
+      FrameReadParams R{};
+      R.in = d_in;
+      R.in_off = d_one->in_off;
+      R.n_streams = 1;
+      R.wrap = wrap;
+      R.pay_off = d_one->pay_off;
+      R.pay_end = &d_one->pay_end;
+      R.want = &d_one->want;
+      R.isize = &d_one->isize;
+      R.bad = &d_one->bad;
+      R.dict_used = &d_one->dict_used;
+      hipLaunchKernelGGL(frame_parse_kernel, dim3(1), dim3(256), 0, c->stream, R);
+    }
+    hipLaunchKernelGGL(one_seek_locate_kernel, dim3((nr + 255u) / 256u), dim3(256), 0, c->stream, Q);
+    hipLaunchKernelGGL(one_seek_select_kernel, dim3(1), dim3(1024), 0, c->stream, Q);
+    hipLaunchKernelGGL(one_seek_layout_kernel, dim3(1), dim3(1024), 0, c->stream, Q);
+    HIP_TRY(c, hipGetLastError());
+    std::vector<uint8_t> back(back_bytes);
+    HIP_TRY(c, hipMemcpyAsync(back.data(), d_back, back_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    auto got = [&](const auto *d) { return (decltype(d))(back.data() + ((const uint8_t *)d - d_back)); };  // d's host copy
+    const OneSeekHead RH = *got(Q.head);
+    const FrameOne one = *got(d_one);
+    const uint32_t *r_lo = got(Q.r_rank_lo), *r_hi = got(Q.r_rank_hi), *sel = got(Q.sel_unit);
+    const uint32_t ns = RH.n_sel;
+    if (one.bad || one.pay_off[0] != raw_off || one.pay_end != raw_end || one.want != index[kSeekWantAt] ||
+        one.isize != index[kSeekIsizeAt]) {  // not the stream the index was built from: nothing is decoded
+      for (uint32_t r = 0; r <= nr; ++r) out_off[r] = 0;
+      if (range_status)
+        for (uint32_t r = 0; r < nr; ++r) range_status[r] = FLATE_HIP_E_CORRUPT;
+      return FLATE_HIP_E_CORRUPT;
+    }
+    if (ns > n) {
+      c->hip_err = "seek ranges: more units selected than the stream has";
+      return FLATE_HIP_E_INTERNAL;
+    }
+    memcpy(out_off, got(Q.r_out_off), ((size_t)nr + 1) * 8);
+    if (n_decoded) *n_decoded = ns;
+    if (range_status)
+      for (uint32_t r = 0; r < nr; ++r) range_status[r] = 0;
+    if (RH.out_total > out_cap) return FLATE_HIP_E_OUT_TOO_SMALL;  // (the size query too: nothing is decoded)
+    if (ns == 0 || RH.out_total == 0) return FLATE_HIP_OK;        // (no range holds a byte)
+
+    // the windows: the caller's device buffer, or the blocks of the selected points uploaded into a staged copy
+    const uint8_t *d_windows = windows;
+    if (!dev && windows_bytes) {
+      if ((rc = ensure(c, c->d_one_seek_win, windows_bytes + 16))) return rc;
+      uint8_t *stage = (uint8_t *)c->d_one_seek_win.p;
+      d_windows = stage;
+      std::vector<uint32_t> ps;  // the selected points behind point 0, rising
+      uint32_t p = 1;
+      for (uint32_t i = 0; i < ns && p < np; ++i) {
+        while (p < np && h_point[p] < sel[i]) ++p;
+        if (p < np && h_point[p] == sel[i]) ps.push_back(p);
+      }
+      for (size_t a = 0; a < ps.size();) {  // neighbours in the index travel as one copy
+        size_t b = a + 1;
+        while (b < ps.size() && ps[b] == ps[b - 1] + 1u) ++b;
+        const uint64_t at = (uint64_t)(ps[a] - 1u) * kSeekWindow, len = (uint64_t)(b - a) * kSeekWindow;
+        HIP_TRY(c, hipMemcpyAsync(stage + at, windows + at, len, hipMemcpyHostToDevice, c->stream));
+        a = b;
+      }
+    }
+
+    const uint32_t per_round = ns < c->one_round_units ? ns : c->one_round_units;
+    const size_t fentries = (size_t)per_round * kWinEntries;
+    OneDecParams D{};
+    OneSeekRoundParams S{};
+    int32_t *d_ds;
+    uint64_t *d_dl;
+    int64_t *d_de;
+    rc = carve(c, c->d_one_dec, [&](Carve &k) {
+      k.take(D.dh, 1);
+      k.take(D.F[0], fentries);
+      k.take(D.F[1], fentries);
+      k.take(D.R, ((size_t)per_round + 1) * kWinEntries);
+      k.take(D.status, (size_t)ns + 1);
+      k.take(D.err_off, (size_t)ns + 1);
+      k.take(D.produced, (size_t)ns + 1);
+      k.take(S.seed, per_round);
+      k.take(S.p_bit_off, per_round);
+      k.take(S.p_bit_end, per_round);
+      k.take(S.p_dict_at, per_round);
+      k.take(S.p_dict_len, per_round);
+      k.take(d_ds, per_round);
+      k.take(d_dl, per_round);
+      k.take(d_de, per_round);
+      k.take(S.u_status, ns);
+    });
+    if (rc) return rc;
+    if ((rc = ensure(c, c->d_one_seek_dense, RH.scratch_total + 64))) return rc;
+    uint8_t *d_dense = (uint8_t *)c->d_one_seek_dense.p;
+    uint8_t *d_out = out;
+    if (!dev) {
+      if ((rc = ensure(c, c->d_out, RH.out_total + 16))) return rc;
+      d_out = (uint8_t *)c->d_out.p;
+    }
+    D.in = d_in;
+    D.one = d_one;
+    D.unit_bit = Q.unit_bit;
+    D.out_off = Q.out_off;
+    D.unit_max = c->one_unit_max;
+    D.unit_list = Q.sel_unit;
+    S.Q = Q;
+    S.windows = d_windows;
+    S.R = D.R;
+    S.d_status = d_ds;
+    S.d_out_len = d_dl;
+    HIP_TRY(c, hipMemsetAsync(D.dh, 0xff, sizeof(OneDecHead), c->stream));
+    bool used[FLATE_HIP_STAGE_COUNT] = {false, false, false, false};
+    for (uint32_t i0 = 0; i0 < ns; i0 += per_round) {
+      const uint32_t count = ns - i0 < per_round ? ns - i0 : per_round;
+      D.u0 = S.i0 = i0;
+      D.count = S.count = count;
+      const uint32_t entry_blocks = (uint32_t)(((uint64_t)count * kWinEntries + 255) / 256);
+      const uint32_t unit_blocks = (count + 255u) / 256u;
+      hipLaunchKernelGGL(one_seek_seed_kernel, dim3(unit_blocks), dim3(256), 0, c->stream, S);
+      hipLaunchKernelGGL(one_seek_load_kernel, dim3((entry_blocks + 15u) / 16u), dim3(256), 0, c->stream, S);
+      hipLaunchKernelGGL(one_tail_kernel, dim3(count), dim3(64), 0, c->stream, D);
+      int cur = 0;
+      for (uint32_t s = 1; s < count; s <<= 1, cur ^= 1)
+        hipLaunchKernelGGL(one_seek_compose_kernel, dim3(entry_blocks), dim3(256), 0, c->stream, D.F[cur], D.F[cur ^ 1],
+                           S.seed, count, s);
+      hipLaunchKernelGGL(one_seek_resolve_kernel, dim3(entry_blocks), dim3(256), 0, c->stream, D.F[cur], D.R, S.seed, count);
+      // DECODE: the round's units as spliced pieces with dictionaries, each with its own end, into their dense slots
+      InfParams I{};
+      I.in = d_in + raw_off;
+      I.in_len = raw_end - raw_off;
+      I.bit_off = S.p_bit_off;
+      I.bit_end = S.p_bit_end;
+      I.n_streams = count;
+      I.out = d_dense;
+      I.out_off = Q.sel_at + i0;
+      I.out_len = d_dl;
+      I.status = d_ds;
+      I.err_off = d_de;
+      I.dict_buf = D.R;
+      I.dict_at = S.p_dict_at;
+      I.dict_len = S.p_dict_len;
+      if ((rc = launch_decoders(c, inflate_route_units(c->inflate, c->num_cus, count), I, true))) return rc;
+      used[FLATE_HIP_STAGE_INFLATE] = true;
+      hipLaunchKernelGGL(one_seek_check_kernel, dim3(unit_blocks), dim3(256), 0, c->stream, S);
+      HIP_TRY(c, hipGetLastError());
+      // the window behind the round's last unit is the carried seed of a segment that continues
+      if (i0 + count < ns)
+        HIP_TRY(c, hipMemcpyAsync(D.R, D.R + (size_t)count * kWinEntries, kWinEntries, hipMemcpyDeviceToDevice, c->stream));
+    }
+
+    // the gather: every range's run of the scratch to its place in out
+    const uint64_t pieces = (RH.out_total + (uint64_t)kBgzfGatherRangeCost * nr + kBgzfGatherWindow - 1) / kBgzfGatherWindow;
+    if (pieces > 0x7fffffffull) return FLATE_HIP_E_TOO_LARGE;
+    BgzfGatherParams G{};
+    G.scratch = d_dense;
+    G.out = d_out;
+    G.r_out_off = Q.r_out_off;
+    G.r_src = Q.r_src;
+    G.n_ranges = nr;
+    hipLaunchKernelGGL(bgzf_gather_kernel, dim3((uint32_t)pieces), dim3(256), 0, c->stream, G);
+    HIP_TRY(c, hipGetLastError());
+    std::vector<int32_t> st(ns);
+    HIP_TRY(c, hipMemcpyAsync(st.data(), S.u_status, (size_t)ns * 4, hipMemcpyDeviceToHost, c->stream));
+    if (!dev) HIP_TRY(c, hipMemcpyAsync(out, d_out, RH.out_total, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (c->profiling && (rc = collect_timing(c, used))) return rc;
+
+    // the statuses: nxt[i] = the first decoded unit at or behind place i with a status
+    std::vector<uint32_t> nxt((size_t)ns + 1);
+    nxt[ns] = ns;
+    for (uint32_t i = ns; i-- > 0;) nxt[i] = st[i] ? i : nxt[i + 1];
+    if (range_status)
+      for (uint32_t r = 0; r < nr; ++r)
+        if (r_lo[r] < r_hi[r] && r_hi[r] <= ns && nxt[r_lo[r]] < r_hi[r]) range_status[r] = st[nxt[r_lo[r]]];
+    if (nxt[0] < ns) {
+      if (bad_unit) *bad_unit = sel[nxt[0]];
+      return st[nxt[0]];
+    }
+    return FLATE_HIP_OK;
   } catch (const std::exception &e) {
     c->hip_err = e.what();
     return FLATE_HIP_E_INTERNAL;

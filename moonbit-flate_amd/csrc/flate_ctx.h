@@ -91,6 +91,10 @@ struct flate_hip_ctx {
   // per-unit results), carved from one buffer; the units of a round (option "one_round_units")
   DevBuf d_one_dec;
   uint32_t one_round_units = 4096;
+  // flate_hip_inflate_one_seek_index / _ranges: the point, range and selection arrays (OneSeekPointsParams,
+  // OneSeekParams), carved from one buffer; a host caller's windows; the dense scratch the selected units are decoded
+  // into.  Both calls carve their rounds' arrays from d_one_dec.
+  DevBuf d_one_seek, d_one_seek_win, d_one_seek_dense;
   DevBuf d_zip_names, d_zip_name_off, d_zip_whead, d_zip_end, d_zip_dir, d_zip_sel;
   hipStream_t guest_stream = nullptr;
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;

@@ -152,6 +152,10 @@ struct InfParams {
   // inflate_simt_kernel, spliced: nonzero = the pieces are a part of a longer stream (a round of
   // flate_hip_inflate_one): the last piece does not run to BFINAL, it ends at bit_off[n_streams] like the others
   uint32_t closed;
+  // inflate_simt_kernel, spliced: pieces that are NOT consecutive in the stream (flate_hip_inflate_one_ranges: the
+  // selected units): piece i ends at bit bit_end[i], or runs to BFINAL where that is ~0; bit_off then has n_streams
+  // entries and `closed` is not read.  NULL: piece i ends where piece i+1 starts, `closed` as above.
+  const uint64_t *bit_end;
   uint32_t size_only;  // inflate_kernel: decode and count, store nothing (FLATE_HIP_SIZE_ONLY)
   uint32_t *simt_lens; // inflate_simt_kernel: per-lane scratch of the header being parsed (inflate_simt_lens_bytes)
   uint32_t sid0;       // inflate_simt_kernel: first stream of this launch (a batch of several rounds)
@@ -536,6 +540,10 @@ struct OneDecParams {
   const uint64_t *unit_bit;  // n_dec + 1 (OneParams::C.member_off)
   const uint64_t *out_off;   // n_dec + 1
   uint32_t u0, count;
+  // one_tail_kernel: the round's units are unit_list[u0 .. u0 + count) -- not consecutive in the stream
+  // (flate_hip_inflate_one_ranges) -- every one of them is walked, and status / err_off / produced are indexed by the
+  // place in the list.  NULL: the units u0 .. u0 + count - 1.
+  const uint32_t *unit_list;
   uint64_t total;            // nothing at or behind out + total is written
   uint64_t unit_max;
   uint16_t *F[2];            // count * 32768 entries each
@@ -569,6 +577,84 @@ __global__ void one_probe_kernel(OneParams P, uint32_t tail);
 __global__ void one_link_kernel(OneParams P);
 __global__ void one_finish_kernel(OneParams P);
 __global__ void one_out_scan_kernel(OneParams P);
+
+// The seek index of one long stream (one_seek_kernels.hip; flate_hip_inflate_one_seek_index / _ranges; the rule and
+// the index's layout: seek_index_rule.h).
+// BUILD.  one_seek_points_kernel (POINTS, one workgroup): mark by the point rule, scan, compact -> point_unit, n_points.
+// Per round of flate_hip_inflate_one's TAIL / COMPOSE / RESOLVE, one_seek_pack_kernel lists the round's point units as
+// runs of R for bgzf_gather_kernel (PACK): run j = R[point_unit[p_lo + j] - u0] -> block p_lo + j - 1 of the windows.
+struct OneSeekPointsParams {
+  const uint64_t *out_off;   // n + 1
+  uint32_t n;
+  uint64_t span;             // >= 1
+  uint64_t *point_unit;      // n entries of room
+  uint32_t *n_points;
+};
+__global__ void one_seek_points_kernel(OneSeekPointsParams P);
+__global__ void one_seek_pack_kernel(const uint64_t *point_unit, uint32_t p_lo, uint32_t np, uint32_t u0,
+                                     uint64_t *r_out_off, uint64_t *r_src);
+// READ.  Locate: one thread per range (seek_locate) and +1 at pstart(first) / -1 behind last into a difference array
+// over the units.  Select: its scan marks the DECODED units; one scan of (1, size) gives each its rank and its place in
+// the dense scratch; compacted in stream order (sel_unit, sel_at).  Layout: the scan of the ranges' lengths, where
+// every range's ONE run starts in the scratch, and the ranks [r_rank_lo, r_rank_hi) of the units [pstart(first), last].
+struct OneSeekHead {         // the result words, read back in front of the arrays
+  uint64_t out_total;        // bytes of all ranges
+  uint64_t scratch_total;    // bytes of all decoded units
+  uint32_t n_sel;            // decoded units
+  uint32_t pad;
+};
+struct OneSeekParams {
+  const uint64_t *unit_bit;  // n + 1: the index, uploaded
+  const uint64_t *out_off;   // n + 1
+  const uint64_t *point_unit;  // n_points
+  uint32_t n, n_points;
+  uint64_t span;
+  uint32_t n_ranges;
+  const uint64_t *begin;     // n_ranges each (device copies of the caller's arrays)
+  const uint64_t *end;
+  int32_t *diff;             // n + 1, zeroed
+  uint32_t *rank;            // n: decoded units in front of unit k
+  uint64_t *scratch_at;      // n: decoded bytes in front of unit k
+  uint64_t *r_b, *r_len;     // per range (locate)
+  uint32_t *r_first, *r_last, *r_seg;
+  uint64_t *r_src;           // layout: where the range's run starts in the scratch
+  // what the host reads back, one block: head | r_out_off (n_ranges + 1) | r_rank_lo | r_rank_hi | sel_unit
+  OneSeekHead *head;
+  uint64_t *r_out_off;
+  uint32_t *r_rank_lo, *r_rank_hi;
+  uint32_t *sel_unit;        // n entries of room, head->n_sel used: the decoded units in stream order
+  uint64_t *sel_at;          // n + 1 entries of room: their places in the scratch, then scratch_total
+};
+__global__ void one_seek_locate_kernel(OneSeekParams P);
+__global__ void one_seek_select_kernel(OneSeekParams P);
+__global__ void one_seek_layout_kernel(OneSeekParams P);
+// A round of `count` units of the list from place i0.  one_seek_seed_kernel: per unit its SEED -- the round-local
+// place of the nearest point at or in front of it, or 0 when its segment continues from the round in front (R[0] is
+// the carried window then) -- and its piece for the decoder.  one_seek_load_kernel: the stored windows of the round's
+// points from `windows` (any alignment) into their R slots (point 0: zeros).  one_tail_kernel through
+// OneDecParams::unit_list.  one_seek_compose_kernel: the SEGMENTED scan step, dst[k] = src[k] o src[k - s] only when
+// k - s is not in front of k's seed.  one_seek_resolve_kernel: R[k + 1] = the composed function of k applied to
+// R[seed[k]], unless k + 1 is a point (its slot holds the stored window).  one_seek_check_kernel: a unit is good iff
+// its piece ends with status 0 and fills its slot exactly.
+struct OneSeekRoundParams {
+  OneSeekParams Q;
+  uint32_t i0, count;
+  const uint8_t *windows;    // device
+  uint8_t *R;                // (count + 1) * 32768
+  uint32_t *seed;            // count
+  uint64_t *p_bit_off;       // count
+  uint64_t *p_bit_end;       // count
+  uint64_t *p_dict_at;       // count
+  uint32_t *p_dict_len;      // count
+  const int32_t *d_status;   // count: what DECODE reports
+  const uint64_t *d_out_len;
+  int32_t *u_status;         // n_sel: per decoded unit
+};
+__global__ void one_seek_seed_kernel(OneSeekRoundParams S);
+__global__ void one_seek_load_kernel(OneSeekRoundParams S);
+__global__ void one_seek_compose_kernel(const uint16_t *src, uint16_t *dst, const uint32_t *seed, uint32_t count, uint32_t s);
+__global__ void one_seek_resolve_kernel(const uint16_t *F, uint8_t *R, const uint32_t *seed, uint32_t count);
+__global__ void one_seek_check_kernel(OneSeekRoundParams S);
 
 size_t inflate_simt_lds_bytes(int lanes_per_wave);  // dynamic LDS of that launch
 size_t inflate_simt_lens_bytes(uint32_t blocks);    // global scratch of that launch (InfParams::simt_lens)

@@ -1082,14 +1082,16 @@ FLATE_D void inflate_simt(const InfParams &P) {
     } else {
       // bit positions are kept relative to the dword the piece starts in (32-bit arithmetic; byte
       // alignment relative to the whole stream is preserved, as stored blocks need it)
-      const uint64_t g0 = P.bit_off[sid], g1 = P.bit_off[sid + 1];
+      const uint64_t g0 = P.bit_off[sid], g1 = P.bit_end ? P.bit_end[sid] : P.bit_off[sid + 1];
       in_base = (g0 >> 5) * 4;
       b.in = P.in + in_base;
       start_bit = (uint32_t)(g0 - 8 * in_base);
       const uint64_t rest = P.in_len - in_base;
       b.in_len = rest < (1ull << 28) ? (uint32_t)rest : (1u << 28);
-      // (closed: the pieces are a part of a longer stream -- the last one, too, ends where the next piece starts)
-      if (sid + 1 != P.n_streams || P.closed) stop_bit = (uint32_t)(g1 - 8 * in_base);  // piece < 2^28 B: host
+      // (closed: the pieces are a part of a longer stream -- the last one, too, ends where the next piece starts;
+      // bit_end: every piece carries its own end, ~0 = it runs to BFINAL)
+      const bool stops = P.bit_end ? g1 != ~0ull : (sid + 1 != P.n_streams || P.closed);
+      if (stops) stop_bit = (uint32_t)(g1 - 8 * in_base);  // piece < 2^28 B: host
     }
   }
   uint32_t dict_len = 0;          // DICT: the lane's dictionary tail, history positions -dict_len .. -1

@@ -187,15 +187,18 @@ __global__ __launch_bounds__(64) void one_tail_kernel(OneDecParams D) {
   const int lane = threadIdx.x;
   const uint32_t i = blockIdx.x;
   if (i >= D.count) return;
-  const uint32_t u = D.u0 + i;
+  const uint32_t u = D.u0 + i;  // the unit, or (unit_list) its place in the list
+  const uint32_t su = D.unit_list ? D.unit_list[u] : u;
   // Units behind a failure are not walked: their tail functions, and every window resolved from them, stay GARBAGE on
   // purpose -- one_pieces_kernel gives those units an empty slot, so nothing is decoded from such a window, and a
   // stale entry is a 15-bit index or a byte: composing it stays in bounds.  The word is read once: other workgroups of
   // this launch lower it meanwhile, but only to units of this round, which lie in front of every unit that a stale
   // value lets through.
-  if (u > uni(D.dh->first_bad)) return;
+  // A unit list is walked whole: a unit that fails there says that the index does not fit the stream, and the
+  // segments behind it start from their own stored windows.
+  if (!D.unit_list && u > uni(D.dh->first_bad)) return;
   const uint64_t raw_off = D.one->pay_off[0], raw_len = D.one->pay_end - raw_off;
-  const OneWalk w = one_walk<true>(sh, D.in + raw_off, raw_len, D.unit_max, D.unit_bit[u], D.out_off[u], lane);
+  const OneWalk w = one_walk<true>(sh, D.in + raw_off, raw_len, D.unit_max, D.unit_bit[su], D.out_off[su], lane);
   uint16_t *t = D.F[0] + (uint64_t)i * kWin;  // entry j: the byte kWin - j places in front of the unit's end
   for (uint32_t j = lane; j < (uint32_t)kWin; j += 64) t[j] = sh.win[(w.out + j) & (kWin - 1)];
   if (lane == 0) {

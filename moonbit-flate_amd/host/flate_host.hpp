@@ -1030,6 +1030,101 @@ inline Err decompress_one(Engine &e, const std::vector<uint8_t> &stream, Wrap wr
   return make_error(e, rc);
 }
 
+// What seek_index_one built: the seek index of ONE long stream, to keep beside the stream and hand to
+// decompress_one_ranges.
+struct OneSeekIndex {
+  std::vector<uint64_t> index;   // the self-describing words (include/flate_hip.h documents the layout)
+  std::vector<uint8_t> windows;  // n_points - 1 blocks of 32768 bytes
+  uint32_t n_units = 0;
+  uint32_t n_points = 0;
+  uint64_t out_bytes = 0;        // what the stream inflates to
+  uint32_t n_candidates = 0;
+  int64_t err_off = -1;          // counted from the raw stream's first byte
+  int status = 0;                // the FLATE_HIP_E_* code behind the error (0 = none)
+};
+
+// seek_index_one: the seek index of ONE long stream, a point per `span` bytes of output (0: 1 MiB;
+// FLATE_HIP_SEEK_SPAN_NONE: no windows), built on the GPU (flate_hip_inflate_one_seek_index; sized by a guess and one
+// retry, as index_one).  Errors are decompress_one's, except that the trailer is not judged; a stream that fails has
+// no index.
+inline Err seek_index_one(Engine &e, const std::vector<uint8_t> &stream, Wrap wrap, uint64_t span, OneSeekIndex &sx) {
+  if (!e.ok()) return make_error(e, e.status());
+  sx = OneSeekIndex();
+  int32_t st = 0;
+  int rc = 0;
+  uint64_t words = 16 + 2 * (stream.size() / 256 + 64) + 64, bytes = 0, got_words = 0, got_bytes = 0;
+  if (span != FLATE_HIP_SEEK_SPAN_NONE)
+    bytes = std::min<uint64_t>(4 * (uint64_t)stream.size() / (span ? span : FLATE_HIP_SEEK_SPAN_DEFAULT) + 4,
+                               stream.size() / 256 + 64) * FLATE_HIP_SEEK_WINDOW_BYTES;  // (never more points than units)
+  for (int attempt = 0; attempt < 2; ++attempt) {
+    sx.index.assign(words, 0);
+    sx.windows.assign(bytes + 1, 0);
+    rc = flate_hip_inflate_one_seek_index(e.ctx(), stream.data(), stream.size(), wrap_code(wrap), span, sx.index.data(), words,
+                                          &got_words, sx.windows.data(), bytes, &got_bytes, &sx.n_units, &sx.n_points,
+                                          &sx.out_bytes, &sx.n_candidates, &st, &sx.err_off, 0);
+    if (rc != FLATE_HIP_E_OUT_TOO_SMALL) break;
+    words = got_words, bytes = got_bytes;
+  }
+  sx.index.resize(rc == 0 ? got_words : 0);
+  sx.windows.resize(rc == 0 ? got_bytes : 0);
+  sx.status = rc;
+  if (rc == 0) return std::nullopt;
+  if (rc == FLATE_HIP_E_CORRUPT) return corrupt_input_error(sx.err_off);
+  if (rc == FLATE_HIP_E_UNEXPECTED_EOF) return err_unexpected_eof();
+  return make_error(e, rc);
+}
+
+// One range of decompress_one_ranges: positions in what the stream inflates to; it reads short at the end.
+struct OneRange {
+  uint64_t begin = 0, end = 0;
+};
+// What decompress_one_ranges found beside the bytes.
+struct OneRangesInfo {
+  std::vector<uint64_t> out_off;      // n_ranges + 1: range r is out[out_off[r], out_off[r + 1])
+  std::vector<int32_t> range_status;  // per range: 0, or the status of the first unit decoded for it that the index
+                                      // does not fit
+  uint32_t n_decoded = 0;             // the units decoded: from the seek point in front of a range up to its end
+  uint32_t bad_unit = 0xffffffffu;    // the first unit the index does not fit
+  int status = 0;                     // the FLATE_HIP_E_* code behind the error (0 = none)
+};
+
+// decompress_one_ranges: random access into ONE long stream through its seek index (flate_hip_inflate_one_ranges) --
+// the bytes of `ranges` back to back in `out`; the size comes from the call's size query.  Errors:
+// make_error(FLATE_HIP_E_INVALID) for an index that is not sound or not this stream's container and length,
+// corrupt_input_error(-1) for a stream the index was not built from or does not fit (info->range_status says which
+// ranges are exact all the same).
+inline Err decompress_one_ranges(Engine &e, const std::vector<uint8_t> &stream, Wrap wrap, const OneSeekIndex &sx,
+                                 const std::vector<OneRange> &ranges, std::vector<uint8_t> &out, OneRangesInfo *info = nullptr) {
+  if (!e.ok()) return make_error(e, e.status());
+  OneRangesInfo I;
+  const uint32_t nr = (uint32_t)ranges.size();
+  std::vector<uint64_t> begin(nr), end(nr);
+  for (uint32_t r = 0; r < nr; ++r) begin[r] = ranges[r].begin, end[r] = ranges[r].end;
+  I.out_off.assign((size_t)nr + 1, 0);
+  I.range_status.assign(nr, 0);
+  out.clear();
+  auto call = [&](uint8_t *buf, uint64_t cap) {
+    return flate_hip_inflate_one_ranges(e.ctx(), stream.data(), stream.size(), wrap_code(wrap), sx.index.data(),
+                                        sx.index.size(), sx.windows.empty() ? nullptr : sx.windows.data(), sx.windows.size(),
+                                        begin.data(), end.data(), nr, buf, cap, I.out_off.data(), I.range_status.data(),
+                                        &I.n_decoded, &I.bad_unit, 0);
+  };
+  int rc = call(nullptr, 0);  // the size query
+  if (rc == FLATE_HIP_E_OUT_TOO_SMALL) {
+    const uint64_t need = I.out_off[nr];
+    std::vector<uint8_t> buf(need + 8);
+    rc = call(buf.data(), need);
+    if (rc != FLATE_HIP_E_INVALID && rc != FLATE_HIP_E_HIP && rc != FLATE_HIP_E_INTERNAL)
+      out.assign(buf.begin(), buf.begin() + std::min<uint64_t>(I.out_off[nr], need));
+  }
+  I.status = rc;
+  if (info) *info = I;
+  if (rc == 0) return std::nullopt;
+  if (rc == FLATE_HIP_E_CORRUPT) return corrupt_input_error(-1);
+  if (rc == FLATE_HIP_E_UNEXPECTED_EOF) return err_unexpected_eof();
+  return make_error(e, rc);
+}
+
 // One range of decompress_bgzf_ranges: positions in the file's uncompressed bytes, or -- virtual_offsets -- BGZF
 // virtual offsets (coffset << 16 | uoffset, as BAM, tabix and CSI indexes store them).
 struct BgzfRange {
