@@ -716,7 +716,8 @@ int flate_hip_bgzf_read_ranges(flate_hip_ctx *ctx, const uint8_t *in, uint64_t i
  *   The slot-write guarantees of flate_hip_inflate_batch hold.  With profiling on, FLATE_HIP_STAGE_INFLATE and
  *   FLATE_HIP_STAGE_CHECKSUM are the decode pass's, as in flate_hip_bgzf_read: the size-only pass of the discovery is in
  *   neither.
- *   Out of scope: zero or garbage padding behind the last member; members of M bytes or more; running a clipped
+ *   Out of scope: zero or garbage padding behind the last member; members of M bytes or more (flate_hip_gzfile_read
+ *   reads them); running a clipped
  *   candidate again unclipped; caching the index across calls; salvage inside flate_hip_gzip_read; zlib or raw
  *   concatenations. */
 int flate_hip_gzip_index(flate_hip_ctx *ctx, const uint8_t *in, uint64_t in_len, uint64_t index_cap,
@@ -801,8 +802,8 @@ int flate_hip_gzip_read(flate_hip_ctx *ctx, const uint8_t *in, uint64_t in_len, 
  *   workgroup.  Profiling: FLATE_HIP_STAGE_INFLATE is DECODE (of several rounds the last),
  *   FLATE_HIP_STAGE_CHECKSUM is VERIFY; FIND, PROBE, LINK, TAIL and COMPOSE are counted in no stage.
  *   Out of scope: finding stored or fixed block starts (streams made of them stay serial inside one unit); fusing
- *   PROBE with TAIL; routing long members of flate_hip_gzip_read here; multi-member input; caching the index across
- *   calls (the seek index below is what a caller keeps). */
+ *   PROBE with TAIL; routing long members of flate_hip_gzip_read here; multi-member input (flate_hip_gzfile_read);
+ *   caching the index across calls (the seek index below is what a caller keeps). */
 int flate_hip_inflate_one(flate_hip_ctx *ctx, const uint8_t *in, uint64_t in_len, uint32_t wrap, uint8_t *out,
                           uint64_t out_cap, uint64_t *out_len, int32_t *status, int64_t *err_off, uint32_t *n_units,
                           uint32_t *n_candidates, uint32_t flags);
@@ -914,6 +915,90 @@ int flate_hip_inflate_one_ranges(flate_hip_ctx *ctx, const uint8_t *in, uint64_t
                                  uint64_t windows_bytes, const uint64_t *begin, const uint64_t *end, uint32_t n_ranges,
                                  uint8_t *out, uint64_t out_cap, uint64_t *out_off, int32_t *range_status,
                                  uint32_t *n_decoded, uint32_t *bad_unit, uint32_t flags);
+
+/* -- Any gzip file: units found across member boundaries ------------------------------
+ * RFC 1952 makes a gzip file a series of members, and everyday files are a few long members, or long and short ones
+ * mixed (rotated logs concatenated after compression, pigz -i, dumps appended to).  WHICH CALL FOR WHICH FILE:
+ * flate_hip_gzip_read for files of many small members (every member serial on one wavefront, no search over bits: the
+ * fastest call there, members below "gzip_member_max" only); flate_hip_inflate_one for exactly one member;
+ * flate_hip_gzfile_read for everything else and for files of unknown make-up: it cuts EVERY member into the units of
+ * flate_hip_inflate_one_index and decodes them in parallel, and pays the search over every bit for it.  The link rule
+ * between members is written once, csrc/gzfile_rule.h; the kernels are csrc/gzfile_kernels.hip.
+ *
+ * THE WALK that defines every result.  in[0, in_len) is the file; BITS ARE COUNTED FROM THE FILE'S FIRST BYTE.  p = 0.
+ * p == in_len: success (in_len == 0: zero members, zero units, FLATE_HIP_OK).  The header rule at p is
+ * flate_hip_gzip_index's over in[p, in_len), never clipped by "gzip_member_max"; no header at p: FLATE_HIP_E_CORRUPT,
+ * the chain breaks at p.  The member's raw stream starts at byte r = p + header length and the serial decoder reads it
+ * over [r, in_len - 8) -- the last 8 bytes of a file can only be a trailer; a stream that needs more is
+ * FLATE_HIP_E_UNEXPECTED_EOF.  A non-zero status ends the walk in this member.  Otherwise b is the bit behind the final
+ * block, the member is in[p, e) with e = ceil(b / 8) + 8, and p = e.  Anything behind the last member, zero bytes
+ * included, is FLATE_HIP_E_CORRUPT at its offset.
+ * UNITS are flate_hip_inflate_one_index's, per member: one starts at bit 8 r of every member whatever block type is
+ * there, and at every dynamic block header the serial decode of that member reaches; every member has at least one
+ * unit.  Unit k starts a member iff k == 0 or the unit in front of it on the chain ended with BFINAL.  HISTORY NEVER
+ * CROSSES A MEMBER: unit k of a member whose first unit is f has min(32768, out_off[k] - out_off[f] + bytes produced)
+ * bytes of history, and a distance beyond that is FLATE_HIP_E_CORRUPT at the serial offset, also when an earlier
+ * member's output lies right in front of it in out.  Limits are per unit ("one_unit_max"); there is no per-member one.
+ *
+ * flate_hip_gzfile_index (discovery only).  Conventions: flate_hip_inflate_one_index's and flate_hip_gzip_index's.  The
+ * four index arrays are HOST arrays; unit_bit / out_off (index_cap entries) and member_off / member_unit (member_cap
+ * entries) are each both given or both NULL (both NULL: a count query); a pair that is too small is
+ * FLATE_HIP_E_OUT_TOO_SMALL with every count set.  flags: FLATE_HIP_DEVICE_PTRS or 0, anything else is
+ * FLATE_HIP_E_INVALID before any HIP call.  Nothing outside in[0, in_len) is read, at any alignment of in; nothing is
+ * written to device memory the caller owns.  n_candidates, bad_member, err_off and stream_err_off may be NULL.
+ * On success: unit_bit[0 .. n] (unit_bit[n]: the bit behind the last member's final block; a unit ends where the next
+ * one starts, a member's last unit with its final block), out_off[0 .. n] (the exclusive prefix sum of what the units
+ * inflate to; *out_bytes = out_off[n]), member_off[0 .. m] (file offsets, member_off[m] = in_len), member_unit[0 .. m]
+ * (the first unit of each member, member_unit[m] = n); *status = 0, *bad_member = 0xffffffff, both offsets -1.
+ * A broken chain: *status and the return value are the walk's code; *bad_member = the whole good members in front;
+ * *err_off = the file offset where the failing member starts, or where no member could start; *stream_err_off = the
+ * serial decoder's error offset counted from that member's raw stream's first byte (-1 for
+ * FLATE_HIP_E_UNEXPECTED_EOF and FLATE_HIP_E_TOO_LARGE, and when no header was found); *n_units = the good units in
+ * front of the failing one, those of the failing member included; *n_members = *bad_member; *out_bytes = 0; the good
+ * prefix of all four arrays is still filled if it fits (unit_bit[n_units]: where the failing unit starts;
+ * member_off[n_members] = *err_off; member_unit[n_members]: the failing member's first unit, or n_units when no header
+ * was found).  The verdict is history-free and trailer-free, exactly as flate_hip_inflate_one_index's is.
+ * *n_candidates: the nodes probed -- every bit offset that passes the dynamic-header rule (bit 0 included) and one per
+ * byte offset that passes the header rule.
+ *
+ * flate_hip_gzfile_read: what zcat gives, the members' bytes back to back.  The total is known after discovery: above
+ * out_cap it is FLATE_HIP_E_OUT_TOO_SMALL with *out_len = the size needed and nothing decoded (out == NULL with
+ * out_cap == 0 is the size query).  Host pointers: the file is uploaded once and out[0, *out_len) downloaded once;
+ * device pointers: nothing outside out[0, *out_len) is written.  THE VERDICT, in this order.  (1) A chain that breaks
+ * (a header, a decode error, a unit too large, a distance in front of its member -- found by TAIL, reported at its
+ * serial offset): *status, *bad_member, *err_off and *stream_err_off as in the index call; delivered are every good
+ * member in front, whole, and the failing member's bytes in front of its failure (a unit that is too large delivers
+ * nothing of itself); nothing behind the failure is written; *out_len is that count; no trailer is judged.  (2) Chain
+ * good, a trailer wrong: every member is decoded and delivered, *out_len is the total, *status = FLATE_HIP_E_CORRUPT
+ * for the first member in file order whose CRC-32 or ISIZE (mod 2^32) is not its trailer's, *bad_member its index,
+ * *err_off its file offset, *stream_err_off that member's length (flate_hip_inflate_batch_framed's convention).
+ * (3) Otherwise 0, 0xffffffff, -1, -1.  The return value is *status when that is not 0.
+ *   How, all on the ctx's stream, no host pass over file bytes, no kernel waits for another workgroup.  CANDIDATES:
+ *   list A, flate_hip_inflate_one_index's FIND over the whole file (decoys inside headers and trailers are candidates
+ *   like any other); list B, flate_hip_gzip_index's header pass, each hit a node at bit 8 * (p + header length); one
+ *   read-back of the two counts.  Both lists stay sorted in one node array; a bit that is in both is two nodes, and
+ *   the path takes the one its predecessor names.  PROBE as in flate_hip_inflate_one_index, limited to
+ *   [.., in_len - 8).  LINK: a node that stops in front of a dynamic header searches list A; one that ends with BFINAL
+ *   takes THE HOP (csrc/gzfile_rule.h): e = ceil(b / 8) + 8; e == in_len: the terminal node; no header at e: the dead
+ *   node, FLATE_HIP_E_CORRUPT at e; else the list B node of the header at e.  RANK, the out-size scan and the tail
+ *   probe as there; a second scan over the path's "starts a member" marks gives member_unit and member_off.  DECODE in
+ *   rounds of "one_round_units": TAIL with ooff = out_off[k] - out_off[first unit of k's member], the SEGMENTED compose
+ *   / resolve of the seek index with every member's first unit as a seed (its dict_len is 0), pieces through the
+ *   lane-per-stream dictionary decoder with a per-piece end.  VERIFY: one checksum launch planned over the members'
+ *   output ranges, a thread per trailer, an ordered min.  Profiling: FLATE_HIP_STAGE_INFLATE is DECODE (of several
+ *   rounds the last), FLATE_HIP_STAGE_CHECKSUM is VERIFY; the rest is counted in no stage.
+ *   Out of scope: zlib or raw concatenations; a seek index or ranges over a multi-member file; routing
+ *   flate_hip_gzip_read or flate_hip_inflate_one here automatically; choosing per member between the serial and the
+ *   unit decoder; stored or fixed block starts as units; caching across calls. */
+int flate_hip_gzfile_index(flate_hip_ctx *ctx, const uint8_t *in, uint64_t in_len, uint64_t index_cap,
+                           uint64_t *unit_bit, uint64_t *out_off, uint64_t member_cap, uint64_t *member_off,
+                           uint64_t *member_unit, uint32_t *n_units, uint32_t *n_members, uint64_t *out_bytes,
+                           uint32_t *n_candidates, int32_t *status, uint32_t *bad_member, int64_t *err_off,
+                           int64_t *stream_err_off, uint32_t flags);
+int flate_hip_gzfile_read(flate_hip_ctx *ctx, const uint8_t *in, uint64_t in_len, uint8_t *out, uint64_t out_cap,
+                          uint64_t *out_len, uint32_t *n_members, uint32_t *n_units, uint32_t *n_candidates,
+                          int32_t *status, uint32_t *bad_member, int64_t *err_off, int64_t *stream_err_off,
+                          uint32_t flags);
 
 /* -- ZIP archives ----------------------------------------------------------------
  * The everyday container of a batch of independent DEFLATE streams (.zip, .npz, .jar, .whl, .docx; PKWARE APPNOTE

@@ -173,6 +173,23 @@ inline int one_args(const uint8_t *in, uint64_t in_len, uint32_t wrap, const uin
   return (flags & ~FLATE_HIP_DEVICE_PTRS) ? FLATE_HIP_E_INVALID : FLATE_HIP_OK;
 }
 
+// ---- a gzip file of any members (flate_hip_gzfile_index / _read) ----
+
+// unit_bit / out_off and member_off / member_unit: each pair comes together or not at all (both absent: the count query)
+inline int gzfile_index_args(const uint8_t *in, uint64_t in_len, const uint64_t *unit_bit, const uint64_t *out_off,
+                             const uint64_t *member_off, const uint64_t *member_unit, const uint32_t *n_units,
+                             const uint32_t *n_members, const uint64_t *out_bytes, const int32_t *status, uint32_t flags) {
+  if (!n_units || !n_members || !out_bytes || !status || (in_len && !in)) return FLATE_HIP_E_INVALID;
+  if ((!unit_bit != !out_off) || (!member_off != !member_unit)) return FLATE_HIP_E_INVALID;
+  return (flags & ~FLATE_HIP_DEVICE_PTRS) ? FLATE_HIP_E_INVALID : FLATE_HIP_OK;
+}
+// out == NULL with out_cap == 0 is the size query
+inline int gzfile_read_args(const uint8_t *in, uint64_t in_len, const uint8_t *out, uint64_t out_cap,
+                            const uint64_t *out_len, const int32_t *status, uint32_t flags) {
+  if (!out_len || !status || (in_len && !in) || (out_cap && !out)) return FLATE_HIP_E_INVALID;
+  return (flags & ~FLATE_HIP_DEVICE_PTRS) ? FLATE_HIP_E_INVALID : FLATE_HIP_OK;
+}
+
 // ---- the seek index of one long stream (flate_hip_inflate_one_seek_index / _ranges; seek_index_rule.h) ----
 
 // the build: index and windows are each a buffer with its capacity, or NULL with 0 (both NULL: the size query)

@@ -14,6 +14,7 @@
 #include "api_checks.h"
 #include "bgzf_range_rule.h"
 #include "bgzf_rule.h"
+#include "gzfile_rule.h"
 #include "gzip_rule.h"
 #include "window_compose.h"
 
@@ -1824,6 +1825,354 @@ int flate_hip_inflate_one_ranges(flate_hip_ctx *c, const uint8_t *in, uint64_t i
       return st[nxt[0]];
     }
     return FLATE_HIP_OK;
+  } catch (const std::exception &e) {
+    c->hip_err = e.what();
+    return FLATE_HIP_E_INTERNAL;
+  }
+}
+
+}  // extern "C"
+
+// ---- a gzip file of any members: the units of all members as one chain (gzfile_kernels.hip, gzfile_rule.h) ----
+namespace {
+
+// The discovery over the file d_in[0, in_len) (DEVICE memory, in_len != 0) on the ctx's stream: the two count passes
+// and their scans, ONE read-back of the two candidate counts, then the fills, the B nodes' bits, the probe of every
+// node, link, rounds, finish, out-scan, the member scan, the tail probe, the member words and ONE read-back of the
+// result words H / G -- with member_out (the members' places in the output, n_b + 2 entries of which G.n_members + 1
+// count) when `mout` is given.  The index stays on the device (P).  Counted in no profiling stage.
+int gzfile_discover(flate_hip_ctx *c, const uint8_t *d_in, uint64_t in_len, OneHead &H, GzFileHead &G, GzFileParams &P,
+                    std::vector<uint64_t> *mout) {
+  int rc;
+  P = GzFileParams{};
+  OneParams PA{};
+  GzipParams PB{};
+  ChainParams &C = P.O.C;
+  uint32_t n_tiles = 0;
+  if ((rc = tiles_for(d_in, 0, in_len, &n_tiles))) return rc;
+  OneHead *head_a;
+  BgzfHead *head_b;
+  rc = carve(c, c->d_gzfile_tiles, [&](Carve &k) {
+    k.take(P.O.head, 1);
+    k.take(P.gh, 1);
+    k.take(P.O.one, 1);
+    k.take(head_a, 1);
+    k.take(head_b, 1);
+    k.take(PA.C.tile_cnt, (size_t)n_tiles + 1);
+    k.take(PB.C.tile_cnt, (size_t)n_tiles + 1);
+  });
+  if (rc) return rc;
+  C.in = PA.C.in = PB.C.in = d_in;
+  C.in_len = PA.C.in_len = PB.C.in_len = in_len;
+  C.n_tiles = PA.C.n_tiles = PB.C.n_tiles = n_tiles;
+  C.head = &P.O.head->h;
+  P.O.unit_max = PA.unit_max = c->one_unit_max;
+  PA.C.head = &head_a->h;
+  PA.head = head_a;
+  PA.one = P.O.one;
+  PB.C.head = head_b;
+  PB.member_max = ~0ull;  // a member's range is never clipped
+  hipLaunchKernelGGL(gzfile_init_kernel, dim3(1), dim3(64), 0, c->stream, P.O.one, in_len);
+  hipLaunchKernelGGL(one_count_kernel, dim3(n_tiles), dim3(256), 0, c->stream, PA);
+  hipLaunchKernelGGL(chain_scan_kernel, dim3(1), dim3(1024), 0, c->stream, PA.C);
+  hipLaunchKernelGGL(gzip_count_kernel, dim3(n_tiles), dim3(256), 0, c->stream, PB);
+  hipLaunchKernelGGL(chain_scan_kernel, dim3(1), dim3(1024), 0, c->stream, PB.C);
+  HIP_TRY(c, hipGetLastError());
+  OneHead HA{};
+  BgzfHead HB{};
+  HIP_TRY(c, hipMemcpyAsync(&HA, head_a, sizeof HA, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(&HB, head_b, sizeof HB, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  const uint32_t na = HA.h.n_cand, nb = HB.n_cand;
+  if ((uint64_t)na + nb > 0x7ffffff0ull) return FLATE_HIP_E_TOO_LARGE;  // (the counts saturate at 2^32 - 1)
+  const uint32_t cap = na + nb;
+  if ((rc = chain_size(C, cap)) || (rc = chain_size(PA.C, na)) || (rc = chain_size(PB.C, nb))) return rc;
+  P.n_a = na;
+  P.n_b = nb;
+
+  const size_t n = cap;
+  uint64_t *hdr_off;
+  rc = carve(c, c->d_gzfile, [&](Carve &k) {
+    k.take(C.cand_off, n);
+    k.take(hdr_off, (size_t)nb + 1);
+    k.take(PB.cand_end, nb);
+    k.take(P.O.probe, n);
+    k.take(C.jump[0], n + 2);
+    k.take(C.jump[1], n + 2);
+    k.take(C.path, C.path_len);
+    k.take(P.O.usize, n);
+    k.take(C.member_off, n + 1);
+    k.take(C.out_off, n + 1);
+    k.take(P.u_start, n + 1);
+    k.take(P.u_final, n);
+    k.take(P.u_member, n + 1);
+    k.take(P.rel_off, n + 1);
+    k.take(P.member_off, (size_t)nb + 2);
+    k.take(P.member_unit, (size_t)nb + 2);
+    k.take(P.member_out, (size_t)nb + 2);
+  });
+  if (rc) return rc;
+  PA.C.cand_off = C.cand_off;
+  PB.C.cand_off = hdr_off;
+  P.hdr_off = hdr_off;
+  hipLaunchKernelGGL(one_fill_kernel, dim3(n_tiles), dim3(256), 0, c->stream, PA);
+  if (nb) {
+    hipLaunchKernelGGL(gzip_fill_kernel, dim3(n_tiles), dim3(256), 0, c->stream, PB);
+    hipLaunchKernelGGL(gzfile_bits_kernel, dim3((nb + 255) / 256), dim3(256), 0, c->stream, P);
+  }
+  if (cap) hipLaunchKernelGGL(one_probe_kernel, dim3(cap), dim3(64), 0, c->stream, P.O, 0u);
+  const uint32_t node_blocks = (uint32_t)(((uint64_t)cap + 2 + 255) / 256);
+  hipLaunchKernelGGL(gzfile_link_kernel, dim3(node_blocks), dim3(256), 0, c->stream, P);
+  for (uint32_t j = 0; (1u << j) < C.path_len; ++j)
+    hipLaunchKernelGGL(chain_round_kernel, dim3(node_blocks), dim3(256), 0, c->stream, C, j);
+  hipLaunchKernelGGL(gzfile_finish_kernel, dim3((C.path_len + 255) / 256), dim3(256), 0, c->stream, P);
+  hipLaunchKernelGGL(one_out_scan_kernel, dim3(1), dim3(1024), 0, c->stream, P.O);
+  hipLaunchKernelGGL(gzfile_members_kernel, dim3(1), dim3(1024), 0, c->stream, P);
+  hipLaunchKernelGGL(one_probe_kernel, dim3(1), dim3(64), 0, c->stream, P.O, 1u);
+  hipLaunchKernelGGL(gzfile_rel_kernel, dim3(node_blocks), dim3(256), 0, c->stream, P);
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipMemcpyAsync(&H, P.O.head, sizeof H, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(&G, P.gh, sizeof G, hipMemcpyDeviceToHost, c->stream));
+  if (mout) {
+    mout->assign((size_t)nb + 2, 0);
+    HIP_TRY(c, hipMemcpyAsync(mout->data(), P.member_out, ((size_t)nb + 2) * 8, hipMemcpyDeviceToHost, c->stream));
+  }
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  if (G.n_members > nb || H.h.n_members > cap) return FLATE_HIP_E_INTERNAL;
+  return FLATE_HIP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int flate_hip_gzfile_index(flate_hip_ctx *c, const uint8_t *in, uint64_t in_len, uint64_t index_cap, uint64_t *unit_bit,
+                           uint64_t *out_off, uint64_t member_cap, uint64_t *member_off, uint64_t *member_unit,
+                           uint32_t *n_units, uint32_t *n_members, uint64_t *out_bytes, uint32_t *n_candidates,
+                           int32_t *status, uint32_t *bad_member, int64_t *err_off, int64_t *stream_err_off,
+                           uint32_t flags) {
+  // every check before any HIP call
+  if (!c) return FLATE_HIP_E_INVALID;
+  int rc = gzfile_index_args(in, in_len, unit_bit, out_off, member_off, member_unit, n_units, n_members, out_bytes, status,
+                             flags);
+  if (rc) return rc;
+  c->hip_err.clear();
+  *n_units = 0, *n_members = 0, *out_bytes = 0, *status = 0;
+  if (n_candidates) *n_candidates = 0;
+  if (bad_member) *bad_member = 0xffffffffu;
+  if (err_off) *err_off = -1;
+  if (stream_err_off) *stream_err_off = -1;
+  try {
+    OneHead H{};
+    GzFileHead G{};
+    GzFileParams P{};
+    G.err_off = G.stream_err_off = -1;
+    if (in_len) {  // (no bytes: zero members, zero units)
+      const uint8_t *d_in = nullptr;
+      if ((rc = stage_input(c, in, in_len, flags, &d_in))) return rc;
+      if ((rc = gzfile_discover(c, d_in, in_len, H, G, P, nullptr))) return rc;
+    }
+    *n_units = H.h.n_members;
+    *n_members = G.n_members;
+    if (n_candidates) *n_candidates = H.h.n_cand;
+    *status = H.h.rc;
+    *out_bytes = H.h.out_bytes;  // (0 on a broken chain)
+    if (H.h.rc) {
+      if (bad_member) *bad_member = G.n_members;
+      if (err_off) *err_off = G.err_off;
+      if (stream_err_off) *stream_err_off = G.stream_err_off;
+    }
+    // the index -- of a broken chain its good prefix, where that fits: the verdict is the walk's either way
+    const uint64_t ue = (uint64_t)H.h.n_members + 1, me = (uint64_t)G.n_members + 1;
+    const bool u_fits = unit_bit && index_cap >= ue, m_fits = member_off && member_cap >= me;
+    if (in_len) {
+      if (u_fits) {
+        HIP_TRY(c, hipMemcpyAsync(unit_bit, P.O.C.member_off, ue * 8, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(out_off, P.O.C.out_off, ue * 8, hipMemcpyDeviceToHost, c->stream));
+      }
+      if (m_fits) {
+        HIP_TRY(c, hipMemcpyAsync(member_off, P.member_off, me * 8, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(member_unit, P.member_unit, me * 8, hipMemcpyDeviceToHost, c->stream));
+      }
+      if (u_fits || m_fits) HIP_TRY(c, hipStreamSynchronize(c->stream));
+    } else {
+      if (u_fits) unit_bit[0] = 0, out_off[0] = 0;
+      if (m_fits) member_off[0] = 0, member_unit[0] = 0;
+    }
+    if (H.h.rc) return H.h.rc;
+    return ((unit_bit && !u_fits) || (member_off && !m_fits)) ? FLATE_HIP_E_OUT_TOO_SMALL : FLATE_HIP_OK;
+  } catch (const std::exception &e) {  // (out of host memory)
+    c->hip_err = e.what();
+    return FLATE_HIP_E_INTERNAL;
+  }
+}
+
+// The whole call: discovery, then flate_hip_inflate_one's rounds over the units of all members -- TAIL with the
+// member-relative offsets, the SEGMENTED compose / resolve with every member's first unit as a seed, DECODE straight
+// into out + out_off[k] with a history that never crosses a member --, then one checksum launch planned over the
+// members' output ranges, the trailers and the verdict.
+int flate_hip_gzfile_read(flate_hip_ctx *c, const uint8_t *in, uint64_t in_len, uint8_t *out, uint64_t out_cap,
+                          uint64_t *out_len, uint32_t *n_members, uint32_t *n_units, uint32_t *n_candidates,
+                          int32_t *status, uint32_t *bad_member, int64_t *err_off, int64_t *stream_err_off,
+                          uint32_t flags) {
+  // every check before any HIP call
+  if (!c) return FLATE_HIP_E_INVALID;
+  int rc = gzfile_read_args(in, in_len, out, out_cap, out_len, status, flags);
+  if (rc) return rc;
+  c->hip_err.clear();
+  *out_len = 0, *status = 0;
+  if (n_members) *n_members = 0;
+  if (n_units) *n_units = 0;
+  if (n_candidates) *n_candidates = 0;
+  if (bad_member) *bad_member = 0xffffffffu;
+  if (err_off) *err_off = -1;
+  if (stream_err_off) *stream_err_off = -1;
+  if (in_len == 0) return FLATE_HIP_OK;
+  try {
+    const bool dev = (flags & FLATE_HIP_DEVICE_PTRS) != 0;
+    const uint8_t *d_in = nullptr;
+    if ((rc = stage_input(c, in, in_len, flags, &d_in))) return rc;
+    OneHead H{};
+    GzFileHead G{};
+    GzFileParams P{};
+    std::vector<uint64_t> mout;
+    if ((rc = gzfile_discover(c, d_in, in_len, H, G, P, &mout))) return rc;
+    if (n_members) *n_members = G.n_members;
+    if (n_units) *n_units = H.h.n_members;
+    if (n_candidates) *n_candidates = H.h.n_cand;
+    // the units to decode: the good ones and, so that the bytes in front of an error are delivered, a unit that fails
+    // behind its header; the total is known here
+    const uint32_t n_dec = H.h.n_members + (H.fail_unit ? 1u : 0u);
+    const uint64_t total = H.prefix_bytes + (H.fail_unit ? H.fail_out : 0ull);
+    *out_len = total;
+    if (total > out_cap) return FLATE_HIP_E_OUT_TOO_SMALL;  // (nothing is decoded; out == NULL: the size query)
+    uint8_t *d_out = out;
+    if (!dev) {
+      if ((rc = ensure(c, c->d_out, total + 16))) return rc;
+      d_out = (uint8_t *)c->d_out.p;
+    }
+    const uint32_t n_mem = H.h.rc == 0 ? G.n_members : 0u;  // the members whose trailers are judged
+    const uint32_t per_round = n_dec < c->one_round_units ? (n_dec ? n_dec : 1u) : c->one_round_units;
+    const size_t fentries = (size_t)per_round * kWinEntries;
+    GzFileDecParams GD{};
+    OneDecParams &D = GD.D;
+    uint32_t *d_sums;
+    int32_t *d_ds;
+    uint64_t *d_dl;
+    int64_t *d_de;
+    rc = carve(c, c->d_one_dec, [&](Carve &k) {
+      k.take(D.dh, 1);
+      k.take(D.F[0], fentries);
+      k.take(D.F[1], fentries);
+      k.take(D.R, ((size_t)per_round + 1) * kWinEntries);
+      k.take(D.status, (size_t)n_dec + 1);
+      k.take(D.err_off, (size_t)n_dec + 1);
+      k.take(D.produced, (size_t)n_dec + 1);
+      k.take(D.p_out_off, (size_t)per_round + 1);
+      k.take(D.p_dict_at, per_round);
+      k.take(D.p_dict_len, per_round);
+      k.take(d_ds, per_round);
+      k.take(d_dl, per_round);
+      k.take(d_de, per_round);
+    });
+    if (rc) return rc;
+    rc = carve(c, c->d_gzfile_dec, [&](Carve &k) {
+      k.take(GD.v, 1);
+      k.take(GD.seed, per_round);
+      k.take(GD.p_bit_off, per_round);
+      k.take(GD.p_bit_end, per_round);
+      k.take(d_sums, (size_t)n_mem + 1);
+    });
+    if (rc) return rc;
+    D.in = d_in;
+    D.one = P.O.one;
+    D.unit_bit = P.O.C.member_off;
+    D.out_off = P.O.C.out_off;
+    D.total = total;
+    D.unit_max = c->one_unit_max;
+    D.d_status = d_ds;
+    D.d_out_len = d_dl;
+    D.head = P.O.head;
+    D.wrap = FLATE_HIP_WRAP_GZIP;
+    D.in_len = in_len;
+    GD.P = P;
+    GD.n_good = H.h.n_members;
+    GD.n_members = n_mem;
+    GD.sums = d_sums;
+    HIP_TRY(c, hipMemsetAsync(D.dh, 0xff, sizeof(OneDecHead), c->stream));     // first_bad, decode_bad: none
+    HIP_TRY(c, hipMemsetAsync(GD.v, 0xff, sizeof(GzFileVerdict), c->stream));  // bad_trailer: none
+    HIP_TRY(c, hipMemsetAsync(D.R, 0, kWinEntries, c->stream));                // in front of the file: zeros
+    bool used[FLATE_HIP_STAGE_COUNT] = {false, false, false, false};
+    for (uint32_t u0 = 0; u0 < n_dec; u0 += per_round) {
+      D.u0 = u0;
+      D.count = n_dec - u0 < per_round ? n_dec - u0 : per_round;
+      const uint32_t unit_blocks = (D.count + 1u + 255u) / 256u;
+      const uint32_t entry_blocks = (uint32_t)(((uint64_t)D.count * kWinEntries + 255) / 256);
+      OneDecParams T = D;  // TAIL: a unit's history is what its own member has produced in front of it
+      T.out_off = P.rel_off;
+      hipLaunchKernelGGL(one_tail_kernel, dim3(D.count), dim3(64), 0, c->stream, T);
+      hipLaunchKernelGGL(gzfile_pieces_kernel, dim3(unit_blocks), dim3(256), 0, c->stream, GD);
+      int cur = 0;
+      for (uint32_t s = 1; s < D.count; s <<= 1, cur ^= 1)
+        hipLaunchKernelGGL(one_seek_compose_kernel, dim3(entry_blocks), dim3(256), 0, c->stream, D.F[cur], D.F[cur ^ 1],
+                           GD.seed, D.count, s);
+      hipLaunchKernelGGL(one_seek_resolve_kernel, dim3(entry_blocks), dim3(256), 0, c->stream, D.F[cur], D.R, GD.seed,
+                         D.count);
+      // DECODE: the round's units as pieces with dictionaries and their own ends, through the lane-per-stream decoder
+      InfParams I{};
+      I.in = d_in;
+      I.in_len = H.raw_len;
+      I.bit_off = GD.p_bit_off;
+      I.bit_end = GD.p_bit_end;
+      I.n_streams = D.count;
+      I.out = d_out;
+      I.out_off = D.p_out_off;
+      I.out_len = d_dl;
+      I.status = d_ds;
+      I.err_off = d_de;
+      I.dict_buf = D.R;
+      I.dict_at = D.p_dict_at;
+      I.dict_len = D.p_dict_len;
+      if ((rc = launch_decoders(c, inflate_route_units(c->inflate, c->num_cus, D.count), I, true))) return rc;  // (of several rounds the stage's time is the last one's)
+      hipLaunchKernelGGL(one_check_kernel, dim3(unit_blocks), dim3(256), 0, c->stream, D);
+      used[FLATE_HIP_STAGE_INFLATE] = true;
+      HIP_TRY(c, hipGetLastError());
+      // the window behind the round's last unit seeds the next round (a round that starts with a member reads none of it)
+      if (u0 + D.count < n_dec)
+        HIP_TRY(c, hipMemcpyAsync(D.R, D.R + (size_t)D.count * kWinEntries, kWinEntries, hipMemcpyDeviceToDevice, c->stream));
+    }
+    bool ctl = false;
+    if (n_mem) {  // VERIFY: one launch planned over the members' output ranges, then a thread per trailer
+      if (mout.size() < (size_t)n_mem + 1) return FLATE_HIP_E_INTERNAL;
+      if ((rc = ctl_begin(c, checksum_ctl_up_bytes(mout.data(), n_mem), 0))) return rc;
+      ctl = true;
+      if ((rc = checksum_device(c, d_out, mout.data(), n_mem, FLATE_HIP_CHECKSUM_CRC32, d_sums, FLATE_HIP_STAGE_CHECKSUM)))
+        return rc;
+      used[FLATE_HIP_STAGE_CHECKSUM] = true;
+      hipLaunchKernelGGL(gzfile_trailer_kernel, dim3((n_mem + 255) / 256), dim3(256), 0, c->stream, GD);
+    }
+    hipLaunchKernelGGL(gzfile_verdict_kernel, dim3(1), dim3(64), 0, c->stream, GD);
+    HIP_TRY(c, hipGetLastError());
+    GzFileVerdict V{};
+    HIP_TRY(c, hipMemcpyAsync(&V, GD.v, sizeof V, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (ctl) ctl_finish(c);
+    if (V.out_len > total) return FLATE_HIP_E_INTERNAL;
+    *out_len = V.out_len;
+    if (!dev && V.out_len) {  // the result comes down once
+      HIP_TRY(c, hipMemcpyAsync(out, d_out, V.out_len, hipMemcpyDeviceToHost, c->stream));
+      HIP_TRY(c, hipStreamSynchronize(c->stream));
+    }
+    if (c->profiling && (rc = collect_timing(c, used))) return rc;
+    if (n_members) *n_members = V.n_members;
+    if (n_units) *n_units = V.n_units;
+    *status = V.status;
+    if (V.status) {
+      if (bad_member) *bad_member = V.bad_member;
+      if (err_off) *err_off = V.err_off;
+      if (stream_err_off) *stream_err_off = V.stream_err_off;
+    }
+    return V.status;
   } catch (const std::exception &e) {
     c->hip_err = e.what();
     return FLATE_HIP_E_INTERNAL;

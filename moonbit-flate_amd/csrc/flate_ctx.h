@@ -95,6 +95,9 @@ struct flate_hip_ctx {
   // OneSeekParams), carved from one buffer; a host caller's windows; the dense scratch the selected units are decoded
   // into.  Both calls carve their rounds' arrays from d_one_dec.
   DevBuf d_one_seek, d_one_seek_win, d_one_seek_dense;
+  // flate_hip_gzfile_index / _read: the two count passes' words and tile counts (sized before the candidates are
+  // counted), the chain's arrays (GzFileParams), and the read's member-wise arrays beside d_one_dec's
+  DevBuf d_gzfile_tiles, d_gzfile, d_gzfile_dec;
   DevBuf d_zip_names, d_zip_name_off, d_zip_whead, d_zip_end, d_zip_dir, d_zip_sel;
   hipStream_t guest_stream = nullptr;
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;

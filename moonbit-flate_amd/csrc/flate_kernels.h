@@ -656,6 +656,69 @@ __global__ void one_seek_compose_kernel(const uint16_t *src, uint16_t *dst, cons
 __global__ void one_seek_resolve_kernel(const uint16_t *F, uint8_t *R, const uint32_t *seed, uint32_t count);
 __global__ void one_seek_check_kernel(OneSeekRoundParams S);
 
+// A gzip FILE of any members, long ones included (gzfile_kernels.hip; flate_hip_gzfile_index / _read; the rule:
+// gzfile_rule.h).  The units of ALL members form one chain over the file's bits: the raw stream of OneParams is
+// in[0, in_len - 8), so every bit and every error offset is counted from the file's first byte.  The nodes are two
+// lists in one array: A, the n_a bit offsets of one_count_kernel / one_fill_kernel (the dynamic-header rule at every
+// bit of the file; sorted), then B, one node per byte offset that passes the gzip header rule (gzip_count_kernel /
+// gzip_fill_kernel without a clip; hdr_off sorted), at the bit behind that header.  one_probe_kernel probes every node.
+// A node that stops in front of a dynamic header links into A as the units of one stream do; one that ends with
+// BFINAL takes THE HOP into B; so the first unit of a member is always a B node and every other unit an A node, and a
+// bit that is in both lists is two nodes of which the path takes the one its predecessor names.
+struct GzFileHead {        // the discovery's verdict, read back as one block with the OneHead in front of it
+  int64_t err_off;         // where the failing member starts, or where no member could start; -1
+  int64_t stream_err_off;  // the serial decoder's offset, counted from that member's raw stream; -1
+  uint32_t n_members;      // whole good members
+  uint32_t no_header;      // the chain broke where a header had to be
+  uint32_t pad[2];
+};
+struct GzFileParams {
+  OneParams O;             // the chain: O.C.cap = n_a + n_b nodes, O.C.member_off = unit_bit
+  uint32_t n_a, n_b;
+  const uint64_t *hdr_off; // n_b + 1: List B's byte offsets
+  uint64_t *u_start;       // cap + 1, per unit: its member's header offset + 1 when it starts a member, else 0
+  uint32_t *u_final;       // cap, per good unit: it ends with BFINAL
+  uint32_t *u_member;      // cap + 1, per unit: its member
+  uint64_t *rel_off;       // cap + 1, per unit: out_off[k] - out_off[its member's first unit]
+  uint64_t *member_off;    // n_b + 2, per member: its header's offset; behind the last: in_len
+  uint64_t *member_unit;   // n_b + 2: its first unit; behind the last: the unit count
+  uint64_t *member_out;    // n_b + 2: out_off[member_unit]
+  GzFileHead *gh;
+};
+__global__ void gzfile_init_kernel(FrameOne *one, uint64_t in_len);
+__global__ void gzfile_bits_kernel(GzFileParams P);
+__global__ void gzfile_link_kernel(GzFileParams P);
+__global__ void gzfile_finish_kernel(GzFileParams P);
+__global__ void gzfile_members_kernel(GzFileParams P);
+__global__ void gzfile_rel_kernel(GzFileParams P);
+// The decode (flate_hip_gzfile_read): flate_hip_inflate_one's rounds with every member's first unit as a SEED of the
+// segmented scan (one_seek_compose_kernel / one_seek_resolve_kernel): TAIL runs with rel_off as its out_off, and a
+// piece's history is min(32768, what its own member has produced in front of it).  gzfile_trailer_kernel: one thread
+// per member, CRC-32 and ISIZE against the trailer, an ordered min; gzfile_verdict_kernel: the call's words.
+struct GzFileVerdict {
+  uint64_t out_len;
+  int64_t err_off, stream_err_off;
+  int32_t status;
+  uint32_t bad_member;
+  uint32_t n_members, n_units;
+  uint32_t bad_trailer;    // 0xffffffff: none (set by the host's fill)
+  uint32_t pad;
+};
+struct GzFileDecParams {
+  OneDecParams D;          // D.out_off = the file's out_off
+  GzFileParams P;
+  uint32_t n_good;         // the discovery's good units
+  uint32_t n_members;      // ... and whole members (gzfile_trailer_kernel)
+  uint32_t *seed;          // count
+  uint64_t *p_bit_off;     // count
+  uint64_t *p_bit_end;     // count: ~0 = the piece runs to BFINAL
+  const uint32_t *sums;    // per member: the CRC-32 of its output
+  GzFileVerdict *v;
+};
+__global__ void gzfile_pieces_kernel(GzFileDecParams G);
+__global__ void gzfile_trailer_kernel(GzFileDecParams G);
+__global__ void gzfile_verdict_kernel(GzFileDecParams G);
+
 size_t inflate_simt_lds_bytes(int lanes_per_wave);  // dynamic LDS of that launch
 size_t inflate_simt_lens_bytes(uint32_t blocks);    // global scratch of that launch (InfParams::simt_lens)
 

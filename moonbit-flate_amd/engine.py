@@ -63,6 +63,10 @@ SEEK_SPAN_DEFAULT = 1 << 20  # FLATE_HIP_SEEK_SPAN_DEFAULT
 SEEK_SPAN_NONE = (1 << 64) - 1  # FLATE_HIP_SEEK_SPAN_NONE: unit 0 is the only point
 SeekIndex = collections.namedtuple("SeekIndex", "rc index windows n_units n_points out_bytes status err_off")
 OneRanges = collections.namedtuple("OneRanges", "rc out_off range_status n_decoded bad_unit")
+GzFileIndex = collections.namedtuple("GzFileIndex", "rc n_units n_members out_bytes n_candidates status bad_member err_off "
+                                     "stream_err_off unit_bit out_off member_off member_unit")
+GzFileRead = collections.namedtuple("GzFileRead", "rc out_len n_members n_units n_candidates status bad_member err_off "
+                                    "stream_err_off")
 
 # flate_hip_zip_entry, as numpy sees it (64 bytes)
 ZIP_ENTRY = np.dtype([("name_off", "<u8"), ("header_off", "<u8"), ("data_off", "<u8"), ("comp_size", "<u8"), ("size", "<u8"),
@@ -354,7 +358,81 @@ class OneSeekCalls:
         return _read_into(out, data, out_cap, "inflate_one_ranges", call, size)
 
 
-class FlateEngine(OneSeekCalls):
+class GzFileCalls:
+    """A gzip file of any members, long ones included: the two methods FlateEngine inherits.  They stand in a class of
+    their own so that their marshalling has its own recorded scenarios (tests/engine_trace_gzfile.py) beside the ones
+    of the methods that were there before."""
+
+    def gzfile_index(self, data, index_cap=None, member_cap=None, query=False):
+        """Where the units and the members of a gzip file start (one member or many, long or short) and where their
+        output goes, found on the GPU from the file's bits (flate_hip_gzfile_index) -> GzFileIndex(rc, n_units,
+        n_members, out_bytes, n_candidates, status, bad_member, err_off, stream_err_off, unit_bit, out_off, member_off,
+        member_unit).  unit_bit (numpy uint64[n_units + 1], bits counted from the FILE's first byte) and out_off as
+        inflate_one_index has them, per member; member_off (file offsets, the last entry len(data)) and member_unit
+        (every member's first unit, the last entry n_units).  status 0, or the walk's: -4, -7 or -6 in member
+        bad_member, which starts at err_off (or where no member can start), at stream_err_off of its raw stream; the
+        arrays then hold the good prefix.  query=True: only the counts (the arrays are None).  index_cap / member_cap:
+        the arrays' sizes (default: a unit per 256 bytes and a member per 4096 bytes of input, and a second call only
+        if the file has more; given and too small: rc -2, that pair None).  Other failures raise FlateError."""
+        data, in_ptr, n, device = _in_buf(data, accept_bytes=True, null_if_empty=True)
+        nu, nm, ob, nc = C.c_uint32(0), C.c_uint32(0), C.c_uint64(0), C.c_uint32(0)
+        st, bad, eo, seo = C.c_int32(0), C.c_uint32(0), C.c_int64(-1), C.c_int64(-1)
+
+        def call(ucap, ub, oo, mcap, mo, mu):
+            return self._tolerate(self._L.flate_hip_gzfile_index(
+                self._ctx, in_ptr, n, ucap, ub, oo, mcap, mo, mu, C.byref(nu), C.byref(nm), C.byref(ob), C.byref(nc),
+                C.byref(st), C.byref(bad), C.byref(eo), C.byref(seo), self._flags(False, False, device)), *PER_CHAIN)
+
+        def result(rc, ub=None, oo=None, mo=None, mu=None):
+            return GzFileIndex(rc, int(nu.value), int(nm.value), int(ob.value), int(nc.value), int(st.value),
+                               int(bad.value), int(eo.value), int(seo.value), ub, oo, mo, mu)
+
+        if query:
+            return result(call(0, None, None, 0, None, None))
+        # no query first: the discovery is the whole cost of the call
+        ucap = n // 256 + 64 if index_cap is None else int(index_cap)
+        mcap = n // 4096 + 64 if member_cap is None else int(member_cap)
+        for _ in range(2):
+            t = [np.zeros(max(c, 1), dtype=np.uint64) for c in (ucap, ucap, mcap, mcap)]
+            rc = call(ucap, t[0].ctypes.data, t[1].ctypes.data, mcap, t[2].ctypes.data, t[3].ctypes.data)
+            ku, km = int(nu.value) + 1, int(nm.value) + 1
+            short_u, short_m = ku > ucap and index_cap is None, km > mcap and member_cap is None
+            if not (short_u or short_m):
+                break
+            ucap, mcap = (ku if short_u else ucap), (km if short_m else mcap)
+        u_ok, m_ok = ku <= ucap, km <= mcap
+        return result(rc, t[0][:ku].copy() if u_ok else None, t[1][:ku].copy() if u_ok else None,
+                      t[2][:km].copy() if m_ok else None, t[3][:km].copy() if m_ok else None)
+
+    def gzfile_read(self, data, out=None, out_cap=None):
+        """A gzip file of any members back into its bytes by one call, what zcat gives (flate_hip_gzfile_read): every
+        member cut into units that are decoded in parallel, every member's CRC-32 and ISIZE checked on the GPU.  For
+        files of many small members gzip_read is faster; for exactly one member inflate_one is the same work.  Returns
+        (out, GzFileRead(rc, out_len, n_members, n_units, n_candidates, status, bad_member, err_off, stream_err_off));
+        the bytes are out[:out_len] (numpy for host data, a torch CUDA tensor for device data).  status 0; a chain
+        that breaks: gzfile_index's words, the good members in front and the failing member's bytes in front of its
+        failure delivered; a wrong trailer: -4 with bad_member, err_off its file offset and stream_err_off its length,
+        everything delivered.  rc -2 with out_len > capacity: out too small, nothing decoded.  out=None: sized by the
+        size query first.  Other failures raise FlateError."""
+        data, in_ptr, n, device = _in_buf(data, accept_bytes=True, null_if_empty=True)
+        ol, nm, nu, nc = C.c_uint64(0), C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
+        st, bad, eo, seo = C.c_int32(0), C.c_uint32(0), C.c_int64(-1), C.c_int64(-1)
+
+        def call(out_ptr, cap):
+            rc = self._tolerate(self._L.flate_hip_gzfile_read(
+                self._ctx, in_ptr, n, out_ptr, cap, C.byref(ol), C.byref(nm), C.byref(nu), C.byref(nc), C.byref(st),
+                C.byref(bad), C.byref(eo), C.byref(seo), self._flags(False, False, device)), *PER_CHAIN)
+            return GzFileRead(rc, int(ol.value), int(nm.value), int(nu.value), int(nc.value), int(st.value),
+                              int(bad.value), int(eo.value), int(seo.value))
+
+        def size():  # the size query: nothing is decoded
+            q = call(None, 0)
+            return (q.out_len, None) if q.rc == E_OUT_TOO_SMALL else (0, q)
+
+        return _read_into(out, data, out_cap, "gzfile_read", call, size)
+
+
+class FlateEngine(OneSeekCalls, GzFileCalls):
     """One engine = one flate_hip_ctx = one GPU + one HIP stream."""
 
     def __init__(self, device=0):

@@ -1030,6 +1030,95 @@ inline Err decompress_one(Engine &e, const std::vector<uint8_t> &stream, Wrap wr
   return make_error(e, rc);
 }
 
+// ---- a gzip file of any members, long ones included ----------------------------------------------
+// What index_gzfile found: the units of every member and the members, bits counted from the FILE's first byte.
+struct GzFileIndex {
+  std::vector<uint64_t> unit_bit;     // n_units + 1
+  std::vector<uint64_t> out_off;      // n_units + 1: the exclusive prefix sum of what the units inflate to
+  std::vector<uint64_t> member_off;   // n_members + 1: file offsets; the last: the file's size
+  std::vector<uint64_t> member_unit;  // n_members + 1: every member's first unit; the last: n_units
+  uint32_t n_units = 0, n_members = 0;
+  uint64_t out_bytes = 0;             // what the file inflates to (0 unless status == 0)
+  uint32_t n_candidates = 0;
+  uint32_t bad_member = 0xffffffffu;  // the member the chain broke in, or in front of which no member can start
+  int64_t err_off = -1;               // where that member starts
+  int64_t stream_err_off = -1;        // the serial decoder's offset, counted from that member's raw stream
+  int status = 0;                     // the FLATE_HIP_E_* code behind the error (0 = none)
+};
+
+// index_gzfile: where the units and the members of a gzip file start and where their output goes, found on the GPU
+// (flate_hip_gzfile_index; sized by a guess and one retry, as index_one).  Errors: corrupt_input_error(err_off) where
+// no member can start or for a block the decoder refuses, err_unexpected_eof for a file that is cut short,
+// FLATE_HIP_E_TOO_LARGE for a unit beyond the option "one_unit_max"; `ix` then holds the good prefix.
+inline Err index_gzfile(Engine &e, const std::vector<uint8_t> &file, GzFileIndex &ix) {
+  if (!e.ok()) return make_error(e, e.status());
+  ix = GzFileIndex();
+  int32_t st = 0;
+  int rc = 0;
+  size_t ucap = file.size() / 256 + 64, mcap = file.size() / 4096 + 64;
+  for (int attempt = 0; attempt < 2; ++attempt) {
+    ix.unit_bit.assign(ucap, 0);
+    ix.out_off.assign(ucap, 0);
+    ix.member_off.assign(mcap, 0);
+    ix.member_unit.assign(mcap, 0);
+    rc = flate_hip_gzfile_index(e.ctx(), file.data(), file.size(), ucap, ix.unit_bit.data(), ix.out_off.data(), mcap,
+                                ix.member_off.data(), ix.member_unit.data(), &ix.n_units, &ix.n_members, &ix.out_bytes,
+                                &ix.n_candidates, &st, &ix.bad_member, &ix.err_off, &ix.stream_err_off, 0);
+    if ((size_t)ix.n_units + 1 <= ucap && (size_t)ix.n_members + 1 <= mcap) break;
+    ucap = std::max(ucap, (size_t)ix.n_units + 1);
+    mcap = std::max(mcap, (size_t)ix.n_members + 1);
+  }
+  ix.unit_bit.resize(std::min(ucap, (size_t)ix.n_units + 1));
+  ix.out_off.resize(ix.unit_bit.size());
+  ix.member_off.resize(std::min(mcap, (size_t)ix.n_members + 1));
+  ix.member_unit.resize(ix.member_off.size());
+  ix.status = rc;
+  if (rc == 0) return std::nullopt;
+  if (rc == FLATE_HIP_E_CORRUPT) return corrupt_input_error(ix.err_off);
+  if (rc == FLATE_HIP_E_UNEXPECTED_EOF) return err_unexpected_eof();
+  return make_error(e, rc);
+}
+
+// What decompress_gzfile found beside the bytes.
+struct GzFileInfo {
+  uint32_t n_members = 0, n_units = 0, n_candidates = 0;
+  uint32_t bad_member = 0xffffffffu;
+  int64_t err_off = -1;         // the failing member's file offset
+  int64_t stream_err_off = -1;  // inside its raw stream; a trailer that does not match: the member's length
+  int status = 0;               // the FLATE_HIP_E_* code behind the error (0 = none)
+};
+
+// decompress_gzfile: a gzip file of any members back into its bytes, what zcat gives, every member cut into units that
+// are decoded in parallel and every trailer checked on the GPU (flate_hip_gzfile_read: a size query, then the decode).
+// Errors are the walk's: corrupt_input_error(err_off), err_unexpected_eof, FLATE_HIP_E_TOO_LARGE; `out` then holds the
+// good members in front and the failing member's bytes in front of its failure (a wrong trailer: everything).
+inline Err decompress_gzfile(Engine &e, const std::vector<uint8_t> &file, std::vector<uint8_t> &out,
+                             GzFileInfo *info = nullptr) {
+  if (!e.ok()) return make_error(e, e.status());
+  GzFileInfo I;
+  int32_t st = 0;
+  uint64_t len = 0;
+  out.clear();
+  auto call = [&](uint8_t *p, uint64_t cap) {
+    return flate_hip_gzfile_read(e.ctx(), file.data(), file.size(), p, cap, &len, &I.n_members, &I.n_units,
+                                 &I.n_candidates, &st, &I.bad_member, &I.err_off, &I.stream_err_off, 0);
+  };
+  int rc = call(nullptr, 0);
+  if (rc == FLATE_HIP_E_OUT_TOO_SMALL && len > 0) {  // (len: the size needed)
+    const uint64_t cap = len;
+    std::vector<uint8_t> buf(cap + 8, 0);
+    rc = call(buf.data(), cap);
+    if (rc == 0 || rc == FLATE_HIP_E_CORRUPT || rc == FLATE_HIP_E_UNEXPECTED_EOF || rc == FLATE_HIP_E_TOO_LARGE)
+      out.assign(buf.begin(), buf.begin() + std::min(len, cap));
+  }
+  I.status = rc;
+  if (info) *info = I;
+  if (rc == 0) return std::nullopt;
+  if (rc == FLATE_HIP_E_CORRUPT) return corrupt_input_error(I.err_off);
+  if (rc == FLATE_HIP_E_UNEXPECTED_EOF) return err_unexpected_eof();
+  return make_error(e, rc);
+}
+
 // What seek_index_one built: the seek index of ONE long stream, to keep beside the stream and hand to
 // decompress_one_ranges.
 struct OneSeekIndex {
