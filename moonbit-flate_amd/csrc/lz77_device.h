@@ -4,14 +4,10 @@
 #pragma once
 
 #include "flate_kernels.h"
+#include "lz77_chase_rule.h"  // kDenseKeep, the ev and pair words of the dense batch's chase
 
 namespace flate {
 
-constexpr int kDenseKeep = 61;  // keep using a dense batch while the next s-1 lane <= this (58..61 measured: 61 best by 0.8 %)
-// An event that starts at lane 62 or 63 has no scan lane left in its batch: the general path's probe masks would
-// shift by 64 (undefined; the hardware shifts by 0) and the batch ends where it began -- the build with 62 hung its
-// run (profiles/r05/README.md section 9).  The parser's progress guard (kStatusNoProgress) is the second line.
-static_assert(kDenseKeep >= 0 && kDenseKeep <= 61, "an event must start at a lane that leaves it a scan lane (a + 2 <= 63)");
 // multi-window streams: 16-bit modular table slots with periodic sweeps (see lz77_stream).  The sweep period and the
 // reach of a sparse batch share one budget (the assert below); round 6 moved it from 8192 / 16384 to 20480 / 4096:
 // 2.5 sweeps fewer per 65535-byte window (config 3's match finder 17.69 -> 17.40 ms, profiles/r06/README.md section 4),

@@ -460,15 +460,12 @@ FLATE_D void lz77_stream(const LzParams &P, const uint32_t sid, uint16_t *table,
           const bool slow = !(fv < fd) || tf >= 16;
           const bool ends = B + fv + tf >= s_limit;
           const int nxt = fv + tf - 1;
-#ifdef FLATE_LZ_TERM_SHORTCUT  // (A/B builds) bit 19: no candidate and no same-slot lane among my probe lanes of this batch
-          const bool off_batch = INTERIOR && fv == 64 && fd == 64;
-#else
-          constexpr bool off_batch = false;
-#endif
           ev = (uint32_t)(fv & 127) | ((uint32_t)tf << 8) | (slow ? 1u << 16 : 0u) |
-               (ends ? 1u << 17 : 0u) | ((ends || nxt > kDenseKeep) ? 1u << 18 : 0u) | (off_batch ? 1u << 19 : 0u) |
+               (ends ? 1u << 17 : 0u) | ((ends || nxt > kDenseKeep) ? 1u << 18 : 0u) |
                ((uint32_t)(nxt & 255) << 24);
         }
+        // the pair word: what up to two steps of the chase from my lane do (one ds_bpermute for the next event's word)
+        const uint32_t ev2 = chase_pair((uint32_t)lane, ev, (uint32_t)__shfl((int)ev, (int)((ev >> kEvNextShift) & 63u)));
         STAMP(t2);
 
         // Lanes inserted by the fast events whose start lanes are in `vis`: lane L belongs to the
@@ -486,43 +483,44 @@ FLATE_D void lz77_stream(const LzParams &P, const uint32_t sid, uint16_t *table,
         uint64_t VISall = 0;              // start lanes of the fast events chased so far
         int a = 0;
         for (;;) {  // events inside this batch
-          // Chase the fast events: x = ev[a]; visit a; a = next[a]; until an event needs the
-          // general path or asks to stop.  Hand-written: a step is 9 scalar
-          // instructions (the compiler's version of this loop cost ~290 cycles per match).
+          // Chase the fast events: visit a; note its match lane; a = its next start lane; until an event needs the
+          // general path or asks to stop.  The steps depend on each other through v_readlane -> scalar ops ->
+          // v_readlane, so the loop reads the pair word (lz77_chase_rule.h): one round trip states two events, or
+          // the one that is left, and the last word has bits 16 and 17 where ev has them.  Hand-written: a step is
+          // 13 scalar instructions (the compiler's version of the one-event loop cost ~290 cycles per match).
           uint32_t x, tmp;
           uint64_t VIS = 0, MFl = 0;
           int a_s = __builtin_amdgcn_readfirstlane(a);
           STAMP(tc0);
+#define FLATE_LZ_CHASE_STEP(BRANCH)                                                           \
+              "s_nop 1\n\t"                                                                   \
+              "v_readlane_b32 %[x], %[ev2], %[a]\n\t"                                         \
+              "s_nop 3\n\t"                                                                   \
+              "s_bitcmp1_b32 %[x], 15\n\t"                                                    \
+              "s_cbranch_scc1 2f\n\t"                                                         \
+              "s_bitset1_b64 %[vis], %[a]\n\t"                                                \
+              "s_bfe_u32 %[t], %[x], 0x60013\n\t" /* a1: six bits from bit 19 */              \
+              "s_bitset1_b64 %[vis], %[t]\n\t"                                                \
+              "s_bfe_u32 %[t], %[x], 0x60008\n\t" /* fv1: six bits from bit 8 */              \
+              "s_bitset1_b64 %[mf], %[t]\n\t"                                                 \
+              "s_and_b32 %[t], %[x], 0x7f\n\t"                                                \
+              "s_bitset1_b64 %[mf], %[t]\n\t"                                                 \
+              "s_lshr_b32 %[a], %[x], 25\n\t"                                                 \
+              "s_bitcmp1_b32 %[x], 18\n\t" BRANCH
+          static_assert(kPairNone == 1u << 15 && kPairFv1Shift == 8 && kPairA1Shift == 19 && kPairNextShift == 25 &&
+                            kEvSlow == 1u << 16 && kEvEnds == 1u << 17 && kEvStop == 1u << 18,
+                        "the loop below names the pair word's bits");
           asm volatile(
               "1:\n\t"
-              "s_nop 1\n\t"
-              "v_readlane_b32 %[x], %[ev], %[a]\n\t"
-              "s_nop 3\n\t"
-              "s_bitcmp1_b32 %[x], 16\n\t"
-              "s_cbranch_scc1 2f\n\t"
-              "s_bitset1_b64 %[vis], %[a]\n\t"
-              "s_and_b32 %[t], %[x], 0x7f\n\t"
-              "s_bitset1_b64 %[mf], %[t]\n\t"
-              "s_lshr_b32 %[a], %[x], 24\n\t"
-              "s_bitcmp1_b32 %[x], 18\n\t"
-              "s_cbranch_scc1 2f\n\t"
-              // (second copy: one taken branch per two events; the lane select written by s_lshr
+              FLATE_LZ_CHASE_STEP("s_cbranch_scc1 2f\n\t")
+              // (second copy: one taken branch per two steps; the lane select written by s_lshr
               // needs its four wait states here too)
-              "s_nop 1\n\t"
-              "v_readlane_b32 %[x], %[ev], %[a]\n\t"
-              "s_nop 3\n\t"
-              "s_bitcmp1_b32 %[x], 16\n\t"
-              "s_cbranch_scc1 2f\n\t"
-              "s_bitset1_b64 %[vis], %[a]\n\t"
-              "s_and_b32 %[t], %[x], 0x7f\n\t"
-              "s_bitset1_b64 %[mf], %[t]\n\t"
-              "s_lshr_b32 %[a], %[x], 24\n\t"
-              "s_bitcmp1_b32 %[x], 18\n\t"
-              "s_cbranch_scc0 1b\n\t"
+              FLATE_LZ_CHASE_STEP("s_cbranch_scc0 1b\n\t")
               "2:\n\t"
               : [x] "=&s"(x), [a] "+s"(a_s), [vis] "+s"(VIS), [mf] "+s"(MFl), [t] "=&s"(tmp)
-              : [ev] "v"(ev)
+              : [ev2] "v"(ev2)
               : "scc");
+#undef FLATE_LZ_CHASE_STEP
           a = a_s;
           MF |= MFl;
           STAMP(tc1);
@@ -533,11 +531,6 @@ FLATE_D void lz77_stream(const LzParams &P, const uint32_t sid, uint16_t *table,
             if (x & (1u << 17)) done = true;
             break;
           }
-#ifdef FLATE_LZ_TERM_SHORTCUT
-          // the batch's usual last event (it starts at a lane a > 0 and finds nothing before lane 64): the general
-          // path would walk its probe lanes, find no match and leave without changing INS or M
-          if (INTERIOR && (x & (1u << 19)) && a != 0) break;
-#endif
           // ---- general event (shared slots, long matches, end of scan) ----
           STAMP(tg0);
           const uint64_t FINS = fast_inserts(VISall);

@@ -1,6 +1,6 @@
 import ctypes as C, importlib, os, sys
 import numpy as np
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 os.environ.setdefault("FLATE_HIP_LIB", os.path.abspath("build/exp/libstamps.so"))
 flate = importlib.import_module("moonbit-flate_amd")
 import torch

@@ -24,6 +24,9 @@ def line_of(text):
 
 lo, hi = line_of("// Progress guard: every batch moves the parser"), line_of("// =============================== sparse batch")
 stream0 = line_of("FLATE_D void lz77_stream(")
+# the line table's numbers of the source file itself (the compiler's version decides whether that is 0, 1 or both)
+main = {int(m.group(1)) for m in (re.match(r'\s*\.file\s+(\d+)\s.*"([^"]*)"(\s+md5\s+\S+)?\s*$', l) for l in asm)
+        if m and m.group(2).endswith(sys.argv[3].split("/")[-1])}
 start = next(i for i, l in enumerate(asm) if l.startswith("_ZN") and key in l.split(":")[0])
 end = next(i for i in range(start, len(asm)) if asm[i].strip().startswith("s_endpgm"))
 cur, last, total, dense = (0, 0), "S", 0, 0
@@ -36,7 +39,7 @@ for l in asm[start + 1:end + 1]:
     if not t or t[0] in ";." or re.match(r"^(\.LBB\d+_\d+|\d+):", t):
         continue
     total += 1
-    if cur[0] == 1 and cur[1] >= stream0:
+    if cur[0] in main and cur[1] >= stream0:
         last = "D" if lo <= cur[1] < hi else "S"
     dense += last == "D"
 print("%s: %d instructions, %d of them in the dense batch (both copies)" % (asm[start].split(":")[0], total, dense))
