@@ -899,7 +899,8 @@ int flate_hip_inflate_one_index(flate_hip_ctx *ctx, const uint8_t *in, uint64_t 
  *   GATHER: every range's one run of the scratch into out.  Locate, select and gather are counted in no profiling
  *   stage; FLATE_HIP_STAGE_INFLATE is DECODE (of several rounds the last).
  *   Out of scope: delivering the output or judging the trailer from the build call; compressed or sparse windows;
- *   importing or exporting other tools' index formats; multi-member input; an index cached inside the ctx; uploading
+ *   importing or exporting other tools' index formats (multi-member input: flate_hip_gzfile_seek_index below); an index
+ *   cached inside the ctx; uploading
  *   only the touched part of the stream from host memory; stored and fixed block starts as units; skipping TAIL for
  *   units whose tail function nobody reads. */
 #define FLATE_HIP_SEEK_SPAN_DEFAULT (1ull << 20)
@@ -987,7 +988,7 @@ int flate_hip_inflate_one_ranges(flate_hip_ctx *ctx, const uint8_t *in, uint64_t
  *   lane-per-stream dictionary decoder with a per-piece end.  VERIFY: one checksum launch planned over the members'
  *   output ranges, a thread per trailer, an ordered min.  Profiling: FLATE_HIP_STAGE_INFLATE is DECODE (of several
  *   rounds the last), FLATE_HIP_STAGE_CHECKSUM is VERIFY; the rest is counted in no stage.
- *   Out of scope: zlib or raw concatenations; a seek index or ranges over a multi-member file; routing
+ *   Out of scope: zlib or raw concatenations; routing
  *   flate_hip_gzip_read or flate_hip_inflate_one here automatically; choosing per member between the serial and the
  *   unit decoder; stored or fixed block starts as units; caching across calls. */
 int flate_hip_gzfile_index(flate_hip_ctx *ctx, const uint8_t *in, uint64_t in_len, uint64_t index_cap,
@@ -999,6 +1000,97 @@ int flate_hip_gzfile_read(flate_hip_ctx *ctx, const uint8_t *in, uint64_t in_len
                           uint64_t *out_len, uint32_t *n_members, uint32_t *n_units, uint32_t *n_candidates,
                           int32_t *status, uint32_t *bad_member, int64_t *err_off, int64_t *stream_err_off,
                           uint32_t flags);
+
+/* -- Seek index for any gzip file: build once, read ranges across members -------------
+ * flate_hip_gzfile_read pays the whole discovery on every call and delivers everything.  flate_hip_gzfile_seek_index
+ * keeps the discovery of a file of ANY members, flate_hip_gzfile_ranges reads byte ranges of what zcat gives through it
+ * and decodes only the units they need.  The rule and the layout are written once, csrc/gzfile_seek_rule.h; the new
+ * kernels are csrc/gzfile_seek_kernels.hip; everything else is the two sections above, unchanged.
+ *
+ * Notation is flate_hip_gzfile_index's: n units, unit_bit[0 .. n] with bits counted from the FILE's first byte,
+ * out_off[0 .. n], T = out_off[n], m members, member_off[0 .. m], member_unit[0 .. m]; f(k) is the first unit of unit
+ * k's member; U[0, T) is what zcat gives.
+ *
+ * THE POINT RULE.  Unit k is a POINT iff k == 0, or k starts a member, or out_off[k] / span > out_off[k - 1] / span.
+ * span is flate_hip_inflate_one_seek_index's (0: FLATE_HIP_SEEK_SPAN_DEFAULT); with FLATE_HIP_SEEK_SPAN_NONE the points
+ * are exactly the member starts and the index is the cached discovery.  pstart(k) and segments are defined as there,
+ * so a segment never crosses a member.
+ * WINDOWS.  A point that starts a member has NO window: history never crosses a member.  Every other point p with unit
+ * u has one block of 32768 bytes, block number p - j with j = the members whose first unit is at or in front of u
+ * (derived, not stored): n_points - m blocks.  A block is the 32 KiB of ITS MEMBER's output in front of unit u, in
+ * stream order; bytes in front of the member's first byte are 0 -- never the bytes of the member in front, although
+ * those lie right there in U.  `windows` is host, or device under FLATE_HIP_DEVICE_PTRS like in, at any byte alignment.
+ * INDEX: a HOST array of 64-bit words: word 0 the magic "FGZFSIDX" (little endian), 1 the version (1), 2 in_len, 3 T,
+ * 4 span, 5 n, 6 m, 7 n_points, 8 .. 15 zero; then unit_bit[n + 1], out_off[n + 1], member_off[m + 1],
+ * member_unit[m + 1], point_unit[n_points]: 16 + 2 (n + 1) + 2 (m + 1) + n_points words.  The empty file (in_len == 0):
+ * the 16 head words alone, n = m = n_points = 0, no windows.
+ *
+ * flate_hip_gzfile_seek_index: BUILD.  Conventions are flate_hip_inflate_one_seek_index's: flags FLATE_HIP_DEVICE_PTRS
+ * or 0, FLATE_HIP_E_INVALID before any HIP call (NULL ctx / in with in_len > 0 / index_words / windows_bytes / n_units /
+ * n_members / n_points / out_bytes / status; index == NULL with index_cap_words > 0, windows == NULL with windows_cap >
+ * 0; any other flag); host pointers are uploaded once.  n_candidates, bad_member, err_off and stream_err_off may be
+ * NULL.  Both sizes are known after POINTS, in front of TAIL: a too-small index_cap_words or windows_cap -- both
+ * buffers NULL with capacity 0 is the size query -- returns FLATE_HIP_E_OUT_TOO_SMALL with every count set
+ * (*index_words, *windows_bytes, *n_units, *n_members, *n_points, *out_bytes = T) and nothing written.  Nothing outside
+ * windows[0, windows_cap) is ever written.
+ * Verdict: *status, *bad_member, *err_off and *stream_err_off are flate_hip_gzfile_index's for the same bytes; in
+ * addition a distance that reaches in front of its member is found by TAIL, which runs over every unit whatever the
+ * span, and reported at its serial offset as flate_hip_gzfile_read reports it (*n_units, *n_members: the good ones in
+ * front).  TRAILERS ARE NOT JUDGED: nothing is decoded to output, so there is nothing to sum; a caller who wants them
+ * judged calls flate_hip_gzfile_read once.  A file whose status is not 0 gets no index: *index_words = *windows_bytes
+ * = 0, *n_points = 0, *out_bytes = 0, the return value is the status; what `windows` holds then is unspecified.
+ * in_len == 0: FLATE_HIP_OK, the 16 head words alone.
+ *   How: flate_hip_gzfile_index's discovery; POINTS, one workgroup, the rule with the discovery's member-start mark
+ *   per unit, a scan that counts points and windows, a compaction; ONE read-back of the index arrays; per round of
+ *   "one_round_units" TAIL over EVERY unit with out_off[k] - out_off[f(k)] as its offset and the segmented COMPOSE /
+ *   RESOLVE with every member's first unit as a seed, exactly as flate_hip_gzfile_read runs them, over slots zeroed
+ *   first so that a member's first window is zeros; in DECODE's place PACK: the round's points as runs for the gather
+ *   kernel of the BGZF range call, a member start being a run of no bytes, so that every window lands in its block.
+ *
+ * flate_hip_gzfile_ranges: READ.  Ranges, out_off, range_status, the layout, the TOUCHED set and *bad_unit are
+ * flate_hip_inflate_one_ranges's over U; a range may cross members.  The DECODED set is the union, over the non-empty
+ * ranges, of [pstart(first), last] (first / last: the range's first and last touched unit): the union over touched k
+ * of [pstart(k), k] and, between two touched units of one range, the units that produce no output -- an empty member
+ * is a segment of its own that no touched unit names, and costs one empty piece.  *n_decoded is its size.  Verdict, in
+ * this order.
+ *  1. FLATE_HIP_E_INVALID before any HIP call: any of flate_hip_bgzf_read_ranges's argument refusals; windows == NULL
+ *     with windows_bytes > 0; an index that fails gzfile_seek_index_ok (host, O(n + m), reads nothing outside the
+ *     words): a wrong magic or version; in_len not the call's; a word count or windows_bytes that is not what the counts
+ *     imply; not (n >= 1, 1 <= m <= n, m <= n_points <= n, span >= 1) and not the empty file's head with in_len = 0 and
+ *     T = 0; unit_bit not strictly increasing; out_off not non-decreasing from 0 to T; member_off not strictly
+ *     increasing from 0 to in_len; member_unit not strictly increasing from 0 to n; a member whose units do not lie
+ *     inside it (unit_bit[member_unit[j]] >= 8 (member_off[j] + 10), unit_bit[member_unit[j + 1] - 1] < 8
+ *     (member_off[j + 1] - 8)); a unit of more than 2^28 bytes of input, a member's last unit measured to 8
+ *     (member_off[j + 1] - 8); point_unit not exactly the point rule's set for the stored span.
+ *  2. n_ranges == 0: out_off[0] = 0 if out_off is given, FLATE_HIP_OK, nothing is read.
+ *  3. The file is not the one the index was built from -- some member's header, parsed on the device, does not end
+ *     where the index has that member's first unit: FLATE_HIP_E_CORRUPT, every range_status FLATE_HIP_E_CORRUPT, every
+ *     out_off 0, nothing decoded.
+ *  4. A total above out_cap: FLATE_HIP_E_OUT_TOO_SMALL, out_off fully written, nothing decoded.  out == NULL with out_cap
+ *     == 0 is the size query -- unless the total is 0, which is FLATE_HIP_OK.
+ *  5. Decode and deliver, as verdict 5 there: a decoded unit is GOOD iff its piece ends with status 0 and fills exactly
+ *     out_off[k + 1] - out_off[k]; range_status, the return value and *bad_unit as there.
+ * The decoders read in[0, in_len - 8) with bits counted from the file's first byte; a unit runs to BFINAL iff the next
+ * unit starts a member or there is none, and its history is min(32768, out_off[k] - out_off[f(k)]) bytes.  Host
+ * pointers: the file is uploaded once, only the blocks of the selected window-bearing points are uploaded, the
+ * delivered bytes come down once; the host reads no file byte and waits once before decoding.
+ *   How: MEMBERS, one thread per member, the header rule at member_off[j] against unit_bit[member_unit[j]], an ordered
+ *   min; REL, one thread per unit; LOCATE, SELECT, LAYOUT and ONE read-back as in flate_hip_inflate_one_ranges; rounds
+ *   over the unit list: SEED (the piece from the index), LOAD (the stored window of each of the round's points into
+ *   its slot by the block formula, ZEROS for a member start, the carried window left alone), TAIL, the segmented scan,
+ *   RESOLVE, DECODE, CHECK; GATHER.  Profiling stages are flate_hip_inflate_one_ranges's.  No kernel waits for another
+ *   workgroup.
+ *   Out of scope: judging trailers from either call; an index of the good prefix of a broken file; zlib or raw
+ *   concatenations; compressed windows; other tools' index formats; caching in the ctx. */
+int flate_hip_gzfile_seek_index(flate_hip_ctx *ctx, const uint8_t *in, uint64_t in_len, uint64_t span, uint64_t *index,
+                                uint64_t index_cap_words, uint64_t *index_words, uint8_t *windows, uint64_t windows_cap,
+                                uint64_t *windows_bytes, uint32_t *n_units, uint32_t *n_members, uint32_t *n_points,
+                                uint64_t *out_bytes, uint32_t *n_candidates, int32_t *status, uint32_t *bad_member,
+                                int64_t *err_off, int64_t *stream_err_off, uint32_t flags);
+int flate_hip_gzfile_ranges(flate_hip_ctx *ctx, const uint8_t *in, uint64_t in_len, const uint64_t *index,
+                            uint64_t index_words, const uint8_t *windows, uint64_t windows_bytes, const uint64_t *begin,
+                            const uint64_t *end, uint32_t n_ranges, uint8_t *out, uint64_t out_cap, uint64_t *out_off,
+                            int32_t *range_status, uint32_t *n_decoded, uint32_t *bad_unit, uint32_t flags);
 
 /* -- ZIP archives ----------------------------------------------------------------
  * The everyday container of a batch of independent DEFLATE streams (.zip, .npz, .jar, .whl, .docx; PKWARE APPNOTE

@@ -78,6 +78,9 @@ def _signatures():
         "flate_hip_gzfile_index": (i, [vp, vp, u64, u64, vp, vp, u64, vp, vp, u32p, u32p, u64p, u32p, i32p, u32p, i64p, i64p,
                                        u32]),
         "flate_hip_gzfile_read": (i, [vp, vp, u64, vp, u64, u64p, u32p, u32p, u32p, i32p, u32p, i64p, i64p, u32]),
+        "flate_hip_gzfile_seek_index": (i, [vp, vp, u64, u64, vp, u64, u64p, vp, u64, u64p, u32p, u32p, u32p, u64p, u32p,
+                                            i32p, u32p, i64p, i64p, u32]),
+        "flate_hip_gzfile_ranges": (i, [vp, vp, u64, vp, u64, vp, u64, vp, vp, u32, vp, u64, vp, vp, u32p, u32p, u32]),
         "flate_hip_zip_bound": (sz, [vp, u32, vp]),
         "flate_hip_zip_write": (i, [vp, vp, vp, u32, vp, vp, vp, u64, u64p, vp, u32]),
         "flate_hip_zip_index": (i, [vp, vp, u64, u64, vp, vp, u32p, u64p, i64p, u32]),
@@ -96,7 +99,8 @@ MAY_BE_MISSING = [
     "flate_hip_bgzf_bound", "flate_hip_bgzf_write", "flate_hip_bgzf_index", "flate_hip_bgzf_read",
     "flate_hip_bgzf_read_ranges", "flate_hip_gzip_index", "flate_hip_gzip_read", "flate_hip_inflate_one_index",
     "flate_hip_inflate_one", "flate_hip_inflate_one_seek_index", "flate_hip_inflate_one_ranges",
-    "flate_hip_gzfile_index", "flate_hip_gzfile_read", "flate_hip_zip_bound", "flate_hip_zip_write", "flate_hip_zip_index", "flate_hip_zip_read",
+    "flate_hip_gzfile_index", "flate_hip_gzfile_read", "flate_hip_gzfile_seek_index", "flate_hip_gzfile_ranges",
+    "flate_hip_zip_bound", "flate_hip_zip_write", "flate_hip_zip_index", "flate_hip_zip_read",
 ]
 
 _lib = None

@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "flate_hip.h"
+#include "gzfile_seek_rule.h"
 #include "seek_index_rule.h"
 
 namespace flate {
@@ -210,6 +211,31 @@ inline int one_ranges_args(const uint8_t *in, uint64_t in_len, uint32_t wrap, co
   if (rc) return rc;
   if (wrap > FLATE_HIP_WRAP_GZIP || (windows_bytes && !windows)) return FLATE_HIP_E_INVALID;
   return seek_index_ok(index, index_words, windows_bytes, wrap, in_len) ? FLATE_HIP_OK : FLATE_HIP_E_INVALID;
+}
+
+// ---- the seek index of a gzip file of any members (flate_hip_gzfile_seek_index / _ranges; gzfile_seek_rule.h) ----
+
+// the build: index and windows are each a buffer with its capacity, or NULL with 0 (both NULL: the size query)
+inline int gzfile_seek_index_args(const uint8_t *in, uint64_t in_len, const uint64_t *index, uint64_t index_cap_words,
+                                  const uint64_t *index_words, const uint8_t *windows, uint64_t windows_cap,
+                                  const uint64_t *windows_bytes, const uint32_t *n_units, const uint32_t *n_members,
+                                  const uint32_t *n_points, const uint64_t *out_bytes, const int32_t *status,
+                                  uint32_t flags) {
+  if (!index_words || !windows_bytes || !n_units || !n_members || !n_points || !out_bytes || !status)
+    return FLATE_HIP_E_INVALID;
+  if ((in_len && !in) || (index_cap_words && !index) || (windows_cap && !windows)) return FLATE_HIP_E_INVALID;
+  return (flags & ~FLATE_HIP_DEVICE_PTRS) ? FLATE_HIP_E_INVALID : FLATE_HIP_OK;
+}
+// the read: flate_hip_bgzf_read_ranges's refusals for byte positions, then the index itself (gzfile_seek_index_ok,
+// O(n + m))
+inline int gzfile_ranges_args(const uint8_t *in, uint64_t in_len, const uint64_t *index, uint64_t index_words,
+                              const uint8_t *windows, uint64_t windows_bytes, const uint64_t *begin, const uint64_t *end,
+                              uint32_t n_ranges, const uint8_t *out, uint64_t out_cap, const uint64_t *out_off,
+                              uint32_t flags) {
+  const int rc = bgzf_ranges_args(in, in_len, FLATE_HIP_BGZF_POS_BYTES, begin, end, n_ranges, out, out_cap, out_off, flags);
+  if (rc) return rc;
+  if (windows_bytes && !windows) return FLATE_HIP_E_INVALID;
+  return gzfile_seek_index_ok(index, index_words, windows_bytes, in_len) ? FLATE_HIP_OK : FLATE_HIP_E_INVALID;
 }
 
 // ---- ZIP archives (flate_hip_zip_write / _index / _read) ----

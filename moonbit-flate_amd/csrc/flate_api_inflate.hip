@@ -2179,6 +2179,507 @@ int flate_hip_gzfile_read(flate_hip_ctx *c, const uint8_t *in, uint64_t in_len, 
   }
 }
 
+// The seek index of a file of any members: the file's discovery, POINTS with every member's first unit as a point,
+// then flate_hip_gzfile_read's rounds of TAIL / segmented COMPOSE / RESOLVE and, in DECODE's place, PACK: the windows
+// in front of the round's window-bearing points into their blocks.  Nothing is decoded to output, no trailer is judged.
+int flate_hip_gzfile_seek_index(flate_hip_ctx *c, const uint8_t *in, uint64_t in_len, uint64_t span, uint64_t *index,
+                                uint64_t index_cap_words, uint64_t *index_words, uint8_t *windows, uint64_t windows_cap,
+                                uint64_t *windows_bytes, uint32_t *n_units, uint32_t *n_members, uint32_t *n_points,
+                                uint64_t *out_bytes, uint32_t *n_candidates, int32_t *status, uint32_t *bad_member,
+                                int64_t *err_off, int64_t *stream_err_off, uint32_t flags) {
+  // every check before any HIP call
+  if (!c) return FLATE_HIP_E_INVALID;
+  int rc = gzfile_seek_index_args(in, in_len, index, index_cap_words, index_words, windows, windows_cap, windows_bytes,
+                                  n_units, n_members, n_points, out_bytes, status, flags);
+  if (rc) return rc;
+  c->hip_err.clear();
+  *index_words = 0, *windows_bytes = 0, *n_units = 0, *n_members = 0, *n_points = 0, *out_bytes = 0, *status = 0;
+  if (n_candidates) *n_candidates = 0;
+  if (bad_member) *bad_member = 0xffffffffu;
+  if (err_off) *err_off = -1;
+  if (stream_err_off) *stream_err_off = -1;
+  auto fail = [&](int st, uint32_t bm, int64_t eo, int64_t seo) {  // a file that fails gets no index
+    *status = st;
+    *index_words = 0, *windows_bytes = 0, *n_points = 0, *out_bytes = 0;
+    if (bad_member) *bad_member = bm;
+    if (err_off) *err_off = eo;
+    if (stream_err_off) *stream_err_off = seo;
+    return st;
+  };
+  span = seek_span(span);
+  auto head = [&](uint64_t T, uint64_t n, uint64_t m, uint64_t np) {
+    for (uint32_t k = 0; k < kGzSeekHeadWords; ++k) index[k] = 0;
+    index[kGzSeekMagicAt] = kGzSeekMagic;
+    index[kGzSeekVersionAt] = kGzSeekVersion;
+    index[kGzSeekInLenAt] = in_len;
+    index[kGzSeekTotalAt] = T;
+    index[kGzSeekSpanAt] = span;
+    index[kGzSeekUnitsAt] = n;
+    index[kGzSeekMembersAt] = m;
+    index[kGzSeekPointsAt] = np;
+  };
+  if (in_len == 0) {  // no bytes: zero members, zero units, the head alone
+    *index_words = gzfile_seek_index_words(0, 0, 0);
+    if (index_cap_words < *index_words) return FLATE_HIP_E_OUT_TOO_SMALL;
+    head(0, 0, 0, 0);
+    return FLATE_HIP_OK;
+  }
+  try {
+    const bool dev = (flags & FLATE_HIP_DEVICE_PTRS) != 0;
+    const uint8_t *d_in = nullptr;
+    if ((rc = stage_input(c, in, in_len, flags, &d_in))) return rc;
+    OneHead H{};
+    GzFileHead G{};
+    GzFileParams P{};
+    if ((rc = gzfile_discover(c, d_in, in_len, H, G, P, nullptr))) return rc;
+    const uint32_t n = H.h.n_members, m = G.n_members;
+    *n_units = n;
+    *n_members = m;
+    if (n_candidates) *n_candidates = H.h.n_cand;
+    auto found = [&]() { return fail(H.h.rc, G.n_members, G.err_off, G.stream_err_off); };  // the discovery's verdict
+    if (H.h.rc == FLATE_HIP_E_TOO_LARGE || H.h.rc == FLATE_HIP_E_INTERNAL) return found();
+    const bool sound = H.h.rc == 0;  // (a file that fails is still walked: an earlier unit's distance may fail first)
+    const uint32_t n_dec = n + (H.fail_unit ? 1u : 0u);
+    if (n_dec == 0) return found();
+    if (sound && (n < 1u || m < 1u || m > n)) return FLATE_HIP_E_INTERNAL;
+    const uint32_t per_round = n_dec < c->one_round_units ? n_dec : c->one_round_units;
+
+    // POINTS: mark, scan, compact; the sizes are known here, in front of TAIL
+    GzSeekPointsParams PP{};
+    GzSeekPackParams K{};
+    rc = carve(c, c->d_one_seek, [&](Carve &k) {
+      k.take(PP.counts, 2);
+      k.take(PP.point_unit, (size_t)n + 1);
+      k.take(K.r_out_off, (size_t)per_round + 1);
+      k.take(K.r_src, per_round);
+    });
+    if (rc) return rc;
+    std::vector<uint64_t> ubit, ooff, moff, munit, points;
+    uint32_t np = 0;
+    uint64_t need_words = 0, need_bytes = 0;
+    if (sound) {
+      PP.out_off = P.O.C.out_off;
+      PP.u_start = P.u_start;
+      PP.n = n;
+      PP.span = span;
+      hipLaunchKernelGGL(gzfile_seek_points_kernel, dim3(1), dim3(1024), 0, c->stream, PP);
+      HIP_TRY(c, hipGetLastError());
+      uint32_t counts[2] = {0, 0};
+      ubit.assign((size_t)n + 1, 0), ooff.assign((size_t)n + 1, 0), points.assign(n, 0);
+      moff.assign((size_t)m + 1, 0), munit.assign((size_t)m + 1, 0);
+      HIP_TRY(c, hipMemcpyAsync(counts, PP.counts, 8, hipMemcpyDeviceToHost, c->stream));
+      HIP_TRY(c, hipMemcpyAsync(points.data(), PP.point_unit, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
+      HIP_TRY(c, hipMemcpyAsync(ubit.data(), P.O.C.member_off, ((size_t)n + 1) * 8, hipMemcpyDeviceToHost, c->stream));
+      HIP_TRY(c, hipMemcpyAsync(ooff.data(), P.O.C.out_off, ((size_t)n + 1) * 8, hipMemcpyDeviceToHost, c->stream));
+      HIP_TRY(c, hipMemcpyAsync(moff.data(), P.member_off, ((size_t)m + 1) * 8, hipMemcpyDeviceToHost, c->stream));
+      HIP_TRY(c, hipMemcpyAsync(munit.data(), P.member_unit, ((size_t)m + 1) * 8, hipMemcpyDeviceToHost, c->stream));
+      HIP_TRY(c, hipStreamSynchronize(c->stream));
+      np = counts[0];
+      if (np < m || np > n || counts[1] != np - m || munit[0] != 0u || munit[m] != n) {
+        c->hip_err = "gzfile seek index: the point count does not fit the units and members";
+        return FLATE_HIP_E_INTERNAL;
+      }
+      need_words = gzfile_seek_index_words(n, m, np);
+      need_bytes = gzfile_seek_windows_bytes(np, m);
+      *index_words = need_words, *windows_bytes = need_bytes, *n_points = np, *out_bytes = H.h.out_bytes;
+      if (index_cap_words < need_words || windows_cap < need_bytes) return FLATE_HIP_E_OUT_TOO_SMALL;  // (the size query too)
+    }
+    uint8_t *d_windows = windows;
+    if (sound && !dev && need_bytes) {
+      if ((rc = ensure(c, c->d_one_seek_win, need_bytes + 16))) return rc;
+      d_windows = (uint8_t *)c->d_one_seek_win.p;
+    }
+
+    const size_t fentries = (size_t)per_round * kWinEntries;
+    GzFileDecParams GD{};
+    OneDecParams &D = GD.D;
+    rc = carve(c, c->d_one_dec, [&](Carve &k) {
+      k.take(D.dh, 1);
+      k.take(D.F[0], fentries);
+      k.take(D.F[1], fentries);
+      k.take(D.R, ((size_t)per_round + 1) * kWinEntries);
+      k.take(D.status, (size_t)n_dec + 1);
+      k.take(D.err_off, (size_t)n_dec + 1);
+      k.take(D.produced, (size_t)n_dec + 1);
+      k.take(D.p_out_off, (size_t)per_round + 1);
+      k.take(D.p_dict_at, per_round);
+      k.take(D.p_dict_len, per_round);
+    });
+    if (rc) return rc;
+    rc = carve(c, c->d_gzfile_dec, [&](Carve &k) {
+      k.take(GD.seed, per_round);
+      k.take(GD.p_bit_off, per_round);
+      k.take(GD.p_bit_end, per_round);
+    });
+    if (rc) return rc;
+    D.in = d_in;
+    D.one = P.O.one;
+    D.unit_bit = P.O.C.member_off;
+    D.out_off = P.O.C.out_off;
+    D.total = H.prefix_bytes + (H.fail_unit ? H.fail_out : 0ull);
+    D.unit_max = c->one_unit_max;
+    GD.P = P;
+    GD.n_good = n;
+    HIP_TRY(c, hipMemsetAsync(D.dh, 0xff, sizeof(OneDecHead), c->stream));  // first_bad: none
+    K.point_unit = PP.point_unit;
+    K.member_unit = P.member_unit;
+    K.m = m;
+    K.n_points = np;
+    uint32_t p_next = 0;  // the first point whose round has not come yet
+    for (uint32_t u0 = 0; u0 < n_dec; u0 += per_round) {
+      D.u0 = u0;
+      D.count = n_dec - u0 < per_round ? n_dec - u0 : per_round;
+      const uint32_t unit_blocks = (D.count + 1u + 255u) / 256u;
+      const uint32_t entry_blocks = (uint32_t)(((uint64_t)D.count * kWinEntries + 255) / 256);
+      if (sound) {
+        // a member's first unit is a seed that RESOLVE never writes: zeros in front of every member, so that a stored
+        // window holds nothing of the member in front (slot 0 is the carried window unless the round starts a member)
+        const bool starts = munit[bgzf_upper_bound(munit.data(), m, u0) - 1u] == u0;
+        uint8_t *from = D.R + (starts ? 0 : kWinEntries);
+        HIP_TRY(c, hipMemsetAsync(from, 0, ((size_t)D.count + (starts ? 1 : 0)) * kWinEntries, c->stream));
+      }
+      OneDecParams T = D;  // TAIL: a unit's history is what its own member has produced in front of it
+      T.out_off = P.rel_off;
+      hipLaunchKernelGGL(one_tail_kernel, dim3(D.count), dim3(64), 0, c->stream, T);
+      hipLaunchKernelGGL(gzfile_pieces_kernel, dim3(unit_blocks), dim3(256), 0, c->stream, GD);  // (the seeds)
+      int cur = 0;
+      for (uint32_t s = 1; s < D.count; s <<= 1, cur ^= 1)
+        hipLaunchKernelGGL(one_seek_compose_kernel, dim3(entry_blocks), dim3(256), 0, c->stream, D.F[cur], D.F[cur ^ 1],
+                           GD.seed, D.count, s);
+      hipLaunchKernelGGL(one_seek_resolve_kernel, dim3(entry_blocks), dim3(256), 0, c->stream, D.F[cur], D.R, GD.seed,
+                         D.count);
+      // PACK: R[i] of the round's window-bearing points -> their blocks, which lie one behind the other in `windows`
+      uint32_t p_hi = p_next;
+      while (p_hi < np && points[p_hi] < (uint64_t)u0 + D.count) ++p_hi;
+      if (p_hi > p_next) {
+        const uint32_t cnt = p_hi - p_next;
+        const uint32_t b_lo = gzfile_seek_blocks_before(munit.data(), m, p_next, (uint32_t)points[p_next]);
+        const uint32_t b_hi = p_hi < np ? gzfile_seek_blocks_before(munit.data(), m, p_hi, (uint32_t)points[p_hi]) : np - m;
+        if (b_hi > b_lo) {
+          K.p_lo = p_next, K.np = cnt, K.u0 = u0;
+          hipLaunchKernelGGL(gzfile_seek_pack_kernel, dim3((cnt + 1u + 255u) / 256u), dim3(256), 0, c->stream, K);
+          BgzfGatherParams GP{};
+          GP.scratch = D.R;  // (R[count] lies behind the last run: the 32 bytes the gather may touch)
+          GP.out = d_windows + (uint64_t)b_lo * kSeekWindow;
+          GP.r_out_off = K.r_out_off;
+          GP.r_src = K.r_src;
+          GP.n_ranges = cnt;
+          const uint64_t pieces = ((uint64_t)(b_hi - b_lo) * kSeekWindow + (uint64_t)cnt * kBgzfGatherRangeCost +
+                                   kBgzfGatherWindow - 1) / kBgzfGatherWindow;
+          hipLaunchKernelGGL(bgzf_gather_kernel, dim3((uint32_t)pieces), dim3(256), 0, c->stream, GP);
+        }
+        p_next = p_hi;
+      }
+      HIP_TRY(c, hipGetLastError());
+      if (u0 + D.count < n_dec)
+        HIP_TRY(c, hipMemcpyAsync(D.R, D.R + (size_t)D.count * kWinEntries, kWinEntries, hipMemcpyDeviceToDevice, c->stream));
+    }
+    OneDecHead R{};
+    HIP_TRY(c, hipMemcpyAsync(&R, D.dh, sizeof R, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (R.first_bad != 0xffffffffu) {  // TAIL's verdict: the serial decoder's, at the serial offset, in its member
+      const uint32_t fb = R.first_bad;
+      if (fb >= n_dec) return FLATE_HIP_E_INTERNAL;
+      int32_t st = 0;
+      int64_t eo = -1;
+      uint32_t bm = 0;
+      HIP_TRY(c, hipMemcpyAsync(&st, D.status + fb, 4, hipMemcpyDeviceToHost, c->stream));
+      HIP_TRY(c, hipMemcpyAsync(&eo, D.err_off + fb, 8, hipMemcpyDeviceToHost, c->stream));
+      HIP_TRY(c, hipMemcpyAsync(&bm, P.u_member + fb, 4, hipMemcpyDeviceToHost, c->stream));
+      HIP_TRY(c, hipStreamSynchronize(c->stream));
+      if (bm >= P.n_b) return FLATE_HIP_E_INTERNAL;
+      uint64_t at = 0, first = 0, bit = 0;
+      HIP_TRY(c, hipMemcpyAsync(&at, P.member_off + bm, 8, hipMemcpyDeviceToHost, c->stream));
+      HIP_TRY(c, hipMemcpyAsync(&first, P.member_unit + bm, 8, hipMemcpyDeviceToHost, c->stream));
+      HIP_TRY(c, hipStreamSynchronize(c->stream));
+      if (first > fb) return FLATE_HIP_E_INTERNAL;
+      HIP_TRY(c, hipMemcpyAsync(&bit, P.O.C.member_off + first, 8, hipMemcpyDeviceToHost, c->stream));
+      HIP_TRY(c, hipStreamSynchronize(c->stream));
+      *n_members = bm;
+      *n_units = fb;
+      const int64_t seo = (st == FLATE_HIP_E_CORRUPT && eo >= 0) ? eo - (int64_t)(bit >> 3) : -1;
+      return fail(st ? st : FLATE_HIP_E_INTERNAL, bm, (int64_t)at, seo);
+    }
+    if (!sound) return found();
+    if (p_next != np) return FLATE_HIP_E_INTERNAL;
+    if (!dev && need_bytes) {
+      HIP_TRY(c, hipMemcpyAsync(windows, d_windows, need_bytes, hipMemcpyDeviceToHost, c->stream));
+      HIP_TRY(c, hipStreamSynchronize(c->stream));
+    }
+    head(H.h.out_bytes, n, m, np);
+    uint64_t *w = index + kGzSeekHeadWords;
+    memcpy(w, ubit.data(), ((size_t)n + 1) * 8), w += (size_t)n + 1;
+    memcpy(w, ooff.data(), ((size_t)n + 1) * 8), w += (size_t)n + 1;
+    memcpy(w, moff.data(), ((size_t)m + 1) * 8), w += (size_t)m + 1;
+    memcpy(w, munit.data(), ((size_t)m + 1) * 8), w += (size_t)m + 1;
+    memcpy(w, points.data(), (size_t)np * 8);
+    return FLATE_HIP_OK;
+  } catch (const std::exception &e) {
+    c->hip_err = e.what();
+    return FLATE_HIP_E_INTERNAL;
+  }
+}
+
+// Random access through the file's seek index: the "same file" check per member, rel, locate, select, layout, ONE
+// read-back (the check's word, the ranges' layout, the unit list), rounds of TAIL / segmented scan / DECODE over the
+// list into a dense scratch, the per-unit check, the gather.
+int flate_hip_gzfile_ranges(flate_hip_ctx *c, const uint8_t *in, uint64_t in_len, const uint64_t *index, uint64_t index_words,
+                            const uint8_t *windows, uint64_t windows_bytes, const uint64_t *begin, const uint64_t *end,
+                            uint32_t n_ranges, uint8_t *out, uint64_t out_cap, uint64_t *out_off, int32_t *range_status,
+                            uint32_t *n_decoded, uint32_t *bad_unit, uint32_t flags) {
+  // every check before any HIP call
+  if (!c) return FLATE_HIP_E_INVALID;
+  int rc = gzfile_ranges_args(in, in_len, index, index_words, windows, windows_bytes, begin, end, n_ranges, out, out_cap,
+                              out_off, flags);
+  if (rc) return rc;
+  c->hip_err.clear();
+  if (n_decoded) *n_decoded = 0;
+  if (bad_unit) *bad_unit = 0xffffffffu;
+  if (n_ranges == 0) {
+    if (out_off) out_off[0] = 0;
+    return FLATE_HIP_OK;
+  }
+  const uint32_t nr = n_ranges;
+  if (index[kGzSeekUnitsAt] == 0) {  // the empty file: every range is empty
+    for (uint32_t r = 0; r <= nr; ++r) out_off[r] = 0;
+    if (range_status)
+      for (uint32_t r = 0; r < nr; ++r) range_status[r] = 0;
+    return FLATE_HIP_OK;
+  }
+  try {
+    const bool dev = (flags & FLATE_HIP_DEVICE_PTRS) != 0;
+    const uint8_t *d_in = nullptr;
+    if ((rc = stage_input(c, in, in_len, flags, &d_in))) return rc;
+    const uint32_t n = (uint32_t)index[kGzSeekUnitsAt], m = (uint32_t)index[kGzSeekMembersAt],
+                   np = (uint32_t)index[kGzSeekPointsAt];
+    const size_t idx_words = (size_t)(index_words - kGzSeekHeadWords);
+    const uint64_t *h_munit = index + kGzSeekHeadWords + 2 * ((size_t)n + 1) + ((size_t)m + 1);
+    const uint64_t *h_point = h_munit + ((size_t)m + 1);
+
+    GzSeekParams GS{};
+    OneSeekParams &Q = GS.Q;
+    Q.n = n, Q.n_points = np, Q.span = index[kGzSeekSpanAt], Q.n_ranges = nr;
+    uint64_t *d_idx, *d_begin, *d_end;
+    FrameOne *d_one;
+    size_t o_back = 0, o_end = 0;
+    rc = carve(c, c->d_one_seek, [&](Carve &k) {
+      k.take(d_idx, idx_words);
+      k.take(d_begin, nr);
+      k.take(d_end, nr);
+      k.take(GS.rel, (size_t)n + 1);
+      k.take(d_one, 1);
+      k.take(Q.diff, (size_t)n + 1);
+      k.take(Q.rank, n);
+      k.take(Q.scratch_at, n);
+      k.take(Q.r_b, nr);
+      k.take(Q.r_len, nr);
+      k.take(Q.r_first, nr);
+      k.take(Q.r_last, nr);
+      k.take(Q.r_seg, nr);
+      k.take(Q.r_src, nr);
+      k.take(Q.sel_at, (size_t)n + 1);
+      o_back = k.at;
+      k.take(Q.head, 1);
+      k.take(GS.bad_member, 1);
+      k.take(Q.r_out_off, (size_t)nr + 1);
+      k.take(Q.r_rank_lo, nr);
+      k.take(Q.r_rank_hi, nr);
+      k.take(Q.sel_unit, n);
+      o_end = k.at;
+    });
+    if (rc) return rc;
+    Q.unit_bit = d_idx, Q.out_off = d_idx + ((size_t)n + 1);
+    GS.member_off = Q.out_off + ((size_t)n + 1), GS.member_unit = GS.member_off + ((size_t)m + 1);
+    Q.point_unit = GS.member_unit + ((size_t)m + 1);
+    Q.begin = d_begin, Q.end = d_end;
+    GS.in = d_in, GS.in_len = in_len, GS.m = m;
+    const size_t back_bytes = o_end - o_back;
+    const uint8_t *d_back = (const uint8_t *)c->d_one_seek.p + o_back;
+    HIP_TRY(c, hipMemcpyAsync(d_idx, index + kGzSeekHeadWords, idx_words * 8, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(d_begin, begin, (size_t)nr * 8, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(d_end, end, (size_t)nr * 8, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemsetAsync(Q.diff, 0, ((size_t)n + 1) * 4, c->stream));
+    HIP_TRY(c, hipMemsetAsync(GS.bad_member, 0xff, 4, c->stream));  // none
+    hipLaunchKernelGGL(gzfile_init_kernel, dim3(1), dim3(64), 0, c->stream, d_one, in_len);
+    hipLaunchKernelGGL(gzfile_seek_members_kernel, dim3((m + 255u) / 256u), dim3(256), 0, c->stream, GS);
+    hipLaunchKernelGGL(gzfile_seek_rel_kernel, dim3((n + 1u + 255u) / 256u), dim3(256), 0, c->stream, GS);
+    hipLaunchKernelGGL(one_seek_locate_kernel, dim3((nr + 255u) / 256u), dim3(256), 0, c->stream, Q);
+    hipLaunchKernelGGL(one_seek_select_kernel, dim3(1), dim3(1024), 0, c->stream, Q);
+    hipLaunchKernelGGL(one_seek_layout_kernel, dim3(1), dim3(1024), 0, c->stream, Q);
+    HIP_TRY(c, hipGetLastError());
+    std::vector<uint8_t> back(back_bytes);
+    HIP_TRY(c, hipMemcpyAsync(back.data(), d_back, back_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    auto got = [&](const auto *d) { return (decltype(d))(back.data() + ((const uint8_t *)d - d_back)); };  // d's host copy
+    const OneSeekHead RH = *got(Q.head);
+    const uint32_t missed = *got(GS.bad_member);
+    const uint32_t *r_lo = got(Q.r_rank_lo), *r_hi = got(Q.r_rank_hi), *sel = got(Q.sel_unit);
+    const uint32_t ns = RH.n_sel;
+    if (missed != 0xffffffffu) {  // some member's header is not where the index has it: nothing is decoded
+      for (uint32_t r = 0; r <= nr; ++r) out_off[r] = 0;
+      if (range_status)
+        for (uint32_t r = 0; r < nr; ++r) range_status[r] = FLATE_HIP_E_CORRUPT;
+      return FLATE_HIP_E_CORRUPT;
+    }
+    if (ns > n) {
+      c->hip_err = "gzfile ranges: more units selected than the file has";
+      return FLATE_HIP_E_INTERNAL;
+    }
+    memcpy(out_off, got(Q.r_out_off), ((size_t)nr + 1) * 8);
+    if (n_decoded) *n_decoded = ns;
+    if (range_status)
+      for (uint32_t r = 0; r < nr; ++r) range_status[r] = 0;
+    if (RH.out_total > out_cap) return FLATE_HIP_E_OUT_TOO_SMALL;  // (the size query too: nothing is decoded)
+    if (ns == 0 || RH.out_total == 0) return FLATE_HIP_OK;        // (no range holds a byte)
+
+    // the windows: the caller's device buffer, or the blocks of the selected window-bearing points uploaded into a
+    // staged copy
+    const uint8_t *d_windows = windows;
+    if (!dev && windows_bytes) {
+      if ((rc = ensure(c, c->d_one_seek_win, windows_bytes + 16))) return rc;
+      uint8_t *stage = (uint8_t *)c->d_one_seek_win.p;
+      d_windows = stage;
+      std::vector<uint32_t> bs;  // the blocks of the selected points, rising
+      uint32_t p = 0, j = 0;     // j: the members whose first unit is at or in front of the point's
+      for (uint32_t i = 0; i < ns && p < np; ++i) {
+        while (p < np && h_point[p] < sel[i]) ++p;
+        if (p >= np || h_point[p] != sel[i]) continue;
+        while (j < m && h_munit[j] <= sel[i]) ++j;
+        if (h_munit[j - 1u] != sel[i]) bs.push_back(p - j);
+      }
+      for (size_t a = 0; a < bs.size();) {  // neighbours in the index travel as one copy
+        size_t b = a + 1;
+        while (b < bs.size() && bs[b] == bs[b - 1] + 1u) ++b;
+        const uint64_t at = (uint64_t)bs[a] * kSeekWindow, len = (uint64_t)(b - a) * kSeekWindow;
+        HIP_TRY(c, hipMemcpyAsync(stage + at, windows + at, len, hipMemcpyHostToDevice, c->stream));
+        a = b;
+      }
+    }
+
+    const uint32_t per_round = ns < c->one_round_units ? ns : c->one_round_units;
+    const size_t fentries = (size_t)per_round * kWinEntries;
+    OneDecParams D{};
+    GzSeekRoundParams Z{};
+    OneSeekRoundParams &S = Z.S;
+    int32_t *d_ds;
+    uint64_t *d_dl;
+    int64_t *d_de;
+    rc = carve(c, c->d_one_dec, [&](Carve &k) {
+      k.take(D.dh, 1);
+      k.take(D.F[0], fentries);
+      k.take(D.F[1], fentries);
+      k.take(D.R, ((size_t)per_round + 1) * kWinEntries);
+      k.take(D.status, (size_t)ns + 1);
+      k.take(D.err_off, (size_t)ns + 1);
+      k.take(D.produced, (size_t)ns + 1);
+      k.take(S.seed, per_round);
+      k.take(S.p_bit_off, per_round);
+      k.take(S.p_bit_end, per_round);
+      k.take(S.p_dict_at, per_round);
+      k.take(S.p_dict_len, per_round);
+      k.take(d_ds, per_round);
+      k.take(d_dl, per_round);
+      k.take(d_de, per_round);
+      k.take(S.u_status, ns);
+    });
+    if (rc) return rc;
+    if ((rc = ensure(c, c->d_one_seek_dense, RH.scratch_total + 64))) return rc;
+    uint8_t *d_dense = (uint8_t *)c->d_one_seek_dense.p;
+    uint8_t *d_out = out;
+    if (!dev) {
+      if ((rc = ensure(c, c->d_out, RH.out_total + 16))) return rc;
+      d_out = (uint8_t *)c->d_out.p;
+    }
+    D.in = d_in;
+    D.one = d_one;
+    D.unit_bit = Q.unit_bit;
+    D.out_off = GS.rel;  // TAIL: a unit's history is what its own member has produced in front of it
+    D.unit_max = c->one_unit_max;
+    D.unit_list = Q.sel_unit;
+    S.Q = Q;
+    S.windows = d_windows;
+    S.R = D.R;
+    S.d_status = d_ds;
+    S.d_out_len = d_dl;
+    Z.member_unit = GS.member_unit;
+    Z.m = m;
+    Z.rel = GS.rel;
+    HIP_TRY(c, hipMemsetAsync(D.dh, 0xff, sizeof(OneDecHead), c->stream));
+    bool used[FLATE_HIP_STAGE_COUNT] = {false, false, false, false};
+    for (uint32_t i0 = 0; i0 < ns; i0 += per_round) {
+      const uint32_t count = ns - i0 < per_round ? ns - i0 : per_round;
+      D.u0 = S.i0 = i0;
+      D.count = S.count = count;
+      const uint32_t entry_blocks = (uint32_t)(((uint64_t)count * kWinEntries + 255) / 256);
+      const uint32_t unit_blocks = (count + 255u) / 256u;
+      hipLaunchKernelGGL(gzfile_seek_seed_kernel, dim3(unit_blocks), dim3(256), 0, c->stream, Z);
+      hipLaunchKernelGGL(gzfile_seek_load_kernel, dim3((entry_blocks + 15u) / 16u), dim3(256), 0, c->stream, Z);
+      hipLaunchKernelGGL(one_tail_kernel, dim3(count), dim3(64), 0, c->stream, D);
+      int cur = 0;
+      for (uint32_t s = 1; s < count; s <<= 1, cur ^= 1)
+        hipLaunchKernelGGL(one_seek_compose_kernel, dim3(entry_blocks), dim3(256), 0, c->stream, D.F[cur], D.F[cur ^ 1],
+                           S.seed, count, s);
+      hipLaunchKernelGGL(one_seek_resolve_kernel, dim3(entry_blocks), dim3(256), 0, c->stream, D.F[cur], D.R, S.seed, count);
+      // DECODE: the round's units as spliced pieces with dictionaries, each with its own end, into their dense slots;
+      // bits are counted from the file's first byte and nothing at or behind the last trailer is read
+      InfParams I{};
+      I.in = d_in;
+      I.in_len = in_len - kGzipTrailerLen;
+      I.bit_off = S.p_bit_off;
+      I.bit_end = S.p_bit_end;
+      I.n_streams = count;
+      I.out = d_dense;
+      I.out_off = Q.sel_at + i0;
+      I.out_len = d_dl;
+      I.status = d_ds;
+      I.err_off = d_de;
+      I.dict_buf = D.R;
+      I.dict_at = S.p_dict_at;
+      I.dict_len = S.p_dict_len;
+      if ((rc = launch_decoders(c, inflate_route_units(c->inflate, c->num_cus, count), I, true))) return rc;
+      used[FLATE_HIP_STAGE_INFLATE] = true;
+      hipLaunchKernelGGL(one_seek_check_kernel, dim3(unit_blocks), dim3(256), 0, c->stream, S);
+      HIP_TRY(c, hipGetLastError());
+      // the window behind the round's last unit is the carried seed of a segment that continues
+      if (i0 + count < ns)
+        HIP_TRY(c, hipMemcpyAsync(D.R, D.R + (size_t)count * kWinEntries, kWinEntries, hipMemcpyDeviceToDevice, c->stream));
+    }
+
+    // the gather: every range's run of the scratch to its place in out
+    const uint64_t pieces = (RH.out_total + (uint64_t)kBgzfGatherRangeCost * nr + kBgzfGatherWindow - 1) / kBgzfGatherWindow;
+    if (pieces > 0x7fffffffull) return FLATE_HIP_E_TOO_LARGE;
+    BgzfGatherParams GP{};
+    GP.scratch = d_dense;
+    GP.out = d_out;
+    GP.r_out_off = Q.r_out_off;
+    GP.r_src = Q.r_src;
+    GP.n_ranges = nr;
+    hipLaunchKernelGGL(bgzf_gather_kernel, dim3((uint32_t)pieces), dim3(256), 0, c->stream, GP);
+    HIP_TRY(c, hipGetLastError());
+    std::vector<int32_t> st(ns);
+    HIP_TRY(c, hipMemcpyAsync(st.data(), S.u_status, (size_t)ns * 4, hipMemcpyDeviceToHost, c->stream));
+    if (!dev) HIP_TRY(c, hipMemcpyAsync(out, d_out, RH.out_total, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (c->profiling && (rc = collect_timing(c, used))) return rc;
+
+    // the statuses: nxt[i] = the first decoded unit at or behind place i with a status
+    std::vector<uint32_t> nxt((size_t)ns + 1);
+    nxt[ns] = ns;
+    for (uint32_t i = ns; i-- > 0;) nxt[i] = st[i] ? i : nxt[i + 1];
+    if (range_status)
+      for (uint32_t r = 0; r < nr; ++r)
+        if (r_lo[r] < r_hi[r] && r_hi[r] <= ns && nxt[r_lo[r]] < r_hi[r]) range_status[r] = st[nxt[r_lo[r]]];
+    if (nxt[0] < ns) {
+      if (bad_unit) *bad_unit = sel[nxt[0]];
+      return st[nxt[0]];
+    }
+    return FLATE_HIP_OK;
+  } catch (const std::exception &e) {
+    c->hip_err = e.what();
+    return FLATE_HIP_E_INTERNAL;
+  }
+}
+
 }  // extern "C"
 
 // ---- one long stream decoded in pieces (Decompressor::read as the reference behaves: the caller

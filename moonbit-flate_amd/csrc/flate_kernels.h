@@ -719,6 +719,59 @@ __global__ void gzfile_pieces_kernel(GzFileDecParams G);
 __global__ void gzfile_trailer_kernel(GzFileDecParams G);
 __global__ void gzfile_verdict_kernel(GzFileDecParams G);
 
+// The seek index of a gzip FILE (gzfile_seek_kernels.hip; flate_hip_gzfile_seek_index / _ranges; the rule and the
+// index's layout: gzfile_seek_rule.h).  Locate, select, layout, compose, resolve, check, TAIL and the gather are the
+// kernels above, unchanged: they see the file's units as the units of one stream.
+// BUILD.  gzfile_seek_points_kernel (POINTS, one workgroup): the point rule with the discovery's member-start mark per
+// unit, scan, compact -> point_unit, counts[0] = points, counts[1] = windows.  gzfile_seek_pack_kernel (PACK): the
+// round's points p_lo .. p_lo + np - 1 as runs of R for bgzf_gather_kernel; a member start is a run of NO bytes, so the
+// window-bearing points land one behind the other from block gzfile_seek_blocks_before(p_lo) on (r_out_off counts from
+// that block; entry np: np_all == p_lo + np ? all windows : the blocks in front of point p_lo + np).
+struct GzSeekPointsParams {
+  const uint64_t *out_off;   // n + 1
+  const uint64_t *u_start;   // n: != 0 where the unit starts a member (GzFileParams::u_start)
+  uint32_t n;
+  uint64_t span;             // >= 1
+  uint64_t *point_unit;      // n entries of room
+  uint32_t *counts;          // 2
+};
+struct GzSeekPackParams {
+  const uint64_t *point_unit;
+  const uint64_t *member_unit;  // m + 1
+  uint32_t m, n_points;
+  uint32_t p_lo, np, u0;
+  uint64_t *r_out_off;       // np + 1
+  uint64_t *r_src;           // np
+};
+__global__ void gzfile_seek_points_kernel(GzSeekPointsParams P);
+__global__ void gzfile_seek_pack_kernel(GzSeekPackParams P);
+// READ.  gzfile_seek_members_kernel: one thread per member, its header must end where the index has its first unit --
+// an ordered min of the members that miss into *bad_member (0xffffffff: none).  gzfile_seek_rel_kernel: one thread per
+// unit, rel[k] = out_off[k] - out_off[f(k)]: TAIL's out_off.  Per round of the unit list: gzfile_seek_seed_kernel
+// (one_seek_seed_kernel's seed; the piece from the index, its end ~0 where the unit runs to BFINAL, its history
+// min(32768, rel)) and gzfile_seek_load_kernel (the stored window of each of the round's points into its R slot by the
+// block formula; a member start's slot is ZERO-FILLED; place 0 of a segment that continues is left alone).
+struct GzSeekParams {
+  OneSeekParams Q;           // the file's units as one stream's
+  const uint8_t *in;
+  uint64_t in_len;
+  const uint64_t *member_off;   // m + 1
+  const uint64_t *member_unit;  // m + 1
+  uint32_t m;
+  uint64_t *rel;             // n + 1
+  uint32_t *bad_member;
+};
+struct GzSeekRoundParams {
+  OneSeekRoundParams S;
+  const uint64_t *member_unit;  // m + 1
+  uint32_t m;
+  const uint64_t *rel;       // n + 1
+};
+__global__ void gzfile_seek_members_kernel(GzSeekParams G);
+__global__ void gzfile_seek_rel_kernel(GzSeekParams G);
+__global__ void gzfile_seek_seed_kernel(GzSeekRoundParams S);
+__global__ void gzfile_seek_load_kernel(GzSeekRoundParams S);
+
 size_t inflate_simt_lds_bytes(int lanes_per_wave);  // dynamic LDS of that launch
 size_t inflate_simt_lens_bytes(uint32_t blocks);    // global scratch of that launch (InfParams::simt_lens)
 

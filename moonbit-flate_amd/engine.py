@@ -67,6 +67,8 @@ GzFileIndex = collections.namedtuple("GzFileIndex", "rc n_units n_members out_by
                                      "stream_err_off unit_bit out_off member_off member_unit")
 GzFileRead = collections.namedtuple("GzFileRead", "rc out_len n_members n_units n_candidates status bad_member err_off "
                                     "stream_err_off")
+GzFileSeekIndex = collections.namedtuple("GzFileSeekIndex", "rc index windows n_units n_members n_points out_bytes "
+                                         "n_candidates status bad_member err_off stream_err_off")
 
 # flate_hip_zip_entry, as numpy sees it (64 bytes)
 ZIP_ENTRY = np.dtype([("name_off", "<u8"), ("header_off", "<u8"), ("data_off", "<u8"), ("comp_size", "<u8"), ("size", "<u8"),
@@ -432,7 +434,85 @@ class GzFileCalls:
         return _read_into(out, data, out_cap, "gzfile_read", call, size)
 
 
-class FlateEngine(OneSeekCalls, GzFileCalls):
+class GzFileSeekCalls:
+    """The seek index of a gzip file of any members: the two methods FlateEngine inherits.  They stand in a class of
+    their own so that their marshalling has its own recorded scenarios (tests/engine_trace_gzfile_seek.py) beside the
+    ones of the methods that were there before."""
+
+    def gzfile_seek_index(self, data, span=0):
+        """The seek index of a gzip file of ANY members (flate_hip_gzfile_seek_index) -> GzFileSeekIndex(rc, index,
+        windows, n_units, n_members, n_points, out_bytes, n_candidates, status, bad_member, err_off, stream_err_off).
+        index: numpy uint64, the self-describing words the header documents; windows: n_points - n_members blocks of
+        32768 bytes (a point that starts a member has none), numpy for host data, a torch CUDA tensor for device data.
+        span: a point per that many bytes of output besides every member start (0: 1 MiB; SEEK_SPAN_NONE: the member
+        starts alone, no windows).  status and the three words behind it are gzfile_index's, trailers are not judged; a
+        file that fails has no index (index and windows are None).  Sized by a guess and one retry, not by a query
+        first: the discovery is most of the cost.  Other failures raise FlateError."""
+        data, in_ptr, n, device = _in_buf(data, accept_bytes=True, null_if_empty=True)
+        iw, wb, nu, nm, npts = C.c_uint64(0), C.c_uint64(0), C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
+        ob, nc, st = C.c_uint64(0), C.c_uint32(0), C.c_int32(0)
+        bad, eo, seo = C.c_uint32(0), C.c_int64(-1), C.c_int64(-1)
+        # a unit per 256 bytes and a member per 4096 bytes of input; the windows of a file that inflates fourfold
+        words = 16 + 2 * (n // 256 + 64) + 2 * (n // 4096 + 64) + 64
+        room = 0 if span == SEEK_SPAN_NONE else min(4 * n // (span or SEEK_SPAN_DEFAULT) + 4, n // 256 + 64) * 32768
+        for _ in range(2):
+            index = np.zeros(words, dtype=np.uint64)
+            windows, w_ptr, _ = _out_buf(None, data, room, None, 0, "gzfile_seek_index", floor=1)
+            rc = self._tolerate(self._L.flate_hip_gzfile_seek_index(
+                self._ctx, in_ptr, n, span, index.ctypes.data, words, C.byref(iw), w_ptr, room, C.byref(wb),
+                C.byref(nu), C.byref(nm), C.byref(npts), C.byref(ob), C.byref(nc), C.byref(st), C.byref(bad),
+                C.byref(eo), C.byref(seo), self._flags(False, False, device)), *PER_CHAIN)
+            if rc != E_OUT_TOO_SMALL:
+                break
+            words, room = int(iw.value), int(wb.value)
+        ok = rc == 0
+        return GzFileSeekIndex(rc, index[:int(iw.value)].copy() if ok else None,
+                               windows[:int(wb.value)] if ok else None, int(nu.value), int(nm.value), int(npts.value),
+                               int(ob.value), int(nc.value), int(st.value), int(bad.value), int(eo.value),
+                               int(seo.value))
+
+    def gzfile_ranges(self, data, seek_index, begin, end, out=None, out_cap=None):
+        """Random access into a gzip file of any members through its seek index (flate_hip_gzfile_ranges): the bytes of
+        the ranges [begin[r], end[r]) of what zcat gives, back to back in out; a range may cross members; only the
+        units from the seek point in front of a range up to its end are decoded.  seek_index: what gzfile_seek_index
+        returned (its windows on the side of data), or an (index, windows) pair.  Returns (out, OneRanges(rc, out_off,
+        range_status, n_decoded, bad_unit)): range r is out[out_off[r]:out_off[r + 1]].  rc 0; -4 with every
+        range_status -4: some member's header is not where the index has it; -2 with out_off[-1] > capacity: out too
+        small, nothing decoded; else the first decoded unit the index does not fit, in bad_unit.  out=None: sized by
+        the size query first.  An index that is refused, begin[r] > end[r] and other refusals raise FlateError."""
+        data, in_ptr, n, device = _in_buf(data, accept_bytes=True, null_if_empty=True)
+        index, windows = (seek_index.index, seek_index.windows) if isinstance(seek_index, GzFileSeekIndex) else seek_index
+        index = np.ascontiguousarray(index, dtype=np.uint64)
+        if windows is None or (windows.numel() if _is_torch(windows) else windows.size) == 0:
+            w_ptr, wb = None, 0
+        else:
+            windows, w_ptr, wb, w_dev = _in_buf(windows)
+            if w_dev != device:
+                raise FlateError(E_INVALID, "gzfile_ranges: the windows must be on the side of the data")
+        begin = np.ascontiguousarray(begin, dtype=np.uint64)
+        end = np.ascontiguousarray(end, dtype=np.uint64)
+        if begin.ndim != 1 or begin.shape != end.shape:
+            raise FlateError(E_INVALID, "gzfile_ranges: begin and end must be one-dimensional and of one length")
+        nr = begin.size
+        out_off = np.zeros(nr + 1, dtype=np.uint64)
+        status = np.zeros(max(nr, 1), dtype=np.int32)
+        nd, bad = C.c_uint32(0), C.c_uint32(0)
+
+        def call(out_ptr, cap):
+            rc = self._tolerate(self._L.flate_hip_gzfile_ranges(
+                self._ctx, in_ptr, n, index.ctypes.data, index.size, w_ptr, wb, begin.ctypes.data, end.ctypes.data, nr,
+                out_ptr, cap, out_off.ctypes.data, status.ctypes.data, C.byref(nd), C.byref(bad),
+                self._flags(False, False, device)), *PER_CHAIN)
+            return OneRanges(rc, out_off, status[:nr], int(nd.value), int(bad.value))
+
+        def size():  # the size query: nothing is decoded
+            q = call(None, 0)
+            return (int(out_off[nr]), None) if q.rc == E_OUT_TOO_SMALL else (0, q)
+
+        return _read_into(out, data, out_cap, "gzfile_ranges", call, size)
+
+
+class FlateEngine(OneSeekCalls, GzFileCalls, GzFileSeekCalls):
     """One engine = one flate_hip_ctx = one GPU + one HIP stream."""
 
     def __init__(self, device=0):

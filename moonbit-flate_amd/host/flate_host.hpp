@@ -1214,6 +1214,90 @@ inline Err decompress_one_ranges(Engine &e, const std::vector<uint8_t> &stream, 
   return make_error(e, rc);
 }
 
+// What seek_index_gzfile built: the seek index of a gzip file of ANY members, to keep beside the file and hand to
+// decompress_gzfile_ranges.
+struct GzFileSeekIndex {
+  std::vector<uint64_t> index;   // the self-describing words (include/flate_hip.h documents the layout)
+  std::vector<uint8_t> windows;  // n_points - n_members blocks of 32768 bytes: a point that starts a member has none
+  uint32_t n_units = 0, n_members = 0, n_points = 0;
+  uint64_t out_bytes = 0;        // what the file inflates to
+  uint32_t n_candidates = 0;
+  uint32_t bad_member = 0xffffffffu;
+  int64_t err_off = -1;          // where the failing member starts, or where no member can start
+  int64_t stream_err_off = -1;   // the serial decoder's offset, counted from that member's raw stream
+  int status = 0;                // the FLATE_HIP_E_* code behind the error (0 = none)
+};
+
+// seek_index_gzfile: the seek index of a gzip file of any members: a point at every member's first unit and per `span`
+// bytes of output (0: 1 MiB; FLATE_HIP_SEEK_SPAN_NONE: the member starts alone, no windows), built on the GPU
+// (flate_hip_gzfile_seek_index; sized by a guess and one retry, as index_gzfile).  Errors are index_gzfile's and a
+// distance in front of its member; trailers are not judged; a file that fails has no index.
+inline Err seek_index_gzfile(Engine &e, const std::vector<uint8_t> &file, uint64_t span, GzFileSeekIndex &sx) {
+  if (!e.ok()) return make_error(e, e.status());
+  sx = GzFileSeekIndex();
+  int32_t st = 0;
+  int rc = 0;
+  uint64_t words = 16 + 2 * (file.size() / 256 + 64) + 2 * (file.size() / 4096 + 64) + 64, bytes = 0, got_words = 0,
+           got_bytes = 0;
+  if (span != FLATE_HIP_SEEK_SPAN_NONE)
+    bytes = std::min<uint64_t>(4 * (uint64_t)file.size() / (span ? span : FLATE_HIP_SEEK_SPAN_DEFAULT) + 4,
+                               file.size() / 256 + 64) * FLATE_HIP_SEEK_WINDOW_BYTES;  // (never more points than units)
+  for (int attempt = 0; attempt < 2; ++attempt) {
+    sx.index.assign(words, 0);
+    sx.windows.assign(bytes + 1, 0);
+    rc = flate_hip_gzfile_seek_index(e.ctx(), file.data(), file.size(), span, sx.index.data(), words, &got_words,
+                                     sx.windows.data(), bytes, &got_bytes, &sx.n_units, &sx.n_members, &sx.n_points,
+                                     &sx.out_bytes, &sx.n_candidates, &st, &sx.bad_member, &sx.err_off, &sx.stream_err_off, 0);
+    if (rc != FLATE_HIP_E_OUT_TOO_SMALL) break;
+    words = got_words, bytes = got_bytes;
+  }
+  sx.index.resize(rc == 0 ? got_words : 0);
+  sx.windows.resize(rc == 0 ? got_bytes : 0);
+  sx.status = rc;
+  if (rc == 0) return std::nullopt;
+  if (rc == FLATE_HIP_E_CORRUPT) return corrupt_input_error(sx.err_off);
+  if (rc == FLATE_HIP_E_UNEXPECTED_EOF) return err_unexpected_eof();
+  return make_error(e, rc);
+}
+
+// decompress_gzfile_ranges: random access into a gzip file of any members through its seek index
+// (flate_hip_gzfile_ranges) -- the bytes of `ranges` of what zcat gives, back to back in `out`; a range may cross
+// members; the size comes from the call's size query.  Errors: make_error(FLATE_HIP_E_INVALID) for an index that is
+// not sound or not of this file's length, corrupt_input_error(-1) for a file whose members are not where the index has
+// them or that the index does not fit (info->range_status says which ranges are exact all the same).
+inline Err decompress_gzfile_ranges(Engine &e, const std::vector<uint8_t> &file, const GzFileSeekIndex &sx,
+                                    const std::vector<OneRange> &ranges, std::vector<uint8_t> &out,
+                                    OneRangesInfo *info = nullptr) {
+  if (!e.ok()) return make_error(e, e.status());
+  OneRangesInfo I;
+  const uint32_t nr = (uint32_t)ranges.size();
+  std::vector<uint64_t> begin(nr), end(nr);
+  for (uint32_t r = 0; r < nr; ++r) begin[r] = ranges[r].begin, end[r] = ranges[r].end;
+  I.out_off.assign((size_t)nr + 1, 0);
+  I.range_status.assign(nr, 0);
+  out.clear();
+  auto call = [&](uint8_t *buf, uint64_t cap) {
+    return flate_hip_gzfile_ranges(e.ctx(), file.data(), file.size(), sx.index.data(), sx.index.size(),
+                                   sx.windows.empty() ? nullptr : sx.windows.data(), sx.windows.size(), begin.data(),
+                                   end.data(), nr, buf, cap, I.out_off.data(), I.range_status.data(), &I.n_decoded,
+                                   &I.bad_unit, 0);
+  };
+  int rc = call(nullptr, 0);  // the size query
+  if (rc == FLATE_HIP_E_OUT_TOO_SMALL) {
+    const uint64_t need = I.out_off[nr];
+    std::vector<uint8_t> buf(need + 8);
+    rc = call(buf.data(), need);
+    if (rc != FLATE_HIP_E_INVALID && rc != FLATE_HIP_E_HIP && rc != FLATE_HIP_E_INTERNAL)
+      out.assign(buf.begin(), buf.begin() + std::min<uint64_t>(I.out_off[nr], need));
+  }
+  I.status = rc;
+  if (info) *info = I;
+  if (rc == 0) return std::nullopt;
+  if (rc == FLATE_HIP_E_CORRUPT) return corrupt_input_error(-1);
+  if (rc == FLATE_HIP_E_UNEXPECTED_EOF) return err_unexpected_eof();
+  return make_error(e, rc);
+}
+
 // One range of decompress_bgzf_ranges: positions in the file's uncompressed bytes, or -- virtual_offsets -- BGZF
 // virtual offsets (coffset << 16 | uoffset, as BAM, tabix and CSI indexes store them).
 struct BgzfRange {
