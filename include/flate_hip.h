@@ -125,6 +125,13 @@ int flate_hip_set_stream(flate_hip_ctx *ctx, void *hip_stream);
  *   "stream_rebase_bytes"  flate_hip_stream_*: a stream longer than this moves the origin of the
  *                        32-bit positions its kernels count in (all distances stay what they were);
  *                        default 1 GiB, read when the stream is opened; results never change
+ *   "one_stored_units"   flate_hip_inflate_one* and flate_hip_gzfile_*: 0 (default) = a unit starts at bit 0
+ *                        and at every dynamic block header; 1 = at every STORED block header too, so that a
+ *                        run of stored blocks (incompressible data) is many units instead of one: it is
+ *                        decoded in parallel, each unit has "one_unit_max" to itself, and seek points fall
+ *                        inside it.  Bytes, status and err_off never change; unit_bit, out_off, n_units and
+ *                        n_candidates do.  A seek index records the rule it was built with and is read
+ *                        with that rule whatever the reading ctx's option says
  *   "debug_buffer_reset"  test hook: buffer_reset (deflate-fast.mbt:55) of the streams opened from now
  *                        on, so that the reference's shift_offsets can be reached in a few windows
  *                        instead of after 2.1 GB (0 = the reference's value)
@@ -739,7 +746,13 @@ int flate_hip_gzip_read(flate_hip_ctx *ctx, const uint8_t *in, uint64_t in_len, 
  * are counted from the RAW stream's first byte.
  *
  * UNITS.  A unit starts at bit 0 and at every dynamic block header (BTYPE = 2) the serial decode reaches; stored and
- * fixed blocks belong to the unit in front of them, so a stream made only of them is one unit.  On success
+ * fixed blocks belong to the unit in front of them, so a stream made only of them is one unit.  With the option
+ * "one_stored_units" at 1 UNITS reads: bit 0, every dynamic header and every STORED header (BTYPE = 0) that the serial
+ * decode reaches; only fixed blocks then belong to the unit in front of them, a stream of stored blocks of any total
+ * length is accepted (the limit below is per unit), and a unit of zero output bytes -- an empty stored block of
+ * Z_SYNC_FLUSH, Z_FULL_FLUSH or pigz -- is a unit like any other.  A stored header is found by its LEN / NLEN pair
+ * (csrc/deflate_block_rule.h: BTYPE = 0, the padding bits unread, four bytes inside the stream, LEN == ~NLEN), so up to
+ * 8 bit offsets in front of one aligned pair are candidates, at most one of them on the path.  On success
  * unit_bit[0 .. n] (unit_bit[n] = the bit behind the final block) and out_off[0 .. n] (the exclusive prefix sum of what
  * the units inflate to) describe the stream; *out_bytes = out_off[n]; *status = 0; *err_off = -1.
  *
@@ -801,7 +814,8 @@ int flate_hip_gzip_read(flate_hip_ctx *ctx, const uint8_t *in, uint64_t in_len, 
  *   the checksum kernels over out[0, total) in 64 KiB pieces and a verdict kernel.  No kernel waits for another
  *   workgroup.  Profiling: FLATE_HIP_STAGE_INFLATE is DECODE (of several rounds the last),
  *   FLATE_HIP_STAGE_CHECKSUM is VERIFY; FIND, PROBE, LINK, TAIL and COMPOSE are counted in no stage.
- *   Out of scope: finding stored or fixed block starts (streams made of them stay serial inside one unit); fusing
+ *   Out of scope: finding fixed block starts (a fixed block has no header beyond its three bits, so there is nothing
+ *   to test: runs of them stay serial inside one unit; stored block starts: option "one_stored_units"); fusing
  *   PROBE with TAIL; routing long members of flate_hip_gzip_read here; multi-member input (flate_hip_gzfile_read);
  *   caching the index across calls (the seek index below is what a caller keeps). */
 int flate_hip_inflate_one(flate_hip_ctx *ctx, const uint8_t *in, uint64_t in_len, uint32_t wrap, uint8_t *out,
@@ -830,7 +844,9 @@ int flate_hip_inflate_one_index(flate_hip_ctx *ctx, const uint8_t *in, uint64_t 
  * TWO BUFFERS.  index: a HOST array of 64-bit words (offset tables are always host arrays in this ABI):
  *   word 0 the magic "FONESIDX" (little endian), 1 the version (1), 2 wrap, 3 in_len, 4 the raw stream's first byte, 5
  *   the byte behind it, 6 T, 7 span, 8 n, 9 n_points, 10 / 11 the container's trailer words as the device parses them
- *   (the checksum as a number and ISIZE; 0 for raw), 12 .. 15 zero;
+ *   (the checksum as a number and ISIZE; 0 for raw), 12 the unit rule the index was built with (0: dynamic headers
+ *   start units; 1: dynamic and stored headers, option "one_stored_units" -- flate_hip_inflate_one_ranges walks the units
+ *   by THIS word and ignores its ctx's option; any other value: FLATE_HIP_E_INVALID), 13 .. 15 zero;
  *   then unit_bit[n + 1], out_off[n + 1], point_unit[n_points] (rising, point_unit[0] = 0):
  *   16 + 2 (n + 1) + n_points words.
  * windows: host, or device under FLATE_HIP_DEVICE_PTRS like in, at any byte alignment: n_points - 1 blocks of 32768
@@ -990,7 +1006,8 @@ int flate_hip_inflate_one_ranges(flate_hip_ctx *ctx, const uint8_t *in, uint64_t
  *   rounds the last), FLATE_HIP_STAGE_CHECKSUM is VERIFY; the rest is counted in no stage.
  *   Out of scope: zlib or raw concatenations; routing
  *   flate_hip_gzip_read or flate_hip_inflate_one here automatically; choosing per member between the serial and the
- *   unit decoder; stored or fixed block starts as units; caching across calls. */
+ *   unit decoder; fixed block starts as units (stored ones: option "one_stored_units"; a member's first unit starts
+ *   behind its header whatever block is there, and the hop behind BFINAL is unchanged); caching across calls. */
 int flate_hip_gzfile_index(flate_hip_ctx *ctx, const uint8_t *in, uint64_t in_len, uint64_t index_cap,
                            uint64_t *unit_bit, uint64_t *out_off, uint64_t member_cap, uint64_t *member_off,
                            uint64_t *member_unit, uint32_t *n_units, uint32_t *n_members, uint64_t *out_bytes,
@@ -1021,7 +1038,9 @@ int flate_hip_gzfile_read(flate_hip_ctx *ctx, const uint8_t *in, uint64_t in_len
  * stream order; bytes in front of the member's first byte are 0 -- never the bytes of the member in front, although
  * those lie right there in U.  `windows` is host, or device under FLATE_HIP_DEVICE_PTRS like in, at any byte alignment.
  * INDEX: a HOST array of 64-bit words: word 0 the magic "FGZFSIDX" (little endian), 1 the version (1), 2 in_len, 3 T,
- * 4 span, 5 n, 6 m, 7 n_points, 8 .. 15 zero; then unit_bit[n + 1], out_off[n + 1], member_off[m + 1],
+ * 4 span, 5 n, 6 m, 7 n_points, 8 the unit rule the index was built with (0 or 1 as in word 12 of the one-stream index:
+ * flate_hip_gzfile_ranges walks by it, any other value is FLATE_HIP_E_INVALID), 9 .. 15 zero; then unit_bit[n + 1],
+ * out_off[n + 1], member_off[m + 1],
  * member_unit[m + 1], point_unit[n_points]: 16 + 2 (n + 1) + 2 (m + 1) + n_points words.  The empty file (in_len == 0):
  * the 16 head words alone, n = m = n_points = 0, no windows.
  *

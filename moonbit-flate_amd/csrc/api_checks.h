@@ -155,6 +155,8 @@ inline int gzip_read_args(const uint8_t *in, uint64_t in_len, const uint8_t *out
 // the option "one_unit_max": the bytes a unit's input spans at most, 1 .. 2^28 (the default, which a caller can only
 // lower: the decoders' positions inside one unit are 32 bits wide)
 inline bool one_unit_max_ok(int64_t value) { return value >= 1 && value <= (1ll << 28); }
+// the option "one_stored_units": the unit rule, 0 (dynamic headers start units: the default) or 1 (stored headers too)
+inline bool one_stored_units_ok(int64_t value) { return value == 0 || value == 1; }
 // unit_bit and out_off come together or not at all (the count query); the input is ONE raw, zlib or gzip stream
 inline int one_index_args(const uint8_t *in, uint64_t in_len, uint32_t wrap, const uint64_t *unit_bit,
                           const uint64_t *out_off, const uint32_t *n_units, const uint64_t *out_bytes,
@@ -210,7 +212,8 @@ inline int one_ranges_args(const uint8_t *in, uint64_t in_len, uint32_t wrap, co
   const int rc = bgzf_ranges_args(in, in_len, FLATE_HIP_BGZF_POS_BYTES, begin, end, n_ranges, out, out_cap, out_off, flags);
   if (rc) return rc;
   if (wrap > FLATE_HIP_WRAP_GZIP || (windows_bytes && !windows)) return FLATE_HIP_E_INVALID;
-  return seek_index_ok(index, index_words, windows_bytes, wrap, in_len) ? FLATE_HIP_OK : FLATE_HIP_E_INVALID;
+  return seek_index_ok(index, index_words, windows_bytes, wrap, in_len) && seek_index_rule_ok(index) ? FLATE_HIP_OK
+                                                                                                     : FLATE_HIP_E_INVALID;
 }
 
 // ---- the seek index of a gzip file of any members (flate_hip_gzfile_seek_index / _ranges; gzfile_seek_rule.h) ----
@@ -235,7 +238,9 @@ inline int gzfile_ranges_args(const uint8_t *in, uint64_t in_len, const uint64_t
   const int rc = bgzf_ranges_args(in, in_len, FLATE_HIP_BGZF_POS_BYTES, begin, end, n_ranges, out, out_cap, out_off, flags);
   if (rc) return rc;
   if (windows_bytes && !windows) return FLATE_HIP_E_INVALID;
-  return gzfile_seek_index_ok(index, index_words, windows_bytes, in_len) ? FLATE_HIP_OK : FLATE_HIP_E_INVALID;
+  return gzfile_seek_index_ok(index, index_words, windows_bytes, in_len) && gzfile_seek_index_rule_ok(index)
+             ? FLATE_HIP_OK
+             : FLATE_HIP_E_INVALID;
 }
 
 // ---- ZIP archives (flate_hip_zip_write / _index / _read) ----

@@ -165,6 +165,27 @@ DBLK_HD bool deflate_dyn_header_ok(const uint8_t *raw, uint64_t raw_len, uint64_
   return dblk_code_ok(lit) && dblk_code_ok(dist);
 }
 
+// THE STORED RULE (option "one_stored_units").  true: read_block_header followed by read_stored_len of
+// inflate_kernels.hip take the block header at `bit` as a stored block's -- BTYPE = 0 with either BFINAL; behind the
+// header's three bits the reader drops the rest of their byte UNREAD, so the padding bits are not examined here either
+// (a rule that asked for zeros would refuse a true header and leave a hole in the chain); the four bytes from
+// q = (bit + 3 + 7) / 8 on lie inside the raw range, and LEN (the first two) is the complement of NLEN.  LEN = 0 is a
+// header.  Whether the LEN data bytes lie inside the stream is not judged: the probe reports
+// FLATE_HIP_E_UNEXPECTED_EOF there, as the serial decoder does.  No byte at or behind raw + raw_len is read.
+// A consequence: up to 8 bit offsets in front of ONE aligned LEN / NLEN pair pass -- the bits 5 .. 7 of byte q - 2 and
+// 0 .. 4 of byte q - 1, wherever the two bits behind them are 0.  At most one of them is on the path; the others are
+// decoys like any other.
+DBLK_HD bool deflate_stored_header_ok(const uint8_t *raw, uint64_t raw_len, uint64_t bit) {
+  if (bit > ~0ull - 10u) return false;
+  const uint64_t b = bit >> 3, q = (bit + 3u + 7u) >> 3;
+  if (q > raw_len || raw_len - q < 4u) return false;  // (b < q: the header's bits lie inside as well)
+  uint32_t w = raw[b];
+  if (b + 1u < q) w |= (uint32_t)raw[b + 1u] << 8;  // (bits 6 and 7 of a byte: BTYPE reaches into the next one)
+  if (((w >> ((bit & 7u) + 1u)) & 3u) != 0u) return false;
+  const uint32_t len = raw[q] | ((uint32_t)raw[q + 1u] << 8), nlen = raw[q + 2u] | ((uint32_t)raw[q + 3u] << 8);
+  return (len ^ nlen) == 0xffffu;
+}
+
 // A unit's input spans less than this many bytes (option "one_unit_max" lowers it): the wave decoders count bytes of
 // one stream in 32 bits and the lane decoders bits
 constexpr uint64_t kOneUnitMax = 1ull << 28;

@@ -371,6 +371,8 @@ int flate_hip_set_option(flate_hip_ctx *c, const char *name, int64_t value) {
     c->gzip_member_max = (uint64_t)value;
   } else if (k == "one_unit_max" && one_unit_max_ok(value)) {
     c->one_unit_max = (uint64_t)value;
+  } else if (k == "one_stored_units" && one_stored_units_ok(value)) {
+    c->one_stored_units = (uint32_t)value;
   } else if (k == "one_round_units" && one_round_units_ok(value)) {
     c->one_round_units = (uint32_t)value;
   } else {

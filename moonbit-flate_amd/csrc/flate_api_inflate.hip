@@ -1128,6 +1128,33 @@ int flate_hip_gzip_read(flate_hip_ctx *c, const uint8_t *in, uint64_t in_len, ui
 // ---- one long stream: block discovery (one_kernels.hip, one_probe_kernel.inc) ----
 namespace {
 
+// FIND's count pass or fill pass over n_tiles tiles, in the build of P's unit rule (option "one_stored_units")
+void one_find_launch(flate_hip_ctx *c, bool count, uint32_t n_tiles, const OneParams &P) {
+  if (count && P.stored_units)
+    hipLaunchKernelGGL(one_count_kernel<true>, dim3(n_tiles), dim3(256), 0, c->stream, P);
+  else if (count)
+    hipLaunchKernelGGL(one_count_kernel<false>, dim3(n_tiles), dim3(256), 0, c->stream, P);
+  else if (P.stored_units)
+    hipLaunchKernelGGL(one_fill_kernel<true>, dim3(n_tiles), dim3(256), 0, c->stream, P);
+  else
+    hipLaunchKernelGGL(one_fill_kernel<false>, dim3(n_tiles), dim3(256), 0, c->stream, P);
+}
+
+// PROBE over n_blocks candidates (or the one tail probe) and TAIL over a round's units, in the build of the unit rule
+// their parameters carry -- the same word for both, so they stop at the same bits
+void one_probe_launch(flate_hip_ctx *c, uint32_t n_blocks, const OneParams &P, uint32_t tail) {
+  if (P.stored_units)
+    hipLaunchKernelGGL(one_probe_kernel<true>, dim3(n_blocks), dim3(64), 0, c->stream, P, tail);
+  else
+    hipLaunchKernelGGL(one_probe_kernel<false>, dim3(n_blocks), dim3(64), 0, c->stream, P, tail);
+}
+void one_tail_launch(flate_hip_ctx *c, uint32_t n_blocks, const OneDecParams &D) {
+  if (D.stored_units)
+    hipLaunchKernelGGL(one_tail_kernel<true>, dim3(n_blocks), dim3(64), 0, c->stream, D);
+  else
+    hipLaunchKernelGGL(one_tail_kernel<false>, dim3(n_blocks), dim3(64), 0, c->stream, D);
+}
+
 // The discovery over the ONE stream d_in[0, in_len) (DEVICE memory) on the ctx's stream: the container's header, count
 // and scan, ONE read-back of the candidate count (the launches behind it have a thread or a wavefront per candidate),
 // then fill, probe, link, rounds, finish, out-scan, the tail probe and ONE read-back of the result words H with the
@@ -1144,6 +1171,7 @@ int one_discover(flate_hip_ctx *c, const uint8_t *d_in, uint64_t in_len, uint32_
   C.in = d_in;
   C.in_len = in_len;
   P.unit_max = c->one_unit_max;
+  P.stored_units = c->one_stored_units;
   if ((rc = tiles_for(d_in, 0, in_len, &C.n_tiles))) return rc;
   rc = carve(c, c->d_one_tiles, [&](Carve &k) {
     k.take(P.head, 1);
@@ -1167,7 +1195,7 @@ int one_discover(flate_hip_ctx *c, const uint8_t *d_in, uint64_t in_len, uint32_
     R.dict_used = &P.one->dict_used;
     hipLaunchKernelGGL(frame_parse_kernel, dim3(1), dim3(256), 0, c->stream, R);
   }
-  hipLaunchKernelGGL(one_count_kernel, dim3(C.n_tiles), dim3(256), 0, c->stream, P);
+  one_find_launch(c, true, C.n_tiles, P);
   hipLaunchKernelGGL(chain_scan_kernel, dim3(1), dim3(1024), 0, c->stream, C);
   HIP_TRY(c, hipGetLastError());
   HIP_TRY(c, hipMemcpyAsync(&H, P.head, sizeof H, hipMemcpyDeviceToHost, c->stream));
@@ -1188,10 +1216,10 @@ int one_discover(flate_hip_ctx *c, const uint8_t *d_in, uint64_t in_len, uint32_
     k.take(C.out_off, n + 1);
   });
   if (rc) return rc;
-  hipLaunchKernelGGL(one_fill_kernel, dim3(C.n_tiles), dim3(256), 0, c->stream, P);
-  hipLaunchKernelGGL(one_probe_kernel, dim3(cap), dim3(64), 0, c->stream, P, 0u);
+  one_find_launch(c, false, C.n_tiles, P);
+  one_probe_launch(c, cap, P, 0u);
   if ((rc = chain_tail(c, C, one_link_kernel, P, one_finish_kernel, one_out_scan_kernel, P))) return rc;
-  hipLaunchKernelGGL(one_probe_kernel, dim3(1), dim3(64), 0, c->stream, P, 1u);
+  one_probe_launch(c, 1, P, 1u);
   HIP_TRY(c, hipGetLastError());
   // ONE read-back behind the count: the result words, then 16 bytes per unit
   const size_t take = (size_t)(index_cap < n + 1 ? index_cap : n + 1);
@@ -1209,7 +1237,7 @@ int one_discover(flate_hip_ctx *c, const uint8_t *d_in, uint64_t in_len, uint32_
 // from the seed R[0] (flate_hip_inflate_one and the build of the seek index run exactly these launches).
 void one_round_windows(flate_hip_ctx *c, const OneDecParams &D) {
   const uint32_t entry_blocks = (uint32_t)(((uint64_t)D.count * kWinEntries + 255) / 256);
-  hipLaunchKernelGGL(one_tail_kernel, dim3(D.count), dim3(64), 0, c->stream, D);
+  one_tail_launch(c, D.count, D);
   int cur = 0;
   for (uint32_t s = 1; s < D.count; s <<= 1, cur ^= 1)
     hipLaunchKernelGGL(one_compose_kernel, dim3(entry_blocks), dim3(256), 0, c->stream, D.F[cur], D.F[cur ^ 1], D.count, s);
@@ -1341,7 +1369,8 @@ int flate_hip_inflate_one(flate_hip_ctx *c, const uint8_t *in, uint64_t in_len, 
     D.unit_bit = P.C.member_off;
     D.out_off = P.C.out_off;
     D.total = total;
-    D.unit_max = c->one_unit_max;
+    D.unit_max = P.unit_max;
+    D.stored_units = P.stored_units;
     D.d_status = d_ds;
     D.d_out_len = d_dl;
     D.head = P.head;
@@ -1508,7 +1537,8 @@ int flate_hip_inflate_one_seek_index(flate_hip_ctx *c, const uint8_t *in, uint64
     D.one = P.one;
     D.unit_bit = P.C.member_off;
     D.out_off = P.C.out_off;
-    D.unit_max = c->one_unit_max;
+    D.unit_max = P.unit_max;
+    D.stored_units = P.stored_units;
     HIP_TRY(c, hipMemsetAsync(D.dh, 0xff, sizeof(OneDecHead), c->stream));  // first_bad: none
     HIP_TRY(c, hipMemsetAsync(D.R, 0, kWinEntries, c->stream));            // in front of the stream: zeros
     uint32_t p_next = 1;  // the first point whose window is not packed yet (point 0 has none)
@@ -1568,6 +1598,7 @@ int flate_hip_inflate_one_seek_index(flate_hip_ctx *c, const uint8_t *in, uint64
     index[kSeekPointsAt] = np;
     index[kSeekWantAt] = one.want;
     index[kSeekIsizeAt] = one.isize;
+    index[kSeekRuleAt] = P.stored_units ? kSeekRuleStored : kSeekRuleDynamic;  // a read walks by this rule
     uint64_t *w = index + kSeekHeadWords;
     memcpy(w, found.data(), ((size_t)n + 1) * 8);
     memcpy(w + (n + 1), found.data() + found.size() / 2, ((size_t)n + 1) * 8);
@@ -1750,6 +1781,7 @@ int flate_hip_inflate_one_ranges(flate_hip_ctx *c, const uint8_t *in, uint64_t i
     D.unit_bit = Q.unit_bit;
     D.out_off = Q.out_off;
     D.unit_max = c->one_unit_max;
+    D.stored_units = index[kSeekRuleAt] == kSeekRuleStored ? 1u : 0u;  // the index's rule, not the context's option
     D.unit_list = Q.sel_unit;
     S.Q = Q;
     S.windows = d_windows;
@@ -1766,7 +1798,7 @@ int flate_hip_inflate_one_ranges(flate_hip_ctx *c, const uint8_t *in, uint64_t i
       const uint32_t unit_blocks = (count + 255u) / 256u;
       hipLaunchKernelGGL(one_seek_seed_kernel, dim3(unit_blocks), dim3(256), 0, c->stream, S);
       hipLaunchKernelGGL(one_seek_load_kernel, dim3((entry_blocks + 15u) / 16u), dim3(256), 0, c->stream, S);
-      hipLaunchKernelGGL(one_tail_kernel, dim3(count), dim3(64), 0, c->stream, D);
+      one_tail_launch(c, count, D);
       int cur = 0;
       for (uint32_t s = 1; s < count; s <<= 1, cur ^= 1)
         hipLaunchKernelGGL(one_seek_compose_kernel, dim3(entry_blocks), dim3(256), 0, c->stream, D.F[cur], D.F[cur ^ 1],
@@ -1867,13 +1899,14 @@ int gzfile_discover(flate_hip_ctx *c, const uint8_t *d_in, uint64_t in_len, OneH
   C.n_tiles = PA.C.n_tiles = PB.C.n_tiles = n_tiles;
   C.head = &P.O.head->h;
   P.O.unit_max = PA.unit_max = c->one_unit_max;
+  P.O.stored_units = PA.stored_units = c->one_stored_units;
   PA.C.head = &head_a->h;
   PA.head = head_a;
   PA.one = P.O.one;
   PB.C.head = head_b;
   PB.member_max = ~0ull;  // a member's range is never clipped
   hipLaunchKernelGGL(gzfile_init_kernel, dim3(1), dim3(64), 0, c->stream, P.O.one, in_len);
-  hipLaunchKernelGGL(one_count_kernel, dim3(n_tiles), dim3(256), 0, c->stream, PA);
+  one_find_launch(c, true, n_tiles, PA);
   hipLaunchKernelGGL(chain_scan_kernel, dim3(1), dim3(1024), 0, c->stream, PA.C);
   hipLaunchKernelGGL(gzip_count_kernel, dim3(n_tiles), dim3(256), 0, c->stream, PB);
   hipLaunchKernelGGL(chain_scan_kernel, dim3(1), dim3(1024), 0, c->stream, PB.C);
@@ -1915,12 +1948,12 @@ int gzfile_discover(flate_hip_ctx *c, const uint8_t *d_in, uint64_t in_len, OneH
   PA.C.cand_off = C.cand_off;
   PB.C.cand_off = hdr_off;
   P.hdr_off = hdr_off;
-  hipLaunchKernelGGL(one_fill_kernel, dim3(n_tiles), dim3(256), 0, c->stream, PA);
+  one_find_launch(c, false, n_tiles, PA);
   if (nb) {
     hipLaunchKernelGGL(gzip_fill_kernel, dim3(n_tiles), dim3(256), 0, c->stream, PB);
     hipLaunchKernelGGL(gzfile_bits_kernel, dim3((nb + 255) / 256), dim3(256), 0, c->stream, P);
   }
-  if (cap) hipLaunchKernelGGL(one_probe_kernel, dim3(cap), dim3(64), 0, c->stream, P.O, 0u);
+  if (cap) one_probe_launch(c, cap, P.O, 0u);
   const uint32_t node_blocks = (uint32_t)(((uint64_t)cap + 2 + 255) / 256);
   hipLaunchKernelGGL(gzfile_link_kernel, dim3(node_blocks), dim3(256), 0, c->stream, P);
   for (uint32_t j = 0; (1u << j) < C.path_len; ++j)
@@ -1928,7 +1961,7 @@ int gzfile_discover(flate_hip_ctx *c, const uint8_t *d_in, uint64_t in_len, OneH
   hipLaunchKernelGGL(gzfile_finish_kernel, dim3((C.path_len + 255) / 256), dim3(256), 0, c->stream, P);
   hipLaunchKernelGGL(one_out_scan_kernel, dim3(1), dim3(1024), 0, c->stream, P.O);
   hipLaunchKernelGGL(gzfile_members_kernel, dim3(1), dim3(1024), 0, c->stream, P);
-  hipLaunchKernelGGL(one_probe_kernel, dim3(1), dim3(64), 0, c->stream, P.O, 1u);
+  one_probe_launch(c, 1, P.O, 1u);
   hipLaunchKernelGGL(gzfile_rel_kernel, dim3(node_blocks), dim3(256), 0, c->stream, P);
   HIP_TRY(c, hipGetLastError());
   HIP_TRY(c, hipMemcpyAsync(&H, P.O.head, sizeof H, hipMemcpyDeviceToHost, c->stream));
@@ -2089,7 +2122,8 @@ int flate_hip_gzfile_read(flate_hip_ctx *c, const uint8_t *in, uint64_t in_len, 
     D.unit_bit = P.O.C.member_off;
     D.out_off = P.O.C.out_off;
     D.total = total;
-    D.unit_max = c->one_unit_max;
+    D.unit_max = P.O.unit_max;
+    D.stored_units = P.O.stored_units;
     D.d_status = d_ds;
     D.d_out_len = d_dl;
     D.head = P.O.head;
@@ -2110,7 +2144,7 @@ int flate_hip_gzfile_read(flate_hip_ctx *c, const uint8_t *in, uint64_t in_len, 
       const uint32_t entry_blocks = (uint32_t)(((uint64_t)D.count * kWinEntries + 255) / 256);
       OneDecParams T = D;  // TAIL: a unit's history is what its own member has produced in front of it
       T.out_off = P.rel_off;
-      hipLaunchKernelGGL(one_tail_kernel, dim3(D.count), dim3(64), 0, c->stream, T);
+      one_tail_launch(c, D.count, T);
       hipLaunchKernelGGL(gzfile_pieces_kernel, dim3(unit_blocks), dim3(256), 0, c->stream, GD);
       int cur = 0;
       for (uint32_t s = 1; s < D.count; s <<= 1, cur ^= 1)
@@ -2217,6 +2251,7 @@ int flate_hip_gzfile_seek_index(flate_hip_ctx *c, const uint8_t *in, uint64_t in
     index[kGzSeekUnitsAt] = n;
     index[kGzSeekMembersAt] = m;
     index[kGzSeekPointsAt] = np;
+    index[kGzSeekRuleAt] = c->one_stored_units ? kSeekRuleStored : kSeekRuleDynamic;  // a read walks by this rule
   };
   if (in_len == 0) {  // no bytes: zero members, zero units, the head alone
     *index_words = gzfile_seek_index_words(0, 0, 0);
@@ -2317,7 +2352,8 @@ int flate_hip_gzfile_seek_index(flate_hip_ctx *c, const uint8_t *in, uint64_t in
     D.unit_bit = P.O.C.member_off;
     D.out_off = P.O.C.out_off;
     D.total = H.prefix_bytes + (H.fail_unit ? H.fail_out : 0ull);
-    D.unit_max = c->one_unit_max;
+    D.unit_max = P.O.unit_max;
+    D.stored_units = P.O.stored_units;
     GD.P = P;
     GD.n_good = n;
     HIP_TRY(c, hipMemsetAsync(D.dh, 0xff, sizeof(OneDecHead), c->stream));  // first_bad: none
@@ -2340,7 +2376,7 @@ int flate_hip_gzfile_seek_index(flate_hip_ctx *c, const uint8_t *in, uint64_t in
       }
       OneDecParams T = D;  // TAIL: a unit's history is what its own member has produced in front of it
       T.out_off = P.rel_off;
-      hipLaunchKernelGGL(one_tail_kernel, dim3(D.count), dim3(64), 0, c->stream, T);
+      one_tail_launch(c, D.count, T);
       hipLaunchKernelGGL(gzfile_pieces_kernel, dim3(unit_blocks), dim3(256), 0, c->stream, GD);  // (the seeds)
       int cur = 0;
       for (uint32_t s = 1; s < D.count; s <<= 1, cur ^= 1)
@@ -2595,6 +2631,7 @@ int flate_hip_gzfile_ranges(flate_hip_ctx *c, const uint8_t *in, uint64_t in_len
     D.unit_bit = Q.unit_bit;
     D.out_off = GS.rel;  // TAIL: a unit's history is what its own member has produced in front of it
     D.unit_max = c->one_unit_max;
+    D.stored_units = index[kGzSeekRuleAt] == kSeekRuleStored ? 1u : 0u;  // the index's rule, not the context's option
     D.unit_list = Q.sel_unit;
     S.Q = Q;
     S.windows = d_windows;
@@ -2614,7 +2651,7 @@ int flate_hip_gzfile_ranges(flate_hip_ctx *c, const uint8_t *in, uint64_t in_len
       const uint32_t unit_blocks = (count + 255u) / 256u;
       hipLaunchKernelGGL(gzfile_seek_seed_kernel, dim3(unit_blocks), dim3(256), 0, c->stream, Z);
       hipLaunchKernelGGL(gzfile_seek_load_kernel, dim3((entry_blocks + 15u) / 16u), dim3(256), 0, c->stream, Z);
-      hipLaunchKernelGGL(one_tail_kernel, dim3(count), dim3(64), 0, c->stream, D);
+      one_tail_launch(c, count, D);
       int cur = 0;
       for (uint32_t s = 1; s < count; s <<= 1, cur ^= 1)
         hipLaunchKernelGGL(one_seek_compose_kernel, dim3(entry_blocks), dim3(256), 0, c->stream, D.F[cur], D.F[cur ^ 1],

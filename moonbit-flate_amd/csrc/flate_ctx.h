@@ -87,6 +87,8 @@ struct flate_hip_ctx {
   DevBuf d_one, d_one_tiles;
   // ... and the bytes a unit's input spans at most (option "one_unit_max": it can only be lowered)
   uint64_t one_unit_max = 1ull << 28;
+  // ... and the unit rule (option "one_stored_units"): 0 = dynamic headers start units, 1 = stored headers too
+  uint32_t one_stored_units = 0;
   // flate_hip_inflate_one: the decode's arrays of one round (OneDecParams: the tail functions twice, the windows, the
   // per-unit results), carved from one buffer; the units of a round (option "one_round_units")
   DevBuf d_one_dec;

@@ -491,6 +491,8 @@ __global__ void gzip_out_scan_kernel(GzipParams P);
 // unit_bit / out_off; a chain that stops at a dynamic header the rule refused takes its verdict from one more probe
 // there (one_probe_kernel, tail form).  C.in is the whole input, C.cand_off the candidates' bits, C.member_off the
 // units' bits (both counted from the raw stream's first byte).  C.cap is the exact candidate count.
+// With OneParams::stored_units (option "one_stored_units") read "dynamic or stored header" for "dynamic header"
+// throughout: the stored-header rule adds candidates, and the walk stops in front of a stored header too.
 struct OneProbe {          // what a candidate's probe left
   uint64_t end_bit;        // where it stopped: in front of a dynamic header, or behind the final block
   uint64_t out;            // bytes it inflates to
@@ -516,6 +518,8 @@ struct OneParams {
   OneProbe *probe;         // cap
   uint64_t *usize;         // cap: per unit of the chain, what it inflates to
   uint64_t unit_max;       // option "one_unit_max": a unit's input spans fewer bytes than this
+  uint32_t stored_units;   // option "one_stored_units": 1 = a stored header starts a unit too: the host launches the
+                           // <true> builds of FIND and PROBE
 };
 // The decode of the units (flate_hip_inflate_one), in rounds of `count` units from unit u0.  one_tail_kernel (TAIL)
 // decodes every unit of the round with a SYMBOLIC window (window_compose.h) and stores its tail function into F[0];
@@ -562,8 +566,13 @@ struct OneDecParams {
   const OneHead *head;
   const uint32_t *sum;       // the checksum of out[0, total), or null
   uint32_t wrap;
+  // TAIL's unit rule, the word that goes with unit_max: what the units were cut by (OneParams::stored_units, or a seek
+  // index's rule word); the host launches that build of one_tail_kernel.  (It stands in the padding behind `wrap`: no
+  // other field moves, so the default build's parameter loads are the ones it had.)
+  uint32_t stored_units;
   uint64_t in_len;
 };
+template <bool STORED>  // (the unit rule of D.stored_units; both builds: one_probe_kernel.inc)
 __global__ void one_tail_kernel(OneDecParams D);
 __global__ void one_pieces_kernel(OneDecParams D);
 __global__ void one_check_kernel(OneDecParams D);
@@ -571,8 +580,13 @@ __global__ void one_compose_kernel(const uint16_t *src, uint16_t *dst, uint32_t 
 __global__ void one_resolve_kernel(const uint16_t *F, uint8_t *R, uint32_t count);
 __global__ void one_verdict_kernel(OneDecParams D);
 __global__ void one_init_kernel(FrameOne *one, uint64_t in_len);
+// (STORED: the unit rule, one_find_kernel.inc -- <false>, dynamic headers alone, is instantiated in one_kernels.hip;
+// <true>, dynamic and stored headers, in one_stored_kernels.hip)
+template <bool STORED>
 __global__ void one_count_kernel(OneParams P);
+template <bool STORED>
 __global__ void one_fill_kernel(OneParams P);
+template <bool STORED>  // (the unit rule of P.stored_units; both builds: one_probe_kernel.inc)
 __global__ void one_probe_kernel(OneParams P, uint32_t tail);
 __global__ void one_link_kernel(OneParams P);
 __global__ void one_finish_kernel(OneParams P);

@@ -126,7 +126,7 @@ __global__ __launch_bounds__(256) void gzfile_finish_kernel(GzFileParams P) {
     h->rc = FLATE_HIP_E_CORRUPT;
     h->err_off = (int64_t)gzfile_hop(C.in, C.in_len, pr.end_bit).e;
     P.gh->no_header = 1u;
-  } else {  // a dynamic header that is no candidate: the tail probe reads it as the serial decoder does
+  } else {  // a header of a unit-starting type that is no candidate: the tail probe reads it as the serial decoder
     P.O.head->tail_bit = pr.end_bit;
     P.O.head->tail = 1u;
   }

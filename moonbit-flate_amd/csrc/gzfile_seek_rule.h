@@ -29,7 +29,9 @@ constexpr uint64_t kGzSeekVersion = 1;
 constexpr uint64_t kGzSeekHeaderMin = 10, kGzSeekTrailer = 8;  // a member's header is at least 10 bytes, its trailer 8
 // the head's words
 constexpr uint32_t kGzSeekMagicAt = 0, kGzSeekVersionAt = 1, kGzSeekInLenAt = 2, kGzSeekTotalAt = 3, kGzSeekSpanAt = 4,
-                   kGzSeekUnitsAt = 5, kGzSeekMembersAt = 6, kGzSeekPointsAt = 7, kGzSeekHeadWords = 16;  // (8 .. 15: 0)
+                   kGzSeekUnitsAt = 5, kGzSeekMembersAt = 6, kGzSeekPointsAt = 7, kGzSeekRuleAt = 8,
+                   kGzSeekHeadWords = 16;  // (9 .. 15: 0)
+// word kGzSeekRuleAt: the unit rule the index was built with, kSeekRuleDynamic or kSeekRuleStored (seek_index_rule.h)
 
 // the member of unit k: the last one whose first unit is at or in front of k (member_unit[0] == 0)
 BGZF_HD uint32_t gzfile_seek_member_of(const uint64_t *member_unit, uint32_t m, uint32_t k) {
@@ -114,6 +116,11 @@ inline bool gzfile_seek_index_ok(const uint64_t *index, uint64_t index_words, ui
     }
   }
   return p == np;
+}
+
+// ... and, for an index that passed gzfile_seek_index_ok: its unit rule is one this library walks by
+inline bool gzfile_seek_index_rule_ok(const uint64_t *index) {
+  return index[kGzSeekRuleAt] == kSeekRuleDynamic || index[kGzSeekRuleAt] == kSeekRuleStored;
 }
 
 }  // namespace flate

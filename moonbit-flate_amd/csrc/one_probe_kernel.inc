@@ -1,8 +1,9 @@
 // one_probe_kernel.inc -- part of inflate_kernels.hip (it uses the shared reader: read_block_header, read_stored_len,
 // read_tables, read_copy, huff_sym).  ONE walk over a unit, one wavefront per unit, in two builds: the PROBE of
 // flate_hip_inflate_one_index decodes the raw stream from a candidate's BIT to the next dynamic block header (or
-// through the final block) and reports where it stopped and how many bytes it produced; the TAIL of
-// flate_hip_inflate_one is the same walk with a symbolic window (below).
+// through the final block; with the option "one_stored_units" to the next dynamic OR STORED header) and reports where
+// it stopped and how many bytes it produced; the TAIL of flate_hip_inflate_one is the same walk with a symbolic window
+// (below).
 //
 // The bits a DEFLATE stream consumes never depend on its history, so the probe keeps none: no window, no distance
 // check, no stores -- a decoy can write nothing -- and 6.5 KiB of LDS.  The reader starts in the state the serial
@@ -19,7 +20,7 @@ struct WalkShared {
 
 struct OneWalk {      // what a walk left (uniform over the wavefront)
   uint64_t base;      // the byte the unit starts in, counted from the raw stream's first byte
-  uint64_t end_bit;   // where it stopped: in front of a dynamic header, or behind the final block
+  uint64_t end_bit;   // where it stopped: in front of a unit-starting header, or behind the final block
   uint64_t out;       // bytes it inflates to
   int64_t err_off;    // counted from the raw stream's first byte, or -1
   int32_t status;     // 0, FLATE_HIP_E_CORRUPT / _UNEXPECTED_EOF / _TOO_LARGE
@@ -31,7 +32,12 @@ struct OneWalk {      // what a walk left (uniform over the wavefront)
 // bytes, and the serial decoder's distance rule is applied with the history the unit really has, min(32768, ooff +
 // bytes produced): the one verdict that depends on history comes out where the reference says so.  On return entry
 // (out + j) & (kWin - 1) of sh.win is the byte kWin - j places in front of the unit's end.
-template <bool SYM>
+// STORED (the option "one_stored_units", or the rule a seek index was built with): a stored header ends the unit as a
+// dynamic one does; the walk only becomes shorter.  A template flag, not a run-time test: the builds for dynamic headers
+// alone are instruction for instruction what they were before the option existed (a wave-uniform test of a parameter
+// word cost the default path 0.7 % of a whole call, DESIGN.md 4.5).  The host picks PROBE's and TAIL's build from the
+// same word (OneParams / OneDecParams::stored_units), so they stop at the same bits.
+template <bool SYM, bool STORED>
 FLATE_D OneWalk one_walk(WalkShared<SYM> &sh, const uint8_t *raw, uint64_t raw_len, uint64_t unit_max, uint64_t start,
                          uint64_t ooff, int lane) {
   uint64_t base = start >> 3;  // the reader counts bytes from here: 32 bits are enough for one unit
@@ -122,13 +128,15 @@ FLATE_D OneWalk one_walk(WalkShared<SYM> &sh, const uint8_t *raw, uint64_t raw_l
       if (err) break;
     }
     if (final_block) break;
-    // the next header: a dynamic one starts the next unit (the serial decoder asks for the same three bits next)
+    // the next header: a dynamic one -- STORED: a stored one as well -- starts the next unit (the serial decoder asks
+    // for the same three bits next)
     step();
     if (!bits_need(b, 3)) {
       err = E_EOF;
       break;
     }
-    if ((bits_peek(b, 3) >> 1) == 2u) break;
+    const uint32_t next_typ = bits_peek(b, 3) >> 1;
+    if (next_typ == 2u || (STORED && next_typ == 0u)) break;
   }
   if constexpr (SYM) __syncthreads();
   OneWalk w;
@@ -144,8 +152,10 @@ FLATE_D OneWalk one_walk(WalkShared<SYM> &sh, const uint8_t *raw, uint64_t raw_l
   return w;
 }
 
-// tail == 0: block c probes candidate c.  tail != 0 (one block): the chain stopped at head->tail_bit, a dynamic header
-// that is no candidate -- the serial decoder fails there, and this probe's status and offset are its verdict.
+// tail == 0: block c probes candidate c.  tail != 0 (one block): the chain stopped at head->tail_bit, a header of a
+// unit-starting type that is no candidate -- the serial decoder fails there, and this probe's status and offset are its
+// verdict.
+template <bool STORED>
 __global__ __launch_bounds__(64) void one_probe_kernel(OneParams P, uint32_t tail) {
   __shared__ WalkShared<false> sh;
   const int lane = threadIdx.x;
@@ -159,7 +169,7 @@ __global__ __launch_bounds__(64) void one_probe_kernel(OneParams P, uint32_t tai
     start = P.C.cand_off[c];
   }
   const uint64_t raw_off = P.one->pay_off[0], raw_len = P.one->pay_end - raw_off;
-  const OneWalk w = one_walk<false>(sh, P.C.in + raw_off, raw_len, P.unit_max, start, 0, lane);
+  const OneWalk w = one_walk<false, STORED>(sh, P.C.in + raw_off, raw_len, P.unit_max, start, 0, lane);
   if (lane != 0) return;
   if (tail) {
     // (status 0 here = the rule refused a header the reader takes: the two disagree.  The CPU model holds the rule
@@ -182,6 +192,7 @@ __global__ __launch_bounds__(64) void one_probe_kernel(OneParams P, uint32_t tai
 
 // TAIL: block i walks unit u0 + i with the symbolic window and stores its tail function: its final window as a function
 // of the one in front.
+template <bool STORED>
 __global__ __launch_bounds__(64) void one_tail_kernel(OneDecParams D) {
   __shared__ WalkShared<true> sh;
   const int lane = threadIdx.x;
@@ -198,7 +209,7 @@ __global__ __launch_bounds__(64) void one_tail_kernel(OneDecParams D) {
   // segments behind it start from their own stored windows.
   if (!D.unit_list && u > uni(D.dh->first_bad)) return;
   const uint64_t raw_off = D.one->pay_off[0], raw_len = D.one->pay_end - raw_off;
-  const OneWalk w = one_walk<true>(sh, D.in + raw_off, raw_len, D.unit_max, D.unit_bit[su], D.out_off[su], lane);
+  const OneWalk w = one_walk<true, STORED>(sh, D.in + raw_off, raw_len, D.unit_max, D.unit_bit[su], D.out_off[su], lane);
   uint16_t *t = D.F[0] + (uint64_t)i * kWin;  // entry j: the byte kWin - j places in front of the unit's end
   for (uint32_t j = lane; j < (uint32_t)kWin; j += 64) t[j] = sh.win[(w.out + j) & (kWin - 1)];
   if (lane == 0) {
@@ -208,3 +219,9 @@ __global__ __launch_bounds__(64) void one_tail_kernel(OneDecParams D) {
     if (w.status) atomicMin(&D.dh->first_bad, u);
   }
 }
+
+// the two unit rules: dynamic headers alone (the default), dynamic and stored headers
+template __global__ void one_probe_kernel<false>(OneParams P, uint32_t tail);
+template __global__ void one_probe_kernel<true>(OneParams P, uint32_t tail);
+template __global__ void one_tail_kernel<false>(OneDecParams D);
+template __global__ void one_tail_kernel<true>(OneDecParams D);

@@ -28,7 +28,12 @@ constexpr uint64_t kSeekUnitBitsMax = 8ull << 28;  // a unit's input spans at mo
 // the head's words
 constexpr uint32_t kSeekMagicAt = 0, kSeekVersionAt = 1, kSeekWrapAt = 2, kSeekInLenAt = 3, kSeekRawOffAt = 4,
                    kSeekRawEndAt = 5, kSeekTotalAt = 6, kSeekSpanAt = 7, kSeekUnitsAt = 8, kSeekPointsAt = 9,
-                   kSeekWantAt = 10, kSeekIsizeAt = 11, kSeekHeadWords = 16;  // (words 12 .. 15: 0)
+                   kSeekWantAt = 10, kSeekIsizeAt = 11, kSeekRuleAt = 12, kSeekHeadWords = 16;  // (words 13 .. 15: 0)
+// THE UNIT RULE the index was built with (word kSeekRuleAt; the option "one_stored_units" of the building context):
+// units start at dynamic headers alone (0: every index from before the word existed), or at dynamic and stored headers.
+// A read walks the units with THIS rule, whatever its own context's option says -- with another one TAIL would run on
+// through a listed unit's end.
+constexpr uint64_t kSeekRuleDynamic = 0, kSeekRuleStored = 1;
 
 BGZF_HD uint64_t seek_span(uint64_t span) { return span ? span : kSeekSpanDefault; }
 
@@ -87,6 +92,12 @@ inline bool seek_index_ok(const uint64_t *index, uint64_t index_words, uint64_t 
       ++p;
     }
   return p == np;
+}
+
+// ... and, for an index that passed seek_index_ok (the head is there): its unit rule is one this library walks by.
+// Any other value fails like the cases above.
+inline bool seek_index_rule_ok(const uint64_t *index) {
+  return index[kSeekRuleAt] == kSeekRuleDynamic || index[kSeekRuleAt] == kSeekRuleStored;
 }
 
 }  // namespace flate

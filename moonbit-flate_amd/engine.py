@@ -813,7 +813,8 @@ class FlateEngine(OneSeekCalls, GzFileCalls, GzFileSeekCalls):
         blocks) start and where their output goes, found on the GPU from the stream's bits
         (flate_hip_inflate_one_index) -> OneIndex(rc, n_units, out_bytes, n_candidates, status, err_off, unit_bit,
         out_off).  A unit starts at bit 0 of the raw stream and at every dynamic-Huffman block header the serial decode
-        reaches; unit_bit (numpy uint64[n_units + 1], bits counted from the raw stream's first byte, the last entry the
+        reaches (after set_option("one_stored_units", 1): at every stored block header too, so that incompressible
+        data is many units); unit_bit (numpy uint64[n_units + 1], bits counted from the raw stream's first byte, the last entry the
         bit behind the final block) and out_off (the exclusive prefix sum of what the units inflate to).  status: 0, or
         what the serial decoder says of the stream without looking at its history or its trailer: -4 (at err_off,
         counted from the raw stream's first byte; a bad container header: 0), -7, or -6 for a unit whose input spans

@@ -65,6 +65,8 @@ class Engine {
   bool ok() const { return rc_ == 0; }
   int status() const { return rc_; }
   flate_hip_ctx *ctx() const { return ctx_; }
+  // flate_hip_set_option: e.g. ("one_stored_units", 1) so that stored block headers start units too
+  int set_option(const char *name, int64_t value) { return flate_hip_set_option(ctx_, name, value); }
 
  private:
   flate_hip_ctx *ctx_ = nullptr;

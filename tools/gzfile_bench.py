@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """flate_hip_gzfile_read on three gzip files made from the same S-text, against the call each kind of file had before.
 
-    python tools/gzfile_bench.py [--mib 1024] [--level 6] [--reps 5] [--only ABC]
+    python tools/gzfile_bench.py [--mib 1024] [--level 6] [--reps 5] [--only ABC] [--workload text|random|mixed]
+                                 [--stored-units]
     python tools/gzfile_bench.py --trace A --calls 3       (run under a kernel trace: gzfile_read alone, --calls times)
     python tools/gzfile_bench.py --steps KERNEL_STATS.csv --calls 3      (that trace's kernel times as per-step times)
 
@@ -13,7 +14,8 @@ Builds --mib MiB of S-text and compresses it with zlib at --level (on the CPU, o
 Every file is put on the device and timed with device pointers, whole calls, best of --reps, the two calls of a pair
 ALTERNATED on the same card (a, b, a, b, ...; the first call of each sizes the ctx's scratch and is not counted); the
 output of every gzfile_read is compared with the input once.  Prints one JSON line; also written to $FLATE_OUT_ROOT
-(default results/)/gzfile_bench.json."""
+(default results/)/gzfile_bench.json.  --workload and --stored-units are tools/one_bench.py's: other plain bytes, and
+the option "one_stored_units" (stored block headers start units too)."""
 import argparse
 import csv
 import importlib
@@ -29,7 +31,9 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 flate = importlib.import_module("moonbit-flate_amd")
+from one_bench import workload  # noqa: E402
 
 HEADER = b"\x1f\x8b\x08\x00\x00\x00\x00\x00\x00\xff"
 # the kernels of a flate_hip_gzfile_read call by step (a prefix of the kernel's name; the rest are "other")
@@ -79,19 +83,23 @@ def main():
     ap.add_argument("--trace", default="")
     ap.add_argument("--calls", type=int, default=3)
     ap.add_argument("--steps", default="")
+    ap.add_argument("--workload", choices=("text", "random", "mixed"), default="text")
+    ap.add_argument("--stored-units", action="store_true")
     a = ap.parse_args()
     if a.steps:
         print(json.dumps({"per_call_ms": steps_of(a.steps, a.calls), "calls": a.calls}))
         return
     import torch
 
-    plain = flate.synth("text", a.mib * 16, 65536)
+    plain = workload(a.workload, a.mib)
     counts = {"A": 1, "B": 16, "C": a.mib * 16}
     eng = flate.FlateEngine(0)
+    eng.set_option("one_stored_units", 1 if a.stored_units else 0)
     out = torch.empty(plain.size + 16, dtype=torch.uint8, device="cuda")
     want = torch.from_numpy(plain)
     res = {"what": "gzip files of one S-text, device pointers, whole calls, ms, pairs alternated", "plain_bytes": int(plain.size),
-           "zlib_level": a.level, "reps": a.reps, "build_id": flate.build_id()}
+           "zlib_level": a.level, "reps": a.reps, "workload": a.workload, "one_stored_units": int(a.stored_units),
+           "build_id": flate.build_id()}
 
     def timed(fn):
         torch.cuda.synchronize()

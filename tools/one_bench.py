@@ -2,6 +2,7 @@
 """flate_hip_inflate_one on one long gzip member, against flate_hip_inflate_stream_read on the same file.
 
     python tools/one_bench.py [--mib 1024] [--level 6] [--reps 5] [--serial-seconds 150]
+                              [--workload text|random|mixed] [--stored-units]
 
 Builds --mib MiB of S-text, compresses it with zlib at --level into ONE gzip member (on the CPU, once), puts the member
 on the device and times, best of --reps, whole calls with device pointers: flate_hip_inflate_one (discovery, decode,
@@ -10,7 +11,10 @@ and n_candidates.  The comparison is flate_hip_inflate_stream_read, the call tha
 stream fed from host memory (the call takes nothing else) in 64 MiB pieces with room for 256 MiB of output per call.  It
 runs for at most --serial-seconds; if that does not reach the end of the stream, the time for the whole stream is its
 measured rate extrapolated and labelled so.  For a per-kernel split run this script under a kernel trace with --reps 1
---serial-seconds 0.  Prints one JSON line; also written to $FLATE_OUT_ROOT (default results/)/one_bench.json."""
+--serial-seconds 0.  --workload: S-text (the default), random bytes (zlib writes them as stored blocks of about 16 KiB),
+or 1 MiB of S-text and 1 MiB of random bytes in turn.  --stored-units sets the option "one_stored_units", so that stored
+block headers start units too; without it a run of stored blocks is one unit, and a call that refuses the member
+(FLATE_HIP_E_TOO_LARGE for a unit of 2^28 bytes) is recorded, not timed.  Prints one JSON line; also written to $FLATE_OUT_ROOT (default results/)/one_bench.json."""
 import argparse
 import ctypes as C
 import importlib
@@ -49,20 +53,35 @@ def serial(eng, raw, limit_s):
     return got, dt, rc == 1
 
 
+def workload(kind, mib):
+    """mib MiB of plain bytes: S-text, random bytes, or 1 MiB of each in turn."""
+    if kind == "text":
+        return flate.synth("text", mib * 16, 65536)
+    rnd = np.random.default_rng(7).integers(0, 256, mib << 20, dtype=np.uint8)
+    if kind == "mixed":
+        text = flate.synth("text", mib * 16, 65536).reshape(mib, 1 << 20)
+        rnd = rnd.reshape(mib, 1 << 20)
+        rnd[0::2] = text[0::2]
+    return rnd.reshape(-1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--mib", type=int, default=1024)
     ap.add_argument("--level", type=int, default=6)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--serial-seconds", type=float, default=150)
+    ap.add_argument("--workload", choices=("text", "random", "mixed"), default="text")
+    ap.add_argument("--stored-units", action="store_true")
     a = ap.parse_args()
     import torch
 
-    plain = flate.synth("text", a.mib * 16, 65536)
+    plain = workload(a.workload, a.mib)
     co = zlib.compressobj(a.level, zlib.DEFLATED, -15)
     raw = co.compress(plain.tobytes()) + co.flush()
     member = b"\x1f\x8b\x08\x00\x00\x00\x00\x00\x00\xff" + raw + struct.pack("<II", zlib.crc32(plain), plain.size & 0xffffffff)
     eng = flate.FlateEngine(0)
+    eng.set_option("one_stored_units", 1 if a.stored_units else 0)
     d = torch.from_numpy(np.frombuffer(member, np.uint8).copy()).cuda()
     out = torch.empty(plain.size + 16, dtype=torch.uint8, device="cuda")
 
@@ -75,11 +94,19 @@ def main():
             times.append((time.perf_counter() - t0) * 1e3)
         return r, [round(t, 3) for t in times]
 
+    res = {"workload": a.workload, "one_stored_units": int(a.stored_units)}
     (_, rd), t_one = best(lambda: eng.inflate_one(d, "gzip", out=out))
+    if rd.rc == -6:  # a unit of 2^28 bytes of input or more: the member is refused whole
+        res.update({"what": "one gzip member: refused", "status": "FLATE_HIP_E_TOO_LARGE", "plain_bytes": int(plain.size),
+                    "member_bytes": len(member), "n_units": rd.n_units, "n_candidates": rd.n_candidates,
+                    "build_id": flate.build_id()})
+        print(json.dumps(res))
+        eng.close()
+        return
     assert rd.rc == 0 and rd.out_len == plain.size, rd
     assert bool((out[:plain.size].cpu() == torch.from_numpy(plain)).all()), "the output is not the input"
     ix, t_ix = best(lambda: eng.inflate_one_index(d, "gzip", query=True))
-    res = {
+    res.update({
         "what": "one gzip member, device pointers, whole calls, ms",
         "plain_bytes": int(plain.size), "member_bytes": len(member), "zlib_level": a.level,
         "inflate_one_ms_best": min(t_one[1:]), "inflate_one_ms_all": t_one,
@@ -88,7 +115,7 @@ def main():
         "n_units": ix.n_units, "n_candidates": ix.n_candidates,
         "decoys_per_gib_of_input": round((ix.n_candidates - ix.n_units) * (1 << 30) / len(raw)),
         "build_id": flate.build_id(),
-    }
+    })
     print(json.dumps(res), file=sys.stderr, flush=True)
     if a.serial_seconds > 0:
         got, dt, done = serial(eng, raw, a.serial_seconds)

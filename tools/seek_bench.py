@@ -2,7 +2,7 @@
 """The seek index of one long gzip member: flate_hip_inflate_one_seek_index and flate_hip_inflate_one_ranges against
 flate_hip_inflate_one on the same file.
 
-    python tools/seek_bench.py [--mib 1024] [--level 6] [--reps 5]
+    python tools/seek_bench.py [--mib 1024] [--level 6] [--reps 5] [--workload text|random|mixed] [--stored-units]
 
 The input is tools/one_bench.py's: --mib MiB of S-text compressed with zlib at --level into ONE gzip member (on the
 CPU, once), on the device; whole calls with device pointers, best of --reps after one call that sizes the ctx's scratch.
@@ -12,7 +12,9 @@ CPU, once), on the device; whole calls with device pointers, best of --reps afte
   (d) one range of 1 byte through the 1 MiB index       (e) the same byte through an index of span 64 KiB
 and the index and window sizes of every span.  `spread` is the largest difference between two calls of the same kind
 inside the alternated pairs: a difference between the kinds below it says nothing.  Prints one JSON line; also written
-to $FLATE_OUT_ROOT (default results/)/seek_bench.json."""
+to $FLATE_OUT_ROOT (default results/)/seek_bench.json.  --workload and --stored-units are tools/one_bench.py's: other
+plain bytes, and the option "one_stored_units" on the building ctx (a read takes the rule from the index); with the
+mixed workload the one byte of (d) and (e) lies in the middle of a random stretch."""
 import argparse
 import importlib
 import json
@@ -26,7 +28,9 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 flate = importlib.import_module("moonbit-flate_amd")
+from one_bench import workload  # noqa: E402
 
 
 def main():
@@ -34,15 +38,18 @@ def main():
     ap.add_argument("--mib", type=int, default=1024)
     ap.add_argument("--level", type=int, default=6)
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--workload", choices=("text", "random", "mixed"), default="text")
+    ap.add_argument("--stored-units", action="store_true")
     a = ap.parse_args()
     import torch
 
-    plain = flate.synth("text", a.mib * 16, 65536)
+    plain = workload(a.workload, a.mib)
     co = zlib.compressobj(a.level, zlib.DEFLATED, -15)
     raw = co.compress(plain.tobytes()) + co.flush()
     member = b"\x1f\x8b\x08\x00\x00\x00\x00\x00\x00\xff" + raw + struct.pack("<II", zlib.crc32(plain), plain.size & 0xffffffff)
     T = int(plain.size)
     eng = flate.FlateEngine(0)
+    eng.set_option("one_stored_units", 1 if a.stored_units else 0)
     d = torch.from_numpy(np.frombuffer(member, np.uint8).copy()).cuda()
     out = torch.empty(T + 16, dtype=torch.uint8, device="cuda")
     d_plain = torch.from_numpy(plain).cuda()
@@ -95,6 +102,8 @@ def main():
         assert bool((o[int(rr.out_off[r]):int(rr.out_off[r + 1])] == d_plain[int(begin[r]):int(end[r])]).all()), r
     # (d), (e)
     at = T // 2 + 12345
+    if a.workload == "mixed" and (at >> 20) % 2 == 0 and at + (1 << 20) < T:
+        at += 1 << 20  # (the even MiB rows are text, the odd ones random bytes: tools/one_bench.py workload)
     (o, r1), t_byte_mib = best(lambda: eng.inflate_one_ranges(d, s_mib, [at], [at + 1], out=out))
     assert r1.rc == 0 and int(o[0]) == int(plain[at])
     s_64k = eng.inflate_one_seek_index(d, "gzip", 65536)
@@ -106,6 +115,7 @@ def main():
 
     res = {
         "what": "one gzip member, device pointers, whole calls, ms",
+        "workload": a.workload, "one_stored_units": int(a.stored_units), "n_candidates": rd.n_candidates,
         "plain_bytes": T, "member_bytes": len(member), "zlib_level": a.level, "n_units": s_mib.n_units,
         "a_build_1mib_ms_best": min(t_build[1:]), "a_build_1mib_ms_all": t_build,
         "a_inflate_one_ms_best": min(t_one_a[1:]), "a_inflate_one_ms_all": t_one_a, "a_spread_ms": spread(t_build, t_one_a),
