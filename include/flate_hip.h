@@ -125,6 +125,8 @@ int flate_hip_set_stream(flate_hip_ctx *ctx, void *hip_stream);
  *   "stream_rebase_bytes"  flate_hip_stream_*: a stream longer than this moves the origin of the
  *                        32-bit positions its kernels count in (all distances stay what they were);
  *                        default 1 GiB, read when the stream is opened; results never change
+ *   "zip_unit_min"       flate_hip_zip_read: 0 (default) = every entry goes to the batch decoders; v >= 1 = a deflated
+ *                        entry of at least v compressed bytes is decoded through units (ZIP archives, below)
  *   "one_stored_units"   flate_hip_inflate_one* and flate_hip_gzfile_*: 0 (default) = a unit starts at bit 0
  *                        and at every dynamic block header; 1 = at every STORED block header too, so that a
  *                        run of stored blocks (incompressible data) is many units instead of one: it is
@@ -1146,8 +1148,41 @@ int flate_hip_gzfile_ranges(flate_hip_ctx *ctx, const uint8_t *in, uint64_t in_l
  *   its own end by binary search, the chain ranked by pointer doubling); one thread per record reads the record and
  *   its local header; a scan of the sizes.  No host pass over file bytes; nothing outside in[0, in_len) is read, at
  *   any alignment of in.
+ *
+ * READING LONG ENTRIES: the option "zip_unit_min".  The batch decoders give an entry one lane or one wavefront, the
+ * right shape for .jar, .whl and .docx and the wrong one for an .npz of a few large arrays or a .zip of one large CSV.
+ * With "zip_unit_min" = v >= 1 (0, the default: off -- the same kernels, no new launch, no new allocation) a selected
+ * deflated entry with comp_size >= v is LONG and is decoded as flate_hip_gzfile_read decodes a long member: in UNITS
+ * found on the device, all long entries as ONE chain.  The rule is written once, csrc/zip_units_rule.h; the kernels are
+ * csrc/zip_units_kernels.hip.  The set L: the selection slots, in ascending order, whose entry has index status 0,
+ * method 8, comp_size >= v, is not FLATE_HIP_E_TOO_LARGE, is the first occurrence of its entry number in sel, and
+ * whose data range overlaps no other such entry's range (archives whose records share data exist; those go to the
+ * batch decoders).  FIND runs over the HULL of L's data ranges only, and every bit of the unit path is counted from
+ * the hull's first byte.  A unit of entry X links to the unit that starts where it stops, inside X's range; a unit
+ * that ends with BFINAL at or before X's end links to the first unit of the next L entry, which starts at 8 * data_off
+ * whatever block type is there; anything else ends the chain.  An L entry is GOOD iff its chain reaches BFINAL
+ * inside its range, its units' output sums to exactly `size`, and every unit passes TAIL and the decode round's
+ * check.  With g = the L entries in front of the first that is not GOOD, L[0, g) are served by units -- unit k of
+ * entry j writes at out_off[j] + (what j's units in front of k produce), with min(32768, that) bytes of history,
+ * never another entry's -- and L[g] and every L entry behind it go to the batch decoders in the same call: a broken
+ * archive costs what it costs with the option off.  CRC-32 and size of every entry are judged by the same kernels.
+ * RESULTS ARE THOSE OF THE OPTION AT 0 for every archive, selection, pointer kind and alignment: out[0,
+ * out_off[n_sel]), out_off, out_len, status, err_off, n_entries, archive_err_off and the return value (the slot of an
+ * entry whose status is not 0 excepted: empty or as far as it came).  The size query and FLATE_HIP_E_OUT_TOO_SMALL are
+ * decided before any discovery.  The options "one_stored_units", "one_unit_max" and "one_round_units" apply as in
+ * flate_hip_gzfile_read.  Which path ran: flate_hip_zip_last_route.
+ *   How: L is host code over the index that comes back anyway, O(|L| log |L|).  FIND's count pass over the hull, ONE
+ *   read-back of the count; fill, the B nodes' bits from the directory, PROBE of every node, link, pointer doubling,
+ *   finish, out-scan, the entry scan, the entry-relative offsets, ONE read-back of the head words and every entry's
+ *   first unit; rounds of TAIL, pieces in ZIP's slots (between two entries' slots a piece of no bits, so that every
+ *   unit's slot is exactly its size), the segmented COMPOSE / RESOLVE with every entry's first unit as a seed, DECODE,
+ *   CHECK; ONE small read-back (g); then ONE batch-decoder launch over the short and the fallback entries, the stored
+ *   copies, the checksums and the verdict as before.  Stages: discovery is counted in no stage, as in
+ *   flate_hip_gzfile_read; FLATE_HIP_STAGE_INFLATE is the batch launch, or the last round's decoder launch when no
+ *   entry is left for the batch decoders.  No kernel waits for another workgroup.
  * Out of scope: archives with prepended data, several disks, encryption, methods other than 0 and 8, comments on
- * write; uploading only the selected entries from host memory; caching the index across calls. */
+ * write; uploading only the selected entries from host memory; caching the index across calls; entries of 4 GiB or
+ * more through units; a seek index for entries; independent chains per entry. */
 typedef struct flate_hip_zip_entry {
   uint64_t name_off;    /* the name's place in the archive (the directory's copy), name_len bytes */
   uint64_t header_off;  /* the local header */
@@ -1188,6 +1223,13 @@ int flate_hip_zip_read(flate_hip_ctx *ctx, const uint8_t *in, uint64_t in_len, c
                        uint32_t n_cap, uint8_t *out, uint64_t out_cap, uint64_t *out_off, uint64_t *out_len,
                        int32_t *status, int64_t *err_off, uint32_t *n_entries, int64_t *archive_err_off,
                        uint32_t flags);
+/* What the last flate_hip_zip_read on this ctx did with the option "zip_unit_min": *unit_entries = the selection slots
+ * served by units; *fallback_entries = the slots that qualified by size but went to the batch decoders (a duplicate,
+ * an overlapping range, at or behind the first entry that is not GOOD); *n_units = the units on the served entries'
+ * path; *n_candidates = FIND's candidates in the hull.  All zero when the option is 0, and after a call that decoded
+ * nothing.  Results are identical by design: this is how a caller sees which path ran.  No HIP call. */
+int flate_hip_zip_last_route(const flate_hip_ctx *ctx, uint32_t *unit_entries, uint32_t *fallback_entries,
+                             uint32_t *n_units, uint32_t *n_candidates);
 
 /* -- exchange step (multi-GPU) ---------------------------------------------------
  * SURVEY 8(e) / section 5; no counterpart in the reference (single-threaded, no communication

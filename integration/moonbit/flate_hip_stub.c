@@ -139,3 +139,13 @@ int flate_hip_mbt_bgzf_read(flate_hip_ctx *c, const uint8_t *in, uint64_t in_len
   res[4] = eof;
   return rc;
 }
+
+/* -- ZIP reads (flate_hip_zip_read with the option "zip_unit_min"): which path the last read on this ctx took, the
+ * four counts of flate_hip_zip_last_route packed into one array: res[0] = unit_entries, res[1] = fallback_entries,
+ * res[2] = n_units, res[3] = n_candidates -- */
+int flate_hip_mbt_zip_last_route(const flate_hip_ctx *c, int64_t *res) {
+  uint32_t w[4] = {0, 0, 0, 0};
+  const int rc = flate_hip_zip_last_route(c, &w[0], &w[1], &w[2], &w[3]);
+  for (int k = 0; k < 4; ++k) res[k] = w[k];
+  return rc;
+}

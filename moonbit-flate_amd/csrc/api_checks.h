@@ -281,6 +281,9 @@ inline int zip_read_args(const uint8_t *in, uint64_t in_len, const uint32_t *sel
   if (sel ? n_sel > n_cap : n_sel != 0) return FLATE_HIP_E_INVALID;  // (sel == NULL: every entry, n_sel is 0)
   return (flags & ~FLATE_HIP_DEVICE_PTRS) ? FLATE_HIP_E_INVALID : FLATE_HIP_OK;
 }
+// the option "zip_unit_min": 0 (the default) = every entry goes to the batch decoders; v >= 1 = a deflated entry of
+// at least v compressed bytes is decoded through units (zip_units_rule.h)
+inline bool zip_unit_min_ok(int64_t value) { return value >= 0; }
 // how many candidates the directory's discovery arrays hold on the first attempt: the records the end record promises
 // and some decoys (names or extras that look like records); never more than fit the directory, 4 bytes apart
 inline uint32_t zip_first_cap(uint64_t n, uint64_t cd_size) {

@@ -375,6 +375,8 @@ int flate_hip_set_option(flate_hip_ctx *c, const char *name, int64_t value) {
     c->one_stored_units = (uint32_t)value;
   } else if (k == "one_round_units" && one_round_units_ok(value)) {
     c->one_round_units = (uint32_t)value;
+  } else if (k == "zip_unit_min" && zip_unit_min_ok(value)) {
+    c->zip_unit_min = (uint64_t)value;
   } else {
     return FLATE_HIP_E_INVALID;
   }
@@ -427,6 +429,14 @@ int flate_hip_last_resident_share(flate_hip_ctx *c, uint32_t *resident_streams, 
   HIP_TRY(c, hipMemcpy(q, c->d_queue.p, 32, hipMemcpyDeviceToHost));
   *resident_streams = q[4] + q[5];
   *queued_streams = c->last_count[0] + c->last_count[1];
+  return FLATE_HIP_OK;
+}
+
+int flate_hip_zip_last_route(const flate_hip_ctx *c, uint32_t *unit_entries, uint32_t *fallback_entries, uint32_t *n_units,
+                             uint32_t *n_candidates) {
+  if (!c || !unit_entries || !fallback_entries || !n_units || !n_candidates) return FLATE_HIP_E_INVALID;
+  *unit_entries = c->zip_route[0], *fallback_entries = c->zip_route[1];
+  *n_units = c->zip_route[2], *n_candidates = c->zip_route[3];
   return FLATE_HIP_OK;
 }
 

@@ -2719,6 +2719,210 @@ int flate_hip_gzfile_ranges(flate_hip_ctx *c, const uint8_t *in, uint64_t in_len
 
 }  // extern "C"
 
+// ---- the LONG entries of a ZIP archive through units (zip_units_kernels.hip, zip_units_rule.h) ----
+// gzfile_discover and flate_hip_gzfile_read's rounds with the format's own glue: the hull as the raw stream, B nodes
+// from the directory, the link that hops from entry to entry, pieces in ZIP's slots.  Read-backs: the candidate count;
+// the head words with entry_unit; the rounds' first_bad / decode_bad (g).
+int flate_host::zip_units_decode(flate_hip_ctx *c, const uint8_t *d_in, uint64_t hull_lo, uint64_t hull_hi,
+                                 const std::vector<ZuEntry> &L, const std::vector<ZuRange> &R, uint8_t *d_out,
+                                 uint64_t total, uint32_t *g, ZipUnitsDecParams &G, uint32_t *n_units, uint32_t *n_cand) {
+  int rc;
+  *g = 0, *n_units = 0, *n_cand = 0;
+  G = ZipUnitsDecParams{};
+  ZipUnitsParams P{};
+  OneParams PA{};
+  ChainParams &C = P.O.C;
+  const uint8_t *h_in = d_in + hull_lo;  // every offset below is counted from here
+  const uint64_t hull_len = hull_hi - hull_lo;
+  const uint32_t nb = (uint32_t)L.size();
+  if (nb == 0 || R.size() != L.size() || hull_len == 0) return FLATE_HIP_E_INTERNAL;
+  uint32_t n_tiles = 0;
+  if ((rc = tiles_for(h_in, 0, hull_len, &n_tiles))) return rc;
+  OneHead *head_a;
+  ZuEntry *dL;
+  ZuRange *dR;
+  rc = carve(c, c->d_zip_units_tiles, [&](Carve &k) {
+    k.take(P.O.head, 1);
+    k.take(P.zh, 1);
+    k.take(P.O.one, 1);
+    k.take(head_a, 1);
+    k.take(PA.C.tile_cnt, (size_t)n_tiles + 1);
+    k.take(dL, nb);
+    k.take(dR, nb);
+    k.take(P.entry_unit, (size_t)nb + 2);
+  });
+  if (rc) return rc;
+  P.L = dL, P.R = dR;
+  HIP_TRY(c, hipMemcpyAsync(dL, L.data(), (size_t)nb * sizeof(ZuEntry), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(dR, R.data(), (size_t)nb * sizeof(ZuRange), hipMemcpyHostToDevice, c->stream));
+  C.in = PA.C.in = h_in;
+  C.in_len = PA.C.in_len = hull_len;
+  C.n_tiles = PA.C.n_tiles = n_tiles;
+  C.head = &P.O.head->h;
+  P.O.unit_max = PA.unit_max = c->one_unit_max;
+  P.O.stored_units = PA.stored_units = c->one_stored_units;
+  PA.C.head = &head_a->h;
+  PA.head = head_a;
+  PA.one = P.O.one;
+  hipLaunchKernelGGL(one_init_kernel, dim3(1), dim3(64), 0, c->stream, P.O.one, hull_len);  // the hull is the raw stream
+  one_find_launch(c, true, n_tiles, PA);
+  hipLaunchKernelGGL(chain_scan_kernel, dim3(1), dim3(1024), 0, c->stream, PA.C);
+  HIP_TRY(c, hipGetLastError());
+  OneHead HA{};
+  HIP_TRY(c, hipMemcpyAsync(&HA, head_a, sizeof HA, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  const uint32_t na = HA.h.n_cand;
+  if ((uint64_t)na + nb > 0x7ffffff0ull) return FLATE_HIP_E_TOO_LARGE;  // (the count saturates at 2^32 - 1)
+  const uint32_t cap = na + nb;
+  if ((rc = chain_size(C, cap)) || (rc = chain_size(PA.C, na))) return rc;
+  P.n_a = na;
+  P.n_b = nb;
+  *n_cand = na;
+
+  const size_t n = cap;
+  rc = carve(c, c->d_zip_units, [&](Carve &k) {
+    k.take(C.cand_off, n);
+    k.take(P.O.probe, n);
+    k.take(C.jump[0], n + 2);
+    k.take(C.jump[1], n + 2);
+    k.take(C.path, C.path_len);
+    k.take(P.O.usize, n);
+    k.take(C.member_off, n + 1);
+    k.take(C.out_off, n + 1);
+    k.take(P.u_start, n + 1);
+    k.take(P.u_final, n);
+    k.take(P.u_entry, n + 1);
+    k.take(P.rel_off, n + 1);
+  });
+  if (rc) return rc;
+  PA.C.cand_off = C.cand_off;
+  if (na) one_find_launch(c, false, n_tiles, PA);
+  hipLaunchKernelGGL(zip_units_bits_kernel, dim3((nb + 255) / 256), dim3(256), 0, c->stream, P);
+  one_probe_launch(c, cap, P.O, 0u);
+  const uint32_t node_blocks = (uint32_t)(((uint64_t)cap + 2 + 255) / 256);
+  hipLaunchKernelGGL(zip_units_link_kernel, dim3(node_blocks), dim3(256), 0, c->stream, P);
+  for (uint32_t j = 0; (1u << j) < C.path_len; ++j)
+    hipLaunchKernelGGL(chain_round_kernel, dim3(node_blocks), dim3(256), 0, c->stream, C, j);
+  hipLaunchKernelGGL(zip_units_finish_kernel, dim3((C.path_len + 255) / 256), dim3(256), 0, c->stream, P);
+  hipLaunchKernelGGL(one_out_scan_kernel, dim3(1), dim3(1024), 0, c->stream, P.O);
+  hipLaunchKernelGGL(zip_units_entries_kernel, dim3(1), dim3(1024), 0, c->stream, P);
+  hipLaunchKernelGGL(zip_units_rel_kernel, dim3(node_blocks), dim3(256), 0, c->stream, P);
+  HIP_TRY(c, hipGetLastError());
+  OneHead H{};
+  ZipUnitsHead Z{};
+  std::vector<uint64_t> entry_unit((size_t)nb + 2, 0);
+  HIP_TRY(c, hipMemcpyAsync(&H, P.O.head, sizeof H, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(&Z, P.zh, sizeof Z, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(entry_unit.data(), P.entry_unit, ((size_t)nb + 2) * 8, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  if (H.h.n_members > cap || Z.n_complete > nb) return FLATE_HIP_E_INTERNAL;
+  // the entries the discovery finds GOOD, and their units: the only ones that are decoded
+  const uint32_t g_disc = Z.n_complete < Z.first_unfit ? Z.n_complete : Z.first_unfit;
+  G.P = P;
+  if (g_disc == 0) return FLATE_HIP_OK;
+  if (entry_unit[g_disc] > H.h.n_members) return FLATE_HIP_E_INTERNAL;
+  const uint32_t n_dec = (uint32_t)entry_unit[g_disc];
+
+  const uint32_t per_round = n_dec < c->one_round_units ? n_dec : c->one_round_units;
+  const size_t fentries = (size_t)per_round * kWinEntries, pieces = 2 * (size_t)per_round;
+  OneDecParams &D = G.D;
+  int32_t *d_ds;
+  uint64_t *d_dl;
+  int64_t *d_de;
+  rc = carve(c, c->d_one_dec, [&](Carve &k) {
+    k.take(D.dh, 1);
+    k.take(D.F[0], fentries);
+    k.take(D.F[1], fentries);
+    k.take(D.R, ((size_t)per_round + 1) * kWinEntries);
+    k.take(D.status, (size_t)n_dec + 1);
+    k.take(D.err_off, (size_t)n_dec + 1);
+    k.take(D.produced, (size_t)n_dec + 1);
+    k.take(D.p_out_off, pieces + 1);
+    k.take(D.p_dict_at, pieces);
+    k.take(D.p_dict_len, pieces);
+    k.take(d_ds, pieces);
+    k.take(d_dl, pieces);
+    k.take(d_de, pieces);
+  });
+  if (rc) return rc;
+  rc = carve(c, c->d_zip_units_dec, [&](Carve &k) {
+    k.take(G.seed, per_round);
+    k.take(G.p_bit_off, pieces);
+    k.take(G.p_bit_end, pieces);
+    k.take(G.du_status, per_round);
+    k.take(G.du_out_len, per_round);
+  });
+  if (rc) return rc;
+  D.in = h_in;
+  D.one = P.O.one;
+  D.unit_bit = C.member_off;
+  D.out_off = C.out_off;
+  D.total = total;
+  D.unit_max = P.O.unit_max;
+  D.stored_units = P.O.stored_units;
+  D.d_status = G.du_status;
+  D.d_out_len = G.du_out_len;
+  D.head = P.O.head;
+  D.wrap = FLATE_HIP_WRAP_RAW;
+  D.in_len = hull_len;
+  G.dp_status = d_ds;
+  G.dp_out_len = d_dl;
+  HIP_TRY(c, hipMemsetAsync(D.dh, 0xff, sizeof(OneDecHead), c->stream));  // first_bad, decode_bad: none
+  HIP_TRY(c, hipMemsetAsync(D.R, 0, kWinEntries, c->stream));
+  uint32_t e_at = 0;  // the entry of the round's first unit
+  for (uint32_t u0 = 0; u0 < n_dec; u0 += per_round) {
+    D.u0 = u0;
+    D.count = n_dec - u0 < per_round ? n_dec - u0 : per_round;
+    // the round's pieces: its units and a gap in front of every entry that starts behind its first unit
+    while (entry_unit[e_at + 1u] <= u0) ++e_at;
+    uint32_t e_hi = e_at;
+    while (e_hi + 1u < g_disc && entry_unit[e_hi + 1u] < (uint64_t)u0 + D.count) ++e_hi;
+    const uint32_t n_pieces = D.count + (e_hi - e_at);
+    const uint32_t unit_blocks = (D.count + 1u + 255u) / 256u;
+    const uint32_t entry_blocks = (uint32_t)(((uint64_t)D.count * kWinEntries + 255) / 256);
+    OneDecParams T = D;  // TAIL: a unit's history is what its own entry has produced in front of it
+    T.out_off = P.rel_off;
+    one_tail_launch(c, D.count, T);
+    hipLaunchKernelGGL(zip_units_pieces_kernel, dim3(unit_blocks), dim3(256), 0, c->stream, G);
+    int cur = 0;
+    for (uint32_t s = 1; s < D.count; s <<= 1, cur ^= 1)
+      hipLaunchKernelGGL(one_seek_compose_kernel, dim3(entry_blocks), dim3(256), 0, c->stream, D.F[cur], D.F[cur ^ 1],
+                         G.seed, D.count, s);
+    hipLaunchKernelGGL(one_seek_resolve_kernel, dim3(entry_blocks), dim3(256), 0, c->stream, D.F[cur], D.R, G.seed, D.count);
+    InfParams I{};
+    I.in = h_in;
+    I.in_len = hull_len;
+    I.bit_off = G.p_bit_off;
+    I.bit_end = G.p_bit_end;
+    I.n_streams = n_pieces;
+    I.out = d_out;
+    I.out_off = D.p_out_off;
+    I.out_len = d_dl;
+    I.status = d_ds;
+    I.err_off = d_de;
+    I.dict_buf = D.R;
+    I.dict_at = D.p_dict_at;
+    I.dict_len = D.p_dict_len;
+    if ((rc = launch_decoders(c, inflate_route_units(c->inflate, c->num_cus, n_pieces), I, true))) return rc;  // (of several rounds the stage's time is the last one's)
+    hipLaunchKernelGGL(zip_units_fold_kernel, dim3(unit_blocks), dim3(256), 0, c->stream, G);
+    OneDecParams K = D;  // the check: status 0 and exactly out_off[k + 1] - out_off[k] bytes
+    K.p_out_off = C.out_off + u0;
+    hipLaunchKernelGGL(one_check_kernel, dim3(unit_blocks), dim3(256), 0, c->stream, K);
+    HIP_TRY(c, hipGetLastError());
+    // the window behind the round's last unit seeds the next round (a round that starts with an entry reads none of it)
+    if (u0 + D.count < n_dec)
+      HIP_TRY(c, hipMemcpyAsync(D.R, D.R + (size_t)D.count * kWinEntries, kWinEntries, hipMemcpyDeviceToDevice, c->stream));
+  }
+  // the one small read-back of g
+  OneDecHead DH{};
+  HIP_TRY(c, hipMemcpyAsync(&DH, D.dh, sizeof DH, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  const uint32_t bad_unit = DH.first_bad < DH.decode_bad ? DH.first_bad : DH.decode_bad;
+  *g = zip_units_served(entry_unit.data(), g_disc, bad_unit);
+  *n_units = (uint32_t)entry_unit[*g];
+  return FLATE_HIP_OK;
+}
+
 // ---- one long stream decoded in pieces (Decompressor::read as the reference behaves: the caller
 // ---- holds a piece of input and a piece of output, never the whole stream; inflate.mbt:382-407) ----
 struct flate_hip_inflate_stream {

@@ -10,6 +10,7 @@
 
 #include "api_checks.h"
 #include "zip_rule.h"
+#include "zip_units_rule.h"
 
 using namespace flate;
 using namespace flate_host;
@@ -179,6 +180,7 @@ int flate_hip_zip_read(flate_hip_ctx *c, const uint8_t *in, uint64_t in_len, con
   int rc = zip_read_args(in, in_len, sel, n_sel, n_cap, out, out_cap, out_off, out_len, status, err_off, flags);
   if (rc) return rc;
   c->hip_err.clear();
+  for (uint32_t &w : c->zip_route) w = 0;
   if (n_entries) *n_entries = 0;
   if (archive_err_off) *archive_err_off = -1;
   out_off[0] = 0;
@@ -237,6 +239,27 @@ int flate_hip_zip_read(flate_hip_ctx *c, const uint8_t *in, uint64_t in_len, con
       d_out = (uint8_t *)c->d_out.p;
     }
 
+    // the option "zip_unit_min": the LONG entries (zip_units_rule.h: the set L) as one chain of units over their hull,
+    // decoded straight into their slots; the entries L[0, g) that come out GOOD are an empty range to the batch
+    // decoders, every other one is theirs as with the option off
+    uint32_t g = 0;
+    ZipUnitsDecParams UG{};
+    if (c->zip_unit_min) {
+      std::vector<ZuEntry> L;
+      std::vector<ZuRange> LR;
+      uint32_t fallback = 0, n_units = 0, n_cand = 0;
+      zip_units_form(ent.data(), n, sel, ns, out_off, c->zip_unit_min, L, LR, &fallback);
+      if (!L.empty()) {
+        uint64_t hull_lo = 0, hull_hi = 0;
+        zip_units_hull(L, LR, &hull_lo, &hull_hi);
+        if ((rc = zip_units_decode(c, d_in, hull_lo, hull_hi, L, LR, d_out, total, &g, UG, &n_units, &n_cand))) return rc;
+        for (uint32_t e = 0; e < g; ++e) soff[L[e].slot] = send[L[e].slot] = 0ull;
+        n_deflate -= g;
+      }
+      c->zip_route[0] = g, c->zip_route[1] = fallback + ((uint32_t)L.size() - g);
+      c->zip_route[2] = n_units, c->zip_route[3] = n_cand;
+    }
+
     // the batch decoders over the entries of method 8 (every other entry is an empty range to them, and its result is
     // replaced by zip_prep_kernel)
     if (n_deflate) {
@@ -274,6 +297,11 @@ int flate_hip_zip_read(flate_hip_ctx *c, const uint8_t *in, uint64_t in_len, con
     {
       StageTimer t(c, FLATE_HIP_STAGE_CHECKSUM);
       hipLaunchKernelGGL(zip_prep_kernel, dim3((ns + 255) / 256), dim3(256), 0, c->stream, R);
+      if (g) {  // the entries the units served: judged by the same checksums and the same verdict as every other
+        UG.g = g;
+        UG.z_out_len = R.out_len, UG.z_status = R.status, UG.z_err_off = R.err_off;
+        hipLaunchKernelGGL(zip_units_verdict_kernel, dim3((g + 255) / 256), dim3(256), 0, c->stream, UG);
+      }
       if (R.n_pieces) hipLaunchKernelGGL(zip_copy_kernel, dim3(R.n_pieces), dim3(256), 0, c->stream, R);
       if ((rc = checksum_device_clipped(c, d_out, out_off, ns, FLATE_HIP_CHECKSUM_CRC32, R.out_len, R.status, R.bad,
                                         (uint32_t *)c->d_frame_sums.p)))
@@ -288,9 +316,11 @@ int flate_hip_zip_read(flate_hip_ctx *c, const uint8_t *in, uint64_t in_len, con
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     ctl_finish(c);
     const float inflate_ms = c->stage_ms[FLATE_HIP_STAGE_INFLATE];  // (the decode driver has collected its own)
-    const bool used[FLATE_HIP_STAGE_COUNT] = {false, false, true, false};
+    // (units alone: the inflate stage is the last round's decoder launch, whose events nothing has collected yet)
+    const bool units_alone = g != 0 && n_deflate == 0;
+    const bool used[FLATE_HIP_STAGE_COUNT] = {false, false, true, units_alone};
     if ((rc = collect_timing(c, used))) return rc;
-    c->stage_ms[FLATE_HIP_STAGE_INFLATE] = inflate_ms;
+    if (!units_alone) c->stage_ms[FLATE_HIP_STAGE_INFLATE] = inflate_ms;
     for (uint32_t j = 0; j < ns; ++j)
       if (status[j]) return status[j];
     return FLATE_HIP_OK;

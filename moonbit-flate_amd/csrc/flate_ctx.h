@@ -101,6 +101,13 @@ struct flate_hip_ctx {
   // counted), the chain's arrays (GzFileParams), and the read's member-wise arrays beside d_one_dec's
   DevBuf d_gzfile_tiles, d_gzfile, d_gzfile_dec;
   DevBuf d_zip_names, d_zip_name_off, d_zip_whead, d_zip_end, d_zip_dir, d_zip_sel;
+  // flate_hip_zip_read with the option "zip_unit_min" (0 = off, the default: none of this is touched): a deflated entry
+  // of at least that many compressed bytes is decoded through units.  The count pass's words, L and the tile counts
+  // (sized before the candidates are counted), the chain's arrays (ZipUnitsParams), the rounds' entry-wise arrays
+  // beside d_one_dec's; and what the last call did (flate_hip_zip_last_route)
+  uint64_t zip_unit_min = 0;
+  DevBuf d_zip_units_tiles, d_zip_units, d_zip_units_dec;
+  uint32_t zip_route[4] = {0, 0, 0, 0};  // unit entries, fallback entries, units, candidates
   hipStream_t guest_stream = nullptr;
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
   int32_t h_status_word = 0;  // landing pads of small async D2H copies

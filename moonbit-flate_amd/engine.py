@@ -512,7 +512,22 @@ class GzFileSeekCalls:
         return _read_into(out, data, out_cap, "gzfile_ranges", call, size)
 
 
-class FlateEngine(OneSeekCalls, GzFileCalls, GzFileSeekCalls):
+class ZipUnitsCalls:
+    """ZIP reads with the option "zip_unit_min": the method FlateEngine inherits.  It stands in a class of its own so
+    that its marshalling has its own recorded scenarios (tests/engine_trace_zip_units.py) beside the ones of the methods
+    that were there before."""
+
+    def zip_last_route(self):
+        """What the last zip_read on this engine did with the option "zip_unit_min" (flate_hip_zip_last_route):
+        (unit_entries, fallback_entries, n_units, n_candidates) -- the selection slots served by units, the slots that
+        qualified by size but went to the batch decoders, the units on the path, FIND's candidates.  All zero with the
+        option at 0: results are identical by design, so this is how to see which path ran."""
+        w = [C.c_uint32(0) for _ in range(4)]
+        self._check(self._L.flate_hip_zip_last_route(self._ctx, *[C.byref(x) for x in w]))
+        return tuple(int(x.value) for x in w)
+
+
+class FlateEngine(OneSeekCalls, GzFileCalls, GzFileSeekCalls, ZipUnitsCalls):
     """One engine = one flate_hip_ctx = one GPU + one HIP stream."""
 
     def __init__(self, device=0):
@@ -1005,7 +1020,9 @@ class FlateEngine(OneSeekCalls, GzFileCalls, GzFileSeekCalls):
         CUDA tensor for device data).  rc 0; -4 with archive_err_off >= 0: a malformed archive, nothing decoded; -2
         with out_off[-1] > capacity: out too small, nothing decoded; otherwise the first non-zero entry status, all other
         entries delivered.  out=None: sized by the size query first.  A name that is not in the archive raises KeyError;
-        other failures raise FlateError."""
+        other failures raise FlateError.  After set_option("zip_unit_min", v) with v >= 1 a deflated entry of at least v
+        compressed bytes (an .npz array, one large CSV) is decoded in parallel through units, with the same results;
+        zip_last_route() says which path ran."""
         data, in_ptr, n, device = _in_buf(data, accept_bytes=True, null_if_empty=True)
         flags = self._flags(False, False, device)
         sel = None

@@ -66,7 +66,17 @@ class Engine {
   int status() const { return rc_; }
   flate_hip_ctx *ctx() const { return ctx_; }
   // flate_hip_set_option: e.g. ("one_stored_units", 1) so that stored block headers start units too
+  // ... or ("zip_unit_min", 1 << 20) so that flate_hip_zip_read decodes long entries in parallel through units
   int set_option(const char *name, int64_t value) { return flate_hip_set_option(ctx_, name, value); }
+  // flate_hip_zip_last_route: what the last ZIP read on this engine did with "zip_unit_min"
+  struct ZipRoute {
+    uint32_t unit_entries = 0, fallback_entries = 0, n_units = 0, n_candidates = 0;
+  };
+  ZipRoute zip_last_route() const {
+    ZipRoute r;
+    (void)flate_hip_zip_last_route(ctx_, &r.unit_entries, &r.fallback_entries, &r.n_units, &r.n_candidates);
+    return r;
+  }
 
  private:
   flate_hip_ctx *ctx_ = nullptr;
