@@ -127,6 +127,12 @@ int flate_hip_set_stream(flate_hip_ctx *ctx, void *hip_stream);
  *                        default 1 GiB, read when the stream is opened; results never change
  *   "zip_unit_min"       flate_hip_zip_read: 0 (default) = every entry goes to the batch decoders; v >= 1 = a deflated
  *                        entry of at least v compressed bytes is decoded through units (ZIP archives, below)
+ *   "gzfile_serial_max"  flate_hip_gzfile_index / _read only: 0 (default) = every member is cut into units; S >= 1
+ *                        (at most 2^28 - 1, like "gzip_member_max") = a member whose header and raw stream fit in
+ *                        S bytes and decode cleanly is ONE unit, decoded whole by the batch decoders.  Bytes,
+ *                        out_len, status, bad_member, err_off, stream_err_off, n_members, member_off and the
+ *                        trailer verdicts never change; n_units, unit_bit, out_off, member_unit and
+ *                        n_candidates do (A gzip FILE of any members, below)
  *   "one_stored_units"   flate_hip_inflate_one* and flate_hip_gzfile_*: 0 (default) = a unit starts at bit 0
  *                        and at every dynamic block header; 1 = at every STORED block header too, so that a
  *                        run of stored blocks (incompressible data) is many units instead of one: it is
@@ -1007,9 +1013,52 @@ int flate_hip_inflate_one_ranges(flate_hip_ctx *ctx, const uint8_t *in, uint64_t
  *   output ranges, a thread per trailer, an ordered min.  Profiling: FLATE_HIP_STAGE_INFLATE is DECODE (of several
  *   rounds the last), FLATE_HIP_STAGE_CHECKSUM is VERIFY; the rest is counted in no stage.
  *   Out of scope: zlib or raw concatenations; routing
- *   flate_hip_gzip_read or flate_hip_inflate_one here automatically; choosing per member between the serial and the
- *   unit decoder; fixed block starts as units (stored ones: option "one_stored_units"; a member's first unit starts
- *   behind its header whatever block is there, and the hop behind BFINAL is unchanged); caching across calls. */
+ *   flate_hip_gzip_read or flate_hip_inflate_one here automatically; fixed block starts as units (stored ones: option
+ *   "one_stored_units"; a member's first unit starts
+ *   behind its header whatever block is there, and the hop behind BFINAL is unchanged); caching across calls.
+ *
+ * SHORT MEMBERS DECODED WHOLE: the option "gzfile_serial_max" = S (0, the default: off -- both calls launch the
+ * kernels above in that order, nothing more).  With S >= 1 a member whose header and raw stream fit in S bytes and
+ * decode cleanly is a WHOLE member, ONE unit of the chain (the rule: csrc/gzfile_serial_rule.h).  For the member whose
+ * header starts at byte p and is hl bytes long, the serial range is in[p + hl, E), E = min(in_len - 8, p + S); the
+ * member is whole iff a size-only serial decode over that range ends its final block with status 0 and p + hl + used
+ * <= E.  It is never searched for block headers and never walked symbolically; flate_hip_gzfile_read decodes all whole
+ * members with ONE batch of the batch decoders (routed like flate_hip_inflate_batch from their count and S) straight
+ * into their places in out, in front of the rounds.  Every other member -- longer, failing for any reason, the one the
+ * chain breaks in -- is cut into units exactly as with S = 0.
+ *   What never changes with the option: the delivered bytes, *out_len, *status, *bad_member, *err_off,
+ *   *stream_err_off, *n_members, member_off and the trailer verdicts.  What DOES change: *n_units, unit_bit, out_off,
+ *   member_unit and *n_candidates (which is why the default stays 0, as for "one_stored_units" and "zip_unit_min").  The
+ *   units are S = 0's units without every unit of a whole member that is not that member's first; unit_bit and out_off
+ *   of the kept units are S = 0's values; member_unit is renumbered; unit_bit[n_units], when the last good unit is a
+ *   whole member, is the BYTE-ROUNDED bit behind its final block, 8 * (p + hl + used).  *n_candidates counts List B and
+ *   the part of List A that was searched; it never exceeds S = 0's count.  "one_unit_max" and "one_round_units" apply
+ *   to ordinary units only: a whole member is bounded by S (with "one_unit_max" lowered below S, a whole member may
+ *   hold a unit that S = 0 refuses as too large).
+ *   How: PHASE 1 -- List B, then ONE size-only launch of the batch decoders over the serial ranges of all B candidates
+ *   (as flate_hip_gzip_index does), the whole test, the hop links of the whole candidates, and a pointer-doubling walk
+ *   from the member at offset 0 for as long as the members it reaches are whole: find_from = the offset of the first
+ *   member on that walk that is not whole, or in_len when the walk reaches the file's end, a dead hop or a file that
+ *   starts with no member.  PHASE 2, only if find_from < in_len -- FIND (list A) over in[find_from, in_len) alone; PROBE
+ *   over A and the B nodes that are not whole.  The chain, the scans and VERIFY are unchanged; the rounds run over the
+ *   runs of units between whole members (a run starts with a member's first unit, a seed).  The whole-member batch is
+ *   counted in FLATE_HIP_STAGE_INFLATE.  Device pointers: nothing at or behind out + T is written, T being what the
+ *   size query reports; T == *out_len except when TAIL alone finds the failure (a distance in front of its member):
+ *   whole members behind the failing one have been decoded by then, so out[*out_len, T) is unspecified in that case
+ *   (with S = 0 it is untouched); the delivered bytes out[0, *out_len) are the same.
+ *   Recommended: S = 1 MiB (1 GiB of S-text at zlib level 6 on one MI355X): a file of 16 384 members
+ *   of 64 KiB reads in 21.1 ms instead of 1246.1 (flate_hip_gzip_read: 20.8), one of 1024 members of 1 MiB in 32.6
+ *   instead of 883.6; what a file of long members pays is the size-only probe of each long member up to its clip,
+ *   + 23 ms on one 1 GiB member (862.5 -> 885.5; S = 64 KiB: + 1.8, 256 KiB: + 4.8, 4 MiB: + 98.9), and S = 256 KiB
+ *   or less leaves the 1 MiB members (about 410 KiB compressed) to the units.
+ *   The option is ignored by flate_hip_gzfile_seek_index / _ranges, flate_hip_inflate_one*, flate_hip_gzip_* and the ZIP
+ *   calls.  Out of scope: FIND in windows between long members (the search runs from the first long member to the
+ *   file's end); running a clipped candidate again unclipped.
+ * flate_hip_gzfile_last_route: what the last flate_hip_gzfile_index or flate_hip_gzfile_read on this ctx did --
+ * *serial_members = the whole members among the discovery's good units, *unit_members = the discovery's other good
+ * members (n_members - serial_members; the member a chain breaks in is counted in neither), *find_from as above (0
+ * with the option off or an empty file: the search ran from the file's first byte; == in_len: no bit-offset search
+ * ran).  Every pointer is required (else FLATE_HIP_E_INVALID); no HIP call. */
 int flate_hip_gzfile_index(flate_hip_ctx *ctx, const uint8_t *in, uint64_t in_len, uint64_t index_cap,
                            uint64_t *unit_bit, uint64_t *out_off, uint64_t member_cap, uint64_t *member_off,
                            uint64_t *member_unit, uint32_t *n_units, uint32_t *n_members, uint64_t *out_bytes,
@@ -1019,6 +1068,8 @@ int flate_hip_gzfile_read(flate_hip_ctx *ctx, const uint8_t *in, uint64_t in_len
                           uint64_t *out_len, uint32_t *n_members, uint32_t *n_units, uint32_t *n_candidates,
                           int32_t *status, uint32_t *bad_member, int64_t *err_off, int64_t *stream_err_off,
                           uint32_t flags);
+int flate_hip_gzfile_last_route(const flate_hip_ctx *ctx, uint32_t *serial_members, uint32_t *unit_members,
+                                uint64_t *find_from);
 
 /* -- Seek index for any gzip file: build once, read ranges across members -------------
  * flate_hip_gzfile_read pays the whole discovery on every call and delivers everything.  flate_hip_gzfile_seek_index

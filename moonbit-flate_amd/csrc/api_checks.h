@@ -243,6 +243,16 @@ inline int gzfile_ranges_args(const uint8_t *in, uint64_t in_len, const uint64_t
              : FLATE_HIP_E_INVALID;
 }
 
+// the option "gzfile_serial_max": 0 (the default) = every member is cut into units; S >= 1 = a member whose header and
+// raw stream fit in S bytes and decode cleanly is decoded whole (gzfile_serial_rule.h); at most 2^28 - 1, the range of
+// the size-only decoders' bit positions, as for "gzip_member_max"
+inline bool gzfile_serial_max_ok(int64_t value) { return value >= 0 && value <= (1ll << 28) - 1; }
+// flate_hip_gzfile_last_route: every result pointer is required
+inline int gzfile_last_route_args(const void *ctx, const uint32_t *serial_members, const uint32_t *unit_members,
+                                  const uint64_t *find_from) {
+  return (!ctx || !serial_members || !unit_members || !find_from) ? FLATE_HIP_E_INVALID : FLATE_HIP_OK;
+}
+
 // ---- ZIP archives (flate_hip_zip_write / _index / _read) ----
 
 // everything flate_hip_zip_write refuses before any HIP call

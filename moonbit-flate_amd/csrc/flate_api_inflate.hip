@@ -1975,6 +1975,234 @@ int gzfile_discover(flate_hip_ctx *c, const uint8_t *d_in, uint64_t in_len, OneH
   return FLATE_HIP_OK;
 }
 
+// The same discovery with the option "gzfile_serial_max" (S >= 1; gzfile_serial_rule.h, gzfile_serial_kernels.hip).
+// PHASE 1 over List B alone: count, scan, a read-back of the B count, fill, the serial ranges, ONE size-only launch of
+// the batch decoders over all B candidates, the whole test with the hop links, pointer doubling over those links, and
+// a read-back of find_from.  PHASE 2, only when find_from < in_len: FIND over in[find_from, in_len) -- the pass runs on
+// d_in + find_from with a FrameOne of its own, and one small kernel moves its bits to the file's origin -- and the
+// read-back of its count.  PROBE runs over all nodes; a whole B node is parked at the raw stream's end for it and gets
+// its phase-1 record back behind it.  Link, rounds, finish, the scans and the rel kernel are gzfile_discover's.  SH =
+// find_from and the whole members among the good units; S = their batch, on the device.
+int gzfile_discover_serial(flate_hip_ctx *c, const uint8_t *d_in, uint64_t in_len, OneHead &H, GzFileHead &G,
+                           GzFileParams &P, GzSerialParams &S, GzSerialHead &SH, std::vector<uint64_t> *mout) {
+  int rc;
+  P = GzFileParams{};
+  S = GzSerialParams{};
+  SH = GzSerialHead{};
+  OneParams PA{};
+  GzipParams PB{};
+  ChainParams &C = P.O.C;
+  uint32_t n_tiles = 0;
+  if ((rc = tiles_for(d_in, 0, in_len, &n_tiles))) return rc;
+  OneHead *head_a;
+  BgzfHead *head_b;
+  FrameOne *one_a;
+  rc = carve(c, c->d_gzfile_tiles, [&](Carve &k) {
+    k.take(P.O.head, 1);
+    k.take(P.gh, 1);
+    k.take(P.O.one, 1);
+    k.take(head_a, 1);
+    k.take(head_b, 1);
+    k.take(one_a, 1);
+    k.take(S.head, 1);
+    k.take(PA.C.tile_cnt, (size_t)n_tiles + 2);  // (a suffix at another alignment: at most one tile more)
+    k.take(PB.C.tile_cnt, (size_t)n_tiles + 1);
+  });
+  if (rc) return rc;
+  C.in = PB.C.in = d_in;
+  C.in_len = PB.C.in_len = in_len;
+  C.n_tiles = PB.C.n_tiles = n_tiles;
+  C.head = &P.O.head->h;
+  P.O.unit_max = PA.unit_max = c->one_unit_max;
+  P.O.stored_units = PA.stored_units = c->one_stored_units;
+  PB.C.head = head_b;
+  PB.member_max = ~0ull;  // a member's range is never clipped
+  hipLaunchKernelGGL(gzfile_init_kernel, dim3(1), dim3(64), 0, c->stream, P.O.one, in_len);
+  hipLaunchKernelGGL(gzip_count_kernel, dim3(n_tiles), dim3(256), 0, c->stream, PB);
+  hipLaunchKernelGGL(chain_scan_kernel, dim3(1), dim3(1024), 0, c->stream, PB.C);
+  HIP_TRY(c, hipGetLastError());
+  BgzfHead HB{};
+  HIP_TRY(c, hipMemcpyAsync(&HB, head_b, sizeof HB, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  const uint32_t nb = HB.n_cand;
+  if (nb > 0x7ffffff0u) return FLATE_HIP_E_TOO_LARGE;  // (the count saturates at 2^32 - 1)
+  if ((rc = chain_size(PB.C, nb))) return rc;
+
+  // PHASE 1
+  uint64_t *hdr_off;
+  InfParams I{};  // size-only: no output buffer, no slots
+  rc = carve(c, c->d_gzfile_serial, [&](Carve &k) {
+    k.take(hdr_off, (size_t)nb + 1);
+    k.take(PB.cand_end, nb);
+    k.take(S.pay_off, (size_t)nb + 1);
+    k.take(S.pay_end, nb);
+    k.take(I.out_len, nb);
+    k.take(I.status, nb);
+    k.take(I.err_off, nb);
+    k.take(I.used, nb);
+    k.take(S.rec, nb);
+    k.take(S.whole, nb);
+    k.take(S.jump[0], (size_t)nb + 2);
+    k.take(S.jump[1], (size_t)nb + 2);
+    k.take(S.w_in_off, (size_t)nb + 1);
+    k.take(S.w_in_end, nb);
+    k.take(S.w_out_off, (size_t)nb + 1);
+    k.take(S.w_size, nb);
+    k.take(S.w_unit, nb);
+  });
+  if (rc) return rc;
+  PB.C.cand_off = hdr_off;
+  P.hdr_off = hdr_off;
+  P.n_b = nb;
+  S.in = d_in;
+  S.in_len = in_len;
+  S.serial_max = c->gzfile_serial_max;
+  S.n_b = nb;
+  S.hdr_off = hdr_off;
+  S.status = I.status;
+  S.out_len = I.out_len;
+  S.used = I.used;
+  uint64_t find_from = in_len;  // (no candidate: no member at offset 0, nothing to search)
+  if (nb) {
+    const uint32_t b_blocks = (nb + 255u) / 256u, w_blocks = (uint32_t)(((uint64_t)nb + 2 + 255) / 256);
+    // every range is at most S < 2^28 bytes: the sub-block decoder at any batch size, or -- switched off -- the scalar
+    // walk; both report `used`
+    const uint64_t longest = in_len < S.serial_max ? in_len : S.serial_max;
+    const InflateRoute route = inflate_route(c->inflate, c->num_cus, nb, longest, false, true);
+    if (route.decoder == kDecodeSimt) {
+      c->hip_err = "gzfile discovery: a size-only pass was routed to the lane-per-stream decoder";
+      return FLATE_HIP_E_INTERNAL;
+    }
+    I.in = d_in;
+    I.in_off = S.pay_off;
+    I.in_end = S.pay_end;
+    I.n_streams = nb;
+    I.in_len = in_len;
+    I.size_only = 1u;
+    hipLaunchKernelGGL(gzip_fill_kernel, dim3(n_tiles), dim3(256), 0, c->stream, PB);
+    hipLaunchKernelGGL(gzfile_serial_ranges_kernel, dim3(b_blocks), dim3(256), 0, c->stream, S);
+    HIP_TRY(c, hipGetLastError());
+    if ((rc = launch_decoders(c, route, I, false))) return rc;
+    hipLaunchKernelGGL(gzfile_serial_nodes_kernel, dim3(w_blocks), dim3(256), 0, c->stream, S);
+    int cur = 0;
+    for (uint64_t s = 1; s < (uint64_t)nb + 2; s <<= 1, cur ^= 1)
+      hipLaunchKernelGGL(gzfile_serial_round_kernel, dim3(w_blocks), dim3(256), 0, c->stream, S.jump[cur], S.jump[cur ^ 1],
+                         nb + 2u);
+    hipLaunchKernelGGL(gzfile_serial_from_kernel, dim3(1), dim3(64), 0, c->stream, S, S.jump[cur]);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(&SH, S.head, sizeof SH, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    find_from = SH.find_from;
+    if (find_from > in_len) return FLATE_HIP_E_INTERNAL;
+  } else {
+    SH.find_from = in_len;
+    HIP_TRY(c, hipMemcpyAsync(S.head, &SH, sizeof SH, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));  // (SH is the caller's: the copy has read it)
+  }
+
+  // PHASE 2: FIND over the bytes from find_from on
+  uint32_t na = 0, n_tiles_a = 0;
+  if (find_from < in_len) {
+    const uint8_t *a_in = d_in + find_from;
+    const uint64_t a_len = in_len - find_from;
+    if ((rc = tiles_for(a_in, 0, a_len, &n_tiles_a))) return rc;
+    if (n_tiles_a > n_tiles + 1u) return FLATE_HIP_E_INTERNAL;
+    PA.C.in = a_in;
+    PA.C.in_len = a_len;
+    PA.C.n_tiles = n_tiles_a;
+    PA.C.head = &head_a->h;
+    PA.head = head_a;
+    PA.one = one_a;
+    hipLaunchKernelGGL(gzfile_init_kernel, dim3(1), dim3(64), 0, c->stream, one_a, a_len);
+    one_find_launch(c, true, n_tiles_a, PA);
+    hipLaunchKernelGGL(chain_scan_kernel, dim3(1), dim3(1024), 0, c->stream, PA.C);
+    HIP_TRY(c, hipGetLastError());
+    OneHead HA{};
+    HIP_TRY(c, hipMemcpyAsync(&HA, head_a, sizeof HA, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    na = HA.h.n_cand;
+  }
+  if ((uint64_t)na + nb > 0x7ffffff0ull) return FLATE_HIP_E_TOO_LARGE;
+  const uint32_t cap = na + nb;
+  if ((rc = chain_size(C, cap)) || (rc = chain_size(PA.C, na))) return rc;
+  P.n_a = S.n_a = na;
+
+  const size_t n = cap;
+  rc = carve(c, c->d_gzfile, [&](Carve &k) {
+    k.take(C.cand_off, n);
+    k.take(P.O.probe, n);
+    k.take(C.jump[0], n + 2);
+    k.take(C.jump[1], n + 2);
+    k.take(C.path, C.path_len);
+    k.take(P.O.usize, n);
+    k.take(C.member_off, n + 1);
+    k.take(C.out_off, n + 1);
+    k.take(P.u_start, n + 1);
+    k.take(P.u_final, n);
+    k.take(P.u_member, n + 1);
+    k.take(P.rel_off, n + 1);
+    k.take(P.member_off, (size_t)nb + 2);
+    k.take(P.member_unit, (size_t)nb + 2);
+    k.take(P.member_out, (size_t)nb + 2);
+  });
+  if (rc) return rc;
+  rc = carve(c, c->d_gzfile_serial_units, [&](Carve &k) {
+    k.take(S.u_whole, n + 1);
+    k.take(S.u_end, n + 1);
+  });
+  if (rc) return rc;
+  PA.C.cand_off = C.cand_off;
+  if (find_from < in_len) {
+    one_find_launch(c, false, n_tiles_a, PA);
+    if (na) hipLaunchKernelGGL(gzfile_serial_base_kernel, dim3((na + 255u) / 256u), dim3(256), 0, c->stream, C.cand_off, na, 8u * find_from);
+  }
+  if (nb) hipLaunchKernelGGL(gzfile_serial_bits_kernel, dim3((nb + 255) / 256), dim3(256), 0, c->stream, P, S);
+  if (cap) one_probe_launch(c, cap, P.O, 0u);
+  if (nb) hipLaunchKernelGGL(gzfile_serial_keep_kernel, dim3((nb + 255) / 256), dim3(256), 0, c->stream, P, S);
+  const uint32_t node_blocks = (uint32_t)(((uint64_t)cap + 2 + 255) / 256);
+  hipLaunchKernelGGL(gzfile_link_kernel, dim3(node_blocks), dim3(256), 0, c->stream, P);
+  for (uint32_t j = 0; (1u << j) < C.path_len; ++j)
+    hipLaunchKernelGGL(chain_round_kernel, dim3(node_blocks), dim3(256), 0, c->stream, C, j);
+  hipLaunchKernelGGL(gzfile_finish_kernel, dim3((C.path_len + 255) / 256), dim3(256), 0, c->stream, P);
+  hipLaunchKernelGGL(gzfile_serial_marks_kernel, dim3(node_blocks), dim3(256), 0, c->stream, P, S);
+  hipLaunchKernelGGL(one_out_scan_kernel, dim3(1), dim3(1024), 0, c->stream, P.O);
+  hipLaunchKernelGGL(gzfile_members_kernel, dim3(1), dim3(1024), 0, c->stream, P);
+  one_probe_launch(c, 1, P.O, 1u);
+  hipLaunchKernelGGL(gzfile_rel_kernel, dim3(node_blocks), dim3(256), 0, c->stream, P);
+  hipLaunchKernelGGL(gzfile_serial_list_kernel, dim3(1), dim3(1024), 0, c->stream, P, S);
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipMemcpyAsync(&H, P.O.head, sizeof H, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(&G, P.gh, sizeof G, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(&SH, S.head, sizeof SH, hipMemcpyDeviceToHost, c->stream));
+  if (mout) {
+    mout->assign((size_t)nb + 2, 0);
+    HIP_TRY(c, hipMemcpyAsync(mout->data(), P.member_out, ((size_t)nb + 2) * 8, hipMemcpyDeviceToHost, c->stream));
+  }
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  if (G.n_members > nb || H.h.n_members > cap || SH.n_whole > nb || SH.n_whole > G.n_members || SH.find_from != find_from)
+    return FLATE_HIP_E_INTERNAL;
+  return FLATE_HIP_OK;
+}
+
+// the discovery of flate_hip_gzfile_index / _read by the ctx's option, and what flate_hip_gzfile_last_route reports
+int gzfile_discover_routed(flate_hip_ctx *c, const uint8_t *d_in, uint64_t in_len, OneHead &H, GzFileHead &G,
+                           GzFileParams &P, GzSerialParams &S, GzSerialHead &SH, std::vector<uint64_t> *mout) {
+  c->gzfile_route[0] = c->gzfile_route[1] = 0;
+  c->gzfile_route_from = 0;
+  int rc;
+  if (!c->gzfile_serial_max) {
+    S = GzSerialParams{};
+    SH = GzSerialHead{};
+    if ((rc = gzfile_discover(c, d_in, in_len, H, G, P, mout))) return rc;
+  } else if ((rc = gzfile_discover_serial(c, d_in, in_len, H, G, P, S, SH, mout))) {
+    return rc;
+  }
+  c->gzfile_route[0] = SH.n_whole;
+  c->gzfile_route[1] = G.n_members - SH.n_whole;
+  c->gzfile_route_from = SH.find_from;
+  return FLATE_HIP_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1999,11 +2227,15 @@ int flate_hip_gzfile_index(flate_hip_ctx *c, const uint8_t *in, uint64_t in_len,
     OneHead H{};
     GzFileHead G{};
     GzFileParams P{};
+    GzSerialParams SP{};
+    GzSerialHead SH{};
     G.err_off = G.stream_err_off = -1;
+    c->gzfile_route[0] = c->gzfile_route[1] = 0;
+    c->gzfile_route_from = 0;
     if (in_len) {  // (no bytes: zero members, zero units)
       const uint8_t *d_in = nullptr;
       if ((rc = stage_input(c, in, in_len, flags, &d_in))) return rc;
-      if ((rc = gzfile_discover(c, d_in, in_len, H, G, P, nullptr))) return rc;
+      if ((rc = gzfile_discover_routed(c, d_in, in_len, H, G, P, SP, SH, nullptr))) return rc;
     }
     *n_units = H.h.n_members;
     *n_members = G.n_members;
@@ -2060,6 +2292,8 @@ int flate_hip_gzfile_read(flate_hip_ctx *c, const uint8_t *in, uint64_t in_len, 
   if (bad_member) *bad_member = 0xffffffffu;
   if (err_off) *err_off = -1;
   if (stream_err_off) *stream_err_off = -1;
+  c->gzfile_route[0] = c->gzfile_route[1] = 0;
+  c->gzfile_route_from = 0;
   if (in_len == 0) return FLATE_HIP_OK;
   try {
     const bool dev = (flags & FLATE_HIP_DEVICE_PTRS) != 0;
@@ -2068,8 +2302,10 @@ int flate_hip_gzfile_read(flate_hip_ctx *c, const uint8_t *in, uint64_t in_len, 
     OneHead H{};
     GzFileHead G{};
     GzFileParams P{};
+    GzSerialParams SP{};
+    GzSerialHead SH{};
     std::vector<uint64_t> mout;
-    if ((rc = gzfile_discover(c, d_in, in_len, H, G, P, &mout))) return rc;
+    if ((rc = gzfile_discover_routed(c, d_in, in_len, H, G, P, SP, SH, &mout))) return rc;
     if (n_members) *n_members = G.n_members;
     if (n_units) *n_units = H.h.n_members;
     if (n_candidates) *n_candidates = H.h.n_cand;
@@ -2085,7 +2321,27 @@ int flate_hip_gzfile_read(flate_hip_ctx *c, const uint8_t *in, uint64_t in_len, 
       d_out = (uint8_t *)c->d_out.p;
     }
     const uint32_t n_mem = H.h.rc == 0 ? G.n_members : 0u;  // the members whose trailers are judged
-    const uint32_t per_round = n_dec < c->one_round_units ? (n_dec ? n_dec : 1u) : c->one_round_units;
+    // the runs of units the rounds go over: all of them, or (option "gzfile_serial_max") what lies between the whole
+    // members -- a run starts with a member's first unit, a seed, and ends where a member does
+    const uint32_t n_whole = SH.n_whole;
+    std::vector<std::pair<uint32_t, uint32_t>> runs;
+    uint32_t longest_run = n_dec;
+    if (n_whole) {
+      std::vector<uint32_t> whole(n_dec);
+      HIP_TRY(c, hipMemcpyAsync(whole.data(), SP.u_whole, (size_t)n_dec * 4, hipMemcpyDeviceToHost, c->stream));
+      HIP_TRY(c, hipStreamSynchronize(c->stream));
+      longest_run = 0;
+      for (uint32_t a = 0; a < n_dec;) {
+        uint32_t b = a;
+        while (b < n_dec && !whole[b]) ++b;
+        if (b > a) runs.emplace_back(a, b);
+        if (b - a > longest_run) longest_run = b - a;
+        a = b + 1u;
+      }
+    } else if (n_dec) {
+      runs.emplace_back(0u, n_dec);
+    }
+    const uint32_t per_round = longest_run < c->one_round_units ? (longest_run ? longest_run : 1u) : c->one_round_units;
     const size_t fentries = (size_t)per_round * kWinEntries;
     GzFileDecParams GD{};
     OneDecParams &D = GD.D;
@@ -2137,9 +2393,35 @@ int flate_hip_gzfile_read(flate_hip_ctx *c, const uint8_t *in, uint64_t in_len, 
     HIP_TRY(c, hipMemsetAsync(GD.v, 0xff, sizeof(GzFileVerdict), c->stream));  // bad_trailer: none
     HIP_TRY(c, hipMemsetAsync(D.R, 0, kWinEntries, c->stream));                // in front of the file: zeros
     bool used[FLATE_HIP_STAGE_COUNT] = {false, false, false, false};
-    for (uint32_t u0 = 0; u0 < n_dec; u0 += per_round) {
+    if (n_whole && total) {
+      // the WHOLE members: ONE batch of independent streams straight into their places, IN FRONT of the rounds.  A slot
+      // ends at the next whole member's start (the last at the end of the good units' output), so it may span the units
+      // between them: whatever the batch leaves there is overwritten by the units that own those bytes
+      InfParams W{};
+      rc = carve(c, c->d_gzfile_serial_dec, [&](Carve &k) {
+        k.take(W.out_len, n_whole);
+        k.take(W.status, n_whole);
+        k.take(W.err_off, n_whole);
+      });
+      if (rc) return rc;
+      W.in = d_in;
+      W.in_off = SP.w_in_off;
+      W.in_end = SP.w_in_end;
+      W.n_streams = n_whole;
+      W.in_len = in_len;
+      W.out = d_out;
+      W.out_off = SP.w_out_off;
+      const uint64_t longest = in_len < SP.serial_max ? in_len : SP.serial_max;
+      if ((rc = launch_decoders(c, inflate_route(c->inflate, c->num_cus, n_whole, longest, false, false), W, false))) return rc;
+      hipLaunchKernelGGL(gzfile_serial_check_kernel, dim3((n_whole + 255u) / 256u), dim3(256), 0, c->stream, SP, n_whole,
+                         W.status, W.out_len, D.dh);
+      used[FLATE_HIP_STAGE_INFLATE] = true;
+      HIP_TRY(c, hipGetLastError());
+    }
+    for (const auto &run : runs)
+    for (uint32_t u0 = run.first; u0 < run.second; u0 += per_round) {
       D.u0 = u0;
-      D.count = n_dec - u0 < per_round ? n_dec - u0 : per_round;
+      D.count = run.second - u0 < per_round ? run.second - u0 : per_round;
       const uint32_t unit_blocks = (D.count + 1u + 255u) / 256u;
       const uint32_t entry_blocks = (uint32_t)(((uint64_t)D.count * kWinEntries + 255) / 256);
       OneDecParams T = D;  // TAIL: a unit's history is what its own member has produced in front of it

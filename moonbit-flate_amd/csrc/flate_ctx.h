@@ -100,6 +100,14 @@ struct flate_hip_ctx {
   // flate_hip_gzfile_index / _read: the two count passes' words and tile counts (sized before the candidates are
   // counted), the chain's arrays (GzFileParams), and the read's member-wise arrays beside d_one_dec's
   DevBuf d_gzfile_tiles, d_gzfile, d_gzfile_dec;
+  // ... with the option "gzfile_serial_max" (0 = off, the default: none of this is touched): a member whose header and
+  // raw stream fit in that many bytes and decode cleanly is one unit, decoded whole by the batch decoders
+  // (gzfile_serial_rule.h).  Phase 1's arrays over List B (sized when the B count is known), the per-unit marks (sized
+  // with the chain), the read's batch results; and what the last index or read call did (flate_hip_gzfile_last_route)
+  uint64_t gzfile_serial_max = 0;
+  DevBuf d_gzfile_serial, d_gzfile_serial_units, d_gzfile_serial_dec;
+  uint32_t gzfile_route[2] = {0, 0};  // serial members, unit members
+  uint64_t gzfile_route_from = 0;     // find_from
   DevBuf d_zip_names, d_zip_name_off, d_zip_whead, d_zip_end, d_zip_dir, d_zip_sel;
   // flate_hip_zip_read with the option "zip_unit_min" (0 = off, the default: none of this is touched): a deflated entry
   // of at least that many compressed bytes is decoded through units.  The count pass's words, L and the tile counts

@@ -733,6 +733,64 @@ __global__ void gzfile_pieces_kernel(GzFileDecParams G);
 __global__ void gzfile_trailer_kernel(GzFileDecParams G);
 __global__ void gzfile_verdict_kernel(GzFileDecParams G);
 
+// Short members decoded WHOLE (gzfile_serial_kernels.hip; the option "gzfile_serial_max" = S >= 1; the rule:
+// gzfile_serial_rule.h).  With the option off none of this is launched and the structures above are what they were.
+// PHASE 1 runs over List B alone, in front of FIND: gzfile_serial_ranges_kernel gives every B candidate its serial
+// range, ONE size-only launch of the batch decoders runs over them (InfParams::used), gzfile_serial_nodes_kernel
+// applies the whole test -- a whole candidate gets its record and links by THE HOP, every other node absorbs --,
+// gzfile_serial_round_kernel doubles the pointers and gzfile_serial_from_kernel reads find_from where the walk from
+// candidate 0 came to rest.  PHASE 2: FIND runs over in[find_from, in_len) only (or not at all);
+// gzfile_serial_base_kernel moves its bits to the file's origin; gzfile_serial_bits_kernel is gzfile_bits_kernel,
+// except that a whole candidate's bit is the raw stream's end, so that PROBE leaves it at once;
+// gzfile_serial_keep_kernel puts a whole candidate's bit and its phase-1 record back behind PROBE.  Link, rounds,
+// finish, the scans and the rel kernel then run over the combined nodes as they are: a whole member is a unit that
+// ends with BFINAL.  gzfile_serial_marks_kernel: per path rank, is the unit a whole member, and where its stream ends;
+// gzfile_serial_list_kernel (one workgroup, behind the out-scan): the whole members of the good units compacted into
+// the streams of ONE batch -- in_off, in_end, the slots (the last one ends at out_off[n_units]) and their sizes.
+// gzfile_serial_check_kernel, behind that batch in the read: status 0 and exactly the size the discovery found, else
+// OneDecHead::decode_bad.
+struct GzSerialHead {
+  uint64_t find_from;      // phase 1: where FIND starts; in_len = nowhere
+  uint32_t n_whole;        // gzfile_serial_list_kernel: the whole members among the good units
+  uint32_t pad;
+};
+struct GzSerialParams {
+  const uint8_t *in;
+  uint64_t in_len;
+  uint64_t serial_max;     // S
+  uint32_t n_a, n_b;
+  const uint64_t *hdr_off; // n_b + 1: List B's byte offsets
+  uint64_t *pay_off;       // n_b + 1: the serial ranges
+  uint64_t *pay_end;       // n_b
+  const int32_t *status;   // n_b each: what the size-only decode left
+  const uint64_t *out_len;
+  const uint64_t *used;
+  OneProbe *rec;           // n_b: a whole candidate's record
+  uint32_t *whole;         // n_b
+  uint32_t *jump[2];       // n_b + 2: the walk's links; n_b = the file's end, n_b + 1 = a dead hop
+  GzSerialHead *head;
+  // behind the chain (sized for its n_a + n_b nodes)
+  uint32_t *u_whole;       // cap + 1, per unit
+  uint64_t *u_end;         // cap + 1, per whole unit: the byte behind its final block
+  // the batch of whole members
+  uint64_t *w_in_off;      // n_b + 1
+  uint64_t *w_in_end;      // n_b
+  uint64_t *w_out_off;     // n_b + 1
+  uint64_t *w_size;        // n_b
+  uint32_t *w_unit;        // n_b
+};
+__global__ void gzfile_serial_ranges_kernel(GzSerialParams S);
+__global__ void gzfile_serial_nodes_kernel(GzSerialParams S);
+__global__ void gzfile_serial_round_kernel(const uint32_t *src, uint32_t *dst, uint32_t n);
+__global__ void gzfile_serial_from_kernel(GzSerialParams S, const uint32_t *jump);
+__global__ void gzfile_serial_base_kernel(uint64_t *cand_off, uint32_t n, uint64_t base_bits);
+__global__ void gzfile_serial_bits_kernel(GzFileParams P, GzSerialParams S);
+__global__ void gzfile_serial_keep_kernel(GzFileParams P, GzSerialParams S);
+__global__ void gzfile_serial_marks_kernel(GzFileParams P, GzSerialParams S);
+__global__ void gzfile_serial_list_kernel(GzFileParams P, GzSerialParams S);
+__global__ void gzfile_serial_check_kernel(GzSerialParams S, uint32_t n_whole, const int32_t *d_status,
+                                           const uint64_t *d_out_len, OneDecHead *dh);
+
 // The seek index of a gzip FILE (gzfile_seek_kernels.hip; flate_hip_gzfile_seek_index / _ranges; the rule and the
 // index's layout: gzfile_seek_rule.h).  Locate, select, layout, compose, resolve, check, TAIL and the gather are the
 // kernels above, unchanged: they see the file's units as the units of one stream.

@@ -409,7 +409,8 @@ class GzFileCalls:
     def gzfile_read(self, data, out=None, out_cap=None):
         """A gzip file of any members back into its bytes by one call, what zcat gives (flate_hip_gzfile_read): every
         member cut into units that are decoded in parallel, every member's CRC-32 and ISIZE checked on the GPU.  For
-        files of many small members gzip_read is faster; for exactly one member inflate_one is the same work.  Returns
+        files of many small members gzip_read is faster -- or set_option("gzfile_serial_max", 1 << 20), which decodes
+        short members whole here (gzfile_last_route); for exactly one member inflate_one is the same work.  Returns
         (out, GzFileRead(rc, out_len, n_members, n_units, n_candidates, status, bad_member, err_off, stream_err_off));
         the bytes are out[:out_len] (numpy for host data, a torch CUDA tensor for device data).  status 0; a chain
         that breaks: gzfile_index's words, the good members in front and the failing member's bytes in front of its
@@ -432,6 +433,22 @@ class GzFileCalls:
             return (q.out_len, None) if q.rc == E_OUT_TOO_SMALL else (0, q)
 
         return _read_into(out, data, out_cap, "gzfile_read", call, size)
+
+
+class GzFileSerialCalls:
+    """gzfile_index / gzfile_read with the option "gzfile_serial_max": the method FlateEngine inherits.  It stands in a
+    class of its own so that its marshalling has its own recorded scenarios (tests/engine_trace_gzfile_serial.py) beside
+    the ones of the methods that were there before."""
+
+    def gzfile_last_route(self):
+        """What the last gzfile_index or gzfile_read on this engine did with the option "gzfile_serial_max"
+        (flate_hip_gzfile_last_route): (serial_members, unit_members, find_from) -- the discovery's good members that
+        were taken WHOLE (one unit each, decoded by the batch decoders), its other good members (cut into units), and
+        the file offset the bit-offset search started at: len(data) = no search ran; 0 with the option at 0.  Bytes and
+        verdicts are identical by design, so this is how to see which path ran."""
+        sm, um, ff = C.c_uint32(0), C.c_uint32(0), C.c_uint64(0)
+        self._check(self._L.flate_hip_gzfile_last_route(self._ctx, C.byref(sm), C.byref(um), C.byref(ff)))
+        return int(sm.value), int(um.value), int(ff.value)
 
 
 class GzFileSeekCalls:
@@ -527,7 +544,7 @@ class ZipUnitsCalls:
         return tuple(int(x.value) for x in w)
 
 
-class FlateEngine(OneSeekCalls, GzFileCalls, GzFileSeekCalls, ZipUnitsCalls):
+class FlateEngine(OneSeekCalls, GzFileCalls, GzFileSerialCalls, GzFileSeekCalls, ZipUnitsCalls):
     """One engine = one flate_hip_ctx = one GPU + one HIP stream."""
 
     def __init__(self, device=0):

@@ -77,6 +77,17 @@ class Engine {
     (void)flate_hip_zip_last_route(ctx_, &r.unit_entries, &r.fallback_entries, &r.n_units, &r.n_candidates);
     return r;
   }
+  // ... or ("gzfile_serial_max", 1 << 20) so that flate_hip_gzfile_index / _read take short members whole
+  // flate_hip_gzfile_last_route: what the last index_gzfile / decompress_gzfile on this engine did with it
+  struct GzFileRoute {
+    uint32_t serial_members = 0, unit_members = 0;
+    uint64_t find_from = 0;
+  };
+  GzFileRoute gzfile_last_route() const {
+    GzFileRoute r;
+    (void)flate_hip_gzfile_last_route(ctx_, &r.serial_members, &r.unit_members, &r.find_from);
+    return r;
+  }
 
  private:
   flate_hip_ctx *ctx_ = nullptr;
