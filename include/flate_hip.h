@@ -127,6 +127,9 @@ int flate_hip_set_stream(flate_hip_ctx *ctx, void *hip_stream);
  *                        default 1 GiB, read when the stream is opened; results never change
  *   "zip_unit_min"       flate_hip_zip_read: 0 (default) = every entry goes to the batch decoders; v >= 1 = a deflated
  *                        entry of at least v compressed bytes is decoded through units (ZIP archives, below)
+ *   "zip_piece_bytes"    flate_hip_zip_write: 0 (default) = every entry is one stream, written by one wavefront; P >= 1
+ *                        = an entry longer than P bytes is written from ceil(len / P) pieces compressed in parallel
+ *                        and spliced into one stream (ZIP archives, below)
  *   "gzfile_serial_max"  flate_hip_gzfile_index / _read only: 0 (default) = every member is cut into units; S >= 1
  *                        (at most 2^28 - 1, like "gzip_member_max") = a member whose header and raw stream fit in
  *                        S bytes and decode cleanly is ONE unit, decoded whole by the batch decoders.  Bytes,
@@ -434,6 +437,35 @@ int flate_hip_deflate_fast_batch_framed(flate_hip_ctx *ctx, const uint8_t *in, c
 int flate_hip_deflate_fast_spliced_framed(flate_hip_ctx *ctx, const uint8_t *in, const uint64_t *in_off,
                                           uint32_t n_streams, uint32_t wrap, uint8_t *out, uint64_t out_cap,
                                           uint64_t *out_len, uint64_t *bit_off, uint32_t flags);
+
+/* GROUPED SPLICE: several spliced members in one call, so that a batch in which some members are long is written by
+ * as many wavefronts as it has pieces.  The n_pieces pieces in[in_off[i], in_off[i+1]) are compressed independently;
+ * group g = the pieces [group_off[g], group_off[g+1]) becomes member g = out[out_off[g], out_off[g+1]): header |
+ * exactly the bytes flate_hip_deflate_fast_spliced produces for the pieces of group g under the same flags | trailer
+ * over the group's (contiguous) input; FLATE_HIP_WRAP_RAW: the bare stream.  Members lie back to back; out_off
+ * (n_groups + 1 entries, HOST) is never optional.
+ *   group_off (HOST, n_groups + 1 entries): group_off[0] == 0, group_off[n_groups] == n_pieces, strictly increasing --
+ *     every group has at least one piece; an empty member is one piece of zero bytes.  Anything else, an unknown wrap
+ *     or flag, or a missing pointer: FLATE_HIP_E_INVALID before any HIP call.
+ *   bit_off (HOST, n_pieces + n_groups entries, may be NULL): group g's index is
+ *     bit_off[group_off[g] + g .. group_off[g+1] + g], n_g + 1 entries counted from the first byte of the member's raw
+ *     stream: what flate_hip_deflate_fast_spliced_framed returns, so flate_hip_inflate_spliced_framed takes a member
+ *     and its slice as they are.
+ *   out_cap: the exact total is enough for ZLIB and GZIP; FLATE_HIP_WRAP_RAW needs the total + 3, as the unframed
+ *     spliced call (the pack kernel stores whole dwords).  Too little: FLATE_HIP_E_OUT_TOO_SMALL, decided on the
+ *     device, nothing written.
+ *   flags: FLATE_HIP_DEVICE_PTRS (in and out), FLATE_HIP_COMPAT_GO.  Host pointers: one copy in, one copy out, no
+ *     "host_pipeline_groups".  n_groups == 0: out_off[0] = 0, FLATE_HIP_OK.
+ *   How: the positions of pieces inside a spliced stream compose as maps x -> x + a / x -> align8(x + a) + b; the end
+ *     of a member -- closing block, trailer, next header -- is one more map of that form (csrc/splice_rule.h), so one
+ *     scan places every piece of every member, the pack kernel writes a closing block at every group's end, and one
+ *     thread per group writes header and trailer last.  Stage accounting: the framed calls'.
+ *   Out of scope: dictionaries, BGZF, grouping across ranks, pieces that share history, and choosing the piece size
+ *     per member.  (ZIP entries in pieces: the option "zip_piece_bytes" of flate_hip_zip_write.) */
+int flate_hip_deflate_fast_grouped_framed(flate_hip_ctx *ctx, const uint8_t *in, const uint64_t *in_off,
+                                          uint32_t n_pieces, const uint32_t *group_off, uint32_t n_groups,
+                                          uint32_t wrap, uint8_t *out, uint64_t out_cap, uint64_t *out_off,
+                                          uint64_t *bit_off, uint32_t flags);
 
 /* READING members: flate_hip_inflate_batch -- its output slots, out_len, status, return value (the first non-zero
  * status), FLATE_HIP_DEVICE_PTRS, options and size limits -- for n_streams zlib or gzip members, member i =
@@ -1231,6 +1263,20 @@ int flate_hip_gzfile_ranges(flate_hip_ctx *ctx, const uint8_t *in, uint64_t in_l
  *   copies, the checksums and the verdict as before.  Stages: discovery is counted in no stage, as in
  *   flate_hip_gzfile_read; FLATE_HIP_STAGE_INFLATE is the batch launch, or the last round's decoder launch when no
  *   entry is left for the batch decoders.  No kernel waits for another workgroup.
+ * WRITING LONG ENTRIES: the option "zip_piece_bytes".  flate_hip_zip_write gives an entry one wavefront, the wrong shape
+ * for an .npz of one large array.  With "zip_piece_bytes" = P >= 1 (0, the default: off) an entry longer than P bytes is
+ * cut into ceil(len / P) pieces of P bytes, the last one shorter (zip_pieces_plan, csrc/splice_rule.h); the pieces of
+ * an entry are one group of a grouped splice (flate_hip_deflate_fast_grouped_framed, above), so the entry's data is ONE
+ * legal DEFLATE stream -- exactly what flate_hip_deflate_fast_spliced writes for those pieces -- and its sizes and
+ * CRC-32 in the local header and the central record are the entry's own: an ordinary ZIP archive.  Entries of at most P
+ * bytes are groups of one piece and their bytes are what they are with the option off.  When no entry is longer than P
+ * the call takes the route of the option at 0: the same kernels, no new launch, no new allocation, the same bytes.
+ * Everything the call refuses with the option off it refuses with it on; more than 2^32 - 2 pieces, or an entry whose
+ * stream reaches 4 GiB: FLATE_HIP_E_TOO_LARGE.  Pieces share no history, so the archive grows as P shrinks (at P =
+ * 65535 a piece is one window of the plain stream with its own first block).  flate_hip_zip_bound does not know P: it
+ * covers every P >= 65535; below that add flate_hip_deflate_bound(0) per piece beyond the first of each entry (the
+ * room is judged on the device either way: too little is FLATE_HIP_E_OUT_TOO_SMALL, nothing written).  Which path ran:
+ * flate_hip_zip_write_last_route.  Out of scope: choosing P per entry, pieces that share history.
  * Out of scope: archives with prepended data, several disks, encryption, methods other than 0 and 8, comments on
  * write; uploading only the selected entries from host memory; caching the index across calls; entries of 4 GiB or
  * more through units; a seek index for entries; independent chains per entry. */
@@ -1281,6 +1327,11 @@ int flate_hip_zip_read(flate_hip_ctx *ctx, const uint8_t *in, uint64_t in_len, c
  * nothing.  Results are identical by design: this is how a caller sees which path ran.  No HIP call. */
 int flate_hip_zip_last_route(const flate_hip_ctx *ctx, uint32_t *unit_entries, uint32_t *fallback_entries,
                              uint32_t *n_units, uint32_t *n_candidates);
+
+/* What the last flate_hip_zip_write on this ctx did with the option "zip_piece_bytes": *long_entries = the entries
+ * written from more than one piece, *n_pieces = the pieces of the whole call.  Both zero on the unchanged route (the
+ * option at 0, or no entry longer than it) and after a call that failed.  No HIP call. */
+int flate_hip_zip_write_last_route(const flate_hip_ctx *ctx, uint32_t *long_entries, uint32_t *n_pieces);
 
 /* -- exchange step (multi-GPU) ---------------------------------------------------
  * SURVEY 8(e) / section 5; no counterpart in the reference (single-threaded, no communication

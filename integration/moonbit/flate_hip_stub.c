@@ -149,3 +149,12 @@ int flate_hip_mbt_zip_last_route(const flate_hip_ctx *c, int64_t *res) {
   for (int k = 0; k < 4; ++k) res[k] = w[k];
   return rc;
 }
+
+/* -- the write side's route query (the option "zip_piece_bytes"): res[0] = long_entries, res[1] = n_pieces.
+ * (flate_hip_deflate_fast_grouped_framed takes its optional index as an array and is bound by the .mbt file directly.) -- */
+int flate_hip_mbt_zip_write_last_route(const flate_hip_ctx *c, int64_t *res) {
+  uint32_t w[2] = {0, 0};
+  const int rc = flate_hip_zip_write_last_route(c, &w[0], &w[1]);
+  res[0] = w[0], res[1] = w[1];
+  return rc;
+}

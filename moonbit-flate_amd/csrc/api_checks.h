@@ -7,6 +7,7 @@
 #include "flate_hip.h"
 #include "gzfile_seek_rule.h"
 #include "seek_index_rule.h"
+#include "splice_rule.h"
 
 namespace flate {
 
@@ -37,6 +38,19 @@ inline bool deflate_batch_ptrs_ok(const uint8_t *in, const uint64_t *in_off, uin
 inline bool deflate_spliced_ptrs_ok(const uint8_t *in, const uint64_t *in_off, uint32_t n, const uint8_t *out,
                                     const uint64_t *out_len) {
   return in_off && out && out_len && (!n || in);
+}
+
+// flate_hip_deflate_fast_grouped_framed: everything that is refused before any HIP call -- the spliced call's pointers
+// (out_off receives the members' index, so it is never optional), an unknown wrap or flag, the groups (grouped_args_ok,
+// splice_rule.h) and pieces that run backwards
+inline int deflate_grouped_args(const uint8_t *in, const uint64_t *in_off, uint32_t n_pieces, const uint32_t *group_off,
+                                uint32_t n_groups, uint32_t wrap, const uint8_t *out, const uint64_t *out_off, uint32_t flags) {
+  if (!in_off || !out_off || !group_off || (n_pieces && !in) || (n_groups && !out)) return FLATE_HIP_E_INVALID;
+  if (wrap > FLATE_HIP_WRAP_GZIP || (flags & ~(FLATE_HIP_DEVICE_PTRS | FLATE_HIP_COMPAT_GO))) return FLATE_HIP_E_INVALID;
+  if (!grouped_args_ok(group_off, n_groups, n_pieces)) return FLATE_HIP_E_INVALID;
+  for (uint32_t i = 0; i < n_pieces; ++i)
+    if (in_off[i + 1] < in_off[i]) return FLATE_HIP_E_INVALID;
+  return FLATE_HIP_OK;
 }
 
 // The dictionary table of a call (flate_hip_inflate_batch_framed needs no more: its members choose by DICTID) ...
@@ -294,6 +308,9 @@ inline int zip_read_args(const uint8_t *in, uint64_t in_len, const uint32_t *sel
 // the option "zip_unit_min": 0 (the default) = every entry goes to the batch decoders; v >= 1 = a deflated entry of
 // at least v compressed bytes is decoded through units (zip_units_rule.h)
 inline bool zip_unit_min_ok(int64_t value) { return value >= 0; }
+// the option "zip_piece_bytes": 0 (the default) = every entry is one stream; P >= 1 = an entry longer than P bytes is
+// written from pieces of P bytes (zip_pieces_plan, splice_rule.h)
+inline bool zip_piece_bytes_ok(int64_t value) { return value >= 0; }
 // how many candidates the directory's discovery arrays hold on the first attempt: the records the end record promises
 // and some decoys (names or extras that look like records); never more than fit the directory, 4 bytes apart
 inline uint32_t zip_first_cap(uint64_t n, uint64_t cd_size) {

@@ -98,7 +98,8 @@ struct EncodeRoute {
   bool pair16, pair32, pairD;
 };
 
-inline EncodeRoute encode_route(const StagePlan &pl, const EncodeOpts &o, uint32_t flags, bool spliced) {
+// grouped: the streams are the pieces of several spliced streams (splice_rule.h) -- as for spliced.
+inline EncodeRoute encode_route(const StagePlan &pl, const EncodeOpts &o, uint32_t flags, bool spliced, bool grouped = false) {
   const uint32_t n = pl.n_streams;
   EncodeRoute r{};
   // One wavefront per block in the histogram and pack kernels when the streams have many blocks
@@ -107,7 +108,7 @@ inline EncodeRoute encode_route(const StagePlan &pl, const EncodeOpts &o, uint32
   // its closing block in that form).  Not for spliced output: where a block starts then depends on
   // the bit its stream starts at (a stored block pads to a byte of the SPLICED stream), which only the
   // stream's own walk knows.
-  r.per_block = o.entropy_per_block != 0 && pl.n_blocks > 0 && !spliced &&
+  r.per_block = o.entropy_per_block != 0 && pl.n_blocks > 0 && !spliced && !grouped &&
                 (o.entropy_per_block == 1 || (uint64_t)pl.n_blocks >= 3ull * n);
   for (uint32_t i = 0; i < n && r.per_block; ++i) r.per_block = pl.blk_base[i + 1] > pl.blk_base[i];
   const bool serial = (flags & FLATE_HIP_LZ_SERIAL) != 0;
@@ -160,5 +161,8 @@ inline size_t entropy_ctl_up(const StagePlan &pl) { return ((size_t)pl.n_streams
 inline size_t frame_before_ctl_up(uint32_t n, size_t dictid_up) { return (size_t)n * 4 + 256 + dictid_up; }
 // read back: the output index (the status words and the spliced total fit the 64)
 inline size_t encode_ctl_down(uint32_t n) { return ((size_t)n + 1) * 8 + 64; }
+// a grouped call: group_off and every piece's group go up; the members' offsets and the groups' bit indexes come back
+inline size_t grouped_ctl_up(uint32_t n_pieces, uint32_t n_groups) { return ((size_t)n_pieces + n_groups + 1) * 4 + 1024; }
+inline size_t grouped_ctl_down(uint32_t n_pieces, uint32_t n_groups) { return ((size_t)n_pieces + 2 * (size_t)n_groups + 1) * 8 + 1024; }
 
 }  // namespace flate

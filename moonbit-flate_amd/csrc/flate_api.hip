@@ -377,6 +377,8 @@ int flate_hip_set_option(flate_hip_ctx *c, const char *name, int64_t value) {
     c->one_round_units = (uint32_t)value;
   } else if (k == "zip_unit_min" && zip_unit_min_ok(value)) {
     c->zip_unit_min = (uint64_t)value;
+  } else if (k == "zip_piece_bytes" && zip_piece_bytes_ok(value)) {
+    c->zip_piece_bytes = (uint64_t)value;
   } else if (k == "gzfile_serial_max" && gzfile_serial_max_ok(value)) {
     c->gzfile_serial_max = (uint64_t)value;
   } else {
@@ -439,6 +441,12 @@ int flate_hip_zip_last_route(const flate_hip_ctx *c, uint32_t *unit_entries, uin
   if (!c || !unit_entries || !fallback_entries || !n_units || !n_candidates) return FLATE_HIP_E_INVALID;
   *unit_entries = c->zip_route[0], *fallback_entries = c->zip_route[1];
   *n_units = c->zip_route[2], *n_candidates = c->zip_route[3];
+  return FLATE_HIP_OK;
+}
+
+int flate_hip_zip_write_last_route(const flate_hip_ctx *c, uint32_t *long_entries, uint32_t *n_pieces) {
+  if (!c || !long_entries || !n_pieces) return FLATE_HIP_E_INVALID;
+  *long_entries = c->zip_write_route[0], *n_pieces = c->zip_write_route[1];
   return FLATE_HIP_OK;
 }
 

@@ -17,6 +17,7 @@
 
 #include "api_checks.h"
 #include "bgzf_rule.h"
+#include "zip_rule.h"
 
 using namespace flate;
 using namespace flate_host;
@@ -36,6 +37,12 @@ struct EncCall {
   uint64_t *total_bytes;
   uint32_t flags;
   bool spliced;
+  // grouped (flate_hip_deflate_fast_grouped_framed; it implies spliced): the n streams are the pieces of n_groups
+  // spliced streams, group g = pieces [group_off[g], group_off[g + 1]); out_off then receives the MEMBERS' offsets
+  // (n_groups + 1) and bit_idx (may be null) the groups' bit indexes (n + n_groups).  All three are HOST arrays.
+  const uint32_t *group_off = nullptr;
+  uint32_t n_groups = 0;
+  uint64_t *bit_idx = nullptr;
 };
 
 // The preset dictionaries of an encode call (flate_hip_deflate_fast_batch_dict), already on the device.
@@ -333,8 +340,9 @@ int blk_sid_up(flate_hip_ctx *c, const StagePlan &pl) {
 // that places the streams (a raw batch, a batch of members -- F, null for raw output -- or one spliced stream), pack.
 // place_cap: the room the scan may give out.
 // ZW (flate_hip_zip_write): the members of a ZIP archive, placed by zip_scan_kernel.
+// GP (a grouped call): several spliced streams, placed by group_scan_kernel.
 void launch_entropy(flate_hip_ctx *c, const EncodeRoute &rt, const HuffParams &H, uint32_t n_blocks, const FrameParams *F,
-                    uint64_t place_cap, const ZipWriteParams *ZW = nullptr) {
+                    uint64_t place_cap, const ZipWriteParams *ZW = nullptr, const GroupParams *GP = nullptr) {
   const uint32_t n = H.n_streams;
   StageTimer t(c, FLATE_HIP_STAGE_HUFF_PACK);
   if (rt.per_block)
@@ -342,7 +350,11 @@ void launch_entropy(flate_hip_ctx *c, const EncodeRoute &rt, const HuffParams &H
   else
     hipLaunchKernelGGL(huff_hist_kernel, dim3(n), dim3(64), 0, c->stream, H);
   hipLaunchKernelGGL(huff_code_kernel, dim3(n), dim3(64), 0, c->stream, H);
-  if (H.spliced) {
+  if (GP) {
+    hipLaunchKernelGGL(group_scan_kernel, dim3(1), dim3(1024), 0, c->stream, *GP);
+    hipLaunchKernelGGL(group_zero_kernel, dim3((uint32_t)(((uint64_t)n + GP->n_groups) / 256 + 1)), dim3(256), 0, c->stream, *GP,
+                       H.out);
+  } else if (H.spliced) {
     SpliceParams S{};
     S.sum = (const uint64_t *)c->d_slot_off.p;
     S.stream_bit = (uint64_t *)c->d_out_off.p;
@@ -369,7 +381,7 @@ void launch_entropy(flate_hip_ctx *c, const EncodeRoute &rt, const HuffParams &H
     hipLaunchKernelGGL(huff_zero_edges_kernel, dim3(n_blocks / 256 + 1), dim3(256), 0, c->stream, H, n_blocks);
     hipLaunchKernelGGL(huff_pack_block_kernel, dim3(n_blocks), dim3(64), 0, c->stream, H);
   } else {
-    hipLaunchKernelGGL(huff_pack_kernel, dim3(n), dim3(64), 0, c->stream, H);
+    hipLaunchKernelGGL(GP ? huff_pack_grouped_kernel : huff_pack_kernel, dim3(n), dim3(64), 0, c->stream, H);
   }
 }
 
@@ -434,6 +446,28 @@ int frame_after(flate_hip_ctx *c, const FrameReq &FR, const FrameParams &F, cons
   return FLATE_HIP_OK;
 }
 
+// A grouped call's members: the checksums of the groups' input, then group_frame_write_kernel.
+int group_frame_after(flate_hip_ctx *c, const FrameReq &FR, const GroupParams &GP, uint8_t *d_out, const uint8_t *d_in,
+                      const uint64_t *sum_off, uint32_t sum_n) {
+  StageTimer t(c, FLATE_HIP_STAGE_CHECKSUM);
+  const int rc = checksum_device(c, d_in, sum_off, sum_n, frame_sum_kind(FR.wrap), (uint32_t *)c->d_frame_sums.p, -1);
+  if (rc) return rc;
+  GroupFrameParams G{};
+  G.member_off = GP.member_off;
+  G.payload_off = GP.payload_off;
+  G.end_bit = GP.end_bit;
+  G.group_off = GP.group_off;
+  G.in_off = (const uint64_t *)c->d_in_off.p;
+  G.sums = (const uint32_t *)c->d_frame_sums.p;
+  G.out = d_out;
+  G.out_cap = GP.out_cap;
+  G.n_groups = sum_n;
+  G.wrap = FR.wrap;
+  G.status = GP.status;
+  hipLaunchKernelGGL(group_frame_write_kernel, dim3(sum_n / 256 + 1), dim3(256), 0, c->stream, G);
+  return FLATE_HIP_OK;
+}
+
 // ---- the container of flate_hip_zip_write (zip_kernels.hip) ----
 // The members of a ZIP archive: zip_scan_kernel places them (30 + name in front of every raw stream), the pack kernels
 // write each raw stream into its member, then the CRC-32s run on the input where it is and zip_write_kernel writes the
@@ -460,18 +494,20 @@ int zip_before(flate_hip_ctx *c, const ZipReq &ZR, uint32_t n) {
   return FLATE_HIP_OK;
 }
 
-ZipWriteParams zip_params(const flate_hip_ctx *c, const EncCall &A, uint8_t *d_out) {
+// GP (entries written in pieces): the entries are its groups, placed by group_scan_kernel
+ZipWriteParams zip_params(const flate_hip_ctx *c, const EncCall &A, uint8_t *d_out, const GroupParams *GP) {
   ZipWriteParams Z{};
-  Z.out_len = (const uint64_t *)c->d_out_len.p;
+  Z.out_len = GP ? nullptr : (const uint64_t *)c->d_out_len.p;
   Z.in_off = (const uint64_t *)c->d_in_off.p;
   Z.name_off = (const uint64_t *)c->d_zip_name_off.p;
   Z.names = (const uint8_t *)c->d_zip_names.p;
   Z.entry_off = (uint64_t *)c->d_frame_off.p;
-  Z.payload_off = (uint64_t *)c->d_out_off.p;
+  Z.payload_off = GP ? GP->payload_off : (uint64_t *)c->d_out_off.p;
+  Z.group_off = GP ? GP->group_off : nullptr;
   Z.sums = (const uint32_t *)c->d_frame_sums.p;
   Z.out = d_out;
   Z.out_cap = A.out_cap;
-  Z.n = A.n;
+  Z.n = GP ? GP->n_groups : A.n;
   Z.status = (int *)c->d_status.p;
   Z.head = (ZipWriteHead *)c->d_zip_whead.p;
   return Z;
@@ -505,21 +541,36 @@ int deflate_common(flate_hip_ctx *c, const EncCall &A, const DeflDict *DD = null
     planned = &made;
   }
   const StagePlan &pl = *planned;
-  const EncodeRoute route = encode_route(pl, c->enc, A.flags, A.spliced);
+  const bool grouped = A.group_off != nullptr;
+  const uint32_t n_groups = A.n_groups;
+  const EncodeRoute route = encode_route(pl, c->enc, A.flags, A.spliced, grouped);
   const uint64_t in_bytes = A.in_off[n];
   // a spliced member's fixed header and trailer; what the checksum kernels sum: the streams, or the one stream
   const uint32_t f_hl = FR ? frame_header_len(FR->wrap, false) : 0u;
   const uint32_t f_tl = FR ? frame_trailer_len(FR->wrap) : 0u;
   const uint64_t whole[2] = {A.in_off[0], A.in_off[n]};
-  const uint64_t *sum_off = A.spliced ? whole : A.in_off;
-  const uint32_t sum_n = A.spliced ? 1u : n;
-  if (FR && A.spliced && A.out_cap < (uint64_t)f_hl + f_tl) return FLATE_HIP_E_OUT_TOO_SMALL;
+  // (grouped: every group's input is contiguous; and every piece's group, for the kernels)
+  std::vector<uint64_t> group_in;
+  std::vector<uint32_t> piece_group;
+  if (grouped) {
+    group_in.resize((size_t)n_groups + 1);
+    piece_group.resize(n);
+    for (uint32_t g = 0; g < n_groups; ++g) {
+      group_in[g] = A.in_off[A.group_off[g]];
+      for (uint32_t i = A.group_off[g]; i < A.group_off[g + 1]; ++i) piece_group[i] = g;
+    }
+    group_in[n_groups] = A.in_off[n];
+  }
+  const uint64_t *sum_off = grouped ? group_in.data() : A.spliced ? whole : A.in_off;
+  const uint32_t sum_n = grouped ? n_groups : A.spliced ? 1u : n;
+  if (FR && A.spliced && !grouped && A.out_cap < (uint64_t)f_hl + f_tl) return FLATE_HIP_E_OUT_TOO_SMALL;
   CtlBytes ctl{lz77_ctl_up(pl) + entropy_ctl_up(pl), encode_ctl_down(n)};
   if (FR) {
     ctl += frame_before_ctl(*FR, n);
     ctl += frame_after_ctl(sum_off, sum_n);
   }
   if (ZR) ctl += zip_ctl(sum_off, sum_n);
+  if (grouped) ctl += CtlBytes{grouped_ctl_up(n, n_groups) + (ZR ? (size_t)n_groups * 4 : 0), grouped_ctl_down(n, n_groups)};
   if ((rc = ctl_begin(c, ctl.up, ctl.down))) return rc;
 
   // stage the input
@@ -541,7 +592,45 @@ int deflate_common(flate_hip_ctx *c, const EncCall &A, const DeflDict *DD = null
 
   // the container in front of the match finder
   if (FR && (rc = frame_before(c, *FR, n, sum_off, sum_n, A.flags))) return rc;
-  if (ZR && (rc = zip_before(c, *ZR, n))) return rc;
+  if (ZR && (rc = zip_before(c, *ZR, grouped ? n_groups : n))) return rc;
+  GroupParams GP{};
+  if (grouped) {
+    uint32_t *d_group_off = nullptr, *d_piece_group = nullptr, *d_header_len = nullptr;
+    if ((rc = carve(c, c->d_group, [&](Carve &k) {
+           k.take(d_group_off, (size_t)n_groups + 1);
+           k.take(d_piece_group, n);
+           k.take(d_header_len, ZR ? n_groups : 0u);
+           k.take(GP.end_bit, n_groups);
+           k.take(GP.payload_off, n_groups);
+           k.take(GP.bit_idx, (size_t)n + n_groups);
+         })))
+      return rc;
+    if ((rc = ensure(c, c->d_frame_off, ((size_t)n + 1) * 8))) return rc;
+    if ((rc = ctl_up(c, d_group_off, A.group_off, ((size_t)n_groups + 1) * 4))) return rc;
+    if ((rc = ctl_up(c, d_piece_group, piece_group.data(), (size_t)n * 4))) return rc;
+    if (!A.bit_idx) GP.bit_idx = nullptr;
+    if (ZR) {  // an entry's header: 30 + its name
+      std::vector<uint32_t> header_len(n_groups);
+      for (uint32_t g = 0; g < n_groups; ++g) header_len[g] = kZipLocalLen + (uint32_t)(ZR->name_off[g + 1] - ZR->name_off[g]);
+      if ((rc = ctl_up(c, d_header_len, header_len.data(), (size_t)n_groups * 4))) return rc;
+      GP.header_len = d_header_len;
+      GP.zip_head = (ZipWriteHead *)c->d_zip_whead.p;
+      GP.zip_name_off = (const uint64_t *)c->d_zip_name_off.p;
+    }
+    GP.sum = (const uint64_t *)c->d_slot_off.p;
+    GP.group_off = d_group_off;
+    GP.piece_group = d_piece_group;
+    GP.header_len_all = f_hl;
+    GP.trailer_len = f_tl;
+    GP.stream_bit = (uint64_t *)c->d_out_off.p;
+    GP.member_off = (uint64_t *)c->d_frame_off.p;
+    GP.total_bytes = (uint64_t *)c->d_out_len.p + n;  // (d_out_len has n + 1 slots)
+    GP.out_cap = A.out_cap;
+    GP.slack = FR || ZR ? 0u : 3u;  // (a trailer or the directory behind the last closing block takes the pack kernel's last dword)
+    GP.status = (int *)c->d_status.p;
+    GP.n_pieces = n;
+    GP.n_groups = n_groups;
+  }
 
   // the match finder
   HIP_TRY(c, hipMemsetAsync(c->d_status.p, 0, 8, c->stream));  // (word 1: frame_scan_kernel's first oversized BGZF member)
@@ -554,29 +643,36 @@ int deflate_common(flate_hip_ctx *c, const EncCall &A, const DeflDict *DD = null
   H.in_off = (const uint64_t *)c->d_in_off.p;
   H.chunk_base = (const uint32_t *)c->d_chunk_base.p;
   H.blk_base = (const uint32_t *)c->d_blk_base.p;
-  H.out = d_out + (A.spliced ? f_hl : 0u);  // (batch members: the header lengths are in the offsets, frame_scan_kernel)
+  // (batch members: the header lengths are in the offsets, frame_scan_kernel; grouped: in the bit positions)
+  H.out = d_out + (A.spliced && !grouped ? f_hl : 0u);
+  H.piece_group = GP.piece_group;
+  H.group_end_bit = GP.end_bit;
   H.n_streams = n;
   H.blk_sid = route.per_block ? (const uint32_t *)c->d_blk_sid.p : nullptr;
   FrameParams F{};
-  if (FR) F = frame_params(c, *FR, A, d_out, whole[1] - whole[0]);
+  if (FR && !grouped) F = frame_params(c, *FR, A, d_out, whole[1] - whole[0]);
   // (a spliced member: header + stream + trailer <= out_cap is enough -- the 3 bytes the pack kernel's last dword may
   // reach past the stream lie in the trailer, which is written after it)
   ZipWriteParams ZW{};
-  if (ZR) ZW = zip_params(c, A, d_out);
-  launch_entropy(c, route, H, pl.n_blocks, FR ? &F : nullptr, FR && A.spliced ? A.out_cap - f_hl - f_tl + 3 : A.out_cap,
-                 ZR ? &ZW : nullptr);
+  if (ZR) ZW = zip_params(c, A, d_out, grouped ? &GP : nullptr);
+  launch_entropy(c, route, H, pl.n_blocks, FR && !grouped ? &F : nullptr,
+                 FR && A.spliced ? A.out_cap - f_hl - f_tl + 3 : A.out_cap, ZR ? &ZW : nullptr, grouped ? &GP : nullptr);
   HIP_TRY(c, hipGetLastError());
 
   // the container behind it
-  if (FR && (rc = frame_after(c, *FR, F, d_in, sum_off, sum_n))) return rc;
+  if (FR && !grouped && (rc = frame_after(c, *FR, F, d_in, sum_off, sum_n))) return rc;
+  if (FR && grouped && (rc = group_frame_after(c, *FR, GP, d_out, d_in, sum_off, sum_n))) return rc;
   if (ZR && (rc = zip_after(c, ZW, d_in, sum_off, sum_n))) return rc;
   HIP_TRY(c, hipGetLastError());
 
   // read back
   uint64_t *out_off = A.out_off;
-  if (out_off && (rc = ctl_down(c, out_off, ((FR && !A.spliced) || ZR) ? c->d_frame_off.p : c->d_out_off.p, ((size_t)n + 1) * 8)))
+  if (grouped) {
+    if ((rc = ctl_down(c, out_off, GP.member_off, ((size_t)n_groups + 1) * 8))) return rc;
+    if (A.bit_idx && (rc = ctl_down(c, A.bit_idx, GP.bit_idx, ((size_t)n + n_groups) * 8))) return rc;
+  } else if (out_off && (rc = ctl_down(c, out_off, ((FR && !A.spliced) || ZR) ? c->d_frame_off.p : c->d_out_off.p, ((size_t)n + 1) * 8)))
     return rc;
-  if (A.spliced && (rc = ctl_down(c, &c->h_total_bytes, (uint64_t *)c->d_out_len.p + n, 8))) return rc;
+  if (A.spliced && !ZR && (rc = ctl_down(c, &c->h_total_bytes, (uint64_t *)c->d_out_len.p + n, 8))) return rc;
   if (ZR && (rc = ctl_down(c, &c->h_total_bytes, &ZW.head->total, 8))) return rc;
   if ((rc = ctl_down(c, &c->h_status_word, c->d_status.p, 4))) return rc;
   const bool bgzf = FR && FR->wrap == kWrapBgzf;
@@ -588,8 +684,8 @@ int deflate_common(flate_hip_ctx *c, const EncCall &A, const DeflDict *DD = null
     c->hip_err = "BGZF: block " + std::to_string((uint32_t)c->h_status_aux) + " compresses to a member of more than 65536 bytes";
   if (c->h_status_word) return encoder_status(c, c->h_status_word);
   // (a BGZF file: the members, then the EOF marker frame_write_kernel has put behind them)
-  const uint64_t produced = ZR          ? c->h_total_bytes
-                            : A.spliced ? c->h_total_bytes + f_hl + f_tl
+  const uint64_t produced = ZR || grouped ? c->h_total_bytes
+                            : A.spliced  ? c->h_total_bytes + f_hl + f_tl
                                         : out_off[n] + (bgzf ? (uint64_t)kBgzfEofLen : 0ull);
   if (A.total_bytes) *A.total_bytes = produced;
   if (!dev) {
@@ -1199,6 +1295,33 @@ int flate_hip_deflate_fast_spliced_framed(flate_hip_ctx *c, const uint8_t *in, c
   }
 }
 
+int flate_hip_deflate_fast_grouped_framed(flate_hip_ctx *c, const uint8_t *in, const uint64_t *in_off, uint32_t n_pieces,
+                                          const uint32_t *group_off, uint32_t n_groups, uint32_t wrap, uint8_t *out,
+                                          uint64_t out_cap, uint64_t *out_off, uint64_t *bit_off, uint32_t flags) {
+  // every check before any HIP call
+  if (!c) return FLATE_HIP_E_INVALID;
+  const int bad = deflate_grouped_args(in, in_off, n_pieces, group_off, n_groups, wrap, out, out_off, flags);
+  if (bad) return bad;
+  c->hip_err.clear();
+  if (n_groups == 0) {
+    out_off[0] = 0;
+    return FLATE_HIP_OK;
+  }
+  try {
+    // (host pointers: one copy in -- the checksums run on it --, compress, one copy out)
+    EncCall A{in, in_off, n_pieces, out, out_cap, out_off, nullptr, flags, true};
+    A.group_off = group_off;
+    A.n_groups = n_groups;
+    A.bit_idx = bit_off;
+    if (wrap == FLATE_HIP_WRAP_RAW) return deflate_common(c, A);
+    const FrameReq FR{wrap, nullptr, nullptr, nullptr, 0};
+    return deflate_common(c, A, nullptr, &FR);
+  } catch (const std::exception &e) {  // (out of host memory in an index vector)
+    c->hip_err = e.what();
+    return FLATE_HIP_E_INTERNAL;
+  }
+}
+
 // ---- BGZF files (the writing half; reading: flate_api_inflate.hip) ----
 
 size_t flate_hip_bgzf_bound(uint64_t in_len, uint32_t block_bytes) {
@@ -1239,6 +1362,23 @@ int flate_hip_bgzf_write(flate_hip_ctx *c, const uint8_t *in, uint64_t in_len, u
 }  // extern "C"
 
 // ---- ZIP archives (the writing half; the entry point and the reading half: flate_api_zip.hip) ----
+// with the option "zip_piece_bytes" and at least one long entry: the entries as the groups of a grouped call
+int flate_host::zip_deflate_pieces(flate_hip_ctx *c, const uint8_t *in, const uint64_t *piece_in_off, uint32_t n_pieces,
+                                   const uint32_t *group_off, uint32_t n, const uint8_t *names, const uint64_t *name_off,
+                                   uint8_t *out, uint64_t out_cap, uint64_t *out_len, uint64_t *entry_off, uint32_t flags) {
+  try {
+    std::vector<uint64_t> index((size_t)n + 1);
+    const ZipReq ZR{names, name_off};
+    EncCall A{in, piece_in_off, n_pieces, out, out_cap, entry_off ? entry_off : index.data(), out_len, flags, true};
+    A.group_off = group_off;
+    A.n_groups = n;
+    return deflate_common(c, A, nullptr, nullptr, nullptr, &ZR);
+  } catch (const std::exception &e) {  // (out of host memory in an index vector)
+    c->hip_err = e.what();
+    return FLATE_HIP_E_INTERNAL;
+  }
+}
+
 int flate_host::zip_deflate(flate_hip_ctx *c, const uint8_t *in, const uint64_t *in_off, uint32_t n, const uint8_t *names,
                             const uint64_t *name_off, uint8_t *out, uint64_t out_cap, uint64_t *out_len, uint64_t *entry_off,
                             uint32_t flags) {

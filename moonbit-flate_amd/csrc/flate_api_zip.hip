@@ -125,6 +125,7 @@ int flate_hip_zip_write(flate_hip_ctx *c, const uint8_t *in, const uint64_t *in_
   if (rc) return rc;
   c->hip_err.clear();
   *out_len = 0;
+  c->zip_write_route[0] = c->zip_write_route[1] = 0;
   if (n == 0) {  // the empty archive: the end record alone
     uint8_t end[kZipEndLen];
     (void)zip_put_end(end, 0, 0, 0);
@@ -139,6 +140,29 @@ int flate_hip_zip_write(flate_hip_ctx *c, const uint8_t *in, const uint64_t *in_
     if (entry_off) entry_off[0] = 0;
     *out_len = kZipEndLen;
     return FLATE_HIP_OK;
+  }
+  // the option "zip_piece_bytes": with at least one entry longer than P the entries are the groups of a grouped call;
+  // otherwise today's route -- the same kernels, no new launch, no new allocation
+  if (c->zip_piece_bytes) {
+    uint32_t long_entries = 0;
+    const uint64_t pieces = zip_pieces_count(in_off, n, c->zip_piece_bytes, &long_entries);
+    if (long_entries) {
+      if (pieces > 0xfffffffeull) return FLATE_HIP_E_TOO_LARGE;
+      for (uint32_t i = 0; i < n; ++i)  // (what the plain route refuses: an entry's sizes are 32-bit fields)
+        if (in_off[i + 1] - in_off[i] >= 0x7ffe0000ull) return FLATE_HIP_E_TOO_LARGE;
+      try {
+        std::vector<uint64_t> piece_in_off((size_t)pieces + 1);
+        std::vector<uint32_t> group_off((size_t)n + 1);
+        zip_pieces_plan(in_off, n, c->zip_piece_bytes, piece_in_off.data(), group_off.data());
+        const int r = zip_deflate_pieces(c, in, piece_in_off.data(), (uint32_t)pieces, group_off.data(), n, names, name_off, out,
+                                         out_cap, out_len, entry_off, flags);
+        if (r == FLATE_HIP_OK) c->zip_write_route[0] = long_entries, c->zip_write_route[1] = (uint32_t)pieces;
+        return r;
+      } catch (const std::exception &e) {  // (out of host memory in an index vector)
+        c->hip_err = e.what();
+        return FLATE_HIP_E_INTERNAL;
+      }
+    }
   }
   return zip_deflate(c, in, in_off, n, names, name_off, out, out_cap, out_len, entry_off, flags);
 }

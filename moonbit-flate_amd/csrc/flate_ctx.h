@@ -61,6 +61,9 @@ struct flate_hip_ctx {
   // the *_framed calls: member offsets, the streams' checksums, per stream its dictionary, the dictionaries' Adler-32
   // (DICTIDs) and, for host callers, the whole dictionaries
   DevBuf d_frame_off, d_frame_sums, d_frame_dict_of, d_frame_ids, d_frame_dicts;
+  // flate_hip_deflate_fast_grouped_framed (it shares d_frame_off: the members' offsets, d_frame_sums: the groups' sums):
+  // group_off, every piece's group, the groups' ends and payload starts, the bit indexes (GroupParams), carved from one buffer
+  DevBuf d_group;
   // flate_hip_inflate_batch_framed (it shares d_frame_off: the raw streams' starts, d_frame_sums, d_frame_ids,
   // d_frame_dicts): the raw streams' ends, the trailers' sums and ISIZEs, the header verdicts, the chosen dictionaries,
   // and per dictionary where its staged tail lies and how long it is
@@ -116,6 +119,11 @@ struct flate_hip_ctx {
   uint64_t zip_unit_min = 0;
   DevBuf d_zip_units_tiles, d_zip_units, d_zip_units_dec;
   uint32_t zip_route[4] = {0, 0, 0, 0};  // unit entries, fallback entries, units, candidates
+  // flate_hip_zip_write with the option "zip_piece_bytes" (0 = off, the default: the same kernels, no new launch, no new
+  // allocation): an entry longer than that many bytes is written from pieces, as one group of a grouped call; and what
+  // the last write did (flate_hip_zip_write_last_route)
+  uint64_t zip_piece_bytes = 0;
+  uint32_t zip_write_route[2] = {0, 0};  // long entries, pieces
   hipStream_t guest_stream = nullptr;
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
   int32_t h_status_word = 0;  // landing pads of small async D2H copies

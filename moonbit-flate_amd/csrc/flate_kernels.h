@@ -125,6 +125,11 @@ struct HuffParams {
   const uint32_t *blk_sid;  // per-block launches (huff_*_block_kernel): stream of every block, else null
   uint32_t no_close;  // spliced mode: the batch's last stream does not write Writer::close's block
                       // (a stream that continues in a later call: flate_hip_stream_write)
+  // grouped mode (huff_pack_grouped_kernel only; splice_rule.h): the streams are the pieces of SEVERAL spliced streams.
+  // Piece i belongs to group piece_group[i]; the last piece of group g ends at bit group_end_bit[g] and writes the
+  // group's closing block.  NULL otherwise.
+  const uint32_t *piece_group;
+  const uint64_t *group_end_bit;
 };
 
 struct CompactParams {
@@ -252,6 +257,57 @@ struct SpliceParams {
 };
 __global__ void splice_scan_kernel(SpliceParams P);
 __global__ void splice_zero_kernel(SpliceParams P, uint8_t *out);
+
+// grouped splice (splice_kernels.hip, splice_rule.h; flate_hip_deflate_fast_grouped_framed): SEVERAL spliced streams
+// in one output, group g = the pieces [group_off[g], group_off[g + 1]) inside header_len bytes in front and
+// trailer_len bytes behind.  Every position is absolute: bits (bytes) counted from out[0].
+struct ZipWriteHead;  // (zip_kernels.h)
+struct GroupParams {
+  const uint64_t *sum;          // per piece {a, b} written by huff_code_kernel
+  const uint32_t *group_off;    // n_groups + 1
+  const uint32_t *piece_group;  // per piece: its group
+  const uint32_t *header_len;   // per group; null: header_len_all for every group
+  uint32_t header_len_all;
+  uint32_t trailer_len;
+  uint64_t *stream_bit;         // n_pieces + 1: piece i's first block (entry n_pieces: 8 * total)
+  uint64_t *end_bit;            // per group: where its last piece ends and its closing block starts
+  uint64_t *payload_off;        // per group: the first byte of its raw stream
+  uint64_t *member_off;         // n_groups + 1: payload_off[g] - header length; entry n_groups: the total
+  uint64_t *bit_idx;            // n_pieces + n_groups, or null: group g's index at [group_off[g] + g, group_off[g + 1] + g],
+                                // counted from the first byte of its raw stream
+  uint64_t *total_bytes;
+  uint64_t out_cap;
+  uint32_t slack;               // bytes behind the total that must fit as well (3 where nothing follows the last
+                                // closing block: the pack kernel stores whole dwords)
+  int *status;                  // -2 if total + slack > out_cap
+  uint32_t n_pieces, n_groups;
+  // the members of a ZIP archive (flate_hip_zip_write with "zip_piece_bytes"; header_len[g] = 30 + name length): the
+  // scan also produces zip_scan_kernel's result words -- k0, the directory's place and size, the archive's total, which
+  // is then what is judged against out_cap -- and refuses a raw stream of 2^32 bytes or more (FLATE_HIP_E_TOO_LARGE).
+  // zip_name_off: n_groups + 1, DEVICE.  NULL otherwise.
+  ZipWriteHead *zip_head;
+  const uint64_t *zip_name_off;
+};
+__global__ void group_scan_kernel(GroupParams P);
+__global__ void group_zero_kernel(GroupParams P, uint8_t *out);
+// huff_pack_kernel over the pieces of a grouped call (HuffParams::piece_group)
+__global__ void huff_pack_grouped_kernel(HuffParams P);
+
+// headers and trailers of the groups' members, one thread per group, behind the pack kernel (frame_kernels.hip)
+struct GroupFrameParams {
+  const uint64_t *member_off;   // n_groups + 1 (group_scan_kernel)
+  const uint64_t *payload_off;  // per group
+  const uint64_t *end_bit;      // per group
+  const uint32_t *group_off;    // n_groups + 1
+  const uint64_t *in_off;       // n_pieces + 1: the pieces' input (gzip: ISIZE of the group's contiguous input)
+  const uint32_t *sums;         // per group: the checksum of its input
+  uint8_t *out;
+  uint64_t out_cap;
+  uint32_t n_groups;
+  uint32_t wrap;                // FLATE_HIP_WRAP_ZLIB / _GZIP
+  const int *status;
+};
+__global__ void group_frame_write_kernel(GroupFrameParams P);
 
 // Containers around the raw streams (frame_kernels.hip; flate_hip_deflate_fast_*_framed): member i of a batch is
 // header | raw stream i | trailer, the members back to back.  wrap = FLATE_HIP_WRAP_ZLIB: two header bytes, or six

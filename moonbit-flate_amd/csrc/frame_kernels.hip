@@ -125,6 +125,31 @@ __global__ __launch_bounds__(256) void frame_write_kernel(FrameParams P) {
   }
 }
 
+// The members of a grouped call (flate_hip_deflate_fast_grouped_framed; group_scan_kernel has placed them): member g's
+// raw stream is spliced from the pieces of group g, whose input is contiguous.  The same bytes as above, no dictionaries.
+__global__ __launch_bounds__(256) void group_frame_write_kernel(GroupFrameParams P) {
+  const uint32_t g = blockIdx.x * 256u + threadIdx.x;
+  if (g >= P.n_groups || *P.status != 0) return;
+  const uint32_t tl = frame_trailer_len(P.wrap);
+  // the raw stream ends behind its closing block: 3 bits, padding, LEN, NLEN
+  const uint64_t raw_end = (((P.end_bit[g] + 3 + 7) & ~7ull) + 32) >> 3;
+  if (raw_end + tl > P.out_cap) return;  // (never: the scan kernel has checked the total)
+  const uint64_t in_len = P.in_off[P.group_off[g + 1]] - P.in_off[P.group_off[g]];
+  uint8_t *h = P.out + P.member_off[g];
+  uint8_t *t = P.out + raw_end;
+  const uint32_t sum = P.sums[g];
+  if (P.wrap == FLATE_HIP_WRAP_GZIP) {
+    h[0] = 0x1f, h[1] = 0x8b, h[2] = 8, h[3] = 0;
+    h[4] = h[5] = h[6] = h[7] = 0;
+    h[8] = 4, h[9] = 255;
+    put_le32(t, sum);
+    put_le32(t + 4, (uint32_t)in_len);
+  } else {
+    h[0] = 0x78, h[1] = 0x01;
+    put_be32(t, sum);
+  }
+}
+
 // ---- reading members (flate_hip_inflate_batch_framed) ----
 
 namespace {

@@ -1168,9 +1168,12 @@ FLATE_D void pack_block(const HuffParams &P, SharedPack &sh, BitSink &S, const B
 #ifndef FLATE_HUFF_PACK_SGPR
 #define FLATE_HUFF_PACK_SGPR 80
 #endif
-__attribute__((amdgpu_num_sgpr(FLATE_HUFF_PACK_SGPR), amdgpu_waves_per_eu(8, 8)))
-__global__ __launch_bounds__(64) void huff_pack_kernel(HuffParams P) {
-  __shared__ SharedPack sh;
+// GROUPED (huff_pack_grouped_kernel): the streams are the pieces of several spliced streams (splice_rule.h); "the last
+// stream" is then every piece that is the last of its group.  A template flag, not a uniform branch: the kernel sits
+// at the 64 vector and 80 scalar registers that eight wavefronts allow, and the batch and spliced instantiation must
+// keep exactly the code it has.
+template <bool GROUPED>
+FLATE_D void huff_pack_stream(const HuffParams &P, SharedPack &sh) {
   const int lane = threadIdx.x;
   const uint32_t sid = blockIdx.x;
   if (sid >= P.n_streams || *P.status != 0) return;
@@ -1183,6 +1186,7 @@ __global__ __launch_bounds__(64) void huff_pack_kernel(HuffParams P) {
   S.flushed = 0;
   S.or_first = S.or_last = P.spliced != 0;
   uint64_t out_bits;  // what this stream must write
+  bool closes = true;  // ... the closing block included
   if (!P.spliced) {
     uint8_t *dst = P.out + P.out_off[sid];
     const uint64_t out_bytes = P.out_len[sid];
@@ -1201,7 +1205,13 @@ __global__ __launch_bounds__(64) void huff_pack_kernel(HuffParams P) {
     const uint64_t mis = (uint64_t)((uintptr_t)P.out & 3u);
     const uint64_t g0 = P.stream_bit[sid] + 8 * mis;  // relative to the aligned dword grid of out
     uint64_t g1 = P.stream_bit[sid + 1] + 8 * mis;
-    const bool last_stream = sid + 1 == P.n_streams && !P.no_close;
+    bool last_stream = sid + 1 == P.n_streams && !P.no_close;
+    if constexpr (GROUPED) {
+      const uint32_t grp = P.piece_group[sid];
+      last_stream = sid + 1 == P.n_streams || P.piece_group[sid + 1] != grp;
+      if (last_stream) g1 = P.group_end_bit[grp] + 8 * mis;  // (stream_bit[sid + 1] lies behind trailer and header)
+    }
+    closes = last_stream;
     if (last_stream) g1 = ((g1 + 3 + 7) & ~7ull) + 32;  // + closing block
     out_bits = g1 - g0;
     S.head = 0;
@@ -1213,11 +1223,22 @@ __global__ __launch_bounds__(64) void huff_pack_kernel(HuffParams P) {
   const uint64_t bit0 = S.bitpos;
 
   for (uint32_t b = 0; b < g.nblocks; ++b) pack_block(P, sh, S, g, b, lane);
-  if (!P.spliced || (sid + 1 == P.n_streams && !P.no_close))
-    emit_stored(S, g.stream, 0, true, lane);  // Compressor::close (deflate.mbt:171-176)
+  if (closes) emit_stored(S, g.stream, 0, true, lane);  // Compressor::close (deflate.mbt:171-176)
   sink_finish(S, lane);
   // the sizes computed by huff_code_kernel and the bits actually written must agree
   if (lane == 0 && S.bitpos - bit0 != out_bits) atomicExch(P.status, -(int)(0x100000u + (sid & 0xfffffu)));  // E_INTERNAL + stream
+}
+
+__attribute__((amdgpu_num_sgpr(FLATE_HUFF_PACK_SGPR), amdgpu_waves_per_eu(8, 8)))
+__global__ __launch_bounds__(64) void huff_pack_kernel(HuffParams P) {
+  __shared__ SharedPack sh;
+  huff_pack_stream<false>(P, sh);
+}
+
+__attribute__((amdgpu_num_sgpr(FLATE_HUFF_PACK_SGPR), amdgpu_waves_per_eu(8, 8)))
+__global__ __launch_bounds__(64) void huff_pack_grouped_kernel(HuffParams P) {
+  __shared__ SharedPack sh;
+  huff_pack_stream<true>(P, sh);
 }
 
 // ---------------------------------------------------------------------------------------

@@ -30,6 +30,10 @@ struct ZipWriteParams {
   uint32_t n;
   int *status;               // scan_sizes_kernel's status word
   ZipWriteHead *head;
+  // entries written in pieces (the option "zip_piece_bytes"; group_scan_kernel has placed them): entry i is the pieces
+  // [group_off[i], group_off[i + 1]) of in_off, its raw size the next entry's start minus its own payload start, and
+  // out_len is not read.  NULL: every entry is one stream.
+  const uint32_t *group_off;
 };
 
 // ---- reading: the end record ----
@@ -163,6 +167,11 @@ namespace flate_host {
 int zip_deflate(flate_hip_ctx *c, const uint8_t *in, const uint64_t *in_off, uint32_t n, const uint8_t *names,
                 const uint64_t *name_off, uint8_t *out, uint64_t out_cap, uint64_t *out_len, uint64_t *entry_off,
                 uint32_t flags);
+// the same for entries written in pieces ("zip_piece_bytes"): entry i = the pieces [group_off[i], group_off[i + 1]) of
+// piece_in_off (zip_pieces_plan, splice_rule.h)
+int zip_deflate_pieces(flate_hip_ctx *c, const uint8_t *in, const uint64_t *piece_in_off, uint32_t n_pieces,
+                       const uint32_t *group_off, uint32_t n, const uint8_t *names, const uint64_t *name_off, uint8_t *out,
+                       uint64_t out_cap, uint64_t *out_len, uint64_t *entry_off, uint32_t flags);
 // flate_api_inflate.hip: the batch decoders over raw streams that are not consecutive in DEVICE memory: stream i =
 // d_in[in_off[i], in_end[i]) into d_out[out_off[i], out_off[i + 1]).  The results reach the host arrays and stay in the
 // ctx's d_out_len / d_istatus / d_ierr.  Returns FLATE_HIP_OK or the first non-zero stream status.

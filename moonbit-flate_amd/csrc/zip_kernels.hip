@@ -75,7 +75,13 @@ __global__ __launch_bounds__(256) void zip_write_kernel(ZipWriteParams P) {
   const uint64_t at = P.entry_off[i];
   const uint32_t nl = (uint32_t)(P.name_off[i + 1] - P.name_off[i]);
   const uint8_t *name = P.names + P.name_off[i];
-  const uint32_t raw = (uint32_t)P.out_len[i], size = (uint32_t)(P.in_off[i + 1] - P.in_off[i]);
+  uint32_t raw, size;
+  if (P.group_off) {
+    raw = (uint32_t)(P.entry_off[i + 1] - P.payload_off[i]);
+    size = (uint32_t)(P.in_off[P.group_off[i + 1]] - P.in_off[P.group_off[i]]);
+  } else {
+    raw = (uint32_t)P.out_len[i], size = (uint32_t)(P.in_off[i + 1] - P.in_off[i]);
+  }
   zip_put_local(P.out + at, name, nl, P.sums[i], raw, size);
   zip_put_central(P.out + h.cd_off + zip_central_place(i, P.name_off[i] - P.name_off[0], h.k0), name, nl, P.sums[i], raw, size, at);
 }

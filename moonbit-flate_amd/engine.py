@@ -544,7 +544,46 @@ class ZipUnitsCalls:
         return tuple(int(x.value) for x in w)
 
 
-class FlateEngine(OneSeekCalls, GzFileCalls, GzFileSerialCalls, GzFileSeekCalls, ZipUnitsCalls):
+class GroupedCalls:
+    """Grouped splice: the method FlateEngine inherits.  It stands in a class of its own so that its marshalling has its
+    own recorded scenarios (tests/engine_trace_grouped.py) beside the ones of the methods that were there before."""
+
+    def deflate_grouped_framed(self, data, in_off, group_off, wrap, compat_go=False, out=None, out_cap=None, index=False):
+        """Several spliced members in one call (flate_hip_deflate_fast_grouped_framed): the pieces
+        data[in_off[i]:in_off[i+1]] are compressed on their own, in parallel; group g = the pieces
+        group_off[g] .. group_off[g+1] - 1 becomes ONE zlib stream, gzip member or ("raw") bare DEFLATE stream, what
+        deflate_spliced_framed writes for those pieces, and the members lie back to back.  group_off starts at 0, ends
+        at the number of pieces and is strictly increasing (an empty member is one piece of zero bytes).
+        data: numpy uint8 (host; returns (exactly the members' bytes, out_off[n_groups+1])) or a torch uint8 CUDA tensor
+        (returns (out tensor, out_off as numpy)).  index=True adds bit_off, numpy uint64[n_pieces + n_groups]: group g's
+        index is bit_off[group_off[g] + g : group_off[g+1] + g + 1], counted from the first byte of the member's raw
+        stream -- inflate_spliced_framed takes a member and this slice as they are."""
+        in_off, n = _offsets(in_off)
+        group_off = np.ascontiguousarray(group_off, dtype=np.uint32)
+        n_groups = group_off.size - 1
+        w = _wrap_code(wrap)
+        data, in_ptr, _, device = _in_buf(data)
+        if out_cap is None and out is None:
+            out_cap = _deflate_room(in_off) + 16 + max(n_groups, 0) * (5 + frame_overhead(wrap))
+        out, out_ptr, cap = _out_buf(out, data, out_cap, out_cap, 0, "deflate_grouped_framed")
+        out_off = np.zeros(max(n_groups, 0) + 1, dtype=np.uint64)
+        bit_off = np.zeros(max(n + n_groups, 1), dtype=np.uint64)
+        self._check(self._L.flate_hip_deflate_fast_grouped_framed(
+            self._ctx, in_ptr, in_off.ctypes.data, n, group_off.ctypes.data, max(n_groups, 0), w, out_ptr, cap,
+            out_off.ctypes.data, bit_off.ctypes.data if index else None, self._flags(compat_go, False, device)))
+        res = (out if device else out[:int(out_off[-1])]), out_off
+        return res + (bit_off[:n + n_groups],) if index else res
+
+    def zip_write_last_route(self):
+        """What the last zip_write on this engine did with the option "zip_piece_bytes"
+        (flate_hip_zip_write_last_route): (long_entries, n_pieces) -- the entries written from more than one piece and
+        the pieces of the whole call.  (0, 0) on the unchanged route: the option at 0, or no entry longer than it."""
+        w = [C.c_uint32(0) for _ in range(2)]
+        self._check(self._L.flate_hip_zip_write_last_route(self._ctx, *[C.byref(x) for x in w]))
+        return tuple(int(x.value) for x in w)
+
+
+class FlateEngine(OneSeekCalls, GzFileCalls, GzFileSerialCalls, GzFileSeekCalls, ZipUnitsCalls, GroupedCalls):
     """One engine = one flate_hip_ctx = one GPU + one HIP stream."""
 
     def __init__(self, device=0):

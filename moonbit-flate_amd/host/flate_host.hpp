@@ -436,6 +436,46 @@ inline Err compress_spliced(Engine &e, const std::vector<std::vector<uint8_t>> &
   return std::nullopt;
 }
 
+// Several spliced members in one call (flate_hip_deflate_fast_grouped_framed): groups[g] is the list of pieces of member
+// g (at least one; an empty member is one empty piece), each compressed on its own and joined at bit granularity inside
+// the member's header and trailer (Wrap::Raw: the bare streams).  members[g] receives member g; bit_off (may be null)
+// receives per member its index, n_g + 1 entries counted from the raw stream's first byte: what
+// decompress_spliced(..., Wrap) takes with the member as it is.
+inline Err compress_grouped(Engine &e, const std::vector<std::vector<std::vector<uint8_t>>> &groups,
+                            std::vector<std::vector<uint8_t>> &members, Wrap wrap,
+                            std::vector<std::vector<uint64_t>> *bit_off = nullptr, uint32_t flags = 0) {
+  if (!e.ok()) return make_error(e, e.status());
+  const uint32_t n_groups = (uint32_t)groups.size();
+  const uint32_t w = wrap_code(wrap);
+  std::vector<uint32_t> group_off(n_groups + 1, 0);
+  std::vector<uint64_t> in_off(1, 0);
+  uint64_t cap = 16;
+  for (uint32_t g = 0; g < n_groups; ++g) {
+    for (const auto &p : groups[g]) {
+      in_off.push_back(in_off.back() + p.size());
+      cap += flate_hip_deflate_bound(p.size());
+    }
+    group_off[g + 1] = (uint32_t)(in_off.size() - 1);
+    cap += 5 + flate_hip_frame_overhead(w, 0);
+  }
+  const uint32_t n = (uint32_t)(in_off.size() - 1);
+  std::vector<uint8_t> in(in_off[n] + 1), buf(cap);
+  uint32_t i = 0;
+  for (const auto &grp : groups)
+    for (const auto &p : grp) std::copy(p.begin(), p.end(), in.begin() + in_off[i++]);
+  std::vector<uint64_t> out_off(n_groups + 1, 0), bo((size_t)n + n_groups + 1, 0);
+  const int rc = flate_hip_deflate_fast_grouped_framed(e.ctx(), in.data(), in_off.data(), n, group_off.data(), n_groups, w,
+                                                       buf.data(), cap, out_off.data(), bo.data(), flags);
+  if (rc != 0) return make_error(e, rc);
+  members.assign(n_groups, {});
+  if (bit_off) bit_off->assign(n_groups, {});
+  for (uint32_t g = 0; g < n_groups; ++g) {
+    members[g].assign(buf.begin() + out_off[g], buf.begin() + out_off[g + 1]);
+    if (bit_off) (*bit_off)[g].assign(bo.begin() + group_off[g] + g, bo.begin() + group_off[g + 1] + g + 1);
+  }
+  return std::nullopt;
+}
+
 // ---- decode side ---------------------------------------------------------------------------
 // pub let ioeof (inflate.mbt:19) and the errors of the Decompressor (inflate.mbt:38,780-785)
 inline const IOError &ioeof() {
