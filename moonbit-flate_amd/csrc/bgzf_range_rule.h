@@ -9,6 +9,8 @@
 
 #include <stdint.h>
 
+#include <vector>
+
 #include "bgzf_rule.h"
 
 namespace flate {
@@ -84,6 +86,22 @@ BGZF_HD BgzfRangeLoc bgzf_range_locate(uint32_t kind, uint64_t begin, uint64_t e
   r.first = bgzf_upper_bound(out_off, n + 1u, r.b) - 1u;
   r.last = bgzf_lower_bound(out_off, n + 1u, r.e) - 1u;
   return r;
+}
+
+// THE STATUS RULE of a ranges call, behind the decode (host only).  st[0 .. ns): the statuses of the decoded members or
+// units in file order; range r touches the decoded [r_lo[r], r_hi[r]).  A range takes the status of the first one it
+// touches that has one; a range that touches none (r_lo[r] == r_hi[r]), that lies outside the decoded ones, or that was
+// settled before the decode (skip != null and skip[r] != 0) keeps what it has.  range_status may be null.  Returns the
+// first decoded one with a status -- the call's verdict is its status -- or ns: there is none.
+inline uint32_t range_statuses(const int32_t *st, uint32_t ns, const uint32_t *r_lo, const uint32_t *r_hi, uint32_t nr,
+                               int32_t *range_status, const int32_t *skip) {
+  std::vector<uint32_t> nxt((size_t)ns + 1);  // nxt[i] = the first decoded one at or behind i with a status
+  nxt[ns] = ns;
+  for (uint32_t i = ns; i-- > 0;) nxt[i] = st[i] ? i : nxt[i + 1];
+  if (range_status)
+    for (uint32_t r = 0; r < nr; ++r)
+      if (!(skip && skip[r]) && r_lo[r] < r_hi[r] && r_hi[r] <= ns && nxt[r_lo[r]] < r_hi[r]) range_status[r] = st[nxt[r_lo[r]]];
+  return nxt[0];
 }
 
 }  // namespace flate

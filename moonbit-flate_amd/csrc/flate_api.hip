@@ -1,6 +1,6 @@
 // flate_api.hip -- C ABI of libflate_hip.so (see include/flate_hip.h): the ctx, its options and what the encode and
 // the decode calls share -- the scratch and the control-array staging, the host-pointer pipeline's copy threads, the
-// staging of preset dictionaries.  (The encode calls: flate_api_deflate.hip; the decode calls: flate_api_inflate.hip;
+// staging of preset dictionaries.  (The encode calls: flate_api_deflate.hip; the decode calls: flate_api_inflate.hip, flate_api_units.hip;
 // what crosses the file boundaries: flate_ctx.h.)
 #include "flate_ctx.h"
 

@@ -1,0 +1,1741 @@
+// flate_api_units.hip -- the decode calls of the C ABI that cut long DEFLATE data into parallel UNITS (see
+// include/flate_hip.h): flate_hip_inflate_one*, flate_hip_gzfile_* and the long entries of flate_hip_zip_read
+// (flate_host::zip_units_decode).  The batch calls, BGZF, plain gzip members and the piecewise stream are
+// flate_api_inflate.hip's; the decoders' launch (launch_decoders) is shared through flate_ctx.h.
+#include "flate_ctx.h"
+
+#include <cstring>
+#include <exception>
+#include <stdexcept>
+
+#include "api_checks.h"
+#include "bgzf_range_rule.h"
+#include "gzfile_rule.h"
+#include "gzip_rule.h"
+#include "unit_rounds.h"
+
+using namespace flate;
+using namespace flate_host;
+
+// ---- one long stream: block discovery (one_kernels.hip, one_probe_kernel.inc) ----
+namespace {
+
+// FIND's count pass or fill pass over n_tiles tiles, in the build of P's unit rule (option "one_stored_units")
+void one_find_launch(flate_hip_ctx *c, bool count, uint32_t n_tiles, const OneParams &P) {
+  if (count && P.stored_units)
+    hipLaunchKernelGGL(one_count_kernel<true>, dim3(n_tiles), dim3(256), 0, c->stream, P);
+  else if (count)
+    hipLaunchKernelGGL(one_count_kernel<false>, dim3(n_tiles), dim3(256), 0, c->stream, P);
+  else if (P.stored_units)
+    hipLaunchKernelGGL(one_fill_kernel<true>, dim3(n_tiles), dim3(256), 0, c->stream, P);
+  else
+    hipLaunchKernelGGL(one_fill_kernel<false>, dim3(n_tiles), dim3(256), 0, c->stream, P);
+}
+
+// PROBE over n_blocks candidates (or the one tail probe), in the build of the unit rule its parameters carry (TAIL:
+// one_tail_launch, unit_rounds.h)
+void one_probe_launch(flate_hip_ctx *c, uint32_t n_blocks, const OneParams &P, uint32_t tail) {
+  if (P.stored_units)
+    hipLaunchKernelGGL(one_probe_kernel<true>, dim3(n_blocks), dim3(64), 0, c->stream, P, tail);
+  else
+    hipLaunchKernelGGL(one_probe_kernel<false>, dim3(n_blocks), dim3(64), 0, c->stream, P, tail);
+}
+
+// The container around ONE stream as the device reads it: one_init_kernel leaves the raw stream's range {0, in_len} in
+// `one`, and for zlib / gzip frame_parse_kernel moves it behind the header and in front of the trailer, by the header
+// rules of flate_hip_inflate_spliced_framed (no dictionaries: FDICT is bad).
+void one_parse_launch(flate_hip_ctx *c, const uint8_t *d_in, uint64_t in_len, FrameOne *one, uint32_t wrap) {
+  hipLaunchKernelGGL(one_init_kernel, dim3(1), dim3(64), 0, c->stream, one, in_len);
+  if (wrap == FLATE_HIP_WRAP_RAW) return;
+  FrameReadParams R{};
+  R.in = d_in;
+  R.in_off = one->in_off;
+  R.n_streams = 1;
+  R.wrap = wrap;
+  R.pay_off = one->pay_off;
+  R.pay_end = &one->pay_end;
+  R.want = &one->want;
+  R.isize = &one->isize;
+  R.bad = &one->bad;
+  R.dict_used = &one->dict_used;
+  hipLaunchKernelGGL(frame_parse_kernel, dim3(1), dim3(256), 0, c->stream, R);
+}
+
+// The discovery over the ONE stream d_in[0, in_len) (DEVICE memory) on the ctx's stream: the container's header, count
+// and scan, ONE read-back of the candidate count (the launches behind it have a thread or a wavefront per candidate),
+// then fill, probe, link, rounds, finish, out-scan, the tail probe and ONE read-back of the result words H with the
+// index (P.C.member_off / P.C.out_off on the device; null when the header is bad).  Counted in no
+// profiling stage.
+// index_cap != 0: the first min(index_cap, candidates + 1) entries of unit_bit / out_off come back into `index` (the
+// two arrays one after the other) in the same read-back as H -- the units are a subset of the candidates, so what fits
+// the caller's arrays is known before the chain is.
+int one_discover(flate_hip_ctx *c, const uint8_t *d_in, uint64_t in_len, uint32_t wrap, uint64_t index_cap, OneHead &H,
+                 OneParams &P, std::vector<uint64_t> &index) {
+  int rc;
+  P = OneParams{};
+  ChainParams &C = P.C;
+  C.in = d_in;
+  C.in_len = in_len;
+  P.unit_max = c->one_unit_max;
+  P.stored_units = c->one_stored_units;
+  if ((rc = tiles_for(d_in, 0, in_len, &C.n_tiles))) return rc;
+  rc = carve(c, c->d_one_tiles, [&](Carve &k) {
+    k.take(P.head, 1);
+    k.take(P.one, 1);
+    k.take(C.tile_cnt, (size_t)C.n_tiles + 1);
+  });
+  if (rc) return rc;
+  C.head = &P.head->h;
+  one_parse_launch(c, d_in, in_len, P.one, wrap);
+  one_find_launch(c, true, C.n_tiles, P);
+  hipLaunchKernelGGL(chain_scan_kernel, dim3(1), dim3(1024), 0, c->stream, C);
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipMemcpyAsync(&H, P.head, sizeof H, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  const uint32_t cap = H.h.n_cand;
+  if ((rc = chain_size(C, cap))) return rc;  // (the count saturates at 2^32 - 1)
+  if (cap == 0) return FLATE_HIP_OK;  // (a bad header: the scan kernel has left FLATE_HIP_E_CORRUPT at offset 0)
+
+  const size_t n = cap;
+  rc = carve(c, c->d_one, [&](Carve &k) {
+    k.take(C.cand_off, n);
+    k.take(P.probe, n);
+    k.take(C.jump[0], n + 2);
+    k.take(C.jump[1], n + 2);
+    k.take(C.path, C.path_len);
+    k.take(P.usize, n);
+    k.take(C.member_off, n + 1);
+    k.take(C.out_off, n + 1);
+  });
+  if (rc) return rc;
+  one_find_launch(c, false, C.n_tiles, P);
+  one_probe_launch(c, cap, P, 0u);
+  if ((rc = chain_tail(c, C, one_link_kernel, P, one_finish_kernel, one_out_scan_kernel, P))) return rc;
+  one_probe_launch(c, 1, P, 1u);
+  HIP_TRY(c, hipGetLastError());
+  // ONE read-back behind the count: the result words, then 16 bytes per unit
+  const size_t take = (size_t)(index_cap < n + 1 ? index_cap : n + 1);
+  index.assign(2 * take, 0);
+  HIP_TRY(c, hipMemcpyAsync(&H, P.head, sizeof H, hipMemcpyDeviceToHost, c->stream));
+  if (take) {
+    HIP_TRY(c, hipMemcpyAsync(index.data(), P.C.member_off, take * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(index.data() + take, P.C.out_off, take * 8, hipMemcpyDeviceToHost, c->stream));
+  }
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return FLATE_HIP_OK;
+}
+
+// ---- what the two reads through a seek index share (flate_hip_inflate_one_ranges, flate_hip_gzfile_ranges) ----
+
+// c->d_one_dec for rounds over the ns selected units: per round the seeds, the pieces and what DECODE reports for
+// them, and per selected unit the status the check kernel folds
+int seek_rounds_carve(flate_hip_ctx *c, OneDecParams &D, OneSeekRoundParams &S, UnitResults &dec, uint32_t ns, uint32_t per_round) {
+  const int rc = unit_rounds_carve(c, D, ns, per_round, [&](Carve &k) {
+    k.take(S.seed, per_round);
+    k.take(S.p_bit_off, per_round);
+    k.take(S.p_bit_end, per_round);
+    k.take(D.p_dict_at, per_round);
+    k.take(D.p_dict_len, per_round);
+    dec.take(k, per_round);
+    k.take(S.u_status, ns);
+  });
+  if (rc) return rc;
+  S.p_dict_at = D.p_dict_at;  // (the kernels of the rounds read these through S)
+  S.p_dict_len = D.p_dict_len;
+  S.R = D.R;
+  S.d_status = dec.status;
+  S.d_out_len = dec.out_len;
+  return FLATE_HIP_OK;
+}
+// the workgroups of a load kernel: 16 of a round's 256-entry blocks each
+uint32_t seek_load_blocks(uint32_t count) {
+  return ((uint32_t)(((uint64_t)count * kWinEntries + 255) / 256) + 15u) / 16u;
+}
+
+// where a read through a seek index delivers, and the ranges' layout as the host has read it back
+struct SeekRangesOut {
+  uint8_t *out;
+  uint32_t nr;
+  uint64_t out_total, scratch_total;  // bytes of all ranges, of all decoded units
+  const uint32_t *r_lo, *r_hi;        // range r touches the selected units [r_lo[r], r_hi[r])
+  const uint32_t *sel;                // the selected units
+  int32_t *range_status;
+  uint32_t *bad_unit;
+  bool dev;
+};
+
+// The rounds over the ns selected units and what follows them: `seeds` (the caller's seed and load kernels, which set
+// S.i0 / S.count) in front of TAIL, the segmented scan, DECODE of the round's units as spliced pieces of in[0, in_len)
+// with dictionaries, each with its own end, into their dense slots, the per-unit check; then the gather of every
+// range's run of the scratch to its place in out, ONE read-back and the statuses.
+template <class Seeds>
+int seek_ranges_decode(flate_hip_ctx *c, OneDecParams &D, OneSeekRoundParams &S, const UnitResults &dec, uint32_t per_round,
+                       uint32_t ns, const uint8_t *in, uint64_t in_len, const SeekRangesOut &O, Seeds seeds) {
+  int rc;
+  if ((rc = ensure(c, c->d_one_seek_dense, O.scratch_total + 64))) return rc;
+  uint8_t *d_dense = (uint8_t *)c->d_one_seek_dense.p;
+  uint8_t *d_out = O.out;
+  if (!O.dev) {
+    if ((rc = ensure(c, c->d_out, O.out_total + 16))) return rc;
+    d_out = (uint8_t *)c->d_out.p;
+  }
+  auto decode = [&](uint32_t i0, uint32_t count) {
+    const int r = unit_decode(c, unit_decode_params(D, in, in_len, S.p_bit_off, S.p_bit_end, false, count, d_dense,
+                                                    S.Q.sel_at + i0, dec));
+    if (r) return r;
+    hipLaunchKernelGGL(one_seek_check_kernel, dim3((count + 255u) / 256u), dim3(256), 0, c->stream, S);
+    return FLATE_HIP_OK;
+  };
+  if ((rc = unit_rounds(c, D, nullptr, S.seed, 0, ns, ns, per_round, seeds, unit_no_hook, decode))) return rc;
+  if ((rc = ranges_gather(c, d_dense, d_out, S.Q.r_out_off, S.Q.r_src, O.nr, O.out_total))) return rc;
+  HIP_TRY(c, hipGetLastError());
+  std::vector<int32_t> st(ns);
+  HIP_TRY(c, hipMemcpyAsync(st.data(), S.u_status, (size_t)ns * 4, hipMemcpyDeviceToHost, c->stream));
+  if (!O.dev) HIP_TRY(c, hipMemcpyAsync(O.out, d_out, O.out_total, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  bool used[FLATE_HIP_STAGE_COUNT] = {false, false, false, false};
+  used[FLATE_HIP_STAGE_INFLATE] = true;
+  if (c->profiling && (rc = collect_timing(c, used))) return rc;
+  const uint32_t bad = range_statuses(st.data(), ns, O.r_lo, O.r_hi, O.nr, O.range_status, nullptr);
+  if (bad == ns) return FLATE_HIP_OK;
+  if (O.bad_unit) *O.bad_unit = O.sel[bad];
+  return st[bad];
+}
+
+}  // namespace
+
+extern "C" {
+
+int flate_hip_inflate_one_index(flate_hip_ctx *c, const uint8_t *in, uint64_t in_len, uint32_t wrap, uint64_t index_cap,
+                                uint64_t *unit_bit, uint64_t *out_off, uint32_t *n_units, uint64_t *out_bytes,
+                                uint32_t *n_candidates, int32_t *status, int64_t *err_off, uint32_t flags) {
+  // every check before any HIP call
+  if (!c) return FLATE_HIP_E_INVALID;
+  int rc = one_index_args(in, in_len, wrap, unit_bit, out_off, n_units, out_bytes, status, flags);
+  if (rc) return rc;
+  c->hip_err.clear();
+  *n_units = 0, *out_bytes = 0, *status = 0;
+  if (n_candidates) *n_candidates = 0;
+  if (err_off) *err_off = -1;
+  OneHead H{};
+  try {
+    OneParams P{};
+    std::vector<uint64_t> index;
+    if (in_len == 0) {  // no header at all, or a raw stream that ends in front of its first block header
+      H.h.rc = wrap == FLATE_HIP_WRAP_RAW ? FLATE_HIP_E_UNEXPECTED_EOF : FLATE_HIP_E_CORRUPT;
+      H.h.err_off = wrap == FLATE_HIP_WRAP_RAW ? -1 : 0;
+    } else {
+      const uint8_t *d_in = nullptr;
+      if ((rc = stage_input(c, in, in_len, flags, &d_in))) return rc;
+      if ((rc = one_discover(c, d_in, in_len, wrap, unit_bit ? index_cap : 0, H, P, index))) return rc;
+    }
+    *n_units = H.h.n_members;
+    if (n_candidates) *n_candidates = H.h.n_cand;
+    *status = H.h.rc;
+    if (err_off) *err_off = H.h.rc ? H.h.err_off : -1;
+    *out_bytes = H.h.out_bytes;  // (0 unless the chain reaches the final block)
+    // the index -- of a stream that fails its good prefix, if that fits: the verdict is the serial decoder's either way
+    const uint64_t entries = (uint64_t)H.h.n_members + 1;
+    if (unit_bit && index_cap >= entries) {
+      if (index.size() >= 2 * entries) {
+        memcpy(unit_bit, index.data(), entries * 8);
+        memcpy(out_off, index.data() + index.size() / 2, entries * 8);
+      } else {  // (a bad header or no input: zero units in front of offset 0)
+        unit_bit[0] = 0, out_off[0] = 0;
+      }
+    }
+    if (H.h.rc) return H.h.rc;
+    return unit_bit && index_cap < entries ? FLATE_HIP_E_OUT_TOO_SMALL : FLATE_HIP_OK;
+  } catch (const std::exception &e) {  // (out of host memory in the index vector)
+    c->hip_err = e.what();
+    return FLATE_HIP_E_INTERNAL;
+  }
+}
+
+// The whole call: discovery, then the units decoded in parallel in rounds of "one_round_units" -- TAIL (symbolic
+// windows), COMPOSE (a scan of the tail functions), DECODE (the units again, each with its resolved 32 KiB of history,
+// straight into out + out_off[k]) --, then the checksum of out[0, total) and the verdict.  Behind the discovery's two
+// read-backs the host reads nothing but the result words.
+int flate_hip_inflate_one(flate_hip_ctx *c, const uint8_t *in, uint64_t in_len, uint32_t wrap, uint8_t *out, uint64_t out_cap,
+                          uint64_t *out_len, int32_t *status, int64_t *err_off, uint32_t *n_units, uint32_t *n_candidates,
+                          uint32_t flags) {
+  // every check before any HIP call
+  if (!c) return FLATE_HIP_E_INVALID;
+  int rc = one_args(in, in_len, wrap, out, out_cap, out_len, status, flags);
+  if (rc) return rc;
+  c->hip_err.clear();
+  *out_len = 0, *status = 0;
+  if (err_off) *err_off = -1;
+  if (n_units) *n_units = 0;
+  if (n_candidates) *n_candidates = 0;
+  auto verdict = [&](int st, int64_t eo) {
+    *status = st;
+    if (err_off) *err_off = st ? eo : -1;
+    return st;
+  };
+  if (in_len == 0)
+    return wrap == FLATE_HIP_WRAP_RAW ? verdict(FLATE_HIP_E_UNEXPECTED_EOF, -1) : verdict(FLATE_HIP_E_CORRUPT, 0);
+  try {
+    const bool dev = (flags & FLATE_HIP_DEVICE_PTRS) != 0;
+    const uint8_t *d_in = nullptr;
+    if ((rc = stage_input(c, in, in_len, flags, &d_in))) return rc;
+    OneHead H{};
+    OneParams P{};
+    std::vector<uint64_t> none;
+    if ((rc = one_discover(c, d_in, in_len, wrap, 0, H, P, none))) return rc;
+    if (n_units) *n_units = H.h.n_members;
+    if (n_candidates) *n_candidates = H.h.n_cand;
+    if (H.h.n_cand == 0) return verdict(H.h.rc, H.h.err_off);  // a bad header
+    if (H.h.rc == FLATE_HIP_E_TOO_LARGE || H.h.rc == FLATE_HIP_E_INTERNAL) return verdict(H.h.rc, H.h.err_off);
+    // the units to decode: the good ones and, so that the bytes in front of an error are delivered, a unit that fails
+    // behind its header; the total is known here
+    const uint32_t n_dec = H.h.n_members + (H.fail_unit ? 1u : 0u);
+    const uint64_t total = H.prefix_bytes + (H.fail_unit ? H.fail_out : 0ull);
+    *out_len = total;
+    if (total > out_cap) return FLATE_HIP_E_OUT_TOO_SMALL;  // (nothing is decoded; out == NULL: the size query)
+    uint8_t *d_out = out;
+    if (!dev) {
+      if ((rc = ensure(c, c->d_out, total + 16))) return rc;
+      d_out = (uint8_t *)c->d_out.p;
+    }
+    const uint32_t per_round = unit_per_round(c, n_dec);
+    OneDecParams D{};
+    uint32_t *d_sum;
+    UnitResults dec;
+    rc = unit_rounds_carve(
+        c, D, n_dec, per_round, [&](Carve &k) { unit_pieces_take(k, D, &dec, per_round); },
+        [&](Carve &k) { k.take(d_sum, 4); });  // (the checksum's words stand in front of the function arrays)
+    if (rc) return rc;
+    if ((rc = unit_dec_params(c, D, d_in, P.one, P.C.member_off, P.C.out_off, P.stored_units, true))) return rc;
+    unit_verdict_params(D, total, dec, P.head, wrap, in_len);
+    // DECODE: the round's units as spliced pieces with dictionaries, through the lane-per-stream decoder.  The
+    // stream's last piece runs to BFINAL (or to its failure); every other round's last piece ends where the next
+    // unit starts, and so does the last unit of a chain that stopped at a header the decoder refuses.
+    auto decode = [&](uint32_t u0, uint32_t count) {
+      const uint32_t unit_blocks = (count + 1u + 255u) / 256u;
+      hipLaunchKernelGGL(one_pieces_kernel, dim3(unit_blocks), dim3(256), 0, c->stream, D);
+      const bool closed = u0 + count < n_dec || (H.h.rc != 0 && !H.fail_unit);
+      const int r = unit_decode(c, unit_decode_params(D, d_in + H.raw_off, H.raw_len, D.unit_bit + u0, nullptr, closed, count,
+                                                      d_out, D.p_out_off, dec));
+      if (r) return r;
+      hipLaunchKernelGGL(one_check_kernel, dim3(unit_blocks), dim3(256), 0, c->stream, D);
+      return FLATE_HIP_OK;
+    };
+    if ((rc = unit_rounds(c, D, nullptr, nullptr, 0, n_dec, n_dec, per_round, unit_no_hook, unit_no_hook, decode))) return rc;
+    bool used[FLATE_HIP_STAGE_COUNT] = {false, false, false, false};
+    used[FLATE_HIP_STAGE_INFLATE] = n_dec != 0;
+    bool ctl = false;
+    if (wrap != FLATE_HIP_WRAP_RAW && total) {
+      const uint64_t whole[2] = {0, total};
+      if ((rc = ctl_begin(c, checksum_ctl_up_bytes(whole, 1), 0))) return rc;
+      ctl = true;
+      D.sum = d_sum;
+      if ((rc = checksum_device(c, d_out, whole, 1, frame_sum_kind(wrap), d_sum, FLATE_HIP_STAGE_CHECKSUM)))
+        return rc;
+      used[FLATE_HIP_STAGE_CHECKSUM] = true;
+    }
+    hipLaunchKernelGGL(one_verdict_kernel, dim3(1), dim3(64), 0, c->stream, D);
+    HIP_TRY(c, hipGetLastError());
+    OneDecHead R{};
+    HIP_TRY(c, hipMemcpyAsync(&R, D.dh, sizeof R, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (ctl) ctl_finish(c);
+    if (R.out_len > total) return FLATE_HIP_E_INTERNAL;
+    *out_len = R.out_len;
+    if (!dev && R.out_len) {  // the result comes down once
+      HIP_TRY(c, hipMemcpyAsync(out, d_out, R.out_len, hipMemcpyDeviceToHost, c->stream));
+      HIP_TRY(c, hipStreamSynchronize(c->stream));
+    }
+    if (c->profiling && (rc = collect_timing(c, used))) return rc;
+    return verdict(R.status, R.err_off);
+  } catch (const std::exception &e) {
+    c->hip_err = e.what();
+    return FLATE_HIP_E_INTERNAL;
+  }
+}
+
+// The seek index: discovery, POINTS, then per round TAIL / COMPOSE / RESOLVE as above and, in DECODE's place, PACK: the
+// windows in front of the round's point units into their blocks.  Nothing is decoded to output.
+int flate_hip_inflate_one_seek_index(flate_hip_ctx *c, const uint8_t *in, uint64_t in_len, uint32_t wrap, uint64_t span,
+                                     uint64_t *index, uint64_t index_cap_words, uint64_t *index_words, uint8_t *windows,
+                                     uint64_t windows_cap, uint64_t *windows_bytes, uint32_t *n_units, uint32_t *n_points,
+                                     uint64_t *out_bytes, uint32_t *n_candidates, int32_t *status, int64_t *err_off,
+                                     uint32_t flags) {
+  // every check before any HIP call
+  if (!c) return FLATE_HIP_E_INVALID;
+  int rc = one_seek_index_args(in, in_len, wrap, index, index_cap_words, index_words, windows, windows_cap, windows_bytes,
+                               n_units, n_points, out_bytes, status, flags);
+  if (rc) return rc;
+  c->hip_err.clear();
+  *index_words = 0, *windows_bytes = 0, *n_units = 0, *n_points = 0, *out_bytes = 0, *status = 0;
+  if (n_candidates) *n_candidates = 0;
+  if (err_off) *err_off = -1;
+  auto verdict = [&](int st, int64_t eo) {  // a stream that fails gets no index
+    *status = st;
+    if (err_off) *err_off = st ? eo : -1;
+    if (st) *index_words = 0, *windows_bytes = 0, *n_points = 0, *out_bytes = 0;
+    return st;
+  };
+  if (in_len == 0)
+    return wrap == FLATE_HIP_WRAP_RAW ? verdict(FLATE_HIP_E_UNEXPECTED_EOF, -1) : verdict(FLATE_HIP_E_CORRUPT, 0);
+  span = seek_span(span);
+  try {
+    const bool dev = (flags & FLATE_HIP_DEVICE_PTRS) != 0;
+    const uint8_t *d_in = nullptr;
+    if ((rc = stage_input(c, in, in_len, flags, &d_in))) return rc;
+    OneHead H{};
+    OneParams P{};
+    std::vector<uint64_t> found;  // unit_bit, then out_off: one entry per candidate and one more, the units in front
+    if ((rc = one_discover(c, d_in, in_len, wrap, ~0ull, H, P, found))) return rc;
+    const uint32_t n = H.h.n_members;
+    *n_units = n;
+    if (n_candidates) *n_candidates = H.h.n_cand;
+    if (H.h.n_cand == 0) return verdict(H.h.rc, H.h.err_off);  // a bad header
+    if (H.h.rc == FLATE_HIP_E_TOO_LARGE || H.h.rc == FLATE_HIP_E_INTERNAL) return verdict(H.h.rc, H.h.err_off);
+    const bool sound = H.h.rc == 0;  // (a stream that fails is still walked: an earlier unit's distance may fail first)
+    const uint32_t n_dec = n + (H.fail_unit ? 1u : 0u);
+    const uint32_t per_round = unit_per_round(c, n_dec);
+
+    // POINTS: mark, scan, compact; the sizes are known here, in front of TAIL
+    OneSeekPointsParams PP{};
+    uint64_t *d_r_out_off, *d_r_src;
+    rc = carve(c, c->d_one_seek, [&](Carve &k) {
+      k.take(PP.n_points, 1);
+      k.take(PP.point_unit, (size_t)n + 1);
+      k.take(d_r_out_off, (size_t)per_round + 1);
+      k.take(d_r_src, per_round);
+    });
+    if (rc) return rc;
+    std::vector<uint64_t> points;
+    FrameOne one{};
+    uint32_t np = 0;
+    uint64_t need_words = 0, need_bytes = 0;
+    if (sound) {
+      PP.out_off = P.C.out_off;
+      PP.n = n;
+      PP.span = span;
+      hipLaunchKernelGGL(one_seek_points_kernel, dim3(1), dim3(1024), 0, c->stream, PP);
+      HIP_TRY(c, hipGetLastError());
+      points.assign(n, 0);
+      HIP_TRY(c, hipMemcpyAsync(&np, PP.n_points, 4, hipMemcpyDeviceToHost, c->stream));
+      HIP_TRY(c, hipMemcpyAsync(points.data(), PP.point_unit, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
+      HIP_TRY(c, hipMemcpyAsync(&one, P.one, sizeof one, hipMemcpyDeviceToHost, c->stream));
+      HIP_TRY(c, hipStreamSynchronize(c->stream));
+      if (np < 1u || np > n || found.size() < 2 * ((size_t)n + 1)) {
+        c->hip_err = "seek index: the point count does not fit the units";
+        return FLATE_HIP_E_INTERNAL;
+      }
+      need_words = seek_index_words(n, np);
+      need_bytes = seek_windows_bytes(np);
+      *index_words = need_words, *windows_bytes = need_bytes, *n_points = np, *out_bytes = H.h.out_bytes;
+      if (index_cap_words < need_words || windows_cap < need_bytes) return FLATE_HIP_E_OUT_TOO_SMALL;  // (the size query too)
+    }
+    uint8_t *d_windows = windows;
+    if (sound && !dev && need_bytes) {
+      if ((rc = ensure(c, c->d_one_seek_win, need_bytes + 16))) return rc;
+      d_windows = (uint8_t *)c->d_one_seek_win.p;
+    }
+
+    OneDecParams D{};
+    if ((rc = unit_rounds_carve(c, D, n_dec, per_round, [](Carve &) {}))) return rc;
+    if ((rc = unit_dec_params(c, D, d_in, P.one, P.C.member_off, P.C.out_off, P.stored_units, true))) return rc;
+    uint32_t p_next = 1;  // the first point whose window is not packed yet (point 0 has none)
+    // PACK: R[i] of the round's point units -> their blocks, which lie one behind the other in `windows`
+    auto pack = [&](uint32_t u0, uint32_t count) {
+      uint32_t p_hi = p_next;
+      while (p_hi < np && points[p_hi] < (uint64_t)u0 + count) ++p_hi;
+      if (p_hi == p_next) return FLATE_HIP_OK;
+      const uint32_t cnt = p_hi - p_next;
+      hipLaunchKernelGGL(one_seek_pack_kernel, dim3((cnt + 1u + 255u) / 256u), dim3(256), 0, c->stream, PP.point_unit, p_next,
+                         cnt, u0, d_r_out_off, d_r_src);
+      uint8_t *blocks = d_windows + (uint64_t)(p_next - 1u) * kSeekWindow;
+      p_next = p_hi;
+      return ranges_gather(c, D.R, blocks, d_r_out_off, d_r_src, cnt, (uint64_t)cnt * kSeekWindow);
+    };
+    if ((rc = unit_rounds(c, D, nullptr, nullptr, 0, n_dec, n_dec, per_round, unit_no_hook, unit_no_hook, pack))) return rc;
+    OneDecHead bad{};
+    if ((rc = unit_first_bad(c, D, n_dec, bad))) return rc;
+    // TAIL's verdict: the serial decoder's, at the serial offset
+    if (bad.first_bad != 0xffffffffu) return verdict(bad.status ? bad.status : FLATE_HIP_E_INTERNAL, bad.err_off);
+    if (!sound) return verdict(H.h.rc, H.h.err_off);
+    if (p_next != np) return FLATE_HIP_E_INTERNAL;
+    if (!dev && need_bytes) {
+      HIP_TRY(c, hipMemcpyAsync(windows, d_windows, need_bytes, hipMemcpyDeviceToHost, c->stream));
+      HIP_TRY(c, hipStreamSynchronize(c->stream));
+    }
+    for (uint32_t k = 0; k < kSeekHeadWords; ++k) index[k] = 0;
+    index[kSeekMagicAt] = kSeekMagic;
+    index[kSeekVersionAt] = kSeekVersion;
+    index[kSeekWrapAt] = wrap;
+    index[kSeekInLenAt] = in_len;
+    index[kSeekRawOffAt] = H.raw_off;
+    index[kSeekRawEndAt] = H.raw_off + H.raw_len;
+    index[kSeekTotalAt] = H.h.out_bytes;
+    index[kSeekSpanAt] = span;
+    index[kSeekUnitsAt] = n;
+    index[kSeekPointsAt] = np;
+    index[kSeekWantAt] = one.want;
+    index[kSeekIsizeAt] = one.isize;
+    index[kSeekRuleAt] = P.stored_units ? kSeekRuleStored : kSeekRuleDynamic;  // a read walks by this rule
+    uint64_t *w = index + kSeekHeadWords;
+    memcpy(w, found.data(), ((size_t)n + 1) * 8);
+    memcpy(w + (n + 1), found.data() + found.size() / 2, ((size_t)n + 1) * 8);
+    memcpy(w + 2 * ((size_t)n + 1), points.data(), (size_t)np * 8);
+    return FLATE_HIP_OK;
+  } catch (const std::exception &e) {
+    c->hip_err = e.what();
+    return FLATE_HIP_E_INTERNAL;
+  }
+}
+
+// Random access through the seek index: locate, select, layout (one_seek_kernels.hip), ONE read-back (the parsed
+// container, the ranges' layout, the unit list), rounds of TAIL / segmented scan / DECODE over the list into a dense
+// scratch, the per-unit check, the gather.
+int flate_hip_inflate_one_ranges(flate_hip_ctx *c, const uint8_t *in, uint64_t in_len, uint32_t wrap, const uint64_t *index,
+                                 uint64_t index_words, const uint8_t *windows, uint64_t windows_bytes, const uint64_t *begin,
+                                 const uint64_t *end, uint32_t n_ranges, uint8_t *out, uint64_t out_cap, uint64_t *out_off,
+                                 int32_t *range_status, uint32_t *n_decoded, uint32_t *bad_unit, uint32_t flags) {
+  // every check before any HIP call
+  if (!c) return FLATE_HIP_E_INVALID;
+  int rc = one_ranges_args(in, in_len, wrap, index, index_words, windows, windows_bytes, begin, end, n_ranges, out, out_cap,
+                           out_off, flags);
+  if (rc) return rc;
+  c->hip_err.clear();
+  if (n_decoded) *n_decoded = 0;
+  if (bad_unit) *bad_unit = 0xffffffffu;
+  if (n_ranges == 0) {
+    if (out_off) out_off[0] = 0;
+    return FLATE_HIP_OK;
+  }
+  const uint32_t nr = n_ranges;
+  try {
+    const bool dev = (flags & FLATE_HIP_DEVICE_PTRS) != 0;
+    const uint8_t *d_in = nullptr;
+    if ((rc = stage_input(c, in, in_len, flags, &d_in))) return rc;
+    const uint32_t n = (uint32_t)index[kSeekUnitsAt], np = (uint32_t)index[kSeekPointsAt];
+    const uint64_t raw_off = index[kSeekRawOffAt], raw_end = index[kSeekRawEndAt];
+    const uint64_t *h_point = index + kSeekHeadWords + 2 * ((size_t)n + 1);
+    const size_t idx_words = 2 * ((size_t)n + 1) + np;
+
+    OneSeekParams Q{};
+    Q.n = n, Q.n_points = np, Q.span = index[kSeekSpanAt], Q.n_ranges = nr;
+    uint64_t *d_idx, *d_begin, *d_end;
+    FrameOne *d_one;
+    size_t o_back = 0, o_end = 0;
+    rc = carve(c, c->d_one_seek, [&](Carve &k) {
+      k.take(d_idx, idx_words);
+      k.take(d_begin, nr);
+      k.take(d_end, nr);
+      k.take(Q.diff, (size_t)n + 1);
+      k.take(Q.rank, n);
+      k.take(Q.scratch_at, n);
+      k.take(Q.r_b, nr);
+      k.take(Q.r_len, nr);
+      k.take(Q.r_first, nr);
+      k.take(Q.r_last, nr);
+      k.take(Q.r_seg, nr);
+      k.take(Q.r_src, nr);
+      k.take(Q.sel_at, (size_t)n + 1);
+      o_back = k.at;
+      k.take(Q.head, 1);
+      k.take(d_one, 1);
+      k.take(Q.r_out_off, (size_t)nr + 1);
+      k.take(Q.r_rank_lo, nr);
+      k.take(Q.r_rank_hi, nr);
+      k.take(Q.sel_unit, n);
+      o_end = k.at;
+    });
+    if (rc) return rc;
+    Q.unit_bit = d_idx, Q.out_off = d_idx + (n + 1), Q.point_unit = d_idx + 2 * ((size_t)n + 1);
+    Q.begin = d_begin, Q.end = d_end;
+    const size_t back_bytes = o_end - o_back;
+    const uint8_t *d_back = (const uint8_t *)c->d_one_seek.p + o_back;
+    HIP_TRY(c, hipMemcpyAsync(d_idx, index + kSeekHeadWords, idx_words * 8, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(d_begin, begin, (size_t)nr * 8, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(d_end, end, (size_t)nr * 8, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemsetAsync(Q.diff, 0, ((size_t)n + 1) * 4, c->stream));
+    // the container as this stream has it: the raw stream's range and the trailer's words
+    one_parse_launch(c, d_in, in_len, d_one, wrap);
+    hipLaunchKernelGGL(one_seek_locate_kernel, dim3((nr + 255u) / 256u), dim3(256), 0, c->stream, Q);
+    hipLaunchKernelGGL(one_seek_select_kernel, dim3(1), dim3(1024), 0, c->stream, Q);
+    hipLaunchKernelGGL(one_seek_layout_kernel, dim3(1), dim3(1024), 0, c->stream, Q);
+    HIP_TRY(c, hipGetLastError());
+    std::vector<uint8_t> back(back_bytes);
+    HIP_TRY(c, hipMemcpyAsync(back.data(), d_back, back_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    auto got = [&](const auto *d) { return (decltype(d))(back.data() + ((const uint8_t *)d - d_back)); };  // d's host copy
+    const OneSeekHead RH = *got(Q.head);
+    const FrameOne one = *got(d_one);
+    const uint32_t *r_lo = got(Q.r_rank_lo), *r_hi = got(Q.r_rank_hi), *sel = got(Q.sel_unit);
+    const uint32_t ns = RH.n_sel;
+    if (one.bad || one.pay_off[0] != raw_off || one.pay_end != raw_end || one.want != index[kSeekWantAt] ||
+        one.isize != index[kSeekIsizeAt]) {  // not the stream the index was built from: nothing is decoded
+      for (uint32_t r = 0; r <= nr; ++r) out_off[r] = 0;
+      if (range_status)
+        for (uint32_t r = 0; r < nr; ++r) range_status[r] = FLATE_HIP_E_CORRUPT;
+      return FLATE_HIP_E_CORRUPT;
+    }
+    if (ns > n) {
+      c->hip_err = "seek ranges: more units selected than the stream has";
+      return FLATE_HIP_E_INTERNAL;
+    }
+    memcpy(out_off, got(Q.r_out_off), ((size_t)nr + 1) * 8);
+    if (n_decoded) *n_decoded = ns;
+    if (range_status)
+      for (uint32_t r = 0; r < nr; ++r) range_status[r] = 0;
+    if (RH.out_total > out_cap) return FLATE_HIP_E_OUT_TOO_SMALL;  // (the size query too: nothing is decoded)
+    if (ns == 0 || RH.out_total == 0) return FLATE_HIP_OK;        // (no range holds a byte)
+
+    // the windows: the caller's device buffer, or the blocks of the selected points uploaded into a staged copy
+    const uint8_t *d_windows = windows;
+    if (!dev && windows_bytes) {
+      if ((rc = ensure(c, c->d_one_seek_win, windows_bytes + 16))) return rc;
+      uint8_t *stage = (uint8_t *)c->d_one_seek_win.p;
+      d_windows = stage;
+      std::vector<uint32_t> ps;  // the selected points behind point 0, rising
+      uint32_t p = 1;
+      for (uint32_t i = 0; i < ns && p < np; ++i) {
+        while (p < np && h_point[p] < sel[i]) ++p;
+        if (p < np && h_point[p] == sel[i]) ps.push_back(p);
+      }
+      for (size_t a = 0; a < ps.size();) {  // neighbours in the index travel as one copy
+        size_t b = a + 1;
+        while (b < ps.size() && ps[b] == ps[b - 1] + 1u) ++b;
+        const uint64_t at = (uint64_t)(ps[a] - 1u) * kSeekWindow, len = (uint64_t)(b - a) * kSeekWindow;
+        HIP_TRY(c, hipMemcpyAsync(stage + at, windows + at, len, hipMemcpyHostToDevice, c->stream));
+        a = b;
+      }
+    }
+
+    const uint32_t per_round = unit_per_round(c, ns);
+    OneDecParams D{};
+    OneSeekRoundParams S{};
+    UnitResults dec;
+    if ((rc = seek_rounds_carve(c, D, S, dec, ns, per_round))) return rc;
+    // TAIL by the index's rule, not the context's option
+    const uint32_t stored = index[kSeekRuleAt] == kSeekRuleStored ? 1u : 0u;
+    if ((rc = unit_dec_params(c, D, d_in, d_one, Q.unit_bit, Q.out_off, stored, false))) return rc;
+    D.unit_list = Q.sel_unit;
+    S.Q = Q;
+    S.windows = d_windows;
+    auto seeds = [&](uint32_t i0, uint32_t count) {
+      S.i0 = i0, S.count = count;
+      hipLaunchKernelGGL(one_seek_seed_kernel, dim3((count + 255u) / 256u), dim3(256), 0, c->stream, S);
+      hipLaunchKernelGGL(one_seek_load_kernel, dim3(seek_load_blocks(count)), dim3(256), 0, c->stream, S);
+      return FLATE_HIP_OK;
+    };
+    const SeekRangesOut O{out, nr, RH.out_total, RH.scratch_total, r_lo, r_hi, sel, range_status, bad_unit, dev};
+    return seek_ranges_decode(c, D, S, dec, per_round, ns, d_in + raw_off, raw_end - raw_off, O, seeds);
+  } catch (const std::exception &e) {
+    c->hip_err = e.what();
+    return FLATE_HIP_E_INTERNAL;
+  }
+}
+
+}  // extern "C"
+
+// ---- a gzip file of any members: the units of all members as one chain (gzfile_kernels.hip, gzfile_rule.h) ----
+namespace {
+
+// The discovery over the file d_in[0, in_len) (DEVICE memory, in_len != 0) on the ctx's stream: the two count passes
+// and their scans, ONE read-back of the two candidate counts, then the fills, the B nodes' bits, the probe of every
+// node, link, rounds, finish, out-scan, the member scan, the tail probe, the member words and ONE read-back of the
+// result words H / G -- with member_out (the members' places in the output, n_b + 2 entries of which G.n_members + 1
+// count) when `mout` is given.  The index stays on the device (P).  Counted in no profiling stage.
+int gzfile_discover(flate_hip_ctx *c, const uint8_t *d_in, uint64_t in_len, OneHead &H, GzFileHead &G, GzFileParams &P,
+                    std::vector<uint64_t> *mout) {
+  int rc;
+  P = GzFileParams{};
+  OneParams PA{};
+  GzipParams PB{};
+  ChainParams &C = P.O.C;
+  uint32_t n_tiles = 0;
+  if ((rc = tiles_for(d_in, 0, in_len, &n_tiles))) return rc;
+  OneHead *head_a;
+  BgzfHead *head_b;
+  rc = carve(c, c->d_gzfile_tiles, [&](Carve &k) {
+    k.take(P.O.head, 1);
+    k.take(P.gh, 1);
+    k.take(P.O.one, 1);
+    k.take(head_a, 1);
+    k.take(head_b, 1);
+    k.take(PA.C.tile_cnt, (size_t)n_tiles + 1);
+    k.take(PB.C.tile_cnt, (size_t)n_tiles + 1);
+  });
+  if (rc) return rc;
+  C.in = PA.C.in = PB.C.in = d_in;
+  C.in_len = PA.C.in_len = PB.C.in_len = in_len;
+  C.n_tiles = PA.C.n_tiles = PB.C.n_tiles = n_tiles;
+  C.head = &P.O.head->h;
+  P.O.unit_max = PA.unit_max = c->one_unit_max;
+  P.O.stored_units = PA.stored_units = c->one_stored_units;
+  PA.C.head = &head_a->h;
+  PA.head = head_a;
+  PA.one = P.O.one;
+  PB.C.head = head_b;
+  PB.member_max = ~0ull;  // a member's range is never clipped
+  hipLaunchKernelGGL(gzfile_init_kernel, dim3(1), dim3(64), 0, c->stream, P.O.one, in_len);
+  one_find_launch(c, true, n_tiles, PA);
+  hipLaunchKernelGGL(chain_scan_kernel, dim3(1), dim3(1024), 0, c->stream, PA.C);
+  hipLaunchKernelGGL(gzip_count_kernel, dim3(n_tiles), dim3(256), 0, c->stream, PB);
+  hipLaunchKernelGGL(chain_scan_kernel, dim3(1), dim3(1024), 0, c->stream, PB.C);
+  HIP_TRY(c, hipGetLastError());
+  OneHead HA{};
+  BgzfHead HB{};
+  HIP_TRY(c, hipMemcpyAsync(&HA, head_a, sizeof HA, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(&HB, head_b, sizeof HB, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  const uint32_t na = HA.h.n_cand, nb = HB.n_cand;
+  if ((uint64_t)na + nb > 0x7ffffff0ull) return FLATE_HIP_E_TOO_LARGE;  // (the counts saturate at 2^32 - 1)
+  const uint32_t cap = na + nb;
+  if ((rc = chain_size(C, cap)) || (rc = chain_size(PA.C, na)) || (rc = chain_size(PB.C, nb))) return rc;
+  P.n_a = na;
+  P.n_b = nb;
+
+  const size_t n = cap;
+  uint64_t *hdr_off;
+  rc = carve(c, c->d_gzfile, [&](Carve &k) {
+    k.take(C.cand_off, n);
+    k.take(hdr_off, (size_t)nb + 1);
+    k.take(PB.cand_end, nb);
+    k.take(P.O.probe, n);
+    k.take(C.jump[0], n + 2);
+    k.take(C.jump[1], n + 2);
+    k.take(C.path, C.path_len);
+    k.take(P.O.usize, n);
+    k.take(C.member_off, n + 1);
+    k.take(C.out_off, n + 1);
+    k.take(P.u_start, n + 1);
+    k.take(P.u_final, n);
+    k.take(P.u_member, n + 1);
+    k.take(P.rel_off, n + 1);
+    k.take(P.member_off, (size_t)nb + 2);
+    k.take(P.member_unit, (size_t)nb + 2);
+    k.take(P.member_out, (size_t)nb + 2);
+  });
+  if (rc) return rc;
+  PA.C.cand_off = C.cand_off;
+  PB.C.cand_off = hdr_off;
+  P.hdr_off = hdr_off;
+  one_find_launch(c, false, n_tiles, PA);
+  if (nb) {
+    hipLaunchKernelGGL(gzip_fill_kernel, dim3(n_tiles), dim3(256), 0, c->stream, PB);
+    hipLaunchKernelGGL(gzfile_bits_kernel, dim3((nb + 255) / 256), dim3(256), 0, c->stream, P);
+  }
+  if (cap) one_probe_launch(c, cap, P.O, 0u);
+  const uint32_t node_blocks = (uint32_t)(((uint64_t)cap + 2 + 255) / 256);
+  hipLaunchKernelGGL(gzfile_link_kernel, dim3(node_blocks), dim3(256), 0, c->stream, P);
+  for (uint32_t j = 0; (1u << j) < C.path_len; ++j)
+    hipLaunchKernelGGL(chain_round_kernel, dim3(node_blocks), dim3(256), 0, c->stream, C, j);
+  hipLaunchKernelGGL(gzfile_finish_kernel, dim3((C.path_len + 255) / 256), dim3(256), 0, c->stream, P);
+  hipLaunchKernelGGL(one_out_scan_kernel, dim3(1), dim3(1024), 0, c->stream, P.O);
+  hipLaunchKernelGGL(gzfile_members_kernel, dim3(1), dim3(1024), 0, c->stream, P);
+  one_probe_launch(c, 1, P.O, 1u);
+  hipLaunchKernelGGL(gzfile_rel_kernel, dim3(node_blocks), dim3(256), 0, c->stream, P);
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipMemcpyAsync(&H, P.O.head, sizeof H, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(&G, P.gh, sizeof G, hipMemcpyDeviceToHost, c->stream));
+  if (mout) {
+    mout->assign((size_t)nb + 2, 0);
+    HIP_TRY(c, hipMemcpyAsync(mout->data(), P.member_out, ((size_t)nb + 2) * 8, hipMemcpyDeviceToHost, c->stream));
+  }
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  if (G.n_members > nb || H.h.n_members > cap) return FLATE_HIP_E_INTERNAL;
+  return FLATE_HIP_OK;
+}
+
+// The same discovery with the option "gzfile_serial_max" (S >= 1; gzfile_serial_rule.h, gzfile_serial_kernels.hip).
+// PHASE 1 over List B alone: count, scan, a read-back of the B count, fill, the serial ranges, ONE size-only launch of
+// the batch decoders over all B candidates, the whole test with the hop links, pointer doubling over those links, and
+// a read-back of find_from.  PHASE 2, only when find_from < in_len: FIND over in[find_from, in_len) -- the pass runs on
+// d_in + find_from with a FrameOne of its own, and one small kernel moves its bits to the file's origin -- and the
+// read-back of its count.  PROBE runs over all nodes; a whole B node is parked at the raw stream's end for it and gets
+// its phase-1 record back behind it.  Link, rounds, finish, the scans and the rel kernel are gzfile_discover's.  SH =
+// find_from and the whole members among the good units; S = their batch, on the device.
+int gzfile_discover_serial(flate_hip_ctx *c, const uint8_t *d_in, uint64_t in_len, OneHead &H, GzFileHead &G,
+                           GzFileParams &P, GzSerialParams &S, GzSerialHead &SH, std::vector<uint64_t> *mout) {
+  int rc;
+  P = GzFileParams{};
+  S = GzSerialParams{};
+  SH = GzSerialHead{};
+  OneParams PA{};
+  GzipParams PB{};
+  ChainParams &C = P.O.C;
+  uint32_t n_tiles = 0;
+  if ((rc = tiles_for(d_in, 0, in_len, &n_tiles))) return rc;
+  OneHead *head_a;
+  BgzfHead *head_b;
+  FrameOne *one_a;
+  rc = carve(c, c->d_gzfile_tiles, [&](Carve &k) {
+    k.take(P.O.head, 1);
+    k.take(P.gh, 1);
+    k.take(P.O.one, 1);
+    k.take(head_a, 1);
+    k.take(head_b, 1);
+    k.take(one_a, 1);
+    k.take(S.head, 1);
+    k.take(PA.C.tile_cnt, (size_t)n_tiles + 2);  // (a suffix at another alignment: at most one tile more)
+    k.take(PB.C.tile_cnt, (size_t)n_tiles + 1);
+  });
+  if (rc) return rc;
+  C.in = PB.C.in = d_in;
+  C.in_len = PB.C.in_len = in_len;
+  C.n_tiles = PB.C.n_tiles = n_tiles;
+  C.head = &P.O.head->h;
+  P.O.unit_max = PA.unit_max = c->one_unit_max;
+  P.O.stored_units = PA.stored_units = c->one_stored_units;
+  PB.C.head = head_b;
+  PB.member_max = ~0ull;  // a member's range is never clipped
+  hipLaunchKernelGGL(gzfile_init_kernel, dim3(1), dim3(64), 0, c->stream, P.O.one, in_len);
+  hipLaunchKernelGGL(gzip_count_kernel, dim3(n_tiles), dim3(256), 0, c->stream, PB);
+  hipLaunchKernelGGL(chain_scan_kernel, dim3(1), dim3(1024), 0, c->stream, PB.C);
+  HIP_TRY(c, hipGetLastError());
+  BgzfHead HB{};
+  HIP_TRY(c, hipMemcpyAsync(&HB, head_b, sizeof HB, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  const uint32_t nb = HB.n_cand;
+  if (nb > 0x7ffffff0u) return FLATE_HIP_E_TOO_LARGE;  // (the count saturates at 2^32 - 1)
+  if ((rc = chain_size(PB.C, nb))) return rc;
+
+  // PHASE 1
+  uint64_t *hdr_off;
+  InfParams I{};  // size-only: no output buffer, no slots
+  rc = carve(c, c->d_gzfile_serial, [&](Carve &k) {
+    k.take(hdr_off, (size_t)nb + 1);
+    k.take(PB.cand_end, nb);
+    k.take(S.pay_off, (size_t)nb + 1);
+    k.take(S.pay_end, nb);
+    k.take(I.out_len, nb);
+    k.take(I.status, nb);
+    k.take(I.err_off, nb);
+    k.take(I.used, nb);
+    k.take(S.rec, nb);
+    k.take(S.whole, nb);
+    k.take(S.jump[0], (size_t)nb + 2);
+    k.take(S.jump[1], (size_t)nb + 2);
+    k.take(S.w_in_off, (size_t)nb + 1);
+    k.take(S.w_in_end, nb);
+    k.take(S.w_out_off, (size_t)nb + 1);
+    k.take(S.w_size, nb);
+    k.take(S.w_unit, nb);
+  });
+  if (rc) return rc;
+  PB.C.cand_off = hdr_off;
+  P.hdr_off = hdr_off;
+  P.n_b = nb;
+  S.in = d_in;
+  S.in_len = in_len;
+  S.serial_max = c->gzfile_serial_max;
+  S.n_b = nb;
+  S.hdr_off = hdr_off;
+  S.status = I.status;
+  S.out_len = I.out_len;
+  S.used = I.used;
+  uint64_t find_from = in_len;  // (no candidate: no member at offset 0, nothing to search)
+  if (nb) {
+    const uint32_t b_blocks = (nb + 255u) / 256u, w_blocks = (uint32_t)(((uint64_t)nb + 2 + 255) / 256);
+    // every range is at most S < 2^28 bytes: the sub-block decoder at any batch size, or -- switched off -- the scalar
+    // walk; both report `used`
+    const uint64_t longest = in_len < S.serial_max ? in_len : S.serial_max;
+    const InflateRoute route = inflate_route(c->inflate, c->num_cus, nb, longest, false, true);
+    if (route.decoder == kDecodeSimt) {
+      c->hip_err = "gzfile discovery: a size-only pass was routed to the lane-per-stream decoder";
+      return FLATE_HIP_E_INTERNAL;
+    }
+    I.in = d_in;
+    I.in_off = S.pay_off;
+    I.in_end = S.pay_end;
+    I.n_streams = nb;
+    I.in_len = in_len;
+    I.size_only = 1u;
+    hipLaunchKernelGGL(gzip_fill_kernel, dim3(n_tiles), dim3(256), 0, c->stream, PB);
+    hipLaunchKernelGGL(gzfile_serial_ranges_kernel, dim3(b_blocks), dim3(256), 0, c->stream, S);
+    HIP_TRY(c, hipGetLastError());
+    if ((rc = launch_decoders(c, route, I, false))) return rc;
+    hipLaunchKernelGGL(gzfile_serial_nodes_kernel, dim3(w_blocks), dim3(256), 0, c->stream, S);
+    int cur = 0;
+    for (uint64_t s = 1; s < (uint64_t)nb + 2; s <<= 1, cur ^= 1)
+      hipLaunchKernelGGL(gzfile_serial_round_kernel, dim3(w_blocks), dim3(256), 0, c->stream, S.jump[cur], S.jump[cur ^ 1],
+                         nb + 2u);
+    hipLaunchKernelGGL(gzfile_serial_from_kernel, dim3(1), dim3(64), 0, c->stream, S, S.jump[cur]);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(&SH, S.head, sizeof SH, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    find_from = SH.find_from;
+    if (find_from > in_len) return FLATE_HIP_E_INTERNAL;
+  } else {
+    SH.find_from = in_len;
+    HIP_TRY(c, hipMemcpyAsync(S.head, &SH, sizeof SH, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));  // (SH is the caller's: the copy has read it)
+  }
+
+  // PHASE 2: FIND over the bytes from find_from on
+  uint32_t na = 0, n_tiles_a = 0;
+  if (find_from < in_len) {
+    const uint8_t *a_in = d_in + find_from;
+    const uint64_t a_len = in_len - find_from;
+    if ((rc = tiles_for(a_in, 0, a_len, &n_tiles_a))) return rc;
+    if (n_tiles_a > n_tiles + 1u) return FLATE_HIP_E_INTERNAL;
+    PA.C.in = a_in;
+    PA.C.in_len = a_len;
+    PA.C.n_tiles = n_tiles_a;
+    PA.C.head = &head_a->h;
+    PA.head = head_a;
+    PA.one = one_a;
+    hipLaunchKernelGGL(gzfile_init_kernel, dim3(1), dim3(64), 0, c->stream, one_a, a_len);
+    one_find_launch(c, true, n_tiles_a, PA);
+    hipLaunchKernelGGL(chain_scan_kernel, dim3(1), dim3(1024), 0, c->stream, PA.C);
+    HIP_TRY(c, hipGetLastError());
+    OneHead HA{};
+    HIP_TRY(c, hipMemcpyAsync(&HA, head_a, sizeof HA, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    na = HA.h.n_cand;
+  }
+  if ((uint64_t)na + nb > 0x7ffffff0ull) return FLATE_HIP_E_TOO_LARGE;
+  const uint32_t cap = na + nb;
+  if ((rc = chain_size(C, cap)) || (rc = chain_size(PA.C, na))) return rc;
+  P.n_a = S.n_a = na;
+
+  const size_t n = cap;
+  rc = carve(c, c->d_gzfile, [&](Carve &k) {
+    k.take(C.cand_off, n);
+    k.take(P.O.probe, n);
+    k.take(C.jump[0], n + 2);
+    k.take(C.jump[1], n + 2);
+    k.take(C.path, C.path_len);
+    k.take(P.O.usize, n);
+    k.take(C.member_off, n + 1);
+    k.take(C.out_off, n + 1);
+    k.take(P.u_start, n + 1);
+    k.take(P.u_final, n);
+    k.take(P.u_member, n + 1);
+    k.take(P.rel_off, n + 1);
+    k.take(P.member_off, (size_t)nb + 2);
+    k.take(P.member_unit, (size_t)nb + 2);
+    k.take(P.member_out, (size_t)nb + 2);
+  });
+  if (rc) return rc;
+  rc = carve(c, c->d_gzfile_serial_units, [&](Carve &k) {
+    k.take(S.u_whole, n + 1);
+    k.take(S.u_end, n + 1);
+  });
+  if (rc) return rc;
+  PA.C.cand_off = C.cand_off;
+  if (find_from < in_len) {
+    one_find_launch(c, false, n_tiles_a, PA);
+    if (na) hipLaunchKernelGGL(gzfile_serial_base_kernel, dim3((na + 255u) / 256u), dim3(256), 0, c->stream, C.cand_off, na, 8u * find_from);
+  }
+  if (nb) hipLaunchKernelGGL(gzfile_serial_bits_kernel, dim3((nb + 255) / 256), dim3(256), 0, c->stream, P, S);
+  if (cap) one_probe_launch(c, cap, P.O, 0u);
+  if (nb) hipLaunchKernelGGL(gzfile_serial_keep_kernel, dim3((nb + 255) / 256), dim3(256), 0, c->stream, P, S);
+  const uint32_t node_blocks = (uint32_t)(((uint64_t)cap + 2 + 255) / 256);
+  hipLaunchKernelGGL(gzfile_link_kernel, dim3(node_blocks), dim3(256), 0, c->stream, P);
+  for (uint32_t j = 0; (1u << j) < C.path_len; ++j)
+    hipLaunchKernelGGL(chain_round_kernel, dim3(node_blocks), dim3(256), 0, c->stream, C, j);
+  hipLaunchKernelGGL(gzfile_finish_kernel, dim3((C.path_len + 255) / 256), dim3(256), 0, c->stream, P);
+  hipLaunchKernelGGL(gzfile_serial_marks_kernel, dim3(node_blocks), dim3(256), 0, c->stream, P, S);
+  hipLaunchKernelGGL(one_out_scan_kernel, dim3(1), dim3(1024), 0, c->stream, P.O);
+  hipLaunchKernelGGL(gzfile_members_kernel, dim3(1), dim3(1024), 0, c->stream, P);
+  one_probe_launch(c, 1, P.O, 1u);
+  hipLaunchKernelGGL(gzfile_rel_kernel, dim3(node_blocks), dim3(256), 0, c->stream, P);
+  hipLaunchKernelGGL(gzfile_serial_list_kernel, dim3(1), dim3(1024), 0, c->stream, P, S);
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipMemcpyAsync(&H, P.O.head, sizeof H, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(&G, P.gh, sizeof G, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(&SH, S.head, sizeof SH, hipMemcpyDeviceToHost, c->stream));
+  if (mout) {
+    mout->assign((size_t)nb + 2, 0);
+    HIP_TRY(c, hipMemcpyAsync(mout->data(), P.member_out, ((size_t)nb + 2) * 8, hipMemcpyDeviceToHost, c->stream));
+  }
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  if (G.n_members > nb || H.h.n_members > cap || SH.n_whole > nb || SH.n_whole > G.n_members || SH.find_from != find_from)
+    return FLATE_HIP_E_INTERNAL;
+  return FLATE_HIP_OK;
+}
+
+// the discovery of flate_hip_gzfile_index / _read by the ctx's option, and what flate_hip_gzfile_last_route reports
+int gzfile_discover_routed(flate_hip_ctx *c, const uint8_t *d_in, uint64_t in_len, OneHead &H, GzFileHead &G,
+                           GzFileParams &P, GzSerialParams &S, GzSerialHead &SH, std::vector<uint64_t> *mout) {
+  c->gzfile_route[0] = c->gzfile_route[1] = 0;
+  c->gzfile_route_from = 0;
+  int rc;
+  if (!c->gzfile_serial_max) {
+    S = GzSerialParams{};
+    SH = GzSerialHead{};
+    if ((rc = gzfile_discover(c, d_in, in_len, H, G, P, mout))) return rc;
+  } else if ((rc = gzfile_discover_serial(c, d_in, in_len, H, G, P, S, SH, mout))) {
+    return rc;
+  }
+  c->gzfile_route[0] = SH.n_whole;
+  c->gzfile_route[1] = G.n_members - SH.n_whole;
+  c->gzfile_route_from = SH.find_from;
+  return FLATE_HIP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int flate_hip_gzfile_index(flate_hip_ctx *c, const uint8_t *in, uint64_t in_len, uint64_t index_cap, uint64_t *unit_bit,
+                           uint64_t *out_off, uint64_t member_cap, uint64_t *member_off, uint64_t *member_unit,
+                           uint32_t *n_units, uint32_t *n_members, uint64_t *out_bytes, uint32_t *n_candidates,
+                           int32_t *status, uint32_t *bad_member, int64_t *err_off, int64_t *stream_err_off,
+                           uint32_t flags) {
+  // every check before any HIP call
+  if (!c) return FLATE_HIP_E_INVALID;
+  int rc = gzfile_index_args(in, in_len, unit_bit, out_off, member_off, member_unit, n_units, n_members, out_bytes, status,
+                             flags);
+  if (rc) return rc;
+  c->hip_err.clear();
+  *n_units = 0, *n_members = 0, *out_bytes = 0, *status = 0;
+  if (n_candidates) *n_candidates = 0;
+  if (bad_member) *bad_member = 0xffffffffu;
+  if (err_off) *err_off = -1;
+  if (stream_err_off) *stream_err_off = -1;
+  try {
+    OneHead H{};
+    GzFileHead G{};
+    GzFileParams P{};
+    GzSerialParams SP{};
+    GzSerialHead SH{};
+    G.err_off = G.stream_err_off = -1;
+    c->gzfile_route[0] = c->gzfile_route[1] = 0;
+    c->gzfile_route_from = 0;
+    if (in_len) {  // (no bytes: zero members, zero units)
+      const uint8_t *d_in = nullptr;
+      if ((rc = stage_input(c, in, in_len, flags, &d_in))) return rc;
+      if ((rc = gzfile_discover_routed(c, d_in, in_len, H, G, P, SP, SH, nullptr))) return rc;
+    }
+    *n_units = H.h.n_members;
+    *n_members = G.n_members;
+    if (n_candidates) *n_candidates = H.h.n_cand;
+    *status = H.h.rc;
+    *out_bytes = H.h.out_bytes;  // (0 on a broken chain)
+    if (H.h.rc) {
+      if (bad_member) *bad_member = G.n_members;
+      if (err_off) *err_off = G.err_off;
+      if (stream_err_off) *stream_err_off = G.stream_err_off;
+    }
+    // the index -- of a broken chain its good prefix, where that fits: the verdict is the walk's either way
+    const uint64_t ue = (uint64_t)H.h.n_members + 1, me = (uint64_t)G.n_members + 1;
+    const bool u_fits = unit_bit && index_cap >= ue, m_fits = member_off && member_cap >= me;
+    if (in_len) {
+      if (u_fits) {
+        HIP_TRY(c, hipMemcpyAsync(unit_bit, P.O.C.member_off, ue * 8, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(out_off, P.O.C.out_off, ue * 8, hipMemcpyDeviceToHost, c->stream));
+      }
+      if (m_fits) {
+        HIP_TRY(c, hipMemcpyAsync(member_off, P.member_off, me * 8, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(member_unit, P.member_unit, me * 8, hipMemcpyDeviceToHost, c->stream));
+      }
+      if (u_fits || m_fits) HIP_TRY(c, hipStreamSynchronize(c->stream));
+    } else {
+      if (u_fits) unit_bit[0] = 0, out_off[0] = 0;
+      if (m_fits) member_off[0] = 0, member_unit[0] = 0;
+    }
+    if (H.h.rc) return H.h.rc;
+    return ((unit_bit && !u_fits) || (member_off && !m_fits)) ? FLATE_HIP_E_OUT_TOO_SMALL : FLATE_HIP_OK;
+  } catch (const std::exception &e) {  // (out of host memory)
+    c->hip_err = e.what();
+    return FLATE_HIP_E_INTERNAL;
+  }
+}
+
+// The whole call: discovery, then flate_hip_inflate_one's rounds over the units of all members -- TAIL with the
+// member-relative offsets, the SEGMENTED compose / resolve with every member's first unit as a seed, DECODE straight
+// into out + out_off[k] with a history that never crosses a member --, then one checksum launch planned over the
+// members' output ranges, the trailers and the verdict.
+int flate_hip_gzfile_read(flate_hip_ctx *c, const uint8_t *in, uint64_t in_len, uint8_t *out, uint64_t out_cap,
+                          uint64_t *out_len, uint32_t *n_members, uint32_t *n_units, uint32_t *n_candidates,
+                          int32_t *status, uint32_t *bad_member, int64_t *err_off, int64_t *stream_err_off,
+                          uint32_t flags) {
+  // every check before any HIP call
+  if (!c) return FLATE_HIP_E_INVALID;
+  int rc = gzfile_read_args(in, in_len, out, out_cap, out_len, status, flags);
+  if (rc) return rc;
+  c->hip_err.clear();
+  *out_len = 0, *status = 0;
+  if (n_members) *n_members = 0;
+  if (n_units) *n_units = 0;
+  if (n_candidates) *n_candidates = 0;
+  if (bad_member) *bad_member = 0xffffffffu;
+  if (err_off) *err_off = -1;
+  if (stream_err_off) *stream_err_off = -1;
+  c->gzfile_route[0] = c->gzfile_route[1] = 0;
+  c->gzfile_route_from = 0;
+  if (in_len == 0) return FLATE_HIP_OK;
+  try {
+    const bool dev = (flags & FLATE_HIP_DEVICE_PTRS) != 0;
+    const uint8_t *d_in = nullptr;
+    if ((rc = stage_input(c, in, in_len, flags, &d_in))) return rc;
+    OneHead H{};
+    GzFileHead G{};
+    GzFileParams P{};
+    GzSerialParams SP{};
+    GzSerialHead SH{};
+    std::vector<uint64_t> mout;
+    if ((rc = gzfile_discover_routed(c, d_in, in_len, H, G, P, SP, SH, &mout))) return rc;
+    if (n_members) *n_members = G.n_members;
+    if (n_units) *n_units = H.h.n_members;
+    if (n_candidates) *n_candidates = H.h.n_cand;
+    // the units to decode: the good ones and, so that the bytes in front of an error are delivered, a unit that fails
+    // behind its header; the total is known here
+    const uint32_t n_dec = H.h.n_members + (H.fail_unit ? 1u : 0u);
+    const uint64_t total = H.prefix_bytes + (H.fail_unit ? H.fail_out : 0ull);
+    *out_len = total;
+    if (total > out_cap) return FLATE_HIP_E_OUT_TOO_SMALL;  // (nothing is decoded; out == NULL: the size query)
+    uint8_t *d_out = out;
+    if (!dev) {
+      if ((rc = ensure(c, c->d_out, total + 16))) return rc;
+      d_out = (uint8_t *)c->d_out.p;
+    }
+    const uint32_t n_mem = H.h.rc == 0 ? G.n_members : 0u;  // the members whose trailers are judged
+    // the runs of units the rounds go over: all of them, or (option "gzfile_serial_max") what lies between the whole
+    // members -- a run starts with a member's first unit, a seed, and ends where a member does
+    const uint32_t n_whole = SH.n_whole;
+    std::vector<std::pair<uint32_t, uint32_t>> runs;
+    uint32_t longest_run = n_dec;
+    if (n_whole) {
+      std::vector<uint32_t> whole(n_dec);
+      HIP_TRY(c, hipMemcpyAsync(whole.data(), SP.u_whole, (size_t)n_dec * 4, hipMemcpyDeviceToHost, c->stream));
+      HIP_TRY(c, hipStreamSynchronize(c->stream));
+      longest_run = 0;
+      for (uint32_t a = 0; a < n_dec;) {
+        uint32_t b = a;
+        while (b < n_dec && !whole[b]) ++b;
+        if (b > a) runs.emplace_back(a, b);
+        if (b - a > longest_run) longest_run = b - a;
+        a = b + 1u;
+      }
+    } else if (n_dec) {
+      runs.emplace_back(0u, n_dec);
+    }
+    const uint32_t per_round = unit_per_round(c, longest_run);
+    GzFileDecParams GD{};
+    OneDecParams &D = GD.D;
+    uint32_t *d_sums;
+    UnitResults dec;
+    rc = unit_rounds_carve(c, D, n_dec, per_round, [&](Carve &k) { unit_pieces_take(k, D, &dec, per_round); });
+    if (rc) return rc;
+    rc = carve(c, c->d_gzfile_dec, [&](Carve &k) {
+      k.take(GD.v, 1);
+      k.take(GD.seed, per_round);
+      k.take(GD.p_bit_off, per_round);
+      k.take(GD.p_bit_end, per_round);
+      k.take(d_sums, (size_t)n_mem + 1);
+    });
+    if (rc) return rc;
+    if ((rc = unit_dec_params(c, D, d_in, P.O.one, P.O.C.member_off, P.O.C.out_off, P.O.stored_units, false))) return rc;
+    unit_verdict_params(D, total, dec, P.O.head, FLATE_HIP_WRAP_GZIP, in_len);
+    GD.P = P;
+    GD.n_good = H.h.n_members;
+    GD.n_members = n_mem;
+    GD.sums = d_sums;
+    HIP_TRY(c, hipMemsetAsync(GD.v, 0xff, sizeof(GzFileVerdict), c->stream));  // bad_trailer: none
+    if ((rc = unit_zero_seed(c, D))) return rc;
+    bool used[FLATE_HIP_STAGE_COUNT] = {false, false, false, false};
+    if (n_whole && total) {
+      // the WHOLE members: ONE batch of independent streams straight into their places, IN FRONT of the rounds.  A slot
+      // ends at the next whole member's start (the last at the end of the good units' output), so it may span the units
+      // between them: whatever the batch leaves there is overwritten by the units that own those bytes
+      InfParams W{};
+      rc = carve(c, c->d_gzfile_serial_dec, [&](Carve &k) {
+        k.take(W.out_len, n_whole);
+        k.take(W.status, n_whole);
+        k.take(W.err_off, n_whole);
+      });
+      if (rc) return rc;
+      W.in = d_in;
+      W.in_off = SP.w_in_off;
+      W.in_end = SP.w_in_end;
+      W.n_streams = n_whole;
+      W.in_len = in_len;
+      W.out = d_out;
+      W.out_off = SP.w_out_off;
+      const uint64_t longest = in_len < SP.serial_max ? in_len : SP.serial_max;
+      if ((rc = launch_decoders(c, inflate_route(c->inflate, c->num_cus, n_whole, longest, false, false), W, false))) return rc;
+      hipLaunchKernelGGL(gzfile_serial_check_kernel, dim3((n_whole + 255u) / 256u), dim3(256), 0, c->stream, SP, n_whole,
+                         W.status, W.out_len, D.dh);
+      used[FLATE_HIP_STAGE_INFLATE] = true;
+      HIP_TRY(c, hipGetLastError());
+    }
+    // the pieces and the seeds of the round (every member's first unit is one)
+    auto pieces = [&](uint32_t, uint32_t count) {
+      hipLaunchKernelGGL(gzfile_pieces_kernel, dim3((count + 1u + 255u) / 256u), dim3(256), 0, c->stream, GD);
+      return FLATE_HIP_OK;
+    };
+    // DECODE: the round's units as pieces with dictionaries and their own ends, through the lane-per-stream decoder
+    auto decode = [&](uint32_t, uint32_t count) {
+      const int r = unit_decode(c, unit_decode_params(D, d_in, H.raw_len, GD.p_bit_off, GD.p_bit_end, false, count, d_out,
+                                                      D.p_out_off, dec));
+      if (r) return r;
+      hipLaunchKernelGGL(one_check_kernel, dim3((count + 1u + 255u) / 256u), dim3(256), 0, c->stream, D);
+      return FLATE_HIP_OK;
+    };
+    // TAIL with the member-relative offsets: a unit's history is what its own member has produced in front of it
+    for (const auto &run : runs) {
+      rc = unit_rounds(c, D, P.rel_off, GD.seed, run.first, run.second, n_dec, per_round, unit_no_hook, pieces, decode);
+      if (rc) return rc;
+      used[FLATE_HIP_STAGE_INFLATE] = true;
+    }
+    bool ctl = false;
+    if (n_mem) {  // VERIFY: one launch planned over the members' output ranges, then a thread per trailer
+      if (mout.size() < (size_t)n_mem + 1) return FLATE_HIP_E_INTERNAL;
+      if ((rc = ctl_begin(c, checksum_ctl_up_bytes(mout.data(), n_mem), 0))) return rc;
+      ctl = true;
+      if ((rc = checksum_device(c, d_out, mout.data(), n_mem, FLATE_HIP_CHECKSUM_CRC32, d_sums, FLATE_HIP_STAGE_CHECKSUM)))
+        return rc;
+      used[FLATE_HIP_STAGE_CHECKSUM] = true;
+      hipLaunchKernelGGL(gzfile_trailer_kernel, dim3((n_mem + 255) / 256), dim3(256), 0, c->stream, GD);
+    }
+    hipLaunchKernelGGL(gzfile_verdict_kernel, dim3(1), dim3(64), 0, c->stream, GD);
+    HIP_TRY(c, hipGetLastError());
+    GzFileVerdict V{};
+    HIP_TRY(c, hipMemcpyAsync(&V, GD.v, sizeof V, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (ctl) ctl_finish(c);
+    if (V.out_len > total) return FLATE_HIP_E_INTERNAL;
+    *out_len = V.out_len;
+    if (!dev && V.out_len) {  // the result comes down once
+      HIP_TRY(c, hipMemcpyAsync(out, d_out, V.out_len, hipMemcpyDeviceToHost, c->stream));
+      HIP_TRY(c, hipStreamSynchronize(c->stream));
+    }
+    if (c->profiling && (rc = collect_timing(c, used))) return rc;
+    if (n_members) *n_members = V.n_members;
+    if (n_units) *n_units = V.n_units;
+    *status = V.status;
+    if (V.status) {
+      if (bad_member) *bad_member = V.bad_member;
+      if (err_off) *err_off = V.err_off;
+      if (stream_err_off) *stream_err_off = V.stream_err_off;
+    }
+    return V.status;
+  } catch (const std::exception &e) {
+    c->hip_err = e.what();
+    return FLATE_HIP_E_INTERNAL;
+  }
+}
+
+// The seek index of a file of any members: the file's discovery, POINTS with every member's first unit as a point,
+// then flate_hip_gzfile_read's rounds of TAIL / segmented COMPOSE / RESOLVE and, in DECODE's place, PACK: the windows
+// in front of the round's window-bearing points into their blocks.  Nothing is decoded to output, no trailer is judged.
+int flate_hip_gzfile_seek_index(flate_hip_ctx *c, const uint8_t *in, uint64_t in_len, uint64_t span, uint64_t *index,
+                                uint64_t index_cap_words, uint64_t *index_words, uint8_t *windows, uint64_t windows_cap,
+                                uint64_t *windows_bytes, uint32_t *n_units, uint32_t *n_members, uint32_t *n_points,
+                                uint64_t *out_bytes, uint32_t *n_candidates, int32_t *status, uint32_t *bad_member,
+                                int64_t *err_off, int64_t *stream_err_off, uint32_t flags) {
+  // every check before any HIP call
+  if (!c) return FLATE_HIP_E_INVALID;
+  int rc = gzfile_seek_index_args(in, in_len, index, index_cap_words, index_words, windows, windows_cap, windows_bytes,
+                                  n_units, n_members, n_points, out_bytes, status, flags);
+  if (rc) return rc;
+  c->hip_err.clear();
+  *index_words = 0, *windows_bytes = 0, *n_units = 0, *n_members = 0, *n_points = 0, *out_bytes = 0, *status = 0;
+  if (n_candidates) *n_candidates = 0;
+  if (bad_member) *bad_member = 0xffffffffu;
+  if (err_off) *err_off = -1;
+  if (stream_err_off) *stream_err_off = -1;
+  auto fail = [&](int st, uint32_t bm, int64_t eo, int64_t seo) {  // a file that fails gets no index
+    *status = st;
+    *index_words = 0, *windows_bytes = 0, *n_points = 0, *out_bytes = 0;
+    if (bad_member) *bad_member = bm;
+    if (err_off) *err_off = eo;
+    if (stream_err_off) *stream_err_off = seo;
+    return st;
+  };
+  span = seek_span(span);
+  auto head = [&](uint64_t T, uint64_t n, uint64_t m, uint64_t np) {
+    for (uint32_t k = 0; k < kGzSeekHeadWords; ++k) index[k] = 0;
+    index[kGzSeekMagicAt] = kGzSeekMagic;
+    index[kGzSeekVersionAt] = kGzSeekVersion;
+    index[kGzSeekInLenAt] = in_len;
+    index[kGzSeekTotalAt] = T;
+    index[kGzSeekSpanAt] = span;
+    index[kGzSeekUnitsAt] = n;
+    index[kGzSeekMembersAt] = m;
+    index[kGzSeekPointsAt] = np;
+    index[kGzSeekRuleAt] = c->one_stored_units ? kSeekRuleStored : kSeekRuleDynamic;  // a read walks by this rule
+  };
+  if (in_len == 0) {  // no bytes: zero members, zero units, the head alone
+    *index_words = gzfile_seek_index_words(0, 0, 0);
+    if (index_cap_words < *index_words) return FLATE_HIP_E_OUT_TOO_SMALL;
+    head(0, 0, 0, 0);
+    return FLATE_HIP_OK;
+  }
+  try {
+    const bool dev = (flags & FLATE_HIP_DEVICE_PTRS) != 0;
+    const uint8_t *d_in = nullptr;
+    if ((rc = stage_input(c, in, in_len, flags, &d_in))) return rc;
+    OneHead H{};
+    GzFileHead G{};
+    GzFileParams P{};
+    if ((rc = gzfile_discover(c, d_in, in_len, H, G, P, nullptr))) return rc;
+    const uint32_t n = H.h.n_members, m = G.n_members;
+    *n_units = n;
+    *n_members = m;
+    if (n_candidates) *n_candidates = H.h.n_cand;
+    auto found = [&]() { return fail(H.h.rc, G.n_members, G.err_off, G.stream_err_off); };  // the discovery's verdict
+    if (H.h.rc == FLATE_HIP_E_TOO_LARGE || H.h.rc == FLATE_HIP_E_INTERNAL) return found();
+    const bool sound = H.h.rc == 0;  // (a file that fails is still walked: an earlier unit's distance may fail first)
+    const uint32_t n_dec = n + (H.fail_unit ? 1u : 0u);
+    if (n_dec == 0) return found();
+    if (sound && (n < 1u || m < 1u || m > n)) return FLATE_HIP_E_INTERNAL;
+    const uint32_t per_round = unit_per_round(c, n_dec);
+
+    // POINTS: mark, scan, compact; the sizes are known here, in front of TAIL
+    GzSeekPointsParams PP{};
+    GzSeekPackParams K{};
+    rc = carve(c, c->d_one_seek, [&](Carve &k) {
+      k.take(PP.counts, 2);
+      k.take(PP.point_unit, (size_t)n + 1);
+      k.take(K.r_out_off, (size_t)per_round + 1);
+      k.take(K.r_src, per_round);
+    });
+    if (rc) return rc;
+    std::vector<uint64_t> ubit, ooff, moff, munit, points;
+    uint32_t np = 0;
+    uint64_t need_words = 0, need_bytes = 0;
+    if (sound) {
+      PP.out_off = P.O.C.out_off;
+      PP.u_start = P.u_start;
+      PP.n = n;
+      PP.span = span;
+      hipLaunchKernelGGL(gzfile_seek_points_kernel, dim3(1), dim3(1024), 0, c->stream, PP);
+      HIP_TRY(c, hipGetLastError());
+      uint32_t counts[2] = {0, 0};
+      ubit.assign((size_t)n + 1, 0), ooff.assign((size_t)n + 1, 0), points.assign(n, 0);
+      moff.assign((size_t)m + 1, 0), munit.assign((size_t)m + 1, 0);
+      HIP_TRY(c, hipMemcpyAsync(counts, PP.counts, 8, hipMemcpyDeviceToHost, c->stream));
+      HIP_TRY(c, hipMemcpyAsync(points.data(), PP.point_unit, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
+      HIP_TRY(c, hipMemcpyAsync(ubit.data(), P.O.C.member_off, ((size_t)n + 1) * 8, hipMemcpyDeviceToHost, c->stream));
+      HIP_TRY(c, hipMemcpyAsync(ooff.data(), P.O.C.out_off, ((size_t)n + 1) * 8, hipMemcpyDeviceToHost, c->stream));
+      HIP_TRY(c, hipMemcpyAsync(moff.data(), P.member_off, ((size_t)m + 1) * 8, hipMemcpyDeviceToHost, c->stream));
+      HIP_TRY(c, hipMemcpyAsync(munit.data(), P.member_unit, ((size_t)m + 1) * 8, hipMemcpyDeviceToHost, c->stream));
+      HIP_TRY(c, hipStreamSynchronize(c->stream));
+      np = counts[0];
+      if (np < m || np > n || counts[1] != np - m || munit[0] != 0u || munit[m] != n) {
+        c->hip_err = "gzfile seek index: the point count does not fit the units and members";
+        return FLATE_HIP_E_INTERNAL;
+      }
+      need_words = gzfile_seek_index_words(n, m, np);
+      need_bytes = gzfile_seek_windows_bytes(np, m);
+      *index_words = need_words, *windows_bytes = need_bytes, *n_points = np, *out_bytes = H.h.out_bytes;
+      if (index_cap_words < need_words || windows_cap < need_bytes) return FLATE_HIP_E_OUT_TOO_SMALL;  // (the size query too)
+    }
+    uint8_t *d_windows = windows;
+    if (sound && !dev && need_bytes) {
+      if ((rc = ensure(c, c->d_one_seek_win, need_bytes + 16))) return rc;
+      d_windows = (uint8_t *)c->d_one_seek_win.p;
+    }
+
+    GzFileDecParams GD{};
+    OneDecParams &D = GD.D;
+    rc = unit_rounds_carve(c, D, n_dec, per_round, [&](Carve &k) { unit_pieces_take(k, D, nullptr, per_round); });
+    if (rc) return rc;
+    rc = carve(c, c->d_gzfile_dec, [&](Carve &k) {
+      k.take(GD.seed, per_round);
+      k.take(GD.p_bit_off, per_round);
+      k.take(GD.p_bit_end, per_round);
+    });
+    if (rc) return rc;
+    if ((rc = unit_dec_params(c, D, d_in, P.O.one, P.O.C.member_off, P.O.C.out_off, P.O.stored_units, false))) return rc;
+    D.total = H.prefix_bytes + (H.fail_unit ? H.fail_out : 0ull);
+    GD.P = P;
+    GD.n_good = n;
+    K.point_unit = PP.point_unit;
+    K.member_unit = P.member_unit;
+    K.m = m;
+    K.n_points = np;
+    uint32_t p_next = 0;  // the first point whose round has not come yet
+    // a member's first unit is a seed that RESOLVE never writes: zeros in front of every member, so that a stored
+    // window holds nothing of the member in front (slot 0 is the carried window unless the round starts a member)
+    auto zeros = [&](uint32_t u0, uint32_t count) {
+      if (!sound) return FLATE_HIP_OK;
+      const bool starts = munit[bgzf_upper_bound(munit.data(), m, u0) - 1u] == u0;
+      uint8_t *from = D.R + (starts ? 0 : kWinEntries);
+      HIP_TRY(c, hipMemsetAsync(from, 0, ((size_t)count + (starts ? 1 : 0)) * kWinEntries, c->stream));
+      return FLATE_HIP_OK;
+    };
+    auto seeds = [&](uint32_t, uint32_t count) {
+      hipLaunchKernelGGL(gzfile_pieces_kernel, dim3((count + 1u + 255u) / 256u), dim3(256), 0, c->stream, GD);
+      return FLATE_HIP_OK;
+    };
+    // PACK: R[i] of the round's window-bearing points -> their blocks, which lie one behind the other in `windows`
+    auto pack = [&](uint32_t u0, uint32_t count) {
+      uint32_t p_hi = p_next;
+      while (p_hi < np && points[p_hi] < (uint64_t)u0 + count) ++p_hi;
+      if (p_hi == p_next) return FLATE_HIP_OK;
+      const uint32_t cnt = p_hi - p_next;
+      const uint32_t b_lo = gzfile_seek_blocks_before(munit.data(), m, p_next, (uint32_t)points[p_next]);
+      const uint32_t b_hi = p_hi < np ? gzfile_seek_blocks_before(munit.data(), m, p_hi, (uint32_t)points[p_hi]) : np - m;
+      K.p_lo = p_next, K.np = cnt, K.u0 = u0;
+      p_next = p_hi;
+      if (b_hi <= b_lo) return FLATE_HIP_OK;
+      hipLaunchKernelGGL(gzfile_seek_pack_kernel, dim3((cnt + 1u + 255u) / 256u), dim3(256), 0, c->stream, K);
+      return ranges_gather(c, D.R, d_windows + (uint64_t)b_lo * kSeekWindow, K.r_out_off, K.r_src, cnt,
+                           (uint64_t)(b_hi - b_lo) * kSeekWindow);
+    };
+    // TAIL with the member-relative offsets: a unit's history is what its own member has produced in front of it
+    if ((rc = unit_rounds(c, D, P.rel_off, GD.seed, 0, n_dec, n_dec, per_round, zeros, seeds, pack))) return rc;
+    OneDecHead bad{};
+    uint32_t bm = 0;
+    if ((rc = unit_first_bad(c, D, n_dec, bad, P.u_member, &bm))) return rc;
+    if (bad.first_bad != 0xffffffffu) {  // TAIL's verdict: the serial decoder's, at the serial offset, in its member
+      const uint32_t fb = bad.first_bad;
+      if (bm >= P.n_b) return FLATE_HIP_E_INTERNAL;
+      uint64_t at = 0, first = 0, bit = 0;
+      HIP_TRY(c, hipMemcpyAsync(&at, P.member_off + bm, 8, hipMemcpyDeviceToHost, c->stream));
+      HIP_TRY(c, hipMemcpyAsync(&first, P.member_unit + bm, 8, hipMemcpyDeviceToHost, c->stream));
+      HIP_TRY(c, hipStreamSynchronize(c->stream));
+      if (first > fb) return FLATE_HIP_E_INTERNAL;
+      HIP_TRY(c, hipMemcpyAsync(&bit, P.O.C.member_off + first, 8, hipMemcpyDeviceToHost, c->stream));
+      HIP_TRY(c, hipStreamSynchronize(c->stream));
+      *n_members = bm;
+      *n_units = fb;
+      const int64_t seo = (bad.status == FLATE_HIP_E_CORRUPT && bad.err_off >= 0) ? bad.err_off - (int64_t)(bit >> 3) : -1;
+      return fail(bad.status ? bad.status : FLATE_HIP_E_INTERNAL, bm, (int64_t)at, seo);
+    }
+    if (!sound) return found();
+    if (p_next != np) return FLATE_HIP_E_INTERNAL;
+    if (!dev && need_bytes) {
+      HIP_TRY(c, hipMemcpyAsync(windows, d_windows, need_bytes, hipMemcpyDeviceToHost, c->stream));
+      HIP_TRY(c, hipStreamSynchronize(c->stream));
+    }
+    head(H.h.out_bytes, n, m, np);
+    uint64_t *w = index + kGzSeekHeadWords;
+    memcpy(w, ubit.data(), ((size_t)n + 1) * 8), w += (size_t)n + 1;
+    memcpy(w, ooff.data(), ((size_t)n + 1) * 8), w += (size_t)n + 1;
+    memcpy(w, moff.data(), ((size_t)m + 1) * 8), w += (size_t)m + 1;
+    memcpy(w, munit.data(), ((size_t)m + 1) * 8), w += (size_t)m + 1;
+    memcpy(w, points.data(), (size_t)np * 8);
+    return FLATE_HIP_OK;
+  } catch (const std::exception &e) {
+    c->hip_err = e.what();
+    return FLATE_HIP_E_INTERNAL;
+  }
+}
+
+// Random access through the file's seek index: the "same file" check per member, rel, locate, select, layout, ONE
+// read-back (the check's word, the ranges' layout, the unit list), rounds of TAIL / segmented scan / DECODE over the
+// list into a dense scratch, the per-unit check, the gather.
+int flate_hip_gzfile_ranges(flate_hip_ctx *c, const uint8_t *in, uint64_t in_len, const uint64_t *index, uint64_t index_words,
+                            const uint8_t *windows, uint64_t windows_bytes, const uint64_t *begin, const uint64_t *end,
+                            uint32_t n_ranges, uint8_t *out, uint64_t out_cap, uint64_t *out_off, int32_t *range_status,
+                            uint32_t *n_decoded, uint32_t *bad_unit, uint32_t flags) {
+  // every check before any HIP call
+  if (!c) return FLATE_HIP_E_INVALID;
+  int rc = gzfile_ranges_args(in, in_len, index, index_words, windows, windows_bytes, begin, end, n_ranges, out, out_cap,
+                              out_off, flags);
+  if (rc) return rc;
+  c->hip_err.clear();
+  if (n_decoded) *n_decoded = 0;
+  if (bad_unit) *bad_unit = 0xffffffffu;
+  if (n_ranges == 0) {
+    if (out_off) out_off[0] = 0;
+    return FLATE_HIP_OK;
+  }
+  const uint32_t nr = n_ranges;
+  if (index[kGzSeekUnitsAt] == 0) {  // the empty file: every range is empty
+    for (uint32_t r = 0; r <= nr; ++r) out_off[r] = 0;
+    if (range_status)
+      for (uint32_t r = 0; r < nr; ++r) range_status[r] = 0;
+    return FLATE_HIP_OK;
+  }
+  try {
+    const bool dev = (flags & FLATE_HIP_DEVICE_PTRS) != 0;
+    const uint8_t *d_in = nullptr;
+    if ((rc = stage_input(c, in, in_len, flags, &d_in))) return rc;
+    const uint32_t n = (uint32_t)index[kGzSeekUnitsAt], m = (uint32_t)index[kGzSeekMembersAt],
+                   np = (uint32_t)index[kGzSeekPointsAt];
+    const size_t idx_words = (size_t)(index_words - kGzSeekHeadWords);
+    const uint64_t *h_munit = index + kGzSeekHeadWords + 2 * ((size_t)n + 1) + ((size_t)m + 1);
+    const uint64_t *h_point = h_munit + ((size_t)m + 1);
+
+    GzSeekParams GS{};
+    OneSeekParams &Q = GS.Q;
+    Q.n = n, Q.n_points = np, Q.span = index[kGzSeekSpanAt], Q.n_ranges = nr;
+    uint64_t *d_idx, *d_begin, *d_end;
+    FrameOne *d_one;
+    size_t o_back = 0, o_end = 0;
+    rc = carve(c, c->d_one_seek, [&](Carve &k) {
+      k.take(d_idx, idx_words);
+      k.take(d_begin, nr);
+      k.take(d_end, nr);
+      k.take(GS.rel, (size_t)n + 1);
+      k.take(d_one, 1);
+      k.take(Q.diff, (size_t)n + 1);
+      k.take(Q.rank, n);
+      k.take(Q.scratch_at, n);
+      k.take(Q.r_b, nr);
+      k.take(Q.r_len, nr);
+      k.take(Q.r_first, nr);
+      k.take(Q.r_last, nr);
+      k.take(Q.r_seg, nr);
+      k.take(Q.r_src, nr);
+      k.take(Q.sel_at, (size_t)n + 1);
+      o_back = k.at;
+      k.take(Q.head, 1);
+      k.take(GS.bad_member, 1);
+      k.take(Q.r_out_off, (size_t)nr + 1);
+      k.take(Q.r_rank_lo, nr);
+      k.take(Q.r_rank_hi, nr);
+      k.take(Q.sel_unit, n);
+      o_end = k.at;
+    });
+    if (rc) return rc;
+    Q.unit_bit = d_idx, Q.out_off = d_idx + ((size_t)n + 1);
+    GS.member_off = Q.out_off + ((size_t)n + 1), GS.member_unit = GS.member_off + ((size_t)m + 1);
+    Q.point_unit = GS.member_unit + ((size_t)m + 1);
+    Q.begin = d_begin, Q.end = d_end;
+    GS.in = d_in, GS.in_len = in_len, GS.m = m;
+    const size_t back_bytes = o_end - o_back;
+    const uint8_t *d_back = (const uint8_t *)c->d_one_seek.p + o_back;
+    HIP_TRY(c, hipMemcpyAsync(d_idx, index + kGzSeekHeadWords, idx_words * 8, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(d_begin, begin, (size_t)nr * 8, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(d_end, end, (size_t)nr * 8, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemsetAsync(Q.diff, 0, ((size_t)n + 1) * 4, c->stream));
+    HIP_TRY(c, hipMemsetAsync(GS.bad_member, 0xff, 4, c->stream));  // none
+    hipLaunchKernelGGL(gzfile_init_kernel, dim3(1), dim3(64), 0, c->stream, d_one, in_len);
+    hipLaunchKernelGGL(gzfile_seek_members_kernel, dim3((m + 255u) / 256u), dim3(256), 0, c->stream, GS);
+    hipLaunchKernelGGL(gzfile_seek_rel_kernel, dim3((n + 1u + 255u) / 256u), dim3(256), 0, c->stream, GS);
+    hipLaunchKernelGGL(one_seek_locate_kernel, dim3((nr + 255u) / 256u), dim3(256), 0, c->stream, Q);
+    hipLaunchKernelGGL(one_seek_select_kernel, dim3(1), dim3(1024), 0, c->stream, Q);
+    hipLaunchKernelGGL(one_seek_layout_kernel, dim3(1), dim3(1024), 0, c->stream, Q);
+    HIP_TRY(c, hipGetLastError());
+    std::vector<uint8_t> back(back_bytes);
+    HIP_TRY(c, hipMemcpyAsync(back.data(), d_back, back_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    auto got = [&](const auto *d) { return (decltype(d))(back.data() + ((const uint8_t *)d - d_back)); };  // d's host copy
+    const OneSeekHead RH = *got(Q.head);
+    const uint32_t missed = *got(GS.bad_member);
+    const uint32_t *r_lo = got(Q.r_rank_lo), *r_hi = got(Q.r_rank_hi), *sel = got(Q.sel_unit);
+    const uint32_t ns = RH.n_sel;
+    if (missed != 0xffffffffu) {  // some member's header is not where the index has it: nothing is decoded
+      for (uint32_t r = 0; r <= nr; ++r) out_off[r] = 0;
+      if (range_status)
+        for (uint32_t r = 0; r < nr; ++r) range_status[r] = FLATE_HIP_E_CORRUPT;
+      return FLATE_HIP_E_CORRUPT;
+    }
+    if (ns > n) {
+      c->hip_err = "gzfile ranges: more units selected than the file has";
+      return FLATE_HIP_E_INTERNAL;
+    }
+    memcpy(out_off, got(Q.r_out_off), ((size_t)nr + 1) * 8);
+    if (n_decoded) *n_decoded = ns;
+    if (range_status)
+      for (uint32_t r = 0; r < nr; ++r) range_status[r] = 0;
+    if (RH.out_total > out_cap) return FLATE_HIP_E_OUT_TOO_SMALL;  // (the size query too: nothing is decoded)
+    if (ns == 0 || RH.out_total == 0) return FLATE_HIP_OK;        // (no range holds a byte)
+
+    // the windows: the caller's device buffer, or the blocks of the selected window-bearing points uploaded into a
+    // staged copy
+    const uint8_t *d_windows = windows;
+    if (!dev && windows_bytes) {
+      if ((rc = ensure(c, c->d_one_seek_win, windows_bytes + 16))) return rc;
+      uint8_t *stage = (uint8_t *)c->d_one_seek_win.p;
+      d_windows = stage;
+      std::vector<uint32_t> bs;  // the blocks of the selected points, rising
+      uint32_t p = 0, j = 0;     // j: the members whose first unit is at or in front of the point's
+      for (uint32_t i = 0; i < ns && p < np; ++i) {
+        while (p < np && h_point[p] < sel[i]) ++p;
+        if (p >= np || h_point[p] != sel[i]) continue;
+        while (j < m && h_munit[j] <= sel[i]) ++j;
+        if (h_munit[j - 1u] != sel[i]) bs.push_back(p - j);
+      }
+      for (size_t a = 0; a < bs.size();) {  // neighbours in the index travel as one copy
+        size_t b = a + 1;
+        while (b < bs.size() && bs[b] == bs[b - 1] + 1u) ++b;
+        const uint64_t at = (uint64_t)bs[a] * kSeekWindow, len = (uint64_t)(b - a) * kSeekWindow;
+        HIP_TRY(c, hipMemcpyAsync(stage + at, windows + at, len, hipMemcpyHostToDevice, c->stream));
+        a = b;
+      }
+    }
+
+    const uint32_t per_round = unit_per_round(c, ns);
+    OneDecParams D{};
+    GzSeekRoundParams Z{};
+    OneSeekRoundParams &S = Z.S;
+    UnitResults dec;
+    if ((rc = seek_rounds_carve(c, D, S, dec, ns, per_round))) return rc;
+    // TAIL by the index's rule, not the context's option; a unit's history is what its own member has produced in front
+    // of it (rel)
+    const uint32_t stored = index[kGzSeekRuleAt] == kSeekRuleStored ? 1u : 0u;
+    if ((rc = unit_dec_params(c, D, d_in, d_one, Q.unit_bit, GS.rel, stored, false))) return rc;
+    D.unit_list = Q.sel_unit;
+    S.Q = Q;
+    S.windows = d_windows;
+    Z.member_unit = GS.member_unit;
+    Z.m = m;
+    Z.rel = GS.rel;
+    auto seeds = [&](uint32_t i0, uint32_t count) {
+      S.i0 = i0, S.count = count;
+      hipLaunchKernelGGL(gzfile_seek_seed_kernel, dim3((count + 255u) / 256u), dim3(256), 0, c->stream, Z);
+      hipLaunchKernelGGL(gzfile_seek_load_kernel, dim3(seek_load_blocks(count)), dim3(256), 0, c->stream, Z);
+      return FLATE_HIP_OK;
+    };
+    // (bits are counted from the file's first byte and nothing at or behind the last trailer is read)
+    const SeekRangesOut O{out, nr, RH.out_total, RH.scratch_total, r_lo, r_hi, sel, range_status, bad_unit, dev};
+    return seek_ranges_decode(c, D, S, dec, per_round, ns, d_in, in_len - kGzipTrailerLen, O, seeds);
+  } catch (const std::exception &e) {
+    c->hip_err = e.what();
+    return FLATE_HIP_E_INTERNAL;
+  }
+}
+
+}  // extern "C"
+
+// ---- the LONG entries of a ZIP archive through units (zip_units_kernels.hip, zip_units_rule.h) ----
+// gzfile_discover and flate_hip_gzfile_read's rounds with the format's own glue: the hull as the raw stream, B nodes
+// from the directory, the link that hops from entry to entry, pieces in ZIP's slots.  Read-backs: the candidate count;
+// the head words with entry_unit; the rounds' first_bad / decode_bad (g).
+int flate_host::zip_units_decode(flate_hip_ctx *c, const uint8_t *d_in, uint64_t hull_lo, uint64_t hull_hi,
+                                 const std::vector<ZuEntry> &L, const std::vector<ZuRange> &R, uint8_t *d_out,
+                                 uint64_t total, uint32_t *g, ZipUnitsDecParams &G, uint32_t *n_units, uint32_t *n_cand) {
+  int rc;
+  *g = 0, *n_units = 0, *n_cand = 0;
+  G = ZipUnitsDecParams{};
+  ZipUnitsParams P{};
+  OneParams PA{};
+  ChainParams &C = P.O.C;
+  const uint8_t *h_in = d_in + hull_lo;  // every offset below is counted from here
+  const uint64_t hull_len = hull_hi - hull_lo;
+  const uint32_t nb = (uint32_t)L.size();
+  if (nb == 0 || R.size() != L.size() || hull_len == 0) return FLATE_HIP_E_INTERNAL;
+  uint32_t n_tiles = 0;
+  if ((rc = tiles_for(h_in, 0, hull_len, &n_tiles))) return rc;
+  OneHead *head_a;
+  ZuEntry *dL;
+  ZuRange *dR;
+  rc = carve(c, c->d_zip_units_tiles, [&](Carve &k) {
+    k.take(P.O.head, 1);
+    k.take(P.zh, 1);
+    k.take(P.O.one, 1);
+    k.take(head_a, 1);
+    k.take(PA.C.tile_cnt, (size_t)n_tiles + 1);
+    k.take(dL, nb);
+    k.take(dR, nb);
+    k.take(P.entry_unit, (size_t)nb + 2);
+  });
+  if (rc) return rc;
+  P.L = dL, P.R = dR;
+  HIP_TRY(c, hipMemcpyAsync(dL, L.data(), (size_t)nb * sizeof(ZuEntry), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(dR, R.data(), (size_t)nb * sizeof(ZuRange), hipMemcpyHostToDevice, c->stream));
+  C.in = PA.C.in = h_in;
+  C.in_len = PA.C.in_len = hull_len;
+  C.n_tiles = PA.C.n_tiles = n_tiles;
+  C.head = &P.O.head->h;
+  P.O.unit_max = PA.unit_max = c->one_unit_max;
+  P.O.stored_units = PA.stored_units = c->one_stored_units;
+  PA.C.head = &head_a->h;
+  PA.head = head_a;
+  PA.one = P.O.one;
+  hipLaunchKernelGGL(one_init_kernel, dim3(1), dim3(64), 0, c->stream, P.O.one, hull_len);  // the hull is the raw stream
+  one_find_launch(c, true, n_tiles, PA);
+  hipLaunchKernelGGL(chain_scan_kernel, dim3(1), dim3(1024), 0, c->stream, PA.C);
+  HIP_TRY(c, hipGetLastError());
+  OneHead HA{};
+  HIP_TRY(c, hipMemcpyAsync(&HA, head_a, sizeof HA, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  const uint32_t na = HA.h.n_cand;
+  if ((uint64_t)na + nb > 0x7ffffff0ull) return FLATE_HIP_E_TOO_LARGE;  // (the count saturates at 2^32 - 1)
+  const uint32_t cap = na + nb;
+  if ((rc = chain_size(C, cap)) || (rc = chain_size(PA.C, na))) return rc;
+  P.n_a = na;
+  P.n_b = nb;
+  *n_cand = na;
+
+  const size_t n = cap;
+  rc = carve(c, c->d_zip_units, [&](Carve &k) {
+    k.take(C.cand_off, n);
+    k.take(P.O.probe, n);
+    k.take(C.jump[0], n + 2);
+    k.take(C.jump[1], n + 2);
+    k.take(C.path, C.path_len);
+    k.take(P.O.usize, n);
+    k.take(C.member_off, n + 1);
+    k.take(C.out_off, n + 1);
+    k.take(P.u_start, n + 1);
+    k.take(P.u_final, n);
+    k.take(P.u_entry, n + 1);
+    k.take(P.rel_off, n + 1);
+  });
+  if (rc) return rc;
+  PA.C.cand_off = C.cand_off;
+  if (na) one_find_launch(c, false, n_tiles, PA);
+  hipLaunchKernelGGL(zip_units_bits_kernel, dim3((nb + 255) / 256), dim3(256), 0, c->stream, P);
+  one_probe_launch(c, cap, P.O, 0u);
+  const uint32_t node_blocks = (uint32_t)(((uint64_t)cap + 2 + 255) / 256);
+  hipLaunchKernelGGL(zip_units_link_kernel, dim3(node_blocks), dim3(256), 0, c->stream, P);
+  for (uint32_t j = 0; (1u << j) < C.path_len; ++j)
+    hipLaunchKernelGGL(chain_round_kernel, dim3(node_blocks), dim3(256), 0, c->stream, C, j);
+  hipLaunchKernelGGL(zip_units_finish_kernel, dim3((C.path_len + 255) / 256), dim3(256), 0, c->stream, P);
+  hipLaunchKernelGGL(one_out_scan_kernel, dim3(1), dim3(1024), 0, c->stream, P.O);
+  hipLaunchKernelGGL(zip_units_entries_kernel, dim3(1), dim3(1024), 0, c->stream, P);
+  hipLaunchKernelGGL(zip_units_rel_kernel, dim3(node_blocks), dim3(256), 0, c->stream, P);
+  HIP_TRY(c, hipGetLastError());
+  OneHead H{};
+  ZipUnitsHead Z{};
+  std::vector<uint64_t> entry_unit((size_t)nb + 2, 0);
+  HIP_TRY(c, hipMemcpyAsync(&H, P.O.head, sizeof H, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(&Z, P.zh, sizeof Z, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(entry_unit.data(), P.entry_unit, ((size_t)nb + 2) * 8, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  if (H.h.n_members > cap || Z.n_complete > nb) return FLATE_HIP_E_INTERNAL;
+  // the entries the discovery finds GOOD, and their units: the only ones that are decoded
+  const uint32_t g_disc = Z.n_complete < Z.first_unfit ? Z.n_complete : Z.first_unfit;
+  G.P = P;
+  if (g_disc == 0) return FLATE_HIP_OK;
+  if (entry_unit[g_disc] > H.h.n_members) return FLATE_HIP_E_INTERNAL;
+  const uint32_t n_dec = (uint32_t)entry_unit[g_disc];
+
+  const uint32_t per_round = unit_per_round(c, n_dec);
+  const size_t pieces = 2 * (size_t)per_round;
+  OneDecParams &D = G.D;
+  UnitResults dec;
+  rc = unit_rounds_carve(c, D, n_dec, per_round, [&](Carve &k) { unit_pieces_take(k, D, &dec, pieces); });
+  if (rc) return rc;
+  rc = carve(c, c->d_zip_units_dec, [&](Carve &k) {
+    k.take(G.seed, per_round);
+    k.take(G.p_bit_off, pieces);
+    k.take(G.p_bit_end, pieces);
+    k.take(G.du_status, per_round);
+    k.take(G.du_out_len, per_round);
+  });
+  if (rc) return rc;
+  if ((rc = unit_dec_params(c, D, h_in, P.O.one, C.member_off, C.out_off, P.O.stored_units, true))) return rc;
+  unit_verdict_params(D, total, UnitResults{G.du_status, G.du_out_len, nullptr}, P.O.head, FLATE_HIP_WRAP_RAW, hull_len);
+  G.dp_status = dec.status;
+  G.dp_out_len = dec.out_len;
+  // the pieces and the seeds of the round (every entry's first unit is one)
+  auto round_pieces = [&](uint32_t, uint32_t count) {
+    hipLaunchKernelGGL(zip_units_pieces_kernel, dim3((count + 1u + 255u) / 256u), dim3(256), 0, c->stream, G);
+    return FLATE_HIP_OK;
+  };
+  uint32_t e_at = 0;  // the entry of the round's first unit
+  auto decode = [&](uint32_t u0, uint32_t count) {
+    // the round's pieces: its units and a gap in front of every entry that starts behind its first unit
+    while (entry_unit[e_at + 1u] <= u0) ++e_at;
+    uint32_t e_hi = e_at;
+    while (e_hi + 1u < g_disc && entry_unit[e_hi + 1u] < (uint64_t)u0 + count) ++e_hi;
+    const uint32_t n_pieces = count + (e_hi - e_at);
+    const uint32_t unit_blocks = (count + 1u + 255u) / 256u;
+    const int r = unit_decode(c, unit_decode_params(D, h_in, hull_len, G.p_bit_off, G.p_bit_end, false, n_pieces, d_out,
+                                                    D.p_out_off, dec));
+    if (r) return r;
+    hipLaunchKernelGGL(zip_units_fold_kernel, dim3(unit_blocks), dim3(256), 0, c->stream, G);
+    OneDecParams K = D;  // the check: status 0 and exactly out_off[k + 1] - out_off[k] bytes
+    K.p_out_off = C.out_off + u0;
+    hipLaunchKernelGGL(one_check_kernel, dim3(unit_blocks), dim3(256), 0, c->stream, K);
+    return FLATE_HIP_OK;
+  };
+  // TAIL with the entry-relative offsets: a unit's history is what its own entry has produced in front of it
+  if ((rc = unit_rounds(c, D, P.rel_off, G.seed, 0, n_dec, n_dec, per_round, unit_no_hook, round_pieces, decode))) return rc;
+  // the one small read-back of g
+  OneDecHead DH{};
+  HIP_TRY(c, hipMemcpyAsync(&DH, D.dh, sizeof DH, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  const uint32_t bad_unit = DH.first_bad < DH.decode_bad ? DH.first_bad : DH.decode_bad;
+  *g = zip_units_served(entry_unit.data(), g_disc, bad_unit);
+  *n_units = (uint32_t)entry_unit[*g];
+  return FLATE_HIP_OK;
+}

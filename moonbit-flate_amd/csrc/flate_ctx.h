@@ -1,6 +1,6 @@
 // flate_ctx.h -- the ctx and the host-side helpers that more than one host file of the C ABI uses (private, host
-// only).  Everything in flate_host but its templates is DEFINED in flate_api.hip; flate_api_deflate.hip (the encode calls) and
-// flate_api_inflate.hip (the decode calls) are the users.
+// only).  Everything in flate_host but its templates is DEFINED in flate_api.hip unless its comment names another file;
+// flate_api_deflate.hip (the encode calls), flate_api_inflate.hip and flate_api_units.hip (the decode calls) are the users.
 // (checksum.hip and gather.hip see the ctx through the flate::ctx_* accessors of flate_kernels.h.)
 #pragma once
 
@@ -200,6 +200,16 @@ int carve(flate_hip_ctx *c, DevBuf &b, Lay lay) {
 }
 // in[0, in_len) on the device: the caller's buffer, or the ctx's staged copy of it
 int stage_input(flate_hip_ctx *c, const uint8_t *in, uint64_t in_len, uint32_t flags, const uint8_t **d_in);
+// The route's kernel over the n streams of I, inside the inflate stage's events (flate_api_inflate.hip: the only place
+// that knows the decoder kernels).  dict: some stream starts from a preset dictionary (the dictionary builds).
+int launch_decoders(flate_hip_ctx *c, const flate::InflateRoute &rt, flate::InfParams I, bool dict);
+// The gather (bgzf_gather_kernel; flate_api_inflate.hip): range r's run scratch[r_src[r], ...) to d_out[r_out_off[r],
+// r_out_off[r + 1]).  piece_bytes: the bytes of all runs, which with the ranges' fixed cost cut the work into
+// workgroups -- more of them than a grid holds is FLATE_HIP_E_TOO_LARGE (for the PACK gathers of the two seek-index
+// builds, which had no such check of their own, out of reach: a round's windows are at most 65536 * 32 KiB).  The caller
+// checks the launch.
+int ranges_gather(flate_hip_ctx *c, const uint8_t *scratch, uint8_t *d_out, const uint64_t *r_out_off, const uint64_t *r_src,
+                  uint32_t n_ranges, uint64_t piece_bytes);
 
 // ---- what the four discoveries share on the host (flate_kernels.h: THE DISCOVERY SKELETON) ----
 // the tiles over the offsets [lo, lo + len) of the device buffer d_in, or FLATE_HIP_E_TOO_LARGE

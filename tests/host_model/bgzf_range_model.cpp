@@ -6,6 +6,9 @@
 //                                  n_ranges, begin[n_ranges], end[n_ranges] (u64 each).  The index comes from the serial
 //                                  walk (bgzf_rule.h).  One line per case: "status b e first last" per range, ';' between
 //   bgzf_range_model checks        one line per argument-check call: name value
+//   bgzf_range_model statuses FILE the status rule behind the decode (range_statuses).  FILE = text, per case the numbers
+//                                  ns nr with_skip with_status, st[ns], r_lo[nr], r_hi[nr], the statuses the ranges start
+//                                  with [nr], skip[nr].  One line per case: the return value, then the ranges' statuses
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -55,6 +58,34 @@ static int locate_file(const char *path) {
   return 0;
 }
 
+static int statuses_file(const char *path) {
+  FILE *f = fopen(path, "r");
+  if (!f) return 2;
+  unsigned ns, nr, with_skip, with_status;
+  while (fscanf(f, "%u %u %u %u", &ns, &nr, &with_skip, &with_status) == 4) {
+    // (exact allocations: a read outside an array is a heap overflow the sanitizer reports)
+    int32_t *st = (int32_t *)malloc(ns ? ns * 4ull : 1), *rs = (int32_t *)malloc(nr ? nr * 4ull : 1),
+            *skip = (int32_t *)malloc(nr ? nr * 4ull : 1);
+    uint32_t *lo = (uint32_t *)malloc(nr ? nr * 4ull : 1), *hi = (uint32_t *)malloc(nr ? nr * 4ull : 1);
+    for (unsigned i = 0; i < ns; ++i)
+      if (fscanf(f, "%d", &st[i]) != 1) return 2;
+    for (unsigned r = 0; r < nr; ++r)
+      if (fscanf(f, "%u", &lo[r]) != 1) return 2;
+    for (unsigned r = 0; r < nr; ++r)
+      if (fscanf(f, "%u", &hi[r]) != 1) return 2;
+    for (unsigned r = 0; r < nr; ++r)
+      if (fscanf(f, "%d", &rs[r]) != 1) return 2;
+    for (unsigned r = 0; r < nr; ++r)
+      if (fscanf(f, "%d", &skip[r]) != 1) return 2;
+    printf("%u", range_statuses(st, ns, lo, hi, nr, with_status ? rs : nullptr, with_skip ? skip : nullptr));
+    for (unsigned r = 0; r < nr; ++r) printf(" %d", rs[r]);
+    printf("\n");
+    free(st), free(rs), free(skip), free(lo), free(hi);
+  }
+  fclose(f);
+  return 0;
+}
+
 static int checks() {
   uint8_t b[4] = {0};
   uint64_t lo[2] = {1, 5}, hi[2] = {1, 9}, back[2] = {1, 4}, off[3] = {0, 0, 0};
@@ -83,6 +114,7 @@ static int checks() {
 int main(int argc, char **argv) {
   if (argc == 3 && !strcmp(argv[1], "locate")) return locate_file(argv[2]);
   if (argc == 2 && !strcmp(argv[1], "checks")) return checks();
-  fprintf(stderr, "usage: %s locate FILE | checks\n", argv[0]);
+  if (argc == 3 && !strcmp(argv[1], "statuses")) return statuses_file(argv[2]);
+  fprintf(stderr, "usage: %s locate FILE | checks | statuses FILE\n", argv[0]);
   return 2;
 }

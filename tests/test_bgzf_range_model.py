@@ -2,7 +2,8 @@
 moonbit-flate_amd/csrc/bgzf_range_rule.h -- the one function the locate kernel and the library's host code compile --
 and api_checks.h's bgzf_ranges_args, built with g++ into a stand-alone program under AddressSanitizer and UBSan, run
 over every well-formed file of the corpus (index and range arrays in allocations of exactly their size) with range
-lists that sit on every edge, and compared with the Python model tests/bgzf_range_ref.py."""
+lists that sit on every edge, and compared with the Python model tests/bgzf_range_ref.py.  The same program runs
+range_statuses, the status rule behind the decode of every ranges call, over hand-made cases."""
 import os
 import struct
 import subprocess
@@ -103,3 +104,62 @@ def test_argument_checks(exe):
         "kind_2": INVALID, "kind_max": INVALID, "flag_go": INVALID, "flag_size_only": INVALID,
         "backwards_bytes": INVALID, "backwards_virtual": INVALID, "backwards_not_reached": 0,
     }
+
+
+CORRUPT, EOF_ = -3, -4  # (any two distinct non-zero statuses: the rule copies them)
+
+# (what, st, [(r_lo, r_hi)], the statuses the ranges start with, skip or None)
+STATUS_CASES = [
+    ("no bad unit", [0, 0, 0, 0, 0, 0, 0], [(0, 2), (2, 5), (5, 7)], [0, 0, 0], None),
+    ("bad in the first range", [0, CORRUPT, 0, 0, 0, 0, 0], [(0, 2), (2, 5), (5, 7)], [0, 0, 0], None),
+    ("bad in a middle range", [0, 0, 0, CORRUPT, 0, 0, 0], [(0, 2), (2, 5), (5, 7)], [0, 0, 0], None),
+    ("bad in the last range, its last unit", [0, 0, 0, 0, 0, 0, EOF_], [(0, 2), (2, 5), (5, 7)], [0, 0, 0], None),
+    ("two ranges share the bad unit", [0, 0, CORRUPT, 0, 0], [(0, 3), (2, 5), (3, 5)], [0, 0, 0], None),
+    ("the first of two bad units in a range wins", [0, EOF_, CORRUPT, 0], [(0, 4), (2, 4)], [0, 0], None),
+    ("an empty range keeps its status", [CORRUPT, 0, 0], [(0, 0), (1, 1), (3, 3), (0, 3)], [0, 7, 0, 0], None),
+    ("a range outside the decoded units keeps its status", [CORRUPT, 0], [(0, 3), (0, 2)], [5, 0], None),
+    ("a range settled before the decode keeps its status", [CORRUPT, 0, 0], [(0, 2), (0, 2), (1, 3)], [-1, 0, 0], [-1, 0, 0]),
+    ("skip given, nothing skipped", [0, 0, EOF_], [(0, 3), (2, 3)], [0, 0], [0, 0]),
+    ("no status array", [0, CORRUPT, 0], [(0, 3)], [9], None),
+    ("no units, no ranges", [], [], [], None),
+    ("unsorted, nested and repeated ranges", [0, 0, CORRUPT, 0, EOF_, 0], [(4, 6), (0, 6), (3, 4), (0, 6), (1, 3)], [0, 0, 0, 0, 0], None),
+]
+
+
+def _statuses_model(st, ranges, start, skip):
+    """The rule, the slow way: every range looks at every unit it touches."""
+    out = list(start)
+    for r, (lo, hi) in enumerate(ranges):
+        if (skip and skip[r]) or hi > len(st):
+            continue
+        bad = [st[i] for i in range(lo, hi) if st[i]]
+        if bad:
+            out[r] = bad[0]
+    first = [i for i, s in enumerate(st) if s]
+    return (first[0] if first else len(st)), out
+
+
+def test_status_rule_behind_the_decode(exe, tmp_path):
+    text = ""
+    for what, st, ranges, start, skip in STATUS_CASES:
+        with_status = 0 if what == "no status array" else 1
+        nums = [len(st), len(ranges), 1 if skip is not None else 0, with_status] + st + [a for a, _ in ranges] + \
+               [b for _, b in ranges] + start + (skip if skip is not None else [0] * len(ranges))
+        text += " ".join(str(x) for x in nums) + "\n"
+    path = tmp_path / "statuses.txt"
+    path.write_text(text)
+    lines = subprocess.run([exe, "statuses", str(path)], check=True, capture_output=True, text=True).stdout.splitlines()
+    assert len(lines) == len(STATUS_CASES)
+    for (what, st, ranges, start, skip), line in zip(STATUS_CASES, lines):
+        got = [int(x) for x in line.split()]
+        first, want = _statuses_model(st, ranges, start, skip)
+        if what == "no status array":
+            want = list(start)
+        assert got[0] == first, what
+        assert got[1:] == want, what
+    # what the cases are for, spelled out
+    by = dict((c[0], _statuses_model(*c[1:])) for c in STATUS_CASES)
+    assert by["no bad unit"] == (7, [0, 0, 0])
+    assert by["bad in a middle range"] == (3, [0, CORRUPT, 0])
+    assert by["two ranges share the bad unit"] == (2, [CORRUPT, CORRUPT, 0])
+    assert by["a range settled before the decode keeps its status"] == (0, [-1, CORRUPT, 0])
