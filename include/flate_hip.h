@@ -866,6 +866,72 @@ int flate_hip_inflate_one_index(flate_hip_ctx *ctx, const uint8_t *in, uint64_t 
                                 uint64_t *out_bytes, uint32_t *n_candidates, int32_t *status, int64_t *err_off,
                                 uint32_t flags);
 
+/* -- One long stream read in PARTS: flate_hip_inflate_one through bounded buffers ------
+ * For a caller that holds a long raw, zlib or gzip stream a piece at a time (a Reader over a multi-gigabyte .gz): the
+ * conventions of flate_hip_inflate_stream_read, the speed of flate_hip_inflate_one.  One call IS flate_hip_inflate_one
+ * on the part in[0, in_len) of the stream, started where the last call stopped; between calls the handle keeps the bit
+ * where the next unit starts, the 32 KiB window in front of it (on the device) and the running checksum (on the device).
+ *
+ * open: wrap is FLATE_HIP_WRAP_RAW / _ZLIB / _GZIP with flate_hip_inflate_one's header rules; flags is 0 or
+ * FLATE_HIP_DEVICE_PTRS (in and out of every read are device buffers), fixed for the handle's life; anything else, or a
+ * NULL ctx or result pointer, is FLATE_HIP_E_INVALID before any HIP call.  The handle records the unit rule (option
+ * "one_stored_units") and "one_unit_max" as the ctx has them at open and uses them whatever the ctx says later, as a
+ * seek index does.  reset: a fresh stream on the same handle, same wrap, flags and options.  The ctx must outlive it.
+ *
+ * read: in[0, in_len) BEGINS with the bytes the last call left unused (*in_used < in_len: move them to the front and
+ * append); final_in != 0: no bytes follow.  Returns FLATE_HIP_OK (call again), FLATE_HIP_STREAM_END (the final block
+ * decoded and the trailer judged, reported with the last bytes; sticky) or a negative status, which is sticky -- every
+ * later call returns it with the same *err_off -- except FLATE_HIP_E_OUT_TOO_SMALL, FLATE_HIP_E_INVALID (NULL reader /
+ * in with in_len > 0 / out with out_cap > 0 / in_used / out_len, before any HIP call) and a failure of the runtime or of
+ * an allocation (FLATE_HIP_E_HIP) in front of the point where the call begins to move the handle's device words: such a
+ * call has changed nothing and may be repeated.  Behind that point -- the part's checksum, the join, the result words,
+ * the window's carry, the download -- FLATE_HIP_E_HIP and FLATE_HIP_E_INTERNAL end the handle (sticky), because running
+ * sum or window may be ahead of the host's state; reset makes it usable again.  err_off and n_units may be NULL.
+ *   ONE CALL.  Discovery runs over the part with the chain's root at the carried bit b0 (0..7) of the part's first raw
+ *   byte: that bit is candidate 0, the bits in front of it in that byte are none.  Every unit whose end lies inside the
+ *   part -- the next unit's header, or the final block -- is COMPLETE.  The unit that the part's end cuts is not: on a
+ *   part that is not final it is left for the next call; on a final part it is judged as the whole call judges it,
+ *   FLATE_HIP_E_UNEXPECTED_EOF with the bytes in front delivered.  FLATE_HIP_E_CORRUPT inside a part is the stream's
+ *   verdict (the bits read are true stream bits) and comes with the bytes in front of it, as in the whole call.  The
+ *   call delivers the longest prefix of complete units whose bytes fit out_cap (with the part's verdict behind them, if
+ *   everything in front of it fits), decoded in rounds through the unchanged TAIL / COMPOSE / RESOLVE / DECODE with the
+ *   handle's window as R[0] of the first round (zeros on the first part); the window behind the last delivered unit
+ *   goes back into the handle.  *in_used = the byte that holds the first bit of the first undelivered unit, whose place
+ *   in that byte becomes b0; *out_len = the bytes delivered; *n_units = the complete units delivered.  Units that did not
+ *   fit, and the cut unit, are simply discovered again by the next call.
+ *     At least one complete unit and not even the first fits: FLATE_HIP_E_OUT_TOO_SMALL with *out_len = the first
+ *     unit's size, the state unchanged.  No complete unit on a part that is not final: FLATE_HIP_OK with *in_used =
+ *     *out_len = 0, the caller appends more; the same with in_len >= "one_unit_max", or a unit beyond it, is
+ *     FLATE_HIP_E_TOO_LARGE.  A RUN OF FIXED BLOCKS -- or of stored blocks with "one_stored_units" at 0 -- IS ONE UNIT:
+ *     it needs a part that holds it whole (and the three bits of the header behind it).
+ *   HISTORY.  The distance rule uses what the STREAM has produced, not the part: TAIL and DECODE see min(32768,
+ *   produced before the part + out_off[k] + bytes produced), so a distance that reaches in front of the stream in a
+ *   later part of a stream that has produced less than 32 KiB fails at the serial offset.
+ *   OFFSETS.  *err_off counts from the raw stream's first byte over all parts; a trailer that does not match reports
+ *   the member's length in bytes, as the whole call reports in_len.
+ *   CONTAINER.  The header is read on the first part; a header that is refused only because the part ends inside it is
+ *   FLATE_HIP_OK with nothing used on a part that is not final (csrc/one_parts_rule.h: the rule's third answer), and a
+ *   bad header on a final one.  On a final part the trailer's bytes are cut off the raw range as in the whole call; on
+ *   any other part the raw range runs to the part's end.  When the final block lies in a part but the 4 or 8 trailer
+ *   bytes do not lie in it whole, the call delivers the bytes, *in_used points behind the final block rounded up to a
+ *   byte, it returns FLATE_HIP_OK, and the next call judges the trailer once it has the bytes (final_in with too few:
+ *   FLATE_HIP_E_UNEXPECTED_EOF).  The checksum of each part's delivered bytes is computed by the checksum kernels and
+ *   joined to the running sum on the device (as two pieces, of the bytes produced before and of *out_len); the verdict
+ *   kernel compares the joined sum, and for gzip the total length mod 2^32, with the trailer.  Bytes behind the trailer
+ *   are not looked at: *in_used stops behind it.
+ *   Host pointers: the part is uploaded once and out[0, *out_len) downloaded once per call.  With device pointers
+ *   nothing outside out[0, *out_len) is written.  Per call the host waits for the discovery's two read-backs and one
+ *   read-back of the result words.
+ *   Out of scope: a file of several members read in parts (flate_hip_gzfile_read takes the whole file); the parallel
+ *   writer in parts; overlapping the copy of part k + 1 with the decode of part k. */
+typedef struct flate_hip_one_reader flate_hip_one_reader;
+int flate_hip_one_reader_open(flate_hip_ctx *ctx, uint32_t wrap, uint32_t flags, flate_hip_one_reader **reader);
+int flate_hip_one_reader_read(flate_hip_one_reader *reader, const uint8_t *in, uint64_t in_len, int final_in,
+                              uint8_t *out, uint64_t out_cap, uint64_t *in_used, uint64_t *out_len, int64_t *err_off,
+                              uint32_t *n_units);
+int flate_hip_one_reader_reset(flate_hip_one_reader *reader);
+void flate_hip_one_reader_free(flate_hip_one_reader *reader);
+
 /* -- Seek index for one long stream: build once, read ranges --------------------------
  * flate_hip_inflate_one pays the whole discovery on every call.  A SEEK INDEX keeps it: flate_hip_inflate_one_seek_index
  * builds one, flate_hip_inflate_one_ranges reads byte ranges of the stream's output through it and decodes only the

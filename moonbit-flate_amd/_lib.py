@@ -89,6 +89,10 @@ def _signatures():
         "flate_hip_gzfile_last_route": (i, [vp, u32p, u32p, u64p]),
         "flate_hip_deflate_fast_grouped_framed": (i, [vp, vp, vp, u32, vp, u32, u32, vp, u64, vp, vp, u32]),
         "flate_hip_zip_write_last_route": (i, [vp, u32p, u32p]),
+        "flate_hip_one_reader_open": (i, [vp, u32, u32, vpp]),
+        "flate_hip_one_reader_read": (i, [vp, vp, u64, i, vp, u64, u64p, u64p, i64p, u32p]),
+        "flate_hip_one_reader_reset": (i, [vp]),
+        "flate_hip_one_reader_free": (None, [vp]),
     }
 
 
@@ -106,7 +110,8 @@ MAY_BE_MISSING = [
     "flate_hip_gzfile_index", "flate_hip_gzfile_read", "flate_hip_gzfile_seek_index", "flate_hip_gzfile_ranges",
     "flate_hip_zip_bound", "flate_hip_zip_write", "flate_hip_zip_index", "flate_hip_zip_read",
     "flate_hip_zip_last_route", "flate_hip_gzfile_last_route", "flate_hip_deflate_fast_grouped_framed",
-    "flate_hip_zip_write_last_route",
+    "flate_hip_zip_write_last_route", "flate_hip_one_reader_open", "flate_hip_one_reader_read",
+    "flate_hip_one_reader_reset", "flate_hip_one_reader_free",
 ]
 
 _lib = None

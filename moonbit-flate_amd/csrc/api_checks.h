@@ -6,6 +6,7 @@
 
 #include "flate_hip.h"
 #include "gzfile_seek_rule.h"
+#include "one_parts_rule.h"
 #include "seek_index_rule.h"
 #include "splice_rule.h"
 
@@ -188,6 +189,20 @@ inline int one_args(const uint8_t *in, uint64_t in_len, uint32_t wrap, const uin
   if (!out_len || !status || (in_len && !in) || (out_cap && !out)) return FLATE_HIP_E_INVALID;
   if (wrap > FLATE_HIP_WRAP_GZIP) return FLATE_HIP_E_INVALID;
   return (flags & ~FLATE_HIP_DEVICE_PTRS) ? FLATE_HIP_E_INVALID : FLATE_HIP_OK;
+}
+
+// flate_hip_one_reader_open / _read (one_parts_rule.h holds the checks; its status words are this header's)
+static_assert(kPartsInvalid == FLATE_HIP_E_INVALID && kPartsOutTooSmall == FLATE_HIP_E_OUT_TOO_SMALL &&
+                  kPartsCorrupt == FLATE_HIP_E_CORRUPT && kPartsTooLarge == FLATE_HIP_E_TOO_LARGE &&
+                  kPartsEof == FLATE_HIP_E_UNEXPECTED_EOF && kPartsStreamEnd == FLATE_HIP_STREAM_END &&
+                  kPartsGzip == FLATE_HIP_WRAP_GZIP && kPartsZlib == FLATE_HIP_WRAP_ZLIB,
+              "one_parts_rule.h restates flate_hip.h");
+inline int one_reader_open_args(const void *ctx, uint32_t wrap, uint32_t flags, const void *reader) {
+  return one_parts_open_args(ctx, wrap, flags, FLATE_HIP_DEVICE_PTRS, reader);
+}
+inline int one_reader_read_args(const void *reader, const uint8_t *in, uint64_t in_len, const uint8_t *out, uint64_t out_cap,
+                                const uint64_t *in_used, const uint64_t *out_len) {
+  return one_parts_read_args(reader, in, in_len, out, out_cap, in_used, out_len);
 }
 
 // ---- a gzip file of any members (flate_hip_gzfile_index / _read) ----

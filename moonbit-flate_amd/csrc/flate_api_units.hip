@@ -21,7 +21,19 @@ using namespace flate_host;
 namespace {
 
 // FIND's count pass or fill pass over n_tiles tiles, in the build of P's unit rule (option "one_stored_units")
-void one_find_launch(flate_hip_ctx *c, bool count, uint32_t n_tiles, const OneParams &P) {
+// parts: the builds whose chain starts at bit FrameOne::b0 (a stream read in parts)
+void one_find_launch(flate_hip_ctx *c, bool count, uint32_t n_tiles, const OneParams &P, bool parts = false) {
+  if (parts) {
+    if (count && P.stored_units)
+      hipLaunchKernelGGL((one_count_kernel<true, true>), dim3(n_tiles), dim3(256), 0, c->stream, P);
+    else if (count)
+      hipLaunchKernelGGL((one_count_kernel<false, true>), dim3(n_tiles), dim3(256), 0, c->stream, P);
+    else if (P.stored_units)
+      hipLaunchKernelGGL((one_fill_kernel<true, true>), dim3(n_tiles), dim3(256), 0, c->stream, P);
+    else
+      hipLaunchKernelGGL((one_fill_kernel<false, true>), dim3(n_tiles), dim3(256), 0, c->stream, P);
+    return;
+  }
   if (count && P.stored_units)
     hipLaunchKernelGGL(one_count_kernel<true>, dim3(n_tiles), dim3(256), 0, c->stream, P);
   else if (count)
@@ -69,15 +81,22 @@ void one_parse_launch(flate_hip_ctx *c, const uint8_t *d_in, uint64_t in_len, Fr
 // index_cap != 0: the first min(index_cap, candidates + 1) entries of unit_bit / out_off come back into `index` (the
 // two arrays one after the other) in the same read-back as H -- the units are a subset of the candidates, so what fits
 // the caller's arrays is known before the chain is.
+// part != null: d_in[0, in_len) is one PART of a stream read in parts (flate_hip_one_reader_read) -- the handle's unit
+// rule, one_part_init_kernel in the parse kernels' place, the chain's root at bit part->b0.
+struct OnePart {
+  uint64_t unit_max;      // the handle's "one_unit_max" and "one_stored_units", recorded at open
+  uint32_t stored_units;
+  uint32_t b0, first, final_in;
+};
 int one_discover(flate_hip_ctx *c, const uint8_t *d_in, uint64_t in_len, uint32_t wrap, uint64_t index_cap, OneHead &H,
-                 OneParams &P, std::vector<uint64_t> &index) {
+                 OneParams &P, std::vector<uint64_t> &index, const OnePart *part = nullptr) {
   int rc;
   P = OneParams{};
   ChainParams &C = P.C;
   C.in = d_in;
   C.in_len = in_len;
-  P.unit_max = c->one_unit_max;
-  P.stored_units = c->one_stored_units;
+  P.unit_max = part ? part->unit_max : c->one_unit_max;
+  P.stored_units = part ? part->stored_units : c->one_stored_units;
   if ((rc = tiles_for(d_in, 0, in_len, &C.n_tiles))) return rc;
   rc = carve(c, c->d_one_tiles, [&](Carve &k) {
     k.take(P.head, 1);
@@ -86,8 +105,12 @@ int one_discover(flate_hip_ctx *c, const uint8_t *d_in, uint64_t in_len, uint32_
   });
   if (rc) return rc;
   C.head = &P.head->h;
-  one_parse_launch(c, d_in, in_len, P.one, wrap);
-  one_find_launch(c, true, C.n_tiles, P);
+  if (part)
+    hipLaunchKernelGGL(one_part_init_kernel, dim3(1), dim3(64), 0, c->stream, P.one, d_in, in_len, wrap, part->first,
+                       part->final_in, part->b0);
+  else
+    one_parse_launch(c, d_in, in_len, P.one, wrap);
+  one_find_launch(c, true, C.n_tiles, P, part != nullptr);
   hipLaunchKernelGGL(chain_scan_kernel, dim3(1), dim3(1024), 0, c->stream, C);
   HIP_TRY(c, hipGetLastError());
   HIP_TRY(c, hipMemcpyAsync(&H, P.head, sizeof H, hipMemcpyDeviceToHost, c->stream));
@@ -108,9 +131,10 @@ int one_discover(flate_hip_ctx *c, const uint8_t *d_in, uint64_t in_len, uint32_
     k.take(C.out_off, n + 1);
   });
   if (rc) return rc;
-  one_find_launch(c, false, C.n_tiles, P);
+  one_find_launch(c, false, C.n_tiles, P, part != nullptr);
   one_probe_launch(c, cap, P, 0u);
-  if ((rc = chain_tail(c, C, one_link_kernel, P, one_finish_kernel, one_out_scan_kernel, P))) return rc;
+  if ((rc = chain_tail(c, C, part ? one_part_link_kernel : one_link_kernel, P, one_finish_kernel, one_out_scan_kernel, P)))
+    return rc;
   one_probe_launch(c, 1, P, 1u);
   HIP_TRY(c, hipGetLastError());
   // ONE read-back behind the count: the result words, then 16 bytes per unit
@@ -626,6 +650,284 @@ int flate_hip_inflate_one_ranges(flate_hip_ctx *c, const uint8_t *in, uint64_t i
     };
     const SeekRangesOut O{out, nr, RH.out_total, RH.scratch_total, r_lo, r_hi, sel, range_status, bad_unit, dev};
     return seek_ranges_decode(c, D, S, dec, per_round, ns, d_in + raw_off, raw_end - raw_off, O, seeds);
+  } catch (const std::exception &e) {
+    c->hip_err = e.what();
+    return FLATE_HIP_E_INTERNAL;
+  }
+}
+
+}  // extern "C"
+
+// ---- ONE stream read in PARTS (one_parts_rule.h, one_parts_kernels.hip) ----
+
+// Between two calls the stream's state rests in the handle: on the device the 32 KiB window and the running checksum
+// (OnePartState), on the host the rule's words (OnePartsState: the carried bit, the bytes produced and consumed, the
+// sticky status).  The unit rule and "one_unit_max" are the ctx's at open, whatever it says later.
+struct flate_hip_one_reader {
+  flate_hip_ctx *ctx = nullptr;
+  uint32_t wrap = 0, flags = 0;
+  uint64_t unit_max = 0;
+  uint32_t stored_units = 0;
+  DevBuf state;
+  OnePartsState s = one_parts_fresh();
+};
+
+namespace {
+
+// a fresh stream: a window of zeros, the sum of nothing
+int one_reader_fresh(flate_hip_one_reader *r) {
+  flate_hip_ctx *c = r->ctx;
+  OnePartState *st = (OnePartState *)r->state.p;
+  const uint32_t empty = r->wrap == FLATE_HIP_WRAP_ZLIB ? 1u : 0u;
+  HIP_TRY(c, hipMemsetAsync(st, 0, sizeof(OnePartState), c->stream));
+  HIP_TRY(c, hipMemcpyAsync(&st->sums[0], &empty, 4, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  r->s = one_parts_fresh();
+  return FLATE_HIP_OK;
+}
+
+// the call's result words, behind everything queued so far
+int one_reader_result(flate_hip_ctx *c, const OnePartState *st, OneDecHead &R, uint32_t &trailer_bad) {
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipMemcpyAsync(&R, &st->res, sizeof R, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(&trailer_bad, &st->trailer_bad, 4, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return FLATE_HIP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int flate_hip_one_reader_open(flate_hip_ctx *c, uint32_t wrap, uint32_t flags, flate_hip_one_reader **out) {
+  // every check before any HIP call
+  if (one_reader_open_args(c, wrap, flags, out)) return FLATE_HIP_E_INVALID;
+  *out = nullptr;
+  c->hip_err.clear();
+  HIP_TRY(c, hipSetDevice(c->device));
+  flate_hip_one_reader *r = new flate_hip_one_reader();
+  r->ctx = c;
+  r->wrap = wrap;
+  r->flags = flags;
+  r->unit_max = c->one_unit_max;
+  r->stored_units = c->one_stored_units;
+  int rc = ensure(c, r->state, sizeof(OnePartState) + 64);
+  if (rc == FLATE_HIP_OK) rc = one_reader_fresh(r);
+  if (rc != FLATE_HIP_OK) {
+    delete r;
+    return rc;
+  }
+  *out = r;
+  return FLATE_HIP_OK;
+}
+
+int flate_hip_one_reader_reset(flate_hip_one_reader *r) {
+  if (!r) return FLATE_HIP_E_INVALID;
+  flate_hip_ctx *c = r->ctx;
+  c->hip_err.clear();
+  HIP_TRY(c, hipSetDevice(c->device));
+  return one_reader_fresh(r);
+}
+
+void flate_hip_one_reader_free(flate_hip_one_reader *r) {
+  if (!r) return;
+  (void)hipSetDevice(r->ctx->device);
+  delete r;
+}
+
+// One call: flate_hip_inflate_one on the part in[0, in_len), its chain rooted at the carried bit -- discovery (the
+// index comes back with the result words: the host picks the units that fit, one_parts_plan), the rounds over those
+// units with the handle's window as R[0] and the stream's history in the distance rule, the part's checksum joined to
+// the running one, the verdict; then the window behind the last delivered unit goes back into the handle.
+int flate_hip_one_reader_read(flate_hip_one_reader *r, const uint8_t *in, uint64_t in_len, int final_in, uint8_t *out,
+                              uint64_t out_cap, uint64_t *in_used, uint64_t *out_len, int64_t *err_off,
+                              uint32_t *n_units) {
+  // every check before any HIP call
+  if (one_reader_read_args(r, in, in_len, out, out_cap, in_used, out_len)) return FLATE_HIP_E_INVALID;
+  *in_used = 0, *out_len = 0;
+  if (n_units) *n_units = 0;
+  OnePartsState &s = r->s;
+  if (err_off) *err_off = s.status < 0 ? s.err_off : -1;
+  if (s.status) return s.status;  // sticky: the stream's end, or its error
+  flate_hip_ctx *c = r->ctx;
+  c->hip_err.clear();
+  auto fail = [&](int st, int64_t eo) {
+    s.status = st, s.err_off = eo;
+    if (err_off) *err_off = eo;
+    return st;
+  };
+  const uint32_t wrap = r->wrap, tl = one_parts_trailer_len(wrap);
+  const bool dev = (r->flags & FLATE_HIP_DEVICE_PTRS) != 0, fin = final_in != 0;
+  try {
+    int rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    OnePartState *st = (OnePartState *)r->state.p;
+    const uint8_t *d_in = nullptr;
+    OneDecHead R{};
+    uint32_t trailer_bad = 0;
+    OnePartParams Q{};
+    Q.st = st;
+    Q.produced_before = s.produced;
+    Q.wrap = wrap;
+
+    if (s.trailer_pending) {  // the final block lies behind; these bytes are the trailer's
+      if (in_len < tl) return fin ? fail(FLATE_HIP_E_UNEXPECTED_EOF, -1) : FLATE_HIP_OK;
+      if ((rc = stage_input(c, in, tl, r->flags, &d_in))) return rc;
+      HIP_TRY(c, hipMemsetAsync(&st->res, 0, sizeof st->res, c->stream));
+      Q.trailer = d_in;
+      Q.member_len = s.consumed + tl;
+      hipLaunchKernelGGL(one_part_verdict_kernel, dim3(1), dim3(64), 0, c->stream, Q);
+      if ((rc = one_reader_result(c, st, R, trailer_bad))) return rc;
+      *in_used = tl;
+      s.consumed += tl;
+      s.trailer_pending = 0;
+      if (R.status) return fail(R.status, R.err_off);
+      s.status = FLATE_HIP_STREAM_END;
+      return FLATE_HIP_STREAM_END;
+    }
+    if (in_len == 0) {
+      if (!fin) return FLATE_HIP_OK;
+      // no bytes at all: a bad header, as in the whole call; else the stream ends in front of a block
+      if (!s.header_done && wrap != FLATE_HIP_WRAP_RAW) return fail(FLATE_HIP_E_CORRUPT, 0);
+      return fail(FLATE_HIP_E_UNEXPECTED_EOF, -1);
+    }
+
+    if ((rc = stage_input(c, in, in_len, r->flags, &d_in))) return rc;
+    const OnePart part{r->unit_max, r->stored_units, s.b0, s.header_done ? 0u : 1u, fin ? 1u : 0u};
+    OneHead H{};
+    OneParams P{};
+    std::vector<uint64_t> index;  // unit_bit, then out_off
+    if ((rc = one_discover(c, d_in, in_len, wrap, ~0ull, H, P, index, &part))) return rc;
+    if (H.h.n_cand == 0) {
+      if (H.bad == kPartsHdrBad) return fail(FLATE_HIP_E_CORRUPT, 0);
+      // the header is refused only because the part ends here, or no raw byte stands behind it: more is needed
+      return fin ? fail(FLATE_HIP_E_UNEXPECTED_EOF, -1) : FLATE_HIP_OK;
+    }
+    const uint32_t n = H.h.n_members;
+    if (index.size() < 2 * ((size_t)n + 1)) {
+      c->hip_err = "one reader: the index does not hold the units";
+      return FLATE_HIP_E_INTERNAL;
+    }
+    const uint64_t *unit_bit = index.data(), *ooff = index.data() + index.size() / 2;
+    const OnePartsPlan plan =
+        one_parts_plan(n, ooff, H.h.rc, H.fail_unit, H.fail_out, fin, out_cap, in_len, r->unit_max);
+    if (plan.action == kPartsNothing) return FLATE_HIP_OK;
+    if (plan.action == kPartsReturn) {
+      if (plan.status == FLATE_HIP_E_OUT_TOO_SMALL) {  // (not sticky: the state is unchanged)
+        *out_len = plan.need;
+        return FLATE_HIP_E_OUT_TOO_SMALL;
+      }
+      return fail(plan.status, H.h.err_off >= 0 ? (int64_t)s.raw_base + H.h.err_off : -1);
+    }
+
+    const uint32_t n_dec = plan.n_del + plan.with_fail;
+    const uint64_t total = plan.total;
+    uint8_t *d_out = out;
+    if (!dev) {
+      if ((rc = ensure(c, c->d_out, total + 16))) return rc;
+      d_out = (uint8_t *)c->d_out.p;
+    }
+    // the history in front of the part, as far as the distance rule can see it (it saturates at the window)
+    const uint64_t hist = s.produced < (uint64_t)kWinEntries ? s.produced : (uint64_t)kWinEntries;
+    const uint32_t per_round = unit_per_round(c, n_dec);
+    OneDecParams D{};
+    UnitResults dec;
+    uint64_t *t_off;
+    rc = unit_rounds_carve(c, D, n_dec, per_round, [&](Carve &k) {
+      unit_pieces_take(k, D, &dec, per_round);
+      k.take(t_off, (size_t)n_dec + 1);
+    });
+    if (rc) return rc;
+    if ((rc = unit_dec_params(c, D, d_in, P.one, P.C.member_off, P.C.out_off, P.stored_units, false))) return rc;
+    D.unit_max = r->unit_max;
+    D.hist_base = hist;
+    unit_verdict_params(D, total, dec, P.head, wrap, in_len);
+    // R[0] of the first round: the handle's window
+    HIP_TRY(c, hipMemcpyAsync(D.R, st->window, kWinEntries, hipMemcpyDeviceToDevice, c->stream));
+    // the last piece runs to BFINAL or to its failure only where the part's verdict is delivered with it
+    const bool open_last = plan.terminal && (H.h.rc == 0 || H.fail_unit);
+    auto decode = [&](uint32_t u0, uint32_t count) {
+      const uint32_t unit_blocks = (count + 1u + 255u) / 256u;
+      hipLaunchKernelGGL(one_pieces_kernel, dim3(unit_blocks), dim3(256), 0, c->stream, D);
+      const bool closed = u0 + count < n_dec || !open_last;
+      const int e = unit_decode(c, unit_decode_params(D, d_in + H.raw_off, H.raw_len, D.unit_bit + u0, nullptr, closed, count,
+                                                      d_out, D.p_out_off, dec));
+      if (e) return e;
+      hipLaunchKernelGGL(one_check_kernel, dim3(unit_blocks), dim3(256), 0, c->stream, D);
+      return FLATE_HIP_OK;
+    };
+    bool used[FLATE_HIP_STAGE_COUNT] = {false, false, false, false};
+    if (n_dec) {
+      hipLaunchKernelGGL(one_part_hist_kernel, dim3((n_dec + 255u) / 256u), dim3(256), 0, c->stream, P.C.out_off, t_off, n_dec,
+                         hist);
+      if ((rc = unit_rounds(c, D, t_off, nullptr, 0, n_dec, n_dec, per_round, unit_no_hook, unit_no_hook, decode))) return rc;
+      used[FLATE_HIP_STAGE_INFLATE] = true;
+    }
+    bool ctl = false;
+    // From here on the call queues work that moves the handle's device words (the running sum, the window): a failure
+    // of the runtime behind this point leaves them ahead of the host's state, so it ends the handle -- sticky, as the
+    // stream's own errors are.  (In front of it nothing of the handle has been touched, and a call may be repeated.)
+    auto dead = [&](int e) {
+      if (ctl) ctl_finish(c);
+      return fail(e, -1);
+    };
+    const bool summed = wrap != FLATE_HIP_WRAP_RAW && total != 0;
+    if (summed) {
+      const uint64_t whole[2] = {0, total};
+      if ((rc = ctl_begin(c, checksum_ctl_up_bytes(whole, 1), 0))) return rc;
+      ctl = true;
+      if ((rc = checksum_device(c, d_out, whole, 1, frame_sum_kind(wrap), &st->sums[1], FLATE_HIP_STAGE_CHECKSUM)))
+        return dead(rc);
+      used[FLATE_HIP_STAGE_CHECKSUM] = true;
+    }
+    // what the handle holds behind this call if nothing fails, and whether the trailer is judged now
+    const bool ended = plan.terminal && H.h.rc == 0;
+    OnePartsState next = s;
+    uint64_t used_in = 0;
+    bool trailer_now = false;
+    one_parts_advance(next, wrap, H.raw_off, unit_bit[plan.n_del], total, ended, in_len, &used_in, &trailer_now);
+    Q.total = total;
+    Q.term_rc = plan.terminal ? H.h.rc : 0;
+    Q.term_err_off = H.h.err_off;
+    if (trailer_now && tl) {
+      Q.trailer = d_in + (used_in - tl);
+      Q.member_len = next.consumed;
+    }
+    hipLaunchKernelGGL(one_part_carry_kernel, dim3(1), dim3(64), 0, c->stream, Q, D);
+    if (summed && s.produced &&
+        (rc = checksum_join_device(c, st->sums, st->slot_off, st->produced, 2, frame_sum_kind(wrap), &st->joined, &st->total)))
+      return dead(rc);
+    hipLaunchKernelGGL(one_part_verdict_kernel, dim3(1), dim3(64), 0, c->stream, Q);
+    if ((rc = one_reader_result(c, st, R, trailer_bad))) return dead(rc);
+    if (ctl) ctl_finish(c);
+    ctl = false;
+    if (R.out_len > total) return dead(FLATE_HIP_E_INTERNAL);
+    // THE CARRY, once the result words are good: the window behind the last unit, which the round driver leaves in
+    // R[count] of the last round (nothing has been queued behind the rounds that writes D.R)
+    if (n_dec && R.status == 0) {
+      const uint32_t last_count = n_dec - ((n_dec - 1u) / per_round) * per_round;
+      if (hipMemcpyAsync(st->window, D.R + (size_t)last_count * kWinEntries, kWinEntries, hipMemcpyDeviceToDevice,
+                         c->stream) != hipSuccess)
+        return dead(FLATE_HIP_E_HIP);
+    }
+    *out_len = R.out_len;
+    if (!dev && R.out_len &&
+        (hipMemcpyAsync(out, d_out, R.out_len, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+         hipStreamSynchronize(c->stream) != hipSuccess)) {
+      *out_len = 0;
+      return dead(FLATE_HIP_E_HIP);
+    }
+    if (c->profiling && (rc = collect_timing(c, used))) return dead(rc);
+    if (n_units) *n_units = plan.n_del;
+    if (R.status)  // (a trailer's mismatch counts from the member's first byte, everything else from the raw stream's)
+      return fail(R.status, trailer_bad || R.err_off < 0 ? R.err_off : (int64_t)s.raw_base + R.err_off);
+    s = next;
+    *in_used = used_in;
+    if (ended && trailer_now) {
+      s.status = FLATE_HIP_STREAM_END;
+      return FLATE_HIP_STREAM_END;
+    }
+    return FLATE_HIP_OK;
   } catch (const std::exception &e) {
     c->hip_err = e.what();
     return FLATE_HIP_E_INTERNAL;

@@ -388,6 +388,8 @@ struct FrameOne {
   uint32_t want, isize, bad, dict_used;  // frame_parse_kernel
   uint32_t sum;             // checksum_join_kernel
   int32_t member_status;    // frame_verdict_spliced_kernel
+  uint32_t b0;              // one_part_init_kernel (a stream read in parts): the first unit starts at this bit of the raw
+                            // range's first byte; 0 everywhere else (one_init_kernel, gzfile_init_kernel)
 };
 struct FrameSplicedParams {
   FrameOne *one;
@@ -627,6 +629,9 @@ struct OneDecParams {
   // other field moves, so the default build's parameter loads are the ones it had.)
   uint32_t stored_units;
   uint64_t in_len;
+  // one_pieces_kernel: bytes of history in front of out_off[0], at most 32768 -- what a stream read in parts produced
+  // before this part (the handle's window holds them); 0 in every other call
+  uint64_t hist_base;
 };
 template <bool STORED>  // (the unit rule of D.stored_units; both builds: one_probe_kernel.inc)
 __global__ void one_tail_kernel(OneDecParams D);
@@ -637,16 +642,60 @@ __global__ void one_resolve_kernel(const uint16_t *F, uint8_t *R, uint32_t count
 __global__ void one_verdict_kernel(OneDecParams D);
 __global__ void one_init_kernel(FrameOne *one, uint64_t in_len);
 // (STORED: the unit rule, one_find_kernel.inc -- <false>, dynamic headers alone, is instantiated in one_kernels.hip;
-// <true>, dynamic and stored headers, in one_stored_kernels.hip)
-template <bool STORED>
+// <true>, dynamic and stored headers, in one_stored_kernels.hip.  PARTS: the root of the chain is bit FrameOne::b0 of
+// the raw range's first byte, not bit 0 -- a stream read in parts; both unit rules in one_parts_kernels.hip)
+template <bool STORED, bool PARTS = false>
 __global__ void one_count_kernel(OneParams P);
-template <bool STORED>
+template <bool STORED, bool PARTS = false>
 __global__ void one_fill_kernel(OneParams P);
 template <bool STORED>  // (the unit rule of P.stored_units; both builds: one_probe_kernel.inc)
 __global__ void one_probe_kernel(OneParams P, uint32_t tail);
 __global__ void one_link_kernel(OneParams P);
 __global__ void one_finish_kernel(OneParams P);
 __global__ void one_out_scan_kernel(OneParams P);
+
+// ONE stream read in PARTS (flate_hip_one_reader_*; one_parts_kernels.hip; the rule: one_parts_rule.h).  A call is the
+// discovery and the rounds above over one part of the stream, between three small kernels of its own:
+//   one_part_init_kernel   in one_init_kernel's and frame_parse_kernel's place: the part's raw range (the header on the
+//                          first part only, with the rule's third answer in FrameOne::bad; the trailer cut off on a
+//                          final part only) and b0
+//   one_part_link_kernel   one_link_kernel with the chain's root at candidate 0 = bit b0 (FIND's PARTS build masks the
+//                          bits in front of it out of that byte)
+//   one_part_hist_kernel   TAIL's offsets: out_off[k] + hist_base, so that the distance rule sees what the STREAM has
+//                          produced (unit_rounds: tail_out_off)
+//   one_part_carry_kernel  behind the rounds: the part's verdict words (one_verdict_kernel's cases without the trailer)
+//                          and the two pieces of the checksum join -- the running sum over produced_before bytes, the
+//                          part's over its own
+//   one_part_verdict_kernel  behind the join: the joined sum becomes the running one, and -- trailer != null -- it and
+//                          the total length are held against the trailer's words
+// The window behind the last delivered unit, R[count] of the last round, goes into OnePartState::window by a copy on
+// the stream, as the round driver's own carry does.
+struct OnePartState {        // per handle, in device memory
+  uint8_t window[32768];     // the 32 KiB in front of the next unit (zeros in front of the stream)
+  uint64_t slot_off[3];      // checksum_join_device: {0, produced_before, produced_before + out_len}
+  uint64_t produced[2];      // ... {produced_before, out_len}
+  uint64_t total;            // ... its length word
+  uint32_t sums[2];          // the running sum, the part's
+  uint32_t joined;
+  uint32_t trailer_bad;      // res.status is a trailer mismatch (err_off is counted from the member's first byte)
+  OneDecHead res;            // the call's result words, read back
+};
+struct OnePartParams {
+  OnePartState *st;
+  uint64_t produced_before;
+  uint64_t total;            // bytes the call delivers if nothing fails
+  int32_t term_rc;           // the discovery's verdict when the call delivers everything in front of it, else 0
+  uint32_t wrap;
+  int64_t term_err_off;
+  const uint8_t *trailer;    // the trailer's bytes when this call judges it, or null
+  uint64_t member_len;       // ... and the member's length with it: err_off of a mismatch
+};
+__global__ void one_part_init_kernel(FrameOne *one, const uint8_t *in, uint64_t in_len, uint32_t wrap, uint32_t first,
+                                     uint32_t final_in, uint32_t b0);
+__global__ void one_part_link_kernel(OneParams P);
+__global__ void one_part_hist_kernel(const uint64_t *out_off, uint64_t *tail_off, uint32_t n, uint64_t hist_base);
+__global__ void one_part_carry_kernel(OnePartParams Q, OneDecParams D);
+__global__ void one_part_verdict_kernel(OnePartParams Q);
 
 // The seek index of one long stream (one_seek_kernels.hip; flate_hip_inflate_one_seek_index / _ranges; the rule and
 // the index's layout: seek_index_rule.h).

@@ -1,8 +1,11 @@
 // one_find_kernel.inc -- FIND of the block discovery (one_kernels.hip: one_count_kernel / one_fill_kernel), as templates
-// on the unit rule.  Included inside namespace flate by the two files that instantiate them: one_kernels.hip the build
+// on the unit rule.  Included inside namespace flate by the files that instantiate them: one_kernels.hip the build
 // for dynamic headers alone (the default), one_stored_kernels.hip the one for dynamic and stored headers (option
-// "one_stored_units").  One build per file ON PURPOSE: how the compiler inlines the rule into a kernel depends on how
-// many kernels of the same file call it, and the default build's instructions must not depend on the other's existence.
+// "one_stored_units"), one_parts_kernels.hip those of a stream read in parts, whose chain starts at a carried bit.
+// A file of its own per build ON PURPOSE: how the compiler inlines the rule into a kernel depends on how many kernels
+// of the same file call it, and the default build's instructions must not depend on the others' existence.  (The
+// PARTS test is a template flag for the same reason: one_kernels.hip and one_stored_kernels.hip compile to what they
+// were before it existed.)
 
 namespace {
 
@@ -10,7 +13,11 @@ namespace {
 // v0 + 16 * tid + (j >> 3).  Returns how many.  STORED (option "one_stored_units"): a stored header starts a unit too --
 // the rule reads at most the 6 bytes from the bit's byte on, in LDS like the head test's; only its "four bytes inside
 // the raw range" comparison sees the stream's end.  The dynamic-only build holds no trace of it.
-template <bool STORED>
+// PARTS (a stream read in parts, one_parts_kernels.hip): the first unit starts at bit b0 = FrameOne::b0 of the raw
+// range's first byte, not at bit 0.  That bit is a candidate whatever it holds, and the bits in front of it in that byte
+// -- bits of the unit the last call delivered -- are none: the root stays candidate 0 and no decoy can stand in front
+// of it.  The other builds hold no trace of it.
+template <bool STORED, bool PARTS>
 __device__ inline uint32_t test_bits(const OneParams &P, const uint8_t *lds, uint64_t v0, uint32_t A, uint32_t hits[4]) {
   hits[0] = hits[1] = hits[2] = hits[3] = 0u;
   const uint64_t raw_off = P.one->pay_off[0], raw_end = P.one->pay_end;
@@ -36,7 +43,10 @@ __device__ inline uint32_t test_bits(const OneParams &P, const uint8_t *lds, uin
         for (uint32_t k = 0; k < 8u; ++k)
           if (deflate_stored_header_ok(l, raw_end - p, k)) m |= 1u << k;
     }
-    if (p == raw_off) m |= 1u;  // bit 0 starts the first unit
+    if (p == raw_off) {
+      if constexpr (PARTS) m = (m | (1u << (P.one->b0 & 7u))) & (0xffu << (P.one->b0 & 7u)) & 0xffu;
+      else m |= 1u;  // bit 0 starts the first unit
+    }
     hits[b >> 2] |= m << (8u * (b & 3u));
     n += (uint32_t)__popc(m);
   }
@@ -45,7 +55,7 @@ __device__ inline uint32_t test_bits(const OneParams &P, const uint8_t *lds, uin
 
 }  // namespace
 
-template <bool STORED>
+template <bool STORED, bool PARTS>
 __global__ __launch_bounds__(256) void one_count_kernel(OneParams P) {
   __shared__ TileLds L;
   if (blockIdx.x == 0 && threadIdx.x == 0) {  // (chain_scan_kernel writes head->h, and nothing behind it)
@@ -62,17 +72,17 @@ __global__ __launch_bounds__(256) void one_count_kernel(OneParams P) {
   const uint32_t A = tile_align(P.C.in);
   const uint64_t v0 = (uint64_t)blockIdx.x * kTileBytes;
   uint32_t hits[4];
-  tile_count(P.C, L, v0, [&](const uint8_t *lds) { return test_bits<STORED>(P, lds, v0, A, hits); });
+  tile_count(P.C, L, v0, [&](const uint8_t *lds) { return test_bits<STORED, PARTS>(P, lds, v0, A, hits); });
 }
 
-template <bool STORED>
+template <bool STORED, bool PARTS>
 __global__ __launch_bounds__(256) void one_fill_kernel(OneParams P) {
   __shared__ TileLds L;
   const uint32_t A = tile_align(P.C.in), cap = P.C.cap;
   const uint64_t v0 = (uint64_t)blockIdx.x * kTileBytes;
   uint32_t first, hits[4];
   if (!tile_fill_load(P.C, L, v0, true, &first)) return;
-  uint32_t at = tile_fill_at(L, first, test_bits<STORED>(P, L.bytes, v0, A, hits));
+  uint32_t at = tile_fill_at(L, first, test_bits<STORED, PARTS>(P, L.bytes, v0, A, hits));
   const uint64_t raw_off = P.one->pay_off[0];
   for (uint32_t j = 0; j < 128u; ++j) {
     if (!((hits[j >> 5] >> (j & 31u)) & 1u)) continue;

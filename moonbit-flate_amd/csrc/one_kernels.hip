@@ -137,7 +137,8 @@ __global__ __launch_bounds__(256) void one_pieces_kernel(OneDecParams D) {
   if (at > limit) at = limit;
   D.p_out_off[i] = at;
   if (i == D.count) return;
-  const uint32_t dict_len = at < (uint64_t)kWinEntries ? (uint32_t)at : kWinEntries;
+  const uint64_t have = at + D.hist_base;  // (hist_base <= kWinEntries: a part's history in front of out_off[0])
+  const uint32_t dict_len = have < (uint64_t)kWinEntries ? (uint32_t)have : kWinEntries;
   D.p_dict_len[i] = dict_len;
   D.p_dict_at[i] = (uint64_t)(i + 1u) * kWinEntries - dict_len;  // the tail of R[i]; R[i + 1] follows it
 }

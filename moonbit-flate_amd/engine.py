@@ -583,7 +583,18 @@ class GroupedCalls:
         return tuple(int(x.value) for x in w)
 
 
-class FlateEngine(OneSeekCalls, GzFileCalls, GzFileSerialCalls, GzFileSeekCalls, ZipUnitsCalls, GroupedCalls):
+class OnePartsCalls:
+    """One long stream read in parts: the method FlateEngine inherits.  It stands in a class of its own so that its
+    marshalling has its own recorded scenarios (tests/engine_trace_one_parts.py) beside the ones of the methods that
+    were there before (tests/engine_trace.py)."""
+
+    def open_one_reader(self, wrap="gzip", device=False):
+        """ONE long stream ("raw", "zlib" or "gzip") read in parts through bounded buffers at inflate_one's speed
+        (flate_hip_one_reader_*): see OneReader.  device: every part and every output is a torch CUDA tensor."""
+        return OneReader(self, wrap, device)
+
+
+class FlateEngine(OneSeekCalls, GzFileCalls, GzFileSerialCalls, GzFileSeekCalls, ZipUnitsCalls, GroupedCalls, OnePartsCalls):
     """One engine = one flate_hip_ctx = one GPU + one HIP stream."""
 
     def __init__(self, device=0):
@@ -1353,6 +1364,62 @@ class StreamReader:
     def __del__(self):
         try:
             self.free()
+        except Exception:
+            pass
+
+
+OnePartRead = collections.namedtuple("OnePartRead", "rc out_len err_off n_units")
+
+
+class OneReader:
+    """flate_hip_inflate_one on a stream the caller holds a part at a time (flate_hip_one_reader_*): every read() decodes
+    the units that lie whole inside the part, in parallel, and the handle carries the bit where the next unit starts,
+    the 32 KiB window and the running checksum.  read(part, final, out, out_cap) -> (in_used, out, OnePartRead(rc,
+    out_len, err_off, n_units)): `part` BEGINS with the bytes the last read left unused (part[in_used:], then new
+    bytes); the bytes are out[:out_len]; rc 0 = go on, 1 = the end of the stream (trailer checked), -2 = not even the
+    first unit fits (out_len: its size; nothing changed), -4 / -7 / -6 = the stream's error, sticky.  out=None: room
+    for out_cap bytes (default: four times the part, 64 KiB at least), and with no out_cap a first unit that does not
+    fit gets a second call with room for it.  The unit rule and "one_unit_max" are the engine's at open."""
+
+    def __init__(self, eng, wrap="gzip", device=False):
+        self._eng, self._L = eng, eng._L
+        self._device = bool(device)
+        self._h = C.c_void_p()
+        eng._check(self._L.flate_hip_one_reader_open(eng._ctx, WRAPS[wrap], eng._flags(False, False, self._device),
+                                                     C.byref(self._h)))
+
+    def read(self, part, final=False, out=None, out_cap=None):
+        part, in_ptr, n, device = _in_buf(part, accept_bytes=True, null_if_empty=True)
+        if device != self._device:
+            raise FlateError(E_INVALID, "OneReader.read: the part is not on the side the reader was opened for")
+        used, ol, eo, nu = C.c_uint64(0), C.c_uint64(0), C.c_int64(-1), C.c_uint32(0)
+
+        def call(out_ptr, cap):
+            rc = self._eng._tolerate(self._L.flate_hip_one_reader_read(
+                self._h, in_ptr, n, 1 if final else 0, out_ptr, cap, C.byref(used), C.byref(ol), C.byref(eo),
+                C.byref(nu)), 1, *PER_CHAIN)  # (1: the end of the stream)
+            return OnePartRead(rc, int(ol.value), int(eo.value), int(nu.value))
+
+        size = max(4 * n, 1 << 16) if out_cap is None else int(out_cap)
+        buf, ptr, cap = _out_buf(out, part, size, out_cap, 0, "OneReader.read", floor=1)
+        res = call(ptr, cap)
+        if res.rc == E_OUT_TOO_SMALL and out is None and out_cap is None:
+            buf, ptr, cap = _out_buf(None, part, res.out_len, None, 0, "OneReader.read", floor=1)
+            res = call(ptr, cap)
+        return int(used.value), (buf[:0] if res.rc == E_OUT_TOO_SMALL else buf[:res.out_len]), res
+
+    def reset(self):
+        """A fresh stream on the same handle: same wrap, same side, same options."""
+        self._eng._check(self._L.flate_hip_one_reader_reset(self._h))
+
+    def close(self):
+        if self._h:
+            self._L.flate_hip_one_reader_free(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
         except Exception:
             pass
 
