@@ -467,6 +467,53 @@ int flate_hip_deflate_fast_grouped_framed(flate_hip_ctx *ctx, const uint8_t *in,
                                           uint32_t wrap, uint8_t *out, uint64_t out_cap, uint64_t *out_off,
                                           uint64_t *bit_off, uint32_t flags);
 
+/* ONE long raw, zlib or gzip stream WRITTEN IN PARTS through bounded buffers: flate_hip_deflate_fast_spliced_framed for
+ * a caller that has neither the whole input nor room for the whole output (a 40 GB dump turned into a .gz through
+ * two fixed buffers).  The handle carries the stream between calls; its state rests on the device.
+ *   open: wrap = FLATE_HIP_WRAP_RAW / _ZLIB / _GZIP.  piece_bytes = P, the bytes of a piece (0: 65535; P must be below
+ *     0x7ffe0000).  flags: a subset of FLATE_HIP_DEVICE_PTRS | FLATE_HIP_COMPAT_GO, fixed for the handle's life.
+ *     Anything else: FLATE_HIP_E_INVALID before any HIP call.
+ *   THE STREAM: with T the total input of all calls, the concatenation of every call's out[0, *out_len) is, byte for
+ *     byte, what flate_hip_deflate_fast_spliced_framed writes for that input with in_off = {0, P, 2P, ..., T} (ceil(T /
+ *     P) pieces; T == 0: n_streams == 0), the same wrap and the same flags; the concatenation of every call's bit_off
+ *     is that call's bit_off, counted from the raw stream's first byte.  Both hold for ANY cut of the input into parts:
+ *     the pieces are independent, and where a piece's blocks fall depends on the start position only modulo 8.
+ *   write: in[0, in_len) begins with the bytes the last call left unused (flate_hip_one_reader_read's convention).  A
+ *     call that is not final consumes k = floor(in_len / P) whole pieces, *in_used = k * P; with in_len < P it returns
+ *     FLATE_HIP_OK with *in_used = *out_len = 0 and launches nothing (the header is written only by a call with k >= 1
+ *     or a final one).  A final call (final_in != 0) consumes everything -- the last piece is shorter, and there may
+ *     be no piece at all.  The first call that writes anything starts with the container's header; a final call ends
+ *     with the closing block and the trailer (CRC-32 or Adler-32 and ISIZE over all T bytes, ISIZE mod 2^32).  A call
+ *     delivers the whole bytes that are finished: the 0..7 bits of the last, incomplete byte stay in the handle on the
+ *     device and share the next call's first byte; a final call delivers everything.  *n_pieces = k.  bit_off: NULL,
+ *     or a HOST array with room for in_len / P + 2 entries: the k pieces' start bits and, on a final call, one entry
+ *     more, the end bit, where the closing block starts.  Returns FLATE_HIP_OK, or FLATE_HIP_STREAM_END for a final
+ *     call that succeeded; after that every write is FLATE_HIP_E_INVALID until reset.
+ *   Room: out_cap >= *out_len is enough to the byte; flate_hip_one_writer_bound(in_len, P) (host only) is enough for
+ *     any call on at most in_len bytes, first and final included.  Too little: FLATE_HIP_E_OUT_TOO_SMALL with *out_len =
+ *     the bytes needed, nothing written to out, the handle unchanged -- the same call repeated with room delivers the
+ *     same bytes.  Nothing outside out[0, *out_len) is ever written, with device pointers too: the pack kernels (whole
+ *     dwords, OR into shared ones) write into the handle's own device buffer, and exactly *out_len bytes are copied
+ *     from it -- device pointers: a copy kernel that reads the length on the device; host pointers: one download.
+ *   Errors: FLATE_HIP_E_INVALID (a NULL handle or pointer; decided before any HIP call), FLATE_HIP_E_OUT_TOO_SMALL,
+ *     FLATE_HIP_E_TOO_LARGE (in_len >= 2^32, or the limits of flate_hip_deflate_fast_spliced on the pieces a call
+ *     consumes) and FLATE_HIP_E_HIP in front of the commit point are repeatable and change nothing.  Behind the
+ *     commit point -- the launch of the one kernel that moves the handle's state -- every failure is sticky until
+ *     reset.  The stream itself may be of any length: positions are 64-bit.
+ *   Host waits per call: one read-back of the result words (device pointers), plus the download (host pointers).  The
+ *     carry byte, the running checksum, the length and the emitted byte count never pass through the host.
+ *   Out of scope: pieces that share history, dictionaries, several members, BGZF, overlapping the upload of part k + 1
+ *     with the compression of part k, range reads through the writer's index, the MoonBit binding. */
+typedef struct flate_hip_one_writer flate_hip_one_writer;
+size_t flate_hip_one_writer_bound(size_t in_len, size_t piece_bytes);
+int flate_hip_one_writer_open(flate_hip_ctx *ctx, uint32_t wrap, uint64_t piece_bytes, uint32_t flags,
+                              flate_hip_one_writer **writer);
+int flate_hip_one_writer_write(flate_hip_one_writer *writer, const uint8_t *in, uint64_t in_len, int final_in,
+                               uint8_t *out, uint64_t out_cap, uint64_t *in_used, uint64_t *out_len, uint64_t *bit_off,
+                               uint32_t *n_pieces);
+int flate_hip_one_writer_reset(flate_hip_one_writer *writer);
+void flate_hip_one_writer_free(flate_hip_one_writer *writer);
+
 /* READING members: flate_hip_inflate_batch -- its output slots, out_len, status, return value (the first non-zero
  * status), FLATE_HIP_DEVICE_PTRS, options and size limits -- for n_streams zlib or gzip members, member i =
  * in[in_off[i], in_off[i+1]) = header | raw stream | trailer.  Header parsing, decoding and the check of the trailer
@@ -922,8 +969,8 @@ int flate_hip_inflate_one_index(flate_hip_ctx *ctx, const uint8_t *in, uint64_t 
  *   Host pointers: the part is uploaded once and out[0, *out_len) downloaded once per call.  With device pointers
  *   nothing outside out[0, *out_len) is written.  Per call the host waits for the discovery's two read-backs and one
  *   read-back of the result words.
- *   Out of scope: a file of several members read in parts (flate_hip_gzfile_read takes the whole file); the parallel
- *   writer in parts; overlapping the copy of part k + 1 with the decode of part k. */
+ *   Out of scope: a file of several members read in parts (flate_hip_gzfile_read takes the whole file); overlapping
+ *   the copy of part k + 1 with the decode of part k.  (The parallel writer in parts: flate_hip_one_writer_*.) */
 typedef struct flate_hip_one_reader flate_hip_one_reader;
 int flate_hip_one_reader_open(flate_hip_ctx *ctx, uint32_t wrap, uint32_t flags, flate_hip_one_reader **reader);
 int flate_hip_one_reader_read(flate_hip_one_reader *reader, const uint8_t *in, uint64_t in_len, int final_in,

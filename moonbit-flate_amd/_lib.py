@@ -93,6 +93,11 @@ def _signatures():
         "flate_hip_one_reader_read": (i, [vp, vp, u64, i, vp, u64, u64p, u64p, i64p, u32p]),
         "flate_hip_one_reader_reset": (i, [vp]),
         "flate_hip_one_reader_free": (None, [vp]),
+        "flate_hip_one_writer_bound": (sz, [sz, sz]),
+        "flate_hip_one_writer_open": (i, [vp, u32, u64, u32, vpp]),
+        "flate_hip_one_writer_write": (i, [vp, vp, u64, i, vp, u64, u64p, u64p, vp, u32p]),
+        "flate_hip_one_writer_reset": (i, [vp]),
+        "flate_hip_one_writer_free": (None, [vp]),
     }
 
 
@@ -111,7 +116,9 @@ MAY_BE_MISSING = [
     "flate_hip_zip_bound", "flate_hip_zip_write", "flate_hip_zip_index", "flate_hip_zip_read",
     "flate_hip_zip_last_route", "flate_hip_gzfile_last_route", "flate_hip_deflate_fast_grouped_framed",
     "flate_hip_zip_write_last_route", "flate_hip_one_reader_open", "flate_hip_one_reader_read",
-    "flate_hip_one_reader_reset", "flate_hip_one_reader_free",
+    "flate_hip_one_reader_reset", "flate_hip_one_reader_free", "flate_hip_one_writer_bound",
+    "flate_hip_one_writer_open", "flate_hip_one_writer_write", "flate_hip_one_writer_reset",
+    "flate_hip_one_writer_free",
 ]
 
 _lib = None

@@ -7,6 +7,7 @@
 #include "flate_hip.h"
 #include "gzfile_seek_rule.h"
 #include "one_parts_rule.h"
+#include "one_writer_rule.h"
 #include "seek_index_rule.h"
 #include "splice_rule.h"
 
@@ -203,6 +204,20 @@ inline int one_reader_open_args(const void *ctx, uint32_t wrap, uint32_t flags, 
 inline int one_reader_read_args(const void *reader, const uint8_t *in, uint64_t in_len, const uint8_t *out, uint64_t out_cap,
                                 const uint64_t *in_used, const uint64_t *out_len) {
   return one_parts_read_args(reader, in, in_len, out, out_cap, in_used, out_len);
+}
+
+// flate_hip_one_writer_open / _write (one_writer_rule.h holds the checks and what a call decides; its words are this
+// header's)
+static_assert(kWriterInvalid == FLATE_HIP_E_INVALID && kWriterOutTooSmall == FLATE_HIP_E_OUT_TOO_SMALL &&
+                  kWriterTooLarge == FLATE_HIP_E_TOO_LARGE && kWriterStreamEnd == FLATE_HIP_STREAM_END &&
+                  kWriterGzip == FLATE_HIP_WRAP_GZIP && kWriterZlib == FLATE_HIP_WRAP_ZLIB && kWriterRaw == FLATE_HIP_WRAP_RAW,
+              "one_writer_rule.h restates flate_hip.h");
+inline int one_writer_open_check(const void *ctx, uint32_t wrap, uint64_t piece_bytes, uint32_t flags, const void *writer) {
+  return one_writer_open_args(ctx, wrap, piece_bytes, flags, FLATE_HIP_DEVICE_PTRS | FLATE_HIP_COMPAT_GO, writer);
+}
+inline int one_writer_write_check(const void *writer, const uint8_t *in, uint64_t in_len, const uint8_t *out, uint64_t out_cap,
+                                  const uint64_t *in_used, const uint64_t *out_len, const uint32_t *n_pieces) {
+  return one_writer_write_args(writer, in, in_len, out, out_cap, in_used, out_len, n_pieces);
 }
 
 // ---- a gzip file of any members (flate_hip_gzfile_index / _read) ----

@@ -17,6 +17,7 @@
 
 #include "api_checks.h"
 #include "bgzf_rule.h"
+#include "checksum_clip.h"
 #include "zip_rule.h"
 
 using namespace flate;
@@ -1115,6 +1116,243 @@ int flate_hip_stream_write(flate_hip_stream *st, const uint8_t *in, uint64_t n, 
   if (rc == FLATE_HIP_E_OUT_TOO_SMALL) st->err = rc;  // (the piece's state is gone with the call)
   if (rc == FLATE_HIP_OK && final) st->closed = true;
   return rc;
+}
+
+// ---- one long stream, written in parts at the batch encoder's speed (one_writer_rule.h, one_writer_kernels.hip) ----
+}  // extern "C"
+
+// Between two calls the stream rests in the handle: on the device the carried byte, the running checksum, the lengths
+// (OneWriterState) and the buffer the pack kernels write into; on the host the rule's three words (OneWriterHost).
+struct flate_hip_one_writer {
+  flate_hip_ctx *ctx = nullptr;
+  uint32_t wrap = 0, flags = 0;
+  uint64_t piece = 0;       // P as given (0: the default)
+  DevBuf state, buf, idx;   // OneWriterState; the call's bytes; the call's index (bits of the raw stream)
+  OneWriterHost s = one_writer_fresh();
+};
+
+namespace {
+
+// a fresh stream: no carry, the sum of nothing
+int one_writer_fresh_state(flate_hip_one_writer *w) {
+  flate_hip_ctx *c = w->ctx;
+  OneWriterState *st = (OneWriterState *)w->state.p;
+  const uint32_t empty = w->wrap == FLATE_HIP_WRAP_ZLIB ? 1u : 0u;
+  HIP_TRY(c, hipMemsetAsync(st, 0, sizeof(OneWriterState), c->stream));
+  HIP_TRY(c, hipMemcpyAsync(&st->sum, &empty, 4, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  w->s = one_writer_fresh();
+  return FLATE_HIP_OK;
+}
+
+// One call that launches: the pieces of the plan through the whole call's kernels into the handle's buffer, the
+// writer's kernels around them, ONE read-back (the result words, and the index where it is asked for), the download
+// for a host caller.
+int one_writer_run(flate_hip_one_writer *w, const OneWriterPlan &plan, const uint8_t *in, uint8_t *out, uint64_t out_cap,
+                   uint64_t *in_used, uint64_t *out_len, uint64_t *bit_off, uint32_t *n_pieces) {
+  flate_hip_ctx *c = w->ctx;
+  const uint32_t n = (uint32_t)plan.n_pieces, wrap = w->wrap, flags = w->flags;
+  const bool dev = (flags & FLATE_HIP_DEVICE_PTRS) != 0, fin = plan.close != 0;
+  const uint64_t P = one_writer_piece(w->piece), bytes = plan.in_used;
+  HIP_TRY(c, hipSetDevice(c->device));
+  int rc;
+
+  // plan: the pieces as the streams of a spliced call
+  std::vector<uint64_t> in_off((size_t)n + 1);
+  for (uint32_t i = 0; i < n; ++i) in_off[i] = (uint64_t)i * P;
+  in_off[n] = bytes;
+  StagePlan pl;
+  if (n && (rc = make_plan(in_off.data(), n, pl, flags))) return rc;
+  const EncodeRoute route = encode_route(pl, c->enc, flags, true);
+  const uint64_t whole[2] = {0, bytes};
+  const bool summed = wrap != FLATE_HIP_WRAP_RAW && bytes != 0;
+  CtlBytes ctl{n ? lz77_ctl_up(pl) + entropy_ctl_up(pl) : 0, encode_ctl_down(n)};
+  if (summed) ctl += frame_after_ctl(whole, 1);
+  if ((rc = ctl_begin(c, ctl.up, ctl.down))) return rc;
+
+  // the input, the handle's buffers, the scratch of both stages
+  const uint8_t *d_in = in;
+  if ((rc = stage_input(c, in, bytes, flags, &d_in))) return rc;
+  const uint64_t cap = one_writer_bound(bytes, w->piece);
+  if ((rc = ensure(c, w->buf, cap + 64))) return rc;  // (16-byte reads of the copy kernel behind the last byte)
+  if ((rc = ensure(c, w->idx, ((size_t)n + 2) * 8))) return rc;
+  if (n) {
+    if ((rc = ensure_entropy_scratch(c, pl.n_blocks, bytes, n))) return rc;
+    if ((rc = ensure(c, c->d_slot_off, ((size_t)n + 1) * 16))) return rc;
+    if ((rc = ensure_lz_scratch(c, pl.n_chunks))) return rc;
+    if ((rc = blk_base_up(c, pl))) return rc;
+  }
+  void *unused = nullptr;
+  if (summed && (rc = ctx_scratch(c, 0, checksum_scratch_bytes(whole, 1), &unused))) return rc;
+  OneWriterState *st = (OneWriterState *)w->state.p;
+  uint8_t *buf = (uint8_t *)w->buf.p;
+  OneWriterParams Q{};
+  Q.st = st;
+  Q.buf = buf;
+  Q.stream_bit = (const uint64_t *)c->d_out_off.p;
+  Q.bit_idx = (uint64_t *)w->idx.p;
+  Q.status = (const int *)c->d_status.p;
+  Q.start_bit = plan.start_bit;
+  Q.in_used = bytes;
+  Q.out_cap = out_cap;
+  Q.n_pieces = n;
+  Q.wrap = wrap;
+  Q.header = plan.header;
+  Q.close = plan.close;
+
+  HIP_TRY(c, hipMemsetAsync(c->d_status.p, 0, 8, c->stream));
+  if (n) {
+    // the match finder and the entropy stage of the whole call; the scan starts at the carried bit, only a final call
+    // closes, and the header or the carry goes in between the zero kernel and the pack kernel's OR
+    if ((rc = run_lz77(c, d_in, in_off.data(), pl, route, flags))) return rc;
+    HuffParams H = huff_params(c, flags, true);
+    H.in = d_in;
+    H.in_off = (const uint64_t *)c->d_in_off.p;
+    H.chunk_base = (const uint32_t *)c->d_chunk_base.p;
+    H.blk_base = (const uint32_t *)c->d_blk_base.p;
+    H.out = buf;
+    H.n_streams = n;
+    H.no_close = fin ? 0u : 1u;
+    SpliceParams S{};
+    S.sum = (const uint64_t *)c->d_slot_off.p;
+    S.stream_bit = (uint64_t *)c->d_out_off.p;
+    S.total_bytes = (uint64_t *)c->d_out_len.p + n;  // (d_out_len has n + 1 slots)
+    S.out_cap = cap + 8;
+    S.status = (int *)c->d_status.p;
+    S.n_streams = n;
+    S.start_bit = plan.start_bit;
+    S.no_close = H.no_close;
+    StageTimer t(c, FLATE_HIP_STAGE_HUFF_PACK);
+    hipLaunchKernelGGL(huff_hist_kernel, dim3(n), dim3(64), 0, c->stream, H);
+    hipLaunchKernelGGL(huff_code_kernel, dim3(n), dim3(64), 0, c->stream, H);
+    hipLaunchKernelGGL(splice_scan_kernel, dim3(1), dim3(1024), 0, c->stream, S);
+    hipLaunchKernelGGL(splice_zero_kernel, dim3(n / 256 + 1), dim3(256), 0, c->stream, S, buf);
+    hipLaunchKernelGGL(one_writer_begin_kernel, dim3(1), dim3(64), 0, c->stream, Q);
+    hipLaunchKernelGGL(huff_pack_kernel, dim3(n), dim3(64), 0, c->stream, H);
+  }
+  HIP_TRY(c, hipGetLastError());
+  if (summed) {  // the checksum of the consumed bytes, on the input where it lies
+    StageTimer t(c, FLATE_HIP_STAGE_CHECKSUM);
+    if ((rc = checksum_device(c, d_in, whole, 1, frame_sum_kind(wrap), &st->part_sum, -1))) return rc;
+  }
+  hipLaunchKernelGGL(one_writer_index_kernel, dim3(n / 256 + 1), dim3(256), 0, c->stream, Q);
+  HIP_TRY(c, hipGetLastError());
+
+  std::vector<uint64_t> index((size_t)n + 1);  // (allocated in front of the commit point)
+  const uint32_t n_idx = n + (fin ? 1u : 0u);
+
+  // THE COMMIT POINT: the one kernel that moves the handle's device words.  A failure of the runtime behind it leaves
+  // them ahead of the host's, so it ends the handle -- sticky until reset.  (In front of it nothing of the handle's
+  // state has been touched, and a call may be repeated.)
+  auto dead = [&](int e) {
+    ctl_finish(c);
+    w->s.status = e;
+    return e;
+  };
+  hipLaunchKernelGGL(one_writer_commit_kernel, dim3(1), dim3(64), 0, c->stream, Q, make_x2n());
+  if (dev) {
+    const uint64_t blocks = cap / (256u * 16u * 8u) + 1u;
+    hipLaunchKernelGGL(one_writer_copy_kernel, dim3((uint32_t)(blocks < 4096u ? blocks : 4096u)), dim3(256), 0, c->stream, st, buf, out);
+  }
+  OneWriterResult R{};
+  if ((rc = ctl_down(c, &R, &st->res, sizeof R))) return dead(rc);
+  if (bit_off && n_idx && (rc = ctl_down(c, index.data(), w->idx.p, (size_t)n_idx * 8))) return dead(rc);
+  if (hipGetLastError() != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) {
+    c->hip_err = "one writer: the call's kernels failed";
+    return dead(FLATE_HIP_E_HIP);
+  }
+  ctl_finish(c);
+  if (R.status == FLATE_HIP_E_OUT_TOO_SMALL) {  // (not sticky: the commit kernel has left the state alone)
+    if (R.out_len <= out_cap) {
+      c->hip_err = "one writer: the handle's buffer is smaller than the call's bytes";
+      return FLATE_HIP_E_INTERNAL;
+    }
+    *out_len = R.out_len;
+    return FLATE_HIP_E_OUT_TOO_SMALL;
+  }
+  if (R.status < 0) return w->s.status = encoder_status(c, R.status);
+  if (R.out_len > cap) {
+    c->hip_err = "one writer: more bytes than the bound";
+    return w->s.status = FLATE_HIP_E_INTERNAL;
+  }
+  if (!dev && R.out_len &&
+      (hipMemcpyAsync(out, buf, R.out_len, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+       hipStreamSynchronize(c->stream) != hipSuccess)) {
+    c->hip_err = "one writer: the download failed";
+    return w->s.status = FLATE_HIP_E_HIP;
+  }
+  const bool used[FLATE_HIP_STAGE_COUNT] = {n != 0, n != 0, summed, false};
+  if ((rc = collect_timing(c, used))) return w->s.status = rc;
+  w->s.started = 1u;
+  w->s.carry_bits = fin ? 0u : (uint32_t)(R.end_bit & 7u);
+  if (fin) w->s.status = FLATE_HIP_STREAM_END;
+  *in_used = bytes;
+  *out_len = R.out_len;
+  *n_pieces = n;
+  if (bit_off)
+    for (uint32_t i = 0; i < n_idx; ++i) bit_off[i] = index[i];
+  return fin ? FLATE_HIP_STREAM_END : FLATE_HIP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t flate_hip_one_writer_bound(size_t in_len, size_t piece_bytes) { return (size_t)one_writer_bound(in_len, piece_bytes); }
+
+int flate_hip_one_writer_open(flate_hip_ctx *c, uint32_t wrap, uint64_t piece_bytes, uint32_t flags,
+                              flate_hip_one_writer **out) {
+  // every check before any HIP call
+  if (one_writer_open_check(c, wrap, piece_bytes, flags, out)) return FLATE_HIP_E_INVALID;
+  *out = nullptr;
+  c->hip_err.clear();
+  HIP_TRY(c, hipSetDevice(c->device));
+  flate_hip_one_writer *w = new flate_hip_one_writer();
+  w->ctx = c;
+  w->wrap = wrap;
+  w->flags = flags;
+  w->piece = piece_bytes;
+  int rc = ensure(c, w->state, sizeof(OneWriterState) + 64);
+  if (rc == FLATE_HIP_OK) rc = one_writer_fresh_state(w);
+  if (rc != FLATE_HIP_OK) {
+    delete w;
+    return rc;
+  }
+  *out = w;
+  return FLATE_HIP_OK;
+}
+
+int flate_hip_one_writer_reset(flate_hip_one_writer *w) {
+  if (!w) return FLATE_HIP_E_INVALID;
+  flate_hip_ctx *c = w->ctx;
+  c->hip_err.clear();
+  HIP_TRY(c, hipSetDevice(c->device));
+  return one_writer_fresh_state(w);
+}
+
+void flate_hip_one_writer_free(flate_hip_one_writer *w) {
+  if (!w) return;
+  (void)hipSetDevice(w->ctx->device);
+  delete w;
+}
+
+int flate_hip_one_writer_write(flate_hip_one_writer *w, const uint8_t *in, uint64_t in_len, int final_in, uint8_t *out,
+                               uint64_t out_cap, uint64_t *in_used, uint64_t *out_len, uint64_t *bit_off,
+                               uint32_t *n_pieces) {
+  // every check, and everything the rule decides, before any HIP call
+  if (one_writer_write_check(w, in, in_len, out, out_cap, in_used, out_len, n_pieces)) return FLATE_HIP_E_INVALID;
+  *in_used = 0, *out_len = 0, *n_pieces = 0;
+  const OneWriterPlan plan = one_writer_plan(w->s, in_len, final_in != 0, w->piece, w->wrap);
+  if (plan.action == kWriterReturn) return plan.status;
+  if (plan.action == kWriterNothing) return FLATE_HIP_OK;
+  flate_hip_ctx *c = w->ctx;
+  c->hip_err.clear();
+  try {
+    return one_writer_run(w, plan, in, out, out_cap, in_used, out_len, bit_off, n_pieces);
+  } catch (const std::exception &e) {  // (out of host memory in an index vector: nothing has been launched)
+    c->hip_err = e.what();
+    return FLATE_HIP_E_INTERNAL;
+  }
 }
 
 int flate_hip_lz77_matches(flate_hip_ctx *c, const uint8_t *in, const uint64_t *in_off, uint32_t n,

@@ -697,6 +697,50 @@ __global__ void one_part_hist_kernel(const uint64_t *out_off, uint64_t *tail_off
 __global__ void one_part_carry_kernel(OnePartParams Q, OneDecParams D);
 __global__ void one_part_verdict_kernel(OnePartParams Q);
 
+// ONE stream written in PARTS (flate_hip_one_writer_*; one_writer_kernels.hip; the rule: one_writer_rule.h).  A call is
+// the whole call's match finder and entropy stage over the pieces it consumes, the scan started at the carried bit
+// (SpliceParams::start_bit) and closed only by a final call (no_close), between four small kernels of its own:
+//   one_writer_begin_kernel   behind splice_zero_kernel, in front of the pack kernel: the header, or the carried bits
+//   one_writer_index_kernel   the scan's positions as bits of the raw stream
+//   one_writer_commit_kernel  behind the pack kernel and the part's checksum: room, closing block of a call without
+//                             pieces, trailer, the checksum join, the new carry, the result words
+//   one_writer_copy_kernel    device callers: the handle's buffer to `out`, the length read on the device
+struct OneWriterResult {     // the call's result words, read back
+  int32_t status;            // FLATE_HIP_OK, FLATE_HIP_STREAM_END, FLATE_HIP_E_OUT_TOO_SMALL (out_len: the bytes needed),
+                             // or the encoder's status word
+  uint32_t n_pieces;
+  uint64_t out_len;
+  uint64_t end_bit;          // of the raw stream: where the next piece, or the closing block, starts
+};
+struct OneWriterState {      // per handle, in device memory; written by one_writer_commit_kernel alone
+  uint64_t emitted;          // bytes of the member delivered so far
+  uint64_t total_in;         // bytes of input consumed so far
+  uint32_t sum;              // their checksum
+  uint32_t carry;            // the last, incomplete byte ...
+  uint32_t carry_bits;       // ... and how many of its bits count (0..7)
+  uint32_t part_sum;         // the checksum of the call's input (checksum_device)
+  OneWriterResult res;
+};
+struct OneWriterParams {
+  OneWriterState *st;
+  uint8_t *buf;               // the handle's buffer: the call's bytes from byte 0
+  const uint64_t *stream_bit; // n_pieces + 1: splice_scan_kernel's positions in buf (not read when n_pieces == 0)
+  uint64_t *bit_idx;          // n_pieces + 1: the same as bits of the raw stream
+  const int *status;          // the encoder's status word
+  uint64_t start_bit;         // SpliceParams::start_bit
+  uint64_t in_used;           // bytes of input the call consumes
+  uint64_t out_cap;
+  uint32_t n_pieces;
+  uint32_t wrap;
+  uint32_t header;            // the call's bytes start with the container's header
+  uint32_t close;             // ... and end with the closing block and the trailer
+};
+struct X2n;  // (checksum_clip.h)
+__global__ void one_writer_begin_kernel(OneWriterParams Q);
+__global__ void one_writer_index_kernel(OneWriterParams Q);
+__global__ void one_writer_commit_kernel(OneWriterParams Q, X2n T);
+__global__ void one_writer_copy_kernel(const OneWriterState *st, const uint8_t *buf, uint8_t *out);
+
 // The seek index of one long stream (one_seek_kernels.hip; flate_hip_inflate_one_seek_index / _ranges; the rule and
 // the index's layout: seek_index_rule.h).
 // BUILD.  one_seek_points_kernel (POINTS, one workgroup): mark by the point rule, scan, compact -> point_unit, n_points.

@@ -594,7 +594,20 @@ class OnePartsCalls:
         return OneReader(self, wrap, device)
 
 
-class FlateEngine(OneSeekCalls, GzFileCalls, GzFileSerialCalls, GzFileSeekCalls, ZipUnitsCalls, GroupedCalls, OnePartsCalls):
+class OneWriterCalls:
+    """One long stream written in parts: the method FlateEngine inherits.  It stands in a class of its own so that its
+    marshalling has its own recorded scenarios (tests/engine_trace_one_writer.py) beside the ones of the methods that
+    were there before (tests/engine_trace.py)."""
+
+    def open_one_writer(self, wrap="gzip", piece_bytes=0, device=False, compat_go=False):
+        """ONE long stream ("raw", "zlib" or "gzip") written in parts through bounded buffers at deflate_spliced_framed's
+        speed (flate_hip_one_writer_*): see OneWriter.  piece_bytes: the bytes of a piece (0: 65535).  device: every
+        part and every output is a torch CUDA tensor."""
+        return OneWriter(self, wrap, piece_bytes, device, compat_go)
+
+
+class FlateEngine(OneSeekCalls, GzFileCalls, GzFileSerialCalls, GzFileSeekCalls, ZipUnitsCalls, GroupedCalls, OnePartsCalls,
+                  OneWriterCalls):
     """One engine = one flate_hip_ctx = one GPU + one HIP stream."""
 
     def __init__(self, device=0):
@@ -1415,6 +1428,76 @@ class OneReader:
     def close(self):
         if self._h:
             self._L.flate_hip_one_reader_free(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+OnePartWrite = collections.namedtuple("OnePartWrite", "rc out_len n_pieces bit_off")
+
+
+def one_writer_bound(in_len, piece_bytes=0):
+    """Room that holds any OneWriter.write of at most in_len bytes (flate_hip_one_writer_bound)."""
+    return int(_lib.load().flate_hip_one_writer_bound(int(in_len), int(piece_bytes)))
+
+
+class OneWriter:
+    """deflate_spliced_framed for a stream the caller holds a part at a time (flate_hip_one_writer_*): every write()
+    compresses the whole pieces of piece_bytes bytes that the part holds, in parallel, and the handle carries the last
+    incomplete byte, the running checksum and the lengths on the device.  The concatenation of what the writes return
+    is, byte for byte, deflate_spliced_framed of the whole input cut every piece_bytes bytes, whatever the parts.
+    write(part, final, out, out_cap, index) -> (in_used, out, OnePartWrite(rc, out_len, n_pieces, bit_off)): `part`
+    BEGINS with the bytes the last write left unused (part[in_used:], then new bytes); the bytes are out[:out_len]; rc 0
+    = go on, 1 = the stream is finished (final=True: closing block and trailer written), -2 = out_cap is too small
+    (out_len: the bytes needed; nothing changed).  index=True: bit_off holds the start bits of the n_pieces pieces,
+    counted from the raw stream's first byte, and on a final write one entry more, where the closing block starts; else
+    None.  out=None: room for out_cap bytes (default: the part and an eighth), and with no out_cap a call that does
+    not fit gets a second call with room for it."""
+
+    def __init__(self, eng, wrap="gzip", piece_bytes=0, device=False, compat_go=False):
+        self._eng, self._L = eng, eng._L
+        self._device = bool(device)
+        self.piece_bytes = int(piece_bytes) or MAX_STORE_BLOCK_SIZE
+        self._h = C.c_void_p()
+        eng._check(self._L.flate_hip_one_writer_open(eng._ctx, WRAPS[wrap], int(piece_bytes),
+                                                     eng._flags(compat_go, False, self._device), C.byref(self._h)))
+
+    def write(self, part, final=False, out=None, out_cap=None, index=False):
+        if part is None and self._device:
+            import torch
+            part = torch.empty(0, dtype=torch.uint8, device="cuda:%d" % self._eng.device)
+        part, in_ptr, n, device = _in_buf(b"" if part is None else part, accept_bytes=True, null_if_empty=True)
+        if device != self._device:
+            raise FlateError(E_INVALID, "OneWriter.write: the part is not on the side the writer was opened for")
+        used, ol, npc = C.c_uint64(0), C.c_uint64(0), C.c_uint32(0)
+        bit_off = np.zeros(n // self.piece_bytes + 2, dtype=np.uint64)
+
+        def call(out_ptr, cap):
+            rc = self._eng._tolerate(self._L.flate_hip_one_writer_write(
+                self._h, in_ptr, n, 1 if final else 0, out_ptr, cap, C.byref(used), C.byref(ol),
+                bit_off.ctypes.data if index else None, C.byref(npc)), 1, E_OUT_TOO_SMALL)  # (1: the stream is finished)
+            k = int(npc.value)
+            return OnePartWrite(rc, int(ol.value), k, bit_off[:k + (1 if rc == 1 else 0)] if index and rc >= 0 else None)
+
+        size = n + n // 8 + 4096 if out_cap is None else int(out_cap)
+        buf, ptr, cap = _out_buf(out, part, size, out_cap, 0, "OneWriter.write", floor=1)
+        res = call(ptr, cap)
+        if res.rc == E_OUT_TOO_SMALL and out is None and out_cap is None:
+            buf, ptr, cap = _out_buf(None, part, res.out_len, None, 0, "OneWriter.write", floor=1)
+            res = call(ptr, cap)
+        return int(used.value), (buf[:0] if res.rc == E_OUT_TOO_SMALL else buf[:res.out_len]), res
+
+    def reset(self):
+        """A fresh stream on the same handle: same wrap, same piece size, same side, same flags."""
+        self._eng._check(self._L.flate_hip_one_writer_reset(self._h))
+
+    def close(self):
+        if self._h:
+            self._L.flate_hip_one_writer_free(self._h)
             self._h = C.c_void_p()
 
     def __del__(self):

@@ -958,6 +958,100 @@ class OneReader {
   Err err_;
 };
 
+// A Writer (writer.mbt:45,53: write, close) over ONE LONG raw, zlib or gzip stream at the batch encoder's speed
+// (flate_hip_one_writer_*): the stream is cut into independent pieces of piece_bytes bytes (0: 65535), every step
+// compresses, in parallel, the whole pieces that are staged, and the handle carries the last incomplete byte, the running
+// checksum and the lengths on the device.  write() stages the bytes and, once part_bytes of them are there, hands the
+// whole pieces to the GPU and what they compress to -- whole bytes -- to the sink; the remainder below a piece stays
+// staged on the host.  close() sends the final call: the last, shorter piece, the closing block and the trailer.  The
+// sink sees the bytes of compress_spliced over the same pieces inside the container, whatever the sizes of the writes.
+// Sticky errors as Writer's.
+class OneWriter {
+ public:
+  OneWriter(ByteSink &w, Engine &e, Wrap wrap, uint64_t piece_bytes = 0, uint32_t flags = 0, size_t part_bytes = 1u << 26)
+      : w_(&w), e_(e), wrap_(wrap), piece_(piece_bytes), flags_(flags & ~FLATE_HIP_DEVICE_PTRS) {
+    const uint64_t P = piece_bytes ? piece_bytes : 65535u;
+    part_ = part_bytes < P ? (size_t)P : part_bytes;
+  }
+  ~OneWriter() { flate_hip_one_writer_free(h_); }
+  OneWriter(const OneWriter &) = delete;
+  OneWriter &operator=(const OneWriter &) = delete;
+
+  std::pair<int, Err> write(const uint8_t *p, size_t n) {
+    if (err_) return {0, err_};
+    pending_.insert(pending_.end(), p, p + n);
+    if (pending_.size() >= part_) {
+      if (Err er = feed(false)) {
+        err_ = er;
+        return {0, err_};
+      }
+    }
+    return {(int)n, std::nullopt};
+  }
+  std::pair<int, Err> write(const std::vector<uint8_t> &b) { return write(b.data(), b.size()); }
+
+  Err close() {
+    if (err_ && *err_ == writer_closed_error()) return std::nullopt;
+    if (err_) return err_;
+    if (Err er = feed(true)) {
+      err_ = er;
+      return err_;
+    }
+    err_ = writer_closed_error();
+    return std::nullopt;
+  }
+  // a fresh stream into `w` on the same handle: same wrap, same piece size, same flags (what is staged is dropped)
+  Err reset(ByteSink &w) {
+    w_ = &w;
+    pending_.clear();
+    err_ = std::nullopt;
+    emitted_ = 0;
+    if (h_) {
+      const int rc = flate_hip_one_writer_reset(h_);
+      if (rc != 0) err_ = make_error(e_, rc);
+    }
+    return err_;
+  }
+  // compressed bytes handed to the sink so far, the calls made, the pieces compressed
+  uint64_t emitted() const { return emitted_; }
+  uint64_t calls() const { return calls_; }
+  uint64_t pieces() const { return pieces_; }
+  size_t resident_bytes() const { return pending_.capacity() + out_.capacity(); }
+
+ private:
+  Err feed(bool final) {
+    if (!e_.ok()) return make_error(e_, e_.status());
+    if (!h_) {
+      const int rc = flate_hip_one_writer_open(e_.ctx(), wrap_code(wrap_), piece_, flags_, &h_);
+      if (rc != 0) return make_error(e_, rc);
+    }
+    const size_t room = flate_hip_one_writer_bound(pending_.size(), (size_t)piece_);
+    if (out_.size() < room) out_.resize(room);
+    uint64_t used = 0, len = 0;
+    uint32_t k = 0;
+    ++calls_;
+    const int rc = flate_hip_one_writer_write(h_, pending_.data(), pending_.size(), final ? 1 : 0, out_.data(), out_.size(),
+                                              &used, &len, nullptr, &k);
+    if (rc != FLATE_HIP_OK && rc != FLATE_HIP_STREAM_END) return make_error(e_, rc);
+    pending_.erase(pending_.begin(), pending_.begin() + (size_t)used);
+    emitted_ += len;
+    pieces_ += k;
+    if (!len) return std::nullopt;
+    auto r = w_->write(out_.data(), (size_t)len);
+    return r.second;
+  }
+  ByteSink *w_;
+  Engine &e_;
+  Wrap wrap_;
+  uint64_t piece_;
+  uint32_t flags_;
+  size_t part_;
+  flate_hip_one_writer *h_ = nullptr;
+  uint64_t emitted_ = 0, calls_ = 0, pieces_ = 0;
+  std::vector<uint8_t> pending_, out_;
+  Err err_;
+};
+
 // One spliced stream decoded in parallel from its index (flate_hip_inflate_spliced).
 inline Err decompress_spliced(Engine &e, const std::vector<uint8_t> &stream, const std::vector<uint64_t> &bit_off,
                               const std::vector<uint64_t> &sizes, std::vector<uint8_t> &out) {
