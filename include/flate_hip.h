@@ -1067,7 +1067,7 @@ void flate_hip_one_reader_free(flate_hip_one_reader *reader);
  *   with its own end, straight into the dense scratch, every unit in a slot of exactly its size.  CHECK per unit, then
  *   GATHER: every range's one run of the scratch into out.  Locate, select and gather are counted in no profiling
  *   stage; FLATE_HIP_STAGE_INFLATE is DECODE (of several rounds the last).
- *   Out of scope: delivering the output or judging the trailer from the build call; compressed or sparse windows;
+ *   Out of scope: delivering the output or judging the trailer from the build call (packed windows: below);
  *   importing or exporting other tools' index formats (multi-member input: flate_hip_gzfile_seek_index below); an index
  *   cached inside the ctx; uploading
  *   only the touched part of the stream from host memory; stored and fixed block starts as units; skipping TAIL for
@@ -1085,6 +1085,93 @@ int flate_hip_inflate_one_ranges(flate_hip_ctx *ctx, const uint8_t *in, uint64_t
                                  uint64_t windows_bytes, const uint64_t *begin, const uint64_t *end, uint32_t n_ranges,
                                  uint8_t *out, uint64_t out_cap, uint64_t *out_off, int32_t *range_status,
                                  uint32_t *n_decoded, uint32_t *bad_unit, uint32_t flags);
+
+/* -- Seek index: sparse, compressed windows packed and read on the device --------------
+ * The windows of a seek index are 32 KiB of raw output per point: at a small span they outweigh the file.  Three opt-in
+ * calls PACK them, UNPACK them and READ ranges straight through the packed form; the two calls above, the index (version
+ * 1) and the raw windows stay what they are.  The rule is written once, csrc/seek_pack_rule.h; the kernels are
+ * csrc/seek_pack_mark_kernel.inc (on the shared block reader) and csrc/seek_pack_kernels.hip.
+ *
+ * THE KEEP RULE (FLATE_HIP_SEEK_PACK_SPARSE).  Let P0 be the output offset of point p and [P0, P1) its segment.  A byte
+ * of block p - 1 is NEEDED iff some copy at output position q in [P0, min(P1, P0 + 32768)) has a source byte a in
+ * [q - dist, q - dist + len) with a < P0.  Later copies cannot reach the block (dist <= 32768); copies of copies are
+ * covered, because the first copy was counted where it happened.  A sparse block has every other byte set to zero: a
+ * read through it delivers the same bytes, because zeroed bytes are never read.
+ * THE EMPTY-BLOCK RULE.  A block all of whose bytes are zero (after sparsifying, or as it came) is stored as NO bytes and
+ * read back by zero fill without a decode.  Every other block is ONE raw DEFLATE stream: byte for byte what
+ * flate_hip_deflate_fast_batch writes under flags 0 for the block's 32768 bytes.
+ * THE PACK INDEX: a HOST array of 64-bit words: 0 the magic "FONESWPK" (little endian), 1 the version (1), 2 mode, 3
+ * n_blocks = n_points - 1, 4 packed_bytes, 5 kept_bytes (SPARSE: the needed bytes; else n_blocks * 32768), 6 .. 10 the
+ * binding to the seek index (its words 3, 6, 7, 8, 12: in_len, T, span, n, the unit rule), 11 .. 15 zero, then
+ * off[n_blocks + 1]: byte offsets into `packed`, off[0] = 0, non-decreasing, block b = packed[off[b], off[b + 1]):
+ * 17 + n_blocks words.  seek_pack_ok (host, O(n_blocks)) is seek_index_ok's counterpart.
+ *
+ * flate_hip_seek_windows_pack: PACK.  index / windows: what the build call returned.  in, windows and packed are host
+ * buffers, or device buffers under FLATE_HIP_DEVICE_PTRS, at any byte alignment; `in` may be NULL without SPARSE (the
+ * stream is only walked to mark; in_len and wrap are still the index's).  mode: FLATE_HIP_SEEK_PACK_COMPRESS, or
+ * _COMPRESS | _SPARSE.  Verdict, in this order.
+ *  1. FLATE_HIP_E_INVALID before any HIP call, nothing written: NULL ctx / pack_words / packed_bytes / kept_bytes; any
+ *     other mode; any flag but FLATE_HIP_DEVICE_PTRS; a wrap above _GZIP; SPARSE with in == NULL and in_len > 0; windows
+ *     == NULL with windows_bytes > 0, pack_index == NULL with pack_cap_words > 0, packed == NULL with packed_cap > 0; an
+ *     index that fails seek_index_ok or names an unknown unit rule.
+ *  2. pack_cap_words < 17 + n_blocks: FLATE_HIP_E_OUT_TOO_SMALL with *pack_words set.  (n_blocks == 0: the head and off =
+ *     {0}, *packed_bytes = 0, FLATE_HIP_OK; nothing is walked.)
+ *  3. With SPARSE: the stream is not the index's -- verdict 3 of flate_hip_inflate_one_ranges, or a walk that fails,
+ *     meets a distance in front of the stream, or ends a segment anywhere but at the segment's end bit with exactly the
+ *     segment's bytes: FLATE_HIP_E_CORRUPT.
+ *  4. packed_cap below the total: FLATE_HIP_E_OUT_TOO_SMALL with *packed_bytes = the bytes needed (the encoder's scan
+ *     knows every size before it packs).  The exact total is enough; flate_hip_seek_windows_pack_bound(n_blocks) =
+ *     n_blocks * flate_hip_deflate_bound(32768) (host only) is always enough; nothing outside packed[0, packed_cap) is
+ *     ever written.
+ *  5. FLATE_HIP_OK: pack_index, packed[0, *packed_bytes), *pack_words, *kept_bytes.
+ *   How: MARK + SPARSIFY, one wavefront per point p >= 1: a token walk from unit_bit[point_unit[p]] through block and
+ *   unit headers alike (the unit rule does not matter) that stops once 32768 bytes of output have passed, at the
+ *   segment's end bit, or behind the final block; no window, no store of the stream's output; the keep mask is 4 KiB of
+ *   bits in LDS; then the same workgroup reads the raw block, zeroes what is not kept, writes a dense scratch slot and
+ *   records "has a non-zero byte" and the kept count.  Without SPARSE only the non-zero test runs.  ONE read-back of the
+ *   per-block records; the non-empty blocks, compacted in order, go as one batch through the unchanged encode path
+ *   straight into `packed` or its staged copy; the host spreads the batch's offsets over off[].  Every loop consumes
+ *   input bits or ends.  A segment whose first 32768 bytes of output take more than 2^30 bytes of input is refused as
+ *   corrupt.
+ *
+ * flate_hip_seek_windows_unpack: (pack_index, packed) -> all n_blocks blocks in the raw layout: the sparsified windows,
+ * or with COMPRESS alone the original windows byte for byte -- what the unchanged flate_hip_inflate_one_ranges takes.
+ * FLATE_HIP_E_INVALID before any HIP call (NULL ctx / windows_bytes, a flag but FLATE_HIP_DEVICE_PTRS, a NULL buffer with
+ * a size, a pack index that fails seek_pack_self_ok); windows_cap < n_blocks * 32768: FLATE_HIP_E_OUT_TOO_SMALL with
+ * *windows_bytes set (the size query too); a block that does not inflate with status 0 to exactly 32768 bytes:
+ * FLATE_HIP_E_CORRUPT with *bad_block (may be NULL) the first one, every other block exact.
+ *
+ * flate_hip_inflate_one_ranges_packed: flate_hip_inflate_one_ranges with (pack_index, pack_words, packed, packed_bytes)
+ * in the place of (windows, windows_bytes).  Everything else is that call's: the arguments and the verdict order,
+ * out_off, range_status, n_decoded, bad_unit and what is written where; verdict 1 additionally runs seek_pack_ok against
+ * the index.  Between SELECT's read-back and the rounds the selected points' blocks are made: the non-empty ones by ONE
+ * launch of the batch decoders into a dense stage of 32 KiB per SELECTED point, the empty ones by zero fill; the
+ * rounds' window copy reads the stage through a point -> slot table, so device scratch for windows grows with the
+ * selection, not with n_points, and with host pointers only the selected blocks' streams are uploaded.  A block that
+ * does not inflate with status 0 to exactly 32768 bytes makes its point's unit a bad unit of status
+ * FLATE_HIP_E_CORRUPT: the call returns the first bad unit's status in stream order with *bad_unit, every range that
+ * decodes that unit gets that range_status and unspecified bytes, every other range is exact.  Delivered bytes equal
+ * the raw call's for both modes.
+ *   Out of scope: the gzfile seek index (its block numbering differs; the pack head's binding leaves room); building the
+ *   packed form without the raw windows ever existing; checksums over windows; other tools' index formats; the MoonBit
+ *   binding. */
+#define FLATE_HIP_SEEK_PACK_COMPRESS 1u /* every block one raw DEFLATE stream */
+#define FLATE_HIP_SEEK_PACK_SPARSE 2u   /* with _COMPRESS: unread bytes become zero first */
+size_t flate_hip_seek_windows_pack_bound(uint64_t n_blocks);
+int flate_hip_seek_windows_pack(flate_hip_ctx *ctx, const uint8_t *in, uint64_t in_len, uint32_t wrap,
+                                const uint64_t *index, uint64_t index_words, const uint8_t *windows,
+                                uint64_t windows_bytes, uint32_t mode, uint64_t *pack_index, uint64_t pack_cap_words,
+                                uint64_t *pack_words, uint8_t *packed, uint64_t packed_cap, uint64_t *packed_bytes,
+                                uint64_t *kept_bytes, uint32_t flags);
+int flate_hip_seek_windows_unpack(flate_hip_ctx *ctx, const uint64_t *pack_index, uint64_t pack_words,
+                                  const uint8_t *packed, uint64_t packed_bytes, uint8_t *windows, uint64_t windows_cap,
+                                  uint64_t *windows_bytes, uint32_t *bad_block, uint32_t flags);
+int flate_hip_inflate_one_ranges_packed(flate_hip_ctx *ctx, const uint8_t *in, uint64_t in_len, uint32_t wrap,
+                                        const uint64_t *index, uint64_t index_words, const uint64_t *pack_index,
+                                        uint64_t pack_words, const uint8_t *packed, uint64_t packed_bytes,
+                                        const uint64_t *begin, const uint64_t *end, uint32_t n_ranges, uint8_t *out,
+                                        uint64_t out_cap, uint64_t *out_off, int32_t *range_status, uint32_t *n_decoded,
+                                        uint32_t *bad_unit, uint32_t flags);
 
 /* -- Any gzip file: units found across member boundaries ------------------------------
  * RFC 1952 makes a gzip file a series of members, and everyday files are a few long members, or long and short ones

@@ -5,7 +5,8 @@ The hyphen in the directory name means: importlib.import_module("moonbit-flate_a
 """
 from .engine import (FlateEngine, FlateError, StreamWriter, build_id, deflate_bound, synth, uniform_offsets, lz_chunks,
                      tokens_from_matches, SYNTH_KINDS, SEED_TEXT, SEED_RAND, STAGES, NO_DICT, zip_bound, ZIP_ENTRY,
-                     SEEK_SPAN_DEFAULT, SEEK_SPAN_NONE, SeekIndex, OneRanges, GzFileSeekIndex)
+                     SEEK_SPAN_DEFAULT, SEEK_SPAN_NONE, SeekIndex, OneRanges, GzFileSeekIndex,
+                     SEEK_PACK_COMPRESS, SEEK_PACK_SPARSE, SeekPack, SeekUnpack)
 from . import build as _build
 
 

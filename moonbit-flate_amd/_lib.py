@@ -75,6 +75,11 @@ def _signatures():
                                                  u32p, i32p, i64p, u32]),
         "flate_hip_inflate_one_ranges": (i, [vp, vp, u64, u32, vp, u64, vp, u64, vp, vp, u32, vp, u64, vp, vp, u32p, u32p,
                                              u32]),
+        "flate_hip_seek_windows_pack_bound": (sz, [u64]),
+        "flate_hip_seek_windows_pack": (i, [vp, vp, u64, u32, vp, u64, vp, u64, u32, vp, u64, u64p, vp, u64, u64p, u64p, u32]),
+        "flate_hip_seek_windows_unpack": (i, [vp, vp, u64, vp, u64, vp, u64, u64p, u32p, u32]),
+        "flate_hip_inflate_one_ranges_packed": (i, [vp, vp, u64, u32, vp, u64, vp, u64, vp, u64, vp, vp, u32, vp, u64, vp, vp,
+                                                    u32p, u32p, u32]),
         "flate_hip_gzfile_index": (i, [vp, vp, u64, u64, vp, vp, u64, vp, vp, u32p, u32p, u64p, u32p, i32p, u32p, i64p, i64p,
                                        u32]),
         "flate_hip_gzfile_read": (i, [vp, vp, u64, vp, u64, u64p, u32p, u32p, u32p, i32p, u32p, i64p, i64p, u32]),
@@ -118,7 +123,8 @@ MAY_BE_MISSING = [
     "flate_hip_zip_write_last_route", "flate_hip_one_reader_open", "flate_hip_one_reader_read",
     "flate_hip_one_reader_reset", "flate_hip_one_reader_free", "flate_hip_one_writer_bound",
     "flate_hip_one_writer_open", "flate_hip_one_writer_write", "flate_hip_one_writer_reset",
-    "flate_hip_one_writer_free",
+    "flate_hip_one_writer_free", "flate_hip_seek_windows_pack_bound", "flate_hip_seek_windows_pack",
+    "flate_hip_seek_windows_unpack", "flate_hip_inflate_one_ranges_packed",
 ]
 
 _lib = None

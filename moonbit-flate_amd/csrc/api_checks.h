@@ -9,6 +9,7 @@
 #include "one_parts_rule.h"
 #include "one_writer_rule.h"
 #include "seek_index_rule.h"
+#include "seek_pack_rule.h"
 #include "splice_rule.h"
 
 namespace flate {
@@ -258,6 +259,44 @@ inline int one_ranges_args(const uint8_t *in, uint64_t in_len, uint32_t wrap, co
   if (wrap > FLATE_HIP_WRAP_GZIP || (windows_bytes && !windows)) return FLATE_HIP_E_INVALID;
   return seek_index_ok(index, index_words, windows_bytes, wrap, in_len) && seek_index_rule_ok(index) ? FLATE_HIP_OK
                                                                                                      : FLATE_HIP_E_INVALID;
+}
+
+// ---- the packed windows of that index (flate_hip_seek_windows_pack / _unpack, flate_hip_inflate_one_ranges_packed;
+// ---- seek_pack_rule.h) ----
+
+// the pack: the mode, the result words, every buffer with its size, then the index itself (seek_index_ok, O(n)); `in`
+// may be NULL without FLATE_HIP_SEEK_PACK_SPARSE, for the stream is only walked to mark
+inline int seek_pack_args(const uint8_t *in, uint64_t in_len, uint32_t wrap, const uint64_t *index, uint64_t index_words,
+                          const uint8_t *windows, uint64_t windows_bytes, uint32_t mode, const uint64_t *pack_index,
+                          uint64_t pack_cap_words, const uint64_t *pack_words, const uint8_t *packed, uint64_t packed_cap,
+                          const uint64_t *packed_bytes, const uint64_t *kept_bytes, uint32_t flags) {
+  if (!pack_words || !packed_bytes || !kept_bytes || !seek_pack_mode_ok(mode)) return FLATE_HIP_E_INVALID;
+  if ((flags & ~FLATE_HIP_DEVICE_PTRS) || wrap > FLATE_HIP_WRAP_GZIP) return FLATE_HIP_E_INVALID;
+  if ((mode & kSeekPackSparse) && in_len && !in) return FLATE_HIP_E_INVALID;
+  if ((windows_bytes && !windows) || (pack_cap_words && !pack_index) || (packed_cap && !packed)) return FLATE_HIP_E_INVALID;
+  return seek_index_ok(index, index_words, windows_bytes, wrap, in_len) && seek_index_rule_ok(index) ? FLATE_HIP_OK
+                                                                                                     : FLATE_HIP_E_INVALID;
+}
+// the unpack: the pack index by itself (seek_pack_self_ok, O(n_blocks))
+inline int seek_unpack_args(const uint64_t *pack_index, uint64_t pack_words, const uint8_t *packed, uint64_t packed_bytes,
+                            const uint8_t *windows, uint64_t windows_cap, const uint64_t *windows_bytes, uint32_t flags) {
+  if (!windows_bytes || (flags & ~FLATE_HIP_DEVICE_PTRS)) return FLATE_HIP_E_INVALID;
+  if ((packed_bytes && !packed) || (windows_cap && !windows)) return FLATE_HIP_E_INVALID;
+  return seek_pack_self_ok(pack_index, pack_words, packed_bytes) ? FLATE_HIP_OK : FLATE_HIP_E_INVALID;
+}
+// the read: one_ranges_args with the windows the pack index stands for, then seek_pack_ok against the index
+inline int one_ranges_packed_args(const uint8_t *in, uint64_t in_len, uint32_t wrap, const uint64_t *index,
+                                  uint64_t index_words, const uint64_t *pack_index, uint64_t pack_words,
+                                  const uint8_t *packed, uint64_t packed_bytes, const uint64_t *begin, const uint64_t *end,
+                                  uint32_t n_ranges, const uint8_t *out, uint64_t out_cap, const uint64_t *out_off,
+                                  uint32_t flags) {
+  const int rc = bgzf_ranges_args(in, in_len, FLATE_HIP_BGZF_POS_BYTES, begin, end, n_ranges, out, out_cap, out_off, flags);
+  if (rc) return rc;
+  if (wrap > FLATE_HIP_WRAP_GZIP || (packed_bytes && !packed)) return FLATE_HIP_E_INVALID;
+  if (!index || index_words < kSeekHeadWords) return FLATE_HIP_E_INVALID;
+  if (!seek_index_ok(index, index_words, seek_windows_bytes(index[kSeekPointsAt]), wrap, in_len) || !seek_index_rule_ok(index))
+    return FLATE_HIP_E_INVALID;
+  return seek_pack_ok(pack_index, pack_words, packed_bytes, index) ? FLATE_HIP_OK : FLATE_HIP_E_INVALID;
 }
 
 // ---- the seek index of a gzip file of any members (flate_hip_gzfile_seek_index / _ranges; gzfile_seek_rule.h) ----

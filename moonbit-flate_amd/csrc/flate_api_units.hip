@@ -186,6 +186,9 @@ struct SeekRangesOut {
   int32_t *range_status;
   uint32_t *bad_unit;
   bool dev;
+  // packed windows: the places in the list of the points whose block did not inflate -- FLATE_HIP_E_CORRUPT there
+  const uint32_t *bad_place = nullptr;
+  uint32_t n_bad_place = 0;
 };
 
 // The rounds over the ns selected units and what follows them: `seeds` (the caller's seed and load kernels, which set
@@ -220,6 +223,7 @@ int seek_ranges_decode(flate_hip_ctx *c, OneDecParams &D, OneSeekRoundParams &S,
   bool used[FLATE_HIP_STAGE_COUNT] = {false, false, false, false};
   used[FLATE_HIP_STAGE_INFLATE] = true;
   if (c->profiling && (rc = collect_timing(c, used))) return rc;
+  for (uint32_t j = 0; j < O.n_bad_place; ++j) st[O.bad_place[j]] = FLATE_HIP_E_CORRUPT;
   const uint32_t bad = range_statuses(st.data(), ns, O.r_lo, O.r_hi, O.nr, O.range_status, nullptr);
   if (bad == ns) return FLATE_HIP_OK;
   if (O.bad_unit) *O.bad_unit = O.sel[bad];
@@ -512,18 +516,27 @@ int flate_hip_inflate_one_seek_index(flate_hip_ctx *c, const uint8_t *in, uint64
   }
 }
 
-// Random access through the seek index: locate, select, layout (one_seek_kernels.hip), ONE read-back (the parsed
-// container, the ranges' layout, the unit list), rounds of TAIL / segmented scan / DECODE over the list into a dense
-// scratch, the per-unit check, the gather.
-int flate_hip_inflate_one_ranges(flate_hip_ctx *c, const uint8_t *in, uint64_t in_len, uint32_t wrap, const uint64_t *index,
-                                 uint64_t index_words, const uint8_t *windows, uint64_t windows_bytes, const uint64_t *begin,
-                                 const uint64_t *end, uint32_t n_ranges, uint8_t *out, uint64_t out_cap, uint64_t *out_off,
-                                 int32_t *range_status, uint32_t *n_decoded, uint32_t *bad_unit, uint32_t flags) {
-  // every check before any HIP call
-  if (!c) return FLATE_HIP_E_INVALID;
-  int rc = one_ranges_args(in, in_len, wrap, index, index_words, windows, windows_bytes, begin, end, n_ranges, out, out_cap,
-                           out_off, flags);
-  if (rc) return rc;
+}  // extern "C"
+
+namespace {
+
+// The windows of the selected points as the rounds of a read load them: the raw blocks (d_slot_of == null: block p - 1
+// of d_windows), or a dense stage of the SELECTED points' blocks with the point -> slot table (packed windows).
+struct OneRangesWin {
+  const uint8_t *d_windows = nullptr;
+  const uint32_t *d_slot_of = nullptr;
+  std::vector<uint32_t> bad_place;  // packed: the places in the list of the points whose block did not inflate
+};
+
+// Random access through the seek index, behind the argument checks: locate, select, layout (one_seek_kernels.hip), ONE
+// read-back (the parsed container, the ranges' layout, the unit list), win(sel, ns, h_point, np, W) -- the windows of
+// the selected points, once the host has the selection --, rounds of TAIL / segmented scan / DECODE over the list into
+// a dense scratch, the per-unit check, the gather.
+template <class Win>
+int one_ranges_run(flate_hip_ctx *c, const uint8_t *in, uint64_t in_len, uint32_t wrap, const uint64_t *index,
+                   const uint64_t *begin, const uint64_t *end, uint32_t n_ranges, uint8_t *out, uint64_t out_cap,
+                   uint64_t *out_off, int32_t *range_status, uint32_t *n_decoded, uint32_t *bad_unit, uint32_t flags, Win win) {
+  int rc;
   c->hip_err.clear();
   if (n_decoded) *n_decoded = 0;
   if (bad_unit) *bad_unit = 0xffffffffu;
@@ -610,26 +623,8 @@ int flate_hip_inflate_one_ranges(flate_hip_ctx *c, const uint8_t *in, uint64_t i
     if (RH.out_total > out_cap) return FLATE_HIP_E_OUT_TOO_SMALL;  // (the size query too: nothing is decoded)
     if (ns == 0 || RH.out_total == 0) return FLATE_HIP_OK;        // (no range holds a byte)
 
-    // the windows: the caller's device buffer, or the blocks of the selected points uploaded into a staged copy
-    const uint8_t *d_windows = windows;
-    if (!dev && windows_bytes) {
-      if ((rc = ensure(c, c->d_one_seek_win, windows_bytes + 16))) return rc;
-      uint8_t *stage = (uint8_t *)c->d_one_seek_win.p;
-      d_windows = stage;
-      std::vector<uint32_t> ps;  // the selected points behind point 0, rising
-      uint32_t p = 1;
-      for (uint32_t i = 0; i < ns && p < np; ++i) {
-        while (p < np && h_point[p] < sel[i]) ++p;
-        if (p < np && h_point[p] == sel[i]) ps.push_back(p);
-      }
-      for (size_t a = 0; a < ps.size();) {  // neighbours in the index travel as one copy
-        size_t b = a + 1;
-        while (b < ps.size() && ps[b] == ps[b - 1] + 1u) ++b;
-        const uint64_t at = (uint64_t)(ps[a] - 1u) * kSeekWindow, len = (uint64_t)(b - a) * kSeekWindow;
-        HIP_TRY(c, hipMemcpyAsync(stage + at, windows + at, len, hipMemcpyHostToDevice, c->stream));
-        a = b;
-      }
-    }
+    OneRangesWin W;
+    if ((rc = win(sel, ns, h_point, np, W))) return rc;
 
     const uint32_t per_round = unit_per_round(c, ns);
     OneDecParams D{};
@@ -641,19 +636,400 @@ int flate_hip_inflate_one_ranges(flate_hip_ctx *c, const uint8_t *in, uint64_t i
     if ((rc = unit_dec_params(c, D, d_in, d_one, Q.unit_bit, Q.out_off, stored, false))) return rc;
     D.unit_list = Q.sel_unit;
     S.Q = Q;
-    S.windows = d_windows;
+    S.windows = W.d_windows;
     auto seeds = [&](uint32_t i0, uint32_t count) {
       S.i0 = i0, S.count = count;
       hipLaunchKernelGGL(one_seek_seed_kernel, dim3((count + 255u) / 256u), dim3(256), 0, c->stream, S);
-      hipLaunchKernelGGL(one_seek_load_kernel, dim3(seek_load_blocks(count)), dim3(256), 0, c->stream, S);
+      if (W.d_slot_of)
+        hipLaunchKernelGGL(seek_pack_load_kernel, dim3(seek_load_blocks(count)), dim3(256), 0, c->stream, S, W.d_slot_of);
+      else
+        hipLaunchKernelGGL(one_seek_load_kernel, dim3(seek_load_blocks(count)), dim3(256), 0, c->stream, S);
       return FLATE_HIP_OK;
     };
-    const SeekRangesOut O{out, nr, RH.out_total, RH.scratch_total, r_lo, r_hi, sel, range_status, bad_unit, dev};
+    SeekRangesOut O{out, nr, RH.out_total, RH.scratch_total, r_lo, r_hi, sel, range_status, bad_unit, dev};
+    O.bad_place = W.bad_place.data();
+    O.n_bad_place = (uint32_t)W.bad_place.size();
     return seek_ranges_decode(c, D, S, dec, per_round, ns, d_in + raw_off, raw_end - raw_off, O, seeds);
   } catch (const std::exception &e) {
     c->hip_err = e.what();
     return FLATE_HIP_E_INTERNAL;
   }
+}
+
+// the selected points behind point 0, rising, with their places in the list
+void selected_points(const uint32_t *sel, uint32_t ns, const uint64_t *h_point, uint32_t np, std::vector<uint32_t> &ps,
+                     std::vector<uint32_t> *places = nullptr) {
+  uint32_t p = 1;
+  for (uint32_t i = 0; i < ns && p < np; ++i) {
+    while (p < np && h_point[p] < sel[i]) ++p;
+    if (p < np && h_point[p] == sel[i]) {
+      ps.push_back(p);
+      if (places) places->push_back(i);
+    }
+  }
+}
+
+}  // namespace
+
+extern "C" {
+
+int flate_hip_inflate_one_ranges(flate_hip_ctx *c, const uint8_t *in, uint64_t in_len, uint32_t wrap, const uint64_t *index,
+                                 uint64_t index_words, const uint8_t *windows, uint64_t windows_bytes, const uint64_t *begin,
+                                 const uint64_t *end, uint32_t n_ranges, uint8_t *out, uint64_t out_cap, uint64_t *out_off,
+                                 int32_t *range_status, uint32_t *n_decoded, uint32_t *bad_unit, uint32_t flags) {
+  // every check before any HIP call
+  if (!c) return FLATE_HIP_E_INVALID;
+  const int rc0 = one_ranges_args(in, in_len, wrap, index, index_words, windows, windows_bytes, begin, end, n_ranges, out,
+                                  out_cap, out_off, flags);
+  if (rc0) return rc0;
+  const bool dev = (flags & FLATE_HIP_DEVICE_PTRS) != 0;
+  // the windows: the caller's device buffer, or the blocks of the selected points uploaded into a staged copy
+  auto win = [&](const uint32_t *sel, uint32_t ns, const uint64_t *h_point, uint32_t np, OneRangesWin &W) -> int {
+    W.d_windows = windows;
+    if (dev || !windows_bytes) return FLATE_HIP_OK;
+    int rc;
+    if ((rc = ensure(c, c->d_one_seek_win, windows_bytes + 16))) return rc;
+    uint8_t *stage = (uint8_t *)c->d_one_seek_win.p;
+    W.d_windows = stage;
+    std::vector<uint32_t> ps;
+    selected_points(sel, ns, h_point, np, ps);
+    for (size_t a = 0; a < ps.size();) {  // neighbours in the index travel as one copy
+      size_t b = a + 1;
+      while (b < ps.size() && ps[b] == ps[b - 1] + 1u) ++b;
+      const uint64_t at = (uint64_t)(ps[a] - 1u) * kSeekWindow, len = (uint64_t)(b - a) * kSeekWindow;
+      HIP_TRY(c, hipMemcpyAsync(stage + at, windows + at, len, hipMemcpyHostToDevice, c->stream));
+      a = b;
+    }
+    return FLATE_HIP_OK;
+  };
+  return one_ranges_run(c, in, in_len, wrap, index, begin, end, n_ranges, out, out_cap, out_off, range_status, n_decoded,
+                        bad_unit, flags, win);
+}
+
+}  // extern "C"
+
+// ---- the PACKED windows of the seek index (seek_pack_rule.h; seek_pack_mark_kernel.inc, seek_pack_kernels.hip) ----
+namespace {
+
+// The non-empty blocks among the nb of a pack index, rising, and the batch decoders' view of them: stream i is
+// packed[off[b_i], off[b_i + 1]) -- the empty blocks between two of them have no bytes, so the streams lie back to back.
+struct PackedBlocks {
+  std::vector<uint32_t> b;
+  std::vector<uint64_t> in_off;
+};
+PackedBlocks packed_blocks(const uint64_t *off, uint32_t nb) {
+  PackedBlocks P;
+  for (uint32_t b = 0; b < nb; ++b)
+    if (off[b + 1] > off[b]) {
+      P.b.push_back(b);
+      P.in_off.push_back(off[b]);
+    }
+  P.in_off.push_back(off[nb]);
+  return P;
+}
+
+// One launch of the batch decoders: stream i of d_streams (in_off, n + 1) into slot i of 32768 bytes of d_slots.
+// good[i]: it inflates with status 0 to exactly 32768 bytes.
+int inflate_blocks(flate_hip_ctx *c, const uint8_t *d_streams, const std::vector<uint64_t> &in_off, uint8_t *d_slots,
+                   const std::vector<uint64_t> &slot_off, std::vector<uint8_t> &good) {
+  const uint32_t n = (uint32_t)in_off.size() - 1u;
+  std::vector<uint64_t> out_len(n, 0);
+  std::vector<int32_t> status(n, 0);
+  std::vector<int64_t> err_off(n, -1);
+  good.assign(n, 0);
+  if (n == 0) return FLATE_HIP_OK;
+  const int rc = flate_hip_inflate_batch(c, d_streams, in_off.data(), n, d_slots, slot_off.data(), out_len.data(), status.data(),
+                                         err_off.data(), FLATE_HIP_DEVICE_PTRS);
+  int first = 0;  // (the batch call returns its first failing stream's status: that is a verdict per block, not the call's)
+  for (uint32_t i = 0; i < n && !first; ++i) first = status[i];
+  if (rc && rc != first) return rc;
+  for (uint32_t i = 0; i < n; ++i) good[i] = status[i] == 0 && out_len[i] == kSeekWindow;
+  return FLATE_HIP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t flate_hip_seek_windows_pack_bound(uint64_t n_blocks) { return (size_t)n_blocks * flate_hip_deflate_bound(kSeekWindow); }
+
+// MARK + SPARSIFY (or the non-zero test alone), ONE read-back of the per-block records, the non-empty blocks compacted
+// in order as one batch through the encoder, the batch's out_off spread over off[].
+int flate_hip_seek_windows_pack(flate_hip_ctx *c, const uint8_t *in, uint64_t in_len, uint32_t wrap, const uint64_t *index,
+                                uint64_t index_words, const uint8_t *windows, uint64_t windows_bytes, uint32_t mode,
+                                uint64_t *pack_index, uint64_t pack_cap_words, uint64_t *pack_words, uint8_t *packed,
+                                uint64_t packed_cap, uint64_t *packed_bytes, uint64_t *kept_bytes, uint32_t flags) {
+  // every check before any HIP call
+  if (!c) return FLATE_HIP_E_INVALID;
+  int rc = seek_pack_args(in, in_len, wrap, index, index_words, windows, windows_bytes, mode, pack_index, pack_cap_words,
+                          pack_words, packed, packed_cap, packed_bytes, kept_bytes, flags);
+  if (rc) return rc;
+  c->hip_err.clear();
+  const uint32_t n = (uint32_t)index[kSeekUnitsAt], np = (uint32_t)index[kSeekPointsAt], nb = np - 1u;
+  const bool sparse = (mode & kSeekPackSparse) != 0, dev = (flags & FLATE_HIP_DEVICE_PTRS) != 0;
+  *pack_words = seek_pack_words(nb), *packed_bytes = 0, *kept_bytes = 0;
+  if (pack_cap_words < seek_pack_words(nb)) return FLATE_HIP_E_OUT_TOO_SMALL;
+  uint64_t *off = pack_index + kSeekPackHeadWords;
+  if (nb == 0) {  // no block: nothing is walked
+    seek_pack_head(pack_index, index, mode, 0, 0);
+    off[0] = 0;
+    return FLATE_HIP_OK;
+  }
+  try {
+    HIP_TRY(c, hipSetDevice(c->device));
+    const uint8_t *d_windows = windows;
+    if (!dev) {
+      if ((rc = ensure(c, c->d_one_seek_win, windows_bytes + 16))) return rc;
+      HIP_TRY(c, hipMemcpyAsync(c->d_one_seek_win.p, windows, windows_bytes, hipMemcpyHostToDevice, c->stream));
+      d_windows = (const uint8_t *)c->d_one_seek_win.p;
+    }
+    const size_t idx_words = 2 * ((size_t)n + 1) + np;
+    uint64_t *d_idx, *d_r_out_off, *d_r_src;
+    FrameOne *d_one;
+    SeekPackBlock *d_blk;
+    rc = carve(c, c->d_seek_pack, [&](Carve &k) {
+      k.take(d_idx, sparse ? idx_words : 0);
+      k.take(d_r_out_off, (size_t)nb + 1);
+      k.take(d_r_src, nb);
+      k.take(d_one, 1);
+      k.take(d_blk, nb);
+    });
+    if (rc) return rc;
+    FrameOne one{};
+    const uint8_t *d_src = d_windows;  // what the encoder reads: the raw blocks, or the sparsified ones
+    if (sparse) {
+      const uint8_t *d_in = nullptr;
+      if ((rc = stage_input(c, in, in_len, flags, &d_in))) return rc;
+      if ((rc = ensure(c, c->d_seek_pack_dense, (size_t)nb * kSeekWindow + 16))) return rc;
+      HIP_TRY(c, hipMemcpyAsync(d_idx, index + kSeekHeadWords, idx_words * 8, hipMemcpyHostToDevice, c->stream));
+      one_parse_launch(c, d_in, in_len, d_one, wrap);  // the container as this stream has it
+      SeekMarkParams M{};
+      M.in = d_in, M.in_len = in_len, M.one = d_one;
+      M.unit_bit = d_idx, M.out_off = d_idx + (n + 1), M.point_unit = d_idx + 2 * ((size_t)n + 1);
+      M.n = n, M.n_points = np;
+      M.windows = d_windows;
+      M.dense = (uint8_t *)c->d_seek_pack_dense.p;
+      M.blk = d_blk;
+      hipLaunchKernelGGL(seek_pack_mark_kernel, dim3(nb), dim3(64), 0, c->stream, M);
+      d_src = M.dense;
+    } else {
+      hipLaunchKernelGGL(seek_pack_flags_kernel, dim3(nb), dim3(256), 0, c->stream, d_windows, nb, d_blk);
+    }
+    HIP_TRY(c, hipGetLastError());
+    std::vector<SeekPackBlock> blk(nb);
+    HIP_TRY(c, hipMemcpyAsync(blk.data(), d_blk, (size_t)nb * sizeof(SeekPackBlock), hipMemcpyDeviceToHost, c->stream));
+    if (sparse) HIP_TRY(c, hipMemcpyAsync(&one, d_one, sizeof one, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    uint64_t kept = 0;
+    std::vector<uint32_t> ne;  // the non-empty blocks, in order
+    for (uint32_t b = 0; b < nb; ++b) {
+      if (blk[b].status) return FLATE_HIP_E_CORRUPT;  // (not the index's stream: the walk failed or left its segment)
+      kept += blk[b].kept;
+      if (blk[b].nonzero) ne.push_back(b);
+    }
+    if (sparse && (one.bad || one.pay_off[0] != index[kSeekRawOffAt] || one.pay_end != index[kSeekRawEndAt] ||
+                   one.want != index[kSeekWantAt] || one.isize != index[kSeekIsizeAt]))
+      return FLATE_HIP_E_CORRUPT;
+    const uint32_t m = (uint32_t)ne.size();
+    std::vector<uint64_t> e_in(m + 1), e_out(m + 1, 0);
+    for (uint32_t i = 0; i <= m; ++i) e_in[i] = (uint64_t)i * kSeekWindow;
+    if (m && m < nb) {  // some block is empty: the others move together (the encoder's streams lie back to back)
+      if ((rc = ensure(c, c->d_seek_pack_stage, (size_t)m * kSeekWindow + 16))) return rc;
+      std::vector<uint64_t> src(m);
+      for (uint32_t i = 0; i < m; ++i) src[i] = (uint64_t)ne[i] * kSeekWindow;
+      HIP_TRY(c, hipMemcpyAsync(d_r_out_off, e_in.data(), ((size_t)m + 1) * 8, hipMemcpyHostToDevice, c->stream));
+      HIP_TRY(c, hipMemcpyAsync(d_r_src, src.data(), (size_t)m * 8, hipMemcpyHostToDevice, c->stream));
+      if ((rc = ranges_gather(c, d_src, (uint8_t *)c->d_seek_pack_stage.p, d_r_out_off, d_r_src, m, (uint64_t)m * kSeekWindow)))
+        return rc;
+      HIP_TRY(c, hipGetLastError());
+      HIP_TRY(c, hipStreamSynchronize(c->stream));  // (the uploads' host arrays end with this scope)
+      d_src = (const uint8_t *)c->d_seek_pack_stage.p;
+    }
+    uint64_t total = 0;
+    if (m) {
+      // straight into the caller's device buffer, or into a staged copy no larger than the bound
+      uint8_t *d_out = packed;
+      uint64_t cap = packed_cap;
+      if (!dev) {
+        const uint64_t bound = flate_hip_seek_windows_pack_bound(m);
+        cap = packed_cap < bound ? packed_cap : bound;
+        if ((rc = ensure(c, c->d_seek_pack_out, cap + 16))) return rc;
+        d_out = (uint8_t *)c->d_seek_pack_out.p;
+      }
+      rc = flate_hip_deflate_fast_batch(c, d_src, e_in.data(), m, d_out, cap, e_out.data(), FLATE_HIP_DEVICE_PTRS);
+      if (rc == FLATE_HIP_E_OUT_TOO_SMALL) *packed_bytes = e_out[m];  // (the scan knows every size before the pack)
+      if (rc) return rc;
+      total = e_out[m];
+      if (!dev) {
+        HIP_TRY(c, hipMemcpyAsync(packed, d_out, total, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+      }
+    }
+    for (uint32_t b = 0, i = 0; b < nb; ++b) {
+      off[b] = e_out[i];
+      if (i < m && ne[i] == b) ++i;
+    }
+    off[nb] = total;
+    const uint64_t kept_all = sparse ? kept : (uint64_t)nb * kSeekWindow;
+    seek_pack_head(pack_index, index, mode, total, kept_all);
+    *packed_bytes = total, *kept_bytes = kept_all;
+    return FLATE_HIP_OK;
+  } catch (const std::exception &e) {
+    c->hip_err = e.what();
+    return FLATE_HIP_E_INTERNAL;
+  }
+}
+
+// All blocks in the raw layout: the non-empty ones by ONE launch of the batch decoders, the empty ones by zero fill.
+int flate_hip_seek_windows_unpack(flate_hip_ctx *c, const uint64_t *pack_index, uint64_t pack_words, const uint8_t *packed,
+                                  uint64_t packed_bytes, uint8_t *windows, uint64_t windows_cap, uint64_t *windows_bytes,
+                                  uint32_t *bad_block, uint32_t flags) {
+  // every check before any HIP call
+  if (!c) return FLATE_HIP_E_INVALID;
+  int rc = seek_unpack_args(pack_index, pack_words, packed, packed_bytes, windows, windows_cap, windows_bytes, flags);
+  if (rc) return rc;
+  c->hip_err.clear();
+  const uint32_t nb = (uint32_t)pack_index[kSeekPackBlocksAt];
+  const uint64_t need = (uint64_t)nb * kSeekWindow;
+  *windows_bytes = need;
+  if (bad_block) *bad_block = 0xffffffffu;
+  if (windows_cap < need) return FLATE_HIP_E_OUT_TOO_SMALL;  // (the size query too)
+  if (nb == 0) return FLATE_HIP_OK;
+  try {
+    HIP_TRY(c, hipSetDevice(c->device));
+    const bool dev = (flags & FLATE_HIP_DEVICE_PTRS) != 0;
+    const uint64_t *off = pack_index + kSeekPackHeadWords;
+    const uint8_t *d_packed = packed;
+    uint8_t *d_win = windows;
+    if (!dev) {
+      if ((rc = ensure(c, c->d_seek_pack_stage, packed_bytes + 16))) return rc;
+      if ((rc = ensure(c, c->d_one_seek_win, need + 16))) return rc;
+      if (packed_bytes) HIP_TRY(c, hipMemcpyAsync(c->d_seek_pack_stage.p, packed, packed_bytes, hipMemcpyHostToDevice, c->stream));
+      d_packed = (const uint8_t *)c->d_seek_pack_stage.p;
+      d_win = (uint8_t *)c->d_one_seek_win.p;
+    }
+    const PackedBlocks P = packed_blocks(off, nb);
+    const uint32_t m = (uint32_t)P.b.size();
+    // (a slot runs to the next non-empty block: what a bad stream writes behind its 32768 bytes is zero-filled below)
+    std::vector<uint64_t> slot_off(m + 1);
+    for (uint32_t i = 0; i < m; ++i) slot_off[i] = (uint64_t)P.b[i] * kSeekWindow;
+    slot_off[m] = m ? slot_off[m - 1] + kSeekWindow : 0;
+    std::vector<uint8_t> good;
+    if ((rc = inflate_blocks(c, d_packed, P.in_off, d_win, slot_off, good))) return rc;
+    for (uint32_t b = 0, i = 0; b < nb;) {  // the runs of empty blocks
+      if (i < m && P.b[i] == b) {
+        ++b, ++i;
+        continue;
+      }
+      const uint32_t e = i < m ? P.b[i] : nb;
+      HIP_TRY(c, hipMemsetAsync(d_win + (uint64_t)b * kSeekWindow, 0, (size_t)(e - b) * kSeekWindow, c->stream));
+      b = e;
+    }
+    if (!dev) HIP_TRY(c, hipMemcpyAsync(windows, d_win, need, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    for (uint32_t i = 0; i < m; ++i)
+      if (!good[i]) {
+        if (bad_block) *bad_block = P.b[i];
+        return FLATE_HIP_E_CORRUPT;
+      }
+    return FLATE_HIP_OK;
+  } catch (const std::exception &e) {
+    c->hip_err = e.what();
+    return FLATE_HIP_E_INTERNAL;
+  }
+}
+
+// flate_hip_inflate_one_ranges with the selected points' blocks made between SELECT's read-back and the rounds: the
+// non-empty ones by ONE launch of the batch decoders into a dense stage of 32 KiB per SELECTED point, the empty ones by
+// zero fill; the rounds' load reads the stage through the point -> slot table.
+int flate_hip_inflate_one_ranges_packed(flate_hip_ctx *c, const uint8_t *in, uint64_t in_len, uint32_t wrap,
+                                        const uint64_t *index, uint64_t index_words, const uint64_t *pack_index,
+                                        uint64_t pack_words, const uint8_t *packed, uint64_t packed_bytes, const uint64_t *begin,
+                                        const uint64_t *end, uint32_t n_ranges, uint8_t *out, uint64_t out_cap,
+                                        uint64_t *out_off, int32_t *range_status, uint32_t *n_decoded, uint32_t *bad_unit,
+                                        uint32_t flags) {
+  // every check before any HIP call
+  if (!c) return FLATE_HIP_E_INVALID;
+  const int rc0 = one_ranges_packed_args(in, in_len, wrap, index, index_words, pack_index, pack_words, packed, packed_bytes,
+                                         begin, end, n_ranges, out, out_cap, out_off, flags);
+  if (rc0) return rc0;
+  const bool dev = (flags & FLATE_HIP_DEVICE_PTRS) != 0;
+  const uint64_t *off = pack_index + kSeekPackHeadWords;
+  auto win = [&](const uint32_t *sel, uint32_t ns, const uint64_t *h_point, uint32_t np, OneRangesWin &W) -> int {
+    int rc;
+    std::vector<uint32_t> ps, places;
+    selected_points(sel, ns, h_point, np, ps, &places);
+    const uint32_t m = (uint32_t)ps.size();
+    if (m == 0) return FLATE_HIP_OK;  // (only point 0 is selected: no window is read)
+    uint32_t *d_slot_of;
+    uint64_t *d_r_out_off, *d_r_src;
+    rc = carve(c, c->d_seek_pack, [&](Carve &k) {
+      k.take(d_r_out_off, (size_t)m + 1);
+      k.take(d_r_src, m);
+      k.take(d_slot_of, np);
+    });
+    if (rc) return rc;
+    if ((rc = ensure(c, c->d_seek_pack_sel, (size_t)m * kSeekWindow + 16))) return rc;
+    uint8_t *stage = (uint8_t *)c->d_seek_pack_sel.p;
+    // the selected blocks' streams, compacted: slot j of the stage is point ps[j]'s
+    std::vector<uint32_t> slot_of(np, 0), s_slot;  // (s_slot: the slots of the non-empty ones)
+    std::vector<uint64_t> s_in(1, 0), s_src;
+    for (uint32_t j = 0; j < m; ++j) {
+      const uint32_t b = ps[j] - 1u;
+      slot_of[ps[j]] = j;
+      if (off[b + 1] > off[b]) {
+        s_slot.push_back(j);
+        s_src.push_back(off[b]);
+        s_in.push_back(s_in.back() + (off[b + 1] - off[b]));
+      }
+    }
+    const uint32_t k = (uint32_t)s_slot.size();
+    HIP_TRY(c, hipMemcpyAsync(d_slot_of, slot_of.data(), (size_t)np * 4, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemsetAsync(stage, 0, (size_t)m * kSeekWindow, c->stream));  // (the empty blocks; a bad block's rest)
+    std::vector<uint8_t> good;
+    if (k) {
+      if ((rc = ensure(c, c->d_seek_pack_stage, s_in[k] + 16))) return rc;
+      uint8_t *d_streams = (uint8_t *)c->d_seek_pack_stage.p;
+      if (dev) {
+        HIP_TRY(c, hipMemcpyAsync(d_r_out_off, s_in.data(), ((size_t)k + 1) * 8, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(d_r_src, s_src.data(), (size_t)k * 8, hipMemcpyHostToDevice, c->stream));
+        if ((rc = ranges_gather(c, packed, d_streams, d_r_out_off, d_r_src, k, s_in[k]))) return rc;
+        HIP_TRY(c, hipGetLastError());
+      } else {  // only the selected blocks' streams are uploaded
+        for (uint32_t i = 0; i < k; ++i)
+          HIP_TRY(c, hipMemcpyAsync(d_streams + s_in[i], packed + s_src[i], s_in[i + 1] - s_in[i], hipMemcpyHostToDevice, c->stream));
+      }
+      HIP_TRY(c, hipStreamSynchronize(c->stream));
+      // ONE launch: every non-empty block into its own slot.  The decoders' slots lie back to back, so with empty blocks
+      // in between a slot runs on to the next non-empty one
+      if (k == m) {
+        std::vector<uint64_t> slot_off(k + 1);
+        for (uint32_t i = 0; i <= k; ++i) slot_off[i] = (uint64_t)i * kSeekWindow;
+        if ((rc = inflate_blocks(c, d_streams, s_in, stage, slot_off, good))) return rc;
+      } else {
+        std::vector<uint64_t> slot_off(k + 1);
+        for (uint32_t i = 0; i < k; ++i) slot_off[i] = (uint64_t)s_slot[i] * kSeekWindow;
+        slot_off[k] = slot_off[k - 1] + kSeekWindow;
+        if ((rc = inflate_blocks(c, d_streams, s_in, stage, slot_off, good))) return rc;
+        // what a bad stream wrote behind its 32768 bytes lies in the empty blocks' slots: zero them again
+        for (uint32_t j = 0, i = 0; j < m; ++j) {
+          if (i < k && s_slot[i] == j) {
+            ++i;
+            continue;
+          }
+          HIP_TRY(c, hipMemsetAsync(stage + (uint64_t)j * kSeekWindow, 0, kSeekWindow, c->stream));
+        }
+      }
+      for (uint32_t i = 0; i < k; ++i)
+        if (!good[i]) W.bad_place.push_back(places[s_slot[i]]);
+    }
+    HIP_TRY(c, hipStreamSynchronize(c->stream));  // (the uploads' host arrays end with this scope)
+    W.d_windows = stage;
+    W.d_slot_of = d_slot_of;
+    return FLATE_HIP_OK;
+  };
+  return one_ranges_run(c, in, in_len, wrap, index, begin, end, n_ranges, out, out_cap, out_off, range_status, n_decoded,
+                        bad_unit, flags, win);
 }
 
 }  // extern "C"

@@ -100,6 +100,11 @@ struct flate_hip_ctx {
   // OneSeekParams), carved from one buffer; a host caller's windows; the dense scratch the selected units are decoded
   // into.  Both calls carve their rounds' arrays from d_one_dec.
   DevBuf d_one_seek, d_one_seek_win, d_one_seek_dense;
+  // flate_hip_seek_windows_pack / _unpack, flate_hip_inflate_one_ranges_packed: the per-block records and the uploaded
+  // index; the sparsified blocks, one slot each; the non-empty blocks compacted (pack), a host caller's packed bytes or
+  // the selected streams compacted (unpack, read); a host caller's encoded bytes; the read's dense stage of the
+  // selected points' blocks
+  DevBuf d_seek_pack, d_seek_pack_dense, d_seek_pack_stage, d_seek_pack_out, d_seek_pack_sel;
   // flate_hip_gzfile_index / _read: the two count passes' words and tile counts (sized before the candidates are
   // counted), the chain's arrays (GzFileParams), and the read's member-wise arrays beside d_one_dec's
   DevBuf d_gzfile_tiles, d_gzfile, d_gzfile_dec;

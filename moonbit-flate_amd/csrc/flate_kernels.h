@@ -819,6 +819,34 @@ __global__ void one_seek_compose_kernel(const uint16_t *src, uint16_t *dst, cons
 __global__ void one_seek_resolve_kernel(const uint16_t *F, uint8_t *R, const uint32_t *seed, uint32_t count);
 __global__ void one_seek_check_kernel(OneSeekRoundParams S);
 
+// The PACKED windows of that index (seek_pack_rule.h; flate_hip_seek_windows_pack / _unpack,
+// flate_hip_inflate_one_ranges_packed).  seek_pack_mark_kernel (seek_pack_mark_kernel.inc, on the shared reader): MARK +
+// SPARSIFY, one wavefront per block b = point b + 1 -- the token walk from the point's bit over at most 32768 bytes of
+// output, the keep mask in LDS, then the raw block with everything else zeroed into slot b of `dense`.
+// seek_pack_flags_kernel: the non-zero test alone (COMPRESS without SPARSE).  seek_pack_load_kernel: one_seek_load_kernel
+// with the unpacked blocks of the SELECTED points in a dense stage, through the point -> slot table.
+struct SeekPackBlock {       // per block, read back once
+  uint32_t nonzero;          // the (sparsified) block has a non-zero byte
+  uint32_t kept;             // bytes the keep rule marks (whole blocks: 32768)
+  int32_t status;            // 0, or FLATE_HIP_E_CORRUPT: the walk failed or left the segment anywhere but at its end
+  uint32_t pad;
+};
+struct SeekMarkParams {
+  const uint8_t *in;         // the whole input (device)
+  uint64_t in_len;
+  const FrameOne *one;       // the raw stream's range as this input has it
+  const uint64_t *unit_bit;  // n + 1: the index, uploaded
+  const uint64_t *out_off;   // n + 1
+  const uint64_t *point_unit;  // n_points
+  uint32_t n, n_points;
+  const uint8_t *windows;    // n_points - 1 blocks, any alignment
+  uint8_t *dense;            // n_points - 1 slots of 32768 bytes, 16-byte aligned
+  SeekPackBlock *blk;        // n_points - 1
+};
+__global__ void seek_pack_mark_kernel(SeekMarkParams M);
+__global__ void seek_pack_flags_kernel(const uint8_t *windows, uint32_t n_blocks, SeekPackBlock *blk);
+__global__ void seek_pack_load_kernel(OneSeekRoundParams S, const uint32_t *slot_of_point);
+
 // A gzip FILE of any members, long ones included (gzfile_kernels.hip; flate_hip_gzfile_index / _read; the rule:
 // gzfile_rule.h).  The units of ALL members form one chain over the file's bits: the raw stream of OneParams is
 // in[0, in_len - 8), so every bit and every error offset is counted from the file's first byte.  The nodes are two

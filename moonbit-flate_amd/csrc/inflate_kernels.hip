@@ -18,6 +18,7 @@
 // (more_bits :789, huff_sym :818-831) has consumed, which is a function of the bits requested so
 // far: roffset = max(roffset, ceil((consumed_bits + requested) / 8)).
 #include "flate_kernels.h"
+#include "seek_pack_rule.h"
 #include "window_compose.h"
 
 #include <type_traits>
@@ -585,6 +586,7 @@ template __global__ void inflate_spec_kernel<FLATE_SPEC_LARGE>(InfParams);
 template __global__ void inflate_spec_dict_kernel<FLATE_SPEC_SMALL>(InfParams);
 template __global__ void inflate_spec_dict_kernel<FLATE_SPEC_LARGE>(InfParams);
 #include "one_probe_kernel.inc"
+#include "seek_pack_mark_kernel.inc"
 
 }  // namespace flate
 

@@ -63,6 +63,9 @@ SEEK_SPAN_DEFAULT = 1 << 20  # FLATE_HIP_SEEK_SPAN_DEFAULT
 SEEK_SPAN_NONE = (1 << 64) - 1  # FLATE_HIP_SEEK_SPAN_NONE: unit 0 is the only point
 SeekIndex = collections.namedtuple("SeekIndex", "rc index windows n_units n_points out_bytes status err_off")
 OneRanges = collections.namedtuple("OneRanges", "rc out_off range_status n_decoded bad_unit")
+SEEK_PACK_COMPRESS, SEEK_PACK_SPARSE = 1, 2  # FLATE_HIP_SEEK_PACK_*
+SeekPack = collections.namedtuple("SeekPack", "rc pack_index packed packed_bytes kept_bytes")
+SeekUnpack = collections.namedtuple("SeekUnpack", "rc windows_bytes bad_block")
 GzFileIndex = collections.namedtuple("GzFileIndex", "rc n_units n_members out_bytes n_candidates status bad_member err_off "
                                      "stream_err_off unit_bit out_off member_off member_unit")
 GzFileRead = collections.namedtuple("GzFileRead", "rc out_len n_members n_units n_candidates status bad_member err_off "
@@ -360,6 +363,101 @@ class OneSeekCalls:
         return _read_into(out, data, out_cap, "inflate_one_ranges", call, size)
 
 
+class SeekPackCalls:
+    """The packed windows of the seek index of one long stream: the three methods FlateEngine inherits.  They stand in a
+    class of their own so that their marshalling has its own recorded scenarios (tests/engine_trace_seek_pack.py)."""
+
+    def seek_windows_pack(self, seek_index, data=None, sparse=True, wrap="gzip", out=None, out_cap=None):
+        """The windows of a seek index, packed (flate_hip_seek_windows_pack) -> SeekPack(rc, pack_index, packed,
+        packed_bytes, kept_bytes).  Every block becomes one raw DEFLATE stream, a block of zeros no bytes at all; with
+        sparse the bytes that its segment never reads become zero first, for which the stream `data` is walked (without
+        sparse data may be None: only its length, taken from the index, is told).  seek_index: what
+        inflate_one_seek_index returned, or an (index, windows) pair; packed lies on the side of the windows.  rc 0; -4:
+        data is not the stream the index was built from; -2 with packed_bytes the bytes needed: out too small, nothing
+        usable written.  out=None: room for the bound.  Refusals raise FlateError."""
+        index, windows = (seek_index.index, seek_index.windows) if isinstance(seek_index, SeekIndex) else seek_index
+        index = np.ascontiguousarray(index, dtype=np.uint64)
+        mode = SEEK_PACK_COMPRESS | (SEEK_PACK_SPARSE if sparse else 0)
+        n_blocks = max(int(index[9]) - 1, 0) if index.size >= 16 else 0
+        if windows is None or (windows.numel() if _is_torch(windows) else windows.size) == 0:
+            windows, w_ptr, wb, device = np.zeros(0, dtype=np.uint8), None, 0, data is not None and _is_torch(data)
+        else:
+            windows, w_ptr, wb, device = _in_buf(windows)
+        if data is None:
+            in_ptr, n = None, int(index[3]) if index.size >= 16 else 0
+        else:
+            data, in_ptr, n, d_dev = _in_buf(data, accept_bytes=True, null_if_empty=True)
+            if d_dev != device and wb:
+                raise FlateError(E_INVALID, "seek_windows_pack: the windows must be on the side of the data")
+        side = windows if wb or data is None else data
+        words = 17 + n_blocks
+        pack_index = np.zeros(words, dtype=np.uint64)
+        bound = int(self._L.flate_hip_seek_windows_pack_bound(n_blocks))
+        out, out_ptr, cap = _out_buf(out, side, bound, out_cap, 0, "seek_windows_pack")
+        pw, pb, kb = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        rc = self._tolerate(self._L.flate_hip_seek_windows_pack(
+            self._ctx, in_ptr, n, WRAPS[wrap], index.ctypes.data, index.size, w_ptr, wb, mode, pack_index.ctypes.data,
+            words, C.byref(pw), out_ptr, cap, C.byref(pb), C.byref(kb), self._flags(False, False, device)),
+            E_OUT_TOO_SMALL, E_CORRUPT)
+        ok = rc == 0
+        return SeekPack(rc, pack_index if ok else None, out[:int(pb.value)] if ok else None, int(pb.value), int(kb.value))
+
+    def seek_windows_unpack(self, pack, out=None, out_cap=None):
+        """All blocks of packed windows in the raw layout (flate_hip_seek_windows_unpack) -> (windows,
+        SeekUnpack(rc, windows_bytes, bad_block)): the sparsified windows, or the original ones of a pack without
+        sparse -- what the unchanged inflate_one_ranges takes.  pack: what seek_windows_pack returned, or a
+        (pack_index, packed) pair.  rc 0; -4 with bad_block the first block that does not inflate to 32768 bytes; -2:
+        out too small.  Refusals raise FlateError."""
+        pack_index, packed = (pack.pack_index, pack.packed) if isinstance(pack, SeekPack) else pack
+        pack_index = np.ascontiguousarray(pack_index, dtype=np.uint64)
+        packed, p_ptr, pb, device = _in_buf(packed, null_if_empty=True)
+        need = (int(pack_index[3]) if pack_index.size >= 17 else 0) * 32768
+        out, out_ptr, cap = _out_buf(out, packed, need, out_cap, 0, "seek_windows_unpack", floor=1)
+        wb, bad = C.c_uint64(0), C.c_uint32(0)
+        rc = self._tolerate(self._L.flate_hip_seek_windows_unpack(
+            self._ctx, pack_index.ctypes.data, pack_index.size, p_ptr, pb, out_ptr, cap, C.byref(wb), C.byref(bad),
+            self._flags(False, False, device)), E_OUT_TOO_SMALL, E_CORRUPT)
+        return out[:int(wb.value)] if rc == 0 else out, SeekUnpack(rc, int(wb.value), int(bad.value))
+
+    def inflate_one_ranges_packed(self, data, index, pack, begin, end, out=None, out_cap=None, wrap="gzip"):
+        """inflate_one_ranges through PACKED windows (flate_hip_inflate_one_ranges_packed): only the blocks of the
+        selected points are inflated, into scratch that grows with the selection.  index: the seek index's words (or a
+        SeekIndex); pack: what seek_windows_pack returned, or a (pack_index, packed) pair, packed on the side of data.
+        Returns (out, OneRanges) as inflate_one_ranges does; a block that does not inflate makes its point's unit the
+        bad unit with status -4."""
+        data, in_ptr, n, device = _in_buf(data, accept_bytes=True, null_if_empty=True)
+        index = np.ascontiguousarray(index.index if isinstance(index, SeekIndex) else index, dtype=np.uint64)
+        pack_index, packed = (pack.pack_index, pack.packed) if isinstance(pack, SeekPack) else pack
+        pack_index = np.ascontiguousarray(pack_index, dtype=np.uint64)
+        if packed is None or (packed.numel() if _is_torch(packed) else packed.size) == 0:
+            p_ptr, pb = None, 0
+        else:
+            packed, p_ptr, pb, p_dev = _in_buf(packed)
+            if p_dev != device:
+                raise FlateError(E_INVALID, "inflate_one_ranges_packed: the packed windows must be on the side of the data")
+        begin = np.ascontiguousarray(begin, dtype=np.uint64)
+        end = np.ascontiguousarray(end, dtype=np.uint64)
+        if begin.ndim != 1 or begin.shape != end.shape:
+            raise FlateError(E_INVALID, "inflate_one_ranges_packed: begin and end must be one-dimensional and of one length")
+        nr = begin.size
+        out_off = np.zeros(nr + 1, dtype=np.uint64)
+        status = np.zeros(max(nr, 1), dtype=np.int32)
+        nd, bad = C.c_uint32(0), C.c_uint32(0)
+
+        def call(out_ptr, cap):
+            rc = self._tolerate(self._L.flate_hip_inflate_one_ranges_packed(
+                self._ctx, in_ptr, n, WRAPS[wrap], index.ctypes.data, index.size, pack_index.ctypes.data, pack_index.size,
+                p_ptr, pb, begin.ctypes.data, end.ctypes.data, nr, out_ptr, cap, out_off.ctypes.data, status.ctypes.data,
+                C.byref(nd), C.byref(bad), self._flags(False, False, device)), *PER_CHAIN)
+            return OneRanges(rc, out_off, status[:nr], int(nd.value), int(bad.value))
+
+        def size():  # the size query: nothing is decoded
+            q = call(None, 0)
+            return (int(out_off[nr]), None) if q.rc == E_OUT_TOO_SMALL else (0, q)
+
+        return _read_into(out, data, out_cap, "inflate_one_ranges_packed", call, size)
+
+
 class GzFileCalls:
     """A gzip file of any members, long ones included: the two methods FlateEngine inherits.  They stand in a class of
     their own so that their marshalling has its own recorded scenarios (tests/engine_trace_gzfile.py) beside the ones
@@ -606,7 +704,7 @@ class OneWriterCalls:
         return OneWriter(self, wrap, piece_bytes, device, compat_go)
 
 
-class FlateEngine(OneSeekCalls, GzFileCalls, GzFileSerialCalls, GzFileSeekCalls, ZipUnitsCalls, GroupedCalls, OnePartsCalls,
+class FlateEngine(OneSeekCalls, SeekPackCalls, GzFileCalls, GzFileSerialCalls, GzFileSeekCalls, ZipUnitsCalls, GroupedCalls, OnePartsCalls,
                   OneWriterCalls):
     """One engine = one flate_hip_ctx = one GPU + one HIP stream."""
 

@@ -1494,6 +1494,95 @@ inline Err decompress_one_ranges(Engine &e, const std::vector<uint8_t> &stream, 
   return make_error(e, rc);
 }
 
+// What pack_seek_windows made of a seek index's windows: to keep beside the index in the windows' place.
+struct SeekPack {
+  std::vector<uint64_t> pack_index;  // the self-describing words (include/flate_hip.h documents the layout)
+  std::vector<uint8_t> packed;       // every non-empty block as one raw DEFLATE stream, back to back
+  uint64_t kept_bytes = 0;           // sparse: the window bytes some segment reads; else every byte
+  int status = 0;                    // the FLATE_HIP_E_* code behind the error (0 = none)
+};
+
+// pack_seek_windows: the windows of sx, every block one raw DEFLATE stream and a block of zeros no bytes at all
+// (flate_hip_seek_windows_pack); sparse: the bytes no segment reads become zero first, for which `stream` is walked
+// (without sparse it is not read).  Errors: make_error(FLATE_HIP_E_INVALID) for an index that is not sound or not this
+// stream's container and length, corrupt_input_error(-1) for a stream the index was not built from.
+inline Err pack_seek_windows(Engine &e, const std::vector<uint8_t> &stream, Wrap wrap, const OneSeekIndex &sx, bool sparse,
+                             SeekPack &pk) {
+  if (!e.ok()) return make_error(e, e.status());
+  pk = SeekPack();
+  const uint64_t nb = sx.n_points ? sx.n_points - 1u : 0u;
+  const uint64_t cap = flate_hip_seek_windows_pack_bound(nb);
+  uint64_t words = 0, bytes = 0;
+  pk.pack_index.assign(17 + nb, 0);
+  pk.packed.assign(cap + 1, 0);
+  const uint32_t mode = FLATE_HIP_SEEK_PACK_COMPRESS | (sparse ? FLATE_HIP_SEEK_PACK_SPARSE : 0u);
+  const int rc = flate_hip_seek_windows_pack(e.ctx(), stream.data(), stream.size(), wrap_code(wrap), sx.index.data(),
+                                             sx.index.size(), sx.windows.empty() ? nullptr : sx.windows.data(),
+                                             sx.windows.size(), mode, pk.pack_index.data(), pk.pack_index.size(), &words,
+                                             pk.packed.data(), cap, &bytes, &pk.kept_bytes, 0);
+  pk.pack_index.resize(rc == 0 ? words : 0);
+  pk.packed.resize(rc == 0 ? bytes : 0);
+  pk.status = rc;
+  if (rc == 0) return std::nullopt;
+  if (rc == FLATE_HIP_E_CORRUPT) return corrupt_input_error(-1);
+  return make_error(e, rc);
+}
+
+// unpack_seek_windows: all blocks of pk in the raw layout (flate_hip_seek_windows_unpack): the sparsified windows, or
+// the original ones of a pack without sparse -- what decompress_one_ranges takes as OneSeekIndex::windows.  Errors:
+// corrupt_input_error(bad block) for a block that does not inflate to 32768 bytes.
+inline Err unpack_seek_windows(Engine &e, const SeekPack &pk, std::vector<uint8_t> &windows) {
+  if (!e.ok()) return make_error(e, e.status());
+  const uint64_t need = pk.pack_index.size() > 3 ? pk.pack_index[3] * FLATE_HIP_SEEK_WINDOW_BYTES : 0;
+  windows.assign(need + 1, 0);
+  uint64_t bytes = 0;
+  uint32_t bad = 0xffffffffu;
+  const int rc = flate_hip_seek_windows_unpack(e.ctx(), pk.pack_index.data(), pk.pack_index.size(),
+                                               pk.packed.empty() ? nullptr : pk.packed.data(), pk.packed.size(),
+                                               windows.data(), need, &bytes, &bad, 0);
+  windows.resize(rc == 0 || rc == FLATE_HIP_E_CORRUPT ? bytes : 0);
+  if (rc == 0) return std::nullopt;
+  if (rc == FLATE_HIP_E_CORRUPT) return corrupt_input_error((int64_t)bad);
+  return make_error(e, rc);
+}
+
+// decompress_one_ranges_packed: decompress_one_ranges through the PACKED windows of sx's index
+// (flate_hip_inflate_one_ranges_packed; sx.windows is not read): only the blocks of the seek points the ranges need
+// are inflated.  Errors are decompress_one_ranges's; a block that does not inflate is a unit the index does not fit.
+inline Err decompress_one_ranges_packed(Engine &e, const std::vector<uint8_t> &stream, Wrap wrap, const OneSeekIndex &sx,
+                                        const SeekPack &pk, const std::vector<OneRange> &ranges, std::vector<uint8_t> &out,
+                                        OneRangesInfo *info = nullptr) {
+  if (!e.ok()) return make_error(e, e.status());
+  OneRangesInfo I;
+  const uint32_t nr = (uint32_t)ranges.size();
+  std::vector<uint64_t> begin(nr), end(nr);
+  for (uint32_t r = 0; r < nr; ++r) begin[r] = ranges[r].begin, end[r] = ranges[r].end;
+  I.out_off.assign((size_t)nr + 1, 0);
+  I.range_status.assign(nr, 0);
+  out.clear();
+  auto call = [&](uint8_t *buf, uint64_t cap) {
+    return flate_hip_inflate_one_ranges_packed(e.ctx(), stream.data(), stream.size(), wrap_code(wrap), sx.index.data(),
+                                               sx.index.size(), pk.pack_index.data(), pk.pack_index.size(),
+                                               pk.packed.empty() ? nullptr : pk.packed.data(), pk.packed.size(), begin.data(),
+                                               end.data(), nr, buf, cap, I.out_off.data(), I.range_status.data(),
+                                               &I.n_decoded, &I.bad_unit, 0);
+  };
+  int rc = call(nullptr, 0);  // the size query
+  if (rc == FLATE_HIP_E_OUT_TOO_SMALL) {
+    const uint64_t need = I.out_off[nr];
+    std::vector<uint8_t> buf(need + 8);
+    rc = call(buf.data(), need);
+    if (rc != FLATE_HIP_E_INVALID && rc != FLATE_HIP_E_HIP && rc != FLATE_HIP_E_INTERNAL)
+      out.assign(buf.begin(), buf.begin() + std::min<uint64_t>(I.out_off[nr], need));
+  }
+  I.status = rc;
+  if (info) *info = I;
+  if (rc == 0) return std::nullopt;
+  if (rc == FLATE_HIP_E_CORRUPT) return corrupt_input_error(-1);
+  if (rc == FLATE_HIP_E_UNEXPECTED_EOF) return err_unexpected_eof();
+  return make_error(e, rc);
+}
+
 // What seek_index_gzfile built: the seek index of a gzip file of ANY members, to keep beside the file and hand to
 // decompress_gzfile_ranges.
 struct GzFileSeekIndex {
