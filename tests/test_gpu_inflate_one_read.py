@@ -11,7 +11,7 @@ import pytest
 
 import one_ref as ref
 from test_gpu_inflate_one import failing_streams, on_device
-from util import flate
+from util import STATUS_OF_ORACLE, flate
 
 pytestmark = pytest.mark.gpu
 
@@ -139,7 +139,7 @@ def test_size_query_capacity_and_wrappers(eng, good):
 
 # ---- failing streams ----
 
-def test_failing_raw_streams_equal_the_serial_decoder(eng, good):
+def test_failing_raw_streams_equal_the_serial_decoder(eng, good, oracle):
     """Every case and variant of the edge corpus, cuts and flipped bits in the 230-unit file, and the distance that
     reaches one byte in front of the stream: status, err_off, out_len and the bytes in front of the error."""
     cases = failing_streams(good)
@@ -151,6 +151,8 @@ def test_failing_raw_streams_equal_the_serial_decoder(eng, good):
     seen = set()
     for k, (what, raw) in enumerate(cases):
         want = bytes(out[int(ooff[k]):int(ooff[k]) + int(olen[k])])
+        orc, obytes, _, oerr = oracle.inflate(raw, caps[k], full=True)  # the yardstick itself against the oracle
+        assert (int(status[k]), int(err[k]), want) == (STATUS_OF_ORACLE[orc], oerr, obytes), (what, orc, oerr, len(obytes))
         rc, got, ol, st, eo, nu, nc, _ = read(eng, raw, ref.RAW, caps[k], device=k % 2 == 1)
         assert (rc, st, eo, ol) == (int(status[k]), int(status[k]), int(err[k]), int(olen[k])), (what, rc, st, eo, ol)
         assert got == want, what

@@ -14,7 +14,7 @@ import one_parts_ref as R
 import one_ref as ref
 import one_window_corpus as corpus
 from test_gpu_inflate_one import failing_streams
-from util import flate
+from util import STATUS_OF_ORACLE, flate
 
 pytestmark = pytest.mark.gpu
 
@@ -232,10 +232,14 @@ def test_a_distance_in_front_of_the_stream_in_part_two(eng):
 # ---- 4. error parity ----
 
 @pytest.fixture(scope="module")
-def failing(eng):
+def failing(eng, oracle):
     what, raw, plain = ref.good_streams(None)[ref.MANY_UNITS]  # (the one file failing_streams cuts and flips)
     cases = failing_streams([None] * ref.MANY_UNITS + [(what, raw, plain, ref.Walk(raw))])
-    return [(what, raw) + whole(eng, raw, ref.RAW, ref.Walk(raw).out_len + 600) for what, raw in cases]
+    out = [(what, raw) + whole(eng, raw, ref.RAW, ref.Walk(raw).out_len + 600) for what, raw in cases]
+    for what, raw, st, eo, ol, got, _ in out:  # the yardstick itself against the oracle on the same bytes
+        rc, want, _, eoff = oracle.inflate(raw, ol + 600, full=True)
+        assert (st, eo, ol, got) == (STATUS_OF_ORACLE[rc], eoff, len(want), want), (what, st, eo, ol, rc, eoff, len(want))
+    return out
 
 
 @pytest.mark.parametrize("split,share", [(s, q) for s in (3, 2) for q in range(4)])

@@ -10,7 +10,7 @@ import pytest
 import one_ref as ref
 import seek_ref as sk
 from test_gpu_inflate_one import failing_streams, on_device
-from util import flate
+from util import STATUS_OF_ORACLE, flate
 
 pytestmark = pytest.mark.gpu
 
@@ -206,7 +206,7 @@ def test_build_size_query_and_short_capacities(eng, good):
         assert eng._L.flate_hip_inflate_one_seek_index(*a) == -1, at
 
 
-def test_failing_streams_get_the_serial_verdict_and_no_index(eng, good):
+def test_failing_streams_get_the_serial_verdict_and_no_index(eng, good, oracle):
     cases = failing_streams(good)
     off = np.zeros(len(cases) + 1, np.uint64)
     np.cumsum(np.array([len(r) for _, r in cases], dtype=np.uint64), out=off[1:])
@@ -215,6 +215,8 @@ def test_failing_streams_get_the_serial_verdict_and_no_index(eng, good):
     out, ooff, olen, status, err = eng.inflate_batch(data, off, caps, check=False)
     seen = set()
     for k, (what, raw) in enumerate(cases):
+        rc, want, _, eoff = oracle.inflate(raw, caps[k], full=True)  # the yardstick itself against the oracle
+        assert (int(status[k]), int(err[k]), int(olen[k])) == (STATUS_OF_ORACLE[rc], eoff, len(want)), (what, rc, eoff)
         g = build(eng, raw, ref.RAW, 4096, device=k % 2 == 1, words=4096, room=128 * sk.WINDOW)
         want = (int(status[k]), int(status[k]), int(err[k]) if status[k] else -1)
         assert (g["rc"], g["status"], g["err_off"]) == want, (what, g)
