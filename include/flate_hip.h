@@ -969,7 +969,7 @@ int flate_hip_inflate_one_index(flate_hip_ctx *ctx, const uint8_t *in, uint64_t 
  *   Host pointers: the part is uploaded once and out[0, *out_len) downloaded once per call.  With device pointers
  *   nothing outside out[0, *out_len) is written.  Per call the host waits for the discovery's two read-backs and one
  *   read-back of the result words.
- *   Out of scope: a file of several members read in parts (flate_hip_gzfile_read takes the whole file); overlapping
+ *   Out of scope: a file of several members read in parts (that is flate_hip_gzfile_reader_*, below); overlapping
  *   the copy of part k + 1 with the decode of part k.  (The parallel writer in parts: flate_hip_one_writer_*.) */
 typedef struct flate_hip_one_reader flate_hip_one_reader;
 int flate_hip_one_reader_open(flate_hip_ctx *ctx, uint32_t wrap, uint32_t flags, flate_hip_one_reader **reader);
@@ -1302,6 +1302,79 @@ int flate_hip_gzfile_read(flate_hip_ctx *ctx, const uint8_t *in, uint64_t in_len
                           uint32_t flags);
 int flate_hip_gzfile_last_route(const flate_hip_ctx *ctx, uint32_t *serial_members, uint32_t *unit_members,
                                 uint64_t *find_from);
+
+/* -- Any gzip file read in PARTS: members and units through bounded buffers ------------
+ * flate_hip_gzfile_read wants the whole file; flate_hip_one_reader_* reads ONE member in parts.  A
+ * flate_hip_gzfile_reader reads a file of ANY members through two bounded buffers: every call is flate_hip_gzfile_read
+ * on the part of the file it is given -- its units cross member boundaries inside the part, the trailers of the members
+ * that end in it are judged in it -- and between two calls the handle holds where the file stands (the rule:
+ * csrc/gzfile_parts_rule.h; the part's kernels: csrc/gzfile_parts_kernels.hip).
+ *
+ * open: flags is 0 or FLATE_HIP_DEVICE_PTRS (in and out of every read are device buffers); anything else, or a NULL ctx
+ * or result pointer, is FLATE_HIP_E_INVALID before any HIP call.  The handle records "one_stored_units" and
+ * "one_unit_max" as the ctx has them at open.  reset: a fresh file on the same handle.  The ctx must outlive it.
+ *
+ * read: in[0, in_len) BEGINS with the bytes the last call left unused; final_in != 0: no bytes follow.  Returns
+ * FLATE_HIP_OK (call again), FLATE_HIP_STREAM_END (a final call whose walk reached the file's end; sticky), the file's
+ * error (sticky: every later call returns it with the same *bad_member, *err_off and *stream_err_off, *in_used = 0), or
+ * one of the repeatable codes, which follow flate_hip_one_reader_read's rule: FLATE_HIP_E_OUT_TOO_SMALL with *out_len =
+ * the first unit's size, FLATE_HIP_E_INVALID (NULL reader / in with in_len > 0 / out with out_cap > 0 / in_used /
+ * out_len, before any HIP call), and FLATE_HIP_E_HIP in front of the point where the call begins to move the handle's
+ * device words -- such a call has changed nothing; behind that point it is sticky.  n_members, n_units, bad_member,
+ * err_off and stream_err_off may be NULL.  An empty file -- a final call without bytes on a fresh handle -- is
+ * FLATE_HIP_STREAM_END with nothing.
+ *   THE CONTRACT.  Let F be the concatenation of everything the calls consumed.  THE WALK of flate_hip_gzfile_read over
+ *   F (above) defines the members, the units, the bytes and the offsets, and the reader's results are independent of
+ *   where the parts are cut and of out_cap.  The concatenation of every call's out[0, *out_len) is F's output up to the
+ *   first failure in file order: a failing unit of member j comes before j's trailer; a chain break delivers the good
+ *   members in front whole and the failing member's bytes in front of its failure, as the whole call; a wrong trailer
+ *   delivers up to and including that member's last byte and nothing behind it.  The sticky status and words are the
+ *   whole call's for that failure: *bad_member counts members over the file, *err_off is the member's FILE offset (or
+ *   the offset where no member could start), *stream_err_off counts from that member's raw stream's first byte across
+ *   parts, and a wrong trailer gives the member's length.  ONE DIFFERENCE from flate_hip_gzfile_read: of a file with a
+ *   wrong trailer in front of a chain break the reader reports the wrong trailer -- the whole call judges no trailer
+ *   once the chain breaks and reports the break, but only the reader's answer can be the same for every cut.  On
+ *   success the *in_used of all calls sum to F's length; *n_members of a call is the number of members whose trailers
+ *   it judged good, *n_units the complete units it delivered.
+ *   STATE.  Between two calls the reader stands at a BOUNDARY (the next part's first byte is where a header must stand,
+ *   or the file's end) or INSIDE a member (the next unit starts at bit b0 of the next part's first byte; the device
+ *   holds the 32 KiB window and the member's running CRC-32).  There is no "trailer pending" state: on EVERY part the
+ *   probes read in[.., in_len - 8), so a final block that is complete has its trailer inside the part; a unit that needs
+ *   more is cut, which is a verdict only on a final part (FLATE_HIP_E_UNEXPECTED_EOF, as the whole call).
+ *   ROOT.  INSIDE: FIND's PARTS build with candidate 0 at bit b0.  BOUNDARY: the header at byte 0 -- a byte that fails
+ *   is FLATE_HIP_E_CORRUPT at the file offset; a header the part cuts, or one with fewer than 8 bytes behind it, uses
+ *   nothing on a part that is not final and is the whole call's FLATE_HIP_E_CORRUPT on a final one.
+ *   THE PARTS HOP behind a final block at bit b, e = ceil(b / 8) + 8 <= in_len: e == in_len is the file's end on a
+ *   final part, else a BOUNDARY stop; a header at e (the header rule over in[e, in_len)) is the next member; otherwise
+ *   the chain is dead on a final part, and on any other part only where a byte of in[e, in_len) fails already -- else a
+ *   BOUNDARY stop at e.
+ *   DELIVERY is flate_hip_one_reader_read's: the longest prefix of complete units that fits out_cap, with the part's
+ *   own verdict behind them when everything in front fits.  A call that delivers no unit and has no verdict uses
+ *   nothing (in_len >= "one_unit_max": FLATE_HIP_E_TOO_LARGE).  *in_used is the byte of the first undelivered unit's
+ *   first bit; if that unit is a member's first, the trailer and the header in front of it are used.  A BOUNDARY stop
+ *   gives *in_used = e.
+ *   HISTORY never crosses a member: a unit of the continued member sees min(32768, the member's bytes before the part +
+ *   its offset inside the part's share of the member + the bytes produced), every other unit flate_hip_gzfile_read's
+ *   value.
+ *   CHECKSUMS.  One checksum launch is planned over the members' ranges inside the delivered bytes; the first range is
+ *   joined to the carried sum on the device; a thread per member that ends among the delivered units holds CRC-32 and
+ *   ISIZE against the trailer in the part.  The window behind the last delivered unit goes back into the handle once
+ *   the result words are good.
+ *   Host pointers: one upload and one download per call.  Device pointers: nothing outside out[0, planned total) is
+ *   written, planned total <= out_cap, and nothing outside out[0, *out_len) except in a call that reports a wrong
+ *   trailer, where out[*out_len, planned total) is unspecified.  Per call the host waits for the discovery's two
+ *   read-backs and one read-back of the result words.
+ *   Out of scope: "gzfile_serial_max" inside the reader (it is ignored: a file of many short members pays FIND per
+ *   part; routing short members whole is the follow-up); zlib or raw concatenations; overlapping the upload of part
+ *   k + 1 with the decode of part k; a seek index built in parts; the MoonBit binding. */
+typedef struct flate_hip_gzfile_reader flate_hip_gzfile_reader;
+int flate_hip_gzfile_reader_open(flate_hip_ctx *ctx, uint32_t flags, flate_hip_gzfile_reader **reader);
+int flate_hip_gzfile_reader_read(flate_hip_gzfile_reader *reader, const uint8_t *in, uint64_t in_len, int final_in,
+                                 uint8_t *out, uint64_t out_cap, uint64_t *in_used, uint64_t *out_len,
+                                 uint32_t *n_members, uint32_t *n_units, uint32_t *bad_member, int64_t *err_off,
+                                 int64_t *stream_err_off);
+int flate_hip_gzfile_reader_reset(flate_hip_gzfile_reader *reader);
+void flate_hip_gzfile_reader_free(flate_hip_gzfile_reader *reader);
 
 /* -- Seek index for any gzip file: build once, read ranges across members -------------
  * flate_hip_gzfile_read pays the whole discovery on every call and delivers everything.  flate_hip_gzfile_seek_index

@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "flate_hip.h"
+#include "gzfile_parts_rule.h"
 #include "gzfile_seek_rule.h"
 #include "one_parts_rule.h"
 #include "one_writer_rule.h"
@@ -204,6 +205,15 @@ inline int one_reader_open_args(const void *ctx, uint32_t wrap, uint32_t flags, 
 }
 inline int one_reader_read_args(const void *reader, const uint8_t *in, uint64_t in_len, const uint8_t *out, uint64_t out_cap,
                                 const uint64_t *in_used, const uint64_t *out_len) {
+  return one_parts_read_args(reader, in, in_len, out, out_cap, in_used, out_len);
+}
+
+// flate_hip_gzfile_reader_open / _read (gzfile_parts_rule.h; a read's pointers are checked as the one reader's)
+inline int gzfile_reader_open_args(const void *ctx, uint32_t flags, const void *reader) {
+  return gzfile_parts_open_args(ctx, flags, FLATE_HIP_DEVICE_PTRS, reader);
+}
+inline int gzfile_reader_read_args(const void *reader, const uint8_t *in, uint64_t in_len, const uint8_t *out,
+                                   uint64_t out_cap, const uint64_t *in_used, const uint64_t *out_len) {
   return one_parts_read_args(reader, in, in_len, out, out_cap, in_used, out_len);
 }
 

@@ -10,6 +10,7 @@
 
 #include "api_checks.h"
 #include "bgzf_range_rule.h"
+#include "gzfile_parts_rule.h"
 #include "gzfile_rule.h"
 #include "gzip_rule.h"
 #include "unit_rounds.h"
@@ -2254,6 +2255,416 @@ int flate_hip_gzfile_ranges(flate_hip_ctx *c, const uint8_t *in, uint64_t in_len
     // (bits are counted from the file's first byte and nothing at or behind the last trailer is read)
     const SeekRangesOut O{out, nr, RH.out_total, RH.scratch_total, r_lo, r_hi, sel, range_status, bad_unit, dev};
     return seek_ranges_decode(c, D, S, dec, per_round, ns, d_in, in_len - kGzipTrailerLen, O, seeds);
+  } catch (const std::exception &e) {
+    c->hip_err = e.what();
+    return FLATE_HIP_E_INTERNAL;
+  }
+}
+
+}  // extern "C"
+
+// ---- a gzip file of any members read in PARTS (gzfile_parts_rule.h, gzfile_parts_kernels.hip) ----
+
+// Between two calls the file's state rests in the handle: on the device the 32 KiB window and the running CRC-32 of
+// the member in progress (GzPartState), on the host the rule's words (GzPartsState).  The unit rule and "one_unit_max"
+// are the ctx's at open, whatever it says later; "gzfile_serial_max" is not read.
+struct flate_hip_gzfile_reader {
+  flate_hip_ctx *ctx = nullptr;
+  uint32_t flags = 0;
+  uint64_t unit_max = 0;
+  uint32_t stored_units = 0;
+  DevBuf state;
+  GzPartsState s = gzfile_parts_fresh();
+};
+
+namespace {
+
+// a fresh file: a window of zeros, the sum of nothing
+int gzfile_reader_fresh(flate_hip_gzfile_reader *r) {
+  flate_hip_ctx *c = r->ctx;
+  HIP_TRY(c, hipMemsetAsync(r->state.p, 0, sizeof(GzPartState), c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  r->s = gzfile_parts_fresh();
+  return FLATE_HIP_OK;
+}
+
+// The discovery over the PART d_in[0, in_len) (DEVICE memory, in_len != 0): gzfile_discover's passes with the part's
+// root and hop -- gzfile_part_init_kernel, FIND in its PARTS build (candidate 0 at the carried bit), the handle's unit
+// rule, gzfile_part_link_kernel / _finish_kernel, and gzfile_part_rel_kernel behind the member scan.  The same two
+// read-backs: the candidate counts (with the root's header verdict in HA.bad: anything but 0 ends the discovery
+// there), then the result words H / G with the INDEX -- unit_bit, out_off and u_start (cap + 1 entries each) and
+// u_final (cap) in one vector of 64-bit words, one array behind the other.
+struct GzPartIn {
+  uint64_t unit_max;
+  uint32_t stored_units;
+  uint32_t inside, b0, final_in;
+  uint64_t hist;
+};
+int gzfile_part_discover(flate_hip_ctx *c, const uint8_t *d_in, uint64_t in_len, const GzPartIn &part, OneHead &H,
+                         GzFileHead &G, GzFileParams &P, uint32_t &root_bad, std::vector<uint64_t> &index,
+                         std::vector<uint32_t> &u_final) {
+  int rc;
+  P = GzFileParams{};
+  OneParams PA{};
+  GzipParams PB{};
+  ChainParams &C = P.O.C;
+  uint32_t n_tiles = 0;
+  if ((rc = tiles_for(d_in, 0, in_len, &n_tiles))) return rc;
+  OneHead *head_a;
+  BgzfHead *head_b;
+  rc = carve(c, c->d_gzfile_tiles, [&](Carve &k) {
+    k.take(P.O.head, 1);
+    k.take(P.gh, 1);
+    k.take(P.O.one, 1);
+    k.take(head_a, 1);
+    k.take(head_b, 1);
+    k.take(PA.C.tile_cnt, (size_t)n_tiles + 1);
+    k.take(PB.C.tile_cnt, (size_t)n_tiles + 1);
+  });
+  if (rc) return rc;
+  C.in = PA.C.in = PB.C.in = d_in;
+  C.in_len = PA.C.in_len = PB.C.in_len = in_len;
+  C.n_tiles = PA.C.n_tiles = PB.C.n_tiles = n_tiles;
+  C.head = &P.O.head->h;
+  P.O.unit_max = PA.unit_max = part.unit_max;
+  P.O.stored_units = PA.stored_units = part.stored_units;
+  PA.C.head = &head_a->h;
+  PA.head = head_a;
+  PA.one = P.O.one;
+  PB.C.head = head_b;
+  PB.member_max = ~0ull;  // a member's range is never clipped
+  hipLaunchKernelGGL(gzfile_part_init_kernel, dim3(1), dim3(64), 0, c->stream, P.O.one, d_in, in_len, part.inside, part.b0);
+  one_find_launch(c, true, n_tiles, PA, true);
+  hipLaunchKernelGGL(chain_scan_kernel, dim3(1), dim3(1024), 0, c->stream, PA.C);
+  hipLaunchKernelGGL(gzip_count_kernel, dim3(n_tiles), dim3(256), 0, c->stream, PB);
+  hipLaunchKernelGGL(chain_scan_kernel, dim3(1), dim3(1024), 0, c->stream, PB.C);
+  HIP_TRY(c, hipGetLastError());
+  OneHead HA{};
+  BgzfHead HB{};
+  HIP_TRY(c, hipMemcpyAsync(&HA, head_a, sizeof HA, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(&HB, head_b, sizeof HB, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  root_bad = HA.bad;
+  if (root_bad) return FLATE_HIP_OK;
+  const uint32_t na = HA.h.n_cand, nb = HB.n_cand;
+  if ((uint64_t)na + nb > 0x7ffffff0ull) return FLATE_HIP_E_TOO_LARGE;  // (the counts saturate at 2^32 - 1)
+  const uint32_t cap = na + nb;
+  if ((rc = chain_size(C, cap)) || (rc = chain_size(PA.C, na)) || (rc = chain_size(PB.C, nb))) return rc;
+  P.n_a = na;
+  P.n_b = nb;
+
+  const size_t n = cap;
+  uint64_t *hdr_off;
+  rc = carve(c, c->d_gzfile, [&](Carve &k) {
+    k.take(C.cand_off, n);
+    k.take(hdr_off, (size_t)nb + 1);
+    k.take(PB.cand_end, nb);
+    k.take(P.O.probe, n);
+    k.take(C.jump[0], n + 2);
+    k.take(C.jump[1], n + 2);
+    k.take(C.path, C.path_len);
+    k.take(P.O.usize, n);
+    k.take(C.member_off, n + 1);
+    k.take(C.out_off, n + 1);
+    k.take(P.u_start, n + 1);
+    k.take(P.u_final, n);
+    k.take(P.u_member, n + 1);
+    k.take(P.rel_off, n + 1);
+    k.take(P.member_off, (size_t)nb + 2);
+    k.take(P.member_unit, (size_t)nb + 2);
+    k.take(P.member_out, (size_t)nb + 2);
+  });
+  if (rc) return rc;
+  PA.C.cand_off = C.cand_off;
+  PB.C.cand_off = hdr_off;
+  P.hdr_off = hdr_off;
+  one_find_launch(c, false, n_tiles, PA, true);
+  if (nb) {
+    hipLaunchKernelGGL(gzip_fill_kernel, dim3(n_tiles), dim3(256), 0, c->stream, PB);
+    hipLaunchKernelGGL(gzfile_bits_kernel, dim3((nb + 255) / 256), dim3(256), 0, c->stream, P);
+  }
+  if (cap) one_probe_launch(c, cap, P.O, 0u);
+  const uint32_t node_blocks = (uint32_t)(((uint64_t)cap + 2 + 255) / 256);
+  hipLaunchKernelGGL(gzfile_part_link_kernel, dim3(node_blocks), dim3(256), 0, c->stream, P, part.inside, part.final_in);
+  for (uint32_t j = 0; (1u << j) < C.path_len; ++j)
+    hipLaunchKernelGGL(chain_round_kernel, dim3(node_blocks), dim3(256), 0, c->stream, C, j);
+  hipLaunchKernelGGL(gzfile_part_finish_kernel, dim3((C.path_len + 255) / 256), dim3(256), 0, c->stream, P, part.final_in);
+  hipLaunchKernelGGL(one_out_scan_kernel, dim3(1), dim3(1024), 0, c->stream, P.O);
+  hipLaunchKernelGGL(gzfile_members_kernel, dim3(1), dim3(1024), 0, c->stream, P);
+  one_probe_launch(c, 1, P.O, 1u);
+  hipLaunchKernelGGL(gzfile_part_rel_kernel, dim3(node_blocks), dim3(256), 0, c->stream, P, part.hist);
+  HIP_TRY(c, hipGetLastError());
+  // ONE read-back behind the counts: the result words, then 28 bytes per node
+  index.assign(3 * (n + 1), 0);
+  u_final.assign(n + 1, 0);
+  HIP_TRY(c, hipMemcpyAsync(&H, P.O.head, sizeof H, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(&G, P.gh, sizeof G, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(index.data(), C.member_off, (n + 1) * 8, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(index.data() + (n + 1), C.out_off, (n + 1) * 8, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(index.data() + 2 * (n + 1), P.u_start, (n + 1) * 8, hipMemcpyDeviceToHost, c->stream));
+  if (n) HIP_TRY(c, hipMemcpyAsync(u_final.data(), P.u_final, n * 4, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  if (H.h.n_members > cap) return FLATE_HIP_E_INTERNAL;
+  return FLATE_HIP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int flate_hip_gzfile_reader_open(flate_hip_ctx *c, uint32_t flags, flate_hip_gzfile_reader **out) {
+  // every check before any HIP call
+  if (gzfile_reader_open_args(c, flags, out)) return FLATE_HIP_E_INVALID;
+  *out = nullptr;
+  c->hip_err.clear();
+  HIP_TRY(c, hipSetDevice(c->device));
+  flate_hip_gzfile_reader *r = new flate_hip_gzfile_reader();
+  r->ctx = c;
+  r->flags = flags;
+  r->unit_max = c->one_unit_max;
+  r->stored_units = c->one_stored_units;
+  int rc = ensure(c, r->state, sizeof(GzPartState) + 64);
+  if (rc == FLATE_HIP_OK) rc = gzfile_reader_fresh(r);
+  if (rc != FLATE_HIP_OK) {
+    delete r;
+    return rc;
+  }
+  *out = r;
+  return FLATE_HIP_OK;
+}
+
+int flate_hip_gzfile_reader_reset(flate_hip_gzfile_reader *r) {
+  if (!r) return FLATE_HIP_E_INVALID;
+  flate_hip_ctx *c = r->ctx;
+  c->hip_err.clear();
+  HIP_TRY(c, hipSetDevice(c->device));
+  return gzfile_reader_fresh(r);
+}
+
+void flate_hip_gzfile_reader_free(flate_hip_gzfile_reader *r) {
+  if (!r) return;
+  (void)hipSetDevice(r->ctx->device);
+  delete r;
+}
+
+// One call: flate_hip_gzfile_read on the part in[0, in_len), its chain rooted where the last call stopped -- discovery
+// (the index comes back with the result words: the host picks the units that fit and finds the members among them,
+// gzfile_parts_call), the rounds over those units with the handle's window as R[0] of the continued member, one
+// checksum launch over the members' ranges with the first joined to the running sum, the trailers of the members that
+// end, the verdict; then the window behind the last delivered unit goes back into the handle.
+int flate_hip_gzfile_reader_read(flate_hip_gzfile_reader *r, const uint8_t *in, uint64_t in_len, int final_in, uint8_t *out,
+                                 uint64_t out_cap, uint64_t *in_used, uint64_t *out_len, uint32_t *n_members,
+                                 uint32_t *n_units, uint32_t *bad_member, int64_t *err_off, int64_t *stream_err_off) {
+  // every check before any HIP call
+  if (gzfile_reader_read_args(r, in, in_len, out, out_cap, in_used, out_len)) return FLATE_HIP_E_INVALID;
+  *in_used = 0, *out_len = 0;
+  if (n_members) *n_members = 0;
+  if (n_units) *n_units = 0;
+  GzPartsState &s = r->s;
+  auto words = [&]() {
+    const bool bad = s.status < 0;
+    if (bad_member) *bad_member = bad ? s.bad_member : 0xffffffffu;
+    if (err_off) *err_off = bad ? s.err_off : -1;
+    if (stream_err_off) *stream_err_off = bad ? s.stream_err_off : -1;
+  };
+  words();
+  if (s.status) return s.status;  // sticky: the file's end, or its error
+  flate_hip_ctx *c = r->ctx;
+  c->hip_err.clear();
+  // a failure that needs no decode: the member in progress, or the place where a header had to stand
+  auto fail_here = [&](int st, bool no_header) {
+    s.status = st;
+    s.bad_member = s.members_done;
+    s.err_off = (int64_t)(no_header ? s.consumed : s.member_off);
+    s.stream_err_off = -1;
+    words();
+    return st;
+  };
+  const bool dev = (r->flags & FLATE_HIP_DEVICE_PTRS) != 0, fin = final_in != 0;
+  try {
+    int rc;
+    if (in_len == 0) {
+      if (!fin) return FLATE_HIP_OK;
+      if (s.inside) return fail_here(FLATE_HIP_E_UNEXPECTED_EOF, false);
+      s.status = FLATE_HIP_STREAM_END;  // the file ends at a member's end (an empty file: at its start)
+      return FLATE_HIP_STREAM_END;
+    }
+    if (s.inside && in_len <= kGzipTrailerLen)  // no raw byte in front of the trailer's room: the next unit is cut
+      return fin ? fail_here(FLATE_HIP_E_UNEXPECTED_EOF, false) : FLATE_HIP_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    GzPartState *st = (GzPartState *)r->state.p;
+    const uint8_t *d_in = nullptr;
+    if ((rc = stage_input(c, in, in_len, r->flags, &d_in))) return rc;
+    // the history in front of the part, as far as the distance rule can see it (it saturates at the window)
+    const uint64_t hist = !s.inside ? 0ull : s.produced < (uint64_t)kWinEntries ? s.produced : (uint64_t)kWinEntries;
+    const GzPartIn part{r->unit_max, r->stored_units, s.inside, s.b0, fin ? 1u : 0u, hist};
+    OneHead H{};
+    GzFileHead G{};
+    GzFileParams P{};
+    uint32_t root_bad = 0;
+    std::vector<uint64_t> index;
+    std::vector<uint32_t> u_final;
+    if ((rc = gzfile_part_discover(c, d_in, in_len, part, H, G, P, root_bad, index, u_final))) return rc;
+    if (root_bad == kPartsHdrBad || (root_bad && fin)) return fail_here(FLATE_HIP_E_CORRUPT, true);
+    if (root_bad) {  // the header is refused only because the part ends here: more is needed
+      if (in_len >= r->unit_max) return fail_here(FLATE_HIP_E_TOO_LARGE, true);
+      return FLATE_HIP_OK;
+    }
+    const size_t n1 = index.size() / 3;
+    GzPartsIndex X{};
+    X.n = H.h.n_members;
+    if ((size_t)X.n + 1 > n1) {
+      c->hip_err = "gzfile reader: the index does not hold the units";
+      return FLATE_HIP_E_INTERNAL;
+    }
+    X.unit_bit = index.data(), X.out_off = index.data() + n1, X.u_start = index.data() + 2 * n1;
+    X.u_final = u_final.data();
+    X.rc = H.h.rc, X.err_off = H.h.err_off, X.fail_unit = H.fail_unit, X.fail_out = H.fail_out, X.no_header = G.no_header;
+    const GzPartsCall call = gzfile_parts_call(s, X, in_len, fin, out_cap, r->unit_max);
+    const OnePartsPlan &plan = call.plan;
+    auto fail = [&](const GzPartsFail &f) {
+      gzfile_parts_fail(s, X, call, f);
+      words();
+      return f.status;
+    };
+    if (plan.action == kPartsNothing) return FLATE_HIP_OK;
+    if (plan.action == kPartsReturn) {
+      if (plan.status == FLATE_HIP_E_OUT_TOO_SMALL) {  // (not sticky: the state is unchanged)
+        *out_len = plan.need;
+        return FLATE_HIP_E_OUT_TOO_SMALL;
+      }
+      return fail(GzPartsFail{plan.status, 0xffffffffu, 0xffffffffu, -1});
+    }
+
+    const uint32_t n_dec = plan.n_del + plan.with_fail, n_segs = (uint32_t)call.segs.size();
+    const uint64_t total = plan.total;
+    uint8_t *d_out = out;
+    if (!dev) {
+      if ((rc = ensure(c, c->d_out, total + 16))) return rc;
+      d_out = (uint8_t *)c->d_out.p;
+    }
+    const uint32_t per_round = unit_per_round(c, n_dec);
+    GzFileDecParams GD{};
+    OneDecParams &D = GD.D;
+    UnitResults dec;
+    rc = unit_rounds_carve(c, D, n_dec, per_round, [&](Carve &k) { unit_pieces_take(k, D, &dec, per_round); });
+    if (rc) return rc;
+    GzPartParams Q{};
+    GzPartSeg *d_segs;
+    uint32_t *d_sums;
+    uint64_t *d_join;  // checksum_join_device's slot_off (3) and out_len (2)
+    rc = carve(c, c->d_gzfile_dec, [&](Carve &k) {
+      k.take(GD.seed, per_round);
+      k.take(GD.p_bit_off, per_round);
+      k.take(GD.p_bit_end, per_round);
+      k.take(d_join, 6);
+      k.take(d_segs, (size_t)n_segs + 1);
+      k.take(d_sums, (size_t)n_segs + 2);
+    });
+    if (rc) return rc;
+    if ((rc = unit_dec_params(c, D, d_in, P.O.one, P.O.C.member_off, P.O.C.out_off, P.O.stored_units, false))) return rc;
+    D.unit_max = r->unit_max;
+    unit_verdict_params(D, total, dec, P.O.head, FLATE_HIP_WRAP_GZIP, in_len);
+    GD.P = P;
+    GD.n_good = plan.n_del;
+    // R[0] of the first round: the handle's window
+    HIP_TRY(c, hipMemcpyAsync(D.R, st->window, kWinEntries, hipMemcpyDeviceToDevice, c->stream));
+    auto pieces = [&](uint32_t, uint32_t count) {
+      hipLaunchKernelGGL(gzfile_part_pieces_kernel, dim3((count + 1u + 255u) / 256u), dim3(256), 0, c->stream, GD, hist);
+      return FLATE_HIP_OK;
+    };
+    auto decode = [&](uint32_t, uint32_t count) {
+      const int e = unit_decode(c, unit_decode_params(D, d_in, H.raw_len, GD.p_bit_off, GD.p_bit_end, false, count, d_out,
+                                                      D.p_out_off, dec));
+      if (e) return e;
+      hipLaunchKernelGGL(one_check_kernel, dim3((count + 1u + 255u) / 256u), dim3(256), 0, c->stream, D);
+      return FLATE_HIP_OK;
+    };
+    bool used[FLATE_HIP_STAGE_COUNT] = {false, false, false, false};
+    if (n_dec) {
+      if ((rc = unit_rounds(c, D, P.rel_off, GD.seed, 0, n_dec, n_dec, per_round, unit_no_hook, pieces, decode))) return rc;
+      used[FLATE_HIP_STAGE_INFLATE] = true;
+    }
+    // the members' sums: ONE launch planned over their ranges of the delivered bytes; the continued member's first
+    // range is joined to the running sum
+    const uint64_t size0 = n_segs ? call.segs[0].out_end - call.segs[0].out_begin : 0ull;
+    Q.st = st;
+    Q.in = d_in;
+    Q.segs = d_segs;
+    Q.sums = d_sums;
+    Q.n_segs = n_segs;
+    Q.n_end = call.n_end;
+    Q.sum0_mode = !(call.continued && s.produced) ? 0u : size0 ? 2u : 1u;
+    Q.keep_sum = n_segs && call.segs.back().trailer_at == ~0ull ? 1u : 0u;
+    Q.n_del = plan.n_del;
+    Q.term_rc = plan.terminal ? H.h.rc : 0;
+    Q.term_err_off = H.h.err_off;
+    Q.total = total;
+    const uint64_t join[5] = {0, s.produced, s.produced + size0, s.produced, size0};
+    size_t up = n_segs * sizeof(GzPartSeg) + sizeof join + 1024;
+    if (n_segs && total) up += checksum_ctl_up_bytes(call.bounds.data(), n_segs);
+    if ((rc = ctl_begin(c, up, 0))) return rc;
+    if (n_segs && (rc = ctl_up(c, d_segs, call.segs.data(), n_segs * sizeof(GzPartSeg)))) return rc;
+    if ((rc = ctl_up(c, d_join, join, sizeof join))) return rc;
+    HIP_TRY(c, hipMemcpyAsync(d_sums, &st->sum, 4, hipMemcpyDeviceToDevice, c->stream));
+    if (n_segs && total) {
+      if ((rc = checksum_device(c, d_out, call.bounds.data(), n_segs, FLATE_HIP_CHECKSUM_CRC32, d_sums + 1,
+                                FLATE_HIP_STAGE_CHECKSUM)))
+        return rc;
+      used[FLATE_HIP_STAGE_CHECKSUM] = true;
+    }
+    // From here on the call queues work that moves the handle's device words (the result words, the running sum, the
+    // window): a failure of the runtime behind this point leaves them ahead of the host's state, so it ends the handle
+    // -- sticky, as the file's own errors are.  (In front of it nothing of the handle has been touched, and a call may
+    // be repeated.)
+    auto dead = [&](int e) {
+      s.status = e, s.bad_member = 0xffffffffu, s.err_off = -1, s.stream_err_off = -1;
+      words();
+      return e;
+    };
+    if (hipMemsetAsync(&st->res, 0xff, sizeof st->res, c->stream) != hipSuccess) return dead(FLATE_HIP_E_HIP);  // bad_trailer: none
+    if (Q.sum0_mode == 2u &&
+        (rc = checksum_join_device(c, d_sums, d_join, d_join + 3, 2, FLATE_HIP_CHECKSUM_CRC32, &st->joined, &st->total)))
+      return dead(rc);
+    if (call.n_end)
+      hipLaunchKernelGGL(gzfile_part_trailer_kernel, dim3((call.n_end + 255u) / 256u), dim3(256), 0, c->stream, Q, D);
+    hipLaunchKernelGGL(gzfile_part_carry_kernel, dim3(1), dim3(64), 0, c->stream, Q, D);
+    GzFileVerdict V{};
+    if (hipGetLastError() != hipSuccess ||
+        hipMemcpyAsync(&V, &st->res, sizeof V, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+        hipStreamSynchronize(c->stream) != hipSuccess)
+      return dead(FLATE_HIP_E_HIP);
+    ctl_finish(c);
+    if (V.out_len > total) return dead(FLATE_HIP_E_INTERNAL);
+    // THE CARRY, once the result words are good: the window behind the last unit, which the round driver leaves in
+    // R[count] of the last round (nothing has been queued behind the rounds that writes D.R)
+    if (n_dec && V.status == 0) {
+      const uint32_t last_count = n_dec - ((n_dec - 1u) / per_round) * per_round;
+      if (hipMemcpyAsync(st->window, D.R + (size_t)last_count * kWinEntries, kWinEntries, hipMemcpyDeviceToDevice,
+                         c->stream) != hipSuccess)
+        return dead(FLATE_HIP_E_HIP);
+    }
+    *out_len = V.out_len;
+    if (!dev && V.out_len &&
+        (hipMemcpyAsync(out, d_out, V.out_len, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+         hipStreamSynchronize(c->stream) != hipSuccess)) {
+      *out_len = 0;
+      return dead(FLATE_HIP_E_HIP);
+    }
+    if (c->profiling && (rc = collect_timing(c, used))) return dead(rc);
+    if (n_members) *n_members = V.n_members;
+    if (n_units) *n_units = V.n_units;
+    if (V.status) {
+      if (V.status == FLATE_HIP_E_INTERNAL) return dead(V.status);
+      return fail(GzPartsFail{V.status, V.bad_trailer, V.bad_member, V.err_off});
+    }
+    s = call.next;
+    *in_used = call.in_used;
+    if (call.at_end) {
+      s.status = FLATE_HIP_STREAM_END;
+      return FLATE_HIP_STREAM_END;
+    }
+    return FLATE_HIP_OK;
   } catch (const std::exception &e) {
     c->hip_err = e.what();
     return FLATE_HIP_E_INTERNAL;

@@ -910,6 +910,52 @@ __global__ void gzfile_pieces_kernel(GzFileDecParams G);
 __global__ void gzfile_trailer_kernel(GzFileDecParams G);
 __global__ void gzfile_verdict_kernel(GzFileDecParams G);
 
+// A gzip file read in PARTS (flate_hip_gzfile_reader_*; gzfile_parts_kernels.hip; the rule: gzfile_parts_rule.h).  A
+// call is the discovery and the rounds above over one part of the file.  FIND (its PARTS build: candidate 0 at bit
+// FrameOne::b0), PROBE, the chain rounds, the out-scan, the tail probe, gzfile_bits_kernel, gzfile_members_kernel,
+// TAIL, COMPOSE, RESOLVE, DECODE, the check and the checksum kernels run as they are, between the part's own:
+//   gzfile_part_init_kernel     the part's FrameOne (raw range in[0, in_len - 8), b0) and the root's header verdict
+//   gzfile_part_link_kernel     gzfile_link_kernel with THE PARTS HOP and the part's root; a BOUNDARY stop takes the
+//                               terminal sink
+//   gzfile_part_finish_kernel   gzfile_finish_kernel; the last good unit's thread records how the chain ended
+//   gzfile_part_rel_kernel      rel_off: the units in front of the part's first header (u_member == 0xffffffff) are the
+//                               continued member's and start at the carried count
+//   gzfile_part_pieces_kernel   gzfile_pieces_kernel; those units' seed is R[0], the handle's window
+//   gzfile_part_trailer_kernel  a thread per member that ends among the delivered units: CRC-32 (the continued member's
+//                               is the joined sum) and ISIZE against the trailer in the part, an ordered min
+//   gzfile_part_carry_kernel    the result words in file order, and the unfinished member's sum back into the handle
+constexpr uint32_t kGzPartEndFile = 0, kGzPartEndStop = 1, kGzPartEndDead = 2;  // GzFileHead::pad[0]
+struct GzPartSeg;            // (gzfile_parts_rule.h)
+struct GzPartState {         // per handle, in device memory
+  uint8_t window[32768];     // the 32 KiB in front of the next unit of the member in progress
+  uint64_t total;            // checksum_join_device's length word
+  uint32_t sum;              // the running CRC-32 of the member in progress (0: of nothing)
+  uint32_t joined;
+  GzFileVerdict res;         // the call's result words, read back: err_off counts from the part's first byte,
+                             // bad_member is the UNIT that TAIL failed in, bad_trailer the segment
+};
+struct GzPartParams {
+  GzPartState *st;
+  const uint8_t *in;
+  const GzPartSeg *segs;     // the members among the decoded units (uploaded)
+  const uint32_t *sums;      // [0]: the running sum as the call found it; [1 + i]: segment i's bytes of this call
+  uint32_t n_segs;
+  uint32_t n_end;            // the first n_end segments end among the delivered units
+  uint32_t sum0_mode;        // segment 0's sum: 0 = its own, 1 = the running one (no bytes in this call), 2 = joined
+  uint32_t keep_sum;         // the last segment goes on behind the call: its sum is the handle's next running sum
+  uint32_t n_del;            // complete units delivered if nothing fails
+  int32_t term_rc;           // the chain's verdict when the call delivers everything in front of it, else 0
+  int64_t term_err_off;
+  uint64_t total;
+};
+__global__ void gzfile_part_init_kernel(FrameOne *one, const uint8_t *in, uint64_t in_len, uint32_t inside, uint32_t b0);
+__global__ void gzfile_part_link_kernel(GzFileParams P, uint32_t inside, uint32_t final_in);
+__global__ void gzfile_part_finish_kernel(GzFileParams P, uint32_t final_in);
+__global__ void gzfile_part_rel_kernel(GzFileParams P, uint64_t hist);
+__global__ void gzfile_part_pieces_kernel(GzFileDecParams G, uint64_t hist);
+__global__ void gzfile_part_trailer_kernel(GzPartParams Q, OneDecParams D);
+__global__ void gzfile_part_carry_kernel(GzPartParams Q, OneDecParams D);
+
 // Short members decoded WHOLE (gzfile_serial_kernels.hip; the option "gzfile_serial_max" = S >= 1; the rule:
 // gzfile_serial_rule.h).  With the option off none of this is launched and the structures above are what they were.
 // PHASE 1 runs over List B alone, in front of FIND: gzfile_serial_ranges_kernel gives every B candidate its serial

@@ -692,6 +692,17 @@ class OnePartsCalls:
         return OneReader(self, wrap, device)
 
 
+class GzFilePartsCalls:
+    """A gzip file of any members read in parts: the method FlateEngine inherits.  It stands in a class of its own so
+    that its marshalling has its own recorded scenarios (tests/engine_trace_gzfile_parts.py) beside the ones of the
+    methods that were there before (tests/engine_trace.py)."""
+
+    def open_gzfile_reader(self, device=False):
+        """A gzip FILE of any members read in parts through bounded buffers at gzfile_read's speed
+        (flate_hip_gzfile_reader_*): see GzFileReader.  device: every part and every output is a torch CUDA tensor."""
+        return GzFileReader(self, device)
+
+
 class OneWriterCalls:
     """One long stream written in parts: the method FlateEngine inherits.  It stands in a class of its own so that its
     marshalling has its own recorded scenarios (tests/engine_trace_one_writer.py) beside the ones of the methods that
@@ -705,7 +716,7 @@ class OneWriterCalls:
 
 
 class FlateEngine(OneSeekCalls, SeekPackCalls, GzFileCalls, GzFileSerialCalls, GzFileSeekCalls, ZipUnitsCalls, GroupedCalls, OnePartsCalls,
-                  OneWriterCalls):
+                  OneWriterCalls, GzFilePartsCalls):
     """One engine = one flate_hip_ctx = one GPU + one HIP stream."""
 
     def __init__(self, device=0):
@@ -1526,6 +1537,64 @@ class OneReader:
     def close(self):
         if self._h:
             self._L.flate_hip_one_reader_free(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+GzFilePartRead = collections.namedtuple("GzFilePartRead", "rc out_len n_members n_units bad_member err_off stream_err_off")
+
+
+class GzFileReader:
+    """flate_hip_gzfile_read on a file the caller holds a part at a time (flate_hip_gzfile_reader_*): every read()
+    decodes the units that lie whole inside the part, across the members in it, judges the trailers of the members that
+    end among them, and the handle carries where the file stands.  read(part, final, out, out_cap) -> (in_used, out,
+    GzFilePartRead(rc, out_len, n_members, n_units, bad_member, err_off, stream_err_off)): `part` BEGINS with the bytes
+    the last read left unused; the bytes are out[:out_len]; rc 0 = go on, 1 = the end of the file, -2 = not even the
+    first unit fits (out_len: its size; nothing changed), -4 / -7 / -6 = the file's error, sticky, with the three words
+    counted over the FILE.  out=None behaves as OneReader's.  The unit rule and "one_unit_max" are the engine's at
+    open; "gzfile_serial_max" is not used."""
+
+    def __init__(self, eng, device=False):
+        self._eng, self._L = eng, eng._L
+        self._device = bool(device)
+        self._h = C.c_void_p()
+        eng._check(self._L.flate_hip_gzfile_reader_open(eng._ctx, eng._flags(False, False, self._device), C.byref(self._h)))
+
+    def read(self, part, final=False, out=None, out_cap=None):
+        part, in_ptr, n, device = _in_buf(part, accept_bytes=True, null_if_empty=True)
+        if device != self._device:
+            raise FlateError(E_INVALID, "GzFileReader.read: the part is not on the side the reader was opened for")
+        used, ol = C.c_uint64(0), C.c_uint64(0)
+        nm, nu, bm = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0xffffffff)
+        eo, so = C.c_int64(-1), C.c_int64(-1)
+
+        def call(out_ptr, cap):
+            rc = self._eng._tolerate(self._L.flate_hip_gzfile_reader_read(
+                self._h, in_ptr, n, 1 if final else 0, out_ptr, cap, C.byref(used), C.byref(ol), C.byref(nm),
+                C.byref(nu), C.byref(bm), C.byref(eo), C.byref(so)), 1, *PER_CHAIN)  # (1: the end of the file)
+            return GzFilePartRead(rc, int(ol.value), int(nm.value), int(nu.value), int(bm.value), int(eo.value),
+                                  int(so.value))
+
+        size = max(4 * n, 1 << 16) if out_cap is None else int(out_cap)
+        buf, ptr, cap = _out_buf(out, part, size, out_cap, 0, "GzFileReader.read", floor=1)
+        res = call(ptr, cap)
+        if res.rc == E_OUT_TOO_SMALL and out is None and out_cap is None:
+            buf, ptr, cap = _out_buf(None, part, res.out_len, None, 0, "GzFileReader.read", floor=1)
+            res = call(ptr, cap)
+        return int(used.value), (buf[:0] if res.rc == E_OUT_TOO_SMALL else buf[:res.out_len]), res
+
+    def reset(self):
+        """A fresh file on the same handle: same side, same options."""
+        self._eng._check(self._L.flate_hip_gzfile_reader_reset(self._h))
+
+    def close(self):
+        if self._h:
+            self._L.flate_hip_gzfile_reader_free(self._h)
             self._h = C.c_void_p()
 
     def __del__(self):

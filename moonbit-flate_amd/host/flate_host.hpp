@@ -958,6 +958,138 @@ class OneReader {
   Err err_;
 };
 
+// The same Reader over a gzip FILE of any members at flate_hip_gzfile_read's speed (flate_hip_gzfile_reader_*): every
+// step decodes, in parallel, the units that lie whole inside the input piece, across the members in it, and judges the
+// trailers of the members that end among them; the handle carries where the file stands.  The pieces and the loop are
+// OneReader's, and so is the grain: the output piece grows to a first unit that does not fit, the input piece (doubled)
+// when it is full and holds no complete unit.  Bytes and errors come out as Reader's: data first, the error (ioeof at the
+// file's end) with the last bytes; a corrupt file reports the member's FILE offset, and failure() holds the other words.
+class GzFileReader {
+ public:
+  struct Failure {
+    uint32_t bad_member = 0xffffffffu;
+    int64_t err_off = -1, stream_err_off = -1;
+  };
+  GzFileReader(ByteSource &r, Engine &e, size_t in_piece = 1u << 24, size_t out_piece = 1u << 26)
+      : r_(&r), e_(e), in_piece_(in_piece < 4096 ? 4096 : in_piece), out_piece_(out_piece < 1 ? 1 : out_piece) {}
+  ~GzFileReader() { flate_hip_gzfile_reader_free(h_); }
+  GzFileReader(const GzFileReader &) = delete;
+  GzFileReader &operator=(const GzFileReader &) = delete;
+
+  // a fresh file from `r` on the same handle, with the unit rule and "one_unit_max" the engine had when the handle was
+  // opened, which is in the first step that decodes
+  void reset(ByteSource &r) {
+    r_ = &r;
+    fresh_ = true;
+    in_.clear();
+    src_end_ = false;
+    len_ = 0;
+    pos_ = 0;
+    members_ = 0;
+    fail_ = Failure();
+    err_ = std::nullopt;
+  }
+
+  std::pair<int, Err> read(uint8_t *p, size_t n) {
+    for (;;) {
+      if (pos_ < len_) {
+        const size_t k = std::min(n, len_ - pos_);
+        std::copy(data_.begin() + pos_, data_.begin() + pos_ + k, p);
+        pos_ += k;
+        if (pos_ == len_) return {(int)k, err_};
+        return {(int)k, std::nullopt};
+      }
+      if (err_) return {0, err_};
+      step();
+    }
+  }
+  Err close() {
+    if (err_ && *err_ == ioeof()) return std::nullopt;
+    return err_;
+  }
+  size_t resident_bytes() const { return in_.capacity() + data_.capacity(); }
+  uint64_t calls() const { return calls_; }
+  uint64_t members() const { return members_; }  // members whose trailers were judged good so far
+  const Failure &failure() const { return fail_; }
+
+ private:
+  void step() {
+    if (!e_.ok()) {
+      err_ = make_error(e_, e_.status());
+      return;
+    }
+    if (!h_) {
+      const int rc = flate_hip_gzfile_reader_open(e_.ctx(), 0, &h_);
+      if (rc != 0) {
+        err_ = make_error(e_, rc);
+        return;
+      }
+      fresh_ = false;
+    }
+    if (fresh_) {
+      const int rc = flate_hip_gzfile_reader_reset(h_);
+      if (rc != 0) {
+        err_ = make_error(e_, rc);
+        return;
+      }
+      fresh_ = false;
+    }
+    bool stalled = false;  // the source gave no byte and no error: decode what is here, do not ask again in this step
+    while (!src_end_ && !stalled && in_.size() < in_piece_) {
+      const size_t at = in_.size();
+      in_.resize(in_piece_);
+      auto r = r_->read(in_.data() + at, in_piece_ - at);
+      in_.resize(at + (size_t)r.first);
+      if (r.second) {
+        if (!(*r.second == ioeof())) {
+          err_ = r.second;
+          return;
+        }
+        src_end_ = true;
+      }
+      stalled = r.first == 0 && !r.second;
+    }
+    if (data_.size() < out_piece_) data_.resize(out_piece_);  // (the piece is filled once, not per step)
+    pos_ = 0;
+    len_ = 0;
+    uint64_t used = 0, got = 0;
+    uint32_t members = 0;
+    Failure f;
+    ++calls_;
+    const int rc = flate_hip_gzfile_reader_read(h_, in_.data(), in_.size(), src_end_ ? 1 : 0, data_.data(), out_piece_, &used,
+                                                &got, &members, nullptr, &f.bad_member, &f.err_off, &f.stream_err_off);
+    if (rc == FLATE_HIP_E_OUT_TOO_SMALL) {  // not even the first unit fits: room for it, nothing has changed
+      out_piece_ = (size_t)got;
+      return;
+    }
+    len_ = (size_t)got;
+    members_ += members;
+    in_.erase(in_.begin(), in_.begin() + (size_t)used);
+    if (rc < 0) fail_ = f;
+    if (rc == FLATE_HIP_STREAM_END) err_ = ioeof();
+    else if (rc == FLATE_HIP_E_CORRUPT) err_ = corrupt_input_error(f.err_off);
+    else if (rc == FLATE_HIP_E_UNEXPECTED_EOF) err_ = err_unexpected_eof();
+    else if (rc != 0) err_ = make_error(e_, rc);
+    else if (got == 0 && used == 0) {
+      if (src_end_) err_ = make_error(e_, FLATE_HIP_E_INTERNAL);  // (no progress on the file's last bytes)
+      else if (stalled) err_ = IOError{"flate_host::GzFileReader: the source delivers neither bytes nor an error"};
+      else if (in_.size() >= in_piece_) in_piece_ *= 2;           // a unit longer than the piece: it has to lie in it whole
+    }
+  }
+  ByteSource *r_;
+  Engine &e_;
+  size_t in_piece_, out_piece_;
+  flate_hip_gzfile_reader *h_ = nullptr;
+  bool fresh_ = false;
+  std::vector<uint8_t> in_;
+  bool src_end_ = false;
+  std::vector<uint8_t> data_;  // the output piece; its first len_ bytes are decoded and not all handed out yet
+  size_t len_ = 0, pos_ = 0;
+  uint64_t calls_ = 0, members_ = 0;
+  Failure fail_;
+  Err err_;
+};
+
 // A Writer (writer.mbt:45,53: write, close) over ONE LONG raw, zlib or gzip stream at the batch encoder's speed
 // (flate_hip_one_writer_*): the stream is cut into independent pieces of piece_bytes bytes (0: 65535), every step
 // compresses, in parallel, the whole pieces that are staged, and the handle carries the last incomplete byte, the running
