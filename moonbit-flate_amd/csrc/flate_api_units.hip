@@ -13,6 +13,7 @@
 #include "gzfile_parts_rule.h"
 #include "gzfile_rule.h"
 #include "gzip_rule.h"
+#include "unit_discovery.h"
 #include "unit_rounds.h"
 
 using namespace flate;
@@ -20,39 +21,6 @@ using namespace flate_host;
 
 // ---- one long stream: block discovery (one_kernels.hip, one_probe_kernel.inc) ----
 namespace {
-
-// FIND's count pass or fill pass over n_tiles tiles, in the build of P's unit rule (option "one_stored_units")
-// parts: the builds whose chain starts at bit FrameOne::b0 (a stream read in parts)
-void one_find_launch(flate_hip_ctx *c, bool count, uint32_t n_tiles, const OneParams &P, bool parts = false) {
-  if (parts) {
-    if (count && P.stored_units)
-      hipLaunchKernelGGL((one_count_kernel<true, true>), dim3(n_tiles), dim3(256), 0, c->stream, P);
-    else if (count)
-      hipLaunchKernelGGL((one_count_kernel<false, true>), dim3(n_tiles), dim3(256), 0, c->stream, P);
-    else if (P.stored_units)
-      hipLaunchKernelGGL((one_fill_kernel<true, true>), dim3(n_tiles), dim3(256), 0, c->stream, P);
-    else
-      hipLaunchKernelGGL((one_fill_kernel<false, true>), dim3(n_tiles), dim3(256), 0, c->stream, P);
-    return;
-  }
-  if (count && P.stored_units)
-    hipLaunchKernelGGL(one_count_kernel<true>, dim3(n_tiles), dim3(256), 0, c->stream, P);
-  else if (count)
-    hipLaunchKernelGGL(one_count_kernel<false>, dim3(n_tiles), dim3(256), 0, c->stream, P);
-  else if (P.stored_units)
-    hipLaunchKernelGGL(one_fill_kernel<true>, dim3(n_tiles), dim3(256), 0, c->stream, P);
-  else
-    hipLaunchKernelGGL(one_fill_kernel<false>, dim3(n_tiles), dim3(256), 0, c->stream, P);
-}
-
-// PROBE over n_blocks candidates (or the one tail probe), in the build of the unit rule its parameters carry (TAIL:
-// one_tail_launch, unit_rounds.h)
-void one_probe_launch(flate_hip_ctx *c, uint32_t n_blocks, const OneParams &P, uint32_t tail) {
-  if (P.stored_units)
-    hipLaunchKernelGGL(one_probe_kernel<true>, dim3(n_blocks), dim3(64), 0, c->stream, P, tail);
-  else
-    hipLaunchKernelGGL(one_probe_kernel<false>, dim3(n_blocks), dim3(64), 0, c->stream, P, tail);
-}
 
 // The container around ONE stream as the device reads it: one_init_kernel leaves the raw stream's range {0, in_len} in
 // `one`, and for zlib / gzip frame_parse_kernel moves it behind the header and in front of the trailer, by the header
@@ -111,27 +79,14 @@ int one_discover(flate_hip_ctx *c, const uint8_t *d_in, uint64_t in_len, uint32_
                        part->final_in, part->b0);
   else
     one_parse_launch(c, d_in, in_len, P.one, wrap);
-  one_find_launch(c, true, C.n_tiles, P, part != nullptr);
-  hipLaunchKernelGGL(chain_scan_kernel, dim3(1), dim3(1024), 0, c->stream, C);
-  HIP_TRY(c, hipGetLastError());
-  HIP_TRY(c, hipMemcpyAsync(&H, P.head, sizeof H, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  find_count(c, P, part != nullptr);
+  if ((rc = find_counts_back(c, P.head, H))) return rc;
   const uint32_t cap = H.h.n_cand;
   if ((rc = chain_size(C, cap))) return rc;  // (the count saturates at 2^32 - 1)
   if (cap == 0) return FLATE_HIP_OK;  // (a bad header: the scan kernel has left FLATE_HIP_E_CORRUPT at offset 0)
 
   const size_t n = cap;
-  rc = carve(c, c->d_one, [&](Carve &k) {
-    k.take(C.cand_off, n);
-    k.take(P.probe, n);
-    k.take(C.jump[0], n + 2);
-    k.take(C.jump[1], n + 2);
-    k.take(C.path, C.path_len);
-    k.take(P.usize, n);
-    k.take(C.member_off, n + 1);
-    k.take(C.out_off, n + 1);
-  });
-  if (rc) return rc;
+  if ((rc = carve(c, c->d_one, [&](Carve &k) { chain_nodes_take(k, P, n, [](Carve &) {}); }))) return rc;
   one_find_launch(c, false, C.n_tiles, P, part != nullptr);
   one_probe_launch(c, cap, P, 0u);
   if ((rc = chain_tail(c, C, part ? one_part_link_kernel : one_link_kernel, P, one_finish_kernel, one_out_scan_kernel, P)))
@@ -202,11 +157,8 @@ int seek_ranges_decode(flate_hip_ctx *c, OneDecParams &D, OneSeekRoundParams &S,
   int rc;
   if ((rc = ensure(c, c->d_one_seek_dense, O.scratch_total + 64))) return rc;
   uint8_t *d_dense = (uint8_t *)c->d_one_seek_dense.p;
-  uint8_t *d_out = O.out;
-  if (!O.dev) {
-    if ((rc = ensure(c, c->d_out, O.out_total + 16))) return rc;
-    d_out = (uint8_t *)c->d_out.p;
-  }
+  uint8_t *d_out;
+  if ((rc = unit_out_buffer(c, O.out, O.dev, O.out_total, d_out))) return rc;
   auto decode = [&](uint32_t i0, uint32_t count) {
     const int r = unit_decode(c, unit_decode_params(D, in, in_len, S.p_bit_off, S.p_bit_end, false, count, d_dense,
                                                     S.Q.sel_at + i0, dec));
@@ -322,11 +274,8 @@ int flate_hip_inflate_one(flate_hip_ctx *c, const uint8_t *in, uint64_t in_len, 
     const uint64_t total = H.prefix_bytes + (H.fail_unit ? H.fail_out : 0ull);
     *out_len = total;
     if (total > out_cap) return FLATE_HIP_E_OUT_TOO_SMALL;  // (nothing is decoded; out == NULL: the size query)
-    uint8_t *d_out = out;
-    if (!dev) {
-      if ((rc = ensure(c, c->d_out, total + 16))) return rc;
-      d_out = (uint8_t *)c->d_out.p;
-    }
+    uint8_t *d_out;
+    if ((rc = unit_out_buffer(c, out, dev, total, d_out))) return rc;
     const uint32_t per_round = unit_per_round(c, n_dec);
     OneDecParams D{};
     uint32_t *d_sum;
@@ -341,14 +290,8 @@ int flate_hip_inflate_one(flate_hip_ctx *c, const uint8_t *in, uint64_t in_len, 
     // stream's last piece runs to BFINAL (or to its failure); every other round's last piece ends where the next
     // unit starts, and so does the last unit of a chain that stopped at a header the decoder refuses.
     auto decode = [&](uint32_t u0, uint32_t count) {
-      const uint32_t unit_blocks = (count + 1u + 255u) / 256u;
-      hipLaunchKernelGGL(one_pieces_kernel, dim3(unit_blocks), dim3(256), 0, c->stream, D);
       const bool closed = u0 + count < n_dec || (H.h.rc != 0 && !H.fail_unit);
-      const int r = unit_decode(c, unit_decode_params(D, d_in + H.raw_off, H.raw_len, D.unit_bit + u0, nullptr, closed, count,
-                                                      d_out, D.p_out_off, dec));
-      if (r) return r;
-      hipLaunchKernelGGL(one_check_kernel, dim3(unit_blocks), dim3(256), 0, c->stream, D);
-      return FLATE_HIP_OK;
+      return unit_decode_chain(c, D, d_in + H.raw_off, H.raw_len, u0, count, closed, d_out, dec);
     };
     if ((rc = unit_rounds(c, D, nullptr, nullptr, 0, n_dec, n_dec, per_round, unit_no_hook, unit_no_hook, decode))) return rc;
     bool used[FLATE_HIP_STAGE_COUNT] = {false, false, false, false};
@@ -369,12 +312,7 @@ int flate_hip_inflate_one(flate_hip_ctx *c, const uint8_t *in, uint64_t in_len, 
     HIP_TRY(c, hipMemcpyAsync(&R, D.dh, sizeof R, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     if (ctl) ctl_finish(c);
-    if (R.out_len > total) return FLATE_HIP_E_INTERNAL;
-    *out_len = R.out_len;
-    if (!dev && R.out_len) {  // the result comes down once
-      HIP_TRY(c, hipMemcpyAsync(out, d_out, R.out_len, hipMemcpyDeviceToHost, c->stream));
-      HIP_TRY(c, hipStreamSynchronize(c->stream));
-    }
+    if ((rc = unit_deliver(c, out, d_out, dev, R.out_len, total, out_len))) return rc;
     if (c->profiling && (rc = collect_timing(c, used))) return rc;
     return verdict(R.status, R.err_off);
   } catch (const std::exception &e) {
@@ -1039,13 +977,9 @@ int flate_hip_inflate_one_ranges_packed(flate_hip_ctx *c, const uint8_t *in, uin
 
 // Between two calls the stream's state rests in the handle: on the device the 32 KiB window and the running checksum
 // (OnePartState), on the host the rule's words (OnePartsState: the carried bit, the bytes produced and consumed, the
-// sticky status).  The unit rule and "one_unit_max" are the ctx's at open, whatever it says later.
-struct flate_hip_one_reader {
-  flate_hip_ctx *ctx = nullptr;
-  uint32_t wrap = 0, flags = 0;
-  uint64_t unit_max = 0;
-  uint32_t stored_units = 0;
-  DevBuf state;
+// sticky status).  The unit rule and "one_unit_max" are the ctx's at open, whatever it says later (UnitReader).
+struct flate_hip_one_reader : UnitReader {
+  uint32_t wrap = 0;
   OnePartsState s = one_parts_fresh();
 };
 
@@ -1079,38 +1013,16 @@ extern "C" {
 int flate_hip_one_reader_open(flate_hip_ctx *c, uint32_t wrap, uint32_t flags, flate_hip_one_reader **out) {
   // every check before any HIP call
   if (one_reader_open_args(c, wrap, flags, out)) return FLATE_HIP_E_INVALID;
-  *out = nullptr;
-  c->hip_err.clear();
-  HIP_TRY(c, hipSetDevice(c->device));
-  flate_hip_one_reader *r = new flate_hip_one_reader();
-  r->ctx = c;
-  r->wrap = wrap;
-  r->flags = flags;
-  r->unit_max = c->one_unit_max;
-  r->stored_units = c->one_stored_units;
-  int rc = ensure(c, r->state, sizeof(OnePartState) + 64);
-  if (rc == FLATE_HIP_OK) rc = one_reader_fresh(r);
-  if (rc != FLATE_HIP_OK) {
-    delete r;
-    return rc;
-  }
-  *out = r;
-  return FLATE_HIP_OK;
+  auto fresh = [wrap](flate_hip_one_reader *r) {
+    r->wrap = wrap;
+    return one_reader_fresh(r);
+  };
+  return unit_reader_open(c, flags, sizeof(OnePartState), fresh, out);
 }
 
-int flate_hip_one_reader_reset(flate_hip_one_reader *r) {
-  if (!r) return FLATE_HIP_E_INVALID;
-  flate_hip_ctx *c = r->ctx;
-  c->hip_err.clear();
-  HIP_TRY(c, hipSetDevice(c->device));
-  return one_reader_fresh(r);
-}
+int flate_hip_one_reader_reset(flate_hip_one_reader *r) { return unit_reader_reset(r, one_reader_fresh); }
 
-void flate_hip_one_reader_free(flate_hip_one_reader *r) {
-  if (!r) return;
-  (void)hipSetDevice(r->ctx->device);
-  delete r;
-}
+void flate_hip_one_reader_free(flate_hip_one_reader *r) { unit_reader_free(r); }
 
 // One call: flate_hip_inflate_one on the part in[0, in_len), its chain rooted at the carried bit -- discovery (the
 // index comes back with the result words: the host picks the units that fit, one_parts_plan), the rounds over those
@@ -1199,11 +1111,8 @@ int flate_hip_one_reader_read(flate_hip_one_reader *r, const uint8_t *in, uint64
 
     const uint32_t n_dec = plan.n_del + plan.with_fail;
     const uint64_t total = plan.total;
-    uint8_t *d_out = out;
-    if (!dev) {
-      if ((rc = ensure(c, c->d_out, total + 16))) return rc;
-      d_out = (uint8_t *)c->d_out.p;
-    }
+    uint8_t *d_out;
+    if ((rc = unit_out_buffer(c, out, dev, total, d_out))) return rc;
     // the history in front of the part, as far as the distance rule can see it (it saturates at the window)
     const uint64_t hist = s.produced < (uint64_t)kWinEntries ? s.produced : (uint64_t)kWinEntries;
     const uint32_t per_round = unit_per_round(c, n_dec);
@@ -1219,19 +1128,11 @@ int flate_hip_one_reader_read(flate_hip_one_reader *r, const uint8_t *in, uint64
     D.unit_max = r->unit_max;
     D.hist_base = hist;
     unit_verdict_params(D, total, dec, P.head, wrap, in_len);
-    // R[0] of the first round: the handle's window
-    HIP_TRY(c, hipMemcpyAsync(D.R, st->window, kWinEntries, hipMemcpyDeviceToDevice, c->stream));
+    if ((rc = unit_window_seed(c, D, st->window))) return rc;
     // the last piece runs to BFINAL or to its failure only where the part's verdict is delivered with it
     const bool open_last = plan.terminal && (H.h.rc == 0 || H.fail_unit);
     auto decode = [&](uint32_t u0, uint32_t count) {
-      const uint32_t unit_blocks = (count + 1u + 255u) / 256u;
-      hipLaunchKernelGGL(one_pieces_kernel, dim3(unit_blocks), dim3(256), 0, c->stream, D);
-      const bool closed = u0 + count < n_dec || !open_last;
-      const int e = unit_decode(c, unit_decode_params(D, d_in + H.raw_off, H.raw_len, D.unit_bit + u0, nullptr, closed, count,
-                                                      d_out, D.p_out_off, dec));
-      if (e) return e;
-      hipLaunchKernelGGL(one_check_kernel, dim3(unit_blocks), dim3(256), 0, c->stream, D);
-      return FLATE_HIP_OK;
+      return unit_decode_chain(c, D, d_in + H.raw_off, H.raw_len, u0, count, u0 + count < n_dec || !open_last, d_out, dec);
     };
     bool used[FLATE_HIP_STAGE_COUNT] = {false, false, false, false};
     if (n_dec) {
@@ -1278,22 +1179,8 @@ int flate_hip_one_reader_read(flate_hip_one_reader *r, const uint8_t *in, uint64
     if ((rc = one_reader_result(c, st, R, trailer_bad))) return dead(rc);
     if (ctl) ctl_finish(c);
     ctl = false;
-    if (R.out_len > total) return dead(FLATE_HIP_E_INTERNAL);
-    // THE CARRY, once the result words are good: the window behind the last unit, which the round driver leaves in
-    // R[count] of the last round (nothing has been queued behind the rounds that writes D.R)
-    if (n_dec && R.status == 0) {
-      const uint32_t last_count = n_dec - ((n_dec - 1u) / per_round) * per_round;
-      if (hipMemcpyAsync(st->window, D.R + (size_t)last_count * kWinEntries, kWinEntries, hipMemcpyDeviceToDevice,
-                         c->stream) != hipSuccess)
-        return dead(FLATE_HIP_E_HIP);
-    }
-    *out_len = R.out_len;
-    if (!dev && R.out_len &&
-        (hipMemcpyAsync(out, d_out, R.out_len, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
-         hipStreamSynchronize(c->stream) != hipSuccess)) {
-      *out_len = 0;
-      return dead(FLATE_HIP_E_HIP);
-    }
+    if ((rc = unit_reader_deliver(c, D, st->window, n_dec, per_round, R.status == 0, out, d_out, dev, R.out_len, total, out_len)))
+      return dead(rc);
     if (c->profiling && (rc = collect_timing(c, used))) return dead(rc);
     if (n_units) *n_units = plan.n_del;
     if (R.status)  // (a trailer's mismatch counts from the member's first byte, everything else from the raw stream's)
@@ -1316,111 +1203,188 @@ int flate_hip_one_reader_read(flate_hip_one_reader *r, const uint8_t *in, uint64
 // ---- a gzip file of any members: the units of all members as one chain (gzfile_kernels.hip, gzfile_rule.h) ----
 namespace {
 
-// The discovery over the file d_in[0, in_len) (DEVICE memory, in_len != 0) on the ctx's stream: the two count passes
-// and their scans, ONE read-back of the two candidate counts, then the fills, the B nodes' bits, the probe of every
-// node, link, rounds, finish, out-scan, the member scan, the tail probe, the member words and ONE read-back of the
-// result words H / G -- with member_out (the members' places in the output, n_b + 2 entries of which G.n_members + 1
-// count) when `mout` is given.  The index stays on the device (P).  Counted in no profiling stage.
-int gzfile_discover(flate_hip_ctx *c, const uint8_t *d_in, uint64_t in_len, OneHead &H, GzFileHead &G, GzFileParams &P,
-                    std::vector<uint64_t> *mout) {
+// A PART of a file read in parts (flate_hip_gzfile_reader_read): the handle's unit rule, where the last call stopped
+// (inside a member at bit b0, or at a header), whether the file ends with the part, and the history in front of it.
+struct GzPartIn {
+  uint64_t unit_max;
+  uint32_t stored_units;
+  uint32_t inside, b0, final_in;
+  uint64_t hist;
+};
+// What the discovery's last read-back fetches beside the result words H / G.  The whole file: member_out, the members'
+// places in the output (n_b + 2 entries of which G.n_members + 1 count).  A part: the INDEX -- unit_bit, out_off and
+// u_start (cap + 1 entries each) in one vector of 64-bit words, one array behind the other, and u_final (cap).
+struct GzFileBack {
+  std::vector<uint64_t> *mout = nullptr;
+  std::vector<uint64_t> *index = nullptr;
+  std::vector<uint32_t> *u_final = nullptr;
+};
+// "gzfile_serial_max": phase 1's words (gzfile_discover_serial) for the chain behind it
+struct GzSerialIn {
+  GzSerialParams &S;
+  GzSerialHead &SH;
+  uint64_t find_from;
+};
+
+// The chain of a file's discovery, behind the counts na / nb of the two lists (unit_discovery.h): the size rule, the
+// carve of c->d_gzfile, the fills and the B nodes' bits, the probe of every node, link, rounds, finish, out-scan, the
+// member scan, the tail probe, the member words and ONE read-back of H / G with what `back` names.
+//   part  the chain's root and hop are the part's: gzfile_part_link_kernel / _finish_kernel / _rel_kernel, FIND in its
+//         PARTS build
+//   ser   List B was filled and sized by phase 1, whose arrays hold hdr_off; FIND's fill runs over the suffix PA names
+//         and one small kernel moves its bits to the file's origin; a whole B node is parked at the raw stream's end for
+//         PROBE and gets its phase-1 record back behind it; the marks between finish and out-scan, the list of whole
+//         members at the end, SH in the read-back
+int gzfile_chain(flate_hip_ctx *c, GzFileParams &P, OneParams &PA, GzipParams &PB, uint32_t na, uint32_t nb,
+                 const GzPartIn *part, const GzSerialIn *ser, OneHead &H, GzFileHead &G, const GzFileBack &back) {
   int rc;
-  P = GzFileParams{};
-  OneParams PA{};
-  GzipParams PB{};
   ChainParams &C = P.O.C;
-  uint32_t n_tiles = 0;
-  if ((rc = tiles_for(d_in, 0, in_len, &n_tiles))) return rc;
-  OneHead *head_a;
+  if ((rc = two_list_size(C, PA.C, ser ? nullptr : &PB.C, na, nb))) return rc;
+  P.n_a = na;
+  P.n_b = nb;
+  const size_t n = C.cap;
+  rc = unit_nodes_carve(
+      c, c->d_gzfile, P, P.u_member, n,
+      [&](Carve &k) {
+        if (ser) return;
+        k.take(PB.C.cand_off, (size_t)nb + 1);
+        k.take(PB.cand_end, nb);
+      },
+      [&](Carve &k) {
+        k.take(P.member_off, (size_t)nb + 2);
+        k.take(P.member_unit, (size_t)nb + 2);
+        k.take(P.member_out, (size_t)nb + 2);
+      });
+  if (rc) return rc;
+  PA.C.cand_off = C.cand_off;
+  if (ser) {
+    GzSerialParams &S = ser->S;
+    S.n_a = na;
+    rc = carve(c, c->d_gzfile_serial_units, [&](Carve &k) {
+      k.take(S.u_whole, n + 1);
+      k.take(S.u_end, n + 1);
+    });
+    if (rc) return rc;
+    if (ser->find_from < C.in_len) {
+      one_find_launch(c, false, PA.C.n_tiles, PA, false);
+      if (na)
+        hipLaunchKernelGGL(gzfile_serial_base_kernel, dim3((na + 255u) / 256u), dim3(256), 0, c->stream, C.cand_off, na,
+                           8u * ser->find_from);
+    }
+    if (nb) hipLaunchKernelGGL(gzfile_serial_bits_kernel, dim3((nb + 255) / 256), dim3(256), 0, c->stream, P, S);
+  } else {
+    P.hdr_off = PB.C.cand_off;
+    one_find_launch(c, false, C.n_tiles, PA, part != nullptr);
+    if (nb) {
+      hipLaunchKernelGGL(gzip_fill_kernel, dim3(C.n_tiles), dim3(256), 0, c->stream, PB);
+      hipLaunchKernelGGL(gzfile_bits_kernel, dim3((nb + 255) / 256), dim3(256), 0, c->stream, P);
+    }
+  }
+  if (n) one_probe_launch(c, C.cap, P.O, 0u);
+  if (ser && nb) hipLaunchKernelGGL(gzfile_serial_keep_kernel, dim3((nb + 255) / 256), dim3(256), 0, c->stream, P, ser->S);
+  auto link = [&](dim3 g) {
+    if (part)
+      hipLaunchKernelGGL(gzfile_part_link_kernel, g, dim3(256), 0, c->stream, P, part->inside, part->final_in);
+    else
+      hipLaunchKernelGGL(gzfile_link_kernel, g, dim3(256), 0, c->stream, P);
+  };
+  auto finish = [&](dim3 g) {
+    if (part)
+      hipLaunchKernelGGL(gzfile_part_finish_kernel, g, dim3(256), 0, c->stream, P, part->final_in);
+    else
+      hipLaunchKernelGGL(gzfile_finish_kernel, g, dim3(256), 0, c->stream, P);
+  };
+  auto marks = [&](uint32_t node_blocks) {
+    if (ser) hipLaunchKernelGGL(gzfile_serial_marks_kernel, dim3(node_blocks), dim3(256), 0, c->stream, P, ser->S);
+  };
+  auto behind = [&](uint32_t node_blocks) {
+    hipLaunchKernelGGL(gzfile_members_kernel, dim3(1), dim3(1024), 0, c->stream, P);
+    one_probe_launch(c, 1, P.O, 1u);
+    if (part)
+      hipLaunchKernelGGL(gzfile_part_rel_kernel, dim3(node_blocks), dim3(256), 0, c->stream, P, part->hist);
+    else
+      hipLaunchKernelGGL(gzfile_rel_kernel, dim3(node_blocks), dim3(256), 0, c->stream, P);
+    if (ser) hipLaunchKernelGGL(gzfile_serial_list_kernel, dim3(1), dim3(1024), 0, c->stream, P, ser->S);
+  };
+  return unit_chain(c, P.O, link, finish, marks, behind, H, G, P.gh, [&]() -> int {
+    if (ser) HIP_TRY(c, hipMemcpyAsync(&ser->SH, ser->S.head, sizeof ser->SH, hipMemcpyDeviceToHost, c->stream));
+    if (back.mout) {
+      back.mout->assign((size_t)nb + 2, 0);
+      HIP_TRY(c, hipMemcpyAsync(back.mout->data(), P.member_out, ((size_t)nb + 2) * 8, hipMemcpyDeviceToHost, c->stream));
+    }
+    if (back.index) {  // 28 bytes per node
+      back.index->assign(3 * (n + 1), 0);
+      back.u_final->assign(n + 1, 0);
+      uint64_t *x = back.index->data();
+      HIP_TRY(c, hipMemcpyAsync(x, C.member_off, (n + 1) * 8, hipMemcpyDeviceToHost, c->stream));
+      HIP_TRY(c, hipMemcpyAsync(x + (n + 1), C.out_off, (n + 1) * 8, hipMemcpyDeviceToHost, c->stream));
+      HIP_TRY(c, hipMemcpyAsync(x + 2 * (n + 1), P.u_start, (n + 1) * 8, hipMemcpyDeviceToHost, c->stream));
+      if (n) HIP_TRY(c, hipMemcpyAsync(back.u_final->data(), P.u_final, n * 4, hipMemcpyDeviceToHost, c->stream));
+    }
+    return FLATE_HIP_OK;
+  });
+}
+
+// The words the two count passes leave and List B's parameters, for a discovery over all of d_in[0, in_len) (P.O.C
+// holds it): c->d_gzfile_tiles, sized before the candidates are counted; `more` takes what "gzfile_serial_max" adds,
+// a_tiles is List A's tile count at most.
+template <class More>
+int gzfile_tiles_carve(flate_hip_ctx *c, GzFileParams &P, OneParams &PA, GzipParams &PB, OneHead *&head_a, size_t a_tiles,
+                       More more) {
+  ChainParams &C = P.O.C;
   BgzfHead *head_b;
-  rc = carve(c, c->d_gzfile_tiles, [&](Carve &k) {
+  const int rc = carve(c, c->d_gzfile_tiles, [&](Carve &k) {
     k.take(P.O.head, 1);
     k.take(P.gh, 1);
     k.take(P.O.one, 1);
     k.take(head_a, 1);
     k.take(head_b, 1);
-    k.take(PA.C.tile_cnt, (size_t)n_tiles + 1);
-    k.take(PB.C.tile_cnt, (size_t)n_tiles + 1);
+    more(k);
+    k.take(PA.C.tile_cnt, a_tiles + 1);
+    k.take(PB.C.tile_cnt, (size_t)C.n_tiles + 1);
   });
   if (rc) return rc;
-  C.in = PA.C.in = PB.C.in = d_in;
-  C.in_len = PA.C.in_len = PB.C.in_len = in_len;
-  C.n_tiles = PA.C.n_tiles = PB.C.n_tiles = n_tiles;
   C.head = &P.O.head->h;
-  P.O.unit_max = PA.unit_max = c->one_unit_max;
-  P.O.stored_units = PA.stored_units = c->one_stored_units;
-  PA.C.head = &head_a->h;
-  PA.head = head_a;
-  PA.one = P.O.one;
+  PB.C.in = C.in;
+  PB.C.in_len = C.in_len;
+  PB.C.n_tiles = C.n_tiles;
   PB.C.head = head_b;
   PB.member_max = ~0ull;  // a member's range is never clipped
-  hipLaunchKernelGGL(gzfile_init_kernel, dim3(1), dim3(64), 0, c->stream, P.O.one, in_len);
-  one_find_launch(c, true, n_tiles, PA);
-  hipLaunchKernelGGL(chain_scan_kernel, dim3(1), dim3(1024), 0, c->stream, PA.C);
-  hipLaunchKernelGGL(gzip_count_kernel, dim3(n_tiles), dim3(256), 0, c->stream, PB);
+  return FLATE_HIP_OK;
+}
+
+// The discovery over the file d_in[0, in_len) (DEVICE memory, in_len != 0) on the ctx's stream, or -- part != null --
+// over one PART of it: the two count passes and their scans, ONE read-back of the two candidate counts, then
+// gzfile_chain.  The index stays on the device (P).  Counted in no profiling stage.  A part's root may be a header that
+// cannot be judged yet: *root_bad is the count pass's verdict (HA.bad), and anything but 0 ends the discovery there.
+int gzfile_discover(flate_hip_ctx *c, const uint8_t *d_in, uint64_t in_len, const GzPartIn *part, OneHead &H, GzFileHead &G,
+                    GzFileParams &P, uint32_t *root_bad, const GzFileBack &back) {
+  int rc;
+  P = GzFileParams{};
+  OneParams PA{};
+  GzipParams PB{};
+  ChainParams &C = P.O.C;
+  C.in = d_in;
+  C.in_len = in_len;
+  if ((rc = tiles_for(d_in, 0, in_len, &C.n_tiles))) return rc;
+  OneHead *head_a;
+  if ((rc = gzfile_tiles_carve(c, P, PA, PB, head_a, C.n_tiles, [](Carve &) {}))) return rc;
+  P.O.unit_max = part ? part->unit_max : c->one_unit_max;
+  P.O.stored_units = part ? part->stored_units : c->one_stored_units;
+  find_params(PA, P.O, head_a);
+  if (part)
+    hipLaunchKernelGGL(gzfile_part_init_kernel, dim3(1), dim3(64), 0, c->stream, P.O.one, d_in, in_len, part->inside, part->b0);
+  else
+    hipLaunchKernelGGL(gzfile_init_kernel, dim3(1), dim3(64), 0, c->stream, P.O.one, in_len);
+  find_count(c, PA, part != nullptr);
+  hipLaunchKernelGGL(gzip_count_kernel, dim3(C.n_tiles), dim3(256), 0, c->stream, PB);
   hipLaunchKernelGGL(chain_scan_kernel, dim3(1), dim3(1024), 0, c->stream, PB.C);
-  HIP_TRY(c, hipGetLastError());
   OneHead HA{};
   BgzfHead HB{};
-  HIP_TRY(c, hipMemcpyAsync(&HA, head_a, sizeof HA, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(&HB, head_b, sizeof HB, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  const uint32_t na = HA.h.n_cand, nb = HB.n_cand;
-  if ((uint64_t)na + nb > 0x7ffffff0ull) return FLATE_HIP_E_TOO_LARGE;  // (the counts saturate at 2^32 - 1)
-  const uint32_t cap = na + nb;
-  if ((rc = chain_size(C, cap)) || (rc = chain_size(PA.C, na)) || (rc = chain_size(PB.C, nb))) return rc;
-  P.n_a = na;
-  P.n_b = nb;
-
-  const size_t n = cap;
-  uint64_t *hdr_off;
-  rc = carve(c, c->d_gzfile, [&](Carve &k) {
-    k.take(C.cand_off, n);
-    k.take(hdr_off, (size_t)nb + 1);
-    k.take(PB.cand_end, nb);
-    k.take(P.O.probe, n);
-    k.take(C.jump[0], n + 2);
-    k.take(C.jump[1], n + 2);
-    k.take(C.path, C.path_len);
-    k.take(P.O.usize, n);
-    k.take(C.member_off, n + 1);
-    k.take(C.out_off, n + 1);
-    k.take(P.u_start, n + 1);
-    k.take(P.u_final, n);
-    k.take(P.u_member, n + 1);
-    k.take(P.rel_off, n + 1);
-    k.take(P.member_off, (size_t)nb + 2);
-    k.take(P.member_unit, (size_t)nb + 2);
-    k.take(P.member_out, (size_t)nb + 2);
-  });
-  if (rc) return rc;
-  PA.C.cand_off = C.cand_off;
-  PB.C.cand_off = hdr_off;
-  P.hdr_off = hdr_off;
-  one_find_launch(c, false, n_tiles, PA);
-  if (nb) {
-    hipLaunchKernelGGL(gzip_fill_kernel, dim3(n_tiles), dim3(256), 0, c->stream, PB);
-    hipLaunchKernelGGL(gzfile_bits_kernel, dim3((nb + 255) / 256), dim3(256), 0, c->stream, P);
-  }
-  if (cap) one_probe_launch(c, cap, P.O, 0u);
-  const uint32_t node_blocks = (uint32_t)(((uint64_t)cap + 2 + 255) / 256);
-  hipLaunchKernelGGL(gzfile_link_kernel, dim3(node_blocks), dim3(256), 0, c->stream, P);
-  for (uint32_t j = 0; (1u << j) < C.path_len; ++j)
-    hipLaunchKernelGGL(chain_round_kernel, dim3(node_blocks), dim3(256), 0, c->stream, C, j);
-  hipLaunchKernelGGL(gzfile_finish_kernel, dim3((C.path_len + 255) / 256), dim3(256), 0, c->stream, P);
-  hipLaunchKernelGGL(one_out_scan_kernel, dim3(1), dim3(1024), 0, c->stream, P.O);
-  hipLaunchKernelGGL(gzfile_members_kernel, dim3(1), dim3(1024), 0, c->stream, P);
-  one_probe_launch(c, 1, P.O, 1u);
-  hipLaunchKernelGGL(gzfile_rel_kernel, dim3(node_blocks), dim3(256), 0, c->stream, P);
-  HIP_TRY(c, hipGetLastError());
-  HIP_TRY(c, hipMemcpyAsync(&H, P.O.head, sizeof H, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(&G, P.gh, sizeof G, hipMemcpyDeviceToHost, c->stream));
-  if (mout) {
-    mout->assign((size_t)nb + 2, 0);
-    HIP_TRY(c, hipMemcpyAsync(mout->data(), P.member_out, ((size_t)nb + 2) * 8, hipMemcpyDeviceToHost, c->stream));
-  }
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  if (G.n_members > nb || H.h.n_members > cap) return FLATE_HIP_E_INTERNAL;
-  return FLATE_HIP_OK;
+  if ((rc = find_counts_back(c, head_a, HA, PB.C.head, &HB))) return rc;
+  if (part && (*root_bad = HA.bad)) return FLATE_HIP_OK;
+  if ((rc = gzfile_chain(c, P, PA, PB, HA.h.n_cand, HB.n_cand, part, nullptr, H, G, back))) return rc;
+  return !part && G.n_members > P.n_b ? FLATE_HIP_E_INTERNAL : FLATE_HIP_OK;
 }
 
 // The same discovery with the option "gzfile_serial_max" (S >= 1; gzfile_serial_rule.h, gzfile_serial_kernels.hip).
@@ -1440,31 +1404,20 @@ int gzfile_discover_serial(flate_hip_ctx *c, const uint8_t *d_in, uint64_t in_le
   OneParams PA{};
   GzipParams PB{};
   ChainParams &C = P.O.C;
-  uint32_t n_tiles = 0;
-  if ((rc = tiles_for(d_in, 0, in_len, &n_tiles))) return rc;
+  C.in = d_in;
+  C.in_len = in_len;
+  if ((rc = tiles_for(d_in, 0, in_len, &C.n_tiles))) return rc;
+  const uint32_t n_tiles = C.n_tiles;
   OneHead *head_a;
-  BgzfHead *head_b;
   FrameOne *one_a;
-  rc = carve(c, c->d_gzfile_tiles, [&](Carve &k) {
-    k.take(P.O.head, 1);
-    k.take(P.gh, 1);
-    k.take(P.O.one, 1);
-    k.take(head_a, 1);
-    k.take(head_b, 1);
-    k.take(one_a, 1);
+  rc = gzfile_tiles_carve(c, P, PA, PB, head_a, (size_t)n_tiles + 1, [&](Carve &k) {  // (a suffix at another alignment:
+    k.take(one_a, 1);                                                                  // at most one tile more)
     k.take(S.head, 1);
-    k.take(PA.C.tile_cnt, (size_t)n_tiles + 2);  // (a suffix at another alignment: at most one tile more)
-    k.take(PB.C.tile_cnt, (size_t)n_tiles + 1);
   });
   if (rc) return rc;
-  C.in = PB.C.in = d_in;
-  C.in_len = PB.C.in_len = in_len;
-  C.n_tiles = PB.C.n_tiles = n_tiles;
-  C.head = &P.O.head->h;
-  P.O.unit_max = PA.unit_max = c->one_unit_max;
-  P.O.stored_units = PA.stored_units = c->one_stored_units;
-  PB.C.head = head_b;
-  PB.member_max = ~0ull;  // a member's range is never clipped
+  BgzfHead *head_b = PB.C.head;
+  P.O.unit_max = c->one_unit_max;
+  P.O.stored_units = c->one_stored_units;
   hipLaunchKernelGGL(gzfile_init_kernel, dim3(1), dim3(64), 0, c->stream, P.O.one, in_len);
   hipLaunchKernelGGL(gzip_count_kernel, dim3(n_tiles), dim3(256), 0, c->stream, PB);
   hipLaunchKernelGGL(chain_scan_kernel, dim3(1), dim3(1024), 0, c->stream, PB.C);
@@ -1549,85 +1502,25 @@ int gzfile_discover_serial(flate_hip_ctx *c, const uint8_t *d_in, uint64_t in_le
   }
 
   // PHASE 2: FIND over the bytes from find_from on
-  uint32_t na = 0, n_tiles_a = 0;
+  uint32_t na = 0;
   if (find_from < in_len) {
-    const uint8_t *a_in = d_in + find_from;
-    const uint64_t a_len = in_len - find_from;
-    if ((rc = tiles_for(a_in, 0, a_len, &n_tiles_a))) return rc;
-    if (n_tiles_a > n_tiles + 1u) return FLATE_HIP_E_INTERNAL;
-    PA.C.in = a_in;
-    PA.C.in_len = a_len;
-    PA.C.n_tiles = n_tiles_a;
-    PA.C.head = &head_a->h;
-    PA.head = head_a;
+    find_params(PA, P.O, head_a);
+    PA.C.in = d_in + find_from;
+    PA.C.in_len = in_len - find_from;
     PA.one = one_a;
-    hipLaunchKernelGGL(gzfile_init_kernel, dim3(1), dim3(64), 0, c->stream, one_a, a_len);
-    one_find_launch(c, true, n_tiles_a, PA);
-    hipLaunchKernelGGL(chain_scan_kernel, dim3(1), dim3(1024), 0, c->stream, PA.C);
-    HIP_TRY(c, hipGetLastError());
+    if ((rc = tiles_for(PA.C.in, 0, PA.C.in_len, &PA.C.n_tiles))) return rc;
+    if (PA.C.n_tiles > n_tiles + 1u) return FLATE_HIP_E_INTERNAL;
+    hipLaunchKernelGGL(gzfile_init_kernel, dim3(1), dim3(64), 0, c->stream, one_a, PA.C.in_len);
+    find_count(c, PA, false);
     OneHead HA{};
-    HIP_TRY(c, hipMemcpyAsync(&HA, head_a, sizeof HA, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if ((rc = find_counts_back(c, head_a, HA))) return rc;
     na = HA.h.n_cand;
   }
-  if ((uint64_t)na + nb > 0x7ffffff0ull) return FLATE_HIP_E_TOO_LARGE;
-  const uint32_t cap = na + nb;
-  if ((rc = chain_size(C, cap)) || (rc = chain_size(PA.C, na))) return rc;
-  P.n_a = S.n_a = na;
-
-  const size_t n = cap;
-  rc = carve(c, c->d_gzfile, [&](Carve &k) {
-    k.take(C.cand_off, n);
-    k.take(P.O.probe, n);
-    k.take(C.jump[0], n + 2);
-    k.take(C.jump[1], n + 2);
-    k.take(C.path, C.path_len);
-    k.take(P.O.usize, n);
-    k.take(C.member_off, n + 1);
-    k.take(C.out_off, n + 1);
-    k.take(P.u_start, n + 1);
-    k.take(P.u_final, n);
-    k.take(P.u_member, n + 1);
-    k.take(P.rel_off, n + 1);
-    k.take(P.member_off, (size_t)nb + 2);
-    k.take(P.member_unit, (size_t)nb + 2);
-    k.take(P.member_out, (size_t)nb + 2);
-  });
-  if (rc) return rc;
-  rc = carve(c, c->d_gzfile_serial_units, [&](Carve &k) {
-    k.take(S.u_whole, n + 1);
-    k.take(S.u_end, n + 1);
-  });
-  if (rc) return rc;
-  PA.C.cand_off = C.cand_off;
-  if (find_from < in_len) {
-    one_find_launch(c, false, n_tiles_a, PA);
-    if (na) hipLaunchKernelGGL(gzfile_serial_base_kernel, dim3((na + 255u) / 256u), dim3(256), 0, c->stream, C.cand_off, na, 8u * find_from);
-  }
-  if (nb) hipLaunchKernelGGL(gzfile_serial_bits_kernel, dim3((nb + 255) / 256), dim3(256), 0, c->stream, P, S);
-  if (cap) one_probe_launch(c, cap, P.O, 0u);
-  if (nb) hipLaunchKernelGGL(gzfile_serial_keep_kernel, dim3((nb + 255) / 256), dim3(256), 0, c->stream, P, S);
-  const uint32_t node_blocks = (uint32_t)(((uint64_t)cap + 2 + 255) / 256);
-  hipLaunchKernelGGL(gzfile_link_kernel, dim3(node_blocks), dim3(256), 0, c->stream, P);
-  for (uint32_t j = 0; (1u << j) < C.path_len; ++j)
-    hipLaunchKernelGGL(chain_round_kernel, dim3(node_blocks), dim3(256), 0, c->stream, C, j);
-  hipLaunchKernelGGL(gzfile_finish_kernel, dim3((C.path_len + 255) / 256), dim3(256), 0, c->stream, P);
-  hipLaunchKernelGGL(gzfile_serial_marks_kernel, dim3(node_blocks), dim3(256), 0, c->stream, P, S);
-  hipLaunchKernelGGL(one_out_scan_kernel, dim3(1), dim3(1024), 0, c->stream, P.O);
-  hipLaunchKernelGGL(gzfile_members_kernel, dim3(1), dim3(1024), 0, c->stream, P);
-  one_probe_launch(c, 1, P.O, 1u);
-  hipLaunchKernelGGL(gzfile_rel_kernel, dim3(node_blocks), dim3(256), 0, c->stream, P);
-  hipLaunchKernelGGL(gzfile_serial_list_kernel, dim3(1), dim3(1024), 0, c->stream, P, S);
-  HIP_TRY(c, hipGetLastError());
-  HIP_TRY(c, hipMemcpyAsync(&H, P.O.head, sizeof H, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(&G, P.gh, sizeof G, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(&SH, S.head, sizeof SH, hipMemcpyDeviceToHost, c->stream));
-  if (mout) {
-    mout->assign((size_t)nb + 2, 0);
-    HIP_TRY(c, hipMemcpyAsync(mout->data(), P.member_out, ((size_t)nb + 2) * 8, hipMemcpyDeviceToHost, c->stream));
-  }
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  if (G.n_members > nb || H.h.n_members > cap || SH.n_whole > nb || SH.n_whole > G.n_members || SH.find_from != find_from)
+  const GzSerialIn ser{S, SH, find_from};
+  GzFileBack back;
+  back.mout = mout;
+  if ((rc = gzfile_chain(c, P, PA, PB, na, nb, nullptr, &ser, H, G, back))) return rc;
+  if (G.n_members > nb || SH.n_whole > nb || SH.n_whole > G.n_members || SH.find_from != find_from)
     return FLATE_HIP_E_INTERNAL;
   return FLATE_HIP_OK;
 }
@@ -1641,7 +1534,9 @@ int gzfile_discover_routed(flate_hip_ctx *c, const uint8_t *d_in, uint64_t in_le
   if (!c->gzfile_serial_max) {
     S = GzSerialParams{};
     SH = GzSerialHead{};
-    if ((rc = gzfile_discover(c, d_in, in_len, H, G, P, mout))) return rc;
+    GzFileBack back;
+    back.mout = mout;
+    if ((rc = gzfile_discover(c, d_in, in_len, nullptr, H, G, P, nullptr, back))) return rc;
   } else if ((rc = gzfile_discover_serial(c, d_in, in_len, H, G, P, S, SH, mout))) {
     return rc;
   }
@@ -1763,11 +1658,8 @@ int flate_hip_gzfile_read(flate_hip_ctx *c, const uint8_t *in, uint64_t in_len, 
     const uint64_t total = H.prefix_bytes + (H.fail_unit ? H.fail_out : 0ull);
     *out_len = total;
     if (total > out_cap) return FLATE_HIP_E_OUT_TOO_SMALL;  // (nothing is decoded; out == NULL: the size query)
-    uint8_t *d_out = out;
-    if (!dev) {
-      if ((rc = ensure(c, c->d_out, total + 16))) return rc;
-      d_out = (uint8_t *)c->d_out.p;
-    }
+    uint8_t *d_out;
+    if ((rc = unit_out_buffer(c, out, dev, total, d_out))) return rc;
     const uint32_t n_mem = H.h.rc == 0 ? G.n_members : 0u;  // the members whose trailers are judged
     // the runs of units the rounds go over: all of them, or (option "gzfile_serial_max") what lies between the whole
     // members -- a run starts with a member's first unit, a seed, and ends where a member does
@@ -1845,11 +1737,7 @@ int flate_hip_gzfile_read(flate_hip_ctx *c, const uint8_t *in, uint64_t in_len, 
     };
     // DECODE: the round's units as pieces with dictionaries and their own ends, through the lane-per-stream decoder
     auto decode = [&](uint32_t, uint32_t count) {
-      const int r = unit_decode(c, unit_decode_params(D, d_in, H.raw_len, GD.p_bit_off, GD.p_bit_end, false, count, d_out,
-                                                      D.p_out_off, dec));
-      if (r) return r;
-      hipLaunchKernelGGL(one_check_kernel, dim3((count + 1u + 255u) / 256u), dim3(256), 0, c->stream, D);
-      return FLATE_HIP_OK;
+      return unit_decode_members(c, D, d_in, H.raw_len, GD.p_bit_off, GD.p_bit_end, count, d_out, dec);
     };
     // TAIL with the member-relative offsets: a unit's history is what its own member has produced in front of it
     for (const auto &run : runs) {
@@ -1873,12 +1761,7 @@ int flate_hip_gzfile_read(flate_hip_ctx *c, const uint8_t *in, uint64_t in_len, 
     HIP_TRY(c, hipMemcpyAsync(&V, GD.v, sizeof V, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     if (ctl) ctl_finish(c);
-    if (V.out_len > total) return FLATE_HIP_E_INTERNAL;
-    *out_len = V.out_len;
-    if (!dev && V.out_len) {  // the result comes down once
-      HIP_TRY(c, hipMemcpyAsync(out, d_out, V.out_len, hipMemcpyDeviceToHost, c->stream));
-      HIP_TRY(c, hipStreamSynchronize(c->stream));
-    }
+    if ((rc = unit_deliver(c, out, d_out, dev, V.out_len, total, out_len))) return rc;
     if (c->profiling && (rc = collect_timing(c, used))) return rc;
     if (n_members) *n_members = V.n_members;
     if (n_units) *n_units = V.n_units;
@@ -1948,7 +1831,7 @@ int flate_hip_gzfile_seek_index(flate_hip_ctx *c, const uint8_t *in, uint64_t in
     OneHead H{};
     GzFileHead G{};
     GzFileParams P{};
-    if ((rc = gzfile_discover(c, d_in, in_len, H, G, P, nullptr))) return rc;
+    if ((rc = gzfile_discover(c, d_in, in_len, nullptr, H, G, P, nullptr, GzFileBack{}))) return rc;
     const uint32_t n = H.h.n_members, m = G.n_members;
     *n_units = n;
     *n_members = m;
@@ -2267,13 +2150,8 @@ int flate_hip_gzfile_ranges(flate_hip_ctx *c, const uint8_t *in, uint64_t in_len
 
 // Between two calls the file's state rests in the handle: on the device the 32 KiB window and the running CRC-32 of
 // the member in progress (GzPartState), on the host the rule's words (GzPartsState).  The unit rule and "one_unit_max"
-// are the ctx's at open, whatever it says later; "gzfile_serial_max" is not read.
-struct flate_hip_gzfile_reader {
-  flate_hip_ctx *ctx = nullptr;
-  uint32_t flags = 0;
-  uint64_t unit_max = 0;
-  uint32_t stored_units = 0;
-  DevBuf state;
+// are the ctx's at open, whatever it says later (UnitReader); "gzfile_serial_max" is not read.
+struct flate_hip_gzfile_reader : UnitReader {
   GzPartsState s = gzfile_parts_fresh();
 };
 
@@ -2288,126 +2166,6 @@ int gzfile_reader_fresh(flate_hip_gzfile_reader *r) {
   return FLATE_HIP_OK;
 }
 
-// The discovery over the PART d_in[0, in_len) (DEVICE memory, in_len != 0): gzfile_discover's passes with the part's
-// root and hop -- gzfile_part_init_kernel, FIND in its PARTS build (candidate 0 at the carried bit), the handle's unit
-// rule, gzfile_part_link_kernel / _finish_kernel, and gzfile_part_rel_kernel behind the member scan.  The same two
-// read-backs: the candidate counts (with the root's header verdict in HA.bad: anything but 0 ends the discovery
-// there), then the result words H / G with the INDEX -- unit_bit, out_off and u_start (cap + 1 entries each) and
-// u_final (cap) in one vector of 64-bit words, one array behind the other.
-struct GzPartIn {
-  uint64_t unit_max;
-  uint32_t stored_units;
-  uint32_t inside, b0, final_in;
-  uint64_t hist;
-};
-int gzfile_part_discover(flate_hip_ctx *c, const uint8_t *d_in, uint64_t in_len, const GzPartIn &part, OneHead &H,
-                         GzFileHead &G, GzFileParams &P, uint32_t &root_bad, std::vector<uint64_t> &index,
-                         std::vector<uint32_t> &u_final) {
-  int rc;
-  P = GzFileParams{};
-  OneParams PA{};
-  GzipParams PB{};
-  ChainParams &C = P.O.C;
-  uint32_t n_tiles = 0;
-  if ((rc = tiles_for(d_in, 0, in_len, &n_tiles))) return rc;
-  OneHead *head_a;
-  BgzfHead *head_b;
-  rc = carve(c, c->d_gzfile_tiles, [&](Carve &k) {
-    k.take(P.O.head, 1);
-    k.take(P.gh, 1);
-    k.take(P.O.one, 1);
-    k.take(head_a, 1);
-    k.take(head_b, 1);
-    k.take(PA.C.tile_cnt, (size_t)n_tiles + 1);
-    k.take(PB.C.tile_cnt, (size_t)n_tiles + 1);
-  });
-  if (rc) return rc;
-  C.in = PA.C.in = PB.C.in = d_in;
-  C.in_len = PA.C.in_len = PB.C.in_len = in_len;
-  C.n_tiles = PA.C.n_tiles = PB.C.n_tiles = n_tiles;
-  C.head = &P.O.head->h;
-  P.O.unit_max = PA.unit_max = part.unit_max;
-  P.O.stored_units = PA.stored_units = part.stored_units;
-  PA.C.head = &head_a->h;
-  PA.head = head_a;
-  PA.one = P.O.one;
-  PB.C.head = head_b;
-  PB.member_max = ~0ull;  // a member's range is never clipped
-  hipLaunchKernelGGL(gzfile_part_init_kernel, dim3(1), dim3(64), 0, c->stream, P.O.one, d_in, in_len, part.inside, part.b0);
-  one_find_launch(c, true, n_tiles, PA, true);
-  hipLaunchKernelGGL(chain_scan_kernel, dim3(1), dim3(1024), 0, c->stream, PA.C);
-  hipLaunchKernelGGL(gzip_count_kernel, dim3(n_tiles), dim3(256), 0, c->stream, PB);
-  hipLaunchKernelGGL(chain_scan_kernel, dim3(1), dim3(1024), 0, c->stream, PB.C);
-  HIP_TRY(c, hipGetLastError());
-  OneHead HA{};
-  BgzfHead HB{};
-  HIP_TRY(c, hipMemcpyAsync(&HA, head_a, sizeof HA, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(&HB, head_b, sizeof HB, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  root_bad = HA.bad;
-  if (root_bad) return FLATE_HIP_OK;
-  const uint32_t na = HA.h.n_cand, nb = HB.n_cand;
-  if ((uint64_t)na + nb > 0x7ffffff0ull) return FLATE_HIP_E_TOO_LARGE;  // (the counts saturate at 2^32 - 1)
-  const uint32_t cap = na + nb;
-  if ((rc = chain_size(C, cap)) || (rc = chain_size(PA.C, na)) || (rc = chain_size(PB.C, nb))) return rc;
-  P.n_a = na;
-  P.n_b = nb;
-
-  const size_t n = cap;
-  uint64_t *hdr_off;
-  rc = carve(c, c->d_gzfile, [&](Carve &k) {
-    k.take(C.cand_off, n);
-    k.take(hdr_off, (size_t)nb + 1);
-    k.take(PB.cand_end, nb);
-    k.take(P.O.probe, n);
-    k.take(C.jump[0], n + 2);
-    k.take(C.jump[1], n + 2);
-    k.take(C.path, C.path_len);
-    k.take(P.O.usize, n);
-    k.take(C.member_off, n + 1);
-    k.take(C.out_off, n + 1);
-    k.take(P.u_start, n + 1);
-    k.take(P.u_final, n);
-    k.take(P.u_member, n + 1);
-    k.take(P.rel_off, n + 1);
-    k.take(P.member_off, (size_t)nb + 2);
-    k.take(P.member_unit, (size_t)nb + 2);
-    k.take(P.member_out, (size_t)nb + 2);
-  });
-  if (rc) return rc;
-  PA.C.cand_off = C.cand_off;
-  PB.C.cand_off = hdr_off;
-  P.hdr_off = hdr_off;
-  one_find_launch(c, false, n_tiles, PA, true);
-  if (nb) {
-    hipLaunchKernelGGL(gzip_fill_kernel, dim3(n_tiles), dim3(256), 0, c->stream, PB);
-    hipLaunchKernelGGL(gzfile_bits_kernel, dim3((nb + 255) / 256), dim3(256), 0, c->stream, P);
-  }
-  if (cap) one_probe_launch(c, cap, P.O, 0u);
-  const uint32_t node_blocks = (uint32_t)(((uint64_t)cap + 2 + 255) / 256);
-  hipLaunchKernelGGL(gzfile_part_link_kernel, dim3(node_blocks), dim3(256), 0, c->stream, P, part.inside, part.final_in);
-  for (uint32_t j = 0; (1u << j) < C.path_len; ++j)
-    hipLaunchKernelGGL(chain_round_kernel, dim3(node_blocks), dim3(256), 0, c->stream, C, j);
-  hipLaunchKernelGGL(gzfile_part_finish_kernel, dim3((C.path_len + 255) / 256), dim3(256), 0, c->stream, P, part.final_in);
-  hipLaunchKernelGGL(one_out_scan_kernel, dim3(1), dim3(1024), 0, c->stream, P.O);
-  hipLaunchKernelGGL(gzfile_members_kernel, dim3(1), dim3(1024), 0, c->stream, P);
-  one_probe_launch(c, 1, P.O, 1u);
-  hipLaunchKernelGGL(gzfile_part_rel_kernel, dim3(node_blocks), dim3(256), 0, c->stream, P, part.hist);
-  HIP_TRY(c, hipGetLastError());
-  // ONE read-back behind the counts: the result words, then 28 bytes per node
-  index.assign(3 * (n + 1), 0);
-  u_final.assign(n + 1, 0);
-  HIP_TRY(c, hipMemcpyAsync(&H, P.O.head, sizeof H, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(&G, P.gh, sizeof G, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(index.data(), C.member_off, (n + 1) * 8, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(index.data() + (n + 1), C.out_off, (n + 1) * 8, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(index.data() + 2 * (n + 1), P.u_start, (n + 1) * 8, hipMemcpyDeviceToHost, c->stream));
-  if (n) HIP_TRY(c, hipMemcpyAsync(u_final.data(), P.u_final, n * 4, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  if (H.h.n_members > cap) return FLATE_HIP_E_INTERNAL;
-  return FLATE_HIP_OK;
-}
-
 }  // namespace
 
 extern "C" {
@@ -2415,37 +2173,12 @@ extern "C" {
 int flate_hip_gzfile_reader_open(flate_hip_ctx *c, uint32_t flags, flate_hip_gzfile_reader **out) {
   // every check before any HIP call
   if (gzfile_reader_open_args(c, flags, out)) return FLATE_HIP_E_INVALID;
-  *out = nullptr;
-  c->hip_err.clear();
-  HIP_TRY(c, hipSetDevice(c->device));
-  flate_hip_gzfile_reader *r = new flate_hip_gzfile_reader();
-  r->ctx = c;
-  r->flags = flags;
-  r->unit_max = c->one_unit_max;
-  r->stored_units = c->one_stored_units;
-  int rc = ensure(c, r->state, sizeof(GzPartState) + 64);
-  if (rc == FLATE_HIP_OK) rc = gzfile_reader_fresh(r);
-  if (rc != FLATE_HIP_OK) {
-    delete r;
-    return rc;
-  }
-  *out = r;
-  return FLATE_HIP_OK;
+  return unit_reader_open(c, flags, sizeof(GzPartState), gzfile_reader_fresh, out);
 }
 
-int flate_hip_gzfile_reader_reset(flate_hip_gzfile_reader *r) {
-  if (!r) return FLATE_HIP_E_INVALID;
-  flate_hip_ctx *c = r->ctx;
-  c->hip_err.clear();
-  HIP_TRY(c, hipSetDevice(c->device));
-  return gzfile_reader_fresh(r);
-}
+int flate_hip_gzfile_reader_reset(flate_hip_gzfile_reader *r) { return unit_reader_reset(r, gzfile_reader_fresh); }
 
-void flate_hip_gzfile_reader_free(flate_hip_gzfile_reader *r) {
-  if (!r) return;
-  (void)hipSetDevice(r->ctx->device);
-  delete r;
-}
+void flate_hip_gzfile_reader_free(flate_hip_gzfile_reader *r) { unit_reader_free(r); }
 
 // One call: flate_hip_gzfile_read on the part in[0, in_len), its chain rooted where the last call stopped -- discovery
 // (the index comes back with the result words: the host picks the units that fit and finds the members among them,
@@ -2504,7 +2237,9 @@ int flate_hip_gzfile_reader_read(flate_hip_gzfile_reader *r, const uint8_t *in, 
     uint32_t root_bad = 0;
     std::vector<uint64_t> index;
     std::vector<uint32_t> u_final;
-    if ((rc = gzfile_part_discover(c, d_in, in_len, part, H, G, P, root_bad, index, u_final))) return rc;
+    GzFileBack back;
+    back.index = &index, back.u_final = &u_final;
+    if ((rc = gzfile_discover(c, d_in, in_len, &part, H, G, P, &root_bad, back))) return rc;
     if (root_bad == kPartsHdrBad || (root_bad && fin)) return fail_here(FLATE_HIP_E_CORRUPT, true);
     if (root_bad) {  // the header is refused only because the part ends here: more is needed
       if (in_len >= r->unit_max) return fail_here(FLATE_HIP_E_TOO_LARGE, true);
@@ -2538,11 +2273,8 @@ int flate_hip_gzfile_reader_read(flate_hip_gzfile_reader *r, const uint8_t *in, 
 
     const uint32_t n_dec = plan.n_del + plan.with_fail, n_segs = (uint32_t)call.segs.size();
     const uint64_t total = plan.total;
-    uint8_t *d_out = out;
-    if (!dev) {
-      if ((rc = ensure(c, c->d_out, total + 16))) return rc;
-      d_out = (uint8_t *)c->d_out.p;
-    }
+    uint8_t *d_out;
+    if ((rc = unit_out_buffer(c, out, dev, total, d_out))) return rc;
     const uint32_t per_round = unit_per_round(c, n_dec);
     GzFileDecParams GD{};
     OneDecParams &D = GD.D;
@@ -2567,18 +2299,13 @@ int flate_hip_gzfile_reader_read(flate_hip_gzfile_reader *r, const uint8_t *in, 
     unit_verdict_params(D, total, dec, P.O.head, FLATE_HIP_WRAP_GZIP, in_len);
     GD.P = P;
     GD.n_good = plan.n_del;
-    // R[0] of the first round: the handle's window
-    HIP_TRY(c, hipMemcpyAsync(D.R, st->window, kWinEntries, hipMemcpyDeviceToDevice, c->stream));
+    if ((rc = unit_window_seed(c, D, st->window))) return rc;
     auto pieces = [&](uint32_t, uint32_t count) {
       hipLaunchKernelGGL(gzfile_part_pieces_kernel, dim3((count + 1u + 255u) / 256u), dim3(256), 0, c->stream, GD, hist);
       return FLATE_HIP_OK;
     };
     auto decode = [&](uint32_t, uint32_t count) {
-      const int e = unit_decode(c, unit_decode_params(D, d_in, H.raw_len, GD.p_bit_off, GD.p_bit_end, false, count, d_out,
-                                                      D.p_out_off, dec));
-      if (e) return e;
-      hipLaunchKernelGGL(one_check_kernel, dim3((count + 1u + 255u) / 256u), dim3(256), 0, c->stream, D);
-      return FLATE_HIP_OK;
+      return unit_decode_members(c, D, d_in, H.raw_len, GD.p_bit_off, GD.p_bit_end, count, d_out, dec);
     };
     bool used[FLATE_HIP_STAGE_COUNT] = {false, false, false, false};
     if (n_dec) {
@@ -2635,22 +2362,8 @@ int flate_hip_gzfile_reader_read(flate_hip_gzfile_reader *r, const uint8_t *in, 
         hipStreamSynchronize(c->stream) != hipSuccess)
       return dead(FLATE_HIP_E_HIP);
     ctl_finish(c);
-    if (V.out_len > total) return dead(FLATE_HIP_E_INTERNAL);
-    // THE CARRY, once the result words are good: the window behind the last unit, which the round driver leaves in
-    // R[count] of the last round (nothing has been queued behind the rounds that writes D.R)
-    if (n_dec && V.status == 0) {
-      const uint32_t last_count = n_dec - ((n_dec - 1u) / per_round) * per_round;
-      if (hipMemcpyAsync(st->window, D.R + (size_t)last_count * kWinEntries, kWinEntries, hipMemcpyDeviceToDevice,
-                         c->stream) != hipSuccess)
-        return dead(FLATE_HIP_E_HIP);
-    }
-    *out_len = V.out_len;
-    if (!dev && V.out_len &&
-        (hipMemcpyAsync(out, d_out, V.out_len, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
-         hipStreamSynchronize(c->stream) != hipSuccess)) {
-      *out_len = 0;
-      return dead(FLATE_HIP_E_HIP);
-    }
+    if ((rc = unit_reader_deliver(c, D, st->window, n_dec, per_round, V.status == 0, out, d_out, dev, V.out_len, total, out_len)))
+      return dead(rc);
     if (c->profiling && (rc = collect_timing(c, used))) return dead(rc);
     if (n_members) *n_members = V.n_members;
     if (n_units) *n_units = V.n_units;
@@ -2674,8 +2387,9 @@ int flate_hip_gzfile_reader_read(flate_hip_gzfile_reader *r, const uint8_t *in, 
 }  // extern "C"
 
 // ---- the LONG entries of a ZIP archive through units (zip_units_kernels.hip, zip_units_rule.h) ----
-// gzfile_discover and flate_hip_gzfile_read's rounds with the format's own glue: the hull as the raw stream, B nodes
-// from the directory, the link that hops from entry to entry, pieces in ZIP's slots.  Read-backs: the candidate count;
+// The two-list discovery (unit_discovery.h) and flate_hip_gzfile_read's rounds with the format's own glue: the hull as
+// the raw stream, B nodes from the directory (no count pass, no chain of their own), the link that hops from entry to
+// entry, no tail probe, pieces in ZIP's slots.  Read-backs: the candidate count;
 // the head words with entry_unit; the rounds' first_bad / decode_bad (g).
 int flate_host::zip_units_decode(flate_hip_ctx *c, const uint8_t *d_in, uint64_t hull_lo, uint64_t hull_hi,
                                  const std::vector<ZuEntry> &L, const std::vector<ZuRange> &R, uint8_t *d_out,
@@ -2709,67 +2423,45 @@ int flate_host::zip_units_decode(flate_hip_ctx *c, const uint8_t *d_in, uint64_t
   P.L = dL, P.R = dR;
   HIP_TRY(c, hipMemcpyAsync(dL, L.data(), (size_t)nb * sizeof(ZuEntry), hipMemcpyHostToDevice, c->stream));
   HIP_TRY(c, hipMemcpyAsync(dR, R.data(), (size_t)nb * sizeof(ZuRange), hipMemcpyHostToDevice, c->stream));
-  C.in = PA.C.in = h_in;
-  C.in_len = PA.C.in_len = hull_len;
-  C.n_tiles = PA.C.n_tiles = n_tiles;
+  C.in = h_in;
+  C.in_len = hull_len;
+  C.n_tiles = n_tiles;
   C.head = &P.O.head->h;
-  P.O.unit_max = PA.unit_max = c->one_unit_max;
-  P.O.stored_units = PA.stored_units = c->one_stored_units;
-  PA.C.head = &head_a->h;
-  PA.head = head_a;
-  PA.one = P.O.one;
+  P.O.unit_max = c->one_unit_max;
+  P.O.stored_units = c->one_stored_units;
+  find_params(PA, P.O, head_a);
   hipLaunchKernelGGL(one_init_kernel, dim3(1), dim3(64), 0, c->stream, P.O.one, hull_len);  // the hull is the raw stream
-  one_find_launch(c, true, n_tiles, PA);
-  hipLaunchKernelGGL(chain_scan_kernel, dim3(1), dim3(1024), 0, c->stream, PA.C);
-  HIP_TRY(c, hipGetLastError());
+  find_count(c, PA, false);
   OneHead HA{};
-  HIP_TRY(c, hipMemcpyAsync(&HA, head_a, sizeof HA, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  if ((rc = find_counts_back(c, head_a, HA))) return rc;
   const uint32_t na = HA.h.n_cand;
-  if ((uint64_t)na + nb > 0x7ffffff0ull) return FLATE_HIP_E_TOO_LARGE;  // (the count saturates at 2^32 - 1)
-  const uint32_t cap = na + nb;
-  if ((rc = chain_size(C, cap)) || (rc = chain_size(PA.C, na))) return rc;
+  if ((rc = two_list_size(C, PA.C, nullptr, na, nb))) return rc;  // (List B is the directory's: no chain of its own)
   P.n_a = na;
   P.n_b = nb;
   *n_cand = na;
 
-  const size_t n = cap;
-  rc = carve(c, c->d_zip_units, [&](Carve &k) {
-    k.take(C.cand_off, n);
-    k.take(P.O.probe, n);
-    k.take(C.jump[0], n + 2);
-    k.take(C.jump[1], n + 2);
-    k.take(C.path, C.path_len);
-    k.take(P.O.usize, n);
-    k.take(C.member_off, n + 1);
-    k.take(C.out_off, n + 1);
-    k.take(P.u_start, n + 1);
-    k.take(P.u_final, n);
-    k.take(P.u_entry, n + 1);
-    k.take(P.rel_off, n + 1);
-  });
+  rc = unit_nodes_carve(c, c->d_zip_units, P, P.u_entry, C.cap, [](Carve &) {}, [](Carve &) {});
   if (rc) return rc;
   PA.C.cand_off = C.cand_off;
-  if (na) one_find_launch(c, false, n_tiles, PA);
+  if (na) one_find_launch(c, false, n_tiles, PA, false);
   hipLaunchKernelGGL(zip_units_bits_kernel, dim3((nb + 255) / 256), dim3(256), 0, c->stream, P);
-  one_probe_launch(c, cap, P.O, 0u);
-  const uint32_t node_blocks = (uint32_t)(((uint64_t)cap + 2 + 255) / 256);
-  hipLaunchKernelGGL(zip_units_link_kernel, dim3(node_blocks), dim3(256), 0, c->stream, P);
-  for (uint32_t j = 0; (1u << j) < C.path_len; ++j)
-    hipLaunchKernelGGL(chain_round_kernel, dim3(node_blocks), dim3(256), 0, c->stream, C, j);
-  hipLaunchKernelGGL(zip_units_finish_kernel, dim3((C.path_len + 255) / 256), dim3(256), 0, c->stream, P);
-  hipLaunchKernelGGL(one_out_scan_kernel, dim3(1), dim3(1024), 0, c->stream, P.O);
-  hipLaunchKernelGGL(zip_units_entries_kernel, dim3(1), dim3(1024), 0, c->stream, P);
-  hipLaunchKernelGGL(zip_units_rel_kernel, dim3(node_blocks), dim3(256), 0, c->stream, P);
-  HIP_TRY(c, hipGetLastError());
+  one_probe_launch(c, C.cap, P.O, 0u);
   OneHead H{};
   ZipUnitsHead Z{};
   std::vector<uint64_t> entry_unit((size_t)nb + 2, 0);
-  HIP_TRY(c, hipMemcpyAsync(&H, P.O.head, sizeof H, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(&Z, P.zh, sizeof Z, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(entry_unit.data(), P.entry_unit, ((size_t)nb + 2) * 8, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  if (H.h.n_members > cap || Z.n_complete > nb) return FLATE_HIP_E_INTERNAL;
+  rc = unit_chain(
+      c, P.O, [&](dim3 g) { hipLaunchKernelGGL(zip_units_link_kernel, g, dim3(256), 0, c->stream, P); },
+      [&](dim3 g) { hipLaunchKernelGGL(zip_units_finish_kernel, g, dim3(256), 0, c->stream, P); }, [](uint32_t) {},
+      [&](uint32_t node_blocks) {  // (ZIP's chain has no tail probe)
+        hipLaunchKernelGGL(zip_units_entries_kernel, dim3(1), dim3(1024), 0, c->stream, P);
+        hipLaunchKernelGGL(zip_units_rel_kernel, dim3(node_blocks), dim3(256), 0, c->stream, P);
+      },
+      H, Z, P.zh, [&]() -> int {
+        HIP_TRY(c, hipMemcpyAsync(entry_unit.data(), P.entry_unit, ((size_t)nb + 2) * 8, hipMemcpyDeviceToHost, c->stream));
+        return FLATE_HIP_OK;
+      });
+  if (rc) return rc;
+  if (Z.n_complete > nb) return FLATE_HIP_E_INTERNAL;
   // the entries the discovery finds GOOD, and their units: the only ones that are decoded
   const uint32_t g_disc = Z.n_complete < Z.first_unfit ? Z.n_complete : Z.first_unfit;
   G.P = P;

@@ -222,18 +222,29 @@ int tiles_for(const uint8_t *d_in, uint64_t lo, uint64_t len, uint32_t *n_tiles)
 // C.cap and C.path_len for arrays of cap candidates, or FLATE_HIP_E_TOO_LARGE
 int chain_size(flate::ChainParams &C, uint32_t cap);
 // The launches behind a format's fill (and whatever it runs over the candidates): its link kernel, the rounds of
-// pointer doubling, its finish and out-scan kernels; one check of all launches so far.
+// pointer doubling, its finish and out-scan kernels; one check of all launches so far.  link(grid) and finish(grid)
+// launch the format's kernels over the grids they are given (256 threads a workgroup) with whatever arguments those
+// take; mid(node_blocks) is the one place for a launch between finish and out-scan.
+template <typename Link, typename Finish, typename Mid, typename SP>
+int chain_tail_by(flate_hip_ctx *c, const flate::ChainParams &C, Link link, Finish finish, Mid mid, void (*out_scan)(SP),
+                  const SP &sp) {
+  const uint32_t node_blocks = (uint32_t)(((uint64_t)C.cap + 2 + 255) / 256);
+  link(dim3(node_blocks));
+  for (uint32_t j = 0; (1u << j) < C.path_len; ++j)
+    hipLaunchKernelGGL(flate::chain_round_kernel, dim3(node_blocks), dim3(256), 0, c->stream, C, j);
+  finish(dim3((C.path_len + 255) / 256));
+  mid(node_blocks);
+  hipLaunchKernelGGL(out_scan, dim3(1), dim3(1024), 0, c->stream, sp);
+  HIP_TRY(c, hipGetLastError());
+  return FLATE_HIP_OK;
+}
+// ... of a format whose link and finish kernels take one parameter block each and that has nothing for `mid`
 template <typename LP, typename FP>
 int chain_tail(flate_hip_ctx *c, const flate::ChainParams &C, void (*link)(LP), const LP &lp, void (*finish)(FP),
                void (*out_scan)(FP), const FP &fp) {
-  const uint32_t node_blocks = (uint32_t)(((uint64_t)C.cap + 2 + 255) / 256);
-  hipLaunchKernelGGL(link, dim3(node_blocks), dim3(256), 0, c->stream, lp);
-  for (uint32_t j = 0; (1u << j) < C.path_len; ++j)
-    hipLaunchKernelGGL(flate::chain_round_kernel, dim3(node_blocks), dim3(256), 0, c->stream, C, j);
-  hipLaunchKernelGGL(finish, dim3((C.path_len + 255) / 256), dim3(256), 0, c->stream, fp);
-  hipLaunchKernelGGL(out_scan, dim3(1), dim3(1024), 0, c->stream, fp);
-  HIP_TRY(c, hipGetLastError());
-  return FLATE_HIP_OK;
+  return chain_tail_by(
+      c, C, [&](dim3 g) { hipLaunchKernelGGL(link, g, dim3(256), 0, c->stream, lp); },
+      [&](dim3 g) { hipLaunchKernelGGL(finish, g, dim3(256), 0, c->stream, fp); }, [](uint32_t) {}, out_scan, fp);
 }
 
 // ---- small index arrays: host <-> device through pinned staging and a copy kernel (copy_ctl_kernel) ----

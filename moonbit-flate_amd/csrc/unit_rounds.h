@@ -8,6 +8,7 @@
 #pragma once
 
 #include "flate_ctx.h"
+#include "unit_discovery_rule.h"
 #include "window_compose.h"
 
 namespace flate_host {
@@ -175,6 +176,123 @@ inline flate::InfParams unit_decode_params(const flate::OneDecParams &D, const u
 // ... through the decoder the unit route names (of several rounds the inflate stage's time is the last one's)
 inline int unit_decode(flate_hip_ctx *c, const flate::InfParams &I) {
   return launch_decoders(c, flate::inflate_route_units(c->inflate, c->num_cus, I.n_streams), I, true);
+}
+
+// THE TWO DECODE BODIES of the calls that deliver output, as unit_rounds' `body`.  The CHAIN form (one stream, whole or
+// in parts): one_pieces_kernel writes the round's pieces, every piece ends where the next unit starts, and the round's
+// last one too when `closed` -- else it runs to BFINAL or to its failure; raw[0, raw_len) is the raw stream.
+inline int unit_decode_chain(flate_hip_ctx *c, const flate::OneDecParams &D, const uint8_t *raw, uint64_t raw_len, uint32_t u0,
+                             uint32_t count, bool closed, uint8_t *d_out, const UnitResults &dec) {
+  const uint32_t unit_blocks = (count + 1u + 255u) / 256u;
+  hipLaunchKernelGGL(flate::one_pieces_kernel, dim3(unit_blocks), dim3(256), 0, c->stream, D);
+  const int r = unit_decode(c, unit_decode_params(D, raw, raw_len, D.unit_bit + u0, nullptr, closed, count, d_out, D.p_out_off, dec));
+  if (r) return r;
+  hipLaunchKernelGGL(flate::one_check_kernel, dim3(unit_blocks), dim3(256), 0, c->stream, D);
+  return FLATE_HIP_OK;
+}
+// ... and the MEMBER form (a gzip file, whole or in parts): the call's `between` hook has written the pieces, each with
+// its own start and end (p_bit_off / p_bit_end)
+inline int unit_decode_members(flate_hip_ctx *c, const flate::OneDecParams &D, const uint8_t *in, uint64_t in_len,
+                               const uint64_t *p_bit_off, const uint64_t *p_bit_end, uint32_t count, uint8_t *d_out,
+                               const UnitResults &dec) {
+  const int r = unit_decode(c, unit_decode_params(D, in, in_len, p_bit_off, p_bit_end, false, count, d_out, D.p_out_off, dec));
+  if (r) return r;
+  hipLaunchKernelGGL(flate::one_check_kernel, dim3((count + 1u + 255u) / 256u), dim3(256), 0, c->stream, D);
+  return FLATE_HIP_OK;
+}
+
+// WHERE A CALL DECODES TO: the caller's device buffer, or the ctx's staged output grown to total + 16 bytes
+inline int unit_out_buffer(flate_hip_ctx *c, uint8_t *out, bool dev, uint64_t total, uint8_t *&d_out) {
+  d_out = out;
+  if (dev) return FLATE_HIP_OK;
+  const int rc = ensure(c, c->d_out, total + 16);
+  if (rc == FLATE_HIP_OK) d_out = (uint8_t *)c->d_out.p;
+  return rc;
+}
+// ... and the result brought down ONCE, behind the read-back of the call's result words: got bytes into a host
+// caller's out, synchronised
+inline hipError_t unit_bring_down(flate_hip_ctx *c, uint8_t *out, const uint8_t *d_out, bool dev, uint64_t got) {
+  if (dev || !got) return hipSuccess;
+  const hipError_t e = hipMemcpyAsync(out, d_out, got, hipMemcpyDeviceToHost, c->stream);
+  return e != hipSuccess ? e : hipStreamSynchronize(c->stream);
+}
+// ... by a whole call: got, which a sound call never reports above total (FLATE_HIP_E_INTERNAL), is *out_len
+inline int unit_deliver(flate_hip_ctx *c, uint8_t *out, const uint8_t *d_out, bool dev, uint64_t got, uint64_t total,
+                        uint64_t *out_len) {
+  if (got > total) return FLATE_HIP_E_INTERNAL;
+  *out_len = got;
+  HIP_TRY(c, unit_bring_down(c, out, d_out, dev, got));
+  return FLATE_HIP_OK;
+}
+
+// ---- what the two readers in parts share (flate_hip_one_reader_*, flate_hip_gzfile_reader_*) ----
+
+// What every handle holds: the ctx, the caller's flags, the unit rule and "one_unit_max" of the ctx AT OPEN, whatever it
+// says later, and the device words that rest between two calls.
+struct UnitReader {
+  flate_hip_ctx *ctx = nullptr;
+  uint32_t flags = 0;
+  uint64_t unit_max = 0;
+  uint32_t stored_units = 0;
+  DevBuf state;
+};
+// open: a handle R with state_bytes of device words, made fresh by fresh(r) (which sets what R adds to the base)
+template <class R, class Fresh>
+int unit_reader_open(flate_hip_ctx *c, uint32_t flags, size_t state_bytes, Fresh fresh, R **out) {
+  *out = nullptr;
+  c->hip_err.clear();
+  HIP_TRY(c, hipSetDevice(c->device));
+  R *r = new R();
+  r->ctx = c;
+  r->flags = flags;
+  r->unit_max = c->one_unit_max;
+  r->stored_units = c->one_stored_units;
+  int rc = ensure(c, r->state, state_bytes + 64);
+  if (rc == FLATE_HIP_OK) rc = fresh(r);
+  if (rc != FLATE_HIP_OK) {
+    delete r;
+    return rc;
+  }
+  *out = r;
+  return FLATE_HIP_OK;
+}
+template <class R, class Fresh>
+int unit_reader_reset(R *r, Fresh fresh) {
+  if (!r) return FLATE_HIP_E_INVALID;
+  flate_hip_ctx *c = r->ctx;
+  c->hip_err.clear();
+  HIP_TRY(c, hipSetDevice(c->device));
+  return fresh(r);
+}
+template <class R>
+void unit_reader_free(R *r) {
+  if (!r) return;
+  (void)hipSetDevice(r->ctx->device);
+  delete r;
+}
+
+// THE SEED of a reader's first round, R[0]: the handle's window
+inline int unit_window_seed(flate_hip_ctx *c, const flate::OneDecParams &D, const uint8_t *window) {
+  HIP_TRY(c, hipMemcpyAsync(D.R, window, flate::kWinEntries, hipMemcpyDeviceToDevice, c->stream));
+  return FLATE_HIP_OK;
+}
+// A reader's result, behind the read-back of its result words: got > total is FLATE_HIP_E_INTERNAL; THE CARRY back into
+// the handle once the words are good (`sound`) -- the window behind the last of the n_dec units, which the round driver
+// leaves in R[count] of the last round (nothing has been queued behind the rounds that writes D.R) --; then the result
+// comes down.  All of it moves the handle's device words or follows work that did: whatever fails here is the caller's
+// to end the handle with, so nothing is reported through HIP_TRY, and a copy that fails delivers nothing.
+inline int unit_reader_deliver(flate_hip_ctx *c, const flate::OneDecParams &D, uint8_t *window, uint32_t n_dec, uint32_t per_round,
+                               bool sound, uint8_t *out, const uint8_t *d_out, bool dev, uint64_t got, uint64_t total,
+                               uint64_t *out_len) {
+  if (got > total) return FLATE_HIP_E_INTERNAL;
+  if (n_dec && sound) {
+    const uint8_t *last = D.R + (size_t)flate::unit_last_count(n_dec, per_round) * flate::kWinEntries;
+    if (hipMemcpyAsync(window, last, flate::kWinEntries, hipMemcpyDeviceToDevice, c->stream) != hipSuccess) return FLATE_HIP_E_HIP;
+  }
+  *out_len = got;
+  if (unit_bring_down(c, out, d_out, dev, got) == hipSuccess) return FLATE_HIP_OK;
+  *out_len = 0;
+  return FLATE_HIP_E_HIP;
 }
 
 // What TAIL found, read back behind the rounds: R.first_bad = the first unit that fails (0xffffffff: none) and, of that

@@ -177,8 +177,9 @@ int zip_deflate_pieces(flate_hip_ctx *c, const uint8_t *in, const uint64_t *piec
 // ctx's d_out_len / d_istatus / d_ierr.  Returns FLATE_HIP_OK or the first non-zero stream status.
 int inflate_ranges_device(flate_hip_ctx *c, const uint8_t *d_in, const uint64_t *in_off, const uint64_t *in_end, uint32_t n,
                           uint8_t *d_out, const uint64_t *out_off, uint64_t *out_len, int32_t *status, int64_t *err_off);
-// flate_api_inflate.hip: the LONG entries of flate_hip_zip_read through units (the option "zip_unit_min"): discovery
-// over the hull d_in[hull_lo, hull_hi), the decode rounds into d_out, and the read-back of what they served.  L / R:
+// flate_api_units.hip: the LONG entries of flate_hip_zip_read through units (the option "zip_unit_min"): the two-list
+// discovery (unit_discovery.h, with ZIP's bits, link, finish, entries and rel kernels as its hooks) over the hull
+// d_in[hull_lo, hull_hi), the decode rounds into d_out, and the read-back of what they served.  L / R:
 // zip_units_form + zip_units_hull (L not empty).  On return *g = the entries L[0, *g) that are decoded and GOOD (the
 // caller gives every other one to the batch decoders), G what zip_units_verdict_kernel needs once the caller has set
 // g and the three z_ arrays, and *n_units / *n_cand the route report's counts.  Discovery is counted in no profiling

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""The launches of the seven unit-round loops, for a comparison of two builds of the library.
+"""The launches of the unit discoveries and the unit-round loops, for a comparison of two builds of the library.
 
     rocprofv3 --kernel-trace -d DIR -o p --output-format csv -- python tools/unit_rounds_trace.py run
     python tools/unit_rounds_trace.py compare A_kernel_trace.csv B_kernel_trace.csv [--out DIR]
@@ -11,7 +11,13 @@ units are the archive's one entry) and makes one call each:
   A flate_hip_inflate_one, B _inflate_one_seek_index, C _inflate_one_ranges on the stream as one gzip member;
   D flate_hip_gzfile_read with "gzfile_serial_max" off and on, E _gzfile_seek_index, F _gzfile_ranges on the chunks as
     three members of 3 + 1 + 3 units (with the option on the middle member is decoded whole: two runs of units);
-  G flate_hip_zip_read with "zip_unit_min" = 1 on the stream as the one entry of an archive.
+  G flate_hip_zip_read with "zip_unit_min" = 1 on the stream as the one entry of an archive;
+  H flate_hip_inflate_one_index on A's stream, I flate_hip_gzfile_index on D's file with "gzfile_serial_max" off and on
+    (the discoveries alone; flate_hip_gzfile_seek_index does not read that option, so E is not repeated with it);
+  J flate_hip_one_reader_* over A's stream in three parts cut inside units, K flate_hip_gzfile_reader_* over D's file in
+    three parts -- one cut inside a member, one inside a gzip header -- with room for one unit a call, so that calls
+    deliver fewer units than they found;
+  L A and D's first read once more with DEVICE pointers (A to G pass host pointers: the output is staged and comes down).
 Every result is compared with the input.  FLATE_HIP_LIB chooses the library, as for every tool here.
 
 `compare` reads the kernel traces of two such runs and holds the ordered lists of (kernel name, grid size, workgroup
@@ -103,6 +109,40 @@ def run():
     eng.set_option("zip_unit_min", 1)                                                       # G
     out, r = eng.zip_read(archive(raw_stream(chunks), plain), out=buf())
     check("G zip_read through units", r.rc == 0 and bytes(out[:int(r.out_len[0])]) == plain and eng.zip_last_route()[0] == 1)
+    eng.set_option("zip_unit_min", 0)
+    ix = eng.inflate_one_index(one, "gzip")                                                 # H
+    check("H inflate_one_index", ix.rc == 0 and ix.out_bytes == len(plain), ix.n_units)
+    for serial in (0, serial_max):                                                          # I
+        eng.set_option("gzfile_serial_max", serial)
+        gx = eng.gzfile_index(members)
+        check("I gzfile_index, gzfile_serial_max %d" % serial, gx.rc == 0 and gx.n_members == 3 and gx.out_bytes == len(plain),
+              gx.n_units)
+    eng.set_option("gzfile_serial_max", 0)
+
+    def feed(rd, f, ends, out_cap):
+        """f through a reader, a part per entry of `ends`, each beginning with what the last call left unused"""
+        got, pos, units, rc = b"", 0, 0, 0
+        for end in ends:
+            for _ in range(UNITS + 2):  # (a call that delivers fewer units than it found is made again over the rest)
+                used, out, r = rd.read(f[pos:end], final=end == len(f), out_cap=out_cap)
+                got, pos, units, rc = got + bytes(out), pos + used, units + r.n_units, r.rc
+                if rc != 0 or used == 0 or pos == end:
+                    break
+        rd.close()
+        return rc == 1 and got == plain and pos == len(f), units
+
+    third = len(one) // 3                                                                   # J
+    check("J one reader in three parts", *feed(eng.open_one_reader("gzip"), one, [third, 2 * third, len(one)], None))
+    m0, m1 = len(member(chunks[:3])), len(member(chunks[3:4]))                              # K
+    check("K gzfile reader in three parts", *feed(eng.open_gzfile_reader(), members, [m0 // 2, m0 + m1 + 4, len(members)],
+                                                  CHUNK + 100))
+    import torch                                                                            # L
+    dev = lambda b: torch.from_numpy(np.frombuffer(b, np.uint8).copy()).cuda()
+    room = lambda: torch.empty(len(plain) + 64, dtype=torch.uint8, device="cuda")
+    out, r = eng.inflate_one(dev(one), "gzip", out=room())
+    check("L inflate_one, device pointers", r.rc == 0 and bytes(out[:r.out_len].cpu().numpy()) == plain, r.n_units)
+    out, r = eng.gzfile_read(dev(members), out=room())
+    check("L gzfile_read, device pointers", r.rc == 0 and bytes(out[:r.out_len].cpu().numpy()) == plain, r.n_units)
     eng.close()
     print("unit_rounds_trace: %d calls ok (%s)" % (len(done), "; ".join(done)))
 
