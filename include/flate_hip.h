@@ -1364,9 +1364,41 @@ int flate_hip_gzfile_last_route(const flate_hip_ctx *ctx, uint32_t *serial_membe
  *   written, planned total <= out_cap, and nothing outside out[0, *out_len) except in a call that reports a wrong
  *   trailer, where out[*out_len, planned total) is unspecified.  Per call the host waits for the discovery's two
  *   read-backs and one read-back of the result words.
- *   Out of scope: "gzfile_serial_max" inside the reader (it is ignored: a file of many short members pays FIND per
- *   part; routing short members whole is the follow-up); zlib or raw concatenations; overlapping the upload of part
- *   k + 1 with the decode of part k; a seek index built in parts; the MoonBit binding. */
+ *   SHORT MEMBERS WHOLE (flate_hip_gzfile_reader_set_serial_max, S >= 1; the rule: csrc/gzfile_parts_serial_rule.h, the
+ *   kernels: csrc/gzfile_parts_serial_kernels.hip).  The ctx option "gzfile_serial_max" is ignored by the reader: the
+ *   setting is the handle's.  With S = 0, the default, a call launches exactly what is described above.  With S >= 1 a
+ *   member that lies whole inside the part, fits in S bytes and decodes cleanly is ONE unit: it is never searched for
+ *   block headers and never walked symbolically, and the call decodes all such members with one batch of the batch
+ *   decoders, in front of the rounds (counted in FLATE_HIP_STAGE_INFLATE).  Every offset p that passes the header rule
+ *   over in[p, in_len) gets the serial range of flate_hip_gzfile_read's option with the PART's in_len, E = min(in_len -
+ *   8, p + S), and one size-only launch of the batch decoders runs over all ranges.  THREE VERDICTS: WHOLE -- the whole
+ *   test holds and the member inflates to at most out_cap bytes; OPEN -- the part is not final, the range was clipped
+ *   by the part and not by S (in_len - 8 < p + S) and the decode ran out of input there (FLATE_HIP_E_UNEXPECTED_EOF, or
+ *   the header alone did not fit in front of E): more bytes could make it whole; LONG -- everything else (longer than
+ *   S, corrupt, 4 GiB or more, larger than out_cap): cut into units exactly as with S = 0, so a bounded output buffer
+ *   always makes the progress S = 0 makes.  A final part has no OPEN verdict.  THE WALK and find_from: INSIDE a member
+ *   find_from = 0 -- the continued member is units, FIND runs in its PARTS build over the part, whole members behind it
+ *   are still single nodes.  At a BOUNDARY the walk goes from the member at byte 0 along THE PARTS HOP for as long as
+ *   members are WHOLE: a LONG member at p gives find_from = p; an OPEN member at p > 0 ends the chain with a BOUNDARY
+ *   stop at p and find_from = in_len; an OPEN member at the root is treated as LONG (find_from = 0), so the reader
+ *   never needs a part of a minimum size; the file's end, a dead hop or a stop give find_from = in_len.  Everywhere in
+ *   the chain a hop that lands on the header of an OPEN member is a BOUNDARY stop there.  FIND runs over in[find_from,
+ *   in_len) only, or not at all.  STATE: with S >= 1 a call whose first undelivered unit is a member's first unit stops
+ *   at the BOUNDARY in front of that member's HEADER (*in_used = the header's offset), so that the next part judges the
+ *   member as a root; no window leaves a call whose last delivered unit is a whole member.  THE CONTRACT holds for every
+ *   cut, every out_cap and every S: the bytes, the sticky status and words and the sum of *in_used are the walk's;
+ *   *n_units and *in_used of a single call depend on S, and the *n_units of a file's calls sum to the walk's units
+ *   minus every unit of a whole member that is not its first.  A whole member is a checksum segment of one unit; the
+ *   guarantee about out[0, planned total) is unchanged (the batch's last slot ends at the planned total).
+ *   set_serial_max: S is 0 .. 2^28 - 1 and the handle must be FRESH -- behind open or reset, before any call has
+ *   consumed a byte -- else FLATE_HIP_E_INVALID, as for a NULL handle; no HIP call; reset keeps S, as it keeps the unit
+ *   rule.  last_route reports on the last read that ran a discovery: *serial_members = the whole members among the units
+ *   it delivered, *open_stop = 1 when its chain ended at a BOUNDARY stop in front of an OPEN member, *find_from = the
+ *   part offset FIND started at (that call's in_len: no bit-offset search ran; 0 with S = 0).  Every pointer is
+ *   required (else FLATE_HIP_E_INVALID); no HIP call.
+ *   Out of scope: FIND in windows between long members (the search runs from find_from to the part's end, so "INSIDE,
+ *   then many short members in the same part" pays FIND over the part); zlib or raw concatenations; overlapping the
+ *   upload of part k + 1 with the decode of part k; a seek index built in parts; the MoonBit binding. */
 typedef struct flate_hip_gzfile_reader flate_hip_gzfile_reader;
 int flate_hip_gzfile_reader_open(flate_hip_ctx *ctx, uint32_t flags, flate_hip_gzfile_reader **reader);
 int flate_hip_gzfile_reader_read(flate_hip_gzfile_reader *reader, const uint8_t *in, uint64_t in_len, int final_in,
@@ -1375,6 +1407,9 @@ int flate_hip_gzfile_reader_read(flate_hip_gzfile_reader *reader, const uint8_t 
                                  int64_t *stream_err_off);
 int flate_hip_gzfile_reader_reset(flate_hip_gzfile_reader *reader);
 void flate_hip_gzfile_reader_free(flate_hip_gzfile_reader *reader);
+int flate_hip_gzfile_reader_set_serial_max(flate_hip_gzfile_reader *reader, uint64_t serial_max);
+int flate_hip_gzfile_reader_last_route(const flate_hip_gzfile_reader *reader, uint32_t *serial_members,
+                                       uint32_t *open_stop, uint64_t *find_from);
 
 /* -- Seek index for any gzip file: build once, read ranges across members -------------
  * flate_hip_gzfile_read pays the whole discovery on every call and delivers everything.  flate_hip_gzfile_seek_index

@@ -6,6 +6,7 @@
 
 #include "flate_hip.h"
 #include "gzfile_parts_rule.h"
+#include "gzfile_parts_serial_rule.h"
 #include "gzfile_seek_rule.h"
 #include "one_parts_rule.h"
 #include "one_writer_rule.h"
@@ -215,6 +216,18 @@ inline int gzfile_reader_open_args(const void *ctx, uint32_t flags, const void *
 inline int gzfile_reader_read_args(const void *reader, const uint8_t *in, uint64_t in_len, const uint8_t *out,
                                    uint64_t out_cap, const uint64_t *in_used, const uint64_t *out_len) {
   return one_parts_read_args(reader, in, in_len, out, out_cap, in_used, out_len);
+}
+
+// flate_hip_gzfile_reader_set_serial_max / _last_route (gzfile_parts_serial_rule.h).  S: gzfile_serial_max_ok's range;
+// fresh: the handle stands behind open or reset and no call has consumed a byte.
+inline bool gzfile_serial_max_ok(int64_t value);
+inline int gzfile_reader_set_serial_max_args(const void *reader, uint64_t serial_max, bool fresh) {
+  if (serial_max > (uint64_t)INT64_MAX || !gzfile_serial_max_ok((int64_t)serial_max)) return FLATE_HIP_E_INVALID;
+  return gzfile_parts_serial_set_args(reader, serial_max, fresh);
+}
+inline int gzfile_reader_last_route_args(const void *reader, const uint32_t *serial_members, const uint32_t *open_stop,
+                                         const uint64_t *find_from) {
+  return gzfile_parts_route_args(reader, serial_members, open_stop, find_from);
 }
 
 // flate_hip_one_writer_open / _write (one_writer_rule.h holds the checks and what a call decides; its words are this

@@ -11,6 +11,7 @@
 #include "api_checks.h"
 #include "bgzf_range_rule.h"
 #include "gzfile_parts_rule.h"
+#include "gzfile_parts_serial_rule.h"
 #include "gzfile_rule.h"
 #include "gzip_rule.h"
 #include "unit_discovery.h"
@@ -1218,12 +1219,15 @@ struct GzFileBack {
   std::vector<uint64_t> *mout = nullptr;
   std::vector<uint64_t> *index = nullptr;
   std::vector<uint32_t> *u_final = nullptr;
+  std::vector<uint32_t> *u_whole = nullptr;  // (a part with whole members: the per-unit marks, cap + 1)
 };
 // "gzfile_serial_max": phase 1's words (gzfile_discover_serial) for the chain behind it
 struct GzSerialIn {
   GzSerialParams &S;
   GzSerialHead &SH;
   uint64_t find_from;
+  const uint32_t *verdict = nullptr;  // a part: the three verdicts of List B (gzfile_parts_serial_rule.h)
+  bool parts_find = false;            // a part INSIDE a member: FIND's PARTS build, over the whole part
 };
 
 // The chain of a file's discovery, behind the counts na / nb of the two lists (unit_discovery.h): the size rule, the
@@ -1235,6 +1239,10 @@ struct GzSerialIn {
 //         and one small kernel moves its bits to the file's origin; a whole B node is parked at the raw stream's end for
 //         PROBE and gets its phase-1 record back behind it; the marks between finish and out-scan, the list of whole
 //         members at the end, SH in the read-back
+//   both  a part of a handle with flate_hip_gzfile_reader_set_serial_max: the part's root, finish and rel kernels, the
+//         link with the OPEN stop; FIND's build is the PARTS one only INSIDE a member (then over the whole part); no list
+//         of whole members -- the call lays out its batch behind its plan -- but whether the chain ended in front of
+//         an OPEN member, and the per-unit marks in the read-back
 int gzfile_chain(flate_hip_ctx *c, GzFileParams &P, OneParams &PA, GzipParams &PB, uint32_t na, uint32_t nb,
                  const GzPartIn *part, const GzSerialIn *ser, OneHead &H, GzFileHead &G, const GzFileBack &back) {
   int rc;
@@ -1260,13 +1268,13 @@ int gzfile_chain(flate_hip_ctx *c, GzFileParams &P, OneParams &PA, GzipParams &P
   if (ser) {
     GzSerialParams &S = ser->S;
     S.n_a = na;
-    rc = carve(c, c->d_gzfile_serial_units, [&](Carve &k) {
+    rc = carve(c, part ? c->d_gzfile_parts_serial_units : c->d_gzfile_serial_units, [&](Carve &k) {
       k.take(S.u_whole, n + 1);
       k.take(S.u_end, n + 1);
     });
     if (rc) return rc;
     if (ser->find_from < C.in_len) {
-      one_find_launch(c, false, PA.C.n_tiles, PA, false);
+      one_find_launch(c, false, PA.C.n_tiles, PA, ser->parts_find);
       if (na)
         hipLaunchKernelGGL(gzfile_serial_base_kernel, dim3((na + 255u) / 256u), dim3(256), 0, c->stream, C.cand_off, na,
                            8u * ser->find_from);
@@ -1283,7 +1291,10 @@ int gzfile_chain(flate_hip_ctx *c, GzFileParams &P, OneParams &PA, GzipParams &P
   if (n) one_probe_launch(c, C.cap, P.O, 0u);
   if (ser && nb) hipLaunchKernelGGL(gzfile_serial_keep_kernel, dim3((nb + 255) / 256), dim3(256), 0, c->stream, P, ser->S);
   auto link = [&](dim3 g) {
-    if (part)
+    if (part && ser)
+      hipLaunchKernelGGL(gzfile_part_serial_link_kernel, g, dim3(256), 0, c->stream, P, ser->verdict, part->inside,
+                         part->final_in);
+    else if (part)
       hipLaunchKernelGGL(gzfile_part_link_kernel, g, dim3(256), 0, c->stream, P, part->inside, part->final_in);
     else
       hipLaunchKernelGGL(gzfile_link_kernel, g, dim3(256), 0, c->stream, P);
@@ -1304,7 +1315,8 @@ int gzfile_chain(flate_hip_ctx *c, GzFileParams &P, OneParams &PA, GzipParams &P
       hipLaunchKernelGGL(gzfile_part_rel_kernel, dim3(node_blocks), dim3(256), 0, c->stream, P, part->hist);
     else
       hipLaunchKernelGGL(gzfile_rel_kernel, dim3(node_blocks), dim3(256), 0, c->stream, P);
-    if (ser) hipLaunchKernelGGL(gzfile_serial_list_kernel, dim3(1), dim3(1024), 0, c->stream, P, ser->S);
+    if (ser && part) hipLaunchKernelGGL(gzfile_part_serial_stop_kernel, dim3(1), dim3(64), 0, c->stream, P, ser->S);
+    else if (ser) hipLaunchKernelGGL(gzfile_serial_list_kernel, dim3(1), dim3(1024), 0, c->stream, P, ser->S);
   };
   return unit_chain(c, P.O, link, finish, marks, behind, H, G, P.gh, [&]() -> int {
     if (ser) HIP_TRY(c, hipMemcpyAsync(&ser->SH, ser->S.head, sizeof ser->SH, hipMemcpyDeviceToHost, c->stream));
@@ -1320,6 +1332,10 @@ int gzfile_chain(flate_hip_ctx *c, GzFileParams &P, OneParams &PA, GzipParams &P
       HIP_TRY(c, hipMemcpyAsync(x + (n + 1), C.out_off, (n + 1) * 8, hipMemcpyDeviceToHost, c->stream));
       HIP_TRY(c, hipMemcpyAsync(x + 2 * (n + 1), P.u_start, (n + 1) * 8, hipMemcpyDeviceToHost, c->stream));
       if (n) HIP_TRY(c, hipMemcpyAsync(back.u_final->data(), P.u_final, n * 4, hipMemcpyDeviceToHost, c->stream));
+      if (back.u_whole) {
+        back.u_whole->assign(n + 1, 0);
+        if (ser) HIP_TRY(c, hipMemcpyAsync(back.u_whole->data(), ser->S.u_whole, (n + 1) * 4, hipMemcpyDeviceToHost, c->stream));
+      }
     }
     return FLATE_HIP_OK;
   });
@@ -1543,6 +1559,151 @@ int gzfile_discover_routed(flate_hip_ctx *c, const uint8_t *d_in, uint64_t in_le
   c->gzfile_route[0] = SH.n_whole;
   c->gzfile_route[1] = G.n_members - SH.n_whole;
   c->gzfile_route_from = SH.find_from;
+  return FLATE_HIP_OK;
+}
+
+// The discovery over one PART of a file with whole members (flate_hip_gzfile_reader_set_serial_max: S >= 1;
+// gzfile_parts_serial_rule.h, gzfile_parts_serial_kernels.hip): gzfile_discover_serial's two phases with the part's
+// root, verdicts and hop, then gzfile_chain with BOTH hooks.  PHASE 1 over the part's List B: the part's words, count,
+// scan, ONE read-back of the B count and the root's verdict (*root_bad: anything but 0 ends the discovery there), fill,
+// the serial ranges with the PART's in_len, ONE size-only launch of the batch decoders, the three verdicts with the
+// links of THE PARTS HOP, pointer doubling, find_from (INSIDE: 0) and its read-back.  PHASE 2, only when find_from <
+// in_len: FIND -- INSIDE a member its PARTS build over the whole part, whose candidate 0 is the chain's root; at a
+// BOUNDARY the ordinary build over in[find_from, in_len), which starts at a member's header -- and the read-back of
+// its count.  SH.pad = the chain ended in front of an OPEN member; S = phase 1's arrays, on the device.
+int gzfile_discover_part_serial(flate_hip_ctx *c, const uint8_t *d_in, uint64_t in_len, const GzPartIn &part, uint64_t serial_max,
+                                uint64_t out_cap, OneHead &H, GzFileHead &G, GzFileParams &P, GzSerialParams &S,
+                                GzSerialHead &SH, uint32_t *root_bad, const GzFileBack &back) {
+  int rc;
+  P = GzFileParams{};
+  S = GzSerialParams{};
+  SH = GzSerialHead{};
+  OneParams PA{};
+  GzipParams PB{};
+  ChainParams &C = P.O.C;
+  C.in = d_in;
+  C.in_len = in_len;
+  if ((rc = tiles_for(d_in, 0, in_len, &C.n_tiles))) return rc;
+  const uint32_t n_tiles = C.n_tiles;
+  OneHead *head_a;
+  FrameOne *one_a;
+  rc = gzfile_tiles_carve(c, P, PA, PB, head_a, (size_t)n_tiles + 1, [&](Carve &k) {  // (a suffix at another alignment:
+    k.take(one_a, 1);                                                                  // at most one tile more)
+    k.take(S.head, 1);
+  });
+  if (rc) return rc;
+  BgzfHead *head_b = PB.C.head;
+  P.O.unit_max = part.unit_max;
+  P.O.stored_units = part.stored_units;
+  hipLaunchKernelGGL(gzfile_part_init_kernel, dim3(1), dim3(64), 0, c->stream, P.O.one, d_in, in_len, part.inside, part.b0);
+  hipLaunchKernelGGL(gzip_count_kernel, dim3(n_tiles), dim3(256), 0, c->stream, PB);
+  hipLaunchKernelGGL(chain_scan_kernel, dim3(1), dim3(1024), 0, c->stream, PB.C);
+  HIP_TRY(c, hipGetLastError());
+  BgzfHead HB{};
+  FrameOne root{};
+  HIP_TRY(c, hipMemcpyAsync(&HB, head_b, sizeof HB, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(&root, P.O.one, sizeof root, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  if ((*root_bad = root.bad)) return FLATE_HIP_OK;
+  const uint32_t nb = HB.n_cand;
+  if (nb > 0x7ffffff0u) return FLATE_HIP_E_TOO_LARGE;  // (the count saturates at 2^32 - 1)
+  if ((rc = chain_size(PB.C, nb))) return rc;
+
+  // PHASE 1
+  uint64_t *hdr_off;
+  InfParams I{};  // size-only: no output buffer, no slots
+  GzPartSerialIn A{part.final_in, part.inside, out_cap, nullptr};
+  rc = carve(c, c->d_gzfile_parts_serial, [&](Carve &k) {
+    k.take(hdr_off, (size_t)nb + 1);
+    k.take(PB.cand_end, nb);
+    k.take(S.pay_off, (size_t)nb + 1);
+    k.take(S.pay_end, nb);
+    k.take(I.out_len, nb);
+    k.take(I.status, nb);
+    k.take(I.err_off, nb);
+    k.take(I.used, nb);
+    k.take(S.rec, nb);
+    k.take(S.whole, nb);
+    k.take(A.verdict, nb);
+    k.take(S.jump[0], (size_t)nb + 2);
+    k.take(S.jump[1], (size_t)nb + 2);
+    k.take(S.w_in_off, (size_t)nb + 1);
+    k.take(S.w_in_end, nb);
+    k.take(S.w_out_off, (size_t)nb + 1);
+    k.take(S.w_size, nb);
+    k.take(S.w_unit, nb);
+  });
+  if (rc) return rc;
+  PB.C.cand_off = hdr_off;
+  P.hdr_off = hdr_off;
+  P.n_b = nb;
+  S.in = d_in;
+  S.in_len = in_len;
+  S.serial_max = serial_max;
+  S.n_b = nb;
+  S.hdr_off = hdr_off;
+  S.status = I.status;
+  S.out_len = I.out_len;
+  S.used = I.used;
+  uint64_t find_from = part.inside ? 0ull : in_len;  // (no candidate: only INSIDE, where the continued member is units)
+  if (nb) {
+    const uint32_t b_blocks = (nb + 255u) / 256u, w_blocks = (uint32_t)(((uint64_t)nb + 2 + 255) / 256);
+    const uint64_t longest = in_len < S.serial_max ? in_len : S.serial_max;
+    const InflateRoute route = inflate_route(c->inflate, c->num_cus, nb, longest, false, true);
+    if (route.decoder == kDecodeSimt) {
+      c->hip_err = "gzfile reader: a size-only pass was routed to the lane-per-stream decoder";
+      return FLATE_HIP_E_INTERNAL;
+    }
+    I.in = d_in;
+    I.in_off = S.pay_off;
+    I.in_end = S.pay_end;
+    I.n_streams = nb;
+    I.in_len = in_len;
+    I.size_only = 1u;
+    hipLaunchKernelGGL(gzip_fill_kernel, dim3(n_tiles), dim3(256), 0, c->stream, PB);
+    hipLaunchKernelGGL(gzfile_serial_ranges_kernel, dim3(b_blocks), dim3(256), 0, c->stream, S);
+    HIP_TRY(c, hipGetLastError());
+    if ((rc = launch_decoders(c, route, I, false))) return rc;
+    hipLaunchKernelGGL(gzfile_part_serial_nodes_kernel, dim3(w_blocks), dim3(256), 0, c->stream, S, A);
+    int cur = 0;
+    for (uint64_t s = 1; s < (uint64_t)nb + 2; s <<= 1, cur ^= 1)
+      hipLaunchKernelGGL(gzfile_serial_round_kernel, dim3(w_blocks), dim3(256), 0, c->stream, S.jump[cur], S.jump[cur ^ 1],
+                         nb + 2u);
+    hipLaunchKernelGGL(gzfile_part_serial_from_kernel, dim3(1), dim3(64), 0, c->stream, S, A, S.jump[cur]);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(&SH, S.head, sizeof SH, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    find_from = SH.find_from;
+    if (find_from > in_len || (part.inside && find_from)) return FLATE_HIP_E_INTERNAL;
+  } else {
+    SH.find_from = find_from;
+    HIP_TRY(c, hipMemcpyAsync(S.head, &SH, sizeof SH, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));  // (SH is the caller's: the copy has read it)
+  }
+
+  // PHASE 2
+  uint32_t na = 0;
+  const bool parts_find = part.inside != 0u;
+  if (find_from < in_len) {
+    find_params(PA, P.O, head_a);
+    if (!parts_find) {
+      PA.C.in = d_in + find_from;
+      PA.C.in_len = in_len - find_from;
+      PA.one = one_a;
+      if ((rc = tiles_for(PA.C.in, 0, PA.C.in_len, &PA.C.n_tiles))) return rc;
+      if (PA.C.n_tiles > n_tiles + 1u) return FLATE_HIP_E_INTERNAL;
+      hipLaunchKernelGGL(gzfile_init_kernel, dim3(1), dim3(64), 0, c->stream, one_a, PA.C.in_len);
+    }
+    find_count(c, PA, parts_find);
+    OneHead HA{};
+    if ((rc = find_counts_back(c, head_a, HA))) return rc;
+    na = HA.h.n_cand;
+  }
+  GzSerialIn ser{S, SH, find_from};
+  ser.verdict = A.verdict;
+  ser.parts_find = parts_find;
+  if ((rc = gzfile_chain(c, P, PA, PB, na, nb, &part, &ser, H, G, back))) return rc;
+  if (SH.find_from != find_from || SH.pad > 1u) return FLATE_HIP_E_INTERNAL;
   return FLATE_HIP_OK;
 }
 
@@ -2150,9 +2311,14 @@ int flate_hip_gzfile_ranges(flate_hip_ctx *c, const uint8_t *in, uint64_t in_len
 
 // Between two calls the file's state rests in the handle: on the device the 32 KiB window and the running CRC-32 of
 // the member in progress (GzPartState), on the host the rule's words (GzPartsState).  The unit rule and "one_unit_max"
-// are the ctx's at open, whatever it says later (UnitReader); "gzfile_serial_max" is not read.
+// are the ctx's at open, whatever it says later (UnitReader); "gzfile_serial_max" is not read: the handle has a setting
+// of its own (flate_hip_gzfile_reader_set_serial_max; gzfile_parts_serial_rule.h), which reset keeps as it keeps the
+// unit rule, and the words of flate_hip_gzfile_reader_last_route.
 struct flate_hip_gzfile_reader : UnitReader {
   GzPartsState s = gzfile_parts_fresh();
+  uint64_t serial_max = 0;
+  uint32_t route_members = 0, route_open = 0;
+  uint64_t route_from = 0;
 };
 
 namespace {
@@ -2163,6 +2329,8 @@ int gzfile_reader_fresh(flate_hip_gzfile_reader *r) {
   HIP_TRY(c, hipMemsetAsync(r->state.p, 0, sizeof(GzPartState), c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   r->s = gzfile_parts_fresh();
+  r->route_members = r->route_open = 0;
+  r->route_from = 0;
   return FLATE_HIP_OK;
 }
 
@@ -2179,6 +2347,21 @@ int flate_hip_gzfile_reader_open(flate_hip_ctx *c, uint32_t flags, flate_hip_gzf
 int flate_hip_gzfile_reader_reset(flate_hip_gzfile_reader *r) { return unit_reader_reset(r, gzfile_reader_fresh); }
 
 void flate_hip_gzfile_reader_free(flate_hip_gzfile_reader *r) { unit_reader_free(r); }
+
+int flate_hip_gzfile_reader_set_serial_max(flate_hip_gzfile_reader *r, uint64_t serial_max) {
+  if (gzfile_reader_set_serial_max_args(r, serial_max, r && gzfile_parts_is_fresh(r->s))) return FLATE_HIP_E_INVALID;
+  r->serial_max = serial_max;
+  return FLATE_HIP_OK;
+}
+
+int flate_hip_gzfile_reader_last_route(const flate_hip_gzfile_reader *r, uint32_t *serial_members, uint32_t *open_stop,
+                                       uint64_t *find_from) {
+  if (gzfile_reader_last_route_args(r, serial_members, open_stop, find_from)) return FLATE_HIP_E_INVALID;
+  *serial_members = r->route_members;
+  *open_stop = r->route_open;
+  *find_from = r->route_from;
+  return FLATE_HIP_OK;
+}
 
 // One call: flate_hip_gzfile_read on the part in[0, in_len), its chain rooted where the last call stopped -- discovery
 // (the index comes back with the result words: the host picks the units that fit and finds the members among them,
@@ -2239,7 +2422,18 @@ int flate_hip_gzfile_reader_read(flate_hip_gzfile_reader *r, const uint8_t *in, 
     std::vector<uint32_t> u_final;
     GzFileBack back;
     back.index = &index, back.u_final = &u_final;
-    if ((rc = gzfile_discover(c, d_in, in_len, &part, H, G, P, &root_bad, back))) return rc;
+    // S >= 1: the members that lie whole inside the part are single units (gzfile_parts_serial_rule.h)
+    const uint64_t S = r->serial_max;
+    GzSerialParams SP{};
+    GzSerialHead SH{};
+    std::vector<uint32_t> u_whole;
+    if (S) {
+      back.u_whole = &u_whole;
+      rc = gzfile_discover_part_serial(c, d_in, in_len, part, S, out_cap, H, G, P, SP, SH, &root_bad, back);
+    } else {
+      rc = gzfile_discover(c, d_in, in_len, &part, H, G, P, &root_bad, back);
+    }
+    if (rc) return rc;
     if (root_bad == kPartsHdrBad || (root_bad && fin)) return fail_here(FLATE_HIP_E_CORRUPT, true);
     if (root_bad) {  // the header is refused only because the part ends here: more is needed
       if (in_len >= r->unit_max) return fail_here(FLATE_HIP_E_TOO_LARGE, true);
@@ -2255,7 +2449,11 @@ int flate_hip_gzfile_reader_read(flate_hip_gzfile_reader *r, const uint8_t *in, 
     X.unit_bit = index.data(), X.out_off = index.data() + n1, X.u_start = index.data() + 2 * n1;
     X.u_final = u_final.data();
     X.rc = H.h.rc, X.err_off = H.h.err_off, X.fail_unit = H.fail_unit, X.fail_out = H.fail_out, X.no_header = G.no_header;
-    const GzPartsCall call = gzfile_parts_call(s, X, in_len, fin, out_cap, r->unit_max);
+    if (S && u_whole.size() < (size_t)X.n + 1) return FLATE_HIP_E_INTERNAL;
+    r->route_members = 0;
+    r->route_open = S ? SH.pad : 0u;
+    r->route_from = S ? SH.find_from : 0ull;
+    const GzPartsCall call = gzfile_parts_serial_call(s, X, in_len, fin, out_cap, r->unit_max, S);
     const OnePartsPlan &plan = call.plan;
     auto fail = [&](const GzPartsFail &f) {
       gzfile_parts_fail(s, X, call, f);
@@ -2275,7 +2473,26 @@ int flate_hip_gzfile_reader_read(flate_hip_gzfile_reader *r, const uint8_t *in, 
     const uint64_t total = plan.total;
     uint8_t *d_out;
     if ((rc = unit_out_buffer(c, out, dev, total, d_out))) return rc;
-    const uint32_t per_round = unit_per_round(c, n_dec);
+    // the runs of units the rounds go over: all of them, or what lies between the whole members -- a run starts with the
+    // continued member's unit or with a member's first unit, and ends where a member does
+    const uint32_t n_whole = S ? gzfile_parts_serial_count(u_whole.data(), n_dec) : 0u;
+    std::vector<std::pair<uint32_t, uint32_t>> runs;
+    uint32_t longest_run = n_dec;
+    if (n_whole) {
+      longest_run = 0;
+      for (uint32_t a = 0; a < n_dec;) {
+        uint32_t b = a;
+        while (b < n_dec && !u_whole[b]) ++b;
+        if (b > a) runs.emplace_back(a, b);
+        if (b - a > longest_run) longest_run = b - a;
+        a = b + 1u;
+      }
+    } else if (n_dec) {
+      runs.emplace_back(0u, n_dec);
+    }
+    // the units whose window the handle carries: the last run's, unless a whole member is the last unit (a BOUNDARY)
+    const uint32_t carry_units = runs.empty() || runs.back().second != n_dec ? 0u : n_dec - runs.back().first;
+    const uint32_t per_round = unit_per_round(c, longest_run);
     GzFileDecParams GD{};
     OneDecParams &D = GD.D;
     UnitResults dec;
@@ -2308,8 +2525,35 @@ int flate_hip_gzfile_reader_read(flate_hip_gzfile_reader *r, const uint8_t *in, 
       return unit_decode_members(c, D, d_in, H.raw_len, GD.p_bit_off, GD.p_bit_end, count, d_out, dec);
     };
     bool used[FLATE_HIP_STAGE_COUNT] = {false, false, false, false};
-    if (n_dec) {
-      if ((rc = unit_rounds(c, D, P.rel_off, GD.seed, 0, n_dec, n_dec, per_round, unit_no_hook, pieces, decode))) return rc;
+    if (n_whole && total) {
+      // the WHOLE members: ONE batch of independent streams straight into their places, IN FRONT of the rounds.  A slot
+      // ends at the next whole member's start and the last at the planned total: whatever the batch leaves between them
+      // is overwritten by the units that own those bytes, and nothing behind the planned total is written
+      hipLaunchKernelGGL(gzfile_part_serial_slots_kernel, dim3(1), dim3(1024), 0, c->stream, P, SP, n_dec, total);
+      InfParams W{};
+      rc = carve(c, c->d_gzfile_parts_serial_dec, [&](Carve &k) {
+        k.take(W.out_len, n_whole);
+        k.take(W.status, n_whole);
+        k.take(W.err_off, n_whole);
+      });
+      if (rc) return rc;
+      W.in = d_in;
+      W.in_off = SP.w_in_off;
+      W.in_end = SP.w_in_end;
+      W.n_streams = n_whole;
+      W.in_len = in_len;
+      W.out = d_out;
+      W.out_off = SP.w_out_off;
+      const uint64_t longest = in_len < S ? in_len : S;
+      if ((rc = launch_decoders(c, inflate_route(c->inflate, c->num_cus, n_whole, longest, false, false), W, false))) return rc;
+      hipLaunchKernelGGL(gzfile_serial_check_kernel, dim3((n_whole + 255u) / 256u), dim3(256), 0, c->stream, SP, n_whole,
+                         W.status, W.out_len, D.dh);
+      used[FLATE_HIP_STAGE_INFLATE] = true;
+      HIP_TRY(c, hipGetLastError());
+    }
+    for (const auto &run : runs) {
+      rc = unit_rounds(c, D, P.rel_off, GD.seed, run.first, run.second, n_dec, per_round, unit_no_hook, pieces, decode);
+      if (rc) return rc;
       used[FLATE_HIP_STAGE_INFLATE] = true;
     }
     // the members' sums: ONE launch planned over their ranges of the delivered bytes; the continued member's first
@@ -2362,11 +2606,12 @@ int flate_hip_gzfile_reader_read(flate_hip_gzfile_reader *r, const uint8_t *in, 
         hipStreamSynchronize(c->stream) != hipSuccess)
       return dead(FLATE_HIP_E_HIP);
     ctl_finish(c);
-    if ((rc = unit_reader_deliver(c, D, st->window, n_dec, per_round, V.status == 0, out, d_out, dev, V.out_len, total, out_len)))
+    if ((rc = unit_reader_deliver(c, D, st->window, carry_units, per_round, V.status == 0, out, d_out, dev, V.out_len, total, out_len)))
       return dead(rc);
     if (c->profiling && (rc = collect_timing(c, used))) return dead(rc);
     if (n_members) *n_members = V.n_members;
     if (n_units) *n_units = V.n_units;
+    if (S && V.n_units <= n_dec) r->route_members = gzfile_parts_serial_count(u_whole.data(), V.n_units);
     if (V.status) {
       if (V.status == FLATE_HIP_E_INTERNAL) return dead(V.status);
       return fail(GzPartsFail{V.status, V.bad_trailer, V.bad_member, V.err_off});

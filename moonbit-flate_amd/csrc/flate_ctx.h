@@ -116,6 +116,10 @@ struct flate_hip_ctx {
   DevBuf d_gzfile_serial, d_gzfile_serial_units, d_gzfile_serial_dec;
   uint32_t gzfile_route[2] = {0, 0};  // serial members, unit members
   uint64_t gzfile_route_from = 0;     // find_from
+  // flate_hip_gzfile_reader_read on a handle with flate_hip_gzfile_reader_set_serial_max (0 = off, the default: none of
+  // this is touched; gzfile_parts_serial_rule.h): phase 1's arrays over the part's List B with the verdicts, the
+  // per-unit marks, the batch results of the whole members
+  DevBuf d_gzfile_parts_serial, d_gzfile_parts_serial_units, d_gzfile_parts_serial_dec;
   DevBuf d_zip_names, d_zip_name_off, d_zip_whead, d_zip_end, d_zip_dir, d_zip_sel;
   // flate_hip_zip_read with the option "zip_unit_min" (0 = off, the default: none of this is touched): a deflated entry
   // of at least that many compressed bytes is decoded through units.  The count pass's words, L and the tile counts

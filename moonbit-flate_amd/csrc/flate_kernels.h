@@ -1014,6 +1014,24 @@ __global__ void gzfile_serial_list_kernel(GzFileParams P, GzSerialParams S);
 __global__ void gzfile_serial_check_kernel(GzSerialParams S, uint32_t n_whole, const int32_t *d_status,
                                            const uint64_t *d_out_len, OneDecHead *dh);
 
+// Short members decoded WHOLE inside a PART (gzfile_parts_serial_kernels.hip; flate_hip_gzfile_reader_set_serial_max;
+// the rule: gzfile_parts_serial_rule.h).  With S = 0 none of this is launched.  Phase 1 above runs over the part, with
+// gzfile_part_serial_nodes_kernel (the three verdicts, THE PARTS HOP) and gzfile_part_serial_from_kernel (INSIDE, the
+// root, the OPEN stop) in the places of the nodes and the from kernel; the chain is the part's, with
+// gzfile_part_serial_link_kernel as its link; gzfile_part_serial_stop_kernel says whether it ended in front of an OPEN
+// member (GzSerialHead::pad); gzfile_part_serial_slots_kernel, behind the host's plan, lays out the batch of the whole
+// members among the units the call decodes.
+struct GzPartSerialIn {
+  uint32_t final_in, inside;
+  uint64_t out_cap;          // a member that inflates to more is not WHOLE
+  uint32_t *verdict;         // n_b: kGzPartLong / kGzPartWhole / kGzPartOpen
+};
+__global__ void gzfile_part_serial_nodes_kernel(GzSerialParams S, GzPartSerialIn A);
+__global__ void gzfile_part_serial_from_kernel(GzSerialParams S, GzPartSerialIn A, const uint32_t *jump);
+__global__ void gzfile_part_serial_link_kernel(GzFileParams P, const uint32_t *verdict, uint32_t inside, uint32_t final_in);
+__global__ void gzfile_part_serial_stop_kernel(GzFileParams P, GzSerialParams S);
+__global__ void gzfile_part_serial_slots_kernel(GzFileParams P, GzSerialParams S, uint32_t n_dec, uint64_t total);
+
 // The seek index of a gzip FILE (gzfile_seek_kernels.hip; flate_hip_gzfile_seek_index / _ranges; the rule and the
 // index's layout: gzfile_seek_rule.h).  Locate, select, layout, compose, resolve, check, TAIL and the gather are the
 // kernels above, unchanged: they see the file's units as the units of one stream.

@@ -697,10 +697,18 @@ class GzFilePartsCalls:
     that its marshalling has its own recorded scenarios (tests/engine_trace_gzfile_parts.py) beside the ones of the
     methods that were there before (tests/engine_trace.py)."""
 
-    def open_gzfile_reader(self, device=False):
+    def open_gzfile_reader(self, device=False, serial_max=0):
         """A gzip FILE of any members read in parts through bounded buffers at gzfile_read's speed
-        (flate_hip_gzfile_reader_*): see GzFileReader.  device: every part and every output is a torch CUDA tensor."""
-        return GzFileReader(self, device)
+        (flate_hip_gzfile_reader_*): see GzFileReader.  device: every part and every output is a torch CUDA tensor.
+        serial_max: GzFileReader.set_serial_max on the fresh handle (0, the default: no call is made)."""
+        r = GzFileReader(self, device)
+        if serial_max:
+            try:
+                r.set_serial_max(serial_max)
+            except Exception:
+                r.close()
+                raise
+        return r
 
 
 class OneWriterCalls:
@@ -1557,7 +1565,18 @@ class GzFileReader:
     the last read left unused; the bytes are out[:out_len]; rc 0 = go on, 1 = the end of the file, -2 = not even the
     first unit fits (out_len: its size; nothing changed), -4 / -7 / -6 = the file's error, sticky, with the three words
     counted over the FILE.  out=None behaves as OneReader's.  The unit rule and "one_unit_max" are the engine's at
-    open; "gzfile_serial_max" is not used."""
+    open; the engine's option "gzfile_serial_max" is not used: the reader has a setting of its own.
+    set_serial_max(S), on a fresh reader (behind open or reset, before a read has consumed a byte; reset keeps it): with
+    S >= 1 a member that lies whole inside a part, fits in S bytes, decodes cleanly and inflates to at most out_cap
+    bytes is ONE unit, decoded with all other such members of the read by one batch of the batch decoders -- no
+    bit-offset search, no symbolic pass; every other member, and the member continued from the last part, is cut into
+    units as with S = 0.  A member that the part cuts but that could still fit in S bytes ends the read in front of its
+    header (in_used is the header's offset) so that the next part takes it whole; if it is the part's first member it
+    is read through units, so no part needs a minimum size.  Bytes, verdicts and the sum of in_used are the same for
+    every S; n_units and in_used of a single read depend on it.  last_route() -> (serial_members, open_stop, find_from)
+    of the last read that ran a discovery: the whole members among the units it delivered, whether its chain ended in
+    front of a member that more bytes could make whole, and the part offset the bit-offset search started at
+    (len(part): none ran; 0 with S = 0)."""
 
     def __init__(self, eng, device=False):
         self._eng, self._L = eng, eng._L
@@ -1591,6 +1610,17 @@ class GzFileReader:
     def reset(self):
         """A fresh file on the same handle: same side, same options."""
         self._eng._check(self._L.flate_hip_gzfile_reader_reset(self._h))
+
+    def set_serial_max(self, serial_max):
+        """Members of at most serial_max bytes that lie whole inside a part are decoded whole (0: none; at most
+        2^28 - 1).  Only on a fresh reader: FlateError(E_INVALID) otherwise."""
+        self._eng._check(self._L.flate_hip_gzfile_reader_set_serial_max(self._h, int(serial_max)))
+
+    def last_route(self):
+        """(serial_members, open_stop, find_from) of the last read that ran a discovery (the class docstring)."""
+        sm, os_, ff = C.c_uint32(0), C.c_uint32(0), C.c_uint64(0)
+        self._eng._check(self._L.flate_hip_gzfile_reader_last_route(self._h, C.byref(sm), C.byref(os_), C.byref(ff)))
+        return int(sm.value), int(os_.value), int(ff.value)
 
     def close(self):
         if self._h:

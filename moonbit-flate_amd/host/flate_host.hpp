@@ -964,11 +964,17 @@ class OneReader {
 // OneReader's, and so is the grain: the output piece grows to a first unit that does not fit, the input piece (doubled)
 // when it is full and holds no complete unit.  Bytes and errors come out as Reader's: data first, the error (ioeof at the
 // file's end) with the last bytes; a corrupt file reports the member's FILE offset, and failure() holds the other words.
+// set_serial_max(S) (flate_hip_gzfile_reader_set_serial_max): members of at most S bytes that lie whole inside an input
+// piece are decoded whole, by one batch per step; only before the first step of a file, and reset keeps it.
 class GzFileReader {
  public:
   struct Failure {
     uint32_t bad_member = 0xffffffffu;
     int64_t err_off = -1, stream_err_off = -1;
+  };
+  struct Route {  // flate_hip_gzfile_reader_last_route
+    uint32_t serial_members = 0, open_stop = 0;
+    uint64_t find_from = 0;
   };
   GzFileReader(ByteSource &r, Engine &e, size_t in_piece = 1u << 24, size_t out_piece = 1u << 26)
       : r_(&r), e_(e), in_piece_(in_piece < 4096 ? 4096 : in_piece), out_piece_(out_piece < 1 ? 1 : out_piece) {}
@@ -986,8 +992,25 @@ class GzFileReader {
     len_ = 0;
     pos_ = 0;
     members_ = 0;
+    serial_members_ = 0;
+    begun_ = false;
     fail_ = Failure();
     err_ = std::nullopt;
+  }
+
+  // S = 0 .. 2^28 - 1, before the first step of the file (after construction or reset): false otherwise, and nothing
+  // changes.  It reaches the handle in the first step that decodes.
+  bool set_serial_max(uint64_t serial_max) {
+    if (begun_ || serial_max > (1ull << 28) - 1) return false;
+    serial_max_ = serial_max;
+    serial_dirty_ = true;
+    return true;
+  }
+  // what the last step's call did (zeros before the first)
+  Route last_route() const {
+    Route t;
+    if (h_) (void)flate_hip_gzfile_reader_last_route(h_, &t.serial_members, &t.open_stop, &t.find_from);
+    return t;
   }
 
   std::pair<int, Err> read(uint8_t *p, size_t n) {
@@ -1010,6 +1033,7 @@ class GzFileReader {
   size_t resident_bytes() const { return in_.capacity() + data_.capacity(); }
   uint64_t calls() const { return calls_; }
   uint64_t members() const { return members_; }  // members whose trailers were judged good so far
+  uint64_t serial_members() const { return serial_members_; }  // ... of which delivered whole (set_serial_max)
   const Failure &failure() const { return fail_; }
 
  private:
@@ -1034,6 +1058,15 @@ class GzFileReader {
       }
       fresh_ = false;
     }
+    if (serial_dirty_) {  // (the handle is fresh: nothing of this file has been decoded)
+      const int rc = flate_hip_gzfile_reader_set_serial_max(h_, serial_max_);
+      if (rc != 0) {
+        err_ = make_error(e_, rc);
+        return;
+      }
+      serial_dirty_ = false;
+    }
+    begun_ = true;
     bool stalled = false;  // the source gave no byte and no error: decode what is here, do not ask again in this step
     while (!src_end_ && !stalled && in_.size() < in_piece_) {
       const size_t at = in_.size();
@@ -1064,6 +1097,7 @@ class GzFileReader {
     }
     len_ = (size_t)got;
     members_ += members;
+    if (serial_max_ && (got || used)) serial_members_ += last_route().serial_members;
     in_.erase(in_.begin(), in_.begin() + (size_t)used);
     if (rc < 0) fail_ = f;
     if (rc == FLATE_HIP_STREAM_END) err_ = ioeof();
@@ -1085,7 +1119,9 @@ class GzFileReader {
   bool src_end_ = false;
   std::vector<uint8_t> data_;  // the output piece; its first len_ bytes are decoded and not all handed out yet
   size_t len_ = 0, pos_ = 0;
-  uint64_t calls_ = 0, members_ = 0;
+  uint64_t calls_ = 0, members_ = 0, serial_members_ = 0;
+  uint64_t serial_max_ = 0;
+  bool serial_dirty_ = false, begun_ = false;
   Failure fail_;
   Err err_;
 };
