@@ -1308,7 +1308,8 @@ int flate_hip_gzfile_last_route(const flate_hip_ctx *ctx, uint32_t *serial_membe
  * flate_hip_gzfile_reader reads a file of ANY members through two bounded buffers: every call is flate_hip_gzfile_read
  * on the part of the file it is given -- its units cross member boundaries inside the part, the trailers of the members
  * that end in it are judged in it -- and between two calls the handle holds where the file stands (the rule:
- * csrc/gzfile_parts_rule.h; the part's kernels: csrc/gzfile_parts_kernels.hip).
+ * csrc/gzfile_parts_rule.h; the chain's kernels are the whole call's, csrc/gzfile_kernels.hip, which run the whole file
+ * as the part that is final and starts at a BOUNDARY; a part's decode words: csrc/gzfile_parts_kernels.hip).
  *
  * open: flags is 0 or FLATE_HIP_DEVICE_PTRS (in and out of every read are device buffers); anything else, or a NULL ctx
  * or result pointer, is FLATE_HIP_E_INVALID before any HIP call.  The handle records "one_stored_units" and
@@ -1365,9 +1366,10 @@ int flate_hip_gzfile_last_route(const flate_hip_ctx *ctx, uint32_t *serial_membe
  *   trailer, where out[*out_len, planned total) is unspecified.  Per call the host waits for the discovery's two
  *   read-backs and one read-back of the result words.
  *   SHORT MEMBERS WHOLE (flate_hip_gzfile_reader_set_serial_max, S >= 1; the rule: csrc/gzfile_parts_serial_rule.h, the
- *   kernels: csrc/gzfile_parts_serial_kernels.hip).  The ctx option "gzfile_serial_max" is ignored by the reader: the
- *   setting is the handle's.  With S = 0, the default, a call launches exactly what is described above.  With S >= 1 a
- *   member that lies whole inside the part, fits in S bytes and decodes cleanly is ONE unit: it is never searched for
+ *   kernels: csrc/gzfile_parts_serial_kernels.hip, which run the whole call's phase 1 too).
+ *   The ctx option "gzfile_serial_max" is ignored by the reader: the setting is the handle's.
+ *   With S = 0, the default, a call launches exactly what is described above.  With S >= 1 a member that lies whole
+ *   inside the part, fits in S bytes and decodes cleanly is ONE unit: it is never searched for
  *   block headers and never walked symbolically, and the call decodes all such members with one batch of the batch
  *   decoders, in front of the rounds (counted in FLATE_HIP_STAGE_INFLATE).  Every offset p that passes the header rule
  *   over in[p, in_len) gets the serial range of flate_hip_gzfile_read's option with the PART's in_len, E = min(in_len -

@@ -27,6 +27,7 @@ GROUPS = {  # which sources a kernel family's measurements depend on (besides th
     "checksum": ["checksum.hip", "checksum_clip.h", "block_scan.h", "carve.h"],
     "frame": ["frame_kernels.hip", "one_writer_kernels.hip", "one_writer_rule.h", "bgzf_kernels.hip", "bgzf_range_kernels.hip", "bgzf_rule.h", "bgzf_range_rule.h",
               "gzip_kernels.hip", "gzip_rule.h", "gzfile_kernels.hip", "gzfile_rule.h", "gzfile_serial_kernels.hip", "gzfile_serial_rule.h", "gzfile_seek_kernels.hip", "gzfile_seek_rule.h",
+              "gzfile_parts_kernels.hip", "gzfile_parts_rule.h", "gzfile_parts_serial_kernels.hip", "gzfile_parts_serial_rule.h",
               "zip_kernels.hip", "zip_kernels.h", "zip_rule.h", "zip_units_kernels.hip", "zip_units_rule.h", "flate_api_zip.hip", "checksum.hip", "checksum_clip.h", "flate_api_inflate.hip", "flate_api_units.hip",
               "inflate_route.h", "flate_api_deflate.hip", "deflate_plan.h", "block_scan.h",
               "chain_kernels.hip", "chain_walk.h", "chain_rule.h", "carve.h", "unit_rounds.h", "unit_discovery.h", "unit_discovery_rule.h"],

@@ -1205,13 +1205,20 @@ int flate_hip_one_reader_read(flate_hip_one_reader *r, const uint8_t *in, uint64
 namespace {
 
 // A PART of a file read in parts (flate_hip_gzfile_reader_read): the handle's unit rule, where the last call stopped
-// (inside a member at bit b0, or at a header), whether the file ends with the part, and the history in front of it.
+// (inside a member at bit b0, or at a header), whether the file ends with the part, the history in front of it, and --
+// with whole members -- the handle's S and the call's out_cap.
 struct GzPartIn {
   uint64_t unit_max;
   uint32_t stored_units;
   uint32_t inside, b0, final_in;
   uint64_t hist;
+  uint64_t serial_max, out_cap;
 };
+// the kernels' word for it; the whole file is the part that is final and starts at a BOUNDARY (flate_kernels.h)
+GzFileMode gzfile_mode(const GzPartIn *part, const uint32_t *verdict) {
+  if (!part) return GzFileMode{0u, 0u, 1u, 0ull, verdict};
+  return GzFileMode{1u, part->inside, part->final_in, part->hist, verdict};
+}
 // What the discovery's last read-back fetches beside the result words H / G.  The whole file: member_out, the members'
 // places in the output (n_b + 2 entries of which G.n_members + 1 count).  A part: the INDEX -- unit_bit, out_off and
 // u_start (cap + 1 entries each) in one vector of 64-bit words, one array behind the other, and u_final (cap).
@@ -1233,16 +1240,15 @@ struct GzSerialIn {
 // The chain of a file's discovery, behind the counts na / nb of the two lists (unit_discovery.h): the size rule, the
 // carve of c->d_gzfile, the fills and the B nodes' bits, the probe of every node, link, rounds, finish, out-scan, the
 // member scan, the tail probe, the member words and ONE read-back of H / G with what `back` names.
-//   part  the chain's root and hop are the part's: gzfile_part_link_kernel / _finish_kernel / _rel_kernel, FIND in its
-//         PARTS build
+//   part  link, finish and rel run in the part's form (GzFileMode), FIND in its PARTS build
 //   ser   List B was filled and sized by phase 1, whose arrays hold hdr_off; FIND's fill runs over the suffix PA names
 //         and one small kernel moves its bits to the file's origin; a whole B node is parked at the raw stream's end for
 //         PROBE and gets its phase-1 record back behind it; the marks between finish and out-scan, the list of whole
 //         members at the end, SH in the read-back
-//   both  a part of a handle with flate_hip_gzfile_reader_set_serial_max: the part's root, finish and rel kernels, the
-//         link with the OPEN stop; FIND's build is the PARTS one only INSIDE a member (then over the whole part); no list
-//         of whole members -- the call lays out its batch behind its plan -- but whether the chain ended in front of
-//         an OPEN member, and the per-unit marks in the read-back
+//   both  a part of a handle with flate_hip_gzfile_reader_set_serial_max: the link stops in front of an OPEN member;
+//         FIND's build is the PARTS one only INSIDE a member (then over the whole part); no list of whole members -- the
+//         call lays out its batch behind its plan -- but whether the chain ended in front of an OPEN member, and the
+//         per-unit marks in the read-back
 int gzfile_chain(flate_hip_ctx *c, GzFileParams &P, OneParams &PA, GzipParams &PB, uint32_t na, uint32_t nb,
                  const GzPartIn *part, const GzSerialIn *ser, OneHead &H, GzFileHead &G, const GzFileBack &back) {
   int rc;
@@ -1290,33 +1296,18 @@ int gzfile_chain(flate_hip_ctx *c, GzFileParams &P, OneParams &PA, GzipParams &P
   }
   if (n) one_probe_launch(c, C.cap, P.O, 0u);
   if (ser && nb) hipLaunchKernelGGL(gzfile_serial_keep_kernel, dim3((nb + 255) / 256), dim3(256), 0, c->stream, P, ser->S);
-  auto link = [&](dim3 g) {
-    if (part && ser)
-      hipLaunchKernelGGL(gzfile_part_serial_link_kernel, g, dim3(256), 0, c->stream, P, ser->verdict, part->inside,
-                         part->final_in);
-    else if (part)
-      hipLaunchKernelGGL(gzfile_part_link_kernel, g, dim3(256), 0, c->stream, P, part->inside, part->final_in);
-    else
-      hipLaunchKernelGGL(gzfile_link_kernel, g, dim3(256), 0, c->stream, P);
-  };
-  auto finish = [&](dim3 g) {
-    if (part)
-      hipLaunchKernelGGL(gzfile_part_finish_kernel, g, dim3(256), 0, c->stream, P, part->final_in);
-    else
-      hipLaunchKernelGGL(gzfile_finish_kernel, g, dim3(256), 0, c->stream, P);
-  };
+  const GzFileMode M = gzfile_mode(part, ser ? ser->verdict : nullptr);
+  auto link = [&](dim3 g) { hipLaunchKernelGGL(gzfile_link_kernel, g, dim3(256), 0, c->stream, P, M); };
+  auto finish = [&](dim3 g) { hipLaunchKernelGGL(gzfile_finish_kernel, g, dim3(256), 0, c->stream, P, M); };
   auto marks = [&](uint32_t node_blocks) {
     if (ser) hipLaunchKernelGGL(gzfile_serial_marks_kernel, dim3(node_blocks), dim3(256), 0, c->stream, P, ser->S);
   };
   auto behind = [&](uint32_t node_blocks) {
     hipLaunchKernelGGL(gzfile_members_kernel, dim3(1), dim3(1024), 0, c->stream, P);
     one_probe_launch(c, 1, P.O, 1u);
-    if (part)
-      hipLaunchKernelGGL(gzfile_part_rel_kernel, dim3(node_blocks), dim3(256), 0, c->stream, P, part->hist);
-    else
-      hipLaunchKernelGGL(gzfile_rel_kernel, dim3(node_blocks), dim3(256), 0, c->stream, P);
+    hipLaunchKernelGGL(gzfile_rel_kernel, dim3(node_blocks), dim3(256), 0, c->stream, P, M);
     if (ser && part) hipLaunchKernelGGL(gzfile_part_serial_stop_kernel, dim3(1), dim3(64), 0, c->stream, P, ser->S);
-    else if (ser) hipLaunchKernelGGL(gzfile_serial_list_kernel, dim3(1), dim3(1024), 0, c->stream, P, ser->S);
+    else if (ser) hipLaunchKernelGGL(gzfile_serial_list_kernel, dim3(1), dim3(1024), 0, c->stream, P, ser->S, 1u, 0u, 0ull);
   };
   return unit_chain(c, P.O, link, finish, marks, behind, H, G, P.gh, [&]() -> int {
     if (ser) HIP_TRY(c, hipMemcpyAsync(&ser->SH, ser->S.head, sizeof ser->SH, hipMemcpyDeviceToHost, c->stream));
@@ -1388,10 +1379,8 @@ int gzfile_discover(flate_hip_ctx *c, const uint8_t *d_in, uint64_t in_len, cons
   P.O.unit_max = part ? part->unit_max : c->one_unit_max;
   P.O.stored_units = part ? part->stored_units : c->one_stored_units;
   find_params(PA, P.O, head_a);
-  if (part)
-    hipLaunchKernelGGL(gzfile_part_init_kernel, dim3(1), dim3(64), 0, c->stream, P.O.one, d_in, in_len, part->inside, part->b0);
-  else
-    hipLaunchKernelGGL(gzfile_init_kernel, dim3(1), dim3(64), 0, c->stream, P.O.one, in_len);
+  hipLaunchKernelGGL(gzfile_init_kernel, dim3(1), dim3(64), 0, c->stream, P.O.one, d_in, in_len, gzfile_mode(part, nullptr),
+                     part ? part->b0 : 0u);
   find_count(c, PA, part != nullptr);
   hipLaunchKernelGGL(gzip_count_kernel, dim3(C.n_tiles), dim3(256), 0, c->stream, PB);
   hipLaunchKernelGGL(chain_scan_kernel, dim3(1), dim3(1024), 0, c->stream, PB.C);
@@ -1403,16 +1392,22 @@ int gzfile_discover(flate_hip_ctx *c, const uint8_t *d_in, uint64_t in_len, cons
   return !part && G.n_members > P.n_b ? FLATE_HIP_E_INTERNAL : FLATE_HIP_OK;
 }
 
-// The same discovery with the option "gzfile_serial_max" (S >= 1; gzfile_serial_rule.h, gzfile_serial_kernels.hip).
+// The same discovery with short members decoded WHOLE (S >= 1: the option "gzfile_serial_max", or -- part != null --
+// flate_hip_gzfile_reader_set_serial_max; gzfile_serial_rule.h, gzfile_parts_serial_rule.h and their kernel files).
 // PHASE 1 over List B alone: count, scan, a read-back of the B count, fill, the serial ranges, ONE size-only launch of
-// the batch decoders over all B candidates, the whole test with the hop links, pointer doubling over those links, and
+// the batch decoders over all B candidates, the verdicts with the hop links, pointer doubling over those links, and
 // a read-back of find_from.  PHASE 2, only when find_from < in_len: FIND over in[find_from, in_len) -- the pass runs on
 // d_in + find_from with a FrameOne of its own, and one small kernel moves its bits to the file's origin -- and the
 // read-back of its count.  PROBE runs over all nodes; a whole B node is parked at the raw stream's end for it and gets
 // its phase-1 record back behind it.  Link, rounds, finish, the scans and the rel kernel are gzfile_discover's.  SH =
 // find_from and the whole members among the good units; S = their batch, on the device.
-int gzfile_discover_serial(flate_hip_ctx *c, const uint8_t *d_in, uint64_t in_len, OneHead &H, GzFileHead &G,
-                           GzFileParams &P, GzSerialParams &S, GzSerialHead &SH, std::vector<uint64_t> *mout) {
+// A PART differs in this: the root's verdict comes back with the B count (*root_bad: anything but 0 ends the discovery
+// there); the ranges end with the PART and the three verdicts are kept for the chain's link; INSIDE a member find_from
+// is 0 and FIND is its PARTS build over the whole part, whose candidate 0 is the chain's root; SH.pad = the chain
+// ended in front of an OPEN member, and there is no list of whole members.
+int gzfile_discover_serial(flate_hip_ctx *c, const uint8_t *d_in, uint64_t in_len, const GzPartIn *part, OneHead &H,
+                           GzFileHead &G, GzFileParams &P, GzSerialParams &S, GzSerialHead &SH, uint32_t *root_bad,
+                           const GzFileBack &back) {
   int rc;
   P = GzFileParams{};
   S = GzSerialParams{};
@@ -1432,15 +1427,19 @@ int gzfile_discover_serial(flate_hip_ctx *c, const uint8_t *d_in, uint64_t in_le
   });
   if (rc) return rc;
   BgzfHead *head_b = PB.C.head;
-  P.O.unit_max = c->one_unit_max;
-  P.O.stored_units = c->one_stored_units;
-  hipLaunchKernelGGL(gzfile_init_kernel, dim3(1), dim3(64), 0, c->stream, P.O.one, in_len);
+  P.O.unit_max = part ? part->unit_max : c->one_unit_max;
+  P.O.stored_units = part ? part->stored_units : c->one_stored_units;
+  hipLaunchKernelGGL(gzfile_init_kernel, dim3(1), dim3(64), 0, c->stream, P.O.one, d_in, in_len, gzfile_mode(part, nullptr),
+                     part ? part->b0 : 0u);
   hipLaunchKernelGGL(gzip_count_kernel, dim3(n_tiles), dim3(256), 0, c->stream, PB);
   hipLaunchKernelGGL(chain_scan_kernel, dim3(1), dim3(1024), 0, c->stream, PB.C);
   HIP_TRY(c, hipGetLastError());
   BgzfHead HB{};
+  FrameOne root{};
   HIP_TRY(c, hipMemcpyAsync(&HB, head_b, sizeof HB, hipMemcpyDeviceToHost, c->stream));
+  if (part) HIP_TRY(c, hipMemcpyAsync(&root, P.O.one, sizeof root, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
+  if (part && (*root_bad = root.bad)) return FLATE_HIP_OK;
   const uint32_t nb = HB.n_cand;
   if (nb > 0x7ffffff0u) return FLATE_HIP_E_TOO_LARGE;  // (the count saturates at 2^32 - 1)
   if ((rc = chain_size(PB.C, nb))) return rc;
@@ -1448,7 +1447,9 @@ int gzfile_discover_serial(flate_hip_ctx *c, const uint8_t *d_in, uint64_t in_le
   // PHASE 1
   uint64_t *hdr_off;
   InfParams I{};  // size-only: no output buffer, no slots
-  rc = carve(c, c->d_gzfile_serial, [&](Carve &k) {
+  GzPartSerialIn A{1u, 0u, ~0ull, nullptr};  // the whole file: the part that is final and starts at a BOUNDARY
+  if (part) A = GzPartSerialIn{part->final_in, part->inside, part->out_cap, nullptr};
+  rc = carve(c, part ? c->d_gzfile_parts_serial : c->d_gzfile_serial, [&](Carve &k) {
     k.take(hdr_off, (size_t)nb + 1);
     k.take(PB.cand_end, nb);
     k.take(S.pay_off, (size_t)nb + 1);
@@ -1459,6 +1460,7 @@ int gzfile_discover_serial(flate_hip_ctx *c, const uint8_t *d_in, uint64_t in_le
     k.take(I.used, nb);
     k.take(S.rec, nb);
     k.take(S.whole, nb);
+    if (part) k.take(A.verdict, nb);
     k.take(S.jump[0], (size_t)nb + 2);
     k.take(S.jump[1], (size_t)nb + 2);
     k.take(S.w_in_off, (size_t)nb + 1);
@@ -1473,13 +1475,14 @@ int gzfile_discover_serial(flate_hip_ctx *c, const uint8_t *d_in, uint64_t in_le
   P.n_b = nb;
   S.in = d_in;
   S.in_len = in_len;
-  S.serial_max = c->gzfile_serial_max;
+  S.serial_max = part ? part->serial_max : c->gzfile_serial_max;
   S.n_b = nb;
   S.hdr_off = hdr_off;
   S.status = I.status;
   S.out_len = I.out_len;
   S.used = I.used;
-  uint64_t find_from = in_len;  // (no candidate: no member at offset 0, nothing to search)
+  // (no candidate: no member at offset 0, nothing to search; INSIDE, the continued member is units)
+  uint64_t find_from = part && part->inside ? 0ull : in_len;
   if (nb) {
     const uint32_t b_blocks = (nb + 255u) / 256u, w_blocks = (uint32_t)(((uint64_t)nb + 2 + 255) / 256);
     // every range is at most S < 2^28 bytes: the sub-block decoder at any batch size, or -- switched off -- the scalar
@@ -1487,7 +1490,8 @@ int gzfile_discover_serial(flate_hip_ctx *c, const uint8_t *d_in, uint64_t in_le
     const uint64_t longest = in_len < S.serial_max ? in_len : S.serial_max;
     const InflateRoute route = inflate_route(c->inflate, c->num_cus, nb, longest, false, true);
     if (route.decoder == kDecodeSimt) {
-      c->hip_err = "gzfile discovery: a size-only pass was routed to the lane-per-stream decoder";
+      c->hip_err = part ? "gzfile reader: a size-only pass was routed to the lane-per-stream decoder"
+                        : "gzfile discovery: a size-only pass was routed to the lane-per-stream decoder";
       return FLATE_HIP_E_INTERNAL;
     }
     I.in = d_in;
@@ -1500,190 +1504,26 @@ int gzfile_discover_serial(flate_hip_ctx *c, const uint8_t *d_in, uint64_t in_le
     hipLaunchKernelGGL(gzfile_serial_ranges_kernel, dim3(b_blocks), dim3(256), 0, c->stream, S);
     HIP_TRY(c, hipGetLastError());
     if ((rc = launch_decoders(c, route, I, false))) return rc;
-    hipLaunchKernelGGL(gzfile_serial_nodes_kernel, dim3(w_blocks), dim3(256), 0, c->stream, S);
+    hipLaunchKernelGGL(gzfile_serial_nodes_kernel, dim3(w_blocks), dim3(256), 0, c->stream, S, A);
     int cur = 0;
     for (uint64_t s = 1; s < (uint64_t)nb + 2; s <<= 1, cur ^= 1)
       hipLaunchKernelGGL(gzfile_serial_round_kernel, dim3(w_blocks), dim3(256), 0, c->stream, S.jump[cur], S.jump[cur ^ 1],
                          nb + 2u);
-    hipLaunchKernelGGL(gzfile_serial_from_kernel, dim3(1), dim3(64), 0, c->stream, S, S.jump[cur]);
+    hipLaunchKernelGGL(gzfile_serial_from_kernel, dim3(1), dim3(64), 0, c->stream, S, A, S.jump[cur]);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipMemcpyAsync(&SH, S.head, sizeof SH, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     find_from = SH.find_from;
-    if (find_from > in_len) return FLATE_HIP_E_INTERNAL;
-  } else {
-    SH.find_from = in_len;
-    HIP_TRY(c, hipMemcpyAsync(S.head, &SH, sizeof SH, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));  // (SH is the caller's: the copy has read it)
-  }
-
-  // PHASE 2: FIND over the bytes from find_from on
-  uint32_t na = 0;
-  if (find_from < in_len) {
-    find_params(PA, P.O, head_a);
-    PA.C.in = d_in + find_from;
-    PA.C.in_len = in_len - find_from;
-    PA.one = one_a;
-    if ((rc = tiles_for(PA.C.in, 0, PA.C.in_len, &PA.C.n_tiles))) return rc;
-    if (PA.C.n_tiles > n_tiles + 1u) return FLATE_HIP_E_INTERNAL;
-    hipLaunchKernelGGL(gzfile_init_kernel, dim3(1), dim3(64), 0, c->stream, one_a, PA.C.in_len);
-    find_count(c, PA, false);
-    OneHead HA{};
-    if ((rc = find_counts_back(c, head_a, HA))) return rc;
-    na = HA.h.n_cand;
-  }
-  const GzSerialIn ser{S, SH, find_from};
-  GzFileBack back;
-  back.mout = mout;
-  if ((rc = gzfile_chain(c, P, PA, PB, na, nb, nullptr, &ser, H, G, back))) return rc;
-  if (G.n_members > nb || SH.n_whole > nb || SH.n_whole > G.n_members || SH.find_from != find_from)
-    return FLATE_HIP_E_INTERNAL;
-  return FLATE_HIP_OK;
-}
-
-// the discovery of flate_hip_gzfile_index / _read by the ctx's option, and what flate_hip_gzfile_last_route reports
-int gzfile_discover_routed(flate_hip_ctx *c, const uint8_t *d_in, uint64_t in_len, OneHead &H, GzFileHead &G,
-                           GzFileParams &P, GzSerialParams &S, GzSerialHead &SH, std::vector<uint64_t> *mout) {
-  c->gzfile_route[0] = c->gzfile_route[1] = 0;
-  c->gzfile_route_from = 0;
-  int rc;
-  if (!c->gzfile_serial_max) {
-    S = GzSerialParams{};
-    SH = GzSerialHead{};
-    GzFileBack back;
-    back.mout = mout;
-    if ((rc = gzfile_discover(c, d_in, in_len, nullptr, H, G, P, nullptr, back))) return rc;
-  } else if ((rc = gzfile_discover_serial(c, d_in, in_len, H, G, P, S, SH, mout))) {
-    return rc;
-  }
-  c->gzfile_route[0] = SH.n_whole;
-  c->gzfile_route[1] = G.n_members - SH.n_whole;
-  c->gzfile_route_from = SH.find_from;
-  return FLATE_HIP_OK;
-}
-
-// The discovery over one PART of a file with whole members (flate_hip_gzfile_reader_set_serial_max: S >= 1;
-// gzfile_parts_serial_rule.h, gzfile_parts_serial_kernels.hip): gzfile_discover_serial's two phases with the part's
-// root, verdicts and hop, then gzfile_chain with BOTH hooks.  PHASE 1 over the part's List B: the part's words, count,
-// scan, ONE read-back of the B count and the root's verdict (*root_bad: anything but 0 ends the discovery there), fill,
-// the serial ranges with the PART's in_len, ONE size-only launch of the batch decoders, the three verdicts with the
-// links of THE PARTS HOP, pointer doubling, find_from (INSIDE: 0) and its read-back.  PHASE 2, only when find_from <
-// in_len: FIND -- INSIDE a member its PARTS build over the whole part, whose candidate 0 is the chain's root; at a
-// BOUNDARY the ordinary build over in[find_from, in_len), which starts at a member's header -- and the read-back of
-// its count.  SH.pad = the chain ended in front of an OPEN member; S = phase 1's arrays, on the device.
-int gzfile_discover_part_serial(flate_hip_ctx *c, const uint8_t *d_in, uint64_t in_len, const GzPartIn &part, uint64_t serial_max,
-                                uint64_t out_cap, OneHead &H, GzFileHead &G, GzFileParams &P, GzSerialParams &S,
-                                GzSerialHead &SH, uint32_t *root_bad, const GzFileBack &back) {
-  int rc;
-  P = GzFileParams{};
-  S = GzSerialParams{};
-  SH = GzSerialHead{};
-  OneParams PA{};
-  GzipParams PB{};
-  ChainParams &C = P.O.C;
-  C.in = d_in;
-  C.in_len = in_len;
-  if ((rc = tiles_for(d_in, 0, in_len, &C.n_tiles))) return rc;
-  const uint32_t n_tiles = C.n_tiles;
-  OneHead *head_a;
-  FrameOne *one_a;
-  rc = gzfile_tiles_carve(c, P, PA, PB, head_a, (size_t)n_tiles + 1, [&](Carve &k) {  // (a suffix at another alignment:
-    k.take(one_a, 1);                                                                  // at most one tile more)
-    k.take(S.head, 1);
-  });
-  if (rc) return rc;
-  BgzfHead *head_b = PB.C.head;
-  P.O.unit_max = part.unit_max;
-  P.O.stored_units = part.stored_units;
-  hipLaunchKernelGGL(gzfile_part_init_kernel, dim3(1), dim3(64), 0, c->stream, P.O.one, d_in, in_len, part.inside, part.b0);
-  hipLaunchKernelGGL(gzip_count_kernel, dim3(n_tiles), dim3(256), 0, c->stream, PB);
-  hipLaunchKernelGGL(chain_scan_kernel, dim3(1), dim3(1024), 0, c->stream, PB.C);
-  HIP_TRY(c, hipGetLastError());
-  BgzfHead HB{};
-  FrameOne root{};
-  HIP_TRY(c, hipMemcpyAsync(&HB, head_b, sizeof HB, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(&root, P.O.one, sizeof root, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  if ((*root_bad = root.bad)) return FLATE_HIP_OK;
-  const uint32_t nb = HB.n_cand;
-  if (nb > 0x7ffffff0u) return FLATE_HIP_E_TOO_LARGE;  // (the count saturates at 2^32 - 1)
-  if ((rc = chain_size(PB.C, nb))) return rc;
-
-  // PHASE 1
-  uint64_t *hdr_off;
-  InfParams I{};  // size-only: no output buffer, no slots
-  GzPartSerialIn A{part.final_in, part.inside, out_cap, nullptr};
-  rc = carve(c, c->d_gzfile_parts_serial, [&](Carve &k) {
-    k.take(hdr_off, (size_t)nb + 1);
-    k.take(PB.cand_end, nb);
-    k.take(S.pay_off, (size_t)nb + 1);
-    k.take(S.pay_end, nb);
-    k.take(I.out_len, nb);
-    k.take(I.status, nb);
-    k.take(I.err_off, nb);
-    k.take(I.used, nb);
-    k.take(S.rec, nb);
-    k.take(S.whole, nb);
-    k.take(A.verdict, nb);
-    k.take(S.jump[0], (size_t)nb + 2);
-    k.take(S.jump[1], (size_t)nb + 2);
-    k.take(S.w_in_off, (size_t)nb + 1);
-    k.take(S.w_in_end, nb);
-    k.take(S.w_out_off, (size_t)nb + 1);
-    k.take(S.w_size, nb);
-    k.take(S.w_unit, nb);
-  });
-  if (rc) return rc;
-  PB.C.cand_off = hdr_off;
-  P.hdr_off = hdr_off;
-  P.n_b = nb;
-  S.in = d_in;
-  S.in_len = in_len;
-  S.serial_max = serial_max;
-  S.n_b = nb;
-  S.hdr_off = hdr_off;
-  S.status = I.status;
-  S.out_len = I.out_len;
-  S.used = I.used;
-  uint64_t find_from = part.inside ? 0ull : in_len;  // (no candidate: only INSIDE, where the continued member is units)
-  if (nb) {
-    const uint32_t b_blocks = (nb + 255u) / 256u, w_blocks = (uint32_t)(((uint64_t)nb + 2 + 255) / 256);
-    const uint64_t longest = in_len < S.serial_max ? in_len : S.serial_max;
-    const InflateRoute route = inflate_route(c->inflate, c->num_cus, nb, longest, false, true);
-    if (route.decoder == kDecodeSimt) {
-      c->hip_err = "gzfile reader: a size-only pass was routed to the lane-per-stream decoder";
-      return FLATE_HIP_E_INTERNAL;
-    }
-    I.in = d_in;
-    I.in_off = S.pay_off;
-    I.in_end = S.pay_end;
-    I.n_streams = nb;
-    I.in_len = in_len;
-    I.size_only = 1u;
-    hipLaunchKernelGGL(gzip_fill_kernel, dim3(n_tiles), dim3(256), 0, c->stream, PB);
-    hipLaunchKernelGGL(gzfile_serial_ranges_kernel, dim3(b_blocks), dim3(256), 0, c->stream, S);
-    HIP_TRY(c, hipGetLastError());
-    if ((rc = launch_decoders(c, route, I, false))) return rc;
-    hipLaunchKernelGGL(gzfile_part_serial_nodes_kernel, dim3(w_blocks), dim3(256), 0, c->stream, S, A);
-    int cur = 0;
-    for (uint64_t s = 1; s < (uint64_t)nb + 2; s <<= 1, cur ^= 1)
-      hipLaunchKernelGGL(gzfile_serial_round_kernel, dim3(w_blocks), dim3(256), 0, c->stream, S.jump[cur], S.jump[cur ^ 1],
-                         nb + 2u);
-    hipLaunchKernelGGL(gzfile_part_serial_from_kernel, dim3(1), dim3(64), 0, c->stream, S, A, S.jump[cur]);
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipMemcpyAsync(&SH, S.head, sizeof SH, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    find_from = SH.find_from;
-    if (find_from > in_len || (part.inside && find_from)) return FLATE_HIP_E_INTERNAL;
+    if (find_from > in_len || (part && part->inside && find_from)) return FLATE_HIP_E_INTERNAL;
   } else {
     SH.find_from = find_from;
     HIP_TRY(c, hipMemcpyAsync(S.head, &SH, sizeof SH, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));  // (SH is the caller's: the copy has read it)
   }
 
-  // PHASE 2
+  // PHASE 2: FIND over the bytes from find_from on (a member's header stands there), or over the part INSIDE a member
   uint32_t na = 0;
-  const bool parts_find = part.inside != 0u;
+  const bool parts_find = part && part->inside;
   if (find_from < in_len) {
     find_params(PA, P.O, head_a);
     if (!parts_find) {
@@ -1692,7 +1532,8 @@ int gzfile_discover_part_serial(flate_hip_ctx *c, const uint8_t *d_in, uint64_t 
       PA.one = one_a;
       if ((rc = tiles_for(PA.C.in, 0, PA.C.in_len, &PA.C.n_tiles))) return rc;
       if (PA.C.n_tiles > n_tiles + 1u) return FLATE_HIP_E_INTERNAL;
-      hipLaunchKernelGGL(gzfile_init_kernel, dim3(1), dim3(64), 0, c->stream, one_a, PA.C.in_len);
+      hipLaunchKernelGGL(gzfile_init_kernel, dim3(1), dim3(64), 0, c->stream, one_a, PA.C.in, PA.C.in_len,
+                         gzfile_mode(nullptr, nullptr), 0u);
     }
     find_count(c, PA, parts_find);
     OneHead HA{};
@@ -1702,8 +1543,30 @@ int gzfile_discover_part_serial(flate_hip_ctx *c, const uint8_t *d_in, uint64_t 
   GzSerialIn ser{S, SH, find_from};
   ser.verdict = A.verdict;
   ser.parts_find = parts_find;
-  if ((rc = gzfile_chain(c, P, PA, PB, na, nb, &part, &ser, H, G, back))) return rc;
-  if (SH.find_from != find_from || SH.pad > 1u) return FLATE_HIP_E_INTERNAL;
+  if ((rc = gzfile_chain(c, P, PA, PB, na, nb, part, &ser, H, G, back))) return rc;
+  if (SH.find_from != find_from) return FLATE_HIP_E_INTERNAL;
+  if (part ? SH.pad > 1u : G.n_members > nb || SH.n_whole > nb || SH.n_whole > G.n_members) return FLATE_HIP_E_INTERNAL;
+  return FLATE_HIP_OK;
+}
+
+// the discovery of flate_hip_gzfile_index / _read by the ctx's option, and what flate_hip_gzfile_last_route reports
+int gzfile_discover_routed(flate_hip_ctx *c, const uint8_t *d_in, uint64_t in_len, OneHead &H, GzFileHead &G,
+                           GzFileParams &P, GzSerialParams &S, GzSerialHead &SH, std::vector<uint64_t> *mout) {
+  c->gzfile_route[0] = c->gzfile_route[1] = 0;
+  c->gzfile_route_from = 0;
+  int rc;
+  GzFileBack back;
+  back.mout = mout;
+  if (!c->gzfile_serial_max) {
+    S = GzSerialParams{};
+    SH = GzSerialHead{};
+    if ((rc = gzfile_discover(c, d_in, in_len, nullptr, H, G, P, nullptr, back))) return rc;
+  } else if ((rc = gzfile_discover_serial(c, d_in, in_len, nullptr, H, G, P, S, SH, nullptr, back))) {
+    return rc;
+  }
+  c->gzfile_route[0] = SH.n_whole;
+  c->gzfile_route[1] = G.n_members - SH.n_whole;
+  c->gzfile_route_from = SH.find_from;
   return FLATE_HIP_OK;
 }
 
@@ -1893,7 +1756,7 @@ int flate_hip_gzfile_read(flate_hip_ctx *c, const uint8_t *in, uint64_t in_len, 
     }
     // the pieces and the seeds of the round (every member's first unit is one)
     auto pieces = [&](uint32_t, uint32_t count) {
-      hipLaunchKernelGGL(gzfile_pieces_kernel, dim3((count + 1u + 255u) / 256u), dim3(256), 0, c->stream, GD);
+      hipLaunchKernelGGL(gzfile_pieces_kernel, dim3((count + 1u + 255u) / 256u), dim3(256), 0, c->stream, GD, 0ull);
       return FLATE_HIP_OK;
     };
     // DECODE: the round's units as pieces with dictionaries and their own ends, through the lane-per-stream decoder
@@ -2080,7 +1943,7 @@ int flate_hip_gzfile_seek_index(flate_hip_ctx *c, const uint8_t *in, uint64_t in
       return FLATE_HIP_OK;
     };
     auto seeds = [&](uint32_t, uint32_t count) {
-      hipLaunchKernelGGL(gzfile_pieces_kernel, dim3((count + 1u + 255u) / 256u), dim3(256), 0, c->stream, GD);
+      hipLaunchKernelGGL(gzfile_pieces_kernel, dim3((count + 1u + 255u) / 256u), dim3(256), 0, c->stream, GD, 0ull);
       return FLATE_HIP_OK;
     };
     // PACK: R[i] of the round's window-bearing points -> their blocks, which lie one behind the other in `windows`
@@ -2218,7 +2081,7 @@ int flate_hip_gzfile_ranges(flate_hip_ctx *c, const uint8_t *in, uint64_t in_len
     HIP_TRY(c, hipMemcpyAsync(d_end, end, (size_t)nr * 8, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipMemsetAsync(Q.diff, 0, ((size_t)n + 1) * 4, c->stream));
     HIP_TRY(c, hipMemsetAsync(GS.bad_member, 0xff, 4, c->stream));  // none
-    hipLaunchKernelGGL(gzfile_init_kernel, dim3(1), dim3(64), 0, c->stream, d_one, in_len);
+    hipLaunchKernelGGL(gzfile_init_kernel, dim3(1), dim3(64), 0, c->stream, d_one, d_in, in_len, gzfile_mode(nullptr, nullptr), 0u);
     hipLaunchKernelGGL(gzfile_seek_members_kernel, dim3((m + 255u) / 256u), dim3(256), 0, c->stream, GS);
     hipLaunchKernelGGL(gzfile_seek_rel_kernel, dim3((n + 1u + 255u) / 256u), dim3(256), 0, c->stream, GS);
     hipLaunchKernelGGL(one_seek_locate_kernel, dim3((nr + 255u) / 256u), dim3(256), 0, c->stream, Q);
@@ -2413,7 +2276,7 @@ int flate_hip_gzfile_reader_read(flate_hip_gzfile_reader *r, const uint8_t *in, 
     if ((rc = stage_input(c, in, in_len, r->flags, &d_in))) return rc;
     // the history in front of the part, as far as the distance rule can see it (it saturates at the window)
     const uint64_t hist = !s.inside ? 0ull : s.produced < (uint64_t)kWinEntries ? s.produced : (uint64_t)kWinEntries;
-    const GzPartIn part{r->unit_max, r->stored_units, s.inside, s.b0, fin ? 1u : 0u, hist};
+    const GzPartIn part{r->unit_max, r->stored_units, s.inside, s.b0, fin ? 1u : 0u, hist, r->serial_max, out_cap};
     OneHead H{};
     GzFileHead G{};
     GzFileParams P{};
@@ -2429,7 +2292,7 @@ int flate_hip_gzfile_reader_read(flate_hip_gzfile_reader *r, const uint8_t *in, 
     std::vector<uint32_t> u_whole;
     if (S) {
       back.u_whole = &u_whole;
-      rc = gzfile_discover_part_serial(c, d_in, in_len, part, S, out_cap, H, G, P, SP, SH, &root_bad, back);
+      rc = gzfile_discover_serial(c, d_in, in_len, &part, H, G, P, SP, SH, &root_bad, back);
     } else {
       rc = gzfile_discover(c, d_in, in_len, &part, H, G, P, &root_bad, back);
     }
@@ -2518,7 +2381,7 @@ int flate_hip_gzfile_reader_read(flate_hip_gzfile_reader *r, const uint8_t *in, 
     GD.n_good = plan.n_del;
     if ((rc = unit_window_seed(c, D, st->window))) return rc;
     auto pieces = [&](uint32_t, uint32_t count) {
-      hipLaunchKernelGGL(gzfile_part_pieces_kernel, dim3((count + 1u + 255u) / 256u), dim3(256), 0, c->stream, GD, hist);
+      hipLaunchKernelGGL(gzfile_pieces_kernel, dim3((count + 1u + 255u) / 256u), dim3(256), 0, c->stream, GD, hist);
       return FLATE_HIP_OK;
     };
     auto decode = [&](uint32_t, uint32_t count) {
@@ -2529,7 +2392,7 @@ int flate_hip_gzfile_reader_read(flate_hip_gzfile_reader *r, const uint8_t *in, 
       // the WHOLE members: ONE batch of independent streams straight into their places, IN FRONT of the rounds.  A slot
       // ends at the next whole member's start and the last at the planned total: whatever the batch leaves between them
       // is overwritten by the units that own those bytes, and nothing behind the planned total is written
-      hipLaunchKernelGGL(gzfile_part_serial_slots_kernel, dim3(1), dim3(1024), 0, c->stream, P, SP, n_dec, total);
+      hipLaunchKernelGGL(gzfile_serial_list_kernel, dim3(1), dim3(1024), 0, c->stream, P, SP, 0u, n_dec, total);
       InfParams W{};
       rc = carve(c, c->d_gzfile_parts_serial_dec, [&](Carve &k) {
         k.take(W.out_len, n_whole);

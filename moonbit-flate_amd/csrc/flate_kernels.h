@@ -876,12 +876,23 @@ struct GzFileParams {
   uint64_t *member_out;    // n_b + 2: out_off[member_unit]
   GzFileHead *gh;
 };
-__global__ void gzfile_init_kernel(FrameOne *one, uint64_t in_len);
+// THE FORM of a discovery.  A file reaches these kernels whole or in parts (below), and the whole file is the part that
+// is final and starts at a BOUNDARY: GzFileMode{} with final_in = 1.  What a part adds -- the root INSIDE a member, THE
+// PARTS HOP of a part that is not final, the carried count, the OPEN stop -- is stated once, in the kernels that take
+// the mode; `part` alone says what no value of the others does: whose result words the call reports.
+struct GzFileMode {
+  uint32_t part;            // a reader's call: the root's header verdict is taken; the member words are the host's
+  uint32_t inside;          // the chain's root is FIND's candidate 0 (bit b0), not the member at offset 0
+  uint32_t final_in;        // the file ends with in[0, in_len)
+  uint64_t hist;            // what the continued member produced in front of the part, saturated at the window
+  const uint32_t *verdict;  // n_b, or null: List B's three verdicts (gzfile_parts_serial_rule.h); null = all LONG
+};
+__global__ void gzfile_init_kernel(FrameOne *one, const uint8_t *in, uint64_t in_len, GzFileMode M, uint32_t b0);
 __global__ void gzfile_bits_kernel(GzFileParams P);
-__global__ void gzfile_link_kernel(GzFileParams P);
-__global__ void gzfile_finish_kernel(GzFileParams P);
+__global__ void gzfile_link_kernel(GzFileParams P, GzFileMode M);
+__global__ void gzfile_finish_kernel(GzFileParams P, GzFileMode M);
 __global__ void gzfile_members_kernel(GzFileParams P);
-__global__ void gzfile_rel_kernel(GzFileParams P);
+__global__ void gzfile_rel_kernel(GzFileParams P, GzFileMode M);
 // The decode (flate_hip_gzfile_read): flate_hip_inflate_one's rounds with every member's first unit as a SEED of the
 // segmented scan (one_seek_compose_kernel / one_seek_resolve_kernel): TAIL runs with rel_off as its out_off, and a
 // piece's history is min(32768, what its own member has produced in front of it).  gzfile_trailer_kernel: one thread
@@ -906,21 +917,17 @@ struct GzFileDecParams {
   const uint32_t *sums;    // per member: the CRC-32 of its output
   GzFileVerdict *v;
 };
-__global__ void gzfile_pieces_kernel(GzFileDecParams G);
+__global__ void gzfile_pieces_kernel(GzFileDecParams G, uint64_t hist);
 __global__ void gzfile_trailer_kernel(GzFileDecParams G);
 __global__ void gzfile_verdict_kernel(GzFileDecParams G);
 
 // A gzip file read in PARTS (flate_hip_gzfile_reader_*; gzfile_parts_kernels.hip; the rule: gzfile_parts_rule.h).  A
 // call is the discovery and the rounds above over one part of the file.  FIND (its PARTS build: candidate 0 at bit
 // FrameOne::b0), PROBE, the chain rounds, the out-scan, the tail probe, gzfile_bits_kernel, gzfile_members_kernel,
-// TAIL, COMPOSE, RESOLVE, DECODE, the check and the checksum kernels run as they are, between the part's own:
-//   gzfile_part_init_kernel     the part's FrameOne (raw range in[0, in_len - 8), b0) and the root's header verdict
-//   gzfile_part_link_kernel     gzfile_link_kernel with THE PARTS HOP and the part's root; a BOUNDARY stop takes the
-//                               terminal sink
-//   gzfile_part_finish_kernel   gzfile_finish_kernel; the last good unit's thread records how the chain ended
-//   gzfile_part_rel_kernel      rel_off: the units in front of the part's first header (u_member == 0xffffffff) are the
-//                               continued member's and start at the carried count
-//   gzfile_part_pieces_kernel   gzfile_pieces_kernel; those units' seed is R[0], the handle's window
+// TAIL, COMPOSE, RESOLVE, DECODE, the check and the checksum kernels run as they are, and so do the kernels that take
+// a GzFileMode, with the part's: the root's header verdict in FrameOne::bad, a BOUNDARY stop into the terminal sink and
+// how the chain ended into GzFileHead::pad[0], the units in front of the part's first header (u_member == 0xffffffff)
+// at the carried count and seeded by R[0], the handle's window.  The part's own:
 //   gzfile_part_trailer_kernel  a thread per member that ends among the delivered units: CRC-32 (the continued member's
 //                               is the joined sum) and ISIZE against the trailer in the part, an ordered min
 //   gzfile_part_carry_kernel    the result words in file order, and the unfinished member's sum back into the handle
@@ -948,28 +955,29 @@ struct GzPartParams {
   int64_t term_err_off;
   uint64_t total;
 };
-__global__ void gzfile_part_init_kernel(FrameOne *one, const uint8_t *in, uint64_t in_len, uint32_t inside, uint32_t b0);
-__global__ void gzfile_part_link_kernel(GzFileParams P, uint32_t inside, uint32_t final_in);
-__global__ void gzfile_part_finish_kernel(GzFileParams P, uint32_t final_in);
-__global__ void gzfile_part_rel_kernel(GzFileParams P, uint64_t hist);
-__global__ void gzfile_part_pieces_kernel(GzFileDecParams G, uint64_t hist);
 __global__ void gzfile_part_trailer_kernel(GzPartParams Q, OneDecParams D);
 __global__ void gzfile_part_carry_kernel(GzPartParams Q, OneDecParams D);
 
-// Short members decoded WHOLE (gzfile_serial_kernels.hip; the option "gzfile_serial_max" = S >= 1; the rule:
-// gzfile_serial_rule.h).  With the option off none of this is launched and the structures above are what they were.
+// Short members decoded WHOLE (gzfile_serial_kernels.hip, gzfile_parts_serial_kernels.hip; the option
+// "gzfile_serial_max" and flate_hip_gzfile_reader_set_serial_max = S >= 1; the rules: gzfile_serial_rule.h,
+// gzfile_parts_serial_rule.h).  With S = 0 none of this is launched and the structures above are what they were.
 // PHASE 1 runs over List B alone, in front of FIND: gzfile_serial_ranges_kernel gives every B candidate its serial
 // range, ONE size-only launch of the batch decoders runs over them (InfParams::used), gzfile_serial_nodes_kernel
-// applies the whole test -- a whole candidate gets its record and links by THE HOP, every other node absorbs --,
-// gzfile_serial_round_kernel doubles the pointers and gzfile_serial_from_kernel reads find_from where the walk from
-// candidate 0 came to rest.  PHASE 2: FIND runs over in[find_from, in_len) only (or not at all);
+// gives each THE THREE VERDICTS -- a WHOLE candidate gets its record and links by THE PARTS HOP, every other node
+// absorbs --, gzfile_serial_round_kernel doubles the pointers and gzfile_serial_from_kernel reads find_from where the
+// walk from candidate 0 came to rest (INSIDE a member: 0; in front of an OPEN member: nowhere, and GzSerialHead::pad).
+// The whole file is the part GzPartSerialIn{1, 0, ~0, null}: its verdicts are WHOLE where the whole test holds and
+// LONG elsewhere, its hop is THE HOP.  PHASE 2: FIND runs over in[find_from, in_len) only (or not at all);
 // gzfile_serial_base_kernel moves its bits to the file's origin; gzfile_serial_bits_kernel is gzfile_bits_kernel,
 // except that a whole candidate's bit is the raw stream's end, so that PROBE leaves it at once;
 // gzfile_serial_keep_kernel puts a whole candidate's bit and its phase-1 record back behind PROBE.  Link, rounds,
 // finish, the scans and the rel kernel then run over the combined nodes as they are: a whole member is a unit that
 // ends with BFINAL.  gzfile_serial_marks_kernel: per path rank, is the unit a whole member, and where its stream ends;
-// gzfile_serial_list_kernel (one workgroup, behind the out-scan): the whole members of the good units compacted into
-// the streams of ONE batch -- in_off, in_end, the slots (the last one ends at out_off[n_units]) and their sizes.
+// gzfile_serial_list_kernel (one workgroup): the whole members among the first units compacted into the streams of
+// ONE batch -- in_off, in_end, the slots and their sizes; the whole call launches it behind the out-scan over the good
+// units (the last slot ends at out_off[n_units]), a reader's call behind the host's plan over the units it decodes
+// (the last slot ends at the planned total).  A part's chain has no list behind it but
+// gzfile_part_serial_stop_kernel: did it end in front of an OPEN member (GzSerialHead::pad).
 // gzfile_serial_check_kernel, behind that batch in the read: status 0 and exactly the size the discovery found, else
 // OneDecHead::decode_bad.
 struct GzSerialHead {
@@ -1002,35 +1010,24 @@ struct GzSerialParams {
   uint64_t *w_size;        // n_b
   uint32_t *w_unit;        // n_b
 };
+struct GzPartSerialIn {      // phase 1's form (the chain's: GzFileMode)
+  uint32_t final_in, inside;
+  uint64_t out_cap;          // a member that inflates to more is not WHOLE
+  uint32_t *verdict;         // n_b, or null: kGzPartLong / kGzPartWhole / kGzPartOpen, kept for the chain's link
+};
 __global__ void gzfile_serial_ranges_kernel(GzSerialParams S);
-__global__ void gzfile_serial_nodes_kernel(GzSerialParams S);
+__global__ void gzfile_serial_nodes_kernel(GzSerialParams S, GzPartSerialIn A);
 __global__ void gzfile_serial_round_kernel(const uint32_t *src, uint32_t *dst, uint32_t n);
-__global__ void gzfile_serial_from_kernel(GzSerialParams S, const uint32_t *jump);
+__global__ void gzfile_serial_from_kernel(GzSerialParams S, GzPartSerialIn A, const uint32_t *jump);
 __global__ void gzfile_serial_base_kernel(uint64_t *cand_off, uint32_t n, uint64_t base_bits);
 __global__ void gzfile_serial_bits_kernel(GzFileParams P, GzSerialParams S);
 __global__ void gzfile_serial_keep_kernel(GzFileParams P, GzSerialParams S);
 __global__ void gzfile_serial_marks_kernel(GzFileParams P, GzSerialParams S);
-__global__ void gzfile_serial_list_kernel(GzFileParams P, GzSerialParams S);
+// from_head: the unit count and the total are the chain's head's (n_dec and total are not read), else the host's
+__global__ void gzfile_serial_list_kernel(GzFileParams P, GzSerialParams S, uint32_t from_head, uint32_t n_dec, uint64_t total);
 __global__ void gzfile_serial_check_kernel(GzSerialParams S, uint32_t n_whole, const int32_t *d_status,
                                            const uint64_t *d_out_len, OneDecHead *dh);
-
-// Short members decoded WHOLE inside a PART (gzfile_parts_serial_kernels.hip; flate_hip_gzfile_reader_set_serial_max;
-// the rule: gzfile_parts_serial_rule.h).  With S = 0 none of this is launched.  Phase 1 above runs over the part, with
-// gzfile_part_serial_nodes_kernel (the three verdicts, THE PARTS HOP) and gzfile_part_serial_from_kernel (INSIDE, the
-// root, the OPEN stop) in the places of the nodes and the from kernel; the chain is the part's, with
-// gzfile_part_serial_link_kernel as its link; gzfile_part_serial_stop_kernel says whether it ended in front of an OPEN
-// member (GzSerialHead::pad); gzfile_part_serial_slots_kernel, behind the host's plan, lays out the batch of the whole
-// members among the units the call decodes.
-struct GzPartSerialIn {
-  uint32_t final_in, inside;
-  uint64_t out_cap;          // a member that inflates to more is not WHOLE
-  uint32_t *verdict;         // n_b: kGzPartLong / kGzPartWhole / kGzPartOpen
-};
-__global__ void gzfile_part_serial_nodes_kernel(GzSerialParams S, GzPartSerialIn A);
-__global__ void gzfile_part_serial_from_kernel(GzSerialParams S, GzPartSerialIn A, const uint32_t *jump);
-__global__ void gzfile_part_serial_link_kernel(GzFileParams P, const uint32_t *verdict, uint32_t inside, uint32_t final_in);
 __global__ void gzfile_part_serial_stop_kernel(GzFileParams P, GzSerialParams S);
-__global__ void gzfile_part_serial_slots_kernel(GzFileParams P, GzSerialParams S, uint32_t n_dec, uint64_t total);
 
 // The seek index of a gzip FILE (gzfile_seek_kernels.hip; flate_hip_gzfile_seek_index / _ranges; the rule and the
 // index's layout: gzfile_seek_rule.h).  Locate, select, layout, compose, resolve, check, TAIL and the gather are the

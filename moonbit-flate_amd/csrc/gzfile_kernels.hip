@@ -1,40 +1,48 @@
-// gzfile_kernels.hip -- a gzip FILE of any members (flate_hip_gzfile_index / _read): the units of all members as ONE
-// chain over the file's bits, the members found from it, and the decode's member-wise parts (flate_kernels.h:
-// GzFileParams, GzFileDecParams; the rule: gzfile_rule.h).
+// gzfile_kernels.hip -- a gzip FILE of any members, whole (flate_hip_gzfile_index / _read) or in PARTS
+// (flate_hip_gzfile_reader_*): the units of all members as ONE chain over the bits of the file or the part, the members
+// found from it, and the whole call's result words (flate_kernels.h: GzFileParams, GzFileMode, GzFileDecParams; the
+// rules: gzfile_rule.h, gzfile_parts_rule.h, gzfile_parts_serial_rule.h).
 //
-// The skeleton is chain_walk.h's with two candidate lists in one node array.  The passes are the existing ones, run
-// over the whole file: one_count_kernel / one_fill_kernel (List A: every bit that passes the dynamic-header rule; the
-// raw stream they are given is in[0, in_len - 8)), gzip_count_kernel / gzip_fill_kernel with no clip (List B: every
-// byte that passes the gzip header rule), one_probe_kernel over all nodes, chain_round_kernel, one_out_scan_kernel and
-// the tail probe.  What is this format's own:
-//   gzfile_init_kernel     the one range: bits and error offsets are counted from the file's first byte
+// The skeleton is chain_walk.h's with two candidate lists in one node array.  The passes are the existing ones:
+// one_count_kernel / one_fill_kernel (List A: every bit that passes the dynamic-header rule; the raw stream they are
+// given is in[0, in_len - 8)), gzip_count_kernel / gzip_fill_kernel with no clip (List B: every byte that passes the
+// gzip header rule), one_probe_kernel over all nodes, chain_round_kernel, one_out_scan_kernel and the tail probe.  What
+// is this format's own (M: the form, which for the whole file is the part that is final and starts at a BOUNDARY):
+//   gzfile_init_kernel     M; the one range: bits and error offsets are counted from the first byte; a part's root
 //   gzfile_bits_kernel     a B node's bit: 8 * (header offset + header length)
-//   gzfile_link_kernel     in front of a dynamic header: the A node at that bit; behind BFINAL: THE HOP into B
-//   gzfile_finish_kernel   path rank r -> unit_bit[r], the unit's size, whether it starts and whether it ends a member;
-//                          the thread at which the path meets a sink writes the verdict or asks for the tail probe
+//   gzfile_link_kernel     M; in front of a dynamic header: the A node at that bit; behind BFINAL: THE LINK into B
+//   gzfile_finish_kernel   M; path rank r -> unit_bit[r], the unit's size, whether it starts and whether it ends a member;
+//                          the thread at which the path meets a sink writes how the chain ended or asks for the tail probe
 //   gzfile_members_kernel  the scan over the "starts a member" marks -> member_off, member_unit, u_member
-//   gzfile_rel_kernel      rel_off, member_out and the verdict's member words
-//   gzfile_pieces_kernel   a round's pieces: slot, history (never across a member), seed, where the piece ends
-//   gzfile_trailer_kernel  one thread per member: CRC-32 and ISIZE against its trailer, an ordered min
-//   gzfile_verdict_kernel  the call's result words
+//   gzfile_rel_kernel      M; rel_off, and for the whole file member_out and the verdict's member words
+//   gzfile_trailer_kernel  the whole file, one thread per member: CRC-32 and ISIZE against its trailer, an ordered min
+//   gzfile_verdict_kernel  the whole call's result words
 // A unit ends strictly above its start and a hop lands above the trailer it skips, so nothing cycles.  No kernel waits
 // for another workgroup; every loop is bounded by a header's length, by the unit count or by 32 search steps.
 #include <hip/hip_runtime.h>
 
 #include "chain_walk.h"
 #include "flate_hip.h"
-#include "gzfile_rule.h"
+#include "gzfile_parts_serial_rule.h"
 #include "window_compose.h"
 
 namespace flate {
 
-__global__ void gzfile_init_kernel(FrameOne *one, uint64_t in_len) {
+// One thread.  The raw range is in[0, in_len - 8): the last 8 bytes can only be a trailer.  A part takes b0 INSIDE, and
+// at a BOUNDARY the root's verdict (the rule's three answers; anything but 0 leaves FIND no candidate) from in[0, in_len).
+__global__ void gzfile_init_kernel(FrameOne *one, const uint8_t *in, uint64_t in_len, GzFileMode M, uint32_t b0) {
   if (blockIdx.x != 0 || threadIdx.x != 0) return;
   FrameOne o{};
   o.in_off[1] = in_len;
   o.pay_off[1] = in_len;
-  o.pay_end = in_len >= kGzipTrailerLen ? in_len - kGzipTrailerLen : 0ull;  // a file's last 8 bytes can only be a trailer
+  o.pay_end = in_len >= kGzipTrailerLen ? in_len - kGzipTrailerLen : 0ull;
   o.dict_used = FLATE_HIP_NO_DICT;
+  if (M.inside) {
+    o.b0 = b0 & 7u;
+  } else if (M.part) {
+    uint64_t hl = 0;
+    o.bad = gzfile_parts_root(in, in_len, &hl);
+  }
   *one = o;
 }
 
@@ -46,14 +54,17 @@ __global__ __launch_bounds__(256) void gzfile_bits_kernel(GzFileParams P) {
   P.O.C.cand_off[P.n_a + j] = gzfile_first_bit(P.O.C.in, P.O.C.in_len, P.hdr_off[j]);
 }
 
-// One thread per node (n_a + n_b + 2 of them).
-__global__ __launch_bounds__(256) void gzfile_link_kernel(GzFileParams P) {
+// One thread per node (n_a + n_b + 2 of them).  THE LINK behind BFINAL is gzfile_parts_serial_hop: with no verdicts
+// THE PARTS HOP, and that on a final part THE HOP.
+__global__ __launch_bounds__(256) void gzfile_link_kernel(GzFileParams P, GzFileMode M) {
   const ChainParams &C = P.O.C;
-  const uint32_t n = C.cap, na = P.n_a;
+  const uint32_t n = C.cap, na = P.n_a, nb = P.n_b;
   const uint32_t c = blockIdx.x * 256u + threadIdx.x;
   if (c == 0) {
-    // the chain starts at the member at offset 0; until a finish thread knows better: no member can start there
-    C.path[0] = (P.n_b && P.hdr_off[0] == 0ull) ? na : n + 1u;
+    // INSIDE: candidate 0, which FIND's PARTS build has put at bit b0; BOUNDARY: the member at offset 0; until a finish
+    // thread knows better: no member can start there
+    if (M.inside) C.path[0] = na ? 0u : n + 1u;
+    else C.path[0] = (nb && P.hdr_off[0] == 0ull) ? na : n + 1u;
     OneHead h{};
     h.h.rc = FLATE_HIP_E_CORRUPT;
     h.h.n_cand = n;
@@ -63,6 +74,7 @@ __global__ __launch_bounds__(256) void gzfile_link_kernel(GzFileParams P) {
     g.err_off = 0;
     g.stream_err_off = -1;
     g.no_header = 1u;
+    g.pad[0] = kGzPartEndDead;
     *P.gh = g;
     C.member_off[0] = 0ull;
     P.u_start[0] = 0ull;
@@ -77,19 +89,23 @@ __global__ __launch_bounds__(256) void gzfile_link_kernel(GzFileParams P) {
       const uint32_t at = chain_find(C.cand_off, 0u, na, pr.end_bit);
       if (at < na) next = at;
     } else {
-      const GzHop hop = gzfile_hop(C.in, C.in_len, pr.end_bit);
-      if (hop.kind == kGzHopEnd) {
+      const GzHop hop = gzfile_parts_serial_hop(C.in, C.in_len, pr.end_bit, M.final_in != 0u, [&](uint64_t e) {
+        if (!M.verdict) return kGzPartLong;
+        const uint32_t at = chain_find(P.hdr_off, 0u, nb, e);
+        return at < nb ? M.verdict[at] : kGzPartLong;
+      });
+      if (hop.kind == kGzHopEnd || hop.kind == kGzHopStop) {
         next = n;
       } else if (hop.kind == kGzHopNext) {
-        const uint32_t at = chain_find(P.hdr_off, 0u, P.n_b, hop.e);
-        if (at < P.n_b) next = na + at;
+        const uint32_t at = chain_find(P.hdr_off, 0u, nb, hop.e);
+        if (at < nb) next = na + at;
       }
     }
   }
   C.jump[0][c] = next;
 }
 
-__global__ __launch_bounds__(256) void gzfile_finish_kernel(GzFileParams P) {
+__global__ __launch_bounds__(256) void gzfile_finish_kernel(GzFileParams P, GzFileMode M) {
   const ChainParams &C = P.O.C;
   const uint32_t n = C.cap;
   const uint32_t r = blockIdx.x * 256u + threadIdx.x;
@@ -119,13 +135,19 @@ __global__ __launch_bounds__(256) void gzfile_finish_kernel(GzFileParams P) {
   C.member_off[r + 1u] = pr.end_bit;
   P.u_start[r + 1u] = 0ull;
   P.gh->no_header = 0u;
-  if (succ == n) {
-    h->rc = 0;
-    h->err_off = -1;
-  } else if (pr.final_block) {  // no member can start behind this one's trailer
-    h->rc = FLATE_HIP_E_CORRUPT;
-    h->err_off = (int64_t)gzfile_hop(C.in, C.in_len, pr.end_bit).e;
-    P.gh->no_header = 1u;
+  if (pr.final_block) {  // how the chain ended: the hop again (succ == n lies only behind a final block)
+    const GzHop hop = gzfile_parts_hop(C.in, C.in_len, pr.end_bit, M.final_in != 0u);
+    if (succ == n) {
+      h->rc = 0;
+      h->err_off = -1;
+      // for gzfile_part_serial_stop_kernel and no one else; the whole file's rel kernel writes err_off over
+      P.gh->pad[0] = hop.kind == kGzHopEnd ? kGzPartEndFile : kGzPartEndStop;
+      P.gh->err_off = (int64_t)hop.e;
+    } else {  // no member can start behind this one's trailer
+      h->rc = FLATE_HIP_E_CORRUPT;
+      h->err_off = (int64_t)hop.e;
+      P.gh->no_header = 1u;
+    }
   } else {  // a header of a unit-starting type that is no candidate: the tail probe reads it as the serial decoder
     P.O.head->tail_bit = pr.end_bit;
     P.O.head->tail = 1u;
@@ -147,14 +169,17 @@ __global__ __launch_bounds__(1024) void gzfile_members_kernel(GzFileParams P) {
       });
 }
 
-// One thread per unit (and the one behind the good ones), behind gzfile_members_kernel and the tail probe.
-__global__ __launch_bounds__(256) void gzfile_rel_kernel(GzFileParams P) {
+// One thread per unit (and the one behind the good ones), behind gzfile_members_kernel and the tail probe.  A unit in
+// front of every member is the continued member's and starts at M.hist (the whole file: only the unit behind no good
+// one, at 0).  The member words are the whole file's: a reader's call counts its members on the host.
+__global__ __launch_bounds__(256) void gzfile_rel_kernel(GzFileParams P, GzFileMode M) {
   const ChainParams &C = P.O.C;
   const uint32_t nu = C.head->n_members;
   const uint32_t k = blockIdx.x * 256u + threadIdx.x;
   if (k > nu) return;
   const uint32_t m = P.u_member[k];
-  P.rel_off[k] = m == 0xffffffffu ? 0ull : C.out_off[k] - C.out_off[P.member_unit[m]];
+  P.rel_off[k] = m == 0xffffffffu ? M.hist + C.out_off[k] : C.out_off[k] - C.out_off[P.member_unit[m]];
+  if (M.part) return;
   if (P.u_start[k]) P.member_out[m] = C.out_off[k];
   if (k != nu) return;
   // the verdict's member words; m = the member of the unit the chain broke in, or the last whole member
@@ -175,31 +200,6 @@ __global__ __launch_bounds__(256) void gzfile_rel_kernel(GzFileParams P) {
   g->n_members = m;
   g->err_off = (int64_t)P.member_off[m];
   g->stream_err_off = (rc == FLATE_HIP_E_CORRUPT && C.head->err_off >= 0) ? C.head->err_off - (int64_t)raw : -1;
-}
-
-// One thread per unit of the round (and one more): one_pieces_kernel's slots, with the history, the seed and the end
-// of a piece taken from the unit's member.
-__global__ __launch_bounds__(256) void gzfile_pieces_kernel(GzFileDecParams G) {
-  const OneDecParams &D = G.D;
-  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-  if (i > D.count) return;
-  const uint32_t u = D.u0 + i, fb = D.dh->first_bad;
-  uint64_t limit = D.total;
-  if (fb != 0xffffffffu) limit = D.out_off[fb] + D.produced[fb];
-  if (limit > D.total) limit = D.total;
-  uint64_t at = u > fb ? limit : D.out_off[u];  // (out_off is defined up to the first failing unit)
-  if (at > limit) at = limit;
-  D.p_out_off[i] = at;
-  if (i == D.count) return;
-  const uint32_t f = (uint32_t)G.P.member_unit[G.P.u_member[u]];  // its member's first unit (u lies behind a header)
-  const uint64_t rel = at > D.out_off[f] ? at - D.out_off[f] : 0ull;  // (a member behind the failure: an empty slot)
-  const uint32_t dict_len = rel < (uint64_t)kWinEntries ? (uint32_t)rel : kWinEntries;
-  D.p_dict_len[i] = dict_len;
-  D.p_dict_at[i] = (uint64_t)(i + 1u) * kWinEntries - dict_len;  // the tail of R[i]; R[i + 1] follows it
-  G.seed[i] = f > D.u0 ? f - D.u0 : 0u;  // (a member that began in a round in front continues from R[0])
-  G.p_bit_off[i] = D.unit_bit[u];
-  // a member's last unit runs to BFINAL, and so does the unit the chain broke in
-  G.p_bit_end[i] = (u >= G.n_good || G.P.u_final[u]) ? ~0ull : D.unit_bit[u + 1u];
 }
 
 // One thread per member, behind the checksums.  Judged only when every unit decoded.

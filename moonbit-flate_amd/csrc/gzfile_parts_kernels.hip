@@ -1,10 +1,9 @@
 // gzfile_parts_kernels.hip -- a gzip FILE of any members read in PARTS (flate_hip_gzfile_reader_*; flate_kernels.h:
 // GzPartState, GzPartParams; the rule: gzfile_parts_rule.h).  A call runs flate_hip_gzfile_read's discovery and rounds
-// over one part of the file; every pass of those runs as it is, and what is the parts' own stands here: the member-wise
-// kernels of gzfile_kernels.hip with the part's root, THE PARTS HOP, the continued member's carried count and window,
-// and the trailers of the members that end among the delivered units.  No kernel waits for another workgroup; every
-// loop is bounded by a header's length (the walks of gzip_header_len and one_parts_header, at most to the part's end),
-// by the unit count or by 32 search steps.
+// over one part of the file; the chain is gzfile_kernels.hip's in the part's form, and what a part's DECODE needs
+// stands here: the pieces of a round with the continued member's carried count and window (every form's: the whole
+// file carries nothing), the trailers of the members that end among the delivered units, and the call's words.  No
+// kernel waits for another workgroup; every loop is bounded by the segment count.
 #include <hip/hip_runtime.h>
 
 #include "chain_walk.h"
@@ -14,131 +13,11 @@
 
 namespace flate {
 
-// One thread: the part's words.  The raw range is in[0, in_len - 8), as gzfile_init_kernel's.  bad: the root's verdict
-// at a BOUNDARY (the rule's three answers); anything but 0 leaves FIND no candidate.  Every read is below in_len.
-__global__ void gzfile_part_init_kernel(FrameOne *one, const uint8_t *in, uint64_t in_len, uint32_t inside, uint32_t b0) {
-  if (blockIdx.x != 0 || threadIdx.x != 0) return;
-  FrameOne o{};
-  o.in_off[1] = in_len;
-  o.pay_off[1] = in_len;
-  o.pay_end = in_len >= kGzipTrailerLen ? in_len - kGzipTrailerLen : 0ull;
-  o.dict_used = FLATE_HIP_NO_DICT;
-  if (inside) {
-    o.b0 = b0 & 7u;
-  } else {
-    uint64_t hl = 0;
-    o.bad = gzfile_parts_root(in, in_len, &hl);
-  }
-  *one = o;
-}
-
-// One thread per node (n_a + n_b + 2 of them).
-__global__ __launch_bounds__(256) void gzfile_part_link_kernel(GzFileParams P, uint32_t inside, uint32_t final_in) {
-  const ChainParams &C = P.O.C;
-  const uint32_t n = C.cap, na = P.n_a;
-  const uint32_t c = blockIdx.x * 256u + threadIdx.x;
-  if (c == 0) {
-    // INSIDE: candidate 0, which FIND's PARTS build has put at bit b0; BOUNDARY: the member at offset 0
-    if (inside) C.path[0] = na ? 0u : n + 1u;
-    else C.path[0] = (P.n_b && P.hdr_off[0] == 0ull) ? na : n + 1u;
-    OneHead h{};
-    h.h.rc = FLATE_HIP_E_CORRUPT;
-    h.h.n_cand = n;
-    h.raw_len = P.O.one->pay_end;
-    *P.O.head = h;
-    GzFileHead g{};
-    g.err_off = 0;
-    g.stream_err_off = -1;
-    g.no_header = 1u;
-    g.pad[0] = kGzPartEndDead;
-    *P.gh = g;
-    C.member_off[0] = 0ull;
-    P.u_start[0] = 0ull;
-  }
-  if (c > n + 1u) return;
-  uint32_t next = c;  // (the sinks absorb)
-  if (c < n) {
-    const OneProbe pr = P.O.probe[c];
-    next = n + 1u;
-    if (pr.status != 0) {
-    } else if (!pr.final_block) {
-      const uint32_t at = chain_find(C.cand_off, 0u, na, pr.end_bit);
-      if (at < na) next = at;
-    } else {
-      const GzHop hop = gzfile_parts_hop(C.in, C.in_len, pr.end_bit, final_in != 0u);
-      if (hop.kind == kGzHopEnd || hop.kind == kGzHopStop) {
-        next = n;
-      } else if (hop.kind == kGzHopNext) {
-        const uint32_t at = chain_find(P.hdr_off, 0u, P.n_b, hop.e);
-        if (at < P.n_b) next = na + at;
-      }
-    }
-  }
-  C.jump[0][c] = next;
-}
-
-__global__ __launch_bounds__(256) void gzfile_part_finish_kernel(GzFileParams P, uint32_t final_in) {
-  const ChainParams &C = P.O.C;
-  const uint32_t n = C.cap;
-  const uint32_t r = blockIdx.x * 256u + threadIdx.x;
-  if (r + 1u >= C.path_len) return;  // (the last entry is a sink: see below)
-  const uint32_t c = C.path[r];
-  if (c >= n) return;
-  BgzfHead *h = C.head;
-  const OneProbe pr = P.O.probe[c];
-  C.member_off[r] = C.cand_off[c];
-  P.u_start[r] = c >= P.n_a ? P.hdr_off[c - P.n_a] + 1u : 0ull;
-  if (pr.status != 0) {  // the decode ends IN this unit: one thread gets here, or one gets below
-    const bool deliver = pr.status != FLATE_HIP_E_TOO_LARGE;
-    P.O.head->fail_out = deliver ? pr.out : 0ull;
-    P.O.head->fail_unit = deliver ? 1u : 0u;
-    h->n_members = r;
-    h->rc = pr.status;
-    h->err_off = pr.err_off;
-    P.gh->no_header = 0u;
-    return;
-  }
-  P.O.usize[r] = pr.out;
-  P.u_final[r] = pr.final_block;
-  // (the chain holds at most n nodes and path_len >= n + 2: r + 1 is inside the path)
-  const uint32_t succ = C.path[r + 1u];
-  if (succ < n) return;
-  h->n_members = r + 1u;  // this is the last good unit
-  C.member_off[r + 1u] = pr.end_bit;
-  P.u_start[r + 1u] = 0ull;
-  P.gh->no_header = 0u;
-  if (pr.final_block) {  // how the chain ended: the hop again
-    const GzHop hop = gzfile_parts_hop(C.in, C.in_len, pr.end_bit, final_in != 0u);
-    if (succ == n) {
-      h->rc = 0;
-      h->err_off = -1;
-      P.gh->pad[0] = hop.kind == kGzHopEnd ? kGzPartEndFile : kGzPartEndStop;
-      P.gh->err_off = (int64_t)hop.e;
-    } else {  // no member can start behind this one's trailer
-      h->rc = FLATE_HIP_E_CORRUPT;
-      h->err_off = (int64_t)hop.e;
-      P.gh->no_header = 1u;
-    }
-  } else {  // a header of a unit-starting type that is no candidate: the tail probe reads it as the serial decoder
-    P.O.head->tail_bit = pr.end_bit;
-    P.O.head->tail = 1u;
-  }
-}
-
-// One thread per unit (and the one behind the good ones), behind gzfile_members_kernel.  hist: what the continued member
-// produced before the part, as far as the distance rule can see it (it saturates at the window).
-__global__ __launch_bounds__(256) void gzfile_part_rel_kernel(GzFileParams P, uint64_t hist) {
-  const ChainParams &C = P.O.C;
-  const uint32_t nu = C.head->n_members;
-  const uint32_t k = blockIdx.x * 256u + threadIdx.x;
-  if (k > nu) return;
-  const uint32_t m = P.u_member[k];
-  P.rel_off[k] = m == 0xffffffffu ? hist + C.out_off[k] : C.out_off[k] - C.out_off[P.member_unit[m]];
-}
-
-// One thread per unit of the round (and one more): gzfile_pieces_kernel, with the continued member's units seeded by
-// R[0] -- the handle's window in the first round, the round driver's carry behind it.
-__global__ __launch_bounds__(256) void gzfile_part_pieces_kernel(GzFileDecParams G, uint64_t hist) {
+// One thread per unit of the round (and one more): one_pieces_kernel's slots, with the history (never across a
+// member), the seed and the end of a piece taken from the unit's member.  The units in front of the first header
+// (u_member == 0xffffffff; the whole file has none) are the continued member's: hist bytes lie in front of them and
+// their seed is R[0] -- the handle's window in the first round, the round driver's carry behind it.
+__global__ __launch_bounds__(256) void gzfile_pieces_kernel(GzFileDecParams G, uint64_t hist) {
   const OneDecParams &D = G.D;
   const uint32_t i = blockIdx.x * 256u + threadIdx.x;
   if (i > D.count) return;

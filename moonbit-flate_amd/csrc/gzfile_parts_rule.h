@@ -1,6 +1,7 @@
 // gzfile_parts_rule.h -- a gzip FILE of any members read in PARTS (flate_hip_gzfile_reader_*), what a call decides,
-// written ONCE: plain C++17 without HIP, compiled into the part kernels (gzfile_parts_kernels.hip), into the library's
-// host code and into tests/host_model/gzfile_parts_rule_model.cpp, which compares it with tests/gzfile_parts_ref.py.
+// written ONCE: plain C++17 without HIP, compiled into the kernels (gzfile_kernels.hip, which run the whole file as the
+// part that is final and starts at a BOUNDARY, and gzfile_parts_kernels.hip), into the library's host code and into
+// tests/host_model/gzfile_parts_rule_model.cpp, which compares it with tests/gzfile_parts_ref.py.
 //
 // A call is flate_hip_gzfile_read's discovery and rounds over the part in[0, in_len) of the file.  Between two calls
 // the reader stands at a BOUNDARY (the next part's first byte is where a header must stand, or the file's end) or

@@ -1,14 +1,14 @@
-// gzfile_parts_serial_kernels.hip -- a gzip FILE read in PARTS with short members decoded WHOLE inside a part
-// (flate_hip_gzfile_reader_set_serial_max: S >= 1; flate_kernels.h: GzSerialParams, GzPartSerialIn; the rule:
-// gzfile_parts_serial_rule.h).  A call runs phase 1 of gzfile_serial_kernels.hip over the part and the chain of
-// gzfile_parts_kernels.hip behind it; the ranges, the pointer-doubling round, the base, bits, keep and marks kernels of
-// the whole call run as they are (a whole member is a B node with its phase-1 record), and what is the parts' own
-// stands here:
-//   gzfile_part_serial_nodes_kernel  THE THREE VERDICTS; a WHOLE candidate's record and its link by THE PARTS HOP
-//   gzfile_part_serial_from_kernel   find_from: INSIDE, the root, where the walk over the whole members came to rest
-//   gzfile_part_serial_link_kernel   gzfile_part_link_kernel; a hop onto the header of an OPEN member is a BOUNDARY stop
-//   gzfile_part_serial_stop_kernel   did the chain end in front of an OPEN member
-//   gzfile_part_serial_slots_kernel  the whole members among the units the call decodes, as the streams of one batch
+// gzfile_parts_serial_kernels.hip -- a gzip FILE's short members decoded WHOLE, the walk of phase 1 and what follows
+// from its verdicts, for the whole file and for a PART alike (the option "gzfile_serial_max",
+// flate_hip_gzfile_reader_set_serial_max: S >= 1; flate_kernels.h: GzSerialParams, GzPartSerialIn; the rule:
+// gzfile_parts_serial_rule.h).  The whole file is the part that is final and starts at a BOUNDARY, with out_cap = ~0
+// and no verdict array.  The other kernels of phase 1 and 2: gzfile_serial_kernels.hip; the chain's link, which stops
+// a hop onto an OPEN member: gzfile_kernels.hip.
+//   gzfile_serial_nodes_kernel      THE THREE VERDICTS; a WHOLE candidate's record and its link by THE PARTS HOP
+//   gzfile_serial_from_kernel       find_from: INSIDE, the root, where the walk over the whole members came to rest
+//   gzfile_part_serial_stop_kernel  a part's chain: did it end in front of an OPEN member
+//   gzfile_serial_list_kernel       the whole members among the good units, or among the units a reader's call
+//                                   decodes, as the streams of one batch
 // No kernel waits for another workgroup; every loop is bounded by a header's length, by the node count or by 32 search
 // steps.  A hop lands above the trailer it skips, so the links rise and nothing cycles.
 #include <hip/hip_runtime.h>
@@ -22,7 +22,7 @@
 namespace flate {
 
 // One thread per node of the walk (n_b + 2 of them): n_b = the file's end or a BOUNDARY stop, n_b + 1 = a dead hop.
-__global__ __launch_bounds__(256) void gzfile_part_serial_nodes_kernel(GzSerialParams S, GzPartSerialIn A) {
+__global__ __launch_bounds__(256) void gzfile_serial_nodes_kernel(GzSerialParams S, GzPartSerialIn A) {
   const uint32_t nb = S.n_b;
   const uint32_t j = blockIdx.x * 256u + threadIdx.x;
   if (j > nb + 1u) return;
@@ -32,7 +32,7 @@ __global__ __launch_bounds__(256) void gzfile_part_serial_nodes_kernel(GzSerialP
     const uint64_t hl = gzip_header_len(S.in + p, S.in_len - p);
     const uint32_t v = gzfile_parts_serial_verdict(S.in_len, A.final_in != 0u, S.serial_max, A.out_cap, p, hl, S.status[j],
                                                    S.used[j], S.out_len[j]);
-    A.verdict[j] = v;
+    if (A.verdict) A.verdict[j] = v;
     S.whole[j] = v == kGzPartWhole ? 1u : 0u;
     if (v == kGzPartWhole) {
       const GzSerialRecord r = gzfile_serial_record(p, hl, S.used[j], S.out_len[j]);
@@ -56,69 +56,20 @@ __global__ __launch_bounds__(256) void gzfile_part_serial_nodes_kernel(GzSerialP
   S.jump[0][j] = next;
 }
 
-// One thread, behind the pointer doubling.
-__global__ void gzfile_part_serial_from_kernel(GzSerialParams S, GzPartSerialIn A, const uint32_t *jump) {
+// One thread, behind the pointer doubling.  (No verdict array: never OPEN, and the walk rests on what is not WHOLE.)
+__global__ void gzfile_serial_from_kernel(GzSerialParams S, GzPartSerialIn A, const uint32_t *jump) {
   if (blockIdx.x != 0 || threadIdx.x != 0) return;
   bool none = true;
   uint64_t rest_off = 0;
   uint32_t rest_verdict = kGzPartLong;
   if (S.n_b && S.hdr_off[0] == 0ull) {
     const uint32_t t = jump[0];
-    if (t < S.n_b) none = false, rest_off = S.hdr_off[t], rest_verdict = A.verdict[t];
+    if (t < S.n_b) none = false, rest_off = S.hdr_off[t], rest_verdict = A.verdict ? A.verdict[t] : kGzPartLong;
   }
   uint32_t open_stop = 0;
   S.head->find_from = gzfile_parts_serial_from(S.in_len, A.inside != 0u, none, rest_off, rest_verdict, &open_stop);
   S.head->n_whole = 0;
   S.head->pad = open_stop;
-}
-
-// One thread per node (n_a + n_b + 2 of them): gzfile_part_link_kernel with the OPEN stop.
-__global__ __launch_bounds__(256) void gzfile_part_serial_link_kernel(GzFileParams P, const uint32_t *verdict, uint32_t inside,
-                                                                      uint32_t final_in) {
-  const ChainParams &C = P.O.C;
-  const uint32_t n = C.cap, na = P.n_a, nb = P.n_b;
-  const uint32_t c = blockIdx.x * 256u + threadIdx.x;
-  if (c == 0) {
-    // INSIDE: candidate 0, which FIND's PARTS build has put at bit b0; BOUNDARY: the member at offset 0
-    if (inside) C.path[0] = na ? 0u : n + 1u;
-    else C.path[0] = (nb && P.hdr_off[0] == 0ull) ? na : n + 1u;
-    OneHead h{};
-    h.h.rc = FLATE_HIP_E_CORRUPT;
-    h.h.n_cand = n;
-    h.raw_len = P.O.one->pay_end;
-    *P.O.head = h;
-    GzFileHead g{};
-    g.err_off = 0;
-    g.stream_err_off = -1;
-    g.no_header = 1u;
-    g.pad[0] = kGzPartEndDead;
-    *P.gh = g;
-    C.member_off[0] = 0ull;
-    P.u_start[0] = 0ull;
-  }
-  if (c > n + 1u) return;
-  uint32_t next = c;  // (the sinks absorb)
-  if (c < n) {
-    const OneProbe pr = P.O.probe[c];
-    next = n + 1u;
-    if (pr.status != 0) {
-    } else if (!pr.final_block) {
-      const uint32_t at = chain_find(C.cand_off, 0u, na, pr.end_bit);
-      if (at < na) next = at;
-    } else {
-      const GzHop hop = gzfile_parts_serial_hop(C.in, C.in_len, pr.end_bit, final_in != 0u, [&](uint64_t e) {
-        const uint32_t at = chain_find(P.hdr_off, 0u, nb, e);
-        return at < nb ? verdict[at] : kGzPartLong;
-      });
-      if (hop.kind == kGzHopEnd || hop.kind == kGzHopStop) {
-        next = n;
-      } else if (hop.kind == kGzHopNext) {
-        const uint32_t at = chain_find(P.hdr_off, 0u, nb, hop.e);
-        if (at < nb) next = na + at;
-      }
-    }
-  }
-  C.jump[0][c] = next;
 }
 
 // One thread, behind the chain: a BOUNDARY stop at a byte where a header passes the rule is the OPEN stop (THE PARTS HOP
@@ -134,13 +85,15 @@ __global__ void gzfile_part_serial_stop_kernel(GzFileParams P, GzSerialParams S)
   S.head->pad = open_stop;
 }
 
-// One workgroup, behind the host's plan: the whole members among the first n_dec units -- the ones the call decodes --
-// as the streams of one batch.  A slot ends at the next whole member's start; the LAST ends at the call's planned
+// One workgroup: the whole members among the first n_dec units as the streams of one batch.  A slot ends at the next
+// whole member's start; the LAST ends at `total`.  from_head (the whole call, behind the out-scan): the good units and
+// where their output ends.  Else (a reader's call, behind the host's plan): the units the call decodes and its planned
 // total, behind which the reader writes nothing.
-__global__ __launch_bounds__(1024) void gzfile_part_serial_slots_kernel(GzFileParams P, GzSerialParams S, uint32_t n_dec,
-                                                                        uint64_t total) {
+__global__ __launch_bounds__(1024) void gzfile_serial_list_kernel(GzFileParams P, GzSerialParams S, uint32_t from_head,
+                                                                  uint32_t n_dec, uint64_t total) {
   __shared__ uint32_t wtot[16];
   const ChainParams &C = P.O.C;
+  if (from_head) n_dec = C.head->n_members, total = C.out_off[n_dec];
   const uint32_t nw = scan_range<16, uint32_t>(
       n_dec, wtot, [&](uint32_t u) { return S.u_whole[u]; },
       [&](uint32_t u, uint32_t k, uint32_t v) {

@@ -1,7 +1,13 @@
 // gzfile_parts_serial_rule.h -- a gzip FILE read in PARTS with short members decoded WHOLE inside a part
 // (flate_hip_gzfile_reader_set_serial_max: S >= 1), written ONCE: plain C++17 without HIP, compiled into the kernels
-// (gzfile_parts_serial_kernels.hip), into the library's host code and into
+// (gzfile_parts_serial_kernels.hip, gzfile_kernels.hip), into the library's host code and into
 // tests/host_model/gzfile_parts_serial_rule_model.cpp, which compares it with tests/gzfile_parts_serial_ref.py.
+//
+// The same kernels run the whole file ("gzfile_serial_max"), which is the part that is final and starts at a BOUNDARY,
+// with out_cap = ~0.  Three equalities carry that, and the model sweeps them: gzfile_parts_hop(.., true) is gzfile_hop;
+// gzfile_parts_serial_verdict(in_len, true, S, ~0, ..) is WHOLE exactly where gzfile_serial_whole holds, LONG elsewhere
+// and never OPEN; gzfile_parts_serial_from(in_len, false, none, off, v != OPEN, ..) is in_len if none, else off, with
+// no OPEN stop -- gzfile_serial_walk's find_from.
 //
 // It joins gzfile_serial_rule.h (the serial range, the whole test, the record of a whole member) and
 // gzfile_parts_rule.h (THE PARTS HOP, the call) over one part in[0, in_len): every offset p that passes the header rule

@@ -1,6 +1,8 @@
 // gzfile_rule.h -- how the units of a gzip FILE chain across its members (flate_hip_gzfile_index / _read), written
-// ONCE: plain C++17 without HIP, compiled into the link kernel (gzfile_kernels.hip), into the library's host code and
-// into tests/host_model/gzfile_rule_model.cpp, which compares it with the walk of tests/gzfile_ref.py.
+// ONCE: plain C++17 without HIP, compiled into the kernels (gzfile_kernels.hip), into the library's host code and
+// into tests/host_model/gzfile_rule_model.cpp, which compares it with the walk of tests/gzfile_ref.py.  The link kernel
+// takes THE HOP through gzfile_parts_rule.h: the whole file is the part that is final, and gzfile_parts_hop(.., true)
+// equals gzfile_hop in all three fields (tests/host_model/gzfile_parts_serial_rule_model.cpp sweeps it).
 //
 // Inside a member the units chain as the units of one stream do (deflate_block_rule.h): a unit that stops in front of
 // a dynamic block header is followed by the unit that starts at that bit.  A unit that ends with BFINAL ends its

@@ -1,7 +1,7 @@
 // gzfile_serial_rule.h -- which members of a gzip FILE are decoded WHOLE (flate_hip_gzfile_index / _read with the
 // option "gzfile_serial_max" = S >= 1), written ONCE: plain C++17 without HIP, compiled into the kernels
-// (gzfile_serial_kernels.hip), into the library's host code and into tests/host_model/gzfile_serial_rule_model.cpp,
-// which compares it with the model of tests/gzfile_serial_ref.py.
+// (gzfile_serial_kernels.hip; the walk's, through gzfile_parts_serial_rule.h), into the library's host code and into
+// tests/host_model/gzfile_serial_rule_model.cpp, which compares it with the model of tests/gzfile_serial_ref.py.
 //
 // A member whose header starts at byte p and is hl bytes long is given the SERIAL RANGE in[p + hl, E) with
 // E = min(in_len - 8, p + S): the file's last 8 bytes can only be a trailer, and header and raw stream together get

@@ -11,6 +11,8 @@
 //     R in_len final out_cap        one call on the part of in_len bytes that begins where the reader stands
 //         -> "rc in_used out_len n_members n_units bad_member err_off stream_err_off serial_members open_stop find_from"
 //   gzfile_parts_serial_rule_model checks   one line per argument-check call: name value
+//   gzfile_parts_serial_rule_model equalities   the whole file as the part that is final and starts at a BOUNDARY: one
+//                                   line per equality: name cases mismatches, then how often each answer occurred
 // The driver of R builds what the discovery over the part yields -- a WHOLE member as one unit with its phase-1 record,
 // every other member's units that are complete in the part's raw range, the chain's end by the hop with the OPEN stop
 // -- and follows flate_hip_gzfile_reader_read step by step; every decision in it is the rule's.  The part lies in an
@@ -338,8 +340,80 @@ static int checks() {
   return 0;
 }
 
+// THE THREE EQUALITIES the kernels rest on when they run the whole file as the part that is final and starts at a
+// BOUNDARY.  One line each: name, the cases swept, the mismatches, then how often each answer occurred.
+static int equalities() {
+  // 1. gzfile_parts_hop(.., final) == gzfile_hop in all three fields, at every end bit of hand-built buffers: four
+  // bytes of a stream, a trailer, and behind it ...
+  const std::vector<uint8_t> head = {0x1f, 0x8b, 8, 0, 0, 0, 0, 0, 0, 3};
+  std::vector<std::vector<uint8_t>> tails;
+  tails.push_back({});                                       // ... the end
+  tails.push_back(head), tails.back().resize(head.size() + 9, 0x55);  // ... a good header (a raw byte, a trailer)
+  tails.push_back({0x00, 0x1f, 0x8b, 8, 0});                 // ... a bad byte
+  tails.push_back({0x1f, 0x8b, 8});                          // ... a header cut in its fixed bytes
+  tails.push_back(head), tails.back().resize(head.size() + 7, 0x55);  // ... a header with no room for a trailer
+  tails.push_back(head), tails.back()[3] = 8, tails.back().resize(head.size() + 12, 0x41);  // ... FNAME without its NUL
+  tails.push_back(head), tails.back()[3] = 0x20;             // ... a reserved FLG bit
+  unsigned long long cases = 0, bad = 0, kinds[3] = {0, 0, 0}, beyond = 0;
+  for (const std::vector<uint8_t> &tail : tails) {
+    std::vector<uint8_t> buf(4 + kGzipTrailerLen, 0xaa);
+    buf.insert(buf.end(), tail.begin(), tail.end());
+    if (buf.size() > 64) return 3;
+    uint8_t *m = exact(buf.data(), buf.size());
+    Free guard{m};
+    const uint64_t n = buf.size();
+    for (uint64_t b = 0; b <= 8 * n + 8; ++b) {  // (the last ones: e > in_len)
+      const GzHop x = gzfile_hop(m, n, b), y = gzfile_parts_hop(m, n, b, true);
+      ++cases;
+      if (x.kind != y.kind || x.e != y.e || x.bit != y.bit || x.kind > kGzHopNext) ++bad;
+      else ++kinds[x.kind];
+      if (x.e > n) ++beyond;
+    }
+  }
+  printf("hop %llu %llu end %llu dead %llu next %llu beyond %llu\n", cases, bad, kinds[kGzHopEnd], kinds[kGzHopDead],
+         kinds[kGzHopNext], beyond);
+
+  // 2. gzfile_parts_serial_verdict(in_len, final, S, ~0, ..) is WHOLE exactly where gzfile_serial_whole holds, LONG
+  // elsewhere, never OPEN
+  cases = bad = 0;
+  unsigned long long n_whole = 0, n_long = 0;
+  const int32_t statuses[] = {0, kPartsCorrupt, kPartsEof, kPartsOutTooSmall, kPartsTooLarge};
+  const uint64_t Ss[] = {1, 5, 16, 30, 64, kGzSerialMax}, hls[] = {0, 10, 12, 19}, outs[] = {0, 7, 1ull << 33, ~0ull};
+  for (uint64_t in_len = 0; in_len <= 48; ++in_len)
+    for (uint64_t p = 0; p <= in_len; ++p)
+      for (uint64_t S : Ss)
+        for (uint64_t hl : hls)
+          for (int32_t st : statuses)
+            for (uint64_t used = 0; used <= in_len + 1; ++used)
+              for (uint64_t out : outs) {
+                const uint32_t v = gzfile_parts_serial_verdict(in_len, true, S, ~0ull, p, hl, st, used, out);
+                const bool whole = gzfile_serial_whole(st, p, hl, used, gzfile_serial_end(in_len, p, S));
+                ++cases;
+                if (v != (whole ? kGzPartWhole : kGzPartLong)) ++bad;
+                whole ? ++n_whole : ++n_long;
+              }
+  printf("verdict %llu %llu whole %llu long %llu\n", cases, bad, n_whole, n_long);
+
+  // 3. gzfile_parts_serial_from at a BOUNDARY with a verdict that is not OPEN: in_len if the walk rested nowhere, else
+  // where it rested, and no OPEN stop -- what the whole call's from kernel computed before it took the part's form
+  cases = bad = 0;
+  const uint64_t lens[] = {0, 1, 18, 77, 1ull << 40};
+  for (uint64_t in_len : lens)
+    for (uint64_t off : lens)
+      for (int none = 0; none < 2; ++none)
+        for (uint32_t v : {kGzPartLong, kGzPartWhole}) {
+          uint32_t open_stop = 7;
+          const uint64_t from = gzfile_parts_serial_from(in_len, false, none != 0, off, v, &open_stop);
+          ++cases;
+          if (from != (none ? in_len : off) || open_stop != 0) ++bad;
+        }
+  printf("from %llu %llu\n", cases, bad);
+  return 0;
+}
+
 int main(int argc, char **argv) {
   if (argc == 3 && !strcmp(argv[1], "run")) return run(argv[2]);
   if (argc == 2 && !strcmp(argv[1], "checks")) return checks();
+  if (argc == 2 && !strcmp(argv[1], "equalities")) return equalities();
   return 2;
 }

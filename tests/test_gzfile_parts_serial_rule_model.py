@@ -141,6 +141,36 @@ def test_long_and_short_members_at_cuts_every_997_bytes(exe, tmp_path):
     rec.check(exe, tmp_path, "mixed_file")
 
 
+# ---- the whole file is the part that is final and starts at a BOUNDARY: what the one set of kernels rests on ----
+
+@pytest.fixture(scope="module")
+def equalities(exe):
+    lines = subprocess.check_output([exe, "equalities"]).decode().split("\n")[:-1]
+    return {t[0]: t[1:] for t in (line.split() for line in lines)}
+
+
+def test_the_parts_hop_of_a_final_part_is_the_hop(equalities):
+    """Every end bit of seven buffers of at most 64 bytes: a trailer, then the end, a good header, a bad byte, a header
+    cut in three ways or a reserved FLG bit; kind, e and bit agree, and every kind and e > in_len occur."""
+    t = equalities["hop"]
+    assert int(t[0]) > 1000 and int(t[1]) == 0, t
+    assert t[2::2] == ["end", "dead", "next", "beyond"] and all(int(x) > 0 for x in t[3::2]), t
+
+
+def test_the_verdict_of_a_final_part_without_a_cap_is_the_whole_test(equalities):
+    """in_len <= 48, every p and used, four header lengths, five statuses, six S, four sizes: WHOLE exactly where
+    gzfile_serial_whole holds, LONG elsewhere, never OPEN."""
+    t = equalities["verdict"]
+    assert int(t[0]) > 1000000 and int(t[1]) == 0, t
+    assert t[2::2] == ["whole", "long"] and all(int(x) > 0 for x in t[3::2]), t
+
+
+def test_find_from_at_a_boundary_without_an_open_member(equalities):
+    """in_len where the walk rested nowhere, else where it rested, and no OPEN stop."""
+    t = equalities["from"]
+    assert int(t[0]) == 100 and int(t[1]) == 0, t
+
+
 def test_argument_checks(exe):
     got = dict(line.split() for line in subprocess.check_output([exe, "checks"]).decode().split("\n")[:-1])
     ok = {k for k, v in got.items() if v == "0"}

@@ -2,7 +2,7 @@
 """The launches of the unit discoveries and the unit-round loops, for a comparison of two builds of the library.
 
     rocprofv3 --kernel-trace -d DIR -o p --output-format csv -- python tools/unit_rounds_trace.py run
-    python tools/unit_rounds_trace.py compare A_kernel_trace.csv B_kernel_trace.csv [--out DIR]
+    python tools/unit_rounds_trace.py compare A_kernel_trace.csv B_kernel_trace.csv [--out DIR] [--map FILE]
 
 `run` builds one fixed small input per entry point that goes over units in rounds -- seven chunks of seeded text,
 compressed by zlib on the CPU with a full flush behind each, so that every chunk is one dynamic block and one unit --
@@ -17,14 +17,19 @@ units are the archive's one entry) and makes one call each:
   J flate_hip_one_reader_* over A's stream in three parts cut inside units, K flate_hip_gzfile_reader_* over D's file in
     three parts -- one cut inside a member, one inside a gzip header -- with room for one unit a call, so that calls
     deliver fewer units than they found;
-  L A and D's first read once more with DEVICE pointers (A to G pass host pointers: the output is staged and comes down).
+  L A and D's first read once more with DEVICE pointers (A to G pass host pointers: the output is staged and comes down);
+  M flate_hip_gzfile_reader_* with set_serial_max over forty short members in three parts (cuts inside members: a call
+    stops in front of an OPEN member, the next one starts at its header).
 Every result is compared with the input.  FLATE_HIP_LIB chooses the library, as for every tool here.
 
 `compare` reads the kernel traces of two such runs and holds the ordered lists of (kernel name, grid size, workgroup
-size) against each other; with --out it writes both lists and a one-line verdict there.  No counters, no times."""
+size) against each other; with --out it writes both lists and a one-line verdict there.  --map FILE: lines "old new" of
+kernels that the second build has under another name (several old names may share a new one); a kernel on either side
+of the map is compared by its name without its parameter list, which changes with the merge.  No counters, no times."""
 import argparse
 import csv
 import os
+import re
 import struct
 import sys
 import zlib
@@ -64,6 +69,14 @@ def archive(raw, plain):
     central = struct.pack("<4sHHHHHHIIIHHHHHII", b"PK\1\2", 20, 20, 0x0800, 8, 0, 0x0021, crc, len(raw), len(plain),
                           len(name), 0, 0, 0, 0, 0, 0) + name
     return local + raw + central + struct.pack("<4sHHHHIIH", b"PK\5\6", 0, 0, 1, 1, len(central), len(local) + len(raw), 0)
+
+
+def forty_members():
+    """Forty gzip members of 200 .. 900 bytes of text, zlib level 6 -> (file, plain)."""
+    import random
+    rng = random.Random(40)
+    plain = [text(rng.randrange(200, 901), 400 + k) for k in range(40)]
+    return b"".join(member([p]) for p in plain), b"".join(plain)
 
 
 def run():
@@ -143,6 +156,16 @@ def run():
     check("L inflate_one, device pointers", r.rc == 0 and bytes(out[:r.out_len].cpu().numpy()) == plain, r.n_units)
     out, r = eng.gzfile_read(dev(members), out=room())
     check("L gzfile_read, device pointers", r.rc == 0 and bytes(out[:r.out_len].cpu().numpy()) == plain, r.n_units)
+    forty, forty_plain = forty_members()                                                    # M
+    got, pos, rd = b"", 0, eng.open_gzfile_reader(serial_max=4096)
+    for end in (len(forty) // 3, 2 * len(forty) // 3, len(forty)):
+        for _ in range(4):  # (a call that stops in front of an OPEN member is made again with the rest)
+            used, out, r = rd.read(forty[pos:end], final=end == len(forty))
+            got, pos = got + bytes(out), pos + used
+            if r.rc != 0 or used == 0 or pos == end:
+                break
+    rd.close()
+    check("M gzfile reader with whole members in three parts", r.rc == 1 and got == forty_plain and pos == len(forty))
     eng.close()
     print("unit_rounds_trace: %d calls ok (%s)" % (len(done), "; ".join(done)))
 
@@ -156,8 +179,21 @@ def launches(path):
     return [(r["Kernel_Name"], dims(r, "Grid"), dims(r, "Workgroup")) for r in rows]
 
 
-def compare(a, b, out):
+def base_name(kernel):
+    words = re.findall(r"[A-Za-z_]\w*", kernel.split("(")[0])
+    return words[-1] if words else kernel
+
+
+def compare(a, b, out, rename=None):
     la, lb = launches(a), launches(b)
+    names = {}
+    if rename:
+        with open(rename) as f:
+            names = dict(line.split() for line in f if line.strip() and not line.startswith("#"))
+    merged = set(names) | set(names.values())
+    norm = lambda x: (names.get(base_name(x[0]), base_name(x[0])),) + x[1:] if base_name(x[0]) in merged else x
+    full_a, full_b = la, lb
+    la, lb = [norm(x) for x in la], [norm(x) for x in lb]
     first = next((i for i, (x, y) in enumerate(zip(la, lb)) if x != y), None)
     if first is None and len(la) != len(lb):
         first = min(len(la), len(lb))
@@ -165,7 +201,7 @@ def compare(a, b, out):
         "DIFFERENT at launch %d of %d / %d: %s | %s" % (first, len(la), len(lb), la[first:first + 1], lb[first:first + 1])
     if out:
         os.makedirs(out, exist_ok=True)
-        for name, l in (("launches_parent.txt", la), ("launches_new.txt", lb)):
+        for name, l in (("launches_parent.txt", full_a), ("launches_new.txt", full_b)):
             with open(os.path.join(out, name), "w") as f:
                 f.writelines("%s\t%s\t%s\n" % x for x in l)
         with open(os.path.join(out, "verdict.txt"), "w") as f:
@@ -182,5 +218,6 @@ if __name__ == "__main__":
     c.add_argument("parent")
     c.add_argument("new")
     c.add_argument("--out")
+    c.add_argument("--map")
     args = ap.parse_args()
-    sys.exit(run() if args.cmd == "run" else compare(args.parent, args.new, args.out))
+    sys.exit(run() if args.cmd == "run" else compare(args.parent, args.new, args.out, args.map))
