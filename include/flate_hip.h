@@ -502,8 +502,8 @@ int flate_hip_deflate_fast_grouped_framed(flate_hip_ctx *ctx, const uint8_t *in,
  *     reset.  The stream itself may be of any length: positions are 64-bit.
  *   Host waits per call: one read-back of the result words (device pointers), plus the download (host pointers).  The
  *     carry byte, the running checksum, the length and the emitted byte count never pass through the host.
- *   Out of scope: pieces that share history, dictionaries, several members, BGZF, overlapping the upload of part k + 1
- *     with the compression of part k, range reads through the writer's index, the MoonBit binding. */
+ *   Out of scope: pieces that share history, dictionaries, several members (BGZF in parts: flate_hip_bgzf_writer_*),
+ *     overlapping the upload of part k + 1 with the compression of part k, range reads through the writer's index, the MoonBit binding. */
 typedef struct flate_hip_one_writer flate_hip_one_writer;
 size_t flate_hip_one_writer_bound(size_t in_len, size_t piece_bytes);
 int flate_hip_one_writer_open(flate_hip_ctx *ctx, uint32_t wrap, uint64_t piece_bytes, uint32_t flags,
@@ -750,6 +750,82 @@ int flate_hip_bgzf_read_ranges(flate_hip_ctx *ctx, const uint8_t *in, uint64_t i
                                uint8_t *out, uint64_t out_cap, uint64_t *out_off, int32_t *range_status,
                                uint32_t *n_members, uint32_t *n_decoded, uint32_t *bad_member,
                                int64_t *err_off, uint32_t flags);
+
+/* -- BGZF files in PARTS: read and written through bounded buffers ---------------------
+ * BAM, bgzipped VCF and tabix-indexed tables run to hundreds of gigabytes; these handles stream one through two fixed
+ * buffers.  A handle is a few host words: nothing of it lives on the device or in the ctx's scratch, so any other call
+ * on the ctx may run between two calls of a handle.  `flags` is fixed at open.
+ *
+ * flate_hip_bgzf_reader_read -- one call is flate_hip_bgzf_read on the part in[0, in_len); the conventions are
+ * flate_hip_gzfile_reader_read's.  `in` begins with the bytes the last call left unused (*in_used says how many were
+ * used); final_in != 0: the file ends with this part.  flags: a subset of FLATE_HIP_DEVICE_PTRS.
+ *   THE CONTRACT.  Let F be the concatenation of everything consumed.  The serial walk of flate_hip_bgzf_index over F
+ *     defines the members.  The concatenation of every call's out[0, *out_len) is the output of F's members IN FRONT OF
+ *     THE FIRST FAILURE in file order, for every cut and every out_cap.  A failure is a position where no member can
+ *     stand, or a member that does not decode or verify (status per member as flate_hip_inflate_batch_framed defines
+ *     it).  The call that reaches the failure delivers the good members in front of it, returns the error, sets
+ *     *bad_member to the member's number counted over the FILE and *err_off to its FILE offset (or to the offset where
+ *     no member could be read), and *in_used = 0.  THE ONE DIFFERENCE from flate_hip_bgzf_read: the whole call delivers
+ *     nothing for a broken chain and everything around a bad member; only "everything in front" can be the same for
+ *     every cut.  On success the *in_used of all calls sum to F's length.
+ *   The part's end.  A member that the part cuts is left unused: *in_used stops in front of it.  Where the walk finds
+ *     no member at offset p of the part: p == in_len is a boundary; on a final part, or with in_len - p >=
+ *     FLATE_HIP_BGZF_MEMBER_MAX (a member is at most that long: no continuation can put one there), it is
+ *     FLATE_HIP_E_CORRUPT at p; else nothing is wrong yet and the next part begins at p.  No finer test of a cut header
+ *     is made: every cut gives the same bytes and the same final verdict, a malformed file is only reported one call
+ *     later.  THE PROGRESS RULE: a part of at least 65536 bytes, or a final one, always makes progress or gives a
+ *     verdict (given room for its first member).
+ *   Delivery.  Of the whole members of the part a call delivers the longest prefix whose output fits out_cap (the sums
+ *     of ISIZE) and whose index fits index_cap; empty members are delivered as far as they go.  *n_members = that
+ *     count.  If not even the first fits: FLATE_HIP_E_OUT_TOO_SMALL with *out_len = its ISIZE and *in_used = 0 --
+ *     repeatable, nothing changes.  Nothing outside out[0, *out_len of a clean call) is written, with device pointers
+ *     too, and that is at most out_cap.
+ *   Returns FLATE_HIP_OK: call again.  FLATE_HIP_STREAM_END: a final call that delivered every member up to in_len
+ *     (an empty file -- a final call without bytes on a fresh handle -- included); sticky.  The file's error: sticky,
+ *     every later call returns it with the same words, *in_used = 0 and *out_len = 0.  Repeatable and changing
+ *     nothing: FLATE_HIP_E_INVALID (a NULL handle or pointer, one index array without the other, index_cap == 0 with
+ *     arrays; decided before any HIP call), FLATE_HIP_E_OUT_TOO_SMALL as above, FLATE_HIP_E_HIP.  The repeatable codes
+ *     leave *bad_member = 0xffffffff: a sticky FLATE_HIP_E_OUT_TOO_SMALL (a member produced more than its ISIZE)
+ *     names the member.  *eof_marker = 1 if the last member delivered so far is the canonical 28 bytes.
+ *   The file's index while streaming.  member_off and out_off: both NULL, or HOST arrays of index_cap entries.  A call
+ *     that delivers k members writes k + 1 entries in FILE coordinates -- compressed and uncompressed offsets, what a
+ *     .gzi holds and the halves of a virtual offset; the last entry of one call equals the first of the next (a call
+ *     that delivers nothing, a sticky one included, writes the one entry where the file stands).
+ *     index_cap < k + 1 clips the delivery to index_cap - 1 members, exactly as out_cap does.
+ *   Out of scope: ranges in parts; overlapping the upload of part k + 1 with the work on part k; a .gzi or .bai
+ *     writer (the arrays are there, the file formats are not); the MoonBit binding. */
+typedef struct flate_hip_bgzf_reader flate_hip_bgzf_reader;
+int flate_hip_bgzf_reader_open(flate_hip_ctx *ctx, uint32_t flags, flate_hip_bgzf_reader **reader);
+int flate_hip_bgzf_reader_read(flate_hip_bgzf_reader *reader, const uint8_t *in, uint64_t in_len, int final_in,
+                               uint8_t *out, uint64_t out_cap, uint64_t *in_used, uint64_t *out_len,
+                               uint64_t index_cap, uint64_t *member_off, uint64_t *out_off, uint32_t *n_members,
+                               uint32_t *bad_member, int64_t *err_off, int *eof_marker);
+int flate_hip_bgzf_reader_reset(flate_hip_bgzf_reader *reader);
+void flate_hip_bgzf_reader_free(flate_hip_bgzf_reader *reader);
+
+/* flate_hip_bgzf_writer_write -- the conventions are flate_hip_one_writer_write's; block_bytes and flags are
+ * flate_hip_bgzf_write's.  A call that is not final consumes the k = in_len / block_bytes whole blocks its part holds
+ * (*in_used = k * block_bytes; with in_len < block_bytes: FLATE_HIP_OK, nothing written, nothing launched) and writes
+ * NO marker.  A final call consumes everything and ends with the 28-byte marker; without bytes it writes the marker
+ * alone.  It returns FLATE_HIP_STREAM_END; after that every write is FLATE_HIP_E_INVALID until reset.  *n_blocks = the
+ * members written (the marker not counted; may be NULL).
+ *   THE FILE: the concatenation of every call's out[0, *out_len) is, byte for byte, what flate_hip_bgzf_write writes
+ *     for the whole input with the same block_bytes and flags, for ANY cut: the blocks are independent.
+ *   member_off: NULL, or a HOST array with room for in_len / block_bytes + 2 entries: the members' FILE offsets and
+ *     where the next member, or the marker, starts.
+ *   Room: flate_hip_bgzf_writer_bound(in_len, block_bytes) always holds a call's output.  Too little:
+ *     FLATE_HIP_E_OUT_TOO_SMALL; a block that 65536 bytes cannot express: FLATE_HIP_E_TOO_LARGE, as in the whole call.
+ *     Both, FLATE_HIP_E_INVALID and FLATE_HIP_E_HIP are repeatable and leave the handle unchanged.
+ *   Out of scope: overlapping the upload of part k + 1 with the work on part k; a .gzi or .bai writer; the MoonBit
+ *     binding. */
+typedef struct flate_hip_bgzf_writer flate_hip_bgzf_writer;
+size_t flate_hip_bgzf_writer_bound(uint64_t in_len, uint32_t block_bytes);
+int flate_hip_bgzf_writer_open(flate_hip_ctx *ctx, uint32_t block_bytes, uint32_t flags, flate_hip_bgzf_writer **writer);
+int flate_hip_bgzf_writer_write(flate_hip_bgzf_writer *writer, const uint8_t *in, uint64_t in_len, int final_in,
+                                uint8_t *out, uint64_t out_cap, uint64_t *in_used, uint64_t *out_len,
+                                uint64_t *member_off, uint32_t *n_blocks);
+int flate_hip_bgzf_writer_reset(flate_hip_bgzf_writer *writer);
+void flate_hip_bgzf_writer_free(flate_hip_bgzf_writer *writer);
 
 /* -- Plain multi-member gzip files: indexed and read in one call each -----------------
  * The gzip files people have -- `cat a.gz b.gz`, rotated logs, Hadoop part files, WARC / WET records, the concatenated

@@ -109,6 +109,15 @@ def _signatures():
         "flate_hip_one_writer_write": (i, [vp, vp, u64, i, vp, u64, u64p, u64p, vp, u32p]),
         "flate_hip_one_writer_reset": (i, [vp]),
         "flate_hip_one_writer_free": (None, [vp]),
+        "flate_hip_bgzf_reader_open": (i, [vp, u32, vpp]),
+        "flate_hip_bgzf_reader_read": (i, [vp, vp, u64, i, vp, u64, u64p, u64p, u64, vp, vp, u32p, u32p, i64p, ip]),
+        "flate_hip_bgzf_reader_reset": (i, [vp]),
+        "flate_hip_bgzf_reader_free": (None, [vp]),
+        "flate_hip_bgzf_writer_bound": (sz, [u64, u32]),
+        "flate_hip_bgzf_writer_open": (i, [vp, u32, u32, vpp]),
+        "flate_hip_bgzf_writer_write": (i, [vp, vp, u64, i, vp, u64, u64p, u64p, vp, u32p]),
+        "flate_hip_bgzf_writer_reset": (i, [vp]),
+        "flate_hip_bgzf_writer_free": (None, [vp]),
     }
 
 
@@ -132,7 +141,10 @@ MAY_BE_MISSING = [
     "flate_hip_one_writer_free", "flate_hip_seek_windows_pack_bound", "flate_hip_seek_windows_pack",
     "flate_hip_seek_windows_unpack", "flate_hip_inflate_one_ranges_packed", "flate_hip_gzfile_reader_open",
     "flate_hip_gzfile_reader_read", "flate_hip_gzfile_reader_reset", "flate_hip_gzfile_reader_free",
-    "flate_hip_gzfile_reader_set_serial_max", "flate_hip_gzfile_reader_last_route",
+    "flate_hip_gzfile_reader_set_serial_max", "flate_hip_gzfile_reader_last_route", "flate_hip_bgzf_reader_open",
+    "flate_hip_bgzf_reader_read", "flate_hip_bgzf_reader_reset", "flate_hip_bgzf_reader_free",
+    "flate_hip_bgzf_writer_bound", "flate_hip_bgzf_writer_open", "flate_hip_bgzf_writer_write",
+    "flate_hip_bgzf_writer_reset", "flate_hip_bgzf_writer_free",
 ]
 
 _lib = None

@@ -11,8 +11,8 @@ LIB_PATH = os.path.join(LIB_DIR, "libflate_hip.so")
 
 SOURCES = ["lz77_kernels.hip",  "huff_pack_kernels.hip", "compact_kernels.hip",
            "inflate_kernels.hip", "splice_kernels.hip", "flate_api.hip", "flate_api_deflate.hip", "flate_api_inflate.hip", "flate_api_units.hip", "gather.hip", "checksum.hip",
-           "frame_kernels.hip", "chain_kernels.hip", "bgzf_kernels.hip", "bgzf_range_kernels.hip", "gzip_kernels.hip", "one_kernels.hip", "one_stored_kernels.hip", "one_parts_kernels.hip", "one_writer_kernels.hip", "one_seek_kernels.hip", "seek_pack_kernels.hip", "gzfile_kernels.hip", "gzfile_serial_kernels.hip", "gzfile_parts_kernels.hip", "gzfile_parts_serial_kernels.hip", "gzfile_seek_kernels.hip", "zip_kernels.hip", "zip_units_kernels.hip", "flate_api_zip.hip", "synth.cpp"]
-HEADERS = ["flate_common.h", "flate_kernels.h", "flate_ctx.h", "api_checks.h", "deflate_plan.h", "inflate_route.h", "checksum_clip.h", "bgzf_rule.h", "bgzf_range_rule.h", "gzip_rule.h", "gzfile_rule.h", "gzfile_serial_rule.h", "gzfile_parts_rule.h", "gzfile_parts_serial_rule.h", "gzfile_seek_rule.h", "deflate_block_rule.h", "window_compose.h", "seek_index_rule.h", "seek_pack_rule.h", "one_parts_rule.h", "one_writer_rule.h", "zip_rule.h", "zip_units_rule.h", "zip_kernels.h", "block_scan.h", "chain_rule.h", "chain_walk.h", "carve.h", "unit_rounds.h", "unit_discovery.h", "unit_discovery_rule.h", "lz77_device.h", "lz77_chase_rule.h", "splice_rule.h",
+           "frame_kernels.hip", "chain_kernels.hip", "bgzf_kernels.hip", "bgzf_range_kernels.hip", "bgzf_parts_kernels.hip", "gzip_kernels.hip", "one_kernels.hip", "one_stored_kernels.hip", "one_parts_kernels.hip", "one_writer_kernels.hip", "one_seek_kernels.hip", "seek_pack_kernels.hip", "gzfile_kernels.hip", "gzfile_serial_kernels.hip", "gzfile_parts_kernels.hip", "gzfile_parts_serial_kernels.hip", "gzfile_seek_kernels.hip", "zip_kernels.hip", "zip_units_kernels.hip", "flate_api_zip.hip", "synth.cpp"]
+HEADERS = ["flate_common.h", "flate_kernels.h", "flate_ctx.h", "api_checks.h", "deflate_plan.h", "inflate_route.h", "checksum_clip.h", "bgzf_rule.h", "bgzf_range_rule.h", "bgzf_parts_rule.h", "gzip_rule.h", "gzfile_rule.h", "gzfile_serial_rule.h", "gzfile_parts_rule.h", "gzfile_parts_serial_rule.h", "gzfile_seek_rule.h", "deflate_block_rule.h", "window_compose.h", "seek_index_rule.h", "seek_pack_rule.h", "one_parts_rule.h", "one_writer_rule.h", "zip_rule.h", "zip_units_rule.h", "zip_kernels.h", "block_scan.h", "chain_rule.h", "chain_walk.h", "carve.h", "unit_rounds.h", "unit_discovery.h", "unit_discovery_rule.h", "lz77_device.h", "lz77_chase_rule.h", "splice_rule.h",
            "inflate_spec_kernel.inc", "inflate_stream_kernel.inc", "one_probe_kernel.inc", "seek_pack_mark_kernel.inc", "one_find_kernel.inc", os.path.join(ROOT, "include", "flate_hip.h")]
 
 
@@ -25,7 +25,7 @@ GROUPS = {  # which sources a kernel family's measurements depend on (besides th
                 "gzfile_parts_serial_kernels.hip", "gzfile_parts_serial_rule.h",
                 "deflate_block_rule.h", "window_compose.h", "chain_kernels.hip", "chain_walk.h", "chain_rule.h", "carve.h", "unit_rounds.h", "unit_discovery.h", "unit_discovery_rule.h", "block_scan.h"],
     "checksum": ["checksum.hip", "checksum_clip.h", "block_scan.h", "carve.h"],
-    "frame": ["frame_kernels.hip", "one_writer_kernels.hip", "one_writer_rule.h", "bgzf_kernels.hip", "bgzf_range_kernels.hip", "bgzf_rule.h", "bgzf_range_rule.h",
+    "frame": ["frame_kernels.hip", "one_writer_kernels.hip", "one_writer_rule.h", "bgzf_kernels.hip", "bgzf_range_kernels.hip", "bgzf_rule.h", "bgzf_range_rule.h", "bgzf_parts_kernels.hip", "bgzf_parts_rule.h",
               "gzip_kernels.hip", "gzip_rule.h", "gzfile_kernels.hip", "gzfile_rule.h", "gzfile_serial_kernels.hip", "gzfile_serial_rule.h", "gzfile_seek_kernels.hip", "gzfile_seek_rule.h",
               "gzfile_parts_kernels.hip", "gzfile_parts_rule.h", "gzfile_parts_serial_kernels.hip", "gzfile_parts_serial_rule.h",
               "zip_kernels.hip", "zip_kernels.h", "zip_rule.h", "zip_units_kernels.hip", "zip_units_rule.h", "flate_api_zip.hip", "checksum.hip", "checksum_clip.h", "flate_api_inflate.hip", "flate_api_units.hip",

@@ -4,6 +4,7 @@
 
 #include <stdint.h>
 
+#include "bgzf_parts_rule.h"
 #include "flate_hip.h"
 #include "gzfile_parts_rule.h"
 #include "gzfile_parts_serial_rule.h"
@@ -138,6 +139,28 @@ inline int bgzf_ranges_args(const uint8_t *in, uint64_t in_len, uint32_t pos_kin
   for (uint32_t r = 0; r < n_ranges; ++r)
     if (begin[r] > end[r]) return FLATE_HIP_E_INVALID;
   return FLATE_HIP_OK;
+}
+// flate_hip_bgzf_reader_* / flate_hip_bgzf_writer_* (bgzf_parts_rule.h): everything that is refused before any HIP
+// call.  member_off and out_off come together or not at all, and then with room for one entry at least; a writer that
+// has ended (a successful final call) refuses every write until reset.
+inline int bgzf_reader_open_args(const void *ctx, uint32_t flags, const void *reader) {
+  return bgzf_parts_reader_open_args(ctx, flags, FLATE_HIP_DEVICE_PTRS, reader) ? FLATE_HIP_E_INVALID : FLATE_HIP_OK;
+}
+inline int bgzf_reader_read_args(const void *reader, const uint8_t *in, uint64_t in_len, const uint8_t *out, uint64_t out_cap,
+                                 const uint64_t *in_used, const uint64_t *out_len, uint64_t index_cap,
+                                 const uint64_t *member_off, const uint64_t *out_off) {
+  return bgzf_parts_reader_read_args(reader, in, in_len, out, out_cap, in_used, out_len, index_cap, member_off, out_off)
+             ? FLATE_HIP_E_INVALID
+             : FLATE_HIP_OK;
+}
+inline int bgzf_writer_open_args(const void *ctx, uint32_t block_bytes, uint32_t flags, const void *writer) {
+  return bgzf_parts_writer_open_args(ctx, bgzf_block_bytes(block_bytes), flags, FLATE_HIP_DEVICE_PTRS | FLATE_HIP_COMPAT_GO, writer)
+             ? FLATE_HIP_E_INVALID
+             : FLATE_HIP_OK;
+}
+inline int bgzf_writer_write_args(const void *writer, const uint8_t *in, uint64_t in_len, const uint8_t *out,
+                                  const uint64_t *in_used, const uint64_t *out_len, bool ended) {
+  return bgzf_parts_writer_write_args(writer, in, in_len, out, in_used, out_len, ended) ? FLATE_HIP_E_INVALID : FLATE_HIP_OK;
 }
 // how many candidates the discovery arrays hold on the first attempt (real files: one member per tens of KiB; a file
 // of nothing but empty members has one per 28 bytes and takes the second attempt, sized from the count)

@@ -676,7 +676,7 @@ int deflate_common(flate_hip_ctx *c, const EncCall &A, const DeflDict *DD = null
   if (A.spliced && !ZR && (rc = ctl_down(c, &c->h_total_bytes, (uint64_t *)c->d_out_len.p + n, 8))) return rc;
   if (ZR && (rc = ctl_down(c, &c->h_total_bytes, &ZW.head->total, 8))) return rc;
   if ((rc = ctl_down(c, &c->h_status_word, c->d_status.p, 4))) return rc;
-  const bool bgzf = FR && FR->wrap == kWrapBgzf;
+  const bool bgzf = FR && frame_is_bgzf(FR->wrap);
   if (bgzf && (rc = ctl_down(c, &c->h_status_aux, (int *)c->d_status.p + 1, 4))) return rc;
   HIP_TRY(c, hipGetLastError());
   HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -687,7 +687,7 @@ int deflate_common(flate_hip_ctx *c, const EncCall &A, const DeflDict *DD = null
   // (a BGZF file: the members, then the EOF marker frame_write_kernel has put behind them)
   const uint64_t produced = ZR || grouped ? c->h_total_bytes
                             : A.spliced  ? c->h_total_bytes + f_hl + f_tl
-                                        : out_off[n] + (bgzf ? (uint64_t)kBgzfEofLen : 0ull);
+                                        : out_off[n] + (FR && FR->wrap == kWrapBgzf ? (uint64_t)kBgzfEofLen : 0ull);
   if (A.total_bytes) *A.total_bytes = produced;
   if (!dev) {
     HIP_TRY(c, hipMemcpyAsync(A.out, c->d_out.p, produced, hipMemcpyDeviceToHost, c->stream));
@@ -1592,6 +1592,84 @@ int flate_hip_bgzf_write(flate_hip_ctx *c, const uint8_t *in, uint64_t in_len, u
     if (!member_off) off.resize((size_t)n + 1), member_off = off.data();
     const FrameReq FR{kWrapBgzf, nullptr, nullptr, nullptr, 0};
     return deflate_common(c, {in, in_off.data(), n, out, out_cap, member_off, out_len, flags, false}, nullptr, &FR);
+  } catch (const std::exception &e) {  // (out of host memory in an index vector)
+    c->hip_err = e.what();
+    return FLATE_HIP_E_INTERNAL;
+  }
+}
+}  // extern "C"
+
+// ---- a BGZF file written in PARTS (bgzf_parts_rule.h) ----
+// The blocks are independent, so a call is flate_hip_bgzf_write over the whole blocks of its part; only the final call
+// writes the marker (kWrapBgzfOpen in front of it).  The handle is a few host words.
+struct flate_hip_bgzf_writer {
+  flate_hip_ctx *ctx = nullptr;
+  uint32_t bb = 0, flags = 0;
+  uint64_t file_off = 0;  // the bytes written so far: where the next member starts
+  bool ended = false;
+};
+
+extern "C" {
+
+size_t flate_hip_bgzf_writer_bound(uint64_t in_len, uint32_t block_bytes) { return flate_hip_bgzf_bound(in_len, block_bytes); }
+
+int flate_hip_bgzf_writer_open(flate_hip_ctx *c, uint32_t block_bytes, uint32_t flags, flate_hip_bgzf_writer **out) {
+  // every check before any HIP call (there is none)
+  if (bgzf_writer_open_args(c, block_bytes, flags, out)) return FLATE_HIP_E_INVALID;
+  flate_hip_bgzf_writer *w = new (std::nothrow) flate_hip_bgzf_writer();
+  if (!w) return FLATE_HIP_E_INTERNAL;
+  w->ctx = c, w->bb = bgzf_block_bytes(block_bytes), w->flags = flags;
+  *out = w;
+  return FLATE_HIP_OK;
+}
+
+int flate_hip_bgzf_writer_reset(flate_hip_bgzf_writer *w) {
+  if (!w) return FLATE_HIP_E_INVALID;
+  w->file_off = 0, w->ended = false;
+  return FLATE_HIP_OK;
+}
+
+void flate_hip_bgzf_writer_free(flate_hip_bgzf_writer *w) { delete w; }
+
+int flate_hip_bgzf_writer_write(flate_hip_bgzf_writer *w, const uint8_t *in, uint64_t in_len, int final_in, uint8_t *out,
+                                uint64_t out_cap, uint64_t *in_used, uint64_t *out_len, uint64_t *member_off,
+                                uint32_t *n_blocks) {
+  // every check, and everything the rule decides, before any HIP call
+  if (bgzf_writer_write_args(w, in, in_len, out, in_used, out_len, w && w->ended)) return FLATE_HIP_E_INVALID;
+  *in_used = 0, *out_len = 0;
+  if (n_blocks) *n_blocks = 0;
+  const bool fin = final_in != 0;
+  const uint64_t blocks = bgzf_writer_blocks(in_len, w->bb, fin), used = bgzf_writer_in_used(in_len, w->bb, fin);
+  if (blocks > 0xfffffffeull) return FLATE_HIP_E_TOO_LARGE;
+  const uint32_t n = (uint32_t)blocks;
+  flate_hip_ctx *c = w->ctx;
+  c->hip_err.clear();
+  auto done = [&](uint64_t bytes) {
+    w->file_off += bytes;
+    *in_used = used, *out_len = bytes;
+    if (n_blocks) *n_blocks = n;
+    if (fin) w->ended = true;
+    return fin ? FLATE_HIP_STREAM_END : FLATE_HIP_OK;
+  };
+  if (n == 0) {
+    if (member_off) member_off[0] = w->file_off;
+    if (!fin) return FLATE_HIP_OK;  // less than a block: nothing is written, nothing is launched
+    uint8_t eof[kBgzfEofLen];       // the marker alone
+    for (uint32_t i = 0; i < kBgzfEofLen; ++i) eof[i] = bgzf_eof_byte(i);
+    const int rc = emit_fixed(c, out, out_cap, eof, kBgzfEofLen, w->flags);
+    return rc ? rc : done(kBgzfEofLen);
+  }
+  try {
+    std::vector<uint64_t> in_off((size_t)n + 1), off((size_t)n + 1);
+    for (uint32_t k = 0; k < n; ++k) in_off[k] = (uint64_t)k * w->bb;
+    in_off[n] = used;
+    uint64_t bytes = 0;
+    const FrameReq FR{fin ? kWrapBgzf : kWrapBgzfOpen, nullptr, nullptr, nullptr, 0};
+    const int rc = deflate_common(c, {in, in_off.data(), n, out, out_cap, off.data(), &bytes, w->flags, false}, nullptr, &FR);
+    if (rc) return rc;  // (too little room, a block BSIZE cannot express: repeatable, the handle is unchanged)
+    if (member_off)
+      for (uint32_t k = 0; k <= n; ++k) member_off[k] = w->file_off + off[k];
+    return done(bytes);
   } catch (const std::exception &e) {  // (out of host memory in an index vector)
     c->hip_err = e.what();
     return FLATE_HIP_E_INTERNAL;

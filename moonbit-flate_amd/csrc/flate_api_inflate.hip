@@ -623,7 +623,10 @@ namespace {
 // the stream has drained (the call's synchronisation), P.member_off / P.out_off = the index, still on the device.  The
 // arrays are sized for bgzf_first_cap candidates; a file with more (H.n_cand, counted by the first attempt) takes a
 // second attempt sized from that count.  Counted in no profiling stage.
-int bgzf_discover(flate_hip_ctx *c, const uint8_t *d_in, uint64_t in_len, BgzfHead &H, BgzfParams &P) {
+// Q (flate_hip_bgzf_reader_read): d_in is a PART of a file -- the same launches with the part's finish and out-scan
+// kernels (bgzf_parts_kernels.hip), whose result words come back in *F beside H (of which n_cand alone is theirs).
+int bgzf_discover(flate_hip_ctx *c, const uint8_t *d_in, uint64_t in_len, BgzfHead &H, BgzfParams &P,
+                  BgzfPartParams *Q = nullptr, BgzfPartFound *F = nullptr) {
   int rc;
   P = BgzfParams{};
   ChainParams &C = P.C;
@@ -644,12 +647,24 @@ int bgzf_discover(flate_hip_ctx *c, const uint8_t *d_in, uint64_t in_len, BgzfHe
       k.take(P.isize, cap);
       k.take(C.member_off, (size_t)cap + 1);
       k.take(C.out_off, (size_t)cap + 1);
+      if (Q) {
+        k.take(Q->found, 1);
+        k.take(Q->idx_member_off, (size_t)cap + 1);
+        k.take(Q->idx_out_off, (size_t)cap + 1);
+      }
     });
     if (rc) return rc;
     hipLaunchKernelGGL(bgzf_count_kernel, dim3(C.n_tiles), dim3(256), 0, c->stream, P);
     hipLaunchKernelGGL(chain_scan_kernel, dim3(1), dim3(1024), 0, c->stream, C);
     hipLaunchKernelGGL(bgzf_fill_kernel, dim3(C.n_tiles), dim3(256), 0, c->stream, P);
-    if ((rc = chain_tail(c, C, bgzf_link_kernel, P, bgzf_finish_kernel, bgzf_out_scan_kernel, P))) return rc;
+    if (Q) {
+      Q->B = P;
+      rc = chain_tail(c, C, bgzf_link_kernel, P, bgzf_part_finish_kernel, bgzf_part_out_scan_kernel, *Q);
+      if (rc) return rc;
+      HIP_TRY(c, hipMemcpyAsync(F, Q->found, sizeof *F, hipMemcpyDeviceToHost, c->stream));
+    } else if ((rc = chain_tail(c, C, bgzf_link_kernel, P, bgzf_finish_kernel, bgzf_out_scan_kernel, P))) {
+      return rc;
+    }
     HIP_TRY(c, hipMemcpyAsync(&H, C.head, sizeof H, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     if (H.n_cand <= cap) return FLATE_HIP_OK;
@@ -664,10 +679,15 @@ int bgzf_discover(flate_hip_ctx *c, const uint8_t *d_in, uint64_t in_len, BgzfHe
 // whose output fits: d_member_off / d_out_off (n + 1 entries each) are the index, still on the device.  It comes back
 // once, 16 bytes per member -- the decoders' routing and the checksum plan are host code --, then the framed gzip read
 // runs over d_in (DEVICE memory: the caller's buffer or the staged copy) into the dense slots, and, for a host caller,
-// out[0, out_bytes) comes down once.  Returns the first non-zero member status, with that member's index and offset.
+// out[0, out_bytes) comes down once.  Returns the first non-zero member status, with that member's index and offset
+// (*bad, the reader in parts: also where its output would start and where the member in front of it lies).
+struct MembersBad {
+  uint32_t j = 0xffffffffu;  // the member, or 0xffffffff: none -- a non-zero return is the call's own failure
+  uint64_t member_off = 0, out_off = 0, prev_off = 0;
+};
 int members_read(flate_hip_ctx *c, const uint8_t *d_in, uint32_t n, const uint64_t *d_member_off,
                  const uint64_t *d_out_off, uint64_t out_bytes, uint8_t *out, uint32_t flags, uint32_t *bad_member,
-                 int64_t *err_off) {
+                 int64_t *err_off, MembersBad *bad = nullptr) {
   const bool dev = (flags & FLATE_HIP_DEVICE_PTRS) != 0;
   int rc;
   std::vector<uint64_t> moff((size_t)n + 1), ooff((size_t)n + 1), olen(n);
@@ -696,12 +716,20 @@ int members_read(flate_hip_ctx *c, const uint8_t *d_in, uint32_t n, const uint64
     if (st[i]) {
       if (bad_member) *bad_member = i;
       if (err_off) *err_off = (int64_t)moff[i];
+      if (bad) *bad = MembersBad{i, moff[i], ooff[i], i ? moff[i - 1] : 0ull};
       return st[i];
     }
   return FLATE_HIP_OK;
 }
 
 }  // namespace
+
+// flate_hip_bgzf_reader_*: the file's state between two calls (bgzf_parts_rule.h), host words only
+struct flate_hip_bgzf_reader {
+  flate_hip_ctx *ctx = nullptr;
+  uint32_t flags = 0;
+  flate::BgzfPartsState s = flate::bgzf_parts_fresh();
+};
 
 // flate_ctx.h
 int flate_host::ranges_gather(flate_hip_ctx *c, const uint8_t *scratch, uint8_t *d_out, const uint64_t *r_out_off,
@@ -788,6 +816,113 @@ int flate_hip_bgzf_read(flate_hip_ctx *c, const uint8_t *in, uint64_t in_len, ui
     *out_len = H.out_bytes;
     if (H.out_bytes > out_cap) return FLATE_HIP_E_OUT_TOO_SMALL;
     return members_read(c, d_in, n, P.C.member_off, P.C.out_off, H.out_bytes, out, flags, bad_member, err_off);
+  } catch (const std::exception &e) {  // (out of host memory in an index vector)
+    c->hip_err = e.what();
+    return FLATE_HIP_E_INTERNAL;
+  }
+}
+
+// ---- a BGZF file read in PARTS (bgzf_parts_rule.h, bgzf_parts_kernels.hip) ----
+// The handle is a few host words: nothing of it lives on the device or in the ctx's scratch, so any other call on the
+// ctx may run between two reads.
+int flate_hip_bgzf_reader_open(flate_hip_ctx *c, uint32_t flags, flate_hip_bgzf_reader **out) {
+  // every check before any HIP call (there is none)
+  if (bgzf_reader_open_args(c, flags, out)) return FLATE_HIP_E_INVALID;
+  flate_hip_bgzf_reader *r = new (std::nothrow) flate_hip_bgzf_reader();
+  if (!r) return FLATE_HIP_E_INTERNAL;
+  r->ctx = c, r->flags = flags;
+  *out = r;
+  return FLATE_HIP_OK;
+}
+
+int flate_hip_bgzf_reader_reset(flate_hip_bgzf_reader *r) {
+  if (!r) return FLATE_HIP_E_INVALID;
+  r->s = bgzf_parts_fresh();
+  return FLATE_HIP_OK;
+}
+
+void flate_hip_bgzf_reader_free(flate_hip_bgzf_reader *r) { delete r; }
+
+// One call: flate_hip_bgzf_read on the part in[0, in_len) -- the discovery with the part's finish and out-scan kernels
+// (the stop behind the last whole member, the clip to out_cap and index_cap, the index in FILE coordinates), the words
+// and the delivered members' index back, bgzf_parts_call, then members_read over the delivered members.
+int flate_hip_bgzf_reader_read(flate_hip_bgzf_reader *r, const uint8_t *in, uint64_t in_len, int final_in, uint8_t *out,
+                               uint64_t out_cap, uint64_t *in_used, uint64_t *out_len, uint64_t index_cap,
+                               uint64_t *member_off, uint64_t *out_off, uint32_t *n_members, uint32_t *bad_member,
+                               int64_t *err_off, int *eof_marker) {
+  // every check before any HIP call
+  if (bgzf_reader_read_args(r, in, in_len, out, out_cap, in_used, out_len, index_cap, member_off, out_off))
+    return FLATE_HIP_E_INVALID;
+  *in_used = 0, *out_len = 0;
+  if (n_members) *n_members = 0;
+  BgzfPartsState &s = r->s;
+  if (member_off) member_off[0] = s.consumed, out_off[0] = s.produced;  // (a call that delivers nothing: where the file stands)
+  auto words = [&]() {
+    const bool bad = s.status < 0;
+    if (bad_member) *bad_member = bad ? s.bad_member : 0xffffffffu;
+    if (err_off) *err_off = bad ? s.err_off : -1;
+    if (eof_marker) *eof_marker = (int)s.eof_marker;
+  };
+  words();
+  if (s.status) return s.status;  // sticky: the file's end, or its error
+  flate_hip_ctx *c = r->ctx;
+  c->hip_err.clear();
+  const bool fin = final_in != 0;
+  if (in_len == 0) {
+    if (!fin) return FLATE_HIP_OK;
+    s.status = FLATE_HIP_STREAM_END;  // the file ends at a member's end (an empty file: at its start)
+    return FLATE_HIP_STREAM_END;
+  }
+  try {
+    int rc;
+    const uint8_t *d_in = nullptr;
+    if ((rc = stage_input(c, in, in_len, r->flags, &d_in))) return rc;
+    BgzfHead H{};
+    BgzfParams P{};
+    BgzfPartParams Q{};
+    BgzfPartFound F{};
+    Q.out_cap = out_cap;
+    Q.base_in = s.consumed, Q.base_out = s.produced;
+    Q.k_max = bgzf_part_k_max(member_off != nullptr, index_cap);
+    Q.final_in = fin ? 1u : 0u;
+    if ((rc = bgzf_discover(c, d_in, in_len, H, P, &Q, &F))) return rc;
+    if (F.k > F.n || F.in_end > in_len || F.out_end > out_cap) {
+      c->hip_err = "BGZF reader: the part's result words do not fit the part";
+      return FLATE_HIP_E_INTERNAL;
+    }
+    BgzfPartCall call = bgzf_parts_call(s, F, in_len, fin);
+    if (call.status == FLATE_HIP_E_OUT_TOO_SMALL) {  // (not sticky: the state is unchanged)
+      *out_len = call.out_len;
+      return FLATE_HIP_E_OUT_TOO_SMALL;
+    }
+    if (member_off) {  // the delivered members' index, in FILE coordinates
+      const size_t bytes = ((size_t)F.k + 1) * 8;
+      HIP_TRY(c, hipMemcpyAsync(member_off, Q.idx_member_off, bytes, hipMemcpyDeviceToHost, c->stream));
+      HIP_TRY(c, hipMemcpyAsync(out_off, Q.idx_out_off, bytes, hipMemcpyDeviceToHost, c->stream));
+      HIP_TRY(c, hipStreamSynchronize(c->stream));
+    }
+    uint32_t delivered = call.decode;
+    if (call.decode) {
+      MembersBad bad;
+      rc = members_read(c, d_in, call.decode, P.C.member_off, P.C.out_off, F.out_end, out, r->flags, nullptr, nullptr, &bad);
+      if (rc && bad.j == 0xffffffffu) return rc;  // the call's own failure: nothing is committed
+      if (rc) {  // member bad.j: the members in front of it are delivered, the file's error is sticky
+        bool eof_before = false;
+        if (bad.j && bad.member_off - bad.prev_off == kBgzfEofLen) {
+          uint8_t m[kBgzfEofLen];
+          HIP_TRY(c, hipMemcpyAsync(m, d_in + bad.prev_off, kBgzfEofLen, hipMemcpyDeviceToHost, c->stream));
+          HIP_TRY(c, hipStreamSynchronize(c->stream));
+          eof_before = bgzf_is_eof_marker(m, kBgzfEofLen);
+        }
+        bgzf_parts_fail(s, call, bad.j, rc, bad.member_off, bad.out_off, eof_before);
+        delivered = bad.j;
+      }
+    }
+    s = call.next;
+    *in_used = call.in_used, *out_len = call.out_len;
+    if (n_members) *n_members = delivered;
+    words();
+    return call.status;
   } catch (const std::exception &e) {  // (out of host memory in an index vector)
     c->hip_err = e.what();
     return FLATE_HIP_E_INTERNAL;

@@ -1,6 +1,7 @@
 // flate_kernels.h -- kernel parameter blocks and launch entry points (internal).
 #pragma once
 
+#include "bgzf_parts_rule.h"
 #include "chain_rule.h"
 #include "flate_common.h"
 #include "flate_hip.h"
@@ -13,14 +14,18 @@ namespace flate {
 // kWrapBgzf: the members of a BGZF file (flate_hip_bgzf_write) -- gzip members with the 18-byte header that carries
 // BSIZE, followed by the 28-byte EOF marker.  INTERNAL: the public *_framed calls refuse every wrap above _GZIP.
 constexpr uint32_t kWrapBgzf = 3u;
+// kWrapBgzfOpen: the same members WITHOUT the marker -- a part of a file that goes on (flate_hip_bgzf_writer_write, a
+// call that is not final).  It differs from kWrapBgzf in nothing else.
+constexpr uint32_t kWrapBgzfOpen = 4u;
+FLATE_HD bool frame_is_bgzf(uint32_t wrap) { return wrap == kWrapBgzf || wrap == kWrapBgzfOpen; }
 FLATE_HD uint32_t frame_header_len(uint32_t wrap, bool with_dict) {
-  return wrap == kWrapBgzf ? 18u : wrap == FLATE_HIP_WRAP_GZIP ? 10u : (with_dict ? 6u : 2u);
+  return frame_is_bgzf(wrap) ? 18u : wrap == FLATE_HIP_WRAP_GZIP ? 10u : (with_dict ? 6u : 2u);
 }
-FLATE_HD uint32_t frame_trailer_len(uint32_t wrap) { return (wrap == FLATE_HIP_WRAP_GZIP || wrap == kWrapBgzf) ? 8u : 4u; }
+FLATE_HD uint32_t frame_trailer_len(uint32_t wrap) { return (wrap == FLATE_HIP_WRAP_GZIP || frame_is_bgzf(wrap)) ? 8u : 4u; }
 // the shortest member: the header without a dictionary, nothing, the trailer
 FLATE_HD uint32_t frame_min_len(uint32_t wrap) { return frame_header_len(wrap, false) + frame_trailer_len(wrap); }
 FLATE_HD uint32_t frame_sum_kind(uint32_t wrap) {
-  return (wrap == FLATE_HIP_WRAP_GZIP || wrap == kWrapBgzf) ? (uint32_t)FLATE_HIP_CHECKSUM_CRC32
+  return (wrap == FLATE_HIP_WRAP_GZIP || frame_is_bgzf(wrap)) ? (uint32_t)FLATE_HIP_CHECKSUM_CRC32
                                                             : (uint32_t)FLATE_HIP_CHECKSUM_ADLER32;
 }
 
@@ -452,6 +457,23 @@ __global__ void bgzf_fill_kernel(BgzfParams P);
 __global__ void bgzf_link_kernel(BgzfParams P);
 __global__ void bgzf_finish_kernel(BgzfParams P);
 __global__ void bgzf_out_scan_kernel(BgzfParams P);
+
+// A PART of a BGZF file (bgzf_parts_kernels.hip; flate_hip_bgzf_reader_read): the count, scan, fill, link and round
+// kernels above over the part, then the part's own finish (THE PART STOP of bgzf_parts_rule.h where the chain's
+// successor is the dead node) and out-scan (the ISIZE scan, DELIVERY, the result words, the FILE-absolute index).
+struct BgzfPartParams {
+  BgzfParams B;
+  BgzfPartFound *found;      // the result words, read back as one block
+  uint64_t out_cap;
+  uint64_t base_in;          // the part's file offset ...
+  uint64_t base_out;         // ... and the output bytes in front of it
+  uint64_t *idx_member_off;  // cap + 1: base_in + member_off
+  uint64_t *idx_out_off;     // cap + 1: base_out + out_off
+  uint32_t k_max;            // bgzf_part_k_max
+  uint32_t final_in;
+};
+__global__ void bgzf_part_finish_kernel(BgzfPartParams Q);
+__global__ void bgzf_part_out_scan_kernel(BgzfPartParams Q);
 
 // BGZF random access (bgzf_range_kernels.hip; flate_hip_bgzf_read_ranges): behind the discovery kernels, on the index
 // where they left it.  Locate: one thread per range (bgzf_range_rule.h) -- b, length, status, the first and the last

@@ -58,7 +58,7 @@ __global__ __launch_bounds__(1024) void frame_scan_kernel(FrameParams P) {
       P.n_streams, wtot,
       [&](uint32_t i) {
         const uint64_t v = P.out_len[i] + header_len(P, i) + tl;
-        if (P.wrap == kWrapBgzf && v > (uint64_t)kBgzfMemberMax) atomicMin(&big_s, i);
+        if (frame_is_bgzf(P.wrap) && v > (uint64_t)kBgzfMemberMax) atomicMin(&big_s, i);
         return v;
       },
       [&](uint32_t i, uint64_t at, uint64_t) {
@@ -68,7 +68,7 @@ __global__ __launch_bounds__(1024) void frame_scan_kernel(FrameParams P) {
   if (threadIdx.x == 0) {  // (behind the scan's barriers: big_s is final)
     P.member_off[P.n_streams] = sum;
     P.payload_off[P.n_streams] = sum;
-    // (a BGZF file ends with the EOF marker behind its last member)
+    // (a BGZF file ends with the EOF marker behind its last member; kWrapBgzfOpen: the file goes on)
     const uint64_t total = sum + (P.wrap == kWrapBgzf ? (uint64_t)kBgzfEofLen : 0ull);
     if (total > P.out_cap) *P.status = FLATE_HIP_E_OUT_TOO_SMALL;
     if (big_s != 0xffffffffu) {
@@ -96,7 +96,7 @@ __global__ __launch_bounds__(256) void frame_write_kernel(FrameParams P) {
   uint8_t *h = P.out + at;
   uint8_t *t = h + hl + raw;
   const uint32_t sum = P.sums[i];
-  if (P.wrap == kWrapBgzf) {
+  if (frame_is_bgzf(P.wrap)) {
     // htslib's header: FEXTRA, XLEN = 6, the subfield 'B' 'C' with BSIZE = the member's size - 1 (the scan has
     // refused the call if that does not fit 16 bits)
     const uint32_t bsize = (uint32_t)(hl + raw + trailer_len(P)) - 1u;

@@ -723,8 +723,25 @@ class OneWriterCalls:
         return OneWriter(self, wrap, piece_bytes, device, compat_go)
 
 
+class BgzfPartsCalls:
+    """A BGZF file read and written in parts: the methods FlateEngine inherits.  They stand in a class of their own so
+    that their marshalling has its own recorded scenarios (tests/engine_trace_bgzf_parts.py) beside the ones of the
+    methods that were there before (tests/engine_trace.py)."""
+
+    def open_bgzf_reader(self, device=False):
+        """A BGZF file read in parts through bounded buffers at bgzf_read's speed (flate_hip_bgzf_reader_*): see
+        BgzfReader.  device: every part and every output is a torch CUDA tensor."""
+        return BgzfReader(self, device)
+
+    def open_bgzf_writer(self, block_bytes=0, device=False, compat_go=False):
+        """A BGZF file written in parts through bounded buffers at bgzf_write's speed (flate_hip_bgzf_writer_*): see
+        BgzfWriter.  block_bytes: as bgzf_write's (0: 65280).  device: every part and every output is a torch CUDA
+        tensor."""
+        return BgzfWriter(self, block_bytes, device, compat_go)
+
+
 class FlateEngine(OneSeekCalls, SeekPackCalls, GzFileCalls, GzFileSerialCalls, GzFileSeekCalls, ZipUnitsCalls, GroupedCalls, OnePartsCalls,
-                  OneWriterCalls, GzFilePartsCalls):
+                  OneWriterCalls, GzFilePartsCalls, BgzfPartsCalls):
     """One engine = one flate_hip_ctx = one GPU + one HIP stream."""
 
     def __init__(self, device=0):
@@ -1695,6 +1712,135 @@ class OneWriter:
     def close(self):
         if self._h:
             self._L.flate_hip_one_writer_free(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+BgzfPartRead = collections.namedtuple("BgzfPartRead", "rc out_len n_members bad_member err_off eof_marker member_off out_off")
+
+
+class BgzfReader:
+    """bgzf_read on a file the caller holds a part at a time (flate_hip_bgzf_reader_*): every read() decodes the members
+    that lie whole inside the part and fit the room, and the handle carries where the file stands (a few host words:
+    any other call of the engine may run between two reads).  read(part, final, out, out_cap, index) -> (in_used, out,
+    BgzfPartRead(rc, out_len, n_members, bad_member, err_off, eof_marker, member_off, out_off)): `part` BEGINS with the
+    bytes the last read left unused (a member the part cuts is left unused); the bytes are out[:out_len]; rc 0 = go on,
+    1 = the end of the file, -2 with bad_member 0xffffffff = not even the first member fits (out_len: its size; nothing
+    changed), anything else below 0 = the file's error, sticky, behind the good members in front of it, with bad_member
+    and err_off counted over the FILE.  A part of at least 65536 bytes, or a final one, always makes progress or gives
+    a verdict.  index: False, True (room for every member the part can hold) or a number of entries; member_off and
+    out_off then hold the n_members + 1 FILE offsets of the delivered members, compressed and uncompressed, and a
+    smaller room clips the read as out_cap does; else None.  out=None behaves as OneReader's."""
+
+    def __init__(self, eng, device=False):
+        self._eng, self._L = eng, eng._L
+        self._device = bool(device)
+        self._h = C.c_void_p()
+        eng._check(self._L.flate_hip_bgzf_reader_open(eng._ctx, eng._flags(False, False, self._device), C.byref(self._h)))
+
+    def read(self, part, final=False, out=None, out_cap=None, index=False):
+        part, in_ptr, n, device = _in_buf(part, accept_bytes=True, null_if_empty=True)
+        if device != self._device:
+            raise FlateError(E_INVALID, "BgzfReader.read: the part is not on the side the reader was opened for")
+        used, ol = C.c_uint64(0), C.c_uint64(0)
+        nm, bm, eo, em = C.c_uint32(0), C.c_uint32(0xffffffff), C.c_int64(-1), C.c_int(0)
+        with_index = index is not False and index is not None
+        index_cap = (n // 28 + 2) if index is True else int(index) if with_index else 0
+        moff = np.zeros(max(index_cap, 1), dtype=np.uint64) if with_index else None
+        ooff = np.zeros(max(index_cap, 1), dtype=np.uint64) if with_index else None
+
+        def call(out_ptr, cap):
+            rc = self._eng._tolerate(self._L.flate_hip_bgzf_reader_read(
+                self._h, in_ptr, n, 1 if final else 0, out_ptr, cap, C.byref(used), C.byref(ol), index_cap,
+                moff.ctypes.data if with_index else None, ooff.ctypes.data if with_index else None, C.byref(nm),
+                C.byref(bm), C.byref(eo), C.byref(em)), 1, E_UNSUPPORTED, *PER_CHAIN)  # (1: the end of the file)
+            k = int(nm.value)
+            return BgzfPartRead(rc, int(ol.value), k, int(bm.value), int(eo.value), int(em.value),
+                                moff[:k + 1].copy() if with_index else None, ooff[:k + 1].copy() if with_index else None)
+
+        size = max(4 * n, 1 << 16) if out_cap is None else int(out_cap)
+        buf, ptr, cap = _out_buf(out, part, size, out_cap, 0, "BgzfReader.read", floor=1)
+        res = call(ptr, cap)
+        if res.rc == E_OUT_TOO_SMALL and res.bad_member == 0xffffffff and out is None and out_cap is None:
+            buf, ptr, cap = _out_buf(None, part, res.out_len, None, 0, "BgzfReader.read", floor=1)
+            res = call(ptr, cap)
+        repeatable = res.rc == E_OUT_TOO_SMALL and res.bad_member == 0xffffffff
+        return int(used.value), (buf[:0] if repeatable else buf[:res.out_len]), res
+
+    def reset(self):
+        """A fresh file on the same handle: same side."""
+        self._eng._check(self._L.flate_hip_bgzf_reader_reset(self._h))
+
+    def close(self):
+        if self._h:
+            self._L.flate_hip_bgzf_reader_free(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+BgzfPartWrite = collections.namedtuple("BgzfPartWrite", "rc out_len n_blocks member_off")
+
+
+def bgzf_writer_bound(in_len, block_bytes=0):
+    """Room that holds any BgzfWriter.write of at most in_len bytes (flate_hip_bgzf_writer_bound; 0: block_bytes is
+    refused)."""
+    return int(_lib.load().flate_hip_bgzf_writer_bound(int(in_len), int(block_bytes)))
+
+
+class BgzfWriter:
+    """bgzf_write for an input the caller holds a part at a time (flate_hip_bgzf_writer_*): every write() compresses
+    the whole blocks of block_bytes bytes that the part holds, and only the final one ends with the EOF marker.  The
+    concatenation of what the writes return is, byte for byte, bgzf_write of the whole input, whatever the parts.
+    write(part, final, out, out_cap, index) -> (in_used, out, BgzfPartWrite(rc, out_len, n_blocks, member_off)): `part`
+    BEGINS with the bytes the last write left unused; the bytes are out[:out_len]; rc 0 = go on, 1 = the file is
+    finished, -2 = out_cap is too small, -6 = a block that 65536 bytes cannot express (both: nothing changed).
+    index=True: member_off holds the n_blocks + 1 FILE offsets of the members written and of what follows them (the
+    next member, or the marker); else None.  out=None: room for bgzf_writer_bound of the part."""
+
+    def __init__(self, eng, block_bytes=0, device=False, compat_go=False):
+        self._eng, self._L = eng, eng._L
+        self._device = bool(device)
+        self.block_bytes = int(block_bytes) or BGZF_BLOCK_DEFAULT
+        self._bb = int(block_bytes)
+        self._h = C.c_void_p()
+        eng._check(self._L.flate_hip_bgzf_writer_open(eng._ctx, int(block_bytes), eng._flags(compat_go, False, self._device),
+                                                      C.byref(self._h)))
+
+    def write(self, part, final=False, out=None, out_cap=None, index=False):
+        if part is None and self._device:
+            import torch
+            part = torch.empty(0, dtype=torch.uint8, device="cuda:%d" % self._eng.device)
+        part, in_ptr, n, device = _in_buf(b"" if part is None else part, accept_bytes=True, null_if_empty=True)
+        if device != self._device:
+            raise FlateError(E_INVALID, "BgzfWriter.write: the part is not on the side the writer was opened for")
+        used, ol, nb = C.c_uint64(0), C.c_uint64(0), C.c_uint32(0)
+        member_off = np.zeros(n // self.block_bytes + 2, dtype=np.uint64)
+        size = bgzf_writer_bound(n, self._bb) if out_cap is None else int(out_cap)
+        buf, ptr, cap = _out_buf(out, part, size, out_cap, 0, "BgzfWriter.write", floor=1)
+        rc = self._eng._tolerate(self._L.flate_hip_bgzf_writer_write(
+            self._h, in_ptr, n, 1 if final else 0, ptr, cap, C.byref(used), C.byref(ol),
+            member_off.ctypes.data if index else None, C.byref(nb)), 1, E_OUT_TOO_SMALL, E_TOO_LARGE)  # (1: finished)
+        k = int(nb.value)
+        res = BgzfPartWrite(rc, int(ol.value), k, member_off[:k + 1] if index and rc >= 0 else None)
+        return int(used.value), buf[:res.out_len], res
+
+    def reset(self):
+        """A fresh file on the same handle: same block size, same side, same flags."""
+        self._eng._check(self._L.flate_hip_bgzf_writer_reset(self._h))
+
+    def close(self):
+        if self._h:
+            self._L.flate_hip_bgzf_writer_free(self._h)
             self._h = C.c_void_p()
 
     def __del__(self):

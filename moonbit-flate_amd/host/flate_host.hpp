@@ -1220,6 +1220,224 @@ class OneWriter {
   Err err_;
 };
 
+// The same Reader over a BGZF file at flate_hip_bgzf_read's speed (flate_hip_bgzf_reader_*): every step decodes, in
+// parallel, the members that lie whole inside the input piece and fit the output piece; the handle is a few host words.
+// The pieces and the loop are GzFileReader's; the input piece never has to grow beyond 65536 bytes, the output piece
+// grows to a first member that does not fit.  Bytes and errors come out as Reader's: data first -- the good members in
+// front of a failure --, the error (ioeof at the file's end) with the last bytes; a corrupt file reports the FILE
+// offset, and failure() holds the other word.
+class BgzfReader {
+ public:
+  struct Failure {
+    uint32_t bad_member = 0xffffffffu;
+    int64_t err_off = -1;
+  };
+  BgzfReader(ByteSource &r, Engine &e, size_t in_piece = 1u << 24, size_t out_piece = 1u << 26)
+      : r_(&r), e_(e), in_piece_(in_piece < FLATE_HIP_BGZF_MEMBER_MAX ? FLATE_HIP_BGZF_MEMBER_MAX : in_piece),
+        out_piece_(out_piece < 1 ? 1 : out_piece) {}
+  ~BgzfReader() { flate_hip_bgzf_reader_free(h_); }
+  BgzfReader(const BgzfReader &) = delete;
+  BgzfReader &operator=(const BgzfReader &) = delete;
+
+  // a fresh file from `r` on the same handle
+  void reset(ByteSource &r) {
+    r_ = &r;
+    fresh_ = true;
+    in_.clear();
+    src_end_ = false;
+    len_ = 0;
+    pos_ = 0;
+    members_ = 0;
+    eof_marker_ = false;
+    fail_ = Failure();
+    err_ = std::nullopt;
+  }
+
+  std::pair<int, Err> read(uint8_t *p, size_t n) {
+    for (;;) {
+      if (pos_ < len_) {
+        const size_t k = std::min(n, len_ - pos_);
+        std::copy(data_.begin() + pos_, data_.begin() + pos_ + k, p);
+        pos_ += k;
+        if (pos_ == len_) return {(int)k, err_};
+        return {(int)k, std::nullopt};
+      }
+      if (err_) return {0, err_};
+      step();
+    }
+  }
+  Err close() {
+    if (err_ && *err_ == ioeof()) return std::nullopt;
+    return err_;
+  }
+  size_t resident_bytes() const { return in_.capacity() + data_.capacity(); }
+  uint64_t calls() const { return calls_; }
+  uint64_t members() const { return members_; }   // members delivered so far
+  bool eof_marker() const { return eof_marker_; }  // the last of them is the canonical marker
+  const Failure &failure() const { return fail_; }
+
+ private:
+  void step() {
+    if (!e_.ok()) {
+      err_ = make_error(e_, e_.status());
+      return;
+    }
+    if (!h_) {
+      const int rc = flate_hip_bgzf_reader_open(e_.ctx(), 0, &h_);
+      if (rc != 0) {
+        err_ = make_error(e_, rc);
+        return;
+      }
+      fresh_ = false;
+    }
+    if (fresh_) {
+      (void)flate_hip_bgzf_reader_reset(h_);
+      fresh_ = false;
+    }
+    bool stalled = false;  // the source gave no byte and no error: decode what is here, do not ask again in this step
+    while (!src_end_ && !stalled && in_.size() < in_piece_) {
+      const size_t at = in_.size();
+      in_.resize(in_piece_);
+      auto r = r_->read(in_.data() + at, in_piece_ - at);
+      in_.resize(at + (size_t)r.first);
+      if (r.second) {
+        if (!(*r.second == ioeof())) {
+          err_ = r.second;
+          return;
+        }
+        src_end_ = true;
+      }
+      stalled = r.first == 0 && !r.second;
+    }
+    if (data_.size() < out_piece_) data_.resize(out_piece_);  // (the piece is filled once, not per step)
+    pos_ = 0;
+    len_ = 0;
+    uint64_t used = 0, got = 0;
+    uint32_t members = 0;
+    int marker = 0;
+    Failure f;
+    ++calls_;
+    const int rc = flate_hip_bgzf_reader_read(h_, in_.data(), in_.size(), src_end_ ? 1 : 0, data_.data(), out_piece_, &used,
+                                              &got, 0, nullptr, nullptr, &members, &f.bad_member, &f.err_off, &marker);
+    if (rc == FLATE_HIP_E_OUT_TOO_SMALL && f.bad_member == 0xffffffffu) {  // not even the first member fits: room for it
+      out_piece_ = (size_t)got;
+      return;
+    }
+    len_ = (size_t)got;
+    members_ += members;
+    eof_marker_ = marker != 0;
+    in_.erase(in_.begin(), in_.begin() + (size_t)used);
+    if (rc < 0) fail_ = f;
+    if (rc == FLATE_HIP_STREAM_END) err_ = ioeof();
+    else if (rc == FLATE_HIP_E_CORRUPT) err_ = corrupt_input_error(f.err_off);
+    else if (rc == FLATE_HIP_E_UNEXPECTED_EOF) err_ = err_unexpected_eof();
+    else if (rc != 0) err_ = make_error(e_, rc);
+    else if (members == 0 && used == 0) {
+      // (a part of 65536 bytes or a final one always makes progress or gives a verdict: only a short part gets here)
+      if (src_end_) err_ = make_error(e_, FLATE_HIP_E_INTERNAL);
+      else if (stalled) err_ = IOError{"flate_host::BgzfReader: the source delivers neither bytes nor an error"};
+    }
+  }
+  ByteSource *r_;
+  Engine &e_;
+  size_t in_piece_, out_piece_;
+  flate_hip_bgzf_reader *h_ = nullptr;
+  bool fresh_ = false;
+  std::vector<uint8_t> in_;
+  bool src_end_ = false;
+  std::vector<uint8_t> data_;  // the output piece; its first len_ bytes are decoded and not all handed out yet
+  size_t len_ = 0, pos_ = 0;
+  uint64_t calls_ = 0, members_ = 0;
+  bool eof_marker_ = false;
+  Failure fail_;
+  Err err_;
+};
+
+// A Writer (write, close) over a BGZF file at flate_hip_bgzf_write's speed (flate_hip_bgzf_writer_*): write() stages
+// the bytes and, once part_bytes of them are there, hands the whole blocks to the GPU and their members to the sink; the
+// remainder below a block stays staged on the host.  close() sends the final call: the last, shorter block and the EOF
+// marker.  The sink sees the bytes of compress_bgzf, whatever the sizes of the writes.  Sticky errors as Writer's.
+class BgzfWriter {
+ public:
+  BgzfWriter(ByteSink &w, Engine &e, uint32_t block_bytes = 0, uint32_t flags = 0, size_t part_bytes = 1u << 26)
+      : w_(&w), e_(e), block_(block_bytes), flags_(flags & ~FLATE_HIP_DEVICE_PTRS) {
+    const size_t bb = block_bytes ? block_bytes : FLATE_HIP_BGZF_BLOCK_DEFAULT;
+    part_ = part_bytes < bb ? bb : part_bytes;
+  }
+  ~BgzfWriter() { flate_hip_bgzf_writer_free(h_); }
+  BgzfWriter(const BgzfWriter &) = delete;
+  BgzfWriter &operator=(const BgzfWriter &) = delete;
+
+  std::pair<int, Err> write(const uint8_t *p, size_t n) {
+    if (err_) return {0, err_};
+    pending_.insert(pending_.end(), p, p + n);
+    if (pending_.size() >= part_) {
+      if (Err er = feed(false)) {
+        err_ = er;
+        return {0, err_};
+      }
+    }
+    return {(int)n, std::nullopt};
+  }
+  std::pair<int, Err> write(const std::vector<uint8_t> &b) { return write(b.data(), b.size()); }
+
+  Err close() {
+    if (err_ && *err_ == writer_closed_error()) return std::nullopt;
+    if (err_) return err_;
+    if (Err er = feed(true)) {
+      err_ = er;
+      return err_;
+    }
+    err_ = writer_closed_error();
+    return std::nullopt;
+  }
+  // a fresh file into `w` on the same handle: same block size, same flags (what is staged is dropped)
+  Err reset(ByteSink &w) {
+    w_ = &w;
+    pending_.clear();
+    err_ = std::nullopt;
+    emitted_ = 0;
+    if (h_) (void)flate_hip_bgzf_writer_reset(h_);
+    return err_;
+  }
+  // compressed bytes handed to the sink so far, the calls made, the members written (the marker not counted)
+  uint64_t emitted() const { return emitted_; }
+  uint64_t calls() const { return calls_; }
+  uint64_t blocks() const { return blocks_; }
+  size_t resident_bytes() const { return pending_.capacity() + out_.capacity(); }
+
+ private:
+  Err feed(bool final) {
+    if (!e_.ok()) return make_error(e_, e_.status());
+    if (!h_) {
+      const int rc = flate_hip_bgzf_writer_open(e_.ctx(), block_, flags_, &h_);
+      if (rc != 0) return make_error(e_, rc);
+    }
+    const size_t room = flate_hip_bgzf_writer_bound(pending_.size(), block_);
+    if (out_.size() < room) out_.resize(room);
+    uint64_t used = 0, len = 0;
+    uint32_t k = 0;
+    ++calls_;
+    const int rc = flate_hip_bgzf_writer_write(h_, pending_.data(), pending_.size(), final ? 1 : 0, out_.data(), out_.size(),
+                                               &used, &len, nullptr, &k);
+    if (rc != FLATE_HIP_OK && rc != FLATE_HIP_STREAM_END) return make_error(e_, rc);
+    pending_.erase(pending_.begin(), pending_.begin() + (size_t)used);
+    emitted_ += len;
+    blocks_ += k;
+    if (!len) return std::nullopt;
+    auto r = w_->write(out_.data(), (size_t)len);
+    return r.second;
+  }
+  ByteSink *w_;
+  Engine &e_;
+  uint32_t block_, flags_;
+  size_t part_;
+  flate_hip_bgzf_writer *h_ = nullptr;
+  uint64_t emitted_ = 0, calls_ = 0, blocks_ = 0;
+  std::vector<uint8_t> pending_, out_;
+  Err err_;
+};
+
 // One spliced stream decoded in parallel from its index (flate_hip_inflate_spliced).
 inline Err decompress_spliced(Engine &e, const std::vector<uint8_t> &stream, const std::vector<uint64_t> &bit_off,
                               const std::vector<uint64_t> &sizes, std::vector<uint8_t> &out) {
